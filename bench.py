@@ -2,10 +2,21 @@
 """bench.py — the hot path measured as BASELINE.json asks: Mrays/s (+ ms/frame) of progressive path tracing, dragon-class
 scene (Scene D: 100 352-triangle mesh + floor disc), 1920x1080, path depth 8, 1 path per pixel per pass, on N GPUs of one node.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
         N > 1: one process per GPU. Started by `python -m torch.distributed.run ... bench.py --gpus N ...` the ranks are
         taken from the environment; started plainly, bench.py starts that launcher itself (before anything touches a GPU)
         and relays rank 0's line — it never reports n_gpus != the ranks that rendered.
+
+A plain run does only what the headline needs: scene setup, the untimed mode-4 replay that counts `value`'s rays (it renders the
+K passes once more, at ~2.5x the time of a timed pass), warm-up, EXACTLY K timed passes (one repetition), the optional output
+dump and the line (metric, value, unit, higher_is_better, dtype, ms_per_step and the configuration). `--full` adds everything
+else, as before: the mode-1 replay (reference-defined counts), `--repeats` 5 by default, per-kernel HIP events, the frame checks
+(`frames_verified`, N > 1: `gather_verified`), one pass alone, the opt-in nearest-first walk, the rocprofv3 roofline child runs
+and the CPU baselines.
+`--dump-outputs DIR`: after the timed passes, the frame the last of them left (normalised radiance, the image a caller of the
+Renderer reads; rank 0's gathered frame for N > 1) is written as DIR/frame.npy (float32, H x W x 4); a frame above 64 MB is
+written as a fixed seeded sample of its pixels instead (DIR/frame_sample.npy + DIR/frame_sample_pixels.npy). Scenes and seeds
+are fixed, so two builds given the same arguments can be compared output for output.
 
 A "step" is one progressive pass (gpuart::Renderer::RenderPathTracingPass) over the whole frame. With N > 1 the FIXED frame
 is sharded by rows (8-row bands dealt round-robin, gpuart_hip_share_of_rank; strong scaling, north_star's "tile scaling");
@@ -18,7 +29,7 @@ What is counted:
     more — the fast mode renders bit-identical images but skips Sun-shadow queries that cannot matter and stops them at the
     first hit —: the reference-defined count (untimed mode-1 replay) over the same wall time is reported beside
     it as `mrays_reference_defined_per_s`, never as the headline.
-  * The K-pass timed sequence is run `--repeats` times (default 5), each bracketed by barrier + synchronize: `ms_per_step` is
+  * The K-pass timed sequence is run `--repeats` times (default 1; 5 with --full), each bracketed by barrier + synchronize: `ms_per_step` is
     the median repetition, `ms_per_step_spread` the fastest and slowest one.
   * `roofline`: device-level fractions, counters collected by rocprofv3 child runs of THIS invocation on the same passes and
     divided by ms_per_step (overlapping launches are never double counted). The traversal step of the BVH queries is balanced
@@ -83,16 +94,25 @@ def parse_args():
                     help="cfg3 (default, the configuration the metric is quoted on): Scene D, depth 8; cfg2 of BASELINE.json: Scene P, "
                          "depth 4; cluster / tree: the reference's two primitive-list scenes (InitCluster / InitTree) on seeded stand-ins; "
                          "dragon871k: cfg3's workload on a mesh of the real Stanford dragon's size (the tree leaves the L2s)")
-    ap.add_argument("--repeats", type=int, default=5, help="how many times the K-pass timed sequence is run (median reported, min/max beside it)")
-    ap.add_argument("--no-verify-gather", action="store_true", help="N > 1: skip the untimed check of the gathered frame against rank 0's own whole-frame render")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: reference-defined counts, repeated timed sequences, "
+                         "frame and gather checks, one pass alone, the nearest-first walk, the rocprofv3 roofline, the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame the timed passes computed (after the last one) to DIR/frame.npy, float32")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="how many times the K-pass timed sequence is run (median reported, min/max beside it); default 1, 5 with --full")
+    ap.add_argument("--no-verify-gather", action="store_true", help="N > 1, --full: skip the untimed check of the gathered frame against rank 0's own whole-frame render")
     ap.add_argument("--gather-timeout", type=float, default=120.0,
                     help="N > 1: seconds a rank waits for the frame gather before it names the ranks that have not arrived and exits non-zero")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true", help="skip the rocprofv3 child runs (roofline counters become null)")
-    ap.add_argument("--verify-gather", action="store_true", help="(kept for old command lines: the check is always made for N > 1 now)")
+    ap.add_argument("--verify-gather", action="store_true", help="(kept for old command lines: with --full the check is always made for N > 1 now)")
     ap.add_argument("--render-only", action="store_true",
                     help="(internal) render warm-up + steps passes of the workload and exit: the program the rocprofv3 child runs profile")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
 
 
 def spawn_ranks(args):
@@ -133,6 +153,25 @@ def run_passes(r, n):
     r.restart_path_tracing(1, n)
     for _ in range(n):
         r.path_tracing_pass()
+
+
+SHAPE_WARM_MAX = 512  # the untimed sequence of the timed shape before the warm-up: at most this many passes
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs writes at most this much
+
+
+def dump_frame(d, frame):
+    """--dump-outputs: the frame (H x W x 4 float32) as d/frame.npy; above DUMP_MAX_BYTES a fixed seeded sample of its pixels instead
+    (d/frame_sample.npy: n x 4, d/frame_sample_pixels.npy: their row-major pixel indices, float64)."""
+    os.makedirs(d, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(d, "frame.npy"), frame)
+        return
+    px = frame.reshape(-1, frame.shape[-1])
+    n = DUMP_MAX_BYTES // 2 // (px.itemsize * px.shape[1] + 8)
+    idx = np.sort(np.random.default_rng(5489).choice(px.shape[0], n, replace=False))
+    np.save(os.path.join(d, "frame_sample.npy"), px[idx])
+    np.save(os.path.join(d, "frame_sample_pixels.npy"), idx.astype(np.float64))
 
 
 PROFILE_REPEATS = 3  # the profiled children render the timed shape — K passes between two observations — this many times
@@ -268,7 +307,8 @@ def main():
         else:
             gather_note = "GPUART_BENCH_BACKEND=%s rehearsal: gathered through host memory" % backend
 
-    # ---- exact work counts: the same K passes, untimed; reference-defined (mode 1) and as the fast mode executes them (mode 4) ----
+    # ---- exact work counts: the same K passes, untimed; as the fast mode executes them (mode 4: `value`'s numerator) and, with
+    #      --full, reference-defined (mode 1) ----
     replay_frames = {}
 
     def count(mode):
@@ -278,16 +318,17 @@ def main():
         run_passes(r, K)
         be.finish()
         c = be.counters(reset=True)
-        replay_frames[mode] = r.read_radiance(False)  # this rank's accumulator after the K passes (frames_verified below)
+        if args.full:
+            replay_frames[mode] = r.read_radiance(False)  # this rank's accumulator after the K passes (frames_verified below)
         be.set_mode(0)
         return [c.rays, c.nodes, c.prim_tests[0], c.prim_tests[1], c.prim_tests[2], c.prim_tests[3], c.segments,
                 c.algorithmic_bytes() + 32 * W * th * K, c.rewalks, c.box_steps]
 
-    counts = torch.tensor(count(1) + count(4), dtype=torch.float64, device=xdev)
+    counts = torch.tensor((count(1) if args.full else []) + count(4), dtype=torch.float64, device=xdev)
     if dist is not None:
         dist.all_reduce(counts)
-    ref, exe = counts[:10].tolist(), counts[10:].tolist()
-    rays, nodes, segments, alg_bytes = ref[0], ref[1], ref[6], ref[7]
+    ref, exe = (counts[:10].tolist(), counts[10:].tolist()) if args.full else (None, counts.tolist())
+    rays, nodes, segments, alg_bytes = (ref[0], ref[1], ref[6], ref[7]) if args.full else (None, None, None, None)
 
     # ---- warm-up (untimed), then EXACTLY K timed passes ----
     full = torch.empty((H, W, 4), dtype=torch.float32, device=dev) if (world > 1 and rank == 0) else None
@@ -365,9 +406,11 @@ def main():
 
     # The first pass sequence of a given shape uses every pass lane for the first time (its stream, its path buffers, the kernel
     # variants of this scene): ~3 ms once, which a W-pass warm-up — it runs on two lanes — does not take off the K timed passes.
-    # One untimed sequence of the timed shape first, then the W warm-up passes the caller asked for.
+    # One untimed sequence of the timed shape first, then the W warm-up passes the caller asked for. Beyond SHAPE_WARM_MAX passes a
+    # sequence already uses every lane with runs of the length the timed one gets (run_planner.h plan(): at most 8 lanes x 64 passes
+    # at once), so a longer K is warmed by SHAPE_WARM_MAX of them.
     r.set_seed(5489)
-    run_passes(r, K)
+    run_passes(r, min(K, SHAPE_WARM_MAX))
     be.finish()
     r.set_seed(5489)
     run_passes(r, Wm)
@@ -390,7 +433,8 @@ def main():
             except B.HipError:
                 pass
             gather(float(max(1, Wm)))
-    be.set_timing(2)
+    if args.full:
+        be.set_timing(2)  # HIP events around every BVH-query kernel too (the roofline's per-launch figures)
     be.kernel_time(0, reset=True)
     be.kernel_time(1, reset=True)
     reps = []  # per repetition: (max over ranks of the wall time, this rank's render time, this rank's gather time)
@@ -422,19 +466,25 @@ def main():
     pass_ms, passes = be.kernel_time(0, reset=True)
     kernel_ms, launches = be.kernel_time(1, reset=True)
     be.set_timing(1)
+    # ---- what the last timed pass left: the normalised frame (rank 0's gathered one for N > 1), untimed ----
+    if args.dump_outputs and rank == 0:
+        dump_frame(args.dump_outputs, r.read_radiance(True) if world == 1 else full.cpu().numpy())
     # ---- the frames that were just timed, checked (untimed): the accumulator the LAST timed repetition left on this rank against the
     #      accumulator of the mode-1 replay of the same K passes — reference-order walks, every reference query performed, the kernels
     #      the oracle is held against in tests/ — bit for bit; the mode-4 replay (whose ray count is `value`'s numerator) likewise. A
     #      line whose timed kernels rendered something else is not a measurement: the run exits non-zero after printing it.
-    timed_frame = r.read_radiance(False)
-    bad = {m: int((timed_frame[..., :3].view(np.uint32) != f[..., :3].view(np.uint32)).any(-1).sum()) for m, f in replay_frames.items()}
-    rows_crc = int(np.bitwise_xor.reduce(timed_frame[..., :3].view(np.uint32).reshape(-1)))
-    frames_bad = torch.tensor([bad.get(1, -1), bad.get(4, -1)], dtype=torch.float64, device=xdev)
-    if dist is not None:
-        dist.all_reduce(frames_bad)
-    frames_bad = [int(x) for x in frames_bad.tolist()]
-    frames_verified = frames_bad == [0, 0]
-    del replay_frames, timed_frame
+    frames_verified = None
+    if args.full:
+        timed_frame = r.read_radiance(False)
+        bad = {m: int((timed_frame[..., :3].view(np.uint32) != f[..., :3].view(np.uint32)).any(-1).sum()) for m, f in replay_frames.items()}
+        rows_crc = int(np.bitwise_xor.reduce(timed_frame[..., :3].view(np.uint32).reshape(-1)))
+        frames_bad = torch.tensor([bad.get(1, -1), bad.get(4, -1)], dtype=torch.float64, device=xdev)
+        if dist is not None:
+            dist.all_reduce(frames_bad)
+        frames_bad = [int(x) for x in frames_bad.tolist()]
+        frames_verified = frames_bad == [0, 0]
+        del timed_frame
+    del replay_frames
     order = sorted(range(len(reps)), key=lambda k: reps[k][0])
     med = order[len(order) // 2]
     elapsed = reps[med][0]
@@ -474,7 +524,7 @@ def main():
                 os._exit(3)
             raise
 
-    verify = dist is not None and not args.no_verify_gather
+    verify = dist is not None and args.full and not args.no_verify_gather
     if dist is not None and gather_note is None and not verify:
         comm_destroy()  # every rank, while all of them are still alive
     if rank != 0:
@@ -507,7 +557,7 @@ def main():
 
     # ---- one pass alone, observed after it (the reference's interactive loop, src/main.cpp:549-599): frame time, not throughput ----
     single_ms = None
-    if world == 1:
+    if world == 1 and args.full:
         ts = []
         for _ in range(7):
             t1 = time.perf_counter()
@@ -519,7 +569,7 @@ def main():
     # ---- the opt-in nearest-child-first walk beside it (untimed for `value`): what exactness costs. The default walks every tree in the
     #      reference's order — the only order proven to return the reference's winner (csrc/hip/device_scene.h, tests/golden/order_adversary.npz)
     nearest = None
-    if world == 1:
+    if world == 1 and args.full:
         be.set_nearest_first(1024)
         ts = []
         for _ in range(max(3, len(reps))):
@@ -542,22 +592,24 @@ def main():
 
     # ---- roofline (gpuart_amd/bench_line.py): counters from rocprofv3 child runs of this invocation that render the timed shape ----
     ms_step = elapsed / K * 1e3
-    prof = trace = None
-    passes_profiled = 0
-    if world == 1 and not args.no_profile:
-        prof, trace, passes_profiled, source = profile_children(args, K)
-    else:
-        source = "not collected (%s)" % ("--no-profile" if args.no_profile else "N > 1: one GPU's counters would not describe the job")
-    roof = BL.assemble_roofline(ms_step, passes_profiled, prof, trace,
-                                executed={"nodes": exe[1] / K, "steps": exe[9] / K, "algorithmic_bytes": exe[7] / K},
-                                reference={"nodes": nodes / K, "algorithmic_bytes": alg_bytes / K},
-                                kernel_events=(kernel_ms, launches, elapsed_all), passes_timed=K * len(reps))
-    roof["source"] = source
-    roof["kernel_ms_summed_per_pass"] = round(kernel_ms / (K * len(reps)), 4)  # HIP events, all repetitions
+    roof = None
+    if args.full:
+        prof = trace = None
+        passes_profiled = 0
+        if world == 1 and not args.no_profile:
+            prof, trace, passes_profiled, source = profile_children(args, K)
+        else:
+            source = "not collected (%s)" % ("--no-profile" if args.no_profile else "N > 1: one GPU's counters would not describe the job")
+        roof = BL.assemble_roofline(ms_step, passes_profiled, prof, trace,
+                                    executed={"nodes": exe[1] / K, "steps": exe[9] / K, "algorithmic_bytes": exe[7] / K},
+                                    reference={"nodes": nodes / K, "algorithmic_bytes": alg_bytes / K},
+                                    kernel_events=(kernel_ms, launches, elapsed_all), passes_timed=K * len(reps))
+        roof["source"] = source
+        roof["kernel_ms_summed_per_pass"] = round(kernel_ms / (K * len(reps)), 4)  # HIP events, all repetitions
 
     # ---- CPU baseline: the oracle (port) on this box's host cores, bounded sample, rank 0, N=1 only ----
     cpu_baseline = None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import oracle as O
         cores = min(len(os.sched_getaffinity(0)), 16)  # the GPU box grants a 16-core CPU share per GPU
         otree, _ = O.build_bvh(scene_descs)
@@ -605,47 +657,51 @@ def main():
                    "gather": None if world == 1 else (gather_note or "gpuart_hip_gather (RCCL send/recv to rank 0 + row scatter), in the timed region"),
                    "bvh_nodes": info["nodes"], "bvh_primitives": info["prims"], "bvh_depth": info["max_depth"],
                    "scene_device_bytes": info["device_bytes"], "scene_setup_s": round(setup_s, 3)},
-        "warmup_note": "before the W warm-up passes: the untimed work-counting replays and one untimed K-pass sequence of the timed shape "
-                       "(first use of every pass lane costs ~3 ms once)",
+        "warmup_note": "before the W warm-up passes: the untimed work-counting replays and one untimed sequence of the timed shape, min(K, %d) "
+                       "passes (first use of every pass lane costs ~3 ms once)" % SHAPE_WARM_MAX,
         "ms_per_frame": round(ms_step, 4),
         "ms_per_frame_note": "throughput figure: wall time of the K passes / K, with up to 64 passes in flight between two observations",
-        "ms_per_frame_single": None if single_ms is None else round(single_ms, 4),
-        "ms_per_frame_single_note": "one pass submitted and observed alone (frame time of the reference's interactive loop), median of 5",
-        "nearest_first_opt_in": nearest,
         "mpaths_per_s": round(W * H * K / elapsed / 1e6, 3),
-        "rays_per_step": rays / K,
         "rays_executed_per_step": exe[0] / K,
         "mrays_executed_per_s": round(exe[0] / elapsed / 1e6, 3),
-        "mrays_reference_defined_per_s": round(rays / elapsed / 1e6, 3),
-        "mrays_reference_defined_note": "every closest-hit query the REFERENCE performs for these passes (mode-1 replay) over the same wall "
-                                        "time: what the images are worth in the reference's own work, not work this run performed",
-        "frames_verified": frames_verified,
-        "frames_verified_note": ("after the last timed repetition every rank's accumulator (its K timed passes) == the accumulator of the untimed mode-1 "
-                                 "replay (reference-order walks, every reference query) and of the mode-4 replay (the one that counts `value`'s rays) of "
-                                 "the same passes and seeds, bit for bit" if frames_verified else
-                                 "MISMATCH: %d pixels differ from the mode-1 replay, %d from the mode-4 replay (summed over ranks): this line is not a measurement" % tuple(frames_bad)),
-        "frames_xor_of_rank0_accumulator_bits": "%08x" % rows_crc,
         "multi_gpu": multi,
-        "nodes_per_step": nodes / K, "nodes_executed_per_step": exe[1] / K,
+        "nodes_executed_per_step": exe[1] / K,
         "rewalked_queries_per_step": exe[8] / K,
         "rewalked_queries_note": "closest-hit queries whose nearest-child-first walk could not certify its answer (a loose winner with a runner-up "
                                  "within the band, an odd box: device_scene.h) and that were walked again in the reference's order; their second walk "
                                  "is part of nodes_executed_per_step",
-        "segments_per_step": segments / K,
-        "algorithmic_bytes_per_ray": round(alg_bytes / rays, 1) if rays else None,
-        "roofline": roof,
-        "cpu_baseline": cpu_baseline,
-        "cpu_baseline_reference_glsl": None if glsl is None else {
-            "value": glsl["value"], "unit": "Mrays/s", "cores": 8, "kind": "reference", "ms_per_frame": glsl["ms_per_frame"],
-            "where": "BUILD CONTAINER (8 vCPU Xeon), not this box: the reference's unmodified GLSL on Mesa llvmpipe, same scene / camera / "
-                     "ray definition (tests/golden/time_llvmpipe.py; profiles/r02/llvmpipe_reference_glsl_container.txt, profiles/r03/llvmpipe_reference_glsl_container_871k.txt)"},
     }
+    if args.full:
+        out.update({
+            "ms_per_frame_single": None if single_ms is None else round(single_ms, 4),
+            "ms_per_frame_single_note": "one pass submitted and observed alone (frame time of the reference's interactive loop), median of 5",
+            "nearest_first_opt_in": nearest,
+            "rays_per_step": rays / K,
+            "mrays_reference_defined_per_s": round(rays / elapsed / 1e6, 3),
+            "mrays_reference_defined_note": "every closest-hit query the REFERENCE performs for these passes (mode-1 replay) over the same wall "
+                                            "time: what the images are worth in the reference's own work, not work this run performed",
+            "frames_verified": frames_verified,
+            "frames_verified_note": ("after the last timed repetition every rank's accumulator (its K timed passes) == the accumulator of the untimed mode-1 "
+                                     "replay (reference-order walks, every reference query) and of the mode-4 replay (the one that counts `value`'s rays) of "
+                                     "the same passes and seeds, bit for bit" if frames_verified else
+                                     "MISMATCH: %d pixels differ from the mode-1 replay, %d from the mode-4 replay (summed over ranks): this line is not a measurement" % tuple(frames_bad)),
+            "frames_xor_of_rank0_accumulator_bits": "%08x" % rows_crc,
+            "nodes_per_step": nodes / K,
+            "segments_per_step": segments / K,
+            "algorithmic_bytes_per_ray": round(alg_bytes / rays, 1) if rays else None,
+            "roofline": roof,
+            "cpu_baseline": cpu_baseline,
+            "cpu_baseline_reference_glsl": None if glsl is None else {
+                "value": glsl["value"], "unit": "Mrays/s", "cores": 8, "kind": "reference", "ms_per_frame": glsl["ms_per_frame"],
+                "where": "BUILD CONTAINER (8 vCPU Xeon), not this box: the reference's unmodified GLSL on Mesa llvmpipe, same scene / camera / "
+                         "ray definition (tests/golden/time_llvmpipe.py; profiles/r02/llvmpipe_reference_glsl_container.txt, profiles/r03/llvmpipe_reference_glsl_container_871k.txt)"},
+        })
     print(json.dumps(out), flush=True)
     r.close()
     shutil.rmtree(tmpdir, ignore_errors=True)
     if dist is not None:
         dist.destroy_process_group()
-    if not frames_verified:
+    if args.full and not frames_verified:
         sys.exit("bench.py: the timed frames differ from the replays' (frames_verified_note)")
     if gather_verified is False:
         sys.exit("bench.py: the gathered frame differs from rank 0's own whole-frame render (multi_gpu.gather_verified_note)")

@@ -184,6 +184,44 @@ def test_bench_py_uses_the_shared_definitions():
     assert BL.METRIC_VERSION == 4
 
 
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_plain_run_times_exactly_the_steps_and_full_keeps_the_repeats(monkeypatch):
+    bench = _bench_module()
+    monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "7", "--warmup", "2"])
+    a = bench.parse_args()
+    assert (a.steps, a.warmup, a.repeats, a.full, a.dump_outputs) == (7, 2, 1, False, None)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse_args()
+    assert (a.steps, a.repeats, a.full, a.dump_outputs) == (64, 5, True, "d")
+
+
+def test_dumped_outputs_are_float32_and_at_most_64_mb(tmp_path):
+    import numpy as np
+    bench = _bench_module()
+    frame = np.random.default_rng(0).random((1080, 1920, 4), dtype=np.float32)
+    bench.dump_frame(str(tmp_path / "p1080"), frame)
+    got = np.load(str(tmp_path / "p1080" / "frame.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, frame)
+    big = np.random.default_rng(1).random((2160, 3840, 4), dtype=np.float32)  # 133 MB: a fixed seeded sample of its pixels instead
+    for d in ("a", "b"):
+        bench.dump_frame(str(tmp_path / d), big)
+    files = sorted(os.listdir(str(tmp_path / "a")))
+    assert files == ["frame_sample.npy", "frame_sample_pixels.npy"]
+    assert sum(os.path.getsize(str(tmp_path / "a" / f)) for f in files) <= 64 << 20
+    px = np.load(str(tmp_path / "a" / "frame_sample_pixels.npy"))
+    sample = np.load(str(tmp_path / "a" / "frame_sample.npy"))
+    assert px.dtype == np.float64 and sample.dtype == np.float32
+    assert np.array_equal(sample, big.reshape(-1, 4)[px.astype(np.int64)])
+    assert np.array_equal(px, np.load(str(tmp_path / "b" / "frame_sample_pixels.npy")))  # the same pixels every run
+
+
 def _lines():
     out = []
     for rnd, names in (("r03", ["bench.json", "bench_driver_config.json", "bench_dragon871k.json", "bench_cfg2.json", "bench_4k.json"]),

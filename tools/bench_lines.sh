@@ -5,11 +5,11 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/$NAME
 mkdir -p $OUT
 cd $R
-timeout -k 10 400 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
-timeout -k 10 400 python3 bench.py --steps 20 --warmup 5 > $OUT/bench_driver_config.json 2> $OUT/bench_driver_config.err
-for w in cfg2 cluster tree dragon871k; do timeout -k 10 400 python3 bench.py --workload $w > $OUT/bench_$w.json 2> $OUT/bench_$w.err; done
-timeout -k 10 400 python3 bench.py --frame 3840x2160 --steps 16 --warmup 4 > $OUT/bench_4k.json 2> $OUT/bench_4k.err
-timeout -k 10 400 python3 bench.py --steps 1 --warmup 2 --no-cpu-baseline --no-profile > $OUT/bench_steps1.json 2> $OUT/bench_steps1.err
+timeout -k 10 400 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 400 python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver_config.json 2> $OUT/bench_driver_config.err
+for w in cfg2 cluster tree dragon871k; do timeout -k 10 400 python3 bench.py --full --workload $w > $OUT/bench_$w.json 2> $OUT/bench_$w.err; done
+timeout -k 10 400 python3 bench.py --full --frame 3840x2160 --steps 16 --warmup 4 > $OUT/bench_4k.json 2> $OUT/bench_4k.err
+timeout -k 10 400 python3 bench.py --full --steps 1 --warmup 2 --no-cpu-baseline --no-profile > $OUT/bench_steps1.json 2> $OUT/bench_steps1.err
 python3 - <<PY
 import json
 for f in ["bench", "bench_driver_config", "bench_cfg2", "bench_cluster", "bench_tree", "bench_dragon871k", "bench_4k", "bench_steps1"]:

@@ -8,16 +8,16 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # the kernel trace profiles the DRIVER's bench command (--steps 20 --warmup 5; minus its own rocprofv3 child runs and the CPU baseline),
 # so that its averages can be held against the HIP-event figures of the same process
-timeout -k 10 250 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o x -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-profile > $OUT/trace.log 2>&1
+timeout -k 10 250 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o x -- python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-profile > $OUT/trace.log 2>&1
 cd $R
 cp $OUT/trace/x_kernel_stats.csv $OUT/kernel_stats.csv
 python3 tools/trace_agreement.py $OUT/trace/x_kernel_trace.csv $OUT/trace.log > $OUT/trace_vs_events.txt
 rm -rf $OUT/trace
-timeout -k 10 400 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
-timeout -k 10 400 python3 bench.py --steps 20 --warmup 5 > $OUT/bench_driver_config.json 2> $OUT/bench_driver_config.err
-for w in cfg2 cluster tree dragon871k; do timeout -k 10 400 python3 bench.py --workload $w > $OUT/bench_$w.json 2> $OUT/bench_$w.err; done
-timeout -k 10 400 python3 bench.py --frame 3840x2160 --steps 16 --warmup 4 > $OUT/bench_4k.json 2> $OUT/bench_4k.err
-timeout -k 10 400 python3 bench.py --steps 1 --warmup 2 --no-cpu-baseline --no-profile > $OUT/bench_steps1.json 2> $OUT/bench_steps1.err
+timeout -k 10 400 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 400 python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver_config.json 2> $OUT/bench_driver_config.err
+for w in cfg2 cluster tree dragon871k; do timeout -k 10 400 python3 bench.py --full --workload $w > $OUT/bench_$w.json 2> $OUT/bench_$w.err; done
+timeout -k 10 400 python3 bench.py --full --frame 3840x2160 --steps 16 --warmup 4 > $OUT/bench_4k.json 2> $OUT/bench_4k.err
+timeout -k 10 400 python3 bench.py --full --steps 1 --warmup 2 --no-cpu-baseline --no-profile > $OUT/bench_steps1.json 2> $OUT/bench_steps1.err
 python3 tools/tile_overhead.py > $OUT/tile_scaling_one_gpu.txt 2>&1
 TILE_K=20 python3 tools/tile_overhead.py > $OUT/tile_scaling_one_gpu_k20.txt 2>&1
 # BASELINE.json's cfg5 as far as one GPU can show it: a rank's share of the 7680x4320 frame among 8 ranks, 256 passes, against the whole frame

@@ -25,7 +25,7 @@ tail = n // max(1, d["repeats"]) if d.get("nearest_first_opt_in") else 0
 sel = rows[-(n + tail):len(rows) - tail]
 assert len(sel) == n, (len(sel), n, len(rows))
 avg = sum(e - s for s, e in sel) / len(sel) / 1e6
-print("command: python3 bench.py --steps %d --warmup %d --no-cpu-baseline --no-profile (under rocprofv3 --kernel-trace --stats)" % (d["steps"], d["warmup"]))
+print("command: python3 bench.py --full --steps %d --warmup %d --no-cpu-baseline --no-profile (under rocprofv3 --kernel-trace --stats)" % (d["steps"], d["warmup"]))
 print("k_trace launches in the timed region: %d" % n)
 print("rocprofv3 kernel trace, average duration of those launches: %.4f ms" % avg)
 print("bench.py HIP events (roofline.kernel_avg_ms):                %.4f ms" % d["roofline"]["kernel_avg_ms"])
