@@ -1659,8 +1659,10 @@ int gpuart_hip_test_cam_rays(gpuart_hip_ctx *c, float *rstart, float *rdir) {
 }
 #endif
 
+#ifdef GPUART_HIP_TEST_HOOKS
 namespace {
 /// One wave that keeps the stream busy for `ticks` of the 100 MHz wall clock (gpuart_hip_test_stall): it ends by itself.
+/// Test builds only, like its launcher: the product code object carries no k_test_* kernel (tests/test_product_library.py).
 __global__ void k_test_stall(unsigned long long ticks, unsigned long long *sink) {
     const unsigned long long t0 = wall_clock64();
     unsigned long long n = 0;
@@ -1668,7 +1670,6 @@ __global__ void k_test_stall(unsigned long long ticks, unsigned long long *sink)
     if (sink && threadIdx.x == 0) *sink = n;
 }
 }  // namespace
-#ifdef GPUART_HIP_TEST_HOOKS
 int gpuart_hip_test_tile_order(gpuart_hip_ctx *c, const uint32_t *order, size_t n) {
     if (!c || !c->frame.W) return fail(GPUART_HIP_ERR_ARG, "no frame size set");
     HIP_TRY(hipSetDevice(c->device));
