@@ -43,6 +43,36 @@ class Counters(C.Structure):
                     algorithmic_bytes=self.algorithmic_bytes())
 
 
+class RayHit(C.Structure):
+    """gpuart_ray_hit (include/gpuart_hip.h): one query's record, 32 bytes."""
+    _fields_ = [("pos", C.c_float), ("p", C.c_float * 3), ("n", C.c_float * 3), ("type", C.c_int32)]
+
+
+# the same record as a NumPy dtype: what trace_rays / pick return for host arrays (hits.view(np.float32).reshape(-1, 8): the raw words)
+RAY_HIT = np.dtype([("pos", np.float32), ("p", np.float32, 3), ("n", np.float32, 3), ("type", np.int32)])
+RAYS_OCCLUSION = 1  # GPUART_HIP_RAYS_OCCLUSION
+
+
+def _user_sphere(us):
+    return None if us is None else (C.c_float * 4)(*[float(x) for x in us])
+
+
+def _rays_array(rays):
+    rays = np.ascontiguousarray(rays, np.float32)
+    if rays.ndim != 2 or rays.shape[1] != 8:
+        raise ValueError("rays must be (n, 8): origin.xyz, tmax, dir.xyz, unused")
+    return rays
+
+
+def _pixels_array(xy):
+    xy = np.asarray(xy)
+    if xy.ndim != 2 or xy.shape[1] != 2:
+        raise ValueError("xy must be (n, 2) frame pixels (x, y), row 0 = bottom")
+    if xy.size and (xy.min() < 0 or xy.max() > 0xffffffff):
+        raise ValueError("pixel coordinates must be non-negative 32-bit values")
+    return np.ascontiguousarray(xy, np.uint32)
+
+
 _hip = None
 _host = None
 TEST_LIBDIR = os.path.join(HERE, "lib_test")  # the same sources + the hooks of include/gpuart_hip_test.h (csrc/Makefile)
@@ -501,6 +531,53 @@ class Backend:
         self._chk(self.L.gpuart_hip_scene_order(self.ctx, C.byref(o)))
         return o.value
 
+    # batched ray queries (include/gpuart_hip.h gpuart_hip_trace_rays / _trace_rays_host / _pick)
+    def trace_rays(self, rays, occlusion=False, user_sphere=None, want_prims=False, out=None, prims_out=None):
+        """Closest hit (or, occlusion=True, "is 0 < closest-hit pos < tmax?") of rays (n, 8) = origin.xyz, tmax, dir.xyz, unused, as the
+        reference answers it; user_sphere = (x, y, z, r) takes part, None = no user sphere.
+        A NumPy array runs through host memory (synchronous) and returns a RAY_HIT record array. A torch tensor on this context's device
+        runs in place, without a copy: torch's current stream is synchronised before, and the context (gpuart_hip_finish, which also
+        launches collected passes) before returning; hits is an (n, 8) float32 tensor (column 7 holds the int32 type: .view(torch.int32)),
+        written into `out` if given. With want_prims, also the primitive ordinals (int32; -1 none, -2 the user sphere)."""
+        flags = C.c_uint32(RAYS_OCCLUSION if occlusion else 0)
+        us = _user_sphere(user_sphere)
+        if type(rays).__module__.startswith("torch"):
+            import torch
+            if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous() or rays.device.type != "cuda":
+                raise ValueError("rays must be a contiguous (n, 8) float32 tensor on the GPU")
+            n = rays.shape[0]
+            hits = out if out is not None else torch.empty((n, 8), dtype=torch.float32, device=rays.device)
+            if hits.dtype != torch.float32 or tuple(hits.shape) != (n, 8) or not hits.is_contiguous() or hits.device != rays.device:
+                raise ValueError("out must be a contiguous (n, 8) float32 tensor on the rays' device")
+            prims = None
+            if want_prims:
+                prims = prims_out if prims_out is not None else torch.empty((n,), dtype=torch.int32, device=rays.device)
+                if prims.dtype != torch.int32 or tuple(prims.shape) != (n,) or not prims.is_contiguous() or prims.device != rays.device:
+                    raise ValueError("prims_out must be a contiguous (n,) int32 tensor on the rays' device")
+            torch.cuda.current_stream(rays.device).synchronize()
+            self._chk(self.L.gpuart_hip_trace_rays(self.ctx, C.c_void_p(rays.data_ptr()), C.c_size_t(n), flags, us,
+                                                   C.c_void_p(hits.data_ptr()), C.c_void_p(prims.data_ptr() if prims is not None else 0)))
+            self.finish()
+            return (hits, prims) if want_prims else hits
+        rays = _rays_array(rays)
+        n = rays.shape[0]
+        hits = np.zeros(n, RAY_HIT)
+        prims = np.zeros(n, np.int32) if want_prims else None
+        self._chk(self.L.gpuart_hip_trace_rays_host(self.ctx, _p(rays), C.c_size_t(n), flags, us, _p(hits),
+                                                    _p(prims) if prims is not None else None))
+        return (hits, prims) if want_prims else hits
+
+    def pick(self, xy, user_sphere=None, want_prims=False):
+        """Closest hit of the camera rays of frame pixels xy (n, 2) = (x, y), row 0 = bottom, any pixel of the frame: a RAY_HIT record
+        array (and the primitive ordinals)."""
+        xy = _pixels_array(xy)
+        n = xy.shape[0]
+        hits = np.zeros(n, RAY_HIT)
+        prims = np.zeros(n, np.int32) if want_prims else None
+        self._chk(self.L.gpuart_hip_pick(self.ctx, _p(xy), C.c_size_t(n), _user_sphere(user_sphere), _p(hits),
+                                         _p(prims) if prims is not None else None))
+        return (hits, prims) if want_prims else hits
+
     # test hooks
     def _hook(self, name, ins, nout, *extra):
         ins = [np.ascontiguousarray(a, np.float32) for a in ins]
@@ -643,6 +720,30 @@ class Renderer:
         return out
 
     def finish(self): return bool(self.L.gpuart_renderer_finish(self.h))
+
+    def trace_rays(self, rays, occlusion=False, user_sphere=True, want_prims=False):
+        """Renderer::TraceRays: rays (n, 8) in host memory; user_sphere = include the renderer's current user sphere. Returns a RAY_HIT
+        record array (and, with want_prims, per ray the index of the hit primitive in the list given to set_primitives — in the
+        caller's order —, -1 none, -2 the user sphere)."""
+        rays = _rays_array(rays)
+        n = rays.shape[0]
+        hits = np.zeros(n, RAY_HIT)
+        prims = np.zeros(n, np.int32) if want_prims else None
+        if not self.L.gpuart_renderer_trace_rays(self.h, _p(rays), C.c_size_t(n), C.c_int(1 if occlusion else 0), C.c_int(1 if user_sphere else 0),
+                                                 _p(hits), _p(prims) if prims is not None else None):
+            raise HipError("trace_rays failed: " + hip_lib().gpuart_hip_last_error().decode())
+        return (hits, prims) if want_prims else hits
+
+    def pick(self, xy, user_sphere=True, want_prims=False):
+        """Renderer::Pick: what lies under frame pixels xy (n, 2) = (x, y), row 0 = bottom. As trace_rays."""
+        xy = _pixels_array(xy)
+        n = xy.shape[0]
+        hits = np.zeros(n, RAY_HIT)
+        prims = np.zeros(n, np.int32) if want_prims else None
+        if not self.L.gpuart_renderer_pick(self.h, _p(xy), C.c_size_t(n), C.c_int(1 if user_sphere else 0), _p(hits),
+                                           _p(prims) if prims is not None else None):
+            raise HipError("pick failed: " + hip_lib().gpuart_hip_last_error().decode())
+        return (hits, prims) if want_prims else hits
 
     def last_setprims_ms(self):
         """(whole call, BVH build, compilation, re-layout + upload) of the last set_primitives, ms, as the library timed them."""

@@ -21,6 +21,7 @@
 
 #include "kernels_pipeline.h"
 #include "kernel_run.h"
+#include "kernels_query.h"
 #ifdef GPUART_HIP_TEST_HOOKS
 #include "kernels_test.h"  // kernels of the device-function hooks (include/gpuart_hip_test.h)
 #endif
@@ -104,6 +105,7 @@ struct gpuart_hip_ctx {
     bool empty_share = false;      ///< gpuart_hip_set_share with th == 0: nothing to render, still a member of the gather
     float4 *d_recs = nullptr, *d_prims = nullptr;
     uint32_t *d_cursor = nullptr;  ///< pixel cursor of k_direct_persistent
+    uint32_t *d_query_cursor = nullptr;  ///< chunk cursor of k_ray_query (primary stream, like d_spill)
     uint4 *d_spill = nullptr;      ///< [spill_levels][grid_lanes] traversal-stack overflow for kernels on the primary stream
     // Birth order of the paths of a run (Frame::tile_order, k_tile_order): the tile's 8x8 blocks, most expensive first. The first run
     // after the tile was (re)allocated — and the first after every change of camera or scene — counts the shaded segments per block
@@ -506,7 +508,7 @@ int gpuart_hip_destroy(gpuart_hip_ctx *c) {
     const bool comm_stuck = bounded_ns::stuck().load();
     if (c->comm && !comm_stuck) (void)comm_drop(c);
     void *ptrs[] = {c->d_recs, c->d_prims, c->d_spill, c->d_direct, c->d_accum, c->d_counters, c->d_scratch, c->d_cursor,
-                    c->d_tile_order[0], c->d_tile_order[1], c->d_tile_cost};
+                    c->d_query_cursor, c->d_tile_order[0], c->d_tile_order[1], c->d_tile_cost};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     void *comm_ptrs[] = {c->d_send, c->d_stage, c->d_hello};
     for (void *p : comm_ptrs) if (p && !comm_stuck) (void)hipFree(p);
@@ -1032,6 +1034,122 @@ int gpuart_hip_scene_info(gpuart_hip_ctx *c, uint64_t *nodes, uint64_t *prims, u
     if (max_depth) *max_depth = c->max_depth;
     if (device_bytes) *device_bytes = c->scene_bytes;
     return 0;
+}
+
+// ---- batched ray queries (kernels_query.h) ----------------------------------------------------------------------------
+static_assert(sizeof(gpuart_ray_hit) == 32 && offsetof(gpuart_ray_hit, n) == 16 && offsetof(gpuart_ray_hit, type) == 28,
+              "a record is the two float4 k_ray_query stores");
+
+/// The checks every query entry point makes before it touches anything: 1 for n == 0 (nothing to do), 0 to go ahead, or the error.
+/// `align`: what the pointers must be aligned to (16 for device memory: the kernel loads and stores float4).
+static int query_check(gpuart_hip_ctx *c, size_t n, const void *src, const gpuart_ray_hit *hits, const int32_t *prims, size_t align,
+                       bool pixels) {
+    if (!c) return fail(GPUART_HIP_ERR_ARG, "ctx == NULL");
+    if (!c->have_scene) return fail(GPUART_HIP_ERR_ARG, "ray query: no scene uploaded");
+    if (pixels && !c->frame.W) return fail(GPUART_HIP_ERR_ARG, "pick: no frame size set");
+    if (pixels && !c->have_camera) return fail(GPUART_HIP_ERR_ARG, "pick: no camera set");
+    if (n > GPUART_HIP_MAX_RAYS) return fail(GPUART_HIP_ERR_ARG, "ray query: n = " + std::to_string(n) + " exceeds GPUART_HIP_MAX_RAYS");
+    if (n == 0) return 1;
+    if (!src || !hits) return fail(GPUART_HIP_ERR_ARG, pixels ? "pick: xy or hits is NULL" : "ray query: rays or hits is NULL");
+    if ((uintptr_t)src % align || (uintptr_t)hits % align || (uintptr_t)prims % 4)
+        return fail(GPUART_HIP_ERR_ARG, "ray query: misaligned pointer (rays and hits need " + std::to_string(align) + " bytes, prims 4)");
+    return 0;
+}
+
+static RayQuery make_query(size_t n, uint32_t flags, const float us[4]) {
+    RayQuery q{};
+    q.n = (uint32_t)n;
+    q.occlusion = (flags & GPUART_HIP_RAYS_OCCLUSION) ? 1u : 0u;
+    q.use_us = us ? 1u : 0u;
+    if (us) memcpy(q.us, us, sizeof q.us);
+    return q;
+}
+
+/// One k_ray_query launch on the primary stream. Its scratch — the chunk cursor and the traversal-stack spill d_spill — belongs to the
+/// primary stream, which nothing on the pass lanes' streams uses: a query may run beside pipeline runs in flight. Collected passes are
+/// not flushed (a query neither observes nor changes what they render), and neither the work counters nor the render timings see it.
+static int launch_ray_query(gpuart_hip_ctx *c, const RayQuery &q, int source) {
+    if (!c->d_query_cursor) HIP_TRY(hipMalloc(&c->d_query_cursor, 64));
+    HIP_TRY(hipMemsetAsync(c->d_query_cursor, 0, sizeof(uint32_t), c->stream));
+    // chunks as the direct-lighting frame takes them (gpuart_hip_render_direct); a small batch gets the waves it can fill
+    TraceTuning tune = c->tune;
+    if (!c->chunk_from_env && q.n / ((size_t)c->direct_waves * 8) < 128) tune.chunk = 64;
+    const dim3 grid(std::max<uint32_t>(1u, std::min<uint32_t>(c->direct_waves, (q.n + tune.chunk - 1) / tune.chunk)));
+    const Scene sc = scene_of(c);
+    const bool flat_only = c->lean_kernels && !c->exact_boxes && (c->type_mask & ~(uint32_t)GD_FLAT_TYPES) == 0;
+    const bool round_only = c->lean_kernels && !c->exact_boxes && !flat_only && (c->type_mask & ~(uint32_t)GD_ROUND_TYPES) == 0;
+#define GD_LAUNCH_QUERY(T)                                                                                                       \
+    do {                                                                                                                         \
+        if (source == RQ_PIXELS) k_ray_query<T, RQ_PIXELS><<<grid, BLOCK, 0, c->stream>>>(sc, c->frame, q, c->d_spill, c->d_query_cursor, tune); \
+        else k_ray_query<T, RQ_RAYS><<<grid, BLOCK, 0, c->stream>>>(sc, c->frame, q, c->d_spill, c->d_query_cursor, tune);               \
+    } while (0)
+    if (c->exact_boxes) GD_LAUNCH_QUERY(GD_ALL_TYPES | GD_EXACT_BOXES);
+    else if (flat_only) GD_LAUNCH_QUERY(GD_FLAT_TYPES);
+    else if (round_only) GD_LAUNCH_QUERY(GD_ROUND_TYPES);
+    else GD_LAUNCH_QUERY(GD_ALL_TYPES);
+#undef GD_LAUNCH_QUERY
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+#define GD_QUERY_STAGE ((size_t)1 << 21)  // queries per staged chunk of the host-memory entry points (136 MB of scratch at most)
+
+int gpuart_hip_trace_rays(gpuart_hip_ctx *c, const float *rays, size_t n, uint32_t flags, const float us[4], gpuart_ray_hit *hits,
+                          int32_t *prims) {
+    int r = query_check(c, n, rays, hits, prims, 16, false);
+    if (r) return r > 0 ? 0 : r;
+    if (flags & ~GPUART_HIP_RAYS_OCCLUSION) return fail(GPUART_HIP_ERR_ARG, "ray query: unknown flags");
+    HIP_TRY(hipSetDevice(c->device));
+    RayQuery q = make_query(n, flags, us);
+    q.rays = (const float4 *)rays;
+    q.hits = (float4 *)hits;
+    q.prims = prims;
+    return launch_ray_query(c, q, RQ_RAYS);
+}
+
+/// The host-memory entry points: chunks of GD_QUERY_STAGE queries through the context's scratch, `src_bytes` of source per query.
+static int staged_query(gpuart_hip_ctx *c, const void *src, size_t src_bytes, size_t n, uint32_t flags, const float us[4], int source,
+                        gpuart_ray_hit *hits, int32_t *prims) {
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t chunk = std::min(n, GD_QUERY_STAGE);
+    int r = ensure_scratch(c, chunk * (32 + 32 + 4));
+    if (r) return r;
+    char *base = (char *)c->d_scratch;
+    float4 *d_hits = (float4 *)(base + chunk * 32);  // (the source area is 32 bytes per query for either source)
+    int32_t *d_prims = (int32_t *)(base + chunk * 64);
+    for (size_t k = 0; k < n; k += chunk) {
+        const size_t m = std::min(chunk, n - k);
+        HIP_TRY(hipMemcpyAsync(base, (const char *)src + k * src_bytes, m * src_bytes, hipMemcpyHostToDevice, c->stream));
+        RayQuery q = make_query(m, flags, us);
+        q.rays = (const float4 *)base;
+        q.xy = (const uint2 *)base;
+        q.hits = d_hits;
+        q.prims = prims ? d_prims : nullptr;
+        if ((r = launch_ray_query(c, q, source))) return r;
+        HIP_TRY(hipMemcpyAsync(hits + k, d_hits, m * 32, hipMemcpyDeviceToHost, c->stream));
+        if (prims) HIP_TRY(hipMemcpyAsync(prims + k, d_prims, m * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return 0;
+}
+
+int gpuart_hip_trace_rays_host(gpuart_hip_ctx *c, const float *rays, size_t n, uint32_t flags, const float us[4], gpuart_ray_hit *hits,
+                               int32_t *prims) {
+    int r = query_check(c, n, rays, hits, prims, 4, false);
+    if (r) return r > 0 ? 0 : r;
+    if (flags & ~GPUART_HIP_RAYS_OCCLUSION) return fail(GPUART_HIP_ERR_ARG, "ray query: unknown flags");
+    return staged_query(c, rays, 32, n, flags, us, RQ_RAYS, hits, prims);
+}
+
+int gpuart_hip_pick(gpuart_hip_ctx *c, const uint32_t *xy, size_t n, const float us[4], gpuart_ray_hit *hits, int32_t *prims) {
+    int r = query_check(c, n, xy, hits, prims, 4, true);
+    if (r) return r > 0 ? 0 : r;
+    for (size_t i = 0; i < n; i++)
+        if (xy[2 * i] >= c->frame.W || xy[2 * i + 1] >= c->frame.H)
+            return fail(GPUART_HIP_ERR_ARG, "pick: pixel " + std::to_string(i) + " (" + std::to_string(xy[2 * i]) + ", " +
+                        std::to_string(xy[2 * i + 1]) + ") lies outside the " + std::to_string(c->frame.W) + " x " +
+                        std::to_string(c->frame.H) + " frame");
+    return staged_query(c, xy, 8, n, 0, us, RQ_PIXELS, hits, prims);
 }
 
 // ---- shares and the multi-GPU gather (gather.h) ---------------------------------------------------------------------

@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
+#include <algorithm>
 
 #include "renderer.h"
 #include "scenes.h"
@@ -109,6 +110,9 @@ Camera make_camera(const float pos[3], const float dir[3], const float up[3], fl
 
 struct gpuart_renderer {
     Renderer impl;
+    /// After gpuart_renderer_set_primitives: descOf[k] = the index in the caller's `prims` of the primitive SetPrimitives left at position k
+    /// (the build sorts its vector); empty for the scenes of the init_* calls, whose ordinals are returned as they are.
+    std::vector<int32_t> descOf;
     gpuart_renderer(unsigned w, unsigned h, const Camera &c, int device) : impl(w, h, c, device) {}
 };
 
@@ -182,16 +186,47 @@ int gpuart_renderer_is_ok(gpuart_renderer *r) { return r && r->impl.GetIsOK(); }
 
 void gpuart_renderer_set_primitives(gpuart_renderer *r, const gpuart_prim_desc *prims, int n, int printInfo) {
     std::vector<Primitive *> list;
-    if (make_list(prims, n, list)) r->impl.SetPrimitives(list, printInfo != 0);
+    r->descOf.clear();
+    if (make_list(prims, n, list)) {
+        // the permutation the build applies: each object's position in the caller's order, looked up after SetPrimitives sorted the list
+        std::vector<std::pair<const Primitive *, int32_t>> pos(list.size());
+        for (size_t i = 0; i < list.size(); i++) pos[i] = {list[i], (int32_t)i};
+        std::sort(pos.begin(), pos.end());
+        r->impl.SetPrimitives(list, printInfo != 0);
+        r->descOf.resize(list.size());
+        for (size_t k = 0; k < list.size(); k++)
+            r->descOf[k] = std::lower_bound(pos.begin(), pos.end(), std::make_pair((const Primitive *)list[k], (int32_t)-1))->second;
+    }
     free_list(list);
 }
-void gpuart_renderer_init_box(gpuart_renderer *r) { InitBox(r->impl); }
-int gpuart_renderer_init_dragon(gpuart_renderer *r, const char *plyPath) { return InitDragon(r->impl, plyPath) ? 1 : 0; }
+void gpuart_renderer_init_box(gpuart_renderer *r) { r->descOf.clear(); InitBox(r->impl); }
+int gpuart_renderer_init_dragon(gpuart_renderer *r, const char *plyPath) { r->descOf.clear(); return InitDragon(r->impl, plyPath) ? 1 : 0; }
 int gpuart_renderer_init_cluster(gpuart_renderer *r, const char *datPath) {
+    r->descOf.clear();
     return (datPath ? InitCluster(r->impl, datPath) : InitCluster(r->impl)) ? 1 : 0;
 }
 int gpuart_renderer_init_tree(gpuart_renderer *r, const char *datPath) {
+    r->descOf.clear();
     return (datPath ? InitTree(r->impl, datPath) : InitTree(r->impl)) ? 1 : 0;
+}
+namespace {
+/// Device ordinals -> indices of the caller's descriptions (capi.h: gpuart_renderer_trace_rays).
+void to_desc_index(const gpuart_renderer *r, int32_t *prims, size_t n) {
+    if (!prims || r->descOf.empty()) return;
+    for (size_t i = 0; i < n; i++)
+        if (prims[i] >= 0 && (size_t)prims[i] < r->descOf.size()) prims[i] = r->descOf[(size_t)prims[i]];
+}
+}  // namespace
+int gpuart_renderer_trace_rays(gpuart_renderer *r, const float *rays, size_t n, int occlusion, int withUserSphere, gpuart_ray_hit *hits,
+                               int32_t *prims) {
+    if (!r->impl.TraceRays(rays, n, occlusion != 0, withUserSphere != 0, hits, prims)) return 0;
+    to_desc_index(r, prims, n);
+    return 1;
+}
+int gpuart_renderer_pick(gpuart_renderer *r, const uint32_t *xy, size_t n, int withUserSphere, gpuart_ray_hit *hits, int32_t *prims) {
+    if (!r->impl.Pick(xy, n, hits, prims, withUserSphere != 0)) return 0;
+    to_desc_index(r, prims, n);
+    return 1;
 }
 int gpuart_renderer_set_camera(gpuart_renderer *r, const float pos[3], const float dir[3], const float up[3], float fovY,
                                float screenDist) {

@@ -77,6 +77,13 @@ int gpuart_renderer_read_radiance(gpuart_renderer *r, float *rgba, int normalize
 int gpuart_renderer_finish(gpuart_renderer *r);
 int gpuart_renderer_save_checkpoint(gpuart_renderer *r, const char *path);
 int gpuart_renderer_load_checkpoint(gpuart_renderer *r, const char *path);
+/* Renderer::TraceRays / Renderer::Pick (host memory, synchronous; 1 on success, 0 on error): rays n x 8 floats {origin.xyz, tmax}
+ * {dir.xyz, unused}, xy[2n] frame pixels. After gpuart_renderer_set_primitives, prims[i] (prims may be NULL) indexes the `prims` array
+ * AS THE CALLER PASSED IT (the build's reordering is undone here); after an init_* scene it is the position in the renderer's sorted list.
+ * -1: nothing hit, -2: the user sphere. */
+int gpuart_renderer_trace_rays(gpuart_renderer *r, const float *rays, size_t n, int occlusion, int withUserSphere, gpuart_ray_hit *hits,
+                               int32_t *prims);
+int gpuart_renderer_pick(gpuart_renderer *r, const uint32_t *xy, size_t n, int withUserSphere, gpuart_ray_hit *hits, int32_t *prims);
 gpuart_hip_ctx *gpuart_renderer_backend(gpuart_renderer *r);
 void gpuart_renderer_params(gpuart_renderer *r, gpuart_params *out);
 /* What the renderer's last SetPrimitives spent inside the library, ms: whole call, BVH build, compilation, re-layout + upload. */

@@ -231,6 +231,27 @@ void Renderer::SetPrimitives(std::vector<Primitive *> &primitives, bool printInf
     ResetPathTracing();
 }
 
+// ---- batched ray queries ------------------------------------------------------------------------
+// `prims` is the device primitive ordinal, which numbers the primitives in the order of the compiled tree's leaves (the uploader appends
+// each leaf's primitives as it meets the leaves in pre-order, lower child first: converter.h `scan`). That is the order of the vector
+// SetPrimitives leaves behind: the build writes its sorted items back into it (bvh.cpp:81, `primitives[i] = items[i].p`), every node
+// splits its item range [from, to) into a lower child [from, split) and an upper child [split, to) (bvh.cpp Subdivide), a leaf holds
+// items [primFirst, primFirst + count) (bvh.cpp:166-167), the compiled tree lays the nodes out in pre-order with the lower child first
+// (bvh.cpp CompileTo), and no leaf of a non-empty scene is empty (a range of more than minPrims = 2 items is split strictly inside,
+// bvh.cpp:218-221) — so leaf k in pre-order holds the items that follow those of leaves 0 .. k-1, and ordinal i is primitives[i].
+bool Renderer::TraceRays(const float *rays, size_t n, bool occlusion, bool withUserSphere, gpuart_ray_hit *hits, int32_t *prims) {
+    if (!IsOK) return false;
+    const float us[4] = {UserSphere.pos.x, UserSphere.pos.y, UserSphere.pos.z, UserSphere.radius};
+    return Check(gpuart_hip_trace_rays_host(Backend, rays, n, occlusion ? GPUART_HIP_RAYS_OCCLUSION : 0u, withUserSphere ? us : nullptr,
+                                            hits, prims), "tracing rays");
+}
+
+bool Renderer::Pick(const uint32_t *xy, size_t n, gpuart_ray_hit *hits, int32_t *prims, bool withUserSphere) {
+    if (!IsOK) return false;
+    const float us[4] = {UserSphere.pos.x, UserSphere.pos.y, UserSphere.pos.z, UserSphere.radius};
+    return Check(gpuart_hip_pick(Backend, xy, n, withUserSphere ? us : nullptr, hits, prims), "picking");
+}
+
 // ---- lighting / user sphere ---------------------------------------------------------------------
 void Renderer::SetUserSphere(const Vec3f &pos, float radius, float emittance) {
     UserSphere.pos = pos;

@@ -121,6 +121,14 @@ public:
     gpuart_hip_ctx *GetBackend() const { return Backend; }
     /// What the last SetPrimitives spent, in ms: the whole call, the BVH build, its compilation, re-layout + upload (for tools/setprims_time.py).
     const double *GetLastSetPrimitivesMs() const { return LastSetPrimitivesMs; }
+    /// Batched ray queries (include/gpuart_hip.h gpuart_hip_trace_rays): `rays` = n x 8 floats {origin.xyz, tmax}{dir.xyz, unused} in host
+    /// memory; closest hit — or, with `occlusion`, "is 0 < closest-hit pos < tmax?" — as the reference's CheckBVHIntersection answers it,
+    /// including the current user sphere when `withUserSphere`. `prims` (may be null): per ray the index of the hit primitive in the
+    /// vector SetPrimitives left behind (-1 none, -2 the user sphere). Synchronous; no image changes. False on error (std::cerr says why).
+    bool TraceRays(const float *rays, size_t n, bool occlusion, bool withUserSphere, gpuart_ray_hit *hits, int32_t *prims);
+    /// Closest hit under frame pixels xy[2n] = (x, y), row 0 = bottom, any pixel of the viewport: the camera ray RenderDirectLighting
+    /// traces for that pixel. Otherwise as TraceRays.
+    bool Pick(const uint32_t *xy, size_t n, gpuart_ray_hit *hits, int32_t *prims, bool withUserSphere = true);
     unsigned GetTileWidth() const { return Tile.w; }
     unsigned GetTileHeight() const { return Tile.h; }
     const BoundingVolumesHierarchy &GetBVH() const { return Tree; }

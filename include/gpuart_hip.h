@@ -253,6 +253,40 @@ int gpuart_hip_scene_info(gpuart_hip_ctx *ctx, uint64_t *nodes, uint64_t *prims,
 int gpuart_hip_set_nearest_first(gpuart_hip_ctx *ctx, uint32_t min_prims);
 int gpuart_hip_scene_order(gpuart_hip_ctx *ctx, int *order);
 
+/* ---- batched ray queries (no reference counterpart: the reference's CheckBVHIntersection, shaders/bvh_intersection.glsl:405-441, and
+ * CheckIntersectionInclUserSphere, shaders/intersection.glsl:71-111, for rays the caller chooses) --------------------------------------
+ * Every query walks the uploaded tree in the reference's order — whatever gpuart_hip_set_nearest_first says — and returns the reference's
+ * answer bit for bit.
+ *   closest hit: pos, point p, normal n and primitive type (0 sphere, 1 disc, 2 triangle, 3 cone) of the reference's closest hit; with a
+ *                user sphere (`userSphere` = centre, radius; NULL = none) the user sphere takes part as in the reference. A miss writes
+ *                pos = -1, p = n = 0, type = -1.
+ *   occlusion (GPUART_HIP_RAYS_OCCLUSION): is 0 < the reference's closest-hit pos < tmax? The walk stops at the first accepted hit below
+ *                tmax (exact: DESIGN.md "Batched ray queries"). Occluded: pos and primitive of the hit that ended the walk, p = n = 0, its
+ *                type; not occluded: pos = -1, type = -1. tmax = +inf: any hit; tmax <= 0 or NaN: never occluded.
+ * `prims` (may be NULL) receives per query the primitive's ordinal — its index among the device primitives, which follow the leaves of
+ * the compiled tree in order —, -1 for none, -2 for the user sphere.
+ * Queries run on the context's primary stream; collected passes are not flushed (no image depends on a query, no query on a pass);
+ * queries change neither gpuart_hip_counters nor gpuart_hip_kernel_time. GPUART_HIP_ERR_ARG without a scene (pick: without a frame size
+ * or camera), for NULL or misaligned pointers, a pixel outside the W x H frame or n > GPUART_HIP_MAX_RAYS; n = 0 does nothing. */
+typedef struct gpuart_ray_hit {
+    float pos, p[3];
+    float n[3];
+    int32_t type;
+} gpuart_ray_hit; /* 32 bytes */
+#define GPUART_HIP_RAYS_OCCLUSION 1u
+#define GPUART_HIP_MAX_RAYS 0x7fffffffu /* queries per call */
+/* Device memory, asynchronous on the context's stream (gpuart_hip_finish before the results are used). rays: n x 8 floats,
+ * {origin.xyz, tmax}{dir.xyz, unused} (tmax is read in occlusion mode only); rays and hits 16-byte aligned, prims 4-byte aligned. */
+int gpuart_hip_trace_rays(gpuart_hip_ctx *ctx, const float *rays, size_t n, uint32_t flags, const float userSphere[4],
+                          gpuart_ray_hit *hits, int32_t *prims);
+/* The same in host memory, synchronous (staged through the context's scratch, in chunks of 2^21 queries). */
+int gpuart_hip_trace_rays_host(gpuart_hip_ctx *ctx, const float *rays, size_t n, uint32_t flags, const float userSphere[4],
+                               gpuart_ray_hit *hits, int32_t *prims);
+/* Closest hit of the camera rays of frame pixels xy[2n] = (x, y), row 0 = bottom, any pixel of the W x H frame (not only the
+ * context's tile): the ray gpuart_hip_render_direct traces for that pixel. Host memory, synchronous. */
+int gpuart_hip_pick(gpuart_hip_ctx *ctx, const uint32_t *xy, size_t n, const float userSphere[4], gpuart_ray_hit *hits,
+                    int32_t *prims);
+
 /* The test hooks (gpuart_hip_test_*: the run planner, the uploader's verdicts, the share-table check, birth orders, a stream stall, the
  * device functions one by one) are NOT part of this interface: include/gpuart_hip_test.h declares them, and only a library built with
  * -DGPUART_HIP_TEST_HOOKS (gpuart_amd/lib_test/, what the test suite loads) defines them. */

@@ -1,0 +1,499 @@
+"""Batched ray queries (include/gpuart_hip.h gpuart_hip_trace_rays / _trace_rays_host / _pick, Renderer::TraceRays / Pick): closest hit and
+occlusion for the caller's rays and for frame pixels, against the reference's own answers (tests/golden/traverse_*.npz, order_adversary.npz:
+the reference's GLSL on llvmpipe), the oracle and the test build's one-thread-per-ray hook, bit for bit."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from gpuart_amd import synth_scenes as S
+from tests.util import golden, pad4, scene
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_HIP = ["gpuart_hip_trace_rays", "gpuart_hip_trace_rays_host", "gpuart_hip_pick"]
+NEW_HOST = ["gpuart_renderer_trace_rays", "gpuart_renderer_pick"]
+WILD = ["scene_pc", "wild_42874", "wild_7", "wild2_5", "pc_min5", "pc_levels4", "p_root_leaf", "soup_levels6"]
+WILD_SPHERE = (-0.4, 0.0, 0.2, 0.25)
+ERR_ARG = -1
+
+
+# ---- CPU ---------------------------------------------------------------------------------------------------------------------
+def _exported(path):
+    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+    return {line.split()[-1] for line in out.splitlines() if line.strip()}
+
+
+@pytest.mark.parametrize("lib", ["lib", "lib_test"])
+def test_libraries_export_the_query_functions(lib):
+    hip = _exported(os.path.join(ROOT, "gpuart_amd", lib, "libgpuart_hip.so"))
+    host = _exported(os.path.join(ROOT, "gpuart_amd", lib, "libgpuart.so"))
+    assert set(NEW_HIP) <= hip, sorted(set(NEW_HIP) - hip)
+    assert set(NEW_HOST) <= host, sorted(set(NEW_HOST) - host)
+    hdr = open(os.path.join(ROOT, "include", "gpuart_hip.h")).read()
+    for n in NEW_HIP:
+        assert re.search(r"\b%s\s*\(" % n, hdr) and "_test_" not in n
+    capi = open(os.path.join(ROOT, "gpuart_amd", "csrc", "host", "capi.h")).read()
+    for n in NEW_HOST:
+        assert re.search(r"\b%s\s*\(" % n, capi)
+
+
+def test_ray_hit_layout_matches_the_header(tmp_path):
+    """sizeof / offsetof of gpuart_ray_hit as a C compiler sees the header == the ctypes structure == the NumPy record of the binding."""
+    from gpuart_amd import binding as B
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "gpuart_hip.h"\n'
+                   'int main(void) { printf("%zu %zu %zu %zu %zu %u %u\\n", sizeof(gpuart_ray_hit), offsetof(gpuart_ray_hit, pos), '
+                   'offsetof(gpuart_ray_hit, p), offsetof(gpuart_ray_hit, n), offsetof(gpuart_ray_hit, type), GPUART_HIP_RAYS_OCCLUSION, '
+                   'GPUART_HIP_MAX_RAYS); return 0; }\n')
+    exe = tmp_path / "layout"
+    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)], check=True)
+    size, opos, op, on, otype, occl, maxn = (int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split())
+    R = B.RayHit
+    assert (size, opos, op, on, otype) == (C.sizeof(R), R.pos.offset, R.p.offset, R.n.offset, R.type.offset) == (32, 0, 4, 16, 28)
+    assert B.RAY_HIT.itemsize == 32 and [B.RAY_HIT.fields[k][1] for k in ("pos", "p", "n", "type")] == [0, 4, 16, 28]
+    assert occl == B.RAYS_OCCLUSION == 1 and maxn >= 2 ** 31 - 1
+
+
+# ---- GPU ---------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def B():
+    from gpuart_amd import binding
+    return binding
+
+
+@pytest.fixture(scope="module")
+def be(B):
+    b = B.Backend(0)
+    yield b
+    b.close()
+
+
+@pytest.fixture(scope="module")
+def O():
+    from oracle import oracle
+    return oracle
+
+
+def rays8(rs, rd, tmax=np.inf):
+    """(n, 8) rays: origin.xyz, tmax, dir.xyz, 0."""
+    n = len(rs)
+    r = np.zeros((n, 8), np.float32)
+    r[:, 0:3] = np.asarray(rs, np.float32)[:, :3]
+    r[:, 3] = tmax
+    r[:, 4:7] = np.asarray(rd, np.float32)[:, :3]
+    return r
+
+
+def words(hits):
+    return hits.view(np.float32).reshape(-1, 8)
+
+
+def hook_record(o0, o1):
+    """The test hook's / golden's (pos, P)(N, type [+0.5 user sphere]) as the words of gpuart_ray_hit and the user-sphere flag."""
+    w = np.concatenate([o0, o1], 1).astype(np.float32)
+    t = o1[:, 3]
+    ush = t == 0.5
+    w[:, 7] = np.floor(t).astype(np.int32).view(np.float32)
+    return w, ush
+
+
+def assert_same_bits(got, exp, what):
+    same = (got.view(np.uint32) == exp.view(np.uint32)) | (np.isnan(got) & np.isnan(exp))
+    bad = ~same.all(1)
+    assert not bad.any(), "%s: %d of %d rows differ; first: row %d got %s expected %s" % (
+        what, int(bad.sum()), len(bad), int(np.nonzero(bad)[0][0]), got[bad][0], exp[bad][0])
+
+
+def tree_prims(tree):
+    """Canonical compiled tree -> per device ordinal (leaves in pre-order, lower child first) (type, 16 floats of data quads)."""
+    q = np.ascontiguousarray(tree, np.float32)
+    bits = q.view(np.uint32)
+    out, stack = [], [0]
+    while stack:
+        addr = stack.pop()
+        flags = int(bits[addr + 2, 0])
+        if flags & 0x80000000:
+            a = addr + 3
+            if flags & ~0xE0000000 & 0xffffffff == 0:
+                out.append((-1, None))  # an empty leaf keeps one dummy record (converter.h)
+            for _ in range(flags & ~0xE0000000 & 0xffffffff):
+                t = int(bits[a, 0])
+                data = np.zeros(16, np.float32)
+                data[:4 * (t + 1)] = q[a + 1:a + 2 + t].reshape(-1)
+                out.append((t, data))
+                a += 2 + t
+        else:
+            stack.append(int(bits[addr + 2, 2]))  # upper child after ...
+            stack.append(int(bits[addr + 2, 1]))  # ... the lower one
+    return out
+
+
+def traverse_sets():
+    """(name, tree, [(rs, rd, o0, o1)], user sphere) of every golden of test_gpu_parity's traversal tests."""
+    from oracle import oracle as O
+    for name in ["box", "scene_pc", "scene_d"]:
+        g = golden("traverse_" + name)
+        tree, _ = O.build_bvh(scene(name))
+        yield name, tree, [(g["rs"], g["rd"], g["o0"], g["o1"]), (g["rs2"], g["rd2"], g["s0"], g["s1"])], S.USER_SPHERE
+    for name in WILD:
+        g = golden("traverse_wild_" + name)
+        yield "wild_" + name, g["tree"], [(g["rs"], g["rd"], g["o0"], g["o1"])], WILD_SPHERE
+
+
+@pytest.mark.gpu
+def test_closest_hit_equals_the_reference(be):
+    """Test 1: every ray set of the traversal goldens (regular, irregular and 200-level trees, other leaf sizes) with the user sphere."""
+    for name, tree, sets, us in traverse_sets():
+        be.upload_bvh(tree)
+        for rs, rd, o0, o1 in sets:
+            exp, ush = hook_record(o0, o1)
+            hits, prims = be.trace_rays(rays8(rs, rd), user_sphere=us, want_prims=True)
+            assert_same_bits(words(hits), exp, "closest hit " + name)
+            assert ((prims == -2) == ush).all() and ((prims == -1) == (hits["type"] == -1)).all(), name
+            assert (prims[(~ush) & (hits["type"] >= 0)] >= 0).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["box", "scene_pc", "scene_d"])
+def test_pick_equals_the_reference_camera_rays(be, O, name):
+    """Test 2: the goldens' first ray set is the camera rays of their W x H frame, golden row y * W + x (checked against the camera rays of
+    the device, test_cam_rays, row 0 = bottom); picking every pixel gives the reference's closest hit of that ray."""
+    g = golden("traverse_" + name)
+    W, H = int(g["W"]), int(g["H"])
+    tree, _ = O.build_bvh(scene(name))
+    be.upload_bvh(tree)
+    be.resize(W, H)
+    be.set_camera(g["cam"])
+    rs, rd = be.test_cam_rays()
+    assert (rs[..., :3].reshape(-1, 3).view(np.uint32) == g["rs"].view(np.uint32)).all()
+    assert (rd[..., :3].reshape(-1, 3).view(np.uint32) == g["rd"].view(np.uint32)).all()
+    y, x = np.divmod(np.arange(W * H), W)
+    xy = np.stack([x, y], 1)
+    exp, _ = hook_record(g["o0"], g["o1"])
+    assert_same_bits(words(be.pick(xy, user_sphere=S.USER_SPHERE)), exp, "pick " + name)
+    # any order, any subset, pixels outside the context's tile included
+    perm = np.random.default_rng(1).permutation(W * H)[:777]
+    be.set_tile(0, 0, 8, 8)
+    try:
+        assert_same_bits(words(be.pick(xy[perm], user_sphere=S.USER_SPHERE)), exp[perm], "pick, shuffled, tile 8x8 " + name)
+    finally:
+        be.resize(W, H)
+
+
+@pytest.mark.gpu
+def test_phantom_hits(be):
+    """Test 3: the 16 order_adversary scenes: the reference's closest hit is a phantom of a grazing triangle far in front of its box; the
+    closest-hit query returns it, and the occlusion query answers golden_pos > 0 and golden_pos < tmax at +inf, just above and just below."""
+    g = golden("order_adversary")
+    for i in range(int(g["n"])):
+        be.upload_bvh(g["tree%d" % i])
+        rs, rd = g["rs%d" % i][None], g["rd%d" % i][None]
+        exp, _ = hook_record(g["o0_%d" % i][None], g["o1_%d" % i][None])
+        assert_same_bits(words(be.trace_rays(rays8(rs, rd))), exp, "adversary %d" % i)
+        pos = np.float32(exp[0, 0])
+        assert pos > 0
+        for tmax in [np.inf, np.nextafter(pos, np.float32(np.inf)), pos, np.nextafter(pos, np.float32(0))]:
+            h = be.trace_rays(rays8(rs, rd, tmax), occlusion=True)
+            assert (h["pos"][0] > 0) == bool(pos < tmax), (i, tmax, h)
+            if pos < tmax:
+                assert h["pos"][0] == pos and h["type"][0] == 2
+
+
+@pytest.mark.gpu
+def test_occlusion_is_exact(be):
+    """Test 4: occlusion on every set of test 1 with seeded random tmax (0, NaN, +inf, negative, at and around the golden pos)."""
+    rng = np.random.default_rng(4)
+    for name, tree, sets, us in traverse_sets():
+        be.upload_bvh(tree)
+        for rs, rd, o0, o1 in sets:
+            gpos = o0[:, 0].astype(np.float32)
+            n = len(gpos)
+            pick = rng.integers(0, 7, n)
+            tmax = np.where(pick == 0, 0.0, np.where(pick == 1, np.nan, np.where(pick == 2, np.inf, np.where(pick == 3, -1.0,
+                   np.where(pick == 4, gpos, np.where(pick == 5, gpos * rng.uniform(0.5, 2.0, n), rng.uniform(0, 50, n))))))).astype(np.float32)
+            near = pick == 6
+            tmax[near & (gpos > 0)] = np.nextafter(gpos[near & (gpos > 0)], np.float32(np.inf))
+            for with_us in (True, False):
+                hits, prims = be.trace_rays(rays8(rs, rd, tmax), occlusion=True, user_sphere=us if with_us else None, want_prims=True)
+                if with_us:
+                    ref = gpos
+                else:  # the reference's closest hit of the tree alone
+                    c = be.trace_rays(rays8(rs, rd))
+                    ref = c["pos"]
+                want = (ref > 0) & (ref < tmax)
+                got = hits["pos"] > 0
+                assert (got == want).all(), "%s: %d of %d answers differ" % (name, int((got != want).sum()), n)
+                assert (hits["pos"][got] < tmax[got]).all()
+                assert (hits["p"] == 0).all() and (hits["n"] == 0).all()
+                assert ((prims >= 0) | (prims == -2) == got).all() and (hits["type"][~got] == -1).all()
+                if not with_us:
+                    assert (prims != -2).all()
+
+
+@pytest.mark.gpu
+def test_primitive_ordinals(be, B):
+    """Test 5: the ordinal of every hit names the primitive whose record, intersected alone (test_intersect), gives the hit's pos, p, n."""
+    for name, tree, sets, us in traverse_sets():
+        be.upload_bvh(tree)
+        plist = tree_prims(tree)
+        assert len(plist) == be.scene_info()["prims"], name
+        for rs, rd, _, _ in sets:
+            hits, prims = be.trace_rays(rays8(rs, rd), user_sphere=us, want_prims=True)
+            idx = np.nonzero(prims >= 0)[0]
+            types = np.array([plist[k][0] for k in prims[idx]])
+            for t in np.unique(types):
+                sel = idx[types == t]
+                quads = np.stack([plist[k][1] for k in prims[sel]])
+                o0, o1 = be.test_intersect(int(t), pad4(rs[sel]), pad4(rd[sel]), quads)
+                exp = np.concatenate([o0, o1[:, :3]], 1)
+                assert_same_bits(words(hits)[sel, :7], exp, "%s, ordinal of type %d" % (name, t))
+
+
+@pytest.mark.gpu
+def test_renderer_ordinals_index_the_callers_list(B, O):
+    """Test 5, Renderer level: a Scene P-class list the build reorders; prims index the list as it was passed, and intersecting
+    descs[prim] alone with the oracle gives the hit's pos. Pick through the Renderer equals the context's pick."""
+    descs = S.scene_p(seed=3, nspheres=96, ndiscs=24)
+    cam = dict(S.DEFAULT_CAMERA)
+    cam["dir"] = S.camera_dir(cam)
+    W, H = 96, 64
+    r = B.Renderer(W, H, cam, device=0)
+    try:
+        r.set_user_sphere((0.0, 0.0, 0.0), 0.0)
+        r.set_primitives(descs)
+        assert r.is_ok()
+        rng = np.random.default_rng(5)
+        n = 20000
+        rs = rng.uniform(-8, 8, (n, 3)).astype(np.float32)
+        rs[:, 2] = rng.uniform(0.1, 6, n)
+        rd = rng.normal(size=(n, 3)).astype(np.float32)
+        rd /= np.linalg.norm(rd, axis=1, keepdims=True)
+        hits, prims = r.trace_rays(rays8(rs, rd), user_sphere=False, want_prims=True)
+        idx = np.nonzero(prims >= 0)[0]
+        assert len(idx) > n // 10
+        tree, _ = O.build_bvh(descs)
+        assert not all(tree_prims(tree)[k][0] == descs[k][0] for k in range(len(descs))), "the build did not reorder the list"
+        for k in idx[:4000]:
+            t, f = descs[prims[k]]
+            r4, d4 = pad4(rs[k:k + 1]), pad4(rd[k:k + 1])
+            if t == S.SPHERE:
+                o0, _ = O.sphere(r4, d4, np.array([f[:4]], np.float32))
+            else:
+                o0, _ = O.disc(r4, d4, np.array([[f[0], f[1], f[2], f[6]]], np.float32), pad4(np.array([f[3:6]], np.float32)))
+            assert o0[0, 0] == hits["pos"][k], (k, prims[k], o0[0], hits[k])
+        y, x = np.divmod(np.arange(W * H), W)
+        xy = np.stack([x, y], 1)
+        got, gp = r.pick(xy, want_prims=True)
+        exp = r.backend.pick(xy, user_sphere=(0.0, 0.0, 0.0, 0.0))
+        assert_same_bits(words(got), words(exp), "Renderer.pick")
+        assert (gp >= -1).all()
+    finally:
+        r.close()
+
+
+def random_rays(rng, n, lo, hi):
+    """Origins inside and outside the box [lo, hi], unit directions with zero and denormal components sprinkled in."""
+    ext = hi - lo
+    rs = (lo + rng.uniform(-0.5, 1.5, (n, 3)) * ext).astype(np.float32)
+    rd = rng.normal(size=(n, 3)).astype(np.float32)
+    rd /= np.linalg.norm(rd, axis=1, keepdims=True)
+    k = rng.integers(0, 3, n)
+    m = rng.random(n) < 0.05
+    rd[m, k[m]] = 0.0
+    m = rng.random(n) < 0.05
+    rd[m, k[m]] = np.float32(1e-40) * np.sign(rng.normal(size=int(m.sum())))
+    m = rng.random(n) < 0.01
+    rd[m] = 0.0
+    return rs, rd
+
+
+@pytest.fixture(scope="module")
+def scene_d_rays(O):
+    tree, _ = O.build_bvh(S.scene_d())
+    lo, hi = tree[0, :3], tree[1, :3]
+    rs, rd = random_rays(np.random.default_rng(6), 1 << 22, lo.astype(np.float64), hi.astype(np.float64))
+    return tree, rs, rd
+
+
+@pytest.mark.gpu
+def test_at_scale_against_the_hook_and_the_oracle(be, O, scene_d_rays):
+    """Test 6: 2^22 seeded random rays on Scene D (cfg3 class) equal the one-thread-per-ray test hook bit for bit (user sphere and not), a
+    65 536-ray subsample equals the oracle; n = 1, 63, 65 and 0 too."""
+    tree, rs, rd = scene_d_rays
+    be.upload_bvh(tree)
+    for us in (S.USER_SPHERE, None):
+        o0, o1 = be.test_traverse(pad4(rs), pad4(rd), us if us is not None else (0, 0, 0, 0))
+        exp, ush = hook_record(o0, o1)
+        hits = be.trace_rays(rays8(rs, rd), user_sphere=us)
+        if us is None and ush.any():
+            # the hook always includes a sphere, and one of radius 0 at the origin still takes the degenerate rays (zero directions):
+            # those rays are checked against the oracle without a user sphere instead
+            o0, o1 = O.traverse(tree, pad4(rs[ush]), pad4(rd[ush]), None)
+            exp[ush] = hook_record(o0, o1)[0]
+        assert_same_bits(words(hits), exp, "2^22 rays, user sphere %s" % (us,))
+    sub = np.random.default_rng(7).choice(len(rs), 65536, replace=False)
+    o0, o1 = O.traverse(tree, pad4(rs[sub]), pad4(rd[sub]), S.USER_SPHERE)
+    exp, _ = hook_record(o0, o1)
+    assert_same_bits(words(be.trace_rays(rays8(rs[sub], rd[sub]), user_sphere=S.USER_SPHERE)), exp, "oracle subsample")
+    for n in (1, 63, 65):
+        o0, o1 = be.test_traverse(pad4(rs[:n]), pad4(rd[:n]), S.USER_SPHERE)
+        assert_same_bits(words(be.trace_rays(rays8(rs[:n], rd[:n]), user_sphere=S.USER_SPHERE)), hook_record(o0, o1)[0], "n = %d" % n)
+    assert len(be.trace_rays(np.zeros((0, 8), np.float32))) == 0
+
+
+@pytest.mark.gpu
+def test_torch_device_path(be, scene_d_rays):
+    """Test 7: the same rays as a GPU tensor (no copy) give the host path's bits; the given output tensors are written in place."""
+    import torch
+    tree, rs, rd = scene_d_rays
+    be.upload_bvh(tree)
+    n = 1 << 20
+    rays = rays8(rs[:n], rd[:n])
+    rays[::3, 3] = np.random.default_rng(8).uniform(0, 30, len(rays[::3]))
+    for occl in (False, True):
+        ref, rp = be.trace_rays(rays, occlusion=occl, user_sphere=S.USER_SPHERE, want_prims=True)
+        t = torch.from_numpy(rays).to("cuda:0")
+        out = torch.full((n, 8), 7.0, device="cuda:0")
+        pout = torch.full((n,), 7, dtype=torch.int32, device="cuda:0")
+        ptr = (out.data_ptr(), pout.data_ptr())
+        h, p = be.trace_rays(t, occlusion=occl, user_sphere=S.USER_SPHERE, want_prims=True, out=out, prims_out=pout)
+        assert h is out and p is pout and (out.data_ptr(), pout.data_ptr()) == ptr
+        assert_same_bits(out.cpu().numpy(), words(ref), "torch path, occlusion %s" % occl)
+        assert (pout.cpu().numpy() == rp).all()
+        h2 = be.trace_rays(t, occlusion=occl, user_sphere=S.USER_SPHERE)
+        assert_same_bits(h2.cpu().numpy(), words(ref), "torch path, allocated output")
+
+
+@pytest.mark.gpu
+def test_queries_do_not_interfere_with_rendering(B, O):
+    """Test 8: queries of both modes interleaved with 12 path-tracing passes (some still collected) and a direct-lighting frame: the
+    accumulator and the frame are bit-identical to a run without queries, and the queries' answers to those made with nothing pending."""
+    W, H = 160, 96
+    cam = dict(S.DEFAULT_CAMERA)
+    cam["dir"] = S.camera_dir(cam)
+    c = O.camera(cam["pos"], cam["dir"], cam["up"], cam["fov_y"], cam["screen_dist"], W, H)
+    sun = O.sun_direction(S.SUN_AZIMUTH, S.SUN_ALTITUDE)
+    P0 = O.make_params(sun, S.SUN_ALTITUDE, True, S.USER_SPHERE, 0.0, 0, float(c[12]), c[0:3], 5, 0.01)
+    P = B.Params()
+    C.memmove(C.byref(P), C.byref(P0), C.sizeof(P))
+    tree, _ = O.build_bvh(S.scene_d())
+    rs, rd = random_rays(np.random.default_rng(9), 300000, tree[0, :3].astype(np.float64), tree[1, :3].astype(np.float64))
+    rays = rays8(rs, rd, np.random.default_rng(10).uniform(0, 20, len(rs)))
+    seeds = O.randseeds(12)
+    y, x = np.divmod(np.arange(0, W * H, 7), W)
+    xy = np.stack([x, y], 1)
+
+    def run(with_queries):
+        b = B.Backend(0)
+        try:
+            b.resize(W, H); b.upload_bvh(tree); b.set_camera(c)
+            b.pt_reset()
+            b.pt_plan(12)
+            answers = []
+            for k in range(12):
+                b.pt_pass(P, seeds[k], 1)
+                if with_queries and k % 3 == 1:
+                    answers.append(words(b.trace_rays(rays, user_sphere=S.USER_SPHERE)).copy())
+                    answers.append(words(b.trace_rays(rays, occlusion=True)).copy())
+                    answers.append(words(b.pick(xy, user_sphere=S.USER_SPHERE)).copy())
+            if with_queries:
+                answers.append(words(b.trace_rays(rays, occlusion=True, user_sphere=S.USER_SPHERE)).copy())
+            b.render_direct(P)
+            if with_queries:
+                answers.append(words(b.pick(xy)).copy())
+            acc, direct = b.read(1), b.read(0)
+            quiet = []
+            if with_queries:  # the same queries with nothing pending
+                b.finish()
+                q = [words(b.trace_rays(rays, user_sphere=S.USER_SPHERE)).copy(), words(b.trace_rays(rays, occlusion=True)).copy(),
+                     words(b.pick(xy, user_sphere=S.USER_SPHERE)).copy()]
+                quiet = q * 4 + [words(b.trace_rays(rays, occlusion=True, user_sphere=S.USER_SPHERE)).copy(), words(b.pick(xy)).copy()]
+            return acc, direct, answers, quiet
+        finally:
+            b.close()
+
+    acc0, dir0, _, _ = run(False)
+    acc1, dir1, answers, quiet = run(True)
+    assert (acc0.view(np.uint32) == acc1.view(np.uint32)).all(), "the accumulator changed"
+    assert (dir0.view(np.uint32) == dir1.view(np.uint32)).all(), "the direct-lighting frame changed"
+    assert len(answers) == len(quiet) == 14
+    for k, (a, q) in enumerate(zip(answers, quiet)):
+        assert_same_bits(a, q, "query %d" % k)
+
+
+@pytest.mark.gpu
+def test_argument_errors(be, B, O):
+    """Test 9: every ERR_ARG case returns the error with a message and leaves hits untouched."""
+    L = be.L
+    fresh = B.Backend(0)
+    rays = rays8(np.zeros((4, 3)), np.ones((4, 3)))
+    xy = np.zeros((4, 2), np.uint32)
+    us = (C.c_float * 4)(0, 0, 0, 0)
+
+    def call(name, ctx, src, n, hits, extra_flags=None, prims=None):
+        if name == "gpuart_hip_pick":
+            return getattr(L, name)(ctx, src, C.c_size_t(n), us, hits, prims)
+        return getattr(L, name)(ctx, src, C.c_size_t(n), C.c_uint32(extra_flags or 0), us, hits, prims)
+
+    try:
+        tree, _ = O.build_bvh(S.box_scene())
+        be.upload_bvh(tree)
+        be.resize(16, 8)
+        be.set_camera(O.camera(S.DEFAULT_CAMERA["pos"], S.camera_dir(S.DEFAULT_CAMERA), S.DEFAULT_CAMERA["up"], S.DEFAULT_CAMERA["fov_y"],
+                               S.DEFAULT_CAMERA["screen_dist"], 16, 8))
+        hits = np.full((5, 8), 7.0, np.float32)  # one spare row: misaligned pointers start 4 bytes in
+        hp = hits.ctypes.data_as(C.c_void_p)
+        rays_buf = np.zeros((5, 8), np.float32)
+        rays_buf[:4] = rays
+        rp = rays_buf.ctypes.data_as(C.c_void_p)
+        xyp = xy.ctypes.data_as(C.c_void_p)
+        off = lambda p, k: C.c_void_p(p.value + k)
+        cases = [
+            ("gpuart_hip_trace_rays_host", fresh.ctx, rp, 4, hp, "no scene"),
+            ("gpuart_hip_trace_rays", fresh.ctx, rp, 4, hp, "no scene"),
+            ("gpuart_hip_pick", fresh.ctx, xyp, 4, hp, "no scene"),
+            ("gpuart_hip_trace_rays_host", be.ctx, None, 4, hp, "NULL"),
+            ("gpuart_hip_trace_rays_host", be.ctx, rp, 4, None, "NULL"),
+            ("gpuart_hip_trace_rays", be.ctx, off(rp, 4), 4, hp, "misaligned"),
+            ("gpuart_hip_trace_rays", be.ctx, rp, 4, off(hp, 4), "misaligned"),
+            ("gpuart_hip_trace_rays_host", be.ctx, off(rp, 2), 4, hp, "misaligned"),
+            ("gpuart_hip_trace_rays_host", be.ctx, rp, 2 ** 31, hp, "GPUART_HIP_MAX_RAYS"),
+            ("gpuart_hip_trace_rays", be.ctx, rp, 2 ** 40, hp, "GPUART_HIP_MAX_RAYS"),
+            ("gpuart_hip_pick", be.ctx, None, 4, hp, "NULL"),
+        ]
+        for name, ctx, src, n, h, msg in cases:
+            rc = call(name, ctx, src, n, h)
+            assert rc == ERR_ARG, (name, msg, rc)
+            assert msg in L.gpuart_hip_last_error().decode(), (name, msg, L.gpuart_hip_last_error())
+            assert (hits == 7.0).all(), (name, msg)
+        assert call("gpuart_hip_trace_rays_host", be.ctx, rp, 4, hp, extra_flags=2) == ERR_ARG
+        assert call("gpuart_hip_trace_rays_host", be.ctx, rp, 4, hp, prims=off(rp, 1)) == ERR_ARG
+        for bad in [(16, 0), (0, 8), (2 ** 32 - 1, 0)]:
+            xb = xy.copy()
+            xb[2] = bad
+            rc = call("gpuart_hip_pick", be.ctx, xb.ctypes.data_as(C.c_void_p), 4, hp)
+            assert rc == ERR_ARG and "outside" in L.gpuart_hip_last_error().decode() and (hits == 7.0).all()
+        with pytest.raises(B.HipError):
+            be.pick(np.array([[16, 0]]))
+        # no camera / no frame size (pick only)
+        nocam = B.Backend(0)
+        try:
+            nocam.upload_bvh(tree)
+            assert call("gpuart_hip_pick", nocam.ctx, xyp, 4, hp) == ERR_ARG and "frame size" in L.gpuart_hip_last_error().decode()
+            nocam.resize(16, 8)
+            assert call("gpuart_hip_pick", nocam.ctx, xyp, 4, hp) == ERR_ARG and "camera" in L.gpuart_hip_last_error().decode()
+            assert call("gpuart_hip_trace_rays_host", nocam.ctx, rp, 4, hp) == 0  # rays need neither
+        finally:
+            nocam.close()
+        assert (hits[4] == 7.0).all()
+        # n = 0 succeeds and touches nothing, NULL pointers included
+        hits[:] = 7.0
+        for name in NEW_HIP:
+            assert call(name, be.ctx, None, 0, None) == 0
+        assert (hits == 7.0).all()
+        assert call("gpuart_hip_trace_rays_host", be.ctx, rp, 4, hp) == 0 and not (hits[:4] == 7.0).all() and (hits[4] == 7.0).all()
+    finally:
+        fresh.close()
