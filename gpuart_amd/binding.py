@@ -345,6 +345,13 @@ def gather_all_read(backends, which, divide_by, root, W, H):
     return out
 
 
+def _library_symbols(path):
+    """{address: name} of a shared library's symbol table (nm; local symbols included)."""
+    import subprocess
+    out = subprocess.run(["nm", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+    return {int(f[0], 16): f[2] for f in (line.split() for line in out.splitlines()) if len(f) == 3}
+
+
 class HipError(RuntimeError):
     """A gpuart_hip_* call returned an error; `code` is the library's (GPUART_HIP_ERR_*: -4 a bounded wait ran out)."""
     code = None
@@ -493,6 +500,19 @@ class Backend:
     def test_stall(self, ms):
         """Keeps the context's primary stream busy for `ms` milliseconds (what a missing peer looks like to the bounded waits)."""
         self._chk(self.L.gpuart_hip_test_stall(self.ctx, C.c_uint32(int(ms))))
+
+    def launched(self, reset=True):
+        """Test build only: the set of product kernels launched on this context since the ledger was last reset (gpuart_hip_test_launches),
+        by their code-object symbols (mangled, without ".kd"); reset=True empties the ledger."""
+        n = C.c_size_t(0)
+        self._chk(self.L.gpuart_hip_test_launches(self.ctx, None, C.c_size_t(0), C.byref(n), C.c_int(0)))
+        buf = C.create_string_buffer(n.value + 1)
+        self._chk(self.L.gpuart_hip_test_launches(self.ctx, buf, C.c_size_t(n.value + 1), C.byref(n), C.c_int(1 if reset else 0)))
+        names = set(buf.value.decode().split())
+        if any(x.startswith("@") for x in names):  # the runtime could not name a kernel: its host handle's symbol in this library
+            syms = _library_symbols(self.L._name)
+            names = {syms.get(int(x[1:], 16), x) if x.startswith("@") else x for x in names}
+        return names
 
     MODE_WAVEFRONT, MODE_REFERENCE_WORK, MODE_MEGAKERNEL = 0, 1, 2
 

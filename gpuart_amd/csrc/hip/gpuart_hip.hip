@@ -1,6 +1,7 @@
 // gpuart_hip.hip — context, scheduling and the C-ABI launcher of libgpuart_hip.so (gfx950 only); the kernels live in
 // kernels_pipeline.h / kernels_test.h, the tree re-layout in converter.h.
 // See include/gpuart_hip.h for the boundary and DESIGN.md for layout / kernel notes.
+#include <dlfcn.h>
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -174,9 +175,23 @@ struct gpuart_hip_ctx {
     uint32_t gather_timeout_ms = 60000;  ///< GPUART_HIP_GATHER_TIMEOUT_MS: bound on the host-side wait for the peers (0: none)
     bool abandoned = false;           ///< a bounded wait on the primary stream ran out: what is queued there may never complete, so
                                       ///< every later wait of this context (comm_destroy, destroy) is bounded too
+#ifdef GPUART_HIP_TEST_HOOKS
+    std::vector<const void *> launched;  ///< launch ledger (gpuart_hip_test_launches): host handles of the kernels launched, each once
+#endif
 };
 
 namespace {
+
+// The launch ledger of the test build: every launch site of a product kernel notes the kernel's host handle on its context
+// (gpuart_hip_test_launches names them); in the product build GD_LEDGER is nothing at all.
+#ifdef GPUART_HIP_TEST_HOOKS
+void ledger_note(gpuart_hip_ctx *c, const void *kernel) {
+    if (std::find(c->launched.begin(), c->launched.end(), kernel) == c->launched.end()) c->launched.push_back(kernel);
+}
+#define GD_LEDGER(c, ...) ledger_note((c), reinterpret_cast<const void *>(&__VA_ARGS__))
+#else
+#define GD_LEDGER(c, ...) ((void)0)
+#endif
 
 /// Waits for everything this context has enqueued, on all of its streams.
 int drain(gpuart_hip_ctx *c) {
@@ -615,8 +630,10 @@ int gpuart_hip_render_direct(gpuart_hip_ctx *c, const gpuart_params *p) {
     TimedLaunch t;
     if ((r = begin_timed(c, t, 0))) return r;
     if (c->plan.mode == 1) {
+        GD_LEDGER(c, k_direct<true>);
         k_direct<true><<<grid, BLOCK, 0, c->stream>>>(sc, c->frame, *p, c->plan.n_slots, c->d_direct, c->d_spill, c->d_counters);
     } else if (c->plan.mode == 2) {
+        GD_LEDGER(c, k_direct<false>);
         k_direct<false><<<grid, BLOCK, 0, c->stream>>>(sc, c->frame, *p, c->plan.n_slots, c->d_direct, c->d_spill, c->d_counters);
     } else {
         // fast mode: persistent lanes, one pixel at a time per lane (kernels_pipeline.h)
@@ -630,10 +647,16 @@ int gpuart_hip_render_direct(gpuart_hip_ctx *c, const gpuart_params *p) {
         if (!c->chunk_from_env && c->plan.n_slots / ((size_t)c->direct_waves * 8) < 128) dtune.chunk = 64;
         const bool flat_only = c->lean_kernels && !c->exact_boxes && (c->type_mask & ~(uint32_t)GD_FLAT_TYPES) == 0;
         const bool round_only = c->lean_kernels && !c->exact_boxes && !flat_only && (c->type_mask & ~(uint32_t)GD_ROUND_TYPES) == 0;
-        if (c->exact_boxes) k_direct_persistent<GD_ALL_TYPES | GD_EXACT_BOXES><<<pgrid, BLOCK, 0, c->stream>>>(sc, c->frame, *p, c->plan.n_slots, c->d_direct, c->d_spill, c->d_cursor, dtune);
-        else if (flat_only) k_direct_persistent<GD_FLAT_TYPES><<<pgrid, BLOCK, 0, c->stream>>>(sc, c->frame, *p, c->plan.n_slots, c->d_direct, c->d_spill, c->d_cursor, dtune);
-        else if (round_only) k_direct_persistent<GD_ROUND_TYPES><<<pgrid, BLOCK, 0, c->stream>>>(sc, c->frame, *p, c->plan.n_slots, c->d_direct, c->d_spill, c->d_cursor, dtune);
-        else k_direct_persistent<GD_ALL_TYPES><<<pgrid, BLOCK, 0, c->stream>>>(sc, c->frame, *p, c->plan.n_slots, c->d_direct, c->d_spill, c->d_cursor, dtune);
+#define GD_LAUNCH_DIRECT(T)                                                                                                    \
+    do {                                                                                                                       \
+        GD_LEDGER(c, k_direct_persistent<T>);                                                                                  \
+        k_direct_persistent<T><<<pgrid, BLOCK, 0, c->stream>>>(sc, c->frame, *p, c->plan.n_slots, c->d_direct, c->d_spill, c->d_cursor, dtune); \
+    } while (0)
+        if (c->exact_boxes) GD_LAUNCH_DIRECT(GD_ALL_TYPES | GD_EXACT_BOXES);
+        else if (flat_only) GD_LAUNCH_DIRECT(GD_FLAT_TYPES);
+        else if (round_only) GD_LAUNCH_DIRECT(GD_ROUND_TYPES);
+        else GD_LAUNCH_DIRECT(GD_ALL_TYPES);
+#undef GD_LAUNCH_DIRECT
     }
     HIP_TRY(hipGetLastError());
     return end_timed(c, t);
@@ -722,6 +745,7 @@ int sort_tile_order(gpuart_hip_ctx *c, PassLane &l) {
     for (auto &o : c->lanes) if (&o != &l && o.used) HIP_TRY(hipStreamWaitEvent(l.main, o.ev_done, 0));
     c->order_next = c->order_cur == 0 ? 1 : 0;
     const size_t tiles = (size_t)((c->frame.tw + 7) / 8) * ((c->frame.th + 7) / 8);
+    GD_LEDGER(c, k_tile_order);
     k_tile_order<<<1, TO_THREADS, 0, l.main>>>(c->d_tile_cost, c->d_tile_order[c->order_next], (uint32_t)tiles);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c->ev_order, l.main));
@@ -762,7 +786,7 @@ int launch_run_persistent(gpuart_hip_ctx *c, PassLane &l, size_t first, size_t c
         TimedLaunch tt;
         HIP_TRY(hipMemsetAsync(l.run_cursor, 0, sizeof(uint32_t), l.main));
         if (c->timing_level >= 2 && (r = begin_timed(c, tt, 1, l.main))) return r;
-#define GD_LAUNCH_RUN(C, R, T) k_run<C, R, T><<<grid, BLOCK, 0, l.main>>>(sc, fr, *p, seeds, b, j, npaths, l.passcolor, l.spill_main, c->d_counters, c->tune, l.run_cursor)
+#define GD_LAUNCH_RUN(C, R, T) do { GD_LEDGER(c, k_run<C, R, T>); k_run<C, R, T><<<grid, BLOCK, 0, l.main>>>(sc, fr, *p, seeds, b, j, npaths, l.passcolor, l.spill_main, c->d_counters, c->tune, l.run_cursor); } while (0)
 #define GD_LAUNCH_RUN_ORD(C, T) do { if (c->ref_order) GD_LAUNCH_RUN(C, false, (T) | GD_REF_ORDER); else GD_LAUNCH_RUN(C, false, T); } while (0)
         if (c->plan.mode == 1 && exact) GD_LAUNCH_RUN(true, true, GD_ALL_TYPES | GD_EXACT_BOXES);
         else if (c->plan.mode == 1) GD_LAUNCH_RUN(true, true, GD_ALL_TYPES);
@@ -780,6 +804,7 @@ int launch_run_persistent(gpuart_hip_ctx *c, PassLane &l, size_t first, size_t c
     if ((r = end_timed(c, t, l.main))) return r;
     HIP_TRY(hipEventRecord(l.ev_done, l.main));
     HIP_TRY(hipStreamWaitEvent(c->stream, l.ev_done, 0));
+    GD_LEDGER(c, k_accumulate);
     k_accumulate<<<dim3((unsigned)((c->plan.tile_pixels + 255) / 256)), 256, 0, c->stream>>>(c->d_accum, l.passcolor, c->plan.tile_pixels, b.batch);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(l.ev_free, c->stream));
@@ -823,7 +848,7 @@ int launch_run(gpuart_hip_ctx *c, size_t first, size_t count) {
         TimedLaunch tt;
         int rr;
         if (detail && (rr = begin_timed(c, tt, 1, l.main))) return rr;
-#define GD_LAUNCH_TRACE(T) k_trace<false, T><<<pgrid, BLOCK, 0, l.main>>>(sc, fr, *p, b, seg_c, seg_s, 1, j_cur, npaths, l.passcolor, l.spill_main, c->d_counters, c->tune)
+#define GD_LAUNCH_TRACE(T) do { GD_LEDGER(c, k_trace<false, T>); k_trace<false, T><<<pgrid, BLOCK, 0, l.main>>>(sc, fr, *p, b, seg_c, seg_s, 1, j_cur, npaths, l.passcolor, l.spill_main, c->d_counters, c->tune); } while (0)
 #define GD_LAUNCH_TRACE_ORD(T) do { if (c->ref_order) GD_LAUNCH_TRACE((T) | GD_REF_ORDER); else GD_LAUNCH_TRACE(T); } while (0)
         if (c->exact_boxes) GD_LAUNCH_TRACE(GD_ALL_TYPES | GD_EXACT_BOXES);
         else if (flat_only) GD_LAUNCH_TRACE_ORD(GD_FLAT_TYPES);
@@ -838,9 +863,11 @@ int launch_run(gpuart_hip_ctx *c, size_t first, size_t count) {
         j_cur = j;
         HIP_TRY(hipMemsetAsync(b.counters, 0, 4 * ((size_t)nseg + 1) * sizeof(uint32_t), l.main));
         if (c->tune.xcd_queues) HIP_TRY(hipMemsetAsync(b.xcd_cursors, 0, 16 * ((size_t)nseg + 1) * sizeof(uint32_t), l.main));
+        GD_LEDGER(c, k_gen);
         k_gen<<<sgrid, BLOCK, 0, l.main>>>(fr, *p, seeds, j, npaths, b, l.passcolor);
         if (nseg && (r = trace(0, -1))) return r;
         for (uint32_t seg = 0; seg < nseg; seg++) {
+            GD_LEDGER(c, k_shade<false>);
             k_shade<false><<<sgrid, BLOCK, 0, l.main>>>(sc, fr, *p, seeds, b, (int)seg, (int)nseg, j, npaths, l.passcolor, c->d_counters);
             // the Sun-shadow queries of this segment travel with the closest-hit queries of the next one
             const int next_c = seg + 1 < nseg ? (int)seg + 1 : -1, sh = p->sunEnabled == 1 ? (int)seg : -1;
@@ -852,6 +879,7 @@ int launch_run(gpuart_hip_ctx *c, size_t first, size_t count) {
     // accumulate in pass order on the primary stream, then release the lane
     HIP_TRY(hipEventRecord(l.ev_done, l.main));
     HIP_TRY(hipStreamWaitEvent(c->stream, l.ev_done, 0));
+    GD_LEDGER(c, k_accumulate);
     k_accumulate<<<dim3((unsigned)((c->plan.tile_pixels + 255) / 256)), 256, 0, c->stream>>>(c->d_accum, l.passcolor, c->plan.tile_pixels, b.batch);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(l.ev_free, c->stream));
@@ -895,6 +923,7 @@ int gpuart_hip_pt_pass(gpuart_hip_ctx *c, const gpuart_params *p, const float ra
         TimedLaunch t;
         if ((r = begin_timed(c, t, 0))) return r;
         dim3 grid(std::min<uint32_t>(c->grid_waves, c->plan.n_slots / BLOCK));
+        GD_LEDGER(c, k_pt_mega<false>);
         k_pt_mega<false><<<grid, BLOCK, 0, c->stream>>>(sc, c->frame, *p, seed, npaths, c->plan.n_slots, c->d_accum, c->d_spill, c->d_counters);
         HIP_TRY(hipGetLastError());
         return end_timed(c, t);
@@ -922,6 +951,7 @@ int gpuart_hip_export(gpuart_hip_ctx *c, int which, void *rgba_device, float div
     const float4 *src = which == 0 ? c->d_direct : c->d_accum;
     if (!(divide_by > 0)) divide_by = 1.0f;
     size_t n = c->plan.tile_pixels;
+    GD_LEDGER(c, k_scale_copy);
     k_scale_copy<<<dim3((unsigned)((n + 255) / 256)), 256, 0, c->stream>>>(src, (float4 *)rgba_device, n, divide_by);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1080,8 +1110,13 @@ static int launch_ray_query(gpuart_hip_ctx *c, const RayQuery &q, int source) {
     const bool round_only = c->lean_kernels && !c->exact_boxes && !flat_only && (c->type_mask & ~(uint32_t)GD_ROUND_TYPES) == 0;
 #define GD_LAUNCH_QUERY(T)                                                                                                       \
     do {                                                                                                                         \
-        if (source == RQ_PIXELS) k_ray_query<T, RQ_PIXELS><<<grid, BLOCK, 0, c->stream>>>(sc, c->frame, q, c->d_spill, c->d_query_cursor, tune); \
-        else k_ray_query<T, RQ_RAYS><<<grid, BLOCK, 0, c->stream>>>(sc, c->frame, q, c->d_spill, c->d_query_cursor, tune);               \
+        if (source == RQ_PIXELS) {                                                                                               \
+            GD_LEDGER(c, k_ray_query<T, RQ_PIXELS>);                                                                             \
+            k_ray_query<T, RQ_PIXELS><<<grid, BLOCK, 0, c->stream>>>(sc, c->frame, q, c->d_spill, c->d_query_cursor, tune);      \
+        } else {                                                                                                                 \
+            GD_LEDGER(c, k_ray_query<T, RQ_RAYS>);                                                                               \
+            k_ray_query<T, RQ_RAYS><<<grid, BLOCK, 0, c->stream>>>(sc, c->frame, q, c->d_spill, c->d_query_cursor, tune);        \
+        }                                                                                                                        \
     } while (0)
     if (c->exact_boxes) GD_LAUNCH_QUERY(GD_ALL_TYPES | GD_EXACT_BOXES);
     else if (flat_only) GD_LAUNCH_QUERY(GD_FLAT_TYPES);
@@ -1447,6 +1482,7 @@ int gather_place(gpuart_hip_ctx *c, const std::vector<GatherHello> &all, float4 
         const gpuart_tile_geom &g = all[k].g;
         const size_t cnt = (size_t)g.tw * g.th;
         const float4 *src = (int)k == c->comm_rank ? c->d_send : c->d_stage + off;
+        if (cnt) GD_LEDGER(c, k_scatter_rows);
         if (cnt) k_scatter_rows<<<dim3((unsigned)((cnt + 255) / 256)), 256, 0, c->stream>>>(g, src, full);
         off += cnt;
     }
@@ -1866,6 +1902,33 @@ int gpuart_hip_test_stall(gpuart_hip_ctx *c, uint32_t ms) {
     HIP_TRY(hipSetDevice(c->device));
     k_test_stall<<<1, 64, 0, c->stream>>>((unsigned long long)ms * 100000ull, nullptr);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+#endif
+
+#ifdef GPUART_HIP_TEST_HOOKS
+int gpuart_hip_test_launches(gpuart_hip_ctx *c, char *buf, size_t cap, size_t *len, int reset) {
+    if (!c || !len || (cap && !buf)) return fail(GPUART_HIP_ERR_ARG, "bad argument");
+    std::string s;
+    for (const void *k : c->launched) {
+        const char *name = hipKernelNameRefByPtr(k, c->stream);
+        if (name && name[0]) {
+            s += name;
+        } else {  // the runtime cannot name it: where its handle lies in this library (the binding looks the offset up in the symbol table)
+            Dl_info di{};
+            char off[32];
+            snprintf(off, sizeof off, "@%zx", dladdr(k, &di) ? (size_t)((const char *)k - (const char *)di.dli_fbase) : (size_t)0);
+            s += off;
+        }
+        s += '\n';
+    }
+    (void)hipGetLastError();  // a failed lookup must not surface as the error of a later launch
+    *len = s.size();
+    if (!buf) return 0;
+    if (cap < s.size() + 1) return fail(GPUART_HIP_ERR_ARG, "launch ledger: the buffer holds " + std::to_string(cap) + " bytes, " +
+                                        std::to_string(s.size() + 1) + " needed");
+    memcpy(buf, s.c_str(), s.size() + 1);
+    if (reset) c->launched.clear();
     return 0;
 }
 #endif

@@ -75,6 +75,13 @@ int gpuart_hip_test_current_tile_order(gpuart_hip_ctx *ctx, uint32_t *order, siz
  * what a peer that has not arrived looks like to the bounded waits of gpuart_hip_gather / gpuart_hip_wait, on one GPU. */
 int gpuart_hip_test_stall(gpuart_hip_ctx *ctx, uint32_t ms);
 
+/* The launch ledger: every product kernel launched on this context since the ledger was last reset, each once, as newline-terminated
+ * names — the kernels' symbols in the code object (mangled, without ".kd"), or "@<hex offset>" of the kernel's host handle in this
+ * library where the HIP runtime cannot name it. Every launch site of the library notes its kernel (test builds only; the k_test_*
+ * kernels of the hooks are not noted). *len = the length of that text; buf == NULL asks for the length only. Otherwise buf (cap bytes)
+ * receives the text and a NUL, GPUART_HIP_ERR_ARG if it does not fit, and reset != 0 then empties the ledger. */
+int gpuart_hip_test_launches(gpuart_hip_ctx *ctx, char *buf, size_t cap, size_t *len, int reset);
+
 /* ---- device-function test hooks (parity tests call the device code through these) ----------
  * Arrays are n x 4 float32 in host memory. Each mirrors one reference GLSL function. */
 int gpuart_hip_test_random(gpuart_hip_ctx *ctx, const float *in, int n, float *out);
