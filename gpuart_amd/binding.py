@@ -13,6 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIBDIR = os.environ.get("GPUART_LIBDIR") or os.path.join(HERE, "lib")  # override: A/B runs of differently built libraries
 HIP_LIB = os.path.join(LIBDIR, "libgpuart_hip.so")
 HOST_LIB = os.path.join(LIBDIR, "libgpuart.so")
+DENOISE_LIB = os.path.join(LIBDIR, "libgpuart_denoise.so")
 
 
 class NativeLibraryMissing(RuntimeError):
@@ -51,6 +52,24 @@ class RayHit(C.Structure):
 # the same record as a NumPy dtype: what trace_rays / pick return for host arrays (hits.view(np.float32).reshape(-1, 8): the raw words)
 RAY_HIT = np.dtype([("pos", np.float32), ("p", np.float32, 3), ("n", np.float32, 3), ("type", np.int32)])
 RAYS_OCCLUSION = 1  # GPUART_HIP_RAYS_OCCLUSION
+
+
+class DenoiseParams(C.Structure):
+    """gpuart_denoise_params (include/gpuart_denoise.h)."""
+    _fields_ = [("iterations", C.c_uint32), ("lum_k", C.c_float), ("normal_pow2", C.c_uint32), ("depth_sigma", C.c_float)]
+
+
+DENOISE_DEFAULTS = dict(iterations=5, lum_k=4.0, normal_pow2=5, depth_sigma=0.05)
+
+
+def denoise_params(params):
+    """None (the library's defaults), a DenoiseParams, or a dict of fields that replace the defaults -> DenoiseParams or None."""
+    if params is None or isinstance(params, DenoiseParams):
+        return params
+    unknown = set(params) - set(DENOISE_DEFAULTS)
+    if unknown:
+        raise ValueError("unknown denoiser parameters: %s" % sorted(unknown))
+    return DenoiseParams(**dict(DENOISE_DEFAULTS, **params))
 
 
 def _user_sphere(us):
@@ -103,6 +122,21 @@ def hip_lib():
         L.gpuart_hip_frame_row.restype = C.c_uint32
         _hip = L
     return _hip
+
+
+_denoise = None
+
+
+def denoise_lib():
+    """libgpuart_denoise.so; raises NativeLibraryMissing if it has not been built (no fallback)."""
+    global _denoise
+    if _denoise is None:
+        if not os.path.exists(DENOISE_LIB):
+            raise NativeLibraryMissing("%s not found — run make -C gpuart_amd/csrc; there is no CPU fallback" % DENOISE_LIB)
+        L = C.CDLL(DENOISE_LIB)
+        L.gpuart_denoise_last_error.restype = C.c_char_p
+        _denoise = L
+    return _denoise
 
 
 def host_lib():
@@ -362,6 +396,7 @@ class Backend:
 
     def __init__(self, device=0, borrowed=None):
         self.L = hip_lib()
+        self.device = device
         self.owned = borrowed is None
         if borrowed is None:
             ctx = C.c_void_p()
@@ -598,6 +633,41 @@ class Backend:
                                          _p(prims) if prims is not None else None))
         return (hits, prims) if want_prims else hits
 
+    def gbuffer(self, user_sphere=None, out=None, prims_out=None):
+        """gpuart_hip_gbuffer: the record and ordinal pick returns for every pixel of the context's tile, in the tile's local order
+        (row 0 = bottom) -> (hits, prims). With torch tensors `out` ((th, tw, 8) float32) and `prims_out` ((th, tw) int32) on this
+        context's device they are written in place (torch's current stream is synchronised first, the context before returning); the
+        returned hits are then that tensor. Otherwise a RAY_HIT record array (th, tw) and an int32 array (th, tw), written into the
+        NumPy arrays `out` / `prims_out` when given."""
+        import torch
+        _, _, tw, th = self.tile
+        dev = torch.device("cuda", self.device)
+        on_device = out is not None and type(out).__module__.startswith("torch")
+        if on_device:
+            if out.dtype != torch.float32 or tuple(out.shape) != (th, tw, 8) or not out.is_contiguous() or out.device != dev:
+                raise ValueError("out must be a contiguous (%d, %d, 8) float32 tensor on %s" % (th, tw, dev))
+            hits = out
+            prims = prims_out if prims_out is not None else torch.empty((th, tw), dtype=torch.int32, device=dev)
+            if prims.dtype != torch.int32 or tuple(prims.shape) != (th, tw) or not prims.is_contiguous() or prims.device != dev:
+                raise ValueError("prims_out must be a contiguous (%d, %d) int32 tensor on %s" % (th, tw, dev))
+        else:
+            hits = torch.empty((th, tw, 8), dtype=torch.float32, device=dev)
+            prims = torch.empty((th, tw), dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        self._chk(self.L.gpuart_hip_gbuffer(self.ctx, _user_sphere(user_sphere), C.c_void_p(hits.data_ptr()), C.c_void_p(prims.data_ptr())))
+        self.finish()
+        if on_device:
+            return hits, prims
+        h = np.ascontiguousarray(hits.cpu().numpy()).view(RAY_HIT).reshape(th, tw)
+        p = prims.cpu().numpy()
+        if out is not None:
+            out.reshape(-1).view(np.uint8)[:] = h.reshape(-1).view(np.uint8)
+            h = out
+        if prims_out is not None:
+            prims_out[...] = p
+            p = prims_out
+        return h, p
+
     # test hooks
     def _hook(self, name, ins, nout, *extra):
         ins = [np.ascontiguousarray(a, np.float32) for a in ins]
@@ -661,7 +731,7 @@ class Renderer:
             self.L.gpuart_renderer_destroy(self.h)
             self.h = None
             raise HipError("Renderer initialisation failed: " + msg)
-        self.backend = Backend(borrowed=self.L.gpuart_renderer_backend(self.h))
+        self.backend = Backend(device=device, borrowed=self.L.gpuart_renderer_backend(self.h))
         self.backend.tile = self.tile
 
     def close(self):
@@ -739,6 +809,16 @@ class Renderer:
             raise HipError("read_radiance failed")
         return out
 
+    def read_denoised(self, params=None):
+        """Renderer::ReadDenoised: the denoised preview of the normalised accumulator, (th, tw, 4) float32; params as Denoiser.run."""
+        _, _, tw, th = self.tile
+        out = np.empty((th, tw, 4), np.float32)
+        p = denoise_params(params)
+        if not self.L.gpuart_renderer_read_denoised(self.h, _p(out), C.byref(p) if p is not None else None):
+            raise HipError("read_denoised failed: %s / %s" % (hip_lib().gpuart_hip_last_error().decode(),
+                                                              denoise_lib().gpuart_denoise_last_error().decode()))
+        return out
+
     def finish(self): return bool(self.L.gpuart_renderer_finish(self.h))
 
     def trace_rays(self, rays, occlusion=False, user_sphere=True, want_prims=False):
@@ -778,3 +858,81 @@ class Renderer:
         p = Params()
         self.L.gpuart_renderer_params(self.h, C.byref(p))
         return p
+
+
+# ---- the denoiser (include/gpuart_denoise.h) ------------------------------------------------------------------------------
+class DenoiseError(RuntimeError):
+    """A gpuart_denoise_* call returned an error; `code` is the library's (GPUART_HIP_ERR_*)."""
+    code = None
+
+
+class Denoiser:
+    """A gpuart_denoise handle on one device."""
+
+    def __init__(self, device=0):
+        self.L = denoise_lib()
+        self.device = device
+        h = C.c_void_p()
+        self._chk(self.L.gpuart_denoise_create(C.c_int(device), C.byref(h)))
+        self.h = h
+
+    def _chk(self, rc):
+        if rc != 0:
+            e = DenoiseError("gpuart_denoise error %d: %s" % (rc, self.L.gpuart_denoise_last_error().decode()))
+            e.code = rc
+            raise e
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.gpuart_denoise_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self, rgba, hits, prims, us_flags=0, params=None, out=None):
+        """Filters radiance rgba (h, w, 4) float32 guided by a G-buffer: hits = the (h, w) RAY_HIT records or their (h, w, 8) float32 words,
+        prims (h, w) int32 (Backend.gbuffer gives both); us_flags = the user sphere's flags (1 emissive, 2 specular); params = None (the
+        defaults), a DenoiseParams or a dict of fields that replace the defaults. torch tensors on this handle's device run in place
+        through gpuart_denoise_run (torch's current stream is synchronised first, the handle before returning) and the result is `out`
+        or a new tensor; NumPy arrays run through gpuart_denoise_run_host and the result is `out` or a new array."""
+        p = denoise_params(params)
+        pp = C.byref(p) if p is not None else None
+        if type(rgba).__module__.startswith("torch"):
+            import torch
+            dev = torch.device("cuda", self.device)
+            if rgba.dtype != torch.float32 or rgba.dim() != 3 or rgba.shape[2] != 4 or not rgba.is_contiguous() or rgba.device != dev:
+                raise ValueError("rgba must be a contiguous (h, w, 4) float32 tensor on %s" % dev)
+            h, w = rgba.shape[0], rgba.shape[1]
+            if hits.dtype != torch.float32 or hits.numel() != h * w * 8 or not hits.is_contiguous() or hits.device != dev:
+                raise ValueError("hits must be a contiguous (h, w, 8) float32 tensor on %s" % dev)
+            if prims.dtype != torch.int32 or prims.numel() != h * w or not prims.is_contiguous() or prims.device != dev:
+                raise ValueError("prims must be a contiguous (h, w) int32 tensor on %s" % dev)
+            res = out if out is not None else torch.empty_like(rgba)
+            if res.dtype != torch.float32 or tuple(res.shape) != (h, w, 4) or not res.is_contiguous() or res.device != dev:
+                raise ValueError("out must be a contiguous (h, w, 4) float32 tensor on %s" % dev)
+            torch.cuda.current_stream(dev).synchronize()
+            self._chk(self.L.gpuart_denoise_run(self.h, C.c_void_p(rgba.data_ptr()), C.c_void_p(hits.data_ptr()), C.c_void_p(prims.data_ptr()),
+                                                C.c_uint32(us_flags), C.c_uint32(w), C.c_uint32(h), pp, C.c_void_p(res.data_ptr())))
+            self.finish()
+            return res
+        rgba = np.ascontiguousarray(rgba, np.float32)
+        if rgba.ndim != 3 or rgba.shape[2] != 4:
+            raise ValueError("rgba must be (h, w, 4) float32")
+        h, w = rgba.shape[:2]
+        hits = np.ascontiguousarray(hits)
+        prims = np.ascontiguousarray(prims, np.int32)
+        if hits.nbytes != h * w * 32 or prims.size != h * w:
+            raise ValueError("hits must hold h*w 32-byte records and prims h*w ordinals")
+        res = out if out is not None else np.empty_like(rgba)
+        if res.dtype != np.float32 or res.shape != (h, w, 4) or not res.flags.c_contiguous:
+            raise ValueError("out must be a contiguous (h, w, 4) float32 array")
+        self._chk(self.L.gpuart_denoise_run_host(self.h, _p(rgba), _p(hits), _p(prims), C.c_uint32(us_flags), C.c_uint32(w), C.c_uint32(h),
+                                                 pp, _p(res)))
+        return res
+
+    def finish(self):
+        self._chk(self.L.gpuart_denoise_finish(self.h))

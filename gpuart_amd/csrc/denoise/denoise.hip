@@ -1,0 +1,328 @@
+// denoise.hip — libgpuart_denoise.so (gfx950): the edge-aware à-trous denoiser of include/gpuart_denoise.h, which states the
+// filter operation by operation. Built without flushing fp32 denormals, with IEEE '/' and sqrt and no contraction, so that every
+// value is the one tests/denoise_ref.py computes in NumPy float32. DESIGN.md "Denoiser" describes the kernels.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <string>
+
+#include "gpuart_denoise.h"
+
+namespace {
+
+thread_local std::string g_last_error;
+
+int fail(int code, const std::string &msg) {
+    g_last_error = msg;
+    return code;
+}
+
+#define HIP_TRY(expr)                                                                              \
+    do {                                                                                           \
+        hipError_t e_ = (expr);                                                                    \
+        if (e_ != hipSuccess)                                                                      \
+            return fail(GPUART_HIP_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+#define DN_FN __device__ __forceinline__
+
+constexpr uint32_t US_EM_NONZERO = 1u, US_SPECULAR = 2u;  // userSphereFlags bits that take a user-sphere pixel out of the filter
+
+/// max(a, b) as the header states it: a > b ? a : b
+DN_FN float gt_or(float a, float b) { return a > b ? a : b; }
+
+DN_FN float lum(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
+
+/// the reference's PRIMITIVE_COLOR (shaders/path_tracing.glsl:123-126); the user sphere has type 0
+DN_FN float3 albedo(int type) {
+    if (type == 0) return make_float3(0.65f, 0.4f, 0.35f);
+    if (type == 1) return make_float3(0.1f, 0.2f, 0.1f);
+    return make_float3(0.3f, 0.3f, 0.3f);
+}
+
+/// Pixel i's class: its primitive type when it is a surface pixel, -1 otherwise.
+DN_FN int surface_type(const float4 *hits, const int32_t *prims, uint32_t us_flags, size_t i) {
+    const int type = __float_as_int(hits[2 * i + 1].w);
+    if (type < 0) return -1;
+    if (prims[i] == -2 && (us_flags & (US_EM_NONZERO | US_SPECULAR))) return -1;
+    return type & 3;
+}
+
+// ---- steps 1 and 2: demodulation, luminance and the 7x7 variance ---------------------------------------------------------------
+// A 16 x 16 block classifies and demodulates its 22 x 22 window (the block and a 3-pixel apron) into LDS once; every pixel then sums
+// its 49 neighbours from there. Output per surface pixel: the state {x.rgb, var} and the guide {n.xyz, pos}. A guide whose pos is NaN
+// marks a pixel that is not a surface pixel (a closest hit's pos is never NaN: it won a comparison).
+constexpr int PT = 16, PR = 3, PS = PT + 2 * PR;
+
+__global__ void __launch_bounds__(PT * PT) k_dn_prepare(const float4 *rgba, const float4 *hits, const int32_t *prims, uint32_t us_flags,
+                                                        int w, int h, float4 *state, float4 *guide) {
+    __shared__ float s_lum[PS * PS];
+    __shared__ int s_surf[PS * PS];
+    const int bx = blockIdx.x * PT - PR, by = blockIdx.y * PT - PR;
+    for (int k = threadIdx.y * PT + threadIdx.x; k < PS * PS; k += PT * PT) {
+        const int gx = bx + k % PS, gy = by + k / PS;
+        int type = -1;
+        float L = 0.0f;
+        if (gx >= 0 && gx < w && gy >= 0 && gy < h) {
+            const size_t i = (size_t)gy * w + gx;
+            type = surface_type(hits, prims, us_flags, i);
+            if (type >= 0) {
+                const float4 c = rgba[i];
+                const float3 a = albedo(type);
+                L = lum(c.x / a.x, c.y / a.y, c.z / a.z);
+            }
+        }
+        s_lum[k] = L;
+        s_surf[k] = type >= 0;
+    }
+    __syncthreads();
+    const int x = blockIdx.x * PT + threadIdx.x, y = blockIdx.y * PT + threadIdx.y;
+    if (x >= w || y >= h) return;
+    const size_t i = (size_t)y * w + x;
+    const int type = surface_type(hits, prims, us_flags, i);
+    if (type < 0) {
+        guide[i] = make_float4(0.0f, 0.0f, 0.0f, __builtin_nanf(""));
+        return;
+    }
+    float cnt = 0.0f, m1 = 0.0f, m2 = 0.0f;
+    for (int dy = 0; dy <= 2 * PR; dy++)
+        for (int dx = 0; dx <= 2 * PR; dx++) {
+            const int k = (threadIdx.y + dy) * PS + threadIdx.x + dx;
+            if (!s_surf[k]) continue;  // (a pixel outside the tile is not a surface pixel)
+            const float L = s_lum[k];
+            cnt += 1.0f;
+            m1 += L;
+            m2 += L * L;
+        }
+    const float mean = m1 / cnt;
+    const float var = gt_or(m2 / cnt - mean * mean, 0.0f);
+    const float4 c = rgba[i];
+    const float3 a = albedo(type);
+    state[i] = make_float4(c.x / a.x, c.y / a.y, c.z / a.z, var);
+    const float4 h0 = hits[2 * i], h1 = hits[2 * i + 1];
+    guide[i] = make_float4(h1.x, h1.y, h1.z, h0.x);
+}
+
+// ---- steps 3 and 4: one à-trous level; the last one remodulates ---------------------------------------------------------------
+// A 64 x 4 block: a wave is a row segment of 64 pixels, so every tap of a wave reads 64 consecutive records (2 x 1 KiB).
+struct Level {
+    float lum_k, depth_sigma, step;
+    int s;
+    uint32_t normal_pow2;
+};
+
+constexpr int AX = 64, AY = 4;
+
+template <bool LAST>
+__global__ void __launch_bounds__(AX * AY) k_dn_atrous(const float4 *st_in, const float4 *guide, float4 *st_out, int w, int h, Level lv,
+                                                       const float4 *rgba, const float4 *hits, float4 *out) {
+    const int x = blockIdx.x * AX + threadIdx.x, y = blockIdx.y * AY + threadIdx.y;
+    if (x >= w || y >= h) return;
+    const size_t i = (size_t)y * w + x;
+    const float4 gp = guide[i];
+    if (!(gp.w == gp.w)) {  // not a surface pixel: copied through by the last level, never a tap
+        if (LAST) out[i] = rgba[i];
+        return;
+    }
+    const float H[5] = {1.0f / 16, 1.0f / 4, 3.0f / 8, 1.0f / 4, 1.0f / 16};
+    const float4 xp = st_in[i];
+    const float Lp = lum(xp.x, xp.y, xp.z);
+    const float sd = sqrtf(xp.w) * lv.lum_k + 1e-4f;
+    const float zs = (lv.depth_sigma * gt_or(gp.w, 1e-6f)) * lv.step;
+    float nr = 0.0f, ng = 0.0f, nb = 0.0f, den = 0.0f, nv = 0.0f;
+    for (int dy = -2; dy <= 2; dy++) {
+        const int qy = y + lv.s * dy;
+        if (qy < 0 || qy >= h) continue;
+        for (int dx = -2; dx <= 2; dx++) {
+            const int qx = x + lv.s * dx;
+            if (qx < 0 || qx >= w) continue;
+            const size_t q = (size_t)qy * w + qx;
+            const float4 gq = guide[q];
+            if (!(gq.w == gq.w)) continue;
+            const float4 xq = st_in[q];
+            const float hk = H[dy + 2] * H[dx + 2];
+            const float e = (lum(xq.x, xq.y, xq.z) - Lp) / sd;
+            const float wl = 1.0f / (1.0f + e * e);
+            float wn = gt_or((gp.x * gq.x + gp.y * gq.y) + gp.z * gq.z, 0.0f);
+            for (uint32_t k = 0; k < lv.normal_pow2; k++) wn = wn * wn;
+            const float dz = fabsf(gq.w - gp.w) / zs;
+            const float wz = 1.0f / (1.0f + dz * dz);
+            const float wt = ((hk * wl) * wn) * wz;
+            nr += wt * xq.x;
+            ng += wt * xq.y;
+            nb += wt * xq.z;
+            den += wt;
+            nv += (wt * wt) * xq.w;
+        }
+    }
+    float4 xo = xp;
+    if (den > 0.0f) xo = make_float4(nr / den, ng / den, nb / den, nv / (den * den));
+    if (LAST) {
+        const float3 a = albedo(__float_as_int(hits[2 * i + 1].w) & 3);
+        out[i] = make_float4(xo.x * a.x, xo.y * a.y, xo.z * a.z, rgba[i].w);
+    } else {
+        st_out[i] = xo;
+    }
+}
+
+}  // namespace
+
+struct gpuart_denoise {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    void *scratch = nullptr;  ///< 48 bytes per pixel: two states and the guide; then (run_host) the staged inputs and output
+    size_t scratch_bytes = 0;
+};
+
+namespace {
+
+int ensure_scratch(gpuart_denoise *d, size_t bytes) {
+    if (bytes <= d->scratch_bytes) return 0;
+    if (d->scratch) {
+        HIP_TRY(hipStreamSynchronize(d->stream));
+        (void)hipFree(d->scratch);
+        d->scratch = nullptr;
+        d->scratch_bytes = 0;
+    }
+    HIP_TRY(hipMalloc(&d->scratch, bytes));
+    d->scratch_bytes = bytes;
+    return 0;
+}
+
+int check_params(const gpuart_denoise_params &p) {
+    if (p.iterations > GPUART_DENOISE_MAX_ITERATIONS)
+        return fail(GPUART_HIP_ERR_ARG, "denoise: iterations = " + std::to_string(p.iterations) + " exceeds " +
+                                            std::to_string(GPUART_DENOISE_MAX_ITERATIONS));
+    if (!std::isfinite(p.lum_k) || !(p.lum_k >= 0)) return fail(GPUART_HIP_ERR_ARG, "denoise: lum_k must be finite and >= 0");
+    if (!std::isfinite(p.depth_sigma) || !(p.depth_sigma > 0)) return fail(GPUART_HIP_ERR_ARG, "denoise: depth_sigma must be finite and > 0");
+    if (p.normal_pow2 > 16) return fail(GPUART_HIP_ERR_ARG, "denoise: normal_pow2 exceeds 16");
+    return 0;
+}
+
+/// The checks both entry points make; `align` is what rgba, hits and out must be aligned to.
+int check_run(gpuart_denoise *d, const void *rgba, const void *hits, const void *prims, uint32_t w, uint32_t h,
+              const gpuart_denoise_params *p, const void *out, size_t align) {
+    if (!d) return fail(GPUART_HIP_ERR_ARG, "denoise: handle is NULL");
+    if (!rgba || !hits || !prims || !out) return fail(GPUART_HIP_ERR_ARG, "denoise: rgba, hits, prims or out is NULL");
+    if ((uintptr_t)rgba % align || (uintptr_t)hits % align || (uintptr_t)out % align || (uintptr_t)prims % 4)
+        return fail(GPUART_HIP_ERR_ARG, "denoise: misaligned pointer (rgba, hits and out need " + std::to_string(align) + " bytes, prims 4)");
+    if (w == 0 || h == 0 || w > 65536 || h > 65536)
+        return fail(GPUART_HIP_ERR_ARG, "denoise: bad size " + std::to_string(w) + " x " + std::to_string(h));
+    return p ? check_params(*p) : 0;
+}
+
+/// The filter on device memory, on the handle's stream; the states and the guide take the first 48 bytes per pixel of the scratch.
+int launch(gpuart_denoise *d, const float4 *rgba, const float4 *hits, const int32_t *prims, uint32_t us_flags, int w, int h,
+           const gpuart_denoise_params &p, float4 *out) {
+    const size_t n = (size_t)w * h;
+    if (p.iterations == 0) {
+        if (out != rgba) HIP_TRY(hipMemcpyAsync(out, rgba, n * sizeof(float4), hipMemcpyDeviceToDevice, d->stream));
+        return 0;
+    }
+    float4 *st[2] = {(float4 *)d->scratch, (float4 *)d->scratch + n};
+    float4 *guide = (float4 *)d->scratch + 2 * n;
+    k_dn_prepare<<<dim3((w + PT - 1) / PT, (h + PT - 1) / PT), dim3(PT, PT), 0, d->stream>>>(rgba, hits, prims, us_flags, w, h, st[0], guide);
+    HIP_TRY(hipGetLastError());
+    const dim3 grid((w + AX - 1) / AX, (h + AY - 1) / AY), block(AX, AY);
+    for (uint32_t it = 0; it < p.iterations; it++) {
+        Level lv;
+        lv.lum_k = p.lum_k;
+        lv.depth_sigma = p.depth_sigma;
+        lv.s = 1 << it;
+        lv.step = (float)lv.s;
+        lv.normal_pow2 = p.normal_pow2;
+        if (it + 1 == p.iterations)
+            k_dn_atrous<true><<<grid, block, 0, d->stream>>>(st[it & 1], guide, nullptr, w, h, lv, rgba, hits, out);
+        else
+            k_dn_atrous<false><<<grid, block, 0, d->stream>>>(st[it & 1], guide, st[(it + 1) & 1], w, h, lv, rgba, hits, out);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char *gpuart_denoise_last_error(void) { return g_last_error.c_str(); }
+
+int gpuart_denoise_defaults(gpuart_denoise_params *p) {
+    if (!p) return fail(GPUART_HIP_ERR_ARG, "denoise: params is NULL");
+    p->iterations = 5;
+    p->lum_k = 4.0f;
+    p->normal_pow2 = 5;
+    p->depth_sigma = 0.05f;
+    return 0;
+}
+
+int gpuart_denoise_create(int device, gpuart_denoise **out) {
+    if (!out) return fail(GPUART_HIP_ERR_ARG, "denoise: out is NULL");
+    *out = nullptr;
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n)
+        return fail(GPUART_HIP_ERR_NO_DEVICE, "denoise: no HIP device " + std::to_string(device));
+    HIP_TRY(hipSetDevice(device));
+    gpuart_denoise *d = new gpuart_denoise;
+    d->device = device;
+    if (hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) != hipSuccess) {
+        delete d;
+        return fail(GPUART_HIP_ERR_DEVICE, "denoise: hipStreamCreateWithFlags failed");
+    }
+    *out = d;
+    return 0;
+}
+
+int gpuart_denoise_destroy(gpuart_denoise *d) {
+    if (!d) return 0;
+    (void)hipSetDevice(d->device);
+    if (d->stream) (void)hipStreamSynchronize(d->stream);
+    if (d->scratch) (void)hipFree(d->scratch);
+    if (d->stream) (void)hipStreamDestroy(d->stream);
+    delete d;
+    return 0;
+}
+
+int gpuart_denoise_finish(gpuart_denoise *d) {
+    if (!d) return fail(GPUART_HIP_ERR_ARG, "denoise: handle is NULL");
+    HIP_TRY(hipSetDevice(d->device));
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    return 0;
+}
+
+int gpuart_denoise_run(gpuart_denoise *d, const float *rgba, const gpuart_ray_hit *hits, const int32_t *prims, uint32_t userSphereFlags,
+                       uint32_t w, uint32_t h, const gpuart_denoise_params *p, float *out) {
+    int r = check_run(d, rgba, hits, prims, w, h, p, out, 16);
+    if (r) return r;
+    gpuart_denoise_params dp;
+    if (p) dp = *p;
+    else gpuart_denoise_defaults(&dp);
+    HIP_TRY(hipSetDevice(d->device));
+    if ((r = ensure_scratch(d, (size_t)w * h * 48))) return r;
+    return launch(d, (const float4 *)rgba, (const float4 *)hits, prims, userSphereFlags, (int)w, (int)h, dp, (float4 *)out);
+}
+
+int gpuart_denoise_run_host(gpuart_denoise *d, const float *rgba, const gpuart_ray_hit *hits, const int32_t *prims,
+                            uint32_t userSphereFlags, uint32_t w, uint32_t h, const gpuart_denoise_params *p, float *out) {
+    int r = check_run(d, rgba, hits, prims, w, h, p, out, 4);
+    if (r) return r;
+    gpuart_denoise_params dp;
+    if (p) dp = *p;
+    else gpuart_denoise_defaults(&dp);
+    HIP_TRY(hipSetDevice(d->device));
+    const size_t n = (size_t)w * h;
+    // the filter's 48 bytes per pixel, then the staged radiance (16, also the output), records (32) and ordinals (4)
+    if ((r = ensure_scratch(d, n * (48 + 16 + 32 + 4)))) return r;
+    char *base = (char *)d->scratch + n * 48;
+    float4 *d_rgba = (float4 *)base;
+    float4 *d_hits = (float4 *)(base + n * 16);
+    int32_t *d_prims = (int32_t *)(base + n * 48);
+    HIP_TRY(hipMemcpyAsync(d_rgba, rgba, n * 16, hipMemcpyHostToDevice, d->stream));
+    HIP_TRY(hipMemcpyAsync(d_hits, hits, n * 32, hipMemcpyHostToDevice, d->stream));
+    HIP_TRY(hipMemcpyAsync(d_prims, prims, n * 4, hipMemcpyHostToDevice, d->stream));
+    if ((r = launch(d, d_rgba, d_hits, d_prims, userSphereFlags, (int)w, (int)h, dp, d_rgba))) return r;
+    HIP_TRY(hipMemcpyAsync(out, d_rgba, n * 16, hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    return 0;
+}
+
+}  // extern "C"

@@ -107,6 +107,7 @@ struct gpuart_hip_ctx {
     float4 *d_recs = nullptr, *d_prims = nullptr;
     uint32_t *d_cursor = nullptr;  ///< pixel cursor of k_direct_persistent
     uint32_t *d_query_cursor = nullptr;  ///< chunk cursor of k_ray_query (primary stream, like d_spill)
+    uint2 *d_tile_xy = nullptr;    ///< gpuart_hip_gbuffer: the frame pixel of every tile pixel, in local order (freed by realloc_tile, built on use)
     uint4 *d_spill = nullptr;      ///< [spill_levels][grid_lanes] traversal-stack overflow for kernels on the primary stream
     // Birth order of the paths of a run (Frame::tile_order, k_tile_order): the tile's 8x8 blocks, most expensive first. The first run
     // after the tile was (re)allocated — and the first after every change of camera or scene — counts the shaded segments per block
@@ -235,6 +236,7 @@ int realloc_tile(gpuart_hip_ctx *c) {
     if (c->d_tile_cost) { (void)hipFree(c->d_tile_cost); c->d_tile_cost = nullptr; }
     c->frame.tile_order = nullptr; c->frame.tile_cost = nullptr;
     c->order_cur = -1; c->order_sorting = false; c->order_stale = true; c->order_from_hook = false;
+    if (c->d_tile_xy) { (void)hipFree(c->d_tile_xy); c->d_tile_xy = nullptr; }
     if (c->d_direct) { (void)hipFree(c->d_direct); c->d_direct = nullptr; }
     if (c->d_accum) { (void)hipFree(c->d_accum); c->d_accum = nullptr; }
     c->plan.tile_pixels = (size_t)c->frame.tw * c->frame.th;
@@ -523,7 +525,7 @@ int gpuart_hip_destroy(gpuart_hip_ctx *c) {
     const bool comm_stuck = bounded_ns::stuck().load();
     if (c->comm && !comm_stuck) (void)comm_drop(c);
     void *ptrs[] = {c->d_recs, c->d_prims, c->d_spill, c->d_direct, c->d_accum, c->d_counters, c->d_scratch, c->d_cursor,
-                    c->d_query_cursor, c->d_tile_order[0], c->d_tile_order[1], c->d_tile_cost};
+                    c->d_query_cursor, c->d_tile_order[0], c->d_tile_order[1], c->d_tile_cost, c->d_tile_xy};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     void *comm_ptrs[] = {c->d_send, c->d_stage, c->d_hello};
     for (void *p : comm_ptrs) if (p && !comm_stuck) (void)hipFree(p);
@@ -1185,6 +1187,35 @@ int gpuart_hip_pick(gpuart_hip_ctx *c, const uint32_t *xy, size_t n, const float
                         std::to_string(xy[2 * i + 1]) + ") lies outside the " + std::to_string(c->frame.W) + " x " +
                         std::to_string(c->frame.H) + " frame");
     return staged_query(c, xy, 8, n, 0, us, RQ_PIXELS, hits, prims);
+}
+
+int gpuart_hip_gbuffer(gpuart_hip_ctx *c, const float us[4], gpuart_ray_hit *hits, int32_t *prims) {
+    if (!c) return fail(GPUART_HIP_ERR_ARG, "ctx == NULL");
+    if (!c->have_scene) return fail(GPUART_HIP_ERR_ARG, "gbuffer: no scene uploaded");
+    if (!c->frame.W) return fail(GPUART_HIP_ERR_ARG, "gbuffer: no frame size set");
+    if (!c->have_camera) return fail(GPUART_HIP_ERR_ARG, "gbuffer: no camera set");
+    if (!hits) return fail(GPUART_HIP_ERR_ARG, "gbuffer: hits is NULL");
+    if ((uintptr_t)hits % 16 || (uintptr_t)prims % 4) return fail(GPUART_HIP_ERR_ARG, "gbuffer: misaligned pointer (hits needs 16 bytes, prims 4)");
+    const size_t n = c->plan.tile_pixels;
+    if (n == 0) return 0;  // an empty share
+    if (n > GPUART_HIP_MAX_RAYS) return fail(GPUART_HIP_ERR_ARG, "gbuffer: the tile exceeds GPUART_HIP_MAX_RAYS pixels");
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->d_tile_xy) {  // the table of the tile's frame pixels, once per tile (realloc_tile drops it)
+        const Frame &f = c->frame;
+        std::vector<uint2> xy(n);
+        for (uint32_t ly = 0; ly < f.th; ly++) {
+            const uint32_t fy = f.y0 + (ly / f.band_rows) * f.band_stride + ly % f.band_rows;
+            for (uint32_t lx = 0; lx < f.tw; lx++) xy[(size_t)ly * f.tw + lx] = make_uint2(f.x0 + lx, fy);
+        }
+        HIP_TRY(hipMalloc(&c->d_tile_xy, n * sizeof(uint2)));
+        HIP_TRY(hipMemcpyAsync(c->d_tile_xy, xy.data(), n * sizeof(uint2), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));  // (xy is freed on return)
+    }
+    RayQuery q = make_query(n, 0, us);
+    q.xy = c->d_tile_xy;
+    q.hits = (float4 *)hits;
+    q.prims = prims;
+    return launch_ray_query(c, q, RQ_PIXELS);
 }
 
 // ---- shares and the multi-GPU gather (gather.h) ---------------------------------------------------------------------

@@ -262,6 +262,9 @@ int gpuart_renderer_read_direct(gpuart_renderer *r, float *rgba) { return r->imp
 int gpuart_renderer_read_radiance(gpuart_renderer *r, float *rgba, int normalized) {
     return r->impl.ReadRadiance(rgba, normalized != 0) ? 1 : 0;
 }
+int gpuart_renderer_read_denoised(gpuart_renderer *r, float *rgba, const gpuart_denoise_params *p) {
+    return r->impl.ReadDenoised(rgba, p) ? 1 : 0;
+}
 int gpuart_renderer_finish(gpuart_renderer *r) { return r->impl.Finish() ? 1 : 0; }
 int gpuart_renderer_save_checkpoint(gpuart_renderer *r, const char *path) { return r->impl.SaveCheckpoint(path) ? 1 : 0; }
 int gpuart_renderer_load_checkpoint(gpuart_renderer *r, const char *path) { return r->impl.LoadCheckpoint(path) ? 1 : 0; }

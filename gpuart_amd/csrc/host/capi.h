@@ -6,6 +6,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "gpuart_denoise.h"
 #include "gpuart_hip.h"
 
 #ifdef __cplusplus
@@ -74,6 +75,9 @@ void gpuart_renderer_restart_path_tracing(gpuart_renderer *r, unsigned pathsPerP
 unsigned gpuart_renderer_path_tracing_pass(gpuart_renderer *r);
 int gpuart_renderer_read_direct(gpuart_renderer *r, float *rgba);
 int gpuart_renderer_read_radiance(gpuart_renderer *r, float *rgba, int normalized);
+/* Renderer::ReadDenoised: the denoised preview of the normalised accumulator (include/gpuart_denoise.h); p = NULL: the defaults.
+ * 1 on success, 0 on error. */
+int gpuart_renderer_read_denoised(gpuart_renderer *r, float *rgba, const gpuart_denoise_params *p);
 int gpuart_renderer_finish(gpuart_renderer *r);
 int gpuart_renderer_save_checkpoint(gpuart_renderer *r, const char *path);
 int gpuart_renderer_load_checkpoint(gpuart_renderer *r, const char *path);

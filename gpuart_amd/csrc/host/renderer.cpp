@@ -14,6 +14,8 @@
 
 #include "utils.h"
 
+#include <hip/hip_runtime_api.h>
+
 #define GPUART_PI 3.1415926f  // the reference's PI (src/renderer.cpp:48); feeds tan() of the field of view
 
 namespace gpuart {
@@ -60,6 +62,7 @@ Renderer::Renderer(unsigned viewportWidth, unsigned viewportHeight, const Camera
     PathTracing.pathsPerPass = PathTracing.pathsPerPixel;
     PathTracing.numPathsRendered = 0;
     CurrentCamera = camera;
+    Device = device;
 
     if (!Check(gpuart_hip_create(device, &Backend), "creating the device back end")) return;
     if (viewportWidth == 0 || viewportHeight == 0) {
@@ -71,6 +74,8 @@ Renderer::Renderer(unsigned viewportWidth, unsigned viewportHeight, const Camera
 }
 
 Renderer::~Renderer() {
+    if (Denoiser) gpuart_denoise_destroy(Denoiser);
+    if (DenoiseMem) (void)hipFree(DenoiseMem);
     if (Backend) gpuart_hip_destroy(Backend);
 }
 
@@ -86,6 +91,7 @@ bool Renderer::UpdateViewportSize(unsigned width, unsigned height) {
     Viewport.height = height;
     if (!Check(gpuart_hip_resize(Backend, width, height), "allocating per-pixel buffers")) return IsOK = false;
     Tile.x = Tile.y = 0; Tile.w = width; Tile.h = height;
+    GBufferValid = false;
     if (!SetCamera(CurrentCamera)) IsOK = false;
     return IsOK;
 }
@@ -94,6 +100,7 @@ bool Renderer::SetTile(unsigned x0, unsigned y0, unsigned w, unsigned h) {
     if (!Backend) return false;
     if (!Check(gpuart_hip_set_tile(Backend, x0, y0, w, h), "setting the tile")) return false;
     Tile.x = x0; Tile.y = y0; Tile.w = w; Tile.h = h;
+    GBufferValid = false;
     ResetPathTracing();
     return true;
 }
@@ -104,6 +111,7 @@ bool Renderer::SetInterleavedTile(unsigned x0, unsigned y0, unsigned w, unsigned
     if (!Check(gpuart_hip_set_tile_interleaved(Backend, x0, y0, w, localRows, bandRows, bandStride), "setting the tile"))
         return false;
     Tile.x = x0; Tile.y = y0; Tile.w = w; Tile.h = localRows;
+    GBufferValid = false;
     ResetPathTracing();
     return true;
 }
@@ -176,6 +184,7 @@ bool Renderer::ReleaseCommunicator(Renderer *const *ranks, int n) {
 
 bool Renderer::SetCamera(const Camera &cam) {
     CurrentCamera = cam;
+    GBufferValid = false;
     if (!Backend) return false;
     const ScreenBasis s = ComputeScreenBasis(cam, Viewport.width, Viewport.height);
     float pos[3], bl[3], dh[3], dv[3];
@@ -216,6 +225,7 @@ void Renderer::SetPrimitives(std::vector<Primitive *> &primitives, bool printInf
     std::unique_ptr<float[]> compiled(new float[compiledFloats]);
     Tree.CompileTo(compiled.get());
     const auto tCompiled = std::chrono::high_resolution_clock::now();
+    GBufferValid = false;
     if (printInfo) std::cout << "done (" << Utils::TimeElapsed(t0) << ").\n";
     if (!Backend || !Check(gpuart_hip_upload_bvh(Backend, compiled.get(), compiledFloats / RGBA_ELEMS), "uploading the BVH"))
         IsOK = false;
@@ -343,6 +353,50 @@ bool Renderer::ReadRadiance(float *rgba, bool normalized) {
     // the division is the reference's ptracingNormalize program (shaders/pt_normalize.glsl:44-47)
     const float div = normalized && PathTracing.numPathsRendered ? (float)PathTracing.numPathsRendered : 1.0f;
     return IsOK && Check(gpuart_hip_read(Backend, 1, rgba, div), "reading the radiance accumulator");
+}
+
+bool Renderer::ReadDenoised(float *rgba, const gpuart_denoise_params *p) {
+    if (!IsOK || !rgba) return false;
+    auto checkDn = [](int status, const char *what) {
+        if (status == 0) return true;
+        std::cerr << "Renderer: error " << status << " while " << what << ": " << gpuart_denoise_last_error() << std::endl;
+        return false;
+    };
+    auto checkHip = [](hipError_t e, const char *what) {
+        if (e == hipSuccess) return true;
+        std::cerr << "Renderer: " << what << ": " << hipGetErrorString(e) << std::endl;
+        return false;
+    };
+    if (!Denoiser && !checkDn(gpuart_denoise_create(Device, &Denoiser), "creating the denoiser")) return false;
+    if (!checkHip(hipSetDevice(Device), "hipSetDevice")) return false;
+    const size_t n = (size_t)Tile.w * Tile.h;
+    if (n != DenoisePixels) {
+        if (DenoiseMem) (void)hipFree(DenoiseMem);
+        DenoiseMem = nullptr;
+        DenoisePixels = 0;
+        GBufferValid = false;
+        if (!checkHip(hipMalloc(&DenoiseMem, n * (16 + 32 + 16 + 4)), "allocating the denoiser's buffers")) return false;
+        DenoisePixels = n;
+    }
+    char *m = (char *)DenoiseMem;
+    float *radiance = (float *)m;
+    gpuart_ray_hit *hits = (gpuart_ray_hit *)(m + n * 16);
+    float *filtered = (float *)(m + n * 48);
+    int32_t *prims = (int32_t *)(m + n * 64);
+    const float us[4] = {UserSphere.pos.x, UserSphere.pos.y, UserSphere.pos.z, UserSphere.radius};
+    if (!GBufferValid || memcmp(us, GBufferSphere, sizeof us) != 0) {
+        GBufferValid = false;
+        if (!Check(gpuart_hip_gbuffer(Backend, us, hits, prims), "building the G-buffer")) return false;
+        memcpy(GBufferSphere, us, sizeof us);
+        GBufferValid = true;
+    }
+    // the division is the reference's ptracingNormalize program (shaders/pt_normalize.glsl:44-47), as in ReadRadiance
+    const float div = PathTracing.numPathsRendered ? (float)PathTracing.numPathsRendered : 1.0f;
+    if (!Check(gpuart_hip_export(Backend, 1, radiance, div), "exporting the radiance")) return false;
+    if (!Check(gpuart_hip_finish(Backend), "waiting for the device")) return false;
+    if (!checkDn(gpuart_denoise_run(Denoiser, radiance, hits, prims, UserSphere.flags, Tile.w, Tile.h, p, filtered), "denoising")) return false;
+    if (!checkDn(gpuart_denoise_finish(Denoiser), "denoising")) return false;
+    return checkHip(hipMemcpy(rgba, filtered, n * 16, hipMemcpyDeviceToHost), "reading the denoised frame");
 }
 
 // ---- checkpoint / resume ---------------------------------------------------------------------------------------------

@@ -17,6 +17,7 @@
 
 #include "bvh.h"
 #include "core.h"
+#include "gpuart_denoise.h"
 #include "gpuart_hip.h"
 #include "math_types.h"
 
@@ -84,6 +85,11 @@ public:
     bool ReadDirectLighting(float *rgba);
     /// Accumulated radiance; normalized = divided by the paths rendered (what ptracingNormalize shows).
     bool ReadRadiance(float *rgba, bool normalized);
+    /// The denoised preview of the accumulator (include/gpuart_denoise.h): the radiance divided by the paths rendered, filtered with the
+    /// G-buffer of the tile (gpuart_hip_gbuffer with the current user sphere, kept until the camera, the scene, the user sphere or the
+    /// tile changes). RGBA32F, tile-sized, row 0 = bottom row; p = nullptr: the defaults. The accumulator, the passes that follow and
+    /// the counters are not touched. Synchronises.
+    bool ReadDenoised(float *rgba, const gpuart_denoise_params *p = nullptr);
     bool Finish();
     void SetMaxPathSegments(unsigned n) { MaxPathSegments = n; ResetPathTracing(); }
     void SetMinWeight(float w) { MinWeight = w; ResetPathTracing(); }
@@ -138,6 +144,12 @@ private:
     enum UserSphereFlags : uint32_t { EM_NONZERO = 1u << 0, SPECULAR = 1u << 1, FUZZY = 1u << 2 };
 
     bool IsOK = false;
+    int Device = 0;
+    gpuart_denoise *Denoiser = nullptr;  ///< made by the first ReadDenoised
+    void *DenoiseMem = nullptr;          ///< device: radiance (16 B), G-buffer record (32), filtered (16), ordinal (4) per tile pixel
+    size_t DenoisePixels = 0;
+    bool GBufferValid = false;           ///< DenoiseMem holds the G-buffer of this camera, scene and tile for GBufferSphere
+    float GBufferSphere[4] = {0, 0, 0, 0};
     double LastSetPrimitivesMs[4] = {0, 0, 0, 0};
     gpuart_hip_ctx *Backend = nullptr;
     BoundingVolumesHierarchy Tree;

@@ -286,6 +286,14 @@ int gpuart_hip_trace_rays_host(gpuart_hip_ctx *ctx, const float *rays, size_t n,
  * context's tile): the ray gpuart_hip_render_direct traces for that pixel. Host memory, synchronous. */
 int gpuart_hip_pick(gpuart_hip_ctx *ctx, const uint32_t *xy, size_t n, const float userSphere[4], gpuart_ray_hit *hits,
                     int32_t *prims);
+/* The G-buffer of the context's tile: for every tile pixel the record and ordinal that picking that frame pixel returns (the same camera
+ * ray, the same user sphere semantics), in the tile's local order as gpuart_hip_read lays it out: record ly * tw + lx is local pixel
+ * (lx, ly), row 0 at the bottom, and local row ly is frame row y0 + (ly / band_rows) * band_stride + ly % band_rows (rectangular tiles
+ * and interleaved shares alike). Device memory, asynchronous on the context's stream as gpuart_hip_trace_rays: hits (tw*th records)
+ * 16-byte aligned, prims (tw*th ordinals, may be NULL) 4-byte aligned. Collected passes are not flushed; counters and timings do not
+ * change. An empty share writes nothing. GPUART_HIP_ERR_ARG without a scene, a frame size or a camera, and for a NULL or misaligned
+ * pointer. include/gpuart_denoise.h filters a frame with it. */
+int gpuart_hip_gbuffer(gpuart_hip_ctx *ctx, const float userSphere[4], gpuart_ray_hit *hits, int32_t *prims);
 
 /* The test hooks (gpuart_hip_test_*: the run planner, the uploader's verdicts, the share-table check, birth orders, a stream stall, the
  * device functions one by one) are NOT part of this interface: include/gpuart_hip_test.h declares them, and only a library built with
