@@ -866,16 +866,22 @@ GD_FN void trav_step_box(const Scene &sc, const Ray &r, F3 rdiv, Trav &t, TravSt
     trav_pop<COUNT>(t, st, wc);
 }
 
-/// Tests the primitives of the pending leaf, then pops. Precondition: state == LEAF or LEAF_TRIS.
+/// The primitive tests of the leaf whose first primitive is `first`, `state` its leaf state (TRAV_LEAF ...); true if ANY_HIT and
+/// something was hit.
 template <bool ANY_HIT, bool COUNT, int TYPES = GD_ALL_TYPES, bool NEAREST = false>
-GD_FN void trav_step_leaf(const Scene &sc, const Ray &r, Trav &t, TravStack &st, WorkCounters *wc, bool ordered = true) {
-    bool stop;
+GD_FN bool leaf_tests(const Scene &sc, const Ray &r, uint32_t first, int state, Trav &t, WorkCounters *wc) {
     // (the triangle-mesh kernels keep the loop for their few other leaves — the floor disc —: the pair path there costs the
     // closest-hit launches 2 % for nothing)
     constexpr bool SMALL_PATH = (TYPES & 0xF) != ((1 << P_DISC) | (1 << P_TRIANGLE));
-    if (t.state & 8) stop = leaf_test_tris<ANY_HIT, COUNT, NEAREST>(sc, r, t.node, t.state == TRAV_LEAF_TRIS, t, wc);
-    else if (SMALL_PATH && t.state != TRAV_LEAF) stop = leaf_test_small<ANY_HIT, COUNT, TYPES, NEAREST>(sc, r, t.node, t.state == TRAV_LEAF_PAIR, t, wc);
-    else stop = leaf_test<ANY_HIT, COUNT, TYPES, NEAREST>(sc, r, t.node, t, wc);
+    if (state & 8) return leaf_test_tris<ANY_HIT, COUNT, NEAREST>(sc, r, first, state == TRAV_LEAF_TRIS, t, wc);
+    if (SMALL_PATH && state != TRAV_LEAF) return leaf_test_small<ANY_HIT, COUNT, TYPES, NEAREST>(sc, r, first, state == TRAV_LEAF_PAIR, t, wc);
+    return leaf_test<ANY_HIT, COUNT, TYPES, NEAREST>(sc, r, first, t, wc);
+}
+
+/// Tests the primitives of the pending leaf, then pops. Precondition: state == LEAF or LEAF_TRIS.
+template <bool ANY_HIT, bool COUNT, int TYPES = GD_ALL_TYPES, bool NEAREST = false>
+GD_FN void trav_step_leaf(const Scene &sc, const Ray &r, Trav &t, TravStack &st, WorkCounters *wc, bool ordered = true) {
+    const bool stop = leaf_tests<ANY_HIT, COUNT, TYPES, NEAREST>(sc, r, t.node, t.state, t, wc);
     if (stop && ANY_HIT) {
         t.state = TRAV_DONE;
         return;
@@ -1054,6 +1060,103 @@ GD_FN void trav_step_leaf_thin(const Scene &sc, F3 ro, F3 rd, Trav &t, TravStack
     ThinFetch pf;
     thin_fetch<M>(sc, t, sub, pf);  // (a state that is not a triangle leaf fetches nothing here)
     trav_step_leaf_thin_on<M, TYPES, NEAREST>(sc, ro, rd, t, st, sub, pf, ordered);
+}
+
+// ---- packet walk: the 64 queries of a wave through ONE walk of the tree ------------------------------------------------------
+// In the reference's order (lower child first, prune on `entry > closest`) the nodes a query visits are the tree's one depth-first
+// pre-order restricted to the nodes that query enters: the order does not depend on the ray. A wave can therefore walk that order
+// for all its lanes at once — one node at a time, the same node for the whole wave — where every lane applies exactly the tests of
+// its own walk (trav_step_box / trav_pop / trav_step_leaf, reference order, fast-form boxes) and is active at exactly the nodes its
+// own walk visits, in the same order and with the same `closest`: the results are those of the per-lane walk bit for bit. It pays
+// where the lanes of a wave visit nearly the same nodes — camera rays of one 8x8 pixel block, the Sun-shadow rays of their hits.
+// The node and the stack pointers are wave-uniform (scalar registers; the node record comes from scalar loads). Every lane writes
+// its own row of every stack entry: its parent's entry parameter and its child's (GD_ENTRY_MISS where its own walk would not have
+// stacked the child), so that a lane's pops accept exactly the entries its own walk would have pushed and accepted. A packet pushes
+// at most one entry per level, as a lane does: the ring, the spill column and their sizing are the per-lane walk's.
+#ifdef GD_STEP_STATS
+__device__ unsigned long long g_packet_stats[4];  // [0] box steps of packets, [1] active lanes in them, [2] leaf steps, [3] active lanes in them
+#endif
+typedef float GdF4v __attribute__((ext_vector_type(4)));
+typedef const GdF4v __attribute__((address_space(4))) *ScalarF4;  ///< constant address space: a load through a uniform address is a scalar load
+GD_FN float4 ld4(ScalarF4 p, int k) { const GdF4v v = p[k]; return make_float4(v.x, v.y, v.z, v.w); }
+
+/// Both boxes of a record (fast form) for one lane: the calls of trav_step_box's GD_QUICK_BOXES branch, its fallback included.
+/// `need`: this lane's answers are used (an idle lane does not ask for the face tests).
+GD_FN void box_pair_fast(const Scene &sc, const Ray &r, F3 rdiv, ScalarF4 rec, float4 q0, float4 q1, float4 q2, float4 q3, bool need,
+                         float &el, float &eh, bool &hl, bool &hh) {
+    const float cs = gq_ray_slack(sc.box_slack, r.o.x, r.o.y, r.o.z, r.d.x, r.d.y, r.d.z, rdiv.x, rdiv.y, rdiv.z);
+    bool sl = false, sh = false;
+    if (GD_QUICK_BOXES && __ballot(cs == cs) != 0) {
+        sl = box_quick(r, rdiv, xyz(q0), xyz(q1), cs, el, hl);
+        sh = box_quick(r, rdiv, xyz(q2), xyz(q3), cs, eh, hh);
+    }
+    if (need & !(sl & sh)) {
+        const float4 p0 = ld4(rec, 0), p1 = ld4(rec, 1), p2 = ld4(rec, 2), p3 = ld4(rec, 3);
+        bool ol, oh;
+        hl = aabb_entry<false, true>(r, rdiv, xyz(p0), xyz(p1), el, &ol);
+        hh = aabb_entry<false, true>(r, rdiv, xyz(p2), xyz(p3), eh, &oh);
+    }
+}
+
+/// Walks the queries of the wave as one packet to completion (state DONE in every lane). Precondition: trav_init of every lane's
+/// query in the reference's order (fast-form boxes; lanes without a query: state DONE). `any_hit`: this lane's query stops at its
+/// first accepted hit (a Sun-shadow query). Results (closest, hit_prim) are those of the per-lane walk in the reference's order.
+template <int TYPES>
+GD_FN void trav_packet(const Scene &sc, F3 ro, F3 rd, F3 rdiv, Trav &t, TravStack &st, bool any_hit) {
+    const Ray r{ro, rd};
+    bool act = t.state != TRAV_DONE;  // this lane's walk is at the packet's node
+    if (__ballot(act) == 0) return;
+    uint32_t ref = sc.root_ref;       // wave-uniform: the node the packet visits (a record, or GD_REF_LEAF | first primitive with the leaf's flags)
+    st.reset();                       // sp / base: wave-uniform
+    t.node = 0;                       // (not used here: nothing of the lane's earlier walk stays alive across the packet)
+    for (;;) {
+        if (!(ref & GD_REF_LEAF)) {
+            // ---- interior node: both children's boxes for every lane; the lanes whose own walk enters the lower child go down it
+            const ScalarF4 rec = (ScalarF4)((const char *)sc.recs + (ref << 6));
+            const float4 q0 = ld4(rec, 0), q1 = ld4(rec, 1), q2 = ld4(rec, 2), q3 = ld4(rec, 3);
+            float el = 0, eh = 0;
+            bool hl = false, hh = false;
+            box_pair_fast(sc, r, rdiv, rec, q0, q1, q2, q3, act, el, eh, hl, hh);
+#ifdef GD_STEP_STATS
+            { const unsigned long long a_ = __ballot(act); if ((threadIdx.x & 63) == 0) { atomicAdd(&g_packet_stats[0], 1ull); atomicAdd(&g_packet_stats[1], (unsigned long long)__popcll(a_)); } }
+#endif
+            const bool lo = act & hl & !(el > t.closest), hi = act & hh & !(eh > t.closest);
+            if (__ballot(hi) != 0) {
+                StackEntry e;
+                e.ref = __float_as_uint(q1.w); e.pe = t.entry; e.he = hi ? eh : GD_ENTRY_MISS;
+                st.push(e);
+            }
+            if (__ballot(lo) != 0) {
+                act = lo;
+                t.entry = lo ? el : t.entry;
+                ref = __float_as_uint(q0.w);
+                continue;
+            }
+        } else {
+            // ---- leaf: the primitive tests of trav_step_leaf for the lanes at it; a shadow query is settled by one accepted hit
+            const int state = (int)(1u | ((ref >> 27) & 14u));
+#ifdef GD_STEP_STATS
+            { const unsigned long long a_ = __ballot(act); if ((threadIdx.x & 63) == 0) { atomicAdd(&g_packet_stats[2], 1ull); atomicAdd(&g_packet_stats[3], (unsigned long long)__popcll(a_)); } }
+#endif
+            if (act) {
+                leaf_tests<false, false, TYPES, false>(sc, r, ref & GD_REF_INDEX, state, t, nullptr);
+                if (any_hit && t.hit_prim != GD_NO_PRIM) t.state = TRAV_DONE;
+            }
+            if (__ballot(t.state != TRAV_DONE) == 0) return;
+        }
+        // ---- pop until some lane's own walk accepts the entry (trav_pop's two tests); an empty stack ends every walk
+        for (;;) {
+            if (st.sp == 0) { t.state = TRAV_DONE; return; }
+            const StackEntry e = st.pop();
+            const bool take = (t.state != TRAV_DONE) & !(e.pe > t.closest) & !(e.he > t.closest);
+            if (__ballot(take) != 0) {
+                act = take;
+                t.entry = take ? e.he : t.entry;
+                ref = (uint32_t)__builtin_amdgcn_readfirstlane((int)e.ref);
+                break;
+            }
+        }
+    }
 }
 
 /// Runs one query to completion (megakernels and test hooks).

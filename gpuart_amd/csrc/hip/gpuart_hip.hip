@@ -145,6 +145,11 @@ struct gpuart_hip_ctx {
     bool chunk_from_env = false;  ///< GPUART_HIP_CHUNK was given: no per-launch choice of the chunk size
     float box_slack = __builtin_inff();  ///< box_quick.h's slack constant of the uploaded tree (+inf — also before any upload —: quick box answers are never taken)
     uint32_t quick_boxes = 1;     ///< GPUART_HIP_QUICK_BOXES (0: box_slack stays +inf — every box test runs its six face tests)
+    uint32_t packet = 2;          ///< GPUART_HIP_PACKET (default 2): packet walks in k_trace (trav_packet) for 1 — the camera rays, 2 — also the Sun-shadow
+                                  ///< rays of segment 0; 0 — none. Trees walked in the reference's order with fast-form boxes only
+    uint32_t packet_max_prims = 1u << 19;  ///< GPUART_HIP_PACKET_MAX_PRIMS: ... and with at most this many primitives. The lanes of a packet follow
+                                           ///< each other while a pixel block sees few primitives: the 871 200-triangle mesh at 1080p ran 2 % SLOWER
+                                           ///< with packets, the 100 352-triangle one 7 % faster (profiles/r07/ab_runs.txt; sizes between: not measured)
     uint32_t exact_boxes = 0;     ///< the uploaded tree holds an irregular box, or a box that does not bound what it holds (converter.h):
                                   ///< box tests take the comparison form and every walk keeps the reference's order
     uint32_t max_depth = 0;
@@ -253,8 +258,8 @@ int realloc_tile(gpuart_hip_ctx *c) {
     // paths: a persistent k_trace wave then takes many rays per lane, and the drain at the end of every launch — waves
     // finishing their last, long rays with few lanes busy — shrinks relative to the useful work (SQ_INSTS_VALU per
     // ray falls by a quarter from 2M to 16M paths per launch at 1080p). run_planner.h decides how many.
-    if (n * std::max<size_t>(1, std::min<size_t>(c->plan.batch_limit, c->plan.batch_paths / n)) > 0x7ffffff0ull)
-        return fail(GPUART_HIP_ERR_ARG, "tile too large");  // two queues share one 32-bit index space in k_trace
+    if (n * std::max<size_t>(1, std::min<size_t>(c->plan.batch_limit, c->plan.batch_paths / n)) > 0x7fffffc0ull)
+        return fail(GPUART_HIP_ERR_ARG, "tile too large");  // two queues share one 32-bit index space in k_trace (the second from a multiple of 64 on)
     for (auto &l : c->lanes) {
         if (l.pathmem) { (void)hipFree(l.pathmem); l.pathmem = nullptr; }
         l.used = false;
@@ -472,6 +477,8 @@ int gpuart_hip_create(int device, gpuart_hip_ctx **out) {
     c->order_auto = env_u32("GPUART_HIP_TILE_ORDER", 1, 0, 1) != 0;
     c->nearest_min_prims = getenv("GPUART_HIP_NEAREST_MIN_PRIMS") ? env_u32("GPUART_HIP_NEAREST_MIN_PRIMS", 1024, 0, 0x7fffffff) : 0xffffffffu;
     c->quick_boxes = env_u32("GPUART_HIP_QUICK_BOXES", 1, 0, 1);
+    c->packet = env_u32("GPUART_HIP_PACKET", 2, 0, 2);
+    c->packet_max_prims = env_u32("GPUART_HIP_PACKET_MAX_PRIMS", 1u << 19, 0, 0xffffffffu);
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return fail(GPUART_HIP_ERR_DEVICE, "hipStreamCreate failed"); }
     c->lanes.resize(env_u32("GPUART_HIP_PASSES_IN_FLIGHT", 8, 1, 32));
     c->plan.lanes_total = (uint32_t)c->lanes.size();
@@ -850,7 +857,11 @@ int launch_run(gpuart_hip_ctx *c, size_t first, size_t count) {
         TimedLaunch tt;
         int rr;
         if (detail && (rr = begin_timed(c, tt, 1, l.main))) return rr;
-#define GD_LAUNCH_TRACE(T) do { GD_LEDGER(c, k_trace<false, T>); k_trace<false, T><<<pgrid, BLOCK, 0, l.main>>>(sc, fr, *p, b, seg_c, seg_s, 1, j_cur, npaths, l.passcolor, l.spill_main, c->d_counters, c->tune); } while (0)
+        // packet walks (GPUART_HIP_PACKET; the GD_REF_ORDER kernels only): the camera rays' launch, the Sun-shadow queries of segment 0
+        TraceTuning tune = c->tune;
+        const uint32_t packet = c->n_prims <= c->packet_max_prims ? c->packet : 0u;
+        tune.packet = (packet >= 1 && seg_c == 0) ? 1u : (packet >= 2 && seg_s == 0) ? 2u : 0u;
+#define GD_LAUNCH_TRACE(T) do { GD_LEDGER(c, k_trace<false, T>); k_trace<false, T><<<pgrid, BLOCK, 0, l.main>>>(sc, fr, *p, b, seg_c, seg_s, 1, j_cur, npaths, l.passcolor, l.spill_main, c->d_counters, tune); } while (0)
 #define GD_LAUNCH_TRACE_ORD(T) do { if (c->ref_order) GD_LAUNCH_TRACE((T) | GD_REF_ORDER); else GD_LAUNCH_TRACE(T); } while (0)
         if (c->exact_boxes) GD_LAUNCH_TRACE(GD_ALL_TYPES | GD_EXACT_BOXES);
         else if (flat_only) GD_LAUNCH_TRACE_ORD(GD_FLAT_TYPES);
@@ -1966,7 +1977,8 @@ int gpuart_hip_test_launches(gpuart_hip_ctx *c, char *buf, size_t cap, size_t *l
 
 #ifdef GD_STEP_STATS
 /// diagnostic builds only: reads (and clears) k_trace's step statistics (kernels_pipeline.h): box steps, lanes in them, leaf steps, lanes in
-/// them, rounds of the wide loop, lanes holding a ray in them, refill episodes
+/// them, rounds of the wide loop, lanes holding a ray in them, refill episodes; then trav_pop's trips, the phase ticks and the packet walks'
+/// steps (box steps, active lanes in them, leaf steps, active lanes in them): 20 words
 int gpuart_hip_debug_step_stats(gpuart_hip_ctx *c, unsigned long long *out) {
     if (!c || !out) return GPUART_HIP_ERR_ARG;
     static unsigned long long zero[8];
@@ -1977,6 +1989,8 @@ int gpuart_hip_debug_step_stats(gpuart_hip_ctx *c, unsigned long long *out) {
     HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(gd::g_pop_stats), zero, 4 * sizeof(unsigned long long)));
     HIP_TRY(hipMemcpyFromSymbol(out + 12, HIP_SYMBOL(g_phase_ticks), 4 * sizeof(unsigned long long)));
     HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_phase_ticks), zero, 4 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemcpyFromSymbol(out + 16, HIP_SYMBOL(gd::g_packet_stats), 4 * sizeof(unsigned long long)));  // out: 20 words
+    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(gd::g_packet_stats), zero, 4 * sizeof(unsigned long long)));
     return 0;
 }
 #endif

@@ -24,6 +24,8 @@ struct TraceTuning {
     uint32_t xcd_queues;    ///< experiment (GPUART_HIP_XCD_QUEUES, default 0): the waves of XCD x (workgroup index mod 8) serve the x-th
                             ///< eighth of the ray queue — contiguous slots, one region of the image — from a cursor of their own, so
                             ///< that an XCD's L2 sees one eighth of the rays' working set; no stealing between the eighths
+    uint32_t packet;        ///< k_trace, set per launch by the host (GPUART_HIP_PACKET): 1 — its closest-hit queries (the camera rays), 2 — its
+                            ///< Sun-shadow queries (those of segment 0) are walked as packets of 64 (trav_packet); 0 — every query per lane
 };
 
 // =================================================================================================
@@ -329,7 +331,16 @@ k_trace(Scene sc, Frame f, gpuart_params P, PathBuffers b, int seg_c, int seg_s,
     uint32_t M = 1, sub = 0;  // M wave-uniform
     const uint32_t *queue_c = b.queue[seg_c & 1];
     const uint32_t n_c = seg_c >= 0 ? b.counters[4 * seg_c] : 0u;
-    const uint32_t n = n_c + (seg_s >= 0 ? b.counters[4 * seg_s + 2] : 0u);
+    // Packet walks (trav_packet; fast-form boxes in the reference's order only): queue entries [p_lo, n) are taken 64 at a time by a
+    // wave that holds no query and walked as one packet. The queries of one packet should visit nearly the same nodes: the camera
+    // rays (k_gen's slot order: few pixels x the interleaved passes of one 8x8 block; tune.packet = 1, the whole launch) and the
+    // Sun-shadow rays of their hits (k_shade appends them per wave, in slot order; tune.packet = 2, the shadow part, which then
+    // starts at the next multiple of 64 — the entries [n_c, sh_base) are holes).
+    constexpr bool PACKET_OK = !COUNT && (TYPES & GD_REF_ORDER) && GD_BOXES_OF(TYPES) == GD_BOXES_FAST;
+    const uint32_t packet = PACKET_OK ? tune.packet : 0u;
+    const uint32_t sh_base = packet == 2 ? (n_c + 63u) & ~63u : n_c;
+    const uint32_t n = sh_base + (seg_s >= 0 ? b.counters[4 * seg_s + 2] : 0u);
+    const uint32_t p_lo = packet == 1 ? 0u : packet == 2 ? sh_base : n;
     uint32_t *cursor = &b.counters[seg_c >= 0 ? 4 * seg_c + 1 : 4 * seg_s + 3];
     const F3 sun = f3(P.sunDirAlt[0], P.sunDirAlt[1], P.sunDirAlt[2]);
     WorkCounters wc = {0, 0, {0, 0, 0, 0}, 0, 0, 0};
@@ -355,6 +366,21 @@ k_trace(Scene sc, Frame f, gpuart_params P, PathBuffers b, int seg_c, int seg_s,
     F3 rdiv = f3(1, 1, 1);
     Trav t; t.state = TRAV_DONE; t.closest = 0; t.hit_prim = GD_NO_PRIM; t.node = 0; t.entry = 0; t.second = 0;
 
+    // this lane takes the query of queue entry i (closest-hit part, then shadow part)
+    auto take_query = [&](uint32_t i) {
+        const bool sh = i >= n_c;
+        const uint32_t s = !sh ? queue_c[i] : i >= sh_base ? b.shadow_queue[i - sh_base] : SLOT_INVALID;
+        if (s != SLOT_INVALID) {
+            slot = s;
+            shadow = sh;
+            refwalk = false;
+            ro = xyz(b.ray_o[s]);
+            rd = sh ? sun : xyz(b.ray_d[s]);
+            rdiv = f3(1 / rd.x, 1 / rd.y, 1 / rd.z);
+            trav_init<GD_BOXES_OF(TYPES)>(sc, Ray{ro, rd}, rdiv, t, st, &wc, COUNT, NEAR && !sh);
+        }
+    };
+
 #ifdef GD_STEP_STATS
     // diagnostic build (never the product): how full the wave's steps are — box steps and the lanes in them, leaf steps and the lanes in
     // them, rounds of the wide loop and the lanes that hold a ray in them, refill episodes (tools/step_stats.py)
@@ -370,6 +396,8 @@ k_trace(Scene sc, Frame f, gpuart_params P, PathBuffers b, int seg_c, int seg_s,
 #ifdef GD_STEP_STATS
         ss_refills++;
 #endif
+        bool in_packet = false;  // wave-uniform: this round walks one packet
+        bool hold = false;       // wave-uniform: the next entries are packet entries, and the wave still holds queries
         while (idle && !exhausted) {
             if (chunk_next == chunk_end) {
                 if (static_end >= q_end) { exhausted = true; break; }
@@ -380,25 +408,28 @@ k_trace(Scene sc, Frame f, gpuart_params P, PathBuffers b, int seg_c, int seg_s,
                 chunk_next = base;
                 chunk_end = min(base + tune.chunk, q_end);
             }
-            uint32_t want = (uint32_t)__popcll(idle), take = min(want, chunk_end - chunk_next);
-            uint32_t rank = (uint32_t)__popcll(idle & ((1ull << lane_id()) - 1));
-            if (slot == SLOT_INVALID && rank < take) {
-                const uint32_t i = chunk_next + rank;
-                const bool sh = i >= n_c;
-                uint32_t s = sh ? b.shadow_queue[i - n_c] : queue_c[i];
-                if (s != SLOT_INVALID) {
-                    slot = s;
-                    shadow = sh;
-                    refwalk = false;
-                    ro = xyz(b.ray_o[s]);
-                    rd = sh ? sun : xyz(b.ray_d[s]);
-                    rdiv = f3(1 / rd.x, 1 / rd.y, 1 / rd.z);
-                    trav_init<GD_BOXES_OF(TYPES)>(sc, Ray{ro, rd}, rdiv, t, st, &wc, COUNT, NEAR && !sh);
-                }
+            if (PACKET_OK && chunk_next >= p_lo) {  // the packet part: the next (up to) 64 entries of the chunk, once the wave is idle
+                if (idle == ~0ull) {
+                    const uint32_t take = min((uint32_t)BLOCK, chunk_end - chunk_next);
+                    if ((uint32_t)lane_id() < take) take_query(chunk_next + (uint32_t)lane_id());
+                    chunk_next += take;
+                    in_packet = true;
+                } else
+                    hold = true;
+                break;
             }
+            uint32_t want = (uint32_t)__popcll(idle), take = min(want, (PACKET_OK ? min(chunk_end, p_lo) : chunk_end) - chunk_next);
+            uint32_t rank = (uint32_t)__popcll(idle & ((1ull << lane_id()) - 1));
+            if (slot == SLOT_INVALID && rank < take) take_query(chunk_next + rank);
             chunk_next += take;
             idle = __ballot(slot == SLOT_INVALID);
             if (take == want) break;
+        }
+        // a packet is walked to its end here; its queries then go through the loops below as finished ones, to be retired
+        if (PACKET_OK && in_packet) {
+            GD_SS_PHASE(ss_t_refill)
+            trav_packet<TYPES>(sc, ro, rd, rdiv, t, st, shadow && any_shadow);
+            GD_SS_PHASE(ss_t_trav)
         }
         const unsigned long long flying = __ballot(slot != SLOT_INVALID && sub == 0);
         GD_SS_PHASE(ss_t_refill)
@@ -472,7 +503,7 @@ k_trace(Scene sc, Frame f, gpuart_params P, PathBuffers b, int seg_c, int seg_s,
             }
             unsigned long long busy = descending | at_leaf;
             if (!busy) break;
-            if (!exhausted && 64u - (uint32_t)__popcll(busy) >= tune.refill_lanes) break;
+            if (!exhausted && !hold && 64u - (uint32_t)__popcll(busy) >= tune.refill_lanes) break;
             // a draining wave may move to pairs / quads once it is down to 32 rays
             if (THIN_OK && exhausted && (uint32_t)__popcll(busy) <= BLOCK / 2) break;
         }
