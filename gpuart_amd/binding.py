@@ -14,6 +14,7 @@ LIBDIR = os.environ.get("GPUART_LIBDIR") or os.path.join(HERE, "lib")  # overrid
 HIP_LIB = os.path.join(LIBDIR, "libgpuart_hip.so")
 HOST_LIB = os.path.join(LIBDIR, "libgpuart.so")
 DENOISE_LIB = os.path.join(LIBDIR, "libgpuart_denoise.so")
+TEMPORAL_LIB = os.path.join(LIBDIR, "libgpuart_temporal.so")
 
 
 class NativeLibraryMissing(RuntimeError):
@@ -70,6 +71,24 @@ def denoise_params(params):
     if unknown:
         raise ValueError("unknown denoiser parameters: %s" % sorted(unknown))
     return DenoiseParams(**dict(DENOISE_DEFAULTS, **params))
+
+
+class TemporalParams(C.Structure):
+    """gpuart_temporal_params (include/gpuart_temporal.h)."""
+    _fields_ = [("max_history", C.c_float), ("plane_tol", C.c_float), ("normal_min", C.c_float)]
+
+
+TEMPORAL_DEFAULTS = dict(max_history=4.0, plane_tol=0.01, normal_min=0.8)
+
+
+def temporal_params(params):
+    """None (the library's defaults), a TemporalParams, or a dict of fields that replace the defaults -> TemporalParams or None."""
+    if params is None or isinstance(params, TemporalParams):
+        return params
+    unknown = set(params) - set(TEMPORAL_DEFAULTS)
+    if unknown:
+        raise ValueError("unknown temporal parameters: %s" % sorted(unknown))
+    return TemporalParams(**dict(TEMPORAL_DEFAULTS, **params))
 
 
 def _user_sphere(us):
@@ -137,6 +156,21 @@ def denoise_lib():
         L.gpuart_denoise_last_error.restype = C.c_char_p
         _denoise = L
     return _denoise
+
+
+_temporal = None
+
+
+def temporal_lib():
+    """libgpuart_temporal.so; raises NativeLibraryMissing if it has not been built (no fallback)."""
+    global _temporal
+    if _temporal is None:
+        if not os.path.exists(TEMPORAL_LIB):
+            raise NativeLibraryMissing("%s not found — run make -C gpuart_amd/csrc; there is no CPU fallback" % TEMPORAL_LIB)
+        L = C.CDLL(TEMPORAL_LIB)
+        L.gpuart_temporal_last_error.restype = C.c_char_p
+        _temporal = L
+    return _temporal
 
 
 def host_lib():
@@ -260,6 +294,27 @@ class TileGeom(C.Structure):
         """Frame rows of the share, in local row order."""
         L = hip_lib()
         return np.array([L.gpuart_hip_frame_row(C.byref(self), C.c_uint32(k)) for k in range(self.th)], np.int64)
+
+
+class TemporalView(C.Structure):
+    """gpuart_temporal_view (include/gpuart_temporal.h): the view a tile was rendered from."""
+    _fields_ = [("pos", C.c_float * 3), ("bottomLeft", C.c_float * 3), ("deltaHorz", C.c_float * 3), ("deltaVert", C.c_float * 3),
+                ("geom", TileGeom), ("userSphere", C.c_float * 4), ("userSphereFlags", C.c_uint32)]
+
+
+def temporal_view(cam, geom, user_sphere=None, us_flags=0):
+    """cam: the 12 floats given to Backend.set_camera (pos, bottomLeft, deltaHorz, deltaVert; more are ignored); geom: a TileGeom
+    (Backend.get_share) or (W, H, x0, y0, tw, th, band_rows, band_stride); user_sphere: (x, y, z, radius) or None."""
+    v = TemporalView()
+    cam = [float(x) for x in cam[:12]]
+    v.pos[:], v.bottomLeft[:], v.deltaHorz[:], v.deltaVert[:] = cam[0:3], cam[3:6], cam[6:9], cam[9:12]
+    if isinstance(geom, TileGeom):
+        C.memmove(C.byref(v.geom), C.byref(geom), C.sizeof(TileGeom))
+    else:
+        v.geom = TileGeom(*[int(g) for g in geom])
+    v.userSphere[:] = [float(x) for x in (user_sphere if user_sphere is not None else (0, 0, 0, 0))]
+    v.userSphereFlags = int(us_flags)
+    return v
 
 
 def share_of_rank(W, H, rank, nranks, band_rows=8):
@@ -788,6 +843,8 @@ class Renderer:
 
     def set_max_path_segments(self, n): self.L.gpuart_renderer_set_max_path_segments(self.h, C.c_uint(n))
     def set_seed(self, seed): self.L.gpuart_renderer_set_seed(self.h, C.c_uint32(seed))
+    def set_min_weight(self, w): self.L.gpuart_renderer_set_min_weight(self.h, C.c_float(w))
+    def set_nearest_first(self, min_prims): return bool(self.L.gpuart_renderer_set_nearest_first(self.h, C.c_uint32(min_prims)))
     def render_direct(self): self.L.gpuart_renderer_render_direct(self.h)
 
     def restart_path_tracing(self, per_pass, per_pixel):
@@ -817,6 +874,27 @@ class Renderer:
         if not self.L.gpuart_renderer_read_denoised(self.h, _p(out), C.byref(p) if p is not None else None):
             raise HipError("read_denoised failed: %s / %s" % (hip_lib().gpuart_hip_last_error().decode(),
                                                               denoise_lib().gpuart_denoise_last_error().decode()))
+        return out
+
+    def set_temporal_history(self, on=True, params=None):
+        """Renderer::SetTemporalHistory: carry path-traced history across set_camera (and user-sphere moves made through the C++
+        API's SetUserSpherePos / SetUserSphereRadius; set_user_sphere also sets emittance and flags, which drops the history);
+        params as Temporal.accumulate, used by the commits."""
+        p = temporal_params(params)
+        if not self.L.gpuart_renderer_set_temporal_history(self.h, C.c_int(1 if on else 0), C.byref(p) if p is not None else None):
+            raise ValueError("temporal parameters out of range")
+
+    def read_preview(self, denoise=None, temporal=None):
+        """Renderer::ReadPreview: the history blended with the accumulator, then denoised, (th, tw, 4) float32; read_denoised while
+        there is no history. denoise as read_denoised's params; temporal as Temporal.accumulate's (None: set_temporal_history's)."""
+        _, _, tw, th = self.tile
+        out = np.empty((th, tw, 4), np.float32)
+        dn, tp = denoise_params(denoise), temporal_params(temporal)
+        if not self.L.gpuart_renderer_read_preview(self.h, _p(out), C.byref(dn) if dn is not None else None,
+                                                   C.byref(tp) if tp is not None else None):
+            raise HipError("read_preview failed: %s / %s / %s" % (hip_lib().gpuart_hip_last_error().decode(),
+                                                                  denoise_lib().gpuart_denoise_last_error().decode(),
+                                                                  temporal_lib().gpuart_temporal_last_error().decode()))
         return out
 
     def finish(self): return bool(self.L.gpuart_renderer_finish(self.h))
@@ -936,3 +1014,93 @@ class Denoiser:
 
     def finish(self):
         self._chk(self.L.gpuart_denoise_finish(self.h))
+
+
+# ---- temporal accumulation (include/gpuart_temporal.h) --------------------------------------------------------------------
+class TemporalError(RuntimeError):
+    """A gpuart_temporal_* call returned an error; `code` is the library's (GPUART_HIP_ERR_*)."""
+    code = None
+
+
+class Temporal:
+    """A gpuart_temporal handle on one device: it owns the history."""
+
+    def __init__(self, device=0):
+        self.L = temporal_lib()
+        self.device = device
+        h = C.c_void_p()
+        self._chk(self.L.gpuart_temporal_create(C.c_int(device), C.byref(h)))
+        self.h = h
+
+    def _chk(self, rc):
+        if rc != 0:
+            e = TemporalError("gpuart_temporal error %d: %s" % (rc, self.L.gpuart_temporal_last_error().decode()))
+            e.code = rc
+            raise e
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.gpuart_temporal_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        """Drops the history."""
+        self._chk(self.L.gpuart_temporal_reset(self.h))
+
+    def accumulate(self, rgba, spp, hits, prims, view, params=None, commit=True, out=None, out_len=None):
+        """Blends the history, re-sampled into `view` (a TemporalView: temporal_view()), with rgba (h, w, 4) float32, the mean of spp
+        paths, guided by the G-buffer of the same tile and view (hits, prims as Denoiser.run); with commit the blend becomes the
+        history. params = None (the defaults), a TemporalParams or a dict of fields that replace the defaults. Returns (blend, len):
+        len (h, w) float32 is the effective sample count behind each pixel. torch tensors on this handle's device run through
+        gpuart_temporal_accumulate (torch's current stream is synchronised first, the handle before returning); NumPy arrays through
+        gpuart_temporal_accumulate_host. out / out_len: where to put the results (new ones otherwise)."""
+        p = temporal_params(params)
+        pp = C.byref(p) if p is not None else None
+        if type(rgba).__module__.startswith("torch"):
+            import torch
+            dev = torch.device("cuda", self.device)
+            if rgba.dtype != torch.float32 or rgba.dim() != 3 or rgba.shape[2] != 4 or not rgba.is_contiguous() or rgba.device != dev:
+                raise ValueError("rgba must be a contiguous (h, w, 4) float32 tensor on %s" % dev)
+            h, w = rgba.shape[0], rgba.shape[1]
+            if hits.dtype != torch.float32 or hits.numel() != h * w * 8 or not hits.is_contiguous() or hits.device != dev:
+                raise ValueError("hits must be a contiguous (h, w, 8) float32 tensor on %s" % dev)
+            if prims.dtype != torch.int32 or prims.numel() != h * w or not prims.is_contiguous() or prims.device != dev:
+                raise ValueError("prims must be a contiguous (h, w) int32 tensor on %s" % dev)
+            res = out if out is not None else torch.empty_like(rgba)
+            if res.dtype != torch.float32 or tuple(res.shape) != (h, w, 4) or not res.is_contiguous() or res.device != dev:
+                raise ValueError("out must be a contiguous (h, w, 4) float32 tensor on %s" % dev)
+            ln = out_len if out_len is not None else torch.empty((h, w), dtype=torch.float32, device=dev)
+            if ln.dtype != torch.float32 or tuple(ln.shape) != (h, w) or not ln.is_contiguous() or ln.device != dev:
+                raise ValueError("out_len must be a contiguous (h, w) float32 tensor on %s" % dev)
+            torch.cuda.current_stream(dev).synchronize()
+            self._chk(self.L.gpuart_temporal_accumulate(self.h, C.c_void_p(rgba.data_ptr()), C.c_uint32(spp), C.c_void_p(hits.data_ptr()),
+                                                        C.c_void_p(prims.data_ptr()), C.c_uint32(w), C.c_uint32(h), C.byref(view), pp,
+                                                        C.c_int(1 if commit else 0), C.c_void_p(res.data_ptr()), C.c_void_p(ln.data_ptr())))
+            self.finish()
+            return res, ln
+        rgba = np.ascontiguousarray(rgba, np.float32)
+        if rgba.ndim != 3 or rgba.shape[2] != 4:
+            raise ValueError("rgba must be (h, w, 4) float32")
+        h, w = rgba.shape[:2]
+        hits = np.ascontiguousarray(hits)
+        prims = np.ascontiguousarray(prims, np.int32)
+        if hits.nbytes != h * w * 32 or prims.size != h * w:
+            raise ValueError("hits must hold h*w 32-byte records and prims h*w ordinals")
+        res = out if out is not None else np.empty_like(rgba)
+        if res.dtype != np.float32 or res.shape != (h, w, 4) or not res.flags.c_contiguous:
+            raise ValueError("out must be a contiguous (h, w, 4) float32 array")
+        ln = out_len if out_len is not None else np.empty((h, w), np.float32)
+        if ln.dtype != np.float32 or ln.shape != (h, w) or not ln.flags.c_contiguous:
+            raise ValueError("out_len must be a contiguous (h, w) float32 array")
+        self._chk(self.L.gpuart_temporal_accumulate_host(self.h, _p(rgba), C.c_uint32(spp), _p(hits), _p(prims), C.c_uint32(w), C.c_uint32(h),
+                                                         C.byref(view), pp, C.c_int(1 if commit else 0), _p(res), _p(ln)))
+        return res, ln
+
+    def finish(self):
+        self._chk(self.L.gpuart_temporal_finish(self.h))

@@ -265,6 +265,14 @@ int gpuart_renderer_read_radiance(gpuart_renderer *r, float *rgba, int normalize
 int gpuart_renderer_read_denoised(gpuart_renderer *r, float *rgba, const gpuart_denoise_params *p) {
     return r->impl.ReadDenoised(rgba, p) ? 1 : 0;
 }
+void gpuart_renderer_set_min_weight(gpuart_renderer *r, float w) { r->impl.SetMinWeight(w); }
+int gpuart_renderer_set_nearest_first(gpuart_renderer *r, uint32_t minPrims) { return r->impl.SetNearestFirst(minPrims) ? 1 : 0; }
+int gpuart_renderer_set_temporal_history(gpuart_renderer *r, int on, const gpuart_temporal_params *tp) {
+    return r->impl.SetTemporalHistory(on != 0, tp) ? 1 : 0;
+}
+int gpuart_renderer_read_preview(gpuart_renderer *r, float *rgba, const gpuart_denoise_params *dn, const gpuart_temporal_params *tp) {
+    return r->impl.ReadPreview(rgba, dn, tp) ? 1 : 0;
+}
 int gpuart_renderer_finish(gpuart_renderer *r) { return r->impl.Finish() ? 1 : 0; }
 int gpuart_renderer_save_checkpoint(gpuart_renderer *r, const char *path) { return r->impl.SaveCheckpoint(path) ? 1 : 0; }
 int gpuart_renderer_load_checkpoint(gpuart_renderer *r, const char *path) { return r->impl.LoadCheckpoint(path) ? 1 : 0; }

@@ -8,6 +8,7 @@
 
 #include "gpuart_denoise.h"
 #include "gpuart_hip.h"
+#include "gpuart_temporal.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -78,6 +79,15 @@ int gpuart_renderer_read_radiance(gpuart_renderer *r, float *rgba, int normalize
 /* Renderer::ReadDenoised: the denoised preview of the normalised accumulator (include/gpuart_denoise.h); p = NULL: the defaults.
  * 1 on success, 0 on error. */
 int gpuart_renderer_read_denoised(gpuart_renderer *r, float *rgba, const gpuart_denoise_params *p);
+/* Renderer::SetMinWeight / SetNearestFirst (1 on success). */
+void gpuart_renderer_set_min_weight(gpuart_renderer *r, float w);
+int gpuart_renderer_set_nearest_first(gpuart_renderer *r, uint32_t minPrims);
+/* Renderer::SetTemporalHistory: carry path-traced history across camera and user-sphere moves (include/gpuart_temporal.h); off by
+ * default. tp = NULL: the library's defaults. 1 on success, 0 for parameters out of range. */
+int gpuart_renderer_set_temporal_history(gpuart_renderer *r, int on, const gpuart_temporal_params *tp);
+/* Renderer::ReadPreview: the history blended with the accumulator, then denoised; what gpuart_renderer_read_denoised returns while
+ * there is no history. dn, tp = NULL: the defaults / what gpuart_renderer_set_temporal_history was given. 1 on success, 0 on error. */
+int gpuart_renderer_read_preview(gpuart_renderer *r, float *rgba, const gpuart_denoise_params *dn, const gpuart_temporal_params *tp);
 int gpuart_renderer_finish(gpuart_renderer *r);
 int gpuart_renderer_save_checkpoint(gpuart_renderer *r, const char *path);
 int gpuart_renderer_load_checkpoint(gpuart_renderer *r, const char *path);

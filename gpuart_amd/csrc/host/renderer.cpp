@@ -63,6 +63,7 @@ Renderer::Renderer(unsigned viewportWidth, unsigned viewportHeight, const Camera
     PathTracing.numPathsRendered = 0;
     CurrentCamera = camera;
     Device = device;
+    gpuart_temporal_defaults(&TemporalParams);
 
     if (!Check(gpuart_hip_create(device, &Backend), "creating the device back end")) return;
     if (viewportWidth == 0 || viewportHeight == 0) {
@@ -74,6 +75,7 @@ Renderer::Renderer(unsigned viewportWidth, unsigned viewportHeight, const Camera
 }
 
 Renderer::~Renderer() {
+    if (Temporal) gpuart_temporal_destroy(Temporal);
     if (Denoiser) gpuart_denoise_destroy(Denoiser);
     if (DenoiseMem) (void)hipFree(DenoiseMem);
     if (Backend) gpuart_hip_destroy(Backend);
@@ -89,6 +91,8 @@ bool Renderer::UpdateViewportSize(unsigned width, unsigned height) {
     if (!Backend || width == 0 || height == 0) return IsOK = false;
     Viewport.width = width;
     Viewport.height = height;
+    DropTemporalHistory();
+    PathTracing.numPathsRendered = 0;  // (the resize clears the accumulator: the SetCamera below has no view to commit)
     if (!Check(gpuart_hip_resize(Backend, width, height), "allocating per-pixel buffers")) return IsOK = false;
     Tile.x = Tile.y = 0; Tile.w = width; Tile.h = height;
     GBufferValid = false;
@@ -101,6 +105,7 @@ bool Renderer::SetTile(unsigned x0, unsigned y0, unsigned w, unsigned h) {
     if (!Check(gpuart_hip_set_tile(Backend, x0, y0, w, h), "setting the tile")) return false;
     Tile.x = x0; Tile.y = y0; Tile.w = w; Tile.h = h;
     GBufferValid = false;
+    DropTemporalHistory();
     ResetPathTracing();
     return true;
 }
@@ -112,6 +117,7 @@ bool Renderer::SetInterleavedTile(unsigned x0, unsigned y0, unsigned w, unsigned
         return false;
     Tile.x = x0; Tile.y = y0; Tile.w = w; Tile.h = localRows;
     GBufferValid = false;
+    DropTemporalHistory();
     ResetPathTracing();
     return true;
 }
@@ -119,6 +125,7 @@ bool Renderer::SetInterleavedTile(unsigned x0, unsigned y0, unsigned w, unsigned
 bool Renderer::SetNearestFirst(uint32_t minPrims) {
     if (!Backend) return false;
     if (!Check(gpuart_hip_set_nearest_first(Backend, minPrims), "choosing the visiting order")) return false;
+    DropTemporalHistory();
     ResetPathTracing();
     return true;
 }
@@ -183,10 +190,12 @@ bool Renderer::ReleaseCommunicator(Renderer *const *ranks, int n) {
 }
 
 bool Renderer::SetCamera(const Camera &cam) {
+    CommitTemporalView();
     CurrentCamera = cam;
     GBufferValid = false;
     if (!Backend) return false;
     const ScreenBasis s = ComputeScreenBasis(cam, Viewport.width, Viewport.height);
+    CurrentBasis = s;
     float pos[3], bl[3], dh[3], dv[3];
     s.Pos.storeIn(pos); s.BottomLeft.storeIn(bl); s.DeltaHorz.storeIn(dh); s.DeltaVert.storeIn(dv);
     if (!Check(gpuart_hip_set_camera(Backend, pos, bl, dh, dv), "setting the camera")) return false;
@@ -226,6 +235,7 @@ void Renderer::SetPrimitives(std::vector<Primitive *> &primitives, bool printInf
     Tree.CompileTo(compiled.get());
     const auto tCompiled = std::chrono::high_resolution_clock::now();
     GBufferValid = false;
+    DropTemporalHistory();
     if (printInfo) std::cout << "done (" << Utils::TimeElapsed(t0) << ").\n";
     if (!Backend || !Check(gpuart_hip_upload_bvh(Backend, compiled.get(), compiledFloats / RGBA_ELEMS), "uploading the BVH"))
         IsOK = false;
@@ -271,12 +281,14 @@ void Renderer::SetUserSphere(const Vec3f &pos, float radius, float emittance) {
 
 void Renderer::SetUserSphereEmittance(float em) {
     UserSphere.emittance = em;
+    DropTemporalHistory();
     SetFlag(EM_NONZERO, em > 0);
 }
 
 void Renderer::SetFlag(uint32_t flag, bool on) {
     if (on) UserSphere.flags |= flag;
     else UserSphere.flags &= ~flag;
+    DropTemporalHistory();
     ResetPathTracing();
 }
 
@@ -355,19 +367,35 @@ bool Renderer::ReadRadiance(float *rgba, bool normalized) {
     return IsOK && Check(gpuart_hip_read(Backend, 1, rgba, div), "reading the radiance accumulator");
 }
 
-bool Renderer::ReadDenoised(float *rgba, const gpuart_denoise_params *p) {
-    if (!IsOK || !rgba) return false;
-    auto checkDn = [](int status, const char *what) {
-        if (status == 0) return true;
-        std::cerr << "Renderer: error " << status << " while " << what << ": " << gpuart_denoise_last_error() << std::endl;
-        return false;
-    };
-    auto checkHip = [](hipError_t e, const char *what) {
-        if (e == hipSuccess) return true;
-        std::cerr << "Renderer: " << what << ": " << hipGetErrorString(e) << std::endl;
-        return false;
-    };
-    if (!Denoiser && !checkDn(gpuart_denoise_create(Device, &Denoiser), "creating the denoiser")) return false;
+namespace {
+bool checkDn(int status, const char *what) {
+    if (status == 0) return true;
+    std::cerr << "Renderer: error " << status << " while " << what << ": " << gpuart_denoise_last_error() << std::endl;
+    return false;
+}
+bool checkTp(int status, const char *what) {
+    if (status == 0) return true;
+    std::cerr << "Renderer: error " << status << " while " << what << ": " << gpuart_temporal_last_error() << std::endl;
+    return false;
+}
+bool checkHip(hipError_t e, const char *what) {
+    if (e == hipSuccess) return true;
+    std::cerr << "Renderer: " << what << ": " << hipGetErrorString(e) << std::endl;
+    return false;
+}
+/// The parts of DenoiseMem for a tile of n pixels.
+struct ViewBuffers {
+    float *radiance;
+    gpuart_ray_hit *hits;
+    float *filtered;
+    int32_t *prims;
+    ViewBuffers(void *mem, size_t n)
+        : radiance((float *)mem), hits((gpuart_ray_hit *)((char *)mem + n * 16)), filtered((float *)((char *)mem + n * 48)),
+          prims((int32_t *)((char *)mem + n * 64)) {}
+};
+}  // namespace
+
+bool Renderer::StageView() {
     if (!checkHip(hipSetDevice(Device), "hipSetDevice")) return false;
     const size_t n = (size_t)Tile.w * Tile.h;
     if (n != DenoisePixels) {
@@ -378,25 +406,96 @@ bool Renderer::ReadDenoised(float *rgba, const gpuart_denoise_params *p) {
         if (!checkHip(hipMalloc(&DenoiseMem, n * (16 + 32 + 16 + 4)), "allocating the denoiser's buffers")) return false;
         DenoisePixels = n;
     }
-    char *m = (char *)DenoiseMem;
-    float *radiance = (float *)m;
-    gpuart_ray_hit *hits = (gpuart_ray_hit *)(m + n * 16);
-    float *filtered = (float *)(m + n * 48);
-    int32_t *prims = (int32_t *)(m + n * 64);
+    const ViewBuffers b(DenoiseMem, n);
     const float us[4] = {UserSphere.pos.x, UserSphere.pos.y, UserSphere.pos.z, UserSphere.radius};
     if (!GBufferValid || memcmp(us, GBufferSphere, sizeof us) != 0) {
         GBufferValid = false;
-        if (!Check(gpuart_hip_gbuffer(Backend, us, hits, prims), "building the G-buffer")) return false;
+        if (!Check(gpuart_hip_gbuffer(Backend, us, b.hits, b.prims), "building the G-buffer")) return false;
         memcpy(GBufferSphere, us, sizeof us);
         GBufferValid = true;
     }
     // the division is the reference's ptracingNormalize program (shaders/pt_normalize.glsl:44-47), as in ReadRadiance
     const float div = PathTracing.numPathsRendered ? (float)PathTracing.numPathsRendered : 1.0f;
-    if (!Check(gpuart_hip_export(Backend, 1, radiance, div), "exporting the radiance")) return false;
-    if (!Check(gpuart_hip_finish(Backend), "waiting for the device")) return false;
-    if (!checkDn(gpuart_denoise_run(Denoiser, radiance, hits, prims, UserSphere.flags, Tile.w, Tile.h, p, filtered), "denoising")) return false;
+    if (!Check(gpuart_hip_export(Backend, 1, b.radiance, div), "exporting the radiance")) return false;
+    return Check(gpuart_hip_finish(Backend), "waiting for the device");
+}
+
+bool Renderer::ReadDenoised(float *rgba, const gpuart_denoise_params *p) {
+    if (!IsOK || !rgba) return false;
+    if (!Denoiser && !checkDn(gpuart_denoise_create(Device, &Denoiser), "creating the denoiser")) return false;
+    if (!StageView()) return false;
+    const size_t n = (size_t)Tile.w * Tile.h;
+    const ViewBuffers b(DenoiseMem, n);
+    if (!checkDn(gpuart_denoise_run(Denoiser, b.radiance, b.hits, b.prims, UserSphere.flags, Tile.w, Tile.h, p, b.filtered), "denoising")) return false;
     if (!checkDn(gpuart_denoise_finish(Denoiser), "denoising")) return false;
-    return checkHip(hipMemcpy(rgba, filtered, n * 16, hipMemcpyDeviceToHost), "reading the denoised frame");
+    return checkHip(hipMemcpy(rgba, b.filtered, n * 16, hipMemcpyDeviceToHost), "reading the denoised frame");
+}
+
+// ---- temporal history (include/gpuart_temporal.h) ---------------------------------------------------------------------
+bool Renderer::SetTemporalHistory(bool on, const gpuart_temporal_params *tp) {
+    if (tp) {
+        // the ranges gpuart_temporal_accumulate accepts: a commit inside a setter has nobody to report them to
+        auto finite = [](float x) { return x - x == 0.0f; };
+        if (!finite(tp->max_history) || !(tp->max_history >= 0) || !finite(tp->plane_tol) || !(tp->plane_tol >= 0) ||
+            !(tp->normal_min >= -1) || !(tp->normal_min <= 1)) {
+            std::cerr << "Renderer: temporal parameters out of range." << std::endl;
+            return false;
+        }
+        TemporalParams = *tp;
+    } else {
+        gpuart_temporal_defaults(&TemporalParams);
+    }
+    if (!on) DropTemporalHistory();
+    TemporalOn = on;
+    return true;
+}
+
+void Renderer::DropTemporalHistoryNow() {
+    if (Temporal) gpuart_temporal_reset(Temporal);
+    HistoryCommitted = false;
+}
+
+bool Renderer::MakeTemporalView(gpuart_temporal_view &v) const {
+    CurrentBasis.Pos.storeIn(v.pos); CurrentBasis.BottomLeft.storeIn(v.bottomLeft);
+    CurrentBasis.DeltaHorz.storeIn(v.deltaHorz); CurrentBasis.DeltaVert.storeIn(v.deltaVert);
+    if (gpuart_hip_get_share(Backend, &v.geom) != 0) return false;
+    v.userSphere[0] = UserSphere.pos.x; v.userSphere[1] = UserSphere.pos.y; v.userSphere[2] = UserSphere.pos.z;
+    v.userSphere[3] = UserSphere.radius;
+    v.userSphereFlags = UserSphere.flags;
+    return true;
+}
+
+void Renderer::CommitTemporalView() {
+    if (!TemporalOn || !IsOK || PathTracing.numPathsRendered == 0) return;
+    // A commit that fails leaves no history rather than a stale one.
+    bool ok = Temporal || checkTp(gpuart_temporal_create(Device, &Temporal), "creating the temporal accumulator");
+    gpuart_temporal_view v;
+    ok = ok && StageView() && MakeTemporalView(v);
+    if (ok) {
+        const ViewBuffers b(DenoiseMem, (size_t)Tile.w * Tile.h);
+        ok = checkTp(gpuart_temporal_accumulate(Temporal, b.radiance, PathTracing.numPathsRendered, b.hits, b.prims, Tile.w, Tile.h, &v,
+                                                &TemporalParams, 1, b.filtered, nullptr), "committing the view to the history") &&
+             checkTp(gpuart_temporal_finish(Temporal), "committing the view to the history");
+    }
+    HistoryCommitted = ok;
+    if (!ok && Temporal) gpuart_temporal_reset(Temporal);
+}
+
+bool Renderer::ReadPreview(float *rgba, const gpuart_denoise_params *dn, const gpuart_temporal_params *tp) {
+    if (!TemporalOn || !HistoryCommitted || PathTracing.numPathsRendered == 0) return ReadDenoised(rgba, dn);
+    if (!IsOK || !rgba) return false;
+    if (!Denoiser && !checkDn(gpuart_denoise_create(Device, &Denoiser), "creating the denoiser")) return false;
+    gpuart_temporal_view v;
+    if (!StageView() || !MakeTemporalView(v)) return false;
+    const size_t n = (size_t)Tile.w * Tile.h;
+    const ViewBuffers b(DenoiseMem, n);
+    if (!checkTp(gpuart_temporal_accumulate(Temporal, b.radiance, PathTracing.numPathsRendered, b.hits, b.prims, Tile.w, Tile.h, &v,
+                                            tp ? tp : &TemporalParams, 0, b.filtered, nullptr), "blending the history")) return false;
+    if (!checkTp(gpuart_temporal_finish(Temporal), "blending the history")) return false;
+    // (the filter may run in place: include/gpuart_denoise.h)
+    if (!checkDn(gpuart_denoise_run(Denoiser, b.filtered, b.hits, b.prims, UserSphere.flags, Tile.w, Tile.h, dn, b.filtered), "denoising")) return false;
+    if (!checkDn(gpuart_denoise_finish(Denoiser), "denoising")) return false;
+    return checkHip(hipMemcpy(rgba, b.filtered, n * 16, hipMemcpyDeviceToHost), "reading the preview");
 }
 
 // ---- checkpoint / resume ---------------------------------------------------------------------------------------------
@@ -457,6 +556,7 @@ bool Renderer::LoadCheckpoint(const char *fileName) {
     if (rng.fail()) return false;
     if (!Check(gpuart_hip_write(Backend, 1, acc.data()), "restoring the radiance accumulator")) return false;
     RndGen = gen;
+    DropTemporalHistory();
     PathTracing.numPathsRendered = h.numPathsRendered;
     PathTracing.pathsPerPixel = h.pathsPerPixel;
     PathTracing.pathsPerPass = h.pathsPerPass;

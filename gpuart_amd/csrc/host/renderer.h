@@ -7,7 +7,7 @@
 // Additions (the reference draws into the GL framebuffer, which no longer exists, and has
 // MAX_PATH_SEGMENTS / the RNG seed / the viewport fixed at compile time):
 //   ReadDirectLighting, ReadRadiance, Finish, SetMaxPathSegments, SetMinWeight, SetSeed,
-//   SetTile, GetBackend, ComputeScreenBasis, GetNumPathsRendered.
+//   SetTile, GetBackend, ComputeScreenBasis, GetNumPathsRendered, ReadDenoised, SetTemporalHistory, ReadPreview.
 #ifndef GPUART_RENDERER_H
 #define GPUART_RENDERER_H
 
@@ -19,6 +19,7 @@
 #include "core.h"
 #include "gpuart_denoise.h"
 #include "gpuart_hip.h"
+#include "gpuart_temporal.h"
 #include "math_types.h"
 
 namespace gpuart {
@@ -55,19 +56,19 @@ public:
     bool UpdateViewportSize(unsigned width, unsigned height);
     bool SetCamera(const Camera &cam);
 
-    void SetSunAzimuth(float azimuth) { Lighting.azimuth = azimuth; ResetPathTracing(); }
+    void SetSunAzimuth(float azimuth) { Lighting.azimuth = azimuth; DropTemporalHistory(); ResetPathTracing(); }
     float GetSunAzimuth() const { return Lighting.azimuth; }
-    void SetSunAltitude(float altitude) { Lighting.altitude = altitude; ResetPathTracing(); }
+    void SetSunAltitude(float altitude) { Lighting.altitude = altitude; DropTemporalHistory(); ResetPathTracing(); }
     float GetSunAltitude() const { return Lighting.altitude; }
-    void SetSunDirectLighting(bool enabled = true) { Lighting.directLightingEnabled = enabled; ResetPathTracing(); }
+    void SetSunDirectLighting(bool enabled = true) { Lighting.directLightingEnabled = enabled; DropTemporalHistory(); ResetPathTracing(); }
     bool IsSunDirectLightingEnabled() const { return Lighting.directLightingEnabled; }
 
     /// Use radius = 0 to effectively disable the user-controlled sphere.
     void SetUserSphere(const Vec3f &pos, float radius, float emittance);
     void SetUserSphereSpecular(bool specular) { SetFlag(SPECULAR, specular); }
     void SetUserSphereFuzzy(bool fuzzy) { SetFlag(FUZZY, fuzzy); }
-    void SetUserSphereRadius(float radius) { UserSphere.radius = radius; ResetPathTracing(); }
-    void SetUserSpherePos(const Vec3f &pos) { UserSphere.pos = pos; ResetPathTracing(); }
+    void SetUserSphereRadius(float radius) { CommitTemporalView(); UserSphere.radius = radius; ResetPathTracing(); }
+    void SetUserSpherePos(const Vec3f &pos) { CommitTemporalView(); UserSphere.pos = pos; ResetPathTracing(); }
     void SetUserSphereEmittance(float em);
     Vec3f GetUserSpherePos() const { return UserSphere.pos; }
     float GetUserSphereRadius() const { return UserSphere.radius; }
@@ -90,10 +91,24 @@ public:
     /// tile changes). RGBA32F, tile-sized, row 0 = bottom row; p = nullptr: the defaults. The accumulator, the passes that follow and
     /// the counters are not touched. Synchronises.
     bool ReadDenoised(float *rgba, const gpuart_denoise_params *p = nullptr);
+    /// Carries path-traced history across camera and user-sphere moves (include/gpuart_temporal.h); off by default. While it is on,
+    /// SetCamera, SetUserSpherePos and SetUserSphereRadius first commit the view they are about to leave, if it has at least one path
+    /// rendered: its normalised accumulator and G-buffer are blended with the history (parameters `tp`; nullptr: the library's
+    /// defaults) and become the history. Every other call that restarts the accumulation drops the history — the scene, the Sun, the
+    /// user sphere's emittance and flags (SetUserSphere included: it sets the emittance), the path limits, the seed, the visiting
+    /// order, the viewport, the tile or share, a loaded checkpoint — and so does switching it off. RestartPathTracing keeps it.
+    /// While it is off no setter does any work for it. False for parameters out of range (nothing changes).
+    bool SetTemporalHistory(bool on, const gpuart_temporal_params *tp = nullptr);
+    bool GetTemporalHistory() const { return TemporalOn; }
+    /// The preview while things move: the history re-sampled into the current view and blended with the current accumulator
+    /// (gpuart_temporal_accumulate without commit; tp = nullptr: what SetTemporalHistory was given), then filtered like ReadDenoised
+    /// (dn). Exactly ReadDenoised while history is off, before the first commit, and before the view's first path. The history, the
+    /// accumulator, the passes that follow and the counters are not touched. Synchronises.
+    bool ReadPreview(float *rgba, const gpuart_denoise_params *dn = nullptr, const gpuart_temporal_params *tp = nullptr);
     bool Finish();
-    void SetMaxPathSegments(unsigned n) { MaxPathSegments = n; ResetPathTracing(); }
-    void SetMinWeight(float w) { MinWeight = w; ResetPathTracing(); }
-    void SetSeed(uint32_t seed) { RndGen.seed(seed); ResetPathTracing(); }
+    void SetMaxPathSegments(unsigned n) { MaxPathSegments = n; DropTemporalHistory(); ResetPathTracing(); }
+    void SetMinWeight(float w) { MinWeight = w; DropTemporalHistory(); ResetPathTracing(); }
+    void SetSeed(uint32_t seed) { RndGen.seed(seed); DropTemporalHistory(); ResetPathTracing(); }
     /// Opts in to the nearer-child-first BVH walk for trees of at least minPrims primitives (0xffffffff = never, the default): ~10 % faster,
     /// soak-verified but NOT proven to return the reference's winner — the reference's phantom hits of grazing triangles are a property
     /// of its own visiting order (include/gpuart_hip.h gpuart_hip_set_nearest_first). Restarts the accumulation like every setter.
@@ -150,6 +165,11 @@ private:
     size_t DenoisePixels = 0;
     bool GBufferValid = false;           ///< DenoiseMem holds the G-buffer of this camera, scene and tile for GBufferSphere
     float GBufferSphere[4] = {0, 0, 0, 0};
+    gpuart_temporal *Temporal = nullptr;  ///< made by the first commit
+    bool TemporalOn = false;
+    bool HistoryCommitted = false;        ///< Temporal holds a history
+    gpuart_temporal_params TemporalParams{};  ///< of the commits (SetTemporalHistory)
+    ScreenBasis CurrentBasis;             ///< what SetCamera gave the back end
     double LastSetPrimitivesMs[4] = {0, 0, 0, 0};
     gpuart_hip_ctx *Backend = nullptr;
     BoundingVolumesHierarchy Tree;
@@ -165,6 +185,12 @@ private:
 
     void SetFlag(uint32_t flag, bool on);
     void ResetPathTracing();
+    /// The device buffers of ReadDenoised / ReadPreview / a commit, the G-buffer of the current view (cached) and the normalised accumulator.
+    bool StageView();
+    bool MakeTemporalView(gpuart_temporal_view &v) const;
+    void CommitTemporalView();
+    void DropTemporalHistory() { if (HistoryCommitted) DropTemporalHistoryNow(); }
+    void DropTemporalHistoryNow();
     bool Check(int status, const char *what);
 };
 
