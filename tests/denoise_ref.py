@@ -43,15 +43,29 @@ def shift(a, oy, ox):
     return out, inside
 
 
-def denoise(rgba, words, prims, us_flags=0, iterations=5, lum_k=4.0, normal_pow2=5, depth_sigma=0.05):
+LEDGER_KEYS = ("not_surface", "den_zero", "pos_small", "var_clamped", "tap_outside", "tap_not_surface", "denormal_out", "denormal_state")
+TINY = np.finfo(np.float32).tiny
+
+
+def denormals(a):
+    """How many values of a are fp32 denormals."""
+    return int(((a != 0) & (np.abs(a) < TINY)).sum())
+
+
+def denoise(rgba, words, prims, us_flags=0, iterations=5, lum_k=4.0, normal_pow2=5, depth_sigma=0.05, want_ledger=False):
+    """-> out (h, w, 4)[, ledger]. The ledger (LEDGER_KEYS -> count) says how many pixels (den_zero: per level) and taps (per level)
+    took each branch, counted from the very masks that select the values below, and how many values of the outputs and of the state
+    (x and var, before the first level and after each) are fp32 denormals."""
     c = np.array(rgba, np.float32)
     words = np.asarray(words).view(np.float32).reshape(c.shape[:2] + (8,))
     prims = np.asarray(prims, np.int32).reshape(c.shape[:2])
     out = c.copy()
+    led = dict.fromkeys(LEDGER_KEYS, 0)
     if iterations == 0:
-        return out
+        return (out, led) if want_ledger else out
     with np.errstate(all="ignore"):
         surf, t = surface(words, prims, us_flags)
+        led["not_surface"] = int((~surf).sum())
         a = PRIMITIVE_COLOR[t]
         # 1. demodulation and luminance
         x = np.where(surf[..., None], c[..., :3] / a, F(0)).astype(np.float32)
@@ -67,15 +81,22 @@ def denoise(rgba, words, prims, us_flags=0, iterations=5, lum_k=4.0, normal_pow2
                 m1 = np.where(v, m1 + Lq, m1)
                 m2 = np.where(v, m2 + Lq * Lq, m2)
         mean = m1 / cnt
-        var = gt_or(m2 / cnt - mean * mean, 0.0)
+        raw = m2 / cnt - mean * mean
+        keep = raw > F(0)    # gt_or(raw, 0)
+        var = np.where(keep, raw, F(0)).astype(np.float32)
+        led["var_clamped"] = int((surf & ~keep & (raw < 0)).sum())
         n = np.ascontiguousarray(words[..., 4:7])
         pos = np.ascontiguousarray(words[..., 0])
+        far = pos > F(1e-6)    # gt_or(pos, 1e-6)
+        zpos = np.where(far, pos, F(1e-6)).astype(np.float32)
+        led["pos_small"] = int((surf & ~far).sum())
+        led["denormal_state"] = denormals(x[surf]) + denormals(var[surf])
         # 3. the à-trous levels
         for i in range(iterations):
             s = 1 << i
             Lp = lum(x)
             sd = np.sqrt(var) * F(lum_k) + F(1e-4)
-            zs = (F(depth_sigma) * gt_or(pos, 1e-6)) * F(s)
+            zs = (F(depth_sigma) * zpos) * F(s)
             num = np.zeros_like(x)
             den = np.zeros(c.shape[:2], np.float32)
             nv = np.zeros(c.shape[:2], np.float32)
@@ -86,7 +107,10 @@ def denoise(rgba, words, prims, us_flags=0, iterations=5, lum_k=4.0, normal_pow2
                     nq, _ = shift(n, s * dy, s * dx)
                     pq, _ = shift(pos, s * dy, s * dx)
                     sq, _ = shift(surf, s * dy, s * dx)
-                    v = inside & sq & surf
+                    v = surf & inside
+                    led["tap_outside"] += int((surf & ~inside).sum())
+                    led["tap_not_surface"] += int((v & ~sq).sum())
+                    v = v & sq
                     hk = H[dy + 2] * H[dx + 2]
                     e = (lum(xq) - Lp) / sd
                     wl = F(1) / (F(1) + e * e)
@@ -100,8 +124,11 @@ def denoise(rgba, words, prims, us_flags=0, iterations=5, lum_k=4.0, normal_pow2
                     den = np.where(v, den + wt, den)
                     nv = np.where(v, nv + (wt * wt) * vq, nv)
             upd = surf & (den > 0)
+            led["den_zero"] += int((surf & ~(den > 0)).sum())
             x = np.where(upd[..., None], num / den[..., None], x)
             var = np.where(upd, nv / (den * den), var)
+            led["denormal_state"] += denormals(x[surf]) + denormals(var[surf])
         # 4. remodulation; every other pixel is copied, alpha everywhere
         out[..., :3] = np.where(surf[..., None], x * a, c[..., :3])
-    return out
+        led["denormal_out"] = denormals(out[..., :3][surf])
+    return (out, led) if want_ledger else out

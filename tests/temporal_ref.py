@@ -62,8 +62,23 @@ def backproject(p, v):
     return fx, fy, k, dn, d
 
 
-def accumulate(hist, rgba, spp, words, prims, cur_view, max_history=4.0, plane_tol=0.01, normal_min=0.8, want_coords=False):
-    """-> (out (h, w, 4), len (h, w), the history a commit leaves[, (fx, fy)])."""
+LEDGER_PIXEL = ("not_surface", "no_history", "dn_zero", "behind", "off_left", "off_right", "off_below", "off_above", "x0_minus_1", "y0_minus_1",
+                "wsum_zero", "found_uncapped", "found_capped")
+LEDGER_TAP = ("tap_off_frame", "tap_off_columns", "tap_below_share", "tap_band_gap", "tap_past_share", "tap_class", "tap_sphere_moved",
+              "tap_normal", "tap_plane", "tap_valid")
+LEDGER_KEYS = LEDGER_PIXEL + LEDGER_TAP
+
+
+def accumulate(hist, rgba, spp, words, prims, cur_view, max_history=4.0, plane_tol=0.01, normal_min=0.8, want_coords=False, want_ledger=False,
+               ignore_k=False):
+    """-> (out (h, w, 4), len (h, w), the history a commit leaves[, (fx, fy)][, ledger]).
+
+    ignore_k is for the tests of the tests alone: it drops "k > 0" from the has-taps condition, as a wrong kernel might, so that a CPU
+    test can show that the cases hold pixels whose value depends on that condition.
+
+    The ledger (LEDGER_KEYS -> count) says how many pixels, and how many taps in the kernel's order of tests, took each branch. Every
+    count is the population of the very mask that selects the values below — a tap leaves `ok` where it is counted — so a branch
+    counted is a branch taken."""
     c = np.array(rgba, np.float32)
     h, w = c.shape[:2]
     words = np.ascontiguousarray(words).view(np.float32).reshape(h, w, 8)
@@ -77,8 +92,18 @@ def accumulate(hist, rgba, spp, words, prims, cur_view, max_history=4.0, plane_t
     out = c.copy()
     ln = np.where(surf, s, F(0)).astype(np.float32)
     coords = None
+    led = dict.fromkeys(LEDGER_KEYS, 0)
+    led["not_surface"] = int((~surf).sum())
+
+    def cut(ok, key, gone):
+        """The taps of `ok` that `gone` takes out are counted under `key` and leave."""
+        led[key] += int((ok & gone).sum())
+        return ok & ~gone
+
     with np.errstate(all="ignore"):
-        if hist is not None:
+        if hist is None:
+            led["no_history"] = int(surf.sum())
+        else:
             hv = hist["view"]
             Wo, Ho, gx0, gy0, tw, th, br, bs = hv["geom"]
             sphere_same = hv["user_sphere"].tobytes() == cur_view["user_sphere"].tobytes()
@@ -87,7 +112,15 @@ def accumulate(hist, rgba, spp, words, prims, cur_view, max_history=4.0, plane_t
             x0, y0 = np.floor(fx), np.floor(fy)
             ax, ay = fx - x0, fy - y0
             tol = F(plane_tol) * np.sqrt(dot(d, d))
-            has = surf & (dn != 0) & (k > 0) & (x0 >= -1) & (x0 < F(Wo)) & (y0 >= -1) & (y0 < F(Ho))
+            front = surf & (dn != 0) & ((k > 0) | bool(ignore_k))
+            x_lo, x_hi, y_lo, y_hi = x0 >= -1, x0 < F(Wo), y0 >= -1, y0 < F(Ho)
+            has = front & x_lo & x_hi & y_lo & y_hi
+            led["dn_zero"] = int((surf & ~(dn != 0)).sum())
+            led["behind"] = int((surf & (dn != 0) & ~(k > 0)).sum())
+            for key, side in (("off_left", x_lo), ("off_right", x_hi), ("off_below", y_lo), ("off_above", y_hi)):
+                led[key] = int((front & ~side).sum())
+            led["x0_minus_1"] = int((has & (x0 == -1)).sum())
+            led["y0_minus_1"] = int((has & (y0 == -1)).sum())
             ix = np.where(has, x0, 0).astype(np.int64)
             iy = np.where(has, y0, 0).astype(np.int64)
             Wsum, hr, hg, hb, hl = (np.zeros((h, w), np.float32) for _ in range(5))
@@ -96,19 +129,22 @@ def accumulate(hist, rgba, spp, words, prims, cur_view, max_history=4.0, plane_t
                 for ox in (0, 1):
                     wt = wy * (ax if ox else F(1) - ax)
                     tx, ty = ix + ox, iy + oy
-                    ok = has & (tx >= 0) & (tx < Wo) & (ty >= 0) & (ty < Ho)
+                    ok = cut(has, "tap_off_frame", ~((tx >= 0) & (tx < Wo) & (ty >= 0) & (ty < Ho)))
                     lx, ry = tx - gx0, ty - gy0
-                    ok &= (lx >= 0) & (lx < tw) & (ry >= 0)
+                    ok = cut(ok, "tap_off_columns", ~((lx >= 0) & (lx < tw)))
+                    ok = cut(ok, "tap_below_share", ~(ry >= 0))
                     r = ry % bs
                     ly = (ry // bs) * br + r
-                    ok &= (r < br) & (ly < th)
+                    ok = cut(ok, "tap_band_gap", ~(r < br))
+                    ok = cut(ok, "tap_past_share", ~(ly < th))
                     lxc, lyc = np.where(ok, lx, 0), np.where(ok, ly, 0)
-                    ok &= hist["cls"][lyc, lxc] == cls
+                    ok = cut(ok, "tap_class", ~(hist["cls"][lyc, lxc] == cls))
                     if not sphere_same:
-                        ok &= (cls & 4) == 0
+                        ok = cut(ok, "tap_sphere_moved", ~((cls & 4) == 0))
                     nt, pt, hc = hist["n"][lyc, lxc], hist["p"][lyc, lxc], hist["col"][lyc, lxc]
-                    ok &= dot(nt, n) >= F(normal_min)
-                    ok &= np.abs(dot((pt - p).astype(np.float32), n)) <= tol
+                    ok = cut(ok, "tap_normal", ~(dot(nt, n) >= F(normal_min)))
+                    ok = cut(ok, "tap_plane", ~(np.abs(dot((pt - p).astype(np.float32), n)) <= tol))
+                    led["tap_valid"] += int(ok.sum())
                     Wsum = np.where(ok, Wsum + wt, Wsum)
                     hr = np.where(ok, hr + wt * hc[..., 0], hr)
                     hg = np.where(ok, hg + wt * hc[..., 1], hg)
@@ -116,7 +152,11 @@ def accumulate(hist, rgba, spp, words, prims, cur_view, max_history=4.0, plane_t
                     hl = np.where(ok, hl + wt * hc[..., 3], hl)
             found = Wsum > 0
             nh = hl / Wsum
-            nh = np.where(nh < F(max_history), nh, F(max_history)).astype(np.float32)
+            under = nh < F(max_history)
+            led["wsum_zero"] = int((has & ~found).sum())
+            led["found_uncapped"] = int((found & under).sum())
+            led["found_capped"] = int((found & ~under).sum())
+            nh = np.where(under, nh, F(max_history)).astype(np.float32)
             den = nh + s
             for ch, acc in enumerate((hr, hg, hb)):
                 out[..., ch] = np.where(found, (nh * (acc / Wsum) + s * c[..., ch]) / den, c[..., ch])
@@ -124,4 +164,4 @@ def accumulate(hist, rgba, spp, words, prims, cur_view, max_history=4.0, plane_t
     col = out.copy()
     col[..., 3] = ln
     new = dict(col=col, cls=cls, n=n.copy(), p=p.copy(), view=cur_view)
-    return (out, ln, new, coords) if want_coords else (out, ln, new)
+    return (out, ln, new) + ((coords,) if want_coords else ()) + ((led,) if want_ledger else ())

@@ -303,9 +303,11 @@ def gpu_view_data(be, B, O, pos, W, H, passes, us, em, flags, seed):
     return rgba, hits, prims, B.temporal_view(c, g, us, flags), T.view(c, g, us or (0, 0, 0, 0), flags)
 
 
-def run_chain(tp, data, params, what, preview_at=2):
+def run_chain(tp, data, params, what, preview_at=2, ledger=None, alias_at=None):
     """Commits the views of `data` one after the other through both entry points and holds every blend and length to the restatement; before
-    view `preview_at` a call without commit, which must equal the restatement too and leave what follows unchanged."""
+    view `preview_at` a call without commit, which must equal the restatement too and leave what follows unchanged. The views may differ
+    in geometry: each call takes its sizes from its own arrays and the history keeps the geometry it was committed with. `ledger`: a
+    dict that the restatement's branch counts of every call are added to; at view `alias_at` the device call's out_rgba is its rgba."""
     import torch
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
     kw = dict(T.DEFAULTS, **(params or {}))
@@ -317,13 +319,17 @@ def run_chain(tp, data, params, what, preview_at=2):
         words = hits.view(np.float32).reshape(rgba.shape[:2] + (8,))
         commits = [False, True] if i == preview_at else [True]
         for commit in commits:
-            exp, exp_len, new = T.accumulate(hist, rgba, spp, words, prims, ref_view, **kw)
+            exp, exp_len, new, led = T.accumulate(hist, rgba, spp, words, prims, ref_view, want_ledger=True, **kw)
+            if ledger is not None:
+                for k, v in led.items():
+                    ledger[k] = ledger.get(k, 0) + v
             tag = "%s, view %d, commit %d" % (what, i, commit)
             out, ln = tp[0].accumulate(rgba, spp, hits, prims, view, params=params, commit=commit)
             assert_same_bits(out, exp, tag + ", host")
             assert_same_bits(ln, exp_len, tag + ", host, length")
-            dout = torch.full(rgba.shape, 7.0, device="cuda:0")
-            res, dln = tp[1].accumulate(t(rgba), spp, t(words), t(prims), view, params=params, commit=commit, out=dout)
+            d_rgba = t(rgba)
+            dout = d_rgba if i == alias_at else torch.full(rgba.shape, 7.0, device="cuda:0")
+            res, dln = tp[1].accumulate(d_rgba, spp, t(words), t(prims), view, params=params, commit=commit, out=dout)
             assert res is dout
             assert_same_bits(dout.cpu().numpy(), exp, tag + ", torch")
             assert_same_bits(dln.cpu().numpy(), exp_len, tag + ", torch, length")
