@@ -15,6 +15,7 @@ HIP_LIB = os.path.join(LIBDIR, "libgpuart_hip.so")
 HOST_LIB = os.path.join(LIBDIR, "libgpuart.so")
 DENOISE_LIB = os.path.join(LIBDIR, "libgpuart_denoise.so")
 TEMPORAL_LIB = os.path.join(LIBDIR, "libgpuart_temporal.so")
+CONVERGE_LIB = os.path.join(LIBDIR, "libgpuart_converge.so")
 
 
 class NativeLibraryMissing(RuntimeError):
@@ -89,6 +90,21 @@ def temporal_params(params):
     if unknown:
         raise ValueError("unknown temporal parameters: %s" % sorted(unknown))
     return TemporalParams(**dict(TEMPORAL_DEFAULTS, **params))
+
+
+class ConvergeSummary(C.Structure):
+    """gpuart_converge_summary (include/gpuart_converge.h): what a measure says about the frame."""
+    _fields_ = [("pixels", C.c_uint64), ("above", C.c_uint64), ("non_finite", C.c_uint64), ("max_error", C.c_float),
+                ("batches", C.c_uint32), ("total", C.c_uint32)]
+
+    def as_dict(self):
+        return dict(pixels=self.pixels, above=self.above, non_finite=self.non_finite, max_error=float(self.max_error),
+                    batches=self.batches, total=self.total)
+
+
+CONVERGE_MAX_PATHS = 1 << 24    # GPUART_CONVERGE_MAX_PATHS
+CONVERGE_DEFAULT_BATCH = 64     # GPUART_CONVERGE_DEFAULT_BATCH
+CONVERGE_DEFAULT_FLOOR = 1.0 / 256   # one step of an 8-bit output (gpuart_cli --until-floor)
 
 
 def _user_sphere(us):
@@ -171,6 +187,21 @@ def temporal_lib():
         L.gpuart_temporal_last_error.restype = C.c_char_p
         _temporal = L
     return _temporal
+
+
+_converge = None
+
+
+def converge_lib():
+    """libgpuart_converge.so; raises NativeLibraryMissing if it has not been built (no fallback)."""
+    global _converge
+    if _converge is None:
+        if not os.path.exists(CONVERGE_LIB):
+            raise NativeLibraryMissing("%s not found — run make -C gpuart_amd/csrc; there is no CPU fallback" % CONVERGE_LIB)
+        L = C.CDLL(CONVERGE_LIB)
+        L.gpuart_converge_last_error.restype = C.c_char_p
+        _converge = L
+    return _converge
 
 
 def host_lib():
@@ -897,6 +928,36 @@ class Renderer:
                                                                   temporal_lib().gpuart_temporal_last_error().decode()))
         return out
 
+    def render_until(self, threshold, max_above_share=0.0, batch_paths=CONVERGE_DEFAULT_BATCH, lum_floor=CONVERGE_DEFAULT_FLOOR):
+        """Renderer::RenderUntil: continue the current accumulation (restart_path_tracing's target is the cap) in batches of at least
+        batch_paths paths per pixel until at most max_above_share of the tile's pixels have a relative standard error of their
+        luminance above threshold (include/gpuart_converge.h). Returns (converged, summary): converged is False when the cap was
+        reached first; summary is the last measure as a dict (ConvergeSummary.as_dict; `total` = the paths rendered), None if none ran."""
+        if not (threshold >= 0 and threshold < float("inf")):
+            raise ValueError("threshold must be finite and >= 0")
+        if not max_above_share >= 0:
+            raise ValueError("max_above_share must be >= 0")
+        if int(batch_paths) != batch_paths or not 1 <= batch_paths <= 0xffffffff:
+            raise ValueError("batch_paths must be an integer >= 1")
+        if not (lum_floor > 0 and lum_floor < float("inf")):
+            raise ValueError("lum_floor must be finite and > 0")
+        s = ConvergeSummary()
+        rc = self.L.gpuart_renderer_render_until(self.h, C.c_float(threshold), C.c_float(max_above_share), C.c_uint(int(batch_paths)),
+                                                 C.c_float(lum_floor), C.byref(s))
+        if rc < 0:
+            raise HipError("render_until failed: %s / %s" % (hip_lib().gpuart_hip_last_error().decode(),
+                                                             converge_lib().gpuart_converge_last_error().decode()))
+        return rc == 1, (s.as_dict() if s.batches else None)
+
+    def read_error_map(self, lum_floor=CONVERGE_DEFAULT_FLOOR):
+        """Renderer::ReadErrorMap: the relative standard error per tile pixel as of render_until's last batch, (th, tw) float32; None
+        before its second batch (and after anything that restarted the accumulation)."""
+        _, _, tw, th = self.tile
+        out = np.empty((th, tw), np.float32)
+        if not self.L.gpuart_renderer_read_error_map(self.h, _p(out), C.c_float(lum_floor)):
+            return None
+        return out
+
     def finish(self): return bool(self.L.gpuart_renderer_finish(self.h))
 
     def trace_rays(self, rays, occlusion=False, user_sphere=True, want_prims=False):
@@ -1104,3 +1165,101 @@ class Temporal:
 
     def finish(self):
         self._chk(self.L.gpuart_temporal_finish(self.h))
+
+
+# ---- the convergence estimate (include/gpuart_converge.h) -----------------------------------------------------------------
+class ConvergeError(RuntimeError):
+    """A gpuart_converge_* call returned an error; `code` is the library's (GPUART_HIP_ERR_*)."""
+    code = None
+
+
+class Converge:
+    """A gpuart_converge handle on one device: it owns the per-pixel state {mean, m2, prevL, 0}."""
+
+    def __init__(self, device=0):
+        self.L = converge_lib()
+        self.device = device
+        h = C.c_void_p()
+        self._chk(self.L.gpuart_converge_create(C.c_int(device), C.byref(h)))
+        self.h = h
+        self.shape = None   # (h, w) of the state; None after reset
+
+    def _chk(self, rc):
+        if rc != 0:
+            e = ConvergeError("gpuart_converge error %d: %s" % (rc, self.L.gpuart_converge_last_error().decode()))
+            e.code = rc
+            raise e
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.gpuart_converge_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        """Forgets every batch: the next update may have any size."""
+        self._chk(self.L.gpuart_converge_reset(self.h))
+        self.shape = None
+
+    def update(self, accum, paths_total):
+        """Shows the estimator the raw accumulator accum (h, w, 4) float32, the sum over paths_total paths per pixel: one more batch.
+        A torch tensor on this handle's device runs through gpuart_converge_update (torch's current stream is synchronised first, the
+        handle before returning); a NumPy array through gpuart_converge_update_host."""
+        if int(paths_total) != paths_total or not 0 < paths_total <= CONVERGE_MAX_PATHS:
+            raise ValueError("paths_total must be an integer in 1..2^24")
+        if type(accum).__module__.startswith("torch"):
+            import torch
+            dev = torch.device("cuda", self.device)
+            if accum.dtype != torch.float32 or accum.dim() != 3 or accum.shape[2] != 4 or not accum.is_contiguous() or accum.device != dev:
+                raise ValueError("accum must be a contiguous (h, w, 4) float32 tensor on %s" % dev)
+            h, w = accum.shape[0], accum.shape[1]
+            torch.cuda.current_stream(dev).synchronize()
+            self._chk(self.L.gpuart_converge_update(self.h, C.c_void_p(accum.data_ptr()), C.c_uint32(int(paths_total)), C.c_uint32(w), C.c_uint32(h)))
+            self.finish()
+        else:
+            accum = np.ascontiguousarray(accum, np.float32)
+            if accum.ndim != 3 or accum.shape[2] != 4:
+                raise ValueError("accum must be (h, w, 4) float32")
+            h, w = accum.shape[:2]
+            self._chk(self.L.gpuart_converge_update_host(self.h, _p(accum), C.c_uint32(int(paths_total)), C.c_uint32(w), C.c_uint32(h)))
+        self.shape = (h, w)
+
+    def measure(self, threshold, lum_floor=CONVERGE_DEFAULT_FLOOR, error_map=False):
+        """The frame's summary (a dict: ConvergeSummary.as_dict) for a threshold on e = standard error / max(mean, lum_floor), after at
+        least two updates. error_map: False (none), True (a new (h, w) float32 NumPy array), a NumPy array to fill, or a torch tensor on
+        this handle's device to fill through gpuart_converge_measure. Returns the summary, or (summary, map) when a map was asked for."""
+        if self.shape is None:
+            raise ValueError("measure before the first update")
+        s = ConvergeSummary()
+        if error_map is not False and error_map is not None and type(error_map).__module__.startswith("torch"):
+            import torch
+            dev = torch.device("cuda", self.device)
+            if error_map.dtype != torch.float32 or tuple(error_map.shape) != self.shape or not error_map.is_contiguous() or error_map.device != dev:
+                raise ValueError("error_map must be a contiguous %s float32 tensor on %s" % (self.shape, dev))
+            torch.cuda.current_stream(dev).synchronize()
+            self._chk(self.L.gpuart_converge_measure(self.h, C.c_float(threshold), C.c_float(lum_floor), C.c_void_p(error_map.data_ptr()), C.byref(s)))
+            return s.as_dict(), error_map
+        if error_map is False or error_map is None:
+            self._chk(self.L.gpuart_converge_measure_host(self.h, C.c_float(threshold), C.c_float(lum_floor), None, C.byref(s)))
+            return s.as_dict()
+        m = np.empty(self.shape, np.float32) if error_map is True else error_map
+        if not isinstance(m, np.ndarray) or m.dtype != np.float32 or m.shape != self.shape or not m.flags.c_contiguous:
+            raise ValueError("error_map must be a contiguous %s float32 array" % (self.shape,))
+        self._chk(self.L.gpuart_converge_measure_host(self.h, C.c_float(threshold), C.c_float(lum_floor), _p(m), C.byref(s)))
+        return s.as_dict(), m
+
+    def state(self):
+        """The per-pixel state (h, w, 4) float32 = {mean, m2, prevL, 0}."""
+        if self.shape is None:
+            raise ValueError("no state before the first update")
+        out = np.empty(self.shape + (4,), np.float32)
+        self._chk(self.L.gpuart_converge_read_state(self.h, _p(out)))
+        return out
+
+    def finish(self):
+        self._chk(self.L.gpuart_converge_finish(self.h))

@@ -273,6 +273,11 @@ int gpuart_renderer_set_temporal_history(gpuart_renderer *r, int on, const gpuar
 int gpuart_renderer_read_preview(gpuart_renderer *r, float *rgba, const gpuart_denoise_params *dn, const gpuart_temporal_params *tp) {
     return r->impl.ReadPreview(rgba, dn, tp) ? 1 : 0;
 }
+int gpuart_renderer_render_until(gpuart_renderer *r, float threshold, float maxAboveShare, unsigned batchPaths, float lumFloor,
+                                 gpuart_converge_summary *last) {
+    return r->impl.RenderUntil(threshold, maxAboveShare, batchPaths, lumFloor, last);
+}
+int gpuart_renderer_read_error_map(gpuart_renderer *r, float *e, float lumFloor) { return r->impl.ReadErrorMap(e, lumFloor) ? 1 : 0; }
 int gpuart_renderer_finish(gpuart_renderer *r) { return r->impl.Finish() ? 1 : 0; }
 int gpuart_renderer_save_checkpoint(gpuart_renderer *r, const char *path) { return r->impl.SaveCheckpoint(path) ? 1 : 0; }
 int gpuart_renderer_load_checkpoint(gpuart_renderer *r, const char *path) { return r->impl.LoadCheckpoint(path) ? 1 : 0; }

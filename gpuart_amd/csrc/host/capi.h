@@ -6,6 +6,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "gpuart_converge.h"
 #include "gpuart_denoise.h"
 #include "gpuart_hip.h"
 #include "gpuart_temporal.h"
@@ -88,6 +89,13 @@ int gpuart_renderer_set_temporal_history(gpuart_renderer *r, int on, const gpuar
 /* Renderer::ReadPreview: the history blended with the accumulator, then denoised; what gpuart_renderer_read_denoised returns while
  * there is no history. dn, tp = NULL: the defaults / what gpuart_renderer_set_temporal_history was given. 1 on success, 0 on error. */
 int gpuart_renderer_read_preview(gpuart_renderer *r, float *rgba, const gpuart_denoise_params *dn, const gpuart_temporal_params *tp);
+/* Renderer::RenderUntil: render on in batches of at least batchPaths paths until at most maxAboveShare of the tile's pixels have a
+ * relative standard error above threshold (include/gpuart_converge.h). 1 converged, 0 the path target was reached first, -1 error;
+ * last (may be NULL) is filled whenever a measure ran. */
+int gpuart_renderer_render_until(gpuart_renderer *r, float threshold, float maxAboveShare, unsigned batchPaths, float lumFloor,
+                                 gpuart_converge_summary *last);
+/* Renderer::ReadErrorMap: the error per tile pixel as of the last batch; 1 on success, 0 before the second batch or on error. */
+int gpuart_renderer_read_error_map(gpuart_renderer *r, float *e, float lumFloor);
 int gpuart_renderer_finish(gpuart_renderer *r);
 int gpuart_renderer_save_checkpoint(gpuart_renderer *r, const char *path);
 int gpuart_renderer_load_checkpoint(gpuart_renderer *r, const char *path);

@@ -2,6 +2,7 @@
 // (src/main.cpp:549-623: scene set-up, camera, direct lighting or progressive path tracing with
 // pathsPerPass / pathsPerPixel), without a window. Writes PFM (float RGB, bottom-up like our rows) and/or
 // an 8-bit PPM (what the reference's default framebuffer would show: clamped to [0,1]), prints one JSON line.
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -24,7 +25,13 @@ static void usage() {
                  "                  [--spp N] [--per-pass K] [--max-segments M] [--seed S] [--tile x0,y0,w,h]\n"
                  "                  [--camera px,py,pz] [--sun az,alt[,off]] [--user-sphere x,y,z,r,em[,specular[,fuzzy]]]\n"
                  "                  [--device D] [--gpus N] [--resume ck] [--checkpoint ck] [--pfm out.pfm] [--ppm out.ppm] [--nearest-first]\n"
-                 "                  [--denoise]\n"
+                 "                  [--denoise] [--until T [--until-share S] [--until-floor F] [--until-batch N] [--error-pfm out.pfm]]\n"
+                 "  --until T: render until the relative standard error of every pixel's luminance is at most T (Renderer::RenderUntil; path\n"
+                 "             tracing on one GPU), --spp being the cap; --until-share S: the share of pixels that may stay above T (default 0);\n"
+                 "             --until-floor F: luminance below which the error is taken relative to F (default 1/256, one step of the 8-bit\n"
+                 "             output); --until-batch N: paths per pixel between two measurements; --error-pfm: the error per pixel (PFM, grey).\n"
+                 "             With --resume the checkpoint's paths are the first batch; one already at --spp renders nothing and is not measured\n"
+                 "             (its line says 0 batches, converged false)\n"
                  "  --denoise: write the denoised preview of the frame (Renderer::ReadDenoised; path tracing on one GPU)\n"
                  "  --nearest-first: opt in to the nearer-child-first BVH walk (~10 % faster; soak-verified, not proven to be the reference's image)\n"
                  "  --gpus N: path tracing of ONE frame on devices D..D+N-1 (8-row bands dealt round-robin, gathered over RCCL)\n";
@@ -46,6 +53,10 @@ int main(int argc, char **argv) {
     unsigned W = 640, H = 480, spp = 16, perPass = 1, maxSeg = 5, device = 0, gpus = 1;
     long seed = -1;
     bool nearestFirst = false, denoise = false;
+    std::string errorPfm;
+    float until = -1, untilShare = 0, untilFloor = 1.0f / 256;
+    unsigned untilBatch = GPUART_CONVERGE_DEFAULT_BATCH;
+    bool haveUntil = false;
     float tile[4] = {0, 0, 0, 0}, campos[3] = {0.1f, -3.05f, 1.0f}, sun[3] = {0, 0, 0}, us[7] = {-0.4f, 0, 0.2f, 0, 0, 0, 0};
     int nTile = 0, nSun = 0, nUs = 0, n;
     for (int i = 1; i < argc; i++) {
@@ -74,10 +85,20 @@ int main(int argc, char **argv) {
         else if (a == "--checkpoint") checkpoint = need("--checkpoint");
         else if (a == "--nearest-first") nearestFirst = true;
         else if (a == "--denoise") denoise = true;
+        else if (a == "--until") { until = strtof(need("--until"), nullptr); haveUntil = true; }
+        else if (a == "--until-share") untilShare = strtof(need("--until-share"), nullptr);
+        else if (a == "--until-floor") untilFloor = strtof(need("--until-floor"), nullptr);
+        else if (a == "--until-batch") untilBatch = (unsigned)atoi(need("--until-batch"));
+        else if (a == "--error-pfm") errorPfm = need("--error-pfm");
         else { usage(); return 2; }
     }
     if (W == 0 || H == 0 || (mode != "direct" && mode != "pt")) { usage(); return 2; }
     if (denoise && (mode != "pt" || gpus != 1)) { usage(); return 2; }
+    if (haveUntil && gpus > 1) {
+        std::cerr << "gpuart_cli: --until needs --gpus 1: the ranks of a sharded frame would stop at different path counts\n";
+        return 2;
+    }
+    if ((haveUntil && mode != "pt") || (!haveUntil && !errorPfm.empty())) { usage(); return 2; }
 
     // the reference's start-up camera (src/main.cpp:609-613), looking at (0,0,0.95)
     gpuart::Camera cam;
@@ -133,12 +154,34 @@ int main(int argc, char **argv) {
             // --per-pass say how far to go on from there
             r.ExtendPathTracing(perPass, spp);
         }
-        // the reference's draw loop: one pass per frame until pathsPerPixel is reached (src/main.cpp:554-582)
-        // (every GPU's pass is only enqueued: the devices work at the same time)
-        for (;;) {
-            for (auto &q : rs) done = q->RenderPathTracingPass();
-            passes++;
-            if (done >= r.GetPathsPerPixel()) break;
+        if (haveUntil) {
+            // the same passes, in batches, until the frame's error estimate is below the threshold or --spp is reached
+            const unsigned start = r.GetNumPathsRendered();
+            gpuart_converge_summary cs{};
+            const int rc = r.RenderUntil(until, untilShare, untilBatch, untilFloor, &cs);
+            if (rc < 0) return 1;
+            done = r.GetNumPathsRendered();
+            passes = (done - start + std::max(1u, perPass) - 1) / std::max(1u, perPass);
+            printf("{\"until\": %.9g, \"paths_rendered\": %u, \"batches\": %u, \"above\": %llu, \"pixels\": %llu, \"max_error\": %.9g, "
+                   "\"converged\": %s}\n", until, done, cs.batches, (unsigned long long)cs.above, (unsigned long long)cs.pixels, cs.max_error,
+                   rc == 1 ? "true" : "false");
+            if (!errorPfm.empty()) {
+                std::vector<float> e((size_t)tw * th);
+                if (!r.ReadErrorMap(e.data(), untilFloor)) { std::cerr << "gpuart_cli: no error map (fewer than two batches were rendered)\n"; return 1; }
+                FILE *f = fopen(errorPfm.c_str(), "wb");
+                if (!f) return 1;
+                fprintf(f, "Pf\n%u %u\n-1.0\n", tw, th);
+                fwrite(e.data(), sizeof(float), e.size(), f);
+                fclose(f);
+            }
+        } else {
+            // the reference's draw loop: one pass per frame until pathsPerPixel is reached (src/main.cpp:554-582)
+            // (every GPU's pass is only enqueued: the devices work at the same time)
+            for (;;) {
+                for (auto &q : rs) done = q->RenderPathTracingPass();
+                passes++;
+                if (done >= r.GetPathsPerPixel()) break;
+            }
         }
         for (auto &q : rs) q->Finish();
         if (!checkpoint.empty() && !r.SaveCheckpoint(checkpoint.c_str())) return 1;

@@ -75,6 +75,8 @@ Renderer::Renderer(unsigned viewportWidth, unsigned viewportHeight, const Camera
 }
 
 Renderer::~Renderer() {
+    if (Converge) gpuart_converge_destroy(Converge);
+    if (ConvergeMem) (void)hipFree(ConvergeMem);
     if (Temporal) gpuart_temporal_destroy(Temporal);
     if (Denoiser) gpuart_denoise_destroy(Denoiser);
     if (DenoiseMem) (void)hipFree(DenoiseMem);
@@ -318,6 +320,7 @@ void Renderer::RenderDirectLighting() {
 
 void Renderer::ResetPathTracing() {
     PathTracing.numPathsRendered = 0;
+    if (Converge) ResetConvergeNow();
     if (Backend && Viewport.width) {
         gpuart_hip_pt_reset(Backend);
         // the passes RenderPathTracingPass() will submit until pathsPerPixel is reached (a scheduling hint)
@@ -498,6 +501,78 @@ bool Renderer::ReadPreview(float *rgba, const gpuart_denoise_params *dn, const g
     return checkHip(hipMemcpy(rgba, b.filtered, n * 16, hipMemcpyDeviceToHost), "reading the preview");
 }
 
+// ---- render until converged (include/gpuart_converge.h) -----------------------------------------------------------------
+namespace {
+bool checkCv(int status, const char *what) {
+    if (status == 0) return true;
+    std::cerr << "Renderer: error " << status << " while " << what << ": " << gpuart_converge_last_error() << std::endl;
+    return false;
+}
+}  // namespace
+
+void Renderer::ResetConvergeNow() {
+    gpuart_converge_reset(Converge);
+    ConvergeBatches = ConvergeTotal = 0;
+}
+
+int Renderer::RenderUntil(float threshold, float maxAboveShare, unsigned batchPaths, float lumFloor, gpuart_converge_summary *last) {
+    if (!IsOK) return -1;
+    auto finite = [](float x) { return x - x == 0.0f; };
+    if (!finite(threshold) || !(threshold >= 0) || !(maxAboveShare >= 0) || batchPaths == 0 || !finite(lumFloor) || !(lumFloor > 0)) {
+        std::cerr << "Renderer: RenderUntil arguments out of range." << std::endl;
+        return -1;
+    }
+    if (!Converge && !checkCv(gpuart_converge_create(Device, &Converge), "creating the convergence estimator")) return -1;
+    if (!checkHip(hipSetDevice(Device), "hipSetDevice")) return -1;
+    const size_t n = (size_t)Tile.w * Tile.h;
+    if (n != ConvergePixels) {
+        if (ConvergeMem) (void)hipFree(ConvergeMem);
+        ConvergeMem = nullptr;
+        ConvergePixels = 0;
+        if (!checkHip(hipMalloc(&ConvergeMem, n * 16), "allocating the estimator's copy of the accumulator")) return -1;
+        ConvergePixels = n;
+    }
+    // the raw accumulator as one more batch: divide_by 1 copies the sums exactly; a buffer of its own: the denoiser's cached view
+    // (StageView) stays as it is. The wait lets the next export reuse the buffer.
+    auto showAccumulator = [&]() {
+        if (!Check(gpuart_hip_export(Backend, 1, ConvergeMem, 1.0f), "exporting the accumulator")) return false;
+        if (!Check(gpuart_hip_finish(Backend), "waiting for the device")) return false;
+        if (!checkCv(gpuart_converge_update(Converge, (const float *)ConvergeMem, PathTracing.numPathsRendered, Tile.w, Tile.h),
+                     "updating the convergence estimate")) return false;
+        ConvergeTotal = PathTracing.numPathsRendered;
+        ConvergeBatches++;
+        return checkCv(gpuart_converge_finish(Converge), "updating the convergence estimate");
+    };
+    // paths the estimate has never seen — a loaded checkpoint, plain passes after a restart — are its first batch, of their own weight
+    if (ConvergeBatches == 0 && PathTracing.numPathsRendered > 0 && !showAccumulator()) return -1;
+    for (;;) {
+        if (PathTracing.numPathsRendered < PathTracing.pathsPerPixel) {
+            const unsigned target = PathTracing.numPathsRendered + std::min(batchPaths, PathTracing.pathsPerPixel - PathTracing.numPathsRendered);
+            const unsigned per = std::max(1u, PathTracing.pathsPerPass);
+            // the passes of this batch are all the back end will see before the export observes them (a scheduling hint)
+            gpuart_hip_pt_plan(Backend, (target - PathTracing.numPathsRendered + per - 1) / per);
+            while (PathTracing.numPathsRendered < target) {
+                const unsigned before = PathTracing.numPathsRendered;
+                if (RenderPathTracingPass() == before) return -1;  // (the pass failed: Check has said why)
+            }
+        }
+        if (PathTracing.numPathsRendered > ConvergeTotal && !showAccumulator()) return -1;
+        if (ConvergeBatches >= 2) {
+            gpuart_converge_summary s;
+            if (!checkCv(gpuart_converge_measure(Converge, threshold, lumFloor, nullptr, &s), "measuring the convergence")) return -1;
+            if (last) *last = s;
+            if ((double)s.above <= (double)maxAboveShare * (double)s.pixels) return 1;
+        }
+        if (PathTracing.numPathsRendered >= PathTracing.pathsPerPixel) return 0;
+    }
+}
+
+bool Renderer::ReadErrorMap(float *e, float lumFloor) {
+    if (!IsOK || !e || !Converge || ConvergeBatches < 2) return false;
+    gpuart_converge_summary s;
+    return checkCv(gpuart_converge_measure_host(Converge, 0.0f, lumFloor, e, &s), "reading the error map");
+}
+
 // ---- checkpoint / resume ---------------------------------------------------------------------------------------------
 namespace {
 const char CK_MAGIC[8] = {'G', 'P', 'U', 'A', 'R', 'T', 'C', 'K'};
@@ -557,6 +632,7 @@ bool Renderer::LoadCheckpoint(const char *fileName) {
     if (!Check(gpuart_hip_write(Backend, 1, acc.data()), "restoring the radiance accumulator")) return false;
     RndGen = gen;
     DropTemporalHistory();
+    if (Converge) ResetConvergeNow();
     PathTracing.numPathsRendered = h.numPathsRendered;
     PathTracing.pathsPerPixel = h.pathsPerPixel;
     PathTracing.pathsPerPass = h.pathsPerPass;

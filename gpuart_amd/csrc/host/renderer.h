@@ -7,7 +7,8 @@
 // Additions (the reference draws into the GL framebuffer, which no longer exists, and has
 // MAX_PATH_SEGMENTS / the RNG seed / the viewport fixed at compile time):
 //   ReadDirectLighting, ReadRadiance, Finish, SetMaxPathSegments, SetMinWeight, SetSeed,
-//   SetTile, GetBackend, ComputeScreenBasis, GetNumPathsRendered, ReadDenoised, SetTemporalHistory, ReadPreview.
+//   SetTile, GetBackend, ComputeScreenBasis, GetNumPathsRendered, ReadDenoised, SetTemporalHistory, ReadPreview, RenderUntil,
+//   ReadErrorMap.
 #ifndef GPUART_RENDERER_H
 #define GPUART_RENDERER_H
 
@@ -17,6 +18,7 @@
 
 #include "bvh.h"
 #include "core.h"
+#include "gpuart_converge.h"
 #include "gpuart_denoise.h"
 #include "gpuart_hip.h"
 #include "gpuart_temporal.h"
@@ -105,6 +107,19 @@ public:
     /// (dn). Exactly ReadDenoised while history is off, before the first commit, and before the view's first path. The history, the
     /// accumulator, the passes that follow and the counters are not touched. Synchronises.
     bool ReadPreview(float *rgba, const gpuart_denoise_params *dn = nullptr, const gpuart_temporal_params *tp = nullptr);
+    /// Render until the noise is below a threshold (include/gpuart_converge.h): continues the current accumulation in batches of at
+    /// least batchPaths paths per pixel (whole RenderPathTracingPass calls; the target of RestartPathTracing / ExtendPathTracing is the
+    /// cap). After every batch the raw accumulator goes to the estimator, from the second batch on the frame is measured: e = the
+    /// standard error of a pixel's mean luminance over max(that luminance, lumFloor). Returns 1 as soon as at most maxAboveShare of the
+    /// tile's pixels have !(e <= threshold), 0 when the cap was reached first, -1 on error (arguments out of range included: threshold
+    /// finite and >= 0, maxAboveShare >= 0, batchPaths >= 1, lumFloor finite and > 0). `last` is filled whenever a measure ran. The
+    /// RandSeed draws, and so the accumulator, are those of the same number of plain RenderPathTracingPass calls; passes rendered by
+    /// such calls in between simply join the next batch, and paths the estimate has never seen (a loaded checkpoint, plain passes
+    /// after a restart) are its first batch, of their own weight, before anything is rendered. Every call that restarts the accumulation restarts the estimate. A batch
+    /// ends in a wait for the device.
+    int RenderUntil(float threshold, float maxAboveShare, unsigned batchPaths, float lumFloor, gpuart_converge_summary *last = nullptr);
+    /// e per tile pixel (Tile.w*Tile.h floats, row 0 = bottom row) as of RenderUntil's last batch; false before its second batch.
+    bool ReadErrorMap(float *e, float lumFloor);
     bool Finish();
     void SetMaxPathSegments(unsigned n) { MaxPathSegments = n; DropTemporalHistory(); ResetPathTracing(); }
     void SetMinWeight(float w) { MinWeight = w; DropTemporalHistory(); ResetPathTracing(); }
@@ -169,6 +184,10 @@ private:
     bool TemporalOn = false;
     bool HistoryCommitted = false;        ///< Temporal holds a history
     gpuart_temporal_params TemporalParams{};  ///< of the commits (SetTemporalHistory)
+    gpuart_converge *Converge = nullptr;  ///< made by the first RenderUntil
+    void *ConvergeMem = nullptr;          ///< device: the raw accumulator of RenderUntil's last batch, 16 B per tile pixel
+    size_t ConvergePixels = 0;
+    unsigned ConvergeBatches = 0, ConvergeTotal = 0;  ///< what Converge has seen since its last reset
     ScreenBasis CurrentBasis;             ///< what SetCamera gave the back end
     double LastSetPrimitivesMs[4] = {0, 0, 0, 0};
     gpuart_hip_ctx *Backend = nullptr;
@@ -191,6 +210,7 @@ private:
     void CommitTemporalView();
     void DropTemporalHistory() { if (HistoryCommitted) DropTemporalHistoryNow(); }
     void DropTemporalHistoryNow();
+    void ResetConvergeNow();
     bool Check(int status, const char *what);
 };
 
