@@ -32,6 +32,19 @@
  * and holds the largest finite e (`max_error`, 0 if there is none). The three reductions are order-independent (integer counts, a
  * maximum over non-negative floats through their bit patterns): the summary is exact and the same in every run.
  *
+ * The accumulator's floor. The estimator's own fp32 arithmetic is harmless: against a float64 two-pass estimate of the same luminances e
+ * differs by at most 1.3e-8 over up to 4096 batches and 2^24 paths (tests/test_converge_range.py, profiles/convergence.txt section 4).
+ * The fp32 accumulator it is shown is not: every luminance carries a rounding error relative to the whole sum, every batch mean is
+ * the difference of two of them spread over the batch's paths, and the estimator cannot tell that noise from the paths' own. Against
+ * the estimate on unrounded sums e changes by up to
+ *   e_floor(total, b) = 2^-22 * sqrt(total / b),      b = the smallest batch after the first, in paths,
+ * for a pixel at or above lum_floor (less below it), and a pixel without any spread reports up to that instead of 0 (measured: up to
+ * 0.45 of it). A threshold below e_floor(total, b) is therefore not reliably reachable: with batches of 64 paths 1e-4 is out of reach
+ * beyond 11.3 million paths and 1e-5 beyond 113 000; with batches of one path (a checkpoint of 2^23 paths continued path by path:
+ * e_floor = 6.9e-4, steady pixels report up to 2.9e-4) 1e-4 is out of reach beyond 176 000 paths. The smallest threshold that can be
+ * reached at the cap of 2^24 paths is 2^-10 / sqrt(b): 1.2e-4 for b = 64, 3.8e-6 for b = 65536. Larger batches lower the floor;
+ * nothing reports that a threshold lies below it — RenderUntil then runs to its cap.
+ *
  * Conventions as include/gpuart_hip.h: 0 on success or a negative gpuart_hip_status (GPUART_HIP_ERR_ARG, _DEVICE, _NO_DEVICE); the
  * message of the last failure (per thread) from gpuart_converge_last_error(). Images are tiles of w x h RGBA32F pixels, row-major,
  * in the local row order of the tile that gpuart_hip_read uses (row 0 at the bottom). One handle per device; it owns its HIP stream,

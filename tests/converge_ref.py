@@ -97,6 +97,67 @@ class Estimator:
         return self.state[..., 1].astype(np.float64) / (self.batches - 1)
 
 
+def reference64(lums, totals, lum_floor):
+    """The same estimate in float64 and in another form: no recurrence, no running mean. lums: the luminance of the accumulator after
+    every batch (any float type, any shape), totals: the path count after every batch. From the batch means y_k = (L_k - L_{k-1}) / b_k
+    (L_0 = 0), two passes: mean = sum b_k y_k / sum b_k, m2 = sum b_k (y_k - mean)^2, e = sqrt(m2 / (nb - 1) / total) / max(mean, floor).
+    Returns (e, mean, m2), float64."""
+    nb = len(totals)
+    if nb < 2 or len(lums) != nb:
+        raise ValueError("a measure needs two batches")
+    b = np.diff(np.concatenate([[0], np.asarray(totals, np.int64)])).astype(np.float64)
+    if (b <= 0).any():
+        raise ValueError("totals must rise")
+    total = float(totals[-1])
+    prev = np.zeros(np.shape(lums[0]), np.float64)
+    ys = []
+    for Lk, bk in zip(lums, b):
+        Lk = np.asarray(Lk, np.float64)
+        ys.append((Lk - prev) / bk)
+        prev = Lk
+    mean = sum(bk * y for bk, y in zip(b, ys)) / b.sum()
+    m2 = sum(bk * (y - mean) ** 2 for bk, y in zip(b, ys))
+    with np.errstate(all="ignore"):
+        e = np.sqrt(m2 / (nb - 1) / total) / np.maximum(mean, float(lum_floor))
+    return e, mean, m2
+
+
+def lum64(a):
+    """L of unrounded float64 sums: the fp32 coefficients, every operation in float64."""
+    a = np.asarray(a, np.float64)
+    return (float(F(0.2126)) * a[..., 0] + float(F(0.7152)) * a[..., 1]) + float(F(0.0722)) * a[..., 2]
+
+
+def accumulator_floor(total, b_min):
+    """What the fp32 accumulator alone can add to e (include/gpuart_converge.h, "The accumulator's floor"): every batch mean is a
+    difference of two luminances that each carry a rounding error relative to the whole sum, spread over the batch's paths;
+    2^-22 * sqrt(total / b_min) bounds the change of e for a pixel at or above lum_floor, b_min being the smallest batch after the first."""
+    return 2.0 ** -22 * float(np.sqrt(float(total) / float(b_min)))
+
+
+def render_until(est, accum_at, rendered, cap, per_pass, batch_paths, threshold, max_above_share, lum_floor):
+    """What one call of Renderer::RenderUntil does, on the Estimator `est` the earlier calls left (a reset one after anything that
+    restarted the accumulation): `rendered` paths are in the accumulator, `cap` and `per_pass` are RestartPathTracing's, accum_at(total)
+    is the raw accumulator after `total` paths. Returns (converged, the summary of the last measure or None, paths rendered)."""
+    per_pass = max(1, min(per_pass, cap))
+    s = None
+    if est.batches == 0 and rendered > 0:
+        est.update(accum_at(rendered), rendered)
+    while True:
+        if rendered < cap:
+            target = rendered + min(batch_paths, cap - rendered)
+            while rendered < target:
+                rendered += min(per_pass, cap - rendered)   # (a pass is clamped to the cap, not to the batch)
+        if rendered > est.total:
+            est.update(accum_at(rendered), rendered)
+        if est.batches >= 2:
+            s, _ = est.measure(threshold, lum_floor)
+            if float(s["above"]) <= float(F(max_above_share)) * float(s["pixels"]):
+                return True, s, rendered
+        if rendered >= cap:
+            return False, s, rendered
+
+
 def stops_at(accums, totals, threshold, max_above_share, lum_floor):
     """What Renderer::RenderUntil does with these accumulators, one per batch: (index of the batch after which it stops or None,
     the summary of its last measure or None)."""

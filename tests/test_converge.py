@@ -181,6 +181,10 @@ def O():
 # has (2048 blocks of 4 rows for up to 64 columns, 682 for 130), so its waves walk several rows.
 SHAPES = [(1, 1), (37, 23), (63, 3), (64, 4), (65, 5), (257, 3), (1920, 2), (3, 8197), (130, 2735)]
 BATCHES = {"equal": [4, 4, 4, 4], "unequal": [100, 3, 1, 7]}
+# The frame-size limits and two sizes one past a multiple of the block: at 65536 columns k_cv_measure's grid cap (2048 blocks / 1024
+# column blocks) is 2 with a single row of blocks, at 1 x 65536 every wave walks 8 rows; 4097 and 2049 columns leave one pixel in the
+# last column block. A smaller loop: equal batches, the device update, one device measure and one host measure with a map.
+EDGE_SHAPES = [(65536, 1), (1, 65536), (4097, 3), (2049, 5)]
 
 
 def synthetic(w, h, sizes, seed):
@@ -223,7 +227,7 @@ def test_kernels_equal_the_restatement_on_synthetic_accumulators(B):
     """read_state after every update, the error map and the summary, bit for bit, through the host entry points (NumPy) and the device
     ones (torch), with and without a map; thresholds and floors taken from the restatement's own values for planted pixels."""
     import torch
-    ledger = R.new_ledger()
+    ledger, edge_ledger = R.new_ledger(), R.new_ledger()   # (each loop meets the floor on its own)
     host, dev = B.Converge(0), B.Converge(0)
     try:
         for w, h in SHAPES:
@@ -275,11 +279,36 @@ def test_kernels_equal_the_restatement_on_synthetic_accumulators(B):
                         assert at["above"] >= at["non_finite"] and np.isfinite(at["max_error"])
                         assert ((st[groups["denormal"], 2] != 0) & (np.abs(st[groups["denormal"], 2]) < np.finfo(F).tiny)).all()
                         assert (e0[groups["black"]] == 0).all()
+        for w, h in EDGE_SHAPES:
+            what = "%dx%d equal" % (w, h)
+            accums, totals, groups = synthetic(w, h, BATCHES["equal"], seed=w * 131 + h)
+            ref = R.Estimator()
+            dev.reset()
+            for k, (acc, total) in enumerate(zip(accums, totals)):
+                exp = ref.update(acc, total)
+                dev.update(torch.from_numpy(acc).to("cuda:0"), total)
+                assert_same(dev.state(), exp, "%s: state after update %d, device" % (what, k))
+            flat = ref.state.reshape(-1, 4)
+            floor = float(flat[groups["at_floor"][0], 0])
+            e0 = ref.error(floor).reshape(-1)
+            thr = float(e0[groups["at_threshold"][0]])
+            assert (e0[groups["at_threshold"]] == F(thr)).all() and np.isfinite(thr) and thr > 0
+            for t, tag in ((thr, "at"), (float(np.nextafter(F(thr), F(-1))), "below")):
+                s_exp, e_exp = ref.measure(t, floor, edge_ledger)
+                cs = B.ConvergeSummary()
+                assert dev.L.gpuart_converge_measure(dev.h, C.c_float(t), C.c_float(floor), None, C.byref(cs)) == 0
+                assert_summary(cs.as_dict(), s_exp, "%s threshold %s device" % (what, tag))
+                s1, m1 = dev.measure(t, floor, error_map=True)
+                assert_summary(s1, s_exp, "%s threshold %s host+map" % (what, tag))
+                assert_same(m1, e_exp, "%s: error map, host" % what)
+            assert s_exp["non_finite"] == len(groups["nan"]) + len(groups["inf"]) + len(groups["overflow"]) > 0
     finally:
         host.close()
         dev.close()
     print("ledger:", ledger)
+    print("ledger of the edge shapes:", edge_ledger)
     assert min(ledger.values()) >= FLOOR, ledger
+    assert min(edge_ledger.values()) >= FLOOR, edge_ledger
 
 
 W0, H0 = 64, 48
