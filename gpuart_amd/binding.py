@@ -13,9 +13,6 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIBDIR = os.environ.get("GPUART_LIBDIR") or os.path.join(HERE, "lib")  # override: A/B runs of differently built libraries
 HIP_LIB = os.path.join(LIBDIR, "libgpuart_hip.so")
 HOST_LIB = os.path.join(LIBDIR, "libgpuart.so")
-DENOISE_LIB = os.path.join(LIBDIR, "libgpuart_denoise.so")
-TEMPORAL_LIB = os.path.join(LIBDIR, "libgpuart_temporal.so")
-CONVERGE_LIB = os.path.join(LIBDIR, "libgpuart_converge.so")
 
 
 class NativeLibraryMissing(RuntimeError):
@@ -159,49 +156,34 @@ def hip_lib():
     return _hip
 
 
-_denoise = None
+_image_libs = {}
+
+
+def _image_lib(name):
+    """libgpuart_<name>.so, one of the image libraries; raises NativeLibraryMissing if it has not been built (no fallback)."""
+    if name not in _image_libs:
+        path = os.path.join(LIBDIR, "libgpuart_%s.so" % name)
+        if not os.path.exists(path):
+            raise NativeLibraryMissing("%s not found — run make -C gpuart_amd/csrc; there is no CPU fallback" % path)
+        L = C.CDLL(path)
+        getattr(L, "gpuart_%s_last_error" % name).restype = C.c_char_p
+        _image_libs[name] = L
+    return _image_libs[name]
 
 
 def denoise_lib():
     """libgpuart_denoise.so; raises NativeLibraryMissing if it has not been built (no fallback)."""
-    global _denoise
-    if _denoise is None:
-        if not os.path.exists(DENOISE_LIB):
-            raise NativeLibraryMissing("%s not found — run make -C gpuart_amd/csrc; there is no CPU fallback" % DENOISE_LIB)
-        L = C.CDLL(DENOISE_LIB)
-        L.gpuart_denoise_last_error.restype = C.c_char_p
-        _denoise = L
-    return _denoise
-
-
-_temporal = None
+    return _image_lib("denoise")
 
 
 def temporal_lib():
     """libgpuart_temporal.so; raises NativeLibraryMissing if it has not been built (no fallback)."""
-    global _temporal
-    if _temporal is None:
-        if not os.path.exists(TEMPORAL_LIB):
-            raise NativeLibraryMissing("%s not found — run make -C gpuart_amd/csrc; there is no CPU fallback" % TEMPORAL_LIB)
-        L = C.CDLL(TEMPORAL_LIB)
-        L.gpuart_temporal_last_error.restype = C.c_char_p
-        _temporal = L
-    return _temporal
-
-
-_converge = None
+    return _image_lib("temporal")
 
 
 def converge_lib():
     """libgpuart_converge.so; raises NativeLibraryMissing if it has not been built (no fallback)."""
-    global _converge
-    if _converge is None:
-        if not os.path.exists(CONVERGE_LIB):
-            raise NativeLibraryMissing("%s not found — run make -C gpuart_amd/csrc; there is no CPU fallback" % CONVERGE_LIB)
-        L = C.CDLL(CONVERGE_LIB)
-        L.gpuart_converge_last_error.restype = C.c_char_p
-        _converge = L
-    return _converge
+    return _image_lib("converge")
 
 
 def host_lib():
@@ -999,31 +981,31 @@ class Renderer:
         return p
 
 
-# ---- the denoiser (include/gpuart_denoise.h) ------------------------------------------------------------------------------
-class DenoiseError(RuntimeError):
-    """A gpuart_denoise_* call returned an error; `code` is the library's (GPUART_HIP_ERR_*)."""
-    code = None
-
-
-class Denoiser:
-    """A gpuart_denoise handle on one device."""
+# ---- the image libraries: what their handles share ----------------------------------------------------------------------------
+class _ImageHandle:
+    """A handle of one of the image libraries on one device. A subclass names its library (NAME: gpuart_<NAME>_create, _destroy,
+    _finish, _last_error) and the error its failed calls raise (Error)."""
+    NAME = Error = None
 
     def __init__(self, device=0):
-        self.L = denoise_lib()
+        self.L = _image_lib(self.NAME)
         self.device = device
         h = C.c_void_p()
-        self._chk(self.L.gpuart_denoise_create(C.c_int(device), C.byref(h)))
+        self._chk(self._fn("create")(C.c_int(device), C.byref(h)))
         self.h = h
+
+    def _fn(self, what):
+        return getattr(self.L, "gpuart_%s_%s" % (self.NAME, what))
 
     def _chk(self, rc):
         if rc != 0:
-            e = DenoiseError("gpuart_denoise error %d: %s" % (rc, self.L.gpuart_denoise_last_error().decode()))
+            e = self.Error("gpuart_%s error %d: %s" % (self.NAME, rc, self._fn("last_error")().decode()))
             e.code = rc
             raise e
 
     def close(self):
         if getattr(self, "h", None):
-            self.L.gpuart_denoise_destroy(self.h)
+            self._fn("destroy")(self.h)
             self.h = None
 
     def __del__(self):
@@ -1031,6 +1013,56 @@ class Denoiser:
             self.close()
         except Exception:
             pass
+
+    def finish(self):
+        self._chk(self._fn("finish")(self.h))
+
+
+def _gbuffer_args(device, rgba, hits, prims, out):
+    """What Denoiser.run and Temporal.accumulate check of a tile's radiance, G-buffer and result: torch tensors on cuda:<device>, or
+    NumPy arrays (made contiguous). -> (dev, rgba, hits, prims, res, h, w): dev is the tensors' torch device, None for NumPy arrays;
+    res is `out`, or a new image like rgba."""
+    if type(rgba).__module__.startswith("torch"):
+        import torch
+        dev = torch.device("cuda", device)
+        if rgba.dtype != torch.float32 or rgba.dim() != 3 or rgba.shape[2] != 4 or not rgba.is_contiguous() or rgba.device != dev:
+            raise ValueError("rgba must be a contiguous (h, w, 4) float32 tensor on %s" % dev)
+        h, w = rgba.shape[0], rgba.shape[1]
+        if hits.dtype != torch.float32 or hits.numel() != h * w * 8 or not hits.is_contiguous() or hits.device != dev:
+            raise ValueError("hits must be a contiguous (h, w, 8) float32 tensor on %s" % dev)
+        if prims.dtype != torch.int32 or prims.numel() != h * w or not prims.is_contiguous() or prims.device != dev:
+            raise ValueError("prims must be a contiguous (h, w) int32 tensor on %s" % dev)
+        res = out if out is not None else torch.empty_like(rgba)
+        if res.dtype != torch.float32 or tuple(res.shape) != (h, w, 4) or not res.is_contiguous() or res.device != dev:
+            raise ValueError("out must be a contiguous (h, w, 4) float32 tensor on %s" % dev)
+        return dev, rgba, hits, prims, res, h, w
+    rgba = np.ascontiguousarray(rgba, np.float32)
+    if rgba.ndim != 3 or rgba.shape[2] != 4:
+        raise ValueError("rgba must be (h, w, 4) float32")
+    h, w = rgba.shape[:2]
+    hits = np.ascontiguousarray(hits)
+    prims = np.ascontiguousarray(prims, np.int32)
+    if hits.nbytes != h * w * 32 or prims.size != h * w:
+        raise ValueError("hits must hold h*w 32-byte records and prims h*w ordinals")
+    res = out if out is not None else np.empty_like(rgba)
+    if res.dtype != np.float32 or res.shape != (h, w, 4) or not res.flags.c_contiguous:
+        raise ValueError("out must be a contiguous (h, w, 4) float32 array")
+    return None, rgba, hits, prims, res, h, w
+
+
+def _dp(t):
+    return C.c_void_p(t.data_ptr())
+
+
+# ---- the denoiser (include/gpuart_denoise.h) ------------------------------------------------------------------------------
+class DenoiseError(RuntimeError):
+    """A gpuart_denoise_* call returned an error; `code` is the library's (GPUART_HIP_ERR_*)."""
+    code = None
+
+
+class Denoiser(_ImageHandle):
+    """A gpuart_denoise handle on one device."""
+    NAME, Error = "denoise", DenoiseError
 
     def run(self, rgba, hits, prims, us_flags=0, params=None, out=None):
         """Filters radiance rgba (h, w, 4) float32 guided by a G-buffer: hits = the (h, w) RAY_HIT records or their (h, w, 8) float32 words,
@@ -1040,41 +1072,17 @@ class Denoiser:
         or a new tensor; NumPy arrays run through gpuart_denoise_run_host and the result is `out` or a new array."""
         p = denoise_params(params)
         pp = C.byref(p) if p is not None else None
-        if type(rgba).__module__.startswith("torch"):
+        dev, rgba, hits, prims, res, h, w = _gbuffer_args(self.device, rgba, hits, prims, out)
+        if dev is not None:
             import torch
-            dev = torch.device("cuda", self.device)
-            if rgba.dtype != torch.float32 or rgba.dim() != 3 or rgba.shape[2] != 4 or not rgba.is_contiguous() or rgba.device != dev:
-                raise ValueError("rgba must be a contiguous (h, w, 4) float32 tensor on %s" % dev)
-            h, w = rgba.shape[0], rgba.shape[1]
-            if hits.dtype != torch.float32 or hits.numel() != h * w * 8 or not hits.is_contiguous() or hits.device != dev:
-                raise ValueError("hits must be a contiguous (h, w, 8) float32 tensor on %s" % dev)
-            if prims.dtype != torch.int32 or prims.numel() != h * w or not prims.is_contiguous() or prims.device != dev:
-                raise ValueError("prims must be a contiguous (h, w) int32 tensor on %s" % dev)
-            res = out if out is not None else torch.empty_like(rgba)
-            if res.dtype != torch.float32 or tuple(res.shape) != (h, w, 4) or not res.is_contiguous() or res.device != dev:
-                raise ValueError("out must be a contiguous (h, w, 4) float32 tensor on %s" % dev)
             torch.cuda.current_stream(dev).synchronize()
-            self._chk(self.L.gpuart_denoise_run(self.h, C.c_void_p(rgba.data_ptr()), C.c_void_p(hits.data_ptr()), C.c_void_p(prims.data_ptr()),
-                                                C.c_uint32(us_flags), C.c_uint32(w), C.c_uint32(h), pp, C.c_void_p(res.data_ptr())))
+            self._chk(self.L.gpuart_denoise_run(self.h, _dp(rgba), _dp(hits), _dp(prims), C.c_uint32(us_flags), C.c_uint32(w), C.c_uint32(h),
+                                                pp, _dp(res)))
             self.finish()
             return res
-        rgba = np.ascontiguousarray(rgba, np.float32)
-        if rgba.ndim != 3 or rgba.shape[2] != 4:
-            raise ValueError("rgba must be (h, w, 4) float32")
-        h, w = rgba.shape[:2]
-        hits = np.ascontiguousarray(hits)
-        prims = np.ascontiguousarray(prims, np.int32)
-        if hits.nbytes != h * w * 32 or prims.size != h * w:
-            raise ValueError("hits must hold h*w 32-byte records and prims h*w ordinals")
-        res = out if out is not None else np.empty_like(rgba)
-        if res.dtype != np.float32 or res.shape != (h, w, 4) or not res.flags.c_contiguous:
-            raise ValueError("out must be a contiguous (h, w, 4) float32 array")
         self._chk(self.L.gpuart_denoise_run_host(self.h, _p(rgba), _p(hits), _p(prims), C.c_uint32(us_flags), C.c_uint32(w), C.c_uint32(h),
                                                  pp, _p(res)))
         return res
-
-    def finish(self):
-        self._chk(self.L.gpuart_denoise_finish(self.h))
 
 
 # ---- temporal accumulation (include/gpuart_temporal.h) --------------------------------------------------------------------
@@ -1083,32 +1091,9 @@ class TemporalError(RuntimeError):
     code = None
 
 
-class Temporal:
+class Temporal(_ImageHandle):
     """A gpuart_temporal handle on one device: it owns the history."""
-
-    def __init__(self, device=0):
-        self.L = temporal_lib()
-        self.device = device
-        h = C.c_void_p()
-        self._chk(self.L.gpuart_temporal_create(C.c_int(device), C.byref(h)))
-        self.h = h
-
-    def _chk(self, rc):
-        if rc != 0:
-            e = TemporalError("gpuart_temporal error %d: %s" % (rc, self.L.gpuart_temporal_last_error().decode()))
-            e.code = rc
-            raise e
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.gpuart_temporal_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    NAME, Error = "temporal", TemporalError
 
     def reset(self):
         """Drops the history."""
@@ -1123,48 +1108,23 @@ class Temporal:
         gpuart_temporal_accumulate_host. out / out_len: where to put the results (new ones otherwise)."""
         p = temporal_params(params)
         pp = C.byref(p) if p is not None else None
-        if type(rgba).__module__.startswith("torch"):
+        dev, rgba, hits, prims, res, h, w = _gbuffer_args(self.device, rgba, hits, prims, out)
+        if dev is not None:
             import torch
-            dev = torch.device("cuda", self.device)
-            if rgba.dtype != torch.float32 or rgba.dim() != 3 or rgba.shape[2] != 4 or not rgba.is_contiguous() or rgba.device != dev:
-                raise ValueError("rgba must be a contiguous (h, w, 4) float32 tensor on %s" % dev)
-            h, w = rgba.shape[0], rgba.shape[1]
-            if hits.dtype != torch.float32 or hits.numel() != h * w * 8 or not hits.is_contiguous() or hits.device != dev:
-                raise ValueError("hits must be a contiguous (h, w, 8) float32 tensor on %s" % dev)
-            if prims.dtype != torch.int32 or prims.numel() != h * w or not prims.is_contiguous() or prims.device != dev:
-                raise ValueError("prims must be a contiguous (h, w) int32 tensor on %s" % dev)
-            res = out if out is not None else torch.empty_like(rgba)
-            if res.dtype != torch.float32 or tuple(res.shape) != (h, w, 4) or not res.is_contiguous() or res.device != dev:
-                raise ValueError("out must be a contiguous (h, w, 4) float32 tensor on %s" % dev)
             ln = out_len if out_len is not None else torch.empty((h, w), dtype=torch.float32, device=dev)
             if ln.dtype != torch.float32 or tuple(ln.shape) != (h, w) or not ln.is_contiguous() or ln.device != dev:
                 raise ValueError("out_len must be a contiguous (h, w) float32 tensor on %s" % dev)
             torch.cuda.current_stream(dev).synchronize()
-            self._chk(self.L.gpuart_temporal_accumulate(self.h, C.c_void_p(rgba.data_ptr()), C.c_uint32(spp), C.c_void_p(hits.data_ptr()),
-                                                        C.c_void_p(prims.data_ptr()), C.c_uint32(w), C.c_uint32(h), C.byref(view), pp,
-                                                        C.c_int(1 if commit else 0), C.c_void_p(res.data_ptr()), C.c_void_p(ln.data_ptr())))
+            self._chk(self.L.gpuart_temporal_accumulate(self.h, _dp(rgba), C.c_uint32(spp), _dp(hits), _dp(prims), C.c_uint32(w), C.c_uint32(h),
+                                                        C.byref(view), pp, C.c_int(1 if commit else 0), _dp(res), _dp(ln)))
             self.finish()
             return res, ln
-        rgba = np.ascontiguousarray(rgba, np.float32)
-        if rgba.ndim != 3 or rgba.shape[2] != 4:
-            raise ValueError("rgba must be (h, w, 4) float32")
-        h, w = rgba.shape[:2]
-        hits = np.ascontiguousarray(hits)
-        prims = np.ascontiguousarray(prims, np.int32)
-        if hits.nbytes != h * w * 32 or prims.size != h * w:
-            raise ValueError("hits must hold h*w 32-byte records and prims h*w ordinals")
-        res = out if out is not None else np.empty_like(rgba)
-        if res.dtype != np.float32 or res.shape != (h, w, 4) or not res.flags.c_contiguous:
-            raise ValueError("out must be a contiguous (h, w, 4) float32 array")
         ln = out_len if out_len is not None else np.empty((h, w), np.float32)
         if ln.dtype != np.float32 or ln.shape != (h, w) or not ln.flags.c_contiguous:
             raise ValueError("out_len must be a contiguous (h, w) float32 array")
         self._chk(self.L.gpuart_temporal_accumulate_host(self.h, _p(rgba), C.c_uint32(spp), _p(hits), _p(prims), C.c_uint32(w), C.c_uint32(h),
                                                          C.byref(view), pp, C.c_int(1 if commit else 0), _p(res), _p(ln)))
         return res, ln
-
-    def finish(self):
-        self._chk(self.L.gpuart_temporal_finish(self.h))
 
 
 # ---- the convergence estimate (include/gpuart_converge.h) -----------------------------------------------------------------
@@ -1173,33 +1133,13 @@ class ConvergeError(RuntimeError):
     code = None
 
 
-class Converge:
+class Converge(_ImageHandle):
     """A gpuart_converge handle on one device: it owns the per-pixel state {mean, m2, prevL, 0}."""
+    NAME, Error = "converge", ConvergeError
 
     def __init__(self, device=0):
-        self.L = converge_lib()
-        self.device = device
-        h = C.c_void_p()
-        self._chk(self.L.gpuart_converge_create(C.c_int(device), C.byref(h)))
-        self.h = h
+        super().__init__(device)
         self.shape = None   # (h, w) of the state; None after reset
-
-    def _chk(self, rc):
-        if rc != 0:
-            e = ConvergeError("gpuart_converge error %d: %s" % (rc, self.L.gpuart_converge_last_error().decode()))
-            e.code = rc
-            raise e
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.gpuart_converge_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def reset(self):
         """Forgets every batch: the next update may have any size."""
@@ -1260,6 +1200,3 @@ class Converge:
         out = np.empty(self.shape + (4,), np.float32)
         self._chk(self.L.gpuart_converge_read_state(self.h, _p(out)))
         return out
-
-    def finish(self):
-        self._chk(self.L.gpuart_converge_finish(self.h))

@@ -2,43 +2,28 @@
 // its reduction over the frame, include/gpuart_converge.h, which states both operation by operation. Built like the denoiser — fp32
 // denormals kept, IEEE '/' and sqrt, no contraction — so that every value is the one tests/converge_ref.py computes in NumPy float32.
 // DESIGN.md "Convergence estimate" describes the kernels.
-#include <hip/hip_runtime.h>
-
 #include <cmath>
-#include <string>
 
+#include "../image/image_lib.h"
 #include "gpuart_converge.h"
 
 namespace {
 
-thread_local std::string g_last_error;
+const char LIB[] = "converge";
 
-int fail(int code, const std::string &msg) {
-    g_last_error = msg;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return fail(GPUART_HIP_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-// A 64 x 4 block: a wave is 64 consecutive pixels of a row, so the accumulator and the state are coalesced 16-byte-per-lane accesses
-// (1 KiB per wave instruction) and the error map 4-byte-per-lane ones.
-constexpr int CX = 64, CY = 4;
+// The row block of image_lib.h: the accumulator and the state are coalesced 16-byte-per-lane accesses (1 KiB per wave instruction) and
+// the error map 4-byte-per-lane ones.
 // k_cv_measure walks the rows with a stride of the grid's, so that a wave ends in three atomics whatever the height: the most blocks it is given.
 constexpr unsigned MEASURE_MAX_BLOCKS = 2048;
 
 /// Pure streaming: 32 bytes in, 16 out per pixel.
-__global__ void __launch_bounds__(CX * CY) k_cv_update(const float4 *accum, float4 *state, int w, int h, float b, float r) {
-    const int x = blockIdx.x * CX + threadIdx.x, y = blockIdx.y * CY + threadIdx.y;
+__global__ void __launch_bounds__(ROW_X * ROW_Y) k_cv_update(const float4 *accum, float4 *state, int w, int h, float b, float r) {
+    const int x = blockIdx.x * ROW_X + threadIdx.x, y = blockIdx.y * ROW_Y + threadIdx.y;
     if (x >= w || y >= h) return;
     const size_t i = (size_t)y * w + x;
     const float4 a = accum[i];
     const float4 s = state[i];
-    const float Lk = (0.2126f * a.x + 0.7152f * a.y) + 0.0722f * a.z;
+    const float Lk = lum(a.x, a.y, a.z);
     const float yk = (Lk - s.z) / b;
     const float d = yk - s.x;
     const float mean = s.x + r * d;
@@ -55,12 +40,12 @@ struct Words {
 /// 16 bytes in per pixel, 4 out with a map. Per wave: __ballot + __popcll for the two counts and a maximum over the lanes, kept in
 /// wave-uniform registers across the rows the wave walks, then one atomic per word.
 template <bool MAP>
-__global__ void __launch_bounds__(CX * CY) k_cv_measure(const float4 *state, int w, int h, float nb1, float total, float threshold,
-                                                         float lum_floor, float *map, Words *out) {
-    const int x = blockIdx.x * CX + threadIdx.x;
+__global__ void __launch_bounds__(ROW_X * ROW_Y) k_cv_measure(const float4 *state, int w, int h, float nb1, float total, float threshold,
+                                                               float lum_floor, float *map, Words *out) {
+    const int x = blockIdx.x * ROW_X + threadIdx.x;
     unsigned long long above = 0, non_finite = 0;
     unsigned int mx = 0;
-    for (int y = blockIdx.y * CY + threadIdx.y; y < h; y += gridDim.y * CY) {  // (wave-uniform: a wave is one row)
+    for (int y = blockIdx.y * ROW_Y + threadIdx.y; y < h; y += gridDim.y * ROW_Y) {  // (wave-uniform: a wave is one row)
         bool ab = false, nf = false;
         if (x < w) {
             const size_t i = (size_t)y * w + x;
@@ -93,13 +78,9 @@ __global__ void __launch_bounds__(CX * CY) k_cv_measure(const float4 *state, int
 
 }  // namespace
 
-struct gpuart_converge {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    void *state = nullptr;  ///< 16 bytes per pixel: {mean, m2, prevL, 0}
-    size_t state_bytes = 0;
-    void *stage = nullptr;  ///< update_host: the accumulator (16 bytes per pixel); measure_host: the error map (4)
-    size_t stage_bytes = 0;
+struct gpuart_converge : ImageHandle {
+    DeviceBuffer state;  ///< 16 bytes per pixel: {mean, m2, prevL, 0}
+    DeviceBuffer stage;  ///< update_host: the accumulator (16 bytes per pixel); measure_host: the error map (4)
     Words *words = nullptr;   ///< device
     Words *pinned = nullptr;  ///< host, pinned: where a measure reads them
     uint32_t w = 0, h = 0;    ///< of the state; 0 after create and reset
@@ -108,26 +89,12 @@ struct gpuart_converge {
 
 namespace {
 
-int ensure(gpuart_converge *c, void **mem, size_t *have, size_t bytes) {
-    if (bytes <= *have) return 0;
-    if (*mem) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        (void)hipFree(*mem);
-        *mem = nullptr;
-        *have = 0;
-    }
-    HIP_TRY(hipMalloc(mem, bytes));
-    *have = bytes;
-    return 0;
-}
-
 /// The checks both update entry points make; `align` is what accum must be aligned to. Nothing has been written when they fail.
 int check_update(gpuart_converge *c, const void *accum, uint32_t paths_total, uint32_t w, uint32_t h, size_t align) {
-    if (!c) return fail(GPUART_HIP_ERR_ARG, "converge: handle is NULL");
+    if (int r = check_handle(LIB, c)) return r;
     if (!accum) return fail(GPUART_HIP_ERR_ARG, "converge: accum is NULL");
-    if ((uintptr_t)accum % align) return fail(GPUART_HIP_ERR_ARG, "converge: misaligned pointer (accum needs " + std::to_string(align) + " bytes)");
-    if (w == 0 || h == 0 || w > 65536 || h > 65536)
-        return fail(GPUART_HIP_ERR_ARG, "converge: bad size " + std::to_string(w) + " x " + std::to_string(h));
+    if (misaligned({accum}, align)) return fail(GPUART_HIP_ERR_ARG, "converge: misaligned pointer (accum needs " + std::to_string(align) + " bytes)");
+    if (int r = check_size(LIB, w, h)) return r;
     if (c->w && (w != c->w || h != c->h))
         return fail(GPUART_HIP_ERR_ARG, "converge: size " + std::to_string(w) + " x " + std::to_string(h) + " is not the state's " + std::to_string(c->w) +
                                             " x " + std::to_string(c->h) + " (reset the handle first)");
@@ -142,13 +109,12 @@ int check_update(gpuart_converge *c, const void *accum, uint32_t paths_total, ui
 int launch_update(gpuart_converge *c, const float4 *accum, uint32_t paths_total, uint32_t w, uint32_t h) {
     const size_t n = (size_t)w * h;
     if (!c->w) {  // the first batch after create or reset: a state of zeros
-        if (int r = ensure(c, &c->state, &c->state_bytes, n * 16)) return r;
-        HIP_TRY(hipMemsetAsync(c->state, 0, n * 16, c->stream));
+        if (int r = ensure(c->stream, c->state, n * 16)) return r;
+        HIP_TRY(hipMemsetAsync(c->state.mem, 0, n * 16, c->stream));
     }
     const float b = (float)(paths_total - c->total), Wn = (float)paths_total;
     const float r = b / Wn;
-    const dim3 grid((w + CX - 1) / CX, (h + CY - 1) / CY), block(CX, CY);
-    k_cv_update<<<grid, block, 0, c->stream>>>(accum, (float4 *)c->state, (int)w, (int)h, b, r);
+    k_cv_update<<<row_grid(w, h), row_block(), 0, c->stream>>>(accum, (float4 *)c->state.mem, (int)w, (int)h, b, r);
     HIP_TRY(hipGetLastError());
     c->w = w;
     c->h = h;
@@ -158,9 +124,9 @@ int launch_update(gpuart_converge *c, const float4 *accum, uint32_t paths_total,
 }
 
 int check_measure(gpuart_converge *c, float threshold, float lum_floor, const void *map, const gpuart_converge_summary *summary) {
-    if (!c) return fail(GPUART_HIP_ERR_ARG, "converge: handle is NULL");
+    if (int r = check_handle(LIB, c)) return r;
     if (!summary) return fail(GPUART_HIP_ERR_ARG, "converge: summary is NULL");
-    if ((uintptr_t)map % 4) return fail(GPUART_HIP_ERR_ARG, "converge: misaligned pointer (error_map needs 4 bytes)");
+    if (misaligned({map}, 4)) return fail(GPUART_HIP_ERR_ARG, "converge: misaligned pointer (error_map needs 4 bytes)");
     if (!std::isfinite(threshold) || !(threshold >= 0)) return fail(GPUART_HIP_ERR_ARG, "converge: threshold must be finite and >= 0");
     if (!std::isfinite(lum_floor) || !(lum_floor > 0)) return fail(GPUART_HIP_ERR_ARG, "converge: lum_floor must be finite and > 0");
     if (c->batches < 2)
@@ -171,14 +137,15 @@ int check_measure(gpuart_converge *c, float threshold, float lum_floor, const vo
 /// The reduction (and the map, in device memory) on the handle's stream; the words are in c->pinned when it returns 0.
 int launch_measure(gpuart_converge *c, float threshold, float lum_floor, float *map) {
     HIP_TRY(hipMemsetAsync(c->words, 0, sizeof(Words), c->stream));
-    const unsigned gx = (c->w + CX - 1) / CX, rows = (c->h + CY - 1) / CY;
-    const unsigned cap = MEASURE_MAX_BLOCKS / gx ? MEASURE_MAX_BLOCKS / gx : 1u;
-    const dim3 grid(gx, rows < cap ? rows : cap), block(CX, CY);
+    dim3 grid = row_grid(c->w, c->h);
+    const unsigned cap = MEASURE_MAX_BLOCKS / grid.x ? MEASURE_MAX_BLOCKS / grid.x : 1u;
+    if (grid.y > cap) grid.y = cap;
+    const dim3 block = row_block();
     const float nb1 = (float)(c->batches - 1), total = (float)c->total;
     if (map)
-        k_cv_measure<true><<<grid, block, 0, c->stream>>>((const float4 *)c->state, (int)c->w, (int)c->h, nb1, total, threshold, lum_floor, map, c->words);
+        k_cv_measure<true><<<grid, block, 0, c->stream>>>((const float4 *)c->state.mem, (int)c->w, (int)c->h, nb1, total, threshold, lum_floor, map, c->words);
     else
-        k_cv_measure<false><<<grid, block, 0, c->stream>>>((const float4 *)c->state, (int)c->w, (int)c->h, nb1, total, threshold, lum_floor, nullptr, c->words);
+        k_cv_measure<false><<<grid, block, 0, c->stream>>>((const float4 *)c->state.mem, (int)c->w, (int)c->h, nb1, total, threshold, lum_floor, nullptr, c->words);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(c->pinned, c->words, sizeof(Words), hipMemcpyDeviceToHost, c->stream));
     return 0;
@@ -202,51 +169,32 @@ extern "C" {
 const char *gpuart_converge_last_error(void) { return g_last_error.c_str(); }
 
 int gpuart_converge_create(int device, gpuart_converge **out) {
-    if (!out) return fail(GPUART_HIP_ERR_ARG, "converge: out is NULL");
-    *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n)
-        return fail(GPUART_HIP_ERR_NO_DEVICE, "converge: no HIP device " + std::to_string(device));
-    HIP_TRY(hipSetDevice(device));
-    gpuart_converge *c = new gpuart_converge;
-    c->device = device;
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
-        delete c;
-        return fail(GPUART_HIP_ERR_DEVICE, "converge: hipStreamCreateWithFlags failed");
-    }
+    if (int r = create_handle(LIB, device, out)) return r;
+    gpuart_converge *c = *out;
     if (hipMalloc((void **)&c->words, sizeof(Words)) != hipSuccess || hipHostMalloc((void **)&c->pinned, sizeof(Words), hipHostMallocDefault) != hipSuccess) {
         gpuart_converge_destroy(c);
+        *out = nullptr;
         return fail(GPUART_HIP_ERR_DEVICE, "converge: allocating the summary words failed");
     }
-    *out = c;
     return 0;
 }
 
 int gpuart_converge_destroy(gpuart_converge *c) {
     if (!c) return 0;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (void *m : {c->state, c->stage, (void *)c->words})
-        if (m) (void)hipFree(m);
+    destroy_handle(c, {c->state.mem, c->stage.mem, (void *)c->words});
     if (c->pinned) (void)hipHostFree(c->pinned);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return 0;
 }
 
 int gpuart_converge_reset(gpuart_converge *c) {
-    if (!c) return fail(GPUART_HIP_ERR_ARG, "converge: handle is NULL");
+    if (int r = check_handle(LIB, c)) return r;
     c->w = c->h = 0;  // the next update zeroes the state it then has
     c->total = c->batches = 0;
     return 0;
 }
 
-int gpuart_converge_finish(gpuart_converge *c) {
-    if (!c) return fail(GPUART_HIP_ERR_ARG, "converge: handle is NULL");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
+int gpuart_converge_finish(gpuart_converge *c) { return finish_handle(LIB, c); }
 
 int gpuart_converge_update(gpuart_converge *c, const float *accum, uint32_t paths_total, uint32_t w, uint32_t h) {
     if (int r = check_update(c, accum, paths_total, w, h, 16)) return r;
@@ -258,9 +206,9 @@ int gpuart_converge_update_host(gpuart_converge *c, const float *accum, uint32_t
     if (int r = check_update(c, accum, paths_total, w, h, 4)) return r;
     HIP_TRY(hipSetDevice(c->device));
     const size_t n = (size_t)w * h;
-    if (int r = ensure(c, &c->stage, &c->stage_bytes, n * 16)) return r;
-    HIP_TRY(hipMemcpyAsync(c->stage, accum, n * 16, hipMemcpyHostToDevice, c->stream));
-    if (int r = launch_update(c, (const float4 *)c->stage, paths_total, w, h)) return r;
+    if (int r = ensure(c->stream, c->stage, n * 16)) return r;
+    HIP_TRY(hipMemcpyAsync(c->stage.mem, accum, n * 16, hipMemcpyHostToDevice, c->stream));
+    if (int r = launch_update(c, (const float4 *)c->stage.mem, paths_total, w, h)) return r;
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -279,20 +227,20 @@ int gpuart_converge_measure_host(gpuart_converge *c, float threshold, float lum_
     HIP_TRY(hipSetDevice(c->device));
     const size_t n = (size_t)c->w * c->h;
     if (error_map)
-        if (int r = ensure(c, &c->stage, &c->stage_bytes, n * 4)) return r;
-    if (int r = launch_measure(c, threshold, lum_floor, error_map ? (float *)c->stage : nullptr)) return r;
-    if (error_map) HIP_TRY(hipMemcpyAsync(error_map, c->stage, n * 4, hipMemcpyDeviceToHost, c->stream));
+        if (int r = ensure(c->stream, c->stage, n * 4)) return r;
+    if (int r = launch_measure(c, threshold, lum_floor, error_map ? (float *)c->stage.mem : nullptr)) return r;
+    if (error_map) HIP_TRY(hipMemcpyAsync(error_map, c->stage.mem, n * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     fill(c, summary);
     return 0;
 }
 
 int gpuart_converge_read_state(gpuart_converge *c, float *state) {
-    if (!c) return fail(GPUART_HIP_ERR_ARG, "converge: handle is NULL");
+    if (int r = check_handle(LIB, c)) return r;
     if (!state || (uintptr_t)state % 4) return fail(GPUART_HIP_ERR_ARG, "converge: state is NULL or misaligned");
     if (!c->w) return fail(GPUART_HIP_ERR_ARG, "converge: no state before the first update");
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipMemcpyAsync(state, c->state, (size_t)c->w * c->h * 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(state, c->state.mem, (size_t)c->w * c->h * 16, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -1,37 +1,19 @@
 // denoise.hip — libgpuart_denoise.so (gfx950): the edge-aware à-trous denoiser of include/gpuart_denoise.h, which states the
 // filter operation by operation. Built without flushing fp32 denormals, with IEEE '/' and sqrt and no contraction, so that every
 // value is the one tests/denoise_ref.py computes in NumPy float32. DESIGN.md "Denoiser" describes the kernels.
-#include <hip/hip_runtime.h>
-
 #include <cmath>
-#include <string>
 
+#include "../image/image_lib.h"
 #include "gpuart_denoise.h"
 
 namespace {
 
-thread_local std::string g_last_error;
-
-int fail(int code, const std::string &msg) {
-    g_last_error = msg;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return fail(GPUART_HIP_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
+const char LIB[] = "denoise";
 
 #define DN_FN __device__ __forceinline__
 
-constexpr uint32_t US_EM_NONZERO = 1u, US_SPECULAR = 2u;  // userSphereFlags bits that take a user-sphere pixel out of the filter
-
 /// max(a, b) as the header states it: a > b ? a : b
 DN_FN float gt_or(float a, float b) { return a > b ? a : b; }
-
-DN_FN float lum(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
 
 /// the reference's PRIMITIVE_COLOR (shaders/path_tracing.glsl:123-126); the user sphere has type 0
 DN_FN float3 albedo(int type) {
@@ -40,12 +22,11 @@ DN_FN float3 albedo(int type) {
     return make_float3(0.3f, 0.3f, 0.3f);
 }
 
-/// Pixel i's class: its primitive type when it is a surface pixel, -1 otherwise.
+/// Pixel i's class: its primitive type when it is a surface pixel (image_lib.h), -1 otherwise.
 DN_FN int surface_type(const float4 *hits, const int32_t *prims, uint32_t us_flags, size_t i) {
     const int type = __float_as_int(hits[2 * i + 1].w);
-    if (type < 0) return -1;
-    if (prims[i] == -2 && (us_flags & (US_EM_NONZERO | US_SPECULAR))) return -1;
-    return type & 3;
+    if (type < 0) return -1;  // (prims is read only where something was hit)
+    return is_surface(type, prims[i], us_flags) ? type & 3 : -1;
 }
 
 // ---- steps 1 and 2: demodulation, luminance and the 7x7 variance ---------------------------------------------------------------
@@ -104,19 +85,17 @@ __global__ void __launch_bounds__(PT * PT) k_dn_prepare(const float4 *rgba, cons
 }
 
 // ---- steps 3 and 4: one à-trous level; the last one remodulates ---------------------------------------------------------------
-// A 64 x 4 block: a wave is a row segment of 64 pixels, so every tap of a wave reads 64 consecutive records (2 x 1 KiB).
+// The row block of image_lib.h: every tap of a wave reads 64 consecutive records (2 x 1 KiB).
 struct Level {
     float lum_k, depth_sigma, step;
     int s;
     uint32_t normal_pow2;
 };
 
-constexpr int AX = 64, AY = 4;
-
 template <bool LAST>
-__global__ void __launch_bounds__(AX * AY) k_dn_atrous(const float4 *st_in, const float4 *guide, float4 *st_out, int w, int h, Level lv,
-                                                       const float4 *rgba, const float4 *hits, float4 *out) {
-    const int x = blockIdx.x * AX + threadIdx.x, y = blockIdx.y * AY + threadIdx.y;
+__global__ void __launch_bounds__(ROW_X * ROW_Y) k_dn_atrous(const float4 *st_in, const float4 *guide, float4 *st_out, int w, int h, Level lv,
+                                                             const float4 *rgba, const float4 *hits, float4 *out) {
+    const int x = blockIdx.x * ROW_X + threadIdx.x, y = blockIdx.y * ROW_Y + threadIdx.y;
     if (x >= w || y >= h) return;
     const size_t i = (size_t)y * w + x;
     const float4 gp = guide[i];
@@ -167,27 +146,11 @@ __global__ void __launch_bounds__(AX * AY) k_dn_atrous(const float4 *st_in, cons
 
 }  // namespace
 
-struct gpuart_denoise {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    void *scratch = nullptr;  ///< 48 bytes per pixel: two states and the guide; then (run_host) the staged inputs and output
-    size_t scratch_bytes = 0;
+struct gpuart_denoise : ImageHandle {
+    DeviceBuffer scratch;  ///< 48 bytes per pixel: two states and the guide; then (run_host) the staged inputs and output
 };
 
 namespace {
-
-int ensure_scratch(gpuart_denoise *d, size_t bytes) {
-    if (bytes <= d->scratch_bytes) return 0;
-    if (d->scratch) {
-        HIP_TRY(hipStreamSynchronize(d->stream));
-        (void)hipFree(d->scratch);
-        d->scratch = nullptr;
-        d->scratch_bytes = 0;
-    }
-    HIP_TRY(hipMalloc(&d->scratch, bytes));
-    d->scratch_bytes = bytes;
-    return 0;
-}
 
 int check_params(const gpuart_denoise_params &p) {
     if (p.iterations > GPUART_DENOISE_MAX_ITERATIONS)
@@ -202,12 +165,11 @@ int check_params(const gpuart_denoise_params &p) {
 /// The checks both entry points make; `align` is what rgba, hits and out must be aligned to.
 int check_run(gpuart_denoise *d, const void *rgba, const void *hits, const void *prims, uint32_t w, uint32_t h,
               const gpuart_denoise_params *p, const void *out, size_t align) {
-    if (!d) return fail(GPUART_HIP_ERR_ARG, "denoise: handle is NULL");
+    if (int r = check_handle(LIB, d)) return r;
     if (!rgba || !hits || !prims || !out) return fail(GPUART_HIP_ERR_ARG, "denoise: rgba, hits, prims or out is NULL");
-    if ((uintptr_t)rgba % align || (uintptr_t)hits % align || (uintptr_t)out % align || (uintptr_t)prims % 4)
+    if (misaligned({rgba, hits, out}, align) || misaligned({prims}, 4))
         return fail(GPUART_HIP_ERR_ARG, "denoise: misaligned pointer (rgba, hits and out need " + std::to_string(align) + " bytes, prims 4)");
-    if (w == 0 || h == 0 || w > 65536 || h > 65536)
-        return fail(GPUART_HIP_ERR_ARG, "denoise: bad size " + std::to_string(w) + " x " + std::to_string(h));
+    if (int r = check_size(LIB, w, h)) return r;
     return p ? check_params(*p) : 0;
 }
 
@@ -219,11 +181,11 @@ int launch(gpuart_denoise *d, const float4 *rgba, const float4 *hits, const int3
         if (out != rgba) HIP_TRY(hipMemcpyAsync(out, rgba, n * sizeof(float4), hipMemcpyDeviceToDevice, d->stream));
         return 0;
     }
-    float4 *st[2] = {(float4 *)d->scratch, (float4 *)d->scratch + n};
-    float4 *guide = (float4 *)d->scratch + 2 * n;
+    float4 *st[2] = {(float4 *)d->scratch.mem, (float4 *)d->scratch.mem + n};
+    float4 *guide = (float4 *)d->scratch.mem + 2 * n;
     k_dn_prepare<<<dim3((w + PT - 1) / PT, (h + PT - 1) / PT), dim3(PT, PT), 0, d->stream>>>(rgba, hits, prims, us_flags, w, h, st[0], guide);
     HIP_TRY(hipGetLastError());
-    const dim3 grid((w + AX - 1) / AX, (h + AY - 1) / AY), block(AX, AY);
+    const dim3 grid = row_grid(w, h), block = row_block();
     for (uint32_t it = 0; it < p.iterations; it++) {
         Level lv;
         lv.lum_k = p.lum_k;
@@ -255,39 +217,16 @@ int gpuart_denoise_defaults(gpuart_denoise_params *p) {
     return 0;
 }
 
-int gpuart_denoise_create(int device, gpuart_denoise **out) {
-    if (!out) return fail(GPUART_HIP_ERR_ARG, "denoise: out is NULL");
-    *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n)
-        return fail(GPUART_HIP_ERR_NO_DEVICE, "denoise: no HIP device " + std::to_string(device));
-    HIP_TRY(hipSetDevice(device));
-    gpuart_denoise *d = new gpuart_denoise;
-    d->device = device;
-    if (hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) != hipSuccess) {
-        delete d;
-        return fail(GPUART_HIP_ERR_DEVICE, "denoise: hipStreamCreateWithFlags failed");
-    }
-    *out = d;
-    return 0;
-}
+int gpuart_denoise_create(int device, gpuart_denoise **out) { return create_handle(LIB, device, out); }
 
 int gpuart_denoise_destroy(gpuart_denoise *d) {
     if (!d) return 0;
-    (void)hipSetDevice(d->device);
-    if (d->stream) (void)hipStreamSynchronize(d->stream);
-    if (d->scratch) (void)hipFree(d->scratch);
-    if (d->stream) (void)hipStreamDestroy(d->stream);
+    destroy_handle(d, {d->scratch.mem});
     delete d;
     return 0;
 }
 
-int gpuart_denoise_finish(gpuart_denoise *d) {
-    if (!d) return fail(GPUART_HIP_ERR_ARG, "denoise: handle is NULL");
-    HIP_TRY(hipSetDevice(d->device));
-    HIP_TRY(hipStreamSynchronize(d->stream));
-    return 0;
-}
+int gpuart_denoise_finish(gpuart_denoise *d) { return finish_handle(LIB, d); }
 
 int gpuart_denoise_run(gpuart_denoise *d, const float *rgba, const gpuart_ray_hit *hits, const int32_t *prims, uint32_t userSphereFlags,
                        uint32_t w, uint32_t h, const gpuart_denoise_params *p, float *out) {
@@ -297,7 +236,7 @@ int gpuart_denoise_run(gpuart_denoise *d, const float *rgba, const gpuart_ray_hi
     if (p) dp = *p;
     else gpuart_denoise_defaults(&dp);
     HIP_TRY(hipSetDevice(d->device));
-    if ((r = ensure_scratch(d, (size_t)w * h * 48))) return r;
+    if ((r = ensure(d->stream, d->scratch, (size_t)w * h * 48))) return r;
     return launch(d, (const float4 *)rgba, (const float4 *)hits, prims, userSphereFlags, (int)w, (int)h, dp, (float4 *)out);
 }
 
@@ -310,17 +249,12 @@ int gpuart_denoise_run_host(gpuart_denoise *d, const float *rgba, const gpuart_r
     else gpuart_denoise_defaults(&dp);
     HIP_TRY(hipSetDevice(d->device));
     const size_t n = (size_t)w * h;
-    // the filter's 48 bytes per pixel, then the staged radiance (16, also the output), records (32) and ordinals (4)
-    if ((r = ensure_scratch(d, n * (48 + 16 + 32 + 4)))) return r;
-    char *base = (char *)d->scratch + n * 48;
-    float4 *d_rgba = (float4 *)base;
-    float4 *d_hits = (float4 *)(base + n * 16);
-    int32_t *d_prims = (int32_t *)(base + n * 48);
-    HIP_TRY(hipMemcpyAsync(d_rgba, rgba, n * 16, hipMemcpyHostToDevice, d->stream));
-    HIP_TRY(hipMemcpyAsync(d_hits, hits, n * 32, hipMemcpyHostToDevice, d->stream));
-    HIP_TRY(hipMemcpyAsync(d_prims, prims, n * 4, hipMemcpyHostToDevice, d->stream));
-    if ((r = launch(d, d_rgba, d_hits, d_prims, userSphereFlags, (int)w, (int)h, dp, d_rgba))) return r;
-    HIP_TRY(hipMemcpyAsync(out, d_rgba, n * 16, hipMemcpyDeviceToHost, d->stream));
+    // the filter's 48 bytes per pixel, then the staged inputs; the staged radiance is also the output
+    if ((r = ensure(d->stream, d->scratch, n * (48 + STAGED_BYTES)))) return r;
+    Staged in;
+    if ((r = stage_gbuffer(d->stream, (char *)d->scratch.mem + n * 48, n, rgba, hits, prims, in))) return r;
+    if ((r = launch(d, in.rgba, in.hits, in.prims, userSphereFlags, (int)w, (int)h, dp, in.rgba))) return r;
+    HIP_TRY(hipMemcpyAsync(out, in.rgba, n * 16, hipMemcpyDeviceToHost, d->stream));
     HIP_TRY(hipStreamSynchronize(d->stream));
     return 0;
 }

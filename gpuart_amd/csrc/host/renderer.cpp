@@ -76,16 +76,16 @@ Renderer::Renderer(unsigned viewportWidth, unsigned viewportHeight, const Camera
 
 Renderer::~Renderer() {
     if (Converge) gpuart_converge_destroy(Converge);
-    if (ConvergeMem) (void)hipFree(ConvergeMem);
+    ConvergeMem.Release();
     if (Temporal) gpuart_temporal_destroy(Temporal);
     if (Denoiser) gpuart_denoise_destroy(Denoiser);
-    if (DenoiseMem) (void)hipFree(DenoiseMem);
+    DenoiseMem.Release();
     if (Backend) gpuart_hip_destroy(Backend);
 }
 
-bool Renderer::Check(int status, const char *what) {
+bool Renderer::Check(int status, const char *what, const char *(*lastError)(void)) {
     if (status == 0) return true;
-    std::cerr << "Renderer: error " << status << " while " << what << ": " << gpuart_hip_last_error() << std::endl;
+    std::cerr << "Renderer: error " << status << " while " << what << ": " << lastError() << std::endl;
     return false;
 }
 
@@ -371,16 +371,8 @@ bool Renderer::ReadRadiance(float *rgba, bool normalized) {
 }
 
 namespace {
-bool checkDn(int status, const char *what) {
-    if (status == 0) return true;
-    std::cerr << "Renderer: error " << status << " while " << what << ": " << gpuart_denoise_last_error() << std::endl;
-    return false;
-}
-bool checkTp(int status, const char *what) {
-    if (status == 0) return true;
-    std::cerr << "Renderer: error " << status << " while " << what << ": " << gpuart_temporal_last_error() << std::endl;
-    return false;
-}
+const auto DN = gpuart_denoise_last_error, TP = gpuart_temporal_last_error, CV = gpuart_converge_last_error;  // for Check
+bool finite(float x) { return x - x == 0.0f; }
 bool checkHip(hipError_t e, const char *what) {
     if (e == hipSuccess) return true;
     std::cerr << "Renderer: " << what << ": " << hipGetErrorString(e) << std::endl;
@@ -398,18 +390,26 @@ struct ViewBuffers {
 };
 }  // namespace
 
+void Renderer::PixelBuffer::Release() {
+    if (mem) (void)hipFree(mem);
+    mem = nullptr;
+    pixels = 0;
+}
+
+bool Renderer::PixelBuffer::Fit(size_t n, size_t bytesPerPixel, const char *what) {
+    if (n == pixels) return true;
+    Release();
+    if (!checkHip(hipMalloc(&mem, n * bytesPerPixel), what)) return false;
+    pixels = n;
+    return true;
+}
+
 bool Renderer::StageView() {
     if (!checkHip(hipSetDevice(Device), "hipSetDevice")) return false;
     const size_t n = (size_t)Tile.w * Tile.h;
-    if (n != DenoisePixels) {
-        if (DenoiseMem) (void)hipFree(DenoiseMem);
-        DenoiseMem = nullptr;
-        DenoisePixels = 0;
-        GBufferValid = false;
-        if (!checkHip(hipMalloc(&DenoiseMem, n * (16 + 32 + 16 + 4)), "allocating the denoiser's buffers")) return false;
-        DenoisePixels = n;
-    }
-    const ViewBuffers b(DenoiseMem, n);
+    if (n != DenoiseMem.pixels) GBufferValid = false;
+    if (!DenoiseMem.Fit(n, 16 + 32 + 16 + 4, "allocating the denoiser's buffers")) return false;
+    const ViewBuffers b(DenoiseMem.mem, n);
     const float us[4] = {UserSphere.pos.x, UserSphere.pos.y, UserSphere.pos.z, UserSphere.radius};
     if (!GBufferValid || memcmp(us, GBufferSphere, sizeof us) != 0) {
         GBufferValid = false;
@@ -425,12 +425,12 @@ bool Renderer::StageView() {
 
 bool Renderer::ReadDenoised(float *rgba, const gpuart_denoise_params *p) {
     if (!IsOK || !rgba) return false;
-    if (!Denoiser && !checkDn(gpuart_denoise_create(Device, &Denoiser), "creating the denoiser")) return false;
+    if (!Denoiser && !Check(gpuart_denoise_create(Device, &Denoiser), "creating the denoiser", DN)) return false;
     if (!StageView()) return false;
     const size_t n = (size_t)Tile.w * Tile.h;
-    const ViewBuffers b(DenoiseMem, n);
-    if (!checkDn(gpuart_denoise_run(Denoiser, b.radiance, b.hits, b.prims, UserSphere.flags, Tile.w, Tile.h, p, b.filtered), "denoising")) return false;
-    if (!checkDn(gpuart_denoise_finish(Denoiser), "denoising")) return false;
+    const ViewBuffers b(DenoiseMem.mem, n);
+    if (!Check(gpuart_denoise_run(Denoiser, b.radiance, b.hits, b.prims, UserSphere.flags, Tile.w, Tile.h, p, b.filtered), "denoising", DN)) return false;
+    if (!Check(gpuart_denoise_finish(Denoiser), "denoising", DN)) return false;
     return checkHip(hipMemcpy(rgba, b.filtered, n * 16, hipMemcpyDeviceToHost), "reading the denoised frame");
 }
 
@@ -438,7 +438,6 @@ bool Renderer::ReadDenoised(float *rgba, const gpuart_denoise_params *p) {
 bool Renderer::SetTemporalHistory(bool on, const gpuart_temporal_params *tp) {
     if (tp) {
         // the ranges gpuart_temporal_accumulate accepts: a commit inside a setter has nobody to report them to
-        auto finite = [](float x) { return x - x == 0.0f; };
         if (!finite(tp->max_history) || !(tp->max_history >= 0) || !finite(tp->plane_tol) || !(tp->plane_tol >= 0) ||
             !(tp->normal_min >= -1) || !(tp->normal_min <= 1)) {
             std::cerr << "Renderer: temporal parameters out of range." << std::endl;
@@ -471,14 +470,14 @@ bool Renderer::MakeTemporalView(gpuart_temporal_view &v) const {
 void Renderer::CommitTemporalView() {
     if (!TemporalOn || !IsOK || PathTracing.numPathsRendered == 0) return;
     // A commit that fails leaves no history rather than a stale one.
-    bool ok = Temporal || checkTp(gpuart_temporal_create(Device, &Temporal), "creating the temporal accumulator");
+    bool ok = Temporal || Check(gpuart_temporal_create(Device, &Temporal), "creating the temporal accumulator", TP);
     gpuart_temporal_view v;
     ok = ok && StageView() && MakeTemporalView(v);
     if (ok) {
-        const ViewBuffers b(DenoiseMem, (size_t)Tile.w * Tile.h);
-        ok = checkTp(gpuart_temporal_accumulate(Temporal, b.radiance, PathTracing.numPathsRendered, b.hits, b.prims, Tile.w, Tile.h, &v,
-                                                &TemporalParams, 1, b.filtered, nullptr), "committing the view to the history") &&
-             checkTp(gpuart_temporal_finish(Temporal), "committing the view to the history");
+        const ViewBuffers b(DenoiseMem.mem, (size_t)Tile.w * Tile.h);
+        ok = Check(gpuart_temporal_accumulate(Temporal, b.radiance, PathTracing.numPathsRendered, b.hits, b.prims, Tile.w, Tile.h, &v,
+                                              &TemporalParams, 1, b.filtered, nullptr), "committing the view to the history", TP) &&
+             Check(gpuart_temporal_finish(Temporal), "committing the view to the history", TP);
     }
     HistoryCommitted = ok;
     if (!ok && Temporal) gpuart_temporal_reset(Temporal);
@@ -487,29 +486,21 @@ void Renderer::CommitTemporalView() {
 bool Renderer::ReadPreview(float *rgba, const gpuart_denoise_params *dn, const gpuart_temporal_params *tp) {
     if (!TemporalOn || !HistoryCommitted || PathTracing.numPathsRendered == 0) return ReadDenoised(rgba, dn);
     if (!IsOK || !rgba) return false;
-    if (!Denoiser && !checkDn(gpuart_denoise_create(Device, &Denoiser), "creating the denoiser")) return false;
+    if (!Denoiser && !Check(gpuart_denoise_create(Device, &Denoiser), "creating the denoiser", DN)) return false;
     gpuart_temporal_view v;
     if (!StageView() || !MakeTemporalView(v)) return false;
     const size_t n = (size_t)Tile.w * Tile.h;
-    const ViewBuffers b(DenoiseMem, n);
-    if (!checkTp(gpuart_temporal_accumulate(Temporal, b.radiance, PathTracing.numPathsRendered, b.hits, b.prims, Tile.w, Tile.h, &v,
-                                            tp ? tp : &TemporalParams, 0, b.filtered, nullptr), "blending the history")) return false;
-    if (!checkTp(gpuart_temporal_finish(Temporal), "blending the history")) return false;
+    const ViewBuffers b(DenoiseMem.mem, n);
+    if (!Check(gpuart_temporal_accumulate(Temporal, b.radiance, PathTracing.numPathsRendered, b.hits, b.prims, Tile.w, Tile.h, &v,
+                                          tp ? tp : &TemporalParams, 0, b.filtered, nullptr), "blending the history", TP)) return false;
+    if (!Check(gpuart_temporal_finish(Temporal), "blending the history", TP)) return false;
     // (the filter may run in place: include/gpuart_denoise.h)
-    if (!checkDn(gpuart_denoise_run(Denoiser, b.filtered, b.hits, b.prims, UserSphere.flags, Tile.w, Tile.h, dn, b.filtered), "denoising")) return false;
-    if (!checkDn(gpuart_denoise_finish(Denoiser), "denoising")) return false;
+    if (!Check(gpuart_denoise_run(Denoiser, b.filtered, b.hits, b.prims, UserSphere.flags, Tile.w, Tile.h, dn, b.filtered), "denoising", DN)) return false;
+    if (!Check(gpuart_denoise_finish(Denoiser), "denoising", DN)) return false;
     return checkHip(hipMemcpy(rgba, b.filtered, n * 16, hipMemcpyDeviceToHost), "reading the preview");
 }
 
 // ---- render until converged (include/gpuart_converge.h) -----------------------------------------------------------------
-namespace {
-bool checkCv(int status, const char *what) {
-    if (status == 0) return true;
-    std::cerr << "Renderer: error " << status << " while " << what << ": " << gpuart_converge_last_error() << std::endl;
-    return false;
-}
-}  // namespace
-
 void Renderer::ResetConvergeNow() {
     gpuart_converge_reset(Converge);
     ConvergeBatches = ConvergeTotal = 0;
@@ -517,31 +508,24 @@ void Renderer::ResetConvergeNow() {
 
 int Renderer::RenderUntil(float threshold, float maxAboveShare, unsigned batchPaths, float lumFloor, gpuart_converge_summary *last) {
     if (!IsOK) return -1;
-    auto finite = [](float x) { return x - x == 0.0f; };
     if (!finite(threshold) || !(threshold >= 0) || !(maxAboveShare >= 0) || batchPaths == 0 || !finite(lumFloor) || !(lumFloor > 0)) {
         std::cerr << "Renderer: RenderUntil arguments out of range." << std::endl;
         return -1;
     }
-    if (!Converge && !checkCv(gpuart_converge_create(Device, &Converge), "creating the convergence estimator")) return -1;
+    if (!Converge && !Check(gpuart_converge_create(Device, &Converge), "creating the convergence estimator", CV)) return -1;
     if (!checkHip(hipSetDevice(Device), "hipSetDevice")) return -1;
     const size_t n = (size_t)Tile.w * Tile.h;
-    if (n != ConvergePixels) {
-        if (ConvergeMem) (void)hipFree(ConvergeMem);
-        ConvergeMem = nullptr;
-        ConvergePixels = 0;
-        if (!checkHip(hipMalloc(&ConvergeMem, n * 16), "allocating the estimator's copy of the accumulator")) return -1;
-        ConvergePixels = n;
-    }
+    if (!ConvergeMem.Fit(n, 16, "allocating the estimator's copy of the accumulator")) return -1;
     // the raw accumulator as one more batch: divide_by 1 copies the sums exactly; a buffer of its own: the denoiser's cached view
     // (StageView) stays as it is. The wait lets the next export reuse the buffer.
     auto showAccumulator = [&]() {
-        if (!Check(gpuart_hip_export(Backend, 1, ConvergeMem, 1.0f), "exporting the accumulator")) return false;
+        if (!Check(gpuart_hip_export(Backend, 1, ConvergeMem.mem, 1.0f), "exporting the accumulator")) return false;
         if (!Check(gpuart_hip_finish(Backend), "waiting for the device")) return false;
-        if (!checkCv(gpuart_converge_update(Converge, (const float *)ConvergeMem, PathTracing.numPathsRendered, Tile.w, Tile.h),
-                     "updating the convergence estimate")) return false;
+        if (!Check(gpuart_converge_update(Converge, (const float *)ConvergeMem.mem, PathTracing.numPathsRendered, Tile.w, Tile.h),
+                   "updating the convergence estimate", CV)) return false;
         ConvergeTotal = PathTracing.numPathsRendered;
         ConvergeBatches++;
-        return checkCv(gpuart_converge_finish(Converge), "updating the convergence estimate");
+        return Check(gpuart_converge_finish(Converge), "updating the convergence estimate", CV);
     };
     // paths the estimate has never seen — a loaded checkpoint, plain passes after a restart — are its first batch, of their own weight
     if (ConvergeBatches == 0 && PathTracing.numPathsRendered > 0 && !showAccumulator()) return -1;
@@ -559,7 +543,7 @@ int Renderer::RenderUntil(float threshold, float maxAboveShare, unsigned batchPa
         if (PathTracing.numPathsRendered > ConvergeTotal && !showAccumulator()) return -1;
         if (ConvergeBatches >= 2) {
             gpuart_converge_summary s;
-            if (!checkCv(gpuart_converge_measure(Converge, threshold, lumFloor, nullptr, &s), "measuring the convergence")) return -1;
+            if (!Check(gpuart_converge_measure(Converge, threshold, lumFloor, nullptr, &s), "measuring the convergence", CV)) return -1;
             if (last) *last = s;
             if ((double)s.above <= (double)maxAboveShare * (double)s.pixels) return 1;
         }
@@ -570,7 +554,7 @@ int Renderer::RenderUntil(float threshold, float maxAboveShare, unsigned batchPa
 bool Renderer::ReadErrorMap(float *e, float lumFloor) {
     if (!IsOK || !e || !Converge || ConvergeBatches < 2) return false;
     gpuart_converge_summary s;
-    return checkCv(gpuart_converge_measure_host(Converge, 0.0f, lumFloor, e, &s), "reading the error map");
+    return Check(gpuart_converge_measure_host(Converge, 0.0f, lumFloor, e, &s), "reading the error map", CV);
 }
 
 // ---- checkpoint / resume ---------------------------------------------------------------------------------------------

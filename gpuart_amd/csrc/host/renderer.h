@@ -175,9 +175,15 @@ private:
 
     bool IsOK = false;
     int Device = 0;
+    /// Device memory for the tile's pixels: allocated again, its content lost, whenever their number changes.
+    struct PixelBuffer {
+        void *mem = nullptr;
+        size_t pixels = 0;
+        bool Fit(size_t n, size_t bytesPerPixel, const char *what);  ///< false if `what` failed (std::cerr says why)
+        void Release();
+    };
     gpuart_denoise *Denoiser = nullptr;  ///< made by the first ReadDenoised
-    void *DenoiseMem = nullptr;          ///< device: radiance (16 B), G-buffer record (32), filtered (16), ordinal (4) per tile pixel
-    size_t DenoisePixels = 0;
+    PixelBuffer DenoiseMem;              ///< radiance (16 B), G-buffer record (32), filtered (16), ordinal (4) per tile pixel
     bool GBufferValid = false;           ///< DenoiseMem holds the G-buffer of this camera, scene and tile for GBufferSphere
     float GBufferSphere[4] = {0, 0, 0, 0};
     gpuart_temporal *Temporal = nullptr;  ///< made by the first commit
@@ -185,8 +191,7 @@ private:
     bool HistoryCommitted = false;        ///< Temporal holds a history
     gpuart_temporal_params TemporalParams{};  ///< of the commits (SetTemporalHistory)
     gpuart_converge *Converge = nullptr;  ///< made by the first RenderUntil
-    void *ConvergeMem = nullptr;          ///< device: the raw accumulator of RenderUntil's last batch, 16 B per tile pixel
-    size_t ConvergePixels = 0;
+    PixelBuffer ConvergeMem;              ///< the raw accumulator of RenderUntil's last batch, 16 B per tile pixel
     unsigned ConvergeBatches = 0, ConvergeTotal = 0;  ///< what Converge has seen since its last reset
     ScreenBasis CurrentBasis;             ///< what SetCamera gave the back end
     double LastSetPrimitivesMs[4] = {0, 0, 0, 0};
@@ -211,7 +216,8 @@ private:
     void DropTemporalHistory() { if (HistoryCommitted) DropTemporalHistoryNow(); }
     void DropTemporalHistoryNow();
     void ResetConvergeNow();
-    bool Check(int status, const char *what);
+    /// A status of the back end or, with their gpuart_*_last_error, of one of the image libraries: false (std::cerr says why) unless 0.
+    bool Check(int status, const char *what, const char *(*lastError)(void) = gpuart_hip_last_error);
 };
 
 }  // namespace gpuart

@@ -1,33 +1,17 @@
 // temporal.hip — libgpuart_temporal.so (gfx950): temporal accumulation by reprojection, include/gpuart_temporal.h, which states the
 // algorithm operation by operation. Built like the denoiser — fp32 denormals kept, IEEE '/' and sqrt, no contraction — so that every
 // value is the one tests/temporal_ref.py computes in NumPy float32. DESIGN.md "Temporal accumulation" describes the kernel.
-#include <hip/hip_runtime.h>
-
 #include <cmath>
 #include <cstring>
-#include <string>
 
+#include "../image/image_lib.h"
 #include "gpuart_temporal.h"
 
 namespace {
 
-thread_local std::string g_last_error;
-
-int fail(int code, const std::string &msg) {
-    g_last_error = msg;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return fail(GPUART_HIP_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
+const char LIB[] = "temporal";
 
 #define TP_FN __host__ __device__ __forceinline__
-
-constexpr uint32_t US_EM_NONZERO = 1u, US_SPECULAR = 2u;  // userSphereFlags bits that take a user-sphere pixel out of the history
 
 struct V3 {
     float x, y, z;
@@ -39,7 +23,7 @@ TP_FN V3 cross(V3 a, V3 b) { return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * 
 // The history of one tile: three planes of 16 bytes per pixel, so that a tap is at most three 16-byte requests and the taps of a wave
 // (neighbouring lanes, neighbouring history pixels) fall into the same lines.
 //   col   {r, g, b, len}
-//   guide {n.xyz, class}   class as int bits: -1 not a surface pixel, else (type & 3) | (user sphere ? 4 : 0)
+//   guide {n.xyz, class}   class as int bits: -1 not a surface pixel (image_lib.h), else (type & 3) | (user sphere ? 4 : 0)
 //   point {p.xyz, 0}
 struct History {
     float4 *col, *guide, *point;
@@ -54,22 +38,21 @@ struct Reproject {
     int have;         ///< the handle has a history
 };
 
-// A 64 x 4 block: a wave is 64 consecutive pixels of a row. The pixel's colour, record and ordinal are coalesced 16-byte-per-lane loads;
-// the four taps of neighbouring lanes are neighbouring history pixels.
-constexpr int AX = 64, AY = 4;
+// The row block of image_lib.h. The pixel's colour, record and ordinal are coalesced 16-byte-per-lane loads; the four taps of
+// neighbouring lanes are neighbouring history pixels.
 
 template <bool COMMIT>
-__global__ void __launch_bounds__(AX * AY) k_tp_accumulate(const float4 *rgba, const float4 *hits, const int32_t *prims, uint32_t us_flags,
-                                                           float s, int w, int h, Reproject rp, History old, float max_history,
-                                                           float plane_tol, float normal_min, float4 *out, float *out_len, History next) {
-    const int x = blockIdx.x * AX + threadIdx.x, y = blockIdx.y * AY + threadIdx.y;
+__global__ void __launch_bounds__(ROW_X * ROW_Y) k_tp_accumulate(const float4 *rgba, const float4 *hits, const int32_t *prims, uint32_t us_flags,
+                                                                 float s, int w, int h, Reproject rp, History old, float max_history,
+                                                                 float plane_tol, float normal_min, float4 *out, float *out_len, History next) {
+    const int x = blockIdx.x * ROW_X + threadIdx.x, y = blockIdx.y * ROW_Y + threadIdx.y;
     if (x >= w || y >= h) return;
     const size_t i = (size_t)y * w + x;
     const float4 c = rgba[i];
     const float4 h0 = hits[2 * i], h1 = hits[2 * i + 1];
     const int32_t prim = prims[i];
     const int type = __float_as_int(h1.w);
-    int cls = -1;
+    int cls = -1;  // is_surface(type, prim, us_flags) of image_lib.h, written out (see there), and the temporal library's own | 4
     if (type >= 0 && !(prim == -2 && (us_flags & (US_EM_NONZERO | US_SPECULAR)))) cls = (type & 3) | (prim == -2 ? 4 : 0);
     const V3 p{h0.y, h0.z, h0.w}, n{h1.x, h1.y, h1.z};
     float4 o = c;
@@ -141,32 +124,15 @@ __global__ void __launch_bounds__(AX * AY) k_tp_accumulate(const float4 *rgba, c
 
 }  // namespace
 
-struct gpuart_temporal {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    void *hist[2] = {nullptr, nullptr};  ///< 48 bytes per pixel each: the planes of History
-    size_t hist_bytes[2] = {0, 0};
+struct gpuart_temporal : ImageHandle {
+    DeviceBuffer hist[2];  ///< 48 bytes per pixel each: the planes of History
     int cur = 0;        ///< hist[cur] is the history when `have`
     bool have = false;
     gpuart_temporal_view view{};  ///< the history's view
-    void *stage = nullptr;        ///< accumulate_host: radiance (16 B, also the blend), records (32), ordinals (4), lengths (4) per pixel
-    size_t stage_bytes = 0;
+    DeviceBuffer stage;  ///< accumulate_host: the staged inputs (the radiance is also the blend), then the lengths (4 B per pixel)
 };
 
 namespace {
-
-int ensure(gpuart_temporal *t, void **mem, size_t *have, size_t bytes) {
-    if (bytes <= *have) return 0;
-    if (*mem) {
-        HIP_TRY(hipStreamSynchronize(t->stream));
-        (void)hipFree(*mem);
-        *mem = nullptr;
-        *have = 0;
-    }
-    HIP_TRY(hipMalloc(mem, bytes));
-    *have = bytes;
-    return 0;
-}
 
 History planes(void *mem, size_t n) {
     float4 *b = (float4 *)mem;
@@ -198,12 +164,11 @@ int check_geom(const gpuart_tile_geom &g, uint32_t w, uint32_t h) {
 /// The checks both entry points make; `align` is what rgba, hits and out_rgba must be aligned to.
 int check_call(gpuart_temporal *t, const void *rgba, uint32_t spp, const void *hits, const void *prims, uint32_t w, uint32_t h,
                const gpuart_temporal_view *view, const gpuart_temporal_params *p, const void *out, const void *out_len, size_t align) {
-    if (!t) return fail(GPUART_HIP_ERR_ARG, "temporal: handle is NULL");
+    if (int r = check_handle(LIB, t)) return r;
     if (!rgba || !hits || !prims || !out || !view) return fail(GPUART_HIP_ERR_ARG, "temporal: rgba, hits, prims, view or out_rgba is NULL");
-    if ((uintptr_t)rgba % align || (uintptr_t)hits % align || (uintptr_t)out % align || (uintptr_t)prims % 4 || (uintptr_t)out_len % 4)
+    if (misaligned({rgba, hits, out}, align) || misaligned({prims, out_len}, 4))
         return fail(GPUART_HIP_ERR_ARG, "temporal: misaligned pointer (rgba, hits and out_rgba need " + std::to_string(align) + " bytes, prims and out_len 4)");
-    if (w == 0 || h == 0 || w > 65536 || h > 65536)
-        return fail(GPUART_HIP_ERR_ARG, "temporal: bad size " + std::to_string(w) + " x " + std::to_string(h));
+    if (int r = check_size(LIB, w, h)) return r;
     if (int r = check_geom(view->geom, w, h)) return r;
     if (spp == 0) return fail(GPUART_HIP_ERR_ARG, "temporal: spp is 0 (the accumulator must hold at least one path)");
     return p ? check_params(*p) : 0;
@@ -231,14 +196,14 @@ int launch(gpuart_temporal *t, const float4 *rgba, uint32_t spp, const float4 *h
         rp.band_rows = (int)hv.geom.band_rows; rp.band_stride = (int)hv.geom.band_stride;
         rp.sphere_same = memcmp(hv.userSphere, view.userSphere, sizeof view.userSphere) == 0;
         rp.have = 1;
-        old = planes(t->hist[t->cur], (size_t)hv.geom.tw * hv.geom.th);
+        old = planes(t->hist[t->cur].mem, (size_t)hv.geom.tw * hv.geom.th);
     }
     const int nxt = t->cur ^ (t->have ? 1 : 0);
     if (commit) {
-        if (int r = ensure(t, &t->hist[nxt], &t->hist_bytes[nxt], n * 48)) return r;
-        next = planes(t->hist[nxt], n);
+        if (int r = ensure(t->stream, t->hist[nxt], n * 48)) return r;
+        next = planes(t->hist[nxt].mem, n);
     }
-    const dim3 grid((w + AX - 1) / AX, (h + AY - 1) / AY), block(AX, AY);
+    const dim3 grid = row_grid(w, h), block = row_block();
     if (commit)
         k_tp_accumulate<true><<<grid, block, 0, t->stream>>>(rgba, hits, prims, view.userSphereFlags, (float)spp, w, h, rp, old, p.max_history,
                                                               p.plane_tol, p.normal_min, out, out_len, next);
@@ -268,46 +233,22 @@ int gpuart_temporal_defaults(gpuart_temporal_params *p) {
     return 0;
 }
 
-int gpuart_temporal_create(int device, gpuart_temporal **out) {
-    if (!out) return fail(GPUART_HIP_ERR_ARG, "temporal: out is NULL");
-    *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n)
-        return fail(GPUART_HIP_ERR_NO_DEVICE, "temporal: no HIP device " + std::to_string(device));
-    HIP_TRY(hipSetDevice(device));
-    gpuart_temporal *t = new gpuart_temporal;
-    t->device = device;
-    if (hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking) != hipSuccess) {
-        delete t;
-        return fail(GPUART_HIP_ERR_DEVICE, "temporal: hipStreamCreateWithFlags failed");
-    }
-    *out = t;
-    return 0;
-}
+int gpuart_temporal_create(int device, gpuart_temporal **out) { return create_handle(LIB, device, out); }
 
 int gpuart_temporal_destroy(gpuart_temporal *t) {
     if (!t) return 0;
-    (void)hipSetDevice(t->device);
-    if (t->stream) (void)hipStreamSynchronize(t->stream);
-    for (void *m : {t->hist[0], t->hist[1], t->stage})
-        if (m) (void)hipFree(m);
-    if (t->stream) (void)hipStreamDestroy(t->stream);
+    destroy_handle(t, {t->hist[0].mem, t->hist[1].mem, t->stage.mem});
     delete t;
     return 0;
 }
 
 int gpuart_temporal_reset(gpuart_temporal *t) {
-    if (!t) return fail(GPUART_HIP_ERR_ARG, "temporal: handle is NULL");
+    if (int r = check_handle(LIB, t)) return r;
     t->have = false;
     return 0;
 }
 
-int gpuart_temporal_finish(gpuart_temporal *t) {
-    if (!t) return fail(GPUART_HIP_ERR_ARG, "temporal: handle is NULL");
-    HIP_TRY(hipSetDevice(t->device));
-    HIP_TRY(hipStreamSynchronize(t->stream));
-    return 0;
-}
+int gpuart_temporal_finish(gpuart_temporal *t) { return finish_handle(LIB, t); }
 
 int gpuart_temporal_accumulate(gpuart_temporal *t, const float *rgba, uint32_t spp, const gpuart_ray_hit *hits, const int32_t *prims,
                                uint32_t w, uint32_t h, const gpuart_temporal_view *view, const gpuart_temporal_params *p, int commit,
@@ -331,18 +272,13 @@ int gpuart_temporal_accumulate_host(gpuart_temporal *t, const float *rgba, uint3
     else gpuart_temporal_defaults(&tp);
     HIP_TRY(hipSetDevice(t->device));
     const size_t n = (size_t)w * h;
-    // the staged radiance (16 bytes per pixel, also the blend), records (32), ordinals (4) and lengths (4)
-    if ((r = ensure(t, &t->stage, &t->stage_bytes, n * (16 + 32 + 4 + 4)))) return r;
-    char *base = (char *)t->stage;
-    float4 *d_rgba = (float4 *)base;
-    float4 *d_hits = (float4 *)(base + n * 16);
-    int32_t *d_prims = (int32_t *)(base + n * 48);
-    float *d_len = (float *)(base + n * 52);
-    HIP_TRY(hipMemcpyAsync(d_rgba, rgba, n * 16, hipMemcpyHostToDevice, t->stream));
-    HIP_TRY(hipMemcpyAsync(d_hits, hits, n * 32, hipMemcpyHostToDevice, t->stream));
-    HIP_TRY(hipMemcpyAsync(d_prims, prims, n * 4, hipMemcpyHostToDevice, t->stream));
-    if ((r = launch(t, d_rgba, spp, d_hits, d_prims, (int)w, (int)h, *view, tp, commit != 0, d_rgba, d_len))) return r;
-    HIP_TRY(hipMemcpyAsync(out_rgba, d_rgba, n * 16, hipMemcpyDeviceToHost, t->stream));
+    // the staged inputs (the staged radiance is also the blend), then the lengths (4 bytes per pixel)
+    if ((r = ensure(t->stream, t->stage, n * (STAGED_BYTES + 4)))) return r;
+    Staged in;
+    if ((r = stage_gbuffer(t->stream, t->stage.mem, n, rgba, hits, prims, in))) return r;
+    float *d_len = (float *)((char *)t->stage.mem + n * STAGED_BYTES);
+    if ((r = launch(t, in.rgba, spp, in.hits, in.prims, (int)w, (int)h, *view, tp, commit != 0, in.rgba, d_len))) return r;
+    HIP_TRY(hipMemcpyAsync(out_rgba, in.rgba, n * 16, hipMemcpyDeviceToHost, t->stream));
     if (out_len) HIP_TRY(hipMemcpyAsync(out_len, d_len, n * 4, hipMemcpyDeviceToHost, t->stream));
     HIP_TRY(hipStreamSynchronize(t->stream));
     return 0;

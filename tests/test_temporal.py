@@ -12,7 +12,7 @@ import pytest
 from gpuart_amd import synth_scenes as S
 from tests import denoise_ref as R
 from tests import temporal_ref as T
-from tests.util import scene
+from tests.util import assert_same_bits, exported, same_bits, scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR_ARG = -1
@@ -28,25 +28,6 @@ CPU_RATIO = {"box": 0.8615, "scene_p": 0.6607}
 RATIO_BOUND = {"box": 0.8961, "scene_p": 0.7455}
 
 
-def _exported(path):
-    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
-    return sorted(line.split()[-1] for line in out.splitlines() if line.strip())
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and (np.ascontiguousarray(a).view(np.uint32) == np.ascontiguousarray(b).view(np.uint32)).all()
-
-
-def assert_same_bits(got, exp, what):
-    got, exp = np.ascontiguousarray(got, np.float32), np.ascontiguousarray(exp, np.float32)
-    assert got.shape == exp.shape, (what, got.shape, exp.shape)
-    if got.ndim == 2:
-        got, exp = got[..., None], exp[..., None]
-    bad = (got.view(np.uint32) != exp.view(np.uint32)).reshape(-1, got.shape[-1]).any(1)
-    assert not bad.any(), "%s: %d of %d pixels differ; first %d: got %s expected %s" % (
-        what, int(bad.sum()), bad.size, int(np.argmax(bad)), got.reshape(-1, got.shape[-1])[bad][0], exp.reshape(-1, exp.shape[-1])[bad][0])
-
-
 def cam_dict(pos):
     cam = dict(S.DEFAULT_CAMERA, pos=tuple(pos))
     cam["dir"] = S.camera_dir(cam)
@@ -60,18 +41,18 @@ def test_temporal_library_exports_exactly_its_header(lib):
     names = sorted(set(re.findall(r"\b(gpuart_temporal_[a-z_0-9]+)\s*\(", hdr)))
     assert len(names) == 8, names
     path = os.path.join(ROOT, "gpuart_amd", lib, "libgpuart_temporal.so")
-    assert _exported(path) == names
+    assert exported(path) == names
     # images alone: it links neither the renderer's back end nor the spatial filter
     dyn = subprocess.run(["readelf", "-d", path], capture_output=True, text=True, check=True).stdout
     assert "libgpuart_hip.so" not in dyn and "libgpuart_denoise.so" not in dyn and "libamdhip64" in dyn, dyn
-    host = _exported(os.path.join(ROOT, "gpuart_amd", lib, "libgpuart.so"))
+    host = exported(os.path.join(ROOT, "gpuart_amd", lib, "libgpuart.so"))
     assert "gpuart_renderer_set_temporal_history" in host and "gpuart_renderer_read_preview" in host
     capi = open(os.path.join(ROOT, "gpuart_amd", "csrc", "host", "capi.h")).read()
     for n in ("gpuart_renderer_set_temporal_history", "gpuart_renderer_read_preview"):
         assert re.search(r"\b%s\s*\(" % n, capi)
     # the other two device libraries gained nothing
-    assert not [n for n in _exported(os.path.join(ROOT, "gpuart_amd", lib, "libgpuart_hip.so")) if "temporal" in n]
-    assert not [n for n in _exported(os.path.join(ROOT, "gpuart_amd", lib, "libgpuart_denoise.so")) if "temporal" in n]
+    assert not [n for n in exported(os.path.join(ROOT, "gpuart_amd", lib, "libgpuart_hip.so")) if "temporal" in n]
+    assert not [n for n in exported(os.path.join(ROOT, "gpuart_amd", lib, "libgpuart_denoise.so")) if "temporal" in n]
 
 
 def test_records_match_the_header(tmp_path):

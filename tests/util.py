@@ -1,5 +1,6 @@
 """Shared helpers for the parity tests: golden loading, scene lookup, bit-exact comparison."""
 import os
+import subprocess
 
 import numpy as np
 
@@ -48,6 +49,27 @@ def bit_mismatch(got, ref):
 def assert_bits(got, ref, what=""):
     n = bit_mismatch(got, ref)
     assert n == 0, "%s: %d of %d rows differ bitwise" % (what, n, np.asarray(ref).shape[0])
+
+
+def same_bits(a, b):
+    """Strictly bit for bit, unlike bit_mismatch: the image libraries' kernels against their restatements."""
+    return a.shape == b.shape and (np.ascontiguousarray(a).view(np.uint32) == np.ascontiguousarray(b).view(np.uint32)).all()
+
+
+def assert_same_bits(got, exp, what):
+    got, exp = np.ascontiguousarray(got, np.float32), np.ascontiguousarray(exp, np.float32)
+    assert got.shape == exp.shape, (what, got.shape, exp.shape)
+    if got.ndim == 2:
+        got, exp = got[..., None], exp[..., None]
+    bad = (got.view(np.uint32) != exp.view(np.uint32)).reshape(-1, got.shape[-1]).any(1)
+    assert not bad.any(), "%s: %d of %d pixels differ; first %d: got %s expected %s" % (
+        what, int(bad.sum()), bad.size, int(np.argmax(bad)), got.reshape(-1, got.shape[-1])[bad][0], exp.reshape(-1, exp.shape[-1])[bad][0])
+
+
+def exported(path):
+    """The names a shared library defines and exports, sorted."""
+    out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+    return sorted(line.split()[-1] for line in out.splitlines() if line.strip())
 
 
 def rmse_per_channel(got, ref):
