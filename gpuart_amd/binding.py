@@ -71,6 +71,24 @@ def denoise_params(params):
     return DenoiseParams(**dict(DENOISE_DEFAULTS, **params))
 
 
+class RefineParams(C.Structure):
+    """gpuart_refine_params (include/gpuart_refine.h)."""
+    _fields_ = [("iterations", C.c_uint32), ("lum_k", C.c_float), ("normal_pow2", C.c_uint32), ("depth_sigma", C.c_float)]
+
+
+REFINE_DEFAULTS = dict(iterations=5, lum_k=1.0, normal_pow2=5, depth_sigma=0.05)
+
+
+def refine_params(params):
+    """None (the library's defaults), a RefineParams, or a dict of fields that replace the defaults -> RefineParams or None."""
+    if params is None or isinstance(params, RefineParams):
+        return params
+    unknown = set(params) - set(REFINE_DEFAULTS)
+    if unknown:
+        raise ValueError("unknown refine parameters: %s" % sorted(unknown))
+    return RefineParams(**dict(REFINE_DEFAULTS, **params))
+
+
 class TemporalParams(C.Structure):
     """gpuart_temporal_params (include/gpuart_temporal.h)."""
     _fields_ = [("max_history", C.c_float), ("plane_tol", C.c_float), ("normal_min", C.c_float)]
@@ -184,6 +202,11 @@ def temporal_lib():
 def converge_lib():
     """libgpuart_converge.so; raises NativeLibraryMissing if it has not been built (no fallback)."""
     return _image_lib("converge")
+
+
+def refine_lib():
+    """libgpuart_refine.so; raises NativeLibraryMissing if it has not been built (no fallback)."""
+    return _image_lib("refine")
 
 
 def host_lib():
@@ -940,6 +963,17 @@ class Renderer:
             return None
         return out
 
+    def read_refined(self, lum_floor=CONVERGE_DEFAULT_FLOOR, params=None):
+        """Renderer::ReadRefined: the normalised accumulator filtered by the error map of render_until's last batch
+        (include/gpuart_refine.h), (th, tw, 4) float32; params as Refine.run. None where read_error_map gives None: before render_until's
+        second batch (and after anything that restarted the accumulation)."""
+        _, _, tw, th = self.tile
+        out = np.empty((th, tw, 4), np.float32)
+        p = refine_params(params)
+        if not self.L.gpuart_renderer_read_refined(self.h, _p(out), C.c_float(lum_floor), C.byref(p) if p is not None else None):
+            return None
+        return out
+
     def finish(self): return bool(self.L.gpuart_renderer_finish(self.h))
 
     def trace_rays(self, rays, occlusion=False, user_sphere=True, want_prims=False):
@@ -1082,6 +1116,43 @@ class Denoiser(_ImageHandle):
             return res
         self._chk(self.L.gpuart_denoise_run_host(self.h, _p(rgba), _p(hits), _p(prims), C.c_uint32(us_flags), C.c_uint32(w), C.c_uint32(h),
                                                  pp, _p(res)))
+        return res
+
+
+# ---- the variance-guided filter (include/gpuart_refine.h) -----------------------------------------------------------------
+class RefineError(RuntimeError):
+    """A gpuart_refine_* call returned an error; `code` is the library's (GPUART_HIP_ERR_*)."""
+    code = None
+
+
+class Refine(_ImageHandle):
+    """A gpuart_refine handle on one device."""
+    NAME, Error = "refine", RefineError
+
+    def run(self, rgba, hits, prims, error, lum_floor, us_flags=0, params=None, out=None):
+        """Filters radiance rgba (h, w, 4) float32 guided by a G-buffer (hits, prims, us_flags as Denoiser.run) and by error (h, w) float32,
+        the map Converge.measure / Renderer.read_error_map give for the same lum_floor; params = None (the defaults), a RefineParams or
+        a dict of fields that replace the defaults. torch tensors on this handle's device run in place through gpuart_refine_run
+        (torch's current stream is synchronised first, the handle before returning) and the result is `out` or a new tensor; NumPy
+        arrays run through gpuart_refine_run_host and the result is `out` or a new array."""
+        p = refine_params(params)
+        pp = C.byref(p) if p is not None else None
+        dev, rgba, hits, prims, res, h, w = _gbuffer_args(self.device, rgba, hits, prims, out)
+        if dev is not None:
+            import torch
+            if not type(error).__module__.startswith("torch") or error.dtype != torch.float32 or error.numel() != h * w or \
+                    not error.is_contiguous() or error.device != dev:
+                raise ValueError("error must be a contiguous (h, w) float32 tensor on %s" % dev)
+            torch.cuda.current_stream(dev).synchronize()
+            self._chk(self.L.gpuart_refine_run(self.h, _dp(rgba), _dp(hits), _dp(prims), C.c_uint32(us_flags), _dp(error), C.c_float(lum_floor),
+                                               C.c_uint32(w), C.c_uint32(h), pp, _dp(res)))
+            self.finish()
+            return res
+        error = np.ascontiguousarray(error, np.float32)
+        if error.size != h * w:
+            raise ValueError("error must hold h*w floats")
+        self._chk(self.L.gpuart_refine_run_host(self.h, _p(rgba), _p(hits), _p(prims), C.c_uint32(us_flags), _p(error), C.c_float(lum_floor),
+                                                C.c_uint32(w), C.c_uint32(h), pp, _p(res)))
         return res
 
 

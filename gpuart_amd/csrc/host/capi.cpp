@@ -278,6 +278,9 @@ int gpuart_renderer_render_until(gpuart_renderer *r, float threshold, float maxA
     return r->impl.RenderUntil(threshold, maxAboveShare, batchPaths, lumFloor, last);
 }
 int gpuart_renderer_read_error_map(gpuart_renderer *r, float *e, float lumFloor) { return r->impl.ReadErrorMap(e, lumFloor) ? 1 : 0; }
+int gpuart_renderer_read_refined(gpuart_renderer *r, float *rgba, float lumFloor, const gpuart_refine_params *p) {
+    return r->impl.ReadRefined(rgba, lumFloor, p) ? 1 : 0;
+}
 int gpuart_renderer_finish(gpuart_renderer *r) { return r->impl.Finish() ? 1 : 0; }
 int gpuart_renderer_save_checkpoint(gpuart_renderer *r, const char *path) { return r->impl.SaveCheckpoint(path) ? 1 : 0; }
 int gpuart_renderer_load_checkpoint(gpuart_renderer *r, const char *path) { return r->impl.LoadCheckpoint(path) ? 1 : 0; }

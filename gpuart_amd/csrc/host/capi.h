@@ -9,6 +9,7 @@
 #include "gpuart_converge.h"
 #include "gpuart_denoise.h"
 #include "gpuart_hip.h"
+#include "gpuart_refine.h"
 #include "gpuart_temporal.h"
 
 #ifdef __cplusplus
@@ -96,6 +97,9 @@ int gpuart_renderer_render_until(gpuart_renderer *r, float threshold, float maxA
                                  gpuart_converge_summary *last);
 /* Renderer::ReadErrorMap: the error per tile pixel as of the last batch; 1 on success, 0 before the second batch or on error. */
 int gpuart_renderer_read_error_map(gpuart_renderer *r, float *e, float lumFloor);
+/* Renderer::ReadRefined: the normalised accumulator filtered by the error map of the last batch (include/gpuart_refine.h); p = NULL:
+ * the defaults. 1 on success, 0 before the second batch or on error. */
+int gpuart_renderer_read_refined(gpuart_renderer *r, float *rgba, float lumFloor, const gpuart_refine_params *p);
 int gpuart_renderer_finish(gpuart_renderer *r);
 int gpuart_renderer_save_checkpoint(gpuart_renderer *r, const char *path);
 int gpuart_renderer_load_checkpoint(gpuart_renderer *r, const char *path);

@@ -25,13 +25,15 @@ static void usage() {
                  "                  [--spp N] [--per-pass K] [--max-segments M] [--seed S] [--tile x0,y0,w,h]\n"
                  "                  [--camera px,py,pz] [--sun az,alt[,off]] [--user-sphere x,y,z,r,em[,specular[,fuzzy]]]\n"
                  "                  [--device D] [--gpus N] [--resume ck] [--checkpoint ck] [--pfm out.pfm] [--ppm out.ppm] [--nearest-first]\n"
-                 "                  [--denoise] [--until T [--until-share S] [--until-floor F] [--until-batch N] [--error-pfm out.pfm]]\n"
+                 "                  [--denoise] [--until T [--until-share S] [--until-floor F] [--until-batch N] [--error-pfm out.pfm] [--refine]]\n"
                  "  --until T: render until the relative standard error of every pixel's luminance is at most T (Renderer::RenderUntil; path\n"
                  "             tracing on one GPU), --spp being the cap; --until-share S: the share of pixels that may stay above T (default 0);\n"
                  "             --until-floor F: luminance below which the error is taken relative to F (default 1/256, one step of the 8-bit\n"
                  "             output); --until-batch N: paths per pixel between two measurements; --error-pfm: the error per pixel (PFM, grey).\n"
                  "             With --resume the checkpoint's paths are the first batch; one already at --spp renders nothing and is not measured\n"
                  "             (its line says 0 batches, converged false)\n"
+                 "  --refine: with --until, write the frame filtered by its own error estimate (Renderer::ReadRefined, with --until-floor as its\n"
+                 "             floor) instead of the raw one; not together with --denoise. A run that never reached two batches writes the raw frame\n"
                  "  --denoise: write the denoised preview of the frame (Renderer::ReadDenoised; path tracing on one GPU)\n"
                  "  --nearest-first: opt in to the nearer-child-first BVH walk (~10 % faster; soak-verified, not proven to be the reference's image)\n"
                  "  --gpus N: path tracing of ONE frame on devices D..D+N-1 (8-row bands dealt round-robin, gathered over RCCL)\n";
@@ -52,7 +54,7 @@ int main(int argc, char **argv) {
     std::string scene = "box", mode = "pt", pfm, ppm, resume, checkpoint;
     unsigned W = 640, H = 480, spp = 16, perPass = 1, maxSeg = 5, device = 0, gpus = 1;
     long seed = -1;
-    bool nearestFirst = false, denoise = false;
+    bool nearestFirst = false, denoise = false, refine = false;
     std::string errorPfm;
     float until = -1, untilShare = 0, untilFloor = 1.0f / 256;
     unsigned untilBatch = GPUART_CONVERGE_DEFAULT_BATCH;
@@ -85,6 +87,7 @@ int main(int argc, char **argv) {
         else if (a == "--checkpoint") checkpoint = need("--checkpoint");
         else if (a == "--nearest-first") nearestFirst = true;
         else if (a == "--denoise") denoise = true;
+        else if (a == "--refine") refine = true;
         else if (a == "--until") { until = strtof(need("--until"), nullptr); haveUntil = true; }
         else if (a == "--until-share") untilShare = strtof(need("--until-share"), nullptr);
         else if (a == "--until-floor") untilFloor = strtof(need("--until-floor"), nullptr);
@@ -96,6 +99,14 @@ int main(int argc, char **argv) {
     if (denoise && (mode != "pt" || gpus != 1)) { usage(); return 2; }
     if (haveUntil && gpus > 1) {
         std::cerr << "gpuart_cli: --until needs --gpus 1: the ranks of a sharded frame would stop at different path counts\n";
+        return 2;
+    }
+    if (refine && !haveUntil) {
+        std::cerr << "gpuart_cli: --refine needs --until: it filters with the error estimate of that render\n";
+        return 2;
+    }
+    if (refine && denoise) {
+        std::cerr << "gpuart_cli: --refine and --denoise both replace the frame that is written: give one of them\n";
         return 2;
     }
     if ((haveUntil && mode != "pt") || (!haveUntil && !errorPfm.empty())) { usage(); return 2; }
@@ -142,7 +153,7 @@ int main(int argc, char **argv) {
 
     std::vector<float> img((size_t)tw * th * 4);
     const auto t0 = std::chrono::high_resolution_clock::now();
-    unsigned done = 0, passes = 0;
+    unsigned done = 0, passes = 0, untilBatches = 0;
     if (mode == "direct") {
         r.RenderDirectLighting();
         ok = r.ReadDirectLighting(img.data());
@@ -161,6 +172,7 @@ int main(int argc, char **argv) {
             const int rc = r.RenderUntil(until, untilShare, untilBatch, untilFloor, &cs);
             if (rc < 0) return 1;
             done = r.GetNumPathsRendered();
+            untilBatches = cs.batches;
             passes = (done - start + std::max(1u, perPass) - 1) / std::max(1u, perPass);
             printf("{\"until\": %.9g, \"paths_rendered\": %u, \"batches\": %u, \"above\": %llu, \"pixels\": %llu, \"max_error\": %.9g, "
                    "\"converged\": %s}\n", until, done, cs.batches, (unsigned long long)cs.above, (unsigned long long)cs.pixels, cs.max_error,
@@ -200,7 +212,11 @@ int main(int argc, char **argv) {
                 _exit(1);
             }
         } else
-            ok = denoise ? r.ReadDenoised(img.data()) : r.ReadRadiance(img.data(), true);
+            if (refine && untilBatches >= 2) ok = r.ReadRefined(img.data(), untilFloor);
+            else {
+                if (refine) std::cerr << "gpuart_cli: --refine: the estimate never reached two batches; writing the raw frame\n";
+                ok = denoise ? r.ReadDenoised(img.data()) : r.ReadRadiance(img.data(), true);
+            }
     }
     const double secs = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
     if (!ok) return 1;

@@ -75,6 +75,8 @@ Renderer::Renderer(unsigned viewportWidth, unsigned viewportHeight, const Camera
 }
 
 Renderer::~Renderer() {
+    if (Refine) gpuart_refine_destroy(Refine);
+    RefineMem.Release();
     if (Converge) gpuart_converge_destroy(Converge);
     ConvergeMem.Release();
     if (Temporal) gpuart_temporal_destroy(Temporal);
@@ -371,7 +373,8 @@ bool Renderer::ReadRadiance(float *rgba, bool normalized) {
 }
 
 namespace {
-const auto DN = gpuart_denoise_last_error, TP = gpuart_temporal_last_error, CV = gpuart_converge_last_error;  // for Check
+const auto DN = gpuart_denoise_last_error, TP = gpuart_temporal_last_error, CV = gpuart_converge_last_error,
+           RF = gpuart_refine_last_error;  // for Check
 bool finite(float x) { return x - x == 0.0f; }
 bool checkHip(hipError_t e, const char *what) {
     if (e == hipSuccess) return true;
@@ -555,6 +558,22 @@ bool Renderer::ReadErrorMap(float *e, float lumFloor) {
     if (!IsOK || !e || !Converge || ConvergeBatches < 2) return false;
     gpuart_converge_summary s;
     return Check(gpuart_converge_measure_host(Converge, 0.0f, lumFloor, e, &s), "reading the error map", CV);
+}
+
+bool Renderer::ReadRefined(float *rgba, float lumFloor, const gpuart_refine_params *p) {
+    if (!IsOK || !rgba || !Converge || ConvergeBatches < 2) return false;
+    if (!Refine && !Check(gpuart_refine_create(Device, &Refine), "creating the variance-guided filter", RF)) return false;
+    if (!StageView()) return false;
+    const size_t n = (size_t)Tile.w * Tile.h;
+    if (!RefineMem.Fit(n, 4, "allocating the filter's error map")) return false;
+    const ViewBuffers b(DenoiseMem.mem, n);
+    // a measure changes nothing of the estimate; it waits for the map itself
+    gpuart_converge_summary s;
+    if (!Check(gpuart_converge_measure(Converge, 0.0f, lumFloor, (float *)RefineMem.mem, &s), "measuring the error map", CV)) return false;
+    if (!Check(gpuart_refine_run(Refine, b.radiance, b.hits, b.prims, UserSphere.flags, (const float *)RefineMem.mem, lumFloor, Tile.w, Tile.h, p,
+                                 b.filtered), "filtering", RF)) return false;
+    if (!Check(gpuart_refine_finish(Refine), "filtering", RF)) return false;
+    return checkHip(hipMemcpy(rgba, b.filtered, n * 16, hipMemcpyDeviceToHost), "reading the refined frame");
 }
 
 // ---- checkpoint / resume ---------------------------------------------------------------------------------------------

@@ -8,7 +8,7 @@
 // MAX_PATH_SEGMENTS / the RNG seed / the viewport fixed at compile time):
 //   ReadDirectLighting, ReadRadiance, Finish, SetMaxPathSegments, SetMinWeight, SetSeed,
 //   SetTile, GetBackend, ComputeScreenBasis, GetNumPathsRendered, ReadDenoised, SetTemporalHistory, ReadPreview, RenderUntil,
-//   ReadErrorMap.
+//   ReadErrorMap, ReadRefined.
 #ifndef GPUART_RENDERER_H
 #define GPUART_RENDERER_H
 
@@ -21,6 +21,7 @@
 #include "gpuart_converge.h"
 #include "gpuart_denoise.h"
 #include "gpuart_hip.h"
+#include "gpuart_refine.h"
 #include "gpuart_temporal.h"
 #include "math_types.h"
 
@@ -120,6 +121,14 @@ public:
     int RenderUntil(float threshold, float maxAboveShare, unsigned batchPaths, float lumFloor, gpuart_converge_summary *last = nullptr);
     /// e per tile pixel (Tile.w*Tile.h floats, row 0 = bottom row) as of RenderUntil's last batch; false before its second batch.
     bool ReadErrorMap(float *e, float lumFloor);
+    /// The frame RenderUntil leaves, filtered by its own error estimate (include/gpuart_refine.h): the radiance divided by the paths
+    /// rendered and the G-buffer of the tile, as ReadDenoised stages them, and the error map of RenderUntil's last batch for lumFloor
+    /// (measured into a device buffer of the Renderer's own). RGBA32F, tile-sized, row 0 = bottom row; p = nullptr: the defaults. False
+    /// before RenderUntil's second batch, exactly where ReadErrorMap is. Paths rendered by plain passes after the last batch are in the
+    /// filtered image but not in the map: the map is then slightly too large and the filter slightly too strong. The accumulator, the
+    /// passes that follow, the counters, the estimate and RenderUntil's later summaries, the temporal history and the cached G-buffer
+    /// are not touched. Synchronises.
+    bool ReadRefined(float *rgba, float lumFloor, const gpuart_refine_params *p = nullptr);
     bool Finish();
     void SetMaxPathSegments(unsigned n) { MaxPathSegments = n; DropTemporalHistory(); ResetPathTracing(); }
     void SetMinWeight(float w) { MinWeight = w; DropTemporalHistory(); ResetPathTracing(); }
@@ -193,6 +202,8 @@ private:
     gpuart_converge *Converge = nullptr;  ///< made by the first RenderUntil
     PixelBuffer ConvergeMem;              ///< the raw accumulator of RenderUntil's last batch, 16 B per tile pixel
     unsigned ConvergeBatches = 0, ConvergeTotal = 0;  ///< what Converge has seen since its last reset
+    gpuart_refine *Refine = nullptr;      ///< made by the first ReadRefined
+    PixelBuffer RefineMem;                ///< ReadRefined's error map, 4 B per tile pixel
     ScreenBasis CurrentBasis;             ///< what SetCamera gave the back end
     double LastSetPrimitivesMs[4] = {0, 0, 0, 0};
     gpuart_hip_ctx *Backend = nullptr;
