@@ -53,9 +53,23 @@ RAY_HIT = np.dtype([("pos", np.float32), ("p", np.float32, 3), ("n", np.float32,
 RAYS_OCCLUSION = 1  # GPUART_HIP_RAYS_OCCLUSION
 
 
+def _params(cls, defaults, noun, params):
+    """None (the library's defaults), a `cls`, or a dict of fields that replace `defaults` -> `cls` or None."""
+    if params is None or isinstance(params, cls):
+        return params
+    unknown = set(params) - set(defaults)
+    if unknown:
+        raise ValueError("unknown %s parameters: %s" % (noun, sorted(unknown)))
+    return cls(**dict(defaults, **params))
+
+
+# the two filters' parameter records are one layout under two names (csrc/image/atrous.h checks both)
+_FILTER_FIELDS = [("iterations", C.c_uint32), ("lum_k", C.c_float), ("normal_pow2", C.c_uint32), ("depth_sigma", C.c_float)]
+
+
 class DenoiseParams(C.Structure):
     """gpuart_denoise_params (include/gpuart_denoise.h)."""
-    _fields_ = [("iterations", C.c_uint32), ("lum_k", C.c_float), ("normal_pow2", C.c_uint32), ("depth_sigma", C.c_float)]
+    _fields_ = _FILTER_FIELDS
 
 
 DENOISE_DEFAULTS = dict(iterations=5, lum_k=4.0, normal_pow2=5, depth_sigma=0.05)
@@ -63,17 +77,12 @@ DENOISE_DEFAULTS = dict(iterations=5, lum_k=4.0, normal_pow2=5, depth_sigma=0.05
 
 def denoise_params(params):
     """None (the library's defaults), a DenoiseParams, or a dict of fields that replace the defaults -> DenoiseParams or None."""
-    if params is None or isinstance(params, DenoiseParams):
-        return params
-    unknown = set(params) - set(DENOISE_DEFAULTS)
-    if unknown:
-        raise ValueError("unknown denoiser parameters: %s" % sorted(unknown))
-    return DenoiseParams(**dict(DENOISE_DEFAULTS, **params))
+    return _params(DenoiseParams, DENOISE_DEFAULTS, "denoiser", params)
 
 
 class RefineParams(C.Structure):
     """gpuart_refine_params (include/gpuart_refine.h)."""
-    _fields_ = [("iterations", C.c_uint32), ("lum_k", C.c_float), ("normal_pow2", C.c_uint32), ("depth_sigma", C.c_float)]
+    _fields_ = _FILTER_FIELDS
 
 
 REFINE_DEFAULTS = dict(iterations=5, lum_k=1.0, normal_pow2=5, depth_sigma=0.05)
@@ -81,12 +90,7 @@ REFINE_DEFAULTS = dict(iterations=5, lum_k=1.0, normal_pow2=5, depth_sigma=0.05)
 
 def refine_params(params):
     """None (the library's defaults), a RefineParams, or a dict of fields that replace the defaults -> RefineParams or None."""
-    if params is None or isinstance(params, RefineParams):
-        return params
-    unknown = set(params) - set(REFINE_DEFAULTS)
-    if unknown:
-        raise ValueError("unknown refine parameters: %s" % sorted(unknown))
-    return RefineParams(**dict(REFINE_DEFAULTS, **params))
+    return _params(RefineParams, REFINE_DEFAULTS, "refine", params)
 
 
 class TemporalParams(C.Structure):
@@ -99,12 +103,7 @@ TEMPORAL_DEFAULTS = dict(max_history=4.0, plane_tol=0.01, normal_min=0.8)
 
 def temporal_params(params):
     """None (the library's defaults), a TemporalParams, or a dict of fields that replace the defaults -> TemporalParams or None."""
-    if params is None or isinstance(params, TemporalParams):
-        return params
-    unknown = set(params) - set(TEMPORAL_DEFAULTS)
-    if unknown:
-        raise ValueError("unknown temporal parameters: %s" % sorted(unknown))
-    return TemporalParams(**dict(TEMPORAL_DEFAULTS, **params))
+    return _params(TemporalParams, TEMPORAL_DEFAULTS, "temporal", params)
 
 
 class ConvergeSummary(C.Structure):
@@ -1053,7 +1052,7 @@ class _ImageHandle:
 
 
 def _gbuffer_args(device, rgba, hits, prims, out):
-    """What Denoiser.run and Temporal.accumulate check of a tile's radiance, G-buffer and result: torch tensors on cuda:<device>, or
+    """What the filters' run and Temporal.accumulate check of a tile's radiance, G-buffer and result: torch tensors on cuda:<device>, or
     NumPy arrays (made contiguous). -> (dev, rgba, hits, prims, res, h, w): dev is the tensors' torch device, None for NumPy arrays;
     res is `out`, or a new image like rgba."""
     if type(rgba).__module__.startswith("torch"):
@@ -1088,13 +1087,32 @@ def _dp(t):
     return C.c_void_p(t.data_ptr())
 
 
-# ---- the denoiser (include/gpuart_denoise.h) ------------------------------------------------------------------------------
+# ---- the two filters: the denoiser (include/gpuart_denoise.h) and the variance-guided one (include/gpuart_refine.h) ---------
+class _Filter(_ImageHandle):
+    """What the two filters' run methods share: gpuart_<NAME>_run for torch tensors, gpuart_<NAME>_run_host for NumPy arrays."""
+
+    def _run(self, p, rgba, hits, prims, us_flags, out, more=lambda dev, h, w, ptr: []):
+        """`more` checks the arguments a library takes between us_flags and the size and returns them, pointers made by ptr."""
+        pp = C.byref(p) if p is not None else None
+        dev, rgba, hits, prims, res, h, w = _gbuffer_args(self.device, rgba, hits, prims, out)
+        ptr = _p if dev is None else _dp
+        args = [self.h, ptr(rgba), ptr(hits), ptr(prims), C.c_uint32(us_flags)] + more(dev, h, w, ptr) + [C.c_uint32(w), C.c_uint32(h), pp, ptr(res)]
+        if dev is None:
+            self._chk(self._fn("run_host")(*args))
+            return res
+        import torch
+        torch.cuda.current_stream(dev).synchronize()
+        self._chk(self._fn("run")(*args))
+        self.finish()
+        return res
+
+
 class DenoiseError(RuntimeError):
     """A gpuart_denoise_* call returned an error; `code` is the library's (GPUART_HIP_ERR_*)."""
     code = None
 
 
-class Denoiser(_ImageHandle):
+class Denoiser(_Filter):
     """A gpuart_denoise handle on one device."""
     NAME, Error = "denoise", DenoiseError
 
@@ -1104,28 +1122,15 @@ class Denoiser(_ImageHandle):
         defaults), a DenoiseParams or a dict of fields that replace the defaults. torch tensors on this handle's device run in place
         through gpuart_denoise_run (torch's current stream is synchronised first, the handle before returning) and the result is `out`
         or a new tensor; NumPy arrays run through gpuart_denoise_run_host and the result is `out` or a new array."""
-        p = denoise_params(params)
-        pp = C.byref(p) if p is not None else None
-        dev, rgba, hits, prims, res, h, w = _gbuffer_args(self.device, rgba, hits, prims, out)
-        if dev is not None:
-            import torch
-            torch.cuda.current_stream(dev).synchronize()
-            self._chk(self.L.gpuart_denoise_run(self.h, _dp(rgba), _dp(hits), _dp(prims), C.c_uint32(us_flags), C.c_uint32(w), C.c_uint32(h),
-                                                pp, _dp(res)))
-            self.finish()
-            return res
-        self._chk(self.L.gpuart_denoise_run_host(self.h, _p(rgba), _p(hits), _p(prims), C.c_uint32(us_flags), C.c_uint32(w), C.c_uint32(h),
-                                                 pp, _p(res)))
-        return res
+        return self._run(denoise_params(params), rgba, hits, prims, us_flags, out)
 
 
-# ---- the variance-guided filter (include/gpuart_refine.h) -----------------------------------------------------------------
 class RefineError(RuntimeError):
     """A gpuart_refine_* call returned an error; `code` is the library's (GPUART_HIP_ERR_*)."""
     code = None
 
 
-class Refine(_ImageHandle):
+class Refine(_Filter):
     """A gpuart_refine handle on one device."""
     NAME, Error = "refine", RefineError
 
@@ -1135,25 +1140,20 @@ class Refine(_ImageHandle):
         a dict of fields that replace the defaults. torch tensors on this handle's device run in place through gpuart_refine_run
         (torch's current stream is synchronised first, the handle before returning) and the result is `out` or a new tensor; NumPy
         arrays run through gpuart_refine_run_host and the result is `out` or a new array."""
-        p = refine_params(params)
-        pp = C.byref(p) if p is not None else None
-        dev, rgba, hits, prims, res, h, w = _gbuffer_args(self.device, rgba, hits, prims, out)
-        if dev is not None:
-            import torch
-            if not type(error).__module__.startswith("torch") or error.dtype != torch.float32 or error.numel() != h * w or \
-                    not error.is_contiguous() or error.device != dev:
-                raise ValueError("error must be a contiguous (h, w) float32 tensor on %s" % dev)
-            torch.cuda.current_stream(dev).synchronize()
-            self._chk(self.L.gpuart_refine_run(self.h, _dp(rgba), _dp(hits), _dp(prims), C.c_uint32(us_flags), _dp(error), C.c_float(lum_floor),
-                                               C.c_uint32(w), C.c_uint32(h), pp, _dp(res)))
-            self.finish()
-            return res
-        error = np.ascontiguousarray(error, np.float32)
-        if error.size != h * w:
-            raise ValueError("error must hold h*w floats")
-        self._chk(self.L.gpuart_refine_run_host(self.h, _p(rgba), _p(hits), _p(prims), C.c_uint32(us_flags), _p(error), C.c_float(lum_floor),
-                                                C.c_uint32(w), C.c_uint32(h), pp, _p(res)))
-        return res
+        def more(dev, h, w, ptr):
+            e = error
+            if dev is None:
+                e = np.ascontiguousarray(e, np.float32)
+                if e.size != h * w:
+                    raise ValueError("error must hold h*w floats")
+            else:
+                import torch
+                if not type(e).__module__.startswith("torch") or e.dtype != torch.float32 or e.numel() != h * w or not e.is_contiguous() or \
+                        e.device != dev:
+                    raise ValueError("error must be a contiguous (h, w) float32 tensor on %s" % dev)
+            return [ptr(e), C.c_float(lum_floor)]
+
+        return self._run(refine_params(params), rgba, hits, prims, us_flags, out, more)
 
 
 # ---- temporal accumulation (include/gpuart_temporal.h) --------------------------------------------------------------------

@@ -4,6 +4,7 @@
 #include <cmath>
 
 #include "../image/image_lib.h"
+#include "../image/atrous.h"
 #include "gpuart_denoise.h"
 
 namespace {
@@ -11,16 +12,6 @@ namespace {
 const char LIB[] = "denoise";
 
 #define DN_FN __device__ __forceinline__
-
-/// max(a, b) as the header states it: a > b ? a : b
-DN_FN float gt_or(float a, float b) { return a > b ? a : b; }
-
-/// the reference's PRIMITIVE_COLOR (shaders/path_tracing.glsl:123-126); the user sphere has type 0
-DN_FN float3 albedo(int type) {
-    if (type == 0) return make_float3(0.65f, 0.4f, 0.35f);
-    if (type == 1) return make_float3(0.1f, 0.2f, 0.1f);
-    return make_float3(0.3f, 0.3f, 0.3f);
-}
 
 /// Pixel i's class: its primitive type when it is a surface pixel (image_lib.h), -1 otherwise.
 DN_FN int surface_type(const float4 *hits, const int32_t *prims, uint32_t us_flags, size_t i) {
@@ -86,12 +77,6 @@ __global__ void __launch_bounds__(PT * PT) k_dn_prepare(const float4 *rgba, cons
 
 // ---- steps 3 and 4: one à-trous level; the last one remodulates ---------------------------------------------------------------
 // The row block of image_lib.h: every tap of a wave reads 64 consecutive records (2 x 1 KiB).
-struct Level {
-    float lum_k, depth_sigma, step;
-    int s;
-    uint32_t normal_pow2;
-};
-
 template <bool LAST>
 __global__ void __launch_bounds__(ROW_X * ROW_Y) k_dn_atrous(const float4 *st_in, const float4 *guide, float4 *st_out, int w, int h, Level lv,
                                                              const float4 *rgba, const float4 *hits, float4 *out) {
@@ -103,45 +88,8 @@ __global__ void __launch_bounds__(ROW_X * ROW_Y) k_dn_atrous(const float4 *st_in
         if (LAST) out[i] = rgba[i];
         return;
     }
-    const float H[5] = {1.0f / 16, 1.0f / 4, 3.0f / 8, 1.0f / 4, 1.0f / 16};
     const float4 xp = st_in[i];
-    const float Lp = lum(xp.x, xp.y, xp.z);
-    const float sd = sqrtf(xp.w) * lv.lum_k + 1e-4f;
-    const float zs = (lv.depth_sigma * gt_or(gp.w, 1e-6f)) * lv.step;
-    float nr = 0.0f, ng = 0.0f, nb = 0.0f, den = 0.0f, nv = 0.0f;
-    for (int dy = -2; dy <= 2; dy++) {
-        const int qy = y + lv.s * dy;
-        if (qy < 0 || qy >= h) continue;
-        for (int dx = -2; dx <= 2; dx++) {
-            const int qx = x + lv.s * dx;
-            if (qx < 0 || qx >= w) continue;
-            const size_t q = (size_t)qy * w + qx;
-            const float4 gq = guide[q];
-            if (!(gq.w == gq.w)) continue;
-            const float4 xq = st_in[q];
-            const float hk = H[dy + 2] * H[dx + 2];
-            const float e = (lum(xq.x, xq.y, xq.z) - Lp) / sd;
-            const float wl = 1.0f / (1.0f + e * e);
-            float wn = gt_or((gp.x * gq.x + gp.y * gq.y) + gp.z * gq.z, 0.0f);
-            for (uint32_t k = 0; k < lv.normal_pow2; k++) wn = wn * wn;
-            const float dz = fabsf(gq.w - gp.w) / zs;
-            const float wz = 1.0f / (1.0f + dz * dz);
-            const float wt = ((hk * wl) * wn) * wz;
-            nr += wt * xq.x;
-            ng += wt * xq.y;
-            nb += wt * xq.z;
-            den += wt;
-            nv += (wt * wt) * xq.w;
-        }
-    }
-    float4 xo = xp;
-    if (den > 0.0f) xo = make_float4(nr / den, ng / den, nb / den, nv / (den * den));
-    if (LAST) {
-        const float3 a = albedo(__float_as_int(hits[2 * i + 1].w) & 3);
-        out[i] = make_float4(xo.x * a.x, xo.y * a.y, xo.z * a.z, rgba[i].w);
-    } else {
-        st_out[i] = xo;
-    }
+    atrous_level<LAST>(x, y, i, gp, xp, xp.w, st_in, guide, st_out, w, h, lv, rgba, hits, out);
 }
 
 }  // namespace
@@ -152,16 +100,6 @@ struct gpuart_denoise : ImageHandle {
 
 namespace {
 
-int check_params(const gpuart_denoise_params &p) {
-    if (p.iterations > GPUART_DENOISE_MAX_ITERATIONS)
-        return fail(GPUART_HIP_ERR_ARG, "denoise: iterations = " + std::to_string(p.iterations) + " exceeds " +
-                                            std::to_string(GPUART_DENOISE_MAX_ITERATIONS));
-    if (!std::isfinite(p.lum_k) || !(p.lum_k >= 0)) return fail(GPUART_HIP_ERR_ARG, "denoise: lum_k must be finite and >= 0");
-    if (!std::isfinite(p.depth_sigma) || !(p.depth_sigma > 0)) return fail(GPUART_HIP_ERR_ARG, "denoise: depth_sigma must be finite and > 0");
-    if (p.normal_pow2 > 16) return fail(GPUART_HIP_ERR_ARG, "denoise: normal_pow2 exceeds 16");
-    return 0;
-}
-
 /// The checks both entry points make; `align` is what rgba, hits and out must be aligned to.
 int check_run(gpuart_denoise *d, const void *rgba, const void *hits, const void *prims, uint32_t w, uint32_t h,
               const gpuart_denoise_params *p, const void *out, size_t align) {
@@ -170,7 +108,7 @@ int check_run(gpuart_denoise *d, const void *rgba, const void *hits, const void 
     if (misaligned({rgba, hits, out}, align) || misaligned({prims}, 4))
         return fail(GPUART_HIP_ERR_ARG, "denoise: misaligned pointer (rgba, hits and out need " + std::to_string(align) + " bytes, prims 4)");
     if (int r = check_size(LIB, w, h)) return r;
-    return p ? check_params(*p) : 0;
+    return p ? check_params(LIB, *p, GPUART_DENOISE_MAX_ITERATIONS) : 0;
 }
 
 /// The filter on device memory, on the handle's stream; the states and the guide take the first 48 bytes per pixel of the scratch.
@@ -187,12 +125,7 @@ int launch(gpuart_denoise *d, const float4 *rgba, const float4 *hits, const int3
     HIP_TRY(hipGetLastError());
     const dim3 grid = row_grid(w, h), block = row_block();
     for (uint32_t it = 0; it < p.iterations; it++) {
-        Level lv;
-        lv.lum_k = p.lum_k;
-        lv.depth_sigma = p.depth_sigma;
-        lv.s = 1 << it;
-        lv.step = (float)lv.s;
-        lv.normal_pow2 = p.normal_pow2;
+        const Level lv = make_level(p, it);
         if (it + 1 == p.iterations)
             k_dn_atrous<true><<<grid, block, 0, d->stream>>>(st[it & 1], guide, nullptr, w, h, lv, rgba, hits, out);
         else
@@ -232,9 +165,7 @@ int gpuart_denoise_run(gpuart_denoise *d, const float *rgba, const gpuart_ray_hi
                        uint32_t w, uint32_t h, const gpuart_denoise_params *p, float *out) {
     int r = check_run(d, rgba, hits, prims, w, h, p, out, 16);
     if (r) return r;
-    gpuart_denoise_params dp;
-    if (p) dp = *p;
-    else gpuart_denoise_defaults(&dp);
+    const gpuart_denoise_params dp = params_or(p, gpuart_denoise_defaults);
     HIP_TRY(hipSetDevice(d->device));
     if ((r = ensure(d->stream, d->scratch, (size_t)w * h * 48))) return r;
     return launch(d, (const float4 *)rgba, (const float4 *)hits, prims, userSphereFlags, (int)w, (int)h, dp, (float4 *)out);
@@ -244,9 +175,7 @@ int gpuart_denoise_run_host(gpuart_denoise *d, const float *rgba, const gpuart_r
                             uint32_t userSphereFlags, uint32_t w, uint32_t h, const gpuart_denoise_params *p, float *out) {
     int r = check_run(d, rgba, hits, prims, w, h, p, out, 4);
     if (r) return r;
-    gpuart_denoise_params dp;
-    if (p) dp = *p;
-    else gpuart_denoise_defaults(&dp);
+    const gpuart_denoise_params dp = params_or(p, gpuart_denoise_defaults);
     HIP_TRY(hipSetDevice(d->device));
     const size_t n = (size_t)w * h;
     // the filter's 48 bytes per pixel, then the staged inputs; the staged radiance is also the output

@@ -4,6 +4,7 @@
 #include <cmath>
 
 #include "../image/image_lib.h"
+#include "../image/atrous.h"
 #include "gpuart_refine.h"
 
 namespace {
@@ -11,16 +12,6 @@ namespace {
 const char LIB[] = "refine";
 
 #define RF_FN __device__ __forceinline__
-
-/// max(a, b) as the header states it: a > b ? a : b
-RF_FN float gt_or(float a, float b) { return a > b ? a : b; }
-
-/// the reference's PRIMITIVE_COLOR (shaders/path_tracing.glsl:123-126); the user sphere has type 0
-RF_FN float3 albedo(int type) {
-    if (type == 0) return make_float3(0.65f, 0.4f, 0.35f);
-    if (type == 1) return make_float3(0.1f, 0.2f, 0.1f);
-    return make_float3(0.3f, 0.3f, 0.3f);
-}
 
 /// neither NaN nor +-inf, whatever the sign: the exponent is not all ones
 RF_FN bool finite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
@@ -55,12 +46,6 @@ __global__ void __launch_bounds__(ROW_X * ROW_Y) k_rf_prepare(const float4 *rgba
 // prefilter come from an LDS tile of the block's variances and a one-pixel apron, 66 x 6, filled once per block: the block's own
 // pixels from the registers that hold their state anyway, the 140 apron pixels by the first 140 threads (4 bytes of the guide and 4 of
 // the state each).
-struct Level {
-    float lum_k, depth_sigma, step;
-    int s;
-    uint32_t normal_pow2;
-};
-
 constexpr int VT_X = ROW_X + 2, VT_Y = ROW_Y + 2, APRON = 2 * VT_X + 2 * ROW_Y;
 
 template <bool LAST>
@@ -117,46 +102,8 @@ __global__ void __launch_bounds__(ROW_X * ROW_Y) k_rf_level(const float4 *st_in,
             gd += g;
         }
     const float gv = gn / gd;
-    // b. the taps
-    const float H[5] = {1.0f / 16, 1.0f / 4, 3.0f / 8, 1.0f / 4, 1.0f / 16};
-    const float Lp = lum(xp.x, xp.y, xp.z);
-    const float sd = sqrtf(gv) * lv.lum_k + 1e-4f;
-    const float zs = (lv.depth_sigma * gt_or(gp.w, 1e-6f)) * lv.step;
-    float nr = 0.0f, ng = 0.0f, nb = 0.0f, den = 0.0f, nv = 0.0f;
-    for (int dy = -2; dy <= 2; dy++) {
-        const int qy = y + lv.s * dy;
-        if (qy < 0 || qy >= h) continue;
-        for (int dx = -2; dx <= 2; dx++) {
-            const int qx = x + lv.s * dx;
-            if (qx < 0 || qx >= w) continue;
-            const size_t q = (size_t)qy * w + qx;
-            const float4 gq = guide[q];
-            if (!(gq.w == gq.w)) continue;
-            const float4 xq = st_in[q];
-            const float hk = H[dy + 2] * H[dx + 2];
-            const float e = (lum(xq.x, xq.y, xq.z) - Lp) / sd;
-            const float wl = 1.0f / (1.0f + e * e);
-            float wn = gt_or((gp.x * gq.x + gp.y * gq.y) + gp.z * gq.z, 0.0f);
-            for (uint32_t n = 0; n < lv.normal_pow2; n++) wn = wn * wn;
-            const float dz = fabsf(gq.w - gp.w) / zs;
-            const float wz = 1.0f / (1.0f + dz * dz);
-            const float wt = ((hk * wl) * wn) * wz;
-            nr += wt * xq.x;
-            ng += wt * xq.y;
-            nb += wt * xq.z;
-            den += wt;
-            nv += (wt * wt) * xq.w;
-        }
-    }
-    // c. the update
-    float4 xo = xp;
-    if (den > 0.0f) xo = make_float4(nr / den, ng / den, nb / den, nv / (den * den));
-    if (LAST) {
-        const float3 a = albedo(__float_as_int(hits[2 * i + 1].w) & 3);
-        out[i] = make_float4(xo.x * a.x, xo.y * a.y, xo.z * a.z, rgba[i].w);
-    } else {
-        st_out[i] = xo;
-    }
+    // b. the taps, c. the update
+    atrous_level<LAST>(x, y, i, gp, xp, gv, st_in, guide, st_out, w, h, lv, rgba, hits, out);
 }
 
 }  // namespace
@@ -167,16 +114,6 @@ struct gpuart_refine : ImageHandle {
 
 namespace {
 
-int check_params(const gpuart_refine_params &p) {
-    if (p.iterations > GPUART_REFINE_MAX_ITERATIONS)
-        return fail(GPUART_HIP_ERR_ARG, "refine: iterations = " + std::to_string(p.iterations) + " exceeds " +
-                                            std::to_string(GPUART_REFINE_MAX_ITERATIONS));
-    if (!std::isfinite(p.lum_k) || !(p.lum_k >= 0)) return fail(GPUART_HIP_ERR_ARG, "refine: lum_k must be finite and >= 0");
-    if (!std::isfinite(p.depth_sigma) || !(p.depth_sigma > 0)) return fail(GPUART_HIP_ERR_ARG, "refine: depth_sigma must be finite and > 0");
-    if (p.normal_pow2 > 16) return fail(GPUART_HIP_ERR_ARG, "refine: normal_pow2 exceeds 16");
-    return 0;
-}
-
 /// The checks both entry points make; `align` is what rgba, hits and out must be aligned to.
 int check_run(gpuart_refine *r, const void *rgba, const void *hits, const void *prims, const void *error, float lum_floor, uint32_t w,
               uint32_t h, const gpuart_refine_params *p, const void *out, size_t align) {
@@ -186,7 +123,7 @@ int check_run(gpuart_refine *r, const void *rgba, const void *hits, const void *
         return fail(GPUART_HIP_ERR_ARG, "refine: misaligned pointer (rgba, hits and out need " + std::to_string(align) + " bytes, prims and error 4)");
     if (int rc = check_size(LIB, w, h)) return rc;
     if (!std::isfinite(lum_floor) || !(lum_floor > 0)) return fail(GPUART_HIP_ERR_ARG, "refine: lum_floor must be finite and > 0");
-    return p ? check_params(*p) : 0;
+    return p ? check_params(LIB, *p, GPUART_REFINE_MAX_ITERATIONS) : 0;
 }
 
 /// The filter on device memory, on the handle's stream; the states and the guide take the first 48 bytes per pixel of the scratch.
@@ -203,12 +140,7 @@ int launch(gpuart_refine *r, const float4 *rgba, const float4 *hits, const int32
     k_rf_prepare<<<grid, block, 0, r->stream>>>(rgba, hits, prims, us_flags, error, lum_floor, w, h, st[0], guide);
     HIP_TRY(hipGetLastError());
     for (uint32_t it = 0; it < p.iterations; it++) {
-        Level lv;
-        lv.lum_k = p.lum_k;
-        lv.depth_sigma = p.depth_sigma;
-        lv.s = 1 << it;
-        lv.step = (float)lv.s;
-        lv.normal_pow2 = p.normal_pow2;
+        const Level lv = make_level(p, it);
         if (it + 1 == p.iterations)
             k_rf_level<true><<<grid, block, 0, r->stream>>>(st[it & 1], guide, nullptr, w, h, lv, rgba, hits, out);
         else
@@ -248,9 +180,7 @@ int gpuart_refine_run(gpuart_refine *r, const float *rgba, const gpuart_ray_hit 
                       const float *error, float lum_floor, uint32_t w, uint32_t h, const gpuart_refine_params *p, float *out) {
     int rc = check_run(r, rgba, hits, prims, error, lum_floor, w, h, p, out, 16);
     if (rc) return rc;
-    gpuart_refine_params rp;
-    if (p) rp = *p;
-    else gpuart_refine_defaults(&rp);
+    const gpuart_refine_params rp = params_or(p, gpuart_refine_defaults);
     HIP_TRY(hipSetDevice(r->device));
     if ((rc = ensure(r->stream, r->scratch, (size_t)w * h * 48))) return rc;
     return launch(r, (const float4 *)rgba, (const float4 *)hits, prims, userSphereFlags, error, lum_floor, (int)w, (int)h, rp, (float4 *)out);
@@ -260,9 +190,7 @@ int gpuart_refine_run_host(gpuart_refine *r, const float *rgba, const gpuart_ray
                            const float *error, float lum_floor, uint32_t w, uint32_t h, const gpuart_refine_params *p, float *out) {
     int rc = check_run(r, rgba, hits, prims, error, lum_floor, w, h, p, out, 4);
     if (rc) return rc;
-    gpuart_refine_params rp;
-    if (p) rp = *p;
-    else gpuart_refine_defaults(&rp);
+    const gpuart_refine_params rp = params_or(p, gpuart_refine_defaults);
     HIP_TRY(hipSetDevice(r->device));
     const size_t n = (size_t)w * h;
     // the filter's 48 bytes per pixel, then the staged inputs and the error map; the staged radiance is also the output

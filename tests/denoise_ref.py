@@ -52,6 +52,48 @@ def denormals(a):
     return int(((a != 0) & (np.abs(a) < TINY)).sum())
 
 
+def level(mask, x, var, n, pos, zpos, s, sd_var, lum_k, normal_pow2, depth_sigma, led):
+    """One à-trous level with a dilation of s over the pixels of `mask` (the denoiser's surface pixels, the variance-guided filter's
+    valid ones): the 25 taps and the update -> (x, var). sd_var is the variance the luminance edge is sized by: var itself in the
+    denoiser, the prefiltered one in tests/refine_ref.py. led counts tap_outside, tap_not_surface (a tap inside the tile that is not
+    in the mask), den_zero and denormal_state. This is the one restatement of gpuart_amd/csrc/image/atrous.h `atrous_level`."""
+    Lp = lum(x)
+    sd = np.sqrt(sd_var) * F(lum_k) + F(1e-4)
+    zs = (F(depth_sigma) * zpos) * F(s)
+    num = np.zeros_like(x)
+    den = np.zeros(x.shape[:2], np.float32)
+    nv = np.zeros(x.shape[:2], np.float32)
+    for dy in range(-2, 3):
+        for dx in range(-2, 3):
+            xq, inside = shift(x, s * dy, s * dx)
+            vq, _ = shift(var, s * dy, s * dx)
+            nq, _ = shift(n, s * dy, s * dx)
+            pq, _ = shift(pos, s * dy, s * dx)
+            sq, _ = shift(mask, s * dy, s * dx)
+            v = mask & inside
+            led["tap_outside"] += int((mask & ~inside).sum())
+            led["tap_not_surface"] += int((v & ~sq).sum())
+            v = v & sq
+            hk = H[dy + 2] * H[dx + 2]
+            e = (lum(xq) - Lp) / sd
+            wl = F(1) / (F(1) + e * e)
+            wn = gt_or((n[..., 0] * nq[..., 0] + n[..., 1] * nq[..., 1]) + n[..., 2] * nq[..., 2], 0.0)
+            for _ in range(normal_pow2):
+                wn = wn * wn
+            dz = np.abs(pq - pos) / zs
+            wz = F(1) / (F(1) + dz * dz)
+            wt = ((hk * wl) * wn) * wz
+            num = np.where(v[..., None], num + wt[..., None] * xq, num)
+            den = np.where(v, den + wt, den)
+            nv = np.where(v, nv + (wt * wt) * vq, nv)
+    upd = mask & (den > 0)
+    led["den_zero"] += int((mask & ~(den > 0)).sum())
+    x = np.where(upd[..., None], num / den[..., None], x)
+    var = np.where(upd, nv / (den * den), var)
+    led["denormal_state"] += denormals(x[mask]) + denormals(var[mask])
+    return x, var
+
+
 def denoise(rgba, words, prims, us_flags=0, iterations=5, lum_k=4.0, normal_pow2=5, depth_sigma=0.05, want_ledger=False):
     """-> out (h, w, 4)[, ledger]. The ledger (LEDGER_KEYS -> count) says how many pixels (den_zero: per level) and taps (per level)
     took each branch, counted from the very masks that select the values below, and how many values of the outputs and of the state
@@ -93,41 +135,7 @@ def denoise(rgba, words, prims, us_flags=0, iterations=5, lum_k=4.0, normal_pow2
         led["denormal_state"] = denormals(x[surf]) + denormals(var[surf])
         # 3. the à-trous levels
         for i in range(iterations):
-            s = 1 << i
-            Lp = lum(x)
-            sd = np.sqrt(var) * F(lum_k) + F(1e-4)
-            zs = (F(depth_sigma) * zpos) * F(s)
-            num = np.zeros_like(x)
-            den = np.zeros(c.shape[:2], np.float32)
-            nv = np.zeros(c.shape[:2], np.float32)
-            for dy in range(-2, 3):
-                for dx in range(-2, 3):
-                    xq, inside = shift(x, s * dy, s * dx)
-                    vq, _ = shift(var, s * dy, s * dx)
-                    nq, _ = shift(n, s * dy, s * dx)
-                    pq, _ = shift(pos, s * dy, s * dx)
-                    sq, _ = shift(surf, s * dy, s * dx)
-                    v = surf & inside
-                    led["tap_outside"] += int((surf & ~inside).sum())
-                    led["tap_not_surface"] += int((v & ~sq).sum())
-                    v = v & sq
-                    hk = H[dy + 2] * H[dx + 2]
-                    e = (lum(xq) - Lp) / sd
-                    wl = F(1) / (F(1) + e * e)
-                    wn = gt_or((n[..., 0] * nq[..., 0] + n[..., 1] * nq[..., 1]) + n[..., 2] * nq[..., 2], 0.0)
-                    for _ in range(normal_pow2):
-                        wn = wn * wn
-                    dz = np.abs(pq - pos) / zs
-                    wz = F(1) / (F(1) + dz * dz)
-                    wt = ((hk * wl) * wn) * wz
-                    num = np.where(v[..., None], num + wt[..., None] * xq, num)
-                    den = np.where(v, den + wt, den)
-                    nv = np.where(v, nv + (wt * wt) * vq, nv)
-            upd = surf & (den > 0)
-            led["den_zero"] += int((surf & ~(den > 0)).sum())
-            x = np.where(upd[..., None], num / den[..., None], x)
-            var = np.where(upd, nv / (den * den), var)
-            led["denormal_state"] += denormals(x[surf]) + denormals(var[surf])
+            x, var = level(surf, x, var, n, pos, zpos, 1 << i, var, lum_k, normal_pow2, depth_sigma, led)
         # 4. remodulation; every other pixel is copied, alpha everywhere
         out[..., :3] = np.where(surf[..., None], x * a, c[..., :3])
         led["denormal_out"] = denormals(out[..., :3][surf])

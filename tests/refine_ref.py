@@ -7,7 +7,7 @@ float32, row 0 at the bottom; the G-buffer is (h, w, 8) float32 words of gpuart_
 tests/denoise_ref.py; the error map is (h, w) float32, the e of tests/converge_ref.py's measure."""
 import numpy as np
 
-from tests.denoise_ref import H, PRIMITIVE_COLOR, denormals, gt_or, lum, shift, surface
+from tests.denoise_ref import PRIMITIVE_COLOR, denormals, gt_or, level, lum, shift, surface
 
 F = np.float32
 G = np.array([1 / 4, 1 / 2, 1 / 4], np.float32)
@@ -53,7 +53,6 @@ def refine(rgba, words, prims, error, lum_floor, us_flags=0, iterations=5, lum_k
         led["denormal_state"] = denormals(x[valid]) + denormals(var[valid])
         # 2. the levels
         for i in range(iterations):
-            s = 1 << i
             # a. the 3x3 variance prefilter, never dilated
             if prefilter:
                 gn = np.zeros(c.shape[:2], np.float32)
@@ -71,42 +70,8 @@ def refine(rgba, words, prims, error, lum_floor, us_flags=0, iterations=5, lum_k
                 gv = gn / gd
             else:
                 gv = var
-            # b. the taps
-            Lp = lum(x)
-            sd = np.sqrt(gv) * F(lum_k) + F(1e-4)
-            zs = (F(depth_sigma) * zpos) * F(s)
-            num = np.zeros_like(x)
-            den = np.zeros(c.shape[:2], np.float32)
-            nv = np.zeros(c.shape[:2], np.float32)
-            for dy in range(-2, 3):
-                for dx in range(-2, 3):
-                    xq, inside = shift(x, s * dy, s * dx)
-                    vq, _ = shift(var, s * dy, s * dx)
-                    nq, _ = shift(n, s * dy, s * dx)
-                    pq, _ = shift(pos, s * dy, s * dx)
-                    sq, _ = shift(valid, s * dy, s * dx)
-                    v = valid & inside
-                    led["tap_outside"] += int((valid & ~inside).sum())
-                    led["tap_not_surface"] += int((v & ~sq).sum())
-                    v = v & sq
-                    hk = H[dy + 2] * H[dx + 2]
-                    d = (lum(xq) - Lp) / sd
-                    wl = F(1) / (F(1) + d * d)
-                    wn = gt_or((n[..., 0] * nq[..., 0] + n[..., 1] * nq[..., 1]) + n[..., 2] * nq[..., 2], 0.0)
-                    for _ in range(normal_pow2):
-                        wn = wn * wn
-                    dz = np.abs(pq - pos) / zs
-                    wz = F(1) / (F(1) + dz * dz)
-                    wt = ((hk * wl) * wn) * wz
-                    num = np.where(v[..., None], num + wt[..., None] * xq, num)
-                    den = np.where(v, den + wt, den)
-                    nv = np.where(v, nv + (wt * wt) * vq, nv)
-            # c. the update
-            upd = valid & (den > 0)
-            led["den_zero"] += int((valid & ~(den > 0)).sum())
-            x = np.where(upd[..., None], num / den[..., None], x)
-            var = np.where(upd, nv / (den * den), var)
-            led["denormal_state"] += denormals(x[valid]) + denormals(var[valid])
+            # b. the taps, c. the update
+            x, var = level(valid, x, var, n, pos, zpos, 1 << i, gv, lum_k, normal_pow2, depth_sigma, led)
         # 3. remodulation; every other pixel is copied, alpha everywhere
         out[..., :3] = np.where(valid[..., None], x * a, c[..., :3])
         led["denormal_out"] = denormals(out[..., :3][valid])

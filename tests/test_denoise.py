@@ -12,7 +12,7 @@ import pytest
 
 from gpuart_amd import synth_scenes as S
 from tests import denoise_ref as R
-from tests.util import assert_same_bits, exported, same_bits, scene
+from tests.util import assert_same_bits, default_camera, exported, filter_params_layout, same_bits, scene, to_device
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR_ARG = -1
@@ -58,14 +58,7 @@ def test_denoise_library_exports_exactly_its_header(lib):
 
 def test_params_record_matches_the_header(tmp_path):
     from gpuart_amd import binding as B
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "gpuart_denoise.h"\n'
-                   'int main(void) { printf("%zu %zu %zu %zu %zu %u\\n", sizeof(gpuart_denoise_params), offsetof(gpuart_denoise_params, iterations), '
-                   'offsetof(gpuart_denoise_params, lum_k), offsetof(gpuart_denoise_params, normal_pow2), offsetof(gpuart_denoise_params, depth_sigma), '
-                   'GPUART_DENOISE_MAX_ITERATIONS); return 0; }\n')
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    got = filter_params_layout(tmp_path, "denoise")
     P = B.DenoiseParams
     assert got == [C.sizeof(P), P.iterations.offset, P.lum_k.offset, P.normal_pow2.offset, P.depth_sigma.offset, 8] == [16, 0, 4, 8, 12, 8]
     assert B.DENOISE_DEFAULTS == R.DEFAULTS
@@ -128,8 +121,7 @@ def tree(O, name):
 
 
 def camera(O, W, H):
-    cam = dict(S.DEFAULT_CAMERA)
-    cam["dir"] = S.camera_dir(cam)
+    cam = default_camera()
     return O.camera(cam["pos"], cam["dir"], cam["up"], cam["fov_y"], cam["screen_dist"], W, H)
 
 
@@ -242,9 +234,8 @@ def check_entry_points(dn, rgba, hits, prims, flags, params, what):
     exp = R.denoise(rgba, hits, prims, flags, **dict(R.DEFAULTS, **(params or {})))
     got = dn.run(rgba, hits, prims, flags, params=params)
     assert_same_bits(got, exp, what + ", host")
-    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
     out = torch.full(rgba.shape, 7.0, device="cuda:0")
-    res = dn.run(t(rgba), t(hits.view(np.float32).reshape(rgba.shape[:2] + (8,))), t(prims), flags, params=params, out=out)
+    res = dn.run(to_device(rgba), to_device(hits.view(np.float32).reshape(rgba.shape[:2] + (8,))), to_device(prims), flags, params=params, out=out)
     assert res is out
     assert_same_bits(out.cpu().numpy(), exp, what + ", torch")
     return exp
@@ -287,8 +278,7 @@ def test_denoising_cuts_the_error_of_low_sample_frames(B, name):
     """160x120, the default camera, the Sun on, no user sphere: against a 512-spp frame of another seed, the surface-pixel RMSE of the
     denoised 1-spp and 4-spp frames is at most 0.75x that of the raw ones."""
     W, H = 160, 120
-    cam = dict(S.DEFAULT_CAMERA)
-    cam["dir"] = S.camera_dir(cam)
+    cam = default_camera()
     r = B.Renderer(W, H, cam)
     try:
         r.set_primitives(scene(name))
@@ -319,8 +309,7 @@ def test_read_denoised_filters_the_accumulator_and_leaves_it_alone(B):
     """Renderer.read_denoised = the restatement of read_radiance(normalized) with pick of every tile pixel; passes after it, the
     accumulator and the counters are those of a run without it. The G-buffer follows the user sphere, the camera and the tile."""
     W, H = 96, 64
-    cam = dict(S.DEFAULT_CAMERA)
-    cam["dir"] = S.camera_dir(cam)
+    cam = default_camera()
     y, x = np.divmod(np.arange(W * H), W)
     xy = np.stack([x, y], 1)
 
@@ -389,8 +378,7 @@ def test_cli_writes_the_denoised_frame(B, tmp_path):
         assert raw.startswith(head)
         imgs[tag] = np.frombuffer(raw[len(head):], np.float32).reshape(H, W, 3)
     # the CLI's camera looks at (0, 0, 0.95) from its default position; its user sphere is emissive
-    cam = dict(S.DEFAULT_CAMERA)
-    cam["dir"] = S.camera_dir(cam)
+    cam = default_camera()
     r = B.Renderer(W, H, cam)
     try:
         r.init_box()
@@ -462,8 +450,7 @@ def test_argument_errors(be, dn, B, O):
     finally:
         fresh.close()
     # the Renderer: no scene
-    cam = dict(S.DEFAULT_CAMERA)
-    cam["dir"] = S.camera_dir(cam)
+    cam = default_camera()
     r = B.Renderer(16, 8, cam)
     try:
         with pytest.raises(B.HipError):

@@ -1,4 +1,4 @@
-"""What libgpuart_denoise.so, libgpuart_temporal.so and libgpuart_converge.so share (gpuart_amd/csrc/image/image_lib.h): every library
+"""What libgpuart_denoise.so, libgpuart_temporal.so, libgpuart_converge.so and libgpuart_refine.so share (gpuart_amd/csrc/image/image_lib.h): every library
 keeps a last error of its own, and one handle of each that grows and shrinks — its buffers allocated again behind work on its stream,
 its staging offsets moved — still computes its restatement's bits."""
 import ctypes as C
@@ -11,18 +11,19 @@ import pytest
 from tests import converge_ref
 from tests import denoise_ref
 from tests import filter_cases as FC
+from tests import refine_ref
 from tests import temporal_ref
-from tests.util import assert_same_bits
+from tests.util import assert_same_bits, to_device
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = ("denoise", "temporal", "converge")
+NAMES = ("denoise", "temporal", "converge", "refine")
 ERR_ARG = -1
 
 
 # ---- CPU --------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("lib", ["lib", "lib_test"])
 def test_each_library_keeps_its_own_last_error(lib):
-    """gpuart_<name>_finish(NULL) fails before any HIP call: that library's last error then carries its own prefix, and the other two
+    """gpuart_<name>_finish(NULL) fails before any HIP call: that library's last error then carries its own prefix, and the other
     libraries' strings are as they were."""
     libs = {n: C.CDLL(os.path.join(ROOT, "gpuart_amd", lib, "libgpuart_%s.so" % n)) for n in NAMES}
     for n in NAMES:
@@ -34,7 +35,7 @@ def test_each_library_keeps_its_own_last_error(lib):
         assert last(n) == ("%s: handle is NULL" % n).encode()
         seen[n] = last(n)
         assert {m: last(m) for m in NAMES} == seen, n
-    assert len(set(seen.values())) == 3
+    assert len(set(seen.values())) == len(NAMES)
 
 
 # ---- GPU --------------------------------------------------------------------------------------------------------------------------
@@ -53,7 +54,7 @@ BATCHES = (4, 3)   # paths of the convergence estimate's two updates per size
 def views():
     """One view per size (tests/filter_cases.py `step`, seed 4242), and per view what each restatement makes of it: the denoised image;
     the blend and lengths of a chain that commits every view; the states after two updates of an estimator reset at every size, and
-    its measure."""
+    its measure; the variance-guided filter of the view with that measure's error map."""
     rng = np.random.default_rng(4242)
     out, hist = [], None
     for geom, pos in zip(GEOMS, POSITIONS):
@@ -66,6 +67,7 @@ def views():
         v["totals"] = [BATCHES[0], BATCHES[0] + BATCHES[1]]
         v["states"] = [est.update(a, t).copy() for a, t in zip(v["accums"], v["totals"])]
         v["summary"], v["error"] = est.measure(0.05, 1.0 / 256)
+        v["refined"] = refine_ref.refine(rgba, words, prims, v["error"], 1.0 / 256)
         out.append(v)
     assert all((v["len"] > v["spp"]).any() for v in out[1:])   # (each found the history of the other size)
     return out
@@ -80,14 +82,16 @@ def test_one_handle_grows_and_shrinks(name, entry):
     from gpuart_amd import binding as B
     from tests.test_converge import assert_summary
     from tests.test_filter_edges import binding_view
-    to = (lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")) if entry == "device" else (lambda a: a)
+    to = to_device if entry == "device" else (lambda a: a)
     back = (lambda a: a.cpu().numpy()) if entry == "device" else (lambda a: a)
-    handle = {"denoise": B.Denoiser, "temporal": B.Temporal, "converge": B.Converge}[name](0)
+    handle = {"denoise": B.Denoiser, "temporal": B.Temporal, "converge": B.Converge, "refine": B.Refine}[name](0)
     try:
         for i, v in enumerate(views()):
             what = "%s, %s, call %d (%d x %d)" % (name, entry, i, v["w"], v["h"])
             if name == "denoise":
                 assert_same_bits(back(handle.run(to(v["rgba"]), to(v["words"]), to(v["prims"]))), v["denoised"], what)
+            elif name == "refine":
+                assert_same_bits(back(handle.run(to(v["rgba"]), to(v["words"]), to(v["prims"]), to(v["error"]), 1.0 / 256)), v["refined"], what)
             elif name == "temporal":
                 out, ln = handle.accumulate(to(v["rgba"]), v["spp"], to(v["words"]), to(v["prims"]), binding_view(B, v["view"]), commit=True)
                 assert_same_bits(back(out), v["blend"], what)

@@ -17,7 +17,7 @@ from tests import filter_cases as FC
 from tests import refine_ref as R
 from tests import temporal_ref as T
 from tests.test_denoise import synthetic_gbuffer
-from tests.util import assert_same_bits, exported, same_bits, scene
+from tests.util import assert_same_bits, default_camera, exported, filter_params_layout, same_bits, scene, to_device
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR_ARG = -1
@@ -55,14 +55,7 @@ def test_refine_library_exports_exactly_its_header(lib):
 
 def test_params_record_matches_the_header(tmp_path):
     from gpuart_amd import binding as B
-    src = tmp_path / "layout.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "gpuart_refine.h"\n'
-                   'int main(void) { printf("%zu %zu %zu %zu %zu %u\\n", sizeof(gpuart_refine_params), offsetof(gpuart_refine_params, iterations), '
-                   'offsetof(gpuart_refine_params, lum_k), offsetof(gpuart_refine_params, normal_pow2), offsetof(gpuart_refine_params, depth_sigma), '
-                   'GPUART_REFINE_MAX_ITERATIONS); return 0; }\n')
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    got = filter_params_layout(tmp_path, "refine")
     P = B.RefineParams
     assert got == [C.sizeof(P), P.iterations.offset, P.lum_k.offset, P.normal_pow2.offset, P.depth_sigma.offset, 8] == [16, 0, 4, 8, 12, 8]
     assert B.REFINE_DEFAULTS == R.DEFAULTS
@@ -230,17 +223,6 @@ def bounded(request):
     binding.phase_log(was)
 
 
-def default_camera():
-    cam = dict(S.DEFAULT_CAMERA)
-    cam["dir"] = S.camera_dir(cam)
-    return cam
-
-
-def to_device(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
-
-
 def check_entry_points(rf, rgba, words, prims, e, lum_floor, flags, params, exp, what):
     """The host entry point, the device one (torch tensors) into a separate output, and the device one in place, against `exp`."""
     import torch
@@ -309,24 +291,6 @@ def test_kernels_equal_the_restatement_on_rendered_frames(rf, B):
                 assert (prims == -2).any() and (hits["type"] < 0).any() and not same_bits(exp, rgba)
     finally:
         r.close()
-
-
-@pytest.mark.gpu
-@pytest.mark.parametrize("entry", ["host", "device"])
-def test_one_handle_grows_and_shrinks(B, entry):
-    """tests/test_image_libs.py's sequence of sizes (one pixel, 65 x 5, one pixel) through one handle: its scratch is allocated again
-    behind work on its stream, then larger than the call needs, and the staged planes move."""
-    from tests.test_image_libs import views
-    back = (lambda a: a.cpu().numpy()) if entry == "device" else (lambda a: a)
-    to = to_device if entry == "device" else (lambda a: a)
-    handle = B.Refine(0)
-    try:
-        for i, v in enumerate(views()):
-            exp = R.refine(v["rgba"], v["words"], v["prims"], v["error"], LUM_FLOOR)
-            got = handle.run(to(v["rgba"]), to(v["words"]), to(v["prims"]), to(v["error"]), LUM_FLOOR)
-            assert_same_bits(back(got), exp, "%s, call %d (%d x %d)" % (entry, i, v["w"], v["h"]))
-    finally:
-        handle.close()
 
 
 @pytest.mark.gpu

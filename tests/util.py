@@ -72,6 +72,31 @@ def exported(path):
     return sorted(line.split()[-1] for line in out.splitlines() if line.strip())
 
 
+def default_camera():
+    """The default camera of the synthetic scenes, with its direction."""
+    cam = dict(S.DEFAULT_CAMERA)
+    cam["dir"] = S.camera_dir(cam)
+    return cam
+
+
+def to_device(a):
+    """A NumPy array as a contiguous torch tensor on GPU 0."""
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
+
+
+def filter_params_layout(tmp_path, name):
+    """[sizeof, the four fields' offsets, GPUART_<NAME>_MAX_ITERATIONS] of gpuart_<name>_params as a C compiler lays include/gpuart_<name>.h out."""
+    rec = "gpuart_%s_params" % name
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "gpuart_%s.h"\n'
+                   'int main(void) { printf("%%zu %%zu %%zu %%zu %%zu %%u\\n", sizeof(%s), %s, GPUART_%s_MAX_ITERATIONS); return 0; }\n'
+                   % (name, rec, ", ".join("offsetof(%s, %s)" % (rec, f) for f in ("iterations", "lum_k", "normal_pow2", "depth_sigma")), name.upper()))
+    exe = tmp_path / "layout"
+    subprocess.run(["gcc", "-I", os.path.join(os.path.dirname(GOLDEN), os.pardir, "include"), "-o", str(exe), str(src)], check=True)
+    return [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+
+
 def rmse_per_channel(got, ref):
     d = np.asarray(got, np.float64)[..., :3] - np.asarray(ref, np.float64)[..., :3]
     return np.sqrt(np.nanmean(d * d, axis=tuple(range(d.ndim - 1))))
