@@ -383,6 +383,20 @@ def tree_class(quads):
     return dict(irregular=bool(flags.value & 1), disorderly=bool(flags.value & 2), type_mask=(flags.value >> 8) & 15)
 
 
+KERNEL_ENTRIES = ("direct", "run", "trace", "query")   # gpuart_hip_test_kernel_choice's `entry`
+
+
+def kernel_choice(type_mask, exact_boxes, ref_order, lean, mode, entry):
+    """The instantiation the library's launch sites would pick, without a device: (TYPES, COUNT, REFWORK); entry: one of KERNEL_ENTRIES."""
+    L = hip_lib()
+    out = (C.c_uint32 * 3)()
+    rc = L.gpuart_hip_test_kernel_choice(C.c_uint32(type_mask), C.c_uint32(exact_boxes), C.c_uint32(ref_order), C.c_uint32(lean), int(mode),
+                                         KERNEL_ENTRIES.index(entry), out)
+    if rc != 0:
+        raise HipError("gpuart_hip error %d: %s" % (rc, L.gpuart_hip_last_error().decode()))
+    return int(out[0]), bool(out[1]), bool(out[2])
+
+
 def tree_slack(quads):
     """(slack constant the upload would give the tree for its quick box answers — inf: none —, a box plane is subnormal), without a device."""
     L = hip_lib()

@@ -8,6 +8,7 @@
 #include <atomic>
 #include <chrono>
 #include <thread>
+#include <utility>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -198,6 +199,46 @@ void ledger_note(gpuart_hip_ctx *c, const void *kernel) {
 #else
 #define GD_LEDGER(c, ...) ((void)0)
 #endif
+
+// ---- the kernel choice ----------------------------------------------------------------------------------------------------------
+// k_direct_persistent, k_run, k_trace and k_ray_query are compiled once per tree class. `kernel_choice` is the one statement of which
+// instantiation a launch runs (pure host code: gpuart_hip_test_kernel_choice), `with_types` the one place that makes it a template argument.
+enum { KC_DIRECT = 0, KC_RUN = 1, KC_TRACE = 2, KC_QUERY = 3 };  ///< the launch sites that choose
+enum { KC_COUNT = 0x100, KC_REFWORK = 0x200 };                  ///< beside k_run's TYPES: its COUNT and REFWORK
+
+/// The rule. A tree with exact boxes takes the comparison-form kernel with every type. Otherwise the lean kernels (GPUART_HIP_LEAN_KERNELS)
+/// serve trees of flat (discs, triangles) or round (spheres, discs) primitives only, and the path tracer's kernels carry GD_REF_ORDER while
+/// the tree is walked in the reference's order; k_direct_persistent and k_ray_query have no such variant. k_run in mode 1 does the
+/// reference's work with its counters: every type, never the order bit. In mode 4 it counts the executed work: a flat but no round variant.
+int kernel_choice(uint32_t type_mask, bool exact_boxes, bool ref_order, bool lean_kernels, int mode, int entry) {
+    const int run = entry != KC_RUN ? 0 : mode == 1 ? KC_COUNT | KC_REFWORK : mode == 4 ? KC_COUNT : 0;
+    if (exact_boxes) return run | GD_ALL_TYPES | GD_EXACT_BOXES;
+    if (run & KC_REFWORK) return run | GD_ALL_TYPES;
+    const bool flat = lean_kernels && (type_mask & ~(uint32_t)GD_FLAT_TYPES) == 0;            // triangle meshes + discs
+    const bool round = lean_kernels && (type_mask & ~(uint32_t)GD_ROUND_TYPES) == 0 && !run;  // spheres + discs
+    const int types = flat ? GD_FLAT_TYPES : round ? GD_ROUND_TYPES : GD_ALL_TYPES;
+    return run | types | (ref_order && (entry == KC_RUN || entry == KC_TRACE) ? GD_REF_ORDER : 0);
+}
+int kernel_choice(const gpuart_hip_ctx *c, int entry) {
+    return kernel_choice(c->type_mask, c->exact_boxes != 0, c->ref_order != 0, c->lean_kernels, c->plan.mode, entry);
+}
+
+/// The instantiations that exist, per kernel: the dispatcher makes no other (tests/test_kernel_variants.py holds the code object to them).
+template <int... T> using TypeList = std::integer_sequence<int, T...>;
+using LeafTypes = TypeList<GD_FLAT_TYPES, GD_ROUND_TYPES, GD_ALL_TYPES, GD_ALL_TYPES | GD_EXACT_BOXES>;  // k_direct_persistent, k_ray_query x 2 sources
+using TraceTypes = TypeList<GD_FLAT_TYPES, GD_ROUND_TYPES, GD_ALL_TYPES, GD_ALL_TYPES | GD_EXACT_BOXES, GD_FLAT_TYPES | GD_REF_ORDER,
+                            GD_ROUND_TYPES | GD_REF_ORDER, GD_ALL_TYPES | GD_REF_ORDER>;                  // k_trace<false, .>
+using RunTypes = TypeList<GD_FLAT_TYPES, GD_ROUND_TYPES, GD_ALL_TYPES, GD_ALL_TYPES | GD_EXACT_BOXES, GD_FLAT_TYPES | GD_REF_ORDER,
+                          GD_ROUND_TYPES | GD_REF_ORDER, GD_ALL_TYPES | GD_REF_ORDER, KC_COUNT | GD_FLAT_TYPES, KC_COUNT | GD_ALL_TYPES,
+                          KC_COUNT | GD_ALL_TYPES | GD_EXACT_BOXES, KC_COUNT | GD_FLAT_TYPES | GD_REF_ORDER, KC_COUNT | GD_ALL_TYPES | GD_REF_ORDER,
+                          KC_COUNT | KC_REFWORK | GD_ALL_TYPES, KC_COUNT | KC_REFWORK | GD_ALL_TYPES | GD_EXACT_BOXES>;  // k_run
+
+/// The dispatcher: `launch(std::integral_constant<int, T>)` for the T of the kernel's list that equals `choice`; an error for any other.
+template <int... T, class Launch>
+int with_types(int choice, TypeList<T...>, const char *kernel, Launch launch) {
+    if (((choice == T && (launch(std::integral_constant<int, T>()), true)) || ...)) return 0;
+    return fail(GPUART_HIP_ERR_DEVICE, std::string("internal: no ") + kernel + " for choice " + std::to_string(choice));
+}
 
 /// Waits for everything this context has enqueued, on all of its streams.
 int drain(gpuart_hip_ctx *c) {
@@ -629,6 +670,15 @@ static int check_ready(gpuart_hip_ctx *c, const gpuart_params *p) {
     return 0;
 }
 
+/// The chunks of a launch of `n` entries through the persistent-lane loop (k_direct_persistent, k_ray_query): its tail is the last chunk a
+/// wave takes from the cursor (128 pixels are two rounds of two dependent queries). Small launches take 64-entry chunks — a 1080p frame
+/// 0.92 -> 0.75 ms; 4K stays at 128 (1.74 against 1.85): fewer cursor atomics, longer coherent runs (32 and 16 are far worse: 1.0 / 1.7 ms).
+static TraceTuning direct_tuning(const gpuart_hip_ctx *c, size_t n) {
+    TraceTuning tune = c->tune;
+    if (!c->chunk_from_env && n / ((size_t)c->direct_waves * 8) < 128) tune.chunk = 64;
+    return tune;
+}
+
 int gpuart_hip_render_direct(gpuart_hip_ctx *c, const gpuart_params *p) {
     int r = check_ready(c, p);
     if (r) return r > 0 ? 0 : r;
@@ -649,23 +699,12 @@ int gpuart_hip_render_direct(gpuart_hip_ctx *c, const gpuart_params *p) {
         if (!c->d_cursor) HIP_TRY(hipMalloc(&c->d_cursor, 64));
         HIP_TRY(hipMemsetAsync(c->d_cursor, 0, sizeof(uint32_t), c->stream));
         const dim3 pgrid(c->direct_waves);  // alone on the GPU: 16 waves per CU measured best
-        // The frame is one launch: its tail is the last chunk a wave takes from the cursor (128 pixels are two rounds of two
-        // dependent queries). Small frames take 64-pixel chunks — 1080p 0.92 -> 0.75 ms per frame; 4K stays at 128 (1.74 against
-        // 1.85): fewer cursor atomics, longer coherent runs (gpurun_out/direct_chunk.txt; 32 and 16 are far worse: 1.0 / 1.7 ms)
-        TraceTuning dtune = c->tune;
-        if (!c->chunk_from_env && c->plan.n_slots / ((size_t)c->direct_waves * 8) < 128) dtune.chunk = 64;
-        const bool flat_only = c->lean_kernels && !c->exact_boxes && (c->type_mask & ~(uint32_t)GD_FLAT_TYPES) == 0;
-        const bool round_only = c->lean_kernels && !c->exact_boxes && !flat_only && (c->type_mask & ~(uint32_t)GD_ROUND_TYPES) == 0;
-#define GD_LAUNCH_DIRECT(T)                                                                                                    \
-    do {                                                                                                                       \
-        GD_LEDGER(c, k_direct_persistent<T>);                                                                                  \
-        k_direct_persistent<T><<<pgrid, BLOCK, 0, c->stream>>>(sc, c->frame, *p, c->plan.n_slots, c->d_direct, c->d_spill, c->d_cursor, dtune); \
-    } while (0)
-        if (c->exact_boxes) GD_LAUNCH_DIRECT(GD_ALL_TYPES | GD_EXACT_BOXES);
-        else if (flat_only) GD_LAUNCH_DIRECT(GD_FLAT_TYPES);
-        else if (round_only) GD_LAUNCH_DIRECT(GD_ROUND_TYPES);
-        else GD_LAUNCH_DIRECT(GD_ALL_TYPES);
-#undef GD_LAUNCH_DIRECT
+        const TraceTuning dtune = direct_tuning(c, c->plan.n_slots);
+        if ((r = with_types(kernel_choice(c, KC_DIRECT), LeafTypes(), "k_direct_persistent", [&](auto T) {
+                GD_LEDGER(c, k_direct_persistent<T()>);
+                k_direct_persistent<T()><<<pgrid, BLOCK, 0, c->stream>>>(sc, c->frame, *p, c->plan.n_slots, c->d_direct, c->d_spill, c->d_cursor, dtune);
+            })))
+            return r;
     }
     HIP_TRY(hipGetLastError());
     return end_timed(c, t);
@@ -763,6 +802,20 @@ int sort_tile_order(gpuart_hip_ctx *c, PassLane &l) {
     return 0;
 }
 
+/// The end of every run: its colour is accumulated in pass order on the primary stream, which releases the lane; a gathering run is sorted.
+int finish_run(gpuart_hip_ctx *c, PassLane &l, bool gathers) {
+    int r;
+    HIP_TRY(hipEventRecord(l.ev_done, l.main));
+    HIP_TRY(hipStreamWaitEvent(c->stream, l.ev_done, 0));
+    GD_LEDGER(c, k_accumulate);
+    k_accumulate<<<dim3((unsigned)((c->plan.tile_pixels + 255) / 256)), 256, 0, c->stream>>>(c->d_accum, l.passcolor, c->plan.tile_pixels, l.pb.batch);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(l.ev_free, c->stream));
+    if (gathers && (r = sort_tile_order(c, l))) return r;
+    l.used = true;
+    return 0;
+}
+
 /// The collected passes [first, first + count) as ONE persistent kernel per path of the pass (k_run, kernel_run.h) on
 /// pass lane `l`; then their colour planes are added to the accumulator in pass order on the primary stream.
 int launch_run_persistent(gpuart_hip_ctx *c, PassLane &l, size_t first, size_t count) {
@@ -774,9 +827,6 @@ int launch_run_persistent(gpuart_hip_ctx *c, PassLane &l, size_t first, size_t c
     for (size_t k = 0; k < count; k++) seeds.seed[k] = c->pend_seeds[first + k];
     if (!l.run_cursor) HIP_TRY(hipMalloc(&l.run_cursor, 64));
     const PathBuffers &b = l.pb;
-    const bool flat_only = c->lean_kernels && !c->exact_boxes && (c->type_mask & ~(uint32_t)GD_FLAT_TYPES) == 0;  // triangle meshes + discs
-    const bool round_only = c->lean_kernels && !c->exact_boxes && !flat_only && (c->type_mask & ~(uint32_t)GD_ROUND_TYPES) == 0;  // spheres + discs
-    const bool exact = c->exact_boxes != 0;  // a tree with irregular boxes: the kernel variants with comparison-form box tests
     // k_run's list entries carry the path slot in RUN_SLOT's bits beside their flags
     // (the LARGEST slot index, n_slots x batch - 1, must fit: a run of exactly 2^28 slots does; the planner never plans a longer one
     //  for mode 0 — run_planner.h RUN_KERNEL_SLOTS — so only modes 1 / 4 / 5 on a tile beyond 2^28 pixels can get here)
@@ -795,34 +845,19 @@ int launch_run_persistent(gpuart_hip_ctx *c, PassLane &l, size_t first, size_t c
         TimedLaunch tt;
         HIP_TRY(hipMemsetAsync(l.run_cursor, 0, sizeof(uint32_t), l.main));
         if (c->timing_level >= 2 && (r = begin_timed(c, tt, 1, l.main))) return r;
-#define GD_LAUNCH_RUN(C, R, T) do { GD_LEDGER(c, k_run<C, R, T>); k_run<C, R, T><<<grid, BLOCK, 0, l.main>>>(sc, fr, *p, seeds, b, j, npaths, l.passcolor, l.spill_main, c->d_counters, c->tune, l.run_cursor); } while (0)
-#define GD_LAUNCH_RUN_ORD(C, T) do { if (c->ref_order) GD_LAUNCH_RUN(C, false, (T) | GD_REF_ORDER); else GD_LAUNCH_RUN(C, false, T); } while (0)
-        if (c->plan.mode == 1 && exact) GD_LAUNCH_RUN(true, true, GD_ALL_TYPES | GD_EXACT_BOXES);
-        else if (c->plan.mode == 1) GD_LAUNCH_RUN(true, true, GD_ALL_TYPES);
-        else if (c->plan.mode == 4 && exact) GD_LAUNCH_RUN(true, false, GD_ALL_TYPES | GD_EXACT_BOXES);
-        else if (c->plan.mode == 4 && flat_only) GD_LAUNCH_RUN_ORD(true, GD_FLAT_TYPES);
-        else if (c->plan.mode == 4) GD_LAUNCH_RUN_ORD(true, GD_ALL_TYPES);
-        else if (exact) GD_LAUNCH_RUN(false, false, GD_ALL_TYPES | GD_EXACT_BOXES);
-        else if (flat_only) GD_LAUNCH_RUN_ORD(false, GD_FLAT_TYPES);
-        else if (round_only) GD_LAUNCH_RUN_ORD(false, GD_ROUND_TYPES);
-        else GD_LAUNCH_RUN_ORD(false, GD_ALL_TYPES);
-#undef GD_LAUNCH_RUN_ORD
-#undef GD_LAUNCH_RUN
+        if ((r = with_types(kernel_choice(c, KC_RUN), RunTypes(), "k_run", [&](auto K) {
+                constexpr bool C = (K() & KC_COUNT) != 0, R = (K() & KC_REFWORK) != 0;
+                constexpr int T = K() & (KC_COUNT - 1);
+                GD_LEDGER(c, k_run<C, R, T>);
+                k_run<C, R, T><<<grid, BLOCK, 0, l.main>>>(sc, fr, *p, seeds, b, j, npaths, l.passcolor, l.spill_main, c->d_counters, c->tune, l.run_cursor);
+            })))
+            return r;
         if (c->timing_level >= 2 && (r = end_timed(c, tt, l.main))) return r;
     }
     if ((r = end_timed(c, t, l.main))) return r;
-    HIP_TRY(hipEventRecord(l.ev_done, l.main));
-    HIP_TRY(hipStreamWaitEvent(c->stream, l.ev_done, 0));
-    GD_LEDGER(c, k_accumulate);
-    k_accumulate<<<dim3((unsigned)((c->plan.tile_pixels + 255) / 256)), 256, 0, c->stream>>>(c->d_accum, l.passcolor, c->plan.tile_pixels, b.batch);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(l.ev_free, c->stream));
-    if (gathers && (r = sort_tile_order(c, l))) return r;
-    l.used = true;
-    return 0;
+    return finish_run(c, l, gathers);
 }
 
-/// One run of the launch-per-stage wavefront pipeline (mode 3) for the pending passes [first, first + count).
 /// One run of the wavefront pipeline for the pending passes [first, first + count) on the next pass lane.
 int launch_run(gpuart_hip_ctx *c, size_t first, size_t count) {
     int r;
@@ -841,8 +876,6 @@ int launch_run(gpuart_hip_ctx *c, size_t first, size_t count) {
     for (size_t k = 0; k < count; k++) seeds.seed[k] = c->pend_seeds[first + k];
     if ((r = ensure_segment_counters(c, l, nseg))) return r;
     const PathBuffers &b = l.pb;
-    const bool flat_only = c->lean_kernels && !c->exact_boxes && (c->type_mask & ~(uint32_t)GD_FLAT_TYPES) == 0;  // triangle meshes + discs
-    const bool round_only = c->lean_kernels && !c->exact_boxes && !flat_only && (c->type_mask & ~(uint32_t)GD_ROUND_TYPES) == 0;  // spheres + discs
     const bool detail = c->timing_level >= 2;
     const dim3 pgrid(c->grid_waves);
     const dim3 sgrid(std::min<uint32_t>(c->shade_waves, b.n_slots * b.batch / BLOCK));  // k_gen / k_shade: grid-stride loops
@@ -861,14 +894,11 @@ int launch_run(gpuart_hip_ctx *c, size_t first, size_t count) {
         TraceTuning tune = c->tune;
         const uint32_t packet = c->n_prims <= c->packet_max_prims ? c->packet : 0u;
         tune.packet = (packet >= 1 && seg_c == 0) ? 1u : (packet >= 2 && seg_s == 0) ? 2u : 0u;
-#define GD_LAUNCH_TRACE(T) do { GD_LEDGER(c, k_trace<false, T>); k_trace<false, T><<<pgrid, BLOCK, 0, l.main>>>(sc, fr, *p, b, seg_c, seg_s, 1, j_cur, npaths, l.passcolor, l.spill_main, c->d_counters, tune); } while (0)
-#define GD_LAUNCH_TRACE_ORD(T) do { if (c->ref_order) GD_LAUNCH_TRACE((T) | GD_REF_ORDER); else GD_LAUNCH_TRACE(T); } while (0)
-        if (c->exact_boxes) GD_LAUNCH_TRACE(GD_ALL_TYPES | GD_EXACT_BOXES);
-        else if (flat_only) GD_LAUNCH_TRACE_ORD(GD_FLAT_TYPES);
-        else if (round_only) GD_LAUNCH_TRACE_ORD(GD_ROUND_TYPES);
-        else GD_LAUNCH_TRACE_ORD(GD_ALL_TYPES);
-#undef GD_LAUNCH_TRACE_ORD
-#undef GD_LAUNCH_TRACE
+        if ((rr = with_types(kernel_choice(c, KC_TRACE), TraceTypes(), "k_trace", [&](auto T) {
+                GD_LEDGER(c, k_trace<false, T()>);
+                k_trace<false, T()><<<pgrid, BLOCK, 0, l.main>>>(sc, fr, *p, b, seg_c, seg_s, 1, j_cur, npaths, l.passcolor, l.spill_main, c->d_counters, tune);
+            })))
+            return rr;
         if (detail && (rr = end_timed(c, tt, l.main))) return rr;
         return 0;
     };
@@ -889,16 +919,7 @@ int launch_run(gpuart_hip_ctx *c, size_t first, size_t count) {
         HIP_TRY(hipGetLastError());
     }
     if ((r = end_timed(c, t, l.main))) return r;
-    // accumulate in pass order on the primary stream, then release the lane
-    HIP_TRY(hipEventRecord(l.ev_done, l.main));
-    HIP_TRY(hipStreamWaitEvent(c->stream, l.ev_done, 0));
-    GD_LEDGER(c, k_accumulate);
-    k_accumulate<<<dim3((unsigned)((c->plan.tile_pixels + 255) / 256)), 256, 0, c->stream>>>(c->d_accum, l.passcolor, c->plan.tile_pixels, b.batch);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(l.ev_free, c->stream));
-    if (gathers && (r = sort_tile_order(c, l))) return r;
-    l.used = true;
-    return 0;
+    return finish_run(c, l, gathers);
 }
 }  // namespace
 }  // extern "C++"
@@ -1114,28 +1135,19 @@ static RayQuery make_query(size_t n, uint32_t flags, const float us[4]) {
 static int launch_ray_query(gpuart_hip_ctx *c, const RayQuery &q, int source) {
     if (!c->d_query_cursor) HIP_TRY(hipMalloc(&c->d_query_cursor, 64));
     HIP_TRY(hipMemsetAsync(c->d_query_cursor, 0, sizeof(uint32_t), c->stream));
-    // chunks as the direct-lighting frame takes them (gpuart_hip_render_direct); a small batch gets the waves it can fill
-    TraceTuning tune = c->tune;
-    if (!c->chunk_from_env && q.n / ((size_t)c->direct_waves * 8) < 128) tune.chunk = 64;
+    // chunks as the direct-lighting frame takes them; a small batch gets the waves it can fill
+    const TraceTuning tune = direct_tuning(c, q.n);
     const dim3 grid(std::max<uint32_t>(1u, std::min<uint32_t>(c->direct_waves, (q.n + tune.chunk - 1) / tune.chunk)));
     const Scene sc = scene_of(c);
-    const bool flat_only = c->lean_kernels && !c->exact_boxes && (c->type_mask & ~(uint32_t)GD_FLAT_TYPES) == 0;
-    const bool round_only = c->lean_kernels && !c->exact_boxes && !flat_only && (c->type_mask & ~(uint32_t)GD_ROUND_TYPES) == 0;
-#define GD_LAUNCH_QUERY(T)                                                                                                       \
-    do {                                                                                                                         \
-        if (source == RQ_PIXELS) {                                                                                               \
-            GD_LEDGER(c, k_ray_query<T, RQ_PIXELS>);                                                                             \
-            k_ray_query<T, RQ_PIXELS><<<grid, BLOCK, 0, c->stream>>>(sc, c->frame, q, c->d_spill, c->d_query_cursor, tune);      \
-        } else {                                                                                                                 \
-            GD_LEDGER(c, k_ray_query<T, RQ_RAYS>);                                                                               \
-            k_ray_query<T, RQ_RAYS><<<grid, BLOCK, 0, c->stream>>>(sc, c->frame, q, c->d_spill, c->d_query_cursor, tune);        \
-        }                                                                                                                        \
-    } while (0)
-    if (c->exact_boxes) GD_LAUNCH_QUERY(GD_ALL_TYPES | GD_EXACT_BOXES);
-    else if (flat_only) GD_LAUNCH_QUERY(GD_FLAT_TYPES);
-    else if (round_only) GD_LAUNCH_QUERY(GD_ROUND_TYPES);
-    else GD_LAUNCH_QUERY(GD_ALL_TYPES);
-#undef GD_LAUNCH_QUERY
+    auto query = [&](auto T, auto S) {
+        GD_LEDGER(c, k_ray_query<T(), S()>);
+        k_ray_query<T(), S()><<<grid, BLOCK, 0, c->stream>>>(sc, c->frame, q, c->d_spill, c->d_query_cursor, tune);
+    };
+    if (int r = with_types(kernel_choice(c, KC_QUERY), LeafTypes(), "k_ray_query", [&](auto T) {
+            if (source == RQ_PIXELS) query(T, std::integral_constant<int, RQ_PIXELS>());
+            else query(T, std::integral_constant<int, RQ_RAYS>());
+        }))
+        return r;
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1685,7 +1697,7 @@ int gpuart_hip_gather_all_read(gpuart_hip_ctx *const *ctxs, int n, int which, fl
     return 0;
 }
 
-// ---- uploader hook: what gpuart_hip_upload_bvh decides about a tree, without a device (include/gpuart_hip.h) ----------
+// ---- the hooks that need no device (include/gpuart_hip_test.h): what gpuart_hip_upload_bvh decides about a tree -------------------
 #ifdef GPUART_HIP_TEST_HOOKS
 int gpuart_hip_test_tree_class(const float *quads, size_t nquads, uint32_t *flags) {
     if (!quads || !nquads || !flags) return fail(GPUART_HIP_ERR_ARG, "bad argument");
@@ -1700,9 +1712,7 @@ int gpuart_hip_test_tree_class(const float *quads, size_t nquads, uint32_t *flag
         return fail(GPUART_HIP_ERR_ARG, std::string("tree: ") + e.what());
     }
 }
-#endif
 
-#ifdef GPUART_HIP_TEST_HOOKS
 int gpuart_hip_test_tree_slack(const float *quads, size_t nquads, float *slack) {
     if (!quads || !nquads || !slack) return fail(GPUART_HIP_ERR_ARG, "bad argument");
     try {
@@ -1716,10 +1726,17 @@ int gpuart_hip_test_tree_slack(const float *quads, size_t nquads, float *slack) 
         return fail(GPUART_HIP_ERR_ARG, std::string("tree: ") + e.what());
     }
 }
-#endif
+
+// ---- kernel choice hook: the rule the launch sites take their instantiation from, asked without a device
+int gpuart_hip_test_kernel_choice(uint32_t type_mask, uint32_t exact_boxes, uint32_t ref_order, uint32_t lean_kernels, int mode, int entry,
+                                  uint32_t choice[3]) {
+    if (!choice || type_mask > 15 || mode < 0 || mode > 5 || entry < KC_DIRECT || entry > KC_QUERY) return fail(GPUART_HIP_ERR_ARG, "bad argument");
+    const int k = kernel_choice(type_mask, exact_boxes != 0, ref_order != 0, lean_kernels != 0, mode, entry);
+    choice[0] = (uint32_t)(k & (KC_COUNT - 1)); choice[1] = (k & KC_COUNT) ? 1u : 0u; choice[2] = (k & KC_REFWORK) ? 1u : 0u;
+    return 0;
+}
 
 // ---- run planner hook: the planner of the context, driven without a device (include/gpuart_hip.h) ---------------------
-#ifdef GPUART_HIP_TEST_HOOKS
 int gpuart_hip_test_planner(const uint32_t cfg[8], const uint32_t *ops, int n_ops, uint32_t *runs, int max_runs) {
     if (!cfg || (!ops && n_ops) || n_ops < 0 || (!runs && max_runs) || max_runs < 0) return fail(GPUART_HIP_ERR_ARG, "bad argument");
     RunPlanner p;

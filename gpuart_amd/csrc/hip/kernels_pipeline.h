@@ -314,6 +314,93 @@ __global__ void __launch_bounds__(BLOCK) k_gen(Frame f, gpuart_params P, SeedBat
 #ifndef GD_TRACE_WAVES_LEAN
 #define GD_TRACE_WAVES_LEAN 6  // the kernels without cone / sphere code fit 6 waves per SIMD (<= 80 VGPRs)
 #endif
+// ---- the persistent-lane loop of k_direct_persistent and k_ray_query (kernels_query.h), stated once ---------------------------------
+// A wave takes chunks of entries (pixel slots, queries) from a cursor, a lane that is done with its entry takes the next one, and once
+// the cursor is dry a wave that is down to 32 (16) entries carries each by a pair (quad) of lanes. The kernels keep the state a lane carries,
+// how it starts an entry, their thin_regroup call, trav_settle and the retire step. (k_trace's and k_run's loops have other exit rules.)
+/// Which entries of [0, n), n < SLOT_INVALID, a wave takes next; every member is wave-uniform (wave_value: scalar registers). The first
+/// chunk of every wave is static (chunk index = workgroup index); later chunks come from the shared cursor, which therefore starts
+/// behind the static ones: no atomic at all for small launches.
+struct ChunkCursor {
+    uint32_t next, end, static_end, n;
+    bool exhausted;
+    GD_FN ChunkCursor(uint32_t n_, uint32_t chunk)
+        : next(min(blockIdx.x * chunk, n_)), end(min((blockIdx.x + 1) * chunk, n_)), static_end(gridDim.x * chunk), n(n_), exhausted(false) {}
+    /// The idle lanes (`idle`: their ballot, not 0; `lane_idle`: this lane is one) take the next entries of the chunk, or of the next one from
+    /// `cursor`: the entry this lane takes, or SLOT_INVALID; `served`: every idle lane got one. Nothing left: sets `exhausted`, gives none.
+    GD_FN uint32_t take(unsigned long long idle, bool lane_idle, uint32_t *cursor, uint32_t chunk, bool &served) {
+        served = false;
+        if (next == end) {
+            if (static_end >= n) { exhausted = true; return SLOT_INVALID; }
+            uint32_t base = 0;
+            if (lane_id() == 0) base = atomicAdd(cursor, chunk);
+            base = wave_value(base) + static_end;
+            if (base >= n) { exhausted = true; return SLOT_INVALID; }
+            next = base;
+            end = min(base + chunk, n);
+        }
+        const uint32_t want = (uint32_t)__popcll(idle), got = min(want, end - next);
+        const uint32_t rank = (uint32_t)__popcll(idle & ((1ull << lane_id()) - 1));
+        const uint32_t entry = lane_idle && rank < got ? next + rank : SLOT_INVALID;
+        next += got;
+        served = got == want;
+        return entry;
+    }
+};
+
+/// Lanes per entry of a draining wave that still holds `left` entries. (A macro: thin_regroup divides by shifts because the compiler sees at
+/// every call that the width is 1, 2 or 4 — not through a function's return value, which changed thin_regroup's code in every kernel.)
+#define GD_THIN_WIDTH(left) ((left) <= BLOCK / 4 && GD_TRACE_THIN >= 4 ? 4u : (left) <= BLOCK / 2 ? 2u : 1u)
+
+/// Wide rounds: traverse until enough lanes have an answer (a lane without an entry is in state DONE). Leaves are tested once
+/// 1/leaf_share of the lanes that still walk wait at one (at most leaf_lanes); the wave goes back once refill_lanes lanes are done.
+/// `follow`: this lane's walk enters the nearer child first (NEAR); `stop()`: this lane, having just done a leaf step, needs no more.
+template <int TYPES, bool NEAR, class Stop>
+GD_FN void wide_rounds(const Scene &sc, const F3 &ro, const F3 &rd, const F3 &rdiv, Trav &t, TravStack &st, const TraceTuning &tune,
+                       bool follow, Stop stop) {
+    for (;;) {
+        if (t.state == TRAV_DESCEND) trav_step_box<false, GD_BOXES_OF(TYPES), NEAR>(sc, Ray{ro, rd}, rdiv, t, st, nullptr, follow);
+        unsigned long long at_leaf = __ballot((t.state & 1) != 0);  // the leaf states are the odd ones
+        unsigned long long descending = __ballot(t.state == TRAV_DESCEND);
+        const uint32_t waiting = (uint32_t)__popcll(at_leaf);
+        if (at_leaf && (waiting >= tune.leaf_lanes || tune.leaf_share * waiting >= waiting + (uint32_t)__popcll(descending))) {
+            if (t.state & 1) {
+                trav_step_leaf<false, false, TYPES, NEAR>(sc, Ray{ro, rd}, t, st, nullptr, follow);
+                if (stop()) t.state = TRAV_DONE;
+            }
+            descending = __ballot(t.state == TRAV_DESCEND);
+            at_leaf = __ballot((t.state & 1) != 0);
+        }
+        const unsigned long long busy = descending | at_leaf;
+        if (!busy) break;
+        if (64u - (uint32_t)__popcll(busy) >= tune.refill_lanes) break;
+    }
+}
+
+/// Thin rounds: the same with W lanes per entry (`sub`: this lane's place in its group; the cursor is dry: entries only ever finish). Lanes
+/// with an answer move their entry on, the others stand still meanwhile: once those (`holds`: an entry is here) are a fair share, it ends.
+template <int W, int TYPES, bool NEAR, class Stop>
+GD_FN void thin_rounds(const Scene &sc, const F3 &ro, const F3 &rd, const F3 &rdiv, Trav &t, TravStack &st, uint32_t sub, bool holds,
+                       const TraceTuning &tune, bool follow, Stop stop) {
+    constexpr unsigned long long LEAD = W == 4 ? 0x1111111111111111ull : 0x5555555555555555ull;
+    for (;;) {
+        if (t.state == TRAV_DESCEND) trav_step_box_thin<W, NEAR>(sc, ro, rd, rdiv, t, st, sub, follow);
+        const unsigned long long at_leaf = __ballot((t.state & 1) != 0) & LEAD;
+        unsigned long long busy = __ballot(t.state != TRAV_DONE) & LEAD;
+        const uint32_t waiting = (uint32_t)__popcll(at_leaf);
+        if (at_leaf && (W * waiting >= tune.leaf_lanes || tune.leaf_share * waiting >= (uint32_t)__popcll(busy))) {
+            if (t.state & 1) {
+                trav_step_leaf_thin<W, TYPES, NEAR>(sc, ro, rd, t, st, sub, follow);
+                if (stop()) t.state = TRAV_DONE;
+            }
+            busy = __ballot(t.state != TRAV_DONE) & LEAD;
+        }
+        if (!busy) break;
+        const uint32_t answered = (uint32_t)__popcll(__ballot(holds && t.state == TRAV_DONE) & LEAD);
+        if (2 * answered >= (uint32_t)__popcll(busy)) break;
+    }
+}
+
 template <bool COUNT, int TYPES>
 __global__ void __launch_bounds__(BLOCK, GD_LEAN_TYPES(TYPES) ? GD_TRACE_WAVES_LEAN : GD_TRACE_WAVES)
 k_trace(Scene sc, Frame f, gpuart_params P, PathBuffers b, int seg_c, int seg_s, int any_shadow, int j, int npaths, float4 *accum,
@@ -439,7 +526,7 @@ k_trace(Scene sc, Frame f, gpuart_params P, PathBuffers b, int seg_c, int seg_s,
         }
         if (THIN_OK && exhausted && M < (uint32_t)GD_TRACE_THIN) {
             const uint32_t left = (uint32_t)__popcll(flying);
-            const uint32_t to = left <= BLOCK / 4 && GD_TRACE_THIN >= 4 ? 4u : left <= BLOCK / 2 ? 2u : 1u;
+            const uint32_t to = GD_THIN_WIDTH(left);
             if (to > M) {
                 uint32_t sh = (shadow ? 1u : 0u) | (refwalk ? 2u : 0u);
                 // (the stack ring doubles as the scratch of the move: row 0 is copied first, and the table is read before that)
@@ -666,10 +753,7 @@ __global__ void __launch_bounds__(BLOCK, GD_DIRECT_WAVES) k_direct_persistent(Sc
     const float AMBIENT = 0.15f;
     const F3 sun = f3(P.sunDirAlt[0], P.sunDirAlt[1], P.sunDirAlt[2]);
     const F3 usc = f3(P.userSphere[0], P.userSphere[1], P.userSphere[2]);
-    const uint32_t n = n_slots;
-    const uint32_t static_end = gridDim.x * tune.chunk;
-    uint32_t chunk_next = min(blockIdx.x * tune.chunk, n), chunk_end = min((blockIdx.x + 1) * tune.chunk, n);  // wave-uniform
-    bool exhausted = false;                                                                                   // wave-uniform
+    ChunkCursor cc(n_slots, tune.chunk);
     uint32_t pixel = SLOT_INVALID;          // index into `out` of the pixel this lane works on
     int stage = DL_PRIMARY, bounce = 0;
     bool refwalk = false;                   // this lane's query is on its second walk, in the reference's order (trav_settle)
@@ -689,41 +773,29 @@ __global__ void __launch_bounds__(BLOCK, GD_DIRECT_WAVES) k_direct_persistent(Sc
     for (;;) {
         // ---- idle lanes take the next pixels
         unsigned long long idle = __ballot(pixel == SLOT_INVALID);
-        while (idle && !exhausted) {
-            if (chunk_next == chunk_end) {
-                if (static_end >= n) { exhausted = true; break; }
-                uint32_t base = 0;
-                if (lane_id() == 0) base = atomicAdd(cursor, tune.chunk);
-                base = wave_value(base) + static_end;
-                if (base >= n) { exhausted = true; break; }
-                chunk_next = base;
-                chunk_end = min(base + tune.chunk, n);
+        while (idle && !cc.exhausted) {
+            bool served;
+            const uint32_t slot = cc.take(idle, pixel == SLOT_INVALID, cursor, tune.chunk, served);
+            uint32_t lx, ly;
+            if (slot != SLOT_INVALID && slot_pixel(f, slot, lx, ly)) {
+                pixel = ly * f.tw + lx;
+                F3 rs0, rd0;
+                camera_ray(f, f.x0 + lx, frame_y(f, ly), rs0, rd0);
+                cw = f3(1, 1, 1); acc = f3(0, 0, 0);
+                stage = DL_PRIMARY; bounce = 0;
+                start_query(rs0, rd0);
             }
-            uint32_t want = (uint32_t)__popcll(idle), take = min(want, chunk_end - chunk_next);
-            uint32_t rank = (uint32_t)__popcll(idle & ((1ull << lane_id()) - 1));
-            if (pixel == SLOT_INVALID && rank < take) {
-                uint32_t lx, ly;
-                if (slot_pixel(f, chunk_next + rank, lx, ly)) {
-                    pixel = ly * f.tw + lx;
-                    F3 rs0, rd0;
-                    camera_ray(f, f.x0 + lx, frame_y(f, ly), rs0, rd0);
-                    cw = f3(1, 1, 1); acc = f3(0, 0, 0);
-                    stage = DL_PRIMARY; bounce = 0;
-                    start_query(rs0, rd0);
-                }
-            }
-            chunk_next += take;
             idle = __ballot(pixel == SLOT_INVALID);
-            if (take == want) break;
+            if (served) break;
         }
         const unsigned long long flying = __ballot(pixel != SLOT_INVALID && sub == 0);
         if (flying == 0) {
-            if (exhausted) break;
+            if (cc.exhausted) break;
             continue;
         }
-        if (THIN_OK && exhausted && M < (uint32_t)GD_TRACE_THIN) {
+        if (THIN_OK && cc.exhausted && M < (uint32_t)GD_TRACE_THIN) {
             const uint32_t left = (uint32_t)__popcll(flying);
-            const uint32_t to = left <= BLOCK / 4 && GD_TRACE_THIN >= 4 ? 4u : left <= BLOCK / 2 ? 2u : 1u;
+            const uint32_t to = GD_THIN_WIDTH(left);
             if (to > M) {
                 __shared__ uint32_t xfer[BLOCK];
                 uint32_t tag = (uint32_t)stage | ((uint32_t)bounce << 8) | (refwalk ? 1u << 16 : 0u);
@@ -739,51 +811,13 @@ __global__ void __launch_bounds__(BLOCK, GD_DIRECT_WAVES) k_direct_persistent(Sc
                 sub = (uint32_t)lane_id() & (M - 1);
             }
         }
-        if (THIN_OK && M > 1) {
-            // the loop below with M lanes per pixel (the cursor is dry: pixels only ever finish)
-            auto thin_rounds = [&](auto width) {
-                constexpr int W = decltype(width)::value;
-                constexpr unsigned long long LEAD = W == 4 ? 0x1111111111111111ull : 0x5555555555555555ull;
-                for (;;) {
-                    // (k_run's L1-warming loads for stacked children buy nothing here: 0.641 / 1.477 against 0.639 / 1.458 ms per 1080p / 4K frame)
-                    if (t.state == TRAV_DESCEND) trav_step_box_thin<W, NEAR>(sc, ro, rd, rdiv, t, st, sub, stage != DL_SUN && !refwalk);
-                    const unsigned long long at_leaf = __ballot((t.state & 1) != 0) & LEAD;
-                    unsigned long long busy = __ballot(t.state != TRAV_DONE) & LEAD;
-                    const uint32_t waiting = (uint32_t)__popcll(at_leaf);
-                    if (at_leaf && (W * waiting >= tune.leaf_lanes || tune.leaf_share * waiting >= (uint32_t)__popcll(busy))) {
-                        if (t.state & 1) {
-                            trav_step_leaf_thin<W, TYPES, NEAR>(sc, ro, rd, t, st, sub, stage != DL_SUN && !refwalk);
-                            if (stage == DL_SUN && t.hit_prim != GD_NO_PRIM) t.state = TRAV_DONE;  // only "anything hit?" is asked
-                        }
-                        busy = __ballot(t.state != TRAV_DONE) & LEAD;
-                    }
-                    if (!busy) break;
-                    // lanes with an answer move their pixel on (the others stand still meanwhile): once they are a fair share of the wave
-                    const uint32_t answered = (uint32_t)__popcll(__ballot(pixel != SLOT_INVALID && t.state == TRAV_DONE) & LEAD);
-                    if (2 * answered >= (uint32_t)__popcll(busy)) break;
-                }
-            };
-            if (M == 2) thin_rounds(std::integral_constant<int, 2>());
-            else thin_rounds(std::integral_constant<int, 4>());
-        } else
-        // ---- traverse until enough lanes have an answer (a lane without a pixel is in state DONE)
-        for (;;) {
-            if (t.state == TRAV_DESCEND) trav_step_box<false, GD_BOXES_OF(TYPES), NEAR>(sc, Ray{ro, rd}, rdiv, t, st, nullptr, stage != DL_SUN && !refwalk);
-            unsigned long long at_leaf = __ballot((t.state & 1) != 0);
-            unsigned long long descending = __ballot(t.state == TRAV_DESCEND);
-            const uint32_t waiting = (uint32_t)__popcll(at_leaf);
-            if (at_leaf && (waiting >= tune.leaf_lanes || tune.leaf_share * waiting >= waiting + (uint32_t)__popcll(descending))) {
-                if (t.state & 1) {
-                    trav_step_leaf<false, false, TYPES, NEAR>(sc, Ray{ro, rd}, t, st, nullptr, stage != DL_SUN && !refwalk);
-                    if (stage == DL_SUN && t.hit_prim != GD_NO_PRIM) t.state = TRAV_DONE;  // only "anything hit?" is asked
-                }
-                descending = __ballot(t.state == TRAV_DESCEND);
-                at_leaf = __ballot((t.state & 1) != 0);
-            }
-            unsigned long long busy = descending | at_leaf;
-            if (!busy) break;
-            if (64u - (uint32_t)__popcll(busy) >= tune.refill_lanes) break;
-        }
+        // ---- traverse until enough lanes have an answer: a Sun-shadow query keeps the reference's order and only asks "anything hit?"
+        // (k_run's L1-warming loads buy nothing in the thin rounds here: 0.641 / 1.477 against 0.639 / 1.458 ms per 1080p / 4K frame)
+        const bool follow = stage != DL_SUN && !refwalk;
+        auto stop = [&] { return stage == DL_SUN && t.hit_prim != GD_NO_PRIM; };
+        if (THIN_OK && M == 2) thin_rounds<2, TYPES, NEAR>(sc, ro, rd, rdiv, t, st, sub, pixel != SLOT_INVALID, tune, follow, stop);
+        else if (THIN_OK && M > 1) thin_rounds<4, TYPES, NEAR>(sc, ro, rd, rdiv, t, st, sub, pixel != SLOT_INVALID, tune, follow, stop);
+        else wide_rounds<TYPES, NEAR>(sc, ro, rd, rdiv, t, st, tune, follow, stop);
         // ---- a finished nearest-first query that cannot vouch for its answer walks again, in the reference's order (device_scene.h)
         if (NEAR && pixel != SLOT_INVALID && t.state == TRAV_DONE && trav_settle<NEAR>(t, stage != DL_SUN && !refwalk)) {
             refwalk = true;

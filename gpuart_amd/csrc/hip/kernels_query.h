@@ -27,9 +27,9 @@ GD_FN void rq_store(const RayQuery &q, uint32_t i, float pos, F3 p, F3 n, int ty
     if (q.prims) q.prims[i] = prim;
 }
 
-/// Persistent lanes over a batch of ray queries, modelled on k_direct_persistent: a wave takes chunks of queries from a cursor, a lane
-/// that has its answer stores it and takes the next query, and once the cursor is dry a wave that is down to 32 (16) rays carries each
-/// by a pair (quad) of lanes. Every walk is the reference's closest-hit walk (lower child first, pruning on entry > closest: the order
+/// Persistent lanes over a batch of ray queries, on the loop it shares with k_direct_persistent (kernels_pipeline.h: ChunkCursor,
+/// wide_rounds, thin_rounds): a wave takes chunks of queries from a cursor, a lane that has its answer stores it and takes the next query,
+/// and once the cursor is dry a wave that is down to 32 (16) rays carries each by a pair (quad) of lanes. Every walk is the reference's closest-hit walk (lower child first, pruning on entry > closest: the order
 /// of shaders/bvh_intersection.glsl:405-441), whatever order the context's render kernels use. An occlusion query walks the same walk
 /// and stops at the first accepted hit whose parameter is below tmax: a prefix of the walk finds such a hit if and only if the minimum
 /// over all primitives the full walk tests — the reference's closest hit — is below tmax.
@@ -42,10 +42,7 @@ __global__ void __launch_bounds__(BLOCK, GD_DIRECT_WAVES) k_ray_query(Scene sc, 
     constexpr bool THIN_OK = GD_TRACE_THIN > 1 && GD_BOXES_OF(TYPES) == GD_BOXES_FAST;
     const bool occl = SOURCE == RQ_RAYS && q.occlusion != 0;  // wave-uniform
     uint32_t M = 1, sub = 0;                                  // M wave-uniform
-    const uint32_t n = q.n;
-    const uint32_t static_end = gridDim.x * tune.chunk;
-    uint32_t chunk_next = min(blockIdx.x * tune.chunk, n), chunk_end = min((blockIdx.x + 1) * tune.chunk, n);  // wave-uniform
-    bool exhausted = false;                                                                                   // wave-uniform
+    ChunkCursor cc(q.n, tune.chunk);
     uint32_t ray = SLOT_INVALID;  // the query this lane works on
     float tmax = __builtin_inff();
     F3 ro = f3(0, 0, 0), rd = f3(1, 0, 0), rdiv = f3(1, 1, 1);
@@ -54,20 +51,10 @@ __global__ void __launch_bounds__(BLOCK, GD_DIRECT_WAVES) k_ray_query(Scene sc, 
     for (;;) {
         // ---- idle lanes take the next queries
         unsigned long long idle = __ballot(ray == SLOT_INVALID);
-        while (idle && !exhausted) {
-            if (chunk_next == chunk_end) {
-                if (static_end >= n) { exhausted = true; break; }
-                uint32_t base = 0;
-                if (lane_id() == 0) base = atomicAdd(cursor, tune.chunk);
-                base = wave_value(base) + static_end;
-                if (base >= n) { exhausted = true; break; }
-                chunk_next = base;
-                chunk_end = min(base + tune.chunk, n);
-            }
-            const uint32_t want = (uint32_t)__popcll(idle), take = min(want, chunk_end - chunk_next);
-            const uint32_t rank = (uint32_t)__popcll(idle & ((1ull << lane_id()) - 1));
-            if (ray == SLOT_INVALID && rank < take) {
-                const uint32_t i = chunk_next + rank;
+        while (idle && !cc.exhausted) {
+            bool served;
+            const uint32_t i = cc.take(idle, ray == SLOT_INVALID, cursor, tune.chunk, served);
+            if (i != SLOT_INVALID) {
                 if (SOURCE == RQ_PIXELS) {
                     const uint2 px = q.xy[i];
                     camera_ray(f, px.x, px.y, ro, rd);
@@ -99,18 +86,17 @@ __global__ void __launch_bounds__(BLOCK, GD_DIRECT_WAVES) k_ray_query(Scene sc, 
                     trav_init<GD_BOXES_OF(TYPES)>(sc, Ray{ro, rd}, rdiv, t, st, nullptr, false);
                 }
             }
-            chunk_next += take;
             idle = __ballot(ray == SLOT_INVALID);
-            if (take == want) break;
+            if (served) break;
         }
         const unsigned long long flying = __ballot(ray != SLOT_INVALID && sub == 0);
         if (flying == 0) {
-            if (exhausted) break;
+            if (cc.exhausted) break;
             continue;
         }
-        if (THIN_OK && exhausted && M < (uint32_t)GD_TRACE_THIN) {
+        if (THIN_OK && cc.exhausted && M < (uint32_t)GD_TRACE_THIN) {
             const uint32_t left = (uint32_t)__popcll(flying);
-            const uint32_t to = left <= BLOCK / 4 && GD_TRACE_THIN >= 4 ? 4u : left <= BLOCK / 2 ? 2u : 1u;
+            const uint32_t to = GD_THIN_WIDTH(left);
             if (to > M) {
                 __shared__ uint32_t xfer[BLOCK];
                 uint32_t tm = __float_as_uint(tmax);
@@ -121,51 +107,12 @@ __global__ void __launch_bounds__(BLOCK, GD_DIRECT_WAVES) k_ray_query(Scene sc, 
                 sub = (uint32_t)lane_id() & (M - 1);
             }
         }
-        if (THIN_OK && M > 1) {
-            // the loop below with M lanes per ray (the cursor is dry: queries only ever finish)
-            auto thin_rounds = [&](auto width) {
-                constexpr int W = decltype(width)::value;
-                constexpr unsigned long long LEAD = W == 4 ? 0x1111111111111111ull : 0x5555555555555555ull;
-                for (;;) {
-                    if (t.state == TRAV_DESCEND) trav_step_box_thin<W, false>(sc, ro, rd, rdiv, t, st, sub, false);
-                    const unsigned long long at_leaf = __ballot((t.state & 1) != 0) & LEAD;
-                    unsigned long long busy = __ballot(t.state != TRAV_DONE) & LEAD;
-                    const uint32_t waiting = (uint32_t)__popcll(at_leaf);
-                    if (at_leaf && (W * waiting >= tune.leaf_lanes || tune.leaf_share * waiting >= (uint32_t)__popcll(busy))) {
-                        if (t.state & 1) {
-                            trav_step_leaf_thin<W, TYPES, false>(sc, ro, rd, t, st, sub, false);
-                            if (occl && t.hit_prim != GD_NO_PRIM && t.closest < tmax) t.state = TRAV_DONE;
-                        }
-                        busy = __ballot(t.state != TRAV_DONE) & LEAD;
-                    }
-                    if (!busy) break;
-                    const uint32_t answered = (uint32_t)__popcll(__ballot(ray != SLOT_INVALID && t.state == TRAV_DONE) & LEAD);
-                    if (2 * answered >= (uint32_t)__popcll(busy)) break;
-                }
-            };
-            if (M == 2) thin_rounds(std::integral_constant<int, 2>());
-            else thin_rounds(std::integral_constant<int, 4>());
-        } else
-        // ---- traverse until enough lanes have an answer (a lane without a query is in state DONE)
-        for (;;) {
-            if (t.state == TRAV_DESCEND) trav_step_box<false, GD_BOXES_OF(TYPES), false>(sc, Ray{ro, rd}, rdiv, t, st, nullptr, false);
-            unsigned long long at_leaf = __ballot((t.state & 1) != 0);
-            unsigned long long descending = __ballot(t.state == TRAV_DESCEND);
-            const uint32_t waiting = (uint32_t)__popcll(at_leaf);
-            if (at_leaf && (waiting >= tune.leaf_lanes || tune.leaf_share * waiting >= waiting + (uint32_t)__popcll(descending))) {
-                if (t.state & 1) {
-                    trav_step_leaf<false, false, TYPES, false>(sc, Ray{ro, rd}, t, st, nullptr, false);
-                    // occlusion: the first leaf after which the walk holds an accepted hit below tmax ends it (closest only decreases, so
-                    // this is the leaf that holds the first such hit of the walk)
-                    if (occl && t.hit_prim != GD_NO_PRIM && t.closest < tmax) t.state = TRAV_DONE;
-                }
-                descending = __ballot(t.state == TRAV_DESCEND);
-                at_leaf = __ballot((t.state & 1) != 0);
-            }
-            const unsigned long long busy = descending | at_leaf;
-            if (!busy) break;
-            if (64u - (uint32_t)__popcll(busy) >= tune.refill_lanes) break;
-        }
+        // ---- traverse until enough lanes have an answer, every walk in the reference's order. Occlusion: the first leaf after which the
+        // walk holds an accepted hit below tmax ends it (closest only decreases, so this is the leaf that holds the first such hit of the walk)
+        auto stop = [&] { return occl && t.hit_prim != GD_NO_PRIM && t.closest < tmax; };
+        if (THIN_OK && M == 2) thin_rounds<2, TYPES, false>(sc, ro, rd, rdiv, t, st, sub, ray != SLOT_INVALID, tune, false, stop);
+        else if (THIN_OK && M > 1) thin_rounds<4, TYPES, false>(sc, ro, rd, rdiv, t, st, sub, ray != SLOT_INVALID, tune, false, stop);
+        else wide_rounds<TYPES, false>(sc, ro, rd, rdiv, t, st, tune, false, stop);
         // ---- lanes with an answer store it and go idle
         if (ray != SLOT_INVALID && t.state == TRAV_DONE) {
             if (sub == 0) {

@@ -36,6 +36,15 @@ int gpuart_hip_test_bounded_call(uint32_t hold_ms, uint32_t timeout_ms, int mark
  * Returns the number of runs (which may exceed max_runs: only the first max_runs are stored), or a negative error. */
 int gpuart_hip_test_planner(const uint32_t cfg[8], const uint32_t *ops, int n_ops, uint32_t *runs, int max_runs);
 
+/* Which instantiation of the BVH-query kernels a launch runs (pure host code: needs no device and no context): the rule every launch
+ * site of the library takes its template arguments from (csrc/hip/gpuart_hip.hip kernel_choice), asked with a context's state as
+ * plain integers. type_mask (0..15), exact_boxes (bit 0 or 1 of gpuart_hip_test_tree_class set), ref_order (the tree is walked in the
+ * reference's order: gpuart_hip_scene_order 1), lean_kernels (GPUART_HIP_LEAN_KERNELS), mode (gpuart_hip_set_mode, 0..5) and entry:
+ * 0 k_direct_persistent (gpuart_hip_render_direct outside modes 1 and 2), 1 k_run, 2 k_trace, 3 k_ray_query (either source).
+ * choice[3] = { TYPES, k_run's COUNT, k_run's REFWORK } (the last two 0 for the other kernels). */
+int gpuart_hip_test_kernel_choice(uint32_t type_mask, uint32_t exact_boxes, uint32_t ref_order, uint32_t lean_kernels, int mode, int entry,
+                                  uint32_t choice[3]);
+
 /* What gpuart_hip_upload_bvh decides about a canonical compiled tree (pure host code: needs no device and no context): *flags =
  * bit 0: some box is irregular (min > max, NaN or infinite on an axis) — box tests take the reference's comparison form;
  * bit 1: some box does not bound what it holds by the reference's own formulas (a child outside its parent, a primitive outside its

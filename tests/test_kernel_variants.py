@@ -1,11 +1,13 @@
 """Every product kernel specialisation held to the oracle, with the launch ledger of the test build as evidence of which one ran.
 
 The device code is a few kernels compiled many times over: the host picks the instantiation from the tree's class (types present, exact
-boxes), the visiting order, the execution mode, GPUART_HIP_LEAN_KERNELS and, for queries, the ray source (csrc/hip/gpuart_hip.hip). A bug in
-one instantiation is invisible on every scene that does not select it. Each row of the matrix below is a (scene, entry point, setting)
-triple; it compares the output with the oracle bit for bit, and asserts that the kernels the ledger saw (Backend.launched,
-gpuart_hip_test_launches) are those `expected_kernels` — a restatement of the host's dispatch rules — names for the row. The CPU test
-checks that the rows together name every kernel of the product's code object, so a new instantiation without a row fails by name.
+boxes), the visiting order, the execution mode, GPUART_HIP_LEAN_KERNELS and, for queries, the ray source. The library states that rule
+once, `kernel_choice` in csrc/hip/gpuart_hip.hip, and one dispatcher there (`with_types`, with a list of the instantiations each kernel
+has) turns its answer into the launch. A bug in one instantiation is invisible on every scene that does not select it. Each row of the
+matrix below is a (scene, entry point, setting) triple; it compares the output with the oracle bit for bit, and asserts that the kernels
+the ledger saw (Backend.launched, gpuart_hip_test_launches) are those `expected_kernels` — a restatement of the host's rule — names for
+the row. The CPU tests check that the rows together name every kernel of the product's code object, so a new instantiation without a row
+fails by name, and that the restatement and the library's rule (gpuart_hip_test_kernel_choice: no device) agree on every input.
 """
 import os
 import zlib
@@ -190,6 +192,50 @@ def test_the_matrix_reaches_every_product_kernel(tmp_path):
     print("%d product kernels, %d matched by rows, exempt: %s\n  %s" % (len(product), len(required), sorted(EXEMPT), "\n  ".join(sorted(required))))
 
 
+def test_the_host_rule_and_its_restatement_agree(tmp_path):
+    """The library's kernel choice (B.kernel_choice: gpuart_hip_test_kernel_choice, pure host code) against `leaf_types` / `expected_kernels`
+    over every tree class (type mask 0-15 x regular / irregular / disorderly), visiting order, GPUART_HIP_LEAN_KERNELS, mode, launch site and
+    query source: wherever the restatement names a kernel of the launch site's family, the rule names the same one, and every answer is a
+    kernel of the product's code object. The quirks of the rule (mode 1: all types, never the order bit; mode 4: flat but no round variant;
+    no order bit on the direct frame and the queries) fail here by name if either side is tidied alone."""
+    from gpuart_amd import binding as B
+    co = _code_object(os.path.join(PRODUCT_DIR, "libgpuart_hip.so"), str(tmp_path))
+    product = set(_demangled(sorted(_kernel_metadata(co))))
+    tf = lambda v: "true" if v else "false"
+    checked = named = 0
+    for mask in range(16):
+        for kind in ("regular", "irregular", "disorderly"):
+            cls = dict(irregular=kind == "irregular", disorderly=kind == "disorderly", type_mask=mask)
+            for ref_order in (0, 1):
+                for lean in (0, 1):
+                    for mode in range(6):
+                        kw = dict(mode=mode, lean=bool(lean), nearest=not ref_order)
+                        for entry in B.KERNEL_ENTRIES:
+                            T, count, refwork = B.kernel_choice(mask, int(kind != "regular"), ref_order, lean, mode, entry)
+                            what = "%s, mask %d, ref_order %d, lean %d, mode %d, %s" % (kind, mask, ref_order, lean, mode, entry)
+                            assert (count, refwork) == (entry == "run" and mode in (1, 4), entry == "run" and mode == 1), what
+                            if entry == "direct":
+                                got = ["k_direct_persistent<%d>" % T]
+                                want = [set.union(*expected_kernels("direct", cls, **kw)[0])] if mode not in (1, 2) else [None]   # k_direct<.> there
+                                assert T == leaf_types(cls, bool(lean)), what
+                            elif entry == "query":
+                                got = ["k_ray_query<%d, %d>" % (T, src) for src in (RQ_RAYS, RQ_PIXELS)]
+                                want = [expected_kernels("query", cls, source=src, **kw)[0][0] for src in (RQ_RAYS, RQ_PIXELS)]
+                            else:
+                                got = ["k_run<%s, %s, %d>" % (tf(count), tf(refwork), T) if entry == "run" else "k_trace<false, %d>" % T]
+                                family = got[0].split("<")[0] + "<"
+                                alts = expected_kernels("pt", cls, **kw)[0]
+                                want = [next((a for a in alts if any(k.startswith(family) for k in a)), None)]   # None: the mode never launches it
+                            for g, w in zip(got, want):
+                                assert g in product, "%s: the rule names %s, which the product does not have" % (what, g)
+                                checked += 1
+                                if w is not None:
+                                    family = g.split("<")[0] + "<"
+                                    assert {k for k in w if k.startswith(family)} == {g}, "%s: the rule names %s, the restatement %s" % (what, g, sorted(w))
+                                    named += 1
+    assert checked == 16 * 3 * 2 * 2 * 6 * 5 and named >= checked * 2 // 3, (checked, named)
+
+
 def test_every_exemption_names_an_existing_test():
     import importlib
     for kernel, test_id in EXEMPT.items():
@@ -222,7 +268,7 @@ def O():
     return oracle
 
 
-def scene_setup(O, tree):
+def scene_setup(O, tree, W=W, H=H):
     """Camera looking at the tree's root box from the front, a user sphere beside its centre, the reference's sun; (cam, params, lo, hi, us)."""
     lo, hi = tree[0, :3].astype(np.float64), tree[1, :3].astype(np.float64)
     if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (lo <= hi).all()):
@@ -483,5 +529,56 @@ def test_host_staging_with_a_ragged_last_chunk(B, O, monkeypatch, record_propert
         got = names_of(b.launched())
         record_property("kernels", sorted(got))
         assert got == expected_kernels("query", cls, source=RQ_RAYS)[0][0], sorted(got)
+    finally:
+        b.close()
+
+
+CURSOR_W, CURSOR_H = 160, 120   # 19 200 pixel slots: beyond three static chunks of 16 per wave at one wave per CU
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("sc", ["scene_p", "box", "wild"])   # round, all types, exact boxes (no thin path: the cursor is still there)
+def test_waves_take_chunks_from_the_shared_cursor(B, O, sc, monkeypatch, record_property):
+    """The chunk cursor the direct frame and the ray queries share (kernels_pipeline.h ChunkCursor), behind its static part: the matrix
+    above never gets there — with the default grid of 16 waves per CU every wave's static first chunk covers its 40x24 frames and 3000
+    queries. Here the knobs are at their minima (one wave per CU, chunks of 16), so the static part is CUs x 16 entries and a 160x120
+    frame, 19 200 + 37 rays and a pick of every pixel take most of their chunks through the atomic cursor. Each against the oracle, bit
+    for bit, and the ledger names the instantiations `expected_kernels` names."""
+    import torch
+    _clean_env(monkeypatch, {"GPUART_HIP_DIRECT_WAVES_PER_CU": "1", "GPUART_HIP_CHUNK": "16"})
+    n_rays = CURSOR_W * CURSOR_H + 37
+    static = torch.cuda.get_device_properties(0).multi_processor_count * 16
+    assert min(n_rays, CURSOR_W * CURSOR_H) >= 3 * static, "%d entries do not reach past the static chunks (%d) of this device" % (CURSOR_W * CURSOR_H, static)
+    tree = tree_of(sc)
+    cls = B.tree_class(tree)
+    c, P, lo, hi, us = scene_setup(O, tree, CURSOR_W, CURSOR_H)
+    rng = np.random.default_rng(zlib.crc32(sc.encode()))
+    b = B.Backend(0)
+    try:
+        b.resize(CURSOR_W, CURSOR_H); b.upload_bvh(tree); b.set_camera(c)
+        b.render_direct(to_params(B, P))
+        exp, _ = O.render_direct(tree, c, CURSOR_W, CURSOR_H, P)
+        assert_bits(b.read(0)[..., :3].reshape(-1, 3), exp[..., :3].reshape(-1, 3), "direct frame, " + sc)
+        rs, rd = random_rays(rng, n_rays, lo, hi)
+        rays = rays8(rs, rd)
+        exp, ush = oracle_records(O, tree, rays, us)
+        rays[:, 3] = tmax_set(rng, exp[:, 0].copy())
+        hits, prims = b.trace_rays(rays, user_sphere=us, want_prims=True)
+        assert_same_bits(words(hits), exp, "closest hit, " + sc)
+        assert ((prims == -2) == ush).all() and ((prims == -1) == (hits["type"] == -1)).all(), sc
+        occ = b.trace_rays(rays, occlusion=True, user_sphere=us)
+        want = (exp[:, 0] > 0) & (exp[:, 0] < rays[:, 3])
+        got = occ["pos"] > 0
+        assert (got == want).all(), "occlusion, %s: %d of %d answers differ from the oracle's closest hit" % (sc, int((got != want).sum()), n_rays)
+        assert (occ["pos"][got] < rays[got, 3]).all() and (occ["type"][~got] == -1).all(), sc
+        crs, crd = O.cam_rays(c, CURSOR_W, CURSOR_H)
+        crays = rays8(crs.reshape(-1, 4)[:, :3], crd.reshape(-1, 4)[:, :3])
+        y, x = np.divmod(np.arange(CURSOR_W * CURSOR_H), CURSOR_W)
+        pexp, _ = oracle_records(O, tree, crays, us)
+        assert_same_bits(words(b.pick(np.stack([x, y], 1), user_sphere=us)), pexp, "pick, " + sc)
+        got = names_of(b.launched())
+        record_property("kernels", sorted(got))
+        want = set.union(*[expected_kernels(e, cls, source=src)[0][0] for e, src in (("direct", 0), ("query", RQ_RAYS), ("query", RQ_PIXELS))])
+        assert got == want, (sorted(got), sorted(want))
     finally:
         b.close()
