@@ -151,6 +151,8 @@ struct gpuart_hip_ctx {
     uint32_t packet_max_prims = 1u << 19;  ///< GPUART_HIP_PACKET_MAX_PRIMS: ... and with at most this many primitives. The lanes of a packet follow
                                            ///< each other while a pixel block sees few primitives: the 871 200-triangle mesh at 1080p ran 2 % SLOWER
                                            ///< with packets, the 100 352-triangle one 7 % faster (profiles/r07/ab_runs.txt; sizes between: not measured)
+    uint32_t gen_walk = 1;        ///< GPUART_HIP_GEN_WALK (default 1): where the camera rays' launch would walk packets and a later k_trace launch follows,
+                                  ///< k_gen walks the camera rays it generates and that launch is not made (launch_run); 0 — always the separate launch
     uint32_t exact_boxes = 0;     ///< the uploaded tree holds an irregular box, or a box that does not bound what it holds (converter.h):
                                   ///< box tests take the comparison form and every walk keeps the reference's order
     uint32_t max_depth = 0;
@@ -520,6 +522,7 @@ int gpuart_hip_create(int device, gpuart_hip_ctx **out) {
     c->quick_boxes = env_u32("GPUART_HIP_QUICK_BOXES", 1, 0, 1);
     c->packet = env_u32("GPUART_HIP_PACKET", 2, 0, 2);
     c->packet_max_prims = env_u32("GPUART_HIP_PACKET_MAX_PRIMS", 1u << 19, 0, 0xffffffffu);
+    c->gen_walk = env_u32("GPUART_HIP_GEN_WALK", 1, 0, 1);
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return fail(GPUART_HIP_ERR_DEVICE, "hipStreamCreate failed"); }
     c->lanes.resize(env_u32("GPUART_HIP_PASSES_IN_FLIGHT", 8, 1, 32));
     c->plan.lanes_total = (uint32_t)c->lanes.size();
@@ -885,16 +888,22 @@ int launch_run(gpuart_hip_ctx *c, size_t first, size_t count) {
     if ((r = run_frame(c, fr, gathers, false))) return r;  // (an order set through gpuart_hip_test_tile_order applies here too)
     if (l.used) HIP_TRY(hipStreamWaitEvent(l.main, l.ev_free, 0));  // the lane's previous pass has been accumulated
     if ((r = begin_timed(c, t, 0, l.main))) return r;
+    // packet walks (GPUART_HIP_PACKET; the GD_REF_ORDER kernels only): the camera rays' launch, the Sun-shadow queries of segment 0
+    const int trace_choice = kernel_choice(c, KC_TRACE);
+    const uint32_t packet = c->n_prims <= c->packet_max_prims ? c->packet : 0u;
+    // k_gen walks the camera rays itself (GPUART_HIP_GEN_WALK) exactly where their launch would walk them as packets — the knob, the tree's
+    // size, a fast-box kernel in the reference's order — and a later k_trace launch follows in the run; then trace(0, -1) is not launched
+    const bool gen_walk = c->gen_walk && packet >= 1 && (trace_choice & GD_REF_ORDER) && !(trace_choice & GD_EXACT_BOXES) && nseg > 0 &&
+                          (nseg >= 2 || p->sunEnabled == 1);
+    const dim3 wgrid(std::max<uint32_t>(1u, std::min<uint32_t>(c->grid_waves, (b.n_slots * b.batch + c->tune.chunk - 1) / c->tune.chunk)));  // (l.spill_main holds grid_waves columns at least)
     // one BVH-query launch: closest-hit queries of segment seg_c and / or Sun-shadow queries of segment seg_s
     auto trace = [&](int seg_c, int seg_s) -> int {
         TimedLaunch tt;
         int rr;
         if (detail && (rr = begin_timed(c, tt, 1, l.main))) return rr;
-        // packet walks (GPUART_HIP_PACKET; the GD_REF_ORDER kernels only): the camera rays' launch, the Sun-shadow queries of segment 0
         TraceTuning tune = c->tune;
-        const uint32_t packet = c->n_prims <= c->packet_max_prims ? c->packet : 0u;
         tune.packet = (packet >= 1 && seg_c == 0) ? 1u : (packet >= 2 && seg_s == 0) ? 2u : 0u;
-        if ((rr = with_types(kernel_choice(c, KC_TRACE), TraceTypes(), "k_trace", [&](auto T) {
+        if ((rr = with_types(trace_choice, TraceTypes(), "k_trace", [&](auto T) {
                 GD_LEDGER(c, k_trace<false, T()>);
                 k_trace<false, T()><<<pgrid, BLOCK, 0, l.main>>>(sc, fr, *p, b, seg_c, seg_s, 1, j_cur, npaths, l.passcolor, l.spill_main, c->d_counters, tune);
             })))
@@ -907,8 +916,15 @@ int launch_run(gpuart_hip_ctx *c, size_t first, size_t count) {
         HIP_TRY(hipMemsetAsync(b.counters, 0, 4 * ((size_t)nseg + 1) * sizeof(uint32_t), l.main));
         if (c->tune.xcd_queues) HIP_TRY(hipMemsetAsync(b.xcd_cursors, 0, 16 * ((size_t)nseg + 1) * sizeof(uint32_t), l.main));
         GD_LEDGER(c, k_gen);
-        k_gen<<<sgrid, BLOCK, 0, l.main>>>(fr, *p, seeds, j, npaths, b, l.passcolor);
-        if (nseg && (r = trace(0, -1))) return r;
+        if (gen_walk) {  // in the per-launch bracket the camera rays' launch had
+            TimedLaunch tt;
+            if (detail && (r = begin_timed(c, tt, 1, l.main))) return r;
+            k_gen<<<wgrid, BLOCK, 0, l.main>>>(sc, fr, *p, seeds, j, npaths, b, l.passcolor, l.spill_main, c->tune.chunk, trace_choice);
+            if (detail && (r = end_timed(c, tt, l.main))) return r;
+        } else {
+            k_gen<<<sgrid, BLOCK, 0, l.main>>>(sc, fr, *p, seeds, j, npaths, b, l.passcolor, l.spill_main, c->tune.chunk, 0);
+            if (nseg && (r = trace(0, -1))) return r;
+        }
         for (uint32_t seg = 0; seg < nseg; seg++) {
             GD_LEDGER(c, k_shade<false>);
             k_shade<false><<<sgrid, BLOCK, 0, l.main>>>(sc, fr, *p, seeds, b, (int)seg, (int)nseg, j, npaths, l.passcolor, c->d_counters);

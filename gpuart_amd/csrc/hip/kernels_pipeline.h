@@ -265,33 +265,6 @@ __global__ void k_accumulate(float4 *__restrict__ accum, const float4 *__restric
     }
 }
 
-// ---- wavefront stage 0: first ray of path j of every pixel (path_tracing.glsl:141-175) ---------------
-__global__ void __launch_bounds__(BLOCK) k_gen(Frame f, gpuart_params P, SeedBatch seeds, int j, int npaths, PathBuffers b,
-                                               float4 *accum) {
-    const bool no_segments = !(P.maxSegments > 0 && 1.0f > P.minWeight);
-    const uint32_t total = b.n_slots * b.batch;
-    for (uint32_t slot = blockIdx.x * BLOCK + threadIdx.x; slot < total; slot += gridDim.x * BLOCK) {
-        uint32_t lx, ly;
-        bool valid = slot_pixel(f, slot_pixel_slot(b, slot), lx, ly);
-        const float4 seed = seeds.seed[slot_pass(b, slot)];
-        uint32_t q = SLOT_INVALID;
-        if (valid) {
-            F3 rs0, rd0, rs, rd;
-            camera_ray(f, f.x0 + lx, frame_y(f, ly), rs0, rd0);
-            if (no_segments) {  // the GLSL loop body never runs: i == 0 and no user-sphere hit
-                path_commit(f, b, accum, slot, j, npaths, path_finish(P, rd0, 0, false, false, f3(0, 0, 0)));
-            } else {
-                path_begin(P, seed, j, rs0, rd0, rs, rd);
-                b.ray_o[slot] = make_float4(rs.x, rs.y, rs.z, 0);
-                b.ray_d[slot] = make_float4(rd.x, rd.y, rd.z, 0);
-                q = slot;  // (colorWeight = 1 and pathColor = 0 are not stored: k_shade knows them for segment 0)
-            }
-        }
-        b.queue[0][slot] = q;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) b.counters[0] = no_segments ? 0u : total;
-}
-
 // ---- wavefront stage 1/3: BVH queries, persistent waves with lane refill ----------------------------------
 // One launch serves two queues at once: the closest-hit queries of segment `seg_c` (slots of queue[seg_c&1]; result ->
 // hit[slot]) and the Sun-shadow queries of segment `seg_s` (slots of shadow_queue; they apply the Sun term and, for
@@ -399,6 +372,70 @@ GD_FN void thin_rounds(const Scene &sc, const F3 &ro, const F3 &rd, const F3 &rd
         const uint32_t answered = (uint32_t)__popcll(__ballot(holds && t.state == TRAV_DONE) & LEAD);
         if (2 * answered >= (uint32_t)__popcll(busy)) break;
     }
+}
+
+// ---- wavefront stage 0: first ray of path j of every pixel (path_tracing.glsl:141-175) ---------------
+// `walk` == 0: a streaming pass that stores every path's first ray and the identity queue of segment 0; k_trace(0, -1) walks them.
+// `walk` != 0 (the host's GPUART_HIP_GEN_WALK; the GD_REF_ORDER fast-box choice `kernel_choice` makes for k_trace): the wave that computes
+// the rays of 64 consecutive path slots — one camera packet of k_trace — also walks them, from its registers: what take_query does for a
+// closest-hit query in the reference's order, then trav_packet, then hit[slot]. No k_trace(0, -1) follows. The same device functions on
+// the same values in the same order: the results are those of the separate launch bit for bit. The ray and queue[0] are stored as
+// before (k_shade(0) reads them); nothing waits for the stores. Packets differ widely in length (sky against mesh), so the waves take
+// chunks from a cursor (ChunkCursor; counters[1], which no other launch of such a run uses). The grid is at most the waves `spill` was
+// sized for.
+__global__ void __launch_bounds__(BLOCK) k_gen(Scene sc, Frame f, gpuart_params P, SeedBatch seeds, int j, int npaths, PathBuffers b,
+                                               float4 *accum, uint4 *spill, uint32_t chunk, int walk) {
+    __shared__ uint2 ring_a[GD_RING * BLOCK];
+    __shared__ float ring_b[GD_RING * BLOCK];
+    const bool no_segments = !(P.maxSegments > 0 && 1.0f > P.minWeight);
+    const uint32_t total = b.n_slots * b.batch;
+    // the first ray of path slot `slot` (a padding slot of a ragged edge tile: none); true: the path has a segment 0 to trace
+    auto first_ray = [&](uint32_t slot, F3 &rs, F3 &rd) {
+        uint32_t lx, ly;
+        bool valid = slot_pixel(f, slot_pixel_slot(b, slot), lx, ly);
+        const float4 seed = seeds.seed[slot_pass(b, slot)];
+        uint32_t q = SLOT_INVALID;
+        if (valid) {
+            F3 rs0, rd0;
+            camera_ray(f, f.x0 + lx, frame_y(f, ly), rs0, rd0);
+            if (no_segments) {  // the GLSL loop body never runs: i == 0 and no user-sphere hit
+                path_commit(f, b, accum, slot, j, npaths, path_finish(P, rd0, 0, false, false, f3(0, 0, 0)));
+            } else {
+                path_begin(P, seed, j, rs0, rd0, rs, rd);
+                b.ray_o[slot] = make_float4(rs.x, rs.y, rs.z, 0);
+                b.ray_d[slot] = make_float4(rd.x, rd.y, rd.z, 0);
+                q = slot;  // (colorWeight = 1 and pathColor = 0 are not stored: k_shade knows them for segment 0)
+            }
+        }
+        b.queue[0][slot] = q;
+        return q != SLOT_INVALID;
+    };
+    if (walk == 0) {
+        for (uint32_t slot = blockIdx.x * BLOCK + threadIdx.x; slot < total; slot += gridDim.x * BLOCK) {
+            F3 rs, rd;
+            first_ray(slot, rs, rd);
+        }
+    } else {
+        TravStack st = make_stack(ring_a, ring_b, spill, gridDim.x * BLOCK);
+        ChunkCursor cur(total, chunk);
+        for (;;) {
+            bool served;
+            const uint32_t slot = cur.take(~0ull, true, &b.counters[1], chunk, served);  // the next (up to) 64 slots of the chunk
+            if (cur.exhausted) break;
+            F3 ro = f3(0, 0, 0), rd = f3(1, 0, 0), rdiv = f3(1, 1, 1);
+            Trav t; t.state = TRAV_DONE; t.closest = 0; t.hit_prim = GD_NO_PRIM; t.node = 0; t.entry = 0; t.second = 0;
+            const bool query = slot != SLOT_INVALID && first_ray(slot, ro, rd);
+            if (query) {  // (k_trace's take_query)
+                rdiv = f3(1 / rd.x, 1 / rd.y, 1 / rd.z);
+                trav_init<GD_BOXES_FAST>(sc, Ray{ro, rd}, rdiv, t, st, nullptr, false);
+            }
+            if (walk == (GD_FLAT_TYPES | GD_REF_ORDER)) trav_packet<GD_FLAT_TYPES | GD_REF_ORDER>(sc, ro, rd, rdiv, t, st, false);
+            else if (walk == (GD_ROUND_TYPES | GD_REF_ORDER)) trav_packet<GD_ROUND_TYPES | GD_REF_ORDER>(sc, ro, rd, rdiv, t, st, false);
+            else trav_packet<GD_ALL_TYPES | GD_REF_ORDER>(sc, ro, rd, rdiv, t, st, false);
+            if (query) b.hit[slot] = make_uint2(__float_as_uint(t.closest), t.hit_prim);
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) b.counters[0] = no_segments ? 0u : total;
 }
 
 template <bool COUNT, int TYPES>
