@@ -116,9 +116,21 @@ class ConvergeSummary(C.Structure):
                     batches=self.batches, total=self.total)
 
 
+class AdaptiveSummary(C.Structure):
+    """gpuart_adaptive_summary (include/gpuart_adaptive.h): what a select says about the frame and its blocks."""
+    _fields_ = [("pixels", C.c_uint64), ("above", C.c_uint64), ("non_finite", C.c_uint64), ("paths_sum", C.c_uint64), ("blocks", C.c_uint32),
+                ("active_blocks", C.c_uint32), ("paths_min", C.c_uint32), ("paths_max", C.c_uint32), ("max_error", C.c_float),
+                ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return dict(pixels=self.pixels, above=self.above, non_finite=self.non_finite, paths_sum=self.paths_sum, blocks=self.blocks,
+                    active_blocks=self.active_blocks, paths_min=self.paths_min, paths_max=self.paths_max, max_error=float(self.max_error))
+
+
 CONVERGE_MAX_PATHS = 1 << 24    # GPUART_CONVERGE_MAX_PATHS
 CONVERGE_DEFAULT_BATCH = 64     # GPUART_CONVERGE_DEFAULT_BATCH
 CONVERGE_DEFAULT_FLOOR = 1.0 / 256   # one step of an 8-bit output (gpuart_cli --until-floor)
+ADAPTIVE_DEFAULT_MIN_PATHS = 8   # GPUART_ADAPTIVE_DEFAULT_MIN_PATHS (gpuart_cli --adaptive-min)
 
 
 def _user_sphere(us):
@@ -206,6 +218,11 @@ def converge_lib():
 def refine_lib():
     """libgpuart_refine.so; raises NativeLibraryMissing if it has not been built (no fallback)."""
     return _image_lib("refine")
+
+
+def adaptive_lib():
+    """libgpuart_adaptive.so; raises NativeLibraryMissing if it has not been built (no fallback)."""
+    return _image_lib("adaptive")
 
 
 def host_lib():
@@ -578,6 +595,31 @@ class Backend:
 
     def export(self, which, device_ptr, divide_by=1.0):
         self._chk(self.L.gpuart_hip_export(self.ctx, C.c_int(which), C.c_void_p(device_ptr), C.c_float(divide_by)))
+
+    def n_blocks(self):
+        """8x8 blocks of the tile, row-major: what an active list indexes and the block counts have one word for."""
+        _, _, tw, th = self.tile
+        return ((tw + 7) // 8) * ((th + 7) // 8)
+
+    def set_active_blocks(self, blocks):
+        """The blocks the passes to come render (gpuart_hip_set_active_blocks): a strictly ascending sequence of block indices, possibly
+        empty; None: every block again."""
+        if blocks is None:
+            self._chk(self.L.gpuart_hip_set_active_blocks(self.ctx, None, C.c_size_t(0)))
+            return
+        b = np.ascontiguousarray(blocks, np.uint32).reshape(-1)
+        keep = b if b.size else np.zeros(1, np.uint32)   # (an empty list is a non-NULL pointer with n = 0)
+        self._chk(self.L.gpuart_hip_set_active_blocks(self.ctx, keep.ctypes.data_as(C.c_void_p), C.c_size_t(b.size)))
+
+    def block_paths(self, device_ptr=None):
+        """Paths per pixel accumulated into each block since the last pt_reset: a uint32 array (gpuart_hip_read_block_paths), or, given a
+        device pointer, exported there on the context's stream (gpuart_hip_export_block_paths; finish() before use)."""
+        if device_ptr is not None:
+            self._chk(self.L.gpuart_hip_export_block_paths(self.ctx, C.c_void_p(device_ptr)))
+            return None
+        out = np.empty(self.n_blocks(), np.uint32)
+        self._chk(self.L.gpuart_hip_read_block_paths(self.ctx, out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def set_share(self, g):
         self._chk(self.L.gpuart_hip_set_share(self.ctx, C.byref(g)))
@@ -967,6 +1009,28 @@ class Renderer:
                                                              converge_lib().gpuart_converge_last_error().decode()))
         return rc == 1, (s.as_dict() if s.batches else None)
 
+    def render_adaptive(self, threshold, min_paths=ADAPTIVE_DEFAULT_MIN_PATHS, batch_paths=CONVERGE_DEFAULT_BATCH, lum_floor=CONVERGE_DEFAULT_FLOOR):
+        """Renderer::RenderAdaptive: render_until's loop with the estimate kept per 8x8 block (include/gpuart_adaptive.h): a block whose
+        pixels all have a relative standard error of at most threshold, and which holds at least min_paths paths and two batches, is
+        retired, and the passes that follow render the remaining blocks only. Returns (converged, summary): converged is True when no
+        block is active any more, False when the cap was reached first; summary is the last select as a dict (AdaptiveSummary.as_dict),
+        None if none ran. Raises HipError for arguments out of range, while temporal history is on, and on errors."""
+        s = AdaptiveSummary()
+        rc = self.L.gpuart_renderer_render_adaptive(self.h, C.c_float(threshold), C.c_uint(int(min_paths)), C.c_uint(int(batch_paths)),
+                                                    C.c_float(lum_floor), C.byref(s))
+        if rc < 0:
+            raise HipError("render_adaptive failed (arguments out of range, temporal history on, or: %s / %s)" % (
+                hip_lib().gpuart_hip_last_error().decode(), adaptive_lib().gpuart_adaptive_last_error().decode()))
+        return rc == 1, (s.as_dict() if s.blocks else None)
+
+    def read_sample_counts(self):
+        """Renderer::ReadSampleCounts: the paths accumulated into every tile pixel (its 8x8 block's count), (th, tw) uint32."""
+        _, _, tw, th = self.tile
+        out = np.empty((th, tw), np.uint32)
+        if not self.L.gpuart_renderer_read_sample_counts(self.h, out.ctypes.data_as(C.c_void_p)):
+            raise HipError("read_sample_counts failed: %s" % hip_lib().gpuart_hip_last_error().decode())
+        return out
+
     def read_error_map(self, lum_floor=CONVERGE_DEFAULT_FLOOR):
         """Renderer::ReadErrorMap: the relative standard error per tile pixel as of render_until's last batch, (th, tw) float32; None
         before its second batch (and after anything that restarted the accumulation)."""
@@ -1026,6 +1090,17 @@ class Renderer:
         p = Params()
         self.L.gpuart_renderer_params(self.h, C.byref(p))
         return p
+
+    @staticmethod
+    def gather_radiance(ranks, root=0, normalized=True):
+        """Renderer::GatherRadiance: the shares of the renderers `ranks` (rank k of len(ranks)) as one full frame (H, W, 4) float32; None
+        on error, and while a rank's path counts are not uniform (render_adaptive retired blocks): the message is on stderr."""
+        r0 = ranks[root]
+        out = np.empty((r0.H, r0.W, 4), np.float32)
+        handles = (C.c_void_p * len(ranks))(*[r.h.value for r in ranks])
+        if not r0.L.gpuart_renderer_gather_radiance(handles, C.c_int(len(ranks)), C.c_int(root), C.c_int(1 if normalized else 0), _p(out)):
+            return None
+        return out
 
 
 # ---- the image libraries: what their handles share ----------------------------------------------------------------------------
@@ -1285,3 +1360,127 @@ class Converge(_ImageHandle):
         out = np.empty(self.shape + (4,), np.float32)
         self._chk(self.L.gpuart_converge_read_state(self.h, _p(out)))
         return out
+
+
+# ---- adaptive sampling: the estimate per 8x8 block (include/gpuart_adaptive.h) --------------------------------------------------
+class AdaptiveError(RuntimeError):
+    """A gpuart_adaptive_* call returned an error; `code` is the library's (GPUART_HIP_ERR_*)."""
+    code = None
+
+
+def _blocks_of(h, w):
+    return ((w + 7) // 8) * ((h + 7) // 8)
+
+
+class Adaptive(_ImageHandle):
+    """A gpuart_adaptive handle on one device: it owns the per-pixel state {mean, m2, prevL, 0} and the per-block words
+    {seen, batches, active, 0}."""
+    NAME, Error = "adaptive", AdaptiveError
+
+    def __init__(self, device=0):
+        super().__init__(device)
+        self.shape = None   # (h, w) of the state; None after reset
+
+    def reset(self):
+        """Forgets every batch: every block is active again and the next update may have any size."""
+        self._chk(self.L.gpuart_adaptive_reset(self.h))
+        self.shape = None
+
+    def _images(self, images, block_paths, what):
+        """torch tensors on this handle's device (-> their torch device) or NumPy arrays (-> None), checked; the arrays made contiguous."""
+        first = images[0]
+        if type(first).__module__.startswith("torch"):
+            import torch
+            dev = torch.device("cuda", self.device)
+            h, w = first.shape[0], first.shape[1]
+            for t in images:
+                if t.dtype != torch.float32 or tuple(t.shape) != (h, w, 4) or not t.is_contiguous() or t.device != dev:
+                    raise ValueError("%s must be contiguous (h, w, 4) float32 tensors on %s" % (what, dev))
+            if not type(block_paths).__module__.startswith("torch") or block_paths.element_size() != 4 or block_paths.is_floating_point() or \
+                    block_paths.numel() != _blocks_of(h, w) or not block_paths.is_contiguous() or block_paths.device != dev:
+                raise ValueError("block_paths must be a contiguous 32-bit integer tensor of one word per 8x8 block on %s" % dev)
+            return dev, list(images), block_paths, h, w
+        images = [a if k else np.ascontiguousarray(a, np.float32) for k, a in enumerate(images)]
+        h, w = images[0].shape[:2]
+        for a in images:
+            if not isinstance(a, np.ndarray) or a.dtype != np.float32 or a.shape != (h, w, 4) or not a.flags.c_contiguous:
+                raise ValueError("%s must be contiguous (h, w, 4) float32 arrays" % what)
+        block_paths = np.ascontiguousarray(block_paths, np.uint32).reshape(-1)
+        if block_paths.size != _blocks_of(h, w):
+            raise ValueError("block_paths must hold one word per 8x8 block")
+        return None, images, block_paths, h, w
+
+    def update(self, accum, block_paths):
+        """Shows the estimator the raw accumulator accum (h, w, 4) float32 and the paths per pixel each 8x8 block holds (one 32-bit word per
+        block, row-major: Backend.block_paths): one more batch for every block whose count moved. torch tensors on this handle's device
+        run through gpuart_adaptive_update (torch's current stream is synchronised first, the handle before returning); NumPy arrays
+        through gpuart_adaptive_update_host."""
+        dev, (accum,), block_paths, h, w = self._images([accum], block_paths, "accum")
+        if dev is not None:
+            import torch
+            torch.cuda.current_stream(dev).synchronize()
+            self._chk(self.L.gpuart_adaptive_update(self.h, _dp(accum), _dp(block_paths), C.c_uint32(w), C.c_uint32(h)))
+            self.finish()
+        else:
+            self._chk(self.L.gpuart_adaptive_update_host(self.h, _p(accum), block_paths.ctypes.data_as(C.c_void_p), C.c_uint32(w), C.c_uint32(h)))
+        self.shape = (h, w)
+
+    def select(self, threshold, lum_floor=CONVERGE_DEFAULT_FLOOR, min_paths=1, error_map=None):
+        """Retires the blocks whose pixels all have e <= threshold, hold at least min_paths paths and two batches. Returns (blocks, summary):
+        the ascending uint32 array of the blocks that stay active and a dict (AdaptiveSummary.as_dict). error_map: None, or a contiguous
+        (h, w) float32 torch tensor on this handle's device that receives e per pixel."""
+        if self.shape is None:
+            raise ValueError("select before the first update")
+        mp = None
+        if error_map is not None:
+            import torch
+            dev = torch.device("cuda", self.device)
+            if not type(error_map).__module__.startswith("torch") or error_map.dtype != torch.float32 or tuple(error_map.shape) != self.shape or \
+                    not error_map.is_contiguous() or error_map.device != dev:
+                raise ValueError("error_map must be a contiguous %s float32 tensor on %s" % (self.shape, dev))
+            torch.cuda.current_stream(dev).synchronize()
+            mp = _dp(error_map)
+        s = AdaptiveSummary()
+        blocks = np.empty(_blocks_of(*self.shape), np.uint32)
+        self._chk(self.L.gpuart_adaptive_select(self.h, C.c_float(threshold), C.c_float(lum_floor), C.c_uint32(int(min_paths)), mp,
+                                                blocks.ctypes.data_as(C.c_void_p), C.byref(s)))
+        return blocks[:s.active_blocks].copy(), s.as_dict()
+
+    def error_map(self, lum_floor=CONVERGE_DEFAULT_FLOOR):
+        """e per pixel, (h, w) float32 (+inf where the block has fewer than two batches), as a torch tensor on this handle's device."""
+        if self.shape is None:
+            raise ValueError("no estimate before the first update")
+        import torch
+        m = torch.empty(self.shape, dtype=torch.float32, device=torch.device("cuda", self.device))
+        self._chk(self.L.gpuart_adaptive_error_map(self.h, C.c_float(lum_floor), _dp(m), C.c_uint32(self.shape[1]), C.c_uint32(self.shape[0])))
+        self.finish()
+        return m
+
+    def normalize(self, accum, block_paths, out=None):
+        """accum / its block's path count (a block without paths: / 1), alpha copied. torch tensors on this handle's device run through
+        gpuart_adaptive_normalize (torch's current stream is synchronised first, the handle before returning); NumPy arrays through
+        gpuart_adaptive_normalize_host. The result is `out` or a new image."""
+        if out is None:
+            if type(accum).__module__.startswith("torch"):
+                import torch
+                out = torch.empty_like(accum)
+            else:
+                out = np.empty(np.shape(accum), np.float32)
+        dev, (accum, out), block_paths, h, w = self._images([accum, out], block_paths, "accum and out")
+        if dev is not None:
+            import torch
+            torch.cuda.current_stream(dev).synchronize()
+            self._chk(self.L.gpuart_adaptive_normalize(self.h, _dp(accum), _dp(block_paths), _dp(out), C.c_uint32(w), C.c_uint32(h)))
+            self.finish()
+        else:
+            self._chk(self.L.gpuart_adaptive_normalize_host(self.h, _p(accum), block_paths.ctypes.data_as(C.c_void_p), _p(out), C.c_uint32(w), C.c_uint32(h)))
+        return out
+
+    def state(self):
+        """(state, block_state): (h, w, 4) float32 {mean, m2, prevL, 0} and (blocks, 4) uint32 {seen, batches, active, 0}."""
+        if self.shape is None:
+            raise ValueError("no state before the first update")
+        out = np.empty(self.shape + (4,), np.float32)
+        blk = np.empty((_blocks_of(*self.shape), 4), np.uint32)
+        self._chk(self.L.gpuart_adaptive_read_state(self.h, _p(out), blk.ctypes.data_as(C.c_void_p)))
+        return out, blk

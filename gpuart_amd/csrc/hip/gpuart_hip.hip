@@ -121,6 +121,15 @@ struct gpuart_hip_ctx {
     bool order_stale = true;           ///< the order in use (or none) was not counted with this camera / scene
     bool order_auto = true;            ///< GPUART_HIP_TILE_ORDER (default 1)
     bool order_from_hook = false;      ///< gpuart_hip_test_tile_order set Frame::tile_order: it stays until the hook clears it
+    // Adaptive sampling (gpuart_hip_set_active_blocks): the blocks the passes to come render — Frame::tile_order of every run, which
+    // then has 64 x active_n path slots — and the paths accumulated per block. While every pass since the last reset covered every block
+    // the host's own count serves (uniform_paths) and the plain k_accumulate runs; the first list makes the device array.
+    uint32_t *d_active = nullptr;      ///< the list (room for every block of the tile)
+    uint32_t active_n = 0;
+    bool have_list = false;
+    uint32_t *d_block_paths = nullptr; ///< one word per block (valid while have_counts)
+    bool have_counts = false;
+    uint32_t uniform_paths = 0;        ///< paths per pixel since the last reset while !have_counts
     std::vector<PassLane> lanes;
     uint32_t next_lane = 0;
     uint32_t spill_levels = 0;
@@ -284,6 +293,9 @@ int realloc_tile(gpuart_hip_ctx *c) {
     if (c->d_tile_cost) { (void)hipFree(c->d_tile_cost); c->d_tile_cost = nullptr; }
     c->frame.tile_order = nullptr; c->frame.tile_cost = nullptr;
     c->order_cur = -1; c->order_sorting = false; c->order_stale = true; c->order_from_hook = false;
+    if (c->d_active) { (void)hipFree(c->d_active); c->d_active = nullptr; }
+    if (c->d_block_paths) { (void)hipFree(c->d_block_paths); c->d_block_paths = nullptr; }
+    c->have_list = false; c->active_n = 0; c->have_counts = false; c->uniform_paths = 0;
     if (c->d_tile_xy) { (void)hipFree(c->d_tile_xy); c->d_tile_xy = nullptr; }
     if (c->d_direct) { (void)hipFree(c->d_direct); c->d_direct = nullptr; }
     if (c->d_accum) { (void)hipFree(c->d_accum); c->d_accum = nullptr; }
@@ -576,7 +588,7 @@ int gpuart_hip_destroy(gpuart_hip_ctx *c) {
     const bool comm_stuck = bounded_ns::stuck().load();
     if (c->comm && !comm_stuck) (void)comm_drop(c);
     void *ptrs[] = {c->d_recs, c->d_prims, c->d_spill, c->d_direct, c->d_accum, c->d_counters, c->d_scratch, c->d_cursor,
-                    c->d_query_cursor, c->d_tile_order[0], c->d_tile_order[1], c->d_tile_cost, c->d_tile_xy};
+                    c->d_query_cursor, c->d_tile_order[0], c->d_tile_order[1], c->d_tile_cost, c->d_tile_xy, c->d_active, c->d_block_paths};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     void *comm_ptrs[] = {c->d_send, c->d_stage, c->d_hello};
     for (void *p : comm_ptrs) if (p && !comm_stuck) (void)hipFree(p);
@@ -728,6 +740,8 @@ int gpuart_hip_pt_reset(gpuart_hip_ctx *c) {
     int r = drain(c);
     if (r) return r;
     c->plan.plan_done = 0;  // a new accumulation: the planned sequence, if any, begins again
+    c->have_list = false; c->active_n = 0; c->have_counts = false; c->uniform_paths = 0;  // every block again, nothing counted
+    if (c->plan.active_slots) c->plan.set_active(0);
     HIP_TRY(hipMemsetAsync(c->d_accum, 0, c->plan.tile_pixels * sizeof(float4), c->stream));
     return 0;
 }
@@ -769,6 +783,7 @@ namespace {
 int run_frame(gpuart_hip_ctx *c, Frame &f, bool &gathers, bool single_pass_run) {
     f = c->frame;
     gathers = false;
+    if (c->have_list) { f.tile_order = c->d_active; return 0; }  // an active block list is the run's order: nothing gathered, nothing sorted
     if (c->order_from_hook || !c->order_auto || !single_pass_run || (c->plan.mode != 0 && c->plan.mode != 5)) return 0;
     if (c->order_sorting && hipEventQuery(c->ev_order) == hipSuccess) {  // (hipErrorNotReady: keep the order in use a little longer)
         c->order_cur = c->order_next;
@@ -811,7 +826,15 @@ int finish_run(gpuart_hip_ctx *c, PassLane &l, bool gathers) {
     HIP_TRY(hipEventRecord(l.ev_done, l.main));
     HIP_TRY(hipStreamWaitEvent(c->stream, l.ev_done, 0));
     GD_LEDGER(c, k_accumulate);
-    k_accumulate<<<dim3((unsigned)((c->plan.tile_pixels + 255) / 256)), 256, 0, c->stream>>>(c->d_accum, l.passcolor, c->plan.tile_pixels, l.pb.batch);
+    if (c->have_counts) {  // the run's blocks only (all of them without a list), and their path counts
+        const uint32_t entries = l.pb.n_slots;
+        k_accumulate<<<dim3((entries + 255) / 256), 256, 0, c->stream>>>(c->d_accum, l.passcolor, c->plan.tile_pixels, l.pb.batch,
+                                                                          c->have_list ? c->d_active : nullptr, c->d_block_paths, entries,
+                                                                          c->frame.tw, c->frame.th, l.pb.batch * (uint32_t)c->pend_npaths);
+    } else {
+        k_accumulate<<<dim3((unsigned)((c->plan.tile_pixels + 255) / 256)), 256, 0, c->stream>>>(c->d_accum, l.passcolor, c->plan.tile_pixels, l.pb.batch,
+                                                                                                 nullptr, nullptr, 0, 0, 0, 0);
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(l.ev_free, c->stream));
     if (gathers && (r = sort_tile_order(c, l))) return r;
@@ -873,6 +896,7 @@ int launch_run(gpuart_hip_ctx *c, size_t first, size_t count) {
     PassLane &l = c->lanes[c->next_lane];
     c->next_lane = (c->next_lane + 1) % c->plan.lanes_in_use;
     l.pb.batch = (uint32_t)count;
+    l.pb.n_slots = (uint32_t)c->plan.slots();  // (every grid, chunk count and counter below comes from the run's slots)
     if (c->plan.uses_run_kernel(count)) return launch_run_persistent(c, l, first, count);
     const uint32_t nseg = segment_bound(c, p);
     SeedBatch seeds{};
@@ -940,6 +964,70 @@ int launch_run(gpuart_hip_ctx *c, size_t first, size_t count) {
 }  // namespace
 }  // extern "C++"
 
+/// `npaths` more paths in every pixel that no k_accumulate launch counts: the host's count while all passes covered all blocks; with
+/// counts on the device (mode 2 after a list was dropped) they go there and back.
+static int count_whole_pass(gpuart_hip_ctx *c, uint32_t npaths) {
+    if (!npaths) return 0;
+    if (!c->have_counts) { c->uniform_paths += npaths; return 0; }
+    const size_t tiles = (size_t)((c->frame.tw + 7) / 8) * ((c->frame.th + 7) / 8);
+    std::vector<uint32_t> h(tiles);
+    HIP_TRY(hipMemcpyAsync(h.data(), c->d_block_paths, tiles * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (auto &v : h) v += npaths;
+    HIP_TRY(hipMemcpyAsync(c->d_block_paths, h.data(), tiles * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int gpuart_hip_set_active_blocks(gpuart_hip_ctx *c, const uint32_t *blocks, size_t n) {
+    if (!c || !c->frame.W) return fail(GPUART_HIP_ERR_ARG, "active blocks: no frame size set");
+    const size_t tiles = (size_t)((c->frame.tw + 7) / 8) * ((c->frame.th + 7) / 8);
+    if (blocks) {  // validated here, on the host: the kernels index pixels and counts with these words
+        if (c->empty_share || !tiles) return fail(GPUART_HIP_ERR_ARG, "active blocks: an empty share has no blocks");
+        if (n > tiles) return fail(GPUART_HIP_ERR_ARG, "active blocks: " + std::to_string(n) + " entries for a tile of " + std::to_string(tiles) + " blocks");
+        for (size_t k = 0; k < n; k++) {
+            if (blocks[k] >= tiles)
+                return fail(GPUART_HIP_ERR_ARG, "active blocks: entry " + std::to_string(k) + " is " + std::to_string(blocks[k]) + ", the tile has " + std::to_string(tiles) + " blocks");
+            if (k && blocks[k] <= blocks[k - 1]) return fail(GPUART_HIP_ERR_ARG, "active blocks: entry " + std::to_string(k) + " is not above its predecessor (strictly ascending, please)");
+        }
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    int r = gpuart_hip_flush(c);  // what was collected belongs to the old list
+    if (r || (r = drain(c))) return r;  // (and no run in flight reads the list while it is replaced)
+    if (!blocks) {
+        c->have_list = false; c->active_n = 0;
+        c->plan.set_active(0);
+        return 0;
+    }
+    if (!c->d_active) HIP_TRY(hipMalloc(&c->d_active, tiles * sizeof(uint32_t)));
+    if (!c->have_counts) {  // from here on the blocks' counts differ: the device array, every block at the host's count
+        if (!c->d_block_paths) HIP_TRY(hipMalloc(&c->d_block_paths, tiles * sizeof(uint32_t)));
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)c->d_block_paths, (int)c->uniform_paths, tiles, c->stream));
+        c->have_counts = true;
+    }
+    if (n) HIP_TRY(hipMemcpyAsync(c->d_active, blocks, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));  // (the lanes' streams read the list; `blocks` is the caller's)
+    c->have_list = true; c->active_n = (uint32_t)n;
+    c->plan.set_active((uint32_t)n * 64);
+    return 0;
+}
+
+static int block_paths_to(gpuart_hip_ctx *c, void *dst, bool host) {
+    if (!c || !dst || !c->frame.W) return fail(GPUART_HIP_ERR_ARG, "block paths: bad argument");
+    if ((uintptr_t)dst % 4) return fail(GPUART_HIP_ERR_ARG, "block paths: misaligned pointer");
+    const size_t tiles = (size_t)((c->frame.tw + 7) / 8) * ((c->frame.th + 7) / 8);
+    if (c->empty_share || !tiles) return 0;
+    HIP_TRY(hipSetDevice(c->device));
+    { int fr = gpuart_hip_flush(c); if (fr) return fr; }
+    if (c->have_counts) HIP_TRY(hipMemcpyAsync(dst, c->d_block_paths, tiles * sizeof(uint32_t), host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
+    else if (host) std::fill((uint32_t *)dst, (uint32_t *)dst + tiles, c->uniform_paths);
+    else HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)dst, (int)c->uniform_paths, tiles, c->stream));
+    if (host) HIP_TRY(hipStreamSynchronize(c->stream));  // (like gpuart_hip_read, also where the host's count served)
+    return 0;
+}
+int gpuart_hip_read_block_paths(gpuart_hip_ctx *c, uint32_t *host) { return block_paths_to(c, host, true); }
+int gpuart_hip_export_block_paths(gpuart_hip_ctx *c, void *device) { return block_paths_to(c, device, false); }
+
 int gpuart_hip_flush(gpuart_hip_ctx *c) {
     if (!c) return fail(GPUART_HIP_ERR_ARG, "ctx == NULL");
     const size_t pending = c->pend_seeds.size();
@@ -964,7 +1052,9 @@ int gpuart_hip_pt_pass(gpuart_hip_ctx *c, const gpuart_params *p, const float ra
     if (r) return r > 0 ? 0 : r;
     if (!randSeed || npaths < 0) return fail(GPUART_HIP_ERR_ARG, "bad argument");
     if (p->maxSegments > GPUART_HIP_MAX_SEGMENTS) return fail(GPUART_HIP_ERR_ARG, "maxSegments exceeds GPUART_HIP_MAX_SEGMENTS");
-    if (npaths == 0) return 0;
+    if (c->have_list && (c->plan.mode == 1 || c->plan.mode == 2 || c->plan.mode == 4))
+        return fail(GPUART_HIP_ERR_ARG, "an active block list is set: mode " + std::to_string(c->plan.mode) + " renders whole tiles only (modes 0, 3 and 5 honour a list)");
+    if (npaths == 0 || (c->have_list && c->active_n == 0)) return 0;
     HIP_TRY(hipSetDevice(c->device));
     const float4 seed = make_float4(randSeed[0], randSeed[1], randSeed[2], randSeed[3]);
     if (c->plan.mode == 2) {  // megakernel: the whole path in one thread, on the primary stream (ablation / cross-check)
@@ -976,8 +1066,10 @@ int gpuart_hip_pt_pass(gpuart_hip_ctx *c, const gpuart_params *p, const float ra
         GD_LEDGER(c, k_pt_mega<false>);
         k_pt_mega<false><<<grid, BLOCK, 0, c->stream>>>(sc, c->frame, *p, seed, npaths, c->plan.n_slots, c->d_accum, c->d_spill, c->d_counters);
         HIP_TRY(hipGetLastError());
-        return end_timed(c, t);
+        if ((r = end_timed(c, t))) return r;
+        return count_whole_pass(c, (uint32_t)npaths);
     }
+    if ((r = count_whole_pass(c, c->have_counts ? 0u : (uint32_t)npaths))) return r;  // (with counts on the device k_accumulate counts the run)
     // Passes are collected and launched run_passes at a time (plan_runs). A pass with different parameters
     // starts a new batch; anything that observes or changes state flushes first.
     if (!c->pend_seeds.empty() && (memcmp(&c->pend_params, p, sizeof *p) != 0 || c->pend_npaths != npaths))
@@ -1753,7 +1845,8 @@ int gpuart_hip_test_kernel_choice(uint32_t type_mask, uint32_t exact_boxes, uint
 }
 
 // ---- run planner hook: the planner of the context, driven without a device (include/gpuart_hip.h) ---------------------
-int gpuart_hip_test_planner(const uint32_t cfg[8], const uint32_t *ops, int n_ops, uint32_t *runs, int max_runs) {
+/// Both planner hooks; `active_ops`: op 7 exists and a record's second word is the run's slots, not the tile's.
+static int planner_hook(const uint32_t cfg[8], const uint32_t *ops, int n_ops, uint32_t *runs, int max_runs, bool active_ops) {
     if (!cfg || (!ops && n_ops) || n_ops < 0 || (!runs && max_runs) || max_runs < 0) return fail(GPUART_HIP_ERR_ARG, "bad argument");
     RunPlanner p;
     p.batch_limit = MAX_BATCH;
@@ -1769,7 +1862,7 @@ int gpuart_hip_test_planner(const uint32_t cfg[8], const uint32_t *ops, int n_op
     auto record = [&](int op, size_t count) {
         if (n_runs < max_runs) {
             uint32_t *o = runs + 6 * (size_t)n_runs;
-            o[0] = (uint32_t)op; o[1] = p.n_slots; o[2] = p.max_batch; o[3] = (uint32_t)count;
+            o[0] = (uint32_t)op; o[1] = active_ops ? (uint32_t)p.slots() : p.n_slots; o[2] = p.max_batch; o[3] = (uint32_t)count;
             o[4] = p.uses_run_kernel(count) ? 1u : 0u; o[5] = (uint32_t)p.pending;
         }
         n_runs++;
@@ -1813,11 +1906,22 @@ int gpuart_hip_test_planner(const uint32_t cfg[8], const uint32_t *ops, int n_op
             break;
         case 5: flush(k); break;
         case 6: alloc_fails = a; break;
+        case 7:  // gpuart_hip_set_active_blocks with a list of `a` blocks (0: dropped; the empty list never reaches the planner)
+            if (!active_ops) return fail(GPUART_HIP_ERR_ARG, "unknown planner op");
+            if (!p.n_slots || a > p.n_slots / 64) return fail(GPUART_HIP_ERR_ARG, "bad active list");
+            flush(k); p.set_active(a * 64);
+            break;
         default: return fail(GPUART_HIP_ERR_ARG, "unknown planner op");
         }
         if (r) return fail(r, "planner: tile refused");
     }
     return n_runs;
+}
+int gpuart_hip_test_planner(const uint32_t cfg[8], const uint32_t *ops, int n_ops, uint32_t *runs, int max_runs) {
+    return planner_hook(cfg, ops, n_ops, runs, max_runs, false);
+}
+int gpuart_hip_test_planner_active(const uint32_t cfg[8], const uint32_t *ops, int n_ops, uint32_t *runs, int max_runs) {
+    return planner_hook(cfg, ops, n_ops, runs, max_runs, true);
 }
 #endif
 

@@ -253,8 +253,23 @@ GD_FN void path_commit(const Frame &f, const PathBuffers &b, float4 *passcolor, 
 
 /// path_tracing.glsl:255 for one finished pass: accum = PrevRadiance + color. Launched in pass order on the
 /// context's primary stream, so float additions happen in the reference's order whatever the overlap of passes.
-__global__ void k_accumulate(float4 *__restrict__ accum, const float4 *__restrict__ passcolor, size_t n, uint32_t batch) {
+/// With per-block path counts (`counts`; adaptive sampling, gpuart_hip_set_active_blocks) it walks `entries` = 64 x blocks entries
+/// instead: entry e is pixel e & 63 of block list[e >> 6] (no list: block e >> 6), the padding of ragged edge blocks skipped. Only those
+/// pixels' planes hold colours of this run — the others' are stale —, and lane 0 of every block adds the run's paths, `add`, to the
+/// block's count. A block appears once per list and runs are accumulated one after the other on one stream: a plain store.
+__global__ void k_accumulate(float4 *__restrict__ accum, const float4 *__restrict__ passcolor, size_t n, uint32_t batch,
+                             const uint32_t *__restrict__ list, uint32_t *__restrict__ counts, uint32_t entries, uint32_t tw, uint32_t th,
+                             uint32_t add) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (counts) {
+        if (i >= entries) return;
+        const uint32_t e = (uint32_t)i, tiles_x = (tw + 7) / 8;
+        const uint32_t t = list ? list[e >> 6] : e >> 6, w = e & 63;
+        if (w == 0) counts[t] += add;
+        const uint32_t lx = (t % tiles_x) * 8 + (w & 7), ly = (t / tiles_x) * 8 + (w >> 3);
+        if (lx >= tw || ly >= th) return;
+        i = (size_t)ly * tw + lx;
+    }
     if (i < n) {
         float4 a = accum[i];
         for (uint32_t k = 0; k < batch; k++) {  // the passes of a batch, oldest first

@@ -26,6 +26,7 @@ struct RunPlanner {
 
     // ---- state ---------------------------------------------------------------------------------------------------------
     uint32_t n_slots = 0;         ///< path slots of the tile (8x8-tile padded)
+    uint32_t active_slots = 0;    ///< path slots of a run while an active block list is set (gpuart_hip_set_active_blocks: 64 x its length); 0: none, n_slots
     size_t tile_pixels = 0;
     uint32_t max_batch = 1;       ///< passes a lane's buffers hold
     uint32_t lanes_in_use = 1;
@@ -38,13 +39,20 @@ struct RunPlanner {
     static constexpr size_t PATH_BYTES = 6 * 16 + 8 + 3 * 4;  ///< path state per slot: six float4, one uint2, three queue words
     static constexpr size_t RUN_KERNEL_SLOTS = (size_t)1 << 28; ///< k_run's list entries address this many path slots of one run (kernel_run.h RUN_SLOT)
 
+    /// Path slots of one pass of a run: what run lengths and the k_run / pipeline crossover are planned from. max_batch and lane_bytes stay
+    /// those of the whole tile: the lanes were allocated for it. (The crossover's constants were measured on whole frames; nobody has
+    /// measured them for sparse lists.)
+    size_t slots() const { return active_slots ? active_slots : n_slots; }
+    /// An active block list of `slots` / 64 blocks was set (0: dropped). The caller has flushed.
+    void set_active(uint32_t slots) { active_slots = slots; plan(); }
+
     /// Bytes of one lane's path state for runs of `batch` passes.
     size_t lane_bytes(size_t batch) const { return (size_t)n_slots * batch * PATH_BYTES + batch * tile_pixels * 16; }
 
     /// A new tile: the run length the budgets allow and the lanes to try first. The caller allocates `lanes_in_use` lanes of
     /// `lane_bytes(max_batch)` and calls `shrink()` while the device refuses.
     void set_tile(uint32_t slots, size_t pixels) {
-        n_slots = slots; tile_pixels = pixels; pending = 0; plan_done = 0;
+        n_slots = slots; active_slots = 0; tile_pixels = pixels; pending = 0; plan_done = 0;
         if (!n_slots) { max_batch = 1; lanes_in_use = 1; run_passes = 1; return; }
         max_batch = (uint32_t)std::max<size_t>(1, std::min<size_t>({(size_t)batch_limit, batch_paths / n_slots, RUN_KERNEL_SLOTS / n_slots}));
         first_lanes();
@@ -69,9 +77,9 @@ struct RunPlanner {
     bool uses_run_kernel(size_t count) const {
         if (mode == 1 || mode == 4 || mode == 5) return true;
         if (mode != 0 || !small_paths) return false;
-        if ((size_t)n_slots * count > RUN_KERNEL_SLOTS) return false;  // (a tile beyond 2^28 pixels: one pass alone goes through the launch pipeline)
+        if (slots() * count > RUN_KERNEL_SLOTS) return false;  // (a tile beyond 2^28 pixels: one pass alone goes through the launch pipeline)
         const size_t passes = planned_passes ? planned_passes : count;
-        return passes <= 1 || passes * (size_t)n_slots <= small_paths;  // one pass observed alone: k_run at every frame size
+        return passes <= 1 || passes * slots() <= small_paths;  // one pass observed alone: k_run at every frame size
     }
 
     /// Passes per pipeline run of a planned sequence of K passes: AS MANY EQUAL RUNS AS THERE ARE LANES — ceil(K / lanes) passes each;
@@ -85,21 +93,22 @@ struct RunPlanner {
     /// never above max_batch. Without a plan: 8M paths.
     void plan() {
         if (!n_slots) { run_passes = 1; return; }
+        const size_t run_slots = slots();  // (of a run: the active blocks' while a list is set)
         const double unit = (double)((size_t)2 << 20);
-        const size_t min_run = std::max<size_t>(1, min_run_paths / n_slots);
+        const size_t min_run = std::max<size_t>(1, min_run_paths / run_slots);
         size_t want;
         if (planned_passes && (mode == 0 || mode == 5) && planned_passes <= max_batch &&
-            (small_paths ? planned_passes == 1 || (size_t)planned_passes * n_slots <= small_paths : mode == 5)) {
+            (small_paths ? planned_passes == 1 || (size_t)planned_passes * run_slots <= small_paths : mode == 5)) {
             want = planned_passes;  // a small sequence is ONE run of the persistent kernel (uses_run_kernel)
         } else if (planned_passes && plan_run_factor > 0) {
-            const double u = (double)planned_passes * n_slots / unit;
-            want = (size_t)(plan_run_factor * std::sqrt(u) * unit / n_slots);
+            const double u = (double)planned_passes * run_slots / unit;
+            want = (size_t)(plan_run_factor * std::sqrt(u) * unit / run_slots);
         } else if (planned_passes) {
             const size_t lanes = std::max<size_t>(1, lanes_in_use);
             const size_t rounds = (planned_passes + lanes * max_batch - 1) / (lanes * max_batch);
             want = (planned_passes + rounds * lanes - 1) / (rounds * lanes);
         } else {
-            want = std::max<size_t>(1, ((size_t)8 << 20) / n_slots);
+            want = std::max<size_t>(1, ((size_t)8 << 20) / run_slots);
         }
         run_passes = std::min<size_t>(max_batch, std::max(min_run, want));
         // ... of EQUAL length: 20 passes in runs of 6 end in a run of 2 that has nothing left to overlap with (four runs of 5 took 5 % less
@@ -133,7 +142,7 @@ struct RunPlanner {
     std::vector<size_t> on_flush() {
         std::vector<size_t> runs;
         if (!pending) return runs;
-        size_t n = uses_run_kernel(pending) ? 1 : std::max<size_t>(1, std::min<size_t>({(size_t)lanes_in_use, pending, pending * n_slots / std::max<size_t>(1, min_run_paths)}));
+        size_t n = uses_run_kernel(pending) ? 1 : std::max<size_t>(1, std::min<size_t>({(size_t)lanes_in_use, pending, pending * slots() / std::max<size_t>(1, min_run_paths)}));
         // the remainder of a PLANNED sequence is the plan's last, shorter run: cut up it would take lanes the plan left alone (20 passes =
         // 6 x 3 + 2: a seventh run, not a seventh and an eighth). Only the plan's TAIL: what a read-back or a state change in the middle
         // of the sequence flushes — or passes nobody planned — is spread over the lanes as before.
@@ -153,7 +162,7 @@ struct RunPlanner {
     const char *check(size_t count) const {
         if (!count) return "an empty pipeline run";
         if (count > max_batch) return "a pipeline run longer than its lane's buffers";
-        if ((size_t)n_slots * count > std::max<size_t>(batch_paths, n_slots)) return "a pipeline run beyond the path budget";
+        if (slots() * count > std::max<size_t>(batch_paths, n_slots)) return "a pipeline run beyond the path budget";
         return nullptr;
     }
 };

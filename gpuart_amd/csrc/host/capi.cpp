@@ -281,6 +281,17 @@ int gpuart_renderer_read_error_map(gpuart_renderer *r, float *e, float lumFloor)
 int gpuart_renderer_read_refined(gpuart_renderer *r, float *rgba, float lumFloor, const gpuart_refine_params *p) {
     return r->impl.ReadRefined(rgba, lumFloor, p) ? 1 : 0;
 }
+int gpuart_renderer_render_adaptive(gpuart_renderer *r, float threshold, unsigned minPaths, unsigned batchPaths, float lumFloor,
+                                    gpuart_adaptive_summary *last) {
+    return r->impl.RenderAdaptive(threshold, minPaths, batchPaths, lumFloor, last);
+}
+int gpuart_renderer_read_sample_counts(gpuart_renderer *r, uint32_t *perPixel) { return r->impl.ReadSampleCounts(perPixel) ? 1 : 0; }
+int gpuart_renderer_gather_radiance(gpuart_renderer *const *ranks, int n, int root, int normalized, float *fullFrame) {
+    if (!ranks || n < 1) return 0;
+    std::vector<Renderer *> impl((size_t)n);
+    for (int k = 0; k < n; k++) impl[(size_t)k] = ranks[k] ? &ranks[k]->impl : nullptr;
+    return Renderer::GatherRadiance(impl.data(), n, root, normalized != 0, fullFrame) ? 1 : 0;
+}
 int gpuart_renderer_finish(gpuart_renderer *r) { return r->impl.Finish() ? 1 : 0; }
 int gpuart_renderer_save_checkpoint(gpuart_renderer *r, const char *path) { return r->impl.SaveCheckpoint(path) ? 1 : 0; }
 int gpuart_renderer_load_checkpoint(gpuart_renderer *r, const char *path) { return r->impl.LoadCheckpoint(path) ? 1 : 0; }

@@ -6,6 +6,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "gpuart_adaptive.h"
 #include "gpuart_converge.h"
 #include "gpuart_denoise.h"
 #include "gpuart_hip.h"
@@ -100,6 +101,15 @@ int gpuart_renderer_read_error_map(gpuart_renderer *r, float *e, float lumFloor)
 /* Renderer::ReadRefined: the normalised accumulator filtered by the error map of the last batch (include/gpuart_refine.h); p = NULL:
  * the defaults. 1 on success, 0 before the second batch or on error. */
 int gpuart_renderer_read_refined(gpuart_renderer *r, float *rgba, float lumFloor, const gpuart_refine_params *p);
+/* Renderer::RenderAdaptive: 1 no block is active any more, 0 the cap was reached first, -1 error; last (may be NULL) is filled whenever
+ * a select ran. */
+int gpuart_renderer_render_adaptive(gpuart_renderer *r, float threshold, unsigned minPaths, unsigned batchPaths, float lumFloor,
+                                    gpuart_adaptive_summary *last);
+/* Renderer::ReadSampleCounts: paths accumulated into every tile pixel, tile-sized, row 0 = bottom row; 1 on success. */
+int gpuart_renderer_read_sample_counts(gpuart_renderer *r, uint32_t *perPixel);
+/* Renderer::GatherRadiance: the shares of renderers 0 .. n-1 (Renderer::SetShare k of n) as one full frame in fullFrame on `root`'s
+ * host; 1 on success, 0 on error, and while a rank's path counts are not uniform (RenderAdaptive retired blocks). */
+int gpuart_renderer_gather_radiance(gpuart_renderer *const *ranks, int n, int root, int normalized, float *fullFrame);
 int gpuart_renderer_finish(gpuart_renderer *r);
 int gpuart_renderer_save_checkpoint(gpuart_renderer *r, const char *path);
 int gpuart_renderer_load_checkpoint(gpuart_renderer *r, const char *path);

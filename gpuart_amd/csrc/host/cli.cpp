@@ -25,6 +25,7 @@ static void usage() {
                  "                  [--spp N] [--per-pass K] [--max-segments M] [--seed S] [--tile x0,y0,w,h]\n"
                  "                  [--camera px,py,pz] [--sun az,alt[,off]] [--user-sphere x,y,z,r,em[,specular[,fuzzy]]]\n"
                  "                  [--device D] [--gpus N] [--resume ck] [--checkpoint ck] [--pfm out.pfm] [--ppm out.ppm] [--nearest-first]\n"
+                 "                  [--adaptive T [--adaptive-min N] [--until-batch N] [--until-floor F] [--samples-pfm out.pfm] [--refine]]\n"
                  "                  [--denoise] [--until T [--until-share S] [--until-floor F] [--until-batch N] [--error-pfm out.pfm] [--refine]]\n"
                  "  --until T: render until the relative standard error of every pixel's luminance is at most T (Renderer::RenderUntil; path\n"
                  "             tracing on one GPU), --spp being the cap; --until-share S: the share of pixels that may stay above T (default 0);\n"
@@ -32,7 +33,11 @@ static void usage() {
                  "             output); --until-batch N: paths per pixel between two measurements; --error-pfm: the error per pixel (PFM, grey).\n"
                  "             With --resume the checkpoint's paths are the first batch; one already at --spp renders nothing and is not measured\n"
                  "             (its line says 0 batches, converged false)\n"
-                 "  --refine: with --until, write the frame filtered by its own error estimate (Renderer::ReadRefined, with --until-floor as its\n"
+                 "  --adaptive T: adaptive sampling (Renderer::RenderAdaptive; path tracing on one GPU): like --until, but every 8x8 block stops by\n"
+                 "             itself as soon as all its pixels are at most T and it holds --adaptive-min paths (default 8) and two batches; the\n"
+                 "             passes that follow render the remaining blocks only. --spp is the cap, --until-batch and --until-floor as for --until;\n"
+                 "             --samples-pfm: the paths per pixel (PFM, grey). Not together with --until, --denoise, --checkpoint or --gpus above 1\n"
+                 "  --refine: with --until or --adaptive, write the frame filtered by its own error estimate (Renderer::ReadRefined, with --until-floor as its\n"
                  "             floor) instead of the raw one; not together with --denoise. A run that never reached two batches writes the raw frame\n"
                  "  --denoise: write the denoised preview of the frame (Renderer::ReadDenoised; path tracing on one GPU)\n"
                  "  --nearest-first: opt in to the nearer-child-first BVH walk (~10 % faster; soak-verified, not proven to be the reference's image)\n"
@@ -58,7 +63,10 @@ int main(int argc, char **argv) {
     std::string errorPfm;
     float until = -1, untilShare = 0, untilFloor = 1.0f / 256;
     unsigned untilBatch = GPUART_CONVERGE_DEFAULT_BATCH;
-    bool haveUntil = false;
+    bool haveUntil = false, haveAdaptive = false;
+    float adaptive = -1;
+    unsigned adaptiveMin = GPUART_ADAPTIVE_DEFAULT_MIN_PATHS;
+    std::string samplesPfm;
     float tile[4] = {0, 0, 0, 0}, campos[3] = {0.1f, -3.05f, 1.0f}, sun[3] = {0, 0, 0}, us[7] = {-0.4f, 0, 0.2f, 0, 0, 0, 0};
     int nTile = 0, nSun = 0, nUs = 0, n;
     for (int i = 1; i < argc; i++) {
@@ -93,6 +101,9 @@ int main(int argc, char **argv) {
         else if (a == "--until-floor") untilFloor = strtof(need("--until-floor"), nullptr);
         else if (a == "--until-batch") untilBatch = (unsigned)atoi(need("--until-batch"));
         else if (a == "--error-pfm") errorPfm = need("--error-pfm");
+        else if (a == "--adaptive") { adaptive = strtof(need("--adaptive"), nullptr); haveAdaptive = true; }
+        else if (a == "--adaptive-min") adaptiveMin = (unsigned)atoi(need("--adaptive-min"));
+        else if (a == "--samples-pfm") samplesPfm = need("--samples-pfm");
         else { usage(); return 2; }
     }
     if (W == 0 || H == 0 || (mode != "direct" && mode != "pt")) { usage(); return 2; }
@@ -101,7 +112,23 @@ int main(int argc, char **argv) {
         std::cerr << "gpuart_cli: --until needs --gpus 1: the ranks of a sharded frame would stop at different path counts\n";
         return 2;
     }
-    if (refine && !haveUntil) {
+    if (haveAdaptive && haveUntil) {
+        std::cerr << "gpuart_cli: --adaptive and --until are two stop rules: give one of them\n";
+        return 2;
+    }
+    if (haveAdaptive && denoise) {
+        std::cerr << "gpuart_cli: --adaptive writes the frame normalised by every block's own path count (or --refine's): not together with --denoise\n";
+        return 2;
+    }
+    if (haveAdaptive && !checkpoint.empty()) {
+        std::cerr << "gpuart_cli: --adaptive leaves blocks at different path counts: a checkpoint holds one, so not together with --checkpoint\n";
+        return 2;
+    }
+    if (haveAdaptive && gpus > 1) {
+        std::cerr << "gpuart_cli: --adaptive needs --gpus 1: the frame gather divides by one path count\n";
+        return 2;
+    }
+    if (refine && !haveUntil && !haveAdaptive) {
         std::cerr << "gpuart_cli: --refine needs --until: it filters with the error estimate of that render\n";
         return 2;
     }
@@ -110,6 +137,7 @@ int main(int argc, char **argv) {
         return 2;
     }
     if ((haveUntil && mode != "pt") || (!haveUntil && !errorPfm.empty())) { usage(); return 2; }
+    if ((haveAdaptive && mode != "pt") || (!haveAdaptive && !samplesPfm.empty())) { usage(); return 2; }
 
     // the reference's start-up camera (src/main.cpp:609-613), looking at (0,0,0.95)
     gpuart::Camera cam;
@@ -184,6 +212,28 @@ int main(int argc, char **argv) {
                 if (!f) return 1;
                 fprintf(f, "Pf\n%u %u\n-1.0\n", tw, th);
                 fwrite(e.data(), sizeof(float), e.size(), f);
+                fclose(f);
+            }
+        } else if (haveAdaptive) {
+            // the same passes, in batches, every block until its own error estimate is below the threshold or --spp is reached
+            const unsigned start = r.GetNumPathsRendered();
+            gpuart_adaptive_summary as{};
+            const int rc = r.RenderAdaptive(adaptive, adaptiveMin, untilBatch, untilFloor, &as);
+            if (rc < 0) return 1;
+            done = r.GetNumPathsRendered();
+            untilBatches = as.blocks ? 2 : 0;  // (a select ran: the estimate has its two batches)
+            passes = (done - start + std::max(1u, perPass) - 1) / std::max(1u, perPass);
+            printf("{\"adaptive\": %.9g, \"paths_issued\": %u, \"paths_min\": %u, \"paths_max\": %u, \"paths_mean\": %.9g, \"active_blocks\": %u, "
+                   "\"blocks\": %u, \"max_error\": %.9g, \"converged\": %s}\n", adaptive, done, as.paths_min, as.paths_max,
+                   as.pixels ? (double)as.paths_sum / (double)as.pixels : 0.0, as.active_blocks, as.blocks, as.max_error, rc == 1 ? "true" : "false");
+            if (!samplesPfm.empty()) {
+                std::vector<uint32_t> cnt((size_t)tw * th);
+                if (!r.ReadSampleCounts(cnt.data())) return 1;
+                std::vector<float> cf(cnt.begin(), cnt.end());
+                FILE *f = fopen(samplesPfm.c_str(), "wb");
+                if (!f) return 1;
+                fprintf(f, "Pf\n%u %u\n-1.0\n", tw, th);
+                fwrite(cf.data(), sizeof(float), cf.size(), f);
                 fclose(f);
             }
         } else {

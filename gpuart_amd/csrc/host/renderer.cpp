@@ -77,6 +77,9 @@ Renderer::Renderer(unsigned viewportWidth, unsigned viewportHeight, const Camera
 Renderer::~Renderer() {
     if (Refine) gpuart_refine_destroy(Refine);
     RefineMem.Release();
+    if (Adaptive) gpuart_adaptive_destroy(Adaptive);
+    AdaptiveMem.Release();
+    if (BlockPathsMem) (void)hipFree(BlockPathsMem);
     if (Converge) gpuart_converge_destroy(Converge);
     ConvergeMem.Release();
     if (Temporal) gpuart_temporal_destroy(Temporal);
@@ -161,6 +164,11 @@ bool Renderer::GatherRadiance(Renderer *const *ranks, int n, int root, bool norm
         if (!ranks[k] || !ranks[k]->IsOK) return false;
         ctxs[(size_t)k] = ranks[k]->Backend;
     }
+    for (int k = 0; k < n; k++)
+        if (ranks[k]->NonUniform) {
+            std::cerr << "Renderer: GatherRadiance after adaptive sampling retired blocks: the shares' path counts are not uniform." << std::endl;
+            return false;
+        }
     Renderer &r0 = *ranks[root];
     const float div = normalized && r0.PathTracing.numPathsRendered ? (float)r0.PathTracing.numPathsRendered : 1.0f;
     // One communicator per set of renderers, kept by the contexts themselves. Whether these contexts are (still) the ranks
@@ -322,7 +330,9 @@ void Renderer::RenderDirectLighting() {
 
 void Renderer::ResetPathTracing() {
     PathTracing.numPathsRendered = 0;
+    CountBase = 0;
     if (Converge) ResetConvergeNow();
+    if (Adaptive) ResetAdaptiveNow();
     if (Backend && Viewport.width) {
         gpuart_hip_pt_reset(Backend);
         // the passes RenderPathTracingPass() will submit until pathsPerPixel is reached (a scheduling hint)
@@ -367,6 +377,11 @@ bool Renderer::ReadDirectLighting(float *rgba) {
 }
 
 bool Renderer::ReadRadiance(float *rgba, bool normalized) {
+    if (IsOK && normalized && NonUniform) {  // every block by its own count, through a device buffer
+        const size_t n = (size_t)Tile.w * Tile.h;
+        if (!rgba || !AdaptiveMem.Fit(n, 16, "allocating the normalised frame") || !ExportNormalized((float *)AdaptiveMem.mem)) return false;
+        return hipMemcpy(rgba, AdaptiveMem.mem, n * 16, hipMemcpyDeviceToHost) == hipSuccess;
+    }
     // the division is the reference's ptracingNormalize program (shaders/pt_normalize.glsl:44-47)
     const float div = normalized && PathTracing.numPathsRendered ? (float)PathTracing.numPathsRendered : 1.0f;
     return IsOK && Check(gpuart_hip_read(Backend, 1, rgba, div), "reading the radiance accumulator");
@@ -374,7 +389,7 @@ bool Renderer::ReadRadiance(float *rgba, bool normalized) {
 
 namespace {
 const auto DN = gpuart_denoise_last_error, TP = gpuart_temporal_last_error, CV = gpuart_converge_last_error,
-           RF = gpuart_refine_last_error;  // for Check
+           RF = gpuart_refine_last_error, AD = gpuart_adaptive_last_error;  // for Check
 bool finite(float x) { return x - x == 0.0f; }
 bool checkHip(hipError_t e, const char *what) {
     if (e == hipSuccess) return true;
@@ -420,10 +435,37 @@ bool Renderer::StageView() {
         memcpy(GBufferSphere, us, sizeof us);
         GBufferValid = true;
     }
-    // the division is the reference's ptracingNormalize program (shaders/pt_normalize.glsl:44-47), as in ReadRadiance
-    const float div = PathTracing.numPathsRendered ? (float)PathTracing.numPathsRendered : 1.0f;
-    if (!Check(gpuart_hip_export(Backend, 1, b.radiance, div), "exporting the radiance")) return false;
-    return Check(gpuart_hip_finish(Backend), "waiting for the device");
+    return ExportNormalized(b.radiance);
+}
+
+bool Renderer::StageBlockPaths() {
+    const size_t nb = TileBlocks();
+    if (nb != BlockPathsWords) {
+        if (BlockPathsMem) (void)hipFree(BlockPathsMem);
+        BlockPathsMem = nullptr;
+        BlockPathsWords = 0;
+        if (!checkHip(hipMalloc((void **)&BlockPathsMem, nb * sizeof(uint32_t)), "allocating the block counts")) return false;
+        BlockPathsWords = nb;
+    }
+    if (!CountBase) return Check(gpuart_hip_export_block_paths(Backend, BlockPathsMem), "exporting the block counts");
+    // a loaded checkpoint's paths are in the accumulator but not in the back end's counts: added on the way
+    std::vector<uint32_t> counts(nb);
+    if (!Check(gpuart_hip_read_block_paths(Backend, counts.data()), "reading the block counts")) return false;
+    for (uint32_t &c : counts) c += CountBase;
+    return checkHip(hipMemcpy(BlockPathsMem, counts.data(), nb * sizeof(uint32_t), hipMemcpyHostToDevice), "staging the block counts");
+}
+
+bool Renderer::ExportNormalized(float *device, bool normalized) {
+    if (!normalized || !NonUniform) {
+        // the division is the reference's ptracingNormalize program (shaders/pt_normalize.glsl:44-47), as in ReadRadiance
+        const float div = normalized && PathTracing.numPathsRendered ? (float)PathTracing.numPathsRendered : 1.0f;
+        if (!Check(gpuart_hip_export(Backend, 1, device, div), "exporting the radiance")) return false;
+        return Check(gpuart_hip_finish(Backend), "waiting for the device");
+    }
+    if (!Check(gpuart_hip_export(Backend, 1, device, 1.0f), "exporting the radiance") || !StageBlockPaths()) return false;
+    if (!Check(gpuart_hip_finish(Backend), "waiting for the device")) return false;
+    return Check(gpuart_adaptive_normalize(Adaptive, device, BlockPathsMem, device, Tile.w, Tile.h), "normalising by the blocks' counts", AD) &&
+           Check(gpuart_adaptive_finish(Adaptive), "normalising by the blocks' counts", AD);
 }
 
 bool Renderer::ReadDenoised(float *rgba, const gpuart_denoise_params *p) {
@@ -439,6 +481,10 @@ bool Renderer::ReadDenoised(float *rgba, const gpuart_denoise_params *p) {
 
 // ---- temporal history (include/gpuart_temporal.h) ---------------------------------------------------------------------
 bool Renderer::SetTemporalHistory(bool on, const gpuart_temporal_params *tp) {
+    if (on && NonUniform) {  // (before the parameters are taken: a refusal changes nothing)
+        std::cerr << "Renderer: temporal history after adaptive sampling retired blocks: the blend takes one path count." << std::endl;
+        return false;
+    }
     if (tp) {
         // the ranges gpuart_temporal_accumulate accepts: a commit inside a setter has nobody to report them to
         if (!finite(tp->max_history) || !(tp->max_history >= 0) || !finite(tp->plane_tol) || !(tp->plane_tol >= 0) ||
@@ -515,6 +561,10 @@ int Renderer::RenderUntil(float threshold, float maxAboveShare, unsigned batchPa
         std::cerr << "Renderer: RenderUntil arguments out of range." << std::endl;
         return -1;
     }
+    if (NonUniform) {
+        std::cerr << "Renderer: RenderUntil after adaptive sampling retired blocks: its estimate keeps one path count for the frame (RenderAdaptive continues)." << std::endl;
+        return -1;
+    }
     if (!Converge && !Check(gpuart_converge_create(Device, &Converge), "creating the convergence estimator", CV)) return -1;
     if (!checkHip(hipSetDevice(Device), "hipSetDevice")) return -1;
     const size_t n = (size_t)Tile.w * Tile.h;
@@ -528,6 +578,7 @@ int Renderer::RenderUntil(float threshold, float maxAboveShare, unsigned batchPa
                    "updating the convergence estimate", CV)) return false;
         ConvergeTotal = PathTracing.numPathsRendered;
         ConvergeBatches++;
+        AdaptiveIsLast = false;
         return Check(gpuart_converge_finish(Converge), "updating the convergence estimate", CV);
     };
     // paths the estimate has never seen — a loaded checkpoint, plain passes after a restart — are its first batch, of their own weight
@@ -554,14 +605,93 @@ int Renderer::RenderUntil(float threshold, float maxAboveShare, unsigned batchPa
     }
 }
 
+// ---- adaptive sampling (include/gpuart_adaptive.h) ------------------------------------------------------------------------------
+void Renderer::ResetAdaptiveNow() {
+    gpuart_adaptive_reset(Adaptive);
+    AdaptiveBatches = AdaptiveTotal = AdaptiveActive = 0;
+    NonUniform = AdaptiveIsLast = false;
+}
+
+int Renderer::RenderAdaptive(float threshold, unsigned minPaths, unsigned batchPaths, float lumFloor, gpuart_adaptive_summary *last) {
+    if (!IsOK) return -1;
+    if (!finite(threshold) || !(threshold >= 0) || minPaths == 0 || batchPaths == 0 || !finite(lumFloor) || !(lumFloor > 0)) {
+        std::cerr << "Renderer: RenderAdaptive arguments out of range." << std::endl;
+        return -1;
+    }
+    if (TemporalOn) {
+        std::cerr << "Renderer: RenderAdaptive while temporal history is on: the blend takes one path count." << std::endl;
+        return -1;
+    }
+    if (!Adaptive && !Check(gpuart_adaptive_create(Device, &Adaptive), "creating the adaptive estimator", AD)) return -1;
+    if (!checkHip(hipSetDevice(Device), "hipSetDevice")) return -1;
+    const size_t n = (size_t)Tile.w * Tile.h;
+    if (!AdaptiveMem.Fit(n, 16, "allocating the estimator's copy of the accumulator")) return -1;
+    std::vector<uint32_t> list(TileBlocks());
+    // the raw accumulator and the blocks' counts as one more batch, in buffers of its own (RenderUntil's showAccumulator)
+    auto showAccumulator = [&]() {
+        if (!Check(gpuart_hip_export(Backend, 1, AdaptiveMem.mem, 1.0f), "exporting the accumulator") || !StageBlockPaths()) return false;
+        if (!Check(gpuart_hip_finish(Backend), "waiting for the device")) return false;
+        if (!Check(gpuart_adaptive_update(Adaptive, (const float *)AdaptiveMem.mem, BlockPathsMem, Tile.w, Tile.h), "updating the adaptive estimate", AD))
+            return false;
+        AdaptiveTotal = PathTracing.numPathsRendered;
+        AdaptiveBatches++;
+        AdaptiveIsLast = true;
+        return Check(gpuart_adaptive_finish(Adaptive), "updating the adaptive estimate", AD);
+    };
+    if (AdaptiveBatches == 0 && PathTracing.numPathsRendered > 0 && !showAccumulator()) return -1;
+    for (;;) {
+        if (PathTracing.numPathsRendered < PathTracing.pathsPerPixel) {
+            const unsigned target = PathTracing.numPathsRendered + std::min(batchPaths, PathTracing.pathsPerPixel - PathTracing.numPathsRendered);
+            const unsigned per = std::max(1u, PathTracing.pathsPerPass);
+            gpuart_hip_pt_plan(Backend, (target - PathTracing.numPathsRendered + per - 1) / per);
+            while (PathTracing.numPathsRendered < target) {
+                const unsigned before = PathTracing.numPathsRendered;
+                if (RenderPathTracingPass() == before) return -1;  // (the pass failed: Check has said why)
+            }
+        }
+        if (PathTracing.numPathsRendered > AdaptiveTotal && !showAccumulator()) return -1;
+        if (AdaptiveBatches >= 2) {
+            gpuart_adaptive_summary s;
+            if (!Check(gpuart_adaptive_select(Adaptive, threshold, lumFloor, minPaths, nullptr, list.data(), &s), "selecting the active blocks", AD)) return -1;
+            if (last) *last = s;
+            // the list only ever shrinks: the same length is the same list
+            if (s.active_blocks < s.blocks && (!NonUniform || s.active_blocks != AdaptiveActive)) {
+                if (!Check(gpuart_hip_set_active_blocks(Backend, list.data(), s.active_blocks), "setting the active blocks")) return -1;
+                NonUniform = true;
+                AdaptiveActive = s.active_blocks;
+            }
+            if (s.active_blocks == 0) return 1;
+        }
+        if (PathTracing.numPathsRendered >= PathTracing.pathsPerPixel) return 0;
+    }
+}
+
+bool Renderer::ReadSampleCounts(uint32_t *perPixel) {
+    if (!IsOK || !perPixel) return false;
+    std::vector<uint32_t> counts(TileBlocks());
+    if (!Check(gpuart_hip_read_block_paths(Backend, counts.data()), "reading the block counts")) return false;
+    const unsigned bw = (Tile.w + 7) / 8;
+    for (unsigned y = 0; y < Tile.h; y++)
+        for (unsigned x = 0; x < Tile.w; x++) perPixel[(size_t)y * Tile.w + x] = counts[(size_t)(y / 8) * bw + x / 8] + CountBase;
+    return true;
+}
+
 bool Renderer::ReadErrorMap(float *e, float lumFloor) {
+    if (IsOK && e && Adaptive && AdaptiveIsLast && AdaptiveBatches >= 2) {  // RenderAdaptive saw the last batch: its map
+        const size_t n = (size_t)Tile.w * Tile.h;
+        if (!RefineMem.Fit(n, 4, "allocating the error map")) return false;
+        if (!Check(gpuart_adaptive_error_map(Adaptive, lumFloor, (float *)RefineMem.mem, Tile.w, Tile.h), "reading the error map", AD) ||
+            !Check(gpuart_adaptive_finish(Adaptive), "reading the error map", AD)) return false;
+        return checkHip(hipMemcpy(e, RefineMem.mem, n * 4, hipMemcpyDeviceToHost), "reading the error map");
+    }
     if (!IsOK || !e || !Converge || ConvergeBatches < 2) return false;
     gpuart_converge_summary s;
     return Check(gpuart_converge_measure_host(Converge, 0.0f, lumFloor, e, &s), "reading the error map", CV);
 }
 
 bool Renderer::ReadRefined(float *rgba, float lumFloor, const gpuart_refine_params *p) {
-    if (!IsOK || !rgba || !Converge || ConvergeBatches < 2) return false;
+    const bool adaptive = Adaptive && AdaptiveIsLast && AdaptiveBatches >= 2;
+    if (!IsOK || !rgba || (!adaptive && (!Converge || ConvergeBatches < 2))) return false;
     if (!Refine && !Check(gpuart_refine_create(Device, &Refine), "creating the variance-guided filter", RF)) return false;
     if (!StageView()) return false;
     const size_t n = (size_t)Tile.w * Tile.h;
@@ -569,7 +699,10 @@ bool Renderer::ReadRefined(float *rgba, float lumFloor, const gpuart_refine_para
     const ViewBuffers b(DenoiseMem.mem, n);
     // a measure changes nothing of the estimate; it waits for the map itself
     gpuart_converge_summary s;
-    if (!Check(gpuart_converge_measure(Converge, 0.0f, lumFloor, (float *)RefineMem.mem, &s), "measuring the error map", CV)) return false;
+    if (adaptive) {
+        if (!Check(gpuart_adaptive_error_map(Adaptive, lumFloor, (float *)RefineMem.mem, Tile.w, Tile.h), "measuring the error map", AD) ||
+            !Check(gpuart_adaptive_finish(Adaptive), "measuring the error map", AD)) return false;
+    } else if (!Check(gpuart_converge_measure(Converge, 0.0f, lumFloor, (float *)RefineMem.mem, &s), "measuring the error map", CV)) return false;
     if (!Check(gpuart_refine_run(Refine, b.radiance, b.hits, b.prims, UserSphere.flags, (const float *)RefineMem.mem, lumFloor, Tile.w, Tile.h, p,
                                  b.filtered), "filtering", RF)) return false;
     if (!Check(gpuart_refine_finish(Refine), "filtering", RF)) return false;
@@ -590,6 +723,10 @@ struct CkHeader {
 
 bool Renderer::SaveCheckpoint(const char *fileName) {
     if (!IsOK) return false;
+    if (NonUniform) {
+        std::cerr << "Renderer: SaveCheckpoint after adaptive sampling retired blocks: a checkpoint holds one path count." << std::endl;
+        return false;
+    }
     std::vector<float> acc((size_t)Tile.w * Tile.h * 4);
     if (!ReadRadiance(acc.data(), false)) return false;
     std::ostringstream rng;
@@ -632,10 +769,14 @@ bool Renderer::LoadCheckpoint(const char *fileName) {
     std::mt19937 gen;
     rng >> gen;
     if (rng.fail()) return false;
-    if (!Check(gpuart_hip_write(Backend, 1, acc.data()), "restoring the radiance accumulator")) return false;
+    // (the reset drops an active block list and the back end's block counts: the checkpoint's paths are CountBase from here on)
+    if (!Check(gpuart_hip_pt_reset(Backend), "clearing the radiance accumulator") ||
+        !Check(gpuart_hip_write(Backend, 1, acc.data()), "restoring the radiance accumulator")) return false;
     RndGen = gen;
     DropTemporalHistory();
     if (Converge) ResetConvergeNow();
+    if (Adaptive) ResetAdaptiveNow();
+    CountBase = h.numPathsRendered;
     PathTracing.numPathsRendered = h.numPathsRendered;
     PathTracing.pathsPerPixel = h.pathsPerPixel;
     PathTracing.pathsPerPass = h.pathsPerPass;

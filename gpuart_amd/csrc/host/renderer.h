@@ -18,6 +18,7 @@
 
 #include "bvh.h"
 #include "core.h"
+#include "gpuart_adaptive.h"
 #include "gpuart_converge.h"
 #include "gpuart_denoise.h"
 #include "gpuart_hip.h"
@@ -129,6 +130,23 @@ public:
     /// passes that follow, the counters, the estimate and RenderUntil's later summaries, the temporal history and the cached G-buffer
     /// are not touched. Synchronises.
     bool ReadRefined(float *rgba, float lumFloor, const gpuart_refine_params *p = nullptr);
+    /// Adaptive sampling (include/gpuart_adaptive.h, gpuart_hip_set_active_blocks): RenderUntil's loop with the estimate kept per 8x8
+    /// block of the tile. It continues the current accumulation in batches of at least batchPaths paths per pixel towards the cap of
+    /// RestartPathTracing / ExtendPathTracing; after every batch the raw accumulator and the blocks' path counts go to the estimator,
+    /// and from the second batch on every block whose pixels all have e <= threshold, and which holds at least minPaths paths and two
+    /// batches, is retired: the passes that follow render the remaining blocks only. Blocks never come back. Returns 1 when no block
+    /// is active, 0 at the cap, -1 on error (arguments out of range included: RenderUntil's checks and minPaths >= 1) and while
+    /// temporal history is on (the blend takes one path count). `last` is filled whenever a select ran. One RandSeed is drawn per pass
+    /// whatever the list is — the draws are those of the same number of plain calls — and a pixel's randomness depends on nothing
+    /// else, so a block that ends with n paths is, bit for bit, that block of a plain render stopped at n paths. Paths already in the
+    /// accumulator (plain passes, a loaded checkpoint, an earlier RenderUntil) are the first batch, of their own weight.
+    /// GetNumPathsRendered keeps counting issued paths: the largest block count. Once a block has been retired the counts are not
+    /// uniform any more: ReadRadiance(normalized), ReadDenoised, ReadPreview and ReadRefined then divide every block by its own count,
+    /// ReadErrorMap / ReadRefined take this estimate's map while it saw the last batch, and RenderUntil, SaveCheckpoint, GatherRadiance
+    /// and SetTemporalHistory(true) are refused until something restarts the accumulation (which also resets this estimate).
+    int RenderAdaptive(float threshold, unsigned minPaths, unsigned batchPaths, float lumFloor, gpuart_adaptive_summary *last = nullptr);
+    /// Paths accumulated into every tile pixel (Tile.w*Tile.h words, row 0 = bottom row): its block's count.
+    bool ReadSampleCounts(uint32_t *perPixel);
     bool Finish();
     void SetMaxPathSegments(unsigned n) { MaxPathSegments = n; DropTemporalHistory(); ResetPathTracing(); }
     void SetMinWeight(float w) { MinWeight = w; DropTemporalHistory(); ResetPathTracing(); }
@@ -202,6 +220,15 @@ private:
     gpuart_converge *Converge = nullptr;  ///< made by the first RenderUntil
     PixelBuffer ConvergeMem;              ///< the raw accumulator of RenderUntil's last batch, 16 B per tile pixel
     unsigned ConvergeBatches = 0, ConvergeTotal = 0;  ///< what Converge has seen since its last reset
+    gpuart_adaptive *Adaptive = nullptr;  ///< made by the first RenderAdaptive
+    PixelBuffer AdaptiveMem;              ///< the raw accumulator of RenderAdaptive's last batch (and the frame a non-uniform ReadRadiance normalises), 16 B per tile pixel
+    uint32_t *BlockPathsMem = nullptr;    ///< device: one word per 8x8 block of the tile, the counts of the last batch or normalisation
+    size_t BlockPathsWords = 0;
+    unsigned AdaptiveBatches = 0, AdaptiveTotal = 0;  ///< what Adaptive has seen since its last reset
+    unsigned AdaptiveActive = 0;          ///< blocks on the back end's list while NonUniform
+    bool NonUniform = false;              ///< a block has been retired: the blocks' path counts differ
+    bool AdaptiveIsLast = false;          ///< the last batch any estimate saw was RenderAdaptive's
+    unsigned CountBase = 0;               ///< paths per pixel a loaded checkpoint brought: the back end's block counts begin above them
     gpuart_refine *Refine = nullptr;      ///< made by the first ReadRefined
     PixelBuffer RefineMem;                ///< ReadRefined's error map, 4 B per tile pixel
     ScreenBasis CurrentBasis;             ///< what SetCamera gave the back end
@@ -227,6 +254,13 @@ private:
     void DropTemporalHistory() { if (HistoryCommitted) DropTemporalHistoryNow(); }
     void DropTemporalHistoryNow();
     void ResetConvergeNow();
+    void ResetAdaptiveNow();
+    size_t TileBlocks() const { return (size_t)((Tile.w + 7) / 8) * ((Tile.h + 7) / 8); }
+    /// The blocks' path counts (the checkpoint's included) into BlockPathsMem; complete after the next gpuart_hip_finish.
+    bool StageBlockPaths();
+    /// The one normalisation: the accumulator divided by the paths rendered into tile-sized device memory, complete on return. While the
+    /// counts are uniform gpuart_hip_export's scalar division, as ever; otherwise the raw export and gpuart_adaptive_normalize.
+    bool ExportNormalized(float *device, bool normalized = true);
     /// A status of the back end or, with their gpuart_*_last_error, of one of the image libraries: false (std::cerr says why) unless 0.
     bool Check(int status, const char *what, const char *(*lastError)(void) = gpuart_hip_last_error);
 };

@@ -125,6 +125,25 @@ int gpuart_hip_write(gpuart_hip_ctx *ctx, int which, const float *rgba_host);
  * hands it to RCCL). Asynchronous on the context's stream; call gpuart_hip_finish before use. */
 int gpuart_hip_export(gpuart_hip_ctx *ctx, int which, void *rgba_device, float divide_by);
 
+/* ---- adaptive sampling: passes over some of the tile's 8x8 blocks (no reference counterpart) ----------------------------
+ * The tile's pixels form ceil(tw/8) x ceil(th/8) blocks of 8x8 (ragged at the right and top edges), numbered row-major in the
+ * tile's local order. With an active list set, gpuart_hip_pt_pass does for every pixel of a listed block, and for no other pixel,
+ * what it does without one: a pixel's randomness depends on the pass's RandSeed and the path's own hit points only. So after any
+ * sequence of passes and list changes accum[p] is the fp32 sum, in pass order, of the pass colours of exactly those passes whose
+ * list held p's block.
+ *
+ * blocks: host memory, n indices, strictly ascending, each below the number of blocks; anything else is GPUART_HIP_ERR_ARG and
+ * nothing changes. blocks == NULL: all blocks again (and the library's own birth order). n == 0 with a pointer: the empty list —
+ * passes succeed, launch nothing and count nothing. Collected passes are flushed first. gpuart_hip_pt_reset clears the list and the
+ * counts; gpuart_hip_resize, _set_tile, _set_tile_interleaved and _set_share drop both. A list is honoured in modes 0, 3 and 5;
+ * gpuart_hip_pt_pass in modes 1, 2 and 4 with a list set is GPUART_HIP_ERR_ARG. */
+int gpuart_hip_set_active_blocks(gpuart_hip_ctx *ctx, const uint32_t *blocks, size_t n);
+/* Paths per pixel accumulated into each block since the last gpuart_hip_pt_reset, one word per block, with or without a list ever
+ * set (gpuart_hip_write does not count). _read: to host memory, synchronises the stream. _export: to caller-owned device memory,
+ * asynchronous on the context's stream like gpuart_hip_export. Both flush collected passes first. */
+int gpuart_hip_read_block_paths(gpuart_hip_ctx *ctx, uint32_t *host);
+int gpuart_hip_export_block_paths(gpuart_hip_ctx *ctx, void *device);
+
 /* ---- one frame on several GPUs ---------------------------------------------------------------
  * The frame is sharded by rows: bands of `band_rows` rows dealt round-robin to the ranks; ranks exchange nothing per pass;
  * when the passes are done every rank sends its rows to one root over RCCL (point-to-point over xGMI) and the root scatters

@@ -35,6 +35,11 @@ int gpuart_hip_test_bounded_call(uint32_t hold_ms, uint32_t timeout_ms, int mark
  *             1 if it goes through k_run, passes still pending afterwards }
  * Returns the number of runs (which may exceed max_runs: only the first max_runs are stored), or a negative error. */
 int gpuart_hip_test_planner(const uint32_t cfg[8], const uint32_t *ops, int n_ops, uint32_t *runs, int max_runs);
+/* The same with the planner's other input, the active block list of adaptive sampling: one more op, 7 ACTIVE(blocks, -) =
+ * gpuart_hip_set_active_blocks with a list of that many blocks (it flushes; 0 drops the list), and the second word of a record is the
+ * path slots of one pass of THAT run (64 x blocks while a list is set) — what run lengths and the k_run / pipeline choice are planned
+ * from, while max_batch stays the allocation's. */
+int gpuart_hip_test_planner_active(const uint32_t cfg[8], const uint32_t *ops, int n_ops, uint32_t *runs, int max_runs);
 
 /* Which instantiation of the BVH-query kernels a launch runs (pure host code: needs no device and no context): the rule every launch
  * site of the library takes its template arguments from (csrc/hip/gpuart_hip.hip kernel_choice), asked with a context's state as
