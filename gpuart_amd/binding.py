@@ -93,6 +93,19 @@ def refine_params(params):
     return _params(RefineParams, REFINE_DEFAULTS, "refine", params)
 
 
+class MomentsParams(C.Structure):
+    """gpuart_moments_params (include/gpuart_moments.h)."""
+    _fields_ = [("min_batches", C.c_float), ("spatial_k", C.c_float)]
+
+
+MOMENTS_DEFAULTS = dict(min_batches=8.0, spatial_k=4.0)
+
+
+def moments_params(params):
+    """None (the library's defaults), a MomentsParams, or a dict of fields that replace the defaults -> MomentsParams or None."""
+    return _params(MomentsParams, MOMENTS_DEFAULTS, "moments", params)
+
+
 class TemporalParams(C.Structure):
     """gpuart_temporal_params (include/gpuart_temporal.h)."""
     _fields_ = [("max_history", C.c_float), ("plane_tol", C.c_float), ("normal_min", C.c_float)]
@@ -223,6 +236,11 @@ def refine_lib():
 def adaptive_lib():
     """libgpuart_adaptive.so; raises NativeLibraryMissing if it has not been built (no fallback)."""
     return _image_lib("adaptive")
+
+
+def moments_lib():
+    """libgpuart_moments.so; raises NativeLibraryMissing if it has not been built (no fallback)."""
+    return _image_lib("moments")
 
 
 def host_lib():
@@ -988,6 +1006,27 @@ class Renderer:
                                                                   temporal_lib().gpuart_temporal_last_error().decode()))
         return out
 
+    def set_history_variance(self, on=True, params=None):
+        """Renderer::SetHistoryVariance: while on, every commit of set_temporal_history also carries the luminance's moments through a
+        second history (include/gpuart_moments.h); turning it on or off drops the temporal history. params = None (the defaults), a
+        MomentsParams or a dict of fields that replace the defaults: read_guided_preview's error map."""
+        p = moments_params(params)
+        if not self.L.gpuart_renderer_set_history_variance(self.h, C.c_int(1 if on else 0), C.byref(p) if p is not None else None):
+            raise ValueError("moments parameters out of range")
+
+    def read_guided_preview(self, lum_floor=CONVERGE_DEFAULT_FLOOR, refine=None, temporal=None):
+        """Renderer::ReadGuidedPreview: the history blended with the accumulator, then filtered by the variance-guided filter with the
+        error map of the history's measured variance, (th, tw, 4) float32. refine as Refine.run's params; temporal as
+        Temporal.accumulate's (None: set_temporal_history's). None while set_history_variance or set_temporal_history is off and
+        before the view's first path."""
+        _, _, tw, th = self.tile
+        out = np.empty((th, tw, 4), np.float32)
+        rf, tp = refine_params(refine), temporal_params(temporal)
+        if not self.L.gpuart_renderer_read_guided_preview(self.h, _p(out), C.c_float(lum_floor), C.byref(rf) if rf is not None else None,
+                                                          C.byref(tp) if tp is not None else None):
+            return None
+        return out
+
     def render_until(self, threshold, max_above_share=0.0, batch_paths=CONVERGE_DEFAULT_BATCH, lum_floor=CONVERGE_DEFAULT_FLOOR):
         """Renderer::RenderUntil: continue the current accumulation (restart_path_tracing's target is the cap) in batches of at least
         batch_paths paths per pixel until at most max_above_share of the tile's pixels have a relative standard error of their
@@ -1285,6 +1324,75 @@ class Temporal(_ImageHandle):
         self._chk(self.L.gpuart_temporal_accumulate_host(self.h, _p(rgba), C.c_uint32(spp), _p(hits), _p(prims), C.c_uint32(w), C.c_uint32(h),
                                                          C.byref(view), pp, C.c_int(1 if commit else 0), _p(res), _p(ln)))
         return res, ln
+
+
+# ---- the history's measured variance (include/gpuart_moments.h) -------------------------------------------------------------
+class MomentsError(RuntimeError):
+    """A gpuart_moments_* call returned an error; `code` is the library's (GPUART_HIP_ERR_*)."""
+    code = None
+
+
+class Moments(_ImageHandle):
+    """A gpuart_moments handle on one device."""
+    NAME, Error = "moments", MomentsError
+
+    def pack(self, rgba, spp, out=None):
+        """rgba (h, w, 4) float32, the mean of spp paths -> {L, L*L, 1/spp, a}, the image a second Temporal handle carries. A torch
+        tensor on this handle's device runs through gpuart_moments_pack (torch's current stream is synchronised first, the handle
+        before returning; out may be rgba itself); a NumPy array through gpuart_moments_pack_host. The result is `out` or a new image."""
+        if type(rgba).__module__.startswith("torch"):
+            import torch
+            dev = torch.device("cuda", self.device)
+            if rgba.dtype != torch.float32 or rgba.dim() != 3 or rgba.shape[2] != 4 or not rgba.is_contiguous() or rgba.device != dev:
+                raise ValueError("rgba must be a contiguous (h, w, 4) float32 tensor on %s" % dev)
+            res = out if out is not None else torch.empty_like(rgba)
+            if res.dtype != torch.float32 or res.shape != rgba.shape or not res.is_contiguous() or res.device != dev:
+                raise ValueError("out must be a contiguous (h, w, 4) float32 tensor on %s" % dev)
+            torch.cuda.current_stream(dev).synchronize()
+            self._chk(self.L.gpuart_moments_pack(self.h, _dp(rgba), C.c_uint32(spp), C.c_uint32(rgba.shape[1]), C.c_uint32(rgba.shape[0]), _dp(res)))
+            self.finish()
+            return res
+        rgba = np.ascontiguousarray(rgba, np.float32)
+        if rgba.ndim != 3 or rgba.shape[2] != 4:
+            raise ValueError("rgba must be (h, w, 4) float32")
+        res = out if out is not None else np.empty_like(rgba)
+        if res.dtype != np.float32 or res.shape != rgba.shape or not res.flags.c_contiguous:
+            raise ValueError("out must be a contiguous (h, w, 4) float32 array")
+        self._chk(self.L.gpuart_moments_pack_host(self.h, _p(rgba), C.c_uint32(spp), C.c_uint32(rgba.shape[1]), C.c_uint32(rgba.shape[0]), _p(res)))
+        return res
+
+    def error(self, rgba, length, moments, hits, prims, lum_floor=CONVERGE_DEFAULT_FLOOR, us_flags=0, params=None, out=None):
+        """The error map (h, w) float32 of a pair of blends: rgba and length are what Temporal.accumulate returned for the radiance,
+        moments what a second handle returned for the packed image; hits, prims, us_flags as Denoiser.run; params = None (the
+        defaults), a MomentsParams or a dict of fields that replace the defaults. torch tensors on this handle's device run through
+        gpuart_moments_error, NumPy arrays through gpuart_moments_error_host. The result is `out` or a new map."""
+        p = moments_params(params)
+        pp = C.byref(p) if p is not None else None
+        dev, rgba, hits, prims, _, h, w = _gbuffer_args(self.device, rgba, hits, prims, None)
+        if dev is not None:
+            import torch
+            for name, a, shape in (("length", length, (h, w)), ("moments", moments, (h, w, 4))):
+                if not type(a).__module__.startswith("torch") or a.dtype != torch.float32 or tuple(a.shape) != shape or not a.is_contiguous() or \
+                        a.device != dev:
+                    raise ValueError("%s must be a contiguous %s float32 tensor on %s" % (name, shape, dev))
+            res = out if out is not None else torch.empty((h, w), dtype=torch.float32, device=dev)
+            if res.dtype != torch.float32 or tuple(res.shape) != (h, w) or not res.is_contiguous() or res.device != dev:
+                raise ValueError("out must be a contiguous (h, w) float32 tensor on %s" % dev)
+            torch.cuda.current_stream(dev).synchronize()
+            self._chk(self.L.gpuart_moments_error(self.h, _dp(rgba), _dp(length), _dp(moments), _dp(hits), _dp(prims), C.c_uint32(us_flags),
+                                                  C.c_float(lum_floor), C.c_uint32(w), C.c_uint32(h), pp, _dp(res)))
+            self.finish()
+            return res
+        length = np.ascontiguousarray(length, np.float32)
+        moments = np.ascontiguousarray(moments, np.float32)
+        if length.shape != (h, w) or moments.shape != (h, w, 4):
+            raise ValueError("length must be (h, w) and moments (h, w, 4) float32")
+        res = out if out is not None else np.empty((h, w), np.float32)
+        if res.dtype != np.float32 or res.shape != (h, w) or not res.flags.c_contiguous:
+            raise ValueError("out must be a contiguous (h, w) float32 array")
+        self._chk(self.L.gpuart_moments_error_host(self.h, _p(rgba), _p(length), _p(moments), _p(hits), _p(prims), C.c_uint32(us_flags),
+                                                   C.c_float(lum_floor), C.c_uint32(w), C.c_uint32(h), pp, _p(res)))
+        return res
 
 
 # ---- the convergence estimate (include/gpuart_converge.h) -----------------------------------------------------------------

@@ -281,6 +281,13 @@ int gpuart_renderer_read_error_map(gpuart_renderer *r, float *e, float lumFloor)
 int gpuart_renderer_read_refined(gpuart_renderer *r, float *rgba, float lumFloor, const gpuart_refine_params *p) {
     return r->impl.ReadRefined(rgba, lumFloor, p) ? 1 : 0;
 }
+int gpuart_renderer_set_history_variance(gpuart_renderer *r, int on, const gpuart_moments_params *p) {
+    return r->impl.SetHistoryVariance(on != 0, p) ? 1 : 0;
+}
+int gpuart_renderer_read_guided_preview(gpuart_renderer *r, float *rgba, float lumFloor, const gpuart_refine_params *rf,
+                                        const gpuart_temporal_params *tp) {
+    return r->impl.ReadGuidedPreview(rgba, lumFloor, rf, tp) ? 1 : 0;
+}
 int gpuart_renderer_render_adaptive(gpuart_renderer *r, float threshold, unsigned minPaths, unsigned batchPaths, float lumFloor,
                                     gpuart_adaptive_summary *last) {
     return r->impl.RenderAdaptive(threshold, minPaths, batchPaths, lumFloor, last);

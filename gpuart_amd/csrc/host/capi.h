@@ -10,6 +10,7 @@
 #include "gpuart_converge.h"
 #include "gpuart_denoise.h"
 #include "gpuart_hip.h"
+#include "gpuart_moments.h"
 #include "gpuart_refine.h"
 #include "gpuart_temporal.h"
 
@@ -101,6 +102,14 @@ int gpuart_renderer_read_error_map(gpuart_renderer *r, float *e, float lumFloor)
 /* Renderer::ReadRefined: the normalised accumulator filtered by the error map of the last batch (include/gpuart_refine.h); p = NULL:
  * the defaults. 1 on success, 0 before the second batch or on error. */
 int gpuart_renderer_read_refined(gpuart_renderer *r, float *rgba, float lumFloor, const gpuart_refine_params *p);
+/* Renderer::SetHistoryVariance: carry the luminance's moments through a second history (include/gpuart_moments.h); toggling drops the
+ * temporal history. p = NULL: the defaults. 1 on success, 0 for parameters out of range. */
+int gpuart_renderer_set_history_variance(gpuart_renderer *r, int on, const gpuart_moments_params *p);
+/* Renderer::ReadGuidedPreview: the history blend filtered by gpuart_refine_run with the error map of the history's measured variance.
+ * rf, tp = NULL: the defaults / what gpuart_renderer_set_temporal_history was given. 1 on success; 0 while the variance or the
+ * history is off, before the view's first path, or on error. */
+int gpuart_renderer_read_guided_preview(gpuart_renderer *r, float *rgba, float lumFloor, const gpuart_refine_params *rf,
+                                        const gpuart_temporal_params *tp);
 /* Renderer::RenderAdaptive: 1 no block is active any more, 0 the cap was reached first, -1 error; last (may be NULL) is filled whenever
  * a select ran. */
 int gpuart_renderer_render_adaptive(gpuart_renderer *r, float threshold, unsigned minPaths, unsigned batchPaths, float lumFloor,

@@ -64,6 +64,7 @@ Renderer::Renderer(unsigned viewportWidth, unsigned viewportHeight, const Camera
     CurrentCamera = camera;
     Device = device;
     gpuart_temporal_defaults(&TemporalParams);
+    gpuart_moments_defaults(&MomentsParams);
 
     if (!Check(gpuart_hip_create(device, &Backend), "creating the device back end")) return;
     if (viewportWidth == 0 || viewportHeight == 0) {
@@ -82,6 +83,9 @@ Renderer::~Renderer() {
     if (BlockPathsMem) (void)hipFree(BlockPathsMem);
     if (Converge) gpuart_converge_destroy(Converge);
     ConvergeMem.Release();
+    if (Moments) gpuart_moments_destroy(Moments);
+    if (TemporalMoments) gpuart_temporal_destroy(TemporalMoments);
+    MomentsMem.Release();
     if (Temporal) gpuart_temporal_destroy(Temporal);
     if (Denoiser) gpuart_denoise_destroy(Denoiser);
     DenoiseMem.Release();
@@ -389,7 +393,7 @@ bool Renderer::ReadRadiance(float *rgba, bool normalized) {
 
 namespace {
 const auto DN = gpuart_denoise_last_error, TP = gpuart_temporal_last_error, CV = gpuart_converge_last_error,
-           RF = gpuart_refine_last_error, AD = gpuart_adaptive_last_error;  // for Check
+           RF = gpuart_refine_last_error, AD = gpuart_adaptive_last_error, MO = gpuart_moments_last_error;  // for Check
 bool finite(float x) { return x - x == 0.0f; }
 bool checkHip(hipError_t e, const char *what) {
     if (e == hipSuccess) return true;
@@ -405,6 +409,12 @@ struct ViewBuffers {
     ViewBuffers(void *mem, size_t n)
         : radiance((float *)mem), hits((gpuart_ray_hit *)((char *)mem + n * 16)), filtered((float *)((char *)mem + n * 48)),
           prims((int32_t *)((char *)mem + n * 64)) {}
+};
+/// MomentsMem's planes: the packed moments, their blend, the radiance blend's len and the error map.
+struct MomentBuffers {
+    float *packed, *blend, *len, *e;
+    MomentBuffers(void *mem, size_t n)
+        : packed((float *)mem), blend((float *)((char *)mem + n * 16)), len((float *)((char *)mem + n * 32)), e((float *)((char *)mem + n * 36)) {}
 };
 }  // namespace
 
@@ -503,6 +513,7 @@ bool Renderer::SetTemporalHistory(bool on, const gpuart_temporal_params *tp) {
 
 void Renderer::DropTemporalHistoryNow() {
     if (Temporal) gpuart_temporal_reset(Temporal);
+    if (TemporalMoments) gpuart_temporal_reset(TemporalMoments);
     HistoryCommitted = false;
 }
 
@@ -527,9 +538,75 @@ void Renderer::CommitTemporalView() {
         ok = Check(gpuart_temporal_accumulate(Temporal, b.radiance, PathTracing.numPathsRendered, b.hits, b.prims, Tile.w, Tile.h, &v,
                                               &TemporalParams, 1, b.filtered, nullptr), "committing the view to the history", TP) &&
              Check(gpuart_temporal_finish(Temporal), "committing the view to the history", TP);
+        if (ok && VarianceOn) {  // the same commit for the moments: the two histories have seen the same views or none
+            const size_t n = (size_t)Tile.w * Tile.h;
+            ok = EnsureVarianceHandles();
+            if (ok) {
+                const MomentBuffers mb(MomentsMem.mem, n);
+                ok = Check(gpuart_moments_pack(Moments, b.radiance, PathTracing.numPathsRendered, Tile.w, Tile.h, mb.packed), "packing the moments", MO) &&
+                     Check(gpuart_moments_finish(Moments), "packing the moments", MO) &&
+                     Check(gpuart_temporal_accumulate(TemporalMoments, mb.packed, PathTracing.numPathsRendered, b.hits, b.prims, Tile.w, Tile.h, &v,
+                                                      &TemporalParams, 1, mb.blend, nullptr), "committing the moments to their history", TP) &&
+                     Check(gpuart_temporal_finish(TemporalMoments), "committing the moments to their history", TP);
+            }
+        }
     }
     HistoryCommitted = ok;
-    if (!ok && Temporal) gpuart_temporal_reset(Temporal);
+    if (!ok) {
+        if (Temporal) gpuart_temporal_reset(Temporal);
+        if (TemporalMoments) gpuart_temporal_reset(TemporalMoments);
+    }
+}
+
+// ---- the history's measured variance (include/gpuart_moments.h) -----------------------------------------------------------
+bool Renderer::SetHistoryVariance(bool on, const gpuart_moments_params *p) {
+    if (p) {
+        // the ranges gpuart_moments_error accepts
+        if (!finite(p->min_batches) || !(p->min_batches > 1) || !finite(p->spatial_k) || !(p->spatial_k >= 0)) {
+            std::cerr << "Renderer: moments parameters out of range." << std::endl;
+            return false;
+        }
+        MomentsParams = *p;
+    } else {
+        gpuart_moments_defaults(&MomentsParams);
+    }
+    if (on != VarianceOn) DropTemporalHistory();  // a history the other handle has not seen
+    VarianceOn = on;
+    return true;
+}
+
+bool Renderer::EnsureVarianceHandles() {
+    if (!checkHip(hipSetDevice(Device), "hipSetDevice")) return false;
+    if (!Temporal && !Check(gpuart_temporal_create(Device, &Temporal), "creating the temporal accumulator", TP)) return false;
+    if (!TemporalMoments && !Check(gpuart_temporal_create(Device, &TemporalMoments), "creating the moments' temporal accumulator", TP)) return false;
+    if (!Moments && !Check(gpuart_moments_create(Device, &Moments), "creating the moments library's handle", MO)) return false;
+    return MomentsMem.Fit((size_t)Tile.w * Tile.h, 16 + 16 + 4 + 4, "allocating the moments' buffers");
+}
+
+bool Renderer::ReadGuidedPreview(float *rgba, float lumFloor, const gpuart_refine_params *rf, const gpuart_temporal_params *tp) {
+    if (!IsOK || !rgba || !VarianceOn || !TemporalOn || PathTracing.numPathsRendered == 0) return false;
+    if (!Refine && !Check(gpuart_refine_create(Device, &Refine), "creating the variance-guided filter", RF)) return false;
+    gpuart_temporal_view v;
+    if (!EnsureVarianceHandles() || !StageView() || !MakeTemporalView(v)) return false;
+    const size_t n = (size_t)Tile.w * Tile.h;
+    const unsigned spp = PathTracing.numPathsRendered;
+    const ViewBuffers b(DenoiseMem.mem, n);
+    const MomentBuffers mb(MomentsMem.mem, n);
+    if (!tp) tp = &TemporalParams;
+    // (without a commit both handles have no history: every blend is its input and len = s)
+    if (!Check(gpuart_temporal_accumulate(Temporal, b.radiance, spp, b.hits, b.prims, Tile.w, Tile.h, &v, tp, 0, b.filtered, mb.len),
+               "blending the history", TP) || !Check(gpuart_temporal_finish(Temporal), "blending the history", TP)) return false;
+    if (!Check(gpuart_moments_pack(Moments, b.radiance, spp, Tile.w, Tile.h, mb.packed), "packing the moments", MO) ||
+        !Check(gpuart_moments_finish(Moments), "packing the moments", MO)) return false;
+    if (!Check(gpuart_temporal_accumulate(TemporalMoments, mb.packed, spp, b.hits, b.prims, Tile.w, Tile.h, &v, tp, 0, mb.blend, nullptr),
+               "blending the moments' history", TP) || !Check(gpuart_temporal_finish(TemporalMoments), "blending the moments' history", TP)) return false;
+    if (!Check(gpuart_moments_error(Moments, b.filtered, mb.len, mb.blend, b.hits, b.prims, UserSphere.flags, lumFloor, Tile.w, Tile.h, &MomentsParams,
+                                    mb.e), "measuring the history's variance", MO) ||
+        !Check(gpuart_moments_finish(Moments), "measuring the history's variance", MO)) return false;
+    // (the filter may run in place: include/gpuart_refine.h)
+    if (!Check(gpuart_refine_run(Refine, b.filtered, b.hits, b.prims, UserSphere.flags, mb.e, lumFloor, Tile.w, Tile.h, rf, b.filtered), "filtering", RF) ||
+        !Check(gpuart_refine_finish(Refine), "filtering", RF)) return false;
+    return checkHip(hipMemcpy(rgba, b.filtered, n * 16, hipMemcpyDeviceToHost), "reading the guided preview");
 }
 
 bool Renderer::ReadPreview(float *rgba, const gpuart_denoise_params *dn, const gpuart_temporal_params *tp) {

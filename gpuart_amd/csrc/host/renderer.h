@@ -8,7 +8,7 @@
 // MAX_PATH_SEGMENTS / the RNG seed / the viewport fixed at compile time):
 //   ReadDirectLighting, ReadRadiance, Finish, SetMaxPathSegments, SetMinWeight, SetSeed,
 //   SetTile, GetBackend, ComputeScreenBasis, GetNumPathsRendered, ReadDenoised, SetTemporalHistory, ReadPreview, RenderUntil,
-//   ReadErrorMap, ReadRefined.
+//   ReadErrorMap, ReadRefined, SetHistoryVariance, ReadGuidedPreview.
 #ifndef GPUART_RENDERER_H
 #define GPUART_RENDERER_H
 
@@ -22,6 +22,7 @@
 #include "gpuart_converge.h"
 #include "gpuart_denoise.h"
 #include "gpuart_hip.h"
+#include "gpuart_moments.h"
 #include "gpuart_refine.h"
 #include "gpuart_temporal.h"
 #include "math_types.h"
@@ -109,6 +110,20 @@ public:
     /// (dn). Exactly ReadDenoised while history is off, before the first commit, and before the view's first path. The history, the
     /// accumulator, the passes that follow and the counters are not touched. Synchronises.
     bool ReadPreview(float *rgba, const gpuart_denoise_params *dn = nullptr, const gpuart_temporal_params *tp = nullptr);
+    /// Carries the moments of the luminance through a second history (include/gpuart_moments.h); off by default. While it is on, every
+    /// commit of SetTemporalHistory also commits the packed image {L, L*L, 1/s, a} of the same view to a second gpuart_temporal handle,
+    /// with the same G-buffer, view and parameters; if either commit fails both histories are dropped. Turning it on or off drops the
+    /// temporal history: the two handles must have seen the same commits. p = nullptr: the library's defaults. False for parameters out
+    /// of range (nothing changes).
+    bool SetHistoryVariance(bool on, const gpuart_moments_params *p = nullptr);
+    bool GetHistoryVariance() const { return VarianceOn; }
+    /// The preview guided by the history's measured variance: the radiance and the packed moments of the current accumulator are blended
+    /// with their histories (gpuart_temporal_accumulate without commit; tp = nullptr: what SetTemporalHistory was given),
+    /// gpuart_moments_error turns the two blends into an error map for lumFloor, and gpuart_refine_run (rf; nullptr: its defaults)
+    /// filters the blended radiance with it. Before the first commit the same sequence runs: every pixel then takes the spatial
+    /// estimate. False while SetHistoryVariance or SetTemporalHistory is off and before the view's first path. The histories, the
+    /// accumulator, the passes that follow, the counters, RenderUntil's estimate and the cached G-buffer are not touched. Synchronises.
+    bool ReadGuidedPreview(float *rgba, float lumFloor, const gpuart_refine_params *rf = nullptr, const gpuart_temporal_params *tp = nullptr);
     /// Render until the noise is below a threshold (include/gpuart_converge.h): continues the current accumulation in batches of at
     /// least batchPaths paths per pixel (whole RenderPathTracingPass calls; the target of RestartPathTracing / ExtendPathTracing is the
     /// cap). After every batch the raw accumulator goes to the estimator, from the second batch on the frame is measured: e = the
@@ -217,6 +232,11 @@ private:
     bool TemporalOn = false;
     bool HistoryCommitted = false;        ///< Temporal holds a history
     gpuart_temporal_params TemporalParams{};  ///< of the commits (SetTemporalHistory)
+    bool VarianceOn = false;                  ///< SetHistoryVariance: the commits also go to TemporalMoments
+    gpuart_temporal *TemporalMoments = nullptr;  ///< the second history: the packed moments, committed whenever Temporal is
+    gpuart_moments *Moments = nullptr;        ///< made with TemporalMoments
+    gpuart_moments_params MomentsParams{};    ///< of ReadGuidedPreview's error map (SetHistoryVariance)
+    PixelBuffer MomentsMem;                   ///< the packed moments (16 B), their blend (16), len (4) and e (4) per tile pixel
     gpuart_converge *Converge = nullptr;  ///< made by the first RenderUntil
     PixelBuffer ConvergeMem;              ///< the raw accumulator of RenderUntil's last batch, 16 B per tile pixel
     unsigned ConvergeBatches = 0, ConvergeTotal = 0;  ///< what Converge has seen since its last reset
@@ -251,6 +271,8 @@ private:
     bool StageView();
     bool MakeTemporalView(gpuart_temporal_view &v) const;
     void CommitTemporalView();
+    /// Temporal, TemporalMoments, Moments and MomentsMem for the tile, made where missing.
+    bool EnsureVarianceHandles();
     void DropTemporalHistory() { if (HistoryCommitted) DropTemporalHistoryNow(); }
     void DropTemporalHistoryNow();
     void ResetConvergeNow();
