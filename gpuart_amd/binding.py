@@ -106,6 +106,44 @@ def moments_params(params):
     return _params(MomentsParams, MOMENTS_DEFAULTS, "moments", params)
 
 
+class DisplayParams(C.Structure):
+    """gpuart_display_params (include/gpuart_display.h)."""
+    _fields_ = [("gain", C.c_float), ("auto_exposure", C.c_uint32), ("key", C.c_float), ("lo_share", C.c_float), ("hi_share", C.c_float),
+                ("adapt", C.c_float), ("min_gain", C.c_float), ("max_gain", C.c_float), ("curve", C.c_uint32), ("white", C.c_float),
+                ("transfer", C.c_uint32), ("dither", C.c_uint32)]
+
+
+DISPLAY_DEFAULTS = dict(gain=1.0, auto_exposure=0, key=0.18, lo_share=0.5, hi_share=0.02, adapt=1.0, min_gain=2.0 ** -16, max_gain=2.0 ** 16,
+                        curve=0, white=4.0, transfer=0, dither=0)
+DISPLAY_CURVES = dict(clamp=0, reinhard=1, aces=2)      # GPUART_DISPLAY_CLAMP, _REINHARD, _ACES
+DISPLAY_TRANSFERS = dict(linear=0, srgb=1)              # GPUART_DISPLAY_LINEAR, _SRGB
+DISPLAY_SOURCES = dict(radiance=0, direct=1, denoised=2, preview=3, guided_preview=4, refined=5)   # gpuart_display_source
+
+
+def display_params(params):
+    """None (the library's defaults), a DisplayParams, or a dict of fields that replace the defaults -> DisplayParams or None. In a dict
+    `curve` and `transfer` may be given by name (DISPLAY_CURVES, DISPLAY_TRANSFERS)."""
+    if isinstance(params, dict):
+        params = dict(params)
+        if isinstance(params.get("curve"), str):
+            params["curve"] = DISPLAY_CURVES[params["curve"]]
+        if isinstance(params.get("transfer"), str):
+            params["transfer"] = DISPLAY_TRANSFERS[params["transfer"]]
+        for k in ("auto_exposure", "dither"):
+            if k in params:
+                params[k] = int(params[k])
+    return _params(DisplayParams, DISPLAY_DEFAULTS, "display", params)
+
+
+class DisplayState(C.Structure):
+    """gpuart_display_state (include/gpuart_display.h)."""
+    _fields_ = [("histogram", C.c_uint64 * 256), ("counted", C.c_uint64), ("skipped", C.c_uint64), ("gain", C.c_float), ("valid", C.c_uint32)]
+
+    def as_dict(self):
+        return dict(histogram=[int(v) for v in self.histogram], counted=int(self.counted), skipped=int(self.skipped),
+                    gain=np.float32(self.gain), valid=int(self.valid))
+
+
 class TemporalParams(C.Structure):
     """gpuart_temporal_params (include/gpuart_temporal.h)."""
     _fields_ = [("max_history", C.c_float), ("plane_tol", C.c_float), ("normal_min", C.c_float)]
@@ -241,6 +279,11 @@ def adaptive_lib():
 def moments_lib():
     """libgpuart_moments.so; raises NativeLibraryMissing if it has not been built (no fallback)."""
     return _image_lib("moments")
+
+
+def display_lib():
+    """libgpuart_display.so; raises NativeLibraryMissing if it has not been built (no fallback)."""
+    return _image_lib("display")
 
 
 def host_lib():
@@ -1090,6 +1133,19 @@ class Renderer:
             return None
         return out
 
+    def read_display(self, source="radiance", params=None, lum_floor=CONVERGE_DEFAULT_FLOOR):
+        """Renderer::ReadDisplay: the frame `source` names (DISPLAY_SOURCES: what read_radiance(True), read_direct, read_denoised,
+        read_preview, read_guided_preview or read_refined returns, the filters with their defaults) encoded on the device as 8-bit RGBA
+        (include/gpuart_display.h), (th, tw, 4) uint8, row 0 at the bottom; params as Display.run. None wherever the matching read
+        fails or gives None; ValueError for parameters out of range."""
+        _, _, tw, th = self.tile
+        out = np.empty((th, tw, 4), np.uint8)
+        p = display_params(params)
+        src = DISPLAY_SOURCES[source] if isinstance(source, str) else int(source)
+        if not self.L.gpuart_renderer_read_display(self.h, _p(out), C.c_int(src), C.byref(p) if p is not None else None, C.c_float(lum_floor)):
+            return None
+        return out
+
     def finish(self): return bool(self.L.gpuart_renderer_finish(self.h))
 
     def trace_rays(self, rays, occlusion=False, user_sphere=True, want_prims=False):
@@ -1396,6 +1452,70 @@ class Moments(_ImageHandle):
 
 
 # ---- the convergence estimate (include/gpuart_converge.h) -----------------------------------------------------------------
+# ---- the display stage (include/gpuart_display.h) ----------------------------------------------------------------------------------
+class DisplayError(RuntimeError):
+    """A gpuart_display_* call returned an error; `code` is the library's (GPUART_HIP_ERR_*)."""
+    code = None
+
+
+def srgb_table():
+    """gpuart_display_srgb_table: E[0..255] as float32; needs no device."""
+    out = np.empty(256, np.float32)
+    rc = display_lib().gpuart_display_srgb_table(_p(out))
+    if rc != 0:
+        raise DisplayError("gpuart_display_srgb_table error %d" % rc)
+    return out
+
+
+class Display(_ImageHandle):
+    """A gpuart_display handle on one device: it keeps the adapted exposure between runs."""
+    NAME, Error = "display", DisplayError
+
+    def reset(self):
+        """Forgets the adapted exposure."""
+        self._chk(self._fn("reset")(self.h))
+
+    def run(self, rgba, params=None, origin=(0, 0), out=None):
+        """Encodes radiance rgba (h, w, 4) float32 as 8-bit RGBA (h, w, 4) uint8; params = None (the defaults), a DisplayParams or a dict
+        of fields that replace the defaults; origin = (x, y) of pixel (0, 0) in the dither pattern. torch tensors on this handle's
+        device run through gpuart_display_run (torch's current stream is synchronised first, the handle before returning) and the
+        result is `out` or a new tensor; NumPy arrays run through gpuart_display_run_host and the result is `out` or a new array."""
+        p = display_params(params)
+        pp = C.byref(p) if p is not None else None
+        if type(rgba).__module__.startswith("torch"):
+            import torch
+            dev = torch.device("cuda", self.device)
+            if rgba.dtype != torch.float32 or rgba.dim() != 3 or rgba.shape[2] != 4 or not rgba.is_contiguous() or rgba.device != dev:
+                raise ValueError("rgba must be a contiguous (h, w, 4) float32 tensor on %s" % dev)
+            h, w = rgba.shape[0], rgba.shape[1]
+            res = out if out is not None else torch.empty((h, w, 4), dtype=torch.uint8, device=dev)
+            if res.dtype != torch.uint8 or tuple(res.shape) != (h, w, 4) or not res.is_contiguous() or res.device != dev:
+                raise ValueError("out must be a contiguous (h, w, 4) uint8 tensor on %s" % dev)
+            torch.cuda.current_stream(dev).synchronize()
+            self._chk(self._fn("run")(self.h, _dp(rgba), _dp(res), C.c_uint32(w), C.c_uint32(h), C.c_uint32(origin[0]), C.c_uint32(origin[1]), pp))
+            self.finish()
+            return res
+        rgba = np.ascontiguousarray(rgba, np.float32)
+        if rgba.ndim != 3 or rgba.shape[2] != 4:
+            raise ValueError("rgba must be (h, w, 4) float32")
+        h, w = rgba.shape[:2]
+        res = out if out is not None else np.empty((h, w, 4), np.uint8)
+        if res.dtype != np.uint8 or res.shape != (h, w, 4) or not res.flags.c_contiguous:
+            raise ValueError("out must be a contiguous (h, w, 4) uint8 array")
+        self._chk(self._fn("run_host")(self.h, _p(rgba), _p(res), C.c_uint32(w), C.c_uint32(h), C.c_uint32(origin[0]), C.c_uint32(origin[1]), pp))
+        return res
+
+    def state(self):
+        """gpuart_display_read_state as a dict: histogram (256 ints), counted, skipped, gain (float32), valid."""
+        s = DisplayState()
+        self._chk(self._fn("read_state")(self.h, C.byref(s)))
+        return s.as_dict()
+
+    @staticmethod
+    def srgb_table():
+        return srgb_table()
+
+
 class ConvergeError(RuntimeError):
     """A gpuart_converge_* call returned an error; `code` is the library's (GPUART_HIP_ERR_*)."""
     code = None

@@ -281,6 +281,9 @@ int gpuart_renderer_read_error_map(gpuart_renderer *r, float *e, float lumFloor)
 int gpuart_renderer_read_refined(gpuart_renderer *r, float *rgba, float lumFloor, const gpuart_refine_params *p) {
     return r->impl.ReadRefined(rgba, lumFloor, p) ? 1 : 0;
 }
+int gpuart_renderer_read_display(gpuart_renderer *r, uint8_t *rgba8, int source, const gpuart_display_params *dp, float lumFloor) {
+    return r->impl.ReadDisplay(rgba8, (gpuart_display_source)source, dp, lumFloor) ? 1 : 0;
+}
 int gpuart_renderer_set_history_variance(gpuart_renderer *r, int on, const gpuart_moments_params *p) {
     return r->impl.SetHistoryVariance(on != 0, p) ? 1 : 0;
 }

@@ -9,6 +9,7 @@
 #include "gpuart_adaptive.h"
 #include "gpuart_converge.h"
 #include "gpuart_denoise.h"
+#include "gpuart_display.h"
 #include "gpuart_hip.h"
 #include "gpuart_moments.h"
 #include "gpuart_refine.h"
@@ -102,6 +103,10 @@ int gpuart_renderer_read_error_map(gpuart_renderer *r, float *e, float lumFloor)
 /* Renderer::ReadRefined: the normalised accumulator filtered by the error map of the last batch (include/gpuart_refine.h); p = NULL:
  * the defaults. 1 on success, 0 before the second batch or on error. */
 int gpuart_renderer_read_refined(gpuart_renderer *r, float *rgba, float lumFloor, const gpuart_refine_params *p);
+/* Renderer::ReadDisplay: the frame `source` names (a gpuart_display_source) as 8-bit RGBA encoded on the device
+ * (include/gpuart_display.h), tile-sized, 4 bytes per pixel; dp = NULL: the defaults; lumFloor for the guided preview and the refined
+ * frame. 1 on success; 0 wherever the Read* of that source gives 0, for parameters out of range, or on error. */
+int gpuart_renderer_read_display(gpuart_renderer *r, uint8_t *rgba8, int source, const gpuart_display_params *dp, float lumFloor);
 /* Renderer::SetHistoryVariance: carry the luminance's moments through a second history (include/gpuart_moments.h); toggling drops the
  * temporal history. p = NULL: the defaults. 1 on success, 0 for parameters out of range. */
 int gpuart_renderer_set_history_variance(gpuart_renderer *r, int on, const gpuart_moments_params *p);

@@ -27,6 +27,8 @@ static void usage() {
                  "                  [--device D] [--gpus N] [--resume ck] [--checkpoint ck] [--pfm out.pfm] [--ppm out.ppm] [--nearest-first]\n"
                  "                  [--adaptive T [--adaptive-min N] [--until-batch N] [--until-floor F] [--samples-pfm out.pfm] [--refine]]\n"
                  "                  [--denoise] [--until T [--until-share S] [--until-floor F] [--until-batch N] [--error-pfm out.pfm] [--refine]]\n"
+                 "                  [--display out.ppm [--tonemap clamp|reinhard|aces] [--white W] [--exposure-ev E] [--auto-exposure] [--key K]\n"
+                 "                   [--srgb] [--dither]]\n"
                  "  --until T: render until the relative standard error of every pixel's luminance is at most T (Renderer::RenderUntil; path\n"
                  "             tracing on one GPU), --spp being the cap; --until-share S: the share of pixels that may stay above T (default 0);\n"
                  "             --until-floor F: luminance below which the error is taken relative to F (default 1/256, one step of the 8-bit\n"
@@ -39,6 +41,11 @@ static void usage() {
                  "             --samples-pfm: the paths per pixel (PFM, grey). Not together with --until, --denoise, --checkpoint or --gpus above 1\n"
                  "  --refine: with --until or --adaptive, write the frame filtered by its own error estimate (Renderer::ReadRefined, with --until-floor as its\n"
                  "             floor) instead of the raw one; not together with --denoise. A run that never reached two batches writes the raw frame\n"
+                 "  --display F: write the frame --pfm would hold (raw, --denoise or --refine) as an 8-bit PPM encoded on the device\n"
+                 "             (Renderer::ReadDisplay, include/gpuart_display.h), top-down as --ppm; without further options the bytes of --ppm.\n"
+                 "             --tonemap: the curve (default clamp); --white W: reinhard's white point (default 4); --exposure-ev E: gain 2^E;\n"
+                 "             --auto-exposure: adapt the gain to the frame's histogram, --key K: the luminance its log-average is brought to\n"
+                 "             (default 0.18); --srgb: the sRGB transfer function (default linear); --dither: 8x8 ordered dither. One GPU only\n"
                  "  --denoise: write the denoised preview of the frame (Renderer::ReadDenoised; path tracing on one GPU)\n"
                  "  --nearest-first: opt in to the nearer-child-first BVH walk (~10 % faster; soak-verified, not proven to be the reference's image)\n"
                  "  --gpus N: path tracing of ONE frame on devices D..D+N-1 (8-row bands dealt round-robin, gathered over RCCL)\n";
@@ -67,6 +74,10 @@ int main(int argc, char **argv) {
     float adaptive = -1;
     unsigned adaptiveMin = GPUART_ADAPTIVE_DEFAULT_MIN_PATHS;
     std::string samplesPfm;
+    std::string display, tonemap = "clamp";
+    bool displayOption = false;  // one of --display's own options was given
+    gpuart_display_params dp;
+    gpuart_display_defaults(&dp);
     float tile[4] = {0, 0, 0, 0}, campos[3] = {0.1f, -3.05f, 1.0f}, sun[3] = {0, 0, 0}, us[7] = {-0.4f, 0, 0.2f, 0, 0, 0, 0};
     int nTile = 0, nSun = 0, nUs = 0, n;
     for (int i = 1; i < argc; i++) {
@@ -104,6 +115,14 @@ int main(int argc, char **argv) {
         else if (a == "--adaptive") { adaptive = strtof(need("--adaptive"), nullptr); haveAdaptive = true; }
         else if (a == "--adaptive-min") adaptiveMin = (unsigned)atoi(need("--adaptive-min"));
         else if (a == "--samples-pfm") samplesPfm = need("--samples-pfm");
+        else if (a == "--display") display = need("--display");
+        else if (a == "--tonemap") { tonemap = need("--tonemap"); displayOption = true; }
+        else if (a == "--white") { dp.white = strtof(need("--white"), nullptr); displayOption = true; }
+        else if (a == "--exposure-ev") { dp.gain = std::exp2(strtof(need("--exposure-ev"), nullptr)); displayOption = true; }
+        else if (a == "--auto-exposure") { dp.auto_exposure = 1; displayOption = true; }
+        else if (a == "--key") { dp.key = strtof(need("--key"), nullptr); displayOption = true; }
+        else if (a == "--srgb") { dp.transfer = GPUART_DISPLAY_SRGB; displayOption = true; }
+        else if (a == "--dither") { dp.dither = 1; displayOption = true; }
         else { usage(); return 2; }
     }
     if (W == 0 || H == 0 || (mode != "direct" && mode != "pt")) { usage(); return 2; }
@@ -137,6 +156,18 @@ int main(int argc, char **argv) {
         return 2;
     }
     if ((haveUntil && mode != "pt") || (!haveUntil && !errorPfm.empty())) { usage(); return 2; }
+    if (displayOption && display.empty()) {
+        std::cerr << "gpuart_cli: --tonemap, --white, --exposure-ev, --auto-exposure, --key, --srgb and --dither shape --display's frame: give --display\n";
+        return 2;
+    }
+    if (!display.empty() && gpus > 1) {
+        std::cerr << "gpuart_cli: --display needs --gpus 1: the display stage is not in the frame gather\n";
+        return 2;
+    }
+    if (tonemap == "clamp") dp.curve = GPUART_DISPLAY_CLAMP;
+    else if (tonemap == "reinhard") dp.curve = GPUART_DISPLAY_REINHARD;
+    else if (tonemap == "aces") dp.curve = GPUART_DISPLAY_ACES;
+    else { usage(); return 2; }
     if ((haveAdaptive && mode != "pt") || (!haveAdaptive && !samplesPfm.empty())) { usage(); return 2; }
 
     // the reference's start-up camera (src/main.cpp:609-613), looking at (0,0,0.95)
@@ -291,9 +322,27 @@ int main(int argc, char **argv) {
                 }
         fclose(f);
     }
+    std::string displayKeys;
+    if (!display.empty()) {  // the same frame, encoded on the device; top-down like --ppm
+        const gpuart_display_source src = mode == "direct" ? GPUART_DISPLAY_DIRECT
+                                          : refine && untilBatches >= 2 ? GPUART_DISPLAY_REFINED
+                                          : denoise ? GPUART_DISPLAY_DENOISED : GPUART_DISPLAY_RADIANCE;
+        std::vector<uint8_t> img8((size_t)tw * th * 4);
+        if (!r.ReadDisplay(img8.data(), src, &dp, untilFloor)) return 1;
+        FILE *f = fopen(display.c_str(), "wb");
+        if (!f) return 1;
+        fprintf(f, "P6\n%u %u\n255\n", tw, th);
+        for (unsigned y = th; y-- > 0;)
+            for (unsigned x = 0; x < tw; x++) fwrite(&img8[4 * ((size_t)y * tw + x)], 1, 3, f);
+        fclose(f);
+        char buf[256];
+        snprintf(buf, sizeof buf, ", \"display\": {\"tonemap\": \"%s\", \"transfer\": \"%s\", \"gain\": %.9g, \"auto_exposure\": %s, \"dither\": %s}",
+                 tonemap.c_str(), dp.transfer ? "srgb" : "linear", dp.gain, dp.auto_exposure ? "true" : "false", dp.dither ? "true" : "false");
+        displayKeys = buf;
+    }
     printf("{\"scene\": \"%s\", \"mode\": \"%s\", \"frame\": [%u, %u], \"tile\": [%u, %u], \"gpus\": %u, \"paths_per_pixel\": %u, "
-           "\"passes\": %u, \"seconds\": %.6f, \"mpaths_per_s\": %.3f}\n",
+           "\"passes\": %u, \"seconds\": %.6f, \"mpaths_per_s\": %.3f%s}\n",
            scene.c_str(), mode.c_str(), W, H, tw, th, gpus, done, passes, secs,
-           mode == "pt" ? (double)tw * th * done / secs / 1e6 : (double)tw * th / secs / 1e6);
+           mode == "pt" ? (double)tw * th * done / secs / 1e6 : (double)tw * th / secs / 1e6, displayKeys.c_str());
     return 0;
 }

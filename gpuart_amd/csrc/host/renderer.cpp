@@ -76,6 +76,8 @@ Renderer::Renderer(unsigned viewportWidth, unsigned viewportHeight, const Camera
 }
 
 Renderer::~Renderer() {
+    if (Display) gpuart_display_destroy(Display);
+    DisplayMem.Release();
     if (Refine) gpuart_refine_destroy(Refine);
     RefineMem.Release();
     if (Adaptive) gpuart_adaptive_destroy(Adaptive);
@@ -393,7 +395,8 @@ bool Renderer::ReadRadiance(float *rgba, bool normalized) {
 
 namespace {
 const auto DN = gpuart_denoise_last_error, TP = gpuart_temporal_last_error, CV = gpuart_converge_last_error,
-           RF = gpuart_refine_last_error, AD = gpuart_adaptive_last_error, MO = gpuart_moments_last_error;  // for Check
+           RF = gpuart_refine_last_error, AD = gpuart_adaptive_last_error, MO = gpuart_moments_last_error,
+           DP = gpuart_display_last_error;  // for Check
 bool finite(float x) { return x - x == 0.0f; }
 bool checkHip(hipError_t e, const char *what) {
     if (e == hipSuccess) return true;
@@ -479,14 +482,21 @@ bool Renderer::ExportNormalized(float *device, bool normalized) {
 }
 
 bool Renderer::ReadDenoised(float *rgba, const gpuart_denoise_params *p) {
-    if (!IsOK || !rgba) return false;
+    const float *plane;
+    if (!rgba || !StageDenoised(p, plane)) return false;
+    return checkHip(hipMemcpy(rgba, plane, (size_t)Tile.w * Tile.h * 16, hipMemcpyDeviceToHost), "reading the denoised frame");
+}
+
+bool Renderer::StageDenoised(const gpuart_denoise_params *p, const float *&plane) {
+    if (!IsOK) return false;
     if (!Denoiser && !Check(gpuart_denoise_create(Device, &Denoiser), "creating the denoiser", DN)) return false;
     if (!StageView()) return false;
     const size_t n = (size_t)Tile.w * Tile.h;
     const ViewBuffers b(DenoiseMem.mem, n);
     if (!Check(gpuart_denoise_run(Denoiser, b.radiance, b.hits, b.prims, UserSphere.flags, Tile.w, Tile.h, p, b.filtered), "denoising", DN)) return false;
     if (!Check(gpuart_denoise_finish(Denoiser), "denoising", DN)) return false;
-    return checkHip(hipMemcpy(rgba, b.filtered, n * 16, hipMemcpyDeviceToHost), "reading the denoised frame");
+    plane = b.filtered;
+    return true;
 }
 
 // ---- temporal history (include/gpuart_temporal.h) ---------------------------------------------------------------------
@@ -584,7 +594,13 @@ bool Renderer::EnsureVarianceHandles() {
 }
 
 bool Renderer::ReadGuidedPreview(float *rgba, float lumFloor, const gpuart_refine_params *rf, const gpuart_temporal_params *tp) {
-    if (!IsOK || !rgba || !VarianceOn || !TemporalOn || PathTracing.numPathsRendered == 0) return false;
+    const float *plane;
+    if (!rgba || !StageGuidedPreview(lumFloor, rf, tp, plane)) return false;
+    return checkHip(hipMemcpy(rgba, plane, (size_t)Tile.w * Tile.h * 16, hipMemcpyDeviceToHost), "reading the guided preview");
+}
+
+bool Renderer::StageGuidedPreview(float lumFloor, const gpuart_refine_params *rf, const gpuart_temporal_params *tp, const float *&plane) {
+    if (!IsOK || !VarianceOn || !TemporalOn || PathTracing.numPathsRendered == 0) return false;
     if (!Refine && !Check(gpuart_refine_create(Device, &Refine), "creating the variance-guided filter", RF)) return false;
     gpuart_temporal_view v;
     if (!EnsureVarianceHandles() || !StageView() || !MakeTemporalView(v)) return false;
@@ -606,12 +622,19 @@ bool Renderer::ReadGuidedPreview(float *rgba, float lumFloor, const gpuart_refin
     // (the filter may run in place: include/gpuart_refine.h)
     if (!Check(gpuart_refine_run(Refine, b.filtered, b.hits, b.prims, UserSphere.flags, mb.e, lumFloor, Tile.w, Tile.h, rf, b.filtered), "filtering", RF) ||
         !Check(gpuart_refine_finish(Refine), "filtering", RF)) return false;
-    return checkHip(hipMemcpy(rgba, b.filtered, n * 16, hipMemcpyDeviceToHost), "reading the guided preview");
+    plane = b.filtered;
+    return true;
 }
 
 bool Renderer::ReadPreview(float *rgba, const gpuart_denoise_params *dn, const gpuart_temporal_params *tp) {
-    if (!TemporalOn || !HistoryCommitted || PathTracing.numPathsRendered == 0) return ReadDenoised(rgba, dn);
-    if (!IsOK || !rgba) return false;
+    const float *plane;
+    if (!rgba || !StagePreview(dn, tp, plane)) return false;
+    return checkHip(hipMemcpy(rgba, plane, (size_t)Tile.w * Tile.h * 16, hipMemcpyDeviceToHost), "reading the preview");
+}
+
+bool Renderer::StagePreview(const gpuart_denoise_params *dn, const gpuart_temporal_params *tp, const float *&plane) {
+    if (!TemporalOn || !HistoryCommitted || PathTracing.numPathsRendered == 0) return StageDenoised(dn, plane);
+    if (!IsOK) return false;
     if (!Denoiser && !Check(gpuart_denoise_create(Device, &Denoiser), "creating the denoiser", DN)) return false;
     gpuart_temporal_view v;
     if (!StageView() || !MakeTemporalView(v)) return false;
@@ -623,7 +646,8 @@ bool Renderer::ReadPreview(float *rgba, const gpuart_denoise_params *dn, const g
     // (the filter may run in place: include/gpuart_denoise.h)
     if (!Check(gpuart_denoise_run(Denoiser, b.filtered, b.hits, b.prims, UserSphere.flags, Tile.w, Tile.h, dn, b.filtered), "denoising", DN)) return false;
     if (!Check(gpuart_denoise_finish(Denoiser), "denoising", DN)) return false;
-    return checkHip(hipMemcpy(rgba, b.filtered, n * 16, hipMemcpyDeviceToHost), "reading the preview");
+    plane = b.filtered;
+    return true;
 }
 
 // ---- render until converged (include/gpuart_converge.h) -----------------------------------------------------------------
@@ -767,8 +791,14 @@ bool Renderer::ReadErrorMap(float *e, float lumFloor) {
 }
 
 bool Renderer::ReadRefined(float *rgba, float lumFloor, const gpuart_refine_params *p) {
+    const float *plane;
+    if (!rgba || !StageRefined(lumFloor, p, plane)) return false;
+    return checkHip(hipMemcpy(rgba, plane, (size_t)Tile.w * Tile.h * 16, hipMemcpyDeviceToHost), "reading the refined frame");
+}
+
+bool Renderer::StageRefined(float lumFloor, const gpuart_refine_params *p, const float *&plane) {
     const bool adaptive = Adaptive && AdaptiveIsLast && AdaptiveBatches >= 2;
-    if (!IsOK || !rgba || (!adaptive && (!Converge || ConvergeBatches < 2))) return false;
+    if (!IsOK || (!adaptive && (!Converge || ConvergeBatches < 2))) return false;
     if (!Refine && !Check(gpuart_refine_create(Device, &Refine), "creating the variance-guided filter", RF)) return false;
     if (!StageView()) return false;
     const size_t n = (size_t)Tile.w * Tile.h;
@@ -783,7 +813,47 @@ bool Renderer::ReadRefined(float *rgba, float lumFloor, const gpuart_refine_para
     if (!Check(gpuart_refine_run(Refine, b.radiance, b.hits, b.prims, UserSphere.flags, (const float *)RefineMem.mem, lumFloor, Tile.w, Tile.h, p,
                                  b.filtered), "filtering", RF)) return false;
     if (!Check(gpuart_refine_finish(Refine), "filtering", RF)) return false;
-    return checkHip(hipMemcpy(rgba, b.filtered, n * 16, hipMemcpyDeviceToHost), "reading the refined frame");
+    plane = b.filtered;
+    return true;
+}
+
+// ---- the display stage (include/gpuart_display.h) ---------------------------------------------------------------------------
+bool Renderer::ReadDisplay(uint8_t *rgba8, gpuart_display_source source, const gpuart_display_params *dp, float lumFloor) {
+    if (!IsOK || !rgba8) return false;
+    if (!checkHip(hipSetDevice(Device), "hipSetDevice")) return false;
+    if (!Display && !Check(gpuart_display_create(Device, &Display), "creating the display stage", DP)) return false;
+    const size_t n = (size_t)Tile.w * Tile.h;
+    if (!DisplayMem.Fit(n, 16 + 4, "allocating the display stage's buffers")) return false;
+    float *own = (float *)DisplayMem.mem;
+    uint8_t *words = (uint8_t *)DisplayMem.mem + n * 16;
+    const float *plane = own;
+    switch (source) {
+    case GPUART_DISPLAY_RADIANCE:
+        if (!ExportNormalized(own)) return false;
+        break;
+    case GPUART_DISPLAY_DIRECT:
+        if (!Check(gpuart_hip_export(Backend, 0, own, 1.0f), "exporting the frame") || !Check(gpuart_hip_finish(Backend), "waiting for the device"))
+            return false;
+        break;
+    case GPUART_DISPLAY_DENOISED:
+        if (!StageDenoised(nullptr, plane)) return false;
+        break;
+    case GPUART_DISPLAY_PREVIEW:
+        if (!StagePreview(nullptr, nullptr, plane)) return false;
+        break;
+    case GPUART_DISPLAY_GUIDED_PREVIEW:
+        if (!StageGuidedPreview(lumFloor, nullptr, nullptr, plane)) return false;
+        break;
+    case GPUART_DISPLAY_REFINED:
+        if (!StageRefined(lumFloor, nullptr, plane)) return false;
+        break;
+    default:
+        std::cerr << "Renderer: ReadDisplay: no such source " << (int)source << std::endl;
+        return false;
+    }
+    if (!Check(gpuart_display_run(Display, plane, words, Tile.w, Tile.h, Tile.x, Tile.y, dp), "encoding the frame", DP) ||
+        !Check(gpuart_display_finish(Display), "encoding the frame", DP)) return false;
+    return checkHip(hipMemcpy(rgba8, words, n * 4, hipMemcpyDeviceToHost), "reading the 8-bit frame");
 }
 
 // ---- checkpoint / resume ---------------------------------------------------------------------------------------------

@@ -8,7 +8,7 @@
 // MAX_PATH_SEGMENTS / the RNG seed / the viewport fixed at compile time):
 //   ReadDirectLighting, ReadRadiance, Finish, SetMaxPathSegments, SetMinWeight, SetSeed,
 //   SetTile, GetBackend, ComputeScreenBasis, GetNumPathsRendered, ReadDenoised, SetTemporalHistory, ReadPreview, RenderUntil,
-//   ReadErrorMap, ReadRefined, SetHistoryVariance, ReadGuidedPreview.
+//   ReadErrorMap, ReadRefined, SetHistoryVariance, ReadGuidedPreview, ReadDisplay.
 #ifndef GPUART_RENDERER_H
 #define GPUART_RENDERER_H
 
@@ -21,11 +21,16 @@
 #include "gpuart_adaptive.h"
 #include "gpuart_converge.h"
 #include "gpuart_denoise.h"
+#include "gpuart_display.h"
 #include "gpuart_hip.h"
 #include "gpuart_moments.h"
 #include "gpuart_refine.h"
 #include "gpuart_temporal.h"
 #include "math_types.h"
+
+/// The luminance floor of the error estimates where none is given: one step of an 8-bit output (gpuart_cli --until-floor,
+/// binding.CONVERGE_DEFAULT_FLOOR).
+constexpr float GPUART_CONVERGE_DEFAULT_FLOOR = 1.0f / 256;
 
 namespace gpuart {
 
@@ -145,6 +150,18 @@ public:
     /// passes that follow, the counters, the estimate and RenderUntil's later summaries, the temporal history and the cached G-buffer
     /// are not touched. Synchronises.
     bool ReadRefined(float *rgba, float lumFloor, const gpuart_refine_params *p = nullptr);
+    /// One of the frames above as 8-bit RGBA, encoded on the device (include/gpuart_display.h): Tile.w*Tile.h*4 bytes, row 0 = bottom row,
+    /// alpha 255. It runs exactly the device sequence of the Read* that `source` names — ReadRadiance(normalized), ReadDirectLighting,
+    /// ReadDenoised, ReadPreview, ReadGuidedPreview or ReadRefined, the filters with their default parameters, lumFloor for the last
+    /// two — then gpuart_display_run on that sequence's plane in device memory (dp = nullptr: the defaults, which are the bytes
+    /// gpuart_cli --ppm makes of the float frame), and copies 4 bytes per pixel back instead of 16. False wherever that Read* is false,
+    /// and for parameters out of range. The dither pattern's origin is the tile's (x0, y0); on an interleaved share it follows the
+    /// share's local rows, not the frame's. With auto_exposure the adapted gain lives in the Renderer's display handle: SetCamera and
+    /// the user-sphere moves keep it (adapting across views is what `adapt` is for), everything that drops the temporal history —
+    /// see SetTemporalHistory — forgets it. The accumulator, the passes that follow, the counters, the estimates, the temporal
+    /// histories and the cached G-buffer are what they are without the call. Synchronises.
+    bool ReadDisplay(uint8_t *rgba8, gpuart_display_source source, const gpuart_display_params *dp = nullptr,
+                     float lumFloor = GPUART_CONVERGE_DEFAULT_FLOOR);
     /// Adaptive sampling (include/gpuart_adaptive.h, gpuart_hip_set_active_blocks): RenderUntil's loop with the estimate kept per 8x8
     /// block of the tile. It continues the current accumulation in batches of at least batchPaths paths per pixel towards the cap of
     /// RestartPathTracing / ExtendPathTracing; after every batch the raw accumulator and the blocks' path counts go to the estimator,
@@ -251,6 +268,8 @@ private:
     unsigned CountBase = 0;               ///< paths per pixel a loaded checkpoint brought: the back end's block counts begin above them
     gpuart_refine *Refine = nullptr;      ///< made by the first ReadRefined
     PixelBuffer RefineMem;                ///< ReadRefined's error map, 4 B per tile pixel
+    gpuart_display *Display = nullptr;    ///< made by the first ReadDisplay
+    PixelBuffer DisplayMem;               ///< ReadDisplay's: the plane of RADIANCE and DIRECT (16 B) and the 8-bit frame (4 B) per tile pixel
     ScreenBasis CurrentBasis;             ///< what SetCamera gave the back end
     double LastSetPrimitivesMs[4] = {0, 0, 0, 0};
     gpuart_hip_ctx *Backend = nullptr;
@@ -273,7 +292,13 @@ private:
     void CommitTemporalView();
     /// Temporal, TemporalMoments, Moments and MomentsMem for the tile, made where missing.
     bool EnsureVarianceHandles();
-    void DropTemporalHistory() { if (HistoryCommitted) DropTemporalHistoryNow(); }
+    /// The device halves of the Read* of the same names: each leaves its frame in device memory, complete, and says where.
+    bool StageDenoised(const gpuart_denoise_params *p, const float *&plane);
+    bool StagePreview(const gpuart_denoise_params *dn, const gpuart_temporal_params *tp, const float *&plane);
+    bool StageGuidedPreview(float lumFloor, const gpuart_refine_params *rf, const gpuart_temporal_params *tp, const float *&plane);
+    bool StageRefined(float lumFloor, const gpuart_refine_params *p, const float *&plane);
+    /// Every call that drops the history also forgets the display stage's adapted exposure.
+    void DropTemporalHistory() { if (Display) gpuart_display_reset(Display); if (HistoryCommitted) DropTemporalHistoryNow(); }
     void DropTemporalHistoryNow();
     void ResetConvergeNow();
     void ResetAdaptiveNow();
