@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../image/image_lib.h"
+#include "../image/estimate.h"
 #include "gpuart_adaptive.h"
 
 namespace {
@@ -30,14 +31,7 @@ __global__ void __launch_bounds__(ROW_X * ROW_Y) k_ad_update(const float4 *accum
     const float b = (float)(p - seen), Wn = (float)p;
     const float r = b / Wn;
     const size_t i = (size_t)y * w + x;
-    const float4 a = accum[i];
-    const float4 s = state[i];
-    const float Lk = lum(a.x, a.y, a.z);
-    const float yk = (Lk - s.z) / b;
-    const float d = yk - s.x;
-    const float mean = s.x + r * d;
-    const float m2 = s.y + (b * d) * (yk - mean);
-    state[i] = make_float4(mean, m2, Lk, 0.0f);
+    state[i] = estimate_step(accum[i], state[i], b, r);
 }
 
 /// Behind k_ad_update on the same stream: no pixel reads a block word while it changes.
@@ -56,9 +50,7 @@ __global__ void __launch_bounds__(256) k_ad_blocks(const uint32_t *paths, uint4 
 /// e of one pixel from its state and its block's words; +inf without an estimate (fewer than two batches).
 __device__ __forceinline__ float error_of(const float4 s, const uint4 b, float lum_floor) {
     if (b.y < 2) return INFINITY;
-    const float v = (s.y < 0.0f ? 0.0f : s.y) / (float)(b.y - 1);  // (a NaN m2 stays NaN)
-    const float se = sqrtf(v / (float)b.x);
-    return se / (s.x > lum_floor ? s.x : lum_floor);
+    return estimate_error(s, (float)(b.y - 1), (float)b.x, lum_floor);
 }
 
 /// One wave per 8x8 block, a lane per pixel: a row of the block is one 128-byte line of the state. Ballot + popcount for the two counts,

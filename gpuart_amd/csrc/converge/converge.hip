@@ -5,6 +5,7 @@
 #include <cmath>
 
 #include "../image/image_lib.h"
+#include "../image/estimate.h"
 #include "gpuart_converge.h"
 
 namespace {
@@ -21,14 +22,7 @@ __global__ void __launch_bounds__(ROW_X * ROW_Y) k_cv_update(const float4 *accum
     const int x = blockIdx.x * ROW_X + threadIdx.x, y = blockIdx.y * ROW_Y + threadIdx.y;
     if (x >= w || y >= h) return;
     const size_t i = (size_t)y * w + x;
-    const float4 a = accum[i];
-    const float4 s = state[i];
-    const float Lk = lum(a.x, a.y, a.z);
-    const float yk = (Lk - s.z) / b;
-    const float d = yk - s.x;
-    const float mean = s.x + r * d;
-    const float m2 = s.y + (b * d) * (yk - mean);
-    state[i] = make_float4(mean, m2, Lk, 0.0f);
+    state[i] = estimate_step(accum[i], state[i], b, r);
 }
 
 /// What the frame's reduction ends in; zeroed on the stream before every k_cv_measure.
@@ -49,10 +43,7 @@ __global__ void __launch_bounds__(ROW_X * ROW_Y) k_cv_measure(const float4 *stat
         bool ab = false, nf = false;
         if (x < w) {
             const size_t i = (size_t)y * w + x;
-            const float4 s = state[i];
-            const float v = (s.y < 0.0f ? 0.0f : s.y) / nb1;  // (a NaN m2 stays NaN: such a pixel has not converged)
-            const float se = sqrtf(v / total);
-            const float e = se / (s.x > lum_floor ? s.x : lum_floor);
+            const float e = estimate_error(state[i], nb1, total, lum_floor);
             if (MAP) map[i] = e;
             ab = !(e <= threshold);
             nf = !(fabsf(e) < INFINITY);  // NaN or +-inf

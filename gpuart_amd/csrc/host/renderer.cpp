@@ -79,12 +79,11 @@ Renderer::~Renderer() {
     if (Display) gpuart_display_destroy(Display);
     DisplayMem.Release();
     if (Refine) gpuart_refine_destroy(Refine);
-    RefineMem.Release();
+    ErrorMem.Release();
     if (Adaptive) gpuart_adaptive_destroy(Adaptive);
-    AdaptiveMem.Release();
-    if (BlockPathsMem) (void)hipFree(BlockPathsMem);
+    BlockPathsMem.Release();
     if (Converge) gpuart_converge_destroy(Converge);
-    ConvergeMem.Release();
+    AccumMem.Release();
     if (Moments) gpuart_moments_destroy(Moments);
     if (TemporalMoments) gpuart_temporal_destroy(TemporalMoments);
     MomentsMem.Release();
@@ -176,7 +175,7 @@ bool Renderer::GatherRadiance(Renderer *const *ranks, int n, int root, bool norm
             return false;
         }
     Renderer &r0 = *ranks[root];
-    const float div = normalized && r0.PathTracing.numPathsRendered ? (float)r0.PathTracing.numPathsRendered : 1.0f;
+    const float div = r0.Divisor(normalized);
     // One communicator per set of renderers, kept by the contexts themselves. Whether these contexts are (still) the ranks
     // 0..n-1 of one is the library's to say: it answers GPUART_HIP_ERR_NO_COMM before anything is transferred, then one is made.
     // Every step that waits for RCCL or for the other GPUs is a named phase (a line on stderr before and after, and the
@@ -383,20 +382,29 @@ bool Renderer::ReadDirectLighting(float *rgba) {
 }
 
 bool Renderer::ReadRadiance(float *rgba, bool normalized) {
-    if (IsOK && normalized && NonUniform) {  // every block by its own count, through a device buffer
-        const size_t n = (size_t)Tile.w * Tile.h;
-        if (!rgba || !AdaptiveMem.Fit(n, 16, "allocating the normalised frame") || !ExportNormalized((float *)AdaptiveMem.mem)) return false;
-        return hipMemcpy(rgba, AdaptiveMem.mem, n * 16, hipMemcpyDeviceToHost) == hipSuccess;
-    }
-    // the division is the reference's ptracingNormalize program (shaders/pt_normalize.glsl:44-47)
-    const float div = normalized && PathTracing.numPathsRendered ? (float)PathTracing.numPathsRendered : 1.0f;
-    return IsOK && Check(gpuart_hip_read(Backend, 1, rgba, div), "reading the radiance accumulator");
+    if (IsOK && normalized && NonUniform)  // every block by its own count, through a device buffer
+        return rgba && AccumMem.Fit((size_t)Tile.w * Tile.h, 16, "allocating the normalised frame") && ExportNormalized((float *)AccumMem.mem) &&
+               ReadPlane(rgba, AccumMem.mem, 16, "reading the normalised frame");
+    return IsOK && Check(gpuart_hip_read(Backend, 1, rgba, Divisor(normalized)), "reading the radiance accumulator");
 }
 
 namespace {
-const auto DN = gpuart_denoise_last_error, TP = gpuart_temporal_last_error, CV = gpuart_converge_last_error,
-           RF = gpuart_refine_last_error, AD = gpuart_adaptive_last_error, MO = gpuart_moments_last_error,
-           DP = gpuart_display_last_error;  // for Check
+/// What the Renderer needs of an image library to make a handle, wait for it and report its failures.
+template <class H>
+struct Lib {
+    int (*create)(int, H **);
+    int (*finish)(H *);
+    const char *(*lastError)(void);
+    const char *creating;
+};
+const Lib<gpuart_denoise> DN{gpuart_denoise_create, gpuart_denoise_finish, gpuart_denoise_last_error, "creating the denoiser"};
+const Lib<gpuart_temporal> TP{gpuart_temporal_create, gpuart_temporal_finish, gpuart_temporal_last_error, "creating the temporal accumulator"};
+const Lib<gpuart_temporal> TPM{gpuart_temporal_create, gpuart_temporal_finish, gpuart_temporal_last_error, "creating the moments' temporal accumulator"};
+const Lib<gpuart_moments> MO{gpuart_moments_create, gpuart_moments_finish, gpuart_moments_last_error, "creating the moments library's handle"};
+const Lib<gpuart_converge> CV{gpuart_converge_create, gpuart_converge_finish, gpuart_converge_last_error, "creating the convergence estimator"};
+const Lib<gpuart_adaptive> AD{gpuart_adaptive_create, gpuart_adaptive_finish, gpuart_adaptive_last_error, "creating the adaptive estimator"};
+const Lib<gpuart_refine> RF{gpuart_refine_create, gpuart_refine_finish, gpuart_refine_last_error, "creating the variance-guided filter"};
+const Lib<gpuart_display> DP{gpuart_display_create, gpuart_display_finish, gpuart_display_last_error, "creating the display stage"};
 bool finite(float x) { return x - x == 0.0f; }
 bool checkHip(hipError_t e, const char *what) {
     if (e == hipSuccess) return true;
@@ -421,24 +429,38 @@ struct MomentBuffers {
 };
 }  // namespace
 
+template <class H, class L>
+bool Renderer::Ensure(H *&h, const L &lib) {
+    return h || Check(lib.create(Device, &h), lib.creating, lib.lastError);
+}
+
+template <class H, class L>
+bool Renderer::Run(int status, H *h, const L &lib, const char *what) {
+    return Check(status, what, lib.lastError) && Check(lib.finish(h), what, lib.lastError);
+}
+
 void Renderer::PixelBuffer::Release() {
     if (mem) (void)hipFree(mem);
     mem = nullptr;
-    pixels = 0;
+    count = 0;
 }
 
-bool Renderer::PixelBuffer::Fit(size_t n, size_t bytesPerPixel, const char *what) {
-    if (n == pixels) return true;
+bool Renderer::PixelBuffer::Fit(size_t n, size_t bytesPerElement, const char *what) {
+    if (n == count) return true;
     Release();
-    if (!checkHip(hipMalloc(&mem, n * bytesPerPixel), what)) return false;
-    pixels = n;
+    if (!checkHip(hipMalloc(&mem, n * bytesPerElement), what)) return false;
+    count = n;
     return true;
+}
+
+bool Renderer::ReadPlane(void *host, const void *plane, size_t bytesPerPixel, const char *what) {
+    return checkHip(hipMemcpy(host, plane, (size_t)Tile.w * Tile.h * bytesPerPixel, hipMemcpyDeviceToHost), what);
 }
 
 bool Renderer::StageView() {
     if (!checkHip(hipSetDevice(Device), "hipSetDevice")) return false;
     const size_t n = (size_t)Tile.w * Tile.h;
-    if (n != DenoiseMem.pixels) GBufferValid = false;
+    if (n != DenoiseMem.count) GBufferValid = false;
     if (!DenoiseMem.Fit(n, 16 + 32 + 16 + 4, "allocating the denoiser's buffers")) return false;
     const ViewBuffers b(DenoiseMem.mem, n);
     const float us[4] = {UserSphere.pos.x, UserSphere.pos.y, UserSphere.pos.z, UserSphere.radius};
@@ -453,50 +475,69 @@ bool Renderer::StageView() {
 
 bool Renderer::StageBlockPaths() {
     const size_t nb = TileBlocks();
-    if (nb != BlockPathsWords) {
-        if (BlockPathsMem) (void)hipFree(BlockPathsMem);
-        BlockPathsMem = nullptr;
-        BlockPathsWords = 0;
-        if (!checkHip(hipMalloc((void **)&BlockPathsMem, nb * sizeof(uint32_t)), "allocating the block counts")) return false;
-        BlockPathsWords = nb;
-    }
-    if (!CountBase) return Check(gpuart_hip_export_block_paths(Backend, BlockPathsMem), "exporting the block counts");
+    if (!BlockPathsMem.Fit(nb, sizeof(uint32_t), "allocating the block counts")) return false;
+    if (!CountBase) return Check(gpuart_hip_export_block_paths(Backend, (uint32_t *)BlockPathsMem.mem), "exporting the block counts");
     // a loaded checkpoint's paths are in the accumulator but not in the back end's counts: added on the way
     std::vector<uint32_t> counts(nb);
     if (!Check(gpuart_hip_read_block_paths(Backend, counts.data()), "reading the block counts")) return false;
     for (uint32_t &c : counts) c += CountBase;
-    return checkHip(hipMemcpy(BlockPathsMem, counts.data(), nb * sizeof(uint32_t), hipMemcpyHostToDevice), "staging the block counts");
+    return checkHip(hipMemcpy(BlockPathsMem.mem, counts.data(), nb * sizeof(uint32_t), hipMemcpyHostToDevice), "staging the block counts");
 }
 
-bool Renderer::ExportNormalized(float *device, bool normalized) {
-    if (!normalized || !NonUniform) {
-        // the division is the reference's ptracingNormalize program (shaders/pt_normalize.glsl:44-47), as in ReadRadiance
-        const float div = normalized && PathTracing.numPathsRendered ? (float)PathTracing.numPathsRendered : 1.0f;
-        if (!Check(gpuart_hip_export(Backend, 1, device, div), "exporting the radiance")) return false;
-        return Check(gpuart_hip_finish(Backend), "waiting for the device");
+bool Renderer::Export(int which, float *device, float div, bool withBlockPaths) {
+    if (!Check(gpuart_hip_export(Backend, which, device, div), "exporting the frame") || (withBlockPaths && !StageBlockPaths())) return false;
+    return Check(gpuart_hip_finish(Backend), "waiting for the device");
+}
+
+bool Renderer::ExportNormalized(float *device) {
+    if (!NonUniform) return Export(1, device, Divisor(true));
+    return Export(1, device, 1.0f, true) &&
+           Run(gpuart_adaptive_normalize(Adaptive, device, (const uint32_t *)BlockPathsMem.mem, device, Tile.w, Tile.h), Adaptive, AD, "normalising by the blocks' counts");
+}
+
+// ---- the frames a read can ask for ------------------------------------------------------------------------------------
+bool Renderer::StageSource(gpuart_display_source source, float lumFloor, const gpuart_denoise_params *dn, const gpuart_refine_params *rf,
+                           const gpuart_temporal_params *tp, float *own, const float *&plane) {
+    switch (source) {
+    case GPUART_DISPLAY_RADIANCE: plane = own; return own && ExportNormalized(own);
+    case GPUART_DISPLAY_DIRECT: plane = own; return own && Export(0, own, 1.0f);
+    case GPUART_DISPLAY_DENOISED: return StageDenoised(dn, plane);
+    case GPUART_DISPLAY_PREVIEW: return StagePreview(dn, tp, plane);
+    case GPUART_DISPLAY_GUIDED_PREVIEW: return StageGuidedPreview(lumFloor, rf, tp, plane);
+    case GPUART_DISPLAY_REFINED: return StageRefined(lumFloor, rf, plane);
+    default:
+        std::cerr << "Renderer: ReadDisplay: no such source " << (int)source << std::endl;
+        return false;
     }
-    if (!Check(gpuart_hip_export(Backend, 1, device, 1.0f), "exporting the radiance") || !StageBlockPaths()) return false;
-    if (!Check(gpuart_hip_finish(Backend), "waiting for the device")) return false;
-    return Check(gpuart_adaptive_normalize(Adaptive, device, BlockPathsMem, device, Tile.w, Tile.h), "normalising by the blocks' counts", AD) &&
-           Check(gpuart_adaptive_finish(Adaptive), "normalising by the blocks' counts", AD);
+}
+
+bool Renderer::ReadStaged(float *rgba, const char *what, gpuart_display_source source, float lumFloor, const gpuart_denoise_params *dn,
+                          const gpuart_refine_params *rf, const gpuart_temporal_params *tp) {
+    const float *plane;
+    return rgba && StageSource(source, lumFloor, dn, rf, tp, nullptr, plane) && ReadPlane(rgba, plane, 16, what);
 }
 
 bool Renderer::ReadDenoised(float *rgba, const gpuart_denoise_params *p) {
-    const float *plane;
-    if (!rgba || !StageDenoised(p, plane)) return false;
-    return checkHip(hipMemcpy(rgba, plane, (size_t)Tile.w * Tile.h * 16, hipMemcpyDeviceToHost), "reading the denoised frame");
+    return ReadStaged(rgba, "reading the denoised frame", GPUART_DISPLAY_DENOISED, 0, p, nullptr, nullptr);
+}
+
+bool Renderer::ReadPreview(float *rgba, const gpuart_denoise_params *dn, const gpuart_temporal_params *tp) {
+    return ReadStaged(rgba, "reading the preview", GPUART_DISPLAY_PREVIEW, 0, dn, nullptr, tp);
+}
+
+bool Renderer::ReadGuidedPreview(float *rgba, float lumFloor, const gpuart_refine_params *rf, const gpuart_temporal_params *tp) {
+    return ReadStaged(rgba, "reading the guided preview", GPUART_DISPLAY_GUIDED_PREVIEW, lumFloor, nullptr, rf, tp);
+}
+
+bool Renderer::ReadRefined(float *rgba, float lumFloor, const gpuart_refine_params *p) {
+    return ReadStaged(rgba, "reading the refined frame", GPUART_DISPLAY_REFINED, lumFloor, nullptr, p, nullptr);
 }
 
 bool Renderer::StageDenoised(const gpuart_denoise_params *p, const float *&plane) {
-    if (!IsOK) return false;
-    if (!Denoiser && !Check(gpuart_denoise_create(Device, &Denoiser), "creating the denoiser", DN)) return false;
-    if (!StageView()) return false;
-    const size_t n = (size_t)Tile.w * Tile.h;
-    const ViewBuffers b(DenoiseMem.mem, n);
-    if (!Check(gpuart_denoise_run(Denoiser, b.radiance, b.hits, b.prims, UserSphere.flags, Tile.w, Tile.h, p, b.filtered), "denoising", DN)) return false;
-    if (!Check(gpuart_denoise_finish(Denoiser), "denoising", DN)) return false;
+    if (!IsOK || !Ensure(Denoiser, DN) || !StageView()) return false;
+    const ViewBuffers b(DenoiseMem.mem, (size_t)Tile.w * Tile.h);
     plane = b.filtered;
-    return true;
+    return Run(gpuart_denoise_run(Denoiser, b.radiance, b.hits, b.prims, UserSphere.flags, Tile.w, Tile.h, p, b.filtered), Denoiser, DN, "denoising");
 }
 
 // ---- temporal history (include/gpuart_temporal.h) ---------------------------------------------------------------------
@@ -537,35 +578,30 @@ bool Renderer::MakeTemporalView(gpuart_temporal_view &v) const {
     return true;
 }
 
+bool Renderer::BlendHistory(const gpuart_temporal_view &v, const gpuart_temporal_params *tp, bool commit, float *len) {
+    const ViewBuffers b(DenoiseMem.mem, (size_t)Tile.w * Tile.h);
+    return Run(gpuart_temporal_accumulate(Temporal, b.radiance, PathTracing.numPathsRendered, b.hits, b.prims, Tile.w, Tile.h, &v,
+                                          tp ? tp : &TemporalParams, commit, b.filtered, len),
+               Temporal, TP, commit ? "committing the view to the history" : "blending the history");
+}
+
+bool Renderer::BlendMoments(const gpuart_temporal_view &v, const gpuart_temporal_params *tp, bool commit) {
+    const size_t n = (size_t)Tile.w * Tile.h;
+    const ViewBuffers b(DenoiseMem.mem, n);
+    const MomentBuffers mb(MomentsMem.mem, n);
+    return Run(gpuart_moments_pack(Moments, b.radiance, PathTracing.numPathsRendered, Tile.w, Tile.h, mb.packed), Moments, MO, "packing the moments") &&
+           Run(gpuart_temporal_accumulate(TemporalMoments, mb.packed, PathTracing.numPathsRendered, b.hits, b.prims, Tile.w, Tile.h, &v,
+                                          tp ? tp : &TemporalParams, commit, mb.blend, nullptr),
+               TemporalMoments, TPM, commit ? "committing the moments to their history" : "blending the moments' history");
+}
+
 void Renderer::CommitTemporalView() {
     if (!TemporalOn || !IsOK || PathTracing.numPathsRendered == 0) return;
-    // A commit that fails leaves no history rather than a stale one.
-    bool ok = Temporal || Check(gpuart_temporal_create(Device, &Temporal), "creating the temporal accumulator", TP);
     gpuart_temporal_view v;
-    ok = ok && StageView() && MakeTemporalView(v);
-    if (ok) {
-        const ViewBuffers b(DenoiseMem.mem, (size_t)Tile.w * Tile.h);
-        ok = Check(gpuart_temporal_accumulate(Temporal, b.radiance, PathTracing.numPathsRendered, b.hits, b.prims, Tile.w, Tile.h, &v,
-                                              &TemporalParams, 1, b.filtered, nullptr), "committing the view to the history", TP) &&
-             Check(gpuart_temporal_finish(Temporal), "committing the view to the history", TP);
-        if (ok && VarianceOn) {  // the same commit for the moments: the two histories have seen the same views or none
-            const size_t n = (size_t)Tile.w * Tile.h;
-            ok = EnsureVarianceHandles();
-            if (ok) {
-                const MomentBuffers mb(MomentsMem.mem, n);
-                ok = Check(gpuart_moments_pack(Moments, b.radiance, PathTracing.numPathsRendered, Tile.w, Tile.h, mb.packed), "packing the moments", MO) &&
-                     Check(gpuart_moments_finish(Moments), "packing the moments", MO) &&
-                     Check(gpuart_temporal_accumulate(TemporalMoments, mb.packed, PathTracing.numPathsRendered, b.hits, b.prims, Tile.w, Tile.h, &v,
-                                                      &TemporalParams, 1, mb.blend, nullptr), "committing the moments to their history", TP) &&
-                     Check(gpuart_temporal_finish(TemporalMoments), "committing the moments to their history", TP);
-            }
-        }
-    }
-    HistoryCommitted = ok;
-    if (!ok) {
-        if (Temporal) gpuart_temporal_reset(Temporal);
-        if (TemporalMoments) gpuart_temporal_reset(TemporalMoments);
-    }
+    // the same commit for the moments: the two histories have seen the same views or none
+    HistoryCommitted = Ensure(Temporal, TP) && StageView() && MakeTemporalView(v) && BlendHistory(v, nullptr, true, nullptr) &&
+                       (!VarianceOn || (EnsureVarianceHandles() && BlendMoments(v, nullptr, true)));
+    if (!HistoryCommitted) DropTemporalHistoryNow();  // A commit that fails leaves no history rather than a stale one.
 }
 
 // ---- the history's measured variance (include/gpuart_moments.h) -----------------------------------------------------------
@@ -587,67 +623,57 @@ bool Renderer::SetHistoryVariance(bool on, const gpuart_moments_params *p) {
 
 bool Renderer::EnsureVarianceHandles() {
     if (!checkHip(hipSetDevice(Device), "hipSetDevice")) return false;
-    if (!Temporal && !Check(gpuart_temporal_create(Device, &Temporal), "creating the temporal accumulator", TP)) return false;
-    if (!TemporalMoments && !Check(gpuart_temporal_create(Device, &TemporalMoments), "creating the moments' temporal accumulator", TP)) return false;
-    if (!Moments && !Check(gpuart_moments_create(Device, &Moments), "creating the moments library's handle", MO)) return false;
+    if (!Ensure(Temporal, TP) || !Ensure(TemporalMoments, TPM) || !Ensure(Moments, MO)) return false;
     return MomentsMem.Fit((size_t)Tile.w * Tile.h, 16 + 16 + 4 + 4, "allocating the moments' buffers");
-}
-
-bool Renderer::ReadGuidedPreview(float *rgba, float lumFloor, const gpuart_refine_params *rf, const gpuart_temporal_params *tp) {
-    const float *plane;
-    if (!rgba || !StageGuidedPreview(lumFloor, rf, tp, plane)) return false;
-    return checkHip(hipMemcpy(rgba, plane, (size_t)Tile.w * Tile.h * 16, hipMemcpyDeviceToHost), "reading the guided preview");
 }
 
 bool Renderer::StageGuidedPreview(float lumFloor, const gpuart_refine_params *rf, const gpuart_temporal_params *tp, const float *&plane) {
     if (!IsOK || !VarianceOn || !TemporalOn || PathTracing.numPathsRendered == 0) return false;
-    if (!Refine && !Check(gpuart_refine_create(Device, &Refine), "creating the variance-guided filter", RF)) return false;
     gpuart_temporal_view v;
-    if (!EnsureVarianceHandles() || !StageView() || !MakeTemporalView(v)) return false;
+    if (!Ensure(Refine, RF) || !EnsureVarianceHandles() || !StageView() || !MakeTemporalView(v)) return false;
     const size_t n = (size_t)Tile.w * Tile.h;
-    const unsigned spp = PathTracing.numPathsRendered;
     const ViewBuffers b(DenoiseMem.mem, n);
     const MomentBuffers mb(MomentsMem.mem, n);
-    if (!tp) tp = &TemporalParams;
     // (without a commit both handles have no history: every blend is its input and len = s)
-    if (!Check(gpuart_temporal_accumulate(Temporal, b.radiance, spp, b.hits, b.prims, Tile.w, Tile.h, &v, tp, 0, b.filtered, mb.len),
-               "blending the history", TP) || !Check(gpuart_temporal_finish(Temporal), "blending the history", TP)) return false;
-    if (!Check(gpuart_moments_pack(Moments, b.radiance, spp, Tile.w, Tile.h, mb.packed), "packing the moments", MO) ||
-        !Check(gpuart_moments_finish(Moments), "packing the moments", MO)) return false;
-    if (!Check(gpuart_temporal_accumulate(TemporalMoments, mb.packed, spp, b.hits, b.prims, Tile.w, Tile.h, &v, tp, 0, mb.blend, nullptr),
-               "blending the moments' history", TP) || !Check(gpuart_temporal_finish(TemporalMoments), "blending the moments' history", TP)) return false;
-    if (!Check(gpuart_moments_error(Moments, b.filtered, mb.len, mb.blend, b.hits, b.prims, UserSphere.flags, lumFloor, Tile.w, Tile.h, &MomentsParams,
-                                    mb.e), "measuring the history's variance", MO) ||
-        !Check(gpuart_moments_finish(Moments), "measuring the history's variance", MO)) return false;
-    // (the filter may run in place: include/gpuart_refine.h)
-    if (!Check(gpuart_refine_run(Refine, b.filtered, b.hits, b.prims, UserSphere.flags, mb.e, lumFloor, Tile.w, Tile.h, rf, b.filtered), "filtering", RF) ||
-        !Check(gpuart_refine_finish(Refine), "filtering", RF)) return false;
-    plane = b.filtered;
-    return true;
-}
-
-bool Renderer::ReadPreview(float *rgba, const gpuart_denoise_params *dn, const gpuart_temporal_params *tp) {
-    const float *plane;
-    if (!rgba || !StagePreview(dn, tp, plane)) return false;
-    return checkHip(hipMemcpy(rgba, plane, (size_t)Tile.w * Tile.h * 16, hipMemcpyDeviceToHost), "reading the preview");
+    if (!BlendHistory(v, tp, false, mb.len) || !BlendMoments(v, tp, false)) return false;
+    if (!Run(gpuart_moments_error(Moments, b.filtered, mb.len, mb.blend, b.hits, b.prims, UserSphere.flags, lumFloor, Tile.w, Tile.h, &MomentsParams, mb.e),
+             Moments, MO, "measuring the history's variance")) return false;
+    plane = b.filtered;  // (the filter may run in place: include/gpuart_refine.h)
+    return Run(gpuart_refine_run(Refine, b.filtered, b.hits, b.prims, UserSphere.flags, mb.e, lumFloor, Tile.w, Tile.h, rf, b.filtered), Refine, RF, "filtering");
 }
 
 bool Renderer::StagePreview(const gpuart_denoise_params *dn, const gpuart_temporal_params *tp, const float *&plane) {
     if (!TemporalOn || !HistoryCommitted || PathTracing.numPathsRendered == 0) return StageDenoised(dn, plane);
-    if (!IsOK) return false;
-    if (!Denoiser && !Check(gpuart_denoise_create(Device, &Denoiser), "creating the denoiser", DN)) return false;
     gpuart_temporal_view v;
-    if (!StageView() || !MakeTemporalView(v)) return false;
-    const size_t n = (size_t)Tile.w * Tile.h;
-    const ViewBuffers b(DenoiseMem.mem, n);
-    if (!Check(gpuart_temporal_accumulate(Temporal, b.radiance, PathTracing.numPathsRendered, b.hits, b.prims, Tile.w, Tile.h, &v,
-                                          tp ? tp : &TemporalParams, 0, b.filtered, nullptr), "blending the history", TP)) return false;
-    if (!Check(gpuart_temporal_finish(Temporal), "blending the history", TP)) return false;
-    // (the filter may run in place: include/gpuart_denoise.h)
-    if (!Check(gpuart_denoise_run(Denoiser, b.filtered, b.hits, b.prims, UserSphere.flags, Tile.w, Tile.h, dn, b.filtered), "denoising", DN)) return false;
-    if (!Check(gpuart_denoise_finish(Denoiser), "denoising", DN)) return false;
-    plane = b.filtered;
-    return true;
+    if (!IsOK || !Ensure(Denoiser, DN) || !StageView() || !MakeTemporalView(v) || !BlendHistory(v, tp, false, nullptr)) return false;
+    const ViewBuffers b(DenoiseMem.mem, (size_t)Tile.w * Tile.h);
+    plane = b.filtered;  // (the filter may run in place: include/gpuart_denoise.h)
+    return Run(gpuart_denoise_run(Denoiser, b.filtered, b.hits, b.prims, UserSphere.flags, Tile.w, Tile.h, dn, b.filtered), Denoiser, DN, "denoising");
+}
+
+// ---- the batch loop of RenderUntil and RenderAdaptive ---------------------------------------------------------------------------
+template <class Show, class Judge>
+int Renderer::RenderBatches(unsigned batchPaths, const unsigned &batches, const unsigned &total, Show show, Judge judge) {
+    const unsigned &rendered = PathTracing.numPathsRendered;
+    // paths the estimate has never seen — a loaded checkpoint, plain passes after a restart, the other estimate's batches — are its
+    // first batch, of their own weight
+    if (batches == 0 && rendered > 0 && !show()) return -1;
+    for (;;) {
+        if (rendered < PathTracing.pathsPerPixel) {
+            const unsigned target = rendered + std::min(batchPaths, PathTracing.pathsPerPixel - rendered);
+            const unsigned per = std::max(1u, PathTracing.pathsPerPass);
+            // the passes of this batch are all the back end will see before the export observes them (a scheduling hint)
+            gpuart_hip_pt_plan(Backend, (target - rendered + per - 1) / per);
+            while (rendered < target) {
+                const unsigned before = rendered;
+                if (RenderPathTracingPass() == before) return -1;  // (the pass failed: Check has said why)
+            }
+        }
+        if (rendered > total && !show()) return -1;
+        if (batches >= 2)
+            if (const int rc = judge()) return rc;
+        if (rendered >= PathTracing.pathsPerPixel) return 0;
+    }
 }
 
 // ---- render until converged (include/gpuart_converge.h) -----------------------------------------------------------------
@@ -666,44 +692,27 @@ int Renderer::RenderUntil(float threshold, float maxAboveShare, unsigned batchPa
         std::cerr << "Renderer: RenderUntil after adaptive sampling retired blocks: its estimate keeps one path count for the frame (RenderAdaptive continues)." << std::endl;
         return -1;
     }
-    if (!Converge && !Check(gpuart_converge_create(Device, &Converge), "creating the convergence estimator", CV)) return -1;
-    if (!checkHip(hipSetDevice(Device), "hipSetDevice")) return -1;
-    const size_t n = (size_t)Tile.w * Tile.h;
-    if (!ConvergeMem.Fit(n, 16, "allocating the estimator's copy of the accumulator")) return -1;
+    if (!Ensure(Converge, CV) || !checkHip(hipSetDevice(Device), "hipSetDevice")) return -1;
+    if (!AccumMem.Fit((size_t)Tile.w * Tile.h, 16, "allocating the estimator's copy of the accumulator")) return -1;
+    float *accum = (float *)AccumMem.mem;
     // the raw accumulator as one more batch: divide_by 1 copies the sums exactly; a buffer of its own: the denoiser's cached view
     // (StageView) stays as it is. The wait lets the next export reuse the buffer.
-    auto showAccumulator = [&]() {
-        if (!Check(gpuart_hip_export(Backend, 1, ConvergeMem.mem, 1.0f), "exporting the accumulator")) return false;
-        if (!Check(gpuart_hip_finish(Backend), "waiting for the device")) return false;
-        if (!Check(gpuart_converge_update(Converge, (const float *)ConvergeMem.mem, PathTracing.numPathsRendered, Tile.w, Tile.h),
-                   "updating the convergence estimate", CV)) return false;
+    auto show = [&]() {
+        if (!Export(1, accum, 1.0f)) return false;
+        if (!Check(gpuart_converge_update(Converge, accum, PathTracing.numPathsRendered, Tile.w, Tile.h), "updating the convergence estimate", CV.lastError))
+            return false;
         ConvergeTotal = PathTracing.numPathsRendered;
         ConvergeBatches++;
         AdaptiveIsLast = false;
-        return Check(gpuart_converge_finish(Converge), "updating the convergence estimate", CV);
+        return Check(gpuart_converge_finish(Converge), "updating the convergence estimate", CV.lastError);
     };
-    // paths the estimate has never seen — a loaded checkpoint, plain passes after a restart — are its first batch, of their own weight
-    if (ConvergeBatches == 0 && PathTracing.numPathsRendered > 0 && !showAccumulator()) return -1;
-    for (;;) {
-        if (PathTracing.numPathsRendered < PathTracing.pathsPerPixel) {
-            const unsigned target = PathTracing.numPathsRendered + std::min(batchPaths, PathTracing.pathsPerPixel - PathTracing.numPathsRendered);
-            const unsigned per = std::max(1u, PathTracing.pathsPerPass);
-            // the passes of this batch are all the back end will see before the export observes them (a scheduling hint)
-            gpuart_hip_pt_plan(Backend, (target - PathTracing.numPathsRendered + per - 1) / per);
-            while (PathTracing.numPathsRendered < target) {
-                const unsigned before = PathTracing.numPathsRendered;
-                if (RenderPathTracingPass() == before) return -1;  // (the pass failed: Check has said why)
-            }
-        }
-        if (PathTracing.numPathsRendered > ConvergeTotal && !showAccumulator()) return -1;
-        if (ConvergeBatches >= 2) {
-            gpuart_converge_summary s;
-            if (!Check(gpuart_converge_measure(Converge, threshold, lumFloor, nullptr, &s), "measuring the convergence", CV)) return -1;
-            if (last) *last = s;
-            if ((double)s.above <= (double)maxAboveShare * (double)s.pixels) return 1;
-        }
-        if (PathTracing.numPathsRendered >= PathTracing.pathsPerPixel) return 0;
-    }
+    auto judge = [&]() {
+        gpuart_converge_summary s;
+        if (!Check(gpuart_converge_measure(Converge, threshold, lumFloor, nullptr, &s), "measuring the convergence", CV.lastError)) return -1;
+        if (last) *last = s;
+        return (double)s.above <= (double)maxAboveShare * (double)s.pixels ? 1 : 0;
+    };
+    return RenderBatches(batchPaths, ConvergeBatches, ConvergeTotal, show, judge);
 }
 
 // ---- adaptive sampling (include/gpuart_adaptive.h) ------------------------------------------------------------------------------
@@ -723,48 +732,33 @@ int Renderer::RenderAdaptive(float threshold, unsigned minPaths, unsigned batchP
         std::cerr << "Renderer: RenderAdaptive while temporal history is on: the blend takes one path count." << std::endl;
         return -1;
     }
-    if (!Adaptive && !Check(gpuart_adaptive_create(Device, &Adaptive), "creating the adaptive estimator", AD)) return -1;
-    if (!checkHip(hipSetDevice(Device), "hipSetDevice")) return -1;
-    const size_t n = (size_t)Tile.w * Tile.h;
-    if (!AdaptiveMem.Fit(n, 16, "allocating the estimator's copy of the accumulator")) return -1;
+    if (!Ensure(Adaptive, AD) || !checkHip(hipSetDevice(Device), "hipSetDevice")) return -1;
+    if (!AccumMem.Fit((size_t)Tile.w * Tile.h, 16, "allocating the estimator's copy of the accumulator")) return -1;
+    float *accum = (float *)AccumMem.mem;
     std::vector<uint32_t> list(TileBlocks());
-    // the raw accumulator and the blocks' counts as one more batch, in buffers of its own (RenderUntil's showAccumulator)
-    auto showAccumulator = [&]() {
-        if (!Check(gpuart_hip_export(Backend, 1, AdaptiveMem.mem, 1.0f), "exporting the accumulator") || !StageBlockPaths()) return false;
-        if (!Check(gpuart_hip_finish(Backend), "waiting for the device")) return false;
-        if (!Check(gpuart_adaptive_update(Adaptive, (const float *)AdaptiveMem.mem, BlockPathsMem, Tile.w, Tile.h), "updating the adaptive estimate", AD))
+    // the raw accumulator and the blocks' counts as one more batch, outside the denoiser's cached view (RenderUntil's show)
+    auto show = [&]() {
+        if (!Export(1, accum, 1.0f, true)) return false;
+        if (!Check(gpuart_adaptive_update(Adaptive, accum, (const uint32_t *)BlockPathsMem.mem, Tile.w, Tile.h), "updating the adaptive estimate", AD.lastError))
             return false;
         AdaptiveTotal = PathTracing.numPathsRendered;
         AdaptiveBatches++;
         AdaptiveIsLast = true;
-        return Check(gpuart_adaptive_finish(Adaptive), "updating the adaptive estimate", AD);
+        return Check(gpuart_adaptive_finish(Adaptive), "updating the adaptive estimate", AD.lastError);
     };
-    if (AdaptiveBatches == 0 && PathTracing.numPathsRendered > 0 && !showAccumulator()) return -1;
-    for (;;) {
-        if (PathTracing.numPathsRendered < PathTracing.pathsPerPixel) {
-            const unsigned target = PathTracing.numPathsRendered + std::min(batchPaths, PathTracing.pathsPerPixel - PathTracing.numPathsRendered);
-            const unsigned per = std::max(1u, PathTracing.pathsPerPass);
-            gpuart_hip_pt_plan(Backend, (target - PathTracing.numPathsRendered + per - 1) / per);
-            while (PathTracing.numPathsRendered < target) {
-                const unsigned before = PathTracing.numPathsRendered;
-                if (RenderPathTracingPass() == before) return -1;  // (the pass failed: Check has said why)
-            }
+    auto judge = [&]() {
+        gpuart_adaptive_summary s;
+        if (!Check(gpuart_adaptive_select(Adaptive, threshold, lumFloor, minPaths, nullptr, list.data(), &s), "selecting the active blocks", AD.lastError)) return -1;
+        if (last) *last = s;
+        // the list only ever shrinks: the same length is the same list
+        if (s.active_blocks < s.blocks && (!NonUniform || s.active_blocks != AdaptiveActive)) {
+            if (!Check(gpuart_hip_set_active_blocks(Backend, list.data(), s.active_blocks), "setting the active blocks")) return -1;
+            NonUniform = true;
+            AdaptiveActive = s.active_blocks;
         }
-        if (PathTracing.numPathsRendered > AdaptiveTotal && !showAccumulator()) return -1;
-        if (AdaptiveBatches >= 2) {
-            gpuart_adaptive_summary s;
-            if (!Check(gpuart_adaptive_select(Adaptive, threshold, lumFloor, minPaths, nullptr, list.data(), &s), "selecting the active blocks", AD)) return -1;
-            if (last) *last = s;
-            // the list only ever shrinks: the same length is the same list
-            if (s.active_blocks < s.blocks && (!NonUniform || s.active_blocks != AdaptiveActive)) {
-                if (!Check(gpuart_hip_set_active_blocks(Backend, list.data(), s.active_blocks), "setting the active blocks")) return -1;
-                NonUniform = true;
-                AdaptiveActive = s.active_blocks;
-            }
-            if (s.active_blocks == 0) return 1;
-        }
-        if (PathTracing.numPathsRendered >= PathTracing.pathsPerPixel) return 0;
-    }
+        return s.active_blocks == 0 ? 1 : 0;
+    };
+    return RenderBatches(batchPaths, AdaptiveBatches, AdaptiveTotal, show, judge);
 }
 
 bool Renderer::ReadSampleCounts(uint32_t *perPixel) {
@@ -777,83 +771,43 @@ bool Renderer::ReadSampleCounts(uint32_t *perPixel) {
     return true;
 }
 
-bool Renderer::ReadErrorMap(float *e, float lumFloor) {
-    if (IsOK && e && Adaptive && AdaptiveIsLast && AdaptiveBatches >= 2) {  // RenderAdaptive saw the last batch: its map
-        const size_t n = (size_t)Tile.w * Tile.h;
-        if (!RefineMem.Fit(n, 4, "allocating the error map")) return false;
-        if (!Check(gpuart_adaptive_error_map(Adaptive, lumFloor, (float *)RefineMem.mem, Tile.w, Tile.h), "reading the error map", AD) ||
-            !Check(gpuart_adaptive_finish(Adaptive), "reading the error map", AD)) return false;
-        return checkHip(hipMemcpy(e, RefineMem.mem, n * 4, hipMemcpyDeviceToHost), "reading the error map");
-    }
-    if (!IsOK || !e || !Converge || ConvergeBatches < 2) return false;
+// ---- the error map of the estimate that saw the last batch ------------------------------------------------------------------
+bool Renderer::StageErrorMap(float lumFloor, const float *&map) {
+    const Estimate which = LastEstimate();
+    if (!IsOK || which == NONE || !checkHip(hipSetDevice(Device), "hipSetDevice")) return false;
+    if (!ErrorMem.Fit((size_t)Tile.w * Tile.h, 4, "allocating the error map")) return false;
+    float *e = (float *)ErrorMem.mem;
+    map = e;
+    if (which == ADAPTIVE) return Run(gpuart_adaptive_error_map(Adaptive, lumFloor, e, Tile.w, Tile.h), Adaptive, AD, "measuring the error map");
+    // a measure changes nothing of the estimate; it waits for the map itself
     gpuart_converge_summary s;
-    return Check(gpuart_converge_measure_host(Converge, 0.0f, lumFloor, e, &s), "reading the error map", CV);
+    return Check(gpuart_converge_measure(Converge, 0.0f, lumFloor, e, &s), "measuring the error map", CV.lastError);
 }
 
-bool Renderer::ReadRefined(float *rgba, float lumFloor, const gpuart_refine_params *p) {
-    const float *plane;
-    if (!rgba || !StageRefined(lumFloor, p, plane)) return false;
-    return checkHip(hipMemcpy(rgba, plane, (size_t)Tile.w * Tile.h * 16, hipMemcpyDeviceToHost), "reading the refined frame");
+bool Renderer::ReadErrorMap(float *e, float lumFloor) {
+    const float *map;
+    return e && StageErrorMap(lumFloor, map) && ReadPlane(e, map, 4, "reading the error map");
 }
 
 bool Renderer::StageRefined(float lumFloor, const gpuart_refine_params *p, const float *&plane) {
-    const bool adaptive = Adaptive && AdaptiveIsLast && AdaptiveBatches >= 2;
-    if (!IsOK || (!adaptive && (!Converge || ConvergeBatches < 2))) return false;
-    if (!Refine && !Check(gpuart_refine_create(Device, &Refine), "creating the variance-guided filter", RF)) return false;
-    if (!StageView()) return false;
-    const size_t n = (size_t)Tile.w * Tile.h;
-    if (!RefineMem.Fit(n, 4, "allocating the filter's error map")) return false;
-    const ViewBuffers b(DenoiseMem.mem, n);
-    // a measure changes nothing of the estimate; it waits for the map itself
-    gpuart_converge_summary s;
-    if (adaptive) {
-        if (!Check(gpuart_adaptive_error_map(Adaptive, lumFloor, (float *)RefineMem.mem, Tile.w, Tile.h), "measuring the error map", AD) ||
-            !Check(gpuart_adaptive_finish(Adaptive), "measuring the error map", AD)) return false;
-    } else if (!Check(gpuart_converge_measure(Converge, 0.0f, lumFloor, (float *)RefineMem.mem, &s), "measuring the error map", CV)) return false;
-    if (!Check(gpuart_refine_run(Refine, b.radiance, b.hits, b.prims, UserSphere.flags, (const float *)RefineMem.mem, lumFloor, Tile.w, Tile.h, p,
-                                 b.filtered), "filtering", RF)) return false;
-    if (!Check(gpuart_refine_finish(Refine), "filtering", RF)) return false;
+    const float *map;
+    if (!IsOK || LastEstimate() == NONE || !Ensure(Refine, RF) || !StageView() || !StageErrorMap(lumFloor, map)) return false;
+    const ViewBuffers b(DenoiseMem.mem, (size_t)Tile.w * Tile.h);
     plane = b.filtered;
-    return true;
+    return Run(gpuart_refine_run(Refine, b.radiance, b.hits, b.prims, UserSphere.flags, map, lumFloor, Tile.w, Tile.h, p, b.filtered), Refine, RF, "filtering");
 }
 
 // ---- the display stage (include/gpuart_display.h) ---------------------------------------------------------------------------
 bool Renderer::ReadDisplay(uint8_t *rgba8, gpuart_display_source source, const gpuart_display_params *dp, float lumFloor) {
     if (!IsOK || !rgba8) return false;
-    if (!checkHip(hipSetDevice(Device), "hipSetDevice")) return false;
-    if (!Display && !Check(gpuart_display_create(Device, &Display), "creating the display stage", DP)) return false;
+    if (!checkHip(hipSetDevice(Device), "hipSetDevice") || !Ensure(Display, DP)) return false;
     const size_t n = (size_t)Tile.w * Tile.h;
     if (!DisplayMem.Fit(n, 16 + 4, "allocating the display stage's buffers")) return false;
-    float *own = (float *)DisplayMem.mem;
     uint8_t *words = (uint8_t *)DisplayMem.mem + n * 16;
-    const float *plane = own;
-    switch (source) {
-    case GPUART_DISPLAY_RADIANCE:
-        if (!ExportNormalized(own)) return false;
-        break;
-    case GPUART_DISPLAY_DIRECT:
-        if (!Check(gpuart_hip_export(Backend, 0, own, 1.0f), "exporting the frame") || !Check(gpuart_hip_finish(Backend), "waiting for the device"))
-            return false;
-        break;
-    case GPUART_DISPLAY_DENOISED:
-        if (!StageDenoised(nullptr, plane)) return false;
-        break;
-    case GPUART_DISPLAY_PREVIEW:
-        if (!StagePreview(nullptr, nullptr, plane)) return false;
-        break;
-    case GPUART_DISPLAY_GUIDED_PREVIEW:
-        if (!StageGuidedPreview(lumFloor, nullptr, nullptr, plane)) return false;
-        break;
-    case GPUART_DISPLAY_REFINED:
-        if (!StageRefined(lumFloor, nullptr, plane)) return false;
-        break;
-    default:
-        std::cerr << "Renderer: ReadDisplay: no such source " << (int)source << std::endl;
-        return false;
-    }
-    if (!Check(gpuart_display_run(Display, plane, words, Tile.w, Tile.h, Tile.x, Tile.y, dp), "encoding the frame", DP) ||
-        !Check(gpuart_display_finish(Display), "encoding the frame", DP)) return false;
-    return checkHip(hipMemcpy(rgba8, words, n * 4, hipMemcpyDeviceToHost), "reading the 8-bit frame");
+    const float *plane;
+    if (!StageSource(source, lumFloor, nullptr, nullptr, nullptr, (float *)DisplayMem.mem, plane)) return false;
+    return Run(gpuart_display_run(Display, plane, words, Tile.w, Tile.h, Tile.x, Tile.y, dp), Display, DP, "encoding the frame") &&
+           ReadPlane(rgba8, words, 4, "reading the 8-bit frame");
 }
 
 // ---- checkpoint / resume ---------------------------------------------------------------------------------------------

@@ -234,11 +234,11 @@ private:
 
     bool IsOK = false;
     int Device = 0;
-    /// Device memory for the tile's pixels: allocated again, its content lost, whenever their number changes.
+    /// Device memory for the tile's pixels, or for its 8x8 blocks: allocated again, its content lost, whenever their number changes.
     struct PixelBuffer {
         void *mem = nullptr;
-        size_t pixels = 0;
-        bool Fit(size_t n, size_t bytesPerPixel, const char *what);  ///< false if `what` failed (std::cerr says why)
+        size_t count = 0;
+        bool Fit(size_t n, size_t bytesPerElement, const char *what);  ///< false if `what` failed (std::cerr says why)
         void Release();
     };
     gpuart_denoise *Denoiser = nullptr;  ///< made by the first ReadDenoised
@@ -255,19 +255,19 @@ private:
     gpuart_moments_params MomentsParams{};    ///< of ReadGuidedPreview's error map (SetHistoryVariance)
     PixelBuffer MomentsMem;                   ///< the packed moments (16 B), their blend (16), len (4) and e (4) per tile pixel
     gpuart_converge *Converge = nullptr;  ///< made by the first RenderUntil
-    PixelBuffer ConvergeMem;              ///< the raw accumulator of RenderUntil's last batch, 16 B per tile pixel
     unsigned ConvergeBatches = 0, ConvergeTotal = 0;  ///< what Converge has seen since its last reset
     gpuart_adaptive *Adaptive = nullptr;  ///< made by the first RenderAdaptive
-    PixelBuffer AdaptiveMem;              ///< the raw accumulator of RenderAdaptive's last batch (and the frame a non-uniform ReadRadiance normalises), 16 B per tile pixel
-    uint32_t *BlockPathsMem = nullptr;    ///< device: one word per 8x8 block of the tile, the counts of the last batch or normalisation
-    size_t BlockPathsWords = 0;
+    /// The raw accumulator of the last batch an estimate was shown, or the frame a non-uniform ReadRadiance normalises: 16 B per tile
+    /// pixel. Nothing reads it after the call that filled it has returned, so the two estimates and that read share it.
+    PixelBuffer AccumMem;
+    PixelBuffer BlockPathsMem;            ///< one word per 8x8 block of the tile, the counts of the last batch or normalisation
     unsigned AdaptiveBatches = 0, AdaptiveTotal = 0;  ///< what Adaptive has seen since its last reset
     unsigned AdaptiveActive = 0;          ///< blocks on the back end's list while NonUniform
     bool NonUniform = false;              ///< a block has been retired: the blocks' path counts differ
     bool AdaptiveIsLast = false;          ///< the last batch any estimate saw was RenderAdaptive's
     unsigned CountBase = 0;               ///< paths per pixel a loaded checkpoint brought: the back end's block counts begin above them
     gpuart_refine *Refine = nullptr;      ///< made by the first ReadRefined
-    PixelBuffer RefineMem;                ///< ReadRefined's error map, 4 B per tile pixel
+    PixelBuffer ErrorMem;                 ///< the error map of ReadErrorMap and ReadRefined, 4 B per tile pixel
     gpuart_display *Display = nullptr;    ///< made by the first ReadDisplay
     PixelBuffer DisplayMem;               ///< ReadDisplay's: the plane of RADIANCE and DIRECT (16 B) and the 8-bit frame (4 B) per tile pixel
     ScreenBasis CurrentBasis;             ///< what SetCamera gave the back end
@@ -292,11 +292,39 @@ private:
     void CommitTemporalView();
     /// Temporal, TemporalMoments, Moments and MomentsMem for the tile, made where missing.
     bool EnsureVarianceHandles();
+    /// Makes the handle `h` of the image library `lib` if it is missing.
+    template <class H, class L> bool Ensure(H *&h, const L &lib);
+    /// Run, then wait for that handle: `status` is what the call just issued on `h` returned; both failures are reported under `what`.
+    template <class H, class L> bool Run(int status, H *h, const L &lib, const char *what);
+    /// The staged view (StageView) blended with the radiance history into the view's filtered plane, `len` (may be null) the blend's
+    /// length per pixel; tp = nullptr: TemporalParams; with `commit` the blend becomes the history. BlendMoments: the same for the
+    /// second history, the view's moments packed and blended with theirs in MomentsMem.
+    bool BlendHistory(const gpuart_temporal_view &v, const gpuart_temporal_params *tp, bool commit, float *len);
+    bool BlendMoments(const gpuart_temporal_view &v, const gpuart_temporal_params *tp, bool commit);
     /// The device halves of the Read* of the same names: each leaves its frame in device memory, complete, and says where.
     bool StageDenoised(const gpuart_denoise_params *p, const float *&plane);
     bool StagePreview(const gpuart_denoise_params *dn, const gpuart_temporal_params *tp, const float *&plane);
     bool StageGuidedPreview(float lumFloor, const gpuart_refine_params *rf, const gpuart_temporal_params *tp, const float *&plane);
     bool StageRefined(float lumFloor, const gpuart_refine_params *p, const float *&plane);
+    /// The one table of the frames a read can ask for: the Stage* that `source` names with the parameters it takes, or for RADIANCE and
+    /// DIRECT the export into `own` (tile-sized device memory; may be null for the others). False for a source that does not exist.
+    bool StageSource(gpuart_display_source source, float lumFloor, const gpuart_denoise_params *dn, const gpuart_refine_params *rf,
+                     const gpuart_temporal_params *tp, float *own, const float *&plane);
+    /// A float Read*: StageSource and ReadPlane, Tile.w*Tile.h elements of device memory into host memory (`what` names a failed copy).
+    bool ReadStaged(float *rgba, const char *what, gpuart_display_source source, float lumFloor, const gpuart_denoise_params *dn,
+                    const gpuart_refine_params *rf, const gpuart_temporal_params *tp);
+    bool ReadPlane(void *host, const void *plane, size_t bytesPerPixel, const char *what);
+    /// Which estimate saw the last batch, and so whose error map counts: RenderAdaptive's while it did, else RenderUntil's; NONE before
+    /// that one's second batch. StageErrorMap leaves that map for lumFloor in ErrorMem, complete on return (false for NONE).
+    enum Estimate { NONE, UNIFORM, ADAPTIVE };
+    Estimate LastEstimate() const {
+        return Adaptive && AdaptiveIsLast && AdaptiveBatches >= 2 ? ADAPTIVE : Converge && ConvergeBatches >= 2 ? UNIFORM : NONE;
+    }
+    bool StageErrorMap(float lumFloor, const float *&map);
+    /// The loop of RenderUntil and RenderAdaptive on an estimate that has seen `batches` batches and `total` paths (both read again after
+    /// every show): show() gives it the accumulator as one more batch, judge() is asked from the second batch on and ends the loop
+    /// with anything but 0. 0 at the cap, -1 where a pass or show failed.
+    template <class Show, class Judge> int RenderBatches(unsigned batchPaths, const unsigned &batches, const unsigned &total, Show show, Judge judge);
     /// Every call that drops the history also forgets the display stage's adapted exposure.
     void DropTemporalHistory() { if (Display) gpuart_display_reset(Display); if (HistoryCommitted) DropTemporalHistoryNow(); }
     void DropTemporalHistoryNow();
@@ -305,9 +333,15 @@ private:
     size_t TileBlocks() const { return (size_t)((Tile.w + 7) / 8) * ((Tile.h + 7) / 8); }
     /// The blocks' path counts (the checkpoint's included) into BlockPathsMem; complete after the next gpuart_hip_finish.
     bool StageBlockPaths();
+    /// What a normalised read divides by: the paths rendered, which is the reference's ptracingNormalize program
+    /// (shaders/pt_normalize.glsl:44-47); 1 for a raw read and before the first path.
+    float Divisor(bool normalized) const { return normalized && PathTracing.numPathsRendered ? (float)PathTracing.numPathsRendered : 1.0f; }
+    /// Image `which` of the back end (0 direct lighting, 1 the accumulator) divided by `div` into tile-sized device memory, with the
+    /// blocks' counts in BlockPathsMem where asked; complete on return.
+    bool Export(int which, float *device, float div, bool withBlockPaths = false);
     /// The one normalisation: the accumulator divided by the paths rendered into tile-sized device memory, complete on return. While the
     /// counts are uniform gpuart_hip_export's scalar division, as ever; otherwise the raw export and gpuart_adaptive_normalize.
-    bool ExportNormalized(float *device, bool normalized = true);
+    bool ExportNormalized(float *device);
     /// A status of the back end or, with their gpuart_*_last_error, of one of the image libraries: false (std::cerr says why) unless 0.
     bool Check(int status, const char *what, const char *(*lastError)(void) = gpuart_hip_last_error);
 };

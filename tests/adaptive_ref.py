@@ -125,33 +125,24 @@ def render_adaptive(est, pass_colour, accum, counts, issued, cap, per_pass, batc
     pass_colour(k, n) the colour image (h, w, 4; alpha ignored) of the pass that starts at issued path k with n paths per pixel: a
     listed pass adds it, in fp32, to the pixels of the listed blocks. Returns (1 converged / 0 at the cap, summary of the last select or
     None, accum, counts, issued, active list)."""
-    accum = np.array(accum, F)
-    h, w = accum.shape[:2]
-    counts = np.array(counts, np.int64).reshape(-1)
-    nb = counts.size
-    if active is None:
-        active = np.arange(nb)
-    per_pass = max(1, min(per_pass, cap))
-    s = None
-    if est.state is None and issued > 0:
-        est.update(accum, counts)
-    while True:
-        if issued < cap:
-            target = issued + min(batch_paths, cap - issued)
-            while issued < target:
-                n = min(per_pass, cap - issued)   # (a pass is clamped to the cap, not to the batch)
-                if len(active):
-                    m = block_mask(h, w, active)
-                    new = accum.copy()
-                    new[..., :3] = accum[..., :3] + np.asarray(pass_colour(issued, n), F)[..., :3]
-                    accum = np.where(m[..., None], new, accum)
-                    counts[np.asarray(active, np.int64)] += n
-                issued += n
-        if issued > int(est.seen.max()) if est.state is not None else issued > 0:
-            est.update(accum, counts)
-        if est.updates >= 2:
-            active, s, _ = est.select(threshold, lum_floor, min_paths)
-            if not len(active):
-                return 1, s, accum, counts, issued, active
-        if issued >= cap:
-            return 0, s, accum, counts, issued, active
+    h, w = np.shape(accum)[:2]
+    st = dict(accum=np.array(accum, F), counts=np.array(counts, np.int64).reshape(-1), summary=None)
+    st["active"] = np.arange(st["counts"].size) if active is None else active
+
+    def render_pass(k, n):
+        if len(st["active"]):
+            m = block_mask(h, w, st["active"])
+            new = st["accum"].copy()
+            new[..., :3] = st["accum"][..., :3] + np.asarray(pass_colour(k, n), F)[..., :3]
+            st["accum"] = np.where(m[..., None], new, st["accum"])
+            st["counts"][np.asarray(st["active"], np.int64)] += n
+
+    def judge():
+        st["active"], st["summary"], _ = est.select(threshold, lum_floor, min_paths)
+        return not len(st["active"])
+
+    # (the loop is the uniform estimate's, tests/converge_ref.py batch_loop: the batches are the update calls, the total the largest count)
+    converged, issued = converge_ref.batch_loop(issued, cap, per_pass, batch_paths,
+                                                lambda: (est.updates, int(est.seen.max()) if est.state is not None else 0),
+                                                lambda total: est.update(st["accum"], st["counts"]), judge, render_pass)
+    return int(converged), st["summary"], st["accum"], st["counts"], issued, st["active"]

@@ -136,27 +136,44 @@ def accumulator_floor(total, b_min):
     return 2.0 ** -22 * float(np.sqrt(float(total) / float(b_min)))
 
 
-def render_until(est, accum_at, rendered, cap, per_pass, batch_paths, threshold, max_above_share, lum_floor):
-    """What one call of Renderer::RenderUntil does, on the Estimator `est` the earlier calls left (a reset one after anything that
-    restarted the accumulation): `rendered` paths are in the accumulator, `cap` and `per_pass` are RestartPathTracing's, accum_at(total)
-    is the raw accumulator after `total` paths. Returns (converged, the summary of the last measure or None, paths rendered)."""
+def batch_loop(rendered, cap, per_pass, batch_paths, seen, show, judge, render_pass=None):
+    """The loop Renderer::RenderUntil and Renderer::RenderAdaptive share (Renderer::RenderBatches): `rendered` paths are in the accumulator,
+    `cap` and `per_pass` are RestartPathTracing's. seen() is what the estimate has seen, (batches, total); show(rendered) gives it the
+    accumulator as one more batch; judge() is asked from the second batch on and ends the loop when true; render_pass(rendered, n), if
+    given, renders a pass of n paths. Paths the estimate has never seen are its first batch, of their own weight. Returns (whether
+    judge ended the loop, paths rendered)."""
     per_pass = max(1, min(per_pass, cap))
-    s = None
-    if est.batches == 0 and rendered > 0:
-        est.update(accum_at(rendered), rendered)
+    if seen()[0] == 0 and rendered > 0:
+        show(rendered)
     while True:
         if rendered < cap:
             target = rendered + min(batch_paths, cap - rendered)
             while rendered < target:
-                rendered += min(per_pass, cap - rendered)   # (a pass is clamped to the cap, not to the batch)
-        if rendered > est.total:
-            est.update(accum_at(rendered), rendered)
-        if est.batches >= 2:
-            s, _ = est.measure(threshold, lum_floor)
-            if float(s["above"]) <= float(F(max_above_share)) * float(s["pixels"]):
-                return True, s, rendered
+                n = min(per_pass, cap - rendered)   # (a pass is clamped to the cap, not to the batch)
+                if render_pass is not None:
+                    render_pass(rendered, n)
+                rendered += n
+        if rendered > seen()[1]:
+            show(rendered)
+        if seen()[0] >= 2 and judge():
+            return True, rendered
         if rendered >= cap:
-            return False, s, rendered
+            return False, rendered
+
+
+def render_until(est, accum_at, rendered, cap, per_pass, batch_paths, threshold, max_above_share, lum_floor):
+    """What one call of Renderer::RenderUntil does, on the Estimator `est` the earlier calls left (a reset one after anything that
+    restarted the accumulation): `rendered` paths are in the accumulator, `cap` and `per_pass` are RestartPathTracing's, accum_at(total)
+    is the raw accumulator after `total` paths. Returns (converged, the summary of the last measure or None, paths rendered)."""
+    last = [None]
+
+    def judge():
+        last[0], _ = est.measure(threshold, lum_floor)
+        return float(last[0]["above"]) <= float(F(max_above_share)) * float(last[0]["pixels"])
+
+    converged, rendered = batch_loop(rendered, cap, per_pass, batch_paths, lambda: (est.batches, est.total),
+                                     lambda total: est.update(accum_at(total), total), judge)
+    return converged, last[0], rendered
 
 
 def stops_at(accums, totals, threshold, max_above_share, lum_floor):

@@ -739,6 +739,41 @@ def test_render_adaptive_at_the_cap_and_its_refusals(B):
 
 
 @pytest.mark.gpu
+def test_the_error_map_is_that_of_the_estimate_that_saw_the_last_batch(B):
+    """RenderUntil, RenderAdaptive, RenderUntil on one accumulation: read_error_map and read_refined take the adaptive estimate's map
+    after the second call and the uniform estimate's again after the third, bit for bit, and the two maps differ."""
+    from tests.test_refine import expected_refined
+    colours = render_inputs("box")[4]
+    sums = {n: functools.reduce(lambda a, c: a + c, colours[:n], np.zeros_like(colours[0])) for n in (4, 8, CAP)}
+    r = make_renderer(B, "box")
+    try:
+        converged, s = r.render_until(1e9, 0.0, BATCH, FLOOR)
+        assert converged and s["total"] == 8 and s["batches"] == 2
+        converged, s = r.render_adaptive(0.1, 1000, BATCH, FLOOR)   # the 8 paths are its first batch, of their own weight
+        assert converged is False and s["active_blocks"] == s["blocks"] == 48 and s["paths_min"] == s["paths_max"] == CAP
+        est = AR.Estimator()
+        rc = AR.render_adaptive(est, lambda k, n: colours[k], sums[8], np.full(48, 8), 8, CAP, 1, BATCH, 0.1, 1000, FLOOR)[0]
+        assert rc == 0 and est.updates == 15
+        e_adaptive = est.error(FLOOR)
+        assert_same_bits(r.read_error_map(FLOOR), e_adaptive, "error map after RenderAdaptive")
+        assert_same_bits(r.read_refined(FLOOR), expected_refined(r, B), "read_refined after RenderAdaptive")
+        converged, s = r.render_until(1e9, 0.0, BATCH, FLOOR)   # nothing left to render: the 56 paths are its third batch
+        assert converged and s["batches"] == 3 and s["total"] == CAP
+        uni = converge_ref.Estimator()
+        for n in (4, 8, CAP):
+            uni.update(sums[n], n)
+        e_uniform = uni.error(FLOOR)
+        assert_same_bits(r.read_error_map(FLOOR), e_uniform, "error map after RenderUntil took the turn back")
+        assert_same_bits(r.read_refined(FLOOR), expected_refined(r, B), "read_refined after RenderUntil took the turn back")
+        differ = e_adaptive.view(np.uint32) != e_uniform.view(np.uint32)
+        assert np.isfinite(e_adaptive).all() and np.isfinite(e_uniform).all() and differ.sum() > differ.size // 2, int(differ.sum())
+        r.restart_path_tracing(1, CAP)
+        assert r.read_error_map(FLOOR) is None and r.read_refined(FLOOR) is None
+    finally:
+        r.close()
+
+
+@pytest.mark.gpu
 def test_render_adaptive_after_a_loaded_checkpoint(B, tmp_path):
     """A loaded checkpoint's six paths are the first batch, of their own weight, and part of every count: the counts, the summary and the
     accumulator are the restatement's on the oracle's colours from pass 6 on (the checkpoint restores the generator), whatever the
