@@ -106,6 +106,20 @@ def moments_params(params):
     return _params(MomentsParams, MOMENTS_DEFAULTS, "moments", params)
 
 
+class AntiLagParams(C.Structure):
+    """gpuart_antilag_params (include/gpuart_antilag.h)."""
+    _fields_ = [("fast_history", C.c_float), ("min_batches", C.c_float), ("min_votes", C.c_float), ("clip", C.c_float), ("z_lo", C.c_float),
+                ("z_hi", C.c_float)]
+
+
+ANTILAG_DEFAULTS = dict(fast_history=4.0, min_batches=8.0, min_votes=8.0, clip=3.0, z_lo=2.0, z_hi=4.0)
+
+
+def antilag_params(params):
+    """None (the library's defaults), an AntiLagParams, or a dict of fields that replace the defaults -> AntiLagParams or None."""
+    return _params(AntiLagParams, ANTILAG_DEFAULTS, "anti-lag", params)
+
+
 class DisplayParams(C.Structure):
     """gpuart_display_params (include/gpuart_display.h)."""
     _fields_ = [("gain", C.c_float), ("auto_exposure", C.c_uint32), ("key", C.c_float), ("lo_share", C.c_float), ("hi_share", C.c_float),
@@ -279,6 +293,11 @@ def adaptive_lib():
 def moments_lib():
     """libgpuart_moments.so; raises NativeLibraryMissing if it has not been built (no fallback)."""
     return _image_lib("moments")
+
+
+def antilag_lib():
+    """libgpuart_antilag.so; raises NativeLibraryMissing if it has not been built (no fallback)."""
+    return _image_lib("antilag")
 
 
 def display_lib():
@@ -993,6 +1012,11 @@ class Renderer:
         self.L.gpuart_renderer_set_user_sphere(self.h, _f3(pos), C.c_float(radius), C.c_float(emittance),
                                                C.c_int(int(specular)), C.c_int(int(fuzzy)))
 
+    def set_user_sphere_pos(self, pos):
+        """Renderer::SetUserSpherePos: moves the user sphere alone; with set_temporal_history on, the view is committed and the history
+        kept (set_user_sphere also sets emittance and flags, which drops it)."""
+        self.L.gpuart_renderer_set_user_sphere_pos(self.h, _f3(pos))
+
     def set_max_path_segments(self, n): self.L.gpuart_renderer_set_max_path_segments(self.h, C.c_uint(n))
     def set_seed(self, seed): self.L.gpuart_renderer_set_seed(self.h, C.c_uint32(seed))
     def set_min_weight(self, w): self.L.gpuart_renderer_set_min_weight(self.h, C.c_float(w))
@@ -1056,6 +1080,15 @@ class Renderer:
         p = moments_params(params)
         if not self.L.gpuart_renderer_set_history_variance(self.h, C.c_int(1 if on else 0), C.byref(p) if p is not None else None):
             raise ValueError("moments parameters out of range")
+
+    def set_history_antilag(self, on=True, params=None):
+        """Renderer::SetHistoryAntiLag: while on (and set_temporal_history and set_history_variance are), every commit also carries the
+        radiance through a third, short history, and read_guided_preview follows it where the lighting has changed
+        (include/gpuart_antilag.h); turning it on or off drops the temporal history. params = None (the defaults), an AntiLagParams or
+        a dict of fields that replace the defaults."""
+        p = antilag_params(params)
+        if not self.L.gpuart_renderer_set_history_antilag(self.h, C.c_int(1 if on else 0), C.byref(p) if p is not None else None):
+            raise ValueError("anti-lag parameters out of range")
 
     def read_guided_preview(self, lum_floor=CONVERGE_DEFAULT_FLOOR, refine=None, temporal=None):
         """Renderer::ReadGuidedPreview: the history blended with the accumulator, then filtered by the variance-guided filter with the
@@ -1449,6 +1482,57 @@ class Moments(_ImageHandle):
         self._chk(self.L.gpuart_moments_error_host(self.h, _p(rgba), _p(length), _p(moments), _p(hits), _p(prims), C.c_uint32(us_flags),
                                                    C.c_float(lum_floor), C.c_uint32(w), C.c_uint32(h), pp, _p(res)))
         return res
+
+
+# ---- a fast history where the lighting changed (include/gpuart_antilag.h) ----------------------------------------------------
+class AntiLagError(RuntimeError):
+    """A gpuart_antilag_* call returned an error; `code` is the library's (GPUART_HIP_ERR_*)."""
+    code = None
+
+
+class AntiLag(_ImageHandle):
+    """A gpuart_antilag handle on one device."""
+    NAME, Error = "antilag", AntiLagError
+
+    def mix(self, slow, slow_len, fast, fast_len, moments, hits, prims, us_flags=0, params=None, out=None, out_len=None, want_alpha=True):
+        """Moves the slow blend and its len towards the fast one where they disagree by more than the measured variance explains:
+        slow, slow_len and fast, fast_len are what two Temporal handles returned for the radiance with a long and a short window,
+        moments what the long window's second handle returned for the packed image; hits, prims, us_flags as Denoiser.run; params =
+        None (the defaults), an AntiLagParams or a dict of fields that replace the defaults. torch tensors on this handle's device run
+        through gpuart_antilag_mix (out may be slow itself, out_len slow_len itself), NumPy arrays through gpuart_antilag_mix_host.
+        -> (out, out_len, alpha); alpha is None without want_alpha."""
+        p = antilag_params(params)
+        pp = C.byref(p) if p is not None else None
+        dev, slow, hits, prims, res, h, w = _gbuffer_args(self.device, slow, hits, prims, out)
+        planes = (("slow_len", slow_len, (h, w)), ("fast", fast, (h, w, 4)), ("fast_len", fast_len, (h, w)), ("moments", moments, (h, w, 4)))
+        if dev is not None:
+            import torch
+            for name, a, shape in planes:
+                if not type(a).__module__.startswith("torch") or a.dtype != torch.float32 or tuple(a.shape) != shape or not a.is_contiguous() or \
+                        a.device != dev:
+                    raise ValueError("%s must be a contiguous %s float32 tensor on %s" % (name, shape, dev))
+            ln = out_len if out_len is not None else torch.empty((h, w), dtype=torch.float32, device=dev)
+            if ln.dtype != torch.float32 or tuple(ln.shape) != (h, w) or not ln.is_contiguous() or ln.device != dev:
+                raise ValueError("out_len must be a contiguous (h, w) float32 tensor on %s" % dev)
+            al = torch.empty((h, w), dtype=torch.float32, device=dev) if want_alpha else None
+            torch.cuda.current_stream(dev).synchronize()
+            self._chk(self.L.gpuart_antilag_mix(self.h, _dp(slow), _dp(slow_len), _dp(fast), _dp(fast_len), _dp(moments), _dp(hits), _dp(prims),
+                                                C.c_uint32(us_flags), C.c_uint32(w), C.c_uint32(h), pp, _dp(res), _dp(ln),
+                                                _dp(al) if al is not None else None))
+            self.finish()
+            return res, ln, al
+        slow_len, fast, fast_len, moments = (np.ascontiguousarray(a, np.float32) for _, a, _ in planes)
+        for (name, _, shape), a in zip(planes, (slow_len, fast, fast_len, moments)):
+            if a.shape != shape:
+                raise ValueError("%s must be %s float32" % (name, shape))
+        ln = out_len if out_len is not None else np.empty((h, w), np.float32)
+        if ln.dtype != np.float32 or ln.shape != (h, w) or not ln.flags.c_contiguous:
+            raise ValueError("out_len must be a contiguous (h, w) float32 array")
+        al = np.empty((h, w), np.float32) if want_alpha else None
+        self._chk(self.L.gpuart_antilag_mix_host(self.h, _p(slow), _p(slow_len), _p(fast), _p(fast_len), _p(moments), _p(hits), _p(prims),
+                                                 C.c_uint32(us_flags), C.c_uint32(w), C.c_uint32(h), pp, _p(res), _p(ln),
+                                                 _p(al) if al is not None else None))
+        return res, ln, al
 
 
 # ---- the convergence estimate (include/gpuart_converge.h) -----------------------------------------------------------------

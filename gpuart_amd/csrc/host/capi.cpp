@@ -251,6 +251,7 @@ void gpuart_renderer_set_user_sphere(gpuart_renderer *r, const float pos[3], flo
     r->impl.SetUserSphereSpecular(specular != 0);
     r->impl.SetUserSphereFuzzy(fuzzy != 0);
 }
+void gpuart_renderer_set_user_sphere_pos(gpuart_renderer *r, const float pos[3]) { r->impl.SetUserSpherePos(Vec3f(pos[0], pos[1], pos[2])); }
 void gpuart_renderer_set_max_path_segments(gpuart_renderer *r, unsigned n) { r->impl.SetMaxPathSegments(n); }
 void gpuart_renderer_set_seed(gpuart_renderer *r, uint32_t seed) { r->impl.SetSeed(seed); }
 void gpuart_renderer_render_direct(gpuart_renderer *r) { r->impl.RenderDirectLighting(); }
@@ -286,6 +287,9 @@ int gpuart_renderer_read_display(gpuart_renderer *r, uint8_t *rgba8, int source,
 }
 int gpuart_renderer_set_history_variance(gpuart_renderer *r, int on, const gpuart_moments_params *p) {
     return r->impl.SetHistoryVariance(on != 0, p) ? 1 : 0;
+}
+int gpuart_renderer_set_history_antilag(gpuart_renderer *r, int on, const gpuart_antilag_params *p) {
+    return r->impl.SetHistoryAntiLag(on != 0, p) ? 1 : 0;
 }
 int gpuart_renderer_read_guided_preview(gpuart_renderer *r, float *rgba, float lumFloor, const gpuart_refine_params *rf,
                                         const gpuart_temporal_params *tp) {

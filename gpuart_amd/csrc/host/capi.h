@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "gpuart_adaptive.h"
+#include "gpuart_antilag.h"
 #include "gpuart_converge.h"
 #include "gpuart_denoise.h"
 #include "gpuart_display.h"
@@ -74,6 +75,8 @@ int gpuart_renderer_set_interleaved_tile(gpuart_renderer *r, unsigned x0, unsign
 void gpuart_renderer_set_sun(gpuart_renderer *r, float azimuth, float altitude, int directLighting);
 void gpuart_renderer_set_user_sphere(gpuart_renderer *r, const float pos[3], float radius, float emittance, int specular,
                                      int fuzzy);
+/* Renderer::SetUserSpherePos: the position alone; with the temporal history on it commits the view and keeps the history. */
+void gpuart_renderer_set_user_sphere_pos(gpuart_renderer *r, const float pos[3]);
 void gpuart_renderer_set_max_path_segments(gpuart_renderer *r, unsigned n);
 void gpuart_renderer_set_seed(gpuart_renderer *r, uint32_t seed);
 void gpuart_renderer_render_direct(gpuart_renderer *r);
@@ -110,6 +113,10 @@ int gpuart_renderer_read_display(gpuart_renderer *r, uint8_t *rgba8, int source,
 /* Renderer::SetHistoryVariance: carry the luminance's moments through a second history (include/gpuart_moments.h); toggling drops the
  * temporal history. p = NULL: the defaults. 1 on success, 0 for parameters out of range. */
 int gpuart_renderer_set_history_variance(gpuart_renderer *r, int on, const gpuart_moments_params *p);
+/* Renderer::SetHistoryAntiLag: carry the radiance through a third, short history and let the guided preview follow it where the lighting
+ * changed (include/gpuart_antilag.h); toggling drops the temporal history. p = NULL: the defaults. 1 on success, 0 for parameters out
+ * of range. */
+int gpuart_renderer_set_history_antilag(gpuart_renderer *r, int on, const gpuart_antilag_params *p);
 /* Renderer::ReadGuidedPreview: the history blend filtered by gpuart_refine_run with the error map of the history's measured variance.
  * rf, tp = NULL: the defaults / what gpuart_renderer_set_temporal_history was given. 1 on success; 0 while the variance or the
  * history is off, before the view's first path, or on error. */

@@ -65,6 +65,7 @@ Renderer::Renderer(unsigned viewportWidth, unsigned viewportHeight, const Camera
     Device = device;
     gpuart_temporal_defaults(&TemporalParams);
     gpuart_moments_defaults(&MomentsParams);
+    gpuart_antilag_defaults(&AntiLagParams);
 
     if (!Check(gpuart_hip_create(device, &Backend), "creating the device back end")) return;
     if (viewportWidth == 0 || viewportHeight == 0) {
@@ -84,6 +85,9 @@ Renderer::~Renderer() {
     BlockPathsMem.Release();
     if (Converge) gpuart_converge_destroy(Converge);
     AccumMem.Release();
+    if (AntiLag) gpuart_antilag_destroy(AntiLag);
+    if (TemporalFast) gpuart_temporal_destroy(TemporalFast);
+    AntiLagMem.Release();
     if (Moments) gpuart_moments_destroy(Moments);
     if (TemporalMoments) gpuart_temporal_destroy(TemporalMoments);
     MomentsMem.Release();
@@ -401,6 +405,8 @@ const Lib<gpuart_denoise> DN{gpuart_denoise_create, gpuart_denoise_finish, gpuar
 const Lib<gpuart_temporal> TP{gpuart_temporal_create, gpuart_temporal_finish, gpuart_temporal_last_error, "creating the temporal accumulator"};
 const Lib<gpuart_temporal> TPM{gpuart_temporal_create, gpuart_temporal_finish, gpuart_temporal_last_error, "creating the moments' temporal accumulator"};
 const Lib<gpuart_moments> MO{gpuart_moments_create, gpuart_moments_finish, gpuart_moments_last_error, "creating the moments library's handle"};
+const Lib<gpuart_temporal> TPF{gpuart_temporal_create, gpuart_temporal_finish, gpuart_temporal_last_error, "creating the fast history's temporal accumulator"};
+const Lib<gpuart_antilag> AL{gpuart_antilag_create, gpuart_antilag_finish, gpuart_antilag_last_error, "creating the anti-lag library's handle"};
 const Lib<gpuart_converge> CV{gpuart_converge_create, gpuart_converge_finish, gpuart_converge_last_error, "creating the convergence estimator"};
 const Lib<gpuart_adaptive> AD{gpuart_adaptive_create, gpuart_adaptive_finish, gpuart_adaptive_last_error, "creating the adaptive estimator"};
 const Lib<gpuart_refine> RF{gpuart_refine_create, gpuart_refine_finish, gpuart_refine_last_error, "creating the variance-guided filter"};
@@ -426,6 +432,11 @@ struct MomentBuffers {
     float *packed, *blend, *len, *e;
     MomentBuffers(void *mem, size_t n)
         : packed((float *)mem), blend((float *)((char *)mem + n * 16)), len((float *)((char *)mem + n * 32)), e((float *)((char *)mem + n * 36)) {}
+};
+/// AntiLagMem's planes: the fast blend, its len and the mix's alpha.
+struct AntiLagBuffers {
+    float *fast, *len, *alpha;
+    AntiLagBuffers(void *mem, size_t n) : fast((float *)mem), len((float *)((char *)mem + n * 16)), alpha((float *)((char *)mem + n * 20)) {}
 };
 }  // namespace
 
@@ -565,6 +576,7 @@ bool Renderer::SetTemporalHistory(bool on, const gpuart_temporal_params *tp) {
 void Renderer::DropTemporalHistoryNow() {
     if (Temporal) gpuart_temporal_reset(Temporal);
     if (TemporalMoments) gpuart_temporal_reset(TemporalMoments);
+    if (TemporalFast) gpuart_temporal_reset(TemporalFast);
     HistoryCommitted = false;
 }
 
@@ -598,9 +610,10 @@ bool Renderer::BlendMoments(const gpuart_temporal_view &v, const gpuart_temporal
 void Renderer::CommitTemporalView() {
     if (!TemporalOn || !IsOK || PathTracing.numPathsRendered == 0) return;
     gpuart_temporal_view v;
-    // the same commit for the moments: the two histories have seen the same views or none
+    // the same commit for the moments and the fast history: the histories have seen the same views or none
     HistoryCommitted = Ensure(Temporal, TP) && StageView() && MakeTemporalView(v) && BlendHistory(v, nullptr, true, nullptr) &&
-                       (!VarianceOn || (EnsureVarianceHandles() && BlendMoments(v, nullptr, true)));
+                       (!VarianceOn || (EnsureVarianceHandles() && BlendMoments(v, nullptr, true))) &&
+                       (!AntiLagActive() || (EnsureAntiLagHandles() && BlendFast(v, nullptr, true)));
     if (!HistoryCommitted) DropTemporalHistoryNow();  // A commit that fails leaves no history rather than a stale one.
 }
 
@@ -627,6 +640,42 @@ bool Renderer::EnsureVarianceHandles() {
     return MomentsMem.Fit((size_t)Tile.w * Tile.h, 16 + 16 + 4 + 4, "allocating the moments' buffers");
 }
 
+// ---- a fast history where the lighting changed (include/gpuart_antilag.h) -------------------------------------------------
+bool Renderer::SetHistoryAntiLag(bool on, const gpuart_antilag_params *p) {
+    if (p) {
+        // the ranges gpuart_antilag_mix accepts; fast_history becomes a max_history
+        if (!finite(p->fast_history) || !(p->fast_history >= 0) || !finite(p->min_batches) || !(p->min_batches > 1) || !finite(p->min_votes) ||
+            !(p->min_votes >= 1) || !finite(p->clip) || !(p->clip > 0) || !finite(p->z_lo) || !(p->z_lo >= 0) || !finite(p->z_hi) ||
+            !(p->z_hi > p->z_lo)) {
+            std::cerr << "Renderer: anti-lag parameters out of range." << std::endl;
+            return false;
+        }
+        AntiLagParams = *p;
+    } else {
+        gpuart_antilag_defaults(&AntiLagParams);
+    }
+    if (on != AntiLagOn) DropTemporalHistory();  // a history the third handle has not seen
+    AntiLagOn = on;
+    return true;
+}
+
+bool Renderer::EnsureAntiLagHandles() {
+    if (!checkHip(hipSetDevice(Device), "hipSetDevice")) return false;
+    if (!Ensure(TemporalFast, TPF) || !Ensure(AntiLag, AL)) return false;
+    return AntiLagMem.Fit((size_t)Tile.w * Tile.h, 16 + 4 + 4, "allocating the anti-lag buffers");
+}
+
+bool Renderer::BlendFast(const gpuart_temporal_view &v, const gpuart_temporal_params *tp, bool commit) {
+    const size_t n = (size_t)Tile.w * Tile.h;
+    const ViewBuffers b(DenoiseMem.mem, n);
+    const AntiLagBuffers ab(AntiLagMem.mem, n);
+    gpuart_temporal_params fp = tp ? *tp : TemporalParams;
+    if (AntiLagParams.fast_history < fp.max_history) fp.max_history = AntiLagParams.fast_history;
+    return Run(gpuart_temporal_accumulate(TemporalFast, b.radiance, PathTracing.numPathsRendered, b.hits, b.prims, Tile.w, Tile.h, &v, &fp, commit,
+                                          ab.fast, ab.len),
+               TemporalFast, TPF, commit ? "committing the view to the fast history" : "blending the fast history");
+}
+
 bool Renderer::StageGuidedPreview(float lumFloor, const gpuart_refine_params *rf, const gpuart_temporal_params *tp, const float *&plane) {
     if (!IsOK || !VarianceOn || !TemporalOn || PathTracing.numPathsRendered == 0) return false;
     gpuart_temporal_view v;
@@ -636,6 +685,14 @@ bool Renderer::StageGuidedPreview(float lumFloor, const gpuart_refine_params *rf
     const MomentBuffers mb(MomentsMem.mem, n);
     // (without a commit both handles have no history: every blend is its input and len = s)
     if (!BlendHistory(v, tp, false, mb.len) || !BlendMoments(v, tp, false)) return false;
+    if (AntiLagActive()) {
+        // the long blend and its len move towards the short one where the lighting changed; the error map below sees the mixed len
+        if (!EnsureAntiLagHandles() || !BlendFast(v, tp, false)) return false;
+        const AntiLagBuffers ab(AntiLagMem.mem, n);
+        if (!Run(gpuart_antilag_mix(AntiLag, b.filtered, mb.len, ab.fast, ab.len, mb.blend, b.hits, b.prims, UserSphere.flags, Tile.w, Tile.h,
+                                    &AntiLagParams, b.filtered, mb.len, ab.alpha),
+                 AntiLag, AL, "mixing the fast history in")) return false;
+    }
     if (!Run(gpuart_moments_error(Moments, b.filtered, mb.len, mb.blend, b.hits, b.prims, UserSphere.flags, lumFloor, Tile.w, Tile.h, &MomentsParams, mb.e),
              Moments, MO, "measuring the history's variance")) return false;
     plane = b.filtered;  // (the filter may run in place: include/gpuart_refine.h)

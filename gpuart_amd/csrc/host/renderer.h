@@ -8,7 +8,7 @@
 // MAX_PATH_SEGMENTS / the RNG seed / the viewport fixed at compile time):
 //   ReadDirectLighting, ReadRadiance, Finish, SetMaxPathSegments, SetMinWeight, SetSeed,
 //   SetTile, GetBackend, ComputeScreenBasis, GetNumPathsRendered, ReadDenoised, SetTemporalHistory, ReadPreview, RenderUntil,
-//   ReadErrorMap, ReadRefined, SetHistoryVariance, ReadGuidedPreview, ReadDisplay.
+//   ReadErrorMap, ReadRefined, SetHistoryVariance, SetHistoryAntiLag, ReadGuidedPreview, ReadDisplay.
 #ifndef GPUART_RENDERER_H
 #define GPUART_RENDERER_H
 
@@ -19,6 +19,7 @@
 #include "bvh.h"
 #include "core.h"
 #include "gpuart_adaptive.h"
+#include "gpuart_antilag.h"
 #include "gpuart_converge.h"
 #include "gpuart_denoise.h"
 #include "gpuart_display.h"
@@ -122,6 +123,15 @@ public:
     /// of range (nothing changes).
     bool SetHistoryVariance(bool on, const gpuart_moments_params *p = nullptr);
     bool GetHistoryVariance() const { return VarianceOn; }
+    /// Carries the radiance through a third, short history as well and lets ReadGuidedPreview follow it where the lighting has changed
+    /// (include/gpuart_antilag.h); off by default, and without effect unless SetTemporalHistory and SetHistoryVariance are both on.
+    /// While it is on, every commit also commits the same staged view to a third gpuart_temporal handle, with the same G-buffer, view
+    /// and parameters but max_history = min(fast_history, the commits' max_history); if any of the three commits fails all three
+    /// histories are dropped. ReadGuidedPreview then blends that history too and gpuart_antilag_mix moves the long blend and its len
+    /// towards the short one before the error map is made. Turning it on or off drops the temporal history: the three handles must
+    /// have seen the same commits. p = nullptr: the library's defaults. False for parameters out of range (nothing changes).
+    bool SetHistoryAntiLag(bool on, const gpuart_antilag_params *p = nullptr);
+    bool GetHistoryAntiLag() const { return AntiLagOn; }
     /// The preview guided by the history's measured variance: the radiance and the packed moments of the current accumulator are blended
     /// with their histories (gpuart_temporal_accumulate without commit; tp = nullptr: what SetTemporalHistory was given),
     /// gpuart_moments_error turns the two blends into an error map for lumFloor, and gpuart_refine_run (rf; nullptr: its defaults)
@@ -254,6 +264,11 @@ private:
     gpuart_moments *Moments = nullptr;        ///< made with TemporalMoments
     gpuart_moments_params MomentsParams{};    ///< of ReadGuidedPreview's error map (SetHistoryVariance)
     PixelBuffer MomentsMem;                   ///< the packed moments (16 B), their blend (16), len (4) and e (4) per tile pixel
+    bool AntiLagOn = false;                   ///< SetHistoryAntiLag: while VarianceOn too, the commits also go to TemporalFast
+    gpuart_temporal *TemporalFast = nullptr;  ///< the third history: the radiance again, over a short window
+    gpuart_antilag *AntiLag = nullptr;        ///< made with TemporalFast
+    gpuart_antilag_params AntiLagParams{};    ///< of the third history's window and ReadGuidedPreview's mix (SetHistoryAntiLag)
+    PixelBuffer AntiLagMem;                   ///< the fast blend (16 B), its len (4) and alpha (4) per tile pixel
     gpuart_converge *Converge = nullptr;  ///< made by the first RenderUntil
     unsigned ConvergeBatches = 0, ConvergeTotal = 0;  ///< what Converge has seen since its last reset
     gpuart_adaptive *Adaptive = nullptr;  ///< made by the first RenderAdaptive
@@ -301,6 +316,13 @@ private:
     /// second history, the view's moments packed and blended with theirs in MomentsMem.
     bool BlendHistory(const gpuart_temporal_view &v, const gpuart_temporal_params *tp, bool commit, float *len);
     bool BlendMoments(const gpuart_temporal_view &v, const gpuart_temporal_params *tp, bool commit);
+    /// The third history is kept and mixed in: both switches are on.
+    bool AntiLagActive() const { return AntiLagOn && VarianceOn; }
+    /// TemporalFast, AntiLag and AntiLagMem for the tile, made where missing.
+    bool EnsureAntiLagHandles();
+    /// BlendHistory for the third history, into AntiLagMem with its len: tp's (nullptr: TemporalParams') max_history is capped by
+    /// fast_history.
+    bool BlendFast(const gpuart_temporal_view &v, const gpuart_temporal_params *tp, bool commit);
     /// The device halves of the Read* of the same names: each leaves its frame in device memory, complete, and says where.
     bool StageDenoised(const gpuart_denoise_params *p, const float *&plane);
     bool StagePreview(const gpuart_denoise_params *dn, const gpuart_temporal_params *tp, const float *&plane);
