@@ -120,6 +120,20 @@ def antilag_params(params):
     return _params(AntiLagParams, ANTILAG_DEFAULTS, "anti-lag", params)
 
 
+class EdgesParams(C.Structure):
+    """gpuart_edges_params (include/gpuart_edges.h)."""
+    _fields_ = [("n_sub", C.c_uint32), ("normal_min", C.c_float), ("plane_tol", C.c_float)]
+
+
+EDGES_DEFAULTS = dict(n_sub=8, normal_min=0.95, plane_tol=0.02)
+EDGES_MAX_SUB = 16  # GPUART_EDGES_MAX_SUB
+
+
+def edges_params(params):
+    """None (the library's defaults), an EdgesParams, or a dict of fields that replace the defaults -> EdgesParams or None."""
+    return _params(EdgesParams, EDGES_DEFAULTS, "edge-resolve", params)
+
+
 class DisplayParams(C.Structure):
     """gpuart_display_params (include/gpuart_display.h)."""
     _fields_ = [("gain", C.c_float), ("auto_exposure", C.c_uint32), ("key", C.c_float), ("lo_share", C.c_float), ("hi_share", C.c_float),
@@ -298,6 +312,11 @@ def moments_lib():
 def antilag_lib():
     """libgpuart_antilag.so; raises NativeLibraryMissing if it has not been built (no fallback)."""
     return _image_lib("antilag")
+
+
+def edges_lib():
+    """libgpuart_edges.so; raises NativeLibraryMissing if it has not been built (no fallback)."""
+    return _image_lib("edges")
 
 
 def display_lib():
@@ -894,6 +913,35 @@ class Backend:
             p = prims_out
         return h, p
 
+    def trace_subpixel(self, pixels, uv, pixel_size, user_sphere=None, want_prims=True, out=None, prims_out=None):
+        """gpuart_hip_trace_subpixel: the closest hits of the sub-pixel camera rays of listed tile pixels. pixels: a contiguous (n,) int32
+        tensor on this context's device holding local pixel indices ly * tw + lx (the bits of uint32 indices; any order, repeats
+        allowed); uv: (n_sub, 2) values in [0, 1), (rand1, rand2) of sub-sample k; pixel_size: gpuart_params.pixelSize. -> hits, an
+        (n_sub, n, 8) float32 tensor (column 7 holds the int32 type), and with want_prims the (n_sub, n) int32 ordinals (-1 none, -2 the
+        user sphere), written into `out` / `prims_out` if given. torch's current stream is synchronised before, and the context
+        (gpuart_hip_finish, which also launches collected passes) before returning."""
+        import torch
+        uv = np.ascontiguousarray(uv, np.float32)
+        if uv.ndim != 2 or uv.shape[1] != 2:
+            raise ValueError("uv must be (n_sub, 2): rand1, rand2 of every sub-sample")
+        if pixels.dtype != torch.int32 or pixels.dim() != 1 or not pixels.is_contiguous() or pixels.device.type != "cuda":
+            raise ValueError("pixels must be a contiguous (n,) int32 tensor on the GPU")
+        n, k = pixels.shape[0], uv.shape[0]
+        hits = out if out is not None else torch.empty((k, n, 8), dtype=torch.float32, device=pixels.device)
+        if hits.dtype != torch.float32 or tuple(hits.shape) != (k, n, 8) or not hits.is_contiguous() or hits.device != pixels.device:
+            raise ValueError("out must be a contiguous (n_sub, n, 8) float32 tensor on the pixels' device")
+        prims = None
+        if want_prims:
+            prims = prims_out if prims_out is not None else torch.empty((k, n), dtype=torch.int32, device=pixels.device)
+            if prims.dtype != torch.int32 or tuple(prims.shape) != (k, n) or not prims.is_contiguous() or prims.device != pixels.device:
+                raise ValueError("prims_out must be a contiguous (n_sub, n) int32 tensor on the pixels' device")
+        torch.cuda.current_stream(pixels.device).synchronize()
+        self._chk(self.L.gpuart_hip_trace_subpixel(self.ctx, C.c_void_p(pixels.data_ptr() if n else 0), C.c_size_t(n), _p(uv), C.c_uint32(k),
+                                                   C.c_float(pixel_size), _user_sphere(user_sphere), C.c_void_p(hits.data_ptr() if n else 0),
+                                                   C.c_void_p(prims.data_ptr() if prims is not None and n else 0)))
+        self.finish()
+        return (hits, prims) if want_prims else hits
+
     # test hooks
     def _hook(self, name, ins, nout, *extra):
         ins = [np.ascontiguousarray(a, np.float32) for a in ins]
@@ -1089,6 +1137,16 @@ class Renderer:
         p = antilag_params(params)
         if not self.L.gpuart_renderer_set_history_antilag(self.h, C.c_int(1 if on else 0), C.byref(p) if p is not None else None):
             raise ValueError("anti-lag parameters out of range")
+
+    def set_edge_resolve(self, on=True, params=None):
+        """Renderer::SetEdgeResolve: while on, read_denoised, read_preview, read_guided_preview and read_refined (and read_display of
+        them) end in mark, the sub-pixel rays and resolve (include/gpuart_edges.h); nothing else sees a resolved value. params = None
+        (the defaults), an EdgesParams or a dict of fields that replace the defaults."""
+        p = edges_params(params)
+        if not self.L.gpuart_renderer_set_edge_resolve(self.h, C.c_int(1 if on else 0), C.byref(p) if p is not None else None):
+            raise ValueError("edge-resolve parameters out of range")
+
+    def get_edge_resolve(self): return bool(self.L.gpuart_renderer_get_edge_resolve(self.h))
 
     def read_guided_preview(self, lum_floor=CONVERGE_DEFAULT_FLOOR, refine=None, temporal=None):
         """Renderer::ReadGuidedPreview: the history blended with the accumulator, then filtered by the variance-guided filter with the
@@ -1533,6 +1591,81 @@ class AntiLag(_ImageHandle):
                                                  C.c_uint32(us_flags), C.c_uint32(w), C.c_uint32(h), pp, _p(res), _p(ln),
                                                  _p(al) if al is not None else None))
         return res, ln, al
+
+
+# ---- geometric edges resolved from a sub-pixel G-buffer (include/gpuart_edges.h) ----------------------------------------------
+class EdgesError(RuntimeError):
+    """A gpuart_edges_* call returned an error; `code` is the library's (GPUART_HIP_ERR_*)."""
+    code = None
+
+
+class Edges(_ImageHandle):
+    """A gpuart_edges handle on one device. Device memory only: torch tensors on this handle's device (torch's current stream is
+    synchronised before a call, the handle before it returns)."""
+    NAME, Error = "edges", EdgesError
+
+    @staticmethod
+    def offsets(n_sub):
+        """gpuart_edges_offsets: the (n_sub, 2) sub-pixel offsets (rand1, rand2) of the header's rotated grid, what Backend.trace_subpixel
+        is given."""
+        if not 1 <= n_sub <= EDGES_MAX_SUB:
+            raise ValueError("n_sub must be in 1..%d" % EDGES_MAX_SUB)
+        uv = np.zeros((n_sub, 2), np.float32)
+        if edges_lib().gpuart_edges_offsets(C.c_uint32(n_sub), _p(uv)) != 0:
+            raise EdgesError(edges_lib().gpuart_edges_last_error().decode())
+        return uv
+
+    def _gbuffer(self, hits, prims):
+        import torch
+        dev = torch.device("cuda", self.device)
+        if not type(prims).__module__.startswith("torch") or prims.dtype != torch.int32 or prims.dim() != 2 or not prims.is_contiguous() or \
+                prims.device != dev:
+            raise ValueError("prims must be a contiguous (h, w) int32 tensor on %s" % dev)
+        h, w = prims.shape
+        if not type(hits).__module__.startswith("torch") or hits.dtype != torch.float32 or hits.numel() != h * w * 8 or \
+                not hits.is_contiguous() or hits.device != dev:
+            raise ValueError("hits must be a contiguous (h, w, 8) float32 tensor on %s" % dev)
+        return torch, dev, h, w
+
+    def mark(self, hits, prims, us_flags=0, params=None):
+        """The edge pixels of a G-buffer (Backend.gbuffer's tensors): -> an (n,) int32 tensor of pixel indices y * w + x in ascending
+        order (the bits of uint32 indices), what Backend.trace_subpixel and resolve take. params = None (the defaults), an EdgesParams
+        or a dict of fields that replace the defaults."""
+        p = edges_params(params)
+        torch, dev, h, w = self._gbuffer(hits, prims)
+        lst = torch.empty((h * w,), dtype=torch.int32, device=dev)
+        count = torch.zeros((1,), dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        self._chk(self.L.gpuart_edges_mark(self.h, _dp(hits), _dp(prims), C.c_uint32(us_flags), C.c_uint32(w), C.c_uint32(h),
+                                           C.byref(p) if p is not None else None, _dp(lst), _dp(count)))
+        self.finish()
+        return lst[:int(count.item())].clone()
+
+    def resolve(self, filtered, hits, prims, lst, sub_hits, sub_prims, us_flags=0, params=None, out=None):
+        """The filtered frame (h, w, 4) mended at the listed pixels from their sub-pixel records (Backend.trace_subpixel's (n_sub, n, 8)
+        and (n_sub, n) tensors; n_sub must be params'): -> `out` or a new tensor; out must not be `filtered`."""
+        p = edges_params(params)
+        torch, dev, h, w = self._gbuffer(hits, prims)
+        n_sub = p.n_sub if p is not None else EDGES_DEFAULTS["n_sub"]
+        if filtered.dtype != torch.float32 or tuple(filtered.shape) != (h, w, 4) or not filtered.is_contiguous() or filtered.device != dev:
+            raise ValueError("filtered must be a contiguous (h, w, 4) float32 tensor on %s" % dev)
+        res = out if out is not None else torch.empty_like(filtered)
+        if res.dtype != torch.float32 or tuple(res.shape) != (h, w, 4) or not res.is_contiguous() or res.device != dev:
+            raise ValueError("out must be a contiguous (h, w, 4) float32 tensor on %s" % dev)
+        if lst.dtype != torch.int32 or lst.dim() != 1 or not lst.is_contiguous() or lst.device != dev:
+            raise ValueError("lst must be a contiguous (n,) int32 tensor on %s" % dev)
+        n = lst.shape[0]
+        if sub_hits.dtype != torch.float32 or tuple(sub_hits.shape) != (n_sub, n, 8) or not sub_hits.is_contiguous() or sub_hits.device != dev:
+            raise ValueError("sub_hits must be a contiguous (%d, %d, 8) float32 tensor on %s" % (n_sub, n, dev))
+        if sub_prims.dtype != torch.int32 or tuple(sub_prims.shape) != (n_sub, n) or not sub_prims.is_contiguous() or sub_prims.device != dev:
+            raise ValueError("sub_prims must be a contiguous (%d, %d) int32 tensor on %s" % (n_sub, n, dev))
+        ptr = lambda t: C.c_void_p(t.data_ptr() if n else 0)
+        torch.cuda.current_stream(dev).synchronize()
+        self._chk(self.L.gpuart_edges_resolve(self.h, _dp(filtered), _dp(hits), _dp(prims), C.c_uint32(us_flags), C.c_uint32(w), C.c_uint32(h),
+                                              ptr(lst), C.c_size_t(n), ptr(sub_hits), ptr(sub_prims), C.byref(p) if p is not None else None,
+                                              _dp(res)))
+        self.finish()
+        return res
 
 
 # ---- the convergence estimate (include/gpuart_converge.h) -----------------------------------------------------------------

@@ -194,7 +194,19 @@ GD_FN F3 direct_lighting_pixel(const Scene &sc, const gpuart_params &P, F3 rstar
 // path_sun    : lines 234-245  (after the Sun shadow query)
 // path_finish : lines 247-252  (after the segment loop)
 
-/// First ray of path j of a pixel (path_tracing.glsl:141-170).
+/// The first ray of a path whose two jitter draws are rand1 and rand2 (path_tracing.glsl:144-170: rdirOrtho1/2, PixelSize,
+/// rdir = rstart - CameraPos). gpuart_hip_trace_subpixel chooses the draws itself.
+GD_FN void path_begin_at(float pixelSize, F3 cameraPos, float rand1, float rand2, F3 rstart0, F3 rdir0, F3 &rstart, F3 &rdir) {
+    F3 o1;
+    if (fabsf(rdir0.x) > 1.0e-5f || fabsf(rdir0.y) > 1.0e-5f) o1 = normalize3(f3(rdir0.y, -rdir0.x, 0));
+    else o1 = normalize3(f3(0, -rdir0.z, rdir0.y));
+    F3 o2 = cross3(normalize3(rdir0), o1);
+    rstart = (rstart0 + ((rand1 - 0.5f) * o1) * pixelSize) + ((rand2 - 0.5f) * o2) * pixelSize;
+    rdir = rstart - cameraPos;
+}
+
+/// First ray of path j of a pixel (path_tracing.glsl:141-170). (Written out rather than calling path_begin_at: the call changed the
+/// instruction order of k_gen and k_run, which are held to what they were.)
 GD_FN void path_begin(const gpuart_params &P, float4 seed, int j, F3 rstart0, F3 rdir0, F3 &rstart, F3 &rdir) {
     F3 o1;
     if (fabsf(rdir0.x) > 1.0e-5f || fabsf(rdir0.y) > 1.0e-5f) o1 = normalize3(f3(rdir0.y, -rdir0.x, 0));

@@ -1228,6 +1228,9 @@ static int query_check(gpuart_hip_ctx *c, size_t n, const void *src, const gpuar
     return 0;
 }
 
+/// d_query_cursor's words: k_ray_query's chunk cursor, then gpuart_hip_trace_subpixel's verdict on its list (word 1) and its draws (from word 16)
+#define GD_QUERY_WORDS (16 + 2 * GPUART_HIP_MAX_SUBPIXEL)
+
 static RayQuery make_query(size_t n, uint32_t flags, const float us[4]) {
     RayQuery q{};
     q.n = (uint32_t)n;
@@ -1241,7 +1244,7 @@ static RayQuery make_query(size_t n, uint32_t flags, const float us[4]) {
 /// primary stream, which nothing on the pass lanes' streams uses: a query may run beside pipeline runs in flight. Collected passes are
 /// not flushed (a query neither observes nor changes what they render), and neither the work counters nor the render timings see it.
 static int launch_ray_query(gpuart_hip_ctx *c, const RayQuery &q, int source) {
-    if (!c->d_query_cursor) HIP_TRY(hipMalloc(&c->d_query_cursor, 64));
+    if (!c->d_query_cursor) HIP_TRY(hipMalloc(&c->d_query_cursor, GD_QUERY_WORDS * sizeof(uint32_t)));
     HIP_TRY(hipMemsetAsync(c->d_query_cursor, 0, sizeof(uint32_t), c->stream));
     // chunks as the direct-lighting frame takes them; a small batch gets the waves it can fill
     const TraceTuning tune = direct_tuning(c, q.n);
@@ -1347,6 +1350,56 @@ int gpuart_hip_gbuffer(gpuart_hip_ctx *c, const float us[4], gpuart_ray_hit *hit
     q.hits = (float4 *)hits;
     q.prims = prims;
     return launch_ray_query(c, q, RQ_PIXELS);
+}
+
+int gpuart_hip_trace_subpixel(gpuart_hip_ctx *c, const uint32_t *pixels, size_t n, const float *uv, uint32_t n_sub, float pixelSize,
+                              const float us[4], gpuart_ray_hit *hits, int32_t *prims) {
+    if (!c) return fail(GPUART_HIP_ERR_ARG, "ctx == NULL");
+    if (!c->have_scene) return fail(GPUART_HIP_ERR_ARG, "subpixel: no scene uploaded");
+    if (!c->frame.W) return fail(GPUART_HIP_ERR_ARG, "subpixel: no frame size set");
+    if (!c->have_camera) return fail(GPUART_HIP_ERR_ARG, "subpixel: no camera set");
+    if (n_sub < 1 || n_sub > GPUART_HIP_MAX_SUBPIXEL)
+        return fail(GPUART_HIP_ERR_ARG, "subpixel: n_sub = " + std::to_string(n_sub) + " is not in 1.." + std::to_string(GPUART_HIP_MAX_SUBPIXEL));
+    if (!uv) return fail(GPUART_HIP_ERR_ARG, "subpixel: uv is NULL");
+    for (uint32_t k = 0; k < 2 * n_sub; k++)
+        if (!(uv[k] >= 0.0f && uv[k] < 1.0f)) return fail(GPUART_HIP_ERR_ARG, "subpixel: uv[" + std::to_string(k) + "] is not in [0, 1)");
+    if (!(pixelSize >= 0.0f) || pixelSize - pixelSize != 0.0f) return fail(GPUART_HIP_ERR_ARG, "subpixel: pixelSize must be finite and >= 0");
+    if (n > GPUART_HIP_MAX_RAYS / n_sub)
+        return fail(GPUART_HIP_ERR_ARG, "subpixel: n * n_sub = " + std::to_string(n) + " * " + std::to_string(n_sub) + " exceeds GPUART_HIP_MAX_RAYS");
+    if (n == 0) return 0;
+    if (!pixels || !hits) return fail(GPUART_HIP_ERR_ARG, "subpixel: pixels or hits is NULL");
+    if ((uintptr_t)pixels % 4 || (uintptr_t)hits % 16 || (uintptr_t)prims % 4)
+        return fail(GPUART_HIP_ERR_ARG, "subpixel: misaligned pointer (hits needs 16 bytes, pixels and prims 4)");
+    if (c->plan.tile_pixels == 0) return fail(GPUART_HIP_ERR_ARG, "subpixel: pixel index outside the tile (an empty share has no pixel)");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t total = n * n_sub;
+    if (int r = ensure_scratch(c, total * 32)) return r;
+    if (!c->d_query_cursor) HIP_TRY(hipMalloc(&c->d_query_cursor, GD_QUERY_WORDS * sizeof(uint32_t)));
+    uint32_t *d_bad = c->d_query_cursor + 1;         // (word 0 is k_ray_query's cursor)
+    float *d_uv = (float *)(c->d_query_cursor + 16);
+    HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(uint32_t), c->stream));
+    HIP_TRY(hipMemcpyAsync(d_uv, uv, 2 * n_sub * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    // two launches of the query kernel: the first makes the rays (kernels_query.h: sub_n != 0), the second walks them
+    RayQuery g = make_query(total, 0, nullptr);
+    g.sub_pixels = pixels;
+    g.sub_uv = d_uv;
+    g.sub_rays = (float4 *)c->d_scratch;
+    g.sub_bad = d_bad;
+    g.sub_n = (uint32_t)n;
+    g.sub_pixel_size = pixelSize;
+    if (int r = launch_ray_query(c, g, RQ_RAYS)) return r;
+    // the list lives in device memory: the generation range-checks it, and the call waits for that verdict (not for the walk) so that a
+    // bad index is an argument error with nothing written, like everywhere else
+    uint32_t bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (bad) return fail(GPUART_HIP_ERR_ARG, "subpixel: a pixel index lies outside the " + std::to_string(c->frame.tw) + " x " +
+                                                 std::to_string(c->frame.th) + " tile");
+    RayQuery q = make_query(total, 0, us);
+    q.rays = (const float4 *)c->d_scratch;
+    q.hits = (float4 *)hits;
+    q.prims = prims;
+    return launch_ray_query(c, q, RQ_RAYS);
 }
 
 // ---- shares and the multi-GPU gather (gather.h) ---------------------------------------------------------------------

@@ -18,6 +18,15 @@ struct RayQuery {
     uint32_t occlusion;   ///< 1: is 0 < closest-hit pos < tmax? (RQ_RAYS only)
     uint32_t use_us;      ///< 1: the user sphere `us` takes part, as in CheckIntersectionInclUserSphere
     float us[4];
+    // RQ_RAYS with sub_n != 0 (gpuart_hip_trace_subpixel): the launch walks nothing; it is the streaming pass that MAKES the n rays a
+    // second, ordinary launch walks. Ray k * sub_n + e is the first segment path_begin makes for tile pixel sub_pixels[e] with the draws
+    // sub_uv[2k], sub_uv[2k + 1], stored into sub_rays in the layout of `rays`
+    const uint32_t *sub_pixels;  ///< local pixel indices ly * tw + lx
+    const float *sub_uv;         ///< device memory: (rand1, rand2) per sub-sample
+    float4 *sub_rays;
+    uint32_t *sub_bad;           ///< set to 1 if an index lies outside the tile (its ray is pixel 0's: nothing is read out of bounds)
+    uint32_t sub_n;
+    float sub_pixel_size;
 };
 
 /// The record of query `i`: pos, point, normal, type and ordinal (the writes of replicas in a thin group are left to the first).
@@ -38,6 +47,24 @@ __global__ void __launch_bounds__(BLOCK, GD_DIRECT_WAVES) k_ray_query(Scene sc, 
                                                                   TraceTuning tune) {
     __shared__ uint2 ring_a[GD_RING * BLOCK];
     __shared__ float ring_b[GD_RING * BLOCK];
+    if (SOURCE == RQ_RAYS && q.sub_n) {  // (launch-uniform) the generation pass of gpuart_hip_trace_subpixel: camera_ray and path_begin_at,
+                                         // the very functions k_gen calls, one ray per thread and stride; no lane holds a walk here
+        for (uint32_t idx = blockIdx.x * BLOCK + threadIdx.x; idx < q.n; idx += gridDim.x * BLOCK) {
+            const uint32_t k = idx / q.sub_n, e = idx - k * q.sub_n;
+            uint32_t p = q.sub_pixels[e];
+            if (p >= (unsigned long long)f.tw * f.th) {
+                *q.sub_bad = 1u;
+                p = 0;
+            }
+            const uint32_t ly = p / f.tw, lx = p - ly * f.tw;
+            F3 rs0, rd0, rs, rd;
+            camera_ray(f, f.x0 + lx, frame_y(f, ly), rs0, rd0);
+            path_begin_at(q.sub_pixel_size, f3(f.cam_pos[0], f.cam_pos[1], f.cam_pos[2]), q.sub_uv[2 * k], q.sub_uv[2 * k + 1], rs0, rd0, rs, rd);
+            q.sub_rays[2 * (size_t)idx] = make_float4(rs.x, rs.y, rs.z, __builtin_inff());
+            q.sub_rays[2 * (size_t)idx + 1] = make_float4(rd.x, rd.y, rd.z, 0.0f);
+        }
+        return;
+    }
     TravStack st = make_stack(ring_a, ring_b, spill, gridDim.x * BLOCK);
     constexpr bool THIN_OK = GD_TRACE_THIN > 1 && GD_BOXES_OF(TYPES) == GD_BOXES_FAST;
     const bool occl = SOURCE == RQ_RAYS && q.occlusion != 0;  // wave-uniform

@@ -291,6 +291,10 @@ int gpuart_renderer_set_history_variance(gpuart_renderer *r, int on, const gpuar
 int gpuart_renderer_set_history_antilag(gpuart_renderer *r, int on, const gpuart_antilag_params *p) {
     return r->impl.SetHistoryAntiLag(on != 0, p) ? 1 : 0;
 }
+int gpuart_renderer_set_edge_resolve(gpuart_renderer *r, int on, const gpuart_edges_params *p) {
+    return r->impl.SetEdgeResolve(on != 0, p) ? 1 : 0;
+}
+int gpuart_renderer_get_edge_resolve(gpuart_renderer *r) { return r->impl.GetEdgeResolve() ? 1 : 0; }
 int gpuart_renderer_read_guided_preview(gpuart_renderer *r, float *rgba, float lumFloor, const gpuart_refine_params *rf,
                                         const gpuart_temporal_params *tp) {
     return r->impl.ReadGuidedPreview(rgba, lumFloor, rf, tp) ? 1 : 0;

@@ -11,6 +11,7 @@
 #include "gpuart_converge.h"
 #include "gpuart_denoise.h"
 #include "gpuart_display.h"
+#include "gpuart_edges.h"
 #include "gpuart_hip.h"
 #include "gpuart_moments.h"
 #include "gpuart_refine.h"
@@ -117,6 +118,11 @@ int gpuart_renderer_set_history_variance(gpuart_renderer *r, int on, const gpuar
  * changed (include/gpuart_antilag.h); toggling drops the temporal history. p = NULL: the defaults. 1 on success, 0 for parameters out
  * of range. */
 int gpuart_renderer_set_history_antilag(gpuart_renderer *r, int on, const gpuart_antilag_params *p);
+/* Renderer::SetEdgeResolve: the filtered reads (denoised, preview, guided preview, refined, and the display of them) end in mark,
+ * sub-pixel rays and resolve (include/gpuart_edges.h). p = NULL: the defaults. 1 on success, 0 for parameters out of range.
+ * gpuart_renderer_get_edge_resolve: 1 while on. */
+int gpuart_renderer_set_edge_resolve(gpuart_renderer *r, int on, const gpuart_edges_params *p);
+int gpuart_renderer_get_edge_resolve(gpuart_renderer *r);
 /* Renderer::ReadGuidedPreview: the history blend filtered by gpuart_refine_run with the error map of the history's measured variance.
  * rf, tp = NULL: the defaults / what gpuart_renderer_set_temporal_history was given. 1 on success; 0 while the variance or the
  * history is off, before the view's first path, or on error. */

@@ -26,7 +26,7 @@ static void usage() {
                  "                  [--camera px,py,pz] [--sun az,alt[,off]] [--user-sphere x,y,z,r,em[,specular[,fuzzy]]]\n"
                  "                  [--device D] [--gpus N] [--resume ck] [--checkpoint ck] [--pfm out.pfm] [--ppm out.ppm] [--nearest-first]\n"
                  "                  [--adaptive T [--adaptive-min N] [--until-batch N] [--until-floor F] [--samples-pfm out.pfm] [--refine]]\n"
-                 "                  [--denoise] [--until T [--until-share S] [--until-floor F] [--until-batch N] [--error-pfm out.pfm] [--refine]]\n"
+                 "                  [--denoise] [--edge-resolve] [--until T [--until-share S] [--until-floor F] [--until-batch N] [--error-pfm out.pfm] [--refine]]\n"
                  "                  [--display out.ppm [--tonemap clamp|reinhard|aces] [--white W] [--exposure-ev E] [--auto-exposure] [--key K]\n"
                  "                   [--srgb] [--dither]]\n"
                  "  --until T: render until the relative standard error of every pixel's luminance is at most T (Renderer::RenderUntil; path\n"
@@ -47,6 +47,8 @@ static void usage() {
                  "             --auto-exposure: adapt the gain to the frame's histogram, --key K: the luminance its log-average is brought to\n"
                  "             (default 0.18); --srgb: the sRGB transfer function (default linear); --dither: 8x8 ordered dither. One GPU only\n"
                  "  --denoise: write the denoised preview of the frame (Renderer::ReadDenoised; path tracing on one GPU)\n"
+                 "  --edge-resolve: with --denoise or --refine, resolve geometric edges in the filtered frame from a sub-pixel G-buffer\n"
+                 "             (Renderer::SetEdgeResolve, include/gpuart_edges.h, its defaults)\n"
                  "  --nearest-first: opt in to the nearer-child-first BVH walk (~10 % faster; soak-verified, not proven to be the reference's image)\n"
                  "  --gpus N: path tracing of ONE frame on devices D..D+N-1 (8-row bands dealt round-robin, gathered over RCCL)\n";
 }
@@ -66,7 +68,7 @@ int main(int argc, char **argv) {
     std::string scene = "box", mode = "pt", pfm, ppm, resume, checkpoint;
     unsigned W = 640, H = 480, spp = 16, perPass = 1, maxSeg = 5, device = 0, gpus = 1;
     long seed = -1;
-    bool nearestFirst = false, denoise = false, refine = false;
+    bool nearestFirst = false, denoise = false, refine = false, edgeResolve = false;
     std::string errorPfm;
     float until = -1, untilShare = 0, untilFloor = 1.0f / 256;
     unsigned untilBatch = GPUART_CONVERGE_DEFAULT_BATCH;
@@ -107,6 +109,7 @@ int main(int argc, char **argv) {
         else if (a == "--nearest-first") nearestFirst = true;
         else if (a == "--denoise") denoise = true;
         else if (a == "--refine") refine = true;
+        else if (a == "--edge-resolve") edgeResolve = true;
         else if (a == "--until") { until = strtof(need("--until"), nullptr); haveUntil = true; }
         else if (a == "--until-share") untilShare = strtof(need("--until-share"), nullptr);
         else if (a == "--until-floor") untilFloor = strtof(need("--until-floor"), nullptr);
@@ -149,6 +152,10 @@ int main(int argc, char **argv) {
     }
     if (refine && !haveUntil && !haveAdaptive) {
         std::cerr << "gpuart_cli: --refine needs --until: it filters with the error estimate of that render\n";
+        return 2;
+    }
+    if (edgeResolve && !denoise && !refine) {
+        std::cerr << "gpuart_cli: --edge-resolve mends a filtered frame: give --denoise or --refine\n";
         return 2;
     }
     if (refine && denoise) {
@@ -207,6 +214,7 @@ int main(int argc, char **argv) {
         if (gpus > 1 && !r.SetShare((int)g, (int)gpus)) return 1;
     }
     gpuart::Renderer &r = *rs[0];
+    if (edgeResolve && !r.SetEdgeResolve(true)) return 1;
     if (nTile == 4 && !r.SetTile((unsigned)tile[0], (unsigned)tile[1], (unsigned)tile[2], (unsigned)tile[3])) return 1;
     const unsigned tw = gpus > 1 ? W : r.GetTileWidth(), th = gpus > 1 ? H : r.GetTileHeight();
 

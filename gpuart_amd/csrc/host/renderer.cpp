@@ -66,6 +66,7 @@ Renderer::Renderer(unsigned viewportWidth, unsigned viewportHeight, const Camera
     gpuart_temporal_defaults(&TemporalParams);
     gpuart_moments_defaults(&MomentsParams);
     gpuart_antilag_defaults(&AntiLagParams);
+    gpuart_edges_defaults(&EdgeParams);
 
     if (!Check(gpuart_hip_create(device, &Backend), "creating the device back end")) return;
     if (viewportWidth == 0 || viewportHeight == 0) {
@@ -81,6 +82,9 @@ Renderer::~Renderer() {
     DisplayMem.Release();
     if (Refine) gpuart_refine_destroy(Refine);
     ErrorMem.Release();
+    if (Edges) gpuart_edges_destroy(Edges);
+    EdgeSubMem.Release();
+    EdgeMem.Release();
     if (Adaptive) gpuart_adaptive_destroy(Adaptive);
     BlockPathsMem.Release();
     if (Converge) gpuart_converge_destroy(Converge);
@@ -410,6 +414,7 @@ const Lib<gpuart_antilag> AL{gpuart_antilag_create, gpuart_antilag_finish, gpuar
 const Lib<gpuart_converge> CV{gpuart_converge_create, gpuart_converge_finish, gpuart_converge_last_error, "creating the convergence estimator"};
 const Lib<gpuart_adaptive> AD{gpuart_adaptive_create, gpuart_adaptive_finish, gpuart_adaptive_last_error, "creating the adaptive estimator"};
 const Lib<gpuart_refine> RF{gpuart_refine_create, gpuart_refine_finish, gpuart_refine_last_error, "creating the variance-guided filter"};
+const Lib<gpuart_edges> ED{gpuart_edges_create, gpuart_edges_finish, gpuart_edges_last_error, "creating the edge resolve's handle"};
 const Lib<gpuart_display> DP{gpuart_display_create, gpuart_display_finish, gpuart_display_last_error, "creating the display stage"};
 bool finite(float x) { return x - x == 0.0f; }
 bool checkHip(hipError_t e, const char *what) {
@@ -477,6 +482,7 @@ bool Renderer::StageView() {
     const float us[4] = {UserSphere.pos.x, UserSphere.pos.y, UserSphere.pos.z, UserSphere.radius};
     if (!GBufferValid || memcmp(us, GBufferSphere, sizeof us) != 0) {
         GBufferValid = false;
+        EdgeListValid = false;  // (the edge list and the sub-pixel records are this G-buffer's)
         if (!Check(gpuart_hip_gbuffer(Backend, us, b.hits, b.prims), "building the G-buffer")) return false;
         memcpy(GBufferSphere, us, sizeof us);
         GBufferValid = true;
@@ -548,7 +554,65 @@ bool Renderer::StageDenoised(const gpuart_denoise_params *p, const float *&plane
     if (!IsOK || !Ensure(Denoiser, DN) || !StageView()) return false;
     const ViewBuffers b(DenoiseMem.mem, (size_t)Tile.w * Tile.h);
     plane = b.filtered;
-    return Run(gpuart_denoise_run(Denoiser, b.radiance, b.hits, b.prims, UserSphere.flags, Tile.w, Tile.h, p, b.filtered), Denoiser, DN, "denoising");
+    return Run(gpuart_denoise_run(Denoiser, b.radiance, b.hits, b.prims, UserSphere.flags, Tile.w, Tile.h, p, b.filtered), Denoiser, DN, "denoising") &&
+           ResolveEdges(plane);
+}
+
+// ---- geometric edges from a sub-pixel G-buffer (include/gpuart_edges.h) ---------------------------------------------------
+bool Renderer::SetEdgeResolve(bool on, const gpuart_edges_params *p) {
+    gpuart_edges_params v;
+    if (p) {
+        // the ranges gpuart_edges_mark and gpuart_hip_trace_subpixel accept
+        if (p->n_sub < 1 || p->n_sub > GPUART_EDGES_MAX_SUB || !(p->normal_min >= -1) || !(p->normal_min <= 1) || !finite(p->plane_tol) ||
+            !(p->plane_tol >= 0)) {
+            std::cerr << "Renderer: edge-resolve parameters out of range." << std::endl;
+            return false;
+        }
+        v = *p;
+    } else {
+        gpuart_edges_defaults(&v);
+    }
+    if (memcmp(&v, &EdgeParams, sizeof v) != 0) EdgeListValid = false;
+    EdgeParams = v;
+    EdgeOn = on;
+    return true;
+}
+
+bool Renderer::ResolveEdges(const float *&plane) {
+    if (!EdgeOn) return true;
+    if (!checkHip(hipSetDevice(Device), "hipSetDevice") || !Ensure(Edges, ED)) return false;
+    const size_t n = (size_t)Tile.w * Tile.h;
+    if (n + 1 != EdgeMem.count) EdgeListValid = false;
+    if (!EdgeMem.Fit(n + 1, 16 + 4, "allocating the edge resolve's buffers")) return false;
+    const ViewBuffers b(DenoiseMem.mem, n);
+    float *out = (float *)EdgeMem.mem;
+    uint32_t *list = (uint32_t *)((char *)EdgeMem.mem + n * 16), *count = list + n;
+    const size_t subs = (size_t)EdgeCount * EdgeParams.n_sub;
+    if (!EdgeListValid || EdgeFlags != UserSphere.flags) {
+        EdgeListValid = false;
+        if (!Run(gpuart_edges_mark(Edges, b.hits, b.prims, UserSphere.flags, Tile.w, Tile.h, &EdgeParams, list, count), Edges, ED, "marking the edge pixels") ||
+            !checkHip(hipMemcpy(&EdgeCount, count, sizeof EdgeCount, hipMemcpyDeviceToHost), "reading the number of edge pixels"))
+            return false;
+        const size_t m = (size_t)EdgeCount * EdgeParams.n_sub;
+        if (!EdgeSubMem.Fit(m ? m : 1, 32 + 4, "allocating the sub-pixel records")) return false;
+        const float pixelSize = ComputePixelSize(CurrentCamera, Viewport.height);
+        float uv[2 * GPUART_EDGES_MAX_SUB];
+        if (!Check(gpuart_edges_offsets(EdgeParams.n_sub, uv), "making the sub-pixel offsets", gpuart_edges_last_error)) return false;
+        if (!Check(gpuart_hip_trace_subpixel(Backend, list, EdgeCount, uv, EdgeParams.n_sub, pixelSize, GBufferSphere,
+                                             (gpuart_ray_hit *)EdgeSubMem.mem, (int32_t *)((char *)EdgeSubMem.mem + m * 32)),
+                   "tracing the sub-pixel rays") ||
+            !Check(gpuart_hip_finish(Backend), "waiting for the device"))
+            return false;
+        EdgeFlags = UserSphere.flags;
+        EdgeListValid = true;
+        return ResolveEdges(plane);  // (with the cache valid: once)
+    }
+    if (!Run(gpuart_edges_resolve(Edges, plane, b.hits, b.prims, UserSphere.flags, Tile.w, Tile.h, list, EdgeCount,
+                                  (const gpuart_ray_hit *)EdgeSubMem.mem, (const int32_t *)((char *)EdgeSubMem.mem + subs * 32), &EdgeParams, out),
+             Edges, ED, "resolving the edges"))
+        return false;
+    plane = out;
+    return true;
 }
 
 // ---- temporal history (include/gpuart_temporal.h) ---------------------------------------------------------------------
@@ -696,7 +760,8 @@ bool Renderer::StageGuidedPreview(float lumFloor, const gpuart_refine_params *rf
     if (!Run(gpuart_moments_error(Moments, b.filtered, mb.len, mb.blend, b.hits, b.prims, UserSphere.flags, lumFloor, Tile.w, Tile.h, &MomentsParams, mb.e),
              Moments, MO, "measuring the history's variance")) return false;
     plane = b.filtered;  // (the filter may run in place: include/gpuart_refine.h)
-    return Run(gpuart_refine_run(Refine, b.filtered, b.hits, b.prims, UserSphere.flags, mb.e, lumFloor, Tile.w, Tile.h, rf, b.filtered), Refine, RF, "filtering");
+    return Run(gpuart_refine_run(Refine, b.filtered, b.hits, b.prims, UserSphere.flags, mb.e, lumFloor, Tile.w, Tile.h, rf, b.filtered), Refine, RF, "filtering") &&
+           ResolveEdges(plane);
 }
 
 bool Renderer::StagePreview(const gpuart_denoise_params *dn, const gpuart_temporal_params *tp, const float *&plane) {
@@ -705,7 +770,8 @@ bool Renderer::StagePreview(const gpuart_denoise_params *dn, const gpuart_tempor
     if (!IsOK || !Ensure(Denoiser, DN) || !StageView() || !MakeTemporalView(v) || !BlendHistory(v, tp, false, nullptr)) return false;
     const ViewBuffers b(DenoiseMem.mem, (size_t)Tile.w * Tile.h);
     plane = b.filtered;  // (the filter may run in place: include/gpuart_denoise.h)
-    return Run(gpuart_denoise_run(Denoiser, b.filtered, b.hits, b.prims, UserSphere.flags, Tile.w, Tile.h, dn, b.filtered), Denoiser, DN, "denoising");
+    return Run(gpuart_denoise_run(Denoiser, b.filtered, b.hits, b.prims, UserSphere.flags, Tile.w, Tile.h, dn, b.filtered), Denoiser, DN, "denoising") &&
+           ResolveEdges(plane);
 }
 
 // ---- the batch loop of RenderUntil and RenderAdaptive ---------------------------------------------------------------------------
@@ -851,7 +917,8 @@ bool Renderer::StageRefined(float lumFloor, const gpuart_refine_params *p, const
     if (!IsOK || LastEstimate() == NONE || !Ensure(Refine, RF) || !StageView() || !StageErrorMap(lumFloor, map)) return false;
     const ViewBuffers b(DenoiseMem.mem, (size_t)Tile.w * Tile.h);
     plane = b.filtered;
-    return Run(gpuart_refine_run(Refine, b.radiance, b.hits, b.prims, UserSphere.flags, map, lumFloor, Tile.w, Tile.h, p, b.filtered), Refine, RF, "filtering");
+    return Run(gpuart_refine_run(Refine, b.radiance, b.hits, b.prims, UserSphere.flags, map, lumFloor, Tile.w, Tile.h, p, b.filtered), Refine, RF, "filtering") &&
+           ResolveEdges(plane);
 }
 
 // ---- the display stage (include/gpuart_display.h) ---------------------------------------------------------------------------

@@ -8,7 +8,7 @@
 // MAX_PATH_SEGMENTS / the RNG seed / the viewport fixed at compile time):
 //   ReadDirectLighting, ReadRadiance, Finish, SetMaxPathSegments, SetMinWeight, SetSeed,
 //   SetTile, GetBackend, ComputeScreenBasis, GetNumPathsRendered, ReadDenoised, SetTemporalHistory, ReadPreview, RenderUntil,
-//   ReadErrorMap, ReadRefined, SetHistoryVariance, SetHistoryAntiLag, ReadGuidedPreview, ReadDisplay.
+//   ReadErrorMap, ReadRefined, SetHistoryVariance, SetHistoryAntiLag, ReadGuidedPreview, ReadDisplay, SetEdgeResolve.
 #ifndef GPUART_RENDERER_H
 #define GPUART_RENDERER_H
 
@@ -23,6 +23,7 @@
 #include "gpuart_converge.h"
 #include "gpuart_denoise.h"
 #include "gpuart_display.h"
+#include "gpuart_edges.h"
 #include "gpuart_hip.h"
 #include "gpuart_moments.h"
 #include "gpuart_refine.h"
@@ -132,6 +133,16 @@ public:
     /// have seen the same commits. p = nullptr: the library's defaults. False for parameters out of range (nothing changes).
     bool SetHistoryAntiLag(bool on, const gpuart_antilag_params *p = nullptr);
     bool GetHistoryAntiLag() const { return AntiLagOn; }
+    /// Resolves geometric edges in the filtered frames from a sub-pixel G-buffer (include/gpuart_edges.h); off by default. While it is
+    /// on, ReadDenoised, ReadPreview, ReadGuidedPreview and ReadRefined — and ReadDisplay of them — end in gpuart_edges_mark on the
+    /// view's G-buffer, gpuart_hip_trace_subpixel for the listed pixels with the header's offset table, and gpuart_edges_resolve of the
+    /// filtered plane into a plane of its own. The list and the sub-pixel records are cached with the G-buffer: they are made again when
+    /// it is (a new camera, user sphere, tile or scene), when the user sphere's flags change, and when this call changes anything. The
+    /// accumulator, the passes that follow, the counters, the estimates, the temporal commits and the moments never see a resolved
+    /// value. p = nullptr: the library's defaults. False for parameters out of range (nothing changes). With the switch off every
+    /// read launches what it launched before the switch existed.
+    bool SetEdgeResolve(bool on, const gpuart_edges_params *p = nullptr);
+    bool GetEdgeResolve() const { return EdgeOn; }
     /// The preview guided by the history's measured variance: the radiance and the packed moments of the current accumulator are blended
     /// with their histories (gpuart_temporal_accumulate without commit; tp = nullptr: what SetTemporalHistory was given),
     /// gpuart_moments_error turns the two blends into an error map for lumFloor, and gpuart_refine_run (rf; nullptr: its defaults)
@@ -269,6 +280,13 @@ private:
     gpuart_antilag *AntiLag = nullptr;        ///< made with TemporalFast
     gpuart_antilag_params AntiLagParams{};    ///< of the third history's window and ReadGuidedPreview's mix (SetHistoryAntiLag)
     PixelBuffer AntiLagMem;                   ///< the fast blend (16 B), its len (4) and alpha (4) per tile pixel
+    bool EdgeOn = false;                      ///< SetEdgeResolve
+    gpuart_edges *Edges = nullptr;            ///< made by the first read while EdgeOn
+    gpuart_edges_params EdgeParams{};         ///< of mark, the sub-pixel rays and resolve (SetEdgeResolve)
+    PixelBuffer EdgeMem;                      ///< the resolved plane (16 B) and the list (4) per tile pixel, then the count: Fit(n + 1, 20)
+    PixelBuffer EdgeSubMem;                   ///< a record (32 B) and an ordinal (4) per listed pixel and sub-sample
+    bool EdgeListValid = false;               ///< EdgeMem's list and EdgeSubMem are those of the cached G-buffer for EdgeFlags
+    uint32_t EdgeFlags = 0, EdgeCount = 0;
     gpuart_converge *Converge = nullptr;  ///< made by the first RenderUntil
     unsigned ConvergeBatches = 0, ConvergeTotal = 0;  ///< what Converge has seen since its last reset
     gpuart_adaptive *Adaptive = nullptr;  ///< made by the first RenderAdaptive
@@ -328,6 +346,8 @@ private:
     bool StagePreview(const gpuart_denoise_params *dn, const gpuart_temporal_params *tp, const float *&plane);
     bool StageGuidedPreview(float lumFloor, const gpuart_refine_params *rf, const gpuart_temporal_params *tp, const float *&plane);
     bool StageRefined(float lumFloor, const gpuart_refine_params *p, const float *&plane);
+    /// Where EdgeOn, the filtered frame `plane` (of the view StageView staged) resolved into EdgeMem's plane, which `plane` then names.
+    bool ResolveEdges(const float *&plane);
     /// The one table of the frames a read can ask for: the Stage* that `source` names with the parameters it takes, or for RADIANCE and
     /// DIRECT the export into `own` (tile-sized device memory; may be null for the others). False for a source that does not exist.
     bool StageSource(gpuart_display_source source, float lumFloor, const gpuart_denoise_params *dn, const gpuart_refine_params *rf,

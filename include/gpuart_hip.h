@@ -313,6 +313,22 @@ int gpuart_hip_pick(gpuart_hip_ctx *ctx, const uint32_t *xy, size_t n, const flo
  * change. An empty share writes nothing. GPUART_HIP_ERR_ARG without a scene, a frame size or a camera, and for a NULL or misaligned
  * pointer. include/gpuart_denoise.h filters a frame with it. */
 int gpuart_hip_gbuffer(gpuart_hip_ctx *ctx, const float userSphere[4], gpuart_ray_hit *hits, int32_t *prims);
+/* Sub-pixel camera rays of listed tile pixels: a G-buffer below the pixel grid (include/gpuart_edges.h resolves geometric edges with
+ * it). pixels: device memory, n local pixel indices ly * tw + lx in the order of gpuart_hip_gbuffer, in any order, repeats allowed. uv:
+ * host memory, 2 * n_sub values in [0, 1). Ray (i, k) is the first segment gpuart_hip_pt_pass traces for pixel pixels[i] when its two
+ * jitter draws are rand1 = uv[2k] and rand2 = uv[2k + 1] (reference shaders/path_tracing.glsl:144-170: rdirOrtho1/2, PixelSize,
+ * rdir = rstart - CameraPos), with PixelSize = pixelSize (gpuart_params.pixelSize: the context keeps none between passes) and CameraPos =
+ * the pos of gpuart_hip_set_camera. It is answered as gpuart_hip_trace_rays answers a closest-hit query — the reference's order, the
+ * user sphere taking part, ordinals -1 / -2 — into hits[k * n + i] and prims[k * n + i] (prims may be NULL): n * n_sub records, device
+ * memory, hits 16-byte aligned, pixels and prims 4-byte aligned. A generation pass writes the rays into the context's scratch
+ * (32 bytes per ray) and the persistent query kernel walks them (two launches of that kernel), on the context's stream; collected passes are not flushed, counters
+ * and timings do not change. The list is range-checked on the device, so the call waits for the generation pass — not for the walk:
+ * gpuart_hip_finish before the results are used. GPUART_HIP_ERR_ARG, with nothing written, without a scene, a frame size or a camera,
+ * for n_sub outside 1..GPUART_HIP_MAX_SUBPIXEL, a uv outside [0, 1), a pixelSize that is negative or not finite, n * n_sub >
+ * GPUART_HIP_MAX_RAYS, NULL or misaligned pointers, or an index >= tw * th; n = 0 does nothing. */
+#define GPUART_HIP_MAX_SUBPIXEL 16u
+int gpuart_hip_trace_subpixel(gpuart_hip_ctx *ctx, const uint32_t *pixels, size_t n, const float *uv, uint32_t n_sub, float pixelSize,
+                              const float userSphere[4], gpuart_ray_hit *hits, int32_t *prims);
 
 /* The test hooks (gpuart_hip_test_*: the run planner, the uploader's verdicts, the share-table check, birth orders, a stream stall, the
  * device functions one by one) are NOT part of this interface: include/gpuart_hip_test.h declares them, and only a library built with
