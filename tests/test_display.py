@@ -282,25 +282,137 @@ def run_entry(handle, entry, img, params, origin=ORIGIN):
 
 
 SIZES = [(1, 1), (63, 3), (64, 4), (65, 5), (257, 9), (65536, 1), (1, 65536)]
+# past the histogram's capped grid (256 blocks of 1024 threads, a stride of 262 144 pixels): the cap alone, the 4-way unrolled body for
+# some threads only (the others take three tail turns), for every thread once with a tail turn for some or for all, and twice;
+# test_sizes_reach_the_histograms_loops has the counts
+BIG_SIZES = [(513, 512), (887, 887), (1049, 1000), (1283, 1025), (1537, 1537)]
+UNCOUNTABLE = (np.nan, np.inf, -1.0, 0.0)
+
+
+def uncountable_pixels(n, stride=262144):
+    """The flat indices at which a frame of n pixels (past one stride) gets a pixel the histogram skips: eight in the first 1024, eight
+    around every multiple of the stride and eight in the last 1024, so that both of the histogram's loops meet them at both ends of
+    the grid."""
+    idx = [0, 1, 2, 3, 511, 1020, 1022, 1023]
+    for m in range(stride, n, stride):
+        idx += list(range(m - 4, m + 4))
+    idx += [n - 1024, n - 1023, n - 1022, n - 1021, n - 4, n - 3, n - 2, n - 1]
+    assert len(set(idx)) == len(idx) and 0 <= min(idx) and max(idx) == n - 1
+    return np.array(idx)
+
+
+def plant_uncountable(img):
+    """NaN, +inf, -1 and 0 in turn, in all three channels, at uncountable_pixels -> how many were planted."""
+    rgb = img[..., :3].reshape(-1, 3)   # (a view)
+    idx = uncountable_pixels(rgb.shape[0])
+    rgb[idx] = np.array(UNCOUNTABLE, np.float32)[np.arange(idx.size) % 4][:, None]
+    return idx.size
 
 
 @functools.lru_cache(maxsize=None)
 def sized_case(w, h):
     img = seeded(np.random.default_rng(100 + w + h), h, w)
+    planted = plant_uncountable(img) if (w, h) in BIG_SIZES else 0
     d = R.Display()
-    return img, d.run(img, ORIGIN, **ALL), d.state()
+    out = d.run(img, ORIGIN, **ALL)
+    assert d.state()["skipped"] == planted and d.state()["counted"] == w * h - planted
+    return img, out, d.state()
+
+
+@functools.lru_cache(maxsize=None)
+def flat_case():
+    """1283 x 1025 of 0.3: every wave of the unrolled body falls into one bin."""
+    img = np.full((1025, 1283, 4), 0.3, np.float32)
+    d = R.Display()
+    out = d.run(img, ORIGIN, **ALL)
+    assert max(d.state()["histogram"]) == 1283 * 1025
+    return img, out, d.state()
+
+
+def hist_constants():
+    """(HIST_THREADS, HIST_UNROLL, the default DP_HIST_MAX_BLOCKS) as gpuart_amd/csrc/display/display.hip has them."""
+    src = open(os.path.join(ROOT, "gpuart_amd", "csrc", "display", "display.hip")).read()
+    out = []
+    for pattern in (r"\bHIST_THREADS\s*=\s*(\d+)", r"\bHIST_UNROLL\s*=\s*(\d+)", r"#define\s+DP_HIST_MAX_BLOCKS\s+(\d+)"):
+        found = re.findall(pattern, src)
+        assert len(found) == 1, (pattern, found)
+        out.append(int(found[0]))
+    return tuple(out)
+
+
+def hist_walk(n, t, threads, unroll, max_blocks):
+    """k_dp_histogram's two loops for thread t of the grid over n pixels -> (blocks wanted, blocks launched, unrolled passes, tail turns)."""
+    want = (n + threads - 1) // threads
+    grid = min(want, max_blocks)
+    stride = grid * threads
+    i, passes, tail = t, 0, 0
+    while i + (unroll - 1) * stride < n:
+        i, passes = i + unroll * stride, passes + 1
+    while i < n:
+        i, tail = i + stride, tail + 1
+    return want, grid, passes, tail
+
+
+def test_sizes_reach_the_histograms_loops():
+    """(CPU) what test_sizes' shapes are for, computed from the constants of display.hip: a grid below the cap, a capped grid without
+    an unrolled pass, exactly one unrolled pass, two, no tail turn and three or more; the figures of each of BIG_SIZES; and the planted
+    pixels lie in the first and the last block's share of both loops."""
+    threads, unroll, max_blocks = hist_constants()
+    walk = {}
+    for w, h in SIZES + BIG_SIZES:
+        n = w * h
+        grid = min((n + threads - 1) // threads, max_blocks)
+        walk[w, h] = [hist_walk(n, t, threads, unroll, max_blocks) for t in (0, grid * threads - 1)]
+    print(walk)
+    every = [v for pair in walk.values() for v in pair]
+    assert any(want <= max_blocks for want, _, _, _ in every)
+    assert any(want > max_blocks and passes == 0 for want, _, passes, _ in every)
+    assert any(passes == 1 for _, _, passes, _ in every) and any(passes >= 2 for _, _, passes, _ in every)
+    assert any(tail == 0 for _, _, _, tail in every) and any(tail >= 3 for _, _, _, tail in every)
+    assert all(want <= max_blocks and passes == 0 for (w, h) in SIZES for want, _, passes, _ in walk[w, h])   # (the gap this closes)
+    assert walk[513, 512] == [(257, 256, 0, 2), (257, 256, 0, 1)]
+    assert walk[887, 887] == [(769, 256, 1, 0), (769, 256, 0, 3)]
+    assert walk[1049, 1000] == [(1025, 256, 1, 1), (1025, 256, 1, 0)]
+    assert walk[1283, 1025] == [(1285, 256, 1, 2), (1285, 256, 1, 1)]
+    assert walk[1537, 1537] == [(2308, 256, 2, 2), (2308, 256, 2, 1)]
+    # 337 threads of 887 x 887 take the unrolled body (five waves and 17 lanes of a sixth) and the others three tail turns, 424 threads
+    # of 1049 x 1000 a tail turn after it, the first 512 of 513 x 512 a second tail turn
+    assert sum(hist_walk(887 * 887, t, threads, unroll, max_blocks)[2] for t in range(0, 1024)) == 337
+    assert sum(hist_walk(1049000, t, threads, unroll, max_blocks)[3] for t in range(0, 1024)) == 424
+    assert sum(hist_walk(513 * 512, t, threads, unroll, max_blocks)[3] == 2 for t in range(0, 1024)) == 512
+    # the planted pixels: in every frame past three strides some are met by the unrolled body and some by the tail
+    stride = max_blocks * threads
+    for w, h in BIG_SIZES[1:]:
+        assert w * h > 3 * stride
+        n = w * h
+        idx = uncountable_pixels(n, stride)
+        passes = np.array([hist_walk(n, int(p % stride), threads, unroll, max_blocks)[2] for p in idx])
+        in_body = idx // stride < passes * unroll
+        assert in_body.sum() >= 8 and (~in_body).sum() >= 8, (w, h)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("entry", ["host", "device"])
-@pytest.mark.parametrize("w,h", SIZES)
+@pytest.mark.parametrize("w,h", SIZES + BIG_SIZES)
 def test_sizes(handles, entry, w, h):
     """Below, at and above the encode's four pixels per thread and 1024 per block and the histogram's block, a width that is no multiple
-    of four, and the longest row and column: every stage on, at an odd origin."""
+    of four, and the longest row and column: every stage on, at an odd origin. BIG_SIZES: past the histogram's capped grid, through its
+    unrolled body and round its tail more than once, with pixels it skips planted at both ends of every stride."""
     img, exp, state = sized_case(w, h)
     handles[entry].reset()
     assert_same_bytes(run_entry(handles[entry], entry, img, ALL), exp, "%d x %d, %s" % (w, h, entry))
     assert_state(handles[entry].state(), state, "%d x %d, %s" % (w, h, entry))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("entry", ["host", "device"])
+def test_a_flat_frame_through_the_unrolled_body(handles, entry):
+    """1283 x 1025 of 0.3: in the unrolled body every lane of every wave counts into one bin, so each wave adds its count through one
+    lane; the bin ends with 1 315 075 counts, a block's LDS word with about 5 000."""
+    img, exp, state = flat_case()
+    handles[entry].reset()
+    assert_same_bytes(run_entry(handles[entry], entry, img, ALL), exp, "flat, %s" % entry)
+    assert_state(handles[entry].state(), state, "flat, %s" % entry)
 
 
 def exact_values(transfer, dither):

@@ -3,6 +3,7 @@ include/gpuart_hip.h): the libraries' boundaries and the parameter record, the r
 tiles and what the resolve is worth on the oracle's protocol (tests/edges_protocol.py), the sub-pixel rays against the oracle and the
 kernels against the restatement bit for bit, Renderer::SetEdgeResolve against the chain of restatements, and what it leaves alone."""
 import ctypes as C
+import functools
 import os
 import re
 import subprocess
@@ -206,6 +207,61 @@ def test_cases_take_every_branch():
             assert c["lst"].size == 0 and same_bits(out, c["filtered"])
         assert (np.diff(c["lst"].astype(np.int64)) > 0).all()
     assert all(v >= 20 for v in total.values()), total
+
+
+WAVE = 64   # one ballot word per wave of k_ed_flag
+
+
+def scan_block():
+    """SCAN_BLOCK of gpuart_amd/csrc/edges/edges.hip: the ballot words k_ed_scan takes per pass of its loop."""
+    src = open(os.path.join(ROOT, "gpuart_amd", "csrc", "edges", "edges.hip")).read()
+    found = re.findall(r"\bSCAN_BLOCK\s*=\s*(\d+)", src)
+    assert len(found) == 1, found
+    return int(found[0])
+
+
+@functools.lru_cache(maxsize=None)
+def chunk_cases():
+    """Tiles whose ballot words fill more than one pass of k_ed_scan's loop, or one pass exactly: 1031 x 130 (2095 words in three
+    chunks, 14 pixels in the last word, a partial last block of k_ed_flag), 1025 x 64 (1025 words: a second chunk of one word), the two
+    limit shapes (1024 words), and the all-edge and the no-edge tile at 1025 x 65 (1041 words, the last one partial)."""
+    return [planted(70, 1031, 130, 1, 1), planted(72, 1025, 64, 1, 2), planted(73, 65536, 1, 1, 1), planted(74, 1, 65536, 1, 4),
+            planted(75, 1025, 65, 1, 1, "all"), planted(76, 1025, 65, 1, 1, "none")]
+
+
+def chunk_counts(c, block):
+    """(ballot words, listed pixels per chunk of `block` words) of a case."""
+    words = (c["prims"].size + WAVE - 1) // WAVE
+    chunks = (words + block - 1) // block
+    return words, np.bincount(c["lst"].astype(np.int64) // WAVE // block, minlength=chunks)
+
+
+def test_chunk_cases_reach_the_scans_carry():
+    """(CPU) what the multi-chunk cases are for, computed from their expected lists, SCAN_BLOCK as edges.hip has it and the wave width:
+    three chunks and more, every chunk of the mixed multi-chunk tiles with a listed pixel (a lost carry moves its prefix), a chunk of
+    exactly one word, a partial last word; and the figures of the 1031 x 130 tile."""
+    block = scan_block()
+    assert block % WAVE == 0
+    stats = {c["name"]: chunk_counts(c, block) for c in chunk_cases()}
+    print(stats)
+    assert max(len(per) for _, per in stats.values()) >= 3
+    multi = [(name, per) for name, (_, per) in stats.items() if name.startswith("mixed") and len(per) > 1]
+    assert len(multi) >= 2 and all((per >= 1).all() for _, per in multi), multi
+    assert any(words % block == 1 for words, _ in stats.values())
+    assert any(c["prims"].size % WAVE for c in chunk_cases())
+    assert any(words == block for words, _ in stats.values())             # one full chunk exactly: the limit shapes
+    first = chunk_cases()[0]
+    assert first["prims"].shape == (130, 1031) and stats[first["name"]][0] == 2095 and first["prims"].size % WAVE == 14
+    assert first["lst"].size == 111604 and list(stats[first["name"]][1]) == [54462, 54606, 2536]
+    every, none = chunk_cases()[4], chunk_cases()[5]
+    assert (every["lst"] == np.arange(1025 * 65)).all() and none["lst"].size == 0 and len(stats[every["name"]][1]) == 2
+    # the long list of the resolve: past 65 536 entries, so with n_sub 2 the sub-sample index k * n + i passes 2^17
+    assert long_list_case()["lst"].size > 65536 and 2 * long_list_case()["lst"].size > 2 ** 17
+
+
+@functools.lru_cache(maxsize=None)
+def long_list_case():
+    return planted(71, 1031, 130, 2, 1)
 
 
 def test_match_follows_the_classes_and_the_thresholds():
@@ -519,6 +575,72 @@ def test_mark_equals_the_restatement(B, O, ed):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("i", range(6))
+def test_mark_across_scan_chunks(B, ed, i):
+    """The list and its count where k_ed_scan's loop goes round more than once, or fills one pass exactly (chunk_cases): the carry
+    between chunks, s_wave used again, the partial last chunk. The no-edge tile carries a count of 0 through two chunks and writes
+    nothing to the list."""
+    import torch
+    assert len(chunk_cases()) == 6
+    c = chunk_cases()[i]
+    lst = check_mark(ed, c["words"], c["prims"], c["flags"], dict(c["params"]), c["name"])
+    assert (lst == c["lst"]).all()
+    if c["name"].startswith("none"):
+        h, w = c["prims"].shape
+        words, prims = to_device(c["words"]), to_device(c["prims"])
+        big = torch.full((h * w + 1,), 0x5A5A5A5A, dtype=torch.int32, device="cuda:0")
+        dp = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
+        torch.cuda.synchronize()
+        assert ed.L.gpuart_edges_mark(ed.h, dp(words), dp(prims), c["flags"], w, h, C.byref(B.EdgesParams(**c["params"])), dp(big), dp(big, 4 * h * w)) == 0
+        ed.finish()
+        assert int(big[h * w].item()) == 0 and (big[:h * w] == 0x5A5A5A5A).all()
+
+
+@pytest.mark.gpu
+def test_mark_through_one_handle_shrinks_and_grows_across_chunks(B):
+    """One handle: 1031 x 130 (three chunks), then 7 x 1 (one word), then 1031 x 130 of another seed. The ballots and prefixes the
+    large frames left past the small frame's word, and the small frame's in front of the second large one, do not show."""
+    h = B.Edges(0)
+    try:
+        for c in (chunk_cases()[0], planted(77, 7, 1, 1, 1), planted(78, 1031, 130, 1, 1)):
+            lst = check_mark(h, c["words"], c["prims"], c["flags"], dict(c["params"]), c["name"])
+            assert (lst == c["lst"]).all()
+    finally:
+        h.close()
+
+
+def check_resolve(ed, c):
+    """ed.resolve of a planted case against `expected`: bit for bit, the unlisted pixels the input's bits, the input untouched."""
+    exp, _ = expected(c)
+    d = [to_device(a) for a in (c["filtered"], c["words"], c["prims"], c["lst"].view(np.int32), c["sw"], c["sp"])]
+    got = ed.resolve(*d, c["flags"], c["params"]).cpu().numpy()
+    assert_same_bits(got, exp, c["name"])
+    assert_same_bits(d[0].cpu().numpy(), c["filtered"], c["name"] + ": the input")
+    h, w = c["prims"].shape
+    listed = np.zeros(h * w, bool)
+    listed[c["lst"]] = True
+    assert same_bits(got.reshape(-1, 4)[~listed], c["filtered"].reshape(-1, 4)[~listed])
+    assert not same_bits(got, c["filtered"])
+
+
+@pytest.mark.gpu
+def test_resolve_with_a_long_list(ed):
+    """1031 x 130 with n_sub 2: 111 456 listed pixels in 436 blocks, the second sub-sample's records from index 111 456 on."""
+    c = long_list_case()
+    assert c["lst"].size > 65536
+    check_resolve(ed, c)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("w,h", [(65536, 1), (1, 65536)])
+def test_resolve_at_the_limit_shapes(ed, w, h):
+    """The longest row and the longest column, n_sub 1: every candidate outside the tile lies on one axis."""
+    c = chunk_cases()[2 if h == 1 else 3]
+    assert c["prims"].shape == (h, w) and c["params"]["n_sub"] == 1
+    check_resolve(ed, c)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("i", range(9))
 def test_resolve_equals_the_restatement_on_planted_tiles(ed, i):
     """n_sub 1, 8, 16 and 3, every flag: bit for bit, the unlisted pixels the input's bits, the inputs untouched."""
@@ -738,6 +860,74 @@ def test_the_switch_leaves_everything_else_alone(B):
         assert_same_bits(g, e, "resolved read %d" % k)
         assert not same_bits(g, off[1][k])
     assert (on[1][-2] == DR.encode(off[2][-1])).all() and not (on[1][-1] == off[1][-1]).all()
+
+
+@pytest.mark.gpu
+def test_edge_resolve_over_antilag_past_one_scan_chunk(B):
+    """320 x 240 (76 800 pixels: 1200 ballot words, two chunks of k_ed_scan) on the box with the emissive user sphere, the history, its
+    variance and anti-lag on (tests/test_antilag.py's P_LEAVE, which lets two views of four paths vote), two views of 4 passes of 1
+    path with the sphere moved between them by set_user_sphere_pos, so that the history is kept. A run with the switch off and one
+    with it on: every filtered read of the second is the chain's resolve of the first's, bit for bit, and not the unresolved frame;
+    read_display of the guided preview is the display restatement of the resolved frame; the accumulator, the counters and the error
+    map are the same; the restatement's list has entries on both sides of pixel 65 536; and the mix did move the guided preview."""
+    from tests.test_antilag import P_LEAVE
+    from tests.test_moments import LUM_FLOOR
+    W, H = 320, 240
+    # closer than the tracks' cameras and looking down: the back wall's upper rim lies in the frame's top rows (from the tracks' cameras
+    # everything above row 123 is sky, and the list ends at pixel 39 620)
+    cam = dict(S.DEFAULT_CAMERA, pos=(0.1, -1.2, 0.6), target=(0.0, 0.0, 0.2))
+    cam["dir"] = S.camera_dir(cam)
+
+    def run(mode):
+        r = B.Renderer(W, H, cam)
+        try:
+            r.set_primitives(scene("box"))
+            r.set_user_sphere(SPHERE[:3], SPHERE[3], emittance=2.0)
+            r.set_temporal_history(True)
+            r.set_history_variance(True)
+            r.set_history_antilag(mode != "no_antilag", P_LEAVE)
+            r.set_edge_resolve(mode == "on")
+            r.backend.set_mode(4)
+            raw, filtered, resolved, lists = [], [], [], []
+            r.restart_path_tracing(1, 12)
+            for i in range(2):
+                if i:
+                    r.set_user_sphere_pos((-0.2, 0.1, 0.3))
+                for _ in range(4):
+                    r.path_tracing_pass()
+                filtered += [r.read_guided_preview(LUM_FLOOR), r.read_preview(), r.read_denoised()]
+                if mode == "no_antilag":
+                    continue
+                raw += [r.read_radiance(False)]
+                if mode == "off":
+                    resolved += [chain(B, r, f)[0] for f in filtered[-3:]]
+                    gp = r.params()
+                    hits, prims = r.backend.gbuffer(user_sphere=tuple(gp.userSphere))
+                    lists += [E.mark(np.ascontiguousarray(hits).view(F).reshape(prims.shape + (8,)), prims, gp.userSphereFlags)]
+            if mode == "no_antilag":
+                return filtered
+            shown = r.read_display("guided_preview", None, LUM_FLOOR)
+            converged, s1 = r.render_until(1e30, 0.0, 4, LUM_FLOOR)
+            assert converged and s1["batches"] == 2
+            raw += [r.read_radiance(False), r.read_error_map(LUM_FLOOR)]
+            return raw, filtered, resolved, (r.backend.counters().as_dict(), s1), shown, lists
+        finally:
+            r.close()
+
+    off, on = run("off"), run("on")
+    assert off[3] == on[3], (off[3], on[3])
+    assert len(off[0]) == len(on[0]) == 4 and off[0][-1] is not None
+    for k, (a, b) in enumerate(zip(off[0], on[0])):
+        assert_same_bits(b, a, "raw result %d" % k)
+    assert len(off[2]) == len(on[1]) == 6
+    for k, (e, g) in enumerate(zip(off[2], on[1])):
+        assert_same_bits(g, e, "resolved read %d" % k)
+        assert not same_bits(g, off[1][k])
+    assert (on[4] == DR.encode(off[2][3])).all() and not (on[4] == off[4]).all()
+    for lst in off[5]:
+        assert (lst < 65536).sum() > 100 and (lst >= 65536).sum() > 100, lst.size
+    plain = run("no_antilag")
+    assert not same_bits(plain[3], off[1][3])     # the second view's guided preview follows the fast history
 
 
 @pytest.mark.gpu

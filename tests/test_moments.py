@@ -456,6 +456,49 @@ def test_kernels_equal_the_restatement_on_planted_tiles(mo, i):
     check_pack(mo, c["x"], (1, 3, 2 ** 24 + 1)[i % 3], c["name"] + ", pack")
 
 
+@functools.lru_cache(maxsize=None)
+def limit_case(w, h):
+    """The longest row (seed 700) or the longest column (seed 701, P_X) of `plant`, with the surface pixels within 3 of both ends of
+    the long axis left without history (len 1, q 1): the first and the last block of k_mo_error take the spatial estimate, with the
+    window's apron outside the tile at both ends."""
+    c = plant(700, w, h) if h == 1 else plant(701, w, h, params=P_X)
+    surf, _ = D.surface(c["words"], c["prims"], c["flags"])
+    at = np.arange(w * h).reshape(h, w)
+    ends = surf & ((at <= 3) | (at >= w * h - 4))
+    assert ends.reshape(-1)[:4].any() and ends.reshape(-1)[-4:].any()
+    c["len"][ends] = 1
+    c["m"][ends, 2] = 1
+    c["e"], c["ledger"] = M.error(c["x"], c["len"], c["m"], c["words"], c["prims"], LUM_FLOOR, c["flags"], want_ledger=True,
+                                  **dict(M.DEFAULTS, **(c["params"] or {})))
+    return c
+
+
+@pytest.mark.parametrize("w,h", [(65536, 1), (1, 65536)])
+def test_limit_cases_take_the_spatial_branch_at_both_ends(w, h):
+    """(CPU) the restatement's ledger for the two limit shapes: pixels take the spatial estimate and window neighbours lie outside the
+    tile, and the planted pixels at both ends of the long axis are among them."""
+    c = limit_case(w, h)
+    led = c["ledger"]
+    print(led)
+    assert led["spatial"] > 0 and led["win_outside"] > 0 and led["temporal"] > 0 and led["not_surface"] > 0, led
+    B = (c["len"] * c["m"][..., 2]).reshape(-1)
+    surf = D.surface(c["words"], c["prims"], c["flags"])[0].reshape(-1)
+    mb = F(dict(M.DEFAULTS, **(c["params"] or {}))["min_batches"])
+    for end in (slice(0, 4), slice(-4, None)):
+        assert (surf[end] & (B[end] < mb)).any() and np.isfinite(c["e"].reshape(-1)[end]).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("w,h", [(65536, 1), (1, 65536)])
+def test_kernels_equal_the_restatement_at_the_limit_shapes(mo, w, h):
+    """65536 x 1 (1024 blocks across) and 1 x 65536 (16384 up): k_mo_error stages an apron that lies outside the tile past both ends
+    of every row block; the first and the last block take the spatial branch."""
+    c = limit_case(w, h)
+    assert c["ledger"]["spatial"] > 0 and c["ledger"]["win_outside"] > 0
+    check_pack(mo, c["x"], 3, c["name"] + ", pack")
+    check_error(mo, c["x"], c["len"], c["m"], c["words"], c["prims"], c["flags"], c["params"], c["e"], c["name"])
+
+
 @pytest.mark.gpu
 def test_kernels_equal_the_restatement_on_the_tracks_blends(mo, B):
     """The box at 160 x 120 with a user sphere that moves before the third view (its history is rejected there), one path per view from
