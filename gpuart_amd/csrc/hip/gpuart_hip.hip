@@ -162,6 +162,8 @@ struct gpuart_hip_ctx {
                                            ///< with packets, the 100 352-triangle one 7 % faster (profiles/r07/ab_runs.txt; sizes between: not measured)
     uint32_t gen_walk = 1;        ///< GPUART_HIP_GEN_WALK (default 1): where the camera rays' launch would walk packets and a later k_trace launch follows,
                                   ///< k_gen walks the camera rays it generates and that launch is not made (launch_run); 0 — always the separate launch
+    uint32_t gen_shade = 2;       ///< GPUART_HIP_GEN_SHADE (default 2): where k_gen walks and the run has a segment 1, 1 — k_gen also shades segment 0 of the paths it
+                                  ///< walked and k_shade(0) is not launched; 2 — and walks their Sun-shadow queries as packets of its own; 0 — the separate launches
     uint32_t exact_boxes = 0;     ///< the uploaded tree holds an irregular box, or a box that does not bound what it holds (converter.h):
                                   ///< box tests take the comparison form and every walk keeps the reference's order
     uint32_t max_depth = 0;
@@ -535,6 +537,7 @@ int gpuart_hip_create(int device, gpuart_hip_ctx **out) {
     c->packet = env_u32("GPUART_HIP_PACKET", 2, 0, 2);
     c->packet_max_prims = env_u32("GPUART_HIP_PACKET_MAX_PRIMS", 1u << 19, 0, 0xffffffffu);
     c->gen_walk = env_u32("GPUART_HIP_GEN_WALK", 1, 0, 1);
+    c->gen_shade = env_u32("GPUART_HIP_GEN_SHADE", 2, 0, 2);
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return fail(GPUART_HIP_ERR_DEVICE, "hipStreamCreate failed"); }
     c->lanes.resize(env_u32("GPUART_HIP_PASSES_IN_FLIGHT", 8, 1, 32));
     c->plan.lanes_total = (uint32_t)c->lanes.size();
@@ -919,6 +922,8 @@ int launch_run(gpuart_hip_ctx *c, size_t first, size_t count) {
     // size, a fast-box kernel in the reference's order — and a later k_trace launch follows in the run; then trace(0, -1) is not launched
     const bool gen_walk = c->gen_walk && packet >= 1 && (trace_choice & GD_REF_ORDER) && !(trace_choice & GD_EXACT_BOXES) && nseg > 0 &&
                           (nseg >= 2 || p->sunEnabled == 1);
+    // ... and shades segment 0 of what it walked (GPUART_HIP_GEN_SHADE) where k_shade(1) follows; at level 2 it walks segment 0's Sun-shadow queries too
+    const int gen_shade = gen_walk && nseg >= 2 ? (int)c->gen_shade : 0;
     const dim3 wgrid(std::max<uint32_t>(1u, std::min<uint32_t>(c->grid_waves, (b.n_slots * b.batch + c->tune.chunk - 1) / c->tune.chunk)));  // (l.spill_main holds grid_waves columns at least)
     // one BVH-query launch: closest-hit queries of segment seg_c and / or Sun-shadow queries of segment seg_s
     auto trace = [&](int seg_c, int seg_s) -> int {
@@ -943,13 +948,14 @@ int launch_run(gpuart_hip_ctx *c, size_t first, size_t count) {
         if (gen_walk) {  // in the per-launch bracket the camera rays' launch had
             TimedLaunch tt;
             if (detail && (r = begin_timed(c, tt, 1, l.main))) return r;
-            k_gen<<<wgrid, BLOCK, 0, l.main>>>(sc, fr, *p, seeds, j, npaths, b, l.passcolor, l.spill_main, c->tune.chunk, trace_choice);
+            k_gen<<<wgrid, BLOCK, 0, l.main>>>(sc, fr, *p, seeds, j, npaths, b, l.passcolor, l.spill_main, c->tune.chunk, trace_choice, gen_shade);
             if (detail && (r = end_timed(c, tt, l.main))) return r;
+            if (gen_shade && (r = trace(1, gen_shade < 2 && p->sunEnabled == 1 ? 0 : -1))) return r;
         } else {
-            k_gen<<<sgrid, BLOCK, 0, l.main>>>(sc, fr, *p, seeds, j, npaths, b, l.passcolor, l.spill_main, c->tune.chunk, 0);
+            k_gen<<<sgrid, BLOCK, 0, l.main>>>(sc, fr, *p, seeds, j, npaths, b, l.passcolor, l.spill_main, c->tune.chunk, 0, 0);
             if (nseg && (r = trace(0, -1))) return r;
         }
-        for (uint32_t seg = 0; seg < nseg; seg++) {
+        for (uint32_t seg = gen_shade ? 1 : 0; seg < nseg; seg++) {
             GD_LEDGER(c, k_shade<false>);
             k_shade<false><<<sgrid, BLOCK, 0, l.main>>>(sc, fr, *p, seeds, b, (int)seg, (int)nseg, j, npaths, l.passcolor, c->d_counters);
             // the Sun-shadow queries of this segment travel with the closest-hit queries of the next one

@@ -394,14 +394,33 @@ GD_FN void thin_rounds(const Scene &sc, const F3 &ro, const F3 &rd, const F3 &rd
 // `walk` != 0 (the host's GPUART_HIP_GEN_WALK; the GD_REF_ORDER fast-box choice `kernel_choice` makes for k_trace): the wave that computes
 // the rays of 64 consecutive path slots — one camera packet of k_trace — also walks them, from its registers: what take_query does for a
 // closest-hit query in the reference's order, then trav_packet, then hit[slot]. No k_trace(0, -1) follows. The same device functions on
-// the same values in the same order: the results are those of the separate launch bit for bit. The ray and queue[0] are stored as
-// before (k_shade(0) reads them); nothing waits for the stores. Packets differ widely in length (sky against mesh), so the waves take
+// the same values in the same order: the results are those of the separate launch bit for bit. With `shade` == 0 the ray and queue[0]
+// are stored as before (k_shade(0) reads them); nothing waits for the stores. Packets differ widely in length (sky against mesh), so the waves take
 // chunks from a cursor (ChunkCursor; counters[1], which no other launch of such a run uses). The grid is at most the waves `spill` was
 // sized for.
-__global__ void __launch_bounds__(BLOCK) k_gen(Scene sc, Frame f, gpuart_params P, SeedBatch seeds, int j, int npaths, PathBuffers b,
-                                               float4 *accum, uint4 *spill, uint32_t chunk, int walk) {
+// `shade` >= 1 (the host's GPUART_HIP_GEN_SHADE; walking form only, and only where k_shade(1) follows): after the walk the wave holds, in
+// registers, all that k_shade(0) would load — the ray, the hit —, so each lane that holds a query shades segment 0 of its slot here:
+// tile_cost_add, path_shade with colorWeight = 1 and pathColor = 0, then k_shade's `broke` branch, its stores of ray_o / ray_d / cw / pc /
+// sun under its conditions, its direct path_commit. The same device functions on the same values in the same order as the separate
+// launch (contraction is off: no operation fuses across what used to be a store and a load): bit-identical. The FIRST ray, queue[0] and
+// hit[slot] are then not stored, and k_shade(0) is not launched. Survivors go to queue[1] (counters[4]), Sun-shadow queries to shadow_queue
+// (counters[2]), with one atomic per list per SHADE_ROUNDS packets and once more when the wave's loop ends (k_shade's reason: one atomic
+// word sustains ~90 appends/us). A packet's slots are consecutive, so the staging list is the packet's first slot (LDS, one word per
+// packet) and one bit per list and packet in every lane — not k_shade's two lists of slots, whose 4 KB would leave LDS for 16 waves per CU
+// where the registers allow 20.
+// `shade` == 2: the lanes whose path wants a Sun-shadow query keep sun_term and pathColor, start that query (k_trace's take_query for a
+// shadow entry: origin = the hit, direction = the Sun) while the others stand in state DONE, the wave walks them as one packet that stops
+// at the first accepted hit, and each retires as k_trace retires a shadow query: sun_visible, the term, path_commit or ONE store of pc.
+// Nothing goes to shadow_queue and sun[slot] is not written. Such a packet holds only the shadow lanes of its own 64 slots (none on sky),
+// where k_trace's packets are 64 dense entries: a separate level of the knob because of that.
+// The launch bound: without it the shading code takes the kernel to 111 VGPRs and 4 waves per SIMD, which costs every level of the knob
+// 1-3.5 % of a pass (the other pass lanes' kernels share the CUs); with it 96 VGPRs and 40 bytes of scratch, path state parked across the
+// walks once per packet.
+__global__ void __launch_bounds__(BLOCK, GD_TRACE_WAVES) k_gen(Scene sc, Frame f, gpuart_params P, SeedBatch seeds, int j, int npaths, PathBuffers b,
+                                               float4 *accum, uint4 *spill, uint32_t chunk, int walk, int shade) {
     __shared__ uint2 ring_a[GD_RING * BLOCK];
     __shared__ float ring_b[GD_RING * BLOCK];
+    __shared__ uint32_t stage_first[SHADE_ROUNDS];  // first slot of the packets since the last flush
     const bool no_segments = !(P.maxSegments > 0 && 1.0f > P.minWeight);
     const uint32_t total = b.n_slots * b.batch;
     // the first ray of path slot `slot` (a padding slot of a ragged edge tile: none); true: the path has a segment 0 to trace
@@ -417,12 +436,14 @@ __global__ void __launch_bounds__(BLOCK) k_gen(Scene sc, Frame f, gpuart_params 
                 path_commit(f, b, accum, slot, j, npaths, path_finish(P, rd0, 0, false, false, f3(0, 0, 0)));
             } else {
                 path_begin(P, seed, j, rs0, rd0, rs, rd);
-                b.ray_o[slot] = make_float4(rs.x, rs.y, rs.z, 0);
-                b.ray_d[slot] = make_float4(rd.x, rd.y, rd.z, 0);
+                if (!shade) {
+                    b.ray_o[slot] = make_float4(rs.x, rs.y, rs.z, 0);
+                    b.ray_d[slot] = make_float4(rd.x, rd.y, rd.z, 0);
+                }
                 q = slot;  // (colorWeight = 1 and pathColor = 0 are not stored: k_shade knows them for segment 0)
             }
         }
-        b.queue[0][slot] = q;
+        if (!shade) b.queue[0][slot] = q;
         return q != SLOT_INVALID;
     };
     if (walk == 0) {
@@ -433,6 +454,32 @@ __global__ void __launch_bounds__(BLOCK) k_gen(Scene sc, Frame f, gpuart_params 
     } else {
         TravStack st = make_stack(ring_a, ring_b, spill, gridDim.x * BLOCK);
         ChunkCursor cur(total, chunk);
+        const F3 sun = f3(P.sunDirAlt[0], P.sunDirAlt[1], P.sunDirAlt[2]);
+        uint32_t rounds = 0, n_next = 0, n_shadow = 0;  // wave-uniform: packets shaded since the last flush, the entries they left for the two lists
+        uint32_t bits_next = 0, bits_shadow = 0;        // bit k: this lane's slot of packet k goes to queue[1] / to shadow_queue
+        // one atomic per list, then the slots packet by packet, in slot order
+        auto flush = [&]() {
+            __syncthreads();
+            uint32_t base1 = 0, base2 = 0;
+            if (lane_id() == 0) {
+                if (n_next) base1 = atomicAdd(&b.counters[4], n_next);
+                if (n_shadow) base2 = atomicAdd(&b.counters[2], n_shadow);
+            }
+            base1 = wave_value(base1);
+            base2 = wave_value(base2);
+            for (uint32_t k = 0; k < rounds; k++) {
+                const uint32_t s = stage_first[k] + (uint32_t)lane_id();  // (a packet's slots: ChunkCursor::take with every lane idle)
+                const bool p1 = (bits_next >> k) & 1u, p2 = (bits_shadow >> k) & 1u;
+                const unsigned long long m1 = __ballot(p1), m2 = __ballot(p2);
+                if (p1) b.queue[1][base1 + rank_below(m1)] = s;
+                if (p2) b.shadow_queue[base2 + rank_below(m2)] = s;
+                base1 += (uint32_t)__popcll(m1);
+                base2 += (uint32_t)__popcll(m2);
+            }
+            __syncthreads();
+            rounds = n_next = n_shadow = 0;
+            bits_next = bits_shadow = 0;
+        };
         for (;;) {
             bool served;
             const uint32_t slot = cur.take(~0ull, true, &b.counters[1], chunk, served);  // the next (up to) 64 slots of the chunk
@@ -447,8 +494,71 @@ __global__ void __launch_bounds__(BLOCK) k_gen(Scene sc, Frame f, gpuart_params 
             if (walk == (GD_FLAT_TYPES | GD_REF_ORDER)) trav_packet<GD_FLAT_TYPES | GD_REF_ORDER>(sc, ro, rd, rdiv, t, st, false);
             else if (walk == (GD_ROUND_TYPES | GD_REF_ORDER)) trav_packet<GD_ROUND_TYPES | GD_REF_ORDER>(sc, ro, rd, rdiv, t, st, false);
             else trav_packet<GD_ALL_TYPES | GD_REF_ORDER>(sc, ro, rd, rdiv, t, st, false);
-            if (query) b.hit[slot] = make_uint2(__float_as_uint(t.closest), t.hit_prim);
+            if (!shade) {
+                if (query) b.hit[slot] = make_uint2(__float_as_uint(t.closest), t.hit_prim);
+                continue;
+            }
+            // ---- segment 0 of the packet's paths: k_shade's body for seg == 0 on the register values
+            bool go_on = false, shadow = false;
+            F3 pathColor = f3(0, 0, 0), sun_term = f3(0, 0, 0);  // path_tracing.glsl:157
+            if (query) {
+                tile_cost_add(f, b, slot);
+                Ray r; r.o = ro; r.d = rd;
+                F3 cw = f3(1, 1, 1);  // path_tracing.glsl:156
+                F3 rstart = r.o, rdir = r.d;
+                const float4 seed = seeds.seed[slot_pass(b, slot)];
+                ShadeResult s = path_shade(sc, P, seed, 0, r, t.closest, t.hit_prim, rstart, rdir, cw, pathColor);
+                if (s.broke) {
+                    uint32_t lx, ly; F3 rs0, rd0;  // (recomputed: cheaper than keeping the camera direction alive across the walk)
+                    slot_pixel(f, slot_pixel_slot(b, slot), lx, ly);
+                    camera_ray(f, f.x0 + lx, frame_y(f, ly), rs0, rd0);
+                    path_commit(f, b, accum, slot, j, npaths, path_finish(P, rd0, 0, s.ush, s.specular, pathColor));
+                } else {
+                    go_on = s.next == PATH_CONTINUES;  // (k_shade's `seg + 1 < nseg` holds: the host shades here only where k_shade(1) follows)
+                    shadow = s.want_shadow && s.sun_matters;
+                    const bool queued = shadow && shade < 2;  // the Sun-shadow query goes to k_trace
+                    if (queued)
+                        b.sun[slot] = make_float4(s.sun_term.x, s.sun_term.y, s.sun_term.z, __uint_as_float(go_on ? 0u : 1u));
+                    if (go_on || queued) b.ray_o[slot] = make_float4(rstart.x, rstart.y, rstart.z, 0);
+                    if (go_on) {
+                        b.ray_d[slot] = make_float4(rdir.x, rdir.y, rdir.z, 0);
+                        b.cw[slot] = make_float4(cw.x, cw.y, cw.z, 0);
+                    }
+                    if (shadow ? queued : go_on) b.pc[slot] = make_float4(pathColor.x, pathColor.y, pathColor.z, 0);
+                    if (!go_on && !shadow) path_commit(f, b, accum, slot, j, npaths, pathColor);
+                    ro = rstart;
+                    sun_term = s.sun_term;
+                }
+            }
+            // ---- the Sun-shadow queries of these hits, walked here as one packet and retired as k_trace retires them
+            if (shade >= 2) {
+                t.state = TRAV_DONE;
+                if (shadow) {  // (k_trace's take_query for a shadow entry)
+                    rd = sun;
+                    rdiv = f3(1 / rd.x, 1 / rd.y, 1 / rd.z);
+                    trav_init<GD_BOXES_FAST>(sc, Ray{ro, rd}, rdiv, t, st, nullptr, false);
+                }
+                if (__ballot(shadow)) {
+                    if (walk == (GD_FLAT_TYPES | GD_REF_ORDER)) trav_packet<GD_FLAT_TYPES | GD_REF_ORDER>(sc, ro, rd, rdiv, t, st, shadow);
+                    else if (walk == (GD_ROUND_TYPES | GD_REF_ORDER)) trav_packet<GD_ROUND_TYPES | GD_REF_ORDER>(sc, ro, rd, rdiv, t, st, shadow);
+                    else trav_packet<GD_ALL_TYPES | GD_REF_ORDER>(sc, ro, rd, rdiv, t, st, shadow);
+                    if (shadow) {
+                        if (sun_visible(P, ro, sun, t.hit_prim)) pathColor = pathColor + sun_term;
+                        if (!go_on) path_commit(f, b, accum, slot, j, npaths, pathColor);
+                        else b.pc[slot] = make_float4(pathColor.x, pathColor.y, pathColor.z, 0);
+                    }
+                    shadow = false;
+                }
+            }
+            if (lane_id() == 0) stage_first[rounds] = slot;
+            const unsigned long long m1 = __ballot(go_on), m2 = __ballot(shadow);
+            if (go_on) bits_next |= 1u << rounds;
+            if (shadow) bits_shadow |= 1u << rounds;
+            n_next += (uint32_t)__popcll(m1);
+            n_shadow += (uint32_t)__popcll(m2);
+            if (++rounds == SHADE_ROUNDS) flush();
         }
+        if (rounds) flush();
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) b.counters[0] = no_segments ? 0u : total;
 }
