@@ -156,17 +156,9 @@ k_run(Scene sc, Frame f, gpuart_params P, SeedBatch seeds, PathBuffers b, int j,
             bool to_shade = false, joins = false, ended = false;
             if (done) {
                 if (ent & RUN_F_SHADOW) {
-                    // path_tracing.glsl:239-245: the Sun term counts if nothing lies towards the Sun
                     const float4 term = b.sun[s];
-                    F3 pathColor = xyz(b.pc[s]);
-                    if (sun_visible(P, ro, sun, t.hit_prim)) pathColor = pathColor + xyz(term);
-                    if (__float_as_uint(term.w) & 1u) {
-                        path_commit(f, b, passcolor, s, j, npaths, pathColor);  // the path ended with that segment
-                        ended = true;
-                    } else {
-                        b.pc[s] = make_float4(pathColor.x, pathColor.y, pathColor.z, 0);
-                        joins = true;  // its next closest-hit query is under way (or already back)
-                    }
+                    ended = shadow_retire(f, P, b, passcolor, s, j, npaths, ro, sun, t.hit_prim, xyz(b.pc[s]), xyz(term), (__float_as_uint(term.w) & 1u) != 0);
+                    joins = !ended;  // the path's next closest-hit query is under way (or already back)
                 } else {
                     b.hit[s] = make_uint2(__float_as_uint(t.closest), t.hit_prim);
                     joins = (ent & RUN_F_JOIN) != 0;
@@ -199,6 +191,7 @@ k_run(Scene sc, Frame f, gpuart_params P, SeedBatch seeds, PathBuffers b, int j,
             const bool can_shade = n_shade >= BLOCK || (n_shade > 0 && want_rays && (exhausted || n_shade >= RUN_SHADE_MIN));
             if (can_shade) {
                 // ---- shade up to 64 paths: path_tracing.glsl:182-233, then the loop header of the next segment
+                // (kernels_pipeline.h's segment step with queued = true and cw.w = seg + 1, written out: shared, it cost a pass alone 1.5-4 %)
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");  // hit / pc written by other lanes of this wave
                 const uint32_t cnt = min(n_shade, (uint32_t)BLOCK);
                 n_shade -= cnt;

@@ -251,6 +251,59 @@ GD_FN void path_commit(const Frame &f, const PathBuffers &b, float4 *passcolor, 
         b.color[slot] = make_float4(c.x, c.y, c.z, 0);
 }
 
+// ---- a path after its BVH queries, stated once: the segment step (k_shade, k_gen) and the Sun-shadow retire (k_trace, k_gen, k_run) ----
+// (k_run's PRODUCE keeps its own text of the step and of the first ray: shared, they cost its single pass 1.5-4 % — profiles/segment_step.txt)
+/// Where a path goes after a segment: a closest-hit query from (rstart, rdir), a Sun-shadow query from rstart that may add sun_term, both or neither.
+struct SegmentStep { bool go_on, shadow; F3 sun_term; };
+
+/// Segment `seg` of the path in `slot`, whose ray (ro, rd) came back with (closest, prim): path_tracing.glsl:182-233 on cw and pathColor (1 and
+/// 0 before segment 0), then where the path goes. A path that ends here is committed here. REFWORK: the shadow query is asked even where its
+/// answer cannot matter. BOUNDED: go on only while seg + 1 < nseg — a host bound too small must not queue a path for a launch that will not come.
+template <bool REFWORK, bool BOUNDED>
+GD_FN SegmentStep segment_shade(const Scene &sc, const Frame &f, const gpuart_params &P, const SeedBatch &seeds, const PathBuffers &b,
+                                float4 *passcolor, uint32_t slot, int j, int npaths, int seg, int nseg, F3 ro, F3 rd, float closest,
+                                uint32_t prim, F3 &rstart, F3 &rdir, F3 &cw, F3 &pathColor) {
+    tile_cost_add(f, b, slot);
+    Ray r; r.o = ro; r.d = rd;
+    rstart = ro; rdir = rd;
+    const float4 seed = seeds.seed[slot_pass(b, slot)];
+    const ShadeResult s = path_shade(sc, P, seed, seg, r, closest, prim, rstart, rdir, cw, pathColor);
+    SegmentStep o = {false, false, s.sun_term};
+    if (s.broke) {
+        uint32_t lx, ly; F3 rs0, rd0;  // (recomputed: cheaper than keeping the camera direction alive for the length of a path)
+        slot_pixel(f, slot_pixel_slot(b, slot), lx, ly);
+        camera_ray(f, f.x0 + lx, frame_y(f, ly), rs0, rd0);
+        path_commit(f, b, passcolor, slot, j, npaths, path_finish(P, rd0, seg, s.ush, s.specular, pathColor));
+    } else {
+        o.go_on = s.next == PATH_CONTINUES && (!BOUNDED || seg + 1 < nseg);
+        o.shadow = s.want_shadow && (REFWORK || s.sun_matters);
+        if (!o.go_on && !o.shadow) path_commit(f, b, passcolor, slot, j, npaths, pathColor);  // ended by the loop header, i >= 1: no special case
+    }
+    return o;
+}
+
+/// What the queries of a step need, stored under ONE rule — it decides which slot arrays a later reader may find stale. `queued`: the Sun-shadow
+/// query goes through memory (false: the caller walks it from its registers and retires it itself). `tag`: cw.w (k_run's text keeps seg + 1 there).
+GD_FN void segment_store(const PathBuffers &b, uint32_t slot, const SegmentStep &s, bool queued, uint32_t tag, F3 rstart, F3 rdir, F3 cw, F3 pathColor) {
+    if (s.shadow && queued) b.sun[slot] = make_float4(s.sun_term.x, s.sun_term.y, s.sun_term.z, __uint_as_float(s.go_on ? 0u : 1u));
+    if (s.go_on || (s.shadow && queued)) b.ray_o[slot] = make_float4(rstart.x, rstart.y, rstart.z, 0);
+    if (s.go_on) {
+        b.ray_d[slot] = make_float4(rdir.x, rdir.y, rdir.z, 0);
+        b.cw[slot] = make_float4(cw.x, cw.y, cw.z, __uint_as_float(tag));
+    }
+    if (s.shadow ? queued : s.go_on) b.pc[slot] = make_float4(pathColor.x, pathColor.y, pathColor.z, 0);
+}
+
+/// A finished Sun-shadow query from `ro` (path_tracing.glsl:239-245): the term counts if nothing lies towards the Sun. `ends`: the path
+/// ended with that segment and is committed; else its colour goes to pc[slot] for the next segment's step. Returns `ends`.
+GD_FN bool shadow_retire(const Frame &f, const gpuart_params &P, const PathBuffers &b, float4 *passcolor, uint32_t slot, int j, int npaths,
+                         F3 ro, F3 sun, uint32_t hit_prim, F3 pathColor, F3 term, bool ends) {
+    if (sun_visible(P, ro, sun, hit_prim)) pathColor = pathColor + term;
+    if (ends) path_commit(f, b, passcolor, slot, j, npaths, pathColor);
+    else b.pc[slot] = make_float4(pathColor.x, pathColor.y, pathColor.z, 0);
+    return ends;
+}
+
 /// path_tracing.glsl:255 for one finished pass: accum = PrevRadiance + color. Launched in pass order on the
 /// context's primary stream, so float additions happen in the reference's order whatever the overlap of passes.
 /// With per-block path counts (`counts`; adaptive sampling, gpuart_hip_set_active_blocks) it walks `entries` = 64 x blocks entries
@@ -399,22 +452,21 @@ GD_FN void thin_rounds(const Scene &sc, const F3 &ro, const F3 &rd, const F3 &rd
 // chunks from a cursor (ChunkCursor; counters[1], which no other launch of such a run uses). The grid is at most the waves `spill` was
 // sized for.
 // `shade` >= 1 (the host's GPUART_HIP_GEN_SHADE; walking form only, and only where k_shade(1) follows): after the walk the wave holds, in
-// registers, all that k_shade(0) would load — the ray, the hit —, so each lane that holds a query shades segment 0 of its slot here:
-// tile_cost_add, path_shade with colorWeight = 1 and pathColor = 0, then k_shade's `broke` branch, its stores of ray_o / ray_d / cw / pc /
-// sun under its conditions, its direct path_commit. The same device functions on the same values in the same order as the separate
-// launch (contraction is off: no operation fuses across what used to be a store and a load): bit-identical. The FIRST ray, queue[0] and
+// registers, all that k_shade(0) would load — the ray, the hit —, so each lane that holds a query takes segment 0 of its slot through the segment
+// step here: colorWeight = 1, pathColor = 0, no segment bound, `queued` = `shade` < 2 (the shadow query goes to k_trace). Contraction is off (no
+// operation fuses across what used to be a store and a load): the separate launch's frames bit for bit. The FIRST ray, queue[0] and
 // hit[slot] are then not stored, and k_shade(0) is not launched. Survivors go to queue[1] (counters[4]), Sun-shadow queries to shadow_queue
 // (counters[2]), with one atomic per list per SHADE_ROUNDS packets and once more when the wave's loop ends (k_shade's reason: one atomic
 // word sustains ~90 appends/us). A packet's slots are consecutive, so the staging list is the packet's first slot (LDS, one word per
 // packet) and one bit per list and packet in every lane — not k_shade's two lists of slots, whose 4 KB would leave LDS for 16 waves per CU
 // where the registers allow 20.
-// `shade` == 2: the lanes whose path wants a Sun-shadow query keep sun_term and pathColor, start that query (k_trace's take_query for a
-// shadow entry: origin = the hit, direction = the Sun) while the others stand in state DONE, the wave walks them as one packet that stops
-// at the first accepted hit, and each retires as k_trace retires a shadow query: sun_visible, the term, path_commit or ONE store of pc.
+// `shade` == 2: the lanes whose path wants a Sun-shadow query keep the step's sun_term and pathColor, start that query (k_trace's take_query
+// for a shadow entry: origin = the hit, direction = the Sun) while the others stand in state DONE, the wave walks them as one packet that
+// stops at the first accepted hit, and each hands its registers to shadow_retire ("the path ends here" = the step's !go_on).
 // Nothing goes to shadow_queue and sun[slot] is not written. Such a packet holds only the shadow lanes of its own 64 slots (none on sky),
 // where k_trace's packets are 64 dense entries: a separate level of the knob because of that.
 // The launch bound: without it the shading code takes the kernel to 111 VGPRs and 4 waves per SIMD, which costs every level of the knob
-// 1-3.5 % of a pass (the other pass lanes' kernels share the CUs); with it 96 VGPRs and 40 bytes of scratch, path state parked across the
+// 1-3.5 % of a pass (the other pass lanes' kernels share the CUs); with it 96 VGPRs and 28 bytes of scratch, path state parked across the
 // walks once per packet.
 __global__ void __launch_bounds__(BLOCK, GD_TRACE_WAVES) k_gen(Scene sc, Frame f, gpuart_params P, SeedBatch seeds, int j, int npaths, PathBuffers b,
                                                float4 *accum, uint4 *spill, uint32_t chunk, int walk, int shade) {
@@ -480,6 +532,12 @@ __global__ void __launch_bounds__(BLOCK, GD_TRACE_WAVES) k_gen(Scene sc, Frame f
             rounds = n_next = n_shadow = 0;
             bits_next = bits_shadow = 0;
         };
+        // the wave's queries as one packet, by the primitive types of the tree (`any_hit`: this lane's query stops at the first accepted hit)
+        auto walk_packet = [&](const F3 &ro, const F3 &rd, const F3 &rdiv, Trav &t, bool any_hit) {
+            if (walk == (GD_FLAT_TYPES | GD_REF_ORDER)) trav_packet<GD_FLAT_TYPES | GD_REF_ORDER>(sc, ro, rd, rdiv, t, st, any_hit);
+            else if (walk == (GD_ROUND_TYPES | GD_REF_ORDER)) trav_packet<GD_ROUND_TYPES | GD_REF_ORDER>(sc, ro, rd, rdiv, t, st, any_hit);
+            else trav_packet<GD_ALL_TYPES | GD_REF_ORDER>(sc, ro, rd, rdiv, t, st, any_hit);
+        };
         for (;;) {
             bool served;
             const uint32_t slot = cur.take(~0ull, true, &b.counters[1], chunk, served);  // the next (up to) 64 slots of the chunk
@@ -491,46 +549,22 @@ __global__ void __launch_bounds__(BLOCK, GD_TRACE_WAVES) k_gen(Scene sc, Frame f
                 rdiv = f3(1 / rd.x, 1 / rd.y, 1 / rd.z);
                 trav_init<GD_BOXES_FAST>(sc, Ray{ro, rd}, rdiv, t, st, nullptr, false);
             }
-            if (walk == (GD_FLAT_TYPES | GD_REF_ORDER)) trav_packet<GD_FLAT_TYPES | GD_REF_ORDER>(sc, ro, rd, rdiv, t, st, false);
-            else if (walk == (GD_ROUND_TYPES | GD_REF_ORDER)) trav_packet<GD_ROUND_TYPES | GD_REF_ORDER>(sc, ro, rd, rdiv, t, st, false);
-            else trav_packet<GD_ALL_TYPES | GD_REF_ORDER>(sc, ro, rd, rdiv, t, st, false);
+            walk_packet(ro, rd, rdiv, t, false);
             if (!shade) {
                 if (query) b.hit[slot] = make_uint2(__float_as_uint(t.closest), t.hit_prim);
                 continue;
             }
-            // ---- segment 0 of the packet's paths: k_shade's body for seg == 0 on the register values
-            bool go_on = false, shadow = false;
-            F3 pathColor = f3(0, 0, 0), sun_term = f3(0, 0, 0);  // path_tracing.glsl:157
+            // ---- segment 0 of the packet's paths, on the register values (no segment bound: the host shades here only where k_shade(1) follows)
+            SegmentStep s = {false, false, f3(0, 0, 0)};
+            F3 pathColor = f3(0, 0, 0);  // path_tracing.glsl:157
             if (query) {
-                tile_cost_add(f, b, slot);
-                Ray r; r.o = ro; r.d = rd;
-                F3 cw = f3(1, 1, 1);  // path_tracing.glsl:156
-                F3 rstart = r.o, rdir = r.d;
-                const float4 seed = seeds.seed[slot_pass(b, slot)];
-                ShadeResult s = path_shade(sc, P, seed, 0, r, t.closest, t.hit_prim, rstart, rdir, cw, pathColor);
-                if (s.broke) {
-                    uint32_t lx, ly; F3 rs0, rd0;  // (recomputed: cheaper than keeping the camera direction alive across the walk)
-                    slot_pixel(f, slot_pixel_slot(b, slot), lx, ly);
-                    camera_ray(f, f.x0 + lx, frame_y(f, ly), rs0, rd0);
-                    path_commit(f, b, accum, slot, j, npaths, path_finish(P, rd0, 0, s.ush, s.specular, pathColor));
-                } else {
-                    go_on = s.next == PATH_CONTINUES;  // (k_shade's `seg + 1 < nseg` holds: the host shades here only where k_shade(1) follows)
-                    shadow = s.want_shadow && s.sun_matters;
-                    const bool queued = shadow && shade < 2;  // the Sun-shadow query goes to k_trace
-                    if (queued)
-                        b.sun[slot] = make_float4(s.sun_term.x, s.sun_term.y, s.sun_term.z, __uint_as_float(go_on ? 0u : 1u));
-                    if (go_on || queued) b.ray_o[slot] = make_float4(rstart.x, rstart.y, rstart.z, 0);
-                    if (go_on) {
-                        b.ray_d[slot] = make_float4(rdir.x, rdir.y, rdir.z, 0);
-                        b.cw[slot] = make_float4(cw.x, cw.y, cw.z, 0);
-                    }
-                    if (shadow ? queued : go_on) b.pc[slot] = make_float4(pathColor.x, pathColor.y, pathColor.z, 0);
-                    if (!go_on && !shadow) path_commit(f, b, accum, slot, j, npaths, pathColor);
-                    ro = rstart;
-                    sun_term = s.sun_term;
-                }
+                F3 cw = f3(1, 1, 1), rstart, rdir;  // path_tracing.glsl:156
+                s = segment_shade<false, false>(sc, f, P, seeds, b, accum, slot, j, npaths, 0, 0, ro, rd, t.closest, t.hit_prim, rstart, rdir, cw, pathColor);
+                segment_store(b, slot, s, shade < 2, 0u, rstart, rdir, cw, pathColor);
+                ro = rstart;
             }
-            // ---- the Sun-shadow queries of these hits, walked here as one packet and retired as k_trace retires them
+            bool shadow = s.shadow;  // this lane's slot goes to shadow_queue
+            // ---- the Sun-shadow queries of these hits, walked here as one packet from the registers
             if (shade >= 2) {
                 t.state = TRAV_DONE;
                 if (shadow) {  // (k_trace's take_query for a shadow entry)
@@ -539,17 +573,12 @@ __global__ void __launch_bounds__(BLOCK, GD_TRACE_WAVES) k_gen(Scene sc, Frame f
                     trav_init<GD_BOXES_FAST>(sc, Ray{ro, rd}, rdiv, t, st, nullptr, false);
                 }
                 if (__ballot(shadow)) {
-                    if (walk == (GD_FLAT_TYPES | GD_REF_ORDER)) trav_packet<GD_FLAT_TYPES | GD_REF_ORDER>(sc, ro, rd, rdiv, t, st, shadow);
-                    else if (walk == (GD_ROUND_TYPES | GD_REF_ORDER)) trav_packet<GD_ROUND_TYPES | GD_REF_ORDER>(sc, ro, rd, rdiv, t, st, shadow);
-                    else trav_packet<GD_ALL_TYPES | GD_REF_ORDER>(sc, ro, rd, rdiv, t, st, shadow);
-                    if (shadow) {
-                        if (sun_visible(P, ro, sun, t.hit_prim)) pathColor = pathColor + sun_term;
-                        if (!go_on) path_commit(f, b, accum, slot, j, npaths, pathColor);
-                        else b.pc[slot] = make_float4(pathColor.x, pathColor.y, pathColor.z, 0);
-                    }
+                    walk_packet(ro, rd, rdiv, t, shadow);
+                    if (shadow) shadow_retire(f, P, b, accum, slot, j, npaths, ro, sun, t.hit_prim, pathColor, s.sun_term, !s.go_on);
                     shadow = false;
                 }
             }
+            const bool go_on = s.go_on;
             if (lane_id() == 0) stage_first[rounds] = slot;
             const unsigned long long m1 = __ballot(go_on), m2 = __ballot(shadow);
             if (go_on) bits_next |= 1u << rounds;
@@ -767,11 +796,8 @@ k_trace(Scene sc, Frame f, gpuart_params P, PathBuffers b, int seg_c, int seg_s,
             if (!shadow) {
                 b.hit[slot] = make_uint2(__float_as_uint(t.closest), t.hit_prim);
             } else {
-                float4 term = b.sun[slot];
-                F3 pathColor = xyz(b.pc[slot]);
-                if (sun_visible(P, ro, sun, t.hit_prim)) pathColor = pathColor + xyz(term);
-                if (__float_as_uint(term.w) & 1u) path_commit(f, b, accum, slot, j, npaths, pathColor);
-                else b.pc[slot] = make_float4(pathColor.x, pathColor.y, pathColor.z, 0);
+                const float4 term = b.sun[slot];
+                shadow_retire(f, P, b, accum, slot, j, npaths, ro, sun, t.hit_prim, xyz(b.pc[slot]), xyz(term), (__float_as_uint(term.w) & 1u) != 0);
             }
         }
         if (slot != SLOT_INVALID && t.state == TRAV_DONE) slot = SLOT_INVALID;
@@ -806,38 +832,17 @@ __global__ void __launch_bounds__(BLOCK) k_shade(Scene sc, Frame f, gpuart_param
       for (uint32_t k = 0; k < SHADE_ROUNDS; k++) {
         uint32_t e = sp * span + k * BLOCK + threadIdx.x;
         uint32_t slot = e < n ? queue[e] : SLOT_INVALID;
-        bool go_on = false, shadow = false;
+        SegmentStep s = {false, false, f3(0, 0, 0)};
         if (slot != SLOT_INVALID) {
-            tile_cost_add(f, b, slot);
-            Ray r; r.o = xyz(b.ray_o[slot]); r.d = xyz(b.ray_d[slot]);
-            uint2 h = b.hit[slot];
-            F3 cw = f3(1, 1, 1), pathColor = f3(0, 0, 0);  // path_tracing.glsl:156-157
+            const F3 ro = xyz(b.ray_o[slot]), rd = xyz(b.ray_d[slot]);
+            const uint2 h = b.hit[slot];
+            F3 cw = f3(1, 1, 1), pathColor = f3(0, 0, 0), rstart, rdir;  // path_tracing.glsl:156-157
             if (seg > 0) { cw = xyz(b.cw[slot]); pathColor = xyz(b.pc[slot]); }
-            F3 rstart = r.o, rdir = r.d;
             segments++;
-            const float4 seed = seeds.seed[slot_pass(b, slot)];
-            ShadeResult s = path_shade(sc, P, seed, seg, r, __uint_as_float(h.x), h.y, rstart, rdir, cw, pathColor);
-            if (s.broke) {
-                uint32_t lx, ly; F3 rs0, rd0;
-                slot_pixel(f, slot_pixel_slot(b, slot), lx, ly);
-                camera_ray(f, f.x0 + lx, frame_y(f, ly), rs0, rd0);
-                path_commit(f, b, accum, slot, j, npaths, path_finish(P, rd0, seg, s.ush, s.specular, pathColor));
-            } else {
-                // `seg + 1 < nseg` can only fail if the host's segment bound were too small: such a path is committed
-                // here instead of being queued for a launch that will not come (it would keep a stale colour)
-                go_on = s.next == PATH_CONTINUES && seg + 1 < nseg;
-                shadow = s.want_shadow && (REFWORK || s.sun_matters);
-                if (shadow)
-                    b.sun[slot] = make_float4(s.sun_term.x, s.sun_term.y, s.sun_term.z, __uint_as_float(go_on ? 0u : 1u));
-                if (go_on || shadow) b.ray_o[slot] = make_float4(rstart.x, rstart.y, rstart.z, 0);
-                if (go_on) {
-                    b.ray_d[slot] = make_float4(rdir.x, rdir.y, rdir.z, 0);
-                    b.cw[slot] = make_float4(cw.x, cw.y, cw.z, 0);
-                }
-                if (go_on || shadow) b.pc[slot] = make_float4(pathColor.x, pathColor.y, pathColor.z, 0);
-                if (!go_on && !shadow) path_commit(f, b, accum, slot, j, npaths, pathColor);  // i >= 1: no special case
-            }
+            s = segment_shade<REFWORK, true>(sc, f, P, seeds, b, accum, slot, j, npaths, seg, nseg, ro, rd, __uint_as_float(h.x), h.y, rstart, rdir, cw, pathColor);
+            segment_store(b, slot, s, true, 0u, rstart, rdir, cw, pathColor);
         }
+        const bool go_on = s.go_on, shadow = s.shadow;
         unsigned long long m1 = __ballot(go_on), m2 = __ballot(shadow);
         unsigned long long below = (1ull << lane_id()) - 1;
         if (go_on) stage_next[n_next + (uint32_t)__popcll(m1 & below)] = slot;
