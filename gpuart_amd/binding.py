@@ -499,6 +499,29 @@ def tree_class(quads):
     return dict(irregular=bool(flags.value & 1), disorderly=bool(flags.value & 2), type_mask=(flags.value >> 8) & 15)
 
 
+def convert_tree(quads, nquads=None, threads=1, top_depth=0):
+    """The arrays the uploader would put on the device for a compiled tree (gpuart_hip_test_convert: its own Converter::convert, no device):
+    dict(recs (R, 4, 4) float32, prims (P, 3, 4) float32, root_min, root_max (3,) float32, root_ref, num_nodes, max_depth, type_mask, irregular,
+    disorderly, subnormal). nquads: how many of the quads the library is told of (default: all). A rejected tree raises HipError with the
+    uploader's message."""
+    L = hip_lib()
+    q = np.ascontiguousarray(quads, np.float32)
+    nq = C.c_size_t(q.size // 4 if nquads is None else int(nquads))
+    assert nq.value <= q.size // 4
+    info, box = (C.c_uint32 * 8)(), (C.c_float * 6)()
+    rc = L.gpuart_hip_test_convert(_p(q), nq, C.c_uint32(threads), C.c_uint32(top_depth), None, C.c_size_t(0), None, C.c_size_t(0), info, box)
+    if rc != 0:
+        raise HipError("gpuart_hip error %d: %s" % (rc, L.gpuart_hip_last_error().decode()))
+    recs, prims = np.empty((info[0], 4, 4), np.float32), np.empty((info[1], 3, 4), np.float32)
+    rc = L.gpuart_hip_test_convert(_p(q), nq, C.c_uint32(threads), C.c_uint32(top_depth), _p(recs), C.c_size_t(info[0]), _p(prims),
+                                   C.c_size_t(info[1]), info, box)
+    if rc != 0:
+        raise HipError("gpuart_hip error %d: %s" % (rc, L.gpuart_hip_last_error().decode()))
+    return dict(recs=recs, prims=prims, root_min=np.array(box[0:3], np.float32), root_max=np.array(box[3:6], np.float32), root_ref=int(info[2]),
+                num_nodes=int(info[3]), max_depth=int(info[4]), type_mask=int(info[5]), irregular=bool(info[6] & 1), disorderly=bool(info[6] & 2),
+                subnormal=bool(info[6] & 4))
+
+
 KERNEL_ENTRIES = ("direct", "run", "trace", "query")   # gpuart_hip_test_kernel_choice's `entry`
 
 

@@ -110,7 +110,9 @@ struct Converter {
         // Coordinates beyond 2^20 (the hostile classes use 1e10 ... 1e30): the intersectors' own arithmetic cancels there — a
         // vertex at -1e30 swallows the ray origin in `origin - v0` — and a hit parameter that is off by more than the band says
         // nothing about the box it came from. (ulp(2^20) = 0.06: no scene a float path tracer renders sensibly is excluded.)
-        static const int LEN[4] = {4, 8, 12, 15};  // (a cone's derived constants 12..14 — width coefficient, cosB, dotAxC1 — included; pads excluded)
+        // (a cone's derived constants 12..14 — width coefficient, cosB, dotAxC1 — included; pads excluded: word 7 of a disc, word 15 of a cone,
+        // every fourth word of a triangle — the device never reads them, tests/test_converter.py)
+        static const int LEN[4] = {4, 7, 12, 15};
         for (int k = 0; k < LEN[type & 3]; k++)
             if (!(std::fabs(d[k]) <= 1048576.0f) && !(type == P_TRIANGLE && (k & 3) == 3)) return false;
         switch (type) {

@@ -6,8 +6,9 @@
 //           fetch of one 64-byte line serves two box tests:
 //             [4r]   = { lo.bbmin.xyz, bits(lo ref) }     ref = record index of an interior child, or
 //             [4r+1] = { lo.bbmax.xyz, bits(hi ref) }           bit31 | first primitive index of a leaf child
-//                                                               (| bit30 when the leaf is one or two triangles, | bit29 when two)
-//             [4r+2] = { hi.bbmin.xyz, 0 }
+//                                                               (| bit30 when the leaf is one or two triangles, | bit28 when it is one or two
+//                                                                primitives not all triangles, | bit29 when two: GD_REF_* below)
+//             [4r+2] = { hi.bbmin.xyz, mark }                   mark = 1 above level GPUART_HIP_TOP_DEPTH (counters only), else 0
 //             [4r+3] = { hi.bbmax.xyz, 0 }
 //           The root's own box and ref travel in the Scene struct.
 //   prims : float4[3*P], fixed 48-byte records, primitive p at [3p..3p+2]:

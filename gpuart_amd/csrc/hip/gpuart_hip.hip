@@ -1894,6 +1894,29 @@ int gpuart_hip_test_tree_slack(const float *quads, size_t nquads, float *slack) 
     }
 }
 
+int gpuart_hip_test_convert(const float *quads, size_t nquads, uint32_t threads, uint32_t top_depth, float *recs, size_t recs_cap,
+                            float *prims, size_t prims_cap, uint32_t info[8], float root_box[6]) {
+    if (!quads || !nquads || !info || !root_box || (!recs && recs_cap) || (!prims && prims_cap)) return fail(GPUART_HIP_ERR_ARG, "bad argument");
+    try {
+        Converter cv;
+        cv.q = quads; cv.nq = nquads;
+        cv.top_depth = top_depth;
+        Converter::Child root;
+        if (!cv.convert(root, std::min(64u, std::max(1u, threads)))) return fail(GPUART_HIP_ERR_ARG, "malformed compiled BVH: " + cv.err);
+        const size_t n_recs = cv.recs.size() / 4, n_prims = cv.prims.size() / 3;
+        if ((recs || prims) && (recs_cap < n_recs || prims_cap < n_prims)) return fail(GPUART_HIP_ERR_ARG, "convert: the arrays do not fit");
+        if (recs && n_recs) memcpy(recs, cv.recs.data(), n_recs * 64);
+        if (prims && n_prims) memcpy(prims, cv.prims.data(), n_prims * 48);
+        info[0] = (uint32_t)n_recs; info[1] = (uint32_t)n_prims; info[2] = root.ref; info[3] = (uint32_t)cv.num_nodes;
+        info[4] = cv.max_depth; info[5] = cv.type_mask;
+        info[6] = (cv.irregular ? 1u : 0u) | (cv.disorderly ? 2u : 0u) | (cv.subnormal ? 4u : 0u); info[7] = 0;
+        memcpy(root_box, root.bmin, 12); memcpy(root_box + 3, root.bmax, 12);
+        return 0;
+    } catch (const std::exception &e) {
+        return fail(GPUART_HIP_ERR_ARG, std::string("tree: ") + e.what());
+    }
+}
+
 // ---- kernel choice hook: the rule the launch sites take their instantiation from, asked without a device
 int gpuart_hip_test_kernel_choice(uint32_t type_mask, uint32_t exact_boxes, uint32_t ref_order, uint32_t lean_kernels, int mode, int entry,
                                   uint32_t choice[3]) {

@@ -65,6 +65,16 @@ int gpuart_hip_test_tree_class(const float *quads, size_t nquads, uint32_t *flag
  * for a tree with bit 0, 1 or 2 of gpuart_hip_test_tree_class set (and, on a context, with GPUART_HIP_QUICK_BOXES=0). Pure host code. */
 int gpuart_hip_test_tree_slack(const float *quads, size_t nquads, float *slack);
 
+/* The arrays gpuart_hip_upload_bvh would put on the device for a canonical compiled tree (pure host code: the upload's own
+ * Converter::convert, needs no device and no context), with the fill pass on `threads` threads (1..64: GPUART_HIP_UPLOAD_THREADS) and
+ * the records of nodes above level `top_depth` marked (GPUART_HIP_TOP_DEPTH). info[8] = { records, primitives, the root's ref,
+ * canonical nodes, deepest level, type mask, bit 0 irregular | bit 1 disorderly | bit 2 subnormal (gpuart_hip_test_tree_class), 0 };
+ * root_box[6] = the root's min and max. recs == NULL and prims == NULL asks for info and root_box alone; otherwise recs (recs_cap
+ * records of 64 bytes) and prims (prims_cap records of 48 bytes) receive the arrays, GPUART_HIP_ERR_ARG if they do not fit. A malformed
+ * tree: GPUART_HIP_ERR_ARG, nothing is written, gpuart_hip_last_error says why. */
+int gpuart_hip_test_convert(const float *quads, size_t nquads, uint32_t threads, uint32_t top_depth, float *recs, size_t recs_cap,
+                            float *prims, size_t prims_cap, uint32_t info[8], float root_box[6]);
+
 /* The validation every rank of gpuart_hip_gather applies to the exchanged share table (pure host code): `shares[k]` and
  * `status[k]` (0: ready) as rank k announced them. 0 if the gather would go ahead — full-width rows, every frame row covered
  * exactly once, every rank ready — else the error code it would return on every rank (gpuart_hip_last_error says why). */

@@ -34,6 +34,7 @@ def test_c_abi_exports_every_declared_symbol():
     product = os.path.join(ROOT, "gpuart_amd", "lib", "libgpuart_hip.so")
     names, hooks = _declared("gpuart_hip.h"), [n for n in _declared("gpuart_hip_test.h") if n.startswith("gpuart_hip_test_")]
     assert len(names) >= 25 and len(hooks) >= 15 and not [n for n in names if "_test_" in n]
+    assert "gpuart_hip_test_convert" in hooks and len(hooks) >= 22
     assert _exported(product) == names, (sorted(set(_exported(product)) - set(names)), sorted(set(names) - set(_exported(product))))
     L = C.CDLL(product)
     for n in names:
