@@ -134,6 +134,27 @@ def edges_params(params):
     return _params(EdgesParams, EDGES_DEFAULTS, "edge-resolve", params)
 
 
+class DespeckleParams(C.Structure):
+    """gpuart_despeckle_params (include/gpuart_despeckle.h)."""
+    _fields_ = [("radius", C.c_uint32), ("rank", C.c_uint32), ("k", C.c_float), ("floor", C.c_float), ("min_count", C.c_uint32)]
+
+
+DESPECKLE_DEFAULTS = dict(radius=1, rank=3, k=2.0, floor=1e-3, min_count=4)
+
+
+def despeckle_params(params):
+    """None (the library's defaults), a DespeckleParams, or a dict of fields that replace the defaults -> DespeckleParams or None."""
+    return _params(DespeckleParams, DESPECKLE_DEFAULTS, "firefly-clamp", params)
+
+
+class DespeckleSummary(C.Structure):
+    """gpuart_despeckle_summary (include/gpuart_despeckle.h): the counts of a handle's last run."""
+    _fields_ = [("surface", C.c_uint64), ("clamped", C.c_uint64), ("too_few", C.c_uint64)]
+
+    def as_dict(self):
+        return dict(surface=int(self.surface), clamped=int(self.clamped), too_few=int(self.too_few))
+
+
 class DisplayParams(C.Structure):
     """gpuart_display_params (include/gpuart_display.h)."""
     _fields_ = [("gain", C.c_float), ("auto_exposure", C.c_uint32), ("key", C.c_float), ("lo_share", C.c_float), ("hi_share", C.c_float),
@@ -317,6 +338,11 @@ def antilag_lib():
 def edges_lib():
     """libgpuart_edges.so; raises NativeLibraryMissing if it has not been built (no fallback)."""
     return _image_lib("edges")
+
+
+def despeckle_lib():
+    """libgpuart_despeckle.so; raises NativeLibraryMissing if it has not been built (no fallback)."""
+    return _image_lib("despeckle")
 
 
 def display_lib():
@@ -1171,6 +1197,26 @@ class Renderer:
 
     def get_edge_resolve(self): return bool(self.L.gpuart_renderer_get_edge_resolve(self.h))
 
+    def set_firefly_clamp(self, on=True, params=None):
+        """Renderer::SetFireflyClamp: while on, the view every filtered read (read_denoised, read_preview, read_guided_preview,
+        read_refined, and read_display of them) and every temporal commit stages is clamped in place first
+        (include/gpuart_despeckle.h); read_radiance, the accumulator and the estimates never see a clamped value. Biased: it removes
+        energy. Changing the switch or its parameters drops the temporal history. params = None (the defaults), a DespeckleParams or a
+        dict of fields that replace the defaults."""
+        p = despeckle_params(params)
+        if not self.L.gpuart_renderer_set_firefly_clamp(self.h, C.c_int(1 if on else 0), C.byref(p) if p is not None else None):
+            raise ValueError("firefly-clamp parameters out of range")
+
+    def get_firefly_clamp(self): return bool(self.L.gpuart_renderer_get_firefly_clamp(self.h))
+
+    def firefly_summary(self):
+        """Renderer::ReadFireflySummary: the counts of the last clamp a read or a commit ran, as a dict (DespeckleSummary.as_dict); None
+        before the first."""
+        s = DespeckleSummary()
+        if not self.L.gpuart_renderer_read_firefly_summary(self.h, C.byref(s)):
+            return None
+        return s.as_dict()
+
     def read_guided_preview(self, lum_floor=CONVERGE_DEFAULT_FLOOR, refine=None, temporal=None):
         """Renderer::ReadGuidedPreview: the history blended with the accumulator, then filtered by the variance-guided filter with the
         error map of the history's measured variance, (th, tw, 4) float32. refine as Refine.run's params; temporal as
@@ -1754,6 +1800,51 @@ class Display(_ImageHandle):
     @staticmethod
     def srgb_table():
         return srgb_table()
+
+
+# ---- the firefly clamp (include/gpuart_despeckle.h) ------------------------------------------------------------------------------
+class DespeckleError(RuntimeError):
+    """A gpuart_despeckle_* call returned an error; `code` is the library's (GPUART_HIP_ERR_*)."""
+    code = None
+
+
+class Despeckle(_ImageHandle):
+    """A gpuart_despeckle handle on one device: it keeps the counts of its last run."""
+    NAME, Error = "despeckle", DespeckleError
+
+    def run(self, rgba, hits, prims, us_flags=0, params=None, out=None, want_scale=False):
+        """gpuart_despeckle_run: clamps radiance rgba (h, w, 4) float32 by its G-buffer (hits, prims, us_flags as Denoiser.run), torch
+        tensors on this handle's device (torch's current stream is synchronised first, the handle before returning). out = None (a new
+        tensor), a tensor of rgba's shape, or rgba itself (in place). params = None (the defaults), a DespeckleParams or a dict of
+        fields that replace the defaults. -> out, or with want_scale (out, scale (h, w) float32: s where clamped, 1 elsewhere)."""
+        import torch
+        p = despeckle_params(params)
+        dev, rgba, hits, prims, res, h, w = _gbuffer_args(self.device, rgba, hits, prims, out)
+        if dev is None:
+            raise ValueError("run takes torch tensors on cuda:%d; NumPy arrays go through run_host" % self.device)
+        scale = torch.empty((h, w), dtype=torch.float32, device=dev) if want_scale else None
+        torch.cuda.current_stream(dev).synchronize()
+        self._chk(self._fn("run")(self.h, _dp(rgba), _dp(hits), _dp(prims), C.c_uint32(us_flags), C.c_uint32(w), C.c_uint32(h),
+                                  C.byref(p) if p is not None else None, _dp(res), _dp(scale) if want_scale else None))
+        self.finish()
+        return (res, scale) if want_scale else res
+
+    def run_host(self, rgba, hits, prims, us_flags=0, params=None, out=None, want_scale=False):
+        """gpuart_despeckle_run_host: the same for NumPy arrays, staged through the handle's memory; the result is `out` or a new array."""
+        p = despeckle_params(params)
+        dev, rgba, hits, prims, res, h, w = _gbuffer_args(self.device, rgba, hits, prims, out)
+        if dev is not None:
+            raise ValueError("run_host takes NumPy arrays; torch tensors go through run")
+        scale = np.empty((h, w), np.float32) if want_scale else None
+        self._chk(self._fn("run_host")(self.h, _p(rgba), _p(hits), _p(prims), C.c_uint32(us_flags), C.c_uint32(w), C.c_uint32(h),
+                                       C.byref(p) if p is not None else None, _p(res), _p(scale) if want_scale else None))
+        return (res, scale) if want_scale else res
+
+    def summary(self):
+        """gpuart_despeckle_read_summary as a dict: surface, clamped, too_few of the last run."""
+        s = DespeckleSummary()
+        self._chk(self._fn("read_summary")(self.h, C.byref(s)))
+        return s.as_dict()
 
 
 class ConvergeError(RuntimeError):

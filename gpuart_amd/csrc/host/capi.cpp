@@ -295,6 +295,13 @@ int gpuart_renderer_set_edge_resolve(gpuart_renderer *r, int on, const gpuart_ed
     return r->impl.SetEdgeResolve(on != 0, p) ? 1 : 0;
 }
 int gpuart_renderer_get_edge_resolve(gpuart_renderer *r) { return r->impl.GetEdgeResolve() ? 1 : 0; }
+int gpuart_renderer_set_firefly_clamp(gpuart_renderer *r, int on, const gpuart_despeckle_params *p) {
+    return r->impl.SetFireflyClamp(on != 0, p) ? 1 : 0;
+}
+int gpuart_renderer_get_firefly_clamp(gpuart_renderer *r) { return r->impl.GetFireflyClamp() ? 1 : 0; }
+int gpuart_renderer_read_firefly_summary(gpuart_renderer *r, gpuart_despeckle_summary *out) {
+    return r->impl.ReadFireflySummary(out) ? 1 : 0;
+}
 int gpuart_renderer_read_guided_preview(gpuart_renderer *r, float *rgba, float lumFloor, const gpuart_refine_params *rf,
                                         const gpuart_temporal_params *tp) {
     return r->impl.ReadGuidedPreview(rgba, lumFloor, rf, tp) ? 1 : 0;

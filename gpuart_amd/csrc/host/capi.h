@@ -10,6 +10,7 @@
 #include "gpuart_antilag.h"
 #include "gpuart_converge.h"
 #include "gpuart_denoise.h"
+#include "gpuart_despeckle.h"
 #include "gpuart_display.h"
 #include "gpuart_edges.h"
 #include "gpuart_hip.h"
@@ -123,6 +124,13 @@ int gpuart_renderer_set_history_antilag(gpuart_renderer *r, int on, const gpuart
  * gpuart_renderer_get_edge_resolve: 1 while on. */
 int gpuart_renderer_set_edge_resolve(gpuart_renderer *r, int on, const gpuart_edges_params *p);
 int gpuart_renderer_get_edge_resolve(gpuart_renderer *r);
+/* Renderer::SetFireflyClamp: the view every filtered read and every temporal commit stages is clamped in place first
+ * (include/gpuart_despeckle.h); changing the switch or its parameters drops the temporal history. p = NULL: the defaults. 1 on success,
+ * 0 for parameters out of range. gpuart_renderer_get_firefly_clamp: 1 while on. gpuart_renderer_read_firefly_summary: the counts of the
+ * last clamp that ran; 0 before the first. */
+int gpuart_renderer_set_firefly_clamp(gpuart_renderer *r, int on, const gpuart_despeckle_params *p);
+int gpuart_renderer_get_firefly_clamp(gpuart_renderer *r);
+int gpuart_renderer_read_firefly_summary(gpuart_renderer *r, gpuart_despeckle_summary *out);
 /* Renderer::ReadGuidedPreview: the history blend filtered by gpuart_refine_run with the error map of the history's measured variance.
  * rf, tp = NULL: the defaults / what gpuart_renderer_set_temporal_history was given. 1 on success; 0 while the variance or the
  * history is off, before the view's first path, or on error. */

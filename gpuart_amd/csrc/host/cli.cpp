@@ -26,7 +26,8 @@ static void usage() {
                  "                  [--camera px,py,pz] [--sun az,alt[,off]] [--user-sphere x,y,z,r,em[,specular[,fuzzy]]]\n"
                  "                  [--device D] [--gpus N] [--resume ck] [--checkpoint ck] [--pfm out.pfm] [--ppm out.ppm] [--nearest-first]\n"
                  "                  [--adaptive T [--adaptive-min N] [--until-batch N] [--until-floor F] [--samples-pfm out.pfm] [--refine]]\n"
-                 "                  [--denoise] [--edge-resolve] [--until T [--until-share S] [--until-floor F] [--until-batch N] [--error-pfm out.pfm] [--refine]]\n"
+                 "                  [--denoise] [--edge-resolve] [--firefly-clamp [--firefly-k K] [--firefly-rank R]]\n"
+                 "                  [--until T [--until-share S] [--until-floor F] [--until-batch N] [--error-pfm out.pfm] [--refine]]\n"
                  "                  [--display out.ppm [--tonemap clamp|reinhard|aces] [--white W] [--exposure-ev E] [--auto-exposure] [--key K]\n"
                  "                   [--srgb] [--dither]]\n"
                  "  --until T: render until the relative standard error of every pixel's luminance is at most T (Renderer::RenderUntil; path\n"
@@ -49,6 +50,9 @@ static void usage() {
                  "  --denoise: write the denoised preview of the frame (Renderer::ReadDenoised; path tracing on one GPU)\n"
                  "  --edge-resolve: with --denoise or --refine, resolve geometric edges in the filtered frame from a sub-pixel G-buffer\n"
                  "             (Renderer::SetEdgeResolve, include/gpuart_edges.h, its defaults)\n"
+                 "  --firefly-clamp: with --denoise or --refine, clamp fireflies ahead of the filter (Renderer::SetFireflyClamp,\n"
+                 "             include/gpuart_despeckle.h; biased: it removes energy); --firefly-k K: the cap's factor (default 2);\n"
+                 "             --firefly-rank R: which of the largest neighbours the cap stands on (1..4, default 3). One GPU only\n"
                  "  --nearest-first: opt in to the nearer-child-first BVH walk (~10 % faster; soak-verified, not proven to be the reference's image)\n"
                  "  --gpus N: path tracing of ONE frame on devices D..D+N-1 (8-row bands dealt round-robin, gathered over RCCL)\n";
 }
@@ -68,7 +72,9 @@ int main(int argc, char **argv) {
     std::string scene = "box", mode = "pt", pfm, ppm, resume, checkpoint;
     unsigned W = 640, H = 480, spp = 16, perPass = 1, maxSeg = 5, device = 0, gpus = 1;
     long seed = -1;
-    bool nearestFirst = false, denoise = false, refine = false, edgeResolve = false;
+    bool nearestFirst = false, denoise = false, refine = false, edgeResolve = false, fireflyClamp = false, haveFireflyOption = false;
+    gpuart_despeckle_params firefly;
+    gpuart_despeckle_defaults(&firefly);
     std::string errorPfm;
     float until = -1, untilShare = 0, untilFloor = 1.0f / 256;
     unsigned untilBatch = GPUART_CONVERGE_DEFAULT_BATCH;
@@ -110,6 +116,9 @@ int main(int argc, char **argv) {
         else if (a == "--denoise") denoise = true;
         else if (a == "--refine") refine = true;
         else if (a == "--edge-resolve") edgeResolve = true;
+        else if (a == "--firefly-clamp") fireflyClamp = true;
+        else if (a == "--firefly-k") { firefly.k = strtof(need("--firefly-k"), nullptr); haveFireflyOption = true; }
+        else if (a == "--firefly-rank") { firefly.rank = (uint32_t)strtoul(need("--firefly-rank"), nullptr, 10); haveFireflyOption = true; }
         else if (a == "--until") { until = strtof(need("--until"), nullptr); haveUntil = true; }
         else if (a == "--until-share") untilShare = strtof(need("--until-share"), nullptr);
         else if (a == "--until-floor") untilFloor = strtof(need("--until-floor"), nullptr);
@@ -156,6 +165,18 @@ int main(int argc, char **argv) {
     }
     if (edgeResolve && !denoise && !refine) {
         std::cerr << "gpuart_cli: --edge-resolve mends a filtered frame: give --denoise or --refine\n";
+        return 2;
+    }
+    if (haveFireflyOption && !fireflyClamp) {
+        std::cerr << "gpuart_cli: --firefly-k and --firefly-rank shape --firefly-clamp: give --firefly-clamp\n";
+        return 2;
+    }
+    if (fireflyClamp && !denoise && !refine) {
+        std::cerr << "gpuart_cli: --firefly-clamp acts ahead of a filter: give --denoise or --refine\n";
+        return 2;
+    }
+    if (fireflyClamp && gpus > 1) {
+        std::cerr << "gpuart_cli: --firefly-clamp needs --gpus 1: the clamp is not in the frame gather\n";
         return 2;
     }
     if (refine && denoise) {
@@ -215,6 +236,7 @@ int main(int argc, char **argv) {
     }
     gpuart::Renderer &r = *rs[0];
     if (edgeResolve && !r.SetEdgeResolve(true)) return 1;
+    if (fireflyClamp && !r.SetFireflyClamp(true, &firefly)) return 1;
     if (nTile == 4 && !r.SetTile((unsigned)tile[0], (unsigned)tile[1], (unsigned)tile[2], (unsigned)tile[3])) return 1;
     const unsigned tw = gpus > 1 ? W : r.GetTileWidth(), th = gpus > 1 ? H : r.GetTileHeight();
 

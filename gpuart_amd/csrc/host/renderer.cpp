@@ -67,6 +67,7 @@ Renderer::Renderer(unsigned viewportWidth, unsigned viewportHeight, const Camera
     gpuart_moments_defaults(&MomentsParams);
     gpuart_antilag_defaults(&AntiLagParams);
     gpuart_edges_defaults(&EdgeParams);
+    gpuart_despeckle_defaults(&FireflyParams);
 
     if (!Check(gpuart_hip_create(device, &Backend), "creating the device back end")) return;
     if (viewportWidth == 0 || viewportHeight == 0) {
@@ -82,6 +83,7 @@ Renderer::~Renderer() {
     DisplayMem.Release();
     if (Refine) gpuart_refine_destroy(Refine);
     ErrorMem.Release();
+    if (Despeckle) gpuart_despeckle_destroy(Despeckle);
     if (Edges) gpuart_edges_destroy(Edges);
     EdgeSubMem.Release();
     EdgeMem.Release();
@@ -415,6 +417,7 @@ const Lib<gpuart_converge> CV{gpuart_converge_create, gpuart_converge_finish, gp
 const Lib<gpuart_adaptive> AD{gpuart_adaptive_create, gpuart_adaptive_finish, gpuart_adaptive_last_error, "creating the adaptive estimator"};
 const Lib<gpuart_refine> RF{gpuart_refine_create, gpuart_refine_finish, gpuart_refine_last_error, "creating the variance-guided filter"};
 const Lib<gpuart_edges> ED{gpuart_edges_create, gpuart_edges_finish, gpuart_edges_last_error, "creating the edge resolve's handle"};
+const Lib<gpuart_despeckle> DS{gpuart_despeckle_create, gpuart_despeckle_finish, gpuart_despeckle_last_error, "creating the firefly clamp's handle"};
 const Lib<gpuart_display> DP{gpuart_display_create, gpuart_display_finish, gpuart_display_last_error, "creating the display stage"};
 bool finite(float x) { return x - x == 0.0f; }
 bool checkHip(hipError_t e, const char *what) {
@@ -487,7 +490,38 @@ bool Renderer::StageView() {
         memcpy(GBufferSphere, us, sizeof us);
         GBufferValid = true;
     }
-    return ExportNormalized(b.radiance);
+    if (!ExportNormalized(b.radiance)) return false;
+    if (!FireflyOn) return true;
+    // in place: every filtered read and every commit takes the clamped frame; the accumulator stays what it is
+    return Ensure(Despeckle, DS) &&
+           Run(gpuart_despeckle_run(Despeckle, b.radiance, b.hits, b.prims, UserSphere.flags, Tile.w, Tile.h, &FireflyParams, b.radiance, nullptr),
+               Despeckle, DS, "clamping the fireflies");
+}
+
+// ---- the firefly clamp (include/gpuart_despeckle.h) -----------------------------------------------------------------------
+bool Renderer::SetFireflyClamp(bool on, const gpuart_despeckle_params *p) {
+    gpuart_despeckle_params v;
+    if (p) {
+        // the ranges gpuart_despeckle_run accepts: a commit inside a setter has nobody to report them to
+        if (p->radius < 1 || p->radius > 2 || p->rank < 1 || p->rank > 4 || !finite(p->k) || !(p->k >= 1) || !finite(p->floor) ||
+            !(p->floor >= 0) || p->min_count < 1 || p->min_count > 24) {
+            std::cerr << "Renderer: firefly-clamp parameters out of range." << std::endl;
+            return false;
+        }
+        v = *p;
+    } else {
+        gpuart_despeckle_defaults(&v);
+    }
+    // a history that has seen other inputs
+    if (on != FireflyOn || memcmp(&v, &FireflyParams, sizeof v) != 0) DropTemporalHistory();
+    FireflyParams = v;
+    FireflyOn = on;
+    return true;
+}
+
+bool Renderer::ReadFireflySummary(gpuart_despeckle_summary *out) {
+    return out && Despeckle && checkHip(hipSetDevice(Device), "hipSetDevice") &&
+           Check(gpuart_despeckle_read_summary(Despeckle, out), "reading the firefly clamp's summary", gpuart_despeckle_last_error);
 }
 
 bool Renderer::StageBlockPaths() {

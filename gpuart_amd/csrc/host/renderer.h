@@ -8,7 +8,8 @@
 // MAX_PATH_SEGMENTS / the RNG seed / the viewport fixed at compile time):
 //   ReadDirectLighting, ReadRadiance, Finish, SetMaxPathSegments, SetMinWeight, SetSeed,
 //   SetTile, GetBackend, ComputeScreenBasis, GetNumPathsRendered, ReadDenoised, SetTemporalHistory, ReadPreview, RenderUntil,
-//   ReadErrorMap, ReadRefined, SetHistoryVariance, SetHistoryAntiLag, ReadGuidedPreview, ReadDisplay, SetEdgeResolve.
+//   ReadErrorMap, ReadRefined, SetHistoryVariance, SetHistoryAntiLag, ReadGuidedPreview, ReadDisplay, SetEdgeResolve,
+//   SetFireflyClamp, ReadFireflySummary.
 #ifndef GPUART_RENDERER_H
 #define GPUART_RENDERER_H
 
@@ -22,6 +23,7 @@
 #include "gpuart_antilag.h"
 #include "gpuart_converge.h"
 #include "gpuart_denoise.h"
+#include "gpuart_despeckle.h"
 #include "gpuart_display.h"
 #include "gpuart_edges.h"
 #include "gpuart_hip.h"
@@ -143,6 +145,20 @@ public:
     /// read launches what it launched before the switch existed.
     bool SetEdgeResolve(bool on, const gpuart_edges_params *p = nullptr);
     bool GetEdgeResolve() const { return EdgeOn; }
+    /// Clamps fireflies ahead of the filters and the temporal history (include/gpuart_despeckle.h); off by default. While it is on, the
+    /// view every filtered read and every commit stages — the normalised accumulator with the view's cached G-buffer — is clamped in
+    /// place by gpuart_despeckle_run before anything reads it: ReadDenoised, ReadPreview, ReadGuidedPreview, ReadRefined and ReadDisplay
+    /// of them filter the clamped frame, and the commits of SetTemporalHistory (so also the moments' and the fast history's input) take
+    /// it. ReadRadiance, ReadDirectLighting, ReadDisplay(RADIANCE / DIRECT), the accumulator, the passes that follow, the counters and
+    /// timings, the convergence and adaptive estimates (they read the raw accumulator), the cached G-buffer and the edge list never see a
+    /// clamped value. The clamp is biased: it removes energy, and with a history that energy does not come back; ReadFireflySummary
+    /// says how many pixels it touched. Switching it on or off, or changing its parameters, drops the temporal history: the existing
+    /// one has seen other inputs. p = nullptr: the library's defaults. False for parameters out of range (nothing changes). With the
+    /// switch off every read launches what it launched before the switch existed.
+    bool SetFireflyClamp(bool on, const gpuart_despeckle_params *p = nullptr);
+    bool GetFireflyClamp() const { return FireflyOn; }
+    /// The counts of the last clamp a read or a commit ran (gpuart_despeckle_read_summary); false before the first.
+    bool ReadFireflySummary(gpuart_despeckle_summary *out);
     /// The preview guided by the history's measured variance: the radiance and the packed moments of the current accumulator are blended
     /// with their histories (gpuart_temporal_accumulate without commit; tp = nullptr: what SetTemporalHistory was given),
     /// gpuart_moments_error turns the two blends into an error map for lumFloor, and gpuart_refine_run (rf; nullptr: its defaults)
@@ -287,6 +303,9 @@ private:
     PixelBuffer EdgeSubMem;                   ///< a record (32 B) and an ordinal (4) per listed pixel and sub-sample
     bool EdgeListValid = false;               ///< EdgeMem's list and EdgeSubMem are those of the cached G-buffer for EdgeFlags
     uint32_t EdgeFlags = 0, EdgeCount = 0;
+    bool FireflyOn = false;                   ///< SetFireflyClamp: StageView ends in the clamp
+    gpuart_despeckle *Despeckle = nullptr;    ///< made by the first StageView while FireflyOn
+    gpuart_despeckle_params FireflyParams{};  ///< of the clamp (SetFireflyClamp)
     gpuart_converge *Converge = nullptr;  ///< made by the first RenderUntil
     unsigned ConvergeBatches = 0, ConvergeTotal = 0;  ///< what Converge has seen since its last reset
     gpuart_adaptive *Adaptive = nullptr;  ///< made by the first RenderAdaptive
