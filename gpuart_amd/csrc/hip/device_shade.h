@@ -18,6 +18,8 @@ struct Frame {
                                  ///< tile_order[k] (kernels_pipeline.h slot_pixel) — the order paths are BORN in; no pixel depends on it
     uint32_t *tile_cost;         ///< null, or per 8x8 block (row-major number) a counter: this run adds one per shaded path segment
                                  ///< (kernels_pipeline.h tile_cost_add; k_tile_order turns the counts into the next tile_order)
+    uint32_t block_order;        ///< the order of the 64 path slots of an 8x8 block (kernels_pipeline.h block_pixel): 0 — row-major, 1 — Z-order;
+                                 ///< like tile_order, the order paths are born in: no pixel depends on it
 };
 
 /// Frame row of local row `ly` of the tile.

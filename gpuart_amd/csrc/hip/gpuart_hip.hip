@@ -164,6 +164,12 @@ struct gpuart_hip_ctx {
                                   ///< k_gen walks the camera rays it generates and that launch is not made (launch_run); 0 — always the separate launch
     uint32_t gen_shade = 2;       ///< GPUART_HIP_GEN_SHADE (default 2): where k_gen walks and the run has a segment 1, 1 — k_gen also shades segment 0 of the paths it
                                   ///< walked and k_shade(0) is not launched; 2 — and walks their Sun-shadow queries as packets of its own; 0 — the separate launches
+    uint32_t shadow_pool = 1;     ///< GPUART_HIP_SHADOW_POOL (default 1): at GPUART_HIP_GEN_SHADE = 2, k_gen pools the Sun-shadow queries of its packets per wave and walks
+                                  ///< them 64 at a time (k_gen's `shade` = 3); 0 — each packet walks the shadow lanes of its own 64 slots
+    uint32_t pool_chunk = 256;    ///< GPUART_HIP_POOL_CHUNK (default 256): the slots k_gen takes from its cursor at a time where it pools; the pool is emptied at a chunk's end
+    uint32_t pool_min_passes = 8; ///< GPUART_HIP_POOL_MIN_PASSES (default 8): ... and it pools only in runs of at least this many passes
+    uint32_t block_order = 2;     ///< GPUART_HIP_BLOCK_ORDER (default 2): the order of the 64 path slots of an 8x8 block (Frame::block_order): 0 — row-major, 1 — Z-order,
+                                  ///< 2 — Z-order in the runs of the launch pipeline of at least 4 passes (a packet is at most 16 pixels, 4x2 at 8 passes), else row-major
     uint32_t exact_boxes = 0;     ///< the uploaded tree holds an irregular box, or a box that does not bound what it holds (converter.h):
                                   ///< box tests take the comparison form and every walk keeps the reference's order
     uint32_t max_depth = 0;
@@ -538,6 +544,11 @@ int gpuart_hip_create(int device, gpuart_hip_ctx **out) {
     c->packet_max_prims = env_u32("GPUART_HIP_PACKET_MAX_PRIMS", 1u << 19, 0, 0xffffffffu);
     c->gen_walk = env_u32("GPUART_HIP_GEN_WALK", 1, 0, 1);
     c->gen_shade = env_u32("GPUART_HIP_GEN_SHADE", 2, 0, 2);
+    c->shadow_pool = env_u32("GPUART_HIP_SHADOW_POOL", 1, 0, 1);
+    c->pool_chunk = env_u32("GPUART_HIP_POOL_CHUNK", 256, 16, 4096);
+    c->pool_min_passes = env_u32("GPUART_HIP_POOL_MIN_PASSES", 8, 1, MAX_BATCH);
+    c->block_order = env_u32("GPUART_HIP_BLOCK_ORDER", 2, 0, 2);
+    c->frame.block_order = c->block_order == 1 ? 1u : 0u;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return fail(GPUART_HIP_ERR_DEVICE, "hipStreamCreate failed"); }
     c->lanes.resize(env_u32("GPUART_HIP_PASSES_IN_FLIGHT", 8, 1, 32));
     c->plan.lanes_total = (uint32_t)c->lanes.size();
@@ -913,6 +924,9 @@ int launch_run(gpuart_hip_ctx *c, size_t first, size_t count) {
     Frame fr;
     bool gathers;
     if ((r = run_frame(c, fr, gathers, false))) return r;  // (an order set through gpuart_hip_test_tile_order applies here too)
+    // by the run: from 4 passes on a packet holds at most 16 pixels, a strip of one or two rows in row-major order; the 21 1/3 pixels of 3 passes
+    // are 8 x 3 there, and cut a Z-curve badly (1 and 2 passes: the whole or half block in either order)
+    if (c->block_order == 2) fr.block_order = count >= 4 ? 1u : 0u;
     if (l.used) HIP_TRY(hipStreamWaitEvent(l.main, l.ev_free, 0));  // the lane's previous pass has been accumulated
     if ((r = begin_timed(c, t, 0, l.main))) return r;
     // packet walks (GPUART_HIP_PACKET; the GD_REF_ORDER kernels only): the camera rays' launch, the Sun-shadow queries of segment 0
@@ -924,7 +938,11 @@ int launch_run(gpuart_hip_ctx *c, size_t first, size_t count) {
                           (nseg >= 2 || p->sunEnabled == 1);
     // ... and shades segment 0 of what it walked (GPUART_HIP_GEN_SHADE) where k_shade(1) follows; at level 2 it walks segment 0's Sun-shadow queries too
     const int gen_shade = gen_walk && nseg >= 2 ? (int)c->gen_shade : 0;
-    const dim3 wgrid(std::max<uint32_t>(1u, std::min<uint32_t>(c->grid_waves, (b.n_slots * b.batch + c->tune.chunk - 1) / c->tune.chunk)));  // (l.spill_main holds grid_waves columns at least)
+    // ... pooled per wave into full packets (GPUART_HIP_SHADOW_POOL): k_gen's level 3, which takes longer chunks (a chunk's end empties the pool).
+    // By the run: at 3 passes per run the pool saves few packet steps and parking the queries costs more.
+    const int gen_level = gen_shade == 2 && c->shadow_pool && count >= c->pool_min_passes ? 3 : gen_shade;
+    const uint32_t gen_chunk = gen_level == 3 ? c->pool_chunk : c->tune.chunk;
+    const dim3 wgrid(std::max<uint32_t>(1u, std::min<uint32_t>(c->grid_waves, (b.n_slots * b.batch + gen_chunk - 1) / gen_chunk)));  // (l.spill_main holds grid_waves columns at least)
     // one BVH-query launch: closest-hit queries of segment seg_c and / or Sun-shadow queries of segment seg_s
     auto trace = [&](int seg_c, int seg_s) -> int {
         TimedLaunch tt;
@@ -948,7 +966,7 @@ int launch_run(gpuart_hip_ctx *c, size_t first, size_t count) {
         if (gen_walk) {  // in the per-launch bracket the camera rays' launch had
             TimedLaunch tt;
             if (detail && (r = begin_timed(c, tt, 1, l.main))) return r;
-            k_gen<<<wgrid, BLOCK, 0, l.main>>>(sc, fr, *p, seeds, j, npaths, b, l.passcolor, l.spill_main, c->tune.chunk, trace_choice, gen_shade);
+            k_gen<<<wgrid, BLOCK, 0, l.main>>>(sc, fr, *p, seeds, j, npaths, b, l.passcolor, l.spill_main, gen_chunk, trace_choice, gen_level);
             if (detail && (r = end_timed(c, tt, l.main))) return r;
             if (gen_shade && (r = trace(1, gen_shade < 2 && p->sunEnabled == 1 ? 0 : -1))) return r;
         } else {

@@ -87,13 +87,23 @@ GD_FN void flush_counters(const WorkCounters &wc, uint32_t segments, unsigned lo
     }
 }
 
+/// Pixel w of an 8x8 block (Frame::block_order). 0: row-major, (w & 7, w >> 3). 1: Z-order — x takes the even bits of w, y the odd ones, so an
+/// aligned group of 8 consecutive w is a 4x2 rectangle and one of 16 a 4x4 one where row-major gives 8x1 and 8x2: the 64 / batch pixels of a
+/// packet (PathBuffers) are a compact footprint, and compact footprints enter fewer distinct nodes. A bijection of the 64 pixels either way.
+GD_FN void block_pixel(uint32_t order, uint32_t w, uint32_t &x, uint32_t &y) {
+    const uint32_t zx = (w & 1u) | ((w >> 1) & 2u) | ((w >> 2) & 4u), zy = ((w >> 1) & 1u) | ((w >> 2) & 2u) | ((w >> 3) & 4u);
+    x = order ? zx : w & 7u;
+    y = order ? zy : w >> 3;
+}
+
 /// slot -> pixel of the tile; false for the padding slots of ragged edge tiles.
 GD_FN bool slot_pixel(const Frame &f, uint32_t slot, uint32_t &lx, uint32_t &ly) {
     uint32_t tiles_x = (f.tw + 7) / 8;
-    uint32_t t = slot >> 6, w = slot & 63;
+    uint32_t t = slot >> 6, w = slot & 63, x, y;
     if (f.tile_order) t = f.tile_order[t];
-    lx = (t % tiles_x) * 8 + (w & 7);
-    ly = (t / tiles_x) * 8 + (w >> 3);
+    block_pixel(f.block_order, w, x, y);
+    lx = (t % tiles_x) * 8 + x;
+    ly = (t / tiles_x) * 8 + y;
     return lx < f.tw && ly < f.th;
 }
 
@@ -465,6 +475,11 @@ GD_FN void thin_rounds(const Scene &sc, const F3 &ro, const F3 &rd, const F3 &rd
 // stops at the first accepted hit, and each hands its registers to shadow_retire ("the path ends here" = the step's !go_on).
 // Nothing goes to shadow_queue and sun[slot] is not written. Such a packet holds only the shadow lanes of its own 64 slots (none on sky),
 // where k_trace's packets are 64 dense entries: a separate level of the knob because of that.
+// `shade` == 3 (the host's GPUART_HIP_SHADOW_POOL on top of level 2): the shadow lanes of a packet join a pool of the wave instead, and the wave
+// walks the pool 64 queries at a time — full packets — and once more, partially, behind the last packet of a cursor chunk (walk_pool). A packet
+// step costs the same however many lanes take part, so fewer, fuller packets are fewer steps. The pool holds slots only (LDS, 512 bytes: the
+// kernel stays within the 8 KB per wave that 20 waves per CU allow); what a query needs is parked where level 1 parks it for k_trace — ray_o,
+// sun, pc[slot], `queued` stores — and comes back through the L1 of the CU that wrote it. Per query the calls and values are level 1's.
 // The launch bound: without it the shading code takes the kernel to 111 VGPRs and 4 waves per SIMD, which costs every level of the knob
 // 1-3.5 % of a pass (the other pass lanes' kernels share the CUs); with it 96 VGPRs and 28 bytes of scratch, path state parked across the
 // walks once per packet.
@@ -473,6 +488,7 @@ __global__ void __launch_bounds__(BLOCK, GD_TRACE_WAVES) k_gen(Scene sc, Frame f
     __shared__ uint2 ring_a[GD_RING * BLOCK];
     __shared__ float ring_b[GD_RING * BLOCK];
     __shared__ uint32_t stage_first[SHADE_ROUNDS];  // first slot of the packets since the last flush
+    __shared__ uint32_t pool[2 * BLOCK];            // `shade` == 3: the slots whose Sun-shadow query is pending, oldest first (at most 63 + 64)
     const bool no_segments = !(P.maxSegments > 0 && 1.0f > P.minWeight);
     const uint32_t total = b.n_slots * b.batch;
     // the first ray of path slot `slot` (a padding slot of a ragged edge tile: none); true: the path has a segment 0 to trace
@@ -538,6 +554,33 @@ __global__ void __launch_bounds__(BLOCK, GD_TRACE_WAVES) k_gen(Scene sc, Frame f
             else if (walk == (GD_ROUND_TYPES | GD_REF_ORDER)) trav_packet<GD_ROUND_TYPES | GD_REF_ORDER>(sc, ro, rd, rdiv, t, st, any_hit);
             else trav_packet<GD_ALL_TYPES | GD_REF_ORDER>(sc, ro, rd, rdiv, t, st, any_hit);
         };
+        // `shade` == 3: the pool's first n queries (n wave-uniform, 1 .. 64) as one packet. Their slots wait in `pool`; the origin, the Sun term with
+        // "the path ends here" and pathColor were parked in ray_o / sun / pc[slot] by the step's store, as for k_trace, by lanes of this wave — the
+        // workgroup fence orders those stores and the pool's words before the loads. All loads are issued before the walk; the retire is k_trace's.
+        uint32_t pending = 0;  // wave-uniform: queries in the pool
+        auto walk_pool = [&](uint32_t n) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+            const bool has = (uint32_t)lane_id() < n;
+            const uint32_t ps = has ? pool[lane_id()] : SLOT_INVALID;
+            const uint32_t rest = pending - n;  // (<= 63) the queries that stay move to the front, in order
+            const uint32_t stays = (uint32_t)lane_id() < rest ? pool[n + (uint32_t)lane_id()] : SLOT_INVALID;
+            F3 po = f3(0, 0, 0), pd = f3(1, 0, 0), pdiv = f3(1, 1, 1);
+            float4 term = make_float4(0, 0, 0, 0), colour = make_float4(0, 0, 0, 0);
+            Trav pt; pt.state = TRAV_DONE; pt.closest = 0; pt.hit_prim = GD_NO_PRIM; pt.node = 0; pt.entry = 0; pt.second = 0;
+            if (has) {  // (k_trace's take_query for a shadow entry)
+                po = xyz(b.ray_o[ps]);
+                term = b.sun[ps];
+                colour = b.pc[ps];
+                pd = sun;
+                pdiv = f3(1 / pd.x, 1 / pd.y, 1 / pd.z);
+                trav_init<GD_BOXES_FAST>(sc, Ray{po, pd}, pdiv, pt, st, nullptr, false);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+            if ((uint32_t)lane_id() < rest) pool[lane_id()] = stays;
+            pending = rest;
+            walk_packet(po, pd, pdiv, pt, has);
+            if (has) shadow_retire(f, P, b, accum, ps, j, npaths, po, sun, pt.hit_prim, xyz(colour), xyz(term), (__float_as_uint(term.w) & 1u) != 0);
+        };
         for (;;) {
             bool served;
             const uint32_t slot = cur.take(~0ull, true, &b.counters[1], chunk, served);  // the next (up to) 64 slots of the chunk
@@ -560,10 +603,20 @@ __global__ void __launch_bounds__(BLOCK, GD_TRACE_WAVES) k_gen(Scene sc, Frame f
             if (query) {
                 F3 cw = f3(1, 1, 1), rstart, rdir;  // path_tracing.glsl:156
                 s = segment_shade<false, false>(sc, f, P, seeds, b, accum, slot, j, npaths, 0, 0, ro, rd, t.closest, t.hit_prim, rstart, rdir, cw, pathColor);
-                segment_store(b, slot, s, shade < 2, 0u, rstart, rdir, cw, pathColor);
+                segment_store(b, slot, s, shade != 2, 0u, rstart, rdir, cw, pathColor);
                 ro = rstart;
             }
             bool shadow = s.shadow;  // this lane's slot goes to shadow_queue
+            if (shade == 3) {
+                // ---- the Sun-shadow queries of these hits join the wave's pool, which is walked 64 at a time: dense packets, as k_trace's are. A chunk's
+                // last packet empties the pool with one partial packet, so that pooled queries stay neighbours on the screen — and the loop can only
+                // end after a chunk's last packet: nothing is pending when it does.
+                const unsigned long long m = __ballot(shadow);
+                if (shadow) pool[pending + rank_below(m)] = slot;
+                pending += (uint32_t)__popcll(m);
+                shadow = false;
+                while (pending >= BLOCK || (pending && cur.next == cur.end)) walk_pool(min(pending, (uint32_t)BLOCK));
+            } else
             // ---- the Sun-shadow queries of these hits, walked here as one packet from the registers
             if (shade >= 2) {
                 t.state = TRAV_DONE;
