@@ -49,6 +49,19 @@ class RayHit(C.Structure):
 
 
 # the same record as a NumPy dtype: what trace_rays / pick return for host arrays (hits.view(np.float32).reshape(-1, 8): the raw words)
+class HipScene(C.Structure):
+    """gpuart_hip_scene (include/gpuart_hip.h)."""
+    _fields_ = [("layout", C.c_uint32), ("exact_boxes", C.c_uint32), ("recs", C.c_void_p), ("n_recs", C.c_uint64), ("prims", C.c_void_p),
+                ("n_prims", C.c_uint64), ("prim_boxes", C.c_void_p), ("root_min", C.c_float * 3), ("root_max", C.c_float * 3),
+                ("root_ref", C.c_uint32), ("box_slack", C.c_float), ("max_depth", C.c_uint32), ("generation", C.c_uint64)]
+
+
+class RefitResult(C.Structure):
+    """gpuart_refit_result (include/gpuart_refit.h)."""
+    _fields_ = [("status", C.c_int32), ("first_bad", C.c_uint32), ("subnormal", C.c_uint32), ("root_min", C.c_float * 3), ("root_max", C.c_float * 3)]
+
+
+REFIT_PAYLOAD = 16  # GPUART_REFIT_PAYLOAD
 RAY_HIT = np.dtype([("pos", np.float32), ("p", np.float32, 3), ("n", np.float32, 3), ("type", np.int32)])
 RAYS_OCCLUSION = 1  # GPUART_HIP_RAYS_OCCLUSION
 
@@ -343,6 +356,12 @@ def edges_lib():
 def despeckle_lib():
     """libgpuart_despeckle.so; raises NativeLibraryMissing if it has not been built (no fallback)."""
     return _image_lib("despeckle")
+
+
+def refit_lib():
+    """libgpuart_refit.so (include/gpuart_refit.h), built by the image libraries' rule; raises NativeLibraryMissing if it has not been built
+    (no fallback)."""
+    return _image_lib("refit")
 
 
 def display_lib():
@@ -682,6 +701,9 @@ class Backend:
             raise e
 
     def close(self):
+        if getattr(self, "_refit", None) is not None:
+            refit_lib().gpuart_refit_destroy(self._refit)
+            self._refit = None
         if self.owned and self.ctx:
             self.L.gpuart_hip_destroy(self.ctx)
             self.ctx = None
@@ -713,6 +735,62 @@ class Backend:
     def set_camera(self, cam):
         cam = np.ascontiguousarray(cam, np.float32)
         self._chk(self.L.gpuart_hip_set_camera(self.ctx, _f3(cam[0:3]), _f3(cam[3:6]), _f3(cam[6:9]), _f3(cam[9:12])))
+
+    # a refit in place (include/gpuart_refit.h)
+    def scene_device(self):
+        """gpuart_hip_scene_device: the uploaded scene's device arrays and what the context knows of its tree, as a HipScene (pointers as
+        integers; valid until the next upload). Flushes and waits for every pass requested so far."""
+        s = HipScene()
+        self._chk(self.L.gpuart_hip_scene_device(self.ctx, C.byref(s)))
+        return s
+
+    def scene_refitted(self, root_min, root_max, subnormal):
+        self._chk(self.L.gpuart_hip_scene_refitted(self.ctx, _f3(root_min), _f3(root_max), C.c_int(1 if subnormal else 0)))
+
+    def refit(self, ordinals, payload):
+        """Replaces the primitives `ordinals` (strictly ascending device ordinals, as trace_rays returns them) by `payload` (n x 16 floats:
+        each primitive's canonical data quads, zero-padded) and refits the tree's boxes on the device; the context adopts the result.
+        Both arguments torch tensors on this device (int32 / float32, contiguous: the call stays device to device) or both anything NumPy
+        converts. Returns dict(root_min, root_max, subnormal, levels). A refused update raises HipError with code -1 (ERR_ARG), `first_bad`
+        = the offending update's index, and nothing changed."""
+        R = refit_lib()
+        scene = self.scene_device()
+        if getattr(self, "_refit", None) is None:
+            h = C.c_void_p()
+            self._chk_refit(R.gpuart_refit_create(C.c_int(self.device), C.byref(h)))
+            self._refit, self._refit_generation = h, None
+        if self._refit_generation != scene.generation:
+            self._chk_refit(R.gpuart_refit_bind(self._refit, C.byref(scene)))
+            self._refit_generation = scene.generation
+        res = RefitResult()
+        if hasattr(ordinals, "data_ptr"):
+            import torch
+            if not (hasattr(payload, "data_ptr") and ordinals.is_cuda and payload.is_cuda and ordinals.is_contiguous() and payload.is_contiguous()
+                    and ordinals.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)) and payload.dtype == torch.float32 and payload.numel() == 16 * ordinals.numel()):
+                raise ValueError("refit: ordinals (int32) and payload (float32, n x 16) must both be contiguous tensors on the device")
+            torch.cuda.synchronize(ordinals.device)   # (the handle's stream is its own: what wrote the tensors must be complete)
+            n = ordinals.numel()
+            rc = R.gpuart_refit_run(self._refit, C.byref(scene), C.c_void_p(ordinals.data_ptr() if n else None),
+                                    C.c_void_p(payload.data_ptr() if n else None), C.c_size_t(n), C.byref(res))
+        else:
+            o = np.ascontiguousarray(ordinals, np.uint32).reshape(-1)
+            p = np.ascontiguousarray(payload, np.float32).reshape(-1)
+            if p.size != 16 * o.size:
+                raise ValueError("refit: payload must hold 16 floats per ordinal")
+            rc = R.gpuart_refit_run_host(self._refit, C.byref(scene), _p(o), _p(p), C.c_size_t(o.size), C.byref(res))
+        self._chk_refit(rc, res)
+        self.scene_refitted(res.root_min[:], res.root_max[:], res.subnormal)
+        levels = C.c_uint32()
+        self._chk_refit(R.gpuart_refit_levels(self._refit, C.byref(levels)))
+        return dict(root_min=np.array(res.root_min[:], np.float32), root_max=np.array(res.root_max[:], np.float32), subnormal=bool(res.subnormal),
+                    levels=int(levels.value))
+
+    def _chk_refit(self, rc, res=None):
+        if rc != 0:
+            e = HipError("gpuart_refit error %d: %s" % (rc, refit_lib().gpuart_refit_last_error().decode()))
+            e.code = rc
+            e.first_bad = int(res.first_bad) if res is not None and res.status else None
+            raise e
 
     # rendering
     def render_direct(self, params):
@@ -1073,6 +1151,16 @@ class Renderer:
     def set_primitives(self, descs, print_info=False):
         arr = descs if isinstance(descs, C.Array) else make_prims(descs)
         self.L.gpuart_renderer_set_primitives(self.h, arr, C.c_int(len(arr)), C.c_int(1 if print_info else 0))
+
+    def update_primitives(self, indices, descs):
+        """Renderer::UpdatePrimitives: the primitives `indices` — distinct, numbering the descriptions set_primitives was given, as the
+        ordinals of trace_rays do — become `descs` (the same types); the tree is refitted on the device and the temporal history kept.
+        False, with nothing changed, on any refusal."""
+        arr = descs if isinstance(descs, C.Array) else make_prims(descs)
+        idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        if idx.size != len(arr):
+            raise ValueError("update_primitives: one description per index")
+        return bool(self.L.gpuart_renderer_update_primitives(self.h, _p(idx), arr, C.c_int(len(arr))))
 
     def init_box(self): self.L.gpuart_renderer_init_box(self.h)
     def init_dragon(self, path): return bool(self.L.gpuart_renderer_init_dragon(self.h, path.encode()))

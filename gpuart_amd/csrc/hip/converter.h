@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "device_scene.h"
+#include "prim_rule.h"
 
 namespace {
 
@@ -32,6 +33,7 @@ struct Converter {
     const float *q;
     size_t nq;
     std::vector<float4, UninitAlloc<float4>> recs, prims;
+    std::vector<float, UninitAlloc<float>> pbox;  ///< per device primitive its constructor's box (min xyz, max xyz): what a refit folds a leaf's box from
     size_t num_nodes = 0;
     uint32_t type_mask = 0;
     uint32_t max_depth = 0;
@@ -105,51 +107,10 @@ struct Converter {
         for (int k = 0; k < 3; k++) ok = ok && cmin[k] >= bmin[k] && cmax[k] <= bmax[k] && cmin[k] <= cmax[k];  // NaN fails
         return ok;
     }
-    static bool prim_in_box(uint32_t type, const float *d, const float *bmin, const float *bmax) {
-        float lo[3], hi[3];
-        // Coordinates beyond 2^20 (the hostile classes use 1e10 ... 1e30): the intersectors' own arithmetic cancels there — a
-        // vertex at -1e30 swallows the ray origin in `origin - v0` — and a hit parameter that is off by more than the band says
-        // nothing about the box it came from. (ulp(2^20) = 0.06: no scene a float path tracer renders sensibly is excluded.)
-        // (a cone's derived constants 12..14 — width coefficient, cosB, dotAxC1 — included; pads excluded: word 7 of a disc, word 15 of a cone,
-        // every fourth word of a triangle — the device never reads them, tests/test_converter.py)
-        static const int LEN[4] = {4, 7, 12, 15};
-        for (int k = 0; k < LEN[type & 3]; k++)
-            if (!(std::fabs(d[k]) <= 1048576.0f) && !(type == P_TRIANGLE && (k & 3) == 3)) return false;
-        switch (type) {
-        case P_SPHERE:
-        case P_DISC:  // (the reference bounds a disc by the sphere of its radius)
-            if (!(d[3] >= 0)) return false;
-            for (int k = 0; k < 3; k++) { lo[k] = d[k] - d[3]; hi[k] = d[k] + d[3]; }
-            break;
-        case P_TRIANGLE:
-            for (int k = 0; k < 3; k++) { lo[k] = std::min(d[k], std::min(d[4 + k], d[8 + k])); hi[k] = std::max(d[k], std::max(d[4 + k], d[8 + k])); }
-            break;
-        case P_CONE: {
-            const float r1 = d[3], r2 = d[7], len = d[11], wc = d[12];
-            if (!(r1 >= 0) || !(r2 >= 0) || !(len >= 0)) return false;
-            for (int k = 0; k < 3; k++) { lo[k] = std::min(d[k] - r1, d[4 + k] - r2); hi[k] = std::max(d[k] + r1, d[4 + k] + r2); }
-            // the intersector works from (centre 1, radius 1, axis, length, width coefficient): they must describe the same frustum
-            const float tol = 1.0e-4f * (len + r1 + r2) + 1.0e-30f;
-            for (int k = 0; k < 3; k++) if (!(std::fabs(d[k] + len * d[8 + k] - d[4 + k]) <= tol)) return false;
-            if (!(std::fabs(r1 + wc * len - r2) <= tol)) return false;
-            // ... and so must the constants that POSITION the surface for cone_hit (device_scene.h; reference shaders/cone.glsl:30-135 with
-            // the host's src/core.cpp:191-226): a unit axis, dotAxC1 = axis . centre 1 (the F and H terms), cosB from the radii and the
-            // length (the normal only — but a record that lies about one derived constant is hand-made: no benefit of the doubt)
-            const float ax2 = d[8] * d[8] + d[9] * d[9] + d[10] * d[10];
-            if (len > 0 && !(std::fabs(ax2 - 1.0f) <= 1.0e-4f)) return false;
-            const float dot_c1 = d[8] * d[0] + d[9] * d[1] + d[10] * d[2];
-            if (!(std::fabs(d[14] - dot_c1) <= 1.0e-4f * (std::fabs(d[0]) + std::fabs(d[1]) + std::fabs(d[2]) + 1.0f))) return false;
-            float cosb = 0.0f;
-            if (std::fabs(r1 - r2) >= 1.0e-7f && len > 0) {
-                const float rr = r1 > r2 ? r1 : r2, h = rr * len / std::fabs(r1 - r2);
-                cosb = (r1 > r2 ? rr : -rr) / std::sqrt(h * h + rr * rr);
-            }
-            if (!(std::fabs(d[13] - cosb) <= 1.0e-3f)) return false;
-            break;
-        }
-        default: return false;
-        }
-        return box_in_box(lo, hi, bmin, bmax);
+    /// A primitive lies inside a box when it meets the preconditions of prim_rule.h (magnitudes, radii, a cone's derived constants) and
+    /// the box its constructor gives it (lo, hi: prim_rule::prim_box, which the caller keeps) does.
+    static bool prim_in_box(uint32_t type, const float *d, const float *lo, const float *hi, const float *bmin, const float *bmax) {
+        return prim_rule::prim_ok(type, d) && box_in_box(lo, hi, bmin, bmax);
     }
 
     /// What the scan keeps of a canonical node: where it lies, the ref its parent stores for it, and (interior nodes) which
@@ -241,11 +202,17 @@ struct Converter {
                 for (uint32_t k = 0; k < cnt; k++) {
                     const uint32_t type = bits(q[4 * a]);
                     pack_prim(type, q + 4 * (a + 1), dst + 3 * k);
-                    loose = loose || !prim_in_box(type, q + 4 * (a + 1), b, b + 4);
+                    float *pb = pbox.data() + 6 * ((size_t)(n.ref & GD_REF_INDEX) + k);
+                    prim_rule::prim_box(type, q + 4 * (a + 1), pb, pb + 3);
+                    loose = loose || !prim_in_box(type, q + 4 * (a + 1), pb, pb + 3, b, b + 4);
                     if (k == 0) dst[0].w = fbits(type | (cnt << 2));  // the first primitive carries the leaf's count
                     a += 1 + LEN[type];
                 }
-                if (cnt == 0) { dst[0] = make_float4(0, 0, 0, fbits(0)); dst[1] = make_float4(0, 0, 0, 0); dst[2] = make_float4(0, 0, 0, 0); }
+                if (cnt == 0) {
+                    dst[0] = make_float4(0, 0, 0, fbits(0)); dst[1] = make_float4(0, 0, 0, 0); dst[2] = make_float4(0, 0, 0, 0);
+                    float *pb = pbox.data() + 6 * (size_t)(n.ref & GD_REF_INDEX);
+                    prim_rule::box_start(pb, pb + 3);
+                }
             } else {
                 const Child L = child_of(table[i + 1]), H = child_of(table[n.hi_index]);
                 irr = irr || bad(L) || bad(H);
@@ -269,6 +236,7 @@ struct Converter {
         if (!scan(0, 0, index, end)) return false;
         recs.resize(4 * n_recs);
         prims.resize(3 * n_prims);
+        pbox.resize(6 * n_prims);
         root = child_of(table[0]);
         note(root);
         const size_t n = table.size();

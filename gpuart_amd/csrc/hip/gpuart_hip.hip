@@ -173,6 +173,11 @@ struct gpuart_hip_ctx {
     uint32_t exact_boxes = 0;     ///< the uploaded tree holds an irregular box, or a box that does not bound what it holds (converter.h):
                                   ///< box tests take the comparison form and every walk keeps the reference's order
     uint32_t max_depth = 0;
+    // For a refit in place (gpuart_hip_scene_device): the record count, the uploads so far, and every primitive's own box — kept on the
+    // host by the upload, moved to the device by the first gpuart_hip_scene_device after it (a context that is never refitted pays no device memory).
+    uint64_t n_recs = 0, generation = 0;
+    std::vector<float, UninitAlloc<float>> h_prim_boxes;
+    float *d_prim_boxes = nullptr;
     float4 *d_direct = nullptr, *d_accum = nullptr;
     unsigned long long *d_counters = nullptr;
     /// Tile size, run lengths, lanes in use, execution mode (gpuart_hip_set_mode: 0 fast — launch pipeline, or k_run for a small
@@ -402,11 +407,14 @@ void update_uv(gpuart_hip_ctx *c) {
 /// box_quick.h's slack constant for a converted tree: its margins are sized by the largest plane coordinate of the tree — the root's,
 /// since every box was checked to lie inside its parent's — and its lemmas want planes that are normal numbers or zero. +inf (no quick
 /// box answers) for a tree with irregular or non-bounding boxes or a subnormal plane.
-float tree_slack(const Converter &cv, const Converter::Child &root) {
-    if (cv.irregular || cv.disorderly || cv.subnormal) return __builtin_inff();
+float slack_of_root(bool unfit, const float bmin[3], const float bmax[3]) {
+    if (unfit) return __builtin_inff();
     float pmax = 0;
-    for (int k = 0; k < 3; k++) pmax = std::max(pmax, std::max(std::fabs(root.bmin[k]), std::fabs(root.bmax[k])));
+    for (int k = 0; k < 3; k++) pmax = std::max(pmax, std::max(std::fabs(bmin[k]), std::fabs(bmax[k])));
     return gq_slack_of_tree(pmax);
+}
+float tree_slack(const Converter &cv, const Converter::Child &root) {
+    return slack_of_root(cv.irregular || cv.disorderly || cv.subnormal, root.bmin, root.bmax);
 }
 
 Scene scene_of(const gpuart_hip_ctx *c) {
@@ -602,7 +610,8 @@ int gpuart_hip_destroy(gpuart_hip_ctx *c) {
     const bool comm_stuck = bounded_ns::stuck().load();
     if (c->comm && !comm_stuck) (void)comm_drop(c);
     void *ptrs[] = {c->d_recs, c->d_prims, c->d_spill, c->d_direct, c->d_accum, c->d_counters, c->d_scratch, c->d_cursor,
-                    c->d_query_cursor, c->d_tile_order[0], c->d_tile_order[1], c->d_tile_cost, c->d_tile_xy, c->d_active, c->d_block_paths};
+                    c->d_query_cursor, c->d_tile_order[0], c->d_tile_order[1], c->d_tile_cost, c->d_tile_xy, c->d_active, c->d_block_paths,
+                    c->d_prim_boxes};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     void *comm_ptrs[] = {c->d_send, c->d_stage, c->d_hello};
     for (void *p : comm_ptrs) if (p && !comm_stuck) (void)hipFree(p);
@@ -674,6 +683,10 @@ int gpuart_hip_upload_bvh(gpuart_hip_ctx *c, const float *quads, size_t nquads) 
     c->ref_order = (!c->exact_boxes && c->n_prims < c->nearest_min_prims) ? 1u : 0u;
     c->max_depth = cv.max_depth;
     c->scene_bytes = cv.recs.size() * 16 + cv.prims.size() * 16;
+    c->n_recs = cv.recs.size() / 4;
+    c->generation++;
+    if (c->d_prim_boxes) { (void)hipFree(c->d_prim_boxes); c->d_prim_boxes = nullptr; }
+    c->h_prim_boxes.swap(cv.pbox);
     if ((r = ensure_spill(c))) return r;
     c->have_scene = true;
     c->order_stale = true;
@@ -1229,6 +1242,48 @@ int gpuart_hip_scene_info(gpuart_hip_ctx *c, uint64_t *nodes, uint64_t *prims, u
     if (prims) *prims = c->n_prims;
     if (max_depth) *max_depth = c->max_depth;
     if (device_bytes) *device_bytes = c->scene_bytes;
+    return 0;
+}
+
+// ---- a refit in place (include/gpuart_refit.h): host code only ------------------------------------------------------------------
+int gpuart_hip_scene_device(gpuart_hip_ctx *c, gpuart_hip_scene *out) {
+    if (!c || !out) return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_device: bad argument");
+    if (!c->have_scene) return fail(GPUART_HIP_ERR_ARG, "no scene uploaded");
+    HIP_TRY(hipSetDevice(c->device));
+    int r;
+    if ((r = gpuart_hip_flush(c))) return r;
+    if ((r = drain(c))) return r;
+    if (!c->d_prim_boxes) {
+        HIP_TRY(hipMalloc(&c->d_prim_boxes, c->h_prim_boxes.size() * sizeof(float) + 16));
+        HIP_TRY(hipMemcpy(c->d_prim_boxes, c->h_prim_boxes.data(), c->h_prim_boxes.size() * sizeof(float), hipMemcpyHostToDevice));
+        std::vector<float, UninitAlloc<float>>().swap(c->h_prim_boxes);
+    }
+    out->layout = 1;
+    out->exact_boxes = c->exact_boxes;
+    out->recs = c->d_recs; out->n_recs = c->n_recs;
+    out->prims = c->d_prims; out->n_prims = c->n_prims;
+    out->prim_boxes = c->d_prim_boxes;
+    memcpy(out->root_min, c->root_min, 12); memcpy(out->root_max, c->root_max, 12);
+    out->root_ref = c->root_ref;
+    out->box_slack = c->box_slack;
+    out->max_depth = c->max_depth;
+    out->generation = c->generation;
+    return 0;
+}
+
+int gpuart_hip_scene_refitted(gpuart_hip_ctx *c, const float root_min[3], const float root_max[3], int subnormal) {
+    if (!c || !root_min || !root_max) return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_refitted: bad argument");
+    if (!c->have_scene) return fail(GPUART_HIP_ERR_ARG, "no scene uploaded");
+    if (c->exact_boxes) return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_refitted: a tree with irregular boxes (or boxes that do not bound their contents) is not refitted");
+    for (int k = 0; k < 3; k++)
+        if (!(root_min[k] <= root_max[k]) || std::isinf(root_min[k]) || std::isinf(root_max[k]))
+            return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_refitted: the root box is not finite and ordered");
+    int r;
+    if ((r = gpuart_hip_flush(c))) return r;
+    if ((r = drain(c))) return r;
+    memcpy(c->root_min, root_min, 12); memcpy(c->root_max, root_max, 12);
+    c->box_slack = c->quick_boxes ? slack_of_root(subnormal != 0, c->root_min, c->root_max) : __builtin_inff();
+    c->order_stale = true;
     return 0;
 }
 

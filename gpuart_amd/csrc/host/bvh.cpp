@@ -6,6 +6,7 @@
 // midpoint, never leaving a side empty when there are more than two primitives.
 #include "bvh.h"
 #include "exact_sort.h"
+#include "../hip/prim_rule.h"
 
 #include <algorithm>
 #include <cassert>
@@ -386,6 +387,165 @@ void BoundingVolumesHierarchy::CompileTo(float *dst, size_t baseQuad) const {
             }
         }
     });
+}
+
+// ---- refit: primitives replaced, boxes folded bottom-up, the topology kept (bvh.h; include/gpuart_refit.h) ----------------------
+uint32_t BoundingVolumesHierarchy::Payload(const Primitive &p, float out[16]) {
+    static thread_local Primitive::Data one;  // (kept between calls: an update of a whole mesh makes a million of them)
+    one.clear();
+    p.StoreIntoBVH(one);  // the header quad, then the data quads
+    std::fill(out, out + prim_rule::PAYLOAD, 0.0f);
+    std::copy(one.begin() + RGBA_ELEMS, one.end(), out);
+    return as_uint(one[0]);
+}
+
+bool BoundingVolumesHierarchy::Locate(uint32_t index, uint32_t &leaf, size_t &header) const {
+    if (index >= NumPrimitives) return false;
+    if (LeafOfFirst.empty())
+        for (size_t i = 0; i < Nodes.size(); i++)
+            if (Nodes[i].count) LeafOfFirst.push_back((uint32_t)i);
+    // the last leaf whose first primitive is not beyond `index`: a few steps on from the leaf found last (ascending lists), else by bisection
+    const auto first = [&](size_t k) { return Nodes[LeafOfFirst[k]].primFirst; };
+    size_t c = LocateCursor < LeafOfFirst.size() && first(LocateCursor) <= index ? LocateCursor : LeafOfFirst.size();
+    for (int step = 0; step < 4 && c + 1 < LeafOfFirst.size() && first(c + 1) <= index; step++) c++;
+    if (c >= LeafOfFirst.size() || (c + 1 < LeafOfFirst.size() && first(c + 1) <= index)) {
+        auto it = std::upper_bound(LeafOfFirst.begin(), LeafOfFirst.end(), index, [&](uint32_t v, uint32_t l) { return v < Nodes[l].primFirst; });
+        if (it == LeafOfFirst.begin()) return false;
+        c = (size_t)(it - LeafOfFirst.begin()) - 1;
+    }
+    LocateCursor = c;
+    leaf = LeafOfFirst[c];
+    const Node &n = Nodes[leaf];
+    if (index - n.primFirst >= n.count) return false;
+    header = n.dataBegin;
+    for (uint32_t k = n.primFirst; k < index; k++) header += RGBA_ELEMS * (2 + (size_t)(as_uint(LeafData[header]) & 3));
+    return true;
+}
+
+bool BoundingVolumesHierarchy::PlanRefit(const uint32_t *indices, const float *payloads, size_t n, const uint32_t *types, size_t *firstBad,
+                                         std::vector<Place> *where) const {
+    if (where) where->resize(n);
+    for (size_t i = 0; i < n; i++) {
+        uint32_t leaf;
+        size_t header;
+        if ((i && indices[i] <= indices[i - 1]) || !Locate(indices[i], leaf, header) || (types && types[i] != as_uint(LeafData[header])) ||
+            !prim_rule::prim_ok(as_uint(LeafData[header]), payloads + prim_rule::PAYLOAD * i)) {
+            if (firstBad) *firstBad = i;
+            return false;
+        }
+        if (where) (*where)[i] = Place{leaf, header};
+    }
+    return true;
+}
+
+bool BoundingVolumesHierarchy::CheckRefit(const uint32_t *indices, const float *payloads, size_t n, size_t *firstBad, const uint32_t *types) const {
+    return PlanRefit(indices, payloads, n, types, firstBad, nullptr);
+}
+
+void BoundingVolumesHierarchy::RefitNode(size_t i) {
+    Node &node = Nodes[i];
+    float lo[3], hi[3];
+    prim_rule::box_start(lo, hi);
+    if (node.count == 0 && node.higher != 0) {
+        prim_rule::box_fold(lo, hi, Nodes[i + 1].lo, Nodes[i + 1].hi);
+        prim_rule::box_fold(lo, hi, Nodes[node.higher].lo, Nodes[node.higher].hi);
+    } else {
+        size_t at = node.dataBegin;
+        for (uint32_t k = 0; k < node.count; k++) {
+            const uint32_t type = as_uint(LeafData[at]) & 3;
+            float plo[3], phi[3];
+            prim_rule::prim_box(type, &LeafData[at + RGBA_ELEMS], plo, phi);
+            prim_rule::box_fold(lo, hi, plo, phi);
+            at += RGBA_ELEMS * (2 + (size_t)type);
+        }
+    }
+    std::copy(lo, lo + 3, node.lo);
+    std::copy(hi, hi + 3, node.hi);
+}
+
+bool BoundingVolumesHierarchy::Refit(const uint32_t *indices, const float *payloads, size_t n, size_t *firstBad, bool touchedOnly) {
+    std::vector<Place> where;
+    if (!PlanRefit(indices, payloads, n, nullptr, firstBad, &where)) return false;
+    for (size_t i = 0; i < n; i++) {
+        const size_t len = RGBA_ELEMS * (size_t)prim_rule::data_quads(as_uint(LeafData[where[i].header]));
+        std::copy(payloads + prim_rule::PAYLOAD * i, payloads + prim_rule::PAYLOAD * i + len, LeafData.begin() + where[i].header + RGBA_ELEMS);
+    }
+    // pre-order: a node's children lie behind it, so a pass from the back meets them first
+    if (!touchedOnly) {
+        for (size_t i = Nodes.size(); i-- > 0;) RefitNode(i);
+        return true;
+    }
+    // the touched leaves and their ancestors, each once (a walk towards the root ends at the first node another walk has marked)
+    std::vector<uint32_t> touched;
+    std::vector<bool> marked(Nodes.size(), false);
+    for (size_t i = 0; i < n; i++)
+        for (uint32_t node = where[i].leaf; !marked[node]; node = Nodes[node].parent) {
+            marked[node] = true;
+            touched.push_back(node);
+            if (node == 0) break;
+        }
+    std::sort(touched.begin(), touched.end());
+    for (size_t k = touched.size(); k-- > 0;) RefitNode(touched[k]);
+    return true;
+}
+
+bool BoundingVolumesHierarchy::Refit(const uint32_t *indices, const Primitive *const *moved, size_t n, size_t *firstBad) {
+    std::vector<float> payloads(prim_rule::PAYLOAD * n);
+    std::vector<uint32_t> types(n);
+    for (size_t i = 0; i < n; i++) types[i] = Payload(*moved[i], payloads.data() + prim_rule::PAYLOAD * i);
+    return CheckRefit(indices, payloads.data(), n, firstBad, types.data()) && Refit(indices, payloads.data(), n, firstBad);
+}
+
+bool BoundingVolumesHierarchy::Load(const float *q, size_t nq) {
+    struct Todo { size_t addr; uint32_t parent; bool isLower; unsigned level; };
+    std::vector<Node, UninitAlloc<Node>> nodes;
+    std::vector<float, UninitAlloc<float>> data;
+    std::vector<Todo> todo{{0, 0, false, 0}};
+    size_t cursor = 0, prims = 0;  // Compile lays the subtrees out contiguously in pre-order: every node starts where the one before it ends
+    unsigned depth = 0;
+    while (!todo.empty()) {
+        const Todo t = todo.back();
+        todo.pop_back();
+        if (t.addr != cursor || t.addr + 3 > nq || t.level > 1024) return false;
+        const uint32_t self = (uint32_t)nodes.size();
+        const float *b = q + RGBA_ELEMS * t.addr;
+        Node n;
+        for (int k = 0; k < 3; k++) { n.lo[k] = b[k]; n.hi[k] = b[4 + k]; }
+        n.parent = t.parent; n.higher = 0; n.isLower = t.isLower; n.count = 0; n.primFirst = 0; n.dataBegin = n.dataEnd = 0;
+        if (self && !t.isLower) nodes[t.parent].higher = self;
+        depth = std::max(depth, t.level);
+        const uint32_t flags = as_uint(b[8]);
+        if (flags & LEAF) {
+            n.count = flags & ~FLAGS_MASK;
+            n.primFirst = (uint32_t)prims;
+            size_t a = t.addr + 3;
+            for (uint32_t k = 0; k < n.count; k++) {
+                if (a + 1 > nq || as_uint(q[RGBA_ELEMS * a]) > 3) return false;
+                a += 2 + (size_t)as_uint(q[RGBA_ELEMS * a]);
+                if (a > nq) return false;
+            }
+            n.dataBegin = data.size();
+            data.insert(data.end(), q + RGBA_ELEMS * (t.addr + 3), q + RGBA_ELEMS * a);
+            n.dataEnd = data.size();
+            prims += n.count;
+            cursor = a;
+        } else {
+            const uint32_t lo = as_uint(b[9]), hi = as_uint(b[10]);
+            if (lo != t.addr + 3 || hi <= lo || hi >= nq) return false;
+            cursor = lo;
+            todo.push_back(Todo{hi, self, false, t.level + 1});
+            todo.push_back(Todo{lo, self, true, t.level + 1});
+        }
+        nodes.push_back(n);
+    }
+    Nodes.swap(nodes);
+    LeafData.swap(data);
+    NumPrimitives = prims;
+    Depth = depth;
+    QuadAddr.clear();
+    LeafOfFirst.clear();
+    LocateCursor = 0;
+    return true;
 }
 
 void BoundingVolumesHierarchy::Print(const Primitive::Data &t, std::ostream &s) {

@@ -46,6 +46,28 @@ public:
     size_t CompiledFloats() const;
     void CompileTo(float *dst, size_t baseQuad = 0) const;
 
+    /// Replaces primitives and refits every box; the topology stays (include/gpuart_refit.h states the contract; this is its statement on
+    /// the host tree, tests/refit_ref.py the restatement). `indices`: n strictly ascending indices into the vector the constructor left
+    /// behind (= the device's primitive ordinals); `payloads`: n x 16 floats, each primitive's data quads as StoreDataIntoBVH writes them,
+    /// zero-padded. A primitive keeps its type. Every leaf's box becomes the running minimum / maximum of its primitives' boxes in leaf
+    /// order (from +-99e29, `<` and `>`, as PrepareNode), every interior node's its lower child's box folded with its upper child's.
+    /// False, with nothing changed, unless the indices are ascending and in range and every payload meets csrc/hip/prim_rule.h; if
+    /// `firstBad` is given it receives the index into the list of the first offending update. n = 0 refits only.
+    /// `touchedOnly`: only the leaves of the listed primitives and their ancestors are recomputed. That is the same tree wherever the
+    /// rule already reproduces every box, as it does on every built and every refitted tree (a running minimum that keeps the first
+    /// of equal values gives the same value folded in one pass or child by child; tests/test_refit_ref.py holds both forms to the
+    /// restatement) — Renderer::UpdatePrimitives' form: a moved primitive costs its path to the root, not the whole tree.
+    bool Refit(const uint32_t *indices, const float *payloads, size_t n, size_t *firstBad = nullptr, bool touchedOnly = false);
+    /// The same from primitives (`moved[i]` must have the type primitive indices[i] has).
+    bool Refit(const uint32_t *indices, const Primitive *const *moved, size_t n, size_t *firstBad = nullptr);
+    /// Refit's verdict alone: would it accept this update? Changes nothing. With `types`, update i must also have type types[i] already.
+    bool CheckRefit(const uint32_t *indices, const float *payloads, size_t n, size_t *firstBad = nullptr, const uint32_t *types = nullptr) const;
+    /// The tree of a canonical compiled quad array (what Compile writes), so that Compile gives the same quads in every word the
+    /// device reads. False for a malformed array.
+    bool Load(const float *quads, size_t nquads);
+    /// The 16 floats of Refit's `payloads` for a primitive; returns its type.
+    static uint32_t Payload(const Primitive &p, float out[16]);
+
     /// Prints a compiled tree, decoding it the way the device code does.
     static void Print(const Primitive::Data &compiledTree, std::ostream &s);
 
@@ -102,6 +124,14 @@ private:
     std::vector<float, UninitAlloc<float>> LeafData;  ///< serialised primitives of all leaves, in leaf order
     size_t NumPrimitives = 0;
     unsigned Depth = 0;
+    /// Where primitive `index` lies: its leaf and the offset of its header quad in LeafData (floats). False if out of range.
+    bool Locate(uint32_t index, uint32_t &leaf, size_t &header) const;
+    mutable std::vector<uint32_t> LeafOfFirst;  ///< the leaves in pre-order = ascending primFirst (made by the first Locate)
+    mutable size_t LocateCursor = 0;            ///< the entry of LeafOfFirst the last Locate found
+    struct Place { uint32_t leaf; size_t header; };
+    /// The verdict on an update (CheckRefit's) and, if `where` is given, where each of its primitives lies.
+    bool PlanRefit(const uint32_t *indices, const float *payloads, size_t n, const uint32_t *types, size_t *firstBad, std::vector<Place> *where) const;
+    void RefitNode(size_t i);  ///< node i's box by the rule, from its primitives or its children's boxes
 
     /// Sequential build of [from, to) appended to `out` (reference src/bvh.cpp:35-152).
     static void Subdivide(Subtree &out, ItemList &prims, size_t from, size_t to, unsigned level,

@@ -160,6 +160,16 @@ void gpuart_sort_permutation(const float *keys, size_t n, unsigned threads, uint
 
 void gpuart_free(void *p) { free(p); }
 
+int gpuart_refit_tree(const float *quads, size_t nquads, const uint32_t *ordinals, const float *payloads, size_t n, float *out,
+                      size_t *firstBad, int touchedOnly) {
+    if (!quads || !out || (n && (!ordinals || !payloads))) return -1;
+    BoundingVolumesHierarchy tree;
+    if (!tree.Load(quads, nquads) || tree.CompiledFloats() != nquads * RGBA_ELEMS) return -1;
+    if (!tree.Refit(ordinals, payloads, n, firstBad, touchedOnly != 0)) return -2;
+    tree.CompileTo(out);
+    return 0;
+}
+
 void gpuart_last_build_ms(double out[2]) { out[0] = g_last_build_ms[0]; out[1] = g_last_build_ms[1]; }
 
 void gpuart_camera_basis(const float pos[3], const float dir[3], const float up[3], float fovY, float screenDist,
@@ -198,6 +208,28 @@ void gpuart_renderer_set_primitives(gpuart_renderer *r, const gpuart_prim_desc *
             r->descOf[k] = std::lower_bound(pos.begin(), pos.end(), std::make_pair((const Primitive *)list[k], (int32_t)-1))->second;
     }
     free_list(list);
+}
+int gpuart_renderer_update_primitives(gpuart_renderer *r, const uint32_t *indices, const gpuart_prim_desc *descs, int n) {
+    if (!r || n < 0 || (n && (!indices || !descs))) return 0;
+    // the caller's numbering -> positions in the renderer's sorted vector, ascending
+    std::vector<uint32_t> ordinalOf(r->descOf.size());
+    for (size_t k = 0; k < r->descOf.size(); k++) ordinalOf[(size_t)r->descOf[k]] = (uint32_t)k;
+    std::vector<std::pair<uint32_t, int>> order((size_t)n);
+    for (int i = 0; i < n; i++) {
+        if (!ordinalOf.empty() && indices[i] >= ordinalOf.size()) return 0;
+        order[(size_t)i] = {ordinalOf.empty() ? indices[i] : ordinalOf[indices[i]], i};
+    }
+    std::sort(order.begin(), order.end());
+    std::vector<uint32_t> sorted((size_t)n);
+    std::vector<gpuart_prim_desc> moved((size_t)n);
+    for (int i = 0; i < n; i++) {
+        sorted[(size_t)i] = order[(size_t)i].first;
+        moved[(size_t)i] = descs[order[(size_t)i].second];
+    }
+    std::vector<Primitive *> list;
+    const bool ok = make_list(moved.data(), n, list) && r->impl.UpdatePrimitives(sorted.data(), list.data(), (size_t)n);
+    free_list(list);
+    return ok ? 1 : 0;
 }
 void gpuart_renderer_init_box(gpuart_renderer *r) { r->descOf.clear(); InitBox(r->impl); }
 int gpuart_renderer_init_dragon(gpuart_renderer *r, const char *plyPath) { r->descOf.clear(); return InitDragon(r->impl, plyPath) ? 1 : 0; }

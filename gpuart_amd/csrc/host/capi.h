@@ -40,6 +40,13 @@ int gpuart_compile_bvh_from_file(int kind, const char *path, float magnification
                                  const gpuart_prim_desc *extra, int nextra, float **quads, size_t *nquads,
                                  unsigned *depth, size_t *nloaded);
 void gpuart_free(void *p);
+/* BoundingVolumesHierarchy::Refit without a device: the compiled tree `quads` (nquads quads, what gpuart_compile_bvh returns) with
+ * the data quads of the primitives `ordinals` (n, strictly ascending, numbered as the tree's leaves hold them) replaced by `payloads`
+ * (n x 16 floats, zero-padded) and every box refitted (include/gpuart_refit.h states the contract), written to `out` (nquads quads).
+ * touchedOnly != 0: Refit's form that recomputes only the moved primitives' leaves and their ancestors (Renderer::UpdatePrimitives' form).
+ * 0; -1 for a malformed tree or NULL pointers; -2 for a refused update (*firstBad, if given, is its index in the list), `out` untouched. */
+int gpuart_refit_tree(const float *quads, size_t nquads, const uint32_t *ordinals, const float *payloads, size_t n, float *out,
+                      size_t *firstBad, int touchedOnly);
 /* What the library itself spent in the last gpuart_compile_bvh / _from_file of this process: out[0] = BoundingVolumesHierarchy's
  * constructor (the build), out[1] = its compilation into quads, in ms — without the harness around them (making and deleting one
  * Primitive object per description, copying the result into the caller's language). */
@@ -63,6 +70,11 @@ gpuart_renderer *gpuart_renderer_create(unsigned width, unsigned height, const f
 void gpuart_renderer_destroy(gpuart_renderer *r);
 int gpuart_renderer_is_ok(gpuart_renderer *r);
 void gpuart_renderer_set_primitives(gpuart_renderer *r, const gpuart_prim_desc *prims, int n, int printInfo);
+/* Renderer::UpdatePrimitives: primitives `indices` (n distinct indices, in any order) become `descs` (the same types); the tree is
+ * refitted on the device, its topology and the histories are kept. After gpuart_renderer_set_primitives the indices number that call's
+ * `prims` array AS THE CALLER PASSED IT, as the ordinals of gpuart_renderer_trace_rays do; after an init_* scene they are positions in
+ * the renderer's sorted list. 1 on success, 0 — with the scene unchanged — on any refusal. */
+int gpuart_renderer_update_primitives(gpuart_renderer *r, const uint32_t *indices, const gpuart_prim_desc *descs, int n);
 void gpuart_renderer_init_box(gpuart_renderer *r);
 int gpuart_renderer_init_dragon(gpuart_renderer *r, const char *plyPath);
 /* InitCluster / InitTree (reference src/scenes.cpp:69-103) on a primitive-list file; NULL = the reference's own path. */

@@ -100,6 +100,7 @@ Renderer::~Renderer() {
     if (Temporal) gpuart_temporal_destroy(Temporal);
     if (Denoiser) gpuart_denoise_destroy(Denoiser);
     DenoiseMem.Release();
+    if (Refitter) gpuart_refit_destroy(Refitter);
     if (Backend) gpuart_hip_destroy(Backend);
 }
 
@@ -276,6 +277,45 @@ void Renderer::SetPrimitives(std::vector<Primitive *> &primitives, bool printInf
                 primitives.size(), ms(tAll, tEnd), ms(tAll, tBuilt), ms(tBuilt, tCompiled), ms(tCompiled, tEnd));
     }
     ResetPathTracing();
+}
+
+// ---- moved primitives: a refit in place (include/gpuart_refit.h) ------------------------------------
+// The host tree gives its verdict first and changes last: a refusal, on the host or on the device (they state one rule,
+// csrc/hip/prim_rule.h), leaves both trees as they were. The view is committed after the verdict and before the device arrays change,
+// while the accumulator and the G-buffer are still those of the scene the paths saw.
+bool Renderer::UpdatePrimitives(const uint32_t *indices, Primitive *const *moved, size_t n) {
+    if (!IsOK || (n && (!indices || !moved))) return false;
+    std::vector<float> payloads(GPUART_REFIT_PAYLOAD * n);
+    std::vector<uint32_t> types(n);
+    size_t bad = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (!moved[i]) return false;
+        types[i] = BoundingVolumesHierarchy::Payload(*moved[i], payloads.data() + GPUART_REFIT_PAYLOAD * i);
+    }
+    if (!Tree.CheckRefit(indices, payloads.data(), n, &bad, types.data())) {
+        std::cerr << "Renderer: UpdatePrimitives: update " << bad << " refused (indices ascending and in range, the same type, a primitive inside the rule)." << std::endl;
+        return false;
+    }
+    gpuart_hip_scene scene;
+    if (!Check(gpuart_hip_scene_device(Backend, &scene), "looking up the scene's device arrays")) return false;
+    if (scene.exact_boxes) {
+        std::cerr << "Renderer: UpdatePrimitives: a tree with irregular boxes (or boxes that do not bound their contents) is not refitted." << std::endl;
+        return false;
+    }
+    if (!Refitter && !Check(gpuart_refit_create(Device, &Refitter), "creating the refit handle", gpuart_refit_last_error)) return false;
+    if (RefitGeneration != scene.generation) {  // (a bind reads every record back: once per upload)
+        if (!Check(gpuart_refit_bind(Refitter, &scene), "binding the refit handle", gpuart_refit_last_error)) return false;
+        RefitGeneration = scene.generation;
+    }
+    CommitTemporalView();
+    gpuart_refit_result res;
+    if (!Check(gpuart_refit_run_host(Refitter, &scene, indices, payloads.data(), n, &res), "refitting the tree", gpuart_refit_last_error)) return false;
+    if (!Check(gpuart_hip_scene_refitted(Backend, res.root_min, res.root_max, (int)res.subnormal), "adopting the refitted tree")) return IsOK = false;
+    Tree.Refit(indices, payloads.data(), n, nullptr, true);
+    GBufferValid = false;
+    EdgeListValid = false;
+    ResetPathTracing();
+    return true;
 }
 
 // ---- batched ray queries ------------------------------------------------------------------------

@@ -9,7 +9,7 @@
 //   ReadDirectLighting, ReadRadiance, Finish, SetMaxPathSegments, SetMinWeight, SetSeed,
 //   SetTile, GetBackend, ComputeScreenBasis, GetNumPathsRendered, ReadDenoised, SetTemporalHistory, ReadPreview, RenderUntil,
 //   ReadErrorMap, ReadRefined, SetHistoryVariance, SetHistoryAntiLag, ReadGuidedPreview, ReadDisplay, SetEdgeResolve,
-//   SetFireflyClamp, ReadFireflySummary.
+//   SetFireflyClamp, ReadFireflySummary, UpdatePrimitives.
 #ifndef GPUART_RENDERER_H
 #define GPUART_RENDERER_H
 
@@ -29,6 +29,7 @@
 #include "gpuart_hip.h"
 #include "gpuart_moments.h"
 #include "gpuart_refine.h"
+#include "gpuart_refit.h"
 #include "gpuart_temporal.h"
 #include "math_types.h"
 
@@ -67,6 +68,16 @@ public:
 
     /// May reorder `primitives`; keeps nothing of them afterwards.
     void SetPrimitives(std::vector<Primitive *> &primitives, bool printInfo);
+    /// Moves primitives of the scene SetPrimitives built and refits its tree on the device (include/gpuart_refit.h); the topology stays, so
+    /// the boxes loosen as primitives drift: a long drift wants a SetPrimitives. `indices`: n strictly ascending indices into the vector
+    /// SetPrimitives left behind (the ordinals TraceRays returns), `moved` the primitives they become, of the same types. Like
+    /// SetUserSpherePos it first commits the view it is about to leave, so the temporal histories survive: their tap validation by hit
+    /// point, normal and class discards what moved, and the lighting elsewhere lags by at most the history window, as for a moved
+    /// diffuse user sphere. The accumulation restarts (ResetPathTracing, which also clears a non-uniform adaptive accumulator: no
+    /// state of RenderAdaptive refuses an update). False — the scene, the tree and the images as they were; std::cerr says why — for
+    /// indices that are not ascending or out of range, a changed type, and a primitive outside csrc/hip/prim_rule.h (a word that is not
+    /// finite or beyond 2^20, a negative radius), and for a scene whose tree the uploader classified irregular or disorderly.
+    bool UpdatePrimitives(const uint32_t *indices, Primitive *const *moved, size_t n);
     bool UpdateViewportSize(unsigned width, unsigned height);
     bool SetCamera(const Camera &cam);
 
@@ -325,6 +336,8 @@ private:
     ScreenBasis CurrentBasis;             ///< what SetCamera gave the back end
     double LastSetPrimitivesMs[4] = {0, 0, 0, 0};
     gpuart_hip_ctx *Backend = nullptr;
+    gpuart_refit *Refitter = nullptr;     ///< made by the first UpdatePrimitives; bound again after every upload (the scene's generation)
+    uint64_t RefitGeneration = 0;         ///< the generation Refitter is bound to (0: none; the first upload's is 1)
     BoundingVolumesHierarchy Tree;
     struct { unsigned width, height; } Viewport{0, 0};
     struct { unsigned x, y, w, h; } Tile{0, 0, 0, 0};  ///< the part of the frame this renderer owns

@@ -5,6 +5,8 @@
 // functions more than one library states: the luminance and "what is a surface pixel". Each library is one translation unit that includes
 // this once, so everything sits in an anonymous namespace and every library has its own copy (its own last error). The checks take the
 // library's name: every message starts with it. DESIGN.md "The image libraries' scaffold" says what stays in each library.
+// refit/refit.hip, which is no image library (it refits the uploaded tree), takes the last error, HIP_TRY, the handle and the grow-only
+// buffer from here too.
 #pragma once
 #include <hip/hip_runtime.h>
 

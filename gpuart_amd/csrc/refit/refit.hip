@@ -1,0 +1,348 @@
+// refit.hip — libgpuart_refit.so (gfx950): listed primitives of an uploaded scene replaced and its tree's boxes refitted in place, as
+// include/gpuart_refit.h states it. Built without flushing fp32 denormals and without contraction: a box plane is copied, a triangle's
+// edge subtracted, exactly as the host uploader does (csrc/hip/converter.h) and tests/refit_ref.py restates in NumPy float32.
+// DESIGN.md "Refit" describes the launches and why nothing is handed between workgroups inside one.
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "../image/image_lib.h"
+#include "../hip/prim_rule.h"
+#include "gpuart_refit.h"
+
+namespace {
+
+const char LIB[] = "refit";
+
+#define RF_FN __device__ __forceinline__
+
+// the refs of a record (csrc/hip/device_scene.h GD_REF_*)
+constexpr uint32_t REF_LEAF = 0x80000000u, REF_INDEX = 0x0fffffffu;
+constexpr uint32_t NONE = GPUART_REFIT_NO_UPDATE;
+enum { WHY_ORDER = 1, WHY_RANGE = 2, WHY_RULE = 3 };  ///< low two bits of the status word
+
+/// What the device sequence leaves for the host, in device memory; all zero before a run. `refused` = ~(4 x index + why) of the first
+/// offending update — the largest over the updates (atomicMax) —, 0 while no update is refused.
+struct Status {
+    uint32_t refused;
+    uint32_t subnormal;  ///< some plane written fails plane_ok
+    float root_min[3], root_max[3];
+};
+
+/// csrc/hip/box_quick.h gq_plane_ok: zero, or at least 2^-60 in magnitude (false for NaN and for a subnormal number, which is kept here).
+RF_FN bool plane_ok(float p) { return p == 0.0f || (p >= 8.6736173798840355e-19f || p <= -8.6736173798840355e-19f); }
+
+RF_FN bool planes_ok(const float lo[3], const float hi[3]) {
+    bool ok = true;
+    for (int k = 0; k < 3; k++) ok = ok && plane_ok(lo[k]) && plane_ok(hi[k]);
+    return ok;
+}
+
+/// The box of the leaf whose primitives start at `first`: its primitives' boxes folded in leaf order; the count is in the first record.
+RF_FN void leaf_box(const float4 *prims, const float *pbox, uint32_t first, float lo[3], float hi[3]) {
+    const uint32_t cnt = __float_as_uint(prims[3 * (size_t)first].w) >> 2;
+    prim_rule::box_start(lo, hi);
+    for (uint32_t k = 0; k < cnt; k++) {
+        const float *b = pbox + 6 * ((size_t)first + k);
+        prim_rule::box_fold(lo, hi, b, b + 3);
+    }
+}
+
+/// The box of the interior node with record `r`: its lower child's box folded with its upper child's.
+RF_FN void record_box(const float4 *recs, uint32_t r, float lo[3], float hi[3]) {
+    const float4 *q = recs + 4 * (size_t)r;
+    const float4 a = q[0], b = q[1], c = q[2], d = q[3];
+    const float llo[3] = {a.x, a.y, a.z}, lhi[3] = {b.x, b.y, b.z}, hlo[3] = {c.x, c.y, c.z}, hhi[3] = {d.x, d.y, d.z};
+    prim_rule::box_start(lo, hi);
+    prim_rule::box_fold(lo, hi, llo, lhi);
+    prim_rule::box_fold(lo, hi, hlo, hhi);
+}
+
+RF_FN void node_box(const float4 *recs, const float4 *prims, const float *pbox, uint32_t ref, float lo[3], float hi[3]) {
+    if (ref & REF_LEAF) leaf_box(prims, pbox, ref & REF_INDEX, lo, hi);
+    else record_box(recs, ref, lo, hi);
+}
+
+// 1. One thread per update: ordinals ascending and in range, the payload inside the rule for the type the primitive has.
+__global__ void __launch_bounds__(256) k_rf_validate(const uint32_t *ord, const float4 *payload, uint32_t n, const float4 *prims, uint32_t n_prims,
+                                                     Status *st) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t p = ord[i];
+    uint32_t why = 0;
+    if (i > 0 && !(ord[i - 1] < p)) why = WHY_ORDER;
+    else if (p >= n_prims) why = WHY_RANGE;
+    else {
+        float d[prim_rule::PAYLOAD];
+        for (int k = 0; k < 4; k++) {
+            const float4 v = payload[4 * (size_t)i + k];
+            d[4 * k] = v.x; d[4 * k + 1] = v.y; d[4 * k + 2] = v.z; d[4 * k + 3] = v.w;
+        }
+        const uint32_t type = __float_as_uint(prims[3 * (size_t)p].w) & 3u;
+        if (!prim_rule::prim_ok(type, d)) why = WHY_RULE;
+    }
+    if (why) atomicMax(&st->refused, ~(4u * i + why));
+}
+
+// 2. One thread per update: the three float4 of the record by the uploader's arithmetic (Converter::pack_prim), word 3 of the first —
+// the type and the leaf's count — kept, and the primitive's own box. Nothing is written once an update is refused: the status word was
+// written by the launch before this one.
+__global__ void __launch_bounds__(256) k_rf_update(const uint32_t *ord, const float4 *payload, uint32_t n, float4 *prims, float *pbox, const Status *st) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n || st->refused) return;
+    const uint32_t p = ord[i];
+    float d[prim_rule::PAYLOAD];
+    for (int k = 0; k < 4; k++) {
+        const float4 v = payload[4 * (size_t)i + k];
+        d[4 * k] = v.x; d[4 * k + 1] = v.y; d[4 * k + 2] = v.z; d[4 * k + 3] = v.w;
+    }
+    float4 *rec = prims + 3 * (size_t)p;
+    const float T = rec[0].w;
+    const uint32_t type = __float_as_uint(T) & 3u;
+    float4 r0 = make_float4(d[0], d[1], d[2], T), r1, r2 = make_float4(0, 0, 0, 0);
+    if (type == prim_rule::SPHERE) r1 = make_float4(d[3], 0, 0, 0);
+    else if (type == prim_rule::DISC) r1 = make_float4(d[4], d[5], d[6], d[3]);
+    else if (type == prim_rule::TRIANGLE) {
+        r1 = make_float4(d[4] - d[0], d[5] - d[1], d[6] - d[2], 0);   // edge1 = v1 - v0
+        r2 = make_float4(d[8] - d[0], d[9] - d[1], d[10] - d[2], 0);  // edge2 = v2 - v0
+    } else {
+        r1 = make_float4(d[8], d[9], d[10], d[11]);
+        r2 = make_float4(d[3], d[12], d[13], d[14]);
+    }
+    rec[0] = r0; rec[1] = r1; rec[2] = r2;
+    float lo[3], hi[3];
+    prim_rule::prim_box(type, d, lo, hi);
+    float *b = pbox + 6 * (size_t)p;
+    for (int k = 0; k < 3; k++) { b[k] = lo[k]; b[3 + k] = hi[k]; }
+}
+
+// 3. One level of the tree: one thread per child of each of the level's records (`order` lists them). A leaf child's box comes from its
+// primitives' boxes, an interior child's from that child's own record, which a launch before this one wrote (it lies a level deeper).
+// The thread writes the twelve box floats of its child's two quads and leaves their fourth words alone: the refs, the
+// GPUART_HIP_TOP_DEPTH mark and the pad. Like the update it does nothing once an update is refused.
+__global__ void __launch_bounds__(256) k_rf_level(const uint32_t *order, uint32_t count, float4 *recs, const float4 *prims, const float *pbox, Status *st) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= 2u * count || st->refused) return;
+    const uint32_t r = order[t >> 1], c = t & 1u;
+    float4 *q = recs + 4 * (size_t)r;
+    const uint32_t ref = __float_as_uint(q[c].w);  // the lower child's ref is word 3 of quad 0, the upper child's of quad 1
+    float lo[3], hi[3];
+    node_box(recs, prims, pbox, ref, lo, hi);
+    float *f = (float *)(q + 2 * c);  // (the fourth words are not stored to: the sibling's thread reads one of them)
+    for (int k = 0; k < 3; k++) { f[k] = lo[k]; f[4 + k] = hi[k]; }
+    if (!planes_ok(lo, hi)) atomicOr(&st->subnormal, 1u);
+}
+
+/// Word 3 of every primitive's first quad (the type, and on a leaf's first primitive its count), gathered for the host's bind.
+__global__ void __launch_bounds__(256) k_rf_type_words(const float4 *prims, uint32_t n_prims, uint32_t *out) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n_prims) out[i] = __float_as_uint(prims[3 * (size_t)i].w);
+}
+
+// 4. The root's box, after the top level: from record 0, or from the primitives when the root is a leaf.
+__global__ void k_rf_root(const float4 *recs, const float4 *prims, const float *pbox, uint32_t root_ref, Status *st) {
+    if (blockIdx.x || threadIdx.x || st->refused) return;
+    float lo[3], hi[3];
+    node_box(recs, prims, pbox, root_ref, lo, hi);
+    for (int k = 0; k < 3; k++) { st->root_min[k] = lo[k]; st->root_max[k] = hi[k]; }
+    if (!planes_ok(lo, hi)) atomicOr(&st->subnormal, 1u);
+}
+
+}  // namespace
+
+struct gpuart_refit : ImageHandle {
+    Status *status = nullptr;    ///< device
+    DeviceBuffer order;          ///< record indices sorted by level, deepest level last
+    std::vector<uint32_t> level; ///< level l's records are order[level[l] .. level[l + 1])
+    DeviceBuffer staging;        ///< run_host: the ordinals, then the payload
+    bool bound = false;
+    gpuart_hip_scene scene{};    ///< what the handle is bound to
+};
+
+namespace {
+
+inline uint32_t ubits(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
+
+int check_scene(const gpuart_refit *h, const gpuart_hip_scene *s) {
+    if (!s) return fail(GPUART_HIP_ERR_ARG, "refit: scene is NULL");
+    if (!h->bound) return fail(GPUART_HIP_ERR_ARG, "refit: the handle is not bound to a scene");
+    if (s->generation != h->scene.generation || s->recs != h->scene.recs || s->prims != h->scene.prims || s->prim_boxes != h->scene.prim_boxes ||
+        s->n_recs != h->scene.n_recs || s->n_prims != h->scene.n_prims || s->root_ref != h->scene.root_ref)
+        return fail(GPUART_HIP_ERR_ARG, "refit: the handle was bound to another upload (generation " + std::to_string(h->scene.generation) + ", the scene's is " +
+                                            std::to_string(s->generation) + "): bind again");
+    return 0;
+}
+
+/// The device sequence on ordinals and payload in device memory, and the read-back.
+int run_device(gpuart_refit *h, const uint32_t *ord, const float4 *payload, uint32_t n, gpuart_refit_result *result) {
+    const gpuart_hip_scene &s = h->scene;
+    float4 *recs = (float4 *)s.recs, *prims = (float4 *)s.prims;
+    float *pbox = (float *)s.prim_boxes;
+    HIP_TRY(hipMemsetAsync(h->status, 0, sizeof(Status), h->stream));
+    if (n) {
+        const uint32_t blocks = (n + 255u) / 256u;
+        k_rf_validate<<<blocks, 256, 0, h->stream>>>(ord, payload, n, prims, (uint32_t)s.n_prims, h->status);
+        HIP_TRY(hipGetLastError());
+        k_rf_update<<<blocks, 256, 0, h->stream>>>(ord, payload, n, prims, pbox, h->status);
+        HIP_TRY(hipGetLastError());
+    }
+    const uint32_t *order = (const uint32_t *)h->order.mem;
+    for (size_t l = h->level.size() - 1; l-- > 0;) {  // deepest level first
+        const uint32_t count = h->level[l + 1] - h->level[l];
+        k_rf_level<<<(2u * count + 255u) / 256u, 256, 0, h->stream>>>(order + h->level[l], count, recs, prims, pbox, h->status);
+        HIP_TRY(hipGetLastError());
+    }
+    k_rf_root<<<1, 64, 0, h->stream>>>(recs, prims, pbox, s.root_ref, h->status);
+    HIP_TRY(hipGetLastError());
+    Status st;
+    HIP_TRY(hipMemcpyAsync(&st, h->status, sizeof st, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const uint32_t key = ~st.refused;  // 4 x index + why
+    if (result) {
+        result->status = st.refused ? GPUART_HIP_ERR_ARG : 0;
+        result->first_bad = st.refused ? key >> 2 : NONE;
+        result->subnormal = st.subnormal;
+        memcpy(result->root_min, st.refused ? s.root_min : st.root_min, 12);
+        memcpy(result->root_max, st.refused ? s.root_max : st.root_max, 12);
+    }
+    if (st.refused) {
+        static const char *const WHY[4] = {"", "its ordinal does not exceed the one before it (ordinals are strictly ascending)",
+                                           "its ordinal is not below the number of primitives",
+                                           "its payload is outside the primitive rule (a word that is not finite or beyond 2^20, a negative radius or length, "
+                                           "or a cone's derived constants that contradict its centres and radii)"};
+        return fail(GPUART_HIP_ERR_ARG, "refit: update " + std::to_string(key >> 2) + " refused: " + WHY[key & 3u] + "; nothing was written");
+    }
+    memcpy(h->scene.root_min, st.root_min, 12);
+    memcpy(h->scene.root_max, st.root_max, 12);
+    return 0;
+}
+
+int check_run(gpuart_refit *h, const gpuart_hip_scene *scene, const void *ordinals, const void *payload, size_t n, size_t align) {
+    if (int rc = check_handle(LIB, h)) return rc;
+    if (int rc = check_scene(h, scene)) return rc;
+    if (n > h->scene.n_prims) return fail(GPUART_HIP_ERR_ARG, "refit: more updates (" + std::to_string(n) + ") than primitives (" + std::to_string(h->scene.n_prims) + ")");
+    if (n && (!ordinals || !payload)) return fail(GPUART_HIP_ERR_ARG, "refit: ordinals or payload is NULL");
+    if (n && (misaligned({ordinals}, 4) || misaligned({payload}, align)))
+        return fail(GPUART_HIP_ERR_ARG, "refit: misaligned pointer (ordinals need 4 bytes, payload " + std::to_string(align) + ")");
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char *gpuart_refit_last_error(void) { return g_last_error.c_str(); }
+
+int gpuart_refit_create(int device, gpuart_refit **out) {
+    if (int rc = create_handle(LIB, device, out)) return rc;
+    gpuart_refit *h = *out;
+    *out = nullptr;
+    const hipError_t e = hipMalloc((void **)&h->status, sizeof(Status));
+    if (e != hipSuccess) {
+        gpuart_refit_destroy(h);
+        return fail(GPUART_HIP_ERR_DEVICE, std::string("refit: allocating the status: ") + hipGetErrorString(e));
+    }
+    *out = h;
+    return 0;
+}
+
+int gpuart_refit_destroy(gpuart_refit *h) {
+    if (!h) return 0;
+    destroy_handle(h, {h->status, h->order.mem, h->staging.mem});
+    delete h;
+    return 0;
+}
+
+int gpuart_refit_finish(gpuart_refit *h) { return finish_handle(LIB, h); }
+
+int gpuart_refit_bind(gpuart_refit *h, const gpuart_hip_scene *s) {
+    if (int rc = check_handle(LIB, h)) return rc;
+    if (!s) return fail(GPUART_HIP_ERR_ARG, "refit: scene is NULL");
+    h->bound = false;
+    if (s->layout != 1) return fail(GPUART_HIP_ERR_ARG, "refit: unknown layout " + std::to_string(s->layout));
+    if (s->exact_boxes) return fail(GPUART_HIP_ERR_ARG, "refit: a tree with irregular boxes (or boxes that do not bound their contents) is not refitted");
+    if (!s->prims || !s->prim_boxes || !s->n_prims || (s->n_recs && !s->recs) || s->n_prims > REF_INDEX || s->n_recs > REF_INDEX)
+        return fail(GPUART_HIP_ERR_ARG, "refit: the scene's arrays or counts are empty or out of range");
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t n_recs = s->n_recs, n_prims = s->n_prims;
+    // every leaf's count, which its first primitive carries, and the records
+    std::vector<float> recs(16 * n_recs);
+    std::vector<uint32_t> tw(n_prims);
+    if (n_recs) HIP_TRY(hipMemcpy(recs.data(), s->recs, recs.size() * 4, hipMemcpyDeviceToHost));
+    if (int rc = ensure(h->stream, h->staging, n_prims * 4)) return rc;
+    k_rf_type_words<<<(uint32_t)((n_prims + 255) / 256), 256, 0, h->stream>>>((const float4 *)s->prims, (uint32_t)n_prims, (uint32_t *)h->staging.mem);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(tw.data(), h->staging.mem, n_prims * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    const auto leaf_ok = [&](uint32_t ref) {
+        const size_t first = ref & REF_INDEX;
+        if (first >= n_prims) return false;
+        const size_t cnt = tw[first] >> 2;
+        return cnt >= 1 && cnt <= n_prims - first;
+    };
+    // Records lie in pre-order: a child's record comes after its parent's, and every record but the root's is some record's child once.
+    std::vector<uint32_t> depth(n_recs, 0);
+    std::vector<char> seen(n_recs, 0);
+    uint32_t deepest = 0;
+    const auto bad_tree = [] { return fail(GPUART_HIP_ERR_ARG, "refit: the records' refs do not form the tree the counts describe"); };
+    if (n_recs ? s->root_ref != 0 : !((s->root_ref & REF_LEAF) && leaf_ok(s->root_ref))) return bad_tree();
+    for (size_t r = 0; r < n_recs; r++) {
+        if (r && !seen[r]) return bad_tree();
+        for (int c = 0; c < 2; c++) {
+            const uint32_t ref = ubits(recs[16 * r + 4 * c + 3]);
+            if (ref & REF_LEAF) {
+                if (!leaf_ok(ref)) return bad_tree();
+            } else {
+                if (ref <= r || ref >= n_recs || seen[ref]) return bad_tree();
+                seen[ref] = 1;
+                depth[ref] = depth[r] + 1;
+                if (depth[ref] > deepest) deepest = depth[ref];
+            }
+        }
+    }
+    // a counting sort by level
+    const size_t levels = n_recs ? (size_t)deepest + 1 : 0;
+    h->level.assign(levels + 1, 0);
+    for (size_t r = 0; r < n_recs; r++) h->level[depth[r] + 1]++;
+    for (size_t l = 0; l < levels; l++) h->level[l + 1] += h->level[l];
+    std::vector<uint32_t> order(n_recs), at(h->level.begin(), h->level.end() - 1);
+    for (size_t r = 0; r < n_recs; r++) order[at[depth[r]]++] = (uint32_t)r;
+    if (n_recs) {
+        if (int rc = ensure(h->stream, h->order, n_recs * 4)) return rc;
+        HIP_TRY(hipMemcpy(h->order.mem, order.data(), n_recs * 4, hipMemcpyHostToDevice));
+    }
+    h->scene = *s;
+    h->bound = true;
+    return 0;
+}
+
+int gpuart_refit_levels(gpuart_refit *h, uint32_t *levels) {
+    if (int rc = check_handle(LIB, h)) return rc;
+    if (!levels) return fail(GPUART_HIP_ERR_ARG, "refit: levels is NULL");
+    if (!h->bound) return fail(GPUART_HIP_ERR_ARG, "refit: the handle is not bound to a scene");
+    *levels = (uint32_t)(h->level.size() - 1);
+    return 0;
+}
+
+int gpuart_refit_run(gpuart_refit *h, const gpuart_hip_scene *scene, const uint32_t *ordinals, const float *payload, size_t n,
+                     gpuart_refit_result *result) {
+    if (int rc = check_run(h, scene, ordinals, payload, n, 16)) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    return run_device(h, ordinals, (const float4 *)payload, (uint32_t)n, result);
+}
+
+int gpuart_refit_run_host(gpuart_refit *h, const gpuart_hip_scene *scene, const uint32_t *ordinals, const float *payload, size_t n,
+                          gpuart_refit_result *result) {
+    if (int rc = check_run(h, scene, ordinals, payload, n, 4)) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    if (!n) return run_device(h, nullptr, nullptr, 0, result);
+    // the payload first: it is read as float4
+    if (int rc = ensure(h->stream, h->staging, n * (64 + 4))) return rc;
+    float4 *dpay = (float4 *)h->staging.mem;
+    uint32_t *dord = (uint32_t *)((char *)h->staging.mem + n * 64);
+    HIP_TRY(hipMemcpyAsync(dpay, payload, n * 64, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(dord, ordinals, n * 4, hipMemcpyHostToDevice, h->stream));
+    return run_device(h, dord, dpay, (uint32_t)n, result);
+}
+
+}  // extern "C"

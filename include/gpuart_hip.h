@@ -259,6 +259,34 @@ int gpuart_hip_kernel_time(gpuart_hip_ctx *ctx, int cls, double *total_ms, uint6
 int gpuart_hip_scene_info(gpuart_hip_ctx *ctx, uint64_t *nodes, uint64_t *prims, uint32_t *max_depth,
                           uint64_t *device_bytes);
 
+/* ---- the uploaded scene's device arrays, for a refit in place (include/gpuart_refit.h; DESIGN.md "Refit") ----------------------
+ * The arrays stay the context's: they are valid until the next gpuart_hip_upload_bvh or gpuart_hip_destroy, and `generation`, which
+ * every upload increments, tells a holder of this struct that it is stale. */
+typedef struct gpuart_hip_scene {
+    uint32_t layout;      /* 1: the records of DESIGN.md section 3 (64-byte two-children records, 48-byte primitive records) */
+    uint32_t exact_boxes; /* the uploader classified the tree irregular or disorderly (gpuart_hip_tree_order: 2) */
+    void *recs;           /* device: n_recs records of four float4, pre-order */
+    uint64_t n_recs;      /* 0: the root is a leaf */
+    void *prims;          /* device: n_prims records of three float4, in the order the leaves are met */
+    uint64_t n_prims;
+    void *prim_boxes;     /* device: n_prims x 6 floats, the box each primitive's constructor gives it (min xyz, max xyz) — which the
+                           * records no longer say: a triangle keeps its edges, a cone one centre. Made on the first call after an upload. */
+    float root_min[3], root_max[3];
+    uint32_t root_ref;
+    float box_slack;
+    uint32_t max_depth;
+    uint64_t generation;
+} gpuart_hip_scene;
+/* Flushes the collected passes and waits for every pass lane and the primary stream — passes requested before the call render the
+ * scene as it is now — and fills *out. GPUART_HIP_ERR_ARG without a scene or with out == NULL. */
+int gpuart_hip_scene_device(gpuart_hip_ctx *ctx, gpuart_hip_scene *out);
+/* Adopts a refit of the arrays in place (the caller has waited for it): the new root box; box_slack by the uploader's own rule, +inf
+ * when `subnormal` (some box plane is within 2^-60 of zero without being zero) or quick boxes are off, else the slack of the root's
+ * largest plane; and the pass kernels' block order is counted again by the next run. The primitive count, the type mask, the tree
+ * order, max_depth and the root ref do not change. GPUART_HIP_ERR_ARG, with nothing changed, without a scene, on a tree the uploader
+ * classified irregular or disorderly, and for a root box that is not finite and ordered. */
+int gpuart_hip_scene_refitted(gpuart_hip_ctx *ctx, const float root_min[3], const float root_max[3], int subnormal);
+
 /* How the fast kernels walk the uploaded tree: 1 (the default for every tree of regular boxes since round 5) in the reference's order —
  * lower child first, shaders/bvh_intersection.glsl:432-441 — which is the only order PROVEN to return the reference's winner; 2 in the
  * reference's order with comparison-form box tests, because a box is irregular or does not bound its contents
