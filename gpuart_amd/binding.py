@@ -4,6 +4,7 @@ GPUART_LIBDIR selects another build of the pair: gpuart_amd/lib_test (the produc
 what tests/conftest.py chooses), or an A/B variant under gpuart_amd/lib_ab/."""
 import ctypes as C
 import os
+import sys
 
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")  # see libgpuart_hip's request_hw_queues(); before any HIP initialisation
 
@@ -61,7 +62,14 @@ class RefitResult(C.Structure):
     _fields_ = [("status", C.c_int32), ("first_bad", C.c_uint32), ("subnormal", C.c_uint32), ("root_min", C.c_float * 3), ("root_max", C.c_float * 3)]
 
 
+class BuildResult(C.Structure):
+    """gpuart_build_result (include/gpuart_build.h)."""
+    _fields_ = [("n_recs", C.c_uint64), ("root_ref", C.c_uint32), ("max_depth", C.c_uint32), ("subnormal", C.c_uint32), ("levels", C.c_uint32),
+                ("root_min", C.c_float * 3), ("root_max", C.c_float * 3)]
+
+
 REFIT_PAYLOAD = 16  # GPUART_REFIT_PAYLOAD
+BUILD_STEPS = ("keys", "sort", "permute", "hierarchy", "number", "emit", "levels")  # gpuart_build_step_ms
 RAY_HIT = np.dtype([("pos", np.float32), ("p", np.float32, 3), ("n", np.float32, 3), ("type", np.int32)])
 RAYS_OCCLUSION = 1  # GPUART_HIP_RAYS_OCCLUSION
 
@@ -364,6 +372,12 @@ def refit_lib():
     return _image_lib("refit")
 
 
+def build_lib():
+    """libgpuart_build.so (include/gpuart_build.h), built by the image libraries' rule; raises NativeLibraryMissing if it has not been built
+    (no fallback)."""
+    return _image_lib("build")
+
+
 def display_lib():
     """libgpuart_display.so; raises NativeLibraryMissing if it has not been built (no fallback)."""
     return _image_lib("display")
@@ -421,6 +435,43 @@ def compile_bvh(descs, max_levels=1024, min_prims=2):
     out = np.ctypeslib.as_array(q, shape=(nq.value, 4)).copy()
     L.gpuart_free(q)
     return out, depth.value
+
+
+def rebuild_tree(quads, order=None):
+    """gpuart_rebuild_tree: BoundingVolumesHierarchy::RebuildMorton on the compiled tree `quads`, without a device -> (quads', new_to_old).
+    `order`: the permutation to check instead of sorting. ValueError for a malformed tree (-1) or a refusal (-2)."""
+    L = host_lib()
+    q = np.ascontiguousarray(quads, np.float32).reshape(-1)
+    o = None if order is None else np.ascontiguousarray(order, np.uint32).reshape(-1)
+    out = C.POINTER(C.c_float)()
+    nout = C.c_size_t(0)
+    perm = np.zeros(max(1, q.size // 8), np.uint32)   # (a primitive takes at least two quads)
+    rc = L.gpuart_rebuild_tree(_p(q), C.c_size_t(q.size // 4), _p(o) if o is not None else None, C.byref(out), C.byref(nout), _p(perm))
+    if rc != 0:
+        raise ValueError("gpuart_rebuild_tree: %d" % rc)
+    res = np.ctypeslib.as_array(out, shape=(nout.value, 4)).copy()
+    L.gpuart_free(out)
+    n = int(o.size) if o is not None else None
+    if n is None:
+        n = sum(1 for _ in _leaf_prims(res))
+    return res, perm[:n].copy()
+
+
+def _leaf_prims(quads):
+    """The header quad address of every primitive of a canonical compiled tree, in the order the leaves are met."""
+    bits = np.ascontiguousarray(quads, np.float32).view(np.uint32)
+    stack = [0]
+    while stack:
+        a = stack.pop()
+        flags = int(bits[a + 2, 0])
+        if flags & 0x80000000:
+            at = a + 3
+            for _ in range(flags & 0x1fffffff):
+                yield at
+                at += 2 + int(bits[at, 0])
+        else:
+            stack.append(int(bits[a + 2, 2]))
+            stack.append(int(bits[a + 2, 1]))
 
 
 def last_build_ms():
@@ -704,6 +755,9 @@ class Backend:
         if getattr(self, "_refit", None) is not None:
             refit_lib().gpuart_refit_destroy(self._refit)
             self._refit = None
+        if getattr(self, "_build", None) is not None:
+            build_lib().gpuart_build_destroy(self._build)
+            self._build = None
         if self.owned and self.ctx:
             self.L.gpuart_hip_destroy(self.ctx)
             self.ctx = None
@@ -790,6 +844,74 @@ class Backend:
             e = HipError("gpuart_refit error %d: %s" % (rc, refit_lib().gpuart_refit_last_error().decode()))
             e.code = rc
             e.first_bad = int(res.first_bad) if res is not None and res.status else None
+            raise e
+
+    # a rebuild on the device (include/gpuart_build.h)
+    def scene_reserve(self, n_recs):
+        """gpuart_hip_scene_reserve: the context's spare arrays, with room for n_recs records, as a HipScene."""
+        s = HipScene()
+        self._chk(self.L.gpuart_hip_scene_reserve(self.ctx, C.c_uint64(n_recs), C.byref(s)))
+        return s
+
+    def scene_rebuilt(self, built):
+        self._chk(self.L.gpuart_hip_scene_rebuilt(self.ctx, C.byref(built)))
+
+    def _build_handle(self):
+        if getattr(self, "_build", None) is None:
+            h = C.c_void_p()
+            self._chk_build(build_lib().gpuart_build_create(C.c_int(self.device), C.byref(h)))
+            self._build = h
+        return self._build
+
+    def rebuild(self, out=None):
+        """Rebuilds the uploaded scene's tree on the device in Morton order (include/gpuart_build.h) and has the context adopt it: the
+        primitives are renumbered, new device ordinal p is the old new_to_old[p]. Returns new_to_old: when torch is in use (the process
+        has imported it) an int32 tensor on this device, and nothing crosses the host; else a NumPy uint32 array. `out` overrides that:
+        a contiguous int32 torch tensor of n_prims entries on this device is written in place and returned, True makes one, False asks
+        for the NumPy array. What the build reported is kept in `last_rebuild`: dict(n_recs, root_ref, max_depth, subnormal, levels,
+        root_min, root_max, step_ms). A refusal raises HipError with code -1 (ERR_ARG) and nothing changed. Passes requested before
+        the call render the old tree."""
+        Bd = build_lib()
+        h = self._build_handle()
+        scene = self.scene_device()
+        n = int(scene.n_prims)
+        spare = self.scene_reserve((n + 1) // 2 - 1 if n else 0)
+        res = BuildResult()
+        if out is None:
+            out = "torch" in sys.modules
+        if out is False:
+            perm = np.zeros(n, np.uint32)
+            rc = Bd.gpuart_build_run_host(h, C.byref(scene), C.byref(spare), _p(perm), C.byref(res))
+        else:
+            import torch
+            perm = torch.empty((n,), dtype=torch.int32, device="cuda:%d" % self.device) if out is True else out
+            if not (hasattr(perm, "data_ptr") and perm.is_cuda and perm.is_contiguous() and perm.dtype == torch.int32 and perm.numel() == n):
+                raise ValueError("rebuild: out must be a contiguous int32 tensor of n_prims entries on the device")
+            torch.cuda.synchronize(perm.device)
+            rc = Bd.gpuart_build_run(h, C.byref(scene), C.byref(spare), C.c_void_p(perm.data_ptr()), C.byref(res))
+        self._chk_build(rc)
+        spare.n_recs, spare.root_ref, spare.max_depth = res.n_recs, res.root_ref, res.max_depth
+        spare.root_min, spare.root_max = res.root_min, res.root_max
+        spare.box_slack = float("inf") if res.subnormal else 0.0
+        self.scene_rebuilt(spare)
+        ms = (C.c_double * 7)()
+        self._chk_build(Bd.gpuart_build_step_ms(h, ms))
+        self.last_rebuild = dict(n_recs=int(res.n_recs), root_ref=int(res.root_ref), max_depth=int(res.max_depth), subnormal=bool(res.subnormal),
+                                 levels=int(res.levels), root_min=np.array(res.root_min[:], np.float32), root_max=np.array(res.root_max[:], np.float32),
+                                 step_ms=dict(zip(BUILD_STEPS, [float(v) for v in ms])))
+        return perm
+
+    def tree_cost(self):
+        """gpuart_build_cost of the uploaded scene's tree: the sum over its records of both children's half-areas over the root's."""
+        cost = C.c_double()
+        scene = self.scene_device()
+        self._chk_build(build_lib().gpuart_build_cost(self._build_handle(), C.byref(scene), C.byref(cost)))
+        return float(cost.value)
+
+    def _chk_build(self, rc):
+        if rc != 0:
+            e = HipError("gpuart_build error %d: %s" % (rc, build_lib().gpuart_build_last_error().decode()))
+            e.code = rc
             raise e
 
     # rendering
@@ -1161,6 +1283,35 @@ class Renderer:
         if idx.size != len(arr):
             raise ValueError("update_primitives: one description per index")
         return bool(self.L.gpuart_renderer_update_primitives(self.h, _p(idx), arr, C.c_int(len(arr))))
+
+    def rebuild_tree(self):
+        """Renderer::RebuildTree: the tree rebuilt on the device in Morton order, the temporal history kept. Returns new_to_old (per new
+        device ordinal the old one; the indices of update_primitives and the ordinals of trace_rays keep numbering the descriptions
+        set_primitives was given), or None — nothing changed — on a refusal."""
+        n = C.c_uint64()
+        self.L.gpuart_renderer_scene_info(self.h, None, C.byref(n), None)
+        perm = np.zeros(int(n.value), np.uint32)
+        return perm if self.L.gpuart_renderer_rebuild_tree(self.h, _p(perm)) else None
+
+    def tree_cost(self):
+        """Renderer::TreeCost, or None on failure."""
+        cost = C.c_double()
+        return float(cost.value) if self.L.gpuart_renderer_tree_cost(self.h, C.byref(cost)) else None
+
+    def last_rebuild_ms(self):
+        out = (C.c_double * 2)()
+        self.L.gpuart_renderer_last_rebuild_ms(self.h, out)
+        return float(out[0]), float(out[1])
+
+    def compile_bvh(self):
+        """GetBVH().Compile() -> quads (n, 4) float32."""
+        q = C.POINTER(C.c_float)()
+        nq = C.c_size_t(0)
+        if self.L.gpuart_renderer_compile_bvh(self.h, C.byref(q), C.byref(nq)) != 0:
+            raise RuntimeError("gpuart_renderer_compile_bvh failed")
+        out = np.ctypeslib.as_array(q, shape=(nq.value, 4)).copy()
+        self.L.gpuart_free(q)
+        return out
 
     def init_box(self): self.L.gpuart_renderer_init_box(self.h)
     def init_dragon(self, path): return bool(self.L.gpuart_renderer_init_dragon(self.h, path.encode()))

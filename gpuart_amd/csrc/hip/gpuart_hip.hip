@@ -178,6 +178,11 @@ struct gpuart_hip_ctx {
     uint64_t n_recs = 0, generation = 0;
     std::vector<float, UninitAlloc<float>> h_prim_boxes;
     float *d_prim_boxes = nullptr;
+    // For a rebuild (gpuart_hip_scene_reserve): a spare set of the three arrays, which a rebuild fills and gpuart_hip_scene_rebuilt swaps
+    // with the scene's. Freed by the next upload.
+    float4 *d_spare_recs = nullptr, *d_spare_prims = nullptr;
+    float *d_spare_boxes = nullptr;
+    uint64_t spare_recs = 0, spare_prims = 0;  ///< what the spare set holds room for
     float4 *d_direct = nullptr, *d_accum = nullptr;
     unsigned long long *d_counters = nullptr;
     /// Tile size, run lengths, lanes in use, execution mode (gpuart_hip_set_mode: 0 fast — launch pipeline, or k_run for a small
@@ -417,6 +422,14 @@ float tree_slack(const Converter &cv, const Converter::Child &root) {
     return slack_of_root(cv.irregular || cv.disorderly || cv.subnormal, root.bmin, root.bmax);
 }
 
+void drop_spare(gpuart_hip_ctx *c) {
+    void *ptrs[] = {c->d_spare_recs, c->d_spare_prims, c->d_spare_boxes};
+    for (void *p : ptrs) if (p) (void)hipFree(p);
+    c->d_spare_recs = c->d_spare_prims = nullptr;
+    c->d_spare_boxes = nullptr;
+    c->spare_recs = c->spare_prims = 0;
+}
+
 Scene scene_of(const gpuart_hip_ctx *c) {
     Scene s;
     s.recs = c->d_recs;
@@ -611,7 +624,7 @@ int gpuart_hip_destroy(gpuart_hip_ctx *c) {
     if (c->comm && !comm_stuck) (void)comm_drop(c);
     void *ptrs[] = {c->d_recs, c->d_prims, c->d_spill, c->d_direct, c->d_accum, c->d_counters, c->d_scratch, c->d_cursor,
                     c->d_query_cursor, c->d_tile_order[0], c->d_tile_order[1], c->d_tile_cost, c->d_tile_xy, c->d_active, c->d_block_paths,
-                    c->d_prim_boxes};
+                    c->d_prim_boxes, c->d_spare_recs, c->d_spare_prims, c->d_spare_boxes};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     void *comm_ptrs[] = {c->d_send, c->d_stage, c->d_hello};
     for (void *p : comm_ptrs) if (p && !comm_stuck) (void)hipFree(p);
@@ -687,6 +700,7 @@ int gpuart_hip_upload_bvh(gpuart_hip_ctx *c, const float *quads, size_t nquads) 
     c->generation++;
     if (c->d_prim_boxes) { (void)hipFree(c->d_prim_boxes); c->d_prim_boxes = nullptr; }
     c->h_prim_boxes.swap(cv.pbox);
+    drop_spare(c);
     if ((r = ensure_spill(c))) return r;
     c->have_scene = true;
     c->order_stale = true;
@@ -1283,6 +1297,80 @@ int gpuart_hip_scene_refitted(gpuart_hip_ctx *c, const float root_min[3], const 
     if ((r = drain(c))) return r;
     memcpy(c->root_min, root_min, 12); memcpy(c->root_max, root_max, 12);
     c->box_slack = c->quick_boxes ? slack_of_root(subnormal != 0, c->root_min, c->root_max) : __builtin_inff();
+    c->order_stale = true;
+    return 0;
+}
+
+// ---- a rebuild on the device (include/gpuart_build.h): host code only ------------------------------------------------------------
+int gpuart_hip_scene_reserve(gpuart_hip_ctx *c, uint64_t n_recs, gpuart_hip_scene *out) {
+    if (!c || !out) return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_reserve: bad argument");
+    if (!c->have_scene) return fail(GPUART_HIP_ERR_ARG, "no scene uploaded");
+    if (n_recs > 0x03fffff0u) return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_reserve: too many records");
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->d_spare_prims || c->spare_recs < n_recs || c->spare_prims != c->n_prims) {
+        drop_spare(c);
+        // (the same slack past the end as an upload's arrays, and like theirs zeroed)
+        const size_t rb = ((size_t)n_recs * 4 + 4) * sizeof(float4), pb = ((size_t)c->n_prims * 3 + 4) * sizeof(float4), bb = (size_t)c->n_prims * 24 + 16;
+        HIP_TRY(hipMalloc(&c->d_spare_recs, rb));
+        HIP_TRY(hipMalloc(&c->d_spare_prims, pb));
+        HIP_TRY(hipMalloc(&c->d_spare_boxes, bb));
+        HIP_TRY(hipMemset(c->d_spare_recs, 0, rb));
+        HIP_TRY(hipMemset(c->d_spare_prims, 0, pb));
+        HIP_TRY(hipMemset(c->d_spare_boxes, 0, bb));
+        c->spare_recs = n_recs;
+        c->spare_prims = c->n_prims;
+    } else {
+        // a reused set (after a rebuild: the scene's former arrays) still holds the records of the tree it was; beyond the n_recs
+        // about to be written it is zeroed again, so the arrays of a rebuilt scene end as an upload's do
+        HIP_TRY(hipMemset((char *)c->d_spare_recs + (size_t)n_recs * 64, 0, (size_t)(c->spare_recs - n_recs) * 64 + 4 * sizeof(float4)));
+    }
+    memset(out, 0, sizeof *out);
+    out->layout = 1;
+    out->recs = c->d_spare_recs; out->n_recs = c->spare_recs;
+    out->prims = c->d_spare_prims; out->n_prims = c->spare_prims;
+    out->prim_boxes = c->d_spare_boxes;
+    out->generation = c->generation;
+    return 0;
+}
+
+int gpuart_hip_scene_rebuilt(gpuart_hip_ctx *c, const gpuart_hip_scene *b) {
+    if (!c || !b) return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_rebuilt: bad argument");
+    if (!c->have_scene) return fail(GPUART_HIP_ERR_ARG, "no scene uploaded");
+    if (c->exact_boxes) return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_rebuilt: a tree with irregular boxes (or boxes that do not bound their contents) is not rebuilt");
+    if (!c->d_spare_prims || b->recs != (void *)c->d_spare_recs || b->prims != (void *)c->d_spare_prims || b->prim_boxes != (void *)c->d_spare_boxes ||
+        b->generation != c->generation || b->layout != 1)
+        return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_rebuilt: the arrays are not the ones gpuart_hip_scene_reserve handed out for this scene");
+    if (b->n_prims != c->n_prims) return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_rebuilt: the primitive count changed");
+    if (b->n_recs > c->spare_recs) return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_rebuilt: more records than were reserved");
+    if (b->max_depth > 1024) return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_rebuilt: tree deeper than 1024 levels");
+    for (int k = 0; k < 3; k++)
+        if (!(b->root_min[k] <= b->root_max[k]) || std::isinf(b->root_min[k]) || std::isinf(b->root_max[k]))
+            return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_rebuilt: the root box is not finite and ordered");
+    if (!c->d_prim_boxes) return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_rebuilt: gpuart_hip_scene_device was not called for this scene");
+    if (b->n_recs ? b->root_ref != 0 : !((b->root_ref & GD_REF_LEAF) && (b->root_ref & GD_REF_INDEX) < c->n_prims))
+        return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_rebuilt: the root ref is neither record 0 of a tree with records nor a leaf inside the primitives");
+    HIP_TRY(hipSetDevice(c->device));
+    int r;
+    if ((r = gpuart_hip_flush(c))) return r;
+    if ((r = drain(c))) return r;
+    // the traversal stacks for the new depth first: a failure here must leave the scene as it was
+    const uint32_t old_depth = c->max_depth;
+    c->max_depth = b->max_depth;
+    if ((r = ensure_spill(c))) { c->max_depth = old_depth; return r; }
+    std::swap(c->d_recs, c->d_spare_recs);
+    std::swap(c->d_prims, c->d_spare_prims);
+    std::swap(c->d_prim_boxes, c->d_spare_boxes);
+    const uint64_t old_recs = c->n_recs;
+    c->n_recs = b->n_recs;
+    c->spare_recs = old_recs;
+    memcpy(c->root_min, b->root_min, 12); memcpy(c->root_max, b->root_max, 12);
+    c->root_ref = b->root_ref;
+    c->max_depth = b->max_depth;
+    c->n_nodes = 2 * c->n_recs + 1;
+    c->scene_bytes = (size_t)c->n_recs * 64 + (size_t)c->n_prims * 48;
+    // `box_slack` of the built scene says +inf when the builder met a subnormal plane (gpuart_build_result.subnormal)
+    c->box_slack = c->quick_boxes ? slack_of_root(std::isinf(b->box_slack), c->root_min, c->root_max) : __builtin_inff();
+    c->generation++;
     c->order_stale = true;
     return 0;
 }

@@ -496,6 +496,136 @@ bool BoundingVolumesHierarchy::Refit(const uint32_t *indices, const Primitive *c
     return CheckRefit(indices, payloads.data(), n, firstBad, types.data()) && Refit(indices, payloads.data(), n, firstBad);
 }
 
+// ---- rebuild in Morton order: the host's statement of include/gpuart_build.h (tests/build_ref.py is the restatement) ----------------
+namespace {
+/// Bits of a 21-bit number spread to every third bit.
+inline uint64_t spread3(uint32_t q) {
+    uint64_t x = q & 0x1fffffu;
+    x = (x | x << 32) & 0x1f00000000ffffull;
+    x = (x | x << 16) & 0x1f0000ff0000ffull;
+    x = (x | x << 8) & 0x100f00f00f00f00full;
+    x = (x | x << 4) & 0x10c30c30c30c30c3ull;
+    x = (x | x << 2) & 0x1249249249249249ull;
+    return x;
+}
+/// The 63-bit key of a box in the root box [rlo, rhi]: fp32, no contraction, IEEE division.
+inline uint64_t morton_key(const float lo[3], const float hi[3], const float rlo[3], const float rhi[3]) {
+    uint64_t key = 0;
+    for (int k = 0; k < 3; k++) {
+        const float c = lo[k] * 0.5f + hi[k] * 0.5f;
+        const float e = rhi[k] - rlo[k];
+        const float t = (c - rlo[k]) / e;
+        uint32_t q = 0;
+        if (e > 0.0f && t > 0.0f) {
+            const float v = t * 2097152.0f;
+            q = v >= 2097151.0f ? 2097151u : (uint32_t)v;
+        }
+        key |= spread3(q) << (2 - k);
+    }
+    return key;
+}
+/// delta(i, j) of leaves i != j: the common prefix of their keys, or past 64 that of their indices.
+inline int leaf_delta(const std::vector<uint64_t> &K, uint32_t i, uint32_t j) {
+    const uint64_t x = K[i] ^ K[j];
+    return x ? __builtin_clzll(x) : 64 + __builtin_clz(i ^ j);
+}
+}  // namespace
+
+bool BoundingVolumesHierarchy::RebuildMorton(std::vector<uint32_t> *newToOld, const uint32_t *order) {
+    const size_t n = NumPrimitives;
+    if (n == 0 || n > 0x0fffffffu) return false;
+    // every primitive's header in LeafData, by old ordinal, and its box
+    std::vector<size_t> header(n);
+    {
+        size_t k = 0;
+        for (const Node &node : Nodes) {
+            size_t at = node.dataBegin;
+            for (uint32_t j = 0; j < node.count; j++, k++) {
+                if (k >= n || node.primFirst + j != k) return false;
+                header[k] = at;
+                at += RGBA_ELEMS * (2 + (size_t)(as_uint(LeafData[at]) & 3));
+            }
+        }
+        if (k != n) return false;
+    }
+    std::vector<float> box(6 * n);
+    float rlo[3], rhi[3];
+    prim_rule::box_start(rlo, rhi);
+    for (size_t k = 0; k < n; k++) {
+        prim_rule::prim_box(as_uint(LeafData[header[k]]) & 3, &LeafData[header[k] + RGBA_ELEMS], &box[6 * k], &box[6 * k + 3]);
+        prim_rule::box_fold(rlo, rhi, &box[6 * k], &box[6 * k + 3]);
+    }
+    std::vector<uint64_t> key(n);
+    for (size_t k = 0; k < n; k++) key[k] = morton_key(&box[6 * k], &box[6 * k + 3], rlo, rhi);
+    std::vector<uint32_t> perm(n);
+    if (order) {
+        // a given order is only checked: a permutation, ascending by (key, old ordinal)
+        std::vector<bool> seen(n, false);
+        for (size_t p = 0; p < n; p++) {
+            const uint32_t o = order[p];
+            if (o >= n || seen[o]) return false;
+            seen[o] = true;
+            if (p && !(key[order[p - 1]] < key[o] || (key[order[p - 1]] == key[o] && order[p - 1] < o))) return false;
+            perm[p] = o;
+        }
+    } else {
+        for (size_t k = 0; k < n; k++) perm[k] = (uint32_t)k;
+        std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
+    }
+    const uint32_t m = (uint32_t)((n + 1) / 2);
+    std::vector<uint64_t> K(m);
+    for (uint32_t j = 0; j < m; j++) K[j] = key[perm[2 * (size_t)j]];
+
+    // the nodes in pre-order, from an explicit stack of leaf ranges (the upper child waits while the lower subtree is laid out)
+    struct Todo { uint32_t a, b, parent; bool isLower; unsigned level; };
+    std::vector<Node, UninitAlloc<Node>> nodes;
+    std::vector<float, UninitAlloc<float>> data;
+    nodes.reserve(2 * (size_t)m - 1);
+    data.reserve(LeafData.size());
+    std::vector<Todo> todo{{0, m - 1, 0, false, 0}};
+    unsigned depth = 0;
+    while (!todo.empty()) {
+        const Todo t = todo.back();
+        todo.pop_back();
+        const uint32_t self = (uint32_t)nodes.size();
+        Node node;
+        for (int k = 0; k < 3; k++) node.lo[k] = node.hi[k] = 0;
+        node.parent = t.parent; node.higher = 0; node.isLower = t.isLower; node.count = 0; node.primFirst = 0; node.dataBegin = node.dataEnd = 0;
+        if (self && !t.isLower) nodes[t.parent].higher = self;
+        depth = std::max(depth, t.level);
+        if (t.a == t.b) {
+            node.primFirst = 2 * t.a;
+            node.count = (size_t)node.primFirst + 1 < n ? 2 : 1;
+            node.dataBegin = data.size();
+            for (uint32_t j = 0; j < node.count; j++) {
+                const size_t at = header[perm[node.primFirst + j]];
+                data.insert(data.end(), LeafData.begin() + at, LeafData.begin() + at + RGBA_ELEMS * (2 + (size_t)(as_uint(LeafData[at]) & 3)));
+            }
+            node.dataEnd = data.size();
+        } else {
+            // delta(a, g) does not grow with g (the leaves are sorted by key, then index): the last g that shares more with a than b does
+            const int whole = leaf_delta(K, t.a, t.b);
+            uint32_t lo = t.a, hi = t.b - 1;  // delta(a, a) is infinite: lo qualifies
+            while (lo < hi) {
+                const uint32_t mid = lo + (hi - lo + 1) / 2;
+                if (leaf_delta(K, t.a, mid) > whole) lo = mid; else hi = mid - 1;
+            }
+            todo.push_back(Todo{lo + 1, t.b, self, false, t.level + 1});
+            todo.push_back(Todo{t.a, lo, self, true, t.level + 1});
+        }
+        nodes.push_back(node);
+    }
+    Nodes.swap(nodes);
+    LeafData.swap(data);
+    Depth = depth;
+    QuadAddr.clear();
+    LeafOfFirst.clear();
+    LocateCursor = 0;
+    for (size_t i = Nodes.size(); i-- > 0;) RefitNode(i);  // pre-order: children lie behind their parent
+    if (newToOld) newToOld->swap(perm);
+    return true;
+}
+
 bool BoundingVolumesHierarchy::Load(const float *q, size_t nq) {
     struct Todo { size_t addr; uint32_t parent; bool isLower; unsigned level; };
     std::vector<Node, UninitAlloc<Node>> nodes;

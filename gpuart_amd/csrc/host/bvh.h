@@ -68,6 +68,15 @@ public:
     /// The 16 floats of Refit's `payloads` for a primitive; returns its type.
     static uint32_t Payload(const Primitive &p, float out[16]);
 
+    /// Rebuilds the topology in Morton order over the primitives as they are now: the host's statement of include/gpuart_build.h
+    /// (tests/build_ref.py is the restatement; csrc/treebuild/build.hip builds the same tree on the device). 63-bit keys from every
+    /// primitive's box centre in the fold of all boxes, a stable sort by key, leaves of two, the split of a leaf range behind the last
+    /// leaf that shares more key (then index) bits with the first than the range's last does, boxes by the refit rule. Afterwards
+    /// Compile() writes that tree and primitive ordinal p is the old newToOld[p]. With `order` (the device's permutation) the sort is
+    /// skipped and the order only checked, in linear time: a permutation, ascending by (key, old ordinal). False, with nothing changed,
+    /// for an empty tree or an order that fails the check.
+    bool RebuildMorton(std::vector<uint32_t> *newToOld, const uint32_t *order = nullptr);
+
     /// Prints a compiled tree, decoding it the way the device code does.
     static void Print(const Primitive::Data &compiledTree, std::ostream &s);
 

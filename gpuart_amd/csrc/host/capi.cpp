@@ -170,6 +170,22 @@ int gpuart_refit_tree(const float *quads, size_t nquads, const uint32_t *ordinal
     return 0;
 }
 
+int gpuart_rebuild_tree(const float *quads, size_t nquads, const uint32_t *order, float **out, size_t *nout, uint32_t *newToOld) {
+    if (!quads || !out || !nout) return -1;
+    BoundingVolumesHierarchy tree;
+    if (!tree.Load(quads, nquads) || tree.CompiledFloats() != nquads * RGBA_ELEMS) return -1;
+    std::vector<uint32_t> perm;
+    if (!tree.RebuildMorton(&perm, order)) return -2;
+    const size_t floats = tree.CompiledFloats();
+    float *q = (float *)malloc(floats * sizeof(float));
+    if (!q) return -1;
+    tree.CompileTo(q);
+    *out = q;
+    *nout = floats / RGBA_ELEMS;
+    if (newToOld) std::copy(perm.begin(), perm.end(), newToOld);
+    return 0;
+}
+
 void gpuart_last_build_ms(double out[2]) { out[0] = g_last_build_ms[0]; out[1] = g_last_build_ms[1]; }
 
 void gpuart_camera_basis(const float pos[3], const float dir[3], const float up[3], float fovY, float screenDist,
@@ -230,6 +246,34 @@ int gpuart_renderer_update_primitives(gpuart_renderer *r, const uint32_t *indice
     const bool ok = make_list(moved.data(), n, list) && r->impl.UpdatePrimitives(sorted.data(), list.data(), (size_t)n);
     free_list(list);
     return ok ? 1 : 0;
+}
+int gpuart_renderer_rebuild_tree(gpuart_renderer *r, uint32_t *newToOld) {
+    if (!r) return 0;
+    std::vector<uint32_t> perm;
+    if (!r->impl.RebuildTree(&perm)) return 0;
+    if (!r->descOf.empty()) {  // the caller's numbering follows the primitives to their new positions
+        std::vector<int32_t> moved(perm.size());
+        for (size_t p = 0; p < perm.size(); p++) moved[p] = r->descOf[perm[p]];
+        r->descOf.swap(moved);
+    }
+    if (newToOld) std::copy(perm.begin(), perm.end(), newToOld);
+    return 1;
+}
+int gpuart_renderer_tree_cost(gpuart_renderer *r, double *cost) { return r && r->impl.TreeCost(cost) ? 1 : 0; }
+void gpuart_renderer_last_rebuild_ms(gpuart_renderer *r, double out[2]) {
+    if (!r || !out) return;
+    out[0] = r->impl.GetLastRebuildMs()[0]; out[1] = r->impl.GetLastRebuildMs()[1];
+}
+int gpuart_renderer_compile_bvh(gpuart_renderer *r, float **quads, size_t *nquads) {
+    if (!r || !quads || !nquads) return -1;
+    const BoundingVolumesHierarchy &t = r->impl.GetBVH();
+    const size_t floats = t.CompiledFloats();
+    float *q = (float *)malloc(floats * sizeof(float));
+    if (!q) return -1;
+    t.CompileTo(q);
+    *quads = q;
+    *nquads = floats / RGBA_ELEMS;
+    return 0;
 }
 void gpuart_renderer_init_box(gpuart_renderer *r) { r->descOf.clear(); InitBox(r->impl); }
 int gpuart_renderer_init_dragon(gpuart_renderer *r, const char *plyPath) { r->descOf.clear(); return InitDragon(r->impl, plyPath) ? 1 : 0; }

@@ -47,6 +47,11 @@ void gpuart_free(void *p);
  * 0; -1 for a malformed tree or NULL pointers; -2 for a refused update (*firstBad, if given, is its index in the list), `out` untouched. */
 int gpuart_refit_tree(const float *quads, size_t nquads, const uint32_t *ordinals, const float *payloads, size_t n, float *out,
                       size_t *firstBad, int touchedOnly);
+/* BoundingVolumesHierarchy::RebuildMorton without a device: the tree of the compiled tree `quads` rebuilt in Morton order
+ * (include/gpuart_build.h states the contract) and compiled again; *out is malloc'ed (gpuart_free), *nout its quads; newToOld receives
+ * the n_prims old ordinals by new ordinal. `order` NULL: the library sorts; else n_prims ordinals that are only checked.
+ * 0; -1 for a malformed tree or NULL pointers; -2 for an empty tree or an order that is not the contract's. */
+int gpuart_rebuild_tree(const float *quads, size_t nquads, const uint32_t *order, float **out, size_t *nout, uint32_t *newToOld);
 /* What the library itself spent in the last gpuart_compile_bvh / _from_file of this process: out[0] = BoundingVolumesHierarchy's
  * constructor (the build), out[1] = its compilation into quads, in ms — without the harness around them (making and deleting one
  * Primitive object per description, copying the result into the caller's language). */
@@ -75,6 +80,16 @@ void gpuart_renderer_set_primitives(gpuart_renderer *r, const gpuart_prim_desc *
  * `prims` array AS THE CALLER PASSED IT, as the ordinals of gpuart_renderer_trace_rays do; after an init_* scene they are positions in
  * the renderer's sorted list. 1 on success, 0 — with the scene unchanged — on any refusal. */
 int gpuart_renderer_update_primitives(gpuart_renderer *r, const uint32_t *indices, const gpuart_prim_desc *descs, int n);
+/* Renderer::RebuildTree. newToOld (n_prims entries, may be NULL) receives, per new device ordinal, the old one. The ordinals of
+ * gpuart_renderer_trace_rays and the indices of gpuart_renderer_update_primitives keep numbering the caller's descriptions after
+ * gpuart_renderer_set_primitives. 1 on success, 0 — with the scene unchanged — on any refusal. */
+int gpuart_renderer_rebuild_tree(gpuart_renderer *r, uint32_t *newToOld);
+/* Renderer::TreeCost. 1 on success. */
+int gpuart_renderer_tree_cost(gpuart_renderer *r, double *cost);
+/* {total, host tree} ms of the last gpuart_renderer_rebuild_tree. */
+void gpuart_renderer_last_rebuild_ms(gpuart_renderer *r, double out[2]);
+/* GetBVH().Compile(): *quads is malloc'ed (gpuart_free), *nquads its length in quads. 0, or -1. */
+int gpuart_renderer_compile_bvh(gpuart_renderer *r, float **quads, size_t *nquads);
 void gpuart_renderer_init_box(gpuart_renderer *r);
 int gpuart_renderer_init_dragon(gpuart_renderer *r, const char *plyPath);
 /* InitCluster / InitTree (reference src/scenes.cpp:69-103) on a primitive-list file; NULL = the reference's own path. */

@@ -101,6 +101,7 @@ Renderer::~Renderer() {
     if (Denoiser) gpuart_denoise_destroy(Denoiser);
     DenoiseMem.Release();
     if (Refitter) gpuart_refit_destroy(Refitter);
+    if (Builder) gpuart_build_destroy(Builder);
     if (Backend) gpuart_hip_destroy(Backend);
 }
 
@@ -316,6 +317,58 @@ bool Renderer::UpdatePrimitives(const uint32_t *indices, Primitive *const *moved
     EdgeListValid = false;
     ResetPathTracing();
     return true;
+}
+
+// ---- a drifted scene: the tree rebuilt on the device (include/gpuart_build.h) ------------------------
+// The device builds into the spare arrays, so every refusal up to the swap leaves the scene as it was; the host tree follows last,
+// from the device's permutation (RebuildMorton checks the order instead of sorting). The temporal histories are kept as for a refit:
+// their tap validation compares hit point, normal and class, and of the ordinal only "is the user sphere" (-2), which a new numbering
+// does not touch.
+bool Renderer::RebuildTree(std::vector<uint32_t> *newToOld) {
+    if (!IsOK) return false;
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    gpuart_hip_scene scene, spare;
+    if (!Check(gpuart_hip_scene_device(Backend, &scene), "looking up the scene's device arrays")) return false;
+    if (scene.exact_boxes || !scene.n_prims || Tree.GetNumPrimitives() != scene.n_prims) {
+        std::cerr << "Renderer: RebuildTree: an empty scene or a tree with irregular boxes (or boxes that do not bound their contents) is not rebuilt." << std::endl;
+        return false;
+    }
+    const uint64_t n = scene.n_prims;
+    if (!Check(gpuart_hip_scene_reserve(Backend, (n + 1) / 2 - 1, &spare), "reserving the spare arrays")) return false;
+    if (!Builder && !Check(gpuart_build_create(Device, &Builder), "creating the build handle", gpuart_build_last_error)) return false;
+    CommitTemporalView();
+    gpuart_build_result res;
+    std::vector<uint32_t> order(n);
+    if (!Check(gpuart_build_run_host(Builder, &scene, &spare, order.data(), &res), "rebuilding the tree", gpuart_build_last_error)) return false;
+    spare.n_recs = res.n_recs;
+    spare.root_ref = res.root_ref;
+    spare.max_depth = res.max_depth;
+    memcpy(spare.root_min, res.root_min, 12); memcpy(spare.root_max, res.root_max, 12);
+    spare.box_slack = res.subnormal ? __builtin_inff() : 0.0f;
+    if (!Check(gpuart_hip_scene_rebuilt(Backend, &spare), "adopting the rebuilt tree")) return false;
+    const auto t1 = std::chrono::high_resolution_clock::now();
+    // (from here the device renders the new tree: a host tree that cannot follow is an inconsistency, not a refusal)
+    if (!Tree.RebuildMorton(nullptr, order.data())) {
+        std::cerr << "Renderer: RebuildTree: the device's order is not the contract's." << std::endl;
+        return IsOK = false;
+    }
+    const auto t2 = std::chrono::high_resolution_clock::now();
+    LastRebuildMs[0] = std::chrono::duration<double, std::milli>(t2 - t0).count();
+    LastRebuildMs[1] = std::chrono::duration<double, std::milli>(t2 - t1).count();
+    if (newToOld) newToOld->swap(order);
+    RefitGeneration = 0;  // the refit handle is bound to the old arrays: the next UpdatePrimitives binds again
+    GBufferValid = false;
+    EdgeListValid = false;
+    ResetPathTracing();
+    return true;
+}
+
+bool Renderer::TreeCost(double *cost) {
+    if (!IsOK || !cost) return false;
+    gpuart_hip_scene scene;
+    if (!Check(gpuart_hip_scene_device(Backend, &scene), "looking up the scene's device arrays")) return false;
+    if (!Builder && !Check(gpuart_build_create(Device, &Builder), "creating the build handle", gpuart_build_last_error)) return false;
+    return Check(gpuart_build_cost(Builder, &scene, cost), "measuring the tree's cost", gpuart_build_last_error);
 }
 
 // ---- batched ray queries ------------------------------------------------------------------------

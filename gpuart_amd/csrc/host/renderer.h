@@ -9,7 +9,7 @@
 //   ReadDirectLighting, ReadRadiance, Finish, SetMaxPathSegments, SetMinWeight, SetSeed,
 //   SetTile, GetBackend, ComputeScreenBasis, GetNumPathsRendered, ReadDenoised, SetTemporalHistory, ReadPreview, RenderUntil,
 //   ReadErrorMap, ReadRefined, SetHistoryVariance, SetHistoryAntiLag, ReadGuidedPreview, ReadDisplay, SetEdgeResolve,
-//   SetFireflyClamp, ReadFireflySummary, UpdatePrimitives.
+//   SetFireflyClamp, ReadFireflySummary, UpdatePrimitives, RebuildTree, TreeCost.
 #ifndef GPUART_RENDERER_H
 #define GPUART_RENDERER_H
 
@@ -21,6 +21,7 @@
 #include "core.h"
 #include "gpuart_adaptive.h"
 #include "gpuart_antilag.h"
+#include "gpuart_build.h"
 #include "gpuart_converge.h"
 #include "gpuart_denoise.h"
 #include "gpuart_despeckle.h"
@@ -78,6 +79,18 @@ public:
     /// indices that are not ascending or out of range, a changed type, and a primitive outside csrc/hip/prim_rule.h (a word that is not
     /// finite or beyond 2^20, a negative radius), and for a scene whose tree the uploader classified irregular or disorderly.
     bool UpdatePrimitives(const uint32_t *indices, Primitive *const *moved, size_t n);
+    /// Rebuilds the scene's tree on the device in Morton order (include/gpuart_build.h) — what a long drift of UpdatePrimitives wants,
+    /// without SetPrimitives' host build, upload and dropped histories. The primitives are renumbered: the primitive with ordinal p
+    /// (TraceRays, UpdatePrimitives) is the one that had ordinal (*newToOld)[p] before — reorder a kept vector by it, and ordinal i is
+    /// primitives[i] again as after SetPrimitives. The temporal histories are kept as for UpdatePrimitives (the view is committed first);
+    /// the accumulation restarts; GetBVH() is the rebuilt tree. False — everything as it was; std::cerr says why — for a scene whose
+    /// tree the uploader classified irregular or disorderly and for an empty scene.
+    bool RebuildTree(std::vector<uint32_t> *newToOld = nullptr);
+    /// The tree's cost as gpuart_build_cost measures it on the device arrays: the sum over the records of both children's half-areas
+    /// over the root's. It grows as refitted boxes loosen; RebuildTree brings it back down.
+    bool TreeCost(double *cost);
+    /// {total, host tree} ms of the last RebuildTree.
+    const double *GetLastRebuildMs() const { return LastRebuildMs; }
     bool UpdateViewportSize(unsigned width, unsigned height);
     bool SetCamera(const Camera &cam);
 
@@ -338,6 +351,8 @@ private:
     gpuart_hip_ctx *Backend = nullptr;
     gpuart_refit *Refitter = nullptr;     ///< made by the first UpdatePrimitives; bound again after every upload (the scene's generation)
     uint64_t RefitGeneration = 0;         ///< the generation Refitter is bound to (0: none; the first upload's is 1)
+    gpuart_build *Builder = nullptr;      ///< made by the first RebuildTree or TreeCost
+    double LastRebuildMs[2] = {0, 0};
     BoundingVolumesHierarchy Tree;
     struct { unsigned width, height; } Viewport{0, 0};
     struct { unsigned x, y, w, h; } Tile{0, 0, 0, 0};  ///< the part of the frame this renderer owns

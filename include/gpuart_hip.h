@@ -286,6 +286,24 @@ int gpuart_hip_scene_device(gpuart_hip_ctx *ctx, gpuart_hip_scene *out);
  * order, max_depth and the root ref do not change. GPUART_HIP_ERR_ARG, with nothing changed, without a scene, on a tree the uploader
  * classified irregular or disorderly, and for a root box that is not finite and ordered. */
 int gpuart_hip_scene_refitted(gpuart_hip_ctx *ctx, const float root_min[3], const float root_max[3], int subnormal);
+/* ---- a rebuild on the device (include/gpuart_build.h; DESIGN.md "Rebuild") ---------------------------------------------------------
+ * Hands out a spare set of arrays the context owns — room for n_recs records and for the scene's n_prims primitives and boxes —,
+ * allocated on the first call and reused while it is large enough (the records beyond n_recs are zeroed again, as behind an upload's);
+ * the next upload frees it. *out: layout 1, the three arrays, n_recs
+ * and n_prims = the room, generation = the scene's; everything else zero. Rendering is unaffected: nothing reads the spare set.
+ * GPUART_HIP_ERR_ARG without a scene. */
+int gpuart_hip_scene_reserve(gpuart_hip_ctx *ctx, uint64_t n_recs, gpuart_hip_scene *out);
+/* Adopts a tree built into the spare set (the caller has waited for the build): flushes the collected passes and waits for them — they
+ * render the old tree —, then the spare set becomes the scene and the old arrays the spare set. Root box, root_ref, n_recs and max_depth
+ * are taken from *built; box_slack by the uploader's rule for that root box, +inf when built->box_slack is +inf (the builder met a
+ * subnormal plane) or quick boxes are off; the traversal stacks are sized for the new depth; `generation` grows, so a refit handle
+ * bound to the old arrays is stale and says so; the block order is counted again by the next run. The primitive count, the type mask
+ * and the tree order stay: primitives keep their types, and their device ordinals are now the built order's.
+ * GPUART_HIP_ERR_ARG, with nothing changed, for arrays that are not the reserved ones or were reserved before another upload or
+ * rebuild, a changed n_prims, n_recs beyond the room, max_depth > 1024, a root box that is not finite and ordered, a root_ref that is
+ * neither 0 with records nor a leaf ref inside n_prims without, a failure to size the traversal stacks, and on a tree
+ * the uploader classified irregular or disorderly. */
+int gpuart_hip_scene_rebuilt(gpuart_hip_ctx *ctx, const gpuart_hip_scene *built);
 
 /* How the fast kernels walk the uploaded tree: 1 (the default for every tree of regular boxes since round 5) in the reference's order —
  * lower child first, shaders/bvh_intersection.glsl:432-441 — which is the only order PROVEN to return the reference's winner; 2 in the
