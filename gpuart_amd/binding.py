@@ -752,12 +752,9 @@ class Backend:
             raise e
 
     def close(self):
-        if getattr(self, "_refit", None) is not None:
-            refit_lib().gpuart_refit_destroy(self._refit)
-            self._refit = None
-        if getattr(self, "_build", None) is not None:
-            build_lib().gpuart_build_destroy(self._build)
-            self._build = None
+        for handle in (getattr(self, "_refit", None), getattr(self, "_build", None)):
+            if handle is not None:
+                handle.close()
         if self.owned and self.ctx:
             self.L.gpuart_hip_destroy(self.ctx)
             self.ctx = None
@@ -810,12 +807,11 @@ class Backend:
         R = refit_lib()
         scene = self.scene_device()
         if getattr(self, "_refit", None) is None:
-            h = C.c_void_p()
-            self._chk_refit(R.gpuart_refit_create(C.c_int(self.device), C.byref(h)))
-            self._refit, self._refit_generation = h, None
-        if self._refit_generation != scene.generation:
-            self._chk_refit(R.gpuart_refit_bind(self._refit, C.byref(scene)))
-            self._refit_generation = scene.generation
+            self._refit = _RefitHandle(self.device)
+        h = self._refit
+        if h.generation != scene.generation:
+            h._chk(R.gpuart_refit_bind(h, C.byref(scene)))
+            h.generation = scene.generation
         res = RefitResult()
         if hasattr(ordinals, "data_ptr"):
             import torch
@@ -824,27 +820,20 @@ class Backend:
                 raise ValueError("refit: ordinals (int32) and payload (float32, n x 16) must both be contiguous tensors on the device")
             torch.cuda.synchronize(ordinals.device)   # (the handle's stream is its own: what wrote the tensors must be complete)
             n = ordinals.numel()
-            rc = R.gpuart_refit_run(self._refit, C.byref(scene), C.c_void_p(ordinals.data_ptr() if n else None),
+            rc = R.gpuart_refit_run(h, C.byref(scene), C.c_void_p(ordinals.data_ptr() if n else None),
                                     C.c_void_p(payload.data_ptr() if n else None), C.c_size_t(n), C.byref(res))
         else:
             o = np.ascontiguousarray(ordinals, np.uint32).reshape(-1)
             p = np.ascontiguousarray(payload, np.float32).reshape(-1)
             if p.size != 16 * o.size:
                 raise ValueError("refit: payload must hold 16 floats per ordinal")
-            rc = R.gpuart_refit_run_host(self._refit, C.byref(scene), _p(o), _p(p), C.c_size_t(o.size), C.byref(res))
-        self._chk_refit(rc, res)
+            rc = R.gpuart_refit_run_host(h, C.byref(scene), _p(o), _p(p), C.c_size_t(o.size), C.byref(res))
+        h._chk(rc, res)
         self.scene_refitted(res.root_min[:], res.root_max[:], res.subnormal)
         levels = C.c_uint32()
-        self._chk_refit(R.gpuart_refit_levels(self._refit, C.byref(levels)))
+        h._chk(R.gpuart_refit_levels(h, C.byref(levels)))
         return dict(root_min=np.array(res.root_min[:], np.float32), root_max=np.array(res.root_max[:], np.float32), subnormal=bool(res.subnormal),
                     levels=int(levels.value))
-
-    def _chk_refit(self, rc, res=None):
-        if rc != 0:
-            e = HipError("gpuart_refit error %d: %s" % (rc, refit_lib().gpuart_refit_last_error().decode()))
-            e.code = rc
-            e.first_bad = int(res.first_bad) if res is not None and res.status else None
-            raise e
 
     # a rebuild on the device (include/gpuart_build.h)
     def scene_reserve(self, n_recs):
@@ -858,9 +847,7 @@ class Backend:
 
     def _build_handle(self):
         if getattr(self, "_build", None) is None:
-            h = C.c_void_p()
-            self._chk_build(build_lib().gpuart_build_create(C.c_int(self.device), C.byref(h)))
-            self._build = h
+            self._build = _BuildHandle(self.device)
         return self._build
 
     def rebuild(self, out=None):
@@ -889,13 +876,13 @@ class Backend:
                 raise ValueError("rebuild: out must be a contiguous int32 tensor of n_prims entries on the device")
             torch.cuda.synchronize(perm.device)
             rc = Bd.gpuart_build_run(h, C.byref(scene), C.byref(spare), C.c_void_p(perm.data_ptr()), C.byref(res))
-        self._chk_build(rc)
+        h._chk(rc)
         spare.n_recs, spare.root_ref, spare.max_depth = res.n_recs, res.root_ref, res.max_depth
         spare.root_min, spare.root_max = res.root_min, res.root_max
         spare.box_slack = float("inf") if res.subnormal else 0.0
         self.scene_rebuilt(spare)
         ms = (C.c_double * 7)()
-        self._chk_build(Bd.gpuart_build_step_ms(h, ms))
+        h._chk(Bd.gpuart_build_step_ms(h, ms))
         self.last_rebuild = dict(n_recs=int(res.n_recs), root_ref=int(res.root_ref), max_depth=int(res.max_depth), subnormal=bool(res.subnormal),
                                  levels=int(res.levels), root_min=np.array(res.root_min[:], np.float32), root_max=np.array(res.root_max[:], np.float32),
                                  step_ms=dict(zip(BUILD_STEPS, [float(v) for v in ms])))
@@ -905,14 +892,9 @@ class Backend:
         """gpuart_build_cost of the uploaded scene's tree: the sum over its records of both children's half-areas over the root's."""
         cost = C.c_double()
         scene = self.scene_device()
-        self._chk_build(build_lib().gpuart_build_cost(self._build_handle(), C.byref(scene), C.byref(cost)))
+        h = self._build_handle()
+        h._chk(build_lib().gpuart_build_cost(h, C.byref(scene), C.byref(cost)))
         return float(cost.value)
-
-    def _chk_build(self, rc):
-        if rc != 0:
-            e = HipError("gpuart_build error %d: %s" % (rc, build_lib().gpuart_build_last_error().decode()))
-            e.code = rc
-            raise e
 
     # rendering
     def render_direct(self, params):
@@ -1610,6 +1592,8 @@ class _ImageHandle:
         self._chk(self._fn("create")(C.c_int(device), C.byref(h)))
         self.h = h
 
+    _as_parameter_ = property(lambda self: self.h)  # what ctypes passes where a call is given the object
+
     def _fn(self, what):
         return getattr(self.L, "gpuart_%s_%s" % (self.NAME, what))
 
@@ -1632,6 +1616,24 @@ class _ImageHandle:
 
     def finish(self):
         self._chk(self._fn("finish")(self.h))
+
+
+class _RefitHandle(_ImageHandle):
+    """Backend.refit's gpuart_refit, made at the first refit; `generation`: that of the upload it is bound to."""
+    NAME, Error = "refit", HipError
+    generation = None
+
+    def _chk(self, rc, res=None):  # res: the run's RefitResult, whose refused update becomes the error's first_bad
+        try:
+            super()._chk(rc)
+        except HipError as e:
+            e.first_bad = int(res.first_bad) if res is not None and res.status else None
+            raise
+
+
+class _BuildHandle(_ImageHandle):
+    """Backend.rebuild's and tree_cost's gpuart_build, made at the first of them."""
+    NAME, Error = "build", HipError
 
 
 def _gbuffer_args(device, rgba, hits, prims, out):

@@ -161,11 +161,6 @@ struct gpuart_antilag : ImageHandle {
 
 namespace {
 
-bool overlaps(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
-
 int check_params(const gpuart_antilag_params *p) {
     if (!p) return 0;
     if (!std::isfinite(p->fast_history) || !(p->fast_history >= 0)) return fail(GPUART_HIP_ERR_ARG, "antilag: fast_history must be finite and >= 0");
@@ -205,13 +200,6 @@ int check_mix(gpuart_antilag *a, const void *slow, const void *slow_len, const v
                 return fail(GPUART_HIP_ERR_ARG, "antilag: an output overlaps another output");
     }
     return 0;
-}
-
-gpuart_antilag_params params_or_defaults(const gpuart_antilag_params *p) {
-    gpuart_antilag_params v;
-    if (p) v = *p;
-    else gpuart_antilag_defaults(&v);
-    return v;
 }
 
 /// The launch; where an output is its input, that input is first copied into the handle's memory and read from there.
@@ -271,7 +259,7 @@ int gpuart_antilag_mix(gpuart_antilag *a, const float *slow, const float *slow_l
     if (int rc = check_mix(a, slow, slow_len, fast, fast_len, moments, hits, prims, w, h, p, out, out_len, alpha, 16)) return rc;
     HIP_TRY(hipSetDevice(a->device));
     return launch_mix(a, (const float4 *)slow, slow_len, (const float4 *)fast, fast_len, (const float4 *)moments, (const float4 *)hits, prims,
-                      userSphereFlags, (int)w, (int)h, params_or_defaults(p), (float4 *)out, out_len, alpha);
+                      userSphereFlags, (int)w, (int)h, params_or_defaults(p, gpuart_antilag_defaults), (float4 *)out, out_len, alpha);
 }
 
 int gpuart_antilag_mix_host(gpuart_antilag *a, const float *slow, const float *slow_len, const float *fast, const float *fast_len,
@@ -292,7 +280,7 @@ int gpuart_antilag_mix_host(gpuart_antilag *a, const float *slow, const float *s
     HIP_TRY(hipMemcpyAsync(d_mom, moments, n * 16, hipMemcpyHostToDevice, a->stream));
     HIP_TRY(hipMemcpyAsync(d_sl, slow_len, n * 4, hipMemcpyHostToDevice, a->stream));
     HIP_TRY(hipMemcpyAsync(d_fl, fast_len, n * 4, hipMemcpyHostToDevice, a->stream));
-    if ((rc = launch_mix(a, in.rgba, d_sl, d_fast, d_fl, d_mom, in.hits, in.prims, userSphereFlags, (int)w, (int)h, params_or_defaults(p), d_out, d_ol,
+    if ((rc = launch_mix(a, in.rgba, d_sl, d_fast, d_fl, d_mom, in.hits, in.prims, userSphereFlags, (int)w, (int)h, params_or_defaults(p, gpuart_antilag_defaults), d_out, d_ol,
                          alpha ? d_al : nullptr)))
         return rc;
     HIP_TRY(hipMemcpyAsync(out, d_out, n * 16, hipMemcpyDeviceToHost, a->stream));

@@ -124,11 +124,6 @@ struct gpuart_despeckle : ImageHandle {
 
 namespace {
 
-bool overlaps(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
-
 int check_params(const gpuart_despeckle_params *p) {
     if (!p) return 0;
     const auto bad = [](const char *what) { return fail(GPUART_HIP_ERR_ARG, std::string("despeckle: ") + what); };
@@ -154,13 +149,6 @@ int check_run(gpuart_despeckle *d, const void *rgba, const void *hits, const voi
     if (scale && (overlaps(scale, n * 4, rgba, n * 16) || overlaps(scale, n * 4, out, n * 16)))
         return fail(GPUART_HIP_ERR_ARG, "despeckle: scale overlaps rgba or out");
     return check_handle(LIB, d);
-}
-
-gpuart_despeckle_params params_or_defaults(const gpuart_despeckle_params *p) {
-    gpuart_despeckle_params v;
-    if (p) v = *p;
-    else gpuart_despeckle_defaults(&v);
-    return v;
 }
 
 /// The clamp on device memory, on the handle's stream; rgba is not out. The counts start from zero.
@@ -224,7 +212,7 @@ int gpuart_despeckle_run(gpuart_despeckle *d, const float *rgba, const gpuart_ra
         HIP_TRY(hipMemcpyAsync(d->staging.mem, rgba, bytes, hipMemcpyDeviceToDevice, d->stream));
         in = (const float4 *)d->staging.mem;
     }
-    return launch(d, in, (const float4 *)hits, prims, userSphereFlags, (int)w, (int)h, params_or_defaults(p), (float4 *)out, scale);
+    return launch(d, in, (const float4 *)hits, prims, userSphereFlags, (int)w, (int)h, params_or_defaults(p, gpuart_despeckle_defaults), (float4 *)out, scale);
 }
 
 int gpuart_despeckle_run_host(gpuart_despeckle *d, const float *rgba, const gpuart_ray_hit *hits, const int32_t *prims,
@@ -238,7 +226,7 @@ int gpuart_despeckle_run_host(gpuart_despeckle *d, const float *rgba, const gpua
     if ((rc = stage_gbuffer(d->stream, d->staging.mem, n, rgba, hits, prims, in))) return rc;
     float4 *dout = (float4 *)((char *)d->staging.mem + n * STAGED_BYTES);
     float *dscale = (float *)((char *)d->staging.mem + n * (STAGED_BYTES + 16));
-    if ((rc = launch(d, in.rgba, in.hits, in.prims, userSphereFlags, (int)w, (int)h, params_or_defaults(p), dout, scale ? dscale : nullptr))) return rc;
+    if ((rc = launch(d, in.rgba, in.hits, in.prims, userSphereFlags, (int)w, (int)h, params_or_defaults(p, gpuart_despeckle_defaults), dout, scale ? dscale : nullptr))) return rc;
     HIP_TRY(hipMemcpyAsync(out, dout, n * 16, hipMemcpyDeviceToHost, d->stream));
     if (scale) HIP_TRY(hipMemcpyAsync(scale, dscale, n * 4, hipMemcpyDeviceToHost, d->stream));
     HIP_TRY(hipStreamSynchronize(d->stream));

@@ -220,11 +220,6 @@ struct gpuart_display : ImageHandle {
 
 namespace {
 
-bool overlaps(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
-
 int check_params(const gpuart_display_params *p) {
     if (!p) return 0;
     const auto bad = [](const char *what) { return fail(GPUART_HIP_ERR_ARG, std::string("display: ") + what); };
@@ -256,13 +251,6 @@ int check_run(gpuart_display *d, const void *rgba, const void *rgba8, uint32_t w
     const size_t n = (size_t)w * h;
     if (overlaps(rgba8, n * 4, rgba, n * 16)) return fail(GPUART_HIP_ERR_ARG, "display: rgba8 overlaps rgba");
     return 0;
-}
-
-gpuart_display_params params_or_defaults(const gpuart_display_params *p) {
-    gpuart_display_params v;
-    if (p) v = *p;
-    else gpuart_display_defaults(&v);
-    return v;
 }
 
 int launch(gpuart_display *d, const float4 *rgba, uint32_t *out, uint32_t w, uint32_t h, uint32_t ox, uint32_t oy, const gpuart_display_params &p) {
@@ -360,7 +348,7 @@ int gpuart_display_run(gpuart_display *d, const float *rgba, uint8_t *rgba8, uin
                        const gpuart_display_params *p) {
     if (int rc = check_run(d, rgba, rgba8, w, h, p, 16, 16)) return rc;
     HIP_TRY(hipSetDevice(d->device));
-    return launch(d, (const float4 *)rgba, (uint32_t *)rgba8, w, h, origin_x, origin_y, params_or_defaults(p));
+    return launch(d, (const float4 *)rgba, (uint32_t *)rgba8, w, h, origin_x, origin_y, params_or_defaults(p, gpuart_display_defaults));
 }
 
 int gpuart_display_run_host(gpuart_display *d, const float *rgba, uint8_t *rgba8, uint32_t w, uint32_t h, uint32_t origin_x,
@@ -373,7 +361,7 @@ int gpuart_display_run_host(gpuart_display *d, const float *rgba, uint8_t *rgba8
     float4 *in = (float4 *)d->staging.mem;
     uint32_t *words = (uint32_t *)((char *)d->staging.mem + n * 16);
     HIP_TRY(hipMemcpyAsync(in, rgba, n * 16, hipMemcpyHostToDevice, d->stream));
-    if ((rc = launch(d, in, words, w, h, origin_x, origin_y, params_or_defaults(p)))) return rc;
+    if ((rc = launch(d, in, words, w, h, origin_x, origin_y, params_or_defaults(p, gpuart_display_defaults)))) return rc;
     HIP_TRY(hipMemcpyAsync(rgba8, words, n * 4, hipMemcpyDeviceToHost, d->stream));
     HIP_TRY(hipStreamSynchronize(d->stream));
     return 0;

@@ -174,18 +174,6 @@ int check_params(const gpuart_edges_params *p) {
     return 0;
 }
 
-gpuart_edges_params params_or_defaults(const gpuart_edges_params *p) {
-    gpuart_edges_params v;
-    if (p) v = *p;
-    else gpuart_edges_defaults(&v);
-    return v;
-}
-
-bool overlaps(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
-
 }  // namespace
 
 extern "C" {
@@ -231,7 +219,7 @@ int gpuart_edges_mark(gpuart_edges *e, const gpuart_ray_hit *hits, const int32_t
     if (int rc = check_size(LIB, w, h)) return rc;
     if (int rc = check_params(p)) return rc;
     HIP_TRY(hipSetDevice(e->device));
-    const gpuart_edges_params v = params_or_defaults(p);
+    const gpuart_edges_params v = params_or_defaults(p, gpuart_edges_defaults);
     const size_t n = (size_t)w * h, words = (n + 63) / 64;
     if (int rc = ensure(e->stream, e->prefix, words * 12)) return rc;
     unsigned long long *ballots = (unsigned long long *)e->prefix.mem;
@@ -256,7 +244,7 @@ int gpuart_edges_resolve(gpuart_edges *e, const float *filtered, const gpuart_ra
         return fail(GPUART_HIP_ERR_ARG, "edges: misaligned pointer (filtered, hits, sub_hits and out need 16 bytes, prims, list and sub_prims 4)");
     if (int rc = check_size(LIB, w, h)) return rc;
     if (int rc = check_params(p)) return rc;
-    const gpuart_edges_params v = params_or_defaults(p);
+    const gpuart_edges_params v = params_or_defaults(p, gpuart_edges_defaults);
     if (n > GPUART_HIP_MAX_RAYS / v.n_sub) return fail(GPUART_HIP_ERR_ARG, "edges: n * n_sub exceeds GPUART_HIP_MAX_RAYS");
     const size_t bytes = (size_t)w * h * 16;
     if (overlaps(out, bytes, filtered, bytes)) return fail(GPUART_HIP_ERR_ARG, "edges: out overlaps filtered");

@@ -62,6 +62,7 @@
 // rays through edges, corners, planes; flat, nested, huge and tiny boxes) and -DGD_QUICK_CHECK device builds (every product box
 // test both ways, mismatches counted) — profiles/r04/quick_box_test.txt.
 #pragma once
+#include "tree_rule.h"
 
 #ifndef GQ_FN
 #error "the includer defines GQ_FN (function attributes) and gq_min / gq_max / gq_med3 / gq_fma / gq_abs"
@@ -79,7 +80,7 @@
 #ifndef GQ_HOST_FN
 #define GQ_HOST_FN static inline
 #endif
-GQ_HOST_FN bool gq_plane_ok(float p) { return p == 0.0f || (p >= 8.6736173798840355e-19f || p <= -8.6736173798840355e-19f); }  // (false for NaN)
+GQ_HOST_FN bool gq_plane_ok(float p) { return tree_rule::plane_ok(p); }
 GQ_HOST_FN float gq_slack_of_tree(float pmax) {
     if (!(pmax >= 0.0f) || !(pmax <= 1.099511627776e12f)) return __builtin_inff();
     return 2.384185791015625e-07f * pmax + 8.0779356694631609e-28f;  // 4 u * Pmax + 2^-90

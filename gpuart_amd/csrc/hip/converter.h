@@ -79,12 +79,9 @@ struct Converter {
     /// +-inf gives the reference a legitimate candidate with parameter +inf ("intersected", entry stays 1e19), which the
     /// fast test cannot tell from no candidate. Boxes are uploaded as they are; a tree with an irregular box anywhere makes
     /// every box test take the comparison form (Scene::exact_boxes, device_scene.h). With finite, ordered bounds the two
-    /// forms agree for every ray, NaN / infinite origins and directions included.
+    /// forms agree for every ray, NaN / infinite origins and directions included. (The condition is tree_rule.h box_ok.)
     bool irregular = false;
-    void note(const Child &c) {
-        for (int k = 0; k < 3; k++)
-            irregular = irregular || !(c.bmin[k] <= c.bmax[k]) || std::isinf(c.bmin[k]) || std::isinf(c.bmax[k]);  // NaN fails <=
-    }
+    void note(const Child &c) { irregular = irregular || !tree_rule::box_ok(c.bmin, c.bmax); }
 
     /// May the fast kernels visit this tree's nodes in their own order (nearer child first, device_scene.h GD_NEAREST)? Their
     /// certificate rests on boxes that bound what they hold: every child box inside its parent's, every primitive inside its
@@ -145,7 +142,7 @@ struct Converter {
             const uint32_t first = (uint32_t)n_prims;
             size_t a = addr + 3;
             static const int LEN[4] = {1, 2, 3, 4};
-            bool all_tris = n >= 1 && n <= 2;
+            bool all_tris = true;
             for (uint32_t i = 0; i < n; i++) {
                 if (a + 1 > nq) { err = "primitive header out of range"; return false; }
                 uint32_t type = bits(q[4 * a]);
@@ -156,7 +153,7 @@ struct Converter {
                 a += 1 + LEN[type];
             }
             n_prims += n ? n : 1;  // an empty leaf (empty scene) keeps one dummy record with count 0
-            table[index].ref = GD_REF_LEAF | (all_tris ? GD_REF_TRIS : n >= 1 && n <= 2 ? GD_REF_SMALL : 0u) | (n == 2 ? GD_REF_TWO : 0u) | first;
+            table[index].ref = tree_rule::leaf_ref(first, n, all_tris);
             end = a;
             return true;
         }
@@ -186,11 +183,7 @@ struct Converter {
     /// Returns whether one of the boxes written is irregular.
     bool fill(size_t from, size_t to, bool &loose, bool &sub) {
         bool irr = false;
-        auto bad = [](const Child &c) {
-            bool r = false;
-            for (int k = 0; k < 3; k++) r = r || !(c.bmin[k] <= c.bmax[k]) || std::isinf(c.bmin[k]) || std::isinf(c.bmax[k]);  // NaN fails <=
-            return r;
-        };
+        auto bad = [](const Child &c) { return !tree_rule::box_ok(c.bmin, c.bmax); };
         static const int LEN[4] = {1, 2, 3, 4};
         for (size_t i = from; i < to; i++) {
             const NodeInfo &n = table[i];

@@ -7,7 +7,7 @@
 //             [4r]   = { lo.bbmin.xyz, bits(lo ref) }     ref = record index of an interior child, or
 //             [4r+1] = { lo.bbmax.xyz, bits(hi ref) }           bit31 | first primitive index of a leaf child
 //                                                               (| bit30 when the leaf is one or two triangles, | bit28 when it is one or two
-//                                                                primitives not all triangles, | bit29 when two: GD_REF_* below)
+//                                                                primitives not all triangles, | bit29 when two: tree_rule.h)
 //             [4r+2] = { hi.bbmin.xyz, mark }                   mark = 1 above level GPUART_HIP_TOP_DEPTH (counters only), else 0
 //             [4r+3] = { hi.bbmax.xyz, 0 }
 //           The root's own box and ref travel in the Scene struct.
@@ -19,6 +19,7 @@
 //           T = bits(type | count << 2): the FIRST primitive of a leaf carries the leaf's primitive count
 #pragma once
 #include "device_math.h"
+#include "tree_rule.h"
 
 // The quick box answer (box_quick.h: certainly the reference's, or withdrawn) on the device's own instructions: v_min / v_max drop a
 // NaN operand, v_med3 turns into min3 when it meets one, |x| is a source modifier, the fma is explicit.
@@ -37,11 +38,12 @@ enum { P_SPHERE = 0, P_DISC = 1, P_TRIANGLE = 2, P_CONE = 3 };
 #define GD_VISIBILITY_OFFSET 1.0e-4f
 #define GD_NO_PRIM 0xffffffffu
 
-#define GD_REF_LEAF 0x80000000u
-#define GD_REF_TRIS 0x40000000u  ///< with GD_REF_LEAF: the leaf holds only triangles, one or two of them
-#define GD_REF_TWO 0x20000000u   ///< with GD_REF_TRIS: two of them (both records are fetched at once; a single-triangle leaf fetches one)
-#define GD_REF_SMALL 0x10000000u ///< with GD_REF_LEAF, without GD_REF_TRIS: one or two primitives of any type (GD_REF_TWO: two) — fetched at once like a triangle pair
-#define GD_REF_INDEX 0x0fffffffu
+// the ref word of a record, stated in tree_rule.h, by the names the walks, the uploader and the tools use
+#define GD_REF_LEAF tree_rule::REF_LEAF
+#define GD_REF_TRIS tree_rule::REF_TRIS    ///< one or two triangles: both records are fetched at once; a single-triangle leaf fetches one
+#define GD_REF_TWO tree_rule::REF_TWO
+#define GD_REF_SMALL tree_rule::REF_SMALL  ///< one or two primitives of any type, fetched at once like a triangle pair
+#define GD_REF_INDEX tree_rule::REF_INDEX
 
 // Visiting order of a closest-hit query. The reference always descends lower-then-upper (shaders/bvh_intersection.glsl:432-441),
 // prunes a node whose box is entered beyond the closest hit so far (:398) and keeps the strictly closer hit (:416): among the hits with

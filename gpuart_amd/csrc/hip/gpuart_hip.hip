@@ -1289,9 +1289,7 @@ int gpuart_hip_scene_refitted(gpuart_hip_ctx *c, const float root_min[3], const 
     if (!c || !root_min || !root_max) return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_refitted: bad argument");
     if (!c->have_scene) return fail(GPUART_HIP_ERR_ARG, "no scene uploaded");
     if (c->exact_boxes) return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_refitted: a tree with irregular boxes (or boxes that do not bound their contents) is not refitted");
-    for (int k = 0; k < 3; k++)
-        if (!(root_min[k] <= root_max[k]) || std::isinf(root_min[k]) || std::isinf(root_max[k]))
-            return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_refitted: the root box is not finite and ordered");
+    if (!tree_rule::box_ok(root_min, root_max)) return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_refitted: the root box is not finite and ordered");
     int r;
     if ((r = gpuart_hip_flush(c))) return r;
     if ((r = drain(c))) return r;
@@ -1343,11 +1341,9 @@ int gpuart_hip_scene_rebuilt(gpuart_hip_ctx *c, const gpuart_hip_scene *b) {
     if (b->n_prims != c->n_prims) return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_rebuilt: the primitive count changed");
     if (b->n_recs > c->spare_recs) return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_rebuilt: more records than were reserved");
     if (b->max_depth > 1024) return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_rebuilt: tree deeper than 1024 levels");
-    for (int k = 0; k < 3; k++)
-        if (!(b->root_min[k] <= b->root_max[k]) || std::isinf(b->root_min[k]) || std::isinf(b->root_max[k]))
-            return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_rebuilt: the root box is not finite and ordered");
+    if (!tree_rule::box_ok(b->root_min, b->root_max)) return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_rebuilt: the root box is not finite and ordered");
     if (!c->d_prim_boxes) return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_rebuilt: gpuart_hip_scene_device was not called for this scene");
-    if (b->n_recs ? b->root_ref != 0 : !((b->root_ref & GD_REF_LEAF) && (b->root_ref & GD_REF_INDEX) < c->n_prims))
+    if (!tree_rule::root_ref_ok(b->root_ref, b->n_recs, c->n_prims))
         return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_rebuilt: the root ref is neither record 0 of a tree with records nor a leaf inside the primitives");
     HIP_TRY(hipSetDevice(c->device));
     int r;

@@ -7,6 +7,7 @@
 #include "bvh.h"
 #include "exact_sort.h"
 #include "../hip/prim_rule.h"
+#include "../hip/tree_rule.h"
 
 #include <algorithm>
 #include <cassert>
@@ -496,44 +497,11 @@ bool BoundingVolumesHierarchy::Refit(const uint32_t *indices, const Primitive *c
     return CheckRefit(indices, payloads.data(), n, firstBad, types.data()) && Refit(indices, payloads.data(), n, firstBad);
 }
 
-// ---- rebuild in Morton order: the host's statement of include/gpuart_build.h (tests/build_ref.py is the restatement) ----------------
-namespace {
-/// Bits of a 21-bit number spread to every third bit.
-inline uint64_t spread3(uint32_t q) {
-    uint64_t x = q & 0x1fffffu;
-    x = (x | x << 32) & 0x1f00000000ffffull;
-    x = (x | x << 16) & 0x1f0000ff0000ffull;
-    x = (x | x << 8) & 0x100f00f00f00f00full;
-    x = (x | x << 4) & 0x10c30c30c30c30c3ull;
-    x = (x | x << 2) & 0x1249249249249249ull;
-    return x;
-}
-/// The 63-bit key of a box in the root box [rlo, rhi]: fp32, no contraction, IEEE division.
-inline uint64_t morton_key(const float lo[3], const float hi[3], const float rlo[3], const float rhi[3]) {
-    uint64_t key = 0;
-    for (int k = 0; k < 3; k++) {
-        const float c = lo[k] * 0.5f + hi[k] * 0.5f;
-        const float e = rhi[k] - rlo[k];
-        const float t = (c - rlo[k]) / e;
-        uint32_t q = 0;
-        if (e > 0.0f && t > 0.0f) {
-            const float v = t * 2097152.0f;
-            q = v >= 2097151.0f ? 2097151u : (uint32_t)v;
-        }
-        key |= spread3(q) << (2 - k);
-    }
-    return key;
-}
-/// delta(i, j) of leaves i != j: the common prefix of their keys, or past 64 that of their indices.
-inline int leaf_delta(const std::vector<uint64_t> &K, uint32_t i, uint32_t j) {
-    const uint64_t x = K[i] ^ K[j];
-    return x ? __builtin_clzll(x) : 64 + __builtin_clz(i ^ j);
-}
-}  // namespace
-
+// ---- rebuild in Morton order: the host's statement of include/gpuart_build.h. The key and delta are tree_rule.h's, which the device
+// applies too; the topology is stated here, top-down, and by Karras' search on the device (tests/build_ref.py restates all of it) ----
 bool BoundingVolumesHierarchy::RebuildMorton(std::vector<uint32_t> *newToOld, const uint32_t *order) {
     const size_t n = NumPrimitives;
-    if (n == 0 || n > 0x0fffffffu) return false;
+    if (n == 0 || n > tree_rule::REF_INDEX) return false;
     // every primitive's header in LeafData, by old ordinal, and its box
     std::vector<size_t> header(n);
     {
@@ -556,7 +524,7 @@ bool BoundingVolumesHierarchy::RebuildMorton(std::vector<uint32_t> *newToOld, co
         prim_rule::box_fold(rlo, rhi, &box[6 * k], &box[6 * k + 3]);
     }
     std::vector<uint64_t> key(n);
-    for (size_t k = 0; k < n; k++) key[k] = morton_key(&box[6 * k], &box[6 * k + 3], rlo, rhi);
+    for (size_t k = 0; k < n; k++) key[k] = tree_rule::morton_key(&box[6 * k], &box[6 * k + 3], rlo, rhi);
     std::vector<uint32_t> perm(n);
     if (order) {
         // a given order is only checked: a permutation, ascending by (key, old ordinal)
@@ -604,11 +572,11 @@ bool BoundingVolumesHierarchy::RebuildMorton(std::vector<uint32_t> *newToOld, co
             node.dataEnd = data.size();
         } else {
             // delta(a, g) does not grow with g (the leaves are sorted by key, then index): the last g that shares more with a than b does
-            const int whole = leaf_delta(K, t.a, t.b);
-            uint32_t lo = t.a, hi = t.b - 1;  // delta(a, a) is infinite: lo qualifies
+            const int whole = tree_rule::key_delta(K[t.a], K[t.b], t.a, t.b);  // (a < b)
+            uint32_t lo = t.a, hi = t.b - 1;  // delta(a, a) is infinite: lo qualifies, and only a mid > a is asked
             while (lo < hi) {
                 const uint32_t mid = lo + (hi - lo + 1) / 2;
-                if (leaf_delta(K, t.a, mid) > whole) lo = mid; else hi = mid - 1;
+                if (tree_rule::key_delta(K[t.a], K[mid], t.a, mid) > whole) lo = mid; else hi = mid - 1;
             }
             todo.push_back(Todo{lo + 1, t.b, self, false, t.level + 1});
             todo.push_back(Todo{t.a, lo, self, true, t.level + 1});

@@ -1,12 +1,12 @@
 // image_lib.h — the scaffold of the ten image libraries (denoise/denoise.hip, temporal/temporal.hip, converge/converge.hip, refine/refine.hip,
 // adaptive/adaptive.hip, moments/moments.hip, display/display.hip, antilag/antilag.hip, edges/edges.hip, despeckle/despeckle.hip), private
 // to them: the last-error string, the handle's device and stream with the shared parts of create / destroy / finish, the grow-only device
-// buffer, the handle and size checks, the 64 x 4 row block, the staging of a G-buffer for the _host entry points, and the two device
-// functions more than one library states: the luminance and "what is a surface pixel". Each library is one translation unit that includes
-// this once, so everything sits in an anonymous namespace and every library has its own copy (its own last error). The checks take the
-// library's name: every message starts with it. DESIGN.md "The image libraries' scaffold" says what stays in each library.
-// refit/refit.hip, which is no image library (it refits the uploaded tree), takes the last error, HIP_TRY, the handle and the grow-only
-// buffer from here too.
+// buffer, the handle, size and overlap checks, the caller's parameters or the defaults, the 64 x 4 row block, the staging of a G-buffer
+// for the _host entry points, and the two device functions more than one library states: the luminance and "what is a surface pixel".
+// Each library is one translation unit that includes this once, so everything sits in an anonymous namespace and every library has its
+// own copy (its own last error). The checks take the library's name: every message starts with it. DESIGN.md "The image libraries'
+// scaffold" says what stays in each library. refit/refit.hip and treebuild/build.hip, which are no image libraries (they work on the
+// uploaded tree), take the last error, HIP_TRY, the handle, the checks and the grow-only buffer from here too.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -92,6 +92,21 @@ inline bool misaligned(std::initializer_list<const void *> ptrs, size_t align) {
     for (const void *p : ptrs)
         if ((uintptr_t)p % align) return true;
     return false;
+}
+
+/// Do the na bytes at a and the nb bytes at b share a byte?
+inline bool overlaps(const void *a, size_t na, const void *b, size_t nb) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + nb && pb < pa + na;
+}
+
+/// The caller's parameters, or with p = NULL what the library's own gpuart_<name>_defaults fills in.
+template <class P>
+P params_or_defaults(const P *p, int (*defaults)(P *)) {
+    P v;
+    if (p) v = *p;
+    else defaults(&v);
+    return v;
 }
 
 // ---- device memory ---------------------------------------------------------------------------------------------------------------

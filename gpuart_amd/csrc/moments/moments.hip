@@ -106,11 +106,6 @@ struct gpuart_moments : ImageHandle {
 
 namespace {
 
-bool overlaps(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
-
 int check_pack(gpuart_moments *m, const void *rgba, uint32_t spp, uint32_t w, uint32_t h, const void *out, size_t align) {
     if (int rc = check_handle(LIB, m)) return rc;
     if (!rgba || !out) return fail(GPUART_HIP_ERR_ARG, "moments: rgba or out is NULL");
@@ -140,13 +135,6 @@ int check_error(gpuart_moments *m, const void *rgba, const void *len, const void
         overlaps(e, n * 4, prims, n * 4))
         return fail(GPUART_HIP_ERR_ARG, "moments: e overlaps an input");
     return 0;
-}
-
-gpuart_moments_params params_or_defaults(const gpuart_moments_params *p) {
-    gpuart_moments_params v;
-    if (p) v = *p;
-    else gpuart_moments_defaults(&v);
-    return v;
 }
 
 int launch_pack(gpuart_moments *m, const float4 *rgba, uint32_t spp, int w, int h, float4 *out) {
@@ -212,7 +200,7 @@ int gpuart_moments_error(gpuart_moments *m, const float *rgba, const float *len,
     if (int rc = check_error(m, rgba, len, moments, hits, prims, lum_floor, w, h, p, e, 16)) return rc;
     HIP_TRY(hipSetDevice(m->device));
     return launch_error(m, (const float4 *)rgba, len, (const float4 *)moments, (const float4 *)hits, prims, userSphereFlags, lum_floor, (int)w,
-                        (int)h, params_or_defaults(p), e);
+                        (int)h, params_or_defaults(p, gpuart_moments_defaults), e);
 }
 
 int gpuart_moments_error_host(gpuart_moments *m, const float *rgba, const float *len, const float *moments, const gpuart_ray_hit *hits,
@@ -231,7 +219,7 @@ int gpuart_moments_error_host(gpuart_moments *m, const float *rgba, const float 
     float *err = ln + n;
     HIP_TRY(hipMemcpyAsync(mom, moments, n * 16, hipMemcpyHostToDevice, m->stream));
     HIP_TRY(hipMemcpyAsync(ln, len, n * 4, hipMemcpyHostToDevice, m->stream));
-    if ((rc = launch_error(m, in.rgba, ln, mom, in.hits, in.prims, userSphereFlags, lum_floor, (int)w, (int)h, params_or_defaults(p), err))) return rc;
+    if ((rc = launch_error(m, in.rgba, ln, mom, in.hits, in.prims, userSphereFlags, lum_floor, (int)w, (int)h, params_or_defaults(p, gpuart_moments_defaults), err))) return rc;
     HIP_TRY(hipMemcpyAsync(e, err, n * 4, hipMemcpyDeviceToHost, m->stream));
     HIP_TRY(hipStreamSynchronize(m->stream));
     return 0;

@@ -2,30 +2,40 @@
 // includes this once, after image/image_lib.h): one launch of k_rf_level per tree level, deepest first, then k_rf_root. A leaf's box is its
 // primitives' boxes folded in leaf order, an interior node's its lower child's folded with its upper child's (include/gpuart_refit.h).
 // Nothing is handed between workgroups inside a launch: a level reads what the launch before it wrote (DESIGN.md "Refit").
+// Before it, what both libraries ask of the gpuart_hip_scene they are given.
 #pragma once
 #include "../hip/prim_rule.h"
+#include "../hip/tree_rule.h"
 
 namespace {
 
 #define RF_FN __device__ __forceinline__
 
-// the refs of a record (csrc/hip/device_scene.h GD_REF_*)
-constexpr uint32_t REF_LEAF = 0x80000000u, REF_INDEX = 0x0fffffffu;
+using tree_rule::REF_INDEX;
+using tree_rule::REF_LEAF;
+
+/// The checks of a scene descriptor whose tree is to be refitted or rebuilt (`done`: "refitted", "rebuilt"). Every message starts with
+/// `lib`, and names the argument where the library takes more than one descriptor (`arg`, else "").
+inline int check_descriptor(const gpuart_hip_scene *s, const char *lib, const char *arg, const char *done) {
+    const std::string w = std::string(lib) + ": " + (*arg ? std::string(arg) + ": " : "");
+    if (s->layout != 1) return fail(GPUART_HIP_ERR_ARG, w + "unknown layout " + std::to_string(s->layout));
+    if (s->exact_boxes) return fail(GPUART_HIP_ERR_ARG, w + "a tree with irregular boxes (or boxes that do not bound their contents) is not " + done);
+    if (!s->prims || !s->prim_boxes || !s->n_prims || (s->n_recs && !s->recs) || s->n_prims > REF_INDEX || s->n_recs > REF_INDEX)
+        return fail(GPUART_HIP_ERR_ARG, w + "the scene's arrays or counts are empty or out of range");
+    return 0;
+}
 
 /// What the device sequence leaves for the host, in device memory; all zero before a run. `refused` = ~(4 x index + why) of the first
 /// offending update — the largest over the updates (atomicMax) —, 0 while no update is refused.
 struct Status {
     uint32_t refused;
-    uint32_t subnormal;  ///< some plane written fails plane_ok
+    uint32_t subnormal;  ///< some plane written fails tree_rule::plane_ok (a subnormal number is kept here, and fails it)
     float root_min[3], root_max[3];
 };
 
-/// csrc/hip/box_quick.h gq_plane_ok: zero, or at least 2^-60 in magnitude (false for NaN and for a subnormal number, which is kept here).
-RF_FN bool plane_ok(float p) { return p == 0.0f || (p >= 8.6736173798840355e-19f || p <= -8.6736173798840355e-19f); }
-
 RF_FN bool planes_ok(const float lo[3], const float hi[3]) {
     bool ok = true;
-    for (int k = 0; k < 3; k++) ok = ok && plane_ok(lo[k]) && plane_ok(hi[k]);
+    for (int k = 0; k < 3; k++) ok = ok && tree_rule::plane_ok(lo[k]) && tree_rule::plane_ok(hi[k]);
     return ok;
 }
 

@@ -188,10 +188,7 @@ int gpuart_refit_bind(gpuart_refit *h, const gpuart_hip_scene *s) {
     if (int rc = check_handle(LIB, h)) return rc;
     if (!s) return fail(GPUART_HIP_ERR_ARG, "refit: scene is NULL");
     h->bound = false;
-    if (s->layout != 1) return fail(GPUART_HIP_ERR_ARG, "refit: unknown layout " + std::to_string(s->layout));
-    if (s->exact_boxes) return fail(GPUART_HIP_ERR_ARG, "refit: a tree with irregular boxes (or boxes that do not bound their contents) is not refitted");
-    if (!s->prims || !s->prim_boxes || !s->n_prims || (s->n_recs && !s->recs) || s->n_prims > REF_INDEX || s->n_recs > REF_INDEX)
-        return fail(GPUART_HIP_ERR_ARG, "refit: the scene's arrays or counts are empty or out of range");
+    if (int rc = check_descriptor(s, LIB, "", "refitted")) return rc;
     HIP_TRY(hipSetDevice(h->device));
     const size_t n_recs = s->n_recs, n_prims = s->n_prims;
     // every leaf's count, which its first primitive carries, and the records
@@ -214,7 +211,7 @@ int gpuart_refit_bind(gpuart_refit *h, const gpuart_hip_scene *s) {
     std::vector<char> seen(n_recs, 0);
     uint32_t deepest = 0;
     const auto bad_tree = [] { return fail(GPUART_HIP_ERR_ARG, "refit: the records' refs do not form the tree the counts describe"); };
-    if (n_recs ? s->root_ref != 0 : !((s->root_ref & REF_LEAF) && leaf_ok(s->root_ref))) return bad_tree();
+    if (!tree_rule::root_ref_ok(s->root_ref, n_recs, n_prims) || (!n_recs && !leaf_ok(s->root_ref))) return bad_tree();
     for (size_t r = 0; r < n_recs; r++) {
         if (r && !seen[r]) return bad_tree();
         for (int c = 0; c < 2; c++) {

@@ -18,7 +18,6 @@ namespace {
 
 const char LIB[] = "build";
 
-constexpr uint32_t REF_TRIS = 0x40000000u, REF_TWO = 0x20000000u, REF_SMALL = 0x10000000u;  // csrc/hip/device_scene.h GD_REF_*
 constexpr uint32_t MAX_LEVELS = GPUART_BUILD_MAX_LEVELS;
 constexpr uint32_t CHILD_LEAF = 0x80000000u;  ///< a child code: this bit | leaf index, or an interior node's index
 constexpr uint32_t PARENT_LOWER = 0x80000000u;  ///< a parent link: this bit when the node is its parent's lower child
@@ -33,35 +32,13 @@ struct Extra {
 };
 
 // 1. One thread per primitive: its 63-bit key from its box and the root box, and its ordinal as the sort's value.
-RF_FN uint64_t spread3(uint32_t q) {
-    uint64_t x = q & 0x1fffffu;
-    x = (x | x << 32) & 0x1f00000000ffffull;
-    x = (x | x << 16) & 0x1f0000ff0000ffull;
-    x = (x | x << 8) & 0x100f00f00f00f00full;
-    x = (x | x << 4) & 0x10c30c30c30c30c3ull;
-    x = (x | x << 2) & 0x1249249249249249ull;
-    return x;
-}
-
 struct Box3 { float lo[3], hi[3]; };
 
 __global__ void __launch_bounds__(256) k_bd_keys(const float *pbox, uint32_t n, Box3 root, uint64_t *keys, uint32_t *vals) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     const float *b = pbox + 6 * (size_t)i;
-    uint64_t key = 0;
-    for (int k = 0; k < 3; k++) {
-        const float c = b[k] * 0.5f + b[3 + k] * 0.5f;
-        const float e = root.hi[k] - root.lo[k];
-        const float t = (c - root.lo[k]) / e;
-        uint32_t q = 0;
-        if (e > 0.0f && t > 0.0f) {
-            const float s = t * 2097152.0f;
-            q = s >= 2097151.0f ? 2097151u : (uint32_t)s;
-        }
-        key |= spread3(q) << (2 - k);
-    }
-    keys[i] = key;
+    keys[i] = tree_rule::morton_key(b, b + 3, root.lo, root.hi);
     vals[i] = i;
 }
 
@@ -84,15 +61,16 @@ __global__ void __launch_bounds__(256) k_bd_permute(const float4 *src, const flo
     for (int k = 0; k < 6; k++) db[k] = sb[k];
 }
 
-/// delta(i, j) over the m leaf keys (leaf j's key is that of position 2j); -1 outside.
+/// delta(i, j) over the m leaf keys (leaf j's key is that of position 2j); -1 outside. Never asked for j == i (k_bd_hierarchy).
 RF_FN int delta(const uint64_t *keys, uint32_t m, uint32_t i, int64_t j) {
     if (j < 0 || j >= (int64_t)m) return -1;
-    const uint64_t x = keys[2 * (size_t)i] ^ keys[2 * (size_t)j];
-    return x ? __clzll((long long)x) : 64 + __clz((int)(i ^ (uint32_t)j));
+    return tree_rule::key_delta(keys[2 * (size_t)i], keys[2 * (size_t)j], i, (uint32_t)j);
 }
 
 // 4. One thread per interior node i (the node whose range begins or ends at leaf i; the root is node 0): its range, split and children,
-// and the parent link of each interior child — slots no other thread writes.
+// and the parent link of each interior child — slots no other thread writes. Every j that delta is asked for differs from i: the
+// neighbours i +- 1, i + (a step >= 1) x d while searching the far end and the split, and the far end itself, l >= 1 steps away
+// (delta(i, i + d) > dmin by the choice of d).
 __global__ void __launch_bounds__(256) k_bd_hierarchy(const uint64_t *keys, uint32_t m, uint32_t *lower, uint32_t *upper, uint32_t *first, uint32_t *parent) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i + 1 >= m) return;
@@ -154,13 +132,14 @@ __global__ void k_bd_offsets(Extra *ex) {
     for (uint32_t l = 0; l < MAX_LEVELS; l++) { ex->cursor[l] = at; at += ex->hist[l]; }
 }
 
-/// The ref of leaf j as Converter::scan forms it: one or two primitives, all triangles or not.
+/// The ref of leaf j: one or two primitives, all triangles or not. The last line is tree_rule::leaf_ref(p, two ? 2 : 1, tris) written
+/// out with its constants (see there).
 RF_FN uint32_t leaf_ref(const float4 *prims, uint32_t n, uint32_t j) {
     const uint32_t p = 2u * j;
     const bool two = p + 1u < n;
     bool tris = (__float_as_uint(prims[3 * (size_t)p].w) & 3u) == (uint32_t)prim_rule::TRIANGLE;
     if (two) tris = tris && (__float_as_uint(prims[3 * (size_t)p + 3].w) & 3u) == (uint32_t)prim_rule::TRIANGLE;
-    return REF_LEAF | p | (tris ? REF_TRIS : REF_SMALL) | (two ? REF_TWO : 0u);
+    return REF_LEAF | p | (tris ? tree_rule::REF_TRIS : tree_rule::REF_SMALL) | (two ? tree_rule::REF_TWO : 0u);
 }
 
 // 6. One thread per interior node: the fourth words of its record — the two refs, the mark and the pad (the box pass writes the other
@@ -237,32 +216,6 @@ struct gpuart_build : ImageHandle {
     double step_ms[7] = {0, 0, 0, 0, 0, 0, 0};
 };
 
-namespace {
-
-bool box_ok(const float lo[3], const float hi[3]) {
-    for (int k = 0; k < 3; k++)
-        if (!(lo[k] <= hi[k]) || std::isinf(lo[k]) || std::isinf(hi[k])) return false;
-    return true;
-}
-
-bool overlap(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && x < y + nb && y < x + na;
-}
-
-int check_scene(const gpuart_hip_scene *s, const char *which) {
-    const std::string w = std::string("build: ") + which;
-    if (!s) return fail(GPUART_HIP_ERR_ARG, w + " is NULL");
-    if (s->layout != 1) return fail(GPUART_HIP_ERR_ARG, w + ": unknown layout " + std::to_string(s->layout));
-    if (s->exact_boxes) return fail(GPUART_HIP_ERR_ARG, w + ": a tree with irregular boxes (or boxes that do not bound their contents) is not rebuilt");
-    if (!s->prims || !s->prim_boxes || !s->n_prims || (s->n_recs && !s->recs) || s->n_prims > REF_INDEX || s->n_recs > REF_INDEX)
-        return fail(GPUART_HIP_ERR_ARG, w + ": the scene's arrays or counts are empty or out of range");
-    if (misaligned({s->recs, s->prims}, 16) || misaligned({s->prim_boxes}, 4)) return fail(GPUART_HIP_ERR_ARG, w + ": misaligned arrays");
-    return 0;
-}
-
-}  // namespace
-
 extern "C" {
 
 const char *gpuart_build_last_error(void) { return g_last_error.c_str(); }
@@ -302,11 +255,13 @@ int gpuart_build_step_ms(gpuart_build *h, double ms[7]) {
 
 int gpuart_build_run(gpuart_build *h, const gpuart_hip_scene *src, const gpuart_hip_scene *dst, uint32_t *new_to_old, gpuart_build_result *result) {
     if (int rc = check_handle(LIB, h)) return rc;
-    if (int rc = check_scene(src, "src")) return rc;
+    if (!src) return fail(GPUART_HIP_ERR_ARG, "build: src is NULL");
+    if (int rc = check_descriptor(src, LIB, "src", "rebuilt")) return rc;
+    if (misaligned({src->recs, src->prims}, 16) || misaligned({src->prim_boxes}, 4)) return fail(GPUART_HIP_ERR_ARG, "build: src: misaligned arrays");
     if (!dst) return fail(GPUART_HIP_ERR_ARG, "build: dst is NULL");
     if (dst->layout != 1) return fail(GPUART_HIP_ERR_ARG, "build: dst: unknown layout " + std::to_string(dst->layout));
     const size_t n = src->n_prims, m = (n + 1) / 2, n_recs = m - 1;
-    if (!box_ok(src->root_min, src->root_max)) return fail(GPUART_HIP_ERR_ARG, "build: the root box is not finite and ordered");
+    if (!tree_rule::box_ok(src->root_min, src->root_max)) return fail(GPUART_HIP_ERR_ARG, "build: the root box is not finite and ordered");
     if (!new_to_old || misaligned({new_to_old}, 4)) return fail(GPUART_HIP_ERR_ARG, "build: new_to_old is NULL or misaligned");
     if (!dst->prims || !dst->prim_boxes || (n_recs && !dst->recs) || misaligned({dst->recs, dst->prims}, 16) || misaligned({dst->prim_boxes}, 4))
         return fail(GPUART_HIP_ERR_ARG, "build: dst's arrays are NULL or misaligned");
@@ -317,10 +272,10 @@ int gpuart_build_run(gpuart_build *h, const gpuart_hip_scene *src, const gpuart_
                                                   D[4] = {{dst->recs, n_recs * 64}, {dst->prims, n * 48}, {dst->prim_boxes, n * 24}, {new_to_old, n * 4}};
     for (const auto &s : S)
         for (const auto &d : D)
-            if (s.bytes && d.bytes && overlap(s.p, s.bytes, d.p, d.bytes)) return fail(GPUART_HIP_ERR_ARG, "build: dst's arrays alias src's");
+            if (s.bytes && d.bytes && overlaps(s.p, s.bytes, d.p, d.bytes)) return fail(GPUART_HIP_ERR_ARG, "build: dst's arrays alias src's");
     for (int a = 0; a < 4; a++)
         for (int b = a + 1; b < 4; b++)
-            if (D[a].bytes && D[b].bytes && overlap(D[a].p, D[a].bytes, D[b].p, D[b].bytes)) return fail(GPUART_HIP_ERR_ARG, "build: dst's arrays overlap");
+            if (D[a].bytes && D[b].bytes && overlaps(D[a].p, D[a].bytes, D[b].p, D[b].bytes)) return fail(GPUART_HIP_ERR_ARG, "build: dst's arrays overlap");
     HIP_TRY(hipSetDevice(h->device));
     if (n == 1) {  // an empty scene keeps one dummy record, whose count is 0 (converter.h)
         uint32_t word = 0;

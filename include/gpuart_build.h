@@ -4,8 +4,9 @@
  * set gpuart_hip_scene_reserve hands out; it knows nothing of contexts, frames or passes, and the caller tells the context afterwards
  * (gpuart_hip_scene_rebuilt). DESIGN.md "Rebuild" has the contract, the launches and the limits.
  *
- * The contract (tests/build_ref.py restates it in NumPy; the host library's BoundingVolumesHierarchy::RebuildMorton is a second
- * statement). Primitive i has the box its constructor gave it (prim_boxes); R is the scene's root box. All in fp32 with denormals kept,
+ * The contract (tests/build_ref.py restates it in NumPy; the key and delta are written once for the device and the host library,
+ * csrc/hip/tree_rule.h, and the host library's BoundingVolumesHierarchy::RebuildMorton is a second statement of the topology only, by
+ * bisection). Primitive i has the box its constructor gave it (prim_boxes); R is the scene's root box. All in fp32 with denormals kept,
  * no contraction and IEEE division:
  *   key      per axis k: c = lo_k*0.5f + hi_k*0.5f, e = Rmax_k - Rmin_k, t = (c - Rmin_k) / e,
  *            q_k = e > 0 && t > 0 ? min(2^21 - 1, (uint32)(t * 2097152.0f)) : 0; bit 3b+2 of the key = bit b of q_x, 3b+1 of q_y, 3b of q_z;
