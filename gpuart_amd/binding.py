@@ -68,7 +68,15 @@ class BuildResult(C.Structure):
                 ("root_min", C.c_float * 3), ("root_max", C.c_float * 3)]
 
 
+class PlocResult(C.Structure):
+    """gpuart_ploc_result (include/gpuart_ploc.h)."""
+    _fields_ = [("n_recs", C.c_uint64), ("root_ref", C.c_uint32), ("max_depth", C.c_uint32), ("subnormal", C.c_uint32), ("iterations", C.c_uint32),
+                ("root_min", C.c_float * 3), ("root_max", C.c_float * 3)]
+
+
 REFIT_PAYLOAD = 16  # GPUART_REFIT_PAYLOAD
+PLOC_STEPS = ("keys", "sort", "iterations", "number", "emit", "permute")  # gpuart_ploc_step_ms
+TREE_MODES = {"morton": 0, "clustered": 1}  # Renderer::TreeMode
 BUILD_STEPS = ("keys", "sort", "permute", "hierarchy", "number", "emit", "levels")  # gpuart_build_step_ms
 RAY_HIT = np.dtype([("pos", np.float32), ("p", np.float32, 3), ("n", np.float32, 3), ("type", np.int32)])
 RAYS_OCCLUSION = 1  # GPUART_HIP_RAYS_OCCLUSION
@@ -378,6 +386,12 @@ def build_lib():
     return _image_lib("build")
 
 
+def ploc_lib():
+    """libgpuart_ploc.so (include/gpuart_ploc.h), built by the image libraries' rule; raises NativeLibraryMissing if it has not been built
+    (no fallback)."""
+    return _image_lib("ploc")
+
+
 def display_lib():
     """libgpuart_display.so; raises NativeLibraryMissing if it has not been built (no fallback)."""
     return _image_lib("display")
@@ -455,6 +469,26 @@ def rebuild_tree(quads, order=None):
     if n is None:
         n = sum(1 for _ in _leaf_prims(res))
     return res, perm[:n].copy()
+
+
+def adopt_tree(quads, order, refs):
+    """gpuart_adopt_tree: BoundingVolumesHierarchy::AdoptTopology on the compiled tree `quads`, without a device -> quads'. `order`: the old
+    ordinal of every new one; `refs`: two child refs per record in pre-order (include/gpuart_ploc.h). ValueError for a malformed tree
+    (-1) or a refusal (-2)."""
+    L = host_lib()
+    q = np.ascontiguousarray(quads, np.float32).reshape(-1)
+    o = np.ascontiguousarray(order, np.uint32).reshape(-1)
+    r = np.ascontiguousarray(refs, np.uint32).reshape(-1)
+    if r.size % 2:
+        raise ValueError("adopt_tree: two refs per record")
+    out = C.POINTER(C.c_float)()
+    nout = C.c_size_t(0)
+    rc = L.gpuart_adopt_tree(_p(q), C.c_size_t(q.size // 4), _p(o), _p(r) if r.size else None, C.c_size_t(r.size // 2), C.byref(out), C.byref(nout))
+    if rc != 0:
+        raise ValueError("gpuart_adopt_tree: %d" % rc)
+    res = np.ctypeslib.as_array(out, shape=(nout.value, 4)).copy()
+    L.gpuart_free(out)
+    return res
 
 
 def _leaf_prims(quads):
@@ -752,7 +786,7 @@ class Backend:
             raise e
 
     def close(self):
-        for handle in (getattr(self, "_refit", None), getattr(self, "_build", None)):
+        for handle in (getattr(self, "_refit", None), getattr(self, "_build", None), getattr(self, "_ploc", None)):
             if handle is not None:
                 handle.close()
         if self.owned and self.ctx:
@@ -850,42 +884,56 @@ class Backend:
             self._build = _BuildHandle(self.device)
         return self._build
 
-    def rebuild(self, out=None):
-        """Rebuilds the uploaded scene's tree on the device in Morton order (include/gpuart_build.h) and has the context adopt it: the
+    def rebuild(self, out=None, mode="morton"):
+        """Rebuilds the uploaded scene's tree on the device and has the context adopt it — `mode` "morton": in Morton order
+        (include/gpuart_build.h), fast to build; "clustered": by locally-ordered clustering (include/gpuart_ploc.h), a tree of lower cost
+        for more launches; `last_rebuild` then holds iterations in place of levels, and gpuart_ploc_step_ms's steps. The
         primitives are renumbered, new device ordinal p is the old new_to_old[p]. Returns new_to_old: when torch is in use (the process
         has imported it) an int32 tensor on this device, and nothing crosses the host; else a NumPy uint32 array. `out` overrides that:
         a contiguous int32 torch tensor of n_prims entries on this device is written in place and returned, True makes one, False asks
         for the NumPy array. What the build reported is kept in `last_rebuild`: dict(n_recs, root_ref, max_depth, subnormal, levels,
         root_min, root_max, step_ms). A refusal raises HipError with code -1 (ERR_ARG) and nothing changed. Passes requested before
         the call render the old tree."""
-        Bd = build_lib()
-        h = self._build_handle()
+        if mode not in TREE_MODES:
+            raise ValueError("rebuild: mode must be one of %s" % sorted(TREE_MODES))
+        clustered = mode == "clustered"
+        if clustered:
+            if getattr(self, "_ploc", None) is None:
+                self._ploc = _PlocHandle(self.device)
+            Bd, h, res = ploc_lib(), self._ploc, PlocResult()
+            run, run_host, step_ms, steps = Bd.gpuart_ploc_run, Bd.gpuart_ploc_run_host, Bd.gpuart_ploc_step_ms, PLOC_STEPS
+        else:
+            Bd, h, res = build_lib(), self._build_handle(), BuildResult()
+            run, run_host, step_ms, steps = Bd.gpuart_build_run, Bd.gpuart_build_run_host, Bd.gpuart_build_step_ms, BUILD_STEPS
         scene = self.scene_device()
         n = int(scene.n_prims)
-        spare = self.scene_reserve((n + 1) // 2 - 1 if n else 0)
-        res = BuildResult()
+        spare = self.scene_reserve((n - 1 if clustered else (n + 1) // 2 - 1) if n else 0)
         if out is None:
             out = "torch" in sys.modules
         if out is False:
             perm = np.zeros(n, np.uint32)
-            rc = Bd.gpuart_build_run_host(h, C.byref(scene), C.byref(spare), _p(perm), C.byref(res))
+            rc = run_host(h, C.byref(scene), C.byref(spare), _p(perm), C.byref(res))
         else:
             import torch
             perm = torch.empty((n,), dtype=torch.int32, device="cuda:%d" % self.device) if out is True else out
             if not (hasattr(perm, "data_ptr") and perm.is_cuda and perm.is_contiguous() and perm.dtype == torch.int32 and perm.numel() == n):
                 raise ValueError("rebuild: out must be a contiguous int32 tensor of n_prims entries on the device")
             torch.cuda.synchronize(perm.device)
-            rc = Bd.gpuart_build_run(h, C.byref(scene), C.byref(spare), C.c_void_p(perm.data_ptr()), C.byref(res))
+            rc = run(h, C.byref(scene), C.byref(spare), C.c_void_p(perm.data_ptr()), C.byref(res))
         h._chk(rc)
         spare.n_recs, spare.root_ref, spare.max_depth = res.n_recs, res.root_ref, res.max_depth
         spare.root_min, spare.root_max = res.root_min, res.root_max
         spare.box_slack = float("inf") if res.subnormal else 0.0
         self.scene_rebuilt(spare)
-        ms = (C.c_double * 7)()
-        h._chk(Bd.gpuart_build_step_ms(h, ms))
+        ms = (C.c_double * len(steps))()
+        h._chk(step_ms(h, ms))
         self.last_rebuild = dict(n_recs=int(res.n_recs), root_ref=int(res.root_ref), max_depth=int(res.max_depth), subnormal=bool(res.subnormal),
-                                 levels=int(res.levels), root_min=np.array(res.root_min[:], np.float32), root_max=np.array(res.root_max[:], np.float32),
-                                 step_ms=dict(zip(BUILD_STEPS, [float(v) for v in ms])))
+                                 root_min=np.array(res.root_min[:], np.float32), root_max=np.array(res.root_max[:], np.float32),
+                                 step_ms=dict(zip(steps, [float(v) for v in ms])))
+        if clustered:
+            self.last_rebuild["iterations"] = int(res.iterations)
+        else:
+            self.last_rebuild["levels"] = int(res.levels)
         return perm
 
     def tree_cost(self):
@@ -1266,14 +1314,17 @@ class Renderer:
             raise ValueError("update_primitives: one description per index")
         return bool(self.L.gpuart_renderer_update_primitives(self.h, _p(idx), arr, C.c_int(len(arr))))
 
-    def rebuild_tree(self):
-        """Renderer::RebuildTree: the tree rebuilt on the device in Morton order, the temporal history kept. Returns new_to_old (per new
+    def rebuild_tree(self, mode="morton"):
+        """Renderer::RebuildTree: the tree rebuilt on the device — `mode` "morton": in Morton order; "clustered": by locally-ordered
+        clustering (Renderer::TREE_CLUSTERED: slower to build, cheaper to walk) —, the temporal history kept. Returns new_to_old (per new
         device ordinal the old one; the indices of update_primitives and the ordinals of trace_rays keep numbering the descriptions
         set_primitives was given), or None — nothing changed — on a refusal."""
         n = C.c_uint64()
         self.L.gpuart_renderer_scene_info(self.h, None, C.byref(n), None)
         perm = np.zeros(int(n.value), np.uint32)
-        return perm if self.L.gpuart_renderer_rebuild_tree(self.h, _p(perm)) else None
+        if mode not in TREE_MODES:
+            raise ValueError("rebuild_tree: mode must be one of %s" % sorted(TREE_MODES))
+        return perm if self.L.gpuart_renderer_rebuild_tree_mode(self.h, C.c_int(TREE_MODES[mode]), _p(perm)) else None
 
     def tree_cost(self):
         """Renderer::TreeCost, or None on failure."""
@@ -1634,6 +1685,11 @@ class _RefitHandle(_ImageHandle):
 class _BuildHandle(_ImageHandle):
     """Backend.rebuild's and tree_cost's gpuart_build, made at the first of them."""
     NAME, Error = "build", HipError
+
+
+class _PlocHandle(_ImageHandle):
+    """Backend.rebuild(mode="clustered")'s gpuart_ploc, made at the first of them."""
+    NAME, Error = "ploc", HipError
 
 
 def _gbuffer_args(device, rgba, hits, prims, out):

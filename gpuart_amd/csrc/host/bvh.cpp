@@ -503,19 +503,8 @@ bool BoundingVolumesHierarchy::RebuildMorton(std::vector<uint32_t> *newToOld, co
     const size_t n = NumPrimitives;
     if (n == 0 || n > tree_rule::REF_INDEX) return false;
     // every primitive's header in LeafData, by old ordinal, and its box
-    std::vector<size_t> header(n);
-    {
-        size_t k = 0;
-        for (const Node &node : Nodes) {
-            size_t at = node.dataBegin;
-            for (uint32_t j = 0; j < node.count; j++, k++) {
-                if (k >= n || node.primFirst + j != k) return false;
-                header[k] = at;
-                at += RGBA_ELEMS * (2 + (size_t)(as_uint(LeafData[at]) & 3));
-            }
-        }
-        if (k != n) return false;
-    }
+    std::vector<size_t> header;
+    if (!PrimHeaders(header)) return false;
     std::vector<float> box(6 * n);
     float rlo[3], rhi[3];
     prim_rule::box_start(rlo, rhi);
@@ -591,6 +580,92 @@ bool BoundingVolumesHierarchy::RebuildMorton(std::vector<uint32_t> *newToOld, co
     LocateCursor = 0;
     for (size_t i = Nodes.size(); i-- > 0;) RefitNode(i);  // pre-order: children lie behind their parent
     if (newToOld) newToOld->swap(perm);
+    return true;
+}
+
+bool BoundingVolumesHierarchy::PrimHeaders(std::vector<size_t> &header) const {
+    const size_t n = NumPrimitives;
+    header.resize(n);
+    size_t k = 0;
+    for (const Node &node : Nodes) {
+        size_t at = node.dataBegin;
+        for (uint32_t j = 0; j < node.count; j++, k++) {
+            if (k >= n || node.primFirst + j != k) return false;
+            header[k] = at;
+            at += RGBA_ELEMS * (2 + (size_t)(as_uint(LeafData[at]) & 3));
+        }
+    }
+    return k == n;
+}
+
+// ---- a topology built elsewhere (the device's clustered rebuild, include/gpuart_ploc.h): checked in one walk, then the nodes are laid
+// out as that walk met them and every box comes from the Refit rule ----
+bool BoundingVolumesHierarchy::AdoptTopology(const uint32_t *newToOld, const uint32_t *refs, size_t nRecs) {
+    const size_t n = NumPrimitives;
+    if (n == 0 || n > tree_rule::REF_INDEX || !newToOld || (nRecs && !refs) || nRecs >= n || (!nRecs && n > 2)) return false;
+    std::vector<size_t> header;
+    if (!PrimHeaders(header)) return false;
+    {
+        std::vector<bool> seen(n, false);
+        for (size_t p = 0; p < n; p++) {
+            if (newToOld[p] >= n || seen[newToOld[p]]) return false;
+            seen[newToOld[p]] = true;
+        }
+    }
+    const auto type_of = [&](size_t p) { return as_uint(LeafData[header[newToOld[p]]]) & 3; };
+    struct Todo { uint32_t ref, parent; bool isLower; unsigned level; };
+    std::vector<Node, UninitAlloc<Node>> nodes;
+    std::vector<float, UninitAlloc<float>> data;
+    nodes.reserve(2 * nRecs + 1);
+    data.reserve(LeafData.size());
+    // (without records the root is the leaf of all the primitives; its flags are made to fit and pass the check below)
+    const bool rootTris = type_of(0) == prim_rule::TRIANGLE && (n < 2 || type_of(1) == prim_rule::TRIANGLE);
+    std::vector<Todo> todo{{nRecs ? 0u : tree_rule::leaf_ref(0, (uint32_t)n, rootTris), 0, false, 0}};
+    size_t nextRec = 0, nextPrim = 0;
+    unsigned depth = 0;
+    while (!todo.empty()) {
+        const Todo t = todo.back();
+        todo.pop_back();
+        if (t.level > 1024) return false;
+        const uint32_t self = (uint32_t)nodes.size();
+        Node node;
+        for (int k = 0; k < 3; k++) node.lo[k] = node.hi[k] = 0;
+        node.parent = t.parent; node.higher = 0; node.isLower = t.isLower; node.count = 0; node.primFirst = 0; node.dataBegin = node.dataEnd = 0;
+        depth = std::max(depth, t.level);
+        if (t.ref & tree_rule::REF_LEAF) {
+            // the next primitives in order, one or two of them, flagged as their types ask
+            const size_t first = t.ref & tree_rule::REF_INDEX, count = t.ref & tree_rule::REF_TWO ? 2 : 1;
+            if (first != nextPrim || first + count > n) return false;
+            bool tris = true;
+            for (size_t j = 0; j < count; j++) tris = tris && type_of(first + j) == prim_rule::TRIANGLE;
+            if (t.ref != tree_rule::leaf_ref((uint32_t)first, (uint32_t)count, tris)) return false;
+            node.primFirst = (uint32_t)first;
+            node.count = (uint32_t)count;
+            node.dataBegin = data.size();
+            for (size_t j = 0; j < count; j++) {
+                const size_t at = header[newToOld[first + j]];
+                data.insert(data.end(), LeafData.begin() + at, LeafData.begin() + at + RGBA_ELEMS * (2 + (size_t)(as_uint(LeafData[at]) & 3)));
+            }
+            node.dataEnd = data.size();
+            nextPrim += count;
+        } else {
+            // a record is met when it is its turn in pre-order, and so exactly once
+            if (t.ref != nextRec || t.ref >= nRecs) return false;
+            nextRec++;
+            todo.push_back(Todo{refs[2 * (size_t)t.ref + 1], self, false, t.level + 1});
+            todo.push_back(Todo{refs[2 * (size_t)t.ref], self, true, t.level + 1});
+        }
+        if (self && !t.isLower) nodes[t.parent].higher = self;
+        nodes.push_back(node);
+    }
+    if (nextRec != nRecs || nextPrim != n) return false;
+    Nodes.swap(nodes);
+    LeafData.swap(data);
+    Depth = depth;
+    QuadAddr.clear();
+    LeafOfFirst.clear();
+    LocateCursor = 0;
+    for (size_t i = Nodes.size(); i-- > 0;) RefitNode(i);  // pre-order: children lie behind their parent
     return true;
 }
 

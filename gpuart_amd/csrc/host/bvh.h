@@ -77,6 +77,15 @@ public:
     /// for an empty tree or an order that fails the check.
     bool RebuildMorton(std::vector<uint32_t> *newToOld, const uint32_t *order = nullptr);
 
+    /// Takes over a topology built elsewhere — the device's clustered rebuild (include/gpuart_ploc.h) — over the primitives as they are
+    /// now, in linear time. `newToOld`: per new ordinal the old one; `refs`: the two child refs of each of the `nRecs` records in
+    /// pre-order (csrc/hip/tree_rule.h: a record's index, or REF_LEAF | flags | the leaf's first new ordinal), lower child first; with
+    /// nRecs = 0 the root is a leaf of the one or two primitives. Checked before anything changes: newToOld is a permutation; the walk
+    /// from record 0 meets every record exactly once and in pre-order, no deeper than 1024 levels; the leaves' ranges tile [0, N) in the
+    /// order they are met, each of one or two primitives, with the flags their primitives' types ask for. The nodes' boxes are then the
+    /// Refit rule's own, so Compile() writes what tests/ploc_ref.py does. False, with nothing changed, for anything else.
+    bool AdoptTopology(const uint32_t *newToOld, const uint32_t *refs, size_t nRecs);
+
     /// Prints a compiled tree, decoding it the way the device code does.
     static void Print(const Primitive::Data &compiledTree, std::ostream &s);
 
@@ -141,6 +150,8 @@ private:
     /// The verdict on an update (CheckRefit's) and, if `where` is given, where each of its primitives lies.
     bool PlanRefit(const uint32_t *indices, const float *payloads, size_t n, const uint32_t *types, size_t *firstBad, std::vector<Place> *where) const;
     void RefitNode(size_t i);  ///< node i's box by the rule, from its primitives or its children's boxes
+    /// Every primitive's header in LeafData, by ordinal. False for a tree whose leaves do not number their primitives in order.
+    bool PrimHeaders(std::vector<size_t> &header) const;
 
     /// Sequential build of [from, to) appended to `out` (reference src/bvh.cpp:35-152).
     static void Subdivide(Subtree &out, ItemList &prims, size_t from, size_t to, unsigned level,

@@ -186,6 +186,20 @@ int gpuart_rebuild_tree(const float *quads, size_t nquads, const uint32_t *order
     return 0;
 }
 
+int gpuart_adopt_tree(const float *quads, size_t nquads, const uint32_t *order, const uint32_t *refs, size_t nRecs, float **out, size_t *nout) {
+    if (!quads || !out || !nout || !order) return -1;
+    BoundingVolumesHierarchy tree;
+    if (!tree.Load(quads, nquads) || tree.CompiledFloats() != nquads * RGBA_ELEMS) return -1;
+    if (!tree.AdoptTopology(order, refs, nRecs)) return -2;
+    const size_t floats = tree.CompiledFloats();
+    float *q = (float *)malloc(floats * sizeof(float));
+    if (!q) return -1;
+    tree.CompileTo(q);
+    *out = q;
+    *nout = floats / RGBA_ELEMS;
+    return 0;
+}
+
 void gpuart_last_build_ms(double out[2]) { out[0] = g_last_build_ms[0]; out[1] = g_last_build_ms[1]; }
 
 void gpuart_camera_basis(const float pos[3], const float dir[3], const float up[3], float fovY, float screenDist,
@@ -247,10 +261,11 @@ int gpuart_renderer_update_primitives(gpuart_renderer *r, const uint32_t *indice
     free_list(list);
     return ok ? 1 : 0;
 }
-int gpuart_renderer_rebuild_tree(gpuart_renderer *r, uint32_t *newToOld) {
+int gpuart_renderer_rebuild_tree(gpuart_renderer *r, uint32_t *newToOld) { return gpuart_renderer_rebuild_tree_mode(r, Renderer::TREE_MORTON, newToOld); }
+int gpuart_renderer_rebuild_tree_mode(gpuart_renderer *r, int mode, uint32_t *newToOld) {
     if (!r) return 0;
     std::vector<uint32_t> perm;
-    if (!r->impl.RebuildTree(&perm)) return 0;
+    if (!r->impl.RebuildTree(&perm, mode)) return 0;
     if (!r->descOf.empty()) {  // the caller's numbering follows the primitives to their new positions
         std::vector<int32_t> moved(perm.size());
         for (size_t p = 0; p < perm.size(); p++) moved[p] = r->descOf[perm[p]];

@@ -52,6 +52,12 @@ int gpuart_refit_tree(const float *quads, size_t nquads, const uint32_t *ordinal
  * the n_prims old ordinals by new ordinal. `order` NULL: the library sorts; else n_prims ordinals that are only checked.
  * 0; -1 for a malformed tree or NULL pointers; -2 for an empty tree or an order that is not the contract's. */
 int gpuart_rebuild_tree(const float *quads, size_t nquads, const uint32_t *order, float **out, size_t *nout, uint32_t *newToOld);
+/* BoundingVolumesHierarchy::AdoptTopology without a device: the canonical compiled tree `quads` takes over the topology the clustered
+ * rebuild made on the device (include/gpuart_ploc.h) and is compiled again; *out is malloc'ed (gpuart_free), *nout its quads. `order`:
+ * n_prims old ordinals by new ordinal; `refs`: the two child refs of each of the n_recs records in pre-order (csrc/hip/tree_rule.h).
+ * 0; -1 for a malformed tree or NULL pointers; -2 for an order that is no permutation or refs that are not a tree over it in pre-order
+ * with leaves of one or two. */
+int gpuart_adopt_tree(const float *quads, size_t nquads, const uint32_t *order, const uint32_t *refs, size_t n_recs, float **out, size_t *nout);
 /* What the library itself spent in the last gpuart_compile_bvh / _from_file of this process: out[0] = BoundingVolumesHierarchy's
  * constructor (the build), out[1] = its compilation into quads, in ms — without the harness around them (making and deleting one
  * Primitive object per description, copying the result into the caller's language). */
@@ -84,6 +90,9 @@ int gpuart_renderer_update_primitives(gpuart_renderer *r, const uint32_t *indice
  * gpuart_renderer_trace_rays and the indices of gpuart_renderer_update_primitives keep numbering the caller's descriptions after
  * gpuart_renderer_set_primitives. 1 on success, 0 — with the scene unchanged — on any refusal. */
 int gpuart_renderer_rebuild_tree(gpuart_renderer *r, uint32_t *newToOld);
+/* The same with Renderer::RebuildTree's mode: 0 the Morton build (what gpuart_renderer_rebuild_tree does), 1 Renderer::TREE_CLUSTERED,
+ * the clustered build of include/gpuart_ploc.h — slower to build, cheaper to walk. */
+int gpuart_renderer_rebuild_tree_mode(gpuart_renderer *r, int mode, uint32_t *newToOld);
 /* Renderer::TreeCost. 1 on success. */
 int gpuart_renderer_tree_cost(gpuart_renderer *r, double *cost);
 /* {total, host tree} ms of the last gpuart_renderer_rebuild_tree. */

@@ -102,6 +102,7 @@ Renderer::~Renderer() {
     DenoiseMem.Release();
     if (Refitter) gpuart_refit_destroy(Refitter);
     if (Builder) gpuart_build_destroy(Builder);
+    if (Clusterer) gpuart_ploc_destroy(Clusterer);
     if (Backend) gpuart_hip_destroy(Backend);
 }
 
@@ -324,8 +325,13 @@ bool Renderer::UpdatePrimitives(const uint32_t *indices, Primitive *const *moved
 // from the device's permutation (RebuildMorton checks the order instead of sorting). The temporal histories are kept as for a refit:
 // their tap validation compares hit point, normal and class, and of the ordinal only "is the user sphere" (-2), which a new numbering
 // does not touch.
-bool Renderer::RebuildTree(std::vector<uint32_t> *newToOld) {
+bool Renderer::RebuildTree(std::vector<uint32_t> *newToOld, int mode) {
     if (!IsOK) return false;
+    if (mode == TREE_CLUSTERED) return RebuildClustered(newToOld);
+    if (mode != TREE_MORTON) {
+        std::cerr << "Renderer: RebuildTree: unknown mode " << mode << "." << std::endl;
+        return false;
+    }
     const auto t0 = std::chrono::high_resolution_clock::now();
     gpuart_hip_scene scene, spare;
     if (!Check(gpuart_hip_scene_device(Backend, &scene), "looking up the scene's device arrays")) return false;
@@ -354,6 +360,57 @@ bool Renderer::RebuildTree(std::vector<uint32_t> *newToOld) {
     }
     const auto t2 = std::chrono::high_resolution_clock::now();
     LastRebuildMs[0] = std::chrono::duration<double, std::milli>(t2 - t0).count();
+    LastRebuildMs[1] = std::chrono::duration<double, std::milli>(t2 - t1).count();
+    if (newToOld) newToOld->swap(order);
+    RefitGeneration = 0;  // the refit handle is bound to the old arrays: the next UpdatePrimitives binds again
+    GBufferValid = false;
+    EdgeListValid = false;
+    ResetPathTracing();
+    return true;
+}
+
+// The clustered build (include/gpuart_ploc.h). The topology is the device's: its ref words come back (two per record), the host tree
+// checks and adopts them, and only then are the device arrays swapped — a refusal anywhere leaves both trees as they were.
+bool Renderer::RebuildClustered(std::vector<uint32_t> *newToOld) {
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    gpuart_hip_scene scene, spare;
+    if (!Check(gpuart_hip_scene_device(Backend, &scene), "looking up the scene's device arrays")) return false;
+    if (scene.exact_boxes || !scene.n_prims || Tree.GetNumPrimitives() != scene.n_prims) {
+        std::cerr << "Renderer: RebuildTree: an empty scene or a tree with irregular boxes (or boxes that do not bound their contents) is not rebuilt." << std::endl;
+        return false;
+    }
+    const uint64_t n = scene.n_prims;
+    if (!Check(gpuart_hip_scene_reserve(Backend, n - 1, &spare), "reserving the spare arrays")) return false;
+    if (!Clusterer && !Check(gpuart_ploc_create(Device, &Clusterer), "creating the clustered build's handle", gpuart_ploc_last_error)) return false;
+    CommitTemporalView();
+    gpuart_ploc_result res;
+    std::vector<uint32_t> order(n);
+    if (!Check(gpuart_ploc_run_host(Clusterer, &scene, &spare, order.data(), &res), "rebuilding the tree", gpuart_ploc_last_error)) return false;
+    const auto t1 = std::chrono::high_resolution_clock::now();
+    // the two ref words of every record: word 3 of its first two quads
+    std::vector<uint32_t> refs(2 * res.n_recs);
+    if (res.n_recs) {
+        std::unique_ptr<uint32_t[]> recs(new uint32_t[16 * res.n_recs]);
+        if (hipMemcpy(recs.get(), spare.recs, 64 * res.n_recs, hipMemcpyDeviceToHost) != hipSuccess) {
+            std::cerr << "Renderer: RebuildTree: reading the built records back failed." << std::endl;
+            return false;
+        }
+        for (uint64_t r = 0; r < res.n_recs; r++) { refs[2 * r] = recs[16 * r + 3]; refs[2 * r + 1] = recs[16 * r + 7]; }
+    }
+    if (!Tree.AdoptTopology(order.data(), refs.data(), res.n_recs)) {
+        std::cerr << "Renderer: RebuildTree: the device's topology is not a tree over the scene's primitives." << std::endl;
+        return false;
+    }
+    const auto t2 = std::chrono::high_resolution_clock::now();
+    spare.n_recs = res.n_recs;
+    spare.root_ref = res.root_ref;
+    spare.max_depth = res.max_depth;
+    memcpy(spare.root_min, res.root_min, 12); memcpy(spare.root_max, res.root_max, 12);
+    spare.box_slack = res.subnormal ? __builtin_inff() : 0.0f;
+    // (the host tree has changed: a device that cannot follow is an inconsistency, not a refusal)
+    if (!Check(gpuart_hip_scene_rebuilt(Backend, &spare), "adopting the rebuilt tree")) return IsOK = false;
+    const auto t3 = std::chrono::high_resolution_clock::now();
+    LastRebuildMs[0] = std::chrono::duration<double, std::milli>(t3 - t0).count();
     LastRebuildMs[1] = std::chrono::duration<double, std::milli>(t2 - t1).count();
     if (newToOld) newToOld->swap(order);
     RefitGeneration = 0;  // the refit handle is bound to the old arrays: the next UpdatePrimitives binds again

@@ -22,6 +22,7 @@
 #include "gpuart_adaptive.h"
 #include "gpuart_antilag.h"
 #include "gpuart_build.h"
+#include "gpuart_ploc.h"
 #include "gpuart_converge.h"
 #include "gpuart_denoise.h"
 #include "gpuart_despeckle.h"
@@ -85,7 +86,13 @@ public:
     /// primitives[i] again as after SetPrimitives. The temporal histories are kept as for UpdatePrimitives (the view is committed first);
     /// the accumulation restarts; GetBVH() is the rebuilt tree. False — everything as it was; std::cerr says why — for a scene whose
     /// tree the uploader classified irregular or disorderly and for an empty scene.
-    bool RebuildTree(std::vector<uint32_t> *newToOld = nullptr);
+    /// `mode`: TREE_MORTON, the build above (0.3-0.6 ms on the device, a tree that walks badly), or TREE_CLUSTERED, the clustered build of
+    /// include/gpuart_ploc.h (locally-ordered clustering from the same order; more launches, a tree of lower cost): Morton when the
+    /// build time is what matters, clustered when the tree will be walked for more than a few passes. The clustered tree's topology
+    /// comes back from the device (two ref words per record) and the host tree adopts it (BoundingVolumesHierarchy::AdoptTopology)
+    /// before the device arrays are swapped: every refusal leaves everything as it was.
+    enum TreeMode { TREE_MORTON = 0, TREE_CLUSTERED = 1 };
+    bool RebuildTree(std::vector<uint32_t> *newToOld = nullptr, int mode = TREE_MORTON);
     /// The tree's cost as gpuart_build_cost measures it on the device arrays: the sum over the records of both children's half-areas
     /// over the root's. It grows as refitted boxes loosen; RebuildTree brings it back down.
     bool TreeCost(double *cost);
@@ -352,6 +359,8 @@ private:
     gpuart_refit *Refitter = nullptr;     ///< made by the first UpdatePrimitives; bound again after every upload (the scene's generation)
     uint64_t RefitGeneration = 0;         ///< the generation Refitter is bound to (0: none; the first upload's is 1)
     gpuart_build *Builder = nullptr;      ///< made by the first RebuildTree or TreeCost
+    gpuart_ploc *Clusterer = nullptr;     ///< made by the first RebuildTree(TREE_CLUSTERED)
+    bool RebuildClustered(std::vector<uint32_t> *newToOld);
     double LastRebuildMs[2] = {0, 0};
     BoundingVolumesHierarchy Tree;
     struct { unsigned width, height; } Viewport{0, 0};
