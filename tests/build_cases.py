@@ -55,8 +55,100 @@ def _mesh_20k():
     return mesh + [mesh[int(k)] for k in rng.choice(len(mesh), 300, replace=False)]
 
 
+# ---- the scenes that tell a wrong rule from the right one (tests/tree_mutants.py says which rules; tests/test_tree_mutants.py holds them to it)
+def _dot(x, y, z, r=0.0):
+    return (SPHERE, [float(x), float(y), float(z), float(r)])
+
+
+def _rows(first=1500000, nx=10, ny=4):
+    """Two anchors that make the root box [0, 2.7]^3 and nx x ny points at x = 2.7 m / 2^21, y = 2.7 (n + 0.5) / 2^21 for consecutive m
+    and n, shuffled: t = x / 2.7 lands on or just below m / 2^21 by the last bit of the division, so (c - Rmin) * (1 / e) puts eight of
+    the forty in the neighbouring x cell; the y cells are hit in the middle under either rule. A point that changes its x cell changes
+    its place among the points of the other rows, so the order changes and not only the ties. (One row does not do: the reference
+    builder lists a row's points in x order, and an order that is sorted already hides every tie.) The anchor at the maximum has t = 1
+    exactly: s = 2^21, which only the clamp keeps inside 21 bits.
+    Kills: key: reciprocal division, key: no clamp, key: round to nearest."""
+    w, scale = np.float32(2.7), np.float32(2097152.0)
+    pts = [(m, n) for m in range(first, first + nx) for n in range(first, first + ny)]
+    pts = [pts[i] for i in np.random.default_rng(1).permutation(len(pts))]
+    return [_dot(0, 0, 0), _dot(w, w, w)] + [_dot(w * np.float32(m) / scale, w * np.float32(n + 0.5) / scale, 1.5) for m, n in pts]
+
+
+def _crowd(seed=0, n=48):
+    """Two anchors and n points inside a 4 x 4 x 4 block of key cells in the middle of the root box, at fractional positions inside the
+    cells (the first seed tried): the low bits of q on all three axes decide order, ties and topology.
+    Kills: key: round to nearest (and whatever else moves a key by one cell)."""
+    rng = np.random.default_rng(seed)
+    cell = 1.0 / 2097152.0
+    p = 0.5 + rng.uniform(0.0, 4.0, (n, 3)) * cell
+    return [_dot(0, 0, 0), _dot(1, 1, 1)] + [_dot(*np.float32(v)) for v in p]
+
+
+def _tiny():
+    """Five spheres of radius 1e-20 a few 1e-20 apart and three ordinary ones: the extents of the small pairs are about 1e-20 and their
+    products about 1e-40, below the smallest normal number — a distance computed with flushed denormals is 0 for all of them, and the
+    xor rule pairs them instead of the distance. Every plane of the small boxes is below 2^-60: the tree is `subnormal`.
+    Kills: ploc: distance flushed."""
+    s = 1e-20
+    small = [_dot(0.0, 0.0, 0.0, s), _dot(7 * s, s, 0.0, s), _dot(9 * s, 4 * s, 2 * s, s), _dot(20 * s, 2 * s, 5 * s, s), _dot(22 * s, 9 * s, s, s)]
+    return small + [_dot(1.0, 0.5, 0.25, 0.125), _dot(0.5, 1.0, 0.75, 0.25), _dot(0.25, 0.25, 1.0, 0.125)]
+
+
+def _denormals(seed=0):
+    """Eight points at whole multiples, below 16, of 2^-149 on every axis (the first seed tried): every coordinate, centre and extent is
+    a denormal. lo * 0.5 + hi * 0.5 rounds each half to even (1 gives 0, 3 gives 4), which (lo + hi) * 0.5 does not; flushed, every key
+    and every box is zero.
+    Kills: key: denormals flushed, key: centre (lo + hi) * 0.5, box: primitive boxes flushed."""
+    rng = np.random.default_rng(seed)
+    d = float(np.float32(2.0) ** -149)
+    return [_dot(*(rng.integers(0, 16, 3) * d)) for _ in range(8)]
+
+
+def _zeros():
+    """Three points at zeros of mixed signs and two spheres above them: the minimum planes of the root and of the leaves below it are
+    +0 or -0 by which of equal values the fold keeps.
+    Kills: box: fold by fminf / fmaxf, box: fold by <= / >=, box: a leaf folded in reverse."""
+    return [_dot(0.0, -0.0, 0.0), _dot(-0.0, 0.0, -0.0), _dot(0.0, 0.0, -0.0), _dot(1.0, 2.0, 3.0, 0.5), _dot(3.0, 1.0, 2.0, 0.25)]
+
+
+def _zeros_update(prims):
+    """The first point with +0 at x moves onto -0 and back."""
+    k = next(i for i, (t, d) in enumerate(prims) if t == SPHERE and d[3] == 0 and not np.signbit(d[0]))
+    there, back = prims[k][1].copy(), prims[k][1].copy()
+    there[0] = -0.0
+    return [(np.array([k], np.uint32), there[None]), (np.array([k], np.uint32), back[None])]
+
+
+def _cone_zero():
+    """A cone whose two ends reach x = 0 and z = 0 from different sides of zero: c1 - r1 = +0 and c2 - r2 = -0 (an apex, r2 = 0, at
+    -0), equal values of which std::min(a, b) keeps a. Everything else lies above.
+    Kills: box: the cone's min / max swapped."""
+    return [(CONE, [1.0, 2.0, 1.0, -0.0, 4.0, -0.0, 1.0, 0.0]), _dot(2.0, 3.0, 2.0, 0.5), _dot(3.0, 1.0, 3.0, 0.25), _dot(1.5, 4.0, 1.5, 0.5)]
+
+
+def _lattice():
+    """27 equal spheres on a 3 x 3 x 3 lattice of pitch 0.37, jittered by 2e-7: the distances of neighbouring pairs agree to the last
+    bits, and which is smallest depends on the rounding of every product and sum.
+    Kills: ploc: distance contracted, ploc: distance associated the other way."""
+    rng = np.random.default_rng(0)
+    return [_dot(*(0.37 * np.array([i, j, k]) + rng.uniform(-2e-7, 2e-7, 3)), 0.1) for i in range(3) for j in range(3) for k in range(3)]
+
+
+SHARP = {
+    "rows42": _rows,
+    "crowd50": _crowd,
+    "tiny8": _tiny,
+    "denormal8": _denormals,
+    "zeros5": _zeros,
+    "cone_zero": _cone_zero,
+    "lattice27": _lattice,
+}
+SUBNORMAL = ("tiny8", "denormal8")   # the cases whose trees have planes below 2^-60: the quick boxes are withdrawn (box_slack = inf)
+# per case, what makes its update from its primitives: a list of (ordinals, payloads), one refit on top of the other
+UPDATES = {"zeros5": _zeros_update}
+
 SCENES = {
-    "n1": lambda: _some(1),                                      # the root is a leaf
+    "n1": lambda: _some(1),                                     # the root is a leaf
     "n2": lambda: _some(2),                                      # one leaf, no record
     "n3": lambda: _some(3),
     "n4": lambda: _some(4),
@@ -69,6 +161,7 @@ SCENES = {
     "scene_d": lambda: S.scene_d(24, 24),
     "mesh20k": _mesh_20k,
 }
+SCENES.update(SHARP)
 SMALL = [n for n in SCENES if n != "mesh20k"]
 
 
@@ -83,6 +176,17 @@ def case(name):
     for a in (tree, built, new_to_old):
         a.setflags(write=False)
     return dict(descs=descs, tree=tree, prims=prims, built=built, new_to_old=new_to_old)
+
+
+@functools.lru_cache(maxsize=None)
+def updates(name):
+    """The case's update of its reference-built tree, a list of (ordinals, payloads) applied one after the other: its own where
+    UPDATES has one, else three tenths of its primitives moved by up to 0.3."""
+    from tests import refit_ref as RR
+    c = case(name)
+    if name in UPDATES:
+        return UPDATES[name](c["prims"])
+    return [RR.random_update(c["tree"], np.random.default_rng(5), 0.3, 0.3)]
 
 
 # ---- the cost measure and the drift track -------------------------------------------------------------------------------------------

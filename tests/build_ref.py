@@ -74,6 +74,17 @@ def delta(K, i, j):
     return 64 + 32 - (i ^ j).bit_length()
 
 
+def leaf_keys(keys, order):
+    """K_j: the key of leaf j's first primitive."""
+    return [keys[order[2 * j]] for j in range((len(order) + 1) // 2)]
+
+
+def split(K, a, b):
+    """The largest g in [a, b) with delta(a, g) > delta(a, b)."""
+    d_ab = delta(K, a, b)
+    return max(g for g in range(a, b) if delta(K, a, g) > d_ab)
+
+
 def build(prims):
     n = len(prims)
     assert n >= 1 and all(0 <= t <= 3 for t, _ in prims)
@@ -82,7 +93,7 @@ def build(prims):
     keys = keys_of(lo, hi, rlo, rhi)
     order = sorted(range(n), key=lambda i: (keys[i], i))
     m = (n + 1) // 2
-    K = [keys[order[2 * j]] for j in range(m)]
+    K = leaf_keys(keys, order)
     quads = []
 
     def node(box_lo, box_hi, flags, parent):
@@ -99,17 +110,14 @@ def build(prims):
         """Lays the subtree over leaves [a, b] out at the end of `quads`; returns its box."""
         if a == b:
             members = order[2 * a:2 * a + 2]
-            blo, bhi = np.full(3, RR.START_LO, F), np.full(3, RR.START_HI, F)
-            for i in members:
-                blo, bhi = RR.fold(blo, bhi, lo[i], hi[i])
+            blo, bhi = RR.leaf_box([(lo[i], hi[i]) for i in members])
             node(blo, bhi, CR.LEAF | flags | len(members), parent)
             for i in members:
                 t, d = prims[i]
                 quads.append(np.array([t, 0, 0, 0], np.uint32).view(F).tolist())
                 quads.extend(np.asarray(d, F)[:4 * (t + 1)].reshape(-1, 4).tolist())
             return blo, bhi
-        d_ab = delta(K, a, b)
-        g = max(g for g in range(a, b) if delta(K, a, g) > d_ab)
+        g = split(K, a, b)
         at = node((0, 0, 0), (0, 0, 0), flags, parent)
         patch(at, 1, at + 3)
         llo, lhi = emit(a, g, at, CR.IS_LOWER)

@@ -9,7 +9,7 @@ from tests import build_cases as BC
 from tests import ploc_ref as PR
 from tests.test_ray_queries import tree_prims
 
-SCENES = dict(BC.SCENES)
+SCENES = {n: f for n, f in BC.SCENES.items() if n not in BC.SHARP}
 SCENES.update({
     # every key ties and d(i, j) is the larger sphere's area: one merge per iteration, 39 iterations, a chain of 39 levels in which every
     # interior node has a leaf of one
@@ -17,6 +17,7 @@ SCENES.update({
     "n17": lambda: BC._some(17),              # 2 r + 1: the window is clipped at both ends at once
     "tris513": lambda: BC._triangles(513, 6),  # mutual pairs across two workgroup boundaries of the nearest kernel
 })
+SCENES.update(BC.SHARP)                        # behind the others: the device tests number their cases
 # 1 099 iterations: beyond the cap, refused (no tree)
 REFUSED = {"chain1100": lambda: [(BC.SPHERE, [0.0, 0.0, 0.0, 1.0 + k / 1024.0]) for k in range(1100)]}
 SMALL = [n for n in SCENES if n != "mesh20k"]

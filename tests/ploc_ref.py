@@ -59,6 +59,16 @@ def _nearest(lo, hi, radius):
     return nn
 
 
+def _slot(lower, upper):
+    """The slots the merged clusters take: the lower partners'."""
+    return lower
+
+
+def _pair(a, b):
+    """The node over clusters a (lower) and b (upper)."""
+    return ("pair", a, b)
+
+
 def build(prims, radius=RADIUS, info=None):
     n = len(prims)
     assert n >= 1 and radius >= 1 and all(0 <= t <= 3 for t, _ in prims)
@@ -80,14 +90,15 @@ def build(prims, radius=RADIUS, info=None):
         mutual = nn[nn] == pos
         lower = np.nonzero(mutual & (pos < nn))[0]
         assert len(lower) >= 1
-        keep = ~(mutual & (pos > nn))
-        for i in lower:
-            j = int(nn[i])
-            node[i] = ("pair", node[i], node[j])
         upper = nn[lower]
+        into = _slot(lower, upper)
+        keep = np.ones(c, bool)
+        keep[lower + upper - into] = False
+        for i, j, s in zip(lower, upper, into):
+            node[s] = _pair(node[i], node[j])
         with np.errstate(all="ignore"):
-            lo[lower], hi[lower] = RR.fold(lo[lower], hi[lower], lo[upper], hi[upper])
-        count[lower] += count[upper]
+            lo[into], hi[into] = RR.fold(lo[lower], hi[lower], lo[upper], hi[upper])
+        count[into] = count[lower] + count[upper]
         node = [node[i] for i in np.nonzero(keep)[0]]
         lo, hi, count = lo[keep], hi[keep], count[keep]
 
@@ -111,9 +122,7 @@ def build(prims, radius=RADIUS, info=None):
         depths[0] = max(depths[0], level)
         if is_leaf(nd):
             members = [nd[1]] if nd[0] == "prim" else [nd[1][1], nd[2][1]]
-            blo, bhi = np.full(3, RR.START_LO, F), np.full(3, RR.START_HI, F)
-            for o in members:
-                blo, bhi = RR.fold(blo, bhi, plo[o], phi[o])
+            blo, bhi = RR.leaf_box([(plo[o], phi[o]) for o in members])
             header(blo, bhi, CR.LEAF | flags | len(members), parent)
             tris = all(prims[o][0] == 2 for o in members)
             ref = REF_LEAF | len(new_to_old) | (REF_TRIS if tris else REF_SMALL) | (REF_TWO if len(members) == 2 else 0)

@@ -43,6 +43,14 @@ def fold(lo, hi, clo, chi):
     return np.where(clo < lo, clo, lo), np.where(chi > hi, chi, hi)
 
 
+def leaf_box(boxes):
+    """A leaf's box: its primitives' boxes, (lo, hi) each, folded in leaf order."""
+    lo, hi = np.full(3, START_LO, F), np.full(3, START_HI, F)
+    for a, b in boxes:
+        lo, hi = fold(lo, hi, a, b)
+    return lo, hi
+
+
 def refit(quads, ordinals=(), payloads=()):
     q = np.array(quads, F).reshape(-1, 4).copy()
     lay = CR.layout(q)
@@ -65,11 +73,13 @@ def refit(quads, ordinals=(), payloads=()):
         for i in range(n - 1, -1, -1):
             lo, hi = np.full(3, START_LO, F), np.full(3, START_HI, F)
             if leaf[i]:
+                boxes = []
                 for k in members[i]:
                     a, t = int(p_addr[k]), int(p_type[k])
                     d = np.zeros(PAYLOAD, F)
                     d[:4 * (t + 1)] = q[a + 1:a + 2 + t].reshape(-1)
-                    lo, hi = fold(lo, hi, *prim_box(t, d))
+                    boxes.append(prim_box(t, d))
+                lo, hi = leaf_box(boxes)
             else:
                 for c in kids[i]:
                     lo, hi = fold(lo, hi, lo_[c], hi_[c])

@@ -89,13 +89,13 @@ def test_device_arrays_equal_the_restatement(be, B, k, name):
     assert (perm == c["new_to_old"]).all(), name
     cv = assert_arrays(be, c["built"], name)
     assert out["n_recs"] == len(cv["recs"]) == (len(c["prims"]) + 1) // 2 - 1 and out["root_ref"] == cv["root_ref"] and out["max_depth"] == cv["max_depth"]
-    assert same_bits(out["root_min"], cv["root_min"]) and same_bits(out["root_max"], cv["root_max"]) and not out["subnormal"]
+    assert same_bits(out["root_min"], cv["root_min"]) and same_bits(out["root_max"], cv["root_max"]) and out["subnormal"] == cv["subnormal"] == (name in BC.SUBNORMAL)
     lay = CR.layout(c["built"])
     inner = ~lay["leaf"]
     assert out["levels"] == (int(lay["depth"][inner].max()) + 1 if inner.any() else 0)
     now = be.scene_device()
     assert now.generation == before.generation + 1 and now.n_prims == before.n_prims and now.exact_boxes == 0
-    assert now.box_slack == B.tree_slack(c["built"])[0] and be.scene_order() == 1
+    assert now.box_slack == B.tree_slack(c["built"])[0] and be.scene_order() == 1 and (now.box_slack == np.inf) == cv["subnormal"]
     assert be.tree_cost() == pytest.approx(BC.cost_of(c["built"])[0], rel=max(1, len(cv["recs"])) * 2.0 ** -52, abs=0)
 
 

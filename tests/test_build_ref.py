@@ -68,9 +68,9 @@ def test_a_built_tree_has_the_contracts_shape(name):
     now = tree_prims(c["built"])
     assert all(now[p][0] == c["prims"][o][0] and same_bytes(now[p][1], c["prims"][o][1]) for p, o in enumerate(perm))
     cv = CR.convert(c["built"])
-    assert not cv["irregular"] and not cv["disorderly"] and not cv["subnormal"]
+    assert not cv["irregular"] and not cv["disorderly"] and cv["subnormal"] == (name in BC.SUBNORMAL)
     tc = B.tree_class(c["built"])   # ... and the uploader's own verdict
-    assert not tc["irregular"] and not tc["disorderly"]
+    assert not tc["irregular"] and not tc["disorderly"] and B.tree_slack(c["built"])[1] == cv["subnormal"]
     assert same_bytes(c["built"][0:2, :3], np.stack(BR.root_box(lo, hi)))
 
 

@@ -53,10 +53,10 @@ def test_device_arrays_equal_the_restatement(be, B, k, name):
     print("%s: %d primitives, %d records, depth %d, %d iterations" % (name, n, out["n_recs"], out["max_depth"], out["iterations"]))
     assert out["n_recs"] == len(cv["recs"]) == info["n_recs"] and out["root_ref"] == cv["root_ref"] and out["max_depth"] == cv["max_depth"] == info["depth"]
     assert out["iterations"] == info["iterations"] and len(out["step_ms"]) == 6
-    assert same_bits(out["root_min"], cv["root_min"]) and same_bits(out["root_max"], cv["root_max"]) and not out["subnormal"]
+    assert same_bits(out["root_min"], cv["root_min"]) and same_bits(out["root_max"], cv["root_max"]) and out["subnormal"] == cv["subnormal"] == (name in BC.SUBNORMAL)
     now = be.scene_device()
     assert now.generation == before.generation + 1 and now.n_prims == before.n_prims and now.exact_boxes == 0
-    assert now.box_slack == B.tree_slack(c["built"])[0] and be.scene_order() == 1
+    assert now.box_slack == B.tree_slack(c["built"])[0] and be.scene_order() == 1 and (now.box_slack == np.inf) == cv["subnormal"]
     # the bound of an fp64 sum of n_recs positive terms in any order
     assert be.tree_cost() == pytest.approx(BC.cost_of(c["built"])[0] if info["n_recs"] else 0.0, rel=max(1, info["n_recs"]) * 2.0 ** -52, abs=0)
 

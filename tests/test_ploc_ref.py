@@ -43,7 +43,7 @@ def test_a_clustered_tree_has_the_contracts_shape(name):
     now = tree_prims(c["built"])
     assert all(now[p][0] == c["prims"][o][0] and same_bytes(now[p][1], c["prims"][o][1]) for p, o in enumerate(c["new_to_old"]))
     cv = CR.convert(c["built"])
-    assert not cv["irregular"] and not cv["disorderly"] and not cv["subnormal"]
+    assert not cv["irregular"] and not cv["disorderly"] and cv["subnormal"] == (name in BC.SUBNORMAL) == B.tree_slack(c["built"])[1]
     assert cv["max_depth"] == info["depth"] and len(cv["recs"]) == info["n_recs"] and cv["root_ref"] == info["root_ref"]
     assert (cv["recs"].view(np.uint32)[:, :2, 3].reshape(-1) == info["refs"]).all()
     tc = B.tree_class(c["built"])   # ... and the uploader's own verdict

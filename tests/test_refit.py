@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from gpuart_amd import synth_scenes as S
+from tests import build_cases as BC
 from tests import converter_ref as CR
 from tests import refit_ref as RR
 from tests.test_kernel_variants import _one_each, scene_setup, to_params, tree_of as variant_tree
@@ -56,6 +57,7 @@ SCENES = {
     "scene_p_min5": (S.scene_p, dict(min_prims=5)),           # leaves of more than two primitives
     "deep_chain": (_deep_chain, {}),                          # a level per node, beyond the LDS ring
 }
+SCENES.update({name: (f, {}) for name, f in BC.SHARP.items()})   # signed zeros, denormals, ties of the last bit: tests/build_cases.py says why
 
 
 @functools.lru_cache(maxsize=None)
@@ -128,8 +130,17 @@ def test_device_arrays_equal_the_restatement(be, B, name):
         lay = CR.layout(cur)
         inner = ~lay["leaf"]
         assert out["levels"] == (int(lay["depth"][inner].max()) + 1 if inner.any() else 0)
-        assert same_bits(out["root_min"], cur[0, :3]) and same_bits(out["root_max"], cur[1, :3]) and not out["subnormal"]
+        assert same_bits(out["root_min"], cur[0, :3]) and same_bits(out["root_max"], cur[1, :3]) and out["subnormal"] == CR.convert(cur)["subnormal"]
     assert not same_bits(device_arrays(be)[1], uploaded[1])
+    if name in BC.SHARP:   # ... and the case's own update (tests/build_cases.updates), on the tree as uploaded
+        be.upload_bvh(tree)
+        cur = tree
+        for k, (ordinals, payloads) in enumerate(BC.updates(name)):
+            out = refit(be, ordinals, payloads, device=k % 2 == 0)
+            cur = RR.refit(cur, ordinals, payloads)
+            assert_arrays(be, cur, "%s, its own update, step %d" % (name, k))
+            sub = CR.convert(cur)["subnormal"]
+            assert out["subnormal"] == sub and (be.scene_device().box_slack == np.inf) == sub
 
 
 @pytest.mark.parametrize("device", [False, True])
