@@ -74,6 +74,13 @@ class PlocResult(C.Structure):
                 ("root_min", C.c_float * 3), ("root_max", C.c_float * 3)]
 
 
+class EditResult(C.Structure):
+    """gpuart_edit_result (include/gpuart_edit.h)."""
+    _fields_ = [("status", C.c_int32), ("first_bad", C.c_uint32), ("n_prims", C.c_uint64), ("type_mask", C.c_uint32),
+                ("root_min", C.c_float * 3), ("root_max", C.c_float * 3)]
+
+
+EDIT_STEPS = ("validate", "scan", "move", "reduce")  # gpuart_edit_step_ms
 REFIT_PAYLOAD = 16  # GPUART_REFIT_PAYLOAD
 PLOC_STEPS = ("keys", "sort", "iterations", "number", "emit", "permute")  # gpuart_ploc_step_ms
 TREE_MODES = {"morton": 0, "clustered": 1}  # Renderer::TreeMode
@@ -392,6 +399,12 @@ def ploc_lib():
     return _image_lib("ploc")
 
 
+def edit_lib():
+    """libgpuart_edit.so (include/gpuart_edit.h), built by the image libraries' rule; raises NativeLibraryMissing if it has not been built
+    (no fallback)."""
+    return _image_lib("edit")
+
+
 def display_lib():
     """libgpuart_display.so; raises NativeLibraryMissing if it has not been built (no fallback)."""
     return _image_lib("display")
@@ -489,6 +502,36 @@ def adopt_tree(quads, order, refs):
     res = np.ctypeslib.as_array(out, shape=(nout.value, 4)).copy()
     L.gpuart_free(out)
     return res
+
+
+def edit_tree(quads, remove, add_types, add_payload, order=None, refs=None):
+    """gpuart_edit_tree: BoundingVolumesHierarchy::EditPrimitives on the compiled tree `quads`, without a device, followed by the Morton
+    rebuild (refs None; `order` None or the permutation to check) or by AdoptTopology of `order` and `refs` -> (quads', new_to_old of
+    the edited list). ValueError for a malformed tree (-1), a refused edit (-2; `first_bad`: the first offender, the removals counted
+    first, or None) or a refused order or topology (-3)."""
+    L = host_lib()
+    q = np.ascontiguousarray(quads, np.float32).reshape(-1)
+    rem = np.ascontiguousarray(remove, np.uint32).reshape(-1)
+    typ = np.ascontiguousarray(add_types, np.uint32).reshape(-1)
+    pay = np.ascontiguousarray(add_payload, np.float32).reshape(-1)
+    if pay.size != 16 * typ.size:
+        raise ValueError("edit_tree: add_payload must hold 16 floats per added primitive")
+    o = None if order is None else np.ascontiguousarray(order, np.uint32).reshape(-1)
+    r = None if refs is None else np.ascontiguousarray(refs, np.uint32).reshape(-1)
+    ptr = lambda a: _p(a) if a is not None and a.size else None
+    out = C.POINTER(C.c_float)()
+    nout, bad = C.c_size_t(0), C.c_size_t(0)
+    perm = np.zeros(q.size // 8 + typ.size + 1, np.uint32)   # (a primitive takes at least two quads)
+    rc = L.gpuart_edit_tree(_p(q), C.c_size_t(q.size // 4), ptr(rem), C.c_size_t(rem.size), ptr(typ), ptr(pay), C.c_size_t(typ.size),
+                            C.c_int(0 if r is None else 1), ptr(o), ptr(r), C.c_size_t(0 if r is None else r.size // 2), C.byref(out), C.byref(nout),
+                            _p(perm), C.byref(bad))
+    if rc != 0:
+        e = ValueError("gpuart_edit_tree: %d" % rc)
+        e.first_bad = int(bad.value) if rc == -2 and bad.value != C.c_size_t(-1).value else None
+        raise e
+    res = np.ctypeslib.as_array(out, shape=(nout.value, 4)).copy()
+    L.gpuart_free(out)
+    return res, perm[:sum(1 for _ in _leaf_prims(res))].copy()
 
 
 def _leaf_prims(quads):
@@ -786,7 +829,7 @@ class Backend:
             raise e
 
     def close(self):
-        for handle in (getattr(self, "_refit", None), getattr(self, "_build", None), getattr(self, "_ploc", None)):
+        for handle in (getattr(self, "_refit", None), getattr(self, "_build", None), getattr(self, "_ploc", None), getattr(self, "_edit", None)):
             if handle is not None:
                 handle.close()
         if self.owned and self.ctx:
@@ -884,6 +927,28 @@ class Backend:
             self._build = _BuildHandle(self.device)
         return self._build
 
+    def _builder(self, clustered):
+        """(handle, an empty result, run, run_host, step_ms, the steps' names) of the clustered or the Morton build."""
+        if clustered:
+            if getattr(self, "_ploc", None) is None:
+                self._ploc = _PlocHandle(self.device)
+            Bd = ploc_lib()
+            return self._ploc, PlocResult(), Bd.gpuart_ploc_run, Bd.gpuart_ploc_run_host, Bd.gpuart_ploc_step_ms, PLOC_STEPS
+        Bd = build_lib()
+        return self._build_handle(), BuildResult(), Bd.gpuart_build_run, Bd.gpuart_build_run_host, Bd.gpuart_build_step_ms, BUILD_STEPS
+
+    def _build_report(self, h, res, step_ms, steps, clustered):
+        ms = (C.c_double * len(steps))()
+        h._chk(step_ms(h, ms))
+        report = dict(n_recs=int(res.n_recs), root_ref=int(res.root_ref), max_depth=int(res.max_depth), subnormal=bool(res.subnormal),
+                      root_min=np.array(res.root_min[:], np.float32), root_max=np.array(res.root_max[:], np.float32),
+                      step_ms=dict(zip(steps, [float(v) for v in ms])))
+        if clustered:
+            report["iterations"] = int(res.iterations)
+        else:
+            report["levels"] = int(res.levels)
+        return report
+
     def rebuild(self, out=None, mode="morton"):
         """Rebuilds the uploaded scene's tree on the device and has the context adopt it — `mode` "morton": in Morton order
         (include/gpuart_build.h), fast to build; "clustered": by locally-ordered clustering (include/gpuart_ploc.h), a tree of lower cost
@@ -897,14 +962,7 @@ class Backend:
         if mode not in TREE_MODES:
             raise ValueError("rebuild: mode must be one of %s" % sorted(TREE_MODES))
         clustered = mode == "clustered"
-        if clustered:
-            if getattr(self, "_ploc", None) is None:
-                self._ploc = _PlocHandle(self.device)
-            Bd, h, res = ploc_lib(), self._ploc, PlocResult()
-            run, run_host, step_ms, steps = Bd.gpuart_ploc_run, Bd.gpuart_ploc_run_host, Bd.gpuart_ploc_step_ms, PLOC_STEPS
-        else:
-            Bd, h, res = build_lib(), self._build_handle(), BuildResult()
-            run, run_host, step_ms, steps = Bd.gpuart_build_run, Bd.gpuart_build_run_host, Bd.gpuart_build_step_ms, BUILD_STEPS
+        h, res, run, run_host, step_ms, steps = self._builder(clustered)
         scene = self.scene_device()
         n = int(scene.n_prims)
         spare = self.scene_reserve((n - 1 if clustered else (n + 1) // 2 - 1) if n else 0)
@@ -925,16 +983,109 @@ class Backend:
         spare.root_min, spare.root_max = res.root_min, res.root_max
         spare.box_slack = float("inf") if res.subnormal else 0.0
         self.scene_rebuilt(spare)
-        ms = (C.c_double * len(steps))()
-        h._chk(step_ms(h, ms))
-        self.last_rebuild = dict(n_recs=int(res.n_recs), root_ref=int(res.root_ref), max_depth=int(res.max_depth), subnormal=bool(res.subnormal),
-                                 root_min=np.array(res.root_min[:], np.float32), root_max=np.array(res.root_max[:], np.float32),
-                                 step_ms=dict(zip(steps, [float(v) for v in ms])))
-        if clustered:
-            self.last_rebuild["iterations"] = int(res.iterations)
-        else:
-            self.last_rebuild["levels"] = int(res.levels)
+        self.last_rebuild = self._build_report(h, res, step_ms, steps, clustered)
         return perm
+
+    # an edit on the device (include/gpuart_edit.h)
+    def scene_reserve_prims(self, n_recs, n_prims):
+        """gpuart_hip_scene_reserve_prims: the context's spare arrays, with room for n_recs records and n_prims primitives, as a HipScene."""
+        s = HipScene()
+        self._chk(self.L.gpuart_hip_scene_reserve_prims(self.ctx, C.c_uint64(n_recs), C.c_uint64(n_prims), C.byref(s)))
+        return s
+
+    def scene_replaced(self, built, type_mask):
+        self._chk(self.L.gpuart_hip_scene_replaced(self.ctx, C.byref(built), C.c_uint32(type_mask)))
+
+    def _edit_handle(self):
+        if getattr(self, "_edit", None) is None:
+            self._edit = _EditHandle(self.device)
+        return self._edit
+
+    def edit(self, remove, add_types, add_payload, mode="clustered", out=None):
+        """Removes the primitives `remove` (strictly ascending device ordinals) from the uploaded scene, appends primitives of the types
+        `add_types` (0..3) with the data quads `add_payload` (n x 16 floats, zero-padded as for refit), builds the tree of the result on
+        the device — `mode` as for rebuild — and has the context adopt it (include/gpuart_edit.h). The three arguments are contiguous
+        tensors on this device (int32, int32, float32: nothing crosses the host) or anything NumPy converts. Returns the composed map,
+        int32: per new device ordinal the old ordinal of a survivor, or n_old + k for the k-th addition — under rebuild's `out` rules (a
+        tensor on the device when torch is in use, else a NumPy array; a tensor of n_new entries is written in place; True / False
+        choose). `last_edit` keeps dict(n_prims, type_mask, root_min, root_max, step_ms, rebuild: what last_rebuild would hold). A
+        refusal raises HipError with code -1 (ERR_ARG), `first_bad` where a removal (index i) or an addition (n_remove + k) is at
+        fault, and nothing changed."""
+        if mode not in TREE_MODES:
+            raise ValueError("edit: mode must be one of %s" % sorted(TREE_MODES))
+        clustered = mode == "clustered"
+        E, h = edit_lib(), self._edit_handle()
+        scene = self.scene_device()
+        n_old = int(scene.n_prims)
+        edited, res = HipScene(), EditResult()
+        on_device = hasattr(remove, "data_ptr")
+        if on_device:
+            import torch
+            ok = all(hasattr(t, "data_ptr") and t.is_cuda and t.is_contiguous() for t in (remove, add_types, add_payload))
+            if not (ok and remove.dtype == torch.int32 and add_types.dtype == torch.int32 and add_payload.dtype == torch.float32 and
+                    add_payload.numel() == 16 * add_types.numel()):
+                raise ValueError("edit: remove (int32), add_types (int32) and add_payload (float32, n x 16) must all be contiguous tensors on the device")
+            n_remove, n_add = remove.numel(), add_types.numel()
+            n_new = n_old - n_remove + n_add
+            source = torch.empty((max(n_new, 1),), dtype=torch.int32, device="cuda:%d" % self.device)
+            torch.cuda.synchronize(source.device)   # (the handle's stream is its own: what wrote the tensors must be complete)
+            ptr = lambda t: C.c_void_p(t.data_ptr() if t.numel() else None)
+            rc = E.gpuart_edit_run(h, C.byref(scene), ptr(remove), C.c_size_t(n_remove), ptr(add_types), ptr(add_payload), C.c_size_t(n_add),
+                                   C.c_void_p(source.data_ptr()), C.byref(edited), C.byref(res))
+        else:
+            r = np.ascontiguousarray(remove, np.uint32).reshape(-1)
+            t = np.ascontiguousarray(add_types, np.uint32).reshape(-1)
+            p = np.ascontiguousarray(add_payload, np.float32).reshape(-1)
+            if p.size != 16 * t.size:
+                raise ValueError("edit: add_payload must hold 16 floats per added primitive")
+            n_remove, n_add = r.size, t.size
+            n_new = n_old - n_remove + n_add
+            source = np.zeros(max(n_new, 1), np.int32)
+            rc = E.gpuart_edit_run_host(h, C.byref(scene), _p(r), C.c_size_t(n_remove), _p(t), _p(p), C.c_size_t(n_add), _p(source), C.byref(edited),
+                                        C.byref(res))
+        h._chk(rc, res)
+        bh, bres, run, run_host, step_ms, steps = self._builder(clustered)
+        spare = self.scene_reserve_prims(n_new - 1 if clustered else (n_new + 1) // 2 - 1, n_new)
+        if on_device:
+            perm = torch.empty((n_new,), dtype=torch.int32, device=source.device)
+            torch.cuda.synchronize(source.device)
+            bh._chk(run(bh, C.byref(edited), C.byref(spare), C.c_void_p(perm.data_ptr()), C.byref(bres)))
+            composed = torch.empty((n_new,), dtype=torch.int32, device=source.device) if out is None or isinstance(out, bool) else out
+            if not (hasattr(composed, "data_ptr") and composed.is_cuda and composed.is_contiguous() and composed.dtype == torch.int32 and composed.numel() == n_new):
+                raise ValueError("edit: out must be a contiguous int32 tensor of n_new entries on the device")
+            torch.cuda.synchronize(source.device)
+            h._chk(E.gpuart_edit_compose(h, C.c_void_p(source.data_ptr()), C.c_void_p(perm.data_ptr()), C.c_size_t(n_new), C.c_void_p(composed.data_ptr())))
+            if out is False:
+                composed = composed.cpu().numpy()
+        else:
+            perm = np.zeros(n_new, np.uint32)
+            bh._chk(run_host(bh, C.byref(edited), C.byref(spare), _p(perm), C.byref(bres)))
+            composed = source[:n_new][perm]
+            if out is None:
+                out = "torch" in sys.modules
+            if out is not False:
+                import torch
+                dev = torch.from_numpy(composed).to("cuda:%d" % self.device)
+                if out is True:
+                    composed = dev
+                else:
+                    if not (hasattr(out, "data_ptr") and out.is_cuda and out.is_contiguous() and out.dtype == torch.int32 and out.numel() == n_new):
+                        raise ValueError("edit: out must be a contiguous int32 tensor of n_new entries on the device")
+                    out.copy_(dev)
+                    torch.cuda.synchronize(out.device)
+                    composed = out
+        spare.n_prims = n_new
+        spare.n_recs, spare.root_ref, spare.max_depth = bres.n_recs, bres.root_ref, bres.max_depth
+        spare.root_min, spare.root_max = bres.root_min, bres.root_max
+        spare.box_slack = float("inf") if bres.subnormal else 0.0
+        self.scene_replaced(spare, int(res.type_mask))
+        ms = (C.c_double * len(EDIT_STEPS))()
+        h._chk(E.gpuart_edit_step_ms(h, ms))
+        self.last_rebuild = self._build_report(bh, bres, step_ms, steps, clustered)
+        self.last_edit = dict(n_prims=int(res.n_prims), type_mask=int(res.type_mask), root_min=np.array(res.root_min[:], np.float32),
+                              root_max=np.array(res.root_max[:], np.float32), step_ms=dict(zip(EDIT_STEPS, [float(v) for v in ms])),
+                              rebuild=self.last_rebuild)
+        return composed
 
     def tree_cost(self):
         """gpuart_build_cost of the uploaded scene's tree: the sum over its records of both children's half-areas over the root's."""
@@ -1326,6 +1477,24 @@ class Renderer:
             raise ValueError("rebuild_tree: mode must be one of %s" % sorted(TREE_MODES))
         return perm if self.L.gpuart_renderer_rebuild_tree_mode(self.h, C.c_int(TREE_MODES[mode]), _p(perm)) else None
 
+    def edit_primitives(self, remove, descs, mode="clustered"):
+        """Renderer::EditPrimitives: the descriptions `remove` — distinct indices, numbered as for update_primitives — leave the scene,
+        `descs` (any types) join it and the tree is built on the device in `mode`, the temporal history kept. Afterwards the caller's
+        descriptions are the ones not removed, in their order, followed by `descs`: update_primitives and trace_rays number that list.
+        Returns source (per new device ordinal the old device ordinal, or n_old + k for descs[k]), or None — nothing changed — on a
+        refusal."""
+        if mode not in TREE_MODES:
+            raise ValueError("edit_primitives: mode must be one of %s" % sorted(TREE_MODES))
+        arr = descs if isinstance(descs, C.Array) else make_prims(descs)
+        idx = np.ascontiguousarray(remove, np.uint32).reshape(-1)
+        n = C.c_uint64()
+        self.L.gpuart_renderer_scene_info(self.h, None, C.byref(n), None)
+        source = np.zeros(int(n.value) + len(arr), np.uint32)
+        n_new = C.c_size_t(0)
+        ok = self.L.gpuart_renderer_edit_primitives(self.h, _p(idx), C.c_int(idx.size), arr, C.c_int(len(arr)), C.c_int(TREE_MODES[mode]), _p(source),
+                                                    C.byref(n_new))
+        return source[:n_new.value].copy() if ok else None
+
     def tree_cost(self):
         """Renderer::TreeCost, or None on failure."""
         cost = C.c_double()
@@ -1690,6 +1859,11 @@ class _BuildHandle(_ImageHandle):
 class _PlocHandle(_ImageHandle):
     """Backend.rebuild(mode="clustered")'s gpuart_ploc, made at the first of them."""
     NAME, Error = "ploc", HipError
+
+
+class _EditHandle(_RefitHandle):
+    """Backend.edit's gpuart_edit, made at the first edit; a refused edit's error carries `first_bad` as a refused refit's does."""
+    NAME, Error = "edit", HipError
 
 
 def _gbuffer_args(device, rgba, hits, prims, out):

@@ -183,6 +183,7 @@ struct gpuart_hip_ctx {
     float4 *d_spare_recs = nullptr, *d_spare_prims = nullptr;
     float *d_spare_boxes = nullptr;
     uint64_t spare_recs = 0, spare_prims = 0;  ///< what the spare set holds room for
+    uint64_t prims_room = 0;  ///< primitives and boxes the scene's own arrays hold room for: n_prims after an upload, more after an edit that shrank the scene
     float4 *d_direct = nullptr, *d_accum = nullptr;
     unsigned long long *d_counters = nullptr;
     /// Tile size, run lengths, lanes in use, execution mode (gpuart_hip_set_mode: 0 fast — launch pipeline, or k_run for a small
@@ -693,6 +694,7 @@ int gpuart_hip_upload_bvh(gpuart_hip_ctx *c, const float *quads, size_t nquads) 
     c->type_mask = cv.type_mask;
     c->n_nodes = cv.num_nodes;
     c->n_prims = cv.prims.size() / 3;
+    c->prims_room = c->n_prims;
     c->ref_order = (!c->exact_boxes && c->n_prims < c->nearest_min_prims) ? 1u : 0u;
     c->max_depth = cv.max_depth;
     c->scene_bytes = cv.recs.size() * 16 + cv.prims.size() * 16;
@@ -1299,16 +1301,19 @@ int gpuart_hip_scene_refitted(gpuart_hip_ctx *c, const float root_min[3], const 
     return 0;
 }
 
-// ---- a rebuild on the device (include/gpuart_build.h): host code only ------------------------------------------------------------
-int gpuart_hip_scene_reserve(gpuart_hip_ctx *c, uint64_t n_recs, gpuart_hip_scene *out) {
-    if (!c || !out) return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_reserve: bad argument");
+// ---- a rebuild on the device (include/gpuart_build.h) and an edit (include/gpuart_edit.h): host code only ----------------------------
+/// The spare set with room for n_recs records and n_prims primitives and boxes. `exact`: a set whose primitive room is not n_prims is
+/// made anew (gpuart_hip_scene_reserve: the builders are told the room as the count to expect); else one that is large enough is reused.
+static int reserve_spare(gpuart_hip_ctx *c, uint64_t n_recs, uint64_t n_prims, bool exact, gpuart_hip_scene *out, const char *name) {
+    if (!c || !out) return fail(GPUART_HIP_ERR_ARG, std::string(name) + ": bad argument");
     if (!c->have_scene) return fail(GPUART_HIP_ERR_ARG, "no scene uploaded");
-    if (n_recs > 0x03fffff0u) return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_reserve: too many records");
+    if (n_recs > 0x03fffff0u) return fail(GPUART_HIP_ERR_ARG, std::string(name) + ": too many records");
+    if (!exact && (n_prims < 1 || n_prims >= 0x05555540u)) return fail(GPUART_HIP_ERR_ARG, std::string(name) + ": the primitive count is 0 or beyond the uploader's bound");
     HIP_TRY(hipSetDevice(c->device));
-    if (!c->d_spare_prims || c->spare_recs < n_recs || c->spare_prims != c->n_prims) {
+    if (!c->d_spare_prims || c->spare_recs < n_recs || (exact ? c->spare_prims != n_prims : c->spare_prims < n_prims)) {
         drop_spare(c);
         // (the same slack past the end as an upload's arrays, and like theirs zeroed)
-        const size_t rb = ((size_t)n_recs * 4 + 4) * sizeof(float4), pb = ((size_t)c->n_prims * 3 + 4) * sizeof(float4), bb = (size_t)c->n_prims * 24 + 16;
+        const size_t rb = ((size_t)n_recs * 4 + 4) * sizeof(float4), pb = ((size_t)n_prims * 3 + 4) * sizeof(float4), bb = (size_t)n_prims * 24 + 16;
         HIP_TRY(hipMalloc(&c->d_spare_recs, rb));
         HIP_TRY(hipMalloc(&c->d_spare_prims, pb));
         HIP_TRY(hipMalloc(&c->d_spare_boxes, bb));
@@ -1316,11 +1321,16 @@ int gpuart_hip_scene_reserve(gpuart_hip_ctx *c, uint64_t n_recs, gpuart_hip_scen
         HIP_TRY(hipMemset(c->d_spare_prims, 0, pb));
         HIP_TRY(hipMemset(c->d_spare_boxes, 0, bb));
         c->spare_recs = n_recs;
-        c->spare_prims = c->n_prims;
+        c->spare_prims = n_prims;
     } else {
         // a reused set (after a rebuild: the scene's former arrays) still holds the records of the tree it was; beyond the n_recs
-        // about to be written it is zeroed again, so the arrays of a rebuilt scene end as an upload's do
+        // about to be written it is zeroed again, so the arrays of a rebuilt scene end as an upload's do — and so is what lies behind
+        // the n_prims primitives and boxes about to be written, where the set has room for more
         HIP_TRY(hipMemset((char *)c->d_spare_recs + (size_t)n_recs * 64, 0, (size_t)(c->spare_recs - n_recs) * 64 + 4 * sizeof(float4)));
+        if (c->spare_prims > n_prims) {
+            HIP_TRY(hipMemset((char *)c->d_spare_prims + (size_t)n_prims * 48, 0, (size_t)(c->spare_prims - n_prims) * 48 + 4 * sizeof(float4)));
+            HIP_TRY(hipMemset((char *)c->d_spare_boxes + (size_t)n_prims * 24, 0, (size_t)(c->spare_prims - n_prims) * 24 + 16));
+        }
     }
     memset(out, 0, sizeof *out);
     out->layout = 1;
@@ -1331,20 +1341,32 @@ int gpuart_hip_scene_reserve(gpuart_hip_ctx *c, uint64_t n_recs, gpuart_hip_scen
     return 0;
 }
 
-int gpuart_hip_scene_rebuilt(gpuart_hip_ctx *c, const gpuart_hip_scene *b) {
-    if (!c || !b) return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_rebuilt: bad argument");
+int gpuart_hip_scene_reserve(gpuart_hip_ctx *c, uint64_t n_recs, gpuart_hip_scene *out) {
+    return reserve_spare(c, n_recs, c ? c->n_prims : 0, true, out, "gpuart_hip_scene_reserve");
+}
+
+int gpuart_hip_scene_reserve_prims(gpuart_hip_ctx *c, uint64_t n_recs, uint64_t n_prims, gpuart_hip_scene *out) {
+    return reserve_spare(c, n_recs, n_prims, false, out, "gpuart_hip_scene_reserve_prims");
+}
+
+/// Adopts the tree built into the spare set. `replace`: the primitive count and the type mask change too (gpuart_hip_scene_replaced).
+static int adopt_built(gpuart_hip_ctx *c, const gpuart_hip_scene *b, bool replace, uint32_t type_mask, const std::string &name) {
+    if (!c || !b) return fail(GPUART_HIP_ERR_ARG, name + ": bad argument");
     if (!c->have_scene) return fail(GPUART_HIP_ERR_ARG, "no scene uploaded");
-    if (c->exact_boxes) return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_rebuilt: a tree with irregular boxes (or boxes that do not bound their contents) is not rebuilt");
+    if (c->exact_boxes) return fail(GPUART_HIP_ERR_ARG, name + ": a tree with irregular boxes (or boxes that do not bound their contents) is not rebuilt");
     if (!c->d_spare_prims || b->recs != (void *)c->d_spare_recs || b->prims != (void *)c->d_spare_prims || b->prim_boxes != (void *)c->d_spare_boxes ||
         b->generation != c->generation || b->layout != 1)
-        return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_rebuilt: the arrays are not the ones gpuart_hip_scene_reserve handed out for this scene");
-    if (b->n_prims != c->n_prims) return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_rebuilt: the primitive count changed");
-    if (b->n_recs > c->spare_recs) return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_rebuilt: more records than were reserved");
-    if (b->max_depth > 1024) return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_rebuilt: tree deeper than 1024 levels");
-    if (!tree_rule::box_ok(b->root_min, b->root_max)) return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_rebuilt: the root box is not finite and ordered");
-    if (!c->d_prim_boxes) return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_rebuilt: gpuart_hip_scene_device was not called for this scene");
-    if (!tree_rule::root_ref_ok(b->root_ref, b->n_recs, c->n_prims))
-        return fail(GPUART_HIP_ERR_ARG, "gpuart_hip_scene_rebuilt: the root ref is neither record 0 of a tree with records nor a leaf inside the primitives");
+        return fail(GPUART_HIP_ERR_ARG, name + ": the arrays are not the ones gpuart_hip_scene_reserve handed out for this scene");
+    if (!replace && b->n_prims != c->n_prims) return fail(GPUART_HIP_ERR_ARG, name + ": the primitive count changed");
+    if (replace && (b->n_prims < 1 || b->n_prims > c->spare_prims))
+        return fail(GPUART_HIP_ERR_ARG, name + ": the primitive count " + std::to_string(b->n_prims) + " is 0 or beyond the reserved room of " + std::to_string(c->spare_prims));
+    if (replace && (type_mask == 0 || type_mask > 15u)) return fail(GPUART_HIP_ERR_ARG, name + ": the type mask is 0 or beyond 15");
+    if (b->n_recs > c->spare_recs) return fail(GPUART_HIP_ERR_ARG, name + ": more records than were reserved");
+    if (b->max_depth > 1024) return fail(GPUART_HIP_ERR_ARG, name + ": tree deeper than 1024 levels");
+    if (!tree_rule::box_ok(b->root_min, b->root_max)) return fail(GPUART_HIP_ERR_ARG, name + ": the root box is not finite and ordered");
+    if (!c->d_prim_boxes) return fail(GPUART_HIP_ERR_ARG, name + ": gpuart_hip_scene_device was not called for this scene");
+    if (!tree_rule::root_ref_ok(b->root_ref, b->n_recs, b->n_prims))
+        return fail(GPUART_HIP_ERR_ARG, name + ": the root ref is neither record 0 of a tree with records nor a leaf inside the primitives");
     HIP_TRY(hipSetDevice(c->device));
     int r;
     if ((r = gpuart_hip_flush(c))) return r;
@@ -1356,9 +1378,16 @@ int gpuart_hip_scene_rebuilt(gpuart_hip_ctx *c, const gpuart_hip_scene *b) {
     std::swap(c->d_recs, c->d_spare_recs);
     std::swap(c->d_prims, c->d_spare_prims);
     std::swap(c->d_prim_boxes, c->d_spare_boxes);
+    // the former scene arrays are the spare set now, with their own room
     const uint64_t old_recs = c->n_recs;
     c->n_recs = b->n_recs;
     c->spare_recs = old_recs;
+    std::swap(c->prims_room, c->spare_prims);
+    if (replace) {
+        c->n_prims = b->n_prims;
+        c->type_mask = type_mask;
+        c->ref_order = (!c->exact_boxes && c->n_prims < c->nearest_min_prims) ? 1u : 0u;
+    }
     memcpy(c->root_min, b->root_min, 12); memcpy(c->root_max, b->root_max, 12);
     c->root_ref = b->root_ref;
     c->max_depth = b->max_depth;
@@ -1369,6 +1398,12 @@ int gpuart_hip_scene_rebuilt(gpuart_hip_ctx *c, const gpuart_hip_scene *b) {
     c->generation++;
     c->order_stale = true;
     return 0;
+}
+
+int gpuart_hip_scene_rebuilt(gpuart_hip_ctx *c, const gpuart_hip_scene *b) { return adopt_built(c, b, false, 0, "gpuart_hip_scene_rebuilt"); }
+
+int gpuart_hip_scene_replaced(gpuart_hip_ctx *c, const gpuart_hip_scene *b, uint32_t type_mask) {
+    return adopt_built(c, b, true, type_mask, "gpuart_hip_scene_replaced");
 }
 
 // ---- batched ray queries (kernels_query.h) ----------------------------------------------------------------------------

@@ -669,6 +669,70 @@ bool BoundingVolumesHierarchy::AdoptTopology(const uint32_t *newToOld, const uin
     return true;
 }
 
+// ---- an edit of the primitive list: the host's statement of include/gpuart_edit.h ----
+bool BoundingVolumesHierarchy::CheckEdit(const uint32_t *remove, size_t nRemove, const uint32_t *addTypes, const float *addPayloads, size_t nAdd,
+                                         size_t *firstBad) const {
+    const auto bad = [&](size_t i) {
+        if (firstBad) *firstBad = i;
+        return false;
+    };
+    const size_t n = NumPrimitives;
+    if (n == 0 || (nRemove && !remove) || (nAdd && (!addTypes || !addPayloads))) return bad(SIZE_MAX);
+    for (size_t i = 0; i < nRemove; i++)
+        if ((i && remove[i] <= remove[i - 1]) || remove[i] >= n) return bad(i);
+    for (size_t k = 0; k < nAdd; k++)
+        if (addTypes[k] > 3 || !prim_rule::prim_ok(addTypes[k], addPayloads + prim_rule::PAYLOAD * k)) return bad(nRemove + k);
+    if (n - nRemove + nAdd == 0 || n - nRemove + nAdd >= 0x05555540u) return bad(SIZE_MAX);
+    return true;
+}
+
+bool BoundingVolumesHierarchy::EditPrimitives(const uint32_t *remove, size_t nRemove, const uint32_t *addTypes, const float *addPayloads, size_t nAdd,
+                                              size_t *firstBad) {
+    if (!CheckEdit(remove, nRemove, addTypes, addPayloads, nAdd, firstBad)) return false;
+    std::vector<size_t> header;
+    if (!PrimHeaders(header)) {
+        if (firstBad) *firstBad = SIZE_MAX;
+        return false;
+    }
+    const size_t n = NumPrimitives;
+    std::vector<float, UninitAlloc<float>> data;
+    data.reserve(LeafData.size() + nAdd * RGBA_ELEMS * 5);
+    size_t next = 0;  // the next removal
+    for (size_t k = 0; k < n; k++) {
+        if (next < nRemove && remove[next] == k) { next++; continue; }
+        const size_t at = header[k];
+        data.insert(data.end(), LeafData.begin() + at, LeafData.begin() + at + RGBA_ELEMS * (2 + (size_t)(as_uint(LeafData[at]) & 3)));
+    }
+    for (size_t k = 0; k < nAdd; k++) {
+        float head[RGBA_ELEMS] = {0, 0, 0, 0};
+        memcpy(head, &addTypes[k], sizeof(uint32_t));
+        data.insert(data.end(), head, head + RGBA_ELEMS);
+        const float *d = addPayloads + prim_rule::PAYLOAD * k;
+        data.insert(data.end(), d, d + RGBA_ELEMS * (size_t)prim_rule::data_quads(addTypes[k]));
+    }
+    // one leaf of everything: what RebuildMorton and AdoptTopology read is the primitives in order
+    Node root;
+    root.parent = 0; root.higher = 0; root.isLower = false;
+    root.count = (uint32_t)(n - nRemove + nAdd); root.primFirst = 0; root.dataBegin = 0; root.dataEnd = data.size();
+    Nodes.clear();
+    Nodes.push_back(root);
+    LeafData.swap(data);
+    NumPrimitives = root.count;
+    Depth = 0;
+    QuadAddr.clear();
+    LeafOfFirst.clear();
+    LocateCursor = 0;
+    RefitNode(0);
+    return true;
+}
+
+bool BoundingVolumesHierarchy::EditPrimitives(const uint32_t *remove, size_t nRemove, const Primitive *const *added, size_t nAdd, size_t *firstBad) {
+    std::vector<float> payloads(prim_rule::PAYLOAD * nAdd);
+    std::vector<uint32_t> types(nAdd);
+    for (size_t k = 0; k < nAdd; k++) types[k] = Payload(*added[k], payloads.data() + prim_rule::PAYLOAD * k);
+    return EditPrimitives(remove, nRemove, types.data(), payloads.data(), nAdd, firstBad);
+}
+
 bool BoundingVolumesHierarchy::Load(const float *q, size_t nq) {
     struct Todo { size_t addr; uint32_t parent; bool isLower; unsigned level; };
     std::vector<Node, UninitAlloc<Node>> nodes;

@@ -86,6 +86,19 @@ public:
     /// Refit rule's own, so Compile() writes what tests/ploc_ref.py does. False, with nothing changed, for anything else.
     bool AdoptTopology(const uint32_t *newToOld, const uint32_t *refs, size_t nRecs);
 
+    /// Replaces the primitive list by an edited one, in the device's order (include/gpuart_edit.h states the contract; tests/edit_ref.py
+    /// restates it): the primitives that are not removed in their old order, then the added ones in the order given. `remove`: nRemove
+    /// strictly ascending ordinals; `addTypes`, `addPayloads`: nAdd types 0..3 and nAdd x 16 floats as for Refit. The tree is left as
+    /// one leaf of all the primitives, to be rebuilt by RebuildMorton or AdoptTopology before anything is compiled from it. False,
+    /// with nothing changed, unless the removals are ascending and in range, every addition meets csrc/hip/prim_rule.h and at least one
+    /// primitive is left (fewer than 0x05555540); `firstBad` then receives the first offender's index, the removals counted first, or
+    /// SIZE_MAX where no single entry is at fault.
+    bool EditPrimitives(const uint32_t *remove, size_t nRemove, const uint32_t *addTypes, const float *addPayloads, size_t nAdd, size_t *firstBad = nullptr);
+    /// The same from primitives.
+    bool EditPrimitives(const uint32_t *remove, size_t nRemove, const Primitive *const *added, size_t nAdd, size_t *firstBad = nullptr);
+    /// EditPrimitives' verdict alone. Changes nothing.
+    bool CheckEdit(const uint32_t *remove, size_t nRemove, const uint32_t *addTypes, const float *addPayloads, size_t nAdd, size_t *firstBad = nullptr) const;
+
     /// Prints a compiled tree, decoding it the way the device code does.
     static void Print(const Primitive::Data &compiledTree, std::ostream &s);
 

@@ -274,6 +274,62 @@ int gpuart_renderer_rebuild_tree_mode(gpuart_renderer *r, int mode, uint32_t *ne
     if (newToOld) std::copy(perm.begin(), perm.end(), newToOld);
     return 1;
 }
+int gpuart_renderer_edit_primitives(gpuart_renderer *r, const uint32_t *remove, int nRemove, const gpuart_prim_desc *added, int nAdd, int mode,
+                                    uint32_t *source, size_t *n_new) {
+    if (!r || nRemove < 0 || nAdd < 0 || (nRemove && !remove) || (nAdd && !added)) return 0;
+    // the caller's numbering -> device ordinals, ascending
+    const size_t nOld = r->impl.GetBVH().GetNumPrimitives();
+    std::vector<uint32_t> ordinalOf(r->descOf.size());
+    for (size_t k = 0; k < r->descOf.size(); k++) ordinalOf[(size_t)r->descOf[k]] = (uint32_t)k;
+    std::vector<uint32_t> sorted((size_t)nRemove);
+    std::vector<bool> gone(std::max(nOld, r->descOf.size()), false);  // by the caller's index
+    for (int i = 0; i < nRemove; i++) {
+        if (remove[i] >= gone.size() || gone[remove[i]]) return 0;
+        gone[remove[i]] = true;
+        sorted[(size_t)i] = ordinalOf.empty() ? remove[i] : ordinalOf[remove[i]];
+    }
+    std::sort(sorted.begin(), sorted.end());
+    std::vector<Primitive *> list;
+    std::vector<uint32_t> from;
+    const bool ok = make_list(added, nAdd, list) && r->impl.EditPrimitives(sorted.data(), (size_t)nRemove, list.data(), (size_t)nAdd, &from, mode);
+    free_list(list);
+    if (!ok) return 0;
+    if (!r->descOf.empty() || nOld) {
+        // a survivor's description keeps its rank among the survivors; the added ones follow
+        std::vector<int32_t> rank(gone.size(), -1);
+        int32_t next = 0;
+        for (size_t d = 0; d < gone.size(); d++)
+            if (!gone[d]) rank[d] = next++;
+        std::vector<int32_t> now(from.size());
+        for (size_t p = 0; p < from.size(); p++)
+            now[p] = from[p] < nOld ? rank[r->descOf.empty() ? from[p] : (size_t)r->descOf[from[p]]] : next + (int32_t)(from[p] - nOld);
+        r->descOf.swap(now);
+    }
+    if (source) std::copy(from.begin(), from.end(), source);
+    if (n_new) *n_new = from.size();
+    return 1;
+}
+int gpuart_edit_tree(const float *quads, size_t nquads, const uint32_t *remove, size_t nRemove, const uint32_t *addTypes, const float *addPayloads,
+                     size_t nAdd, int adopt, const uint32_t *order, const uint32_t *refs, size_t nRecs, float **out, size_t *nout, uint32_t *newToOld,
+                     size_t *firstBad) {
+    if (!quads || !out || !nout || (adopt && !order)) return -1;
+    BoundingVolumesHierarchy tree;
+    if (!tree.Load(quads, nquads) || tree.CompiledFloats() != nquads * RGBA_ELEMS) return -1;
+    if (!tree.EditPrimitives(remove, nRemove, addTypes, addPayloads, nAdd, firstBad)) return -2;
+    std::vector<uint32_t> perm;
+    if (adopt) {
+        if (!tree.AdoptTopology(order, refs, nRecs)) return -3;
+        perm.assign(order, order + tree.GetNumPrimitives());
+    } else if (!tree.RebuildMorton(&perm, order)) return -3;
+    const size_t floats = tree.CompiledFloats();
+    float *q = (float *)malloc(floats * sizeof(float));
+    if (!q) return -1;
+    tree.CompileTo(q);
+    *out = q;
+    *nout = floats / RGBA_ELEMS;
+    if (newToOld) std::copy(perm.begin(), perm.end(), newToOld);
+    return 0;
+}
 int gpuart_renderer_tree_cost(gpuart_renderer *r, double *cost) { return r && r->impl.TreeCost(cost) ? 1 : 0; }
 void gpuart_renderer_last_rebuild_ms(gpuart_renderer *r, double out[2]) {
     if (!r || !out) return;

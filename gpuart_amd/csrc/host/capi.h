@@ -93,6 +93,22 @@ int gpuart_renderer_rebuild_tree(gpuart_renderer *r, uint32_t *newToOld);
 /* The same with Renderer::RebuildTree's mode: 0 the Morton build (what gpuart_renderer_rebuild_tree does), 1 Renderer::TREE_CLUSTERED,
  * the clustered build of include/gpuart_ploc.h — slower to build, cheaper to walk. */
 int gpuart_renderer_rebuild_tree_mode(gpuart_renderer *r, int mode, uint32_t *newToOld);
+/* Renderer::EditPrimitives. `remove`: nRemove distinct indices into the caller's descriptions, in any order; `added`: nAdd descriptions of
+ * any types. Afterwards the caller's descriptions are the ones that were not removed, in their order, followed by `added`: that list is
+ * what the ordinals of gpuart_renderer_trace_rays and the indices of gpuart_renderer_update_primitives number from now on. source (n_new
+ * entries, may be NULL) receives, per new device ordinal, the old device ordinal of a survivor or n_old + k for added[k]; *n_new (may be
+ * NULL) the new count. mode as gpuart_renderer_rebuild_tree_mode. 1 on success, 0 — with the scene unchanged — on any refusal. */
+int gpuart_renderer_edit_primitives(gpuart_renderer *r, const uint32_t *remove, int nRemove, const gpuart_prim_desc *added, int nAdd, int mode,
+                                    uint32_t *source, size_t *n_new);
+/* BoundingVolumesHierarchy::EditPrimitives without a device: the compiled tree `quads` with the primitives `remove` (nRemove strictly
+ * ascending device ordinals) removed and nAdd primitives of `addTypes` / `addPayloads` (16 floats each) appended, then rebuilt — with
+ * adopt == 0 in Morton order (`order` as for gpuart_rebuild_tree: NULL, or the permutation to check), else by AdoptTopology of `order`
+ * and `refs` (nRecs records) — and compiled; *out is malloc'ed (gpuart_free), *nout its quads. newToOld (may be NULL) receives the
+ * rebuild's permutation of the edited list. 0, -1 for a malformed tree or NULL arguments, -2 for a refused edit (*firstBad, may be NULL,
+ * the first offender or SIZE_MAX), -3 for a refused order or topology. */
+int gpuart_edit_tree(const float *quads, size_t nquads, const uint32_t *remove, size_t nRemove, const uint32_t *addTypes, const float *addPayloads,
+                     size_t nAdd, int adopt, const uint32_t *order, const uint32_t *refs, size_t nRecs, float **out, size_t *nout, uint32_t *newToOld,
+                     size_t *firstBad);
 /* Renderer::TreeCost. 1 on success. */
 int gpuart_renderer_tree_cost(gpuart_renderer *r, double *cost);
 /* {total, host tree} ms of the last gpuart_renderer_rebuild_tree. */

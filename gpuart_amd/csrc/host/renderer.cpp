@@ -103,6 +103,7 @@ Renderer::~Renderer() {
     if (Refitter) gpuart_refit_destroy(Refitter);
     if (Builder) gpuart_build_destroy(Builder);
     if (Clusterer) gpuart_ploc_destroy(Clusterer);
+    if (Editor) gpuart_edit_destroy(Editor);
     if (Backend) gpuart_hip_destroy(Backend);
 }
 
@@ -413,6 +414,98 @@ bool Renderer::RebuildClustered(std::vector<uint32_t> *newToOld) {
     LastRebuildMs[0] = std::chrono::duration<double, std::milli>(t3 - t0).count();
     LastRebuildMs[1] = std::chrono::duration<double, std::milli>(t2 - t1).count();
     if (newToOld) newToOld->swap(order);
+    RefitGeneration = 0;  // the refit handle is bound to the old arrays: the next UpdatePrimitives binds again
+    GBufferValid = false;
+    EdgeListValid = false;
+    ResetPathTracing();
+    return true;
+}
+
+// ---- a scene that gains or loses primitives: the list edited and its tree built on the device (include/gpuart_edit.h) ----
+// The order of RebuildTree and RebuildClustered: the host's verdict, the view committed, the device edit into the library's staging
+// arrays and the build from them into the spare set — every refusal up to here leaves both trees as they were —, then the host tree
+// follows and the context adopts the result.
+bool Renderer::EditPrimitives(const uint32_t *remove, size_t nRemove, Primitive *const *added, size_t nAdd, std::vector<uint32_t> *source, int mode) {
+    if (!IsOK || (nRemove && !remove) || (nAdd && !added)) return false;
+    if (mode != TREE_MORTON && mode != TREE_CLUSTERED) {
+        std::cerr << "Renderer: EditPrimitives: unknown mode " << mode << "." << std::endl;
+        return false;
+    }
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    std::vector<float> payloads(GPUART_REFIT_PAYLOAD * nAdd);
+    std::vector<uint32_t> types(nAdd);
+    for (size_t k = 0; k < nAdd; k++) {
+        if (!added[k]) return false;
+        types[k] = BoundingVolumesHierarchy::Payload(*added[k], payloads.data() + GPUART_REFIT_PAYLOAD * k);
+    }
+    size_t bad = 0;
+    if (!Tree.CheckEdit(remove, nRemove, types.data(), payloads.data(), nAdd, &bad)) {
+        std::cerr << "Renderer: EditPrimitives: refused (removals ascending and in range, added primitives inside the rule, a primitive left); first offender "
+                  << (bad == SIZE_MAX ? std::string("none") : std::to_string(bad)) << "." << std::endl;
+        return false;
+    }
+    gpuart_hip_scene scene, edited, spare;
+    if (!Check(gpuart_hip_scene_device(Backend, &scene), "looking up the scene's device arrays")) return false;
+    if (scene.exact_boxes || !scene.n_prims || Tree.GetNumPrimitives() != scene.n_prims) {
+        std::cerr << "Renderer: EditPrimitives: an empty scene or a tree with irregular boxes (or boxes that do not bound their contents) is not edited." << std::endl;
+        return false;
+    }
+    const bool clustered = mode == TREE_CLUSTERED;
+    if (!Editor && !Check(gpuart_edit_create(Device, &Editor), "creating the edit handle", gpuart_edit_last_error)) return false;
+    if (clustered && !Clusterer && !Check(gpuart_ploc_create(Device, &Clusterer), "creating the clustered build's handle", gpuart_ploc_last_error)) return false;
+    if (!clustered && !Builder && !Check(gpuart_build_create(Device, &Builder), "creating the build handle", gpuart_build_last_error)) return false;
+    CommitTemporalView();
+    const uint64_t nOld = scene.n_prims, n = nOld - nRemove + nAdd;
+    std::vector<int32_t> from(n);
+    gpuart_edit_result er;
+    if (!Check(gpuart_edit_run_host(Editor, &scene, remove, nRemove, types.data(), payloads.data(), nAdd, from.data(), &edited, &er), "editing the primitive list",
+               gpuart_edit_last_error))
+        return false;
+    if (!Check(gpuart_hip_scene_reserve_prims(Backend, clustered ? n - 1 : (n + 1) / 2 - 1, n, &spare), "reserving the spare arrays")) return false;
+    std::vector<uint32_t> order(n), refs;
+    uint64_t nRecs = 0;
+    if (clustered) {
+        gpuart_ploc_result res;
+        if (!Check(gpuart_ploc_run_host(Clusterer, &edited, &spare, order.data(), &res), "building the edited tree", gpuart_ploc_last_error)) return false;
+        nRecs = res.n_recs;
+        spare.root_ref = res.root_ref; spare.max_depth = res.max_depth;
+        memcpy(spare.root_min, res.root_min, 12); memcpy(spare.root_max, res.root_max, 12);
+        spare.box_slack = res.subnormal ? __builtin_inff() : 0.0f;
+        refs.resize(2 * nRecs);
+        if (nRecs) {  // the two ref words of every record: word 3 of its first two quads
+            std::unique_ptr<uint32_t[]> recs(new uint32_t[16 * nRecs]);
+            if (hipMemcpy(recs.get(), spare.recs, 64 * nRecs, hipMemcpyDeviceToHost) != hipSuccess) {
+                std::cerr << "Renderer: EditPrimitives: reading the built records back failed." << std::endl;
+                return false;
+            }
+            for (uint64_t r = 0; r < nRecs; r++) { refs[2 * r] = recs[16 * r + 3]; refs[2 * r + 1] = recs[16 * r + 7]; }
+        }
+    } else {
+        gpuart_build_result res;
+        if (!Check(gpuart_build_run_host(Builder, &edited, &spare, order.data(), &res), "building the edited tree", gpuart_build_last_error)) return false;
+        nRecs = res.n_recs;
+        spare.root_ref = res.root_ref; spare.max_depth = res.max_depth;
+        memcpy(spare.root_min, res.root_min, 12); memcpy(spare.root_max, res.root_max, 12);
+        spare.box_slack = res.subnormal ? __builtin_inff() : 0.0f;
+    }
+    spare.n_recs = nRecs;
+    spare.n_prims = n;
+    const auto t1 = std::chrono::high_resolution_clock::now();
+    // (from here the host tree changes: a tree or a device that cannot follow is an inconsistency, not a refusal)
+    if (!Tree.EditPrimitives(remove, nRemove, types.data(), payloads.data(), nAdd) ||
+        !(clustered ? Tree.AdoptTopology(order.data(), refs.data(), nRecs) : Tree.RebuildMorton(nullptr, order.data()))) {
+        std::cerr << "Renderer: EditPrimitives: the device's tree is not the contract's over the edited primitives." << std::endl;
+        return IsOK = false;
+    }
+    const auto t2 = std::chrono::high_resolution_clock::now();
+    if (!Check(gpuart_hip_scene_replaced(Backend, &spare, er.type_mask), "adopting the edited tree")) return IsOK = false;
+    const auto t3 = std::chrono::high_resolution_clock::now();
+    LastRebuildMs[0] = std::chrono::duration<double, std::milli>(t3 - t0).count();
+    LastRebuildMs[1] = std::chrono::duration<double, std::milli>(t2 - t1).count();
+    if (source) {
+        source->resize(n);
+        for (uint64_t p = 0; p < n; p++) (*source)[p] = (uint32_t)from[order[p]];
+    }
     RefitGeneration = 0;  // the refit handle is bound to the old arrays: the next UpdatePrimitives binds again
     GBufferValid = false;
     EdgeListValid = false;

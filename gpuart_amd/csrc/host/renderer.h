@@ -23,6 +23,7 @@
 #include "gpuart_antilag.h"
 #include "gpuart_build.h"
 #include "gpuart_ploc.h"
+#include "gpuart_edit.h"
 #include "gpuart_converge.h"
 #include "gpuart_denoise.h"
 #include "gpuart_despeckle.h"
@@ -93,6 +94,15 @@ public:
     /// before the device arrays are swapped: every refusal leaves everything as it was.
     enum TreeMode { TREE_MORTON = 0, TREE_CLUSTERED = 1 };
     bool RebuildTree(std::vector<uint32_t> *newToOld = nullptr, int mode = TREE_MORTON);
+    /// Removes the primitives with the device ordinals `remove` (strictly ascending) from the scene, appends `added` (any types) and
+    /// builds the tree of the result on the device in `mode` (include/gpuart_edit.h): device to device but for the lists, with no host
+    /// build and no upload. The host tree gives its verdict first; the device edits into staging arrays and builds into the spare set,
+    /// so a refusal up to there leaves both trees as they were; then the host tree follows (BoundingVolumesHierarchy::EditPrimitives,
+    /// then the device's order or topology) and the context adopts the result (gpuart_hip_scene_replaced). `*source` receives, per new
+    /// device ordinal, the old ordinal of a survivor or nOld + k for added[k]. The temporal histories are kept exactly as for
+    /// RebuildTree; UpdatePrimitives, RebuildTree, TreeCost, TraceRays and Pick work on the edited scene. The caller keeps `added`.
+    bool EditPrimitives(const uint32_t *remove, size_t nRemove, Primitive *const *added, size_t nAdd, std::vector<uint32_t> *source = nullptr,
+                        int mode = TREE_CLUSTERED);
     /// The tree's cost as gpuart_build_cost measures it on the device arrays: the sum over the records of both children's half-areas
     /// over the root's. It grows as refitted boxes loosen; RebuildTree brings it back down.
     bool TreeCost(double *cost);
@@ -360,6 +370,7 @@ private:
     uint64_t RefitGeneration = 0;         ///< the generation Refitter is bound to (0: none; the first upload's is 1)
     gpuart_build *Builder = nullptr;      ///< made by the first RebuildTree or TreeCost
     gpuart_ploc *Clusterer = nullptr;     ///< made by the first RebuildTree(TREE_CLUSTERED)
+    gpuart_edit *Editor = nullptr;        ///< made by the first EditPrimitives
     bool RebuildClustered(std::vector<uint32_t> *newToOld);
     double LastRebuildMs[2] = {0, 0};
     BoundingVolumesHierarchy Tree;

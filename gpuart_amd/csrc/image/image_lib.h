@@ -5,8 +5,8 @@
 // for the _host entry points, and the two device functions more than one library states: the luminance and "what is a surface pixel".
 // Each library is one translation unit that includes this once, so everything sits in an anonymous namespace and every library has its
 // own copy (its own last error). The checks take the library's name: every message starts with it. DESIGN.md "The image libraries'
-// scaffold" says what stays in each library. refit/refit.hip and treebuild/build.hip, which are no image libraries (they work on the
-// uploaded tree), take the last error, HIP_TRY, the handle, the checks and the grow-only buffer from here too.
+// scaffold" says what stays in each library. refit/refit.hip, treebuild/build.hip, ploc/ploc.hip and edit/edit.hip, which are no image
+// libraries (they work on the uploaded tree), take the last error, HIP_TRY, the handle, the checks and the grow-only buffer from here too.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -9,6 +9,7 @@
 
 #include "../image/image_lib.h"
 #include "box_pass.h"
+#include "prim_pack.h"
 #include "gpuart_refit.h"
 
 namespace {
@@ -29,17 +30,14 @@ __global__ void __launch_bounds__(256) k_rf_validate(const uint32_t *ord, const 
     else if (p >= n_prims) why = WHY_RANGE;
     else {
         float d[prim_rule::PAYLOAD];
-        for (int k = 0; k < 4; k++) {
-            const float4 v = payload[4 * (size_t)i + k];
-            d[4 * k] = v.x; d[4 * k + 1] = v.y; d[4 * k + 2] = v.z; d[4 * k + 3] = v.w;
-        }
+        load_payload(payload, i, d);
         const uint32_t type = __float_as_uint(prims[3 * (size_t)p].w) & 3u;
         if (!prim_rule::prim_ok(type, d)) why = WHY_RULE;
     }
     if (why) atomicMax(&st->refused, ~(4u * i + why));
 }
 
-// 2. One thread per update: the three float4 of the record by the uploader's arithmetic (Converter::pack_prim), word 3 of the first —
+// 2. One thread per update: the three float4 of the record by the uploader's arithmetic (prim_pack.h), word 3 of the first —
 // the type and the leaf's count — kept, and the primitive's own box. Nothing is written once an update is refused: the status word was
 // written by the launch before this one.
 __global__ void __launch_bounds__(256) k_rf_update(const uint32_t *ord, const float4 *payload, uint32_t n, float4 *prims, float *pbox, const Status *st) {
@@ -47,24 +45,13 @@ __global__ void __launch_bounds__(256) k_rf_update(const uint32_t *ord, const fl
     if (i >= n || st->refused) return;
     const uint32_t p = ord[i];
     float d[prim_rule::PAYLOAD];
-    for (int k = 0; k < 4; k++) {
-        const float4 v = payload[4 * (size_t)i + k];
-        d[4 * k] = v.x; d[4 * k + 1] = v.y; d[4 * k + 2] = v.z; d[4 * k + 3] = v.w;
-    }
+    load_payload(payload, i, d);
     float4 *rec = prims + 3 * (size_t)p;
     const float T = rec[0].w;
     const uint32_t type = __float_as_uint(T) & 3u;
-    float4 r0 = make_float4(d[0], d[1], d[2], T), r1, r2 = make_float4(0, 0, 0, 0);
-    if (type == prim_rule::SPHERE) r1 = make_float4(d[3], 0, 0, 0);
-    else if (type == prim_rule::DISC) r1 = make_float4(d[4], d[5], d[6], d[3]);
-    else if (type == prim_rule::TRIANGLE) {
-        r1 = make_float4(d[4] - d[0], d[5] - d[1], d[6] - d[2], 0);   // edge1 = v1 - v0
-        r2 = make_float4(d[8] - d[0], d[9] - d[1], d[10] - d[2], 0);  // edge2 = v2 - v0
-    } else {
-        r1 = make_float4(d[8], d[9], d[10], d[11]);
-        r2 = make_float4(d[3], d[12], d[13], d[14]);
-    }
-    rec[0] = r0; rec[1] = r1; rec[2] = r2;
+    float4 r[3];
+    pack_prim(type, d, T, r);
+    rec[0] = r[0]; rec[1] = r[1]; rec[2] = r[2];
     float lo[3], hi[3];
     prim_rule::prim_box(type, d, lo, hi);
     float *b = pbox + 6 * (size_t)p;

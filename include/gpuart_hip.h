@@ -304,6 +304,22 @@ int gpuart_hip_scene_reserve(gpuart_hip_ctx *ctx, uint64_t n_recs, gpuart_hip_sc
  * neither 0 with records nor a leaf ref inside n_prims without, a failure to size the traversal stacks, and on a tree
  * the uploader classified irregular or disorderly. */
 int gpuart_hip_scene_rebuilt(gpuart_hip_ctx *ctx, const gpuart_hip_scene *built);
+/* ---- an edit on the device (include/gpuart_edit.h; DESIGN.md "Edit") ----------------------------------------------------------------
+ * gpuart_hip_scene_reserve with room for n_prims >= 1 primitives and boxes instead of the scene's own count: a spare set that is
+ * large enough in both counts is reused (*out says its room, which may be more than was asked for), else it is made anew. Beyond the
+ * n_recs records and behind the n_prims primitives and boxes the set is zeroed, so what a builder writes there ends as an upload's
+ * arrays do. The context remembers the room of the spare set and of the scene's own arrays apart from the counts: after an adoption
+ * the former scene arrays are the spare set with their own room, and a later gpuart_hip_scene_reserve, which wants a set of exactly the
+ * scene's count, makes a new one where the room differs. GPUART_HIP_ERR_ARG without a scene, for n_prims = 0 or beyond the uploader's
+ * bound (0x05555540). */
+int gpuart_hip_scene_reserve_prims(gpuart_hip_ctx *ctx, uint64_t n_recs, uint64_t n_prims, gpuart_hip_scene *out);
+/* gpuart_hip_scene_rebuilt for a tree of another primitive list: n_prims becomes built->n_prims (1 <= n_prims <= the reserved room) and
+ * the type mask, which selects the kernel specialisation, becomes type_mask (bit t: primitives of type t are present; non-zero, at most
+ * 15) — the caller vouches for it as for the root box. What follows from the two is computed as an upload computes it: the tree order
+ * against the nearest-first threshold, the scene's bytes and node count, the traversal stacks, box_slack; `generation` grows.
+ * GPUART_HIP_ERR_ARG, with nothing changed, for everything gpuart_hip_scene_rebuilt refuses but a changed count, for such a type mask
+ * and for a count of 0 or beyond the room. */
+int gpuart_hip_scene_replaced(gpuart_hip_ctx *ctx, const gpuart_hip_scene *built, uint32_t type_mask);
 
 /* How the fast kernels walk the uploaded tree: 1 (the default for every tree of regular boxes since round 5) in the reference's order —
  * lower child first, shaders/bvh_intersection.glsl:432-441 — which is the only order PROVEN to return the reference's winner; 2 in the
