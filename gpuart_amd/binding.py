@@ -448,6 +448,13 @@ def make_prims(descs):
 
 
 # ---- pure host functions ------------------------------------------------------------------------
+def _take_quads(L, q, n):
+    """The n quads the host library allocated at q, copied out as an (n, 4) float32 array and freed."""
+    out = np.ctypeslib.as_array(q, shape=(n, 4)).copy()
+    L.gpuart_free(q)
+    return out
+
+
 def compile_bvh(descs, max_levels=1024, min_prims=2):
     """BoundingVolumesHierarchy(prims, max_levels, min_prims).Compile() -> (quads (n,4) float32, depth)."""
     L = host_lib()
@@ -459,9 +466,7 @@ def compile_bvh(descs, max_levels=1024, min_prims=2):
                               C.byref(depth))
     if rc != 0:
         raise RuntimeError("gpuart_compile_bvh failed")
-    out = np.ctypeslib.as_array(q, shape=(nq.value, 4)).copy()
-    L.gpuart_free(q)
-    return out, depth.value
+    return _take_quads(L, q, nq.value), depth.value
 
 
 def rebuild_tree(quads, order=None):
@@ -476,8 +481,7 @@ def rebuild_tree(quads, order=None):
     rc = L.gpuart_rebuild_tree(_p(q), C.c_size_t(q.size // 4), _p(o) if o is not None else None, C.byref(out), C.byref(nout), _p(perm))
     if rc != 0:
         raise ValueError("gpuart_rebuild_tree: %d" % rc)
-    res = np.ctypeslib.as_array(out, shape=(nout.value, 4)).copy()
-    L.gpuart_free(out)
+    res = _take_quads(L, out, nout.value)
     n = int(o.size) if o is not None else None
     if n is None:
         n = sum(1 for _ in _leaf_prims(res))
@@ -499,9 +503,7 @@ def adopt_tree(quads, order, refs):
     rc = L.gpuart_adopt_tree(_p(q), C.c_size_t(q.size // 4), _p(o), _p(r) if r.size else None, C.c_size_t(r.size // 2), C.byref(out), C.byref(nout))
     if rc != 0:
         raise ValueError("gpuart_adopt_tree: %d" % rc)
-    res = np.ctypeslib.as_array(out, shape=(nout.value, 4)).copy()
-    L.gpuart_free(out)
-    return res
+    return _take_quads(L, out, nout.value)
 
 
 def edit_tree(quads, remove, add_types, add_payload, order=None, refs=None):
@@ -529,8 +531,7 @@ def edit_tree(quads, remove, add_types, add_payload, order=None, refs=None):
         e = ValueError("gpuart_edit_tree: %d" % rc)
         e.first_bad = int(bad.value) if rc == -2 and bad.value != C.c_size_t(-1).value else None
         raise e
-    res = np.ctypeslib.as_array(out, shape=(nout.value, 4)).copy()
-    L.gpuart_free(out)
+    res = _take_quads(L, out, nout.value)
     return res, perm[:sum(1 for _ in _leaf_prims(res))].copy()
 
 
@@ -571,9 +572,7 @@ def compile_bvh_from_file(kind, path, magnification=1.0, translation=(0, 0, 0), 
                                         C.byref(nl))
     if rc != 0:
         raise RuntimeError("loading %s failed" % path)
-    out = np.ctypeslib.as_array(q, shape=(nq.value, 4)).copy()
-    L.gpuart_free(q)
-    return out, depth.value, nl.value
+    return _take_quads(L, q, nq.value), depth.value, nl.value
 
 
 def sort_permutation(keys, threads=8):
@@ -949,6 +948,25 @@ class Backend:
             report["levels"] = int(res.levels)
         return report
 
+    def _fill_spare(self, spare, res):
+        """What a build reported (BuildResult or PlocResult), into the descriptor of the spare set it built into."""
+        spare.n_recs, spare.root_ref, spare.max_depth = res.n_recs, res.root_ref, res.max_depth
+        spare.root_min, spare.root_max = res.root_min, res.root_max
+        spare.box_slack = float("inf") if res.subnormal else 0.0
+
+    def _out_tensor(self, out, n, fn, count):
+        """rebuild's `out` rule: the contiguous int32 tensor of n entries on the device that receives the result — `out` itself (else
+        ValueError in `fn`'s name), a new one for True, and for None when the process has imported torch — or None: the result is a NumPy array."""
+        if out is None:
+            out = "torch" in sys.modules
+        if out is False:
+            return None
+        import torch
+        t = torch.empty((n,), dtype=torch.int32, device="cuda:%d" % self.device) if out is True else out
+        if not (hasattr(t, "data_ptr") and t.is_cuda and t.is_contiguous() and t.dtype == torch.int32 and t.numel() == n):
+            raise ValueError("%s: out must be a contiguous int32 tensor of %s entries on the device" % (fn, count))
+        return t
+
     def rebuild(self, out=None, mode="morton"):
         """Rebuilds the uploaded scene's tree on the device and has the context adopt it — `mode` "morton": in Morton order
         (include/gpuart_build.h), fast to build; "clustered": by locally-ordered clustering (include/gpuart_ploc.h), a tree of lower cost
@@ -966,22 +984,16 @@ class Backend:
         scene = self.scene_device()
         n = int(scene.n_prims)
         spare = self.scene_reserve((n - 1 if clustered else (n + 1) // 2 - 1) if n else 0)
-        if out is None:
-            out = "torch" in sys.modules
-        if out is False:
+        perm = self._out_tensor(out, n, "rebuild", "n_prims")
+        if perm is None:
             perm = np.zeros(n, np.uint32)
             rc = run_host(h, C.byref(scene), C.byref(spare), _p(perm), C.byref(res))
         else:
             import torch
-            perm = torch.empty((n,), dtype=torch.int32, device="cuda:%d" % self.device) if out is True else out
-            if not (hasattr(perm, "data_ptr") and perm.is_cuda and perm.is_contiguous() and perm.dtype == torch.int32 and perm.numel() == n):
-                raise ValueError("rebuild: out must be a contiguous int32 tensor of n_prims entries on the device")
             torch.cuda.synchronize(perm.device)
             rc = run(h, C.byref(scene), C.byref(spare), C.c_void_p(perm.data_ptr()), C.byref(res))
         h._chk(rc)
-        spare.n_recs, spare.root_ref, spare.max_depth = res.n_recs, res.root_ref, res.max_depth
-        spare.root_min, spare.root_max = res.root_min, res.root_max
-        spare.box_slack = float("inf") if res.subnormal else 0.0
+        self._fill_spare(spare, res)
         self.scene_rebuilt(spare)
         self.last_rebuild = self._build_report(h, res, step_ms, steps, clustered)
         return perm
@@ -1050,9 +1062,7 @@ class Backend:
             perm = torch.empty((n_new,), dtype=torch.int32, device=source.device)
             torch.cuda.synchronize(source.device)
             bh._chk(run(bh, C.byref(edited), C.byref(spare), C.c_void_p(perm.data_ptr()), C.byref(bres)))
-            composed = torch.empty((n_new,), dtype=torch.int32, device=source.device) if out is None or isinstance(out, bool) else out
-            if not (hasattr(composed, "data_ptr") and composed.is_cuda and composed.is_contiguous() and composed.dtype == torch.int32 and composed.numel() == n_new):
-                raise ValueError("edit: out must be a contiguous int32 tensor of n_new entries on the device")
+            composed = self._out_tensor(True if out is False else out, n_new, "edit", "n_new")   # (False: a tensor first, copied to the host below)
             torch.cuda.synchronize(source.device)
             h._chk(E.gpuart_edit_compose(h, C.c_void_p(source.data_ptr()), C.c_void_p(perm.data_ptr()), C.c_size_t(n_new), C.c_void_p(composed.data_ptr())))
             if out is False:
@@ -1061,23 +1071,14 @@ class Backend:
             perm = np.zeros(n_new, np.uint32)
             bh._chk(run_host(bh, C.byref(edited), C.byref(spare), _p(perm), C.byref(bres)))
             composed = source[:n_new][perm]
-            if out is None:
-                out = "torch" in sys.modules
-            if out is not False:
+            target = self._out_tensor(out, n_new, "edit", "n_new")
+            if target is not None:
                 import torch
-                dev = torch.from_numpy(composed).to("cuda:%d" % self.device)
-                if out is True:
-                    composed = dev
-                else:
-                    if not (hasattr(out, "data_ptr") and out.is_cuda and out.is_contiguous() and out.dtype == torch.int32 and out.numel() == n_new):
-                        raise ValueError("edit: out must be a contiguous int32 tensor of n_new entries on the device")
-                    out.copy_(dev)
-                    torch.cuda.synchronize(out.device)
-                    composed = out
+                target.copy_(torch.from_numpy(composed))
+                torch.cuda.synchronize(target.device)
+                composed = target
         spare.n_prims = n_new
-        spare.n_recs, spare.root_ref, spare.max_depth = bres.n_recs, bres.root_ref, bres.max_depth
-        spare.root_min, spare.root_max = bres.root_min, bres.root_max
-        spare.box_slack = float("inf") if bres.subnormal else 0.0
+        self._fill_spare(spare, bres)
         self.scene_replaced(spare, int(res.type_mask))
         ms = (C.c_double * len(EDIT_STEPS))()
         h._chk(E.gpuart_edit_step_ms(h, ms))
@@ -1511,9 +1512,7 @@ class Renderer:
         nq = C.c_size_t(0)
         if self.L.gpuart_renderer_compile_bvh(self.h, C.byref(q), C.byref(nq)) != 0:
             raise RuntimeError("gpuart_renderer_compile_bvh failed")
-        out = np.ctypeslib.as_array(q, shape=(nq.value, 4)).copy()
-        self.L.gpuart_free(q)
-        return out
+        return _take_quads(self.L, q, nq.value)
 
     def init_box(self): self.L.gpuart_renderer_init_box(self.h)
     def init_dragon(self, path): return bool(self.L.gpuart_renderer_init_dragon(self.h, path.encode()))

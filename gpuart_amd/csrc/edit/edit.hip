@@ -3,25 +3,22 @@
 // subtracted exactly as the host uploader does (csrc/hip/converter.h; refit/prim_pack.h restates it for the device) and
 // tests/edit_ref.py restates in NumPy float32. DESIGN.md "Edit" describes the launches; nothing is handed between workgroups inside
 // one, and the only atomic sets the status word.
-#include <cstring>
 #include <vector>
 
 #include <rocprim/device/device_scan.hpp>
 
 #include "../image/image_lib.h"
+#include "../tree/tree_lib.h"
 #include "../refit/prim_pack.h"
-#include "../hip/tree_rule.h"
 #include "gpuart_edit.h"
 
 namespace {
 
 const char LIB[] = "edit";
 
-enum { WHY_ORDER = 1, WHY_RANGE = 2, WHY_RULE = 3 };  ///< low two bits of the status word
-constexpr uint32_t ITEMS = 8;                          ///< boxes per thread of the reduction's first launch
+constexpr uint32_t ITEMS = 8;  ///< boxes per thread of the reduction's first launch
 
-/// What the device sequence leaves for the host, in device memory; zero before a run. `refused` = ~(4 x index + why) of the first
-/// offender (the largest over all: atomicMax), 0 while nothing is refused.
+/// What the device sequence leaves for the host, in device memory; zero before a run. `refused`: tree_lib.h's refusal word.
 struct Status {
     uint32_t refused;
     uint32_t type_mask;
@@ -67,7 +64,7 @@ __global__ void __launch_bounds__(256) k_ed_validate(const uint32_t *remove, uin
         load_payload(payload, k, d);
         if (type > 3u || !prim_rule::prim_ok(type, d)) why = WHY_RULE;
     }
-    if (why) atomicMax(&st->refused, ~(4u * i + why));
+    if (why) refuse(&st->refused, i, why);
 }
 
 // 2. One thread per removal: its primitive's keep flag cleared (the flags were set to 1 by a fill before this launch). An ordinal out
@@ -87,14 +84,7 @@ __global__ void __launch_bounds__(256) k_ed_compact(const float4 *src, const flo
     if (i >= n_old || st->refused || !keep[i]) return;
     const uint32_t q = pos[i];
     if (q >= n_keep) return;  // (cannot happen once validation passed: the removals are distinct and in range)
-    const float4 *s = src + 3 * (size_t)i;
-    float4 r0 = s[0];
-    r0.w = __uint_as_float((__float_as_uint(r0.w) & 3u) | count << 2);
-    float4 *d = dst + 3 * (size_t)q;
-    d[0] = r0; d[1] = s[1]; d[2] = s[2];
-    const float *sb = src_box + 6 * (size_t)i;
-    float *db = dst_box + 6 * (size_t)q;
-    for (int k = 0; k < 6; k++) db[k] = sb[k];
+    move_prim(src, src_box, i, count, dst, dst_box, q);
     source[q] = (int32_t)i;
 }
 
@@ -180,8 +170,7 @@ struct gpuart_edit : ImageHandle {
     DeviceBuffer scratch;      ///< keep flags, their scan, the partial results
     DeviceBuffer temp;         ///< the scan's
     DeviceBuffer staging;      ///< run_host: payload, removals, types, source
-    hipEvent_t ev[5] = {};
-    double step_ms[4] = {0, 0, 0, 0};
+    StepTimer timer;           ///< validate and flags, scan, compact and append, reduce
 };
 
 namespace {
@@ -190,10 +179,7 @@ int check_run(gpuart_edit *h, const gpuart_hip_scene *src, const void *remove, s
               const void *source, const gpuart_hip_scene *edited, size_t payload_align) {
     if (int rc = check_handle(LIB, h)) return rc;
     if (!src || !edited) return fail(GPUART_HIP_ERR_ARG, "edit: src or edited is NULL");
-    if (src->layout != 1) return fail(GPUART_HIP_ERR_ARG, "edit: src: unknown layout " + std::to_string(src->layout));
-    if (src->exact_boxes) return fail(GPUART_HIP_ERR_ARG, "edit: src: a tree with irregular boxes (or boxes that do not bound their contents) is not edited");
-    if (!src->prims || !src->prim_boxes || !src->n_prims || src->n_prims > tree_rule::REF_INDEX)
-        return fail(GPUART_HIP_ERR_ARG, "edit: src: the scene's arrays or counts are empty or out of range");
+    if (int rc = check_descriptor(src, LIB, "src", "edited", false)) return rc;
     if (misaligned({src->prims}, 16) || misaligned({src->prim_boxes}, 4)) return fail(GPUART_HIP_ERR_ARG, "edit: src: misaligned arrays");
     if (n_remove > src->n_prims) return fail(GPUART_HIP_ERR_ARG, "edit: more removals (" + std::to_string(n_remove) + ") than primitives (" + std::to_string(src->n_prims) + ")");
     if (n_add >= GPUART_EDIT_MAX_PRIMS) return fail(GPUART_HIP_ERR_ARG, "edit: too many additions");
@@ -228,15 +214,13 @@ int run_device(gpuart_edit *h, const gpuart_hip_scene *src, const uint32_t *remo
         for (const auto &s : S)
             if (overlaps(s.p, s.bytes, b->mem, b->bytes)) return fail(GPUART_HIP_ERR_ARG, "edit: src's arrays are the handle's own staging arrays");
 
-    const auto blocks = [](size_t items) { return (uint32_t)((items + 255) / 256); };
     const uint32_t count = n_new == 1 ? 1u : 0u;  // a list of one primitive is a leaf of one
     float4 *dprims = (float4 *)h->prims.mem;
     float *dbox = (float *)h->boxes.mem;
-    int at = 0;
-    const auto mark = [&] { return hipEventRecord(h->ev[at++], h->stream); };
+    h->timer.start(h->stream);
 
     HIP_TRY(hipMemsetAsync(h->status, 0, sizeof(Status), h->stream));
-    HIP_TRY(mark());
+    HIP_TRY(h->timer.mark());
     if (n_remove + n_add) {
         k_ed_validate<<<blocks((size_t)n_remove + n_add), 256, 0, h->stream>>>(remove, n_remove, types, payload, n_add, n_old, h->status);
         HIP_TRY(hipGetLastError());
@@ -246,9 +230,9 @@ int run_device(gpuart_edit *h, const gpuart_hip_scene *src, const uint32_t *remo
         k_ed_flags<<<blocks(n_remove), 256, 0, h->stream>>>(remove, n_remove, n_old, keep);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(mark());
+    HIP_TRY(h->timer.mark());
     HIP_TRY(rocprim::exclusive_scan(h->temp.mem, scan_bytes, keep, pos, 0u, (size_t)n_old, rocprim::plus<uint32_t>(), h->stream));
-    HIP_TRY(mark());
+    HIP_TRY(h->timer.mark());
     k_ed_compact<<<blocks(n_old), 256, 0, h->stream>>>((const float4 *)src->prims, (const float *)src->prim_boxes, keep, pos, n_old, n_keep, count, dprims, dbox,
                                                        source, h->status);
     HIP_TRY(hipGetLastError());
@@ -256,7 +240,7 @@ int run_device(gpuart_edit *h, const gpuart_hip_scene *src, const uint32_t *remo
         k_ed_append<<<blocks(n_add), 256, 0, h->stream>>>(types, payload, n_add, n_old, n_keep, count, dprims, dbox, source, h->status);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(mark());
+    HIP_TRY(h->timer.mark());
     k_ed_reduce<<<parts, 256, 0, h->stream>>>(dprims, dbox, n_new, partial, h->status);
     HIP_TRY(hipGetLastError());
     k_ed_root<<<1, 256, 0, h->stream>>>(partial, parts, h->status);
@@ -264,32 +248,25 @@ int run_device(gpuart_edit *h, const gpuart_hip_scene *src, const uint32_t *remo
     // the slack behind the list ends in zeros, as behind an upload's
     HIP_TRY(hipMemsetAsync((char *)dprims + (size_t)n_new * 48, 0, 4 * sizeof(float4), h->stream));
     HIP_TRY(hipMemsetAsync((char *)dbox + (size_t)n_new * 24, 0, 16, h->stream));
-    HIP_TRY(mark());
+    HIP_TRY(h->timer.mark());
     Status st;
     HIP_TRY(hipMemcpyAsync(&st, h->status, sizeof st, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    for (int k = 0; k < 4; k++) {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, h->ev[k], h->ev[k + 1]));
-        h->step_ms[k] = ms;
-    }
-    const uint32_t key = ~st.refused;  // 4 x index + why
+    if (int rc = h->timer.read()) return rc;
     if (result) {
         memset(result, 0, sizeof *result);
         result->status = st.refused ? GPUART_HIP_ERR_ARG : 0;
-        result->first_bad = st.refused ? key >> 2 : GPUART_EDIT_NONE;
+        result->first_bad = st.refused ? refused_index(st.refused) : GPUART_EDIT_NONE;
         result->n_prims = st.refused ? 0 : n_new;
         result->type_mask = st.refused ? 0 : st.type_mask;
         if (!st.refused) { memcpy(result->root_min, st.root_min, 12); memcpy(result->root_max, st.root_max, 12); }
     }
     if (st.refused) {
-        static const char *const WHY[4] = {"", "its ordinal does not exceed the one before it (ordinals are strictly ascending)",
-                                           "its ordinal is not below the number of primitives",
-                                           "its type is above 3 or its payload is outside the primitive rule (a word that is not finite or beyond 2^20, a negative "
-                                           "radius or length, or a cone's derived constants that contradict its centres and radii)"};
-        const uint32_t i = key >> 2;
+        const char *why = refused_why(st.refused, "its type is above 3 or its payload is outside the primitive rule (a word that is not finite or beyond 2^20, a "
+                                                  "negative radius or length, or a cone's derived constants that contradict its centres and radii)");
+        const uint32_t i = refused_index(st.refused);
         return fail(GPUART_HIP_ERR_ARG, std::string("edit: ") + (i < n_remove ? "removal " + std::to_string(i) : "addition " + std::to_string(i - n_remove)) +
-                                            " refused: " + WHY[key & 3u] + "; nothing was edited");
+                                            " refused: " + why + "; nothing was edited");
     }
     memset(edited, 0, sizeof *edited);
     edited->layout = 1;
@@ -309,36 +286,23 @@ extern "C" {
 const char *gpuart_edit_last_error(void) { return g_last_error.c_str(); }
 
 int gpuart_edit_create(int device, gpuart_edit **out) {
-    if (int rc = create_handle(LIB, device, out)) return rc;
-    gpuart_edit *h = *out;
-    *out = nullptr;
-    hipError_t e = hipMalloc((void **)&h->status, sizeof(Status));
-    for (int k = 0; k < 5 && e == hipSuccess; k++) e = hipEventCreate(&h->ev[k]);
-    if (e != hipSuccess) {
-        gpuart_edit_destroy(h);
-        return fail(GPUART_HIP_ERR_DEVICE, std::string("edit: allocating the status: ") + hipGetErrorString(e));
-    }
-    *out = h;
-    return 0;
+    return create_tree_handle(LIB, device, out, gpuart_edit_destroy, [](gpuart_edit *h) {
+        const hipError_t e = hipMalloc((void **)&h->status, sizeof(Status));
+        return e == hipSuccess ? h->timer.create(4) : e;
+    });
 }
 
 int gpuart_edit_destroy(gpuart_edit *h) {
     if (!h) return 0;
     destroy_handle(h, {h->status, h->prims.mem, h->boxes.mem, h->scratch.mem, h->temp.mem, h->staging.mem});
-    for (hipEvent_t e : h->ev)
-        if (e) (void)hipEventDestroy(e);
+    h->timer.destroy();
     delete h;
     return 0;
 }
 
 int gpuart_edit_finish(gpuart_edit *h) { return finish_handle(LIB, h); }
 
-int gpuart_edit_step_ms(gpuart_edit *h, double ms[4]) {
-    if (int rc = check_handle(LIB, h)) return rc;
-    if (!ms) return fail(GPUART_HIP_ERR_ARG, "edit: ms is NULL");
-    memcpy(ms, h->step_ms, sizeof h->step_ms);
-    return 0;
-}
+int gpuart_edit_step_ms(gpuart_edit *h, double ms[4]) { return step_ms(LIB, h, ms); }
 
 int gpuart_edit_run(gpuart_edit *h, const gpuart_hip_scene *src, const uint32_t *remove, size_t n_remove, const uint32_t *add_types,
                     const float *add_payload, size_t n_add, int32_t *source, gpuart_hip_scene *edited, gpuart_edit_result *result) {
@@ -375,7 +339,7 @@ int gpuart_edit_compose(gpuart_edit *h, const int32_t *source, const uint32_t *p
     if (n >= GPUART_EDIT_MAX_PRIMS) return fail(GPUART_HIP_ERR_ARG, "edit: too many primitives: " + std::to_string(n));
     if (overlaps(out, n * 4, source, n * 4) || overlaps(out, n * 4, perm, n * 4)) return fail(GPUART_HIP_ERR_ARG, "edit: out overlaps source or perm");
     HIP_TRY(hipSetDevice(h->device));
-    k_ed_compose<<<(uint32_t)((n + 255) / 256), 256, 0, h->stream>>>(source, perm, (uint32_t)n, out);
+    k_ed_compose<<<blocks(n), 256, 0, h->stream>>>(source, perm, (uint32_t)n, out);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(h->stream));
     return 0;

@@ -282,6 +282,56 @@ void Renderer::SetPrimitives(std::vector<Primitive *> &primitives, bool printInf
     ResetPathTracing();
 }
 
+namespace {
+/// What the Renderer needs of an image or tree library to make a handle, wait for it and report its failures.
+template <class H>
+struct Lib {
+    int (*create)(int, H **);
+    int (*finish)(H *);
+    const char *(*lastError)(void);
+    const char *creating;
+};
+const Lib<gpuart_denoise> DN{gpuart_denoise_create, gpuart_denoise_finish, gpuart_denoise_last_error, "creating the denoiser"};
+const Lib<gpuart_temporal> TP{gpuart_temporal_create, gpuart_temporal_finish, gpuart_temporal_last_error, "creating the temporal accumulator"};
+const Lib<gpuart_temporal> TPM{gpuart_temporal_create, gpuart_temporal_finish, gpuart_temporal_last_error, "creating the moments' temporal accumulator"};
+const Lib<gpuart_moments> MO{gpuart_moments_create, gpuart_moments_finish, gpuart_moments_last_error, "creating the moments library's handle"};
+const Lib<gpuart_temporal> TPF{gpuart_temporal_create, gpuart_temporal_finish, gpuart_temporal_last_error, "creating the fast history's temporal accumulator"};
+const Lib<gpuart_antilag> AL{gpuart_antilag_create, gpuart_antilag_finish, gpuart_antilag_last_error, "creating the anti-lag library's handle"};
+const Lib<gpuart_converge> CV{gpuart_converge_create, gpuart_converge_finish, gpuart_converge_last_error, "creating the convergence estimator"};
+const Lib<gpuart_adaptive> AD{gpuart_adaptive_create, gpuart_adaptive_finish, gpuart_adaptive_last_error, "creating the adaptive estimator"};
+const Lib<gpuart_refine> RF{gpuart_refine_create, gpuart_refine_finish, gpuart_refine_last_error, "creating the variance-guided filter"};
+const Lib<gpuart_edges> ED{gpuart_edges_create, gpuart_edges_finish, gpuart_edges_last_error, "creating the edge resolve's handle"};
+const Lib<gpuart_despeckle> DS{gpuart_despeckle_create, gpuart_despeckle_finish, gpuart_despeckle_last_error, "creating the firefly clamp's handle"};
+const Lib<gpuart_display> DP{gpuart_display_create, gpuart_display_finish, gpuart_display_last_error, "creating the display stage"};
+const Lib<gpuart_refit> RT{gpuart_refit_create, gpuart_refit_finish, gpuart_refit_last_error, "creating the refit handle"};
+const Lib<gpuart_build> BD{gpuart_build_create, gpuart_build_finish, gpuart_build_last_error, "creating the build handle"};
+const Lib<gpuart_ploc> PL{gpuart_ploc_create, gpuart_ploc_finish, gpuart_ploc_last_error, "creating the clustered build's handle"};
+const Lib<gpuart_edit> ET{gpuart_edit_create, gpuart_edit_finish, gpuart_edit_last_error, "creating the edit handle"};
+
+std::chrono::high_resolution_clock::time_point Now() { return std::chrono::high_resolution_clock::now(); }
+template <class T> double Ms(T from, T to) { return std::chrono::duration<double, std::milli>(to - from).count(); }
+
+/// One build into `spare`, which then says what was built: the two builds' result records differ in the name of their fifth word only.
+template <class H, class R>
+int RunBuild(H *h, int (*runHost)(H *, const gpuart_hip_scene *, const gpuart_hip_scene *, uint32_t *, R *), const gpuart_hip_scene &src, gpuart_hip_scene &spare,
+             uint32_t *order) {
+    R res;
+    const int rc = runHost(h, &src, &spare, order, &res);
+    if (rc != 0) return rc;
+    spare.n_recs = res.n_recs;
+    spare.root_ref = res.root_ref;
+    spare.max_depth = res.max_depth;
+    memcpy(spare.root_min, res.root_min, 12); memcpy(spare.root_max, res.root_max, 12);
+    spare.box_slack = res.subnormal ? __builtin_inff() : 0.0f;
+    return 0;
+}
+}  // namespace
+
+template <class H, class L>
+bool Renderer::Ensure(H *&h, const L &lib) {
+    return h || Check(lib.create(Device, &h), lib.creating, lib.lastError);
+}
+
 // ---- moved primitives: a refit in place (include/gpuart_refit.h) ------------------------------------
 // The host tree gives its verdict first and changes last: a refusal, on the host or on the device (they state one rule,
 // csrc/hip/prim_rule.h), leaves both trees as they were. The view is committed after the verdict and before the device arrays change,
@@ -305,7 +355,7 @@ bool Renderer::UpdatePrimitives(const uint32_t *indices, Primitive *const *moved
         std::cerr << "Renderer: UpdatePrimitives: a tree with irregular boxes (or boxes that do not bound their contents) is not refitted." << std::endl;
         return false;
     }
-    if (!Refitter && !Check(gpuart_refit_create(Device, &Refitter), "creating the refit handle", gpuart_refit_last_error)) return false;
+    if (!Ensure(Refitter, RT)) return false;
     if (RefitGeneration != scene.generation) {  // (a bind reads every record back: once per upload)
         if (!Check(gpuart_refit_bind(Refitter, &scene), "binding the refit handle", gpuart_refit_last_error)) return false;
         RefitGeneration = scene.generation;
@@ -315,114 +365,93 @@ bool Renderer::UpdatePrimitives(const uint32_t *indices, Primitive *const *moved
     if (!Check(gpuart_refit_run_host(Refitter, &scene, indices, payloads.data(), n, &res), "refitting the tree", gpuart_refit_last_error)) return false;
     if (!Check(gpuart_hip_scene_refitted(Backend, res.root_min, res.root_max, (int)res.subnormal), "adopting the refitted tree")) return IsOK = false;
     Tree.Refit(indices, payloads.data(), n, nullptr, true);
-    GBufferValid = false;
-    EdgeListValid = false;
-    ResetPathTracing();
+    TreeChanged(false);
     return true;
 }
 
-// ---- a drifted scene: the tree rebuilt on the device (include/gpuart_build.h) ------------------------
-// The device builds into the spare arrays, so every refusal up to the swap leaves the scene as it was; the host tree follows last,
-// from the device's permutation (RebuildMorton checks the order instead of sorting). The temporal histories are kept as for a refit:
-// their tap validation compares hit point, normal and class, and of the ordinal only "is the user sphere" (-2), which a new numbering
-// does not touch.
+// ---- a drifted scene: the tree rebuilt on the device (include/gpuart_build.h, include/gpuart_ploc.h) ----
+// The device builds into the spare arrays, so every refusal up to the swap leaves the scene as it was. The temporal histories are kept as
+// for a refit: their tap validation compares hit point, normal and class, and of the ordinal only "is the user sphere" (-2), which a new
+// numbering does not touch. RebuildTree, EditPrimitives and TreeCost state their shared steps once, here.
+bool Renderer::RefusesTreeChange(const gpuart_hip_scene &scene, const char *fn, const char *done) {
+    if (!scene.exact_boxes && scene.n_prims && Tree.GetNumPrimitives() == scene.n_prims) return false;
+    std::cerr << "Renderer: " << fn << ": an empty scene or a tree with irregular boxes (or boxes that do not bound their contents) is not " << done << "." << std::endl;
+    return true;
+}
+
+bool Renderer::EnsureBuilder(bool clustered) { return clustered ? Ensure(Clusterer, PL) : Ensure(Builder, BD); }
+
+bool Renderer::BuildIntoSpare(const gpuart_hip_scene &src, bool clustered, bool withPrims, bool commit, const char *fn, const char *what, gpuart_hip_scene &spare,
+                              BuiltTree &built) {
+    const uint64_t n = src.n_prims, room = clustered ? n - 1 : (n + 1) / 2 - 1;
+    if (!Check(withPrims ? gpuart_hip_scene_reserve_prims(Backend, room, n, &spare) : gpuart_hip_scene_reserve(Backend, room, &spare), "reserving the spare arrays"))
+        return false;
+    if (!EnsureBuilder(clustered)) return false;
+    if (commit) CommitTemporalView();
+    built.order.resize(n);
+    const int rc = clustered ? RunBuild(Clusterer, gpuart_ploc_run_host, src, spare, built.order.data())
+                             : RunBuild(Builder, gpuart_build_run_host, src, spare, built.order.data());
+    if (!Check(rc, what, clustered ? PL.lastError : BD.lastError)) return false;
+    built.ran = Now();
+    built.nRecs = spare.n_recs;
+    built.refs.resize(clustered ? 2 * built.nRecs : 0);
+    if (clustered && built.nRecs) {  // the topology is the device's: the two ref words of every record, word 3 of its first two quads
+        std::unique_ptr<uint32_t[]> recs(new uint32_t[16 * built.nRecs]);
+        if (hipMemcpy(recs.get(), spare.recs, 64 * built.nRecs, hipMemcpyDeviceToHost) != hipSuccess) {
+            std::cerr << "Renderer: " << fn << ": reading the built records back failed." << std::endl;
+            return false;
+        }
+        for (uint64_t r = 0; r < built.nRecs; r++) { built.refs[2 * r] = recs[16 * r + 3]; built.refs[2 * r + 1] = recs[16 * r + 7]; }
+    }
+    return true;
+}
+
+bool Renderer::TreeFollows(bool clustered, const BuiltTree &built) {
+    return clustered ? Tree.AdoptTopology(built.order.data(), built.refs.data(), built.nRecs) : Tree.RebuildMorton(nullptr, built.order.data());
+}
+
+void Renderer::TreeChanged(bool newArrays) {
+    if (newArrays) RefitGeneration = 0;
+    GBufferValid = false;
+    EdgeListValid = false;
+    ResetPathTracing();
+}
+
+// The two modes commit in different orders (DESIGN.md "The tree libraries' scaffold"). Morton: the context adopts the spare set, then the
+// host tree follows from the device's permutation (RebuildMorton checks the order instead of sorting) — a host tree that cannot is an
+// inconsistency. Clustered: the host tree checks and adopts the device's topology first — a refusal still leaves both trees as they were
+// — and only then are the device arrays swapped; there a device that cannot follow is the inconsistency.
 bool Renderer::RebuildTree(std::vector<uint32_t> *newToOld, int mode) {
     if (!IsOK) return false;
-    if (mode == TREE_CLUSTERED) return RebuildClustered(newToOld);
-    if (mode != TREE_MORTON) {
+    if (mode != TREE_MORTON && mode != TREE_CLUSTERED) {
         std::cerr << "Renderer: RebuildTree: unknown mode " << mode << "." << std::endl;
         return false;
     }
-    const auto t0 = std::chrono::high_resolution_clock::now();
+    const bool clustered = mode == TREE_CLUSTERED;
+    const auto t0 = Now();
     gpuart_hip_scene scene, spare;
     if (!Check(gpuart_hip_scene_device(Backend, &scene), "looking up the scene's device arrays")) return false;
-    if (scene.exact_boxes || !scene.n_prims || Tree.GetNumPrimitives() != scene.n_prims) {
-        std::cerr << "Renderer: RebuildTree: an empty scene or a tree with irregular boxes (or boxes that do not bound their contents) is not rebuilt." << std::endl;
+    if (RefusesTreeChange(scene, "RebuildTree", "rebuilt")) return false;
+    BuiltTree built;
+    if (!BuildIntoSpare(scene, clustered, false, true, "RebuildTree", "rebuilding the tree", spare, built)) return false;
+    if (!clustered && !Check(gpuart_hip_scene_rebuilt(Backend, &spare), "adopting the rebuilt tree")) return false;
+    const auto t1 = clustered ? built.ran : Now();
+    if (!TreeFollows(clustered, built)) {
+        std::cerr << "Renderer: RebuildTree: the device's " << (clustered ? "topology is not a tree over the scene's primitives." : "order is not the contract's.") << std::endl;
+        if (!clustered) IsOK = false;
         return false;
     }
-    const uint64_t n = scene.n_prims;
-    if (!Check(gpuart_hip_scene_reserve(Backend, (n + 1) / 2 - 1, &spare), "reserving the spare arrays")) return false;
-    if (!Builder && !Check(gpuart_build_create(Device, &Builder), "creating the build handle", gpuart_build_last_error)) return false;
-    CommitTemporalView();
-    gpuart_build_result res;
-    std::vector<uint32_t> order(n);
-    if (!Check(gpuart_build_run_host(Builder, &scene, &spare, order.data(), &res), "rebuilding the tree", gpuart_build_last_error)) return false;
-    spare.n_recs = res.n_recs;
-    spare.root_ref = res.root_ref;
-    spare.max_depth = res.max_depth;
-    memcpy(spare.root_min, res.root_min, 12); memcpy(spare.root_max, res.root_max, 12);
-    spare.box_slack = res.subnormal ? __builtin_inff() : 0.0f;
-    if (!Check(gpuart_hip_scene_rebuilt(Backend, &spare), "adopting the rebuilt tree")) return false;
-    const auto t1 = std::chrono::high_resolution_clock::now();
-    // (from here the device renders the new tree: a host tree that cannot follow is an inconsistency, not a refusal)
-    if (!Tree.RebuildMorton(nullptr, order.data())) {
-        std::cerr << "Renderer: RebuildTree: the device's order is not the contract's." << std::endl;
-        return IsOK = false;
-    }
-    const auto t2 = std::chrono::high_resolution_clock::now();
-    LastRebuildMs[0] = std::chrono::duration<double, std::milli>(t2 - t0).count();
-    LastRebuildMs[1] = std::chrono::duration<double, std::milli>(t2 - t1).count();
-    if (newToOld) newToOld->swap(order);
-    RefitGeneration = 0;  // the refit handle is bound to the old arrays: the next UpdatePrimitives binds again
-    GBufferValid = false;
-    EdgeListValid = false;
-    ResetPathTracing();
-    return true;
-}
-
-// The clustered build (include/gpuart_ploc.h). The topology is the device's: its ref words come back (two per record), the host tree
-// checks and adopts them, and only then are the device arrays swapped — a refusal anywhere leaves both trees as they were.
-bool Renderer::RebuildClustered(std::vector<uint32_t> *newToOld) {
-    const auto t0 = std::chrono::high_resolution_clock::now();
-    gpuart_hip_scene scene, spare;
-    if (!Check(gpuart_hip_scene_device(Backend, &scene), "looking up the scene's device arrays")) return false;
-    if (scene.exact_boxes || !scene.n_prims || Tree.GetNumPrimitives() != scene.n_prims) {
-        std::cerr << "Renderer: RebuildTree: an empty scene or a tree with irregular boxes (or boxes that do not bound their contents) is not rebuilt." << std::endl;
-        return false;
-    }
-    const uint64_t n = scene.n_prims;
-    if (!Check(gpuart_hip_scene_reserve(Backend, n - 1, &spare), "reserving the spare arrays")) return false;
-    if (!Clusterer && !Check(gpuart_ploc_create(Device, &Clusterer), "creating the clustered build's handle", gpuart_ploc_last_error)) return false;
-    CommitTemporalView();
-    gpuart_ploc_result res;
-    std::vector<uint32_t> order(n);
-    if (!Check(gpuart_ploc_run_host(Clusterer, &scene, &spare, order.data(), &res), "rebuilding the tree", gpuart_ploc_last_error)) return false;
-    const auto t1 = std::chrono::high_resolution_clock::now();
-    // the two ref words of every record: word 3 of its first two quads
-    std::vector<uint32_t> refs(2 * res.n_recs);
-    if (res.n_recs) {
-        std::unique_ptr<uint32_t[]> recs(new uint32_t[16 * res.n_recs]);
-        if (hipMemcpy(recs.get(), spare.recs, 64 * res.n_recs, hipMemcpyDeviceToHost) != hipSuccess) {
-            std::cerr << "Renderer: RebuildTree: reading the built records back failed." << std::endl;
-            return false;
-        }
-        for (uint64_t r = 0; r < res.n_recs; r++) { refs[2 * r] = recs[16 * r + 3]; refs[2 * r + 1] = recs[16 * r + 7]; }
-    }
-    if (!Tree.AdoptTopology(order.data(), refs.data(), res.n_recs)) {
-        std::cerr << "Renderer: RebuildTree: the device's topology is not a tree over the scene's primitives." << std::endl;
-        return false;
-    }
-    const auto t2 = std::chrono::high_resolution_clock::now();
-    spare.n_recs = res.n_recs;
-    spare.root_ref = res.root_ref;
-    spare.max_depth = res.max_depth;
-    memcpy(spare.root_min, res.root_min, 12); memcpy(spare.root_max, res.root_max, 12);
-    spare.box_slack = res.subnormal ? __builtin_inff() : 0.0f;
-    // (the host tree has changed: a device that cannot follow is an inconsistency, not a refusal)
-    if (!Check(gpuart_hip_scene_rebuilt(Backend, &spare), "adopting the rebuilt tree")) return IsOK = false;
-    const auto t3 = std::chrono::high_resolution_clock::now();
-    LastRebuildMs[0] = std::chrono::duration<double, std::milli>(t3 - t0).count();
-    LastRebuildMs[1] = std::chrono::duration<double, std::milli>(t2 - t1).count();
-    if (newToOld) newToOld->swap(order);
-    RefitGeneration = 0;  // the refit handle is bound to the old arrays: the next UpdatePrimitives binds again
-    GBufferValid = false;
-    EdgeListValid = false;
-    ResetPathTracing();
+    const auto t2 = Now();
+    if (clustered && !Check(gpuart_hip_scene_rebuilt(Backend, &spare), "adopting the rebuilt tree")) return IsOK = false;
+    LastRebuildMs[0] = Ms(t0, Now());
+    LastRebuildMs[1] = Ms(t1, t2);
+    if (newToOld) newToOld->swap(built.order);
+    TreeChanged(true);
     return true;
 }
 
 // ---- a scene that gains or loses primitives: the list edited and its tree built on the device (include/gpuart_edit.h) ----
-// The order of RebuildTree and RebuildClustered: the host's verdict, the view committed, the device edit into the library's staging
+// The order of the clustered RebuildTree: the host's verdict, the view committed, the device edit into the library's staging
 // arrays and the build from them into the spare set — every refusal up to here leaves both trees as they were —, then the host tree
 // follows and the context adopts the result.
 bool Renderer::EditPrimitives(const uint32_t *remove, size_t nRemove, Primitive *const *added, size_t nAdd, std::vector<uint32_t> *source, int mode) {
@@ -431,7 +460,7 @@ bool Renderer::EditPrimitives(const uint32_t *remove, size_t nRemove, Primitive 
         std::cerr << "Renderer: EditPrimitives: unknown mode " << mode << "." << std::endl;
         return false;
     }
-    const auto t0 = std::chrono::high_resolution_clock::now();
+    const auto t0 = Now();
     std::vector<float> payloads(GPUART_REFIT_PAYLOAD * nAdd);
     std::vector<uint32_t> types(nAdd);
     for (size_t k = 0; k < nAdd; k++) {
@@ -446,70 +475,34 @@ bool Renderer::EditPrimitives(const uint32_t *remove, size_t nRemove, Primitive 
     }
     gpuart_hip_scene scene, edited, spare;
     if (!Check(gpuart_hip_scene_device(Backend, &scene), "looking up the scene's device arrays")) return false;
-    if (scene.exact_boxes || !scene.n_prims || Tree.GetNumPrimitives() != scene.n_prims) {
-        std::cerr << "Renderer: EditPrimitives: an empty scene or a tree with irregular boxes (or boxes that do not bound their contents) is not edited." << std::endl;
-        return false;
-    }
+    if (RefusesTreeChange(scene, "EditPrimitives", "edited")) return false;
     const bool clustered = mode == TREE_CLUSTERED;
-    if (!Editor && !Check(gpuart_edit_create(Device, &Editor), "creating the edit handle", gpuart_edit_last_error)) return false;
-    if (clustered && !Clusterer && !Check(gpuart_ploc_create(Device, &Clusterer), "creating the clustered build's handle", gpuart_ploc_last_error)) return false;
-    if (!clustered && !Builder && !Check(gpuart_build_create(Device, &Builder), "creating the build handle", gpuart_build_last_error)) return false;
+    if (!Ensure(Editor, ET) || !EnsureBuilder(clustered)) return false;
     CommitTemporalView();
-    const uint64_t nOld = scene.n_prims, n = nOld - nRemove + nAdd;
+    const uint64_t n = scene.n_prims - nRemove + nAdd;
     std::vector<int32_t> from(n);
     gpuart_edit_result er;
     if (!Check(gpuart_edit_run_host(Editor, &scene, remove, nRemove, types.data(), payloads.data(), nAdd, from.data(), &edited, &er), "editing the primitive list",
                gpuart_edit_last_error))
         return false;
-    if (!Check(gpuart_hip_scene_reserve_prims(Backend, clustered ? n - 1 : (n + 1) / 2 - 1, n, &spare), "reserving the spare arrays")) return false;
-    std::vector<uint32_t> order(n), refs;
-    uint64_t nRecs = 0;
-    if (clustered) {
-        gpuart_ploc_result res;
-        if (!Check(gpuart_ploc_run_host(Clusterer, &edited, &spare, order.data(), &res), "building the edited tree", gpuart_ploc_last_error)) return false;
-        nRecs = res.n_recs;
-        spare.root_ref = res.root_ref; spare.max_depth = res.max_depth;
-        memcpy(spare.root_min, res.root_min, 12); memcpy(spare.root_max, res.root_max, 12);
-        spare.box_slack = res.subnormal ? __builtin_inff() : 0.0f;
-        refs.resize(2 * nRecs);
-        if (nRecs) {  // the two ref words of every record: word 3 of its first two quads
-            std::unique_ptr<uint32_t[]> recs(new uint32_t[16 * nRecs]);
-            if (hipMemcpy(recs.get(), spare.recs, 64 * nRecs, hipMemcpyDeviceToHost) != hipSuccess) {
-                std::cerr << "Renderer: EditPrimitives: reading the built records back failed." << std::endl;
-                return false;
-            }
-            for (uint64_t r = 0; r < nRecs; r++) { refs[2 * r] = recs[16 * r + 3]; refs[2 * r + 1] = recs[16 * r + 7]; }
-        }
-    } else {
-        gpuart_build_result res;
-        if (!Check(gpuart_build_run_host(Builder, &edited, &spare, order.data(), &res), "building the edited tree", gpuart_build_last_error)) return false;
-        nRecs = res.n_recs;
-        spare.root_ref = res.root_ref; spare.max_depth = res.max_depth;
-        memcpy(spare.root_min, res.root_min, 12); memcpy(spare.root_max, res.root_max, 12);
-        spare.box_slack = res.subnormal ? __builtin_inff() : 0.0f;
-    }
-    spare.n_recs = nRecs;
+    BuiltTree built;
+    if (!BuildIntoSpare(edited, clustered, true, false, "EditPrimitives", "building the edited tree", spare, built)) return false;
     spare.n_prims = n;
-    const auto t1 = std::chrono::high_resolution_clock::now();
+    const auto t1 = Now();
     // (from here the host tree changes: a tree or a device that cannot follow is an inconsistency, not a refusal)
-    if (!Tree.EditPrimitives(remove, nRemove, types.data(), payloads.data(), nAdd) ||
-        !(clustered ? Tree.AdoptTopology(order.data(), refs.data(), nRecs) : Tree.RebuildMorton(nullptr, order.data()))) {
+    if (!Tree.EditPrimitives(remove, nRemove, types.data(), payloads.data(), nAdd) || !TreeFollows(clustered, built)) {
         std::cerr << "Renderer: EditPrimitives: the device's tree is not the contract's over the edited primitives." << std::endl;
         return IsOK = false;
     }
-    const auto t2 = std::chrono::high_resolution_clock::now();
+    const auto t2 = Now();
     if (!Check(gpuart_hip_scene_replaced(Backend, &spare, er.type_mask), "adopting the edited tree")) return IsOK = false;
-    const auto t3 = std::chrono::high_resolution_clock::now();
-    LastRebuildMs[0] = std::chrono::duration<double, std::milli>(t3 - t0).count();
-    LastRebuildMs[1] = std::chrono::duration<double, std::milli>(t2 - t1).count();
+    LastRebuildMs[0] = Ms(t0, Now());
+    LastRebuildMs[1] = Ms(t1, t2);
     if (source) {
         source->resize(n);
-        for (uint64_t p = 0; p < n; p++) (*source)[p] = (uint32_t)from[order[p]];
+        for (uint64_t p = 0; p < n; p++) (*source)[p] = (uint32_t)from[built.order[p]];
     }
-    RefitGeneration = 0;  // the refit handle is bound to the old arrays: the next UpdatePrimitives binds again
-    GBufferValid = false;
-    EdgeListValid = false;
-    ResetPathTracing();
+    TreeChanged(true);
     return true;
 }
 
@@ -517,7 +510,7 @@ bool Renderer::TreeCost(double *cost) {
     if (!IsOK || !cost) return false;
     gpuart_hip_scene scene;
     if (!Check(gpuart_hip_scene_device(Backend, &scene), "looking up the scene's device arrays")) return false;
-    if (!Builder && !Check(gpuart_build_create(Device, &Builder), "creating the build handle", gpuart_build_last_error)) return false;
+    if (!Ensure(Builder, BD)) return false;
     return Check(gpuart_build_cost(Builder, &scene, cost), "measuring the tree's cost", gpuart_build_last_error);
 }
 
@@ -642,26 +635,6 @@ bool Renderer::ReadRadiance(float *rgba, bool normalized) {
 }
 
 namespace {
-/// What the Renderer needs of an image library to make a handle, wait for it and report its failures.
-template <class H>
-struct Lib {
-    int (*create)(int, H **);
-    int (*finish)(H *);
-    const char *(*lastError)(void);
-    const char *creating;
-};
-const Lib<gpuart_denoise> DN{gpuart_denoise_create, gpuart_denoise_finish, gpuart_denoise_last_error, "creating the denoiser"};
-const Lib<gpuart_temporal> TP{gpuart_temporal_create, gpuart_temporal_finish, gpuart_temporal_last_error, "creating the temporal accumulator"};
-const Lib<gpuart_temporal> TPM{gpuart_temporal_create, gpuart_temporal_finish, gpuart_temporal_last_error, "creating the moments' temporal accumulator"};
-const Lib<gpuart_moments> MO{gpuart_moments_create, gpuart_moments_finish, gpuart_moments_last_error, "creating the moments library's handle"};
-const Lib<gpuart_temporal> TPF{gpuart_temporal_create, gpuart_temporal_finish, gpuart_temporal_last_error, "creating the fast history's temporal accumulator"};
-const Lib<gpuart_antilag> AL{gpuart_antilag_create, gpuart_antilag_finish, gpuart_antilag_last_error, "creating the anti-lag library's handle"};
-const Lib<gpuart_converge> CV{gpuart_converge_create, gpuart_converge_finish, gpuart_converge_last_error, "creating the convergence estimator"};
-const Lib<gpuart_adaptive> AD{gpuart_adaptive_create, gpuart_adaptive_finish, gpuart_adaptive_last_error, "creating the adaptive estimator"};
-const Lib<gpuart_refine> RF{gpuart_refine_create, gpuart_refine_finish, gpuart_refine_last_error, "creating the variance-guided filter"};
-const Lib<gpuart_edges> ED{gpuart_edges_create, gpuart_edges_finish, gpuart_edges_last_error, "creating the edge resolve's handle"};
-const Lib<gpuart_despeckle> DS{gpuart_despeckle_create, gpuart_despeckle_finish, gpuart_despeckle_last_error, "creating the firefly clamp's handle"};
-const Lib<gpuart_display> DP{gpuart_display_create, gpuart_display_finish, gpuart_display_last_error, "creating the display stage"};
 bool finite(float x) { return x - x == 0.0f; }
 bool checkHip(hipError_t e, const char *what) {
     if (e == hipSuccess) return true;
@@ -690,11 +663,6 @@ struct AntiLagBuffers {
     AntiLagBuffers(void *mem, size_t n) : fast((float *)mem), len((float *)((char *)mem + n * 16)), alpha((float *)((char *)mem + n * 20)) {}
 };
 }  // namespace
-
-template <class H, class L>
-bool Renderer::Ensure(H *&h, const L &lib) {
-    return h || Check(lib.create(Device, &h), lib.creating, lib.lastError);
-}
 
 template <class H, class L>
 bool Renderer::Run(int status, H *h, const L &lib, const char *what) {

@@ -13,6 +13,7 @@
 #ifndef GPUART_RENDERER_H
 #define GPUART_RENDERER_H
 
+#include <chrono>
 #include <cstdint>
 #include <random>
 #include <vector>
@@ -371,7 +372,26 @@ private:
     gpuart_build *Builder = nullptr;      ///< made by the first RebuildTree or TreeCost
     gpuart_ploc *Clusterer = nullptr;     ///< made by the first RebuildTree(TREE_CLUSTERED)
     gpuart_edit *Editor = nullptr;        ///< made by the first EditPrimitives
-    bool RebuildClustered(std::vector<uint32_t> *newToOld);
+    /// What BuildIntoSpare hands out beside the spare set's descriptor: new_to_old, the two ref words of each of the nRecs records (the
+    /// clustered build's; the Morton order implies its own) and when the device run returned.
+    struct BuiltTree {
+        std::vector<uint32_t> order, refs;
+        uint64_t nRecs = 0;
+        std::chrono::high_resolution_clock::time_point ran;
+    };
+    /// The opening refusal of RebuildTree and EditPrimitives (`fn`): an empty scene, irregular boxes, or a host tree of another count is not `done`.
+    bool RefusesTreeChange(const gpuart_hip_scene &scene, const char *fn, const char *done);
+    bool EnsureBuilder(bool clustered);
+    /// The tree of `src`'s primitives built into the spare set, which is reserved first (`withPrims`: with primitive arrays of its own, for
+    /// a list that is not the scene's) and then described by `spare`; `commit`: the view is committed between making the handle and the
+    /// run. Failures are reported under `what` (the run) and `fn` (the read-back of the refs) and leave everything as it was.
+    bool BuildIntoSpare(const gpuart_hip_scene &src, bool clustered, bool withPrims, bool commit, const char *fn, const char *what, gpuart_hip_scene &spare,
+                        BuiltTree &built);
+    /// The host tree follows the device's: the Morton order checked and rebuilt, or the clustered topology checked and adopted.
+    bool TreeFollows(bool clustered, const BuiltTree &built);
+    /// After the device's primitives or tree changed: the G-buffer, the edge list and the accumulator are those of another scene; with
+    /// `newArrays` the refit handle is bound to the old ones, and the next UpdatePrimitives binds again.
+    void TreeChanged(bool newArrays);
     double LastRebuildMs[2] = {0, 0};
     BoundingVolumesHierarchy Tree;
     struct { unsigned width, height; } Viewport{0, 0};
@@ -392,7 +412,7 @@ private:
     void CommitTemporalView();
     /// Temporal, TemporalMoments, Moments and MomentsMem for the tile, made where missing.
     bool EnsureVarianceHandles();
-    /// Makes the handle `h` of the image library `lib` if it is missing.
+    /// Makes the handle `h` of the image or tree library `lib` if it is missing.
     template <class H, class L> bool Ensure(H *&h, const L &lib);
     /// Run, then wait for that handle: `status` is what the call just issued on `h` returned; both failures are reported under `what`.
     template <class H, class L> bool Run(int status, H *h, const L &lib, const char *what);

@@ -6,7 +6,8 @@
 // Each library is one translation unit that includes this once, so everything sits in an anonymous namespace and every library has its
 // own copy (its own last error). The checks take the library's name: every message starts with it. DESIGN.md "The image libraries'
 // scaffold" says what stays in each library. refit/refit.hip, treebuild/build.hip, ploc/ploc.hip and edit/edit.hip, which are no image
-// libraries (they work on the uploaded tree), take the last error, HIP_TRY, the handle, the checks and the grow-only buffer from here too.
+// libraries (they work on the uploaded tree), take the last error, HIP_TRY, the handle, the checks and the grow-only buffer from here too;
+// what those four share beyond that is in tree/tree_lib.h.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,21 +1,19 @@
 // ploc.hip — libgpuart_ploc.so (gfx950): the tree of an uploaded scene rebuilt on the device by locally-ordered clustering, as
 // include/gpuart_ploc.h states it. Built without flushing fp32 denormals and without contraction, so that NumPy float32
-// (tests/ploc_ref.py) restates the distances and the boxes exactly. The keys are the Morton rule's (hip/tree_rule.h), the descriptor
-// checks, the Status and the root's box the refit's (refit/box_pass.h). DESIGN.md "Clustered rebuild" describes the launches; nothing
+// (tests/ploc_ref.py) restates the distances and the boxes exactly. The keys are the Morton rule's (hip/tree_rule.h); the argument checks,
+// the keys' kernel and their sort the tree libraries' (tree/tree_lib.h); the Status and the root's box the refit's (refit/box_pass.h). DESIGN.md "Clustered rebuild" describes the launches; nothing
 // is handed between workgroups inside a launch, and atomics only count.
 //
 // A node has an id: the initial cluster of sorted position p is node p (one primitive), the k-th merge of the whole build makes node
 // n + k (k from a scan of the iteration's new-node flags, on top of the merges of the iterations before). Per id: its box, its parent
 // (with PARENT_LOWER when it is the lower child), the records and the primitives of its subtree; per merged node its two children.
-#include <algorithm>
-#include <cstdlib>
-#include <cstring>
 #include <vector>
 
-#include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
 #include "../image/image_lib.h"
+#define TREE_LIB_MORTON
+#include "../tree/tree_lib.h"
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wunused-function"  // box_pass.h's level kernel is not launched here: every box is computed when its node is made
 #include "../refit/box_pass.h"
@@ -27,7 +25,6 @@ namespace {
 const char LIB[] = "ploc";
 
 constexpr uint32_t RADIUS = GPUART_PLOC_RADIUS, MAX_ITERATIONS = GPUART_PLOC_MAX_ITERATIONS;
-constexpr uint32_t PARENT_LOWER = 0x80000000u;  ///< a parent link: this bit when the node is its parent's lower child
 constexpr uint32_t BOX_STRIDE = 7;              ///< floats per staged box in LDS (6 and one of padding: an odd stride has no bank conflicts)
 
 /// After an iteration: the clusters left and the merged nodes made so far. Iteration t reads state[t & 1] and writes state[(t + 1) & 1].
@@ -42,17 +39,7 @@ struct Extra {
     uint32_t broken;  ///< a parent link that leads nowhere, or a position out of range (cannot happen)
 };
 
-struct Box3 { float lo[3], hi[3]; };
-
-// 1. One thread per primitive: its 63-bit key from its box and the root box, and its ordinal as the sort's value.
-__global__ void __launch_bounds__(256) k_pl_keys(const float *pbox, uint32_t n, Box3 root, uint64_t *keys, uint32_t *vals) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    const float *b = pbox + 6 * (size_t)i;
-    keys[i] = tree_rule::morton_key(b, b + 3, root.lo, root.hi);
-    vals[i] = i;
-}
-
+// 1. The keys and their sort: tree_lib.h's morton_sort.
 // 2. One thread per sorted position p: initial cluster p = node p, one primitive with that primitive's box.
 __global__ void __launch_bounds__(256) k_pl_init(const float *pbox, const uint32_t *sorted, uint32_t n, float *nbox, uint32_t *parent, uint32_t *nrec,
                                                  uint32_t *npr, uint32_t *cnode, Extra *ex) {
@@ -188,14 +175,7 @@ __global__ void __launch_bounds__(256) k_pl_permute(const float4 *src, const flo
         const uint32_t link = parent[p];
         if (npr[link & ~PARENT_LOWER] == 2) cnt = link >> 31 ? 2u : 0u;
     }
-    const float4 *s = src + 3 * (size_t)old;
-    float4 r0 = s[0];
-    r0.w = __uint_as_float((__float_as_uint(r0.w) & 3u) | cnt << 2);
-    float4 *d = dst + 3 * (size_t)at;
-    d[0] = r0; d[1] = s[1]; d[2] = s[2];
-    const float *sb = src_box + 6 * (size_t)old;
-    float *db = dst_box + 6 * (size_t)at;
-    for (int k = 0; k < 6; k++) db[k] = sb[k];
+    move_prim(src, src_box, old, cnt, dst, dst_box, at);
     new_to_old[at] = old;
 }
 
@@ -234,8 +214,7 @@ struct gpuart_ploc : ImageHandle {
     DeviceBuffer scratch;    ///< keys in and out, ordinals, the nodes' arrays, the cluster arrays, flags and their scan
     DeviceBuffer temp;       ///< the sort's and the scan's
     DeviceBuffer staging;    ///< run_host: the permutation
-    hipEvent_t ev[7] = {};
-    double step_ms[6] = {0, 0, 0, 0, 0, 0};
+    StepTimer timer;         ///< reported as keys, sort, iterations (with the initial clusters), number, emit, permute
 };
 
 extern "C" {
@@ -243,66 +222,30 @@ extern "C" {
 const char *gpuart_ploc_last_error(void) { return g_last_error.c_str(); }
 
 int gpuart_ploc_create(int device, gpuart_ploc **out) {
-    if (int rc = create_handle(LIB, device, out)) return rc;
-    gpuart_ploc *h = *out;
-    *out = nullptr;
-    hipError_t e = hipMalloc((void **)&h->extra, sizeof(Extra));
-    for (int k = 0; k < 7 && e == hipSuccess; k++) e = hipEventCreate(&h->ev[k]);
-    if (e != hipSuccess) {
-        gpuart_ploc_destroy(h);
-        return fail(GPUART_HIP_ERR_DEVICE, std::string("ploc: allocating the status: ") + hipGetErrorString(e));
-    }
-    *out = h;
-    return 0;
+    return create_tree_handle(LIB, device, out, gpuart_ploc_destroy, [](gpuart_ploc *h) {
+        const hipError_t e = hipMalloc((void **)&h->extra, sizeof(Extra));
+        return e == hipSuccess ? h->timer.create(6) : e;
+    });
 }
 
 int gpuart_ploc_destroy(gpuart_ploc *h) {
     if (!h) return 0;
     destroy_handle(h, {h->extra, h->scratch.mem, h->temp.mem, h->staging.mem});
-    for (hipEvent_t e : h->ev)
-        if (e) (void)hipEventDestroy(e);
+    h->timer.destroy();
     delete h;
     return 0;
 }
 
 int gpuart_ploc_finish(gpuart_ploc *h) { return finish_handle(LIB, h); }
 
-int gpuart_ploc_step_ms(gpuart_ploc *h, double ms[6]) {
-    if (int rc = check_handle(LIB, h)) return rc;
-    if (!ms) return fail(GPUART_HIP_ERR_ARG, "ploc: ms is NULL");
-    memcpy(ms, h->step_ms, sizeof h->step_ms);
-    return 0;
-}
+int gpuart_ploc_step_ms(gpuart_ploc *h, double ms[6]) { return step_ms(LIB, h, ms); }
 
 int gpuart_ploc_run(gpuart_ploc *h, const gpuart_hip_scene *src, const gpuart_hip_scene *dst, uint32_t *new_to_old, gpuart_ploc_result *result) {
-    if (int rc = check_handle(LIB, h)) return rc;
-    if (!src) return fail(GPUART_HIP_ERR_ARG, "ploc: src is NULL");
-    if (int rc = check_descriptor(src, LIB, "src", "rebuilt")) return rc;
-    if (misaligned({src->recs, src->prims}, 16) || misaligned({src->prim_boxes}, 4)) return fail(GPUART_HIP_ERR_ARG, "ploc: src: misaligned arrays");
-    if (!dst) return fail(GPUART_HIP_ERR_ARG, "ploc: dst is NULL");
-    if (dst->layout != 1) return fail(GPUART_HIP_ERR_ARG, "ploc: dst: unknown layout " + std::to_string(dst->layout));
+    uint32_t word[2];
+    if (int rc = check_build(LIB, h, src, dst, new_to_old, [](size_t n) { return n - 1; }, word)) return rc;
     const size_t n = src->n_prims, room = n - 1;
-    if (!tree_rule::box_ok(src->root_min, src->root_max)) return fail(GPUART_HIP_ERR_ARG, "ploc: the root box is not finite and ordered");
-    if (!new_to_old || misaligned({new_to_old}, 4)) return fail(GPUART_HIP_ERR_ARG, "ploc: new_to_old is NULL or misaligned");
-    if (!dst->prims || !dst->prim_boxes || (room && !dst->recs) || misaligned({dst->recs, dst->prims}, 16) || misaligned({dst->prim_boxes}, 4))
-        return fail(GPUART_HIP_ERR_ARG, "ploc: dst's arrays are NULL or misaligned");
-    if (dst->n_prims < n || dst->n_recs < room)
-        return fail(GPUART_HIP_ERR_ARG, "ploc: dst is too small: " + std::to_string(dst->n_recs) + " records and " + std::to_string(dst->n_prims) +
-                                            " primitives for " + std::to_string(room) + " and " + std::to_string(n));
-    const struct { const void *p; size_t bytes; } S[3] = {{src->recs, src->n_recs * 64}, {src->prims, n * 48}, {src->prim_boxes, n * 24}},
-                                                  D[4] = {{dst->recs, room * 64}, {dst->prims, n * 48}, {dst->prim_boxes, n * 24}, {new_to_old, n * 4}};
-    for (const auto &s : S)
-        for (const auto &d : D)
-            if (s.bytes && d.bytes && overlaps(s.p, s.bytes, d.p, d.bytes)) return fail(GPUART_HIP_ERR_ARG, "ploc: dst's arrays alias src's");
-    for (int a = 0; a < 4; a++)
-        for (int b = a + 1; b < 4; b++)
-            if (D[a].bytes && D[b].bytes && overlaps(D[a].p, D[a].bytes, D[b].p, D[b].bytes)) return fail(GPUART_HIP_ERR_ARG, "ploc: dst's arrays overlap");
-    HIP_TRY(hipSetDevice(h->device));
     uint32_t root_ref = 0;
-    if (n <= 2) {  // the root is a leaf: its ref from the primitives' type words. An empty scene keeps one dummy record of count 0 (converter.h)
-        uint32_t word[2] = {0, 0};
-        for (size_t k = 0; k < n; k++) HIP_TRY(hipMemcpy(&word[k], (const char *)src->prims + 48 * k + 12, 4, hipMemcpyDeviceToHost));
-        if (n == 1 && (word[0] >> 2) == 0) return fail(GPUART_HIP_ERR_ARG, "ploc: src: an empty scene is not rebuilt");
+    if (n <= 2) {  // the root is a leaf: its ref from the primitives' type words
         const uint32_t tri = (uint32_t)prim_rule::TRIANGLE;
         root_ref = tree_rule::leaf_ref(0, (uint32_t)n, (word[0] & 3u) == tri && (n == 1 || (word[1] & 3u) == tri));
     }
@@ -317,27 +260,12 @@ int gpuart_ploc_run(gpuart_ploc *h, const gpuart_hip_scene *src, const gpuart_hi
     uint32_t *lower = rec_of + 2 * N, *upper = lower + N;
     uint32_t *cnode[2] = {upper + N, upper + 2 * N};
     uint32_t *nn = cnode[1] + N, *first_of = nn + N, *depth_of = first_of + 2 * N;
-    size_t sort_bytes = 0, scan_bytes = 0;
-    HIP_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys_in, keys, vals_in, sorted, n, 0, 63, h->stream));
+    size_t scan_bytes = 0;  // (the scan shares the sort's temporary storage)
     HIP_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, flags, scan, (uint64_t)0, n, rocprim::plus<uint64_t>(), h->stream));
-    const size_t temp_bytes = std::max(sort_bytes, scan_bytes);
-    if (int rc = ensure(h->stream, h->temp, temp_bytes + 16)) return rc;
-
-    uint32_t top_depth = 0;
-    if (const char *e = getenv("GPUART_HIP_TOP_DEPTH")) top_depth = (uint32_t)atoi(e);
-    Box3 root;
-    memcpy(root.lo, src->root_min, 12); memcpy(root.hi, src->root_max, 12);
-    const auto blocks = [](size_t items) { return (uint32_t)((items + 255) / 256); };
-    int at = 0;
-    const auto mark = [&] { return hipEventRecord(h->ev[at++], h->stream); };
+    h->timer.start(h->stream);
 
     HIP_TRY(hipMemsetAsync(h->extra, 0, sizeof(Extra), h->stream));
-    HIP_TRY(mark());
-    k_pl_keys<<<blocks(n), 256, 0, h->stream>>>((const float *)src->prim_boxes, (uint32_t)n, root, keys_in, vals_in);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(mark());
-    HIP_TRY(rocprim::radix_sort_pairs(h->temp.mem, sort_bytes, keys_in, keys, vals_in, sorted, n, 0, 63, h->stream));
-    HIP_TRY(mark());
+    if (int rc = morton_sort(h->timer, h->temp, scan_bytes, src, keys_in, keys, vals_in, sorted)) return rc;
     k_pl_init<<<blocks(n), 256, 0, h->stream>>>((const float *)src->prim_boxes, sorted, (uint32_t)n, nbox, parent, nrec, npr, cnode[0], h->extra);
     HIP_TRY(hipGetLastError());
     State state = {(uint32_t)n, 0};
@@ -352,7 +280,7 @@ int gpuart_ploc_run(gpuart_ploc *h, const gpuart_hip_scene *src, const gpuart_hi
         HIP_TRY(hipGetLastError());
         k_pl_merge<<<g, 256, 0, h->stream>>>(nn, c, flags);
         HIP_TRY(hipGetLastError());
-        size_t bytes = temp_bytes;
+        size_t bytes = scan_bytes;
         HIP_TRY(rocprim::exclusive_scan(h->temp.mem, bytes, flags, scan, (uint64_t)0, c, rocprim::plus<uint64_t>(), h->stream));
         k_pl_scatter<<<g, 256, 0, h->stream>>>(cnode[t], nn, flags, scan, c, (uint32_t)n, &h->extra->state[t], &h->extra->state[t ^ 1u], nbox, lower, upper,
                                                  parent, nrec, npr, cnode[t ^ 1u]);
@@ -364,25 +292,25 @@ int gpuart_ploc_run(gpuart_ploc *h, const gpuart_hip_scene *src, const gpuart_hi
         if (state.c == 0 || state.c >= c || state.nodes >= n)
             return fail(GPUART_HIP_ERR_DEVICE, "ploc: an iteration left " + std::to_string(state.c) + " clusters of " + std::to_string(c));
     }
-    HIP_TRY(mark());
+    HIP_TRY(h->timer.mark());
     const uint32_t total = state.nodes, root_id = n > 1 ? (uint32_t)n + total - 1 : 0u;  // the last iteration merges the last two clusters
     float4 *drecs = (float4 *)dst->recs, *dprims = (float4 *)dst->prims;
     float *dbox = (float *)dst->prim_boxes;
     k_pl_number<<<blocks(n + total), 256, 0, h->stream>>>((uint32_t)n, total, root_id, parent, lower, nrec, npr, rec_of, first_of, depth_of, h->extra);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(mark());
+    HIP_TRY(h->timer.mark());
     k_pl_permute<<<blocks(n), 256, 0, h->stream>>>((const float4 *)src->prims, (const float *)src->prim_boxes, sorted, (uint32_t)n, parent, npr, first_of, dprims,
                                                     dbox, new_to_old, h->extra);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(mark());
+    HIP_TRY(h->timer.mark());
     if (total) {
-        k_pl_emit<<<blocks(total), 256, 0, h->stream>>>((uint32_t)n, total, (uint32_t)room, lower, upper, npr, rec_of, first_of, depth_of, nbox, dprims, top_depth,
+        k_pl_emit<<<blocks(total), 256, 0, h->stream>>>((uint32_t)n, total, (uint32_t)room, lower, upper, npr, rec_of, first_of, depth_of, nbox, dprims, top_depth(),
                                                         drecs, h->extra);
         HIP_TRY(hipGetLastError());
     }
     k_rf_root<<<1, 64, 0, h->stream>>>(drecs, dprims, dbox, root_ref, &h->extra->st);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(mark());
+    HIP_TRY(h->timer.mark());
     Extra ex;
     HIP_TRY(hipMemcpyAsync(&ex, h->extra, sizeof ex, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -391,13 +319,8 @@ int gpuart_ploc_run(gpuart_ploc *h, const gpuart_hip_scene *src, const gpuart_hi
         HIP_TRY(hipMemsetAsync((char *)dst->recs + (size_t)ex.n_recs * 64, 0, (room - ex.n_recs) * 64, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
     }
-    // keys, sort, iterations (with the initial clusters), number, emit, permute
-    const int from[6] = {0, 1, 2, 3, 5, 4};
-    for (int k = 0; k < 6; k++) {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, h->ev[from[k]], h->ev[from[k] + 1]));
-        h->step_ms[k] = ms;
-    }
+    const int from[6] = {0, 1, 2, 3, 5, 4};  // keys, sort, iterations (with the initial clusters), number, emit, permute
+    if (int rc = h->timer.read(from)) return rc;
     if (result) {
         result->n_recs = ex.n_recs;
         result->root_ref = root_ref;
@@ -411,14 +334,7 @@ int gpuart_ploc_run(gpuart_ploc *h, const gpuart_hip_scene *src, const gpuart_hi
 }
 
 int gpuart_ploc_run_host(gpuart_ploc *h, const gpuart_hip_scene *src, const gpuart_hip_scene *dst, uint32_t *new_to_old, gpuart_ploc_result *result) {
-    if (int rc = check_handle(LIB, h)) return rc;
-    if (!src || !new_to_old || !src->n_prims) return fail(GPUART_HIP_ERR_ARG, "ploc: src or new_to_old is NULL, or the scene is empty");
-    HIP_TRY(hipSetDevice(h->device));
-    if (int rc = ensure(h->stream, h->staging, src->n_prims * sizeof(uint32_t))) return rc;
-    if (int rc = gpuart_ploc_run(h, src, dst, (uint32_t *)h->staging.mem, result)) return rc;
-    HIP_TRY(hipMemcpyAsync(new_to_old, h->staging.mem, src->n_prims * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return 0;
+    return run_staged(LIB, h, gpuart_ploc_run, src, dst, new_to_old, result);
 }
 
 }  // extern "C"

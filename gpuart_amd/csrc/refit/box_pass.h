@@ -1,32 +1,15 @@
 // box_pass.h — the box pass of a tree in device memory, shared by refit/refit.hip and treebuild/build.hip (each one translation unit that
-// includes this once, after image/image_lib.h): one launch of k_rf_level per tree level, deepest first, then k_rf_root. A leaf's box is its
+// includes this once, after tree/tree_lib.h): one launch of k_rf_level per tree level, deepest first, then k_rf_root. A leaf's box is its
 // primitives' boxes folded in leaf order, an interior node's its lower child's folded with its upper child's (include/gpuart_refit.h).
 // Nothing is handed between workgroups inside a launch: a level reads what the launch before it wrote (DESIGN.md "Refit").
-// Before it, what both libraries ask of the gpuart_hip_scene they are given.
+// ploc/ploc.hip takes the Status and k_rf_root from here.
 #pragma once
-#include "../hip/prim_rule.h"
-#include "../hip/tree_rule.h"
 
 namespace {
 
 #define RF_FN __device__ __forceinline__
 
-using tree_rule::REF_INDEX;
-using tree_rule::REF_LEAF;
-
-/// The checks of a scene descriptor whose tree is to be refitted or rebuilt (`done`: "refitted", "rebuilt"). Every message starts with
-/// `lib`, and names the argument where the library takes more than one descriptor (`arg`, else "").
-inline int check_descriptor(const gpuart_hip_scene *s, const char *lib, const char *arg, const char *done) {
-    const std::string w = std::string(lib) + ": " + (*arg ? std::string(arg) + ": " : "");
-    if (s->layout != 1) return fail(GPUART_HIP_ERR_ARG, w + "unknown layout " + std::to_string(s->layout));
-    if (s->exact_boxes) return fail(GPUART_HIP_ERR_ARG, w + "a tree with irregular boxes (or boxes that do not bound their contents) is not " + done);
-    if (!s->prims || !s->prim_boxes || !s->n_prims || (s->n_recs && !s->recs) || s->n_prims > REF_INDEX || s->n_recs > REF_INDEX)
-        return fail(GPUART_HIP_ERR_ARG, w + "the scene's arrays or counts are empty or out of range");
-    return 0;
-}
-
-/// What the device sequence leaves for the host, in device memory; all zero before a run. `refused` = ~(4 x index + why) of the first
-/// offending update — the largest over the updates (atomicMax) —, 0 while no update is refused.
+/// What the device sequence leaves for the host, in device memory; all zero before a run. `refused`: tree_lib.h's refusal word.
 struct Status {
     uint32_t refused;
     uint32_t subnormal;  ///< some plane written fails tree_rule::plane_ok (a subnormal number is kept here, and fails it)

@@ -2,12 +2,13 @@
 // include/gpuart_refit.h states it. Built without flushing fp32 denormals and without contraction: a box plane is copied, a triangle's
 // edge subtracted, exactly as the host uploader does (csrc/hip/converter.h) and tests/refit_ref.py restates in NumPy float32.
 // DESIGN.md "Refit" describes the launches and why nothing is handed between workgroups inside one. The box pass (k_rf_level, k_rf_root)
-// is in box_pass.h, which treebuild/build.hip shares.
+// is in box_pass.h, which treebuild/build.hip shares; the descriptor's checks and the refusal word are the tree libraries' (tree/tree_lib.h).
 #include <cmath>
 #include <cstring>
 #include <vector>
 
 #include "../image/image_lib.h"
+#include "../tree/tree_lib.h"
 #include "box_pass.h"
 #include "prim_pack.h"
 #include "gpuart_refit.h"
@@ -17,7 +18,6 @@ namespace {
 const char LIB[] = "refit";
 
 constexpr uint32_t NONE = GPUART_REFIT_NO_UPDATE;
-enum { WHY_ORDER = 1, WHY_RANGE = 2, WHY_RULE = 3 };  ///< low two bits of the status word
 
 // 1. One thread per update: ordinals ascending and in range, the payload inside the rule for the type the primitive has.
 __global__ void __launch_bounds__(256) k_rf_validate(const uint32_t *ord, const float4 *payload, uint32_t n, const float4 *prims, uint32_t n_prims,
@@ -34,7 +34,7 @@ __global__ void __launch_bounds__(256) k_rf_validate(const uint32_t *ord, const 
         const uint32_t type = __float_as_uint(prims[3 * (size_t)p].w) & 3u;
         if (!prim_rule::prim_ok(type, d)) why = WHY_RULE;
     }
-    if (why) atomicMax(&st->refused, ~(4u * i + why));
+    if (why) refuse(&st->refused, i, why);
 }
 
 // 2. One thread per update: the three float4 of the record by the uploader's arithmetic (prim_pack.h), word 3 of the first —
@@ -96,10 +96,9 @@ int run_device(gpuart_refit *h, const uint32_t *ord, const float4 *payload, uint
     float *pbox = (float *)s.prim_boxes;
     HIP_TRY(hipMemsetAsync(h->status, 0, sizeof(Status), h->stream));
     if (n) {
-        const uint32_t blocks = (n + 255u) / 256u;
-        k_rf_validate<<<blocks, 256, 0, h->stream>>>(ord, payload, n, prims, (uint32_t)s.n_prims, h->status);
+        k_rf_validate<<<blocks(n), 256, 0, h->stream>>>(ord, payload, n, prims, (uint32_t)s.n_prims, h->status);
         HIP_TRY(hipGetLastError());
-        k_rf_update<<<blocks, 256, 0, h->stream>>>(ord, payload, n, prims, pbox, h->status);
+        k_rf_update<<<blocks(n), 256, 0, h->stream>>>(ord, payload, n, prims, pbox, h->status);
         HIP_TRY(hipGetLastError());
     }
     const uint32_t *order = (const uint32_t *)h->order.mem;
@@ -113,20 +112,17 @@ int run_device(gpuart_refit *h, const uint32_t *ord, const float4 *payload, uint
     Status st;
     HIP_TRY(hipMemcpyAsync(&st, h->status, sizeof st, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    const uint32_t key = ~st.refused;  // 4 x index + why
     if (result) {
         result->status = st.refused ? GPUART_HIP_ERR_ARG : 0;
-        result->first_bad = st.refused ? key >> 2 : NONE;
+        result->first_bad = st.refused ? refused_index(st.refused) : NONE;
         result->subnormal = st.subnormal;
         memcpy(result->root_min, st.refused ? s.root_min : st.root_min, 12);
         memcpy(result->root_max, st.refused ? s.root_max : st.root_max, 12);
     }
     if (st.refused) {
-        static const char *const WHY[4] = {"", "its ordinal does not exceed the one before it (ordinals are strictly ascending)",
-                                           "its ordinal is not below the number of primitives",
-                                           "its payload is outside the primitive rule (a word that is not finite or beyond 2^20, a negative radius or length, "
-                                           "or a cone's derived constants that contradict its centres and radii)"};
-        return fail(GPUART_HIP_ERR_ARG, "refit: update " + std::to_string(key >> 2) + " refused: " + WHY[key & 3u] + "; nothing was written");
+        const char *why = refused_why(st.refused, "its payload is outside the primitive rule (a word that is not finite or beyond 2^20, a negative radius or length, "
+                                                  "or a cone's derived constants that contradict its centres and radii)");
+        return fail(GPUART_HIP_ERR_ARG, "refit: update " + std::to_string(refused_index(st.refused)) + " refused: " + why + "; nothing was written");
     }
     memcpy(h->scene.root_min, st.root_min, 12);
     memcpy(h->scene.root_max, st.root_max, 12);
@@ -150,16 +146,7 @@ extern "C" {
 const char *gpuart_refit_last_error(void) { return g_last_error.c_str(); }
 
 int gpuart_refit_create(int device, gpuart_refit **out) {
-    if (int rc = create_handle(LIB, device, out)) return rc;
-    gpuart_refit *h = *out;
-    *out = nullptr;
-    const hipError_t e = hipMalloc((void **)&h->status, sizeof(Status));
-    if (e != hipSuccess) {
-        gpuart_refit_destroy(h);
-        return fail(GPUART_HIP_ERR_DEVICE, std::string("refit: allocating the status: ") + hipGetErrorString(e));
-    }
-    *out = h;
-    return 0;
+    return create_tree_handle(LIB, device, out, gpuart_refit_destroy, [](gpuart_refit *h) { return hipMalloc((void **)&h->status, sizeof(Status)); });
 }
 
 int gpuart_refit_destroy(gpuart_refit *h) {
@@ -175,7 +162,7 @@ int gpuart_refit_bind(gpuart_refit *h, const gpuart_hip_scene *s) {
     if (int rc = check_handle(LIB, h)) return rc;
     if (!s) return fail(GPUART_HIP_ERR_ARG, "refit: scene is NULL");
     h->bound = false;
-    if (int rc = check_descriptor(s, LIB, "", "refitted")) return rc;
+    if (int rc = check_descriptor(s, LIB, "", "refitted", true)) return rc;
     HIP_TRY(hipSetDevice(h->device));
     const size_t n_recs = s->n_recs, n_prims = s->n_prims;
     // every leaf's count, which its first primitive carries, and the records
@@ -183,7 +170,7 @@ int gpuart_refit_bind(gpuart_refit *h, const gpuart_hip_scene *s) {
     std::vector<uint32_t> tw(n_prims);
     if (n_recs) HIP_TRY(hipMemcpy(recs.data(), s->recs, recs.size() * 4, hipMemcpyDeviceToHost));
     if (int rc = ensure(h->stream, h->staging, n_prims * 4)) return rc;
-    k_rf_type_words<<<(uint32_t)((n_prims + 255) / 256), 256, 0, h->stream>>>((const float4 *)s->prims, (uint32_t)n_prims, (uint32_t *)h->staging.mem);
+    k_rf_type_words<<<blocks(n_prims), 256, 0, h->stream>>>((const float4 *)s->prims, (uint32_t)n_prims, (uint32_t *)h->staging.mem);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(tw.data(), h->staging.mem, n_prims * 4, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));

@@ -1,16 +1,15 @@
 // build.hip — libgpuart_build.so (gfx950): the tree of an uploaded scene rebuilt on the device in Morton order, as include/gpuart_build.h
 // states it, and the cost measure of a tree. Built without flushing fp32 denormals and without contraction, so that NumPy float32
 // (tests/build_ref.py) restates the keys and the boxes exactly. The topology is Karras' parallel construction (every interior node
-// finds its range and split from the sorted keys alone); the box pass is the refit's (refit/box_pass.h). DESIGN.md "Rebuild" describes
-// the launches; nothing is handed between workgroups inside a hand-written launch.
+// finds its range and split from the sorted keys alone); the box pass is the refit's (refit/box_pass.h), the argument checks, the keys and
+// their sort the tree libraries' (tree/tree_lib.h). DESIGN.md "Rebuild" describes the launches; nothing is handed between workgroups
+// inside a hand-written launch.
 #include <cmath>
-#include <cstdlib>
-#include <cstring>
 #include <vector>
 
-#include <rocprim/device/device_radix_sort.hpp>
-
 #include "../image/image_lib.h"
+#define TREE_LIB_MORTON
+#include "../tree/tree_lib.h"
 #include "../refit/box_pass.h"
 #include "gpuart_build.h"
 
@@ -20,7 +19,6 @@ const char LIB[] = "build";
 
 constexpr uint32_t MAX_LEVELS = GPUART_BUILD_MAX_LEVELS;
 constexpr uint32_t CHILD_LEAF = 0x80000000u;  ///< a child code: this bit | leaf index, or an interior node's index
-constexpr uint32_t PARENT_LOWER = 0x80000000u;  ///< a parent link: this bit when the node is its parent's lower child
 constexpr uint32_t COST_ITEMS = 8;  ///< records per thread of the cost kernel
 
 /// What the build leaves for the host beside the refit's Status.
@@ -31,17 +29,7 @@ struct Extra {
     uint32_t cursor[MAX_LEVELS];  ///< where the next record of a level goes in the per-level lists
 };
 
-// 1. One thread per primitive: its 63-bit key from its box and the root box, and its ordinal as the sort's value.
-struct Box3 { float lo[3], hi[3]; };
-
-__global__ void __launch_bounds__(256) k_bd_keys(const float *pbox, uint32_t n, Box3 root, uint64_t *keys, uint32_t *vals) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    const float *b = pbox + 6 * (size_t)i;
-    keys[i] = tree_rule::morton_key(b, b + 3, root.lo, root.hi);
-    vals[i] = i;
-}
-
+// 1, 2. The keys and their sort: tree_lib.h's morton_sort.
 // 3. One thread per new position: the primitive's record and box moved there; word 3 of the first quad says the type and, on a leaf's
 // first primitive, the leaf's count.
 __global__ void __launch_bounds__(256) k_bd_permute(const float4 *src, const float *src_box, const uint32_t *new_to_old, uint32_t n, float4 *dst,
@@ -49,16 +37,8 @@ __global__ void __launch_bounds__(256) k_bd_permute(const float4 *src, const flo
     const uint32_t p = blockIdx.x * 256u + threadIdx.x;
     if (p >= n) return;
     const uint32_t old = new_to_old[p];
-    const float4 *s = src + 3 * (size_t)old;
-    float4 r0 = s[0];
-    const uint32_t type = __float_as_uint(r0.w) & 3u;
     const uint32_t cnt = (p & 1u) ? 0u : (p + 1u < n ? 2u : 1u);
-    r0.w = __uint_as_float(type | cnt << 2);
-    float4 *d = dst + 3 * (size_t)p;
-    d[0] = r0; d[1] = s[1]; d[2] = s[2];
-    const float *sb = src_box + 6 * (size_t)old;
-    float *db = dst_box + 6 * (size_t)p;
-    for (int k = 0; k < 6; k++) db[k] = sb[k];
+    move_prim(src, src_box, old, cnt, dst, dst_box, p);
 }
 
 /// delta(i, j) over the m leaf keys (leaf j's key is that of position 2j); -1 outside. Never asked for j == i (k_bd_hierarchy).
@@ -212,8 +192,7 @@ struct gpuart_build : ImageHandle {
     DeviceBuffer temp;         ///< the sort's
     DeviceBuffer partial;      ///< the cost's partial sums
     DeviceBuffer staging;      ///< run_host: the permutation
-    hipEvent_t ev[8] = {};
-    double step_ms[7] = {0, 0, 0, 0, 0, 0, 0};
+    StepTimer timer;           ///< keys, sort, permute, hierarchy, number, emit, boxes
 };
 
 extern "C" {
@@ -221,67 +200,29 @@ extern "C" {
 const char *gpuart_build_last_error(void) { return g_last_error.c_str(); }
 
 int gpuart_build_create(int device, gpuart_build **out) {
-    if (int rc = create_handle(LIB, device, out)) return rc;
-    gpuart_build *h = *out;
-    *out = nullptr;
-    hipError_t e = hipMalloc((void **)&h->status, sizeof(Status));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->extra, sizeof(Extra));
-    for (int k = 0; k < 8 && e == hipSuccess; k++) e = hipEventCreate(&h->ev[k]);
-    if (e != hipSuccess) {
-        gpuart_build_destroy(h);
-        return fail(GPUART_HIP_ERR_DEVICE, std::string("build: allocating the status: ") + hipGetErrorString(e));
-    }
-    *out = h;
-    return 0;
+    return create_tree_handle(LIB, device, out, gpuart_build_destroy, [](gpuart_build *h) {
+        hipError_t e = hipMalloc((void **)&h->status, sizeof(Status));
+        if (e == hipSuccess) e = hipMalloc((void **)&h->extra, sizeof(Extra));
+        return e == hipSuccess ? h->timer.create(7) : e;
+    });
 }
 
 int gpuart_build_destroy(gpuart_build *h) {
     if (!h) return 0;
     destroy_handle(h, {h->status, h->extra, h->scratch.mem, h->temp.mem, h->partial.mem, h->staging.mem});
-    for (hipEvent_t e : h->ev)
-        if (e) (void)hipEventDestroy(e);
+    h->timer.destroy();
     delete h;
     return 0;
 }
 
 int gpuart_build_finish(gpuart_build *h) { return finish_handle(LIB, h); }
 
-int gpuart_build_step_ms(gpuart_build *h, double ms[7]) {
-    if (int rc = check_handle(LIB, h)) return rc;
-    if (!ms) return fail(GPUART_HIP_ERR_ARG, "build: ms is NULL");
-    memcpy(ms, h->step_ms, sizeof h->step_ms);
-    return 0;
-}
+int gpuart_build_step_ms(gpuart_build *h, double ms[7]) { return step_ms(LIB, h, ms); }
 
 int gpuart_build_run(gpuart_build *h, const gpuart_hip_scene *src, const gpuart_hip_scene *dst, uint32_t *new_to_old, gpuart_build_result *result) {
-    if (int rc = check_handle(LIB, h)) return rc;
-    if (!src) return fail(GPUART_HIP_ERR_ARG, "build: src is NULL");
-    if (int rc = check_descriptor(src, LIB, "src", "rebuilt")) return rc;
-    if (misaligned({src->recs, src->prims}, 16) || misaligned({src->prim_boxes}, 4)) return fail(GPUART_HIP_ERR_ARG, "build: src: misaligned arrays");
-    if (!dst) return fail(GPUART_HIP_ERR_ARG, "build: dst is NULL");
-    if (dst->layout != 1) return fail(GPUART_HIP_ERR_ARG, "build: dst: unknown layout " + std::to_string(dst->layout));
+    uint32_t word[2];  // (of a root that is a leaf: the refs come from the permuted records here)
+    if (int rc = check_build(LIB, h, src, dst, new_to_old, [](size_t n) { return (n + 1) / 2 - 1; }, word)) return rc;
     const size_t n = src->n_prims, m = (n + 1) / 2, n_recs = m - 1;
-    if (!tree_rule::box_ok(src->root_min, src->root_max)) return fail(GPUART_HIP_ERR_ARG, "build: the root box is not finite and ordered");
-    if (!new_to_old || misaligned({new_to_old}, 4)) return fail(GPUART_HIP_ERR_ARG, "build: new_to_old is NULL or misaligned");
-    if (!dst->prims || !dst->prim_boxes || (n_recs && !dst->recs) || misaligned({dst->recs, dst->prims}, 16) || misaligned({dst->prim_boxes}, 4))
-        return fail(GPUART_HIP_ERR_ARG, "build: dst's arrays are NULL or misaligned");
-    if (dst->n_prims < n || dst->n_recs < n_recs)
-        return fail(GPUART_HIP_ERR_ARG, "build: dst is too small: " + std::to_string(dst->n_recs) + " records and " + std::to_string(dst->n_prims) +
-                                            " primitives for " + std::to_string(n_recs) + " and " + std::to_string(n));
-    const struct { const void *p; size_t bytes; } S[3] = {{src->recs, src->n_recs * 64}, {src->prims, n * 48}, {src->prim_boxes, n * 24}},
-                                                  D[4] = {{dst->recs, n_recs * 64}, {dst->prims, n * 48}, {dst->prim_boxes, n * 24}, {new_to_old, n * 4}};
-    for (const auto &s : S)
-        for (const auto &d : D)
-            if (s.bytes && d.bytes && overlaps(s.p, s.bytes, d.p, d.bytes)) return fail(GPUART_HIP_ERR_ARG, "build: dst's arrays alias src's");
-    for (int a = 0; a < 4; a++)
-        for (int b = a + 1; b < 4; b++)
-            if (D[a].bytes && D[b].bytes && overlaps(D[a].p, D[a].bytes, D[b].p, D[b].bytes)) return fail(GPUART_HIP_ERR_ARG, "build: dst's arrays overlap");
-    HIP_TRY(hipSetDevice(h->device));
-    if (n == 1) {  // an empty scene keeps one dummy record, whose count is 0 (converter.h)
-        uint32_t word = 0;
-        HIP_TRY(hipMemcpy(&word, (const char *)src->prims + 12, 4, hipMemcpyDeviceToHost));
-        if ((word >> 2) == 0) return fail(GPUART_HIP_ERR_ARG, "build: src: an empty scene is not rebuilt");
-    }
 
     // scratch: keys in, keys out (8 bytes each), then the 4-byte arrays
     const size_t N8 = (n + 1) & ~(size_t)1, M4 = (m + 3) & ~(size_t)3;
@@ -289,51 +230,38 @@ int gpuart_build_run(gpuart_build *h, const gpuart_hip_scene *src, const gpuart_
     uint64_t *keys_in = (uint64_t *)h->scratch.mem, *keys = keys_in + N8;
     uint32_t *vals_in = (uint32_t *)(keys + N8);
     uint32_t *lower = vals_in + N8, *upper = lower + M4, *first = upper + M4, *parent = first + M4, *rec = parent + M4, *depth = rec + M4, *order = depth + M4;
-    size_t temp_bytes = 0;
-    HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, keys_in, keys, vals_in, new_to_old, n, 0, 63, h->stream));
-    if (int rc = ensure(h->stream, h->temp, temp_bytes + 16)) return rc;
 
     const float4 *sprims = (const float4 *)src->prims;
     float4 *drecs = (float4 *)dst->recs, *dprims = (float4 *)dst->prims;
     float *dbox = (float *)dst->prim_boxes;
-    uint32_t top_depth = 0;
-    if (const char *e = getenv("GPUART_HIP_TOP_DEPTH")) top_depth = (uint32_t)atoi(e);
-    Box3 root;
-    memcpy(root.lo, src->root_min, 12); memcpy(root.hi, src->root_max, 12);
-    const uint32_t nb = (uint32_t)((n + 255) / 256), mb = (uint32_t)((m - 1 + 255) / 256);
-    int at = 0;
-    const auto mark = [&] { return hipEventRecord(h->ev[at++], h->stream); };
+    const uint32_t mb = blocks(m - 1);
+    h->timer.start(h->stream);
 
     HIP_TRY(hipMemsetAsync(h->status, 0, sizeof(Status), h->stream));
     HIP_TRY(hipMemsetAsync(h->extra, 0, sizeof(Extra), h->stream));
-    HIP_TRY(mark());
-    k_bd_keys<<<nb, 256, 0, h->stream>>>((const float *)src->prim_boxes, (uint32_t)n, root, keys_in, vals_in);
+    if (int rc = morton_sort(h->timer, h->temp, 0, src, keys_in, keys, vals_in, new_to_old)) return rc;
+    k_bd_permute<<<blocks(n), 256, 0, h->stream>>>(sprims, (const float *)src->prim_boxes, new_to_old, (uint32_t)n, dprims, dbox);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(mark());
-    HIP_TRY(rocprim::radix_sort_pairs(h->temp.mem, temp_bytes, keys_in, keys, vals_in, new_to_old, n, 0, 63, h->stream));
-    HIP_TRY(mark());
-    k_bd_permute<<<nb, 256, 0, h->stream>>>(sprims, (const float *)src->prim_boxes, new_to_old, (uint32_t)n, dprims, dbox);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(mark());
+    HIP_TRY(h->timer.mark());
     if (n_recs) {
         k_bd_hierarchy<<<mb, 256, 0, h->stream>>>(keys, (uint32_t)m, lower, upper, first, parent);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(mark());
+    HIP_TRY(h->timer.mark());
     if (n_recs) {
         k_bd_number<<<mb, 256, 0, h->stream>>>(parent, first, (uint32_t)m, rec, depth, h->extra);
         HIP_TRY(hipGetLastError());
         k_bd_offsets<<<1, 64, 0, h->stream>>>(h->extra);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(mark());
+    HIP_TRY(h->timer.mark());
     if (n_recs) {
-        k_bd_emit<<<mb, 256, 0, h->stream>>>(lower, upper, rec, depth, (uint32_t)m, dprims, (uint32_t)n, top_depth, drecs, order, h->extra);
+        k_bd_emit<<<mb, 256, 0, h->stream>>>(lower, upper, rec, depth, (uint32_t)m, dprims, (uint32_t)n, top_depth(), drecs, order, h->extra);
     } else {
         k_bd_root_leaf<<<1, 64, 0, h->stream>>>(dprims, (uint32_t)n, h->extra);
     }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(mark());
+    HIP_TRY(h->timer.mark());
     // the per-level counts, once: they size the level launches
     Extra ex;
     HIP_TRY(hipMemcpyAsync(&ex, h->extra, sizeof ex, hipMemcpyDeviceToHost, h->stream));
@@ -355,15 +283,11 @@ int gpuart_build_run(gpuart_build *h, const gpuart_hip_scene *src, const gpuart_
     const uint32_t root_ref = n_recs ? 0u : ex.root_ref;
     k_rf_root<<<1, 64, 0, h->stream>>>(drecs, dprims, dbox, root_ref, h->status);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(mark());
+    HIP_TRY(h->timer.mark());
     Status st;
     HIP_TRY(hipMemcpyAsync(&st, h->status, sizeof st, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    for (int k = 0; k < 7; k++) {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, h->ev[k], h->ev[k + 1]));
-        h->step_ms[k] = ms;
-    }
+    if (int rc = h->timer.read()) return rc;
     if (result) {
         result->n_recs = n_recs;
         result->root_ref = root_ref;
@@ -377,14 +301,7 @@ int gpuart_build_run(gpuart_build *h, const gpuart_hip_scene *src, const gpuart_
 }
 
 int gpuart_build_run_host(gpuart_build *h, const gpuart_hip_scene *src, const gpuart_hip_scene *dst, uint32_t *new_to_old, gpuart_build_result *result) {
-    if (int rc = check_handle(LIB, h)) return rc;
-    if (!src || !new_to_old || !src->n_prims) return fail(GPUART_HIP_ERR_ARG, "build: src or new_to_old is NULL, or the scene is empty");
-    HIP_TRY(hipSetDevice(h->device));
-    if (int rc = ensure(h->stream, h->staging, src->n_prims * sizeof(uint32_t))) return rc;
-    if (int rc = gpuart_build_run(h, src, dst, (uint32_t *)h->staging.mem, result)) return rc;
-    HIP_TRY(hipMemcpyAsync(new_to_old, h->staging.mem, src->n_prims * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return 0;
+    return run_staged(LIB, h, gpuart_build_run, src, dst, new_to_old, result);
 }
 
 int gpuart_build_cost(gpuart_build *h, const gpuart_hip_scene *scene, double *cost) {

@@ -144,6 +144,16 @@ def test_product_and_test_builds_run_the_same_kernels(tmp_path):
         assert a == b, "%s of %s and %s differ (%d vs %d bytes)" % (sec, product_host, tested_host, len(a), len(b))
 
 
+@pytest.mark.parametrize("name", ["refit", "build", "ploc", "edit"])
+def test_the_tree_libraries_the_suite_loads_are_copies_of_the_products(name):
+    """The four tree libraries have no hooks: gpuart_amd/lib_test holds copies of the gpuart_amd/lib ones (csrc/Makefile), byte for byte."""
+    import filecmp
+    lib = "libgpuart_%s.so" % name
+    product, tested = os.path.join(PRODUCT_DIR, lib), os.path.join(ROOT, "gpuart_amd", "lib_test", lib)
+    assert os.path.exists(product) and os.path.exists(tested), "%s not built: run __graft_entry__.build()" % lib
+    assert filecmp.cmp(product, tested, shallow=False), "%s and %s differ" % (product, tested)
+
+
 # ---- GPU: the product pair against the reference, in fresh child processes --------------------------------------------------------
 
 
