@@ -83,7 +83,7 @@ struct Converter {
     bool irregular = false;
     void note(const Child &c) { irregular = irregular || !tree_rule::box_ok(c.bmin, c.bmax); }
 
-    /// May the fast kernels visit this tree's nodes in their own order (nearer child first, device_scene.h GD_NEAREST)? Their
+    /// May the fast kernels visit this tree's nodes in their own order (nearer child first, device_scene.h "Visiting order")? Their
     /// certificate rests on boxes that bound what they hold: every child box inside its parent's, every primitive inside its
     /// leaf's box by the very formulas the reference's constructors use (reference src/core.cpp:36-65,80-90,136-150,217-225) —
     /// which only bound a primitive with radii >= 0 and, for a cone, with derived constants (axis, length, width coefficient)
@@ -136,7 +136,7 @@ struct Converter {
         if (flags & 0x80000000u) {
             uint32_t n = flags & ~0xE0000000u;
             // (a primitive's byte offset, 48 x index, and a record's, 64 x index, fit 32 bits: the kernels address both as base + 32-bit
-            //  offset, device_scene.h GD_ADDR32 — 89 million primitives / 67 million interior nodes; the reference's own format ends at
+            //  offset, device_scene.h trav_step_box and the leaf tests — 89 million primitives / 67 million interior nodes; the reference's own format ends at
             //  2^31 floats = 76 million triangles with their leaves)
             if (n_prims >= 0x05555540u) { err = "too many primitives"; return false; }
             const uint32_t first = (uint32_t)n_prims;

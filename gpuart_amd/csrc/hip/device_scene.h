@@ -19,6 +19,7 @@
 //           T = bits(type | count << 2): the FIRST primitive of a leaf carries the leaf's primitive count
 #pragma once
 #include "device_math.h"
+#include "diag.h"
 #include "tree_rule.h"
 
 // The quick box answer (box_quick.h: certainly the reference's, or withdrawn) on the device's own instructions: v_min / v_max drop a
@@ -91,31 +92,13 @@ enum { P_SPHERE = 0, P_DISC = 1, P_TRIANGLE = 2, P_CONE = 3 };
 // it for primitives it does not test. Measured: tools/order_soak.py, 3.7e11 rays of six scenes against the reference-order kernels
 // without a differing pixel (profiles/r04/order_soak_final.txt) — soak-verified, not proven; hence opt-in. The counting "reference work"
 // variants, trees with irregular boxes, Sun-shadow queries and the one-thread-per-pixel kernels keep the reference's order in any case.
-#ifndef GD_NEAREST
-#define GD_NEAREST 1
-#endif
-#ifndef GD_NEAREST_DIRECT
-#define GD_NEAREST_DIRECT 0  ///< the persistent direct-lighting kernel too (measured slower: kernels_pipeline.h)
-#endif
 #ifndef GD_NEAREST_BAND
 #define GD_NEAREST_BAND 1.00390625f  ///< 1 + 2^-8 (free up to 2^-8, +2.5 % time at 2^-6: profiles/r04/nearest_child_first.txt)
 #endif
-#ifndef GD_CERT_ODD
-#define GD_CERT_ODD 1      // ablation switches of the certificate's parts (tools/ab_build.sh; never 0 in the product build)
-#endif
-#ifndef GD_CERT_HITS
-#define GD_CERT_HITS 1
-#endif
-// Round 6, the step's bookkeeping (profiles/r06/step_isa_budget.txt); both bit-identical by construction, 0 = the code of round 5 for A/B:
-#ifndef GD_POP_WHOLE
-#define GD_POP_WHOLE 1     ///< TravStack::pop reads an entry's three words at once (one LDS round trip per accepted pop instead of two)
-#endif
-#ifndef GD_ADDR32
-#define GD_ADDR32 1        ///< node records / triangle leaves addressed as base + 32-bit byte offset (converter.h bounds both arrays below 4 GB)
-#endif
-#ifndef GD_QUICK_BOXES
-#define GD_QUICK_BOXES 1   ///< fast-form box tests try the quick answer of box_quick.h first (0: always the six face tests; A/B builds)
-#endif
+// The step's bookkeeping since round 6 (profiles/r06/step_isa_budget.txt), bit-identical by construction: TravStack::pop reads an entry's
+// three words at once, and node records / leaf records are addressed as base + 32-bit byte offset (converter.h bounds both arrays below
+// 4 GB). Fast-form box tests try the quick answer of box_quick.h first (measured against the six face tests alone: LAB_NOTES.md,
+// "Quick box answers").
 #define GD_PRIM_LOOSE 0x40000000u  ///< in Trav::hit_prim during a NEAREST walk: a box on the winner's path is entered beyond the winner's parameter
 #define GD_PRIM_ADRIFT 0x20000000u ///< ... beyond the winner's parameter x BAND: the parameter and its boxes disagree by more than rounding
 #define GD_PRIM_FLAGS (GD_PRIM_LOOSE | GD_PRIM_ADRIFT)
@@ -271,7 +254,7 @@ GD_FN float triangle_t(float rox, float roy, float roz, float rdx, float rdy, fl
 #define GD_EXACT_BOXES 0x10  ///< beside a type mask: the kernel variant for trees with irregular boxes (box tests in comparison form)
 #define GD_REF_ORDER 0x20    ///< beside a type mask: regular boxes, every walk keeps the reference's order — the product's default since round 5
                              ///< (top of this file); without it: the opt-in nearest-child-first variants
-#define GD_NEAREST_OF(TYPES) (GD_NEAREST && !((TYPES) & (GD_EXACT_BOXES | GD_REF_ORDER)))
+#define GD_NEAREST_OF(TYPES) (!((TYPES) & (GD_EXACT_BOXES | GD_REF_ORDER)))
 /// How a kernel tests boxes: the fast (med3) form, the exact comparison form, or whichever Scene::exact_boxes asks for
 /// (kernels off the fast path: one wave-uniform branch per step).
 enum { GD_BOXES_FAST = 0, GD_BOXES_EXACT = 1, GD_BOXES_RUNTIME = 2 };
@@ -383,13 +366,6 @@ GD_FN bool box_quick(const Ray &r, F3 rdiv, F3 bmin, F3 bmax, float cs, float &p
     return gq_box(k0, k1, k2, k3, k4, k5, fabsf(rdiv.x), fabsf(rdiv.y), fabsf(rdiv.z), cs, pos, hit);
 }
 
-#ifdef GD_QUICK_CHECK
-// Diagnostic build (never the product): every fast-form box test of a step is ALSO run through the six face tests and the quick
-// answers that stand are compared with them. [0] boxes, [1] quick answers that stand, [2] steps, [3] steps that had to run the face
-// tests (a lane withdrew), [4] standing answers that differ from the face tests (must stay 0), [5] of them: marked odd by the face tests.
-__device__ unsigned long long g_quick_stats[8];
-#endif
-
 /// Running result of one query (the traversal state proper follows below).
 struct Trav {
     float closest;
@@ -416,11 +392,6 @@ GD_FN bool take_hit(Trav &t, float pos, uint32_t pi) {
         return true;
     }
     const bool win = (pos < t.closest) | ((pos == t.closest) & ((int)pi < (int)(t.hit_prim & ~GD_PRIM_FLAGS)));
-    if (!GD_CERT_HITS) {
-        t.hit_prim = win ? pi : t.hit_prim;
-        t.closest = win ? pos : t.closest;
-        return win;
-    }
     t.second = fminf(t.second, win ? t.closest : pos);  // (second >= closest unless it is the -inf of an odd box, which sticks)
     t.hit_prim = win ? (pi | (t.entry > pos ? GD_PRIM_LOOSE : 0u) | (t.entry > pos * GD_NEAREST_BAND ? GD_PRIM_ADRIFT : 0u)) : t.hit_prim;
     t.closest = win ? pos : t.closest;
@@ -435,12 +406,8 @@ GD_FN bool leaf_test(const Scene &sc, const Ray &r, uint32_t first, Trav &t, Wor
     uint32_t count = 1;
     for (uint32_t i = 0; i < count; i++) {
         uint32_t pi = first + i;
-#if GD_ADDR32
         const float4 *pp = (const float4 *)((const char *)sc.prims + pi * 48u);
         float4 q0 = pp[0], q1 = pp[1], q2 = pp[2];
-#else
-        float4 q0 = sc.prims[3 * (size_t)pi], q1 = sc.prims[3 * (size_t)pi + 1], q2 = sc.prims[3 * (size_t)pi + 2];
-#endif
         if (i == 0) {
             count = __float_as_uint(q0.w) >> 2;
             if (count == 0) break;  // empty leaf (empty scene)
@@ -459,25 +426,13 @@ GD_FN bool leaf_test(const Scene &sc, const Ray &r, uint32_t first, Trav &t, Wor
 /// vector-memory request pipeline). The first one wins ties (`pos < closest` is strict), as in the reference's loop.
 template <bool ANY_HIT, bool COUNT, bool NEAREST = false>
 GD_FN bool leaf_test_tris(const Scene &sc, const Ray &r, uint32_t first, bool two, Trav &t, WorkCounters *wc) {
-#if GD_ADDR32
     const float4 *pa = (const float4 *)((const char *)sc.prims + first * 48u);
-#else
-    const float4 *pa = sc.prims + 3 * (size_t)first;
-#endif
     const float4 a0 = pa[0], a1 = pa[1], a2 = pa[2];
     if (COUNT) wc->prims[P_TRIANGLE] += two ? 2 : 1;
     float tb = -1.0f;
     if (two) {
         const float4 b0 = pa[3], b1 = pa[4], b2 = pa[5];
         tb = triangle_t(r.o.x, r.o.y, r.o.z, r.d.x, r.d.y, r.d.z, b0, b1, b2);
-#ifdef GD_LEAF_PROBE  // measurement hook (never in the product build): one more triangle test per pair, result unused
-        {
-            float ox = r.o.x;
-            asm volatile("" : "+v"(ox));
-            const float tc = triangle_t(ox, r.o.y, r.o.z, r.d.x, r.d.y, r.d.z, b0, b1, b2);
-            asm volatile("" ::"v"(tc));
-        }
-#endif
     }
     const float ta = triangle_t(r.o.x, r.o.y, r.o.z, r.d.x, r.d.y, r.d.z, a0, a1, a2);
     if (take_hit<NEAREST>(t, ta, first) && ANY_HIT) return true;
@@ -490,11 +445,7 @@ GD_FN bool leaf_test_tris(const Scene &sc, const Ray &r, uint32_t first, bool tw
 /// primitive, and nothing waits for the count in the first record. Same tests in the same order as the loop of `leaf_test`.
 template <bool ANY_HIT, bool COUNT, int TYPES = GD_ALL_TYPES, bool NEAREST = false>
 GD_FN bool leaf_test_small(const Scene &sc, const Ray &r, uint32_t first, bool two, Trav &t, WorkCounters *wc) {
-#if GD_ADDR32
     const float4 *pa = (const float4 *)((const char *)sc.prims + first * 48u);
-#else
-    const float4 *pa = sc.prims + 3 * (size_t)first;
-#endif
     const float4 a0 = pa[0], a1 = pa[1], a2 = pa[2];
     float tb = -1.0f;
     F3 p, n; int ptype;
@@ -532,12 +483,6 @@ struct StackEntry {
 #define GD_RING_SLOT(i) ((i) % GD_RING)  // i < 1024 + GD_RING: a multiply-shift
 #endif
 
-#ifdef GD_RUN_TIMELINE
-__device__ unsigned long long g_stack_events[4];  // diagnostic build: pushes, pushes that spill an entry to global memory, pops, pops that reload one
-#define GD_STACK_EVENT(k) atomicAdd(&g_stack_events[k], 1ull)
-#else
-#define GD_STACK_EVENT(k)
-#endif
 struct TravStack {
     uint2 *ring_a;           ///< LDS, [GD_RING][BLOCK]: (ref, pe)
     float *ring_b;           ///< LDS, [GD_RING][BLOCK]: he
@@ -557,9 +502,9 @@ struct TravStack {
     /// `writer`: this lane performs the stores. A ray that several lanes carry as identical replicas (the thin-wave modes
     /// below) has ONE column; every replica keeps sp / base and reads the column, only the first one writes it.
     GD_FN void push(StackEntry e, bool writer = true) {
-        if (writer) GD_STACK_EVENT(0);
+        GD_STACK_EVENT(writer, 0);
         if (sp - base == GD_RING) {
-            if (writer) GD_STACK_EVENT(1);
+            GD_STACK_EVENT(writer, 1);
             uint32_t o = GD_RING_SLOT(base) * ring_stride;
             uint2 a = ring_a[o];
             if (writer) spill[(size_t)base * spill_stride] = make_uint4(a.x, a.y, __float_as_uint(ring_b[o]), 0);
@@ -575,9 +520,9 @@ struct TravStack {
         sp++;
     }
     GD_FN StackEntry pop(bool writer = true) {  // precondition: sp > 0
-        if (writer) GD_STACK_EVENT(2);
+        GD_STACK_EVENT(writer, 2);
         if (sp == base) {
-            if (writer) GD_STACK_EVENT(3);
+            GD_STACK_EVENT(writer, 3);
             base--;
             uint4 v = spill[(size_t)base * spill_stride];
             uint32_t o = GD_RING_SLOT(base) * ring_stride;
@@ -592,12 +537,10 @@ struct TravStack {
         uint2 a = ring_a[o];
         StackEntry e;
         e.ref = a.x; e.pe = __uint_as_float(a.y); e.he = ring_b[o];
-#if GD_POP_WHOLE
         // Keep the entry's three words in the two LDS reads issued here: left alone the compiler reads the parameters first (4 + 4 bytes),
         // compares, and fetches the ref with a THIRD read once the entry is accepted — a second LDS round trip in the dependent chain
         // pop -> enter -> record address -> fetch of every step that ends in a pop.
         asm volatile("" : "+v"(e.ref), "+v"(e.pe), "+v"(e.he));
-#endif
         return e;
     }
 };
@@ -630,27 +573,15 @@ GD_FN void trav_enter(Trav &t, uint32_t ref, float entry) {
     }
 }
 
-#ifdef GD_STEP_STATS
-__device__ unsigned long long g_pop_stats[4];  // [0] trips of trav_pop's loop as waves execute them, [1] lanes in those trips, [2] calls (wave level), [3] lanes in the calls
-#endif
 /// Returns to the nearest pending upper child that is still worth visiting (or finishes).
 /// `band`: 1 in the reference's order; GD_NEAREST_BAND in an ordered NEAREST walk.
 template <bool COUNT>
 GD_FN void trav_pop(Trav &t, TravStack &st, WorkCounters *wc, bool writer = true, float band = 1.0f) {
     const float limit = t.closest * band;  // (x 1.0f is exact)
-#ifdef GD_STEP_STATS
-    {
-        const unsigned long long act = __ballot(1);
-        if ((int)(threadIdx.x & 63) == __ffsll((long long)act) - 1) { atomicAdd(&g_pop_stats[2], 1ull); atomicAdd(&g_pop_stats[3], (unsigned long long)__popcll(act)); }
-    }
-#endif
+    // (diag.h: calls, and below the trips of the loop, as the WAVE executes them — one count per call / trip with any lane in it — and the lanes in them)
+    GD_STATS({ const unsigned long long act = __ballot(1); if ((int)(threadIdx.x & 63) == __ffsll((long long)act) - 1) { atomicAdd(&g_pop_stats[2], 1ull); atomicAdd(&g_pop_stats[3], (unsigned long long)__popcll(act)); } })
     for (;;) {
-#ifdef GD_STEP_STATS
-        {   // diagnostic build: trips of this loop as the WAVE executes them (one count per trip with any lane in it) and lane-level pops
-            const unsigned long long act = __ballot(1);
-            if ((int)(threadIdx.x & 63) == __ffsll((long long)act) - 1) { atomicAdd(&g_pop_stats[0], 1ull); atomicAdd(&g_pop_stats[1], (unsigned long long)__popcll(act)); }
-        }
-#endif
+        GD_STATS({ const unsigned long long act = __ballot(1); if ((int)(threadIdx.x & 63) == __ffsll((long long)act) - 1) { atomicAdd(&g_pop_stats[0], 1ull); atomicAdd(&g_pop_stats[1], (unsigned long long)__popcll(act)); } })
         if (st.sp == 0) { t.state = TRAV_DONE; return; }
         StackEntry e = st.pop(writer);
         if (e.pe > limit) continue;       // the reference's parent re-test fails: skip the upper child
@@ -708,19 +639,9 @@ GD_FN void trav_init(const Scene &sc, const Ray &r, F3 rdiv, Trav &t, TravStack 
     }
     if (hit) trav_enter(t, sc.root_ref, entry);  // entry > 1e19 cannot happen
     else t.state = TRAV_DONE;
-#ifdef GD_ROOT_PROBE
-    // Measurement hook (never in the product build): what the fetch of the root's record costs a ray — every lane that starts a
-    // query fetches record 0 once more (same address in all lanes, as the real fetch of that record is). Passing the record in
-    // kernel arguments instead could at best save this much; built for real (the visit of the root fused into this function,
-    // record from scalar loads) it LOST 1.6-3.5 %: the fused visit is issued for the few lanes that start a query, beside the
-    // wave's regular box step (profiles/r03/request_trims.txt).
-    for (int k = 0; k < GD_ROOT_PROBE; k++) {
-        const float4 *rp = sc.recs;
-        asm volatile("" : "+v"(rp));
-        float4 d0 = rp[0], d1 = rp[1], d2 = rp[2], d3 = rp[3];
-        asm volatile("" ::"v"(d0.x), "v"(d0.w), "v"(d1.x), "v"(d1.w), "v"(d2.x), "v"(d2.z), "v"(d3.x), "v"(d3.z));
-    }
-#endif
+    // (the root's record is fetched by the first box step like any other: its visit fused into this function, record from scalar
+    //  loads, built for real it lost 1.6-3.5 % — issued for the few lanes that start a query, beside the wave's regular box step:
+    //  profiles/r03/request_trims.txt)
 }
 
 /// One interior-node visit: fetch its record, test both children's boxes, descend / stack / pop.
@@ -732,39 +653,14 @@ GD_FN void trav_init(const Scene &sc, const Ray &r, F3 rdiv, Trav &t, TravStack 
 template <bool COUNT, int BOXES = GD_BOXES_RUNTIME, bool NEAREST = false>
 GD_FN void trav_step_box(const Scene &sc, const Ray &r, F3 rdiv, Trav &t, TravStack &st, WorkCounters *wc, bool ordered = true) {
     static_assert(!NEAREST || BOXES == GD_BOXES_FAST, "nearest-first walks are for trees of regular boxes");
-#if GD_ADDR32
     // (the uploader refuses trees beyond 2^26 records: a record's byte offset fits 32 bits, and base + zero-extended offset is an
     // addressing mode of the load itself — no 64-bit address arithmetic per step, one address register instead of two)
     const float4 *rec = (const float4 *)((const char *)sc.recs + (uint32_t)(t.node << 6));
-#else
-    const float4 *rec = sc.recs + 4 * (size_t)t.node;
-#endif
     float4 q0 = rec[0], q1 = rec[1], q2 = rec[2], q3 = rec[3];
     // Keep the two child refs in the 16-byte loads: without this the compiler narrows the loads to 12 bytes and
     // fetches a ref with a separate, dependent 4-byte load inside the branch that needs it (one more memory
     // round trip per step).
     asm volatile("" : "+v"(q0.w), "+v"(q1.w));
-#if defined(GD_TA_PROBE) || defined(GD_VALU_PROBE)
-    // Measurement hooks (never defined in the product build; tools/ab_build.sh x "-DGD_TA_PROBE=2"): n more 16-byte fetches of
-    // the same record line, resp. n more dependent VALU instructions, per node visit — what tells a request-bound kernel from
-    // an issue-bound one (profiles/r02/vector_memory_bound.txt).
-#ifdef GD_TA_PROBE
-    for (int k = 0; k < GD_TA_PROBE; k++) {
-        const float4 *rp = rec + (k & 3);
-        asm volatile("" : "+v"(rp));
-        float4 dummy = *rp;
-        asm volatile("" ::"v"(dummy.x), "v"(dummy.y), "v"(dummy.z), "v"(dummy.w));
-    }
-#endif
-#ifdef GD_VALU_PROBE
-    {
-        float dummy = q0.x;
-#pragma unroll
-        for (int k = 0; k < GD_VALU_PROBE; k++) asm volatile("v_add_f32 %0, %0, %1" : "+v"(dummy) : "v"(q1.x));
-        asm volatile("" ::"v"(dummy));
-    }
-#endif
-#endif
     float el, eh;
     bool hl, hh;
     // (a version carrying both boxes' arithmetic in packed 2-wide vectors made the compiler turn the validity selects
@@ -772,7 +668,7 @@ GD_FN void trav_step_box(const Scene &sc, const Ray &r, F3 rdiv, Trav &t, TravSt
     if (BOXES == GD_BOXES_EXACT || (BOXES == GD_BOXES_RUNTIME && sc.exact_boxes)) {  // trees with an irregular box (wild input) only
         hl = aabb_entry<true>(r, rdiv, xyz(q0), xyz(q1), el);
         hh = aabb_entry<true>(r, rdiv, xyz(q2), xyz(q3), eh);
-    } else if (GD_QUICK_BOXES && BOXES == GD_BOXES_FAST) {
+    } else if (BOXES == GD_BOXES_FAST) {
         // the quick answer first (box_quick.h): it stands for all but a few boxes in 100 000; the lanes where one of the two is
         // withdrawn run the six face tests (a divergent region that the wave skips when no lane needs it)
         // (the ray's slack is a pure function of the ray: the compiler computes it where the ray changes — the refill —, not per step)
@@ -786,8 +682,7 @@ GD_FN void trav_step_box(const Scene &sc, const Ray &r, F3 rdiv, Trav &t, TravSt
             sh = box_quick(r, rdiv, xyz(q2), xyz(q3), cs, eh, hh);
         }
         bool ol = false, oh = false;
-#ifdef GD_QUICK_CHECK
-        {
+        GD_QCHECK({  // every box ALSO through the six face tests; the quick answers that stand are compared with them (diag.h: g_quick_stats)
             float fl, fh; bool xl, xh;
             const bool gl = aabb_entry<false, true>(r, rdiv, xyz(q0), xyz(q1), fl, &xl);
             const bool gh = aabb_entry<false, true>(r, rdiv, xyz(q2), xyz(q3), fh, &xh);
@@ -801,8 +696,7 @@ GD_FN void trav_step_box(const Scene &sc, const Ray &r, F3 rdiv, Trav &t, TravSt
             atomicAdd(&g_quick_stats[1], (unsigned long long)sl + (unsigned long long)sh);
             if (bad_l | bad_h) atomicAdd(&g_quick_stats[4], (unsigned long long)bad_l + (unsigned long long)bad_h);
             if ((sl & xl) | (sh & xh)) atomicAdd(&g_quick_stats[5], 1ull);
-        }
-#endif
+        })
         if (!(sl & sh)) {
             // (the boxes are fetched again — an L1 hit, a few times per 100 000 boxes — so that the record's 14 registers are not
             //  kept alive across the quick tests for this region's sake: k_trace has none to spare)
@@ -813,14 +707,8 @@ GD_FN void trav_step_box(const Scene &sc, const Ray &r, F3 rdiv, Trav &t, TravSt
             hh = aabb_entry<false, true>(r, rdiv, xyz(p2), xyz(p3), eh, &oh);
         }
         // a box whose entry parameter is not its slab entry: this query's answer may hinge on the visiting order (trav_settle)
-        if (NEAREST && GD_CERT_ODD) t.second = (ordered & (ol | oh)) ? -__builtin_inff() : t.second;
-    } else if (NEAREST && GD_CERT_ODD) {
-        bool ol, oh;
-        hl = aabb_entry<false, true>(r, rdiv, xyz(q0), xyz(q1), el, &ol);
-        hh = aabb_entry<false, true>(r, rdiv, xyz(q2), xyz(q3), eh, &oh);
-        // a box whose entry parameter is not its slab entry: this query's answer may hinge on the visiting order (trav_settle)
-        t.second = (ordered & (ol | oh)) ? -__builtin_inff() : t.second;
-    } else {
+        if (NEAREST) t.second = (ordered & (ol | oh)) ? -__builtin_inff() : t.second;
+    } else {  // GD_BOXES_RUNTIME on a tree of regular boxes (kernels off the fast path): the six face tests, no quick answer
         hl = aabb_entry(r, rdiv, xyz(q0), xyz(q1), el);
         hh = aabb_entry(r, rdiv, xyz(q2), xyz(q3), eh);
     }
@@ -942,9 +830,6 @@ GD_FN void thin_fetch(const Scene &sc, const Trav &t, uint32_t sub, ThinFetch &p
     }
 }
 
-#ifndef GD_THIN_PREFETCH
-#define GD_THIN_PREFETCH 1
-#endif
 /// Where a thin-wave step may warm the vector L1 for a child it STACKS (a pop will fetch that child's record — or a leaf's first
 /// primitive record — many dependent steps later; in a draining wave that fetch is a round trip to the L2 on the ray's critical path,
 /// and the memory system is idle): one 4-byte `global_load_lds` per stacked child into a sink in LDS that nobody reads — a load without
@@ -987,13 +872,9 @@ GD_FN void trav_step_box_thin_on(F3 ro, F3 rd, F3 rdiv, Trav &t, TravStack &st, 
         float pos;
         bool hit;
         bool odd_box = false;
-        if (GD_QUICK_BOXES) {  // a pair: each lane one whole box — the quick answer first, as in trav_step_box (`slack`: Scene::box_slack)
-            const float cs = gq_ray_slack(slack, ro.x, ro.y, ro.z, rd.x, rd.y, rd.z, rdiv.x, rdiv.y, rdiv.z);
-            if (!box_quick(Ray{ro, rd}, rdiv, xyz(bmin), xyz(bmax), cs, pos, hit)) hit = aabb_entry<false, true>(Ray{ro, rd}, rdiv, xyz(bmin), xyz(bmax), pos, &odd_box);
-        } else if (NEAREST)
-            hit = aabb_entry<false, true>(Ray{ro, rd}, rdiv, xyz(bmin), xyz(bmax), pos, &odd_box);
-        else
-            hit = aabb_entry(Ray{ro, rd}, rdiv, xyz(bmin), xyz(bmax), pos);
+        // a pair: each lane one whole box — the quick answer first, as in trav_step_box (`slack`: Scene::box_slack)
+        const float cs = gq_ray_slack(slack, ro.x, ro.y, ro.z, rd.x, rd.y, rd.z, rdiv.x, rdiv.y, rdiv.z);
+        if (!box_quick(Ray{ro, rd}, rdiv, xyz(bmin), xyz(bmax), cs, pos, hit)) hit = aabb_entry<false, true>(Ray{ro, rd}, rdiv, xyz(bmin), xyz(bmax), pos, &odd_box);
         if (NEAREST) {
             const uint32_t odd = odd_box ? 1u : 0u;
             if (ordered & ((odd | quad_u<GD_QUAD_PERM(1, 0, 3, 2)>(odd)) != 0)) t.second = -INF;
@@ -1015,7 +896,7 @@ GD_FN void trav_step_box_thin_on(F3 ro, F3 rd, F3 rdiv, Trav &t, TravStack &st, 
         StackEntry s;
         s.ref = ref_hi; s.pe = t.entry; s.he = eh;
         st.push(s, writer);
-        if (GD_THIN_PREFETCH && warm.sink && writer && !(el > limit)) {  // (if the other child is not entered either, this one is popped at once)
+        if (warm.sink && writer && !(el > limit)) {  // (if the other child is not entered either, this one is popped at once)
             const float4 *line = (ref_hi & GD_REF_LEAF) ? warm.prims + 3 * (size_t)(ref_hi & GD_REF_INDEX) : warm.recs + 4 * (size_t)ref_hi;
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)line, (__attribute__((address_space(3))) void *)warm.sink, 4, 0, 0);
         }
@@ -1076,20 +957,17 @@ GD_FN void trav_step_leaf_thin(const Scene &sc, F3 ro, F3 rd, Trav &t, TravStack
 // its own row of every stack entry: its parent's entry parameter and its child's (GD_ENTRY_MISS where its own walk would not have
 // stacked the child), so that a lane's pops accept exactly the entries its own walk would have pushed and accepted. A packet pushes
 // at most one entry per level, as a lane does: the ring, the spill column and their sizing are the per-lane walk's.
-#ifdef GD_STEP_STATS
-__device__ unsigned long long g_packet_stats[4];  // [0] box steps of packets, [1] active lanes in them, [2] leaf steps, [3] active lanes in them
-#endif
 typedef float GdF4v __attribute__((ext_vector_type(4)));
 typedef const GdF4v __attribute__((address_space(4))) *ScalarF4;  ///< constant address space: a load through a uniform address is a scalar load
 GD_FN float4 ld4(ScalarF4 p, int k) { const GdF4v v = p[k]; return make_float4(v.x, v.y, v.z, v.w); }
 
-/// Both boxes of a record (fast form) for one lane: the calls of trav_step_box's GD_QUICK_BOXES branch, its fallback included.
+/// Both boxes of a record (fast form) for one lane: the calls of trav_step_box's fast-form branch, its fallback included.
 /// `need`: this lane's answers are used (an idle lane does not ask for the face tests).
 GD_FN void box_pair_fast(const Scene &sc, const Ray &r, F3 rdiv, ScalarF4 rec, float4 q0, float4 q1, float4 q2, float4 q3, bool need,
                          float &el, float &eh, bool &hl, bool &hh) {
     const float cs = gq_ray_slack(sc.box_slack, r.o.x, r.o.y, r.o.z, r.d.x, r.d.y, r.d.z, rdiv.x, rdiv.y, rdiv.z);
     bool sl = false, sh = false;
-    if (GD_QUICK_BOXES && __ballot(cs == cs) != 0) {
+    if (__ballot(cs == cs) != 0) {
         sl = box_quick(r, rdiv, xyz(q0), xyz(q1), cs, el, hl);
         sh = box_quick(r, rdiv, xyz(q2), xyz(q3), cs, eh, hh);
     }
@@ -1120,9 +998,7 @@ GD_FN void trav_packet(const Scene &sc, F3 ro, F3 rd, F3 rdiv, Trav &t, TravStac
             float el = 0, eh = 0;
             bool hl = false, hh = false;
             box_pair_fast(sc, r, rdiv, rec, q0, q1, q2, q3, act, el, eh, hl, hh);
-#ifdef GD_STEP_STATS
-            { const unsigned long long a_ = __ballot(act); if ((threadIdx.x & 63) == 0) { atomicAdd(&g_packet_stats[0], 1ull); atomicAdd(&g_packet_stats[1], (unsigned long long)__popcll(a_)); } }
-#endif
+            GD_STATS({ const unsigned long long a_ = __ballot(act); if ((threadIdx.x & 63) == 0) { atomicAdd(&g_packet_stats[0], 1ull); atomicAdd(&g_packet_stats[1], (unsigned long long)__popcll(a_)); } })
             const bool lo = act & hl & !(el > t.closest), hi = act & hh & !(eh > t.closest);
             if (__ballot(hi) != 0) {
                 StackEntry e;
@@ -1138,9 +1014,7 @@ GD_FN void trav_packet(const Scene &sc, F3 ro, F3 rd, F3 rdiv, Trav &t, TravStac
         } else {
             // ---- leaf: the primitive tests of trav_step_leaf for the lanes at it; a shadow query is settled by one accepted hit
             const int state = (int)(1u | ((ref >> 27) & 14u));
-#ifdef GD_STEP_STATS
-            { const unsigned long long a_ = __ballot(act); if ((threadIdx.x & 63) == 0) { atomicAdd(&g_packet_stats[2], 1ull); atomicAdd(&g_packet_stats[3], (unsigned long long)__popcll(a_)); } }
-#endif
+            GD_STATS({ const unsigned long long a_ = __ballot(act); if ((threadIdx.x & 63) == 0) { atomicAdd(&g_packet_stats[2], 1ull); atomicAdd(&g_packet_stats[3], (unsigned long long)__popcll(a_)); } })
             if (act) {
                 leaf_tests<false, false, TYPES, false>(sc, r, ref & GD_REF_INDEX, state, t, nullptr);
                 if (any_hit && t.hit_prim != GD_NO_PRIM) t.state = TRAV_DONE;
@@ -1187,17 +1061,6 @@ GD_FN void traverse(const Scene &sc, const Ray &r, TravStack &st, float &closest
 /// Recomputes point, normal and type of the winning primitive (pure function of ray + record).
 GD_FN void shade_prim(const Scene &sc, const Ray &r, uint32_t pi, Surface &s) {
     float4 q0 = sc.prims[3 * pi], q1 = sc.prims[3 * pi + 1], q2 = sc.prims[3 * pi + 2];
-#ifdef GD_SHADE_PROBE
-    // Measurement hook (never in the product build): the hit primitive's three quads are fetched GD_SHADE_PROBE more times — what
-    // carrying them over from the query instead of re-fetching them could at best save: nothing measurable
-    // (profiles/r03/request_trims.txt)
-    for (int k = 0; k < GD_SHADE_PROBE; k++) {
-        const float4 *rp = sc.prims + 3 * (size_t)pi;
-        asm volatile("" : "+v"(rp));
-        float4 d0 = rp[0], d1 = rp[1], d2 = rp[2];
-        asm volatile("" ::"v"(d0.x), "v"(d0.w), "v"(d1.x), "v"(d1.w), "v"(d2.x), "v"(d2.w));
-    }
-#endif
     prim_hit(r, q0, q1, q2, s.pos, s.p, s.n, s.ptype);
 }
 

@@ -2386,61 +2386,5 @@ int gpuart_hip_test_launches(gpuart_hip_ctx *c, char *buf, size_t cap, size_t *l
 }
 #endif
 
-#ifdef GD_STEP_STATS
-/// diagnostic builds only: reads (and clears) k_trace's step statistics (kernels_pipeline.h): box steps, lanes in them, leaf steps, lanes in
-/// them, rounds of the wide loop, lanes holding a ray in them, refill episodes; then trav_pop's trips, the phase ticks and the packet walks'
-/// steps (box steps, active lanes in them, leaf steps, active lanes in them): 20 words
-int gpuart_hip_debug_step_stats(gpuart_hip_ctx *c, unsigned long long *out) {
-    if (!c || !out) return GPUART_HIP_ERR_ARG;
-    static unsigned long long zero[8];
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_step_stats), sizeof(zero)));
-    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_step_stats), zero, sizeof(zero)));
-    HIP_TRY(hipMemcpyFromSymbol(out + 8, HIP_SYMBOL(gd::g_pop_stats), 4 * sizeof(unsigned long long)));   // out: 16 words
-    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(gd::g_pop_stats), zero, 4 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemcpyFromSymbol(out + 12, HIP_SYMBOL(g_phase_ticks), 4 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_phase_ticks), zero, 4 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemcpyFromSymbol(out + 16, HIP_SYMBOL(gd::g_packet_stats), 4 * sizeof(unsigned long long)));  // out: 20 words
-    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(gd::g_packet_stats), zero, 4 * sizeof(unsigned long long)));
-    return 0;
-}
-#endif
-#ifdef GD_QUICK_CHECK
-/// diagnostic builds only: reads (and clears) the counters of the quick box answers checked against the six face tests (device_scene.h)
-int gpuart_hip_debug_quick_stats(gpuart_hip_ctx *c, unsigned long long *out) {
-    if (!c || !out) return GPUART_HIP_ERR_ARG;
-    static unsigned long long zero[8];
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(gd::g_quick_stats), sizeof(zero)));
-    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(gd::g_quick_stats), zero, sizeof(zero)));
-    return 0;
-}
-#endif
-#ifdef GD_RUN_TIMELINE
-/// diagnostic builds only: the per-wave timeline of the last k_run launch (kernel_run.h), 24 words per wave
-int gpuart_hip_debug_run_timeline(gpuart_hip_ctx *c, unsigned long long *out, size_t waves) {
-    if (!c || !out || waves > 8192) return GPUART_HIP_ERR_ARG;
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_run_timeline), waves * 24 * sizeof(unsigned long long)));
-    return 0;
-}
-/// diagnostic builds only: reads (and clears) the traversal-stack event counters (pushes, spilling pushes, pops, reloading pops)
-int gpuart_hip_debug_stack_events(gpuart_hip_ctx *c, unsigned long long *out) {
-    if (!c || !out) return GPUART_HIP_ERR_ARG;
-    static unsigned long long zero[4];
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(gd::g_stack_events), sizeof(zero)));
-    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(gd::g_stack_events), zero, sizeof(zero)));
-    return 0;
-}
-/// diagnostic builds only: reads (and clears) the busy-lane histogram of the k_run launches since the last call, 256 words
-int gpuart_hip_debug_run_hist(gpuart_hip_ctx *c, unsigned long long *out) {
-    if (!c || !out) return GPUART_HIP_ERR_ARG;
-    static unsigned long long zero[256];
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_run_hist), sizeof(zero)));
-    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_run_hist), zero, sizeof(zero)));
-    return 0;
-}
-#endif
+#include "diag_host.h"  // the gpuart_hip_debug_* entry points of the three diagnostic builds
 }  // extern "C"

@@ -52,10 +52,6 @@
 #ifndef RUN_TAIL_DIV
 #define RUN_TAIL_DIV 2                ///< tail: retire / shade once the finished lanes are 1/RUN_TAIL_DIV of the traversing ones
 #endif
-#ifndef RUN_PIPE
-#define RUN_PIPE 1                    ///< thin modes fetch ahead: what a ray's next step needs is requested as soon as the step before has decided
-                                      ///< it, and a leaf entered in this round is tested in the next one, after its triangles have arrived
-#endif
 #ifndef RUN_THIN
 #define RUN_THIN 4                    ///< most lanes per ray in the tail (1: never leave wide mode; 2; 4). Once the cursor is dry and a wave is
                                       ///< down to 32 (16) live paths and queries in flight, its rays are carried by pairs (quads) of lanes
@@ -66,29 +62,6 @@
 // 28 spills, 6-entry ring) lose everywhere. The shading code inside the kernel sets the register count; 4 waves it stays.
 #ifndef GD_RUN_WAVES
 #define GD_RUN_WAVES 4              ///< waves per SIMD: 8.5 KB of LDS per wave -> 18 waves per CU; <= 128 VGPRs (shading code inside)
-#endif
-
-#ifdef GD_RUN_TIMELINE
-// diagnostic build (tools/run_timeline.py): per wave, the 100 MHz clock at its start, when the cursor ran dry, at its end,
-// and the lane-rounds it spent traversing (active lanes summed over the rounds of the TRAVERSE loop / rounds)
-__device__ unsigned long long g_run_timeline[24 * 8192];
-__device__ unsigned long long g_run_hist[2 * 128];  // busy lane-time and wave-time per 25 us bucket
-#endif
-
-#ifdef GD_RUN_TIMELINE
-// one round of the TRAVERSE loop with `n` busy lanes (replicas included)
-#define GD_RUN_TL_ROUND(n)                                                                                                                     \
-    {                                                                                                                                          \
-        tl_lanes += (unsigned long long)(n); tl_rounds++; if (exhausted) tl_tail_rounds++;                                                     \
-        if (M == 2) tl_r2++; else if (M == 4) tl_r4++;                                                                                         \
-        if (!exhausted) { tl_nready += n_ready; tl_nshade += n_shade; }                                                                        \
-        const unsigned long long now = wall_clock64();                                                                                         \
-        const unsigned bucket = (unsigned)min((now - (tl_zero ? tl_zero : tl_start)) / 2500ull, 127ull);                                       \
-        if (lane_id() == 0) { tl_hist[bucket] += (unsigned)(now - tl_prev) * (unsigned)(n); tl_hist[128 + bucket] += (unsigned)(now - tl_prev); } \
-        tl_prev = now;                                                                                                                         \
-    }
-#else
-#define GD_RUN_TL_ROUND(n)
 #endif
 
 namespace {
@@ -120,7 +93,7 @@ k_run(Scene sc, Frame f, gpuart_params P, SeedBatch seeds, PathBuffers b, int j,
     // every group, `sub` = this lane's index in its group. Never entered by the
     // counting variants (their counters are per lane) and by trees with irregular boxes (comparison-form box tests).
     constexpr bool THIN_OK = RUN_THIN > 1 && !COUNT && GD_BOXES_OF(TYPES) == GD_BOXES_FAST;
-    // closest-hit queries enter the nearer child first (device_scene.h, GD_NEAREST); the counters of mode 4 count that walk
+    // closest-hit queries enter the nearer child first (device_scene.h, "Visiting order"); the counters of mode 4 count that walk
     constexpr bool NEAR = GD_NEAREST_OF(TYPES) && !REFWORK;
     uint32_t M = 1, sub = 0;                                   // M wave-uniform
     unsigned long long lead = ~0ull;                           // wave-uniform
@@ -131,15 +104,16 @@ k_run(Scene sc, Frame f, gpuart_params P, SeedBatch seeds, PathBuffers b, int j,
     F3 ro = f3(0, 0, 0), rd = f3(1, 0, 0), rdiv = f3(1, 1, 1);
     Trav t; t.state = TRAV_DONE; t.closest = 0; t.hit_prim = GD_NO_PRIM; t.node = 0; t.entry = 0; t.second = 0;
 
-#ifdef GD_RUN_TIMELINE
-    unsigned long long tl_start = wall_clock64(), tl_dry = 0, tl_lanes = 0, tl_rounds = 0, tl_prev = tl_start, tl_nready = 0, tl_nshade = 0;
-    unsigned long long tl_tail_trav = 0, tl_tail_other = 0, tl_tail_rounds = 0, tl_tail_trig = 0, tl_mark = tl_start;
-    unsigned long long tl_m2 = 0, tl_m4 = 0, tl_r2 = 0, tl_r4 = 0;  // when the wave went to pairs / quads, rounds in either mode
-    unsigned long long tp_box = 0, tp_nbox = 0, tp_leaf = 0, tp_nleaf = 0, tp_loop = 0, tp_busy = 0;  // shader-clock cycles of the quad rounds: box steps, leaf steps, whole rounds
-    __shared__ unsigned tl_hist[2 * 128];
-    tl_hist[lane_id()] = 0; tl_hist[64 + lane_id()] = 0; tl_hist[128 + lane_id()] = 0; tl_hist[192 + lane_id()] = 0;
-    const unsigned long long tl_zero = g_run_hist[2 * 128 - 1];  // the host stores the launch's reference clock there (0: use own start)
-#endif
+    // diag.h, the wave's timeline (tools/run_timeline.py). tl_m* / tl_r*: when the wave went to pairs / quads, rounds in either mode; tp_*:
+    // shader-clock cycles of the quad rounds — box steps, leaf steps, whole rounds; tl_zero: the launch's reference clock, which the host
+    // stores in the histogram's last word (0: use own start)
+    GD_TIMELINE(unsigned long long tl_start = wall_clock64(), tl_dry = 0, tl_lanes = 0, tl_rounds = 0, tl_prev = tl_start, tl_nready = 0, tl_nshade = 0;)
+    GD_TIMELINE(unsigned long long tl_tail_trav = 0, tl_tail_other = 0, tl_tail_rounds = 0, tl_tail_trig = 0, tl_mark = tl_start;)
+    GD_TIMELINE(unsigned long long tl_m2 = 0, tl_m4 = 0, tl_r2 = 0, tl_r4 = 0;)
+    GD_TIMELINE(unsigned long long tp_box = 0, tp_nbox = 0, tp_leaf = 0, tp_nleaf = 0, tp_loop = 0, tp_busy = 0;)
+    GD_TIMELINE(__shared__ unsigned tl_hist[2 * 128];)
+    GD_TIMELINE(tl_hist[lane_id()] = 0; tl_hist[64 + lane_id()] = 0; tl_hist[128 + lane_id()] = 0; tl_hist[192 + lane_id()] = 0;)
+    GD_TIMELINE(const unsigned long long tl_zero = g_run_hist[2 * 128 - 1];)
     for (;;) {
         bool start = false;  // this lane begins a query in this round
         // ---- a finished nearest-first query that cannot vouch for its answer walks again, in the reference's order (every replica alike)
@@ -266,9 +240,7 @@ k_run(Scene sc, Frame f, gpuart_params P, SeedBatch seeds, PathBuffers b, int j,
             }
             if (base >= total) {
                 exhausted = true;
-#ifdef GD_RUN_TIMELINE
-                tl_dry = wall_clock64();
-#endif
+                GD_TIMELINE(tl_dry = wall_clock64();)
                 continue;
             }
             const uint32_t slot = base + lane_id();
@@ -302,9 +274,7 @@ k_run(Scene sc, Frame f, gpuart_params P, SeedBatch seeds, PathBuffers b, int j,
                 thin_regroup(to, flying, xfer, ring_a, ring_b, spill, ent, unused, ro, rd, rdiv, t, st);
                 if ((uint32_t)lane_id() / to >= (uint32_t)__popcll(flying)) ent = SLOT_INVALID;  // the groups beyond the rays in flight are idle
                 M = to;
-#ifdef GD_RUN_TIMELINE
-                if (M == 2) tl_m2 = wall_clock64(); else { tl_m4 = wall_clock64(); }
-#endif
+                GD_TIMELINE(if (M == 2) tl_m2 = wall_clock64(); else { tl_m4 = wall_clock64(); })
                 sub = (uint32_t)lane_id() & (M - 1);
                 lead = M == 4 ? 0x1111111111111111ull : 0x5555555555555555ull;
             }
@@ -333,15 +303,12 @@ k_run(Scene sc, Frame f, gpuart_params P, SeedBatch seeds, PathBuffers b, int j,
         if (__ballot(ent != SLOT_INVALID) == 0) break;  // nothing in flight; PRODUCE could not make anything: all done
 
         // ---- TRAVERSE until enough lanes have finished (a lane without an entry is in state DONE) ---------------------
-#ifdef GD_RUN_TIMELINE
-        { const unsigned long long now = wall_clock64(); if (exhausted) { tl_tail_other += now - tl_mark; tl_tail_trig++; } tl_mark = now; }
-#endif
+        GD_TIMELINE({ const unsigned long long now = wall_clock64(); if (exhausted) { tl_tail_other += now - tl_mark; tl_tail_trig++; } tl_mark = now; })
         if (THIN_OK && M > 1) {
             // the same loop with M lanes per ray: ballots count groups (their first lanes), thresholds are in lanes
             auto thin_rounds = [&](auto width) {
                 constexpr int W = decltype(width)::value;
                 constexpr unsigned long long LEAD = W == 4 ? 0x1111111111111111ull : 0x5555555555555555ull;
-#if RUN_PIPE
                 // Software-pipelined: a ray's record / triangles are requested the moment the step before has decided what comes next
                 // (thin_fetch), and a triangle leaf entered in this round's box phase is tested in the NEXT round's leaf phase — its
                 // data then arrives beside the other rays' steps instead of stalling the whole wave at the head of the leaf phase.
@@ -349,54 +316,30 @@ k_run(Scene sc, Frame f, gpuart_params P, SeedBatch seeds, PathBuffers b, int j,
                 pf.a = pf.b = pf.c = make_float4(0, 0, 0, 0);
                 thin_fetch<W>(sc, t, sub, pf);
                 bool fresh = false;  // this lane's leaf was entered in this round: its triangles are on their way
-#endif
                 for (;;) {
-#ifdef GD_RUN_TIMELINE
-                    const unsigned long long pc0 = __builtin_amdgcn_s_memtime();
-#endif
-#if RUN_PIPE
+                    GD_TIMELINE(const unsigned long long pc0 = __builtin_amdgcn_s_memtime();)
                     if (t.state == TRAV_DESCEND) {
                         trav_step_box_thin_on<W, NEAR>(ro, rd, rdiv, t, st, sub, pf, sc.box_slack, !(ent & (RUN_F_SHADOW | RUN_F_REWALK)), ThinPrefetch{sc.recs, sc.prims, warm_sink});
                         thin_fetch<W>(sc, t, sub, pf);
                         fresh = (t.state & 8) != 0;
                     }
                     const bool leaf_now = (t.state & 1) != 0 && !fresh;
-#else
-                    if (t.state == TRAV_DESCEND) trav_step_box_thin<W, NEAR>(sc, ro, rd, rdiv, t, st, sub, !(ent & (RUN_F_SHADOW | RUN_F_REWALK)), warm_sink);
-                    const bool leaf_now = (t.state & 1) != 0;
-#endif
-#ifdef GD_RUN_TIMELINE
-                    if (W == 4) { tp_box += __builtin_amdgcn_s_memtime() - pc0; tp_nbox++; }
-#endif
+                    GD_TIMELINE(if (W == 4) { tp_box += __builtin_amdgcn_s_memtime() - pc0; tp_nbox++; })
                     unsigned long long at_leaf = __ballot(leaf_now) & LEAD;
                     unsigned long long busy = __ballot(t.state != TRAV_DONE) & LEAD;
                     const uint32_t waiting = (uint32_t)__popcll(at_leaf);
                     if (at_leaf && (W * waiting >= tune.leaf_lanes || tune.leaf_share * waiting >= (uint32_t)__popcll(busy))) {
-#ifdef GD_RUN_TIMELINE
-                        const unsigned long long pl0 = __builtin_amdgcn_s_memtime();
-#endif
+                        GD_TIMELINE(const unsigned long long pl0 = __builtin_amdgcn_s_memtime();)
                         if (leaf_now) {
-#if RUN_PIPE
                             trav_step_leaf_thin_on<W, TYPES, NEAR>(sc, ro, rd, t, st, sub, pf, !(ent & (RUN_F_SHADOW | RUN_F_REWALK)));
-#else
-                            trav_step_leaf_thin<W, TYPES, NEAR>(sc, ro, rd, t, st, sub, !(ent & (RUN_F_SHADOW | RUN_F_REWALK)));
-#endif
                             if (!REFWORK && (ent & RUN_F_SHADOW) && t.hit_prim != GD_NO_PRIM) t.state = TRAV_DONE;
-#if RUN_PIPE
                             thin_fetch<W>(sc, t, sub, pf);
-#endif
                         }
                         busy = __ballot(t.state != TRAV_DONE) & LEAD;
-#ifdef GD_RUN_TIMELINE
-                        if (W == 4) { tp_leaf += __builtin_amdgcn_s_memtime() - pl0; tp_nleaf++; }
-#endif
+                        GD_TIMELINE(if (W == 4) { tp_leaf += __builtin_amdgcn_s_memtime() - pl0; tp_nleaf++; })
                     }
-#if RUN_PIPE
                     fresh = false;
-#endif
-#ifdef GD_RUN_TIMELINE
-                    if (W == 4) { tp_loop += __builtin_amdgcn_s_memtime() - pc0; tp_busy += (uint32_t)__popcll(busy); }
-#endif
+                    GD_TIMELINE(if (W == 4) { tp_loop += __builtin_amdgcn_s_memtime() - pc0; tp_busy += (uint32_t)__popcll(busy); })
                     GD_RUN_TL_ROUND((uint32_t)__popcll(busy))
                     if (!busy) break;
                     if ((uint32_t)BLOCK - W * (uint32_t)__popcll(busy) >= tune.refill_lanes) {
@@ -434,13 +377,10 @@ k_run(Scene sc, Frame f, gpuart_params P, SeedBatch seeds, PathBuffers b, int j,
                 if (n_ready || n_shade || !exhausted || finished * RUN_TAIL_DIV >= (uint32_t)__popcll(busy)) break;
             }
         }
-#ifdef GD_RUN_TIMELINE
-        { const unsigned long long now = wall_clock64(); if (exhausted) tl_tail_trav += now - tl_mark; tl_mark = now; }
-#endif
+        GD_TIMELINE({ const unsigned long long now = wall_clock64(); if (exhausted) tl_tail_trav += now - tl_mark; tl_mark = now; })
     }
     if (COUNT) flush_counters(wc, segments, gcounters);
-#ifdef GD_RUN_TIMELINE
-    if (lane_id() == 0 && blockIdx.x < 8192) {
+    GD_TIMELINE(if (lane_id() == 0 && blockIdx.x < 8192) {
         unsigned long long *o = g_run_timeline + 24 * blockIdx.x;
         o[12] = tl_m2; o[13] = tl_m4; o[14] = tl_r2; o[15] = tl_r4;
         o[16] = tp_box; o[17] = tp_nbox; o[18] = tp_leaf; o[19] = tp_nleaf; o[20] = tp_loop; o[21] = tp_busy; o[22] = 0; o[23] = 0;
@@ -448,8 +388,7 @@ k_run(Scene sc, Frame f, gpuart_params P, SeedBatch seeds, PathBuffers b, int j,
         o[0] = tl_start; o[1] = tl_dry; o[2] = wall_clock64(); o[3] = tl_lanes; o[4] = tl_rounds;
         for (int k = 0; k < 256; k++) if (tl_hist[k]) atomicAdd(&g_run_hist[k], (unsigned long long)tl_hist[k]);
         o[5] = ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32) | (unsigned)__builtin_amdgcn_s_getreg(63492);  // XCC_ID, HW_ID
-    }
-#endif
+    })
 }
 
 }  // namespace

@@ -33,11 +33,6 @@ struct TraceTuning {
 // =================================================================================================
 namespace {
 
-#ifdef GD_STEP_STATS
-__device__ unsigned long long g_step_stats[8];
-__device__ unsigned long long g_phase_ticks[4];  // k_trace: summed over waves, shader-clock ticks in refill / traverse / settle + retire
-#endif
-
 /// Per-path state of one run of the wavefront pipeline: `batch` passes x `n_slots` pixel slots (pixel slot p: 8x8 tile
 /// p/64 of the tile in row-major tile order, pixel p%64 inside it), all arrays SoA and 16-byte aligned.
 /// Path slot s = pixel slot x batch + pass (slot_pass / slot_pixel_slot below): the passes of a run are INTERLEAVED per
@@ -162,20 +157,11 @@ __global__ void __launch_bounds__(TO_THREADS) k_tile_order(uint32_t *__restrict_
     }
 }
 
-/// Lane 0's value in every lane, where all 64 lanes are active (the persistent loops' wave-uniform control flow). GD_UNIFORM = 1: through
-/// v_readfirstlane — a SCALAR the compiler knows to be the same in every lane, so that what is derived from it (the chunk bounds, `exhausted`)
-/// lives in scalar registers and wave-uniform branches on it are scalar branches; a shuffle (ds_bpermute, the code of rounds 1-5: 0) yields
-/// a vector value, the loop exits that test it became execution-mask arithmetic on both paths.
-#ifndef GD_UNIFORM
-#define GD_UNIFORM 1
-#endif
-GD_FN uint32_t wave_value(uint32_t v) {
-#if GD_UNIFORM
-    return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-#else
-    return (uint32_t)__shfl(v, 0, 64);
-#endif
-}
+/// Lane 0's value in every lane, where all 64 lanes are active (the persistent loops' wave-uniform control flow). Through v_readfirstlane:
+/// a SCALAR the compiler knows to be the same in every lane, so that what is derived from it (the chunk bounds, `exhausted`) lives in
+/// scalar registers and wave-uniform branches on it are scalar branches. A shuffle (ds_bpermute, the code of rounds 1-5) yields a vector
+/// value: the loop exits that test it became execution-mask arithmetic on both paths (profiles/r06/step_isa_budget.txt).
+GD_FN uint32_t wave_value(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 
 /// The traversal stack of this lane: its column of the wave's LDS ring, its column of the launch's spill area
 /// (`wave` of `total_lanes / 64` waves).
@@ -656,7 +642,7 @@ k_trace(Scene sc, Frame f, gpuart_params P, PathBuffers b, int seg_c, int seg_s,
     // Thin-wave modes (device_scene.h): once the queue is empty and the wave is down to 32 (16) rays, pairs (quads) of lanes carry
     // them. Not in the counting variant (its counters are per lane) nor for trees with irregular boxes.
     constexpr bool THIN_OK = GD_TRACE_THIN > 1 && !COUNT && GD_BOXES_OF(TYPES) == GD_BOXES_FAST;
-    // closest-hit queries enter the nearer child first (device_scene.h, GD_NEAREST): fewer node visits; a query whose answer that
+    // closest-hit queries enter the nearer child first (device_scene.h, "Visiting order"): fewer node visits; a query whose answer that
     // walk cannot certify goes round again in the reference's order (`refwalk`)
     constexpr bool NEAR = GD_NEAREST_OF(TYPES) && !COUNT;
     uint32_t M = 1, sub = 0;  // M wave-uniform
@@ -712,21 +698,14 @@ k_trace(Scene sc, Frame f, gpuart_params P, PathBuffers b, int seg_c, int seg_s,
         }
     };
 
-#ifdef GD_STEP_STATS
-    // diagnostic build (never the product): how full the wave's steps are — box steps and the lanes in them, leaf steps and the lanes in
-    // them, rounds of the wide loop and the lanes that hold a ray in them, refill episodes (tools/step_stats.py)
-    uint32_t ss_box = 0, ss_box_lanes = 0, ss_leaf = 0, ss_leaf_lanes = 0, ss_rounds = 0, ss_held = 0, ss_refills = 0;
-    unsigned long long ss_t_refill = 0, ss_t_trav = 0, ss_t_retire = 0, ss_mark = __builtin_amdgcn_s_memtime();  // shader-clock ticks per phase of the outer loop
-#define GD_SS_PHASE(acc) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); acc += now_ - ss_mark; ss_mark = now_; }
-#else
-#define GD_SS_PHASE(acc)
-#endif
+    // diag.h: how full the wave's steps are — box steps and the lanes in them, leaf steps and the lanes in them, rounds of the wide loop and
+    // the lanes that hold a ray in them, refill episodes —, and the shader-clock ticks per phase of the outer loop (tools/step_stats.py)
+    GD_STATS(uint32_t ss_box = 0, ss_box_lanes = 0, ss_leaf = 0, ss_leaf_lanes = 0, ss_rounds = 0, ss_held = 0, ss_refills = 0;)
+    GD_STATS(unsigned long long ss_t_refill = 0, ss_t_trav = 0, ss_t_retire = 0, ss_mark = __builtin_amdgcn_s_memtime();)
     for (;;) {
         // ---- refill idle lanes from the queue
         unsigned long long idle = __ballot(slot == SLOT_INVALID);
-#ifdef GD_STEP_STATS
-        ss_refills++;
-#endif
+        GD_STATS(ss_refills++;)
         bool in_packet = false;  // wave-uniform: this round walks one packet
         bool hold = false;       // wave-uniform: the next entries are packet entries, and the wave still holds queries
         while (idle && !exhausted) {
@@ -811,9 +790,7 @@ k_trace(Scene sc, Frame f, gpuart_params P, PathBuffers b, int seg_c, int seg_s,
         } else
         // ---- traverse until enough lanes have finished (a lane without a ray is in state DONE)
         for (;;) {
-#ifdef GD_STEP_STATS
-            { const unsigned long long dd = __ballot(t.state == TRAV_DESCEND); if (dd) { ss_box++; ss_box_lanes += (uint32_t)__popcll(dd); } ss_rounds++; ss_held += (uint32_t)__popcll(__ballot(slot != SLOT_INVALID)); }
-#endif
+            GD_STATS({ const unsigned long long dd = __ballot(t.state == TRAV_DESCEND); if (dd) { ss_box++; ss_box_lanes += (uint32_t)__popcll(dd); } ss_rounds++; ss_held += (uint32_t)__popcll(__ballot(slot != SLOT_INVALID)); })
             if (t.state == TRAV_DESCEND) trav_step_box<COUNT, GD_BOXES_OF(TYPES), NEAR>(sc, Ray{ro, rd}, rdiv, t, st, COUNT ? &wc : nullptr, !shadow && !refwalk);
             unsigned long long at_leaf = __ballot((t.state & 1) != 0);  // the leaf states are the odd ones
             unsigned long long descending = __ballot(t.state == TRAV_DESCEND);
@@ -821,9 +798,7 @@ k_trace(Scene sc, Frame f, gpuart_params P, PathBuffers b, int seg_c, int seg_s,
             // a wave that is draining its last rays must not hold leaves back for a quorum it can no longer reach
             const uint32_t waiting = (uint32_t)__popcll(at_leaf);
             if (at_leaf && (waiting >= tune.leaf_lanes || tune.leaf_share * waiting >= waiting + (uint32_t)__popcll(descending))) {
-#ifdef GD_STEP_STATS
-                ss_leaf++; ss_leaf_lanes += waiting;
-#endif
+                GD_STATS(ss_leaf++; ss_leaf_lanes += waiting;)
                 if (t.state & 1) {
                     trav_step_leaf<false, COUNT, TYPES, NEAR>(sc, Ray{ro, rd}, t, st, COUNT ? &wc : nullptr, !shadow && !refwalk);
                     // the reference only asks a shadow query whether anything was hit: one accepted hit settles it
@@ -857,13 +832,11 @@ k_trace(Scene sc, Frame f, gpuart_params P, PathBuffers b, int seg_c, int seg_s,
         GD_SS_PHASE(ss_t_retire)
     }
     if (COUNT) flush_counters(wc, 0, gcounters);
-#ifdef GD_STEP_STATS
-    if (lane_id() == 0) {
+    GD_STATS(if (lane_id() == 0) {
         const uint32_t v[7] = {ss_box, ss_box_lanes, ss_leaf, ss_leaf_lanes, ss_rounds, ss_held, ss_refills};
         for (int k = 0; k < 7; k++) atomicAdd(&g_step_stats[k], (unsigned long long)v[k]);
         atomicAdd(&g_phase_ticks[0], ss_t_refill); atomicAdd(&g_phase_ticks[1], ss_t_trav); atomicAdd(&g_phase_ticks[2], ss_t_retire);
-    }
-#endif
+    })
 }
 
 // ---- wavefront stage 2: shade segment `seg` of every path in queue[seg&1] (path_tracing.glsl:182-233) ---
@@ -965,10 +938,12 @@ __global__ void __launch_bounds__(BLOCK, GD_DIRECT_WAVES) k_direct_persistent(Sc
     // thin-wave modes (device_scene.h) for the end of the frame: once the pixel cursor is dry and the wave is down to 32 (16)
     // pixels, pairs (quads) of lanes carry them
     constexpr bool THIN_OK = GD_TRACE_THIN > 1 && GD_BOXES_OF(TYPES) == GD_BOXES_FAST;
-    // Nearer child first (device_scene.h, GD_NEAREST) does not pay here: a frame's primary rays are coherent and half of its queries are
-    // Sun-shadow queries, which keep the reference's order anyway — with the certificate's bookkeeping the frame took 0.710 instead of
-    // 0.688 ms at 1080p, 1.715 instead of 1.695 at 4K (profiles/r04/direct_lighting_order.txt). GD_NEAREST_DIRECT=1 turns it on.
-    constexpr bool NEAR = GD_NEAREST_OF(TYPES) && GD_NEAREST_DIRECT;
+    // Every query here keeps the reference's order. Nearer child first (device_scene.h, "Visiting order") does not pay: a frame's primary
+    // rays are coherent and half of its queries are Sun-shadow queries, which keep the reference's order anyway — with the certificate's
+    // bookkeeping the frame took 0.710 instead of 0.688 ms at 1080p, 1.715 instead of 1.695 at 4K (profiles/r04/direct_lighting_order.txt).
+    // NEAR stays as a constant, and `refwalk` with it: what only a nearest-first walk sets still travels through thin_regroup's tag, and
+    // taking it out changes this kernel's registers and instructions (profiles/switches.txt).
+    constexpr bool NEAR = false;
     uint32_t M = 1, sub = 0;  // M wave-uniform
     const float AMBIENT = 0.15f;
     const F3 sun = f3(P.sunDirAlt[0], P.sunDirAlt[1], P.sunDirAlt[2]);

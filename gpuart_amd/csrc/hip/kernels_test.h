@@ -64,7 +64,7 @@ __global__ void k_test_aabb(const float4 *rs, const float4 *rd, const float4 *bm
         // the tightest a tree could have), and the six face tests where it is withdrawn
         const float pmax = fmaxf(fmaxf(fmaxf(fabsf(lo.x), fabsf(lo.y)), fmaxf(fabsf(lo.z), fabsf(hi.x))), fmaxf(fabsf(hi.y), fabsf(hi.z)));
         const bool sub = !(gq_plane_ok(lo.x) & gq_plane_ok(lo.y) & gq_plane_ok(lo.z) & gq_plane_ok(hi.x) & gq_plane_ok(hi.y) & gq_plane_ok(hi.z));  // (as converter.h)
-        const float cs = gq_ray_slack((GD_QUICK_BOXES && quick && !sub) ? gq_slack_of_tree(pmax) : __builtin_inff(), r.o.x, r.o.y, r.o.z, r.d.x, r.d.y, r.d.z, rdiv.x, rdiv.y, rdiv.z);
+        const float cs = gq_ray_slack((quick && !sub) ? gq_slack_of_tree(pmax) : __builtin_inff(), r.o.x, r.o.y, r.o.z, r.d.x, r.d.y, r.d.z, rdiv.x, rdiv.y, rdiv.z);
         if (!box_quick(r, rdiv, lo, hi, cs, pos, h)) h = aabb_entry(r, rdiv, lo, hi, pos);
     } else
         h = aabb_entry<true>(r, rdiv, lo, hi, pos);

@@ -231,7 +231,7 @@ def random_wild_case(seed):
 # triangle's box has zero thickness, its entry parameter and the triangle's own hit parameter are the same number computed two
 # ways, a few ulps apart in either direction: which of two coincident surfaces the reference reports then hinges on the
 # order in which its walk meets them and on what it pruned in between. A walk in any other order has to notice (device_scene.h,
-# GD_NEAREST) — this class is what checks that it does.
+# "Visiting order") — this class is what checks that it does.
 def lattice_prims(rs, n):
     L = lambda lo, hi: f32(rs.randint(int(lo * 4), int(hi * 4) + 1) / 4.0)
     prims = []

@@ -49,7 +49,7 @@ REF_LEAF, REF_TRIS, REF_TWO, REF_SMALL, REF_INDEX = 1 << 31, 1 << 30, 1 << 29, 1
 DATA_QUADS = (1, 2, 3, 4)            # StoreDataIntoBVH of sphere, disc, triangle, cone
 NON_PAD = ([0, 1, 2, 3], [0, 1, 2, 3, 4, 5, 6], [0, 1, 2, 4, 5, 6, 8, 9, 10], list(range(15)))
 MAX_DEPTH = 1024
-MAX_PRIMS = 0x05555540               # 48 bytes x index and 64 bytes x index fit 32 bits on the device (device_scene.h GD_ADDR32)
+MAX_PRIMS = 0x05555540               # 48 bytes x index and 64 bytes x index fit 32 bits on the device (device_scene.h trav_step_box and the leaf tests)
 MAX_RECS = 0x03fffff0
 COORD_LIMIT = np.float32(1048576.0)  # 2^20
 PLANE_MIN = np.float32(2.0 ** -60)

@@ -1297,7 +1297,7 @@ def test_random_scenes_soak(wild):
     # ends of the float range, denormals, odd cameras / user spheres / Sun altitudes; 8 000 cases of it found no difference)
     # "lattice" (round 4): coplanar, overlapping axis-aligned triangles and discs, coincident spheres — boxes that are not
     # conservative for their primitives in fp32, where the reference's winner hinges on its visiting order and the fast kernels'
-    # nearest-first walk has to notice (device_scene.h GD_NEAREST): without its certificate 133 of 1 500 such scenes differed
+    # nearest-first walk has to notice (device_scene.h "Visiting order"): without its certificate 133 of 1 500 such scenes differed
     # "grazing" (round 5): fans of triangulated sheets seen edge-on — frames full of the reference's phantom hits (shaders/triangle.glsl:50-76
     # at grazing angles), which only a walk in the reference's order reproduces: the default walks must equal the oracle (which equals the
     # reference's GLSL on 2 000 cases of the class); the opt-in nearest-first walk is rendered too, its differing scenes counted, not failed

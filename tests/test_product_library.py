@@ -154,6 +154,49 @@ def test_the_tree_libraries_the_suite_loads_are_copies_of_the_products(name):
     assert filecmp.cmp(product, tested, shallow=False), "%s and %s differ" % (product, tested)
 
 
+# ---- CPU: the compile-time knobs and the three diagnostic builds --------------------------------------------------------------------
+
+CSRC = os.path.join(ROOT, "gpuart_amd", "csrc")
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+DIAGNOSTIC_BUILDS = ("GD_STEP_STATS", "GD_QUICK_CHECK", "GD_RUN_TIMELINE")
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="no hipcc here")
+@pytest.mark.parametrize("name", DIAGNOSTIC_BUILDS)
+def test_a_diagnostic_build_still_compiles(name):
+    """No test builds the diagnostic libraries (csrc/hip/diag.h; tools/README.md), so each must at least pass the compiler's front end,
+    host and device side, with the Makefile's own flags and the test hooks: what a diagnostic site names must still exist."""
+    flags = subprocess.run(["make", "-s", "-C", CSRC, "--eval", "print-hipflags: ; @echo $(HIPFLAGS)", "print-hipflags"], check=True,
+                           capture_output=True, text=True).stdout.split()
+    assert "--offload-arch=gfx950" in flags, "HIPFLAGS of csrc/Makefile not read: %s" % flags
+    r = subprocess.run([HIPCC] + flags + ["-DGPUART_HIP_TEST_HOOKS", "-D" + name, "-fsyntax-only", "hip/gpuart_hip.hip"], cwd=CSRC,
+                       capture_output=True, text=True)
+    assert r.returncode == 0, "-D%s no longer compiles:\n%s" % (name, r.stderr[-4000:])
+
+
+def test_the_knob_table_lists_what_the_sources_let_a_build_set():
+    """tools/README.md's table of compile-time knobs and diagnostic builds against the device sources: every `#ifndef NAME` that is
+    followed by `#define NAME` (a default a build may override) and every `#ifdef GD_*` (a diagnostic build), no more and no fewer. A
+    switch added for an experiment shows up here until it is listed or gone."""
+    import glob
+    found = set()
+    for path in sorted(glob.glob(os.path.join(CSRC, "hip", "*.h"))) + [os.path.join(CSRC, "display", "display.hip")]:
+        with open(path) as f:
+            text = f.read()
+        found |= set(re.findall(r"^[ \t]*#[ \t]*ifndef[ \t]+(\w+)[^\n]*\n[ \t]*#[ \t]*define[ \t]+\1\b", text, re.M))
+        found |= set(re.findall(r"^[ \t]*#[ \t]*ifdef[ \t]+(GD_\w+)", text, re.M))
+        found |= set(re.findall(r"\bdefined[ \t]*\(?[ \t]*(GD_\w+)", text))
+    with open(os.path.join(ROOT, "tools", "README.md")) as f:
+        doc = f.read()
+    section = doc.split("## Compile-time knobs and diagnostic builds", 1)
+    assert len(section) == 2, "tools/README.md has no section 'Compile-time knobs and diagnostic builds'"
+    listed = re.findall(r"^\| `(\w+)` \|", section[1].split("\n## ", 1)[0], re.M)
+    assert len(listed) == len(set(listed)), "listed twice: %s" % sorted(n for n in set(listed) if listed.count(n) > 1)
+    assert set(DIAGNOSTIC_BUILDS) <= found, "diagnostic builds the sources no longer know: %s" % sorted(set(DIAGNOSTIC_BUILDS) - found)
+    assert found == set(listed), "in the sources, not in the table: %s; in the table, not in the sources: %s" % (
+        sorted(found - set(listed)), sorted(set(listed) - found))
+
+
 # ---- GPU: the product pair against the reference, in fresh child processes --------------------------------------------------------
 
 

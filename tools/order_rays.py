@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Looks for single RAYS on which the fast kernels' closest-hit walk (nearer child first + certificate, device_scene.h GD_NEAREST)
+"""Looks for single RAYS on which the fast kernels' closest-hit walk (nearer child first + certificate, device_scene.h "Visiting order")
 and the reference-order walk disagree, through the traversal test hook (gpuart_hip_test_traverse, any_hit 2 vs 0): camera rays,
 then rounds of bounce rays off the hits (cosine-hemisphere directions from the device's own sampler, fresh seed per round) —
 the population a path tracer produces. Disagreeing rays are printed and saved with the tree (npz) for a CPU post-mortem

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Does the order in which the fast kernels visit a node's children (nearer child first, device_scene.h GD_NEAREST) ever change a
+"""Does the order in which the fast kernels visit a node's children (nearer child first, device_scene.h "Visiting order") ever change a
 pixel? Two renderers on one GPU render the same passes of the same scene — one in the fast mode under test (0, 3 or 5), one in
 mode 1 ("reference work": k_run in the reference's lower-then-upper order, every query in full) — and the accumulators are
 compared bit for bit after every chunk of K passes. No oracle involved: the reference-order kernels are pinned to the reference by
