@@ -170,6 +170,20 @@ def edges_params(params):
     return _params(EdgesParams, EDGES_DEFAULTS, "edge-resolve", params)
 
 
+class UpscaleParams(C.Structure):
+    """gpuart_upscale_params (include/gpuart_upscale.h)."""
+    _fields_ = [("normal_min", C.c_float), ("plane_tol", C.c_float)]
+
+
+UPSCALE_DEFAULTS = dict(normal_min=0.95, plane_tol=0.02)
+UPSCALE_SCALES = (2, 3, 4)  # GPUART_UPSCALE_MIN_SCALE..GPUART_UPSCALE_MAX_SCALE
+
+
+def upscale_params(params):
+    """None (the library's defaults), an UpscaleParams, or a dict of fields that replace the defaults -> UpscaleParams or None."""
+    return _params(UpscaleParams, UPSCALE_DEFAULTS, "upscaler", params)
+
+
 class DespeckleParams(C.Structure):
     """gpuart_despeckle_params (include/gpuart_despeckle.h)."""
     _fields_ = [("radius", C.c_uint32), ("rank", C.c_uint32), ("k", C.c_float), ("floor", C.c_float), ("min_count", C.c_uint32)]
@@ -379,6 +393,11 @@ def edges_lib():
 def despeckle_lib():
     """libgpuart_despeckle.so; raises NativeLibraryMissing if it has not been built (no fallback)."""
     return _image_lib("despeckle")
+
+
+def upscale_lib():
+    """libgpuart_upscale.so; raises NativeLibraryMissing if it has not been built (no fallback)."""
+    return _image_lib("upscale")
 
 
 def refit_lib():
@@ -1315,8 +1334,23 @@ class Backend:
         context's device they are written in place (torch's current stream is synchronised first, the context before returning); the
         returned hits are then that tensor. Otherwise a RAY_HIT record array (th, tw) and an int32 array (th, tw), written into the
         NumPy arrays `out` / `prims_out` when given."""
-        import torch
         _, _, tw, th = self.tile
+        return self._gbuffer(tw, th, out, prims_out,
+                             lambda hits, prims: self.L.gpuart_hip_gbuffer(self.ctx, _user_sphere(user_sphere), hits, prims))
+
+    def gbuffer_scaled(self, scale, user_sphere=None, out=None, prims_out=None):
+        """gpuart_hip_gbuffer_scaled: the G-buffer of the frame `scale` (2..4) times larger in each direction, for the tile scaled alike:
+        what gbuffer() returns on a context resized to scale*W x scale*H with the tile (scale*x0, scale*y0, scale*tw, scale*th), bit for
+        bit -> (hits, prims) of (scale*th, scale*tw) pixels. `out` and `prims_out` as gbuffer's, at that size."""
+        _, _, tw, th = self.tile
+        s = int(scale)
+        return self._gbuffer(tw * max(s, 0), th * max(s, 0), out, prims_out,
+                             lambda hits, prims: self.L.gpuart_hip_gbuffer_scaled(self.ctx, C.c_uint32(s & 0xffffffff), _user_sphere(user_sphere), hits, prims))
+
+    def _gbuffer(self, tw, th, out, prims_out, call):
+        """What gbuffer and gbuffer_scaled share: the (th, tw) outputs checked or made, `call(hits, prims)` on their device pointers, the
+        wait, and the copy into NumPy arrays where no tensors were given."""
+        import torch
         dev = torch.device("cuda", self.device)
         on_device = out is not None and type(out).__module__.startswith("torch")
         if on_device:
@@ -1330,7 +1364,7 @@ class Backend:
             hits = torch.empty((th, tw, 8), dtype=torch.float32, device=dev)
             prims = torch.empty((th, tw), dtype=torch.int32, device=dev)
         torch.cuda.current_stream(dev).synchronize()
-        self._chk(self.L.gpuart_hip_gbuffer(self.ctx, _user_sphere(user_sphere), C.c_void_p(hits.data_ptr()), C.c_void_p(prims.data_ptr())))
+        self._chk(call(C.c_void_p(hits.data_ptr()), C.c_void_p(prims.data_ptr())))
         self.finish()
         if on_device:
             return hits, prims
@@ -1746,6 +1780,36 @@ class Renderer:
             return None
         return out
 
+    def read_upscaled(self, source="denoised", scale=2, lum_floor=CONVERGE_DEFAULT_FLOOR, params=None):
+        """Renderer::ReadUpscaled: the frame `source` names (DISPLAY_SOURCES) upsampled `scale` (2..4) times under the guidance of a
+        G-buffer of the larger frame (include/gpuart_upscale.h), (scale*th, scale*tw, 4) float32, row 0 at the bottom; params as
+        Upscaler.run. None for a scale out of range, an interleaved tile, parameters out of range and wherever the matching read fails
+        or gives None (the message is on stderr)."""
+        _, _, tw, th = self.tile
+        s = int(scale)
+        out = np.empty((th * max(s, 1), tw * max(s, 1), 4), np.float32)
+        p = upscale_params(params)
+        src = DISPLAY_SOURCES[source] if isinstance(source, str) else int(source)
+        if not self.L.gpuart_renderer_read_upscaled(self.h, _p(out), C.c_int(src), C.c_uint32(s & 0xffffffff), C.c_float(lum_floor),
+                                                    C.byref(p) if p is not None else None):
+            return None
+        return out
+
+    def read_upscaled_display(self, source="denoised", scale=2, params=None, lum_floor=CONVERGE_DEFAULT_FLOOR, upscale=None):
+        """Renderer::ReadUpscaledDisplay: read_upscaled's plane encoded on the device as 8-bit RGBA through the renderer's display handle
+        (params as Display.run, upscale as Upscaler.run), (scale*th, scale*tw, 4) uint8. None where read_upscaled gives None."""
+        _, _, tw, th = self.tile
+        s = int(scale)
+        out = np.empty((th * max(s, 1), tw * max(s, 1), 4), np.uint8)
+        p = display_params(params)
+        u = upscale_params(upscale)
+        src = DISPLAY_SOURCES[source] if isinstance(source, str) else int(source)
+        if not self.L.gpuart_renderer_read_upscaled_display(self.h, _p(out), C.c_int(src), C.c_uint32(s & 0xffffffff),
+                                                            C.byref(p) if p is not None else None, C.c_float(lum_floor),
+                                                            C.byref(u) if u is not None else None):
+            return None
+        return out
+
     def finish(self): return bool(self.L.gpuart_renderer_finish(self.h))
 
     def trace_rays(self, rays, occlusion=False, user_sphere=True, want_prims=False):
@@ -1937,6 +2001,53 @@ class Denoiser(_Filter):
         through gpuart_denoise_run (torch's current stream is synchronised first, the handle before returning) and the result is `out`
         or a new tensor; NumPy arrays run through gpuart_denoise_run_host and the result is `out` or a new array."""
         return self._run(denoise_params(params), rgba, hits, prims, us_flags, out)
+
+
+class UpscaleError(RuntimeError):
+    """A gpuart_upscale_* call returned an error; `code` is the library's (GPUART_HIP_ERR_*)."""
+    code = None
+
+
+class Upscaler(_ImageHandle):
+    """A gpuart_upscale handle on one device."""
+    NAME, Error = "upscale", UpscaleError
+
+    def run(self, scale, filtered, hits, prims, hi_hits, hi_prims, us_flags=0, params=None, out=None):
+        """Upsamples the filtered frame (h, w, 4) float32 `scale` times guided by its G-buffer (hits, prims: Backend.gbuffer) and the
+        larger frame's (hi_hits, hi_prims: Backend.gbuffer_scaled) -> (scale*h, scale*w, 4) float32; us_flags and params as
+        Denoiser.run (an UpscaleParams). torch tensors on this handle's device run in place through gpuart_upscale_run (torch's current
+        stream is synchronised first, the handle before returning); NumPy arrays run through gpuart_upscale_run_host. The result is
+        `out` or a new tensor or array."""
+        p = upscale_params(params)
+        s = int(scale)
+        k = max(s, 1)
+        if type(filtered).__module__.startswith("torch"):
+            import torch
+            dev, filtered, hits, prims, _, h, w = _gbuffer_args(self.device, filtered, hits, prims, None)
+            if hi_hits.dtype != torch.float32 or hi_hits.numel() != k * k * h * w * 8 or not hi_hits.is_contiguous() or hi_hits.device != dev:
+                raise ValueError("hi_hits must be a contiguous (scale*h, scale*w, 8) float32 tensor on %s" % dev)
+            if hi_prims.dtype != torch.int32 or hi_prims.numel() != k * k * h * w or not hi_prims.is_contiguous() or hi_prims.device != dev:
+                raise ValueError("hi_prims must be a contiguous (scale*h, scale*w) int32 tensor on %s" % dev)
+            res = out if out is not None else torch.empty((k * h, k * w, 4), dtype=torch.float32, device=dev)
+            if res.dtype != torch.float32 or tuple(res.shape) != (k * h, k * w, 4) or not res.is_contiguous() or res.device != dev:
+                raise ValueError("out must be a contiguous (scale*h, scale*w, 4) float32 tensor on %s" % dev)
+            ptr, fn = _dp, "run"
+            torch.cuda.current_stream(dev).synchronize()
+        else:
+            _, filtered, hits, prims, _, h, w = _gbuffer_args(self.device, filtered, hits, prims, None)
+            hi_hits = np.ascontiguousarray(hi_hits)
+            hi_prims = np.ascontiguousarray(hi_prims, np.int32)
+            if hi_hits.nbytes != k * k * h * w * 32 or hi_prims.size != k * k * h * w:
+                raise ValueError("hi_hits must hold scale*h * scale*w 32-byte records and hi_prims as many ordinals")
+            res = out if out is not None else np.empty((k * h, k * w, 4), np.float32)
+            if res.dtype != np.float32 or res.shape != (k * h, k * w, 4) or not res.flags.c_contiguous:
+                raise ValueError("out must be a contiguous (scale*h, scale*w, 4) float32 array")
+            ptr, fn = _p, "run_host"
+        self._chk(self._fn(fn)(self.h, C.c_uint32(s & 0xffffffff), ptr(filtered), ptr(hits), ptr(prims), C.c_uint32(w), C.c_uint32(h),
+                               ptr(hi_hits), ptr(hi_prims), C.c_uint32(us_flags), C.byref(p) if p is not None else None, ptr(res)))
+        if fn == "run":
+            self.finish()
+        return res
 
 
 class RefineError(RuntimeError):

@@ -109,6 +109,8 @@ struct gpuart_hip_ctx {
     uint32_t *d_cursor = nullptr;  ///< pixel cursor of k_direct_persistent
     uint32_t *d_query_cursor = nullptr;  ///< chunk cursor of k_ray_query (primary stream, like d_spill)
     uint2 *d_tile_xy = nullptr;    ///< gpuart_hip_gbuffer: the frame pixel of every tile pixel, in local order (freed by realloc_tile, built on use)
+    uint2 *d_scaled_xy = nullptr;  ///< gpuart_hip_gbuffer_scaled: the same table of the tile scaled by scaled_xy_scale (freed by realloc_tile, built on use)
+    uint32_t scaled_xy_scale = 0;
     uint4 *d_spill = nullptr;      ///< [spill_levels][grid_lanes] traversal-stack overflow for kernels on the primary stream
     // Birth order of the paths of a run (Frame::tile_order, k_tile_order): the tile's 8x8 blocks, most expensive first. The first run
     // after the tile was (re)allocated — and the first after every change of camera or scene — counts the shaded segments per block
@@ -316,6 +318,7 @@ int realloc_tile(gpuart_hip_ctx *c) {
     if (c->d_block_paths) { (void)hipFree(c->d_block_paths); c->d_block_paths = nullptr; }
     c->have_list = false; c->active_n = 0; c->have_counts = false; c->uniform_paths = 0;
     if (c->d_tile_xy) { (void)hipFree(c->d_tile_xy); c->d_tile_xy = nullptr; }
+    if (c->d_scaled_xy) { (void)hipFree(c->d_scaled_xy); c->d_scaled_xy = nullptr; c->scaled_xy_scale = 0; }
     if (c->d_direct) { (void)hipFree(c->d_direct); c->d_direct = nullptr; }
     if (c->d_accum) { (void)hipFree(c->d_accum); c->d_accum = nullptr; }
     c->plan.tile_pixels = (size_t)c->frame.tw * c->frame.th;
@@ -401,9 +404,11 @@ int ensure_spill(gpuart_hip_ctx *c) {
     return 0;
 }
 
-void update_uv(gpuart_hip_ctx *c) {
-    float w = (float)c->frame.W, h = (float)c->frame.H;
-    float *k = c->frame.uv_coef;
+/// The UV plane equations of a frame of f.W x f.H pixels: the one statement of them, for the context's frame at a resize and for the
+/// scaled frame of gpuart_hip_gbuffer_scaled.
+void update_uv(Frame &f) {
+    float w = (float)f.W, h = (float)f.H;
+    float *k = f.uv_coef;
     plane_coef(w, 0, 0, 0, w, h, 1, 0, 1, k + 0);  // A.u (V1,V0,V2)
     plane_coef(w, 0, 0, 0, w, h, 0, 0, 1, k + 3);  // A.v
     plane_coef(w, h, 0, 0, 0, h, 1, 0, 0, k + 6);  // B.u (V2,V0,V3)
@@ -624,7 +629,7 @@ int gpuart_hip_destroy(gpuart_hip_ctx *c) {
     const bool comm_stuck = bounded_ns::stuck().load();
     if (c->comm && !comm_stuck) (void)comm_drop(c);
     void *ptrs[] = {c->d_recs, c->d_prims, c->d_spill, c->d_direct, c->d_accum, c->d_counters, c->d_scratch, c->d_cursor,
-                    c->d_query_cursor, c->d_tile_order[0], c->d_tile_order[1], c->d_tile_cost, c->d_tile_xy, c->d_active, c->d_block_paths,
+                    c->d_query_cursor, c->d_tile_order[0], c->d_tile_order[1], c->d_tile_cost, c->d_tile_xy, c->d_scaled_xy, c->d_active, c->d_block_paths,
                     c->d_prim_boxes, c->d_spare_recs, c->d_spare_prims, c->d_spare_boxes};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     void *comm_ptrs[] = {c->d_send, c->d_stage, c->d_hello};
@@ -643,7 +648,7 @@ int gpuart_hip_resize(gpuart_hip_ctx *c, uint32_t width, uint32_t height) {
     c->frame.W = width; c->frame.H = height;
     c->frame.x0 = 0; c->frame.y0 = 0; c->frame.tw = width; c->frame.th = height;
     c->frame.band_rows = height; c->frame.band_stride = height;
-    update_uv(c);
+    update_uv(c->frame);
     return realloc_tile(c);
 }
 
@@ -1441,7 +1446,8 @@ static RayQuery make_query(size_t n, uint32_t flags, const float us[4]) {
 /// One k_ray_query launch on the primary stream. Its scratch — the chunk cursor and the traversal-stack spill d_spill — belongs to the
 /// primary stream, which nothing on the pass lanes' streams uses: a query may run beside pipeline runs in flight. Collected passes are
 /// not flushed (a query neither observes nor changes what they render), and neither the work counters nor the render timings see it.
-static int launch_ray_query(gpuart_hip_ctx *c, const RayQuery &q, int source) {
+/// `frame`: the frame an RQ_PIXELS query's pixels belong to (gpuart_hip_gbuffer_scaled's); NULL: the context's.
+static int launch_ray_query(gpuart_hip_ctx *c, const RayQuery &q, int source, const Frame *frame = nullptr) {
     if (!c->d_query_cursor) HIP_TRY(hipMalloc(&c->d_query_cursor, GD_QUERY_WORDS * sizeof(uint32_t)));
     HIP_TRY(hipMemsetAsync(c->d_query_cursor, 0, sizeof(uint32_t), c->stream));
     // chunks as the direct-lighting frame takes them; a small batch gets the waves it can fill
@@ -1450,7 +1456,7 @@ static int launch_ray_query(gpuart_hip_ctx *c, const RayQuery &q, int source) {
     const Scene sc = scene_of(c);
     auto query = [&](auto T, auto S) {
         GD_LEDGER(c, k_ray_query<T(), S()>);
-        k_ray_query<T(), S()><<<grid, BLOCK, 0, c->stream>>>(sc, c->frame, q, c->d_spill, c->d_query_cursor, tune);
+        k_ray_query<T(), S()><<<grid, BLOCK, 0, c->stream>>>(sc, frame ? *frame : c->frame, q, c->d_spill, c->d_query_cursor, tune);
     };
     if (int r = with_types(kernel_choice(c, KC_QUERY), LeafTypes(), "k_ray_query", [&](auto T) {
             if (source == RQ_PIXELS) query(T, std::integral_constant<int, RQ_PIXELS>());
@@ -1548,6 +1554,53 @@ int gpuart_hip_gbuffer(gpuart_hip_ctx *c, const float us[4], gpuart_ray_hit *hit
     q.hits = (float4 *)hits;
     q.prims = prims;
     return launch_ray_query(c, q, RQ_PIXELS);
+}
+
+int gpuart_hip_gbuffer_scaled(gpuart_hip_ctx *c, uint32_t scale, const float us[4], gpuart_ray_hit *hits, int32_t *prims) {
+    if (!c) return fail(GPUART_HIP_ERR_ARG, "ctx == NULL");
+    if (scale < 2 || scale > 4) return fail(GPUART_HIP_ERR_ARG, "gbuffer_scaled: scale = " + std::to_string(scale) + " is not in 2..4");
+    if (!c->have_scene) return fail(GPUART_HIP_ERR_ARG, "gbuffer_scaled: no scene uploaded");
+    if (!c->frame.W) return fail(GPUART_HIP_ERR_ARG, "gbuffer_scaled: no frame size set");
+    if (!c->have_camera) return fail(GPUART_HIP_ERR_ARG, "gbuffer_scaled: no camera set");
+    if (!hits || !prims) return fail(GPUART_HIP_ERR_ARG, "gbuffer_scaled: hits or prims is NULL");
+    if ((uintptr_t)hits % 16 || (uintptr_t)prims % 4)
+        return fail(GPUART_HIP_ERR_ARG, "gbuffer_scaled: misaligned pointer (hits needs 16 bytes, prims 4)");
+    const Frame &lo = c->frame;
+    if (lo.th > lo.band_rows && lo.band_stride != lo.band_rows)
+        return fail(GPUART_HIP_ERR_ARG, "gbuffer_scaled: the share is interleaved (its scaled tile would be no rectangle)");
+    if ((uint64_t)lo.W * scale > 65536 || (uint64_t)lo.H * scale > 65536)
+        return fail(GPUART_HIP_ERR_ARG, "gbuffer_scaled: a side of the scaled frame exceeds 65536");
+    const uint64_t n = (uint64_t)c->plan.tile_pixels * scale * scale;
+    if (n > GPUART_HIP_MAX_RAYS) return fail(GPUART_HIP_ERR_ARG, "gbuffer_scaled: the scaled tile exceeds GPUART_HIP_MAX_RAYS pixels");
+    if (n == 0) return 0;  // an empty share
+    HIP_TRY(hipSetDevice(c->device));
+    // the frame the context would have after a resize to scale*W x scale*H and a tile of (scale*x0, scale*y0, scale*tw, scale*th): a copy,
+    // the context's own stays as it is
+    Frame f = lo;
+    f.W = lo.W * scale; f.H = lo.H * scale;
+    f.x0 = lo.x0 * scale; f.y0 = lo.y0 * scale; f.tw = lo.tw * scale; f.th = lo.th * scale;
+    f.band_rows = f.band_stride = f.th;
+    f.tile_order = nullptr; f.tile_cost = nullptr;
+    update_uv(f);
+    if (!c->d_scaled_xy || c->scaled_xy_scale != scale) {  // the table of the scaled tile's frame pixels, once per tile and scale
+        if (c->d_scaled_xy) {
+            HIP_TRY(hipStreamSynchronize(c->stream));  // (an earlier query may still read it)
+            (void)hipFree(c->d_scaled_xy);
+            c->d_scaled_xy = nullptr; c->scaled_xy_scale = 0;
+        }
+        std::vector<uint2> xy((size_t)n);
+        for (uint32_t ly = 0; ly < f.th; ly++)
+            for (uint32_t lx = 0; lx < f.tw; lx++) xy[(size_t)ly * f.tw + lx] = make_uint2(f.x0 + lx, f.y0 + ly);
+        HIP_TRY(hipMalloc(&c->d_scaled_xy, (size_t)n * sizeof(uint2)));
+        HIP_TRY(hipMemcpyAsync(c->d_scaled_xy, xy.data(), (size_t)n * sizeof(uint2), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));  // (xy is freed on return)
+        c->scaled_xy_scale = scale;
+    }
+    RayQuery q = make_query((size_t)n, 0, us);
+    q.xy = c->d_scaled_xy;
+    q.hits = (float4 *)hits;
+    q.prims = prims;
+    return launch_ray_query(c, q, RQ_PIXELS, &f);
 }
 
 int gpuart_hip_trace_subpixel(gpuart_hip_ctx *c, const uint32_t *pixels, size_t n, const float *uv, uint32_t n_sub, float pixelSize,

@@ -432,6 +432,13 @@ int gpuart_renderer_read_refined(gpuart_renderer *r, float *rgba, float lumFloor
 int gpuart_renderer_read_display(gpuart_renderer *r, uint8_t *rgba8, int source, const gpuart_display_params *dp, float lumFloor) {
     return r->impl.ReadDisplay(rgba8, (gpuart_display_source)source, dp, lumFloor) ? 1 : 0;
 }
+int gpuart_renderer_read_upscaled(gpuart_renderer *r, float *rgba, int source, uint32_t scale, float lumFloor, const gpuart_upscale_params *p) {
+    return r->impl.ReadUpscaled(rgba, (gpuart_display_source)source, scale, lumFloor, p) ? 1 : 0;
+}
+int gpuart_renderer_read_upscaled_display(gpuart_renderer *r, uint8_t *rgba8, int source, uint32_t scale, const gpuart_display_params *dp,
+                                          float lumFloor, const gpuart_upscale_params *p) {
+    return r->impl.ReadUpscaledDisplay(rgba8, (gpuart_display_source)source, scale, dp, lumFloor, p) ? 1 : 0;
+}
 int gpuart_renderer_set_history_variance(gpuart_renderer *r, int on, const gpuart_moments_params *p) {
     return r->impl.SetHistoryVariance(on != 0, p) ? 1 : 0;
 }

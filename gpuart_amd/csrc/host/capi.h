@@ -17,6 +17,7 @@
 #include "gpuart_moments.h"
 #include "gpuart_refine.h"
 #include "gpuart_temporal.h"
+#include "gpuart_upscale.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -164,6 +165,14 @@ int gpuart_renderer_read_refined(gpuart_renderer *r, float *rgba, float lumFloor
  * (include/gpuart_display.h), tile-sized, 4 bytes per pixel; dp = NULL: the defaults; lumFloor for the guided preview and the refined
  * frame. 1 on success; 0 wherever the Read* of that source gives 0, for parameters out of range, or on error. */
 int gpuart_renderer_read_display(gpuart_renderer *r, uint8_t *rgba8, int source, const gpuart_display_params *dp, float lumFloor);
+/* Renderer::ReadUpscaled: the frame `source` names (a gpuart_display_source) upsampled `scale` (2..4) times under the guidance of a
+ * G-buffer of the larger frame (include/gpuart_upscale.h): scale*w * scale*h * 4 floats for a tile of w x h, row 0 = bottom row; p = NULL:
+ * the defaults. 1 on success; 0 for scale out of range, an interleaved tile, parameters out of range, and wherever the source's read
+ * fails. */
+int gpuart_renderer_read_upscaled(gpuart_renderer *r, float *rgba, int source, uint32_t scale, float lumFloor, const gpuart_upscale_params *p);
+/* Renderer::ReadUpscaledDisplay: the same plane as 8-bit RGBA (include/gpuart_display.h), scale*w * scale*h * 4 bytes. */
+int gpuart_renderer_read_upscaled_display(gpuart_renderer *r, uint8_t *rgba8, int source, uint32_t scale, const gpuart_display_params *dp,
+                                          float lumFloor, const gpuart_upscale_params *p);
 /* Renderer::SetHistoryVariance: carry the luminance's moments through a second history (include/gpuart_moments.h); toggling drops the
  * temporal history. p = NULL: the defaults. 1 on success, 0 for parameters out of range. */
 int gpuart_renderer_set_history_variance(gpuart_renderer *r, int on, const gpuart_moments_params *p);

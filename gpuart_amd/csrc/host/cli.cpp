@@ -29,7 +29,7 @@ static void usage() {
                  "                  [--denoise] [--edge-resolve] [--firefly-clamp [--firefly-k K] [--firefly-rank R]]\n"
                  "                  [--until T [--until-share S] [--until-floor F] [--until-batch N] [--error-pfm out.pfm] [--refine]]\n"
                  "                  [--display out.ppm [--tonemap clamp|reinhard|aces] [--white W] [--exposure-ev E] [--auto-exposure] [--key K]\n"
-                 "                   [--srgb] [--dither]]\n"
+                 "                   [--srgb] [--dither] [--upscale S]]\n"
                  "  --until T: render until the relative standard error of every pixel's luminance is at most T (Renderer::RenderUntil; path\n"
                  "             tracing on one GPU), --spp being the cap; --until-share S: the share of pixels that may stay above T (default 0);\n"
                  "             --until-floor F: luminance below which the error is taken relative to F (default 1/256, one step of the 8-bit\n"
@@ -47,6 +47,9 @@ static void usage() {
                  "             --tonemap: the curve (default clamp); --white W: reinhard's white point (default 4); --exposure-ev E: gain 2^E;\n"
                  "             --auto-exposure: adapt the gain to the frame's histogram, --key K: the luminance its log-average is brought to\n"
                  "             (default 0.18); --srgb: the sRGB transfer function (default linear); --dither: 8x8 ordered dither. One GPU only\n"
+                 "  --upscale S: with --display, write the frame S (2..4) times larger in each direction: the same source upsampled under the\n"
+                 "             guidance of a G-buffer of the larger frame (Renderer::ReadUpscaledDisplay, include/gpuart_upscale.h, its defaults).\n"
+                 "             One GPU only\n"
                  "  --denoise: write the denoised preview of the frame (Renderer::ReadDenoised; path tracing on one GPU)\n"
                  "  --edge-resolve: with --denoise or --refine, resolve geometric edges in the filtered frame from a sub-pixel G-buffer\n"
                  "             (Renderer::SetEdgeResolve, include/gpuart_edges.h, its defaults)\n"
@@ -84,6 +87,8 @@ int main(int argc, char **argv) {
     std::string samplesPfm;
     std::string display, tonemap = "clamp";
     bool displayOption = false;  // one of --display's own options was given
+    unsigned upscale = 0;        // --upscale S (0: not given)
+    bool haveUpscale = false;
     gpuart_display_params dp;
     gpuart_display_defaults(&dp);
     float tile[4] = {0, 0, 0, 0}, campos[3] = {0.1f, -3.05f, 1.0f}, sun[3] = {0, 0, 0}, us[7] = {-0.4f, 0, 0.2f, 0, 0, 0, 0};
@@ -135,6 +140,7 @@ int main(int argc, char **argv) {
         else if (a == "--key") { dp.key = strtof(need("--key"), nullptr); displayOption = true; }
         else if (a == "--srgb") { dp.transfer = GPUART_DISPLAY_SRGB; displayOption = true; }
         else if (a == "--dither") { dp.dither = 1; displayOption = true; }
+        else if (a == "--upscale") { upscale = (unsigned)atoi(need("--upscale")); haveUpscale = true; }
         else { usage(); return 2; }
     }
     if (W == 0 || H == 0 || (mode != "direct" && mode != "pt")) { usage(); return 2; }
@@ -186,6 +192,18 @@ int main(int argc, char **argv) {
     if ((haveUntil && mode != "pt") || (!haveUntil && !errorPfm.empty())) { usage(); return 2; }
     if (displayOption && display.empty()) {
         std::cerr << "gpuart_cli: --tonemap, --white, --exposure-ev, --auto-exposure, --key, --srgb and --dither shape --display's frame: give --display\n";
+        return 2;
+    }
+    if (haveUpscale && display.empty()) {
+        std::cerr << "gpuart_cli: --upscale enlarges --display's frame: give --display\n";
+        return 2;
+    }
+    if (haveUpscale && (upscale < GPUART_UPSCALE_MIN_SCALE || upscale > GPUART_UPSCALE_MAX_SCALE)) {
+        std::cerr << "gpuart_cli: --upscale takes 2, 3 or 4\n";
+        return 2;
+    }
+    if (haveUpscale && gpus > 1) {
+        std::cerr << "gpuart_cli: --upscale needs --gpus 1: a share's larger frame is no rectangle\n";
         return 2;
     }
     if (!display.empty() && gpus > 1) {
@@ -357,13 +375,14 @@ int main(int argc, char **argv) {
         const gpuart_display_source src = mode == "direct" ? GPUART_DISPLAY_DIRECT
                                           : refine && untilBatches >= 2 ? GPUART_DISPLAY_REFINED
                                           : denoise ? GPUART_DISPLAY_DENOISED : GPUART_DISPLAY_RADIANCE;
-        std::vector<uint8_t> img8((size_t)tw * th * 4);
-        if (!r.ReadDisplay(img8.data(), src, &dp, untilFloor)) return 1;
+        const unsigned k = haveUpscale ? upscale : 1u, dw = k * tw, dh = k * th;
+        std::vector<uint8_t> img8((size_t)dw * dh * 4);
+        if (!(haveUpscale ? r.ReadUpscaledDisplay(img8.data(), src, upscale, &dp, untilFloor) : r.ReadDisplay(img8.data(), src, &dp, untilFloor))) return 1;
         FILE *f = fopen(display.c_str(), "wb");
         if (!f) return 1;
-        fprintf(f, "P6\n%u %u\n255\n", tw, th);
-        for (unsigned y = th; y-- > 0;)
-            for (unsigned x = 0; x < tw; x++) fwrite(&img8[4 * ((size_t)y * tw + x)], 1, 3, f);
+        fprintf(f, "P6\n%u %u\n255\n", dw, dh);
+        for (unsigned y = dh; y-- > 0;)
+            for (unsigned x = 0; x < dw; x++) fwrite(&img8[4 * ((size_t)y * dw + x)], 1, 3, f);
         fclose(f);
         char buf[256];
         snprintf(buf, sizeof buf, ", \"display\": {\"tonemap\": \"%s\", \"transfer\": \"%s\", \"gain\": %.9g, \"auto_exposure\": %s, \"dither\": %s}",

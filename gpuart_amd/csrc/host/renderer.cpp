@@ -79,6 +79,9 @@ Renderer::Renderer(unsigned viewportWidth, unsigned viewportHeight, const Camera
 }
 
 Renderer::~Renderer() {
+    if (Upscaler) gpuart_upscale_destroy(Upscaler);
+    UpscaleWords.Release();
+    UpscaleMem.Release();
     if (Display) gpuart_display_destroy(Display);
     DisplayMem.Release();
     if (Refine) gpuart_refine_destroy(Refine);
@@ -302,6 +305,7 @@ const Lib<gpuart_adaptive> AD{gpuart_adaptive_create, gpuart_adaptive_finish, gp
 const Lib<gpuart_refine> RF{gpuart_refine_create, gpuart_refine_finish, gpuart_refine_last_error, "creating the variance-guided filter"};
 const Lib<gpuart_edges> ED{gpuart_edges_create, gpuart_edges_finish, gpuart_edges_last_error, "creating the edge resolve's handle"};
 const Lib<gpuart_despeckle> DS{gpuart_despeckle_create, gpuart_despeckle_finish, gpuart_despeckle_last_error, "creating the firefly clamp's handle"};
+const Lib<gpuart_upscale> UP{gpuart_upscale_create, gpuart_upscale_finish, gpuart_upscale_last_error, "creating the upscaler"};
 const Lib<gpuart_display> DP{gpuart_display_create, gpuart_display_finish, gpuart_display_last_error, "creating the display stage"};
 const Lib<gpuart_refit> RT{gpuart_refit_create, gpuart_refit_finish, gpuart_refit_last_error, "creating the refit handle"};
 const Lib<gpuart_build> BD{gpuart_build_create, gpuart_build_finish, gpuart_build_last_error, "creating the build handle"};
@@ -687,7 +691,7 @@ bool Renderer::ReadPlane(void *host, const void *plane, size_t bytesPerPixel, co
     return checkHip(hipMemcpy(host, plane, (size_t)Tile.w * Tile.h * bytesPerPixel, hipMemcpyDeviceToHost), what);
 }
 
-bool Renderer::StageView() {
+bool Renderer::EnsureGBuffer() {
     if (!checkHip(hipSetDevice(Device), "hipSetDevice")) return false;
     const size_t n = (size_t)Tile.w * Tile.h;
     if (n != DenoiseMem.count) GBufferValid = false;
@@ -696,11 +700,18 @@ bool Renderer::StageView() {
     const float us[4] = {UserSphere.pos.x, UserSphere.pos.y, UserSphere.pos.z, UserSphere.radius};
     if (!GBufferValid || memcmp(us, GBufferSphere, sizeof us) != 0) {
         GBufferValid = false;
-        EdgeListValid = false;  // (the edge list and the sub-pixel records are this G-buffer's)
+        EdgeListValid = false;  // (the edge list and the sub-pixel records are this G-buffer's,
+        UpscaleValid = false;   //  and so is the larger frame's G-buffer)
         if (!Check(gpuart_hip_gbuffer(Backend, us, b.hits, b.prims), "building the G-buffer")) return false;
         memcpy(GBufferSphere, us, sizeof us);
         GBufferValid = true;
     }
+    return true;
+}
+
+bool Renderer::StageView() {
+    if (!EnsureGBuffer()) return false;
+    const ViewBuffers b(DenoiseMem.mem, (size_t)Tile.w * Tile.h);
     if (!ExportNormalized(b.radiance)) return false;
     if (!FireflyOn) return true;
     // in place: every filtered read and every commit takes the clamped frame; the accumulator stays what it is
@@ -1177,6 +1188,78 @@ bool Renderer::ReadDisplay(uint8_t *rgba8, gpuart_display_source source, const g
     if (!StageSource(source, lumFloor, nullptr, nullptr, nullptr, (float *)DisplayMem.mem, plane)) return false;
     return Run(gpuart_display_run(Display, plane, words, Tile.w, Tile.h, Tile.x, Tile.y, dp), Display, DP, "encoding the frame") &&
            ReadPlane(rgba8, words, 4, "reading the 8-bit frame");
+}
+
+// ---- the upscaler (include/gpuart_upscale.h) --------------------------------------------------------------------------------
+bool Renderer::StageUpscaled(gpuart_display_source source, uint32_t scale, float lumFloor, const gpuart_upscale_params *p, const float *&plane,
+                             size_t &n) {
+    if (!IsOK) return false;
+    // the refusals first: nothing has changed when one of them returns
+    if (scale < GPUART_UPSCALE_MIN_SCALE || scale > GPUART_UPSCALE_MAX_SCALE) {
+        std::cerr << "Renderer: ReadUpscaled: scale " << scale << " is not in 2..4." << std::endl;
+        return false;
+    }
+    if (p && (!(p->normal_min >= -1) || !(p->normal_min <= 1) || !finite(p->plane_tol) || !(p->plane_tol >= 0))) {
+        std::cerr << "Renderer: upscaler parameters out of range." << std::endl;
+        return false;
+    }
+    if (source < GPUART_DISPLAY_RADIANCE || source > GPUART_DISPLAY_REFINED) {
+        std::cerr << "Renderer: ReadUpscaled: no such source " << (int)source << std::endl;
+        return false;
+    }
+    gpuart_tile_geom g;
+    if (!Check(gpuart_hip_get_share(Backend, &g), "reading the tile")) return false;
+    if (g.th > g.band_rows && g.band_stride != g.band_rows) {
+        std::cerr << "Renderer: ReadUpscaled: the tile is interleaved with other renderers' (a share of several GPUs); its larger frame would "
+                     "be no rectangle." << std::endl;
+        return false;
+    }
+    if (!checkHip(hipSetDevice(Device), "hipSetDevice") || !Ensure(Upscaler, UP)) return false;
+    const size_t lo = (size_t)Tile.w * Tile.h;
+    n = lo * scale * scale;
+    // the low plane, with edge resolve skipped for this call: the switch and its cache stay what they are
+    if (!DisplayMem.Fit(lo, 16 + 4, "allocating the display stage's buffers")) return false;
+    const bool edgeOn = EdgeOn;
+    EdgeOn = false;
+    const float *low;
+    const bool staged = StageSource(source, lumFloor, nullptr, nullptr, nullptr, (float *)DisplayMem.mem, low);
+    EdgeOn = edgeOn;
+    if (!staged || !EnsureGBuffer()) return false;  // (RADIANCE and DIRECT stage no view)
+    // the larger frame's G-buffer, of the view whose G-buffer is cached
+    if (n != UpscaleMem.count || scale != UpscaleScale) UpscaleValid = false;
+    if (!UpscaleMem.Fit(n, 32 + 16 + 4, "allocating the upscaler's buffers")) return false;
+    gpuart_ray_hit *hiHits = (gpuart_ray_hit *)UpscaleMem.mem;
+    float *out = (float *)((char *)UpscaleMem.mem + n * 32);
+    int32_t *hiPrims = (int32_t *)((char *)UpscaleMem.mem + n * 48);
+    if (!UpscaleValid) {
+        if (!Check(gpuart_hip_gbuffer_scaled(Backend, scale, GBufferSphere, hiHits, hiPrims), "building the larger frame's G-buffer") ||
+            !Check(gpuart_hip_finish(Backend), "waiting for the device"))
+            return false;
+        UpscaleScale = scale;
+        UpscaleValid = true;
+    }
+    const ViewBuffers b(DenoiseMem.mem, lo);
+    plane = out;
+    return Run(gpuart_upscale_run(Upscaler, scale, low, b.hits, b.prims, Tile.w, Tile.h, hiHits, hiPrims, UserSphere.flags, p, out), Upscaler, UP,
+               "upsampling the frame");
+}
+
+bool Renderer::ReadUpscaled(float *rgba, gpuart_display_source source, uint32_t scale, float lumFloor, const gpuart_upscale_params *p) {
+    const float *plane;
+    size_t n;
+    return rgba && StageUpscaled(source, scale, lumFloor, p, plane, n) &&
+           checkHip(hipMemcpy(rgba, plane, n * 16, hipMemcpyDeviceToHost), "reading the upsampled frame");
+}
+
+bool Renderer::ReadUpscaledDisplay(uint8_t *rgba8, gpuart_display_source source, uint32_t scale, const gpuart_display_params *dp, float lumFloor,
+                                   const gpuart_upscale_params *p) {
+    const float *plane;
+    size_t n;
+    if (!rgba8 || !IsOK || !checkHip(hipSetDevice(Device), "hipSetDevice") || !Ensure(Display, DP)) return false;
+    if (!StageUpscaled(source, scale, lumFloor, p, plane, n) || !UpscaleWords.Fit(n, 4, "allocating the 8-bit frame")) return false;
+    return Run(gpuart_display_run(Display, plane, (uint8_t *)UpscaleWords.mem, scale * Tile.w, scale * Tile.h, scale * Tile.x, scale * Tile.y, dp), Display,
+               DP, "encoding the frame") &&
+           checkHip(hipMemcpy(rgba8, UpscaleWords.mem, n * 4, hipMemcpyDeviceToHost), "reading the 8-bit frame");
 }
 
 // ---- checkpoint / resume ---------------------------------------------------------------------------------------------

@@ -35,6 +35,7 @@
 #include "gpuart_refine.h"
 #include "gpuart_refit.h"
 #include "gpuart_temporal.h"
+#include "gpuart_upscale.h"
 #include "math_types.h"
 
 /// The luminance floor of the error estimates where none is given: one step of an 8-bit output (gpuart_cli --until-floor,
@@ -241,6 +242,24 @@ public:
     /// histories and the cached G-buffer are what they are without the call. Synchronises.
     bool ReadDisplay(uint8_t *rgba8, gpuart_display_source source, const gpuart_display_params *dp = nullptr,
                      float lumFloor = GPUART_CONVERGE_DEFAULT_FLOOR);
+    /// One of the frames above `scale` (2..4) times larger in each direction, upsampled under the guidance of a G-buffer of the larger
+    /// frame (include/gpuart_upscale.h): scale*Tile.w x scale*Tile.h RGBA32F, row 0 = bottom row, the tile (scale*x0, scale*y0) of a
+    /// frame of scale times the viewport. It runs the device sequence of the Read* that `source` names (any source of ReadDisplay; the
+    /// filters with their default parameters, lumFloor where they take one) with edge resolve skipped for this call even while
+    /// SetEdgeResolve is on — the upscaler places every output pixel on its own surface, which is what edge resolve approximates by
+    /// averaging; the switch, its cache and every other read are untouched —, ensures the view's G-buffer also for RADIANCE and DIRECT,
+    /// takes the larger frame's G-buffer from gpuart_hip_gbuffer_scaled into a buffer of its own (cached like the view's G-buffer: made
+    /// again after a new camera, user sphere, tile or scene, and when `scale` changes; 52 bytes per output pixel with the plane) and
+    /// runs gpuart_upscale_run (p = nullptr: the defaults). False, with a message and nothing changed, for scale outside 2..4, for an
+    /// interleaved tile or a share of several GPUs, for parameters out of range, and wherever the Read* of `source` is false. It never
+    /// commits a history; the accumulator, the passes that follow, the counters, the estimates, the histories and the cached G-buffer
+    /// are what they are without the call, and while it is unused nothing launches that did not launch before. Synchronises.
+    bool ReadUpscaled(float *rgba, gpuart_display_source source, uint32_t scale, float lumFloor = GPUART_CONVERGE_DEFAULT_FLOOR,
+                      const gpuart_upscale_params *p = nullptr);
+    /// The same plane as 8-bit RGBA through the Renderer's one display handle, at the scaled size and the scaled tile origin:
+    /// scale*Tile.w * scale*Tile.h * 4 bytes leave the device. Its exposure state adapts as ReadDisplay's does.
+    bool ReadUpscaledDisplay(uint8_t *rgba8, gpuart_display_source source, uint32_t scale, const gpuart_display_params *dp = nullptr,
+                             float lumFloor = GPUART_CONVERGE_DEFAULT_FLOOR, const gpuart_upscale_params *p = nullptr);
     /// Adaptive sampling (include/gpuart_adaptive.h, gpuart_hip_set_active_blocks): RenderUntil's loop with the estimate kept per 8x8
     /// block of the tile. It continues the current accumulation in batches of at least batchPaths paths per pixel towards the cap of
     /// RestartPathTracing / ExtendPathTracing; after every batch the raw accumulator and the blocks' path counts go to the estimator,
@@ -364,6 +383,11 @@ private:
     PixelBuffer ErrorMem;                 ///< the error map of ReadErrorMap and ReadRefined, 4 B per tile pixel
     gpuart_display *Display = nullptr;    ///< made by the first ReadDisplay
     PixelBuffer DisplayMem;               ///< ReadDisplay's: the plane of RADIANCE and DIRECT (16 B) and the 8-bit frame (4 B) per tile pixel
+    gpuart_upscale *Upscaler = nullptr;   ///< made by the first ReadUpscaled
+    PixelBuffer UpscaleMem;               ///< per output pixel the larger frame's record (32 B), the upsampled plane (16) and the ordinal (4)
+    PixelBuffer UpscaleWords;             ///< ReadUpscaledDisplay's 8-bit frame, 4 B per output pixel
+    bool UpscaleValid = false;            ///< UpscaleMem holds the larger frame's G-buffer of the cached G-buffer's view for UpscaleScale
+    uint32_t UpscaleScale = 0;
     ScreenBasis CurrentBasis;             ///< what SetCamera gave the back end
     double LastSetPrimitivesMs[4] = {0, 0, 0, 0};
     gpuart_hip_ctx *Backend = nullptr;
@@ -408,6 +432,10 @@ private:
     void ResetPathTracing();
     /// The device buffers of ReadDenoised / ReadPreview / a commit, the G-buffer of the current view (cached) and the normalised accumulator.
     bool StageView();
+    /// StageView's first half: DenoiseMem for the tile and in it the G-buffer of the current view and user sphere, made where it is stale.
+    bool EnsureGBuffer();
+    /// The device half of ReadUpscaled and ReadUpscaledDisplay: the upsampled plane in UpscaleMem, complete, `n` its pixels.
+    bool StageUpscaled(gpuart_display_source source, uint32_t scale, float lumFloor, const gpuart_upscale_params *p, const float *&plane, size_t &n);
     bool MakeTemporalView(gpuart_temporal_view &v) const;
     void CommitTemporalView();
     /// Temporal, TemporalMoments, Moments and MomentsMem for the tile, made where missing.

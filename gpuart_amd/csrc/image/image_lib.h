@@ -1,5 +1,5 @@
-// image_lib.h — the scaffold of the ten image libraries (denoise/denoise.hip, temporal/temporal.hip, converge/converge.hip, refine/refine.hip,
-// adaptive/adaptive.hip, moments/moments.hip, display/display.hip, antilag/antilag.hip, edges/edges.hip, despeckle/despeckle.hip), private
+// image_lib.h — the scaffold of the eleven image libraries (denoise/denoise.hip, temporal/temporal.hip, converge/converge.hip, refine/refine.hip,
+// adaptive/adaptive.hip, moments/moments.hip, display/display.hip, antilag/antilag.hip, edges/edges.hip, despeckle/despeckle.hip, upscale/upscale.hip), private
 // to them: the last-error string, the handle's device and stream with the shared parts of create / destroy / finish, the grow-only device
 // buffer, the handle, size and overlap checks, the caller's parameters or the defaults, the 64 x 4 row block, the staging of a G-buffer
 // for the _host entry points, and the two device functions more than one library states: the luminance and "what is a surface pixel".

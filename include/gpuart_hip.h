@@ -375,6 +375,18 @@ int gpuart_hip_pick(gpuart_hip_ctx *ctx, const uint32_t *xy, size_t n, const flo
  * change. An empty share writes nothing. GPUART_HIP_ERR_ARG without a scene, a frame size or a camera, and for a NULL or misaligned
  * pointer. include/gpuart_denoise.h filters a frame with it. */
 int gpuart_hip_gbuffer(gpuart_hip_ctx *ctx, const float userSphere[4], gpuart_ray_hit *hits, int32_t *prims);
+/* A G-buffer above the pixel grid (include/gpuart_upscale.h upsamples a filtered frame with it): the G-buffer the context would give at
+ * the same camera and user sphere if its frame were scale*W x scale*H and its tile (scale*x0, scale*y0, scale*tw, scale*th), bit for bit
+ * what gpuart_hip_gbuffer returns on a context resized and tiled that way. Record ly * (scale*tw) + lx is pixel (lx, ly) of the scaled
+ * tile, row 0 at the bottom. The camera rays are those of the scaled frame (its own UV plane equations, computed where a resize
+ * computes them), walked by the query kernel gpuart_hip_gbuffer launches. Device memory, asynchronous on the context's stream: hits
+ * (scale^2 * tw*th records) 16-byte aligned, prims (as many ordinals) 4-byte aligned. The context's frame, tile, accumulators, collected
+ * passes, counters and timings do not change; the context keeps the table of the scaled tile's pixels (8 bytes per scaled pixel) until
+ * the tile or the scale changes. An empty share writes nothing. GPUART_HIP_ERR_ARG, with nothing written, for scale outside 2..4, without
+ * a scene, a frame size or a camera, for a NULL or misaligned pointer, for an interleaved share (more than one band and band_stride !=
+ * band_rows: its scaled tile would be no rectangle), for a scaled tile above GPUART_HIP_MAX_RAYS pixels or a scaled frame side above
+ * 65536. */
+int gpuart_hip_gbuffer_scaled(gpuart_hip_ctx *ctx, uint32_t scale, const float userSphere[4], gpuart_ray_hit *hits, int32_t *prims);
 /* Sub-pixel camera rays of listed tile pixels: a G-buffer below the pixel grid (include/gpuart_edges.h resolves geometric edges with
  * it). pixels: device memory, n local pixel indices ly * tw + lx in the order of gpuart_hip_gbuffer, in any order, repeats allowed. uv:
  * host memory, 2 * n_sub values in [0, 1). Ray (i, k) is the first segment gpuart_hip_pt_pass traces for pixel pixels[i] when its two
