@@ -87,6 +87,11 @@ TREE_MODES = {"morton": 0, "clustered": 1}  # Renderer::TreeMode
 BUILD_STEPS = ("keys", "sort", "permute", "hierarchy", "number", "emit", "levels")  # gpuart_build_step_ms
 RAY_HIT = np.dtype([("pos", np.float32), ("p", np.float32, 3), ("n", np.float32, 3), ("type", np.int32)])
 RAYS_OCCLUSION = 1  # GPUART_HIP_RAYS_OCCLUSION
+# gpuart_nearest_hit (include/gpuart_nearest.h): prim -1 none, -2 the user sphere; type -1 none
+NEAREST_HIT = np.dtype([("dist", np.float32), ("q", np.float32, 3), ("d2", np.float32), ("prim", np.int32), ("type", np.int32), ("zero", np.uint32)])
+NEAREST_CHUNK = 64  # GPUART_NEAREST_CHUNK
+NEAREST_RING = 8    # GPUART_NEAREST_RING
+NEAREST_MAX_DEPTH = 1024  # GPUART_NEAREST_MAX_DEPTH
 
 
 def _params(cls, defaults, noun, params):
@@ -294,6 +299,13 @@ def _rays_array(rays):
     return rays
 
 
+def _points_array(points):
+    points = np.ascontiguousarray(points, np.float32)
+    if points.ndim != 2 or points.shape[1] != 4:
+        raise ValueError("points must be (n, 4): p.xyz, r")
+    return points
+
+
 def _pixels_array(xy):
     xy = np.asarray(xy)
     if xy.ndim != 2 or xy.shape[1] != 2:
@@ -422,6 +434,12 @@ def edit_lib():
     """libgpuart_edit.so (include/gpuart_edit.h), built by the image libraries' rule; raises NativeLibraryMissing if it has not been built
     (no fallback)."""
     return _image_lib("edit")
+
+
+def nearest_lib():
+    """libgpuart_nearest.so (include/gpuart_nearest.h), built by the image libraries' rule; raises NativeLibraryMissing if it has not been built
+    (no fallback)."""
+    return _image_lib("nearest")
 
 
 def display_lib():
@@ -847,7 +865,8 @@ class Backend:
             raise e
 
     def close(self):
-        for handle in (getattr(self, "_refit", None), getattr(self, "_build", None), getattr(self, "_ploc", None), getattr(self, "_edit", None)):
+        for handle in (getattr(self, "_refit", None), getattr(self, "_build", None), getattr(self, "_ploc", None), getattr(self, "_edit", None),
+                       getattr(self, "_nearest", None)):
             if handle is not None:
                 handle.close()
         if self.owned and self.ctx:
@@ -1316,6 +1335,51 @@ class Backend:
         self._chk(self.L.gpuart_hip_trace_rays_host(self.ctx, _p(rays), C.c_size_t(n), flags, us, _p(hits),
                                                     _p(prims) if prims is not None else None))
         return (hits, prims) if want_prims else hits
+
+    def _nearest_handle(self, scene):
+        """The context's gpuart_nearest, made at the first closest_points and bound to `scene` unless it is already (its generation: an
+        upload, a rebuild and an edit raise it, a refit in place keeps it and the nesting the binding checked)."""
+        if getattr(self, "_nearest", None) is None:
+            self._nearest = _NearestHandle(self.device)
+        h = self._nearest
+        if h.generation != scene.generation:
+            h.generation = None
+            h._chk(h.L.gpuart_nearest_bind(h, C.byref(scene)))
+            h.generation = scene.generation
+        return h
+
+    def closest_points(self, points, user_sphere=None, out=None):
+        """Per query (p.xyz, r) of points (n, 4) the nearest surface point among the scene's primitives within r, as
+        include/gpuart_nearest.h defines it; user_sphere = (x, y, z, R) takes part with ordinal -2, None = no user sphere.
+        A NumPy array runs through host memory (synchronous) and returns a NEAREST_HIT record array. A contiguous (n, 4) float32 tensor
+        on this context's device runs in place, without a copy: torch's current stream is synchronised before, the handle's stream
+        before returning; the result is an (n, 8) float32 tensor — dist, q.xyz, d2, prim, type, 0; columns 5 and 6 hold int32:
+        .view(torch.int32) — written into `out` if given. The scene's descriptor is fetched at every call, as Backend.refit does.
+        A scene the uploader classified irregular or disorderly, and an empty one, raise HipError (code -1) with nothing written."""
+        N = nearest_lib()
+        us = _user_sphere(user_sphere)
+        scene = self.scene_device()
+        h = self._nearest_handle(scene)
+        if type(points).__module__.startswith("torch"):
+            import torch
+            if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous() or points.device.type != "cuda":
+                raise ValueError("points must be a contiguous (n, 4) float32 tensor on the GPU")
+            index = points.device.index if points.device.index is not None else torch.cuda.current_device()
+            if index != self.device:
+                raise ValueError("points is on cuda:%d, this context on device %d: the kernel reads the tensor's memory in place" % (index, self.device))
+            n = points.shape[0]
+            hits = out if out is not None else torch.empty((n, 8), dtype=torch.float32, device=points.device)
+            if hits.dtype != torch.float32 or tuple(hits.shape) != (n, 8) or not hits.is_contiguous() or hits.device != points.device:
+                raise ValueError("out must be a contiguous (n, 8) float32 tensor on the points' device")
+            torch.cuda.current_stream(points.device).synchronize()
+            h._chk(N.gpuart_nearest_run(h, C.byref(scene), C.c_void_p(points.data_ptr() if n else None), C.c_size_t(n), us,
+                                        C.c_void_p(hits.data_ptr() if n else None)))
+            h.finish()
+            return hits
+        points = _points_array(points)
+        hits = np.zeros(points.shape[0], NEAREST_HIT)
+        h._chk(N.gpuart_nearest_run_host(h, C.byref(scene), _p(points), C.c_size_t(points.shape[0]), us, _p(hits)))
+        return hits
 
     def pick(self, xy, user_sphere=None, want_prims=False):
         """Closest hit of the camera rays of frame pixels xy (n, 2) = (x, y), row 0 = bottom, any pixel of the frame: a RAY_HIT record
@@ -1836,6 +1900,16 @@ class Renderer:
             raise HipError("pick failed: " + hip_lib().gpuart_hip_last_error().decode())
         return (hits, prims) if want_prims else hits
 
+    def closest_points(self, points, user_sphere=True):
+        """Renderer::ClosestPoints: points (n, 4) = p.xyz, r in host memory; user_sphere = include the renderer's current user sphere.
+        Returns a NEAREST_HIT record array; a hit's prim is the device ordinal (-2: the user sphere)."""
+        points = _points_array(points)
+        hits = np.zeros(points.shape[0], NEAREST_HIT)
+        if not self.L.gpuart_renderer_closest_points(self.h, _p(points), C.c_size_t(points.shape[0]), C.c_int(1 if user_sphere else 0), _p(hits)):
+            raise HipError("closest_points refused or failed: Renderer::ClosestPoints says why on stderr (an empty scene and a tree with irregular "
+                           "boxes are not queried)")
+        return hits
+
     def last_setprims_ms(self):
         """(whole call, BVH build, compilation, re-layout + upload) of the last set_primitives, ms, as the library timed them."""
         out = (C.c_double * 4)()
@@ -1927,6 +2001,12 @@ class _PlocHandle(_ImageHandle):
 class _EditHandle(_RefitHandle):
     """Backend.edit's gpuart_edit, made at the first edit; a refused edit's error carries `first_bad` as a refused refit's does."""
     NAME, Error = "edit", HipError
+
+
+class _NearestHandle(_ImageHandle):
+    """Backend.closest_points' gpuart_nearest, made at the first call; `generation`: that of the scene it is bound to."""
+    NAME, Error = "nearest", HipError
+    generation = None
 
 
 def _gbuffer_args(device, rgba, hits, prims, out):

@@ -375,6 +375,9 @@ int gpuart_renderer_pick(gpuart_renderer *r, const uint32_t *xy, size_t n, int w
     to_desc_index(r, prims, n);
     return 1;
 }
+int gpuart_renderer_closest_points(gpuart_renderer *r, const float *points, size_t n, int withUserSphere, gpuart_nearest_hit *hits) {
+    return r->impl.ClosestPoints(points, n, withUserSphere != 0, hits) ? 1 : 0;
+}
 int gpuart_renderer_set_camera(gpuart_renderer *r, const float pos[3], const float dir[3], const float up[3], float fovY,
                                float screenDist) {
     return r->impl.SetCamera(make_camera(pos, dir, up, fovY, screenDist)) ? 1 : 0;

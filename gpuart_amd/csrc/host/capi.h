@@ -14,6 +14,7 @@
 #include "gpuart_display.h"
 #include "gpuart_edges.h"
 #include "gpuart_hip.h"
+#include "gpuart_nearest.h"
 #include "gpuart_moments.h"
 #include "gpuart_refine.h"
 #include "gpuart_temporal.h"
@@ -216,6 +217,9 @@ int gpuart_renderer_load_checkpoint(gpuart_renderer *r, const char *path);
 int gpuart_renderer_trace_rays(gpuart_renderer *r, const float *rays, size_t n, int occlusion, int withUserSphere, gpuart_ray_hit *hits,
                                int32_t *prims);
 int gpuart_renderer_pick(gpuart_renderer *r, const uint32_t *xy, size_t n, int withUserSphere, gpuart_ray_hit *hits, int32_t *prims);
+/* Renderer::ClosestPoints (host memory, synchronous; 1 on success, 0 on refusal or error): points n x 4 floats {p.xyz, r}, hits n records
+ * of include/gpuart_nearest.h; a hit's prim is the device ordinal, the position in the renderer's sorted list (-2: the user sphere). */
+int gpuart_renderer_closest_points(gpuart_renderer *r, const float *points, size_t n, int withUserSphere, gpuart_nearest_hit *hits);
 gpuart_hip_ctx *gpuart_renderer_backend(gpuart_renderer *r);
 void gpuart_renderer_params(gpuart_renderer *r, gpuart_params *out);
 /* What the renderer's last SetPrimitives spent inside the library, ms: whole call, BVH build, compilation, re-layout + upload. */

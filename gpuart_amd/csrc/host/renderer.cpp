@@ -107,6 +107,7 @@ Renderer::~Renderer() {
     if (Builder) gpuart_build_destroy(Builder);
     if (Clusterer) gpuart_ploc_destroy(Clusterer);
     if (Editor) gpuart_edit_destroy(Editor);
+    if (Nearest) gpuart_nearest_destroy(Nearest);
     if (Backend) gpuart_hip_destroy(Backend);
 }
 
@@ -311,6 +312,7 @@ const Lib<gpuart_refit> RT{gpuart_refit_create, gpuart_refit_finish, gpuart_refi
 const Lib<gpuart_build> BD{gpuart_build_create, gpuart_build_finish, gpuart_build_last_error, "creating the build handle"};
 const Lib<gpuart_ploc> PL{gpuart_ploc_create, gpuart_ploc_finish, gpuart_ploc_last_error, "creating the clustered build's handle"};
 const Lib<gpuart_edit> ET{gpuart_edit_create, gpuart_edit_finish, gpuart_edit_last_error, "creating the edit handle"};
+const Lib<gpuart_nearest> NE{gpuart_nearest_create, gpuart_nearest_finish, gpuart_nearest_last_error, "creating the closest-point handle"};
 
 std::chrono::high_resolution_clock::time_point Now() { return std::chrono::high_resolution_clock::now(); }
 template <class T> double Ms(T from, T to) { return std::chrono::duration<double, std::milli>(to - from).count(); }
@@ -537,6 +539,27 @@ bool Renderer::Pick(const uint32_t *xy, size_t n, gpuart_ray_hit *hits, int32_t 
     if (!IsOK) return false;
     const float us[4] = {UserSphere.pos.x, UserSphere.pos.y, UserSphere.pos.z, UserSphere.radius};
     return Check(gpuart_hip_pick(Backend, xy, n, withUserSphere ? us : nullptr, hits, prims), "picking");
+}
+
+// ---- closest-point queries (include/gpuart_nearest.h) ---------------------------------------------
+// The descriptor is looked up at every call: its generation says whether the handle's binding (the nesting check of every record) still
+// holds — an upload, a rebuild and an edit raise it, a refit in place does not.
+bool Renderer::ClosestPoints(const float *points, size_t n, bool withUserSphere, gpuart_nearest_hit *hits) {
+    if (!IsOK || (n && (!points || !hits))) return false;
+    gpuart_hip_scene scene;
+    if (!Check(gpuart_hip_scene_device(Backend, &scene), "looking up the scene's device arrays")) return false;
+    if (scene.exact_boxes || !Tree.GetNumPrimitives()) {
+        std::cerr << "Renderer: ClosestPoints: an empty scene or a tree with irregular boxes (or boxes that do not bound their contents) is not queried." << std::endl;
+        return false;
+    }
+    if (!Ensure(Nearest, NE)) return false;
+    if (NearestGeneration != scene.generation) {
+        NearestGeneration = 0;
+        if (!Check(gpuart_nearest_bind(Nearest, &scene), "binding the closest-point handle", gpuart_nearest_last_error)) return false;
+        NearestGeneration = scene.generation;
+    }
+    const float us[4] = {UserSphere.pos.x, UserSphere.pos.y, UserSphere.pos.z, UserSphere.radius};
+    return Check(gpuart_nearest_run_host(Nearest, &scene, points, n, withUserSphere ? us : nullptr, hits), "querying closest points", gpuart_nearest_last_error);
 }
 
 // ---- lighting / user sphere ---------------------------------------------------------------------

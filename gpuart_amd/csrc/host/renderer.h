@@ -25,6 +25,7 @@
 #include "gpuart_build.h"
 #include "gpuart_ploc.h"
 #include "gpuart_edit.h"
+#include "gpuart_nearest.h"
 #include "gpuart_converge.h"
 #include "gpuart_denoise.h"
 #include "gpuart_despeckle.h"
@@ -322,6 +323,12 @@ public:
     /// Closest hit under frame pixels xy[2n] = (x, y), row 0 = bottom, any pixel of the viewport: the camera ray RenderDirectLighting
     /// traces for that pixel. Otherwise as TraceRays.
     bool Pick(const uint32_t *xy, size_t n, gpuart_ray_hit *hits, int32_t *prims, bool withUserSphere = true);
+    /// Closest-point queries (include/gpuart_nearest.h): `points` = n x 4 floats {p.xyz, r} in host memory; per query the nearest surface
+    /// point among the scene's primitives within r (and the current user sphere when `withUserSphere`, ordinal -2), its distance and the
+    /// primitive's index in the vector SetPrimitives left behind, as that header defines them. Synchronous; no image changes. The handle
+    /// is made by the first call and bound again after SetPrimitives, RebuildTree and EditPrimitives (a refit keeps the binding). False
+    /// on refusal — an empty scene, a tree with irregular boxes — or error (std::cerr says why).
+    bool ClosestPoints(const float *points, size_t n, bool withUserSphere, gpuart_nearest_hit *hits);
     unsigned GetTileWidth() const { return Tile.w; }
     unsigned GetTileHeight() const { return Tile.h; }
     const BoundingVolumesHierarchy &GetBVH() const { return Tree; }
@@ -396,6 +403,8 @@ private:
     gpuart_build *Builder = nullptr;      ///< made by the first RebuildTree or TreeCost
     gpuart_ploc *Clusterer = nullptr;     ///< made by the first RebuildTree(TREE_CLUSTERED)
     gpuart_edit *Editor = nullptr;        ///< made by the first EditPrimitives
+    gpuart_nearest *Nearest = nullptr;    ///< made by the first ClosestPoints
+    uint64_t NearestGeneration = 0;       ///< the generation Nearest is bound to (0: none)
     /// What BuildIntoSpare hands out beside the spare set's descriptor: new_to_old, the two ref words of each of the nRecs records (the
     /// clustered build's; the Morton order implies its own) and when the device run returned.
     struct BuiltTree {

@@ -1,0 +1,612 @@
+// nearest.hip — libgpuart_nearest.so (gfx950): closest-point queries over an uploaded scene's tree, as include/gpuart_nearest.h states
+// them. Built without flushing fp32 denormals and without contraction: the rule (csrc/hip/nearest_rule.h) is restated in NumPy float32
+// (tests/nearest_ref.py) and every answer is compared bit for bit. DESIGN.md "Closest points" describes the kernel. The library reads
+// the scene's arrays and writes none of them.
+//
+// Compile-time switches (tools/nearest_time.py builds the variants; the shipped library sets none):
+//   NEAREST_PLAIN   k_nearest as one thread per query with a grid stride and no refill: the A/B partner of the persistent-lane form
+//   NEAREST_COUNT   box steps and primitive tests counted per query and summed (gpuart_nearest_counts): a counting build, not a timed one
+//   NEAREST_REFILL  idle lanes of a wave at which it takes new queries (default 16)
+#include "../image/image_lib.h"
+#include "../tree/tree_lib.h"
+#include "../hip/nearest_rule.h"
+#include "gpuart_nearest.h"
+
+#ifndef NEAREST_REFILL
+#define NEAREST_REFILL 16
+#endif
+
+namespace {
+
+namespace nr = nearest_rule;
+using tree_rule::REF_TWO;
+using tree_rule::REF_TRIS;
+using tree_rule::REF_SMALL;
+
+const char LIB[] = "nearest";
+
+constexpr uint32_t BLOCK = 256;                      ///< four waves
+constexpr uint32_t WAVES = BLOCK / 64;
+constexpr uint32_t CHUNK = GPUART_NEAREST_CHUNK;     ///< queries a wave takes from the cursor at a time
+constexpr uint32_t RING = GPUART_NEAREST_RING;       ///< stack entries a lane keeps in LDS; older ones go to its global column
+constexpr uint32_t NONE = 0xffffffffu;               ///< no query
+constexpr size_t HOST_CHUNK = (size_t)1 << 20;       ///< queries per staged launch of run_host
+constexpr size_t SPILL_BUDGET = (size_t)512 << 20;   ///< most bytes of global stack columns: the grid shrinks for deep trees
+
+/// What the launches leave for the host, in device memory.
+struct Status {
+    uint32_t refused;   ///< the nesting check: tree_lib.h's refusal word
+    uint32_t overflow;  ///< a walk met a full stack column (a descriptor whose max_depth is below the tree's depth): its answer is void
+    unsigned long long box_steps, prim_tests;  ///< NEAREST_COUNT
+};
+
+struct SceneView {
+    const float4 *recs, *prims;
+    const float *pbox;
+    uint32_t n_recs, n_prims, root_ref;
+    float root_lo[3], root_hi[3];
+};
+
+__device__ __forceinline__ void xyz(const float4 &v, float o[3]) { o[0] = v.x; o[1] = v.y; o[2] = v.z; }
+
+// ---- the nesting check ----------------------------------------------------------------------------------------------------------------
+enum { WHY_BOX = 1, WHY_REF = 2, WHY_NEST = 3 };
+
+__device__ __forceinline__ bool inside(const float lo[3], const float hi[3], const float plo[3], const float phi[3]) {
+    bool ok = true;
+    for (int k = 0; k < 3; k++) ok = ok && lo[k] >= plo[k] && hi[k] <= phi[k] && lo[k] <= hi[k];  // (a NaN fails)
+    return ok;
+}
+
+/// The child `ref` with box [lo, hi] that record `r` holds (r = n_recs: the descriptor's root): 0, or why the tree is refused.
+__device__ uint32_t check_child(const SceneView &sc, uint32_t r, const float lo[3], const float hi[3], uint32_t ref) {
+    if (!tree_rule::box_ok(lo, hi)) return WHY_BOX;
+    if (!(ref & REF_LEAF)) {
+        if (ref >= sc.n_recs || (r < sc.n_recs && ref <= r)) return WHY_REF;
+        const float4 *c = sc.recs + 4 * (size_t)ref;
+        float l0[3], h0[3], l1[3], h1[3];
+        xyz(c[0], l0); xyz(c[1], h0); xyz(c[2], l1); xyz(c[3], h1);
+        return inside(l0, h0, lo, hi) && inside(l1, h1, lo, hi) ? 0u : (uint32_t)WHY_NEST;
+    }
+    const uint32_t first = ref & REF_INDEX;
+    if (first >= sc.n_prims) return WHY_REF;
+    const uint32_t count = (ref & (REF_TRIS | REF_SMALL)) ? ((ref & REF_TWO) ? 2u : 1u) : __float_as_uint(sc.prims[3 * (size_t)first].w) >> 2;
+    if (count > sc.n_prims - first) return WHY_REF;
+    for (uint32_t k = 0; k < count; k++) {
+        const float *b = sc.pbox + 6 * (size_t)(first + k);
+        const float pl[3] = {b[0], b[1], b[2]}, ph[3] = {b[3], b[4], b[5]};
+        if (!inside(pl, ph, lo, hi)) return WHY_NEST;
+    }
+    return 0;
+}
+
+// One thread per record, and one more for the descriptor's root box and root ref.
+__global__ void __launch_bounds__(256) k_nr_nesting(SceneView sc, Status *st) {
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    if (r > sc.n_recs) return;
+    uint32_t why;
+    if (r == sc.n_recs) {
+        why = check_child(sc, r, sc.root_lo, sc.root_hi, sc.root_ref);
+    } else {
+        const float4 *c = sc.recs + 4 * (size_t)r;
+        const float4 a = c[0], b = c[1], e = c[2], f = c[3];
+        float l0[3], h0[3], l1[3], h1[3];
+        xyz(a, l0); xyz(b, h0); xyz(e, l1); xyz(f, h1);
+        why = check_child(sc, r, l0, h0, __float_as_uint(a.w));
+        if (!why) why = check_child(sc, r, l1, h1, __float_as_uint(b.w));
+    }
+    if (why) refuse(&st->refused, r, why);
+}
+
+// ---- the walk -------------------------------------------------------------------------------------------------------------------------
+/// A lane's query and its walk.
+struct Lane {
+    uint32_t qi;           ///< the query, or NONE
+    uint32_t node;         ///< the ref to visit next
+    uint32_t sp, spilled;  ///< stack entries in all, and how many of them (the oldest) are in the global column
+    float p[3], r2;
+    float best, q[3];      ///< the best so far: d2 (+inf: none) and the point
+    uint32_t ord, type;    ///< its ordinal (NO_PRIM: none) and type
+#ifdef NEAREST_COUNT
+    uint32_t boxes, tests;
+#endif
+};
+
+/// The stack of a lane: the newest RING entries in a column of LDS (entry i at ring[(i % RING) * BLOCK + thread]: a wave's lanes are
+/// neighbours, no bank is shared), the older ones in the lane's column of `spill` (entry i at spill[i * lanes + lane]).
+struct Stack {
+    uint2 *ring;   ///< LDS, this thread's column
+    uint2 *spill;  ///< global, this lane's column
+    size_t lanes;
+    uint32_t cap;  ///< entries of the global column
+    uint32_t *overflow;
+};
+
+__device__ __forceinline__ void push(Lane &L, const Stack &st, uint32_t ref, float d2) {
+    if (L.sp - L.spilled == RING) {
+        if (L.spilled >= st.cap) {  // (no tree the descriptor describes gets here: the entry is dropped and the run is reported void)
+            *st.overflow = 1u;
+            return;
+        }
+        st.spill[L.spilled * st.lanes] = st.ring[(L.spilled % RING) * BLOCK];
+        L.spilled++;
+    }
+    st.ring[(L.sp % RING) * BLOCK] = make_uint2(ref, __float_as_uint(d2));
+    L.sp++;
+}
+
+__device__ __forceinline__ uint2 pop(Lane &L, const Stack &st) {
+    L.sp--;
+    if (L.sp >= L.spilled) return st.ring[(L.sp % RING) * BLOCK];
+    L.spilled = L.sp;
+    return st.spill[L.sp * st.lanes];
+}
+
+struct PrimData { float rec[12], box[6]; };
+
+__device__ __forceinline__ void load_prim(const SceneView &sc, uint32_t i, PrimData &d) {
+    const float4 a = sc.prims[3u * i], b = sc.prims[3u * i + 1u], c = sc.prims[3u * i + 2u];
+    const float *bx = sc.pbox + 6u * i;
+    d.rec[0] = a.x; d.rec[1] = a.y; d.rec[2] = a.z; d.rec[3] = a.w;
+    d.rec[4] = b.x; d.rec[5] = b.y; d.rec[6] = b.z; d.rec[7] = b.w;
+    d.rec[8] = c.x; d.rec[9] = c.y; d.rec[10] = c.z; d.rec[11] = c.w;
+    for (int k = 0; k < 6; k++) d.box[k] = bx[k];
+}
+
+/// One candidate: primitive `ord` of `type` with record and box `d`.
+__device__ __forceinline__ void candidate(Lane &L, uint32_t type, const PrimData &d, uint32_t ord) {
+    float q[3];
+    const float d2 = nr::closest_on_prim(type, d.rec, d.box, L.p, q);
+    if (nr::better(d2, ord, L.r2, L.best, L.ord)) {
+        L.best = d2; L.ord = ord; L.type = type & 3u;
+        L.q[0] = q[0]; L.q[1] = q[1]; L.q[2] = q[2];
+    }
+#ifdef NEAREST_COUNT
+    L.tests++;
+#endif
+}
+
+__device__ __forceinline__ void store_hit(gpuart_nearest_hit *hits, uint32_t i, const Lane &L) {
+    float4 *o = (float4 *)(hits + i);
+    if (L.ord == nr::NO_PRIM) {
+        o[0] = make_float4(-1.0f, 0.0f, 0.0f, 0.0f);
+        o[1] = make_float4(0.0f, __int_as_float(-1), __int_as_float(-1), 0.0f);
+    } else {
+        o[0] = make_float4(sqrtf(L.best), L.q[0], L.q[1], L.q[2]);
+        o[1] = make_float4(L.best, __uint_as_float(L.ord), __uint_as_float(L.type), 0.0f);
+    }
+}
+
+/// The query is answered: its record is stored and the lane is idle.
+__device__ __forceinline__ void finish(Lane &L, gpuart_nearest_hit *hits, Status *status) {
+    store_hit(hits, L.qi, L);
+#ifdef NEAREST_COUNT
+    atomicAdd(&status->box_steps, (unsigned long long)L.boxes);
+    atomicAdd(&status->prim_tests, (unsigned long long)L.tests);
+#endif
+    L.qi = NONE;
+}
+
+/// The next node off the stack that is not pruned by now, or the end of the walk.
+__device__ __forceinline__ void next_node(Lane &L, const Stack &st, gpuart_nearest_hit *hits, Status *status) {
+    for (;;) {
+        if (L.sp == 0) { finish(L, hits, status); return; }
+        const uint2 e = pop(L, st);
+        if (!nr::pruned(__uint_as_float(e.y), L.r2, L.best)) { L.node = e.x; return; }
+    }
+}
+
+/// Query i begins: a miss at once, or the user sphere as the first candidate and the root.
+__device__ __forceinline__ void begin(Lane &L, const SceneView &sc, const Stack &st, const float4 *points, uint32_t i, const float4 us, bool use_us,
+                                      gpuart_nearest_hit *hits, Status *status) {
+    const float4 pt = points[i];
+    L.qi = i;
+    L.p[0] = pt.x; L.p[1] = pt.y; L.p[2] = pt.z;
+    L.r2 = pt.w * pt.w;
+    L.best = __builtin_inff(); L.ord = nr::NO_PRIM; L.type = 0;
+    L.q[0] = L.q[1] = L.q[2] = 0.0f;
+    L.sp = L.spilled = 0;
+#ifdef NEAREST_COUNT
+    L.boxes = L.tests = 0;
+#endif
+    if (!nr::query_ok(L.p, pt.w)) { finish(L, hits, status); return; }
+    if (use_us) {
+        PrimData d;
+        for (int k = 0; k < 12; k++) d.rec[k] = 0.0f;
+        d.rec[0] = us.x; d.rec[1] = us.y; d.rec[2] = us.z; d.rec[4] = us.w;
+        d.box[0] = us.x - us.w; d.box[1] = us.y - us.w; d.box[2] = us.z - us.w;
+        d.box[3] = us.x + us.w; d.box[4] = us.y + us.w; d.box[5] = us.z + us.w;
+        candidate(L, nr::SPHERE, d, nr::USER_SPHERE);
+    }
+    if (nr::pruned(nr::box_d2(sc.root_lo, sc.root_hi, L.p), L.r2, L.best)) { finish(L, hits, status); return; }
+    L.node = sc.root_ref;
+}
+
+/// One step of a lane's walk: a record (both boxes, the nearer child entered, the farther stacked with its distance) or a leaf.
+__device__ __forceinline__ void step(Lane &L, const SceneView &sc, const Stack &st, gpuart_nearest_hit *hits, Status *status) {
+    const uint32_t ref = L.node;
+    if (!(ref & REF_LEAF)) {
+        const float4 *rec = sc.recs + 4u * ref;  // (base + 32-bit offset: 4 * n_recs <= 2^30)
+        const float4 a = rec[0], b = rec[1], c = rec[2], d = rec[3];
+        float l0[3], h0[3], l1[3], h1[3];
+        xyz(a, l0); xyz(b, h0); xyz(c, l1); xyz(d, h1);
+        const float dlo = nr::box_d2(l0, h0, L.p), dhi = nr::box_d2(l1, h1, L.p);
+        const uint32_t rlo = __float_as_uint(a.w), rhi = __float_as_uint(b.w);
+        const bool klo = !nr::pruned(dlo, L.r2, L.best), khi = !nr::pruned(dhi, L.r2, L.best);
+#ifdef NEAREST_COUNT
+        L.boxes++;
+#endif
+        if (klo && khi) {
+            const bool upper_first = dhi < dlo;
+            push(L, st, upper_first ? rlo : rhi, upper_first ? dlo : dhi);
+            L.node = upper_first ? rhi : rlo;
+        } else if (klo) L.node = rlo;
+        else if (khi) L.node = rhi;
+        else next_node(L, st, hits, status);
+        return;
+    }
+    // a leaf: a flagged one holds one or two primitives (REF_TWO: both records and boxes are in flight at once); an unflagged one says
+    // its count in its first record's word and is walked primitive by primitive, the next one's loads ahead of this one's test
+    const uint32_t first = ref & REF_INDEX;
+    const bool flagged = (ref & (REF_TRIS | REF_SMALL)) != 0;
+    PrimData cur, nxt;
+    load_prim(sc, first, cur);
+    nxt = cur;
+    if (flagged && (ref & REF_TWO)) load_prim(sc, first + 1u, nxt);
+    const uint32_t count = flagged ? ((ref & REF_TWO) ? 2u : 1u) : __float_as_uint(cur.rec[3]) >> 2;
+    for (uint32_t k = 0; k < count; k++) {
+        if (!flagged && k + 1u < count) load_prim(sc, first + k + 1u, nxt);
+        candidate(L, __float_as_uint(cur.rec[3]) & 3u, cur, first + k);
+        cur = nxt;
+    }
+    next_node(L, st, hits, status);
+}
+
+struct Launch {
+    SceneView sc;
+    const float4 *points;
+    uint32_t n;
+    float4 us;
+    uint32_t use_us;
+    gpuart_nearest_hit *hits;
+    uint2 *spill;
+    uint32_t cap;
+    uint32_t *cursor;
+    Status *status;
+};
+
+#ifndef NEAREST_PLAIN
+__device__ __forceinline__ uint32_t wave_value(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ uint64_t least(uint64_t a, uint64_t b) { return a < b ? a : b; }
+#endif
+
+// k_nearest. Persistent lanes: a wave takes chunks of CHUNK queries — its first by its place in the grid, later ones from the cursor — and
+// a lane whose walk has ended stores its record and is idle; once NEAREST_REFILL lanes are idle (or all) the idle lanes take the next
+// queries of the chunk. Queries differ in length by orders of magnitude: a point on the surface ends after one descent, a point far
+// outside walks much of the tree. Types are branched on at run time (closest_on_prim): the descriptor does not carry the type mask, and
+// one launch per mask would need a reduction over the records in bind for a gain that only the leaf step could show (a probe with the
+// leaf's type fixed to "triangle" compiled to the same 96 VGPRs and occupancy: DESIGN.md).
+__global__ void __launch_bounds__(BLOCK) k_nearest(Launch a) {
+    __shared__ uint2 ring[RING * BLOCK];
+    const size_t lanes = (size_t)gridDim.x * BLOCK;
+    const Stack st{ring + threadIdx.x, a.spill + ((size_t)blockIdx.x * BLOCK + threadIdx.x), lanes, a.cap, &a.status->overflow};
+    Lane L;
+    L.qi = NONE;
+#ifdef NEAREST_PLAIN
+    for (size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x; i < a.n; i += lanes) {
+        begin(L, a.sc, st, a.points, (uint32_t)i, a.us, a.use_us != 0, a.hits, a.status);
+        while (L.qi != NONE) step(L, a.sc, st, a.hits, a.status);
+    }
+#else
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = wave_value(blockIdx.x * WAVES + threadIdx.x / 64u), waves = gridDim.x * WAVES;
+    // the cursor (wave-uniform): [next, end) is what is left of the wave's chunk; chunks behind the static ones come from the counter
+    const uint64_t static_end = (uint64_t)waves * CHUNK;
+    uint32_t next = (uint32_t)least((uint64_t)wave * CHUNK, a.n), end = (uint32_t)least(((uint64_t)wave + 1) * CHUNK, a.n);
+    bool dry = false;
+    for (;;) {
+        unsigned long long idle = __ballot(L.qi == NONE);
+        if (idle && !dry && ((uint32_t)__popcll(idle) >= NEAREST_REFILL || idle == ~0ull)) {
+            while (idle && !dry) {
+                if (next == end) {
+                    uint32_t got = 0;
+                    if (static_end < a.n) {
+                        if (lane == 0) got = atomicAdd(a.cursor, CHUNK);
+                        got = wave_value(got);
+                    }
+                    const uint64_t base = static_end + got;
+                    if (static_end >= a.n || base >= a.n) { dry = true; break; }
+                    next = (uint32_t)base;
+                    end = (uint32_t)least(base + CHUNK, a.n);
+                }
+                const uint32_t want = (uint32_t)__popcll(idle), got = min(want, end - next);
+                const uint32_t rank = (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
+                if (L.qi == NONE && rank < got) begin(L, a.sc, st, a.points, next + rank, a.us, a.use_us != 0, a.hits, a.status);
+                next += got;
+                idle = __ballot(L.qi == NONE);  // (a query that was a miss at once has left its lane idle)
+            }
+            idle = __ballot(L.qi == NONE);
+        }
+        if (idle == ~0ull) {
+            if (dry) break;
+            continue;
+        }
+        if (L.qi != NONE) step(L, a.sc, st, a.hits, a.status);
+    }
+#endif
+}
+
+}  // namespace
+
+struct gpuart_nearest : ImageHandle {
+    Status *status = nullptr;    ///< device
+    uint32_t *cursor = nullptr;  ///< device
+    gpuart_hip_scene scene{};    ///< what the handle is bound to
+    bool bound = false;
+    DeviceBuffer spill;          ///< the lanes' global stack columns
+    DeviceBuffer staging;        ///< run_host: points and hits of a chunk
+    uint32_t device_blocks = 0;  ///< of k_nearest: what the device holds at once
+    uint32_t max_blocks = 0;     ///< the most a launch takes: device_blocks, or what gpuart_nearest_set_limits says
+    size_t spill_budget = SPILL_BUDGET, host_chunk = HOST_CHUNK;  ///< likewise
+    uint32_t last_blocks = 0, last_launches = 0;  ///< the last launch's grid; the launches of the last run
+    StepTimer check, walk;       ///< one step each
+    bool walked = false;
+};
+
+namespace {
+
+SceneView view_of(const gpuart_hip_scene *s) {
+    SceneView v;
+    v.recs = (const float4 *)s->recs;
+    v.prims = (const float4 *)s->prims;
+    v.pbox = (const float *)s->prim_boxes;
+    v.n_recs = (uint32_t)s->n_recs;
+    v.n_prims = (uint32_t)s->n_prims;
+    v.root_ref = s->root_ref;
+    memcpy(v.root_lo, s->root_min, 12);
+    memcpy(v.root_hi, s->root_max, 12);
+    return v;
+}
+
+int check_user_sphere(const float us[4]) {
+    if (!us) return 0;
+    for (int k = 0; k < 4; k++)
+        if (!(fabsf(us[k]) < INFINITY)) return fail(GPUART_HIP_ERR_ARG, "nearest: the user sphere has a word that is not finite");
+    if (!(us[3] >= 0)) return fail(GPUART_HIP_ERR_ARG, "nearest: the user sphere's radius is negative");
+    return 0;
+}
+
+int check_bound(const gpuart_nearest *h, const gpuart_hip_scene *s) {
+    if (!s) return fail(GPUART_HIP_ERR_ARG, "nearest: scene is NULL");
+    if (!h->bound) return fail(GPUART_HIP_ERR_ARG, "nearest: the handle is not bound to a scene: gpuart_nearest_bind first");
+    if (s->generation != h->scene.generation || s->recs != h->scene.recs || s->prims != h->scene.prims || s->prim_boxes != h->scene.prim_boxes ||
+        s->n_recs != h->scene.n_recs || s->n_prims != h->scene.n_prims || s->root_ref != h->scene.root_ref)
+        return fail(GPUART_HIP_ERR_ARG, "nearest: the handle was bound to another upload (generation " + std::to_string(h->scene.generation) + ", the scene's is " +
+                                            std::to_string(s->generation) + "): bind again");
+    if (!tree_rule::box_ok(s->root_min, s->root_max)) return fail(GPUART_HIP_ERR_ARG, "nearest: the root box is not finite and ordered");
+    return 0;
+}
+
+/// One launch over n queries in device memory.
+int launch(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, uint32_t n, const float us[4], gpuart_nearest_hit *hits) {
+    const size_t levels = (size_t)s->max_depth + 2;
+    const size_t by_budget = std::max<size_t>(1, h->spill_budget / (levels * sizeof(uint2) * BLOCK));
+    const size_t by_work = ((size_t)n + (size_t)CHUNK * WAVES - 1) / ((size_t)CHUNK * WAVES);
+    const uint32_t grid = (uint32_t)std::min({by_budget, by_work, (size_t)h->max_blocks});
+    if (int rc = ensure(h->stream, h->spill, levels * sizeof(uint2) * BLOCK * grid)) return rc;
+    Launch a;
+    a.sc = view_of(s);
+    a.points = (const float4 *)points;
+    a.n = n;
+    a.us = us ? make_float4(us[0], us[1], us[2], us[3]) : make_float4(0, 0, 0, 0);
+    a.use_us = us ? 1u : 0u;
+    a.hits = hits;
+    a.spill = (uint2 *)h->spill.mem;
+    a.cap = (uint32_t)levels;
+    a.cursor = h->cursor;
+    a.status = h->status;
+    HIP_TRY(hipMemsetAsync(h->cursor, 0, sizeof(uint32_t), h->stream));
+    h->walk.start(h->stream);
+    HIP_TRY(h->walk.mark());
+    k_nearest<<<grid, BLOCK, 0, h->stream>>>(a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(h->walk.mark());
+    h->walked = true;
+    h->last_blocks = grid;
+    h->last_launches++;
+    return 0;
+}
+
+/// What a finished stream may have left: a walk that met a full stack column.
+int read_overflow(gpuart_nearest *h) {
+    uint32_t over = 0;
+    HIP_TRY(hipMemcpyAsync(&over, &h->status->overflow, 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (over) {
+        HIP_TRY(hipMemsetAsync(&h->status->overflow, 0, 4, h->stream));
+        return fail(GPUART_HIP_ERR_ARG, "nearest: a walk met a full stack: the tree is deeper than the descriptor's max_depth says; the results are void");
+    }
+    return 0;
+}
+
+int check_run(gpuart_nearest *h, const gpuart_hip_scene *s, const void *points, size_t n, const float us[4], const void *hits, size_t align) {
+    if (int rc = check_handle(LIB, h)) return rc;
+    if (int rc = check_bound(h, s)) return rc;
+    if (n > GPUART_HIP_MAX_RAYS) return fail(GPUART_HIP_ERR_ARG, "nearest: too many queries: " + std::to_string(n));
+    if (int rc = check_user_sphere(us)) return rc;
+    if (n && (!points || !hits)) return fail(GPUART_HIP_ERR_ARG, "nearest: points or hits is NULL");
+    if (misaligned({points, hits}, align)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned pointer (points and hits need " + std::to_string(align) + " bytes)");
+    if (n && overlaps(points, n * 16, hits, n * 32)) return fail(GPUART_HIP_ERR_ARG, "nearest: hits overlaps points");
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char *gpuart_nearest_last_error(void) { return g_last_error.c_str(); }
+
+int gpuart_nearest_create(int device, gpuart_nearest **out) {
+    const int rc = create_tree_handle(LIB, device, out, gpuart_nearest_destroy, [](gpuart_nearest *h) {
+        hipError_t e = hipMalloc((void **)&h->status, sizeof(Status));
+        if (e == hipSuccess) e = hipMalloc((void **)&h->cursor, sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMemset(h->status, 0, sizeof(Status));
+        if (e == hipSuccess) e = h->check.create(1);
+        if (e == hipSuccess) e = h->walk.create(1);
+        return e;
+    });
+    if (rc) return rc;
+    gpuart_nearest *h = *out;
+    int per_cu = 0, cus = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_nearest, BLOCK, 0) != hipSuccess || per_cu < 1) per_cu = 1;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < 1) cus = 1;
+    h->device_blocks = h->max_blocks = (uint32_t)per_cu * (uint32_t)cus;
+    return 0;
+}
+
+int gpuart_nearest_destroy(gpuart_nearest *h) {
+    if (!h) return 0;
+    destroy_handle(h, {h->status, h->cursor, h->spill.mem, h->staging.mem});
+    h->check.destroy();
+    h->walk.destroy();
+    delete h;
+    return 0;
+}
+
+int gpuart_nearest_finish(gpuart_nearest *h) {
+    if (int rc = finish_handle(LIB, h)) return rc;
+    return read_overflow(h);
+}
+
+int gpuart_nearest_bind(gpuart_nearest *h, const gpuart_hip_scene *s) {
+    if (int rc = check_handle(LIB, h)) return rc;
+    h->bound = false;
+    if (!s) return fail(GPUART_HIP_ERR_ARG, "nearest: scene is NULL");
+    if (int rc = check_descriptor(s, LIB, "", "queried for closest points", true)) return rc;
+    if (misaligned({s->recs, s->prims}, 16) || misaligned({s->prim_boxes}, 4)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned arrays");
+    if (!tree_rule::box_ok(s->root_min, s->root_max)) return fail(GPUART_HIP_ERR_ARG, "nearest: the root box is not finite and ordered");
+    if (s->max_depth > GPUART_NEAREST_MAX_DEPTH)
+        return fail(GPUART_HIP_ERR_ARG, "nearest: the descriptor says a tree of " + std::to_string(s->max_depth) + " levels: more than " +
+                                            std::to_string(GPUART_NEAREST_MAX_DEPTH) + ", the deepest tree an upload or a rebuild accepts");
+    if (!tree_rule::root_ref_ok(s->root_ref, s->n_recs, s->n_prims)) return fail(GPUART_HIP_ERR_ARG, "nearest: the root ref is neither record 0 nor a leaf inside the primitives");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipMemsetAsync(h->status, 0, sizeof(Status), h->stream));
+    h->check.start(h->stream);
+    HIP_TRY(h->check.mark());
+    k_nr_nesting<<<blocks(s->n_recs + 1), 256, 0, h->stream>>>(view_of(s), h->status);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(h->check.mark());
+    uint32_t refused = 0;
+    HIP_TRY(hipMemcpyAsync(&refused, &h->status->refused, 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (int rc = h->check.read()) return rc;
+    if (refused) {
+        const char *const why[4] = {"", "a box it holds is not finite and ordered", "a ref or a leaf's count it holds is out of range, or an interior child is not behind its parent",
+                                    "a child's boxes (or a leaf's primitive boxes) do not lie inside the box it holds for that child"};
+        const uint32_t r = refused_index(refused);
+        return fail(GPUART_HIP_ERR_ARG, "nearest: " + (r == s->n_recs ? std::string("the root") : "record " + std::to_string(r)) + " refused: " + why[~refused & 3u] +
+                                            "; a pruned walk is exact only in a tree of nested boxes");
+    }
+    h->scene = *s;
+    h->bound = true;
+    return 0;
+}
+
+int gpuart_nearest_run(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, size_t n, const float us[4], gpuart_nearest_hit *hits) {
+    if (int rc = check_run(h, s, points, n, us, hits, 16)) return rc;
+    if (!n) return 0;
+    HIP_TRY(hipSetDevice(h->device));
+    h->last_launches = 0;
+    return launch(h, s, points, (uint32_t)n, us, hits);
+}
+
+int gpuart_nearest_run_host(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, size_t n, const float us[4], gpuart_nearest_hit *hits) {
+    if (int rc = check_run(h, s, points, n, us, hits, 4)) return rc;
+    if (!n) return 0;
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t chunk = std::min(n, h->host_chunk);
+    h->last_launches = 0;
+    if (int rc = ensure(h->stream, h->staging, chunk * (16 + 32))) return rc;
+    float *dpoints = (float *)h->staging.mem;
+    gpuart_nearest_hit *dhits = (gpuart_nearest_hit *)((char *)h->staging.mem + chunk * 16);
+    for (size_t at = 0; at < n; at += chunk) {
+        const size_t m = std::min(chunk, n - at);
+        HIP_TRY(hipMemcpyAsync(dpoints, points + 4 * at, m * 16, hipMemcpyHostToDevice, h->stream));
+        if (int rc = launch(h, s, dpoints, (uint32_t)m, us, dhits)) return rc;
+        HIP_TRY(hipMemcpyAsync(hits + at, dhits, m * 32, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    return read_overflow(h);
+}
+
+int gpuart_nearest_brute_host(gpuart_nearest *, const float *, size_t, const float *prims, const float *prim_boxes, size_t n_prims, const float *points, size_t n,
+                              const float us[4], gpuart_nearest_hit *hits) {
+    if ((n_prims && (!prims || !prim_boxes)) || (n && (!points || !hits))) return fail(GPUART_HIP_ERR_ARG, "nearest: prims, prim_boxes, points or hits is NULL");
+    if (n_prims > REF_INDEX) return fail(GPUART_HIP_ERR_ARG, "nearest: too many primitives: " + std::to_string(n_prims));
+    if (int rc = check_user_sphere(us)) return rc;
+    for (size_t i = 0; i < n; i++) {
+        const float *p = points + 4 * i, r = p[3], r2 = r * r;
+        float best = INFINITY, bq[3] = {0, 0, 0}, q[3];
+        uint32_t ord = nr::NO_PRIM, type = 0;
+        if (nr::query_ok(p, r)) {
+            if (us) {
+                const float rec[12] = {us[0], us[1], us[2], 0, us[3], 0, 0, 0, 0, 0, 0, 0};
+                const float box[6] = {us[0] - us[3], us[1] - us[3], us[2] - us[3], us[0] + us[3], us[1] + us[3], us[2] + us[3]};
+                const float d2 = nr::closest_on_prim(nr::SPHERE, rec, box, p, q);
+                if (nr::better(d2, nr::USER_SPHERE, r2, best, ord)) { best = d2; ord = nr::USER_SPHERE; type = nr::SPHERE; memcpy(bq, q, 12); }
+            }
+            for (size_t k = 0; k < n_prims; k++) {
+                const float *rec = prims + 12 * k;
+                uint32_t w;
+                memcpy(&w, rec + 3, 4);
+                const float d2 = nr::closest_on_prim(w & 3u, rec, prim_boxes + 6 * k, p, q);
+                if (nr::better(d2, (uint32_t)k, r2, best, ord)) { best = d2; ord = (uint32_t)k; type = w & 3u; memcpy(bq, q, 12); }
+            }
+        }
+        gpuart_nearest_hit &o = hits[i];
+        if (ord == nr::NO_PRIM) o = gpuart_nearest_hit{-1.0f, {0, 0, 0}, 0.0f, -1, -1, 0};
+        else o = gpuart_nearest_hit{sqrtf(best), {bq[0], bq[1], bq[2]}, best, (int32_t)ord, (int32_t)type, 0};
+    }
+    return 0;
+}
+
+int gpuart_nearest_step_ms(gpuart_nearest *h, double ms[2]) {
+    if (int rc = check_handle(LIB, h)) return rc;
+    if (!ms) return fail(GPUART_HIP_ERR_ARG, "nearest: ms is NULL");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->walked)
+        if (int rc = h->walk.read()) return rc;
+    ms[0] = h->check.ms[0];
+    ms[1] = h->walk.ms[0];
+    return 0;
+}
+
+int gpuart_nearest_set_limits(gpuart_nearest *h, uint32_t max_blocks, size_t spill_bytes, size_t host_chunk) {
+    if (int rc = check_handle(LIB, h)) return rc;
+    h->max_blocks = max_blocks ? std::min(max_blocks, h->device_blocks) : h->device_blocks;
+    h->spill_budget = spill_bytes ? spill_bytes : SPILL_BUDGET;
+    h->host_chunk = host_chunk ? std::min(host_chunk, HOST_CHUNK) : HOST_CHUNK;
+    return 0;
+}
+
+int gpuart_nearest_last_launch(gpuart_nearest *h, uint32_t *blocks, uint32_t *launches) {
+    if (int rc = check_handle(LIB, h)) return rc;
+    if (blocks) *blocks = h->last_blocks;
+    if (launches) *launches = h->last_launches;
+    return 0;
+}
+
+int gpuart_nearest_counts(gpuart_nearest *h, uint64_t out[2]) {
+    if (int rc = check_handle(LIB, h)) return rc;
+    if (!out) return fail(GPUART_HIP_ERR_ARG, "nearest: out is NULL");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    Status st;
+    HIP_TRY(hipMemcpy(&st, h->status, sizeof st, hipMemcpyDeviceToHost));
+    out[0] = st.box_steps; out[1] = st.prim_tests;
+    HIP_TRY(hipMemset(&h->status->box_steps, 0, 16));
+    return 0;
+}
+
+}  // extern "C"

@@ -1,0 +1,113 @@
+/* gpuart_nearest.h — C ABI of libgpuart_nearest.so: closest-point queries over an uploaded scene's tree, on the device (MI355X, gfx950).
+ * "Which primitive is nearest to this point, where on it, and how far": the question of contact, proximity, snapping and distance
+ * fields, answered from the tree the context already keeps current through refits, rebuilds and edits (include/gpuart_refit.h,
+ * gpuart_build.h, gpuart_ploc.h, gpuart_edit.h). The library reads the arrays gpuart_hip_scene_device hands out, writes nothing of them
+ * and knows nothing of contexts. DESIGN.md "Closest points".
+ *
+ * The contract (csrc/hip/nearest_rule.h states it for host and device, tests/nearest_ref.py restates it in NumPy float32; plain fp32, no
+ * contraction, IEEE division and square root, denormals kept):
+ *   point     closest_on_prim(type, record, box, p): q_raw, the point of the primitive's SURFACE nearest to p — a sphere's surface (a p
+ *             inside is at r - |p - c|; a p at the centre goes to +x), a disc's plane projection or its rim, a triangle's seven Voronoi
+ *             regions, a cone's lateral surface between t = 0 and t = length (what the intersector hits: no caps; a p on the axis takes
+ *             a fixed perpendicular) —, then q = min(max(q_raw, box_lo), box_hi) per component into the primitive's own box
+ *             (prim_boxes), d = p - q and d2 = (d.x*d.x + d.y*d.y) + d.z*d.z. A degenerate primitive (zero area, radius or length)
+ *             yields a finite point of its box: zero denominators select the start of the edge or axis, a NaN is clamped to box_lo;
+ *   answer    of the query (p, r): among the primitives with d2 <= r*r (fp32 product; r = +inf accepts everything) the one of least d2;
+ *             equal d2 goes to the lowest device ordinal. With a user sphere (c, R) the sphere takes part with ordinal -2, clamped to
+ *             c -+ R, and loses ties to every tree primitive;
+ *   miss      r NaN or negative, a word of p that is not finite, or nothing accepted: dist = -1, q = 0, d2 = 0, prim = -1, type = -1.
+ *             A hit writes dist = sqrtf(d2), q, d2, the ordinal and the primitive's type (0 sphere, 1 disc, 2 triangle, 3 cone);
+ *   walk      a child is skipped if and only if the squared distance of p to its box is > the best d2 so far, strictly, or > r*r. Since
+ *             q lies in the primitive's box and the tree's boxes are nested, that distance never exceeds the d2 of anything below the
+ *             child, bit for bit (the lemma of nearest_rule.h): the pruned walk returns the record of the brute force over all
+ *             primitives, in any child order. The kernel enters the nearer child first.
+ *
+ * The lemma needs nested boxes. Uploads refuse leaves that do not hold their primitives (exact_boxes), and refits, rebuilds and edits
+ * fold boxes exactly; only a hand-compiled tree can hold a child's box that leaves its parent's. gpuart_nearest_bind therefore checks
+ * every record in one streaming launch — an interior child's two boxes inside the box its parent's record holds for it, a leaf child's
+ * prim_boxes likewise, refs and leaf counts in range, an interior child behind its parent (pre-order) — and refuses the tree otherwise.
+ * An in-place refit keeps nesting by construction and the generation: no second bind.
+ *
+ * Limits: one GPU; scenes the uploader classified irregular or disorderly (exact_boxes) are refused; the answer is the nearest SURFACE
+ * point under the clamp — for a cone whose derived constants sit at the edge of the primitive rule's tolerance the clamp may move q by
+ * that tolerance.
+ *
+ * Conventions as gpuart_edit.h: 0 or a negative gpuart_hip_status; the last failure's message (per thread) from
+ * gpuart_nearest_last_error(), beginning "nearest:". One handle per device; it owns its HIP stream, its traversal stacks and staging. */
+#ifndef GPUART_NEAREST_H
+#define GPUART_NEAREST_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "gpuart_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct gpuart_nearest gpuart_nearest;
+
+#define GPUART_NEAREST_CHUNK 64u /* queries a wave of k_nearest takes from the cursor at a time */
+#define GPUART_NEAREST_RING 8u   /* stack entries a lane keeps in LDS; a walk that stacks more spills to the lane's global column, which is
+                                  * sized from scene->max_depth */
+
+#define GPUART_NEAREST_MAX_DEPTH 1024u /* bind refuses a descriptor whose max_depth is above this: the deepest tree an upload or a rebuild
+                                        * accepts, and what bounds the lanes' spill columns */
+
+typedef struct gpuart_nearest_hit {
+    float dist, q[3]; /* sqrtf(d2) and the point; a miss: -1, 0 */
+    float d2;
+    int32_t prim;     /* device ordinal; -1 none, -2 the user sphere */
+    int32_t type;     /* 0..3; -1 none */
+    uint32_t zero;
+} gpuart_nearest_hit; /* 32 bytes */
+
+int gpuart_nearest_create(int device, gpuart_nearest **out);
+int gpuart_nearest_destroy(gpuart_nearest *h);
+
+/* Checks the descriptor (layout, exact_boxes, arrays, counts, alignment, a finite ordered root box, the root ref, max_depth <=
+ * GPUART_NEAREST_MAX_DEPTH) and the nesting of
+ * every record (one launch, one small read-back; synchronous), and remembers scene->generation and the arrays. GPUART_HIP_ERR_ARG with
+ * the handle unbound when a check fails; the message names the first offending record. */
+int gpuart_nearest_bind(gpuart_nearest *h, const gpuart_hip_scene *scene);
+
+/* points: n x 4 floats {p.xyz, r}; hits: n records — device memory, 16-byte aligned, asynchronous on the handle's stream
+ * (gpuart_nearest_finish before the results are used). userSphere: {c.xyz, R} in host memory, NULL = none; finite words and R >= 0.
+ * GPUART_HIP_ERR_ARG, with nothing written, for a descriptor that is not the bound one (another generation or other arrays: bind again),
+ * an unbound handle, NULL or misaligned pointers, hits overlapping points, such a user sphere and n > GPUART_HIP_MAX_RAYS; n = 0 does
+ * nothing. */
+int gpuart_nearest_run(gpuart_nearest *h, const gpuart_hip_scene *scene, const float *points, size_t n, const float userSphere[4],
+                       gpuart_nearest_hit *hits);
+/* The same in host memory (4-byte alignment), synchronous, staged through the handle's memory in chunks of 2^20 queries. */
+int gpuart_nearest_run_host(gpuart_nearest *h, const gpuart_hip_scene *scene, const float *points, size_t n, const float userSphere[4],
+                            gpuart_nearest_hit *hits);
+/* The definition itself, with no device: recs (n_recs x 16 words; ignored), prims (n_prims x 12 words), prim_boxes (n_prims x 6), points
+ * and hits all in host memory; every primitive is tested in ordinal order. h may be NULL. What the CPU tests hold nearest_rule.h to, and
+ * what a caller without a GPU can use. GPUART_HIP_ERR_ARG for NULL pointers where the matching count is above zero. */
+int gpuart_nearest_brute_host(gpuart_nearest *h, const float *recs, size_t n_recs, const float *prims, const float *prim_boxes, size_t n_prims,
+                              const float *points, size_t n, const float userSphere[4], gpuart_nearest_hit *hits);
+
+/* How a run is cut up, for callers with little memory and for the tests, which reach the cursor, a shrunk grid and the staging loop with
+ * a few hundred queries: the most workgroups of 256 lanes a launch takes (0: what the device holds at once, the default, which also
+ * caps it; a launch never takes more than ceil(n / 256)), the most bytes of the lanes' spill columns (0: 512 MiB; (max_depth + 2) x 2 KiB
+ * per workgroup, at least one workgroup runs), and the queries per staged launch of gpuart_nearest_run_host (0: 2^20, which also caps
+ * it). The answers do not depend on any of them. */
+int gpuart_nearest_set_limits(gpuart_nearest *h, uint32_t max_blocks, size_t spill_bytes, size_t host_chunk);
+/* The workgroups of the last launch, and the launches of the last gpuart_nearest_run (1) or gpuart_nearest_run_host; either may be NULL. */
+int gpuart_nearest_last_launch(gpuart_nearest *h, uint32_t *blocks, uint32_t *launches);
+
+/* Device time in ms of the steps of the last bind and the last run: the nesting check, the walk. */
+int gpuart_nearest_step_ms(gpuart_nearest *h, double ms[2]);
+/* Box steps and primitive tests of the runs since the last call, summed over the queries — in a counting build of the library
+ * (-DNEAREST_COUNT, tools/nearest_time.py); the shipped kernel does not count and this yields zeros. Synchronous. */
+int gpuart_nearest_counts(gpuart_nearest *h, uint64_t out[2]);
+/* Waits for the handle's stream; GPUART_HIP_ERR_ARG if a walk since the last call met a full stack (a descriptor whose max_depth is below
+ * the tree's depth: the results are void; nothing is written out of bounds). */
+int gpuart_nearest_finish(gpuart_nearest *h);
+const char *gpuart_nearest_last_error(void);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* GPUART_NEAREST_H */
