@@ -1381,6 +1381,74 @@ class Backend:
         h._chk(N.gpuart_nearest_run_host(h, C.byref(scene), _p(points), C.c_size_t(points.shape[0]), us, _p(hits)))
         return hits
 
+    def within(self, points, user_sphere=None, max_items=1 << 27, out=None):
+        """Per query (p.xyz, r) of points (n, 4) the list of every primitive within r, as include/gpuart_nearest.h "Neighbour lists" defines
+        it, in CSR form: (offsets, items), list i = items[offsets[i]:offsets[i + 1]] in the tree's order (the user sphere, ordinal -2,
+        first). A NumPy array runs through host memory (synchronous) and returns (offsets uint32 (n + 1,), items NEAREST_HIT (total,)).
+        A contiguous (n, 4) float32 tensor on this context's device runs in place: the count, one 8-byte read-back of the total, the
+        fill; it returns (offsets int32 tensor (n + 1,), items float32 tensor (total, 8)), written into out = (offsets, items) if given
+        (an items tensor with more rows than the total is returned whole, rows from the total on untouched). A total above max_items,
+        and an `out` items tensor below the total, raise ValueError naming the total before anything is allocated or filled. Refusals
+        as closest_points."""
+        N = nearest_lib()
+        us = _user_sphere(user_sphere)
+        max_items = int(max_items)
+        if max_items < 0:
+            raise ValueError("max_items is negative")
+        scene = self.scene_device()
+        h = self._nearest_handle(scene)
+        total = C.c_uint64(0)
+
+        def refuse_above(total, rc=0):
+            if total > max_items:
+                raise ValueError("the lists hold %d items, more than max_items = %d" % (total, max_items))
+            h._chk(rc)
+
+        if type(points).__module__.startswith("torch"):
+            import torch
+            if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous() or points.device.type != "cuda":
+                raise ValueError("points must be a contiguous (n, 4) float32 tensor on the GPU")
+            index = points.device.index if points.device.index is not None else torch.cuda.current_device()
+            if index != self.device:
+                raise ValueError("points is on cuda:%d, this context on device %d: the kernel reads the tensor's memory in place" % (index, self.device))
+            n = points.shape[0]
+            offsets, items = out if out is not None else (None, None)
+            if offsets is None:
+                offsets = torch.zeros((n + 1,), dtype=torch.int32, device=points.device)
+            if offsets.dtype != torch.int32 or tuple(offsets.shape) != (n + 1,) or not offsets.is_contiguous() or offsets.device != points.device:
+                raise ValueError("out[0] must be a contiguous (n + 1,) int32 tensor on the points' device")
+            if items is not None and (items.dtype != torch.float32 or items.dim() != 2 or items.shape[1] != 8 or not items.is_contiguous() or
+                                      items.device != points.device):
+                raise ValueError("out[1] must be a contiguous (capacity, 8) float32 tensor on the points' device")
+            torch.cuda.current_stream(points.device).synchronize()
+            if n == 0:
+                offsets.zero_()
+                return offsets, items if items is not None else torch.empty((0, 8), dtype=torch.float32, device=points.device)
+            h._chk(N.gpuart_nearest_within_count(h, C.byref(scene), C.c_void_p(points.data_ptr()), C.c_size_t(n), us, C.c_void_p(offsets.data_ptr())))
+            rc = N.gpuart_nearest_within_total(h, C.byref(total))
+            refuse_above(total.value, rc)
+            if items is None:
+                items = torch.empty((total.value, 8), dtype=torch.float32, device=points.device)
+            elif items.shape[0] < total.value:
+                raise ValueError("out[1] has room for %d items, the lists hold %d" % (items.shape[0], total.value))
+            cap = items.shape[0]
+            h._chk(N.gpuart_nearest_within_fill(h, C.byref(scene), C.c_void_p(points.data_ptr()), C.c_size_t(n), us, C.c_void_p(offsets.data_ptr()),
+                                                C.c_void_p(items.data_ptr() if cap else None), C.c_size_t(cap)))
+            h.finish()
+            return offsets, items
+        if out is not None:
+            raise ValueError("out goes with device tensors")
+        points = _points_array(points)
+        n = points.shape[0]
+        offsets = np.zeros(n + 1, np.uint32)
+        args = (h, C.byref(scene), _p(points), C.c_size_t(n), us, _p(offsets))
+        rc = N.gpuart_nearest_within_host(*args, None, C.c_size_t(0), C.byref(total))
+        refuse_above(total.value, rc)
+        items = np.zeros(total.value, NEAREST_HIT)
+        if total.value:     # (the fill alone: the offsets are the count's of a moment ago)
+            h._chk(N.gpuart_nearest_within_fill_host(*args, _p(items), C.c_size_t(total.value)))
+        return offsets, items
+
     def pick(self, xy, user_sphere=None, want_prims=False):
         """Closest hit of the camera rays of frame pixels xy (n, 2) = (x, y), row 0 = bottom, any pixel of the frame: a RAY_HIT record
         array (and the primitive ordinals)."""
@@ -1909,6 +1977,23 @@ class Renderer:
             raise HipError("closest_points refused or failed: Renderer::ClosestPoints says why on stderr (an empty scene and a tree with irregular "
                            "boxes are not queried)")
         return hits
+
+    def primitives_within(self, points, with_user_sphere=True):
+        """Renderer::PrimitivesWithin: points (n, 4) = p.xyz, r in host memory -> (offsets uint32 (n + 1,), items NEAREST_HIT (total,)),
+        list i = items[offsets[i]:offsets[i + 1]]; ordinals as closest_points reports them."""
+        points = _points_array(points)
+        n = points.shape[0]
+        offsets = np.zeros(n + 1, np.uint32)
+        total = C.c_uint64(0)
+        us = C.c_int(1 if with_user_sphere else 0)
+        ok = self.L.gpuart_renderer_primitives_within(self.h, _p(points), C.c_size_t(n), us, _p(offsets), None, C.c_size_t(0), C.byref(total))
+        items = np.zeros(total.value if ok else 0, NEAREST_HIT)
+        if ok and total.value:
+            ok = self.L.gpuart_renderer_primitives_within_fill(self.h, _p(points), C.c_size_t(n), us, _p(offsets), _p(items), C.c_size_t(len(items)))
+        if not ok:
+            raise HipError("primitives_within refused or failed: Renderer::PrimitivesWithin says why on stderr (an empty scene and a tree with "
+                           "irregular boxes are not queried)")
+        return offsets, items
 
     def last_setprims_ms(self):
         """(whole call, BVH build, compilation, re-layout + upload) of the last set_primitives, ms, as the library timed them."""

@@ -177,4 +177,12 @@ NR_FN bool better(float d2, uint32_t ord, float r2, float best_d2, uint32_t best
 /// Is the child whose box is at squared distance b skipped: strictly beyond the best so far, or beyond the radius.
 NR_FN bool pruned(float b, float r2, float best_d2) { return b > best_d2 || b > r2; }
 
+// ---- the neighbour list: every primitive within r, not the nearest one (gpuart_nearest_within_*) -------------------------------------
+/// Is the primitive at squared distance d2 an item of the list of a query of squared radius r2. A NaN d2 is not.
+NR_FN bool within_accept(float d2, float r2) { return d2 <= r2; }
+
+/// Is the child whose box is at squared distance b skipped by a list's walk: beyond the radius, strictly. There is no best so far. By the
+/// lemma b <= d2 of everything below the child, so b > r2 implies d2 > r2 for all of it: the walk loses no item.
+NR_FN bool within_pruned(float b, float r2) { return b > r2; }
+
 }  // namespace nearest_rule

@@ -378,6 +378,16 @@ int gpuart_renderer_pick(gpuart_renderer *r, const uint32_t *xy, size_t n, int w
 int gpuart_renderer_closest_points(gpuart_renderer *r, const float *points, size_t n, int withUserSphere, gpuart_nearest_hit *hits) {
     return r->impl.ClosestPoints(points, n, withUserSphere != 0, hits) ? 1 : 0;
 }
+
+int gpuart_renderer_primitives_within(gpuart_renderer *r, const float *points, size_t n, int withUserSphere, uint32_t *offsets,
+                                      gpuart_nearest_hit *items, size_t capacity, uint64_t *total) {
+    return r->impl.PrimitivesWithin(points, n, withUserSphere != 0, offsets, items, capacity, total) ? 1 : 0;
+}
+
+int gpuart_renderer_primitives_within_fill(gpuart_renderer *r, const float *points, size_t n, int withUserSphere, const uint32_t *offsets,
+                                           gpuart_nearest_hit *items, size_t capacity) {
+    return r->impl.FillPrimitivesWithin(points, n, withUserSphere != 0, offsets, items, capacity) ? 1 : 0;
+}
 int gpuart_renderer_set_camera(gpuart_renderer *r, const float pos[3], const float dir[3], const float up[3], float fovY,
                                float screenDist) {
     return r->impl.SetCamera(make_camera(pos, dir, up, fovY, screenDist)) ? 1 : 0;

@@ -220,6 +220,15 @@ int gpuart_renderer_pick(gpuart_renderer *r, const uint32_t *xy, size_t n, int w
 /* Renderer::ClosestPoints (host memory, synchronous; 1 on success, 0 on refusal or error): points n x 4 floats {p.xyz, r}, hits n records
  * of include/gpuart_nearest.h; a hit's prim is the device ordinal, the position in the renderer's sorted list (-2: the user sphere). */
 int gpuart_renderer_closest_points(gpuart_renderer *r, const float *points, size_t n, int withUserSphere, gpuart_nearest_hit *hits);
+/* Renderer::PrimitivesWithin (host memory, synchronous; 1 on success, 0 on refusal or error) by the two-call protocol of
+ * gpuart_nearest_within_host: offsets[n + 1] and *total are always written; items (capacity records) only when it is not NULL and
+ * capacity >= *total — call once with items = NULL to learn the total, then again with room for it. Ordinals as closest_points'. */
+int gpuart_renderer_primitives_within(gpuart_renderer *r, const float *points, size_t n, int withUserSphere, uint32_t *offsets,
+                                      gpuart_nearest_hit *items, size_t capacity, uint64_t *total);
+/* The second call without its count: Renderer::FillPrimitivesWithin fills items (capacity >= offsets[n]) for the offsets the first call
+ * wrote, so the queries are walked twice in all and not three times. */
+int gpuart_renderer_primitives_within_fill(gpuart_renderer *r, const float *points, size_t n, int withUserSphere, const uint32_t *offsets,
+                                           gpuart_nearest_hit *items, size_t capacity);
 gpuart_hip_ctx *gpuart_renderer_backend(gpuart_renderer *r);
 void gpuart_renderer_params(gpuart_renderer *r, gpuart_params *out);
 /* What the renderer's last SetPrimitives spent inside the library, ms: whole call, BVH build, compilation, re-layout + upload. */

@@ -544,12 +544,10 @@ bool Renderer::Pick(const uint32_t *xy, size_t n, gpuart_ray_hit *hits, int32_t 
 // ---- closest-point queries (include/gpuart_nearest.h) ---------------------------------------------
 // The descriptor is looked up at every call: its generation says whether the handle's binding (the nesting check of every record) still
 // holds — an upload, a rebuild and an edit raise it, a refit in place does not.
-bool Renderer::ClosestPoints(const float *points, size_t n, bool withUserSphere, gpuart_nearest_hit *hits) {
-    if (!IsOK || (n && (!points || !hits))) return false;
-    gpuart_hip_scene scene;
+bool Renderer::BindNearest(const char *who, gpuart_hip_scene &scene) {
     if (!Check(gpuart_hip_scene_device(Backend, &scene), "looking up the scene's device arrays")) return false;
     if (scene.exact_boxes || !Tree.GetNumPrimitives()) {
-        std::cerr << "Renderer: ClosestPoints: an empty scene or a tree with irregular boxes (or boxes that do not bound their contents) is not queried." << std::endl;
+        std::cerr << "Renderer: " << who << ": an empty scene or a tree with irregular boxes (or boxes that do not bound their contents) is not queried." << std::endl;
         return false;
     }
     if (!Ensure(Nearest, NE)) return false;
@@ -558,8 +556,44 @@ bool Renderer::ClosestPoints(const float *points, size_t n, bool withUserSphere,
         if (!Check(gpuart_nearest_bind(Nearest, &scene), "binding the closest-point handle", gpuart_nearest_last_error)) return false;
         NearestGeneration = scene.generation;
     }
+    return true;
+}
+
+bool Renderer::ClosestPoints(const float *points, size_t n, bool withUserSphere, gpuart_nearest_hit *hits) {
+    if (!IsOK || (n && (!points || !hits))) return false;
+    gpuart_hip_scene scene;
+    if (!BindNearest("ClosestPoints", scene)) return false;
     const float us[4] = {UserSphere.pos.x, UserSphere.pos.y, UserSphere.pos.z, UserSphere.radius};
     return Check(gpuart_nearest_run_host(Nearest, &scene, points, n, withUserSphere ? us : nullptr, hits), "querying closest points", gpuart_nearest_last_error);
+}
+
+// ---- neighbour lists (include/gpuart_nearest.h, "Neighbour lists") ----------------------------------
+bool Renderer::PrimitivesWithin(const float *points, size_t n, bool withUserSphere, uint32_t *offsets, gpuart_nearest_hit *items, size_t capacity, uint64_t *total) {
+    if (!IsOK || (n && !points) || !offsets || !total) return false;
+    gpuart_hip_scene scene;
+    if (!BindNearest("PrimitivesWithin", scene)) return false;
+    const float us[4] = {UserSphere.pos.x, UserSphere.pos.y, UserSphere.pos.z, UserSphere.radius};
+    return Check(gpuart_nearest_within_host(Nearest, &scene, points, n, withUserSphere ? us : nullptr, offsets, items, capacity, total),
+                 "listing the primitives within a radius", gpuart_nearest_last_error);
+}
+
+bool Renderer::PrimitivesWithin(const float *points, size_t n, bool withUserSphere, std::vector<uint32_t> &offsets, std::vector<gpuart_nearest_hit> &items) {
+    offsets.assign(n + 1, 0u);
+    items.clear();
+    uint64_t total = 0;
+    if (!PrimitivesWithin(points, n, withUserSphere, offsets.data(), nullptr, 0, &total)) return false;
+    if (!total) return true;
+    items.resize(total);
+    return FillPrimitivesWithin(points, n, withUserSphere, offsets.data(), items.data(), items.size());
+}
+
+bool Renderer::FillPrimitivesWithin(const float *points, size_t n, bool withUserSphere, const uint32_t *offsets, gpuart_nearest_hit *items, size_t capacity) {
+    if (!IsOK || (n && !points) || !offsets) return false;
+    gpuart_hip_scene scene;
+    if (!BindNearest("PrimitivesWithin", scene)) return false;
+    const float us[4] = {UserSphere.pos.x, UserSphere.pos.y, UserSphere.pos.z, UserSphere.radius};
+    return Check(gpuart_nearest_within_fill_host(Nearest, &scene, points, n, withUserSphere ? us : nullptr, offsets, items, capacity),
+                 "filling the lists of the primitives within a radius", gpuart_nearest_last_error);
 }
 
 // ---- lighting / user sphere ---------------------------------------------------------------------

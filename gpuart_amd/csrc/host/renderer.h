@@ -329,6 +329,16 @@ public:
     /// is made by the first call and bound again after SetPrimitives, RebuildTree and EditPrimitives (a refit keeps the binding). False
     /// on refusal — an empty scene, a tree with irregular boxes — or error (std::cerr says why).
     bool ClosestPoints(const float *points, size_t n, bool withUserSphere, gpuart_nearest_hit *hits);
+    /// Neighbour lists (include/gpuart_nearest.h, "Neighbour lists"): per query every primitive within r, as CSR — list i is
+    /// items[offsets[i] .. offsets[i + 1]), in the tree's order, the user sphere (ordinal -2) first. The ordinals are those ClosestPoints
+    /// reports; the handle, its binding and the refusals are ClosestPoints'. Synchronous; no image changes.
+    bool PrimitivesWithin(const float *points, size_t n, bool withUserSphere, std::vector<uint32_t> &offsets, std::vector<gpuart_nearest_hit> &items);
+    /// The same by the two-call protocol of gpuart_nearest_within_host: offsets[n + 1] and *total are always written, items only when
+    /// it is not NULL and `capacity` records hold the total.
+    bool PrimitivesWithin(const float *points, size_t n, bool withUserSphere, uint32_t *offsets, gpuart_nearest_hit *items, size_t capacity, uint64_t *total);
+    /// The fill alone, for the offsets a call with items = NULL has just written (gpuart_nearest_within_fill_host): the second step of the
+    /// vector form above, which so walks the queries twice and not three times.
+    bool FillPrimitivesWithin(const float *points, size_t n, bool withUserSphere, const uint32_t *offsets, gpuart_nearest_hit *items, size_t capacity);
     unsigned GetTileWidth() const { return Tile.w; }
     unsigned GetTileHeight() const { return Tile.h; }
     const BoundingVolumesHierarchy &GetBVH() const { return Tree; }
@@ -403,8 +413,10 @@ private:
     gpuart_build *Builder = nullptr;      ///< made by the first RebuildTree or TreeCost
     gpuart_ploc *Clusterer = nullptr;     ///< made by the first RebuildTree(TREE_CLUSTERED)
     gpuart_edit *Editor = nullptr;        ///< made by the first EditPrimitives
-    gpuart_nearest *Nearest = nullptr;    ///< made by the first ClosestPoints
+    gpuart_nearest *Nearest = nullptr;    ///< made by the first ClosestPoints or PrimitivesWithin
     uint64_t NearestGeneration = 0;       ///< the generation Nearest is bound to (0: none)
+    /// The scene's descriptor with Nearest made and bound to it; false on refusal (`who` names the caller on std::cerr) or error.
+    bool BindNearest(const char *who, gpuart_hip_scene &scene);
     /// What BuildIntoSpare hands out beside the spare set's descriptor: new_to_old, the two ref words of each of the nRecs records (the
     /// clustered build's; the Morton order implies its own) and when the device run returned.
     struct BuiltTree {

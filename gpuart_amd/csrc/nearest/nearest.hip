@@ -1,12 +1,24 @@
 // nearest.hip — libgpuart_nearest.so (gfx950): closest-point queries over an uploaded scene's tree, as include/gpuart_nearest.h states
 // them. Built without flushing fp32 denormals and without contraction: the rule (csrc/hip/nearest_rule.h) is restated in NumPy float32
 // (tests/nearest_ref.py) and every answer is compared bit for bit. DESIGN.md "Closest points" describes the kernel. The library reads
-// the scene's arrays and writes none of them.
+// the scene's arrays and writes none of them. Behind k_nearest, which is held to the instructions it had, the neighbour lists of the same
+// header — every primitive within r, as CSR: k_within_count, rocPRIM's scan, k_within_fill — with the walk restated for them.
 //
 // Compile-time switches (tools/nearest_time.py builds the variants; the shipped library sets none):
-//   NEAREST_PLAIN   k_nearest as one thread per query with a grid stride and no refill: the A/B partner of the persistent-lane form
-//   NEAREST_COUNT   box steps and primitive tests counted per query and summed (gpuart_nearest_counts): a counting build, not a timed one
+//   NEAREST_PLAIN   k_nearest and k_within as one thread per query with a grid stride and no refill: the A/B partner of the persistent-lane form
+//   NEAREST_COUNT   box steps and primitive tests counted per query and summed (gpuart_nearest_counts, gpuart_nearest_within_counts): a
+//                   counting build, not a timed one
 //   NEAREST_REFILL  idle lanes of a wave at which it takes new queries (default 16)
+//   NEAREST_TOTAL_REDUCE  the lists' total by rocPRIM's reduce over the lengths, between the count and the scan, instead of the count
+//                   kernel's one atomic per wave: the A/B partner of the total that ships (tools/within_time.py)
+#include <rocprim/device/device_scan.hpp>
+#ifdef NEAREST_TOTAL_REDUCE
+#include <rocprim/device/device_reduce.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
+#endif
+
+#include <vector>
+
 #include "../image/image_lib.h"
 #include "../tree/tree_lib.h"
 #include "../hip/nearest_rule.h"
@@ -38,6 +50,11 @@ struct Status {
     uint32_t refused;   ///< the nesting check: tree_lib.h's refusal word
     uint32_t overflow;  ///< a walk met a full stack column (a descriptor whose max_depth is below the tree's depth): its answer is void
     unsigned long long box_steps, prim_tests;  ///< NEAREST_COUNT
+    // the neighbour lists (k_within), behind what k_nearest knows
+    uint32_t mismatch;  ///< a fill met a list that is longer or shorter than its offsets say, or an index at or beyond the capacity
+    uint32_t pad;
+    unsigned long long total;                      ///< of the last count: the items of all lists
+    unsigned long long w_box_steps, w_prim_tests;  ///< NEAREST_COUNT
 };
 
 struct SceneView {
@@ -336,6 +353,241 @@ __global__ void __launch_bounds__(BLOCK) k_nearest(Launch a) {
 #endif
 }
 
+// ---- the neighbour lists --------------------------------------------------------------------------------------------------------------
+// k_within<FILL>: the walk of k_nearest without a best so far. The lane, its stack and the persistent-lane loop are RESTATED here and not
+// shared with k_nearest through a template or a header: that kernel's instructions are held to what they were (profiles/within.txt), and
+// DESIGN.md "Neighbour lists" names the three as a candidate for a later "state once" change.
+struct WLane {
+    uint32_t qi;           ///< the query, or NONE
+    uint32_t node;         ///< the ref to visit next
+    uint32_t sp, spilled;  ///< stack entries in all, and how many of them (the oldest) are in the global column
+    float p[3], r2;
+    uint32_t at, end;      ///< count: the items so far, unused; fill: where the next item goes, and where the list ends
+#ifdef NEAREST_COUNT
+    uint32_t boxes, tests;
+#endif
+};
+
+/// The stack of a lane as Stack above, its entries the ref alone: ring[(i % RING) * BLOCK + thread], spill[i * lanes + lane].
+struct WStack {
+    uint32_t *ring, *spill;
+    size_t lanes;
+    uint32_t cap;
+    uint32_t *overflow;
+};
+
+struct WLaunch {
+    SceneView sc;
+    const float4 *points;
+    uint32_t n;
+    float4 us;
+    uint32_t use_us;
+    uint32_t *offsets;          ///< count: written; fill: read
+    gpuart_nearest_hit *items;  ///< fill
+    uint32_t capacity;          ///< fill: records of items
+    uint32_t *spill;
+    uint32_t cap;
+    uint32_t *cursor;
+    Status *status;
+};
+
+__device__ __forceinline__ void wpush(WLane &L, const WStack &st, uint32_t ref) {
+    if (L.sp - L.spilled == RING) {
+        if (L.spilled >= st.cap) {  // (as push above: the entry is dropped and the run is reported void)
+            *st.overflow = 1u;
+            return;
+        }
+        st.spill[L.spilled * st.lanes] = st.ring[(L.spilled % RING) * BLOCK];
+        L.spilled++;
+    }
+    st.ring[(L.sp % RING) * BLOCK] = ref;
+    L.sp++;
+}
+
+__device__ __forceinline__ uint32_t wpop(WLane &L, const WStack &st) {
+    L.sp--;
+    if (L.sp >= L.spilled) return st.ring[(L.sp % RING) * BLOCK];
+    L.spilled = L.sp;
+    return st.spill[L.sp * st.lanes];
+}
+
+/// One candidate: an item of the list if it is accepted. The fill stores it where the offsets put it, and nowhere else: an index at or
+/// beyond the list's end or the capacity is not written and marks the run.
+template <bool FILL>
+__device__ __forceinline__ void wcandidate(WLane &L, const WLaunch &a, uint32_t type, const PrimData &d, uint32_t ord) {
+    float q[3];
+    const float d2 = nr::closest_on_prim(type, d.rec, d.box, L.p, q);
+    if (nr::within_accept(d2, L.r2)) {
+        if (FILL) {
+            if (L.at < L.end && L.at < a.capacity) {
+                float4 *o = (float4 *)(a.items + L.at);
+                o[0] = make_float4(sqrtf(d2), q[0], q[1], q[2]);
+                o[1] = make_float4(d2, __uint_as_float(ord), __uint_as_float(type & 3u), 0.0f);
+            } else {
+                a.status->mismatch = 1u;
+            }
+        }
+        L.at++;
+    }
+#ifdef NEAREST_COUNT
+    L.tests++;
+#endif
+}
+
+/// The walk has ended: the count stores the list's length, the fill holds the list to its offsets; the lane is idle.
+template <bool FILL>
+__device__ __forceinline__ void wfinish(WLane &L, const WLaunch &a, unsigned long long &sum) {
+    if (FILL) {
+        if (L.at != L.end) a.status->mismatch = 1u;
+    } else {
+        a.offsets[L.qi] = L.at;
+        sum += L.at;
+    }
+#ifdef NEAREST_COUNT
+    atomicAdd(&a.status->w_box_steps, (unsigned long long)L.boxes);
+    atomicAdd(&a.status->w_prim_tests, (unsigned long long)L.tests);
+#endif
+    L.qi = NONE;
+}
+
+template <bool FILL>
+__device__ __forceinline__ void wnext(WLane &L, const WStack &st, const WLaunch &a, unsigned long long &sum) {
+    if (L.sp == 0) { wfinish<FILL>(L, a, sum); return; }
+    L.node = wpop(L, st);  // (what was stacked was not pruned, and nothing has changed since: there is no best so far)
+}
+
+/// Query i begins: an empty list at once, or the user sphere as the first candidate and the root.
+template <bool FILL>
+__device__ __forceinline__ void wbegin(WLane &L, const WLaunch &a, uint32_t i, unsigned long long &sum) {
+    const float4 pt = a.points[i];
+    L.qi = i;
+    L.p[0] = pt.x; L.p[1] = pt.y; L.p[2] = pt.z;
+    L.r2 = pt.w * pt.w;
+    L.sp = L.spilled = 0;
+    L.at = L.end = 0;
+    if (FILL) { L.at = a.offsets[i]; L.end = a.offsets[i + 1u]; }
+#ifdef NEAREST_COUNT
+    L.boxes = L.tests = 0;
+#endif
+    if (!nr::query_ok(L.p, pt.w)) { wfinish<FILL>(L, a, sum); return; }
+    if (a.use_us) {
+        PrimData d;
+        for (int k = 0; k < 12; k++) d.rec[k] = 0.0f;
+        d.rec[0] = a.us.x; d.rec[1] = a.us.y; d.rec[2] = a.us.z; d.rec[4] = a.us.w;
+        d.box[0] = a.us.x - a.us.w; d.box[1] = a.us.y - a.us.w; d.box[2] = a.us.z - a.us.w;
+        d.box[3] = a.us.x + a.us.w; d.box[4] = a.us.y + a.us.w; d.box[5] = a.us.z + a.us.w;
+        wcandidate<FILL>(L, a, nr::SPHERE, d, nr::USER_SPHERE);
+    }
+    if (nr::within_pruned(nr::box_d2(a.sc.root_lo, a.sc.root_hi, L.p), L.r2)) { wfinish<FILL>(L, a, sum); return; }
+    L.node = a.sc.root_ref;
+}
+
+/// One step of a lane's walk: a record (both boxes; the lower child entered, the upper stacked, each unless pruned) or a leaf (as step).
+template <bool FILL>
+__device__ __forceinline__ void wstep(WLane &L, const WStack &st, const WLaunch &a, unsigned long long &sum) {
+    const uint32_t ref = L.node;
+    if (!(ref & REF_LEAF)) {
+        const float4 *rec = a.sc.recs + 4u * ref;
+        const float4 ra = rec[0], rb = rec[1], rc = rec[2], rd = rec[3];
+        float l0[3], h0[3], l1[3], h1[3];
+        xyz(ra, l0); xyz(rb, h0); xyz(rc, l1); xyz(rd, h1);
+        const bool klo = !nr::within_pruned(nr::box_d2(l0, h0, L.p), L.r2), khi = !nr::within_pruned(nr::box_d2(l1, h1, L.p), L.r2);
+        const uint32_t rlo = __float_as_uint(ra.w), rhi = __float_as_uint(rb.w);
+#ifdef NEAREST_COUNT
+        L.boxes++;
+#endif
+        if (klo && khi) {
+            wpush(L, st, rhi);
+            L.node = rlo;
+        } else if (klo) L.node = rlo;
+        else if (khi) L.node = rhi;
+        else wnext<FILL>(L, st, a, sum);
+        return;
+    }
+    const uint32_t first = ref & REF_INDEX;
+    const bool flagged = (ref & (REF_TRIS | REF_SMALL)) != 0;
+    PrimData cur, nxt;
+    load_prim(a.sc, first, cur);
+    nxt = cur;
+    if (flagged && (ref & REF_TWO)) load_prim(a.sc, first + 1u, nxt);
+    const uint32_t count = flagged ? ((ref & REF_TWO) ? 2u : 1u) : __float_as_uint(cur.rec[3]) >> 2;
+    for (uint32_t k = 0; k < count; k++) {
+        if (!flagged && k + 1u < count) load_prim(a.sc, first + k + 1u, nxt);
+        wcandidate<FILL>(L, a, __float_as_uint(cur.rec[3]) & 3u, cur, first + k);
+        cur = nxt;
+    }
+    wnext<FILL>(L, st, a, sum);
+}
+
+// k_within_count (FILL = false) and k_within_fill (FILL = true): the persistent-lane loop of k_nearest. The count leaves each list's length
+// at offsets[qi] and adds the lengths of a wave's queries, summed in 64 bits lane by lane and then across the wave, to the status' total
+// with one atomic per wave at the end of its life. The fill writes list qi from offsets[qi] on, in the order of the walk.
+template <bool FILL>
+__device__ __forceinline__ void within_body(const WLaunch &a, uint32_t *ring) {
+    const size_t lanes = (size_t)gridDim.x * BLOCK;
+    const WStack st{ring + threadIdx.x, a.spill + ((size_t)blockIdx.x * BLOCK + threadIdx.x), lanes, a.cap, &a.status->overflow};
+    WLane L;
+    L.qi = NONE;
+    unsigned long long sum = 0;
+#ifdef NEAREST_PLAIN
+    for (size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x; i < a.n; i += lanes) {
+        wbegin<FILL>(L, a, (uint32_t)i, sum);
+        while (L.qi != NONE) wstep<FILL>(L, st, a, sum);
+    }
+#else
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = wave_value(blockIdx.x * WAVES + threadIdx.x / 64u), waves = gridDim.x * WAVES;
+    const uint64_t static_end = (uint64_t)waves * CHUNK;
+    uint32_t next = (uint32_t)least((uint64_t)wave * CHUNK, a.n), end = (uint32_t)least(((uint64_t)wave + 1) * CHUNK, a.n);
+    bool dry = false;
+    for (;;) {
+        unsigned long long idle = __ballot(L.qi == NONE);
+        if (idle && !dry && ((uint32_t)__popcll(idle) >= NEAREST_REFILL || idle == ~0ull)) {
+            while (idle && !dry) {
+                if (next == end) {
+                    uint32_t got = 0;
+                    if (static_end < a.n) {
+                        if (lane == 0) got = atomicAdd(a.cursor, CHUNK);
+                        got = wave_value(got);
+                    }
+                    const uint64_t base = static_end + got;
+                    if (static_end >= a.n || base >= a.n) { dry = true; break; }
+                    next = (uint32_t)base;
+                    end = (uint32_t)least(base + CHUNK, a.n);
+                }
+                const uint32_t want = (uint32_t)__popcll(idle), got = min(want, end - next);
+                const uint32_t rank = (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
+                if (L.qi == NONE && rank < got) wbegin<FILL>(L, a, next + rank, sum);
+                next += got;
+                idle = __ballot(L.qi == NONE);  // (a query whose list is empty at once has left its lane idle)
+            }
+            idle = __ballot(L.qi == NONE);
+        }
+        if (idle == ~0ull) {
+            if (dry) break;
+            continue;
+        }
+        if (L.qi != NONE) wstep<FILL>(L, st, a, sum);
+    }
+#endif
+#ifndef NEAREST_TOTAL_REDUCE
+    if (!FILL) {
+        for (int d = 32; d > 0; d >>= 1) sum += __shfl_down(sum, d, 64);
+        if ((threadIdx.x & 63u) == 0 && sum) atomicAdd(&a.status->total, sum);
+    }
+#endif
+}
+
+__global__ void __launch_bounds__(BLOCK) k_within_count(WLaunch a) {
+    __shared__ uint32_t ring[RING * BLOCK];
+    within_body<false>(a, ring);
+}
+
+__global__ void __launch_bounds__(BLOCK) k_within_fill(WLaunch a) {
+    __shared__ uint32_t ring[RING * BLOCK];
+    within_body<true>(a, ring);
+}
+
 }  // namespace
 
 struct gpuart_nearest : ImageHandle {
@@ -351,6 +603,17 @@ struct gpuart_nearest : ImageHandle {
     uint32_t last_blocks = 0, last_launches = 0;  ///< the last launch's grid; the launches of the last run
     StepTimer check, walk;       ///< one step each
     bool walked = false;
+    // the neighbour lists
+    DeviceBuffer scan_temp;      ///< rocPRIM's
+    uint32_t within_blocks[2] = {0, 0};  ///< of k_within_count and k_within_fill: what the device holds at once
+    uint64_t max_items = GPUART_NEAREST_WITHIN_MAX_ITEMS;
+    StepTimer wcount, wfill;     ///< count and scan; fill
+    bool counted = false, filled = false;  ///< the timers' events have been recorded
+    bool fill_pending = false;   ///< a fill was launched since the last finish looked at the mismatch word
+    bool total_read = false;     ///< last_total is the last count's
+    uint64_t last_total = 0;
+    size_t counted_n = 0;        ///< the queries of the last count
+    std::vector<uint32_t> host_offsets;  ///< within_host: a chunk's
 };
 
 namespace {
@@ -440,6 +703,186 @@ int check_run(gpuart_nearest *h, const gpuart_hip_scene *s, const void *points, 
     return 0;
 }
 
+// ---- the neighbour lists: the host's part -----------------------------------------------------------------------------------------------
+int check_within(gpuart_nearest *h, const gpuart_hip_scene *s, const void *points, size_t n, const float us[4], const void *offsets, size_t align) {
+    if (int rc = check_handle(LIB, h)) return rc;
+    if (int rc = check_bound(h, s)) return rc;
+    if (n > GPUART_HIP_MAX_RAYS) return fail(GPUART_HIP_ERR_ARG, "nearest: too many queries: " + std::to_string(n));
+    if (int rc = check_user_sphere(us)) return rc;
+    if (n && (!points || !offsets)) return fail(GPUART_HIP_ERR_ARG, "nearest: points or offsets is NULL");
+    if (misaligned({points}, align) || misaligned({offsets}, 4)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned pointer (points needs " + std::to_string(align) + " bytes, offsets 4)");
+    if (n && overlaps(points, n * 16, offsets, (n + 1) * 4)) return fail(GPUART_HIP_ERR_ARG, "nearest: offsets overlaps points");
+    return 0;
+}
+
+int too_many(uint64_t total, uint64_t cap) {
+    return fail(GPUART_HIP_ERR_ARG, "nearest: the lists hold " + std::to_string(total) + " items, more than the " + std::to_string(cap) + " a result may hold");
+}
+
+/// The grid, the spill columns and the launch's arguments but the lists' own.
+int within_args(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, uint32_t n, const float us[4], int pass, WLaunch &a, uint32_t &grid) {
+    const size_t levels = (size_t)s->max_depth + 2;
+    const size_t by_budget = std::max<size_t>(1, h->spill_budget / (levels * sizeof(uint32_t) * BLOCK));  // (entries of 4 bytes: half of k_nearest's columns)
+    const size_t by_work = ((size_t)n + (size_t)CHUNK * WAVES - 1) / ((size_t)CHUNK * WAVES);
+    grid = (uint32_t)std::min({by_budget, by_work, (size_t)h->max_blocks, (size_t)h->within_blocks[pass]});
+    if (int rc = ensure(h->stream, h->spill, levels * sizeof(uint32_t) * BLOCK * grid)) return rc;
+    a.sc = view_of(s);
+    a.points = (const float4 *)points;
+    a.n = n;
+    a.us = us ? make_float4(us[0], us[1], us[2], us[3]) : make_float4(0, 0, 0, 0);
+    a.use_us = us ? 1u : 0u;
+    a.offsets = nullptr;
+    a.items = nullptr;
+    a.capacity = 0;
+    a.spill = (uint32_t *)h->spill.mem;
+    a.cap = (uint32_t)levels;
+    a.cursor = h->cursor;
+    a.status = h->status;
+    return 0;
+}
+
+#ifdef NEAREST_TOTAL_REDUCE
+struct Widen {
+    __host__ __device__ unsigned long long operator()(uint32_t v) const { return v; }
+};
+#endif
+
+/// The count of n queries in device memory into offsets[0 .. n], scanned in place; the total stays in the status.
+int launch_count(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, uint32_t n, const float us[4], uint32_t *offsets) {
+    WLaunch a;
+    uint32_t grid;
+    if (int rc = within_args(h, s, points, n, us, 0, a, grid)) return rc;
+    a.offsets = offsets;
+    size_t scan_bytes = 0;
+    HIP_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, offsets, offsets, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), h->stream));
+#ifdef NEAREST_TOTAL_REDUCE
+    size_t reduce_bytes = 0;
+    HIP_TRY(rocprim::reduce(nullptr, reduce_bytes, rocprim::make_transform_iterator(offsets, Widen()), &h->status->total, 0ull, (size_t)n,
+                            rocprim::plus<unsigned long long>(), h->stream));
+    scan_bytes = std::max(scan_bytes, reduce_bytes);  // (one temporary buffer serves both, one after the other)
+#endif
+    if (int rc = ensure(h->stream, h->scan_temp, scan_bytes + 16)) return rc;
+    HIP_TRY(hipMemsetAsync(h->cursor, 0, sizeof(uint32_t), h->stream));
+    HIP_TRY(hipMemsetAsync(&h->status->total, 0, sizeof(unsigned long long), h->stream));
+    HIP_TRY(hipMemsetAsync(offsets + n, 0, sizeof(uint32_t), h->stream));
+    h->wcount.start(h->stream);
+    HIP_TRY(h->wcount.mark());
+    k_within_count<<<grid, BLOCK, 0, h->stream>>>(a);
+    HIP_TRY(hipGetLastError());
+#ifdef NEAREST_TOTAL_REDUCE
+    HIP_TRY(rocprim::reduce(h->scan_temp.mem, reduce_bytes, rocprim::make_transform_iterator(offsets, Widen()), &h->status->total, 0ull, (size_t)n,
+                            rocprim::plus<unsigned long long>(), h->stream));
+#endif
+    HIP_TRY(h->wcount.mark());
+    HIP_TRY(rocprim::exclusive_scan(h->scan_temp.mem, scan_bytes, offsets, offsets, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), h->stream));
+    HIP_TRY(h->wcount.mark());
+    h->counted = true;
+    h->total_read = false;
+    h->counted_n = n;
+    h->last_blocks = grid;
+    h->last_launches++;
+    return 0;
+}
+
+/// Waits for the stream and reads the last count's total.
+int read_total(gpuart_nearest *h) {
+    if (h->total_read) return 0;
+    unsigned long long t = 0;
+    HIP_TRY(hipMemcpyAsync(&t, &h->status->total, 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->last_total = t;
+    h->total_read = true;
+    return 0;
+}
+
+int launch_fill(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, uint32_t n, const float us[4], const uint32_t *offsets,
+                gpuart_nearest_hit *items, uint32_t capacity) {
+    WLaunch a;
+    uint32_t grid;
+    if (int rc = within_args(h, s, points, n, us, 1, a, grid)) return rc;
+    a.offsets = const_cast<uint32_t *>(offsets);
+    a.items = items;
+    a.capacity = capacity;
+    HIP_TRY(hipMemsetAsync(h->cursor, 0, sizeof(uint32_t), h->stream));
+    h->wfill.start(h->stream);
+    HIP_TRY(h->wfill.mark());
+    k_within_fill<<<grid, BLOCK, 0, h->stream>>>(a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(h->wfill.mark());
+    h->filled = h->fill_pending = true;
+    h->last_blocks = grid;
+    h->last_launches++;
+    return 0;
+}
+
+/// What a finished stream may have left: a fill whose lists were not what its offsets said.
+int read_mismatch(gpuart_nearest *h) {
+    uint32_t bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, &h->status->mismatch, 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (bad) {
+        HIP_TRY(hipMemsetAsync(&h->status->mismatch, 0, 4, h->stream));
+        return fail(GPUART_HIP_ERR_ARG, "nearest: the offsets are not this query set's count: the results are void");
+    }
+    return 0;
+}
+
+/// The fill pass in host memory, staged in chunks of host_chunk queries: a chunk's points and its offsets, made local to the chunk, go
+/// to the staging buffer (points, then items, then offsets), its items come back to items + offsets[chunk]. offsets: ascending, n + 1.
+int fill_staged(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, size_t n, const float us[4], const uint32_t *offsets,
+                gpuart_nearest_hit *items) {
+    const size_t chunk = std::min(n, h->host_chunk);
+    h->host_offsets.resize(chunk + 1);
+    uint32_t *local = h->host_offsets.data();
+    for (size_t at = 0; at < n; at += chunk) {
+        const size_t m = std::min(chunk, n - at);
+        const size_t room = offsets[at + m] - offsets[at];
+        if (int rc = ensure(h->stream, h->staging, chunk * 16 + room * 32 + (chunk + 1) * 4)) return rc;
+        float *dpoints = (float *)h->staging.mem;
+        gpuart_nearest_hit *ditems = (gpuart_nearest_hit *)((char *)h->staging.mem + chunk * 16);
+        uint32_t *doffsets = (uint32_t *)((char *)h->staging.mem + chunk * 16 + room * 32);
+        for (size_t k = 0; k <= m; k++) local[k] = offsets[at + k] - offsets[at];
+        HIP_TRY(hipMemcpyAsync(dpoints, points + 4 * at, m * 16, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(doffsets, local, (m + 1) * 4, hipMemcpyHostToDevice, h->stream));
+        if (int rc = launch_fill(h, s, dpoints, (uint32_t)m, us, doffsets, ditems, (uint32_t)room)) return rc;
+        if (room) HIP_TRY(hipMemcpyAsync(items + offsets[at], ditems, room * 32, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    h->fill_pending = false;
+    if (int rc = read_overflow(h)) return rc;
+    return read_mismatch(h);
+}
+
+/// The ordinals in the order of the unpruned depth-first walk from root_ref, lower child first; 0, or why the records are refused.
+int tree_order(const float *recs, size_t n_recs, uint32_t root_ref, const float *prims, size_t n_prims, std::vector<uint32_t> &order) {
+    order.clear();
+    if (!n_prims) return 0;
+    std::vector<uint32_t> stack{root_ref};
+    size_t visited = 0;
+    while (!stack.empty()) {
+        const uint32_t ref = stack.back();
+        stack.pop_back();
+        if (!(ref & REF_LEAF)) {
+            if (ref >= n_recs || ++visited > n_recs) return fail(GPUART_HIP_ERR_ARG, "nearest: a ref is out of range, or the records are no tree");
+            uint32_t lo, hi;
+            memcpy(&lo, recs + 16 * (size_t)ref + 3, 4);
+            memcpy(&hi, recs + 16 * (size_t)ref + 7, 4);
+            stack.push_back(hi);
+            stack.push_back(lo);
+            continue;
+        }
+        const uint32_t first = ref & REF_INDEX;
+        if (first >= n_prims) return fail(GPUART_HIP_ERR_ARG, "nearest: a leaf is out of range");
+        uint32_t w;
+        memcpy(&w, prims + 12 * (size_t)first + 3, 4);
+        const uint32_t count = (ref & (REF_TRIS | REF_SMALL)) ? ((ref & REF_TWO) ? 2u : 1u) : w >> 2;
+        if (count > n_prims - first || order.size() + count > n_prims) return fail(GPUART_HIP_ERR_ARG, "nearest: a leaf is out of range, or the records are no tree");
+        for (uint32_t k = 0; k < count; k++) order.push_back(first + k);
+    }
+    if (order.size() != n_prims) return fail(GPUART_HIP_ERR_ARG, "nearest: the records reach " + std::to_string(order.size()) + " of " + std::to_string(n_prims) + " primitives");
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -453,6 +896,8 @@ int gpuart_nearest_create(int device, gpuart_nearest **out) {
         if (e == hipSuccess) e = hipMemset(h->status, 0, sizeof(Status));
         if (e == hipSuccess) e = h->check.create(1);
         if (e == hipSuccess) e = h->walk.create(1);
+        if (e == hipSuccess) e = h->wcount.create(2);
+        if (e == hipSuccess) e = h->wfill.create(1);
         return e;
     });
     if (rc) return rc;
@@ -461,26 +906,38 @@ int gpuart_nearest_create(int device, gpuart_nearest **out) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_nearest, BLOCK, 0) != hipSuccess || per_cu < 1) per_cu = 1;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < 1) cus = 1;
     h->device_blocks = h->max_blocks = (uint32_t)per_cu * (uint32_t)cus;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_within_count, BLOCK, 0) != hipSuccess || per_cu < 1) per_cu = 1;
+    h->within_blocks[0] = (uint32_t)per_cu * (uint32_t)cus;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_within_fill, BLOCK, 0) != hipSuccess || per_cu < 1) per_cu = 1;
+    h->within_blocks[1] = (uint32_t)per_cu * (uint32_t)cus;
     return 0;
 }
 
 int gpuart_nearest_destroy(gpuart_nearest *h) {
     if (!h) return 0;
-    destroy_handle(h, {h->status, h->cursor, h->spill.mem, h->staging.mem});
+    destroy_handle(h, {h->status, h->cursor, h->spill.mem, h->staging.mem, h->scan_temp.mem});
     h->check.destroy();
     h->walk.destroy();
+    h->wcount.destroy();
+    h->wfill.destroy();
     delete h;
     return 0;
 }
 
 int gpuart_nearest_finish(gpuart_nearest *h) {
     if (int rc = finish_handle(LIB, h)) return rc;
-    return read_overflow(h);
+    if (int rc = read_overflow(h)) return rc;
+    if (!h->fill_pending) return 0;
+    h->fill_pending = false;
+    return read_mismatch(h);
 }
 
 int gpuart_nearest_bind(gpuart_nearest *h, const gpuart_hip_scene *s) {
     if (int rc = check_handle(LIB, h)) return rc;
     h->bound = false;
+    h->counted_n = 0;  // (the status is zeroed below, the last count's total with it: a fill wants a count of this binding)
+    h->last_total = 0;
+    h->total_read = true;
     if (!s) return fail(GPUART_HIP_ERR_ARG, "nearest: scene is NULL");
     if (int rc = check_descriptor(s, LIB, "", "queried for closest points", true)) return rc;
     if (misaligned({s->recs, s->prims}, 16) || misaligned({s->prim_boxes}, 4)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned arrays");
@@ -606,6 +1063,180 @@ int gpuart_nearest_counts(gpuart_nearest *h, uint64_t out[2]) {
     HIP_TRY(hipMemcpy(&st, h->status, sizeof st, hipMemcpyDeviceToHost));
     out[0] = st.box_steps; out[1] = st.prim_tests;
     HIP_TRY(hipMemset(&h->status->box_steps, 0, 16));
+    return 0;
+}
+
+// ---- the neighbour lists --------------------------------------------------------------------------------------------------------------
+int gpuart_nearest_within_count(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, size_t n, const float us[4], uint32_t *offsets) {
+    if (int rc = check_within(h, s, points, n, us, offsets, 16)) return rc;
+    h->last_launches = 0;
+    if (!n) {
+        h->last_total = 0;
+        h->total_read = true;
+        h->counted_n = 0;
+        return 0;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    return launch_count(h, s, points, (uint32_t)n, us, offsets);
+}
+
+int gpuart_nearest_within_total(gpuart_nearest *h, uint64_t *total) {
+    if (int rc = check_handle(LIB, h)) return rc;
+    if (!total) return fail(GPUART_HIP_ERR_ARG, "nearest: total is NULL");
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = read_total(h)) return rc;
+    *total = h->last_total;
+    return h->last_total > h->max_items ? too_many(h->last_total, h->max_items) : 0;
+}
+
+int gpuart_nearest_within_fill(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, size_t n, const float us[4], const uint32_t *offsets,
+                               gpuart_nearest_hit *items, size_t capacity) {
+    if (int rc = check_within(h, s, points, n, us, offsets, 16)) return rc;
+    if (misaligned({items}, 16)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned pointer (items needs 16 bytes)");
+    if (n != h->counted_n) return fail(GPUART_HIP_ERR_ARG, "nearest: the last count was of " + std::to_string(h->counted_n) + " queries, not of " + std::to_string(n));
+    if (!n) return 0;
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = read_total(h)) return rc;
+    if (h->last_total > h->max_items) return too_many(h->last_total, h->max_items);
+    if (capacity < h->last_total)
+        return fail(GPUART_HIP_ERR_ARG, "nearest: items has room for " + std::to_string(capacity) + " records, the last count's total is " + std::to_string(h->last_total));
+    if (capacity && !items) return fail(GPUART_HIP_ERR_ARG, "nearest: items is NULL");
+    capacity = std::min<size_t>(capacity, GPUART_NEAREST_WITHIN_MAX_ITEMS);
+    if (capacity && (overlaps(items, capacity * 32, points, n * 16) || overlaps(items, capacity * 32, offsets, (n + 1) * 4)))
+        return fail(GPUART_HIP_ERR_ARG, "nearest: items overlaps points or offsets");
+    h->last_launches = 0;
+    return launch_fill(h, s, points, (uint32_t)n, us, offsets, items, (uint32_t)capacity);
+}
+
+int gpuart_nearest_within_host(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, size_t n, const float us[4], uint32_t *offsets,
+                               gpuart_nearest_hit *items, size_t capacity, uint64_t *total) {
+    if (int rc = check_within(h, s, points, n, us, offsets, 4)) return rc;
+    if (!offsets || !total) return fail(GPUART_HIP_ERR_ARG, "nearest: offsets or total is NULL");
+    if (misaligned({items}, 4)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned pointer (items needs 4 bytes)");
+    offsets[0] = 0;
+    *total = 0;
+    h->last_launches = 0;
+    if (!n) return 0;
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t chunk = std::min(n, h->host_chunk);
+    // the staging buffer: a chunk's points, then its items, then its offsets
+    if (int rc = ensure(h->stream, h->staging, chunk * 16 + (chunk + 1) * 4)) return rc;
+    h->host_offsets.resize(chunk + 1);
+    uint32_t *local = h->host_offsets.data();
+    uint64_t base = 0;
+    for (size_t at = 0; at < n; at += chunk) {
+        const size_t m = std::min(chunk, n - at);
+        float *dpoints = (float *)h->staging.mem;
+        uint32_t *doffsets = (uint32_t *)((char *)h->staging.mem + chunk * 16);
+        HIP_TRY(hipMemcpyAsync(dpoints, points + 4 * at, m * 16, hipMemcpyHostToDevice, h->stream));
+        if (int rc = launch_count(h, s, dpoints, (uint32_t)m, us, doffsets)) return rc;
+        HIP_TRY(hipMemcpyAsync(local, doffsets, m * 4, hipMemcpyDeviceToHost, h->stream));
+        if (int rc = read_total(h)) return rc;
+        for (size_t k = 0; k < m; k++) offsets[at + k] = (uint32_t)(base + local[k]);  // (rebased: the chunk's lists follow the earlier chunks')
+        base += h->last_total;
+    }
+    offsets[n] = (uint32_t)base;
+    *total = base;
+    h->last_total = base;
+    h->counted_n = n;
+    if (int rc = read_overflow(h)) return rc;
+    if (base > h->max_items) return too_many(base, h->max_items);
+    if (!items || capacity < base) return 0;
+    return fill_staged(h, s, points, n, us, offsets, items);
+}
+
+int gpuart_nearest_within_fill_host(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, size_t n, const float us[4], const uint32_t *offsets,
+                                    gpuart_nearest_hit *items, size_t capacity) {
+    if (int rc = check_within(h, s, points, n, us, offsets, 4)) return rc;
+    if (!offsets) return fail(GPUART_HIP_ERR_ARG, "nearest: offsets is NULL");
+    if (misaligned({items}, 4)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned pointer (items needs 4 bytes)");
+    if (offsets[0] != 0) return fail(GPUART_HIP_ERR_ARG, "nearest: offsets[0] is not 0");
+    for (size_t i = 0; i < n; i++)
+        if (offsets[i + 1] < offsets[i]) return fail(GPUART_HIP_ERR_ARG, "nearest: the offsets decrease at query " + std::to_string(i));
+    const uint64_t total = offsets[n];
+    if (total > h->max_items) return too_many(total, h->max_items);
+    if (capacity < total)
+        return fail(GPUART_HIP_ERR_ARG, "nearest: items has room for " + std::to_string(capacity) + " records, the offsets end at " + std::to_string(total));
+    if (total && !items) return fail(GPUART_HIP_ERR_ARG, "nearest: items is NULL");
+    h->last_launches = 0;
+    if (!n) return 0;
+    HIP_TRY(hipSetDevice(h->device));
+    return fill_staged(h, s, points, n, us, offsets, items);
+}
+
+int gpuart_nearest_within_brute_host(const float *recs, size_t n_recs, uint32_t root_ref, const float *prims, const float *prim_boxes, size_t n_prims,
+                                     const float *points, size_t n, const float us[4], uint32_t *offsets, gpuart_nearest_hit *items, size_t capacity,
+                                     uint64_t *total) {
+    if ((n_prims && (!prims || !prim_boxes)) || (n_recs && !recs) || (n && !points) || !offsets || !total)
+        return fail(GPUART_HIP_ERR_ARG, "nearest: recs, prims, prim_boxes, points, offsets or total is NULL");
+    if (n_prims > REF_INDEX || n_recs > REF_INDEX) return fail(GPUART_HIP_ERR_ARG, "nearest: too many primitives or records: " + std::to_string(n_prims));
+    if (n > GPUART_HIP_MAX_RAYS) return fail(GPUART_HIP_ERR_ARG, "nearest: too many queries: " + std::to_string(n));
+    if (int rc = check_user_sphere(us)) return rc;
+    std::vector<uint32_t> order;
+    if (int rc = tree_order(recs, n_recs, root_ref, prims, n_prims, order)) return rc;
+    // one rule for both passes: visit(i, emit) calls emit(record) for every item of list i, in the contract's order
+    auto visit = [&](size_t i, auto &&emit) {
+        const float *p = points + 4 * i, r = p[3], r2 = r * r;
+        float q[3];
+        if (!nr::query_ok(p, r)) return;
+        if (us) {
+            const float rec[12] = {us[0], us[1], us[2], 0, us[3], 0, 0, 0, 0, 0, 0, 0};
+            const float box[6] = {us[0] - us[3], us[1] - us[3], us[2] - us[3], us[0] + us[3], us[1] + us[3], us[2] + us[3]};
+            const float d2 = nr::closest_on_prim(nr::SPHERE, rec, box, p, q);
+            if (nr::within_accept(d2, r2)) emit(gpuart_nearest_hit{sqrtf(d2), {q[0], q[1], q[2]}, d2, (int32_t)nr::USER_SPHERE, (int32_t)nr::SPHERE, 0});
+        }
+        for (const uint32_t k : order) {
+            const float *rec = prims + 12 * (size_t)k;
+            uint32_t w;
+            memcpy(&w, rec + 3, 4);
+            const float d2 = nr::closest_on_prim(w & 3u, rec, prim_boxes + 6 * (size_t)k, p, q);
+            if (nr::within_accept(d2, r2)) emit(gpuart_nearest_hit{sqrtf(d2), {q[0], q[1], q[2]}, d2, (int32_t)k, (int32_t)(w & 3u), 0});
+        }
+    };
+    uint64_t sum = 0;
+    for (size_t i = 0; i < n; i++) {
+        offsets[i] = (uint32_t)sum;
+        visit(i, [&](const gpuart_nearest_hit &) { sum++; });
+    }
+    offsets[n] = (uint32_t)sum;
+    *total = sum;
+    if (sum > GPUART_NEAREST_WITHIN_MAX_ITEMS) return too_many(sum, GPUART_NEAREST_WITHIN_MAX_ITEMS);
+    if (!items || capacity < sum) return 0;
+    size_t at = 0;
+    for (size_t i = 0; i < n; i++) visit(i, [&](const gpuart_nearest_hit &r) { items[at++] = r; });
+    return 0;
+}
+
+int gpuart_nearest_within_set_max_items(gpuart_nearest *h, uint64_t max_items) {
+    if (int rc = check_handle(LIB, h)) return rc;
+    h->max_items = max_items ? std::min<uint64_t>(max_items, GPUART_NEAREST_WITHIN_MAX_ITEMS) : GPUART_NEAREST_WITHIN_MAX_ITEMS;
+    return 0;
+}
+
+int gpuart_nearest_within_step_ms(gpuart_nearest *h, double ms[3]) {
+    if (int rc = check_handle(LIB, h)) return rc;
+    if (!ms) return fail(GPUART_HIP_ERR_ARG, "nearest: ms is NULL");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->counted)
+        if (int rc = h->wcount.read()) return rc;
+    if (h->filled)
+        if (int rc = h->wfill.read()) return rc;
+    ms[0] = h->wcount.ms[0];
+    ms[1] = h->wcount.ms[1];
+    ms[2] = h->wfill.ms[0];
+    return 0;
+}
+
+int gpuart_nearest_within_counts(gpuart_nearest *h, uint64_t out[2]) {
+    if (int rc = check_handle(LIB, h)) return rc;
+    if (!out) return fail(GPUART_HIP_ERR_ARG, "nearest: out is NULL");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    Status st;
+    HIP_TRY(hipMemcpy(&st, h->status, sizeof st, hipMemcpyDeviceToHost));
+    out[0] = st.w_box_steps; out[1] = st.w_prim_tests;
+    HIP_TRY(hipMemset(&h->status->w_box_steps, 0, 16));
     return 0;
 }
 

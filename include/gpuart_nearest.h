@@ -91,7 +91,7 @@ int gpuart_nearest_brute_host(gpuart_nearest *h, const float *recs, size_t n_rec
 /* How a run is cut up, for callers with little memory and for the tests, which reach the cursor, a shrunk grid and the staging loop with
  * a few hundred queries: the most workgroups of 256 lanes a launch takes (0: what the device holds at once, the default, which also
  * caps it; a launch never takes more than ceil(n / 256)), the most bytes of the lanes' spill columns (0: 512 MiB; (max_depth + 2) x 2 KiB
- * per workgroup, at least one workgroup runs), and the queries per staged launch of gpuart_nearest_run_host (0: 2^20, which also caps
+ * per workgroup, 1 KiB for the walks of the neighbour lists, whose stack entries are 4 bytes; at least one workgroup runs), and the queries per staged launch of gpuart_nearest_run_host (0: 2^20, which also caps
  * it). The answers do not depend on any of them. */
 int gpuart_nearest_set_limits(gpuart_nearest *h, uint32_t max_blocks, size_t spill_bytes, size_t host_chunk);
 /* The workgroups of the last launch, and the launches of the last gpuart_nearest_run (1) or gpuart_nearest_run_host; either may be NULL. */
@@ -106,6 +106,67 @@ int gpuart_nearest_counts(gpuart_nearest *h, uint64_t out[2]);
  * the tree's depth: the results are void; nothing is written out of bounds). */
 int gpuart_nearest_finish(gpuart_nearest *h);
 const char *gpuart_nearest_last_error(void);
+
+/* ---- Neighbour lists: every primitive within r of a point (DESIGN.md "Neighbour lists"; tests/within_ref.py restates this) ----------
+ *   query     (p, r), exactly as above;
+ *   list      one gpuart_nearest_hit per primitive whose d2 = dist2(p, closest_on_prim(..)) satisfies d2 <= r*r (the product in fp32, the
+ *             comparison <=; r = +inf lists every primitive). An item is, bit for bit, the record gpuart_nearest_run writes for (p, +inf)
+ *             if that primitive were alone in the scene: sqrtf(d2), q, d2, the device ordinal, the type, 0. With a user sphere the sphere
+ *             takes part with ordinal -2 under the same acceptance. An invalid query (r NaN or negative, a word of p that is not finite)
+ *             has an empty list;
+ *   order     inside a list: the user sphere first, if accepted; then the primitives in the order of the UNPRUNED depth-first walk of the
+ *             tree, lower child first, a leaf's primitives by ascending ordinal. The order is a function of the tree alone: equal for
+ *             equal trees, kept by a refit, changed by a rebuild or an edit. A caller may rely on nothing beyond that — not on distance,
+ *             not on ordinal;
+ *   walk      a child is skipped if and only if the squared distance of p to its box is > r*r; the root likewise. There is no best so
+ *             far. Corollary of the lemma of nearest_rule.h: that distance is <= the d2 of everything below the child, so what is skipped
+ *             has d2 > r*r and the pruned walk loses no item;
+ *   output    CSR: offsets[n + 1] (uint32; offsets[0] = 0, offsets[i + 1] - offsets[i] the length of list i, offsets[n] the total) and
+ *             items[total]. The total is computed exactly in 64 bits. A total above GPUART_NEAREST_WITHIN_MAX_ITEMS, or above the lower
+ *             cap gpuart_nearest_within_set_max_items sets, is refused (GPUART_HIP_ERR_ARG) and nothing is written to items.
+ * Two passes over the same queries: a count, which walks every query, writes the lengths and scans them in place, and a fill, which walks
+ * again and writes the items where the offsets put them. All of these need a bound handle as gpuart_nearest_run does, and make its
+ * refusals with nothing written. */
+#define GPUART_NEAREST_WITHIN_MAX_ITEMS 0x7fffffffu /* 2^31 - 1: an int32 holds every offset */
+
+/* points: n x 4 floats, offsets: n + 1 words — device memory (16- and 4-byte aligned, not overlapping), asynchronous on the handle's
+ * stream. n = 0 does nothing. */
+int gpuart_nearest_within_count(gpuart_nearest *h, const gpuart_hip_scene *scene, const float *points, size_t n, const float userSphere[4],
+                                uint32_t *offsets);
+/* Waits for the stream and yields the exact total of the last count. GPUART_HIP_ERR_ARG, with *total written, if it is above the cap. */
+int gpuart_nearest_within_total(gpuart_nearest *h, uint64_t *total);
+/* Writes list i at items[offsets[i] ..] in the contract's order: the same points, n and user sphere as the last count, and its offsets.
+ * items: `capacity` records in device memory, 16-byte aligned (NULL with capacity 0). Asynchronous. Every store is guarded: an index
+ * >= offsets[i + 1] or >= capacity is not written, and a list that is longer or shorter than its offsets say marks the run:
+ * gpuart_nearest_finish then returns GPUART_HIP_ERR_ARG, "the offsets are not this query set's count: the results are void". A fill
+ * never writes outside items[0 .. capacity), whatever it is handed. Refused before any launch: a capacity below the last count's total
+ * (the call waits for the stream to learn it), that total above the cap, another n than the last count's. */
+int gpuart_nearest_within_fill(gpuart_nearest *h, const gpuart_hip_scene *scene, const float *points, size_t n, const float userSphere[4],
+                               const uint32_t *offsets, gpuart_nearest_hit *items, size_t capacity);
+/* Both passes in host memory (4-byte alignment), synchronous, staged in chunks of the host_chunk of gpuart_nearest_set_limits; a chunk's
+ * offsets are rebased on the host, so the result is the unstaged one's byte for byte. Always writes offsets[0 .. n] and *total; writes
+ * items only when items != NULL and capacity >= total — a short capacity is no error: call again with room for *total. A total above
+ * the cap is GPUART_HIP_ERR_ARG. gpuart_nearest_last_launch counts the launches of both passes. */
+int gpuart_nearest_within_host(gpuart_nearest *h, const gpuart_hip_scene *scene, const float *points, size_t n, const float userSphere[4],
+                               uint32_t *offsets, gpuart_nearest_hit *items, size_t capacity, uint64_t *total);
+/* The fill pass alone in host memory, staged likewise: for the caller who has the offsets of gpuart_nearest_within_host(items = NULL) and
+ * now has room for offsets[n] items — the queries are walked twice in all, not three times. offsets must start at 0 and ascend, capacity
+ * must hold offsets[n] (GPUART_HIP_ERR_ARG otherwise, nothing written); offsets that are not these queries' count are reported as by
+ * gpuart_nearest_finish, and nothing is written outside items[0 .. offsets[n]). */
+int gpuart_nearest_within_fill_host(gpuart_nearest *h, const gpuart_hip_scene *scene, const float *points, size_t n, const float userSphere[4],
+                                    const uint32_t *offsets, gpuart_nearest_hit *items, size_t capacity);
+/* The definition itself, with no device and no pruning: the tree order is derived from recs (n_recs x 16 words) and root_ref by an
+ * unpruned walk, and every primitive is tested. Host memory; offsets, items, capacity and total as gpuart_nearest_within_host.
+ * GPUART_HIP_ERR_ARG for NULL pointers where the matching count is above zero, and for records that do not reach every primitive once. */
+int gpuart_nearest_within_brute_host(const float *recs, size_t n_recs, uint32_t root_ref, const float *prims, const float *prim_boxes, size_t n_prims,
+                                     const float *points, size_t n, const float userSphere[4], uint32_t *offsets, gpuart_nearest_hit *items,
+                                     size_t capacity, uint64_t *total);
+/* Lowers the cap on a total (0: GPUART_NEAREST_WITHIN_MAX_ITEMS, which also caps it): for callers with little memory, and for the tests. */
+int gpuart_nearest_within_set_max_items(gpuart_nearest *h, uint64_t max_items);
+/* Device time in ms of the last count, its scan and the last fill. */
+int gpuart_nearest_within_step_ms(gpuart_nearest *h, double ms[3]);
+/* gpuart_nearest_counts for the walks of the lists, both passes. */
+int gpuart_nearest_within_counts(gpuart_nearest *h, uint64_t out[2]);
 
 #ifdef __cplusplus
 }
