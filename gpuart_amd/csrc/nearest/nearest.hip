@@ -1,21 +1,17 @@
 // nearest.hip — libgpuart_nearest.so (gfx950): closest-point queries over an uploaded scene's tree, as include/gpuart_nearest.h states
 // them. Built without flushing fp32 denormals and without contraction: the rule (csrc/hip/nearest_rule.h) is restated in NumPy float32
 // (tests/nearest_ref.py) and every answer is compared bit for bit. DESIGN.md "Closest points" describes the kernel. The library reads
-// the scene's arrays and writes none of them. Behind k_nearest, which is held to the instructions it had, the neighbour lists of the same
-// header — every primitive within r, as CSR: k_within_count, rocPRIM's scan, k_within_fill — with the walk restated for them.
+// the scene's arrays and writes none of them. Behind k_nearest, the neighbour lists of the same header — every primitive within r, as CSR:
+// k_within_count, rocPRIM's scan, k_within_fill. The three kernels differ in what a candidate does, in how a record's children are ordered
+// and in what ends a query; a lane's state, its stack, the leaf walk, the user sphere, a query's prologue and the persistent-lane loop are
+// stated once ("the walk: what the three kernels share") and compile to the kernels the written-out copies gave (profiles/nearest_walk.txt).
 //
 // Compile-time switches (tools/nearest_time.py builds the variants; the shipped library sets none):
-//   NEAREST_PLAIN   k_nearest and k_within as one thread per query with a grid stride and no refill: the A/B partner of the persistent-lane form
+//   NEAREST_PLAIN   the three kernels as one thread per query with a grid stride and no refill: the A/B partner of the persistent-lane form
 //   NEAREST_COUNT   box steps and primitive tests counted per query and summed (gpuart_nearest_counts, gpuart_nearest_within_counts): a
 //                   counting build, not a timed one
 //   NEAREST_REFILL  idle lanes of a wave at which it takes new queries (default 16)
-//   NEAREST_TOTAL_REDUCE  the lists' total by rocPRIM's reduce over the lengths, between the count and the scan, instead of the count
-//                   kernel's one atomic per wave: the A/B partner of the total that ships (tools/within_time.py)
 #include <rocprim/device/device_scan.hpp>
-#ifdef NEAREST_TOTAL_REDUCE
-#include <rocprim/device/device_reduce.hpp>
-#include <rocprim/iterator/transform_iterator.hpp>
-#endif
 
 #include <vector>
 
@@ -115,51 +111,64 @@ __global__ void __launch_bounds__(256) k_nr_nesting(SceneView sc, Status *st) {
     if (why) refuse(&st->refused, r, why);
 }
 
-// ---- the walk -------------------------------------------------------------------------------------------------------------------------
-/// A lane's query and its walk.
-struct Lane {
+// ---- the walk: what the three kernels share ---------------------------------------------------------------------------------------------
+/// A lane's query and its walk, whatever the query asks for.
+struct Walk {
     uint32_t qi;           ///< the query, or NONE
     uint32_t node;         ///< the ref to visit next
     uint32_t sp, spilled;  ///< stack entries in all, and how many of them (the oldest) are in the global column
     float p[3], r2;
-    float best, q[3];      ///< the best so far: d2 (+inf: none) and the point
-    uint32_t ord, type;    ///< its ordinal (NO_PRIM: none) and type
 #ifdef NEAREST_COUNT
     uint32_t boxes, tests;
 #endif
 };
 
-/// The stack of a lane: the newest RING entries in a column of LDS (entry i at ring[(i % RING) * BLOCK + thread]: a wave's lanes are
-/// neighbours, no bank is shared), the older ones in the lane's column of `spill` (entry i at spill[i * lanes + lane]).
+/// The stack of a lane, of entries E (k_nearest: a ref and its box's distance; the lists: a ref): the newest RING entries in a column of LDS
+/// (entry i at ring[(i % RING) * BLOCK + thread]: a wave's lanes are neighbours, no bank is shared), the older ones in the lane's column
+/// of `columns` (entry i at spill[i * lanes + lane]).
+template <class E>
 struct Stack {
-    uint2 *ring;   ///< LDS, this thread's column
-    uint2 *spill;  ///< global, this lane's column
+    E *ring;       ///< LDS, this thread's column
+    E *spill;      ///< global, this lane's column
     size_t lanes;
     uint32_t cap;  ///< entries of the global column
     uint32_t *overflow;
+
+    __device__ __forceinline__ Stack(E *lds, E *columns, uint32_t cap_, Status *status)
+        : ring(lds + threadIdx.x), spill(columns + ((size_t)blockIdx.x * BLOCK + threadIdx.x)), lanes((size_t)gridDim.x * BLOCK), cap(cap_),
+          overflow(&status->overflow) {}
+
+    __device__ __forceinline__ void push(Walk &L, const E &e) const {
+        if (L.sp - L.spilled == RING) {
+            if (L.spilled >= cap) {  // (no tree the descriptor describes gets here: the entry is dropped and the run is reported void)
+                *overflow = 1u;
+                return;
+            }
+            spill[L.spilled * lanes] = ring[(L.spilled % RING) * BLOCK];
+            L.spilled++;
+        }
+        ring[(L.sp % RING) * BLOCK] = e;
+        L.sp++;
+    }
+
+    __device__ __forceinline__ E pop(Walk &L) const {
+        L.sp--;
+        if (L.sp >= L.spilled) return ring[(L.sp % RING) * BLOCK];
+        L.spilled = L.sp;
+        return spill[L.sp * lanes];
+    }
 };
 
-__device__ __forceinline__ void push(Lane &L, const Stack &st, uint32_t ref, float d2) {
-    if (L.sp - L.spilled == RING) {
-        if (L.spilled >= st.cap) {  // (no tree the descriptor describes gets here: the entry is dropped and the run is reported void)
-            *st.overflow = 1u;
-            return;
-        }
-        st.spill[L.spilled * st.lanes] = st.ring[(L.spilled % RING) * BLOCK];
-        L.spilled++;
-    }
-    st.ring[(L.sp % RING) * BLOCK] = make_uint2(ref, __float_as_uint(d2));
-    L.sp++;
-}
-
-__device__ __forceinline__ uint2 pop(Lane &L, const Stack &st) {
-    L.sp--;
-    if (L.sp >= L.spilled) return st.ring[(L.sp % RING) * BLOCK];
-    L.spilled = L.sp;
-    return st.spill[L.sp * st.lanes];
-}
-
 struct PrimData { float rec[12], box[6]; };
+
+/// The user sphere (centre x, y, z; radius r) as a primitive's record and box: the first candidate of a query, on the device and in the
+/// brute-force host functions.
+__host__ __device__ inline void user_sphere_prim(float x, float y, float z, float r, PrimData &d) {
+    for (int k = 0; k < 12; k++) d.rec[k] = 0.0f;
+    d.rec[0] = x; d.rec[1] = y; d.rec[2] = z; d.rec[4] = r;
+    d.box[0] = x - r; d.box[1] = y - r; d.box[2] = z - r;
+    d.box[3] = x + r; d.box[4] = y + r; d.box[5] = z + r;
+}
 
 __device__ __forceinline__ void load_prim(const SceneView &sc, uint32_t i, PrimData &d) {
     const float4 a = sc.prims[3u * i], b = sc.prims[3u * i + 1u], c = sc.prims[3u * i + 2u];
@@ -169,6 +178,121 @@ __device__ __forceinline__ void load_prim(const SceneView &sc, uint32_t i, PrimD
     d.rec[8] = c.x; d.rec[9] = c.y; d.rec[10] = c.z; d.rec[11] = c.w;
     for (int k = 0; k < 6; k++) d.box[k] = bx[k];
 }
+
+/// The leaf `ref`: candidate(type, record and box, ordinal) for each of its primitives. A flagged leaf holds one or two primitives (REF_TWO:
+/// both records and boxes are in flight at once); an unflagged one says its count in its first record's word and is walked primitive by
+/// primitive, the next one's loads ahead of this one's test.
+template <class Candidate>
+__device__ __forceinline__ void walk_leaf(const SceneView &sc, uint32_t ref, Candidate candidate) {
+    const uint32_t first = ref & REF_INDEX;
+    const bool flagged = (ref & (REF_TRIS | REF_SMALL)) != 0;
+    PrimData cur, nxt;
+    load_prim(sc, first, cur);
+    nxt = cur;
+    if (flagged && (ref & REF_TWO)) load_prim(sc, first + 1u, nxt);
+    const uint32_t count = flagged ? ((ref & REF_TWO) ? 2u : 1u) : __float_as_uint(cur.rec[3]) >> 2;
+    for (uint32_t k = 0; k < count; k++) {
+        if (!flagged && k + 1u < count) load_prim(sc, first + k + 1u, nxt);
+        candidate(__float_as_uint(cur.rec[3]) & 3u, cur, first + k);
+        cur = nxt;
+    }
+}
+
+/// Query i enters the lane: its point and radius, an empty stack, counters at zero. Returns the radius as the caller gave it.
+__device__ __forceinline__ float take_query(Walk &L, const float4 *points, uint32_t i) {
+    const float4 pt = points[i];
+    L.qi = i;
+    L.p[0] = pt.x; L.p[1] = pt.y; L.p[2] = pt.z;
+    L.r2 = pt.w * pt.w;
+    L.sp = L.spilled = 0;
+#ifdef NEAREST_COUNT
+    L.boxes = L.tests = 0;
+#endif
+    return pt.w;
+}
+
+#ifndef NEAREST_PLAIN
+__device__ __forceinline__ uint32_t wave_value(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ uint64_t least(uint64_t a, uint64_t b) { return a < b ? a : b; }
+#endif
+
+/// The queries of a launch (a.points, a.n) through the lanes of the grid. A kernel says what a query is by the type of its lane:
+/// begin(L, st, a, i) starts query i in lane L — or ends it at once —, step(L, st, a) takes its walk one record or one leaf further, and
+/// whichever of the two finds the walk at its end stores the answer and sets L.qi = NONE.
+/// Persistent lanes: a wave takes chunks of CHUNK queries — its first by its place in the grid, later ones from the cursor — and a lane
+/// whose walk has ended is idle; once NEAREST_REFILL lanes are idle (or all) the idle lanes take the next queries of the chunk. Queries
+/// differ in length by orders of magnitude: a point on the surface ends after one descent, a point far outside walks much of the tree.
+/// Returns the lane as its last query left it (the count's sum rides in it).
+/// The lane is a local of this function and begin and step are found by the lane's type, on purpose: with the caller's lane passed in by
+/// reference the compiler arranges the loop while the lane is still memory, and k_nearest came out at 104 VGPRs, 4 waves per SIMD where
+/// it has 5 (profiles/nearest_walk.txt lists the forms that were compiled and what each cost).
+template <class L_, class E, class A>
+__device__ __forceinline__ L_ walk_queries(const Stack<E> &st, const A &a) {
+    L_ L;
+    L.qi = NONE;
+#ifdef NEAREST_PLAIN
+    for (size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x; i < a.n; i += st.lanes) {
+        begin(L, st, a, (uint32_t)i);
+        while (L.qi != NONE) step(L, st, a);
+    }
+#else
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = wave_value(blockIdx.x * WAVES + threadIdx.x / 64u), waves = gridDim.x * WAVES;
+    // the cursor (wave-uniform): [next, end) is what is left of the wave's chunk; chunks behind the static ones come from the counter
+    const uint64_t static_end = (uint64_t)waves * CHUNK;
+    uint32_t next = (uint32_t)least((uint64_t)wave * CHUNK, a.n), end = (uint32_t)least(((uint64_t)wave + 1) * CHUNK, a.n);
+    bool dry = false;
+    for (;;) {
+        unsigned long long idle = __ballot(L.qi == NONE);
+        if (idle && !dry && ((uint32_t)__popcll(idle) >= NEAREST_REFILL || idle == ~0ull)) {
+            while (idle && !dry) {
+                if (next == end) {
+                    uint32_t got = 0;
+                    if (static_end < a.n) {
+                        if (lane == 0) got = atomicAdd(a.cursor, CHUNK);
+                        got = wave_value(got);
+                    }
+                    const uint64_t base = static_end + got;
+                    if (static_end >= a.n || base >= a.n) { dry = true; break; }
+                    next = (uint32_t)base;
+                    end = (uint32_t)least(base + CHUNK, a.n);
+                }
+                const uint32_t want = (uint32_t)__popcll(idle), got = min(want, end - next);
+                const uint32_t rank = (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
+                if (L.qi == NONE && rank < got) begin(L, st, a, next + rank);
+                next += got;
+                idle = __ballot(L.qi == NONE);  // (a query that was answered at once has left its lane idle)
+            }
+            idle = __ballot(L.qi == NONE);
+        }
+        if (idle == ~0ull) {
+            if (dry) break;
+            continue;
+        }
+        if (L.qi != NONE) step(L, st, a);
+    }
+#endif
+    return L;
+}
+
+// ---- closest points: k_nearest ----------------------------------------------------------------------------------------------------------
+struct Launch {
+    SceneView sc;
+    const float4 *points;
+    uint32_t n;
+    float4 us;
+    uint32_t use_us;
+    gpuart_nearest_hit *hits;
+    uint2 *spill;
+    uint32_t cap;
+    uint32_t *cursor;
+    Status *status;
+};
+
+struct Lane : Walk {
+    float best, q[3];    ///< the best so far: d2 (+inf: none) and the point
+    uint32_t ord, type;  ///< its ordinal (NO_PRIM: none) and type
+};
 
 /// One candidate: primitive `ord` of `type` with record and box `d`.
 __device__ __forceinline__ void candidate(Lane &L, uint32_t type, const PrimData &d, uint32_t ord) {
@@ -195,187 +319,78 @@ __device__ __forceinline__ void store_hit(gpuart_nearest_hit *hits, uint32_t i, 
 }
 
 /// The query is answered: its record is stored and the lane is idle.
-__device__ __forceinline__ void finish(Lane &L, gpuart_nearest_hit *hits, Status *status) {
-    store_hit(hits, L.qi, L);
+__device__ __forceinline__ void finish(Lane &L, const Launch &a) {
+    store_hit(a.hits, L.qi, L);
 #ifdef NEAREST_COUNT
-    atomicAdd(&status->box_steps, (unsigned long long)L.boxes);
-    atomicAdd(&status->prim_tests, (unsigned long long)L.tests);
+    atomicAdd(&a.status->box_steps, (unsigned long long)L.boxes);
+    atomicAdd(&a.status->prim_tests, (unsigned long long)L.tests);
 #endif
     L.qi = NONE;
 }
 
 /// The next node off the stack that is not pruned by now, or the end of the walk.
-__device__ __forceinline__ void next_node(Lane &L, const Stack &st, gpuart_nearest_hit *hits, Status *status) {
+__device__ __forceinline__ void next_node(Lane &L, const Stack<uint2> &st, const Launch &a) {
     for (;;) {
-        if (L.sp == 0) { finish(L, hits, status); return; }
-        const uint2 e = pop(L, st);
+        if (L.sp == 0) { finish(L, a); return; }
+        const uint2 e = st.pop(L);
         if (!nr::pruned(__uint_as_float(e.y), L.r2, L.best)) { L.node = e.x; return; }
     }
 }
 
 /// Query i begins: a miss at once, or the user sphere as the first candidate and the root.
-__device__ __forceinline__ void begin(Lane &L, const SceneView &sc, const Stack &st, const float4 *points, uint32_t i, const float4 us, bool use_us,
-                                      gpuart_nearest_hit *hits, Status *status) {
-    const float4 pt = points[i];
-    L.qi = i;
-    L.p[0] = pt.x; L.p[1] = pt.y; L.p[2] = pt.z;
-    L.r2 = pt.w * pt.w;
+__device__ __forceinline__ void begin(Lane &L, const Stack<uint2> &, const Launch &a, uint32_t i) {
+    const float r = take_query(L, a.points, i);
     L.best = __builtin_inff(); L.ord = nr::NO_PRIM; L.type = 0;
     L.q[0] = L.q[1] = L.q[2] = 0.0f;
-    L.sp = L.spilled = 0;
-#ifdef NEAREST_COUNT
-    L.boxes = L.tests = 0;
-#endif
-    if (!nr::query_ok(L.p, pt.w)) { finish(L, hits, status); return; }
-    if (use_us) {
+    if (!nr::query_ok(L.p, r)) { finish(L, a); return; }
+    if (a.use_us) {
         PrimData d;
-        for (int k = 0; k < 12; k++) d.rec[k] = 0.0f;
-        d.rec[0] = us.x; d.rec[1] = us.y; d.rec[2] = us.z; d.rec[4] = us.w;
-        d.box[0] = us.x - us.w; d.box[1] = us.y - us.w; d.box[2] = us.z - us.w;
-        d.box[3] = us.x + us.w; d.box[4] = us.y + us.w; d.box[5] = us.z + us.w;
+        user_sphere_prim(a.us.x, a.us.y, a.us.z, a.us.w, d);
         candidate(L, nr::SPHERE, d, nr::USER_SPHERE);
     }
-    if (nr::pruned(nr::box_d2(sc.root_lo, sc.root_hi, L.p), L.r2, L.best)) { finish(L, hits, status); return; }
-    L.node = sc.root_ref;
+    if (nr::pruned(nr::box_d2(a.sc.root_lo, a.sc.root_hi, L.p), L.r2, L.best)) { finish(L, a); return; }
+    L.node = a.sc.root_ref;
 }
 
 /// One step of a lane's walk: a record (both boxes, the nearer child entered, the farther stacked with its distance) or a leaf.
-__device__ __forceinline__ void step(Lane &L, const SceneView &sc, const Stack &st, gpuart_nearest_hit *hits, Status *status) {
+__device__ __forceinline__ void step(Lane &L, const Stack<uint2> &st, const Launch &a) {
     const uint32_t ref = L.node;
     if (!(ref & REF_LEAF)) {
-        const float4 *rec = sc.recs + 4u * ref;  // (base + 32-bit offset: 4 * n_recs <= 2^30)
-        const float4 a = rec[0], b = rec[1], c = rec[2], d = rec[3];
+        const float4 *rec = a.sc.recs + 4u * ref;  // (base + 32-bit offset: 4 * n_recs <= 2^30)
+        const float4 ra = rec[0], rb = rec[1], rc = rec[2], rd = rec[3];
         float l0[3], h0[3], l1[3], h1[3];
-        xyz(a, l0); xyz(b, h0); xyz(c, l1); xyz(d, h1);
+        xyz(ra, l0); xyz(rb, h0); xyz(rc, l1); xyz(rd, h1);
         const float dlo = nr::box_d2(l0, h0, L.p), dhi = nr::box_d2(l1, h1, L.p);
-        const uint32_t rlo = __float_as_uint(a.w), rhi = __float_as_uint(b.w);
+        const uint32_t rlo = __float_as_uint(ra.w), rhi = __float_as_uint(rb.w);
         const bool klo = !nr::pruned(dlo, L.r2, L.best), khi = !nr::pruned(dhi, L.r2, L.best);
 #ifdef NEAREST_COUNT
         L.boxes++;
 #endif
         if (klo && khi) {
             const bool upper_first = dhi < dlo;
-            push(L, st, upper_first ? rlo : rhi, upper_first ? dlo : dhi);
+            st.push(L, make_uint2(upper_first ? rlo : rhi, __float_as_uint(upper_first ? dlo : dhi)));
             L.node = upper_first ? rhi : rlo;
         } else if (klo) L.node = rlo;
         else if (khi) L.node = rhi;
-        else next_node(L, st, hits, status);
+        else next_node(L, st, a);
         return;
     }
-    // a leaf: a flagged one holds one or two primitives (REF_TWO: both records and boxes are in flight at once); an unflagged one says
-    // its count in its first record's word and is walked primitive by primitive, the next one's loads ahead of this one's test
-    const uint32_t first = ref & REF_INDEX;
-    const bool flagged = (ref & (REF_TRIS | REF_SMALL)) != 0;
-    PrimData cur, nxt;
-    load_prim(sc, first, cur);
-    nxt = cur;
-    if (flagged && (ref & REF_TWO)) load_prim(sc, first + 1u, nxt);
-    const uint32_t count = flagged ? ((ref & REF_TWO) ? 2u : 1u) : __float_as_uint(cur.rec[3]) >> 2;
-    for (uint32_t k = 0; k < count; k++) {
-        if (!flagged && k + 1u < count) load_prim(sc, first + k + 1u, nxt);
-        candidate(L, __float_as_uint(cur.rec[3]) & 3u, cur, first + k);
-        cur = nxt;
-    }
-    next_node(L, st, hits, status);
+    walk_leaf(a.sc, ref, [&](uint32_t type, const PrimData &d, uint32_t ord) { candidate(L, type, d, ord); });
+    next_node(L, st, a);
 }
 
-struct Launch {
-    SceneView sc;
-    const float4 *points;
-    uint32_t n;
-    float4 us;
-    uint32_t use_us;
-    gpuart_nearest_hit *hits;
-    uint2 *spill;
-    uint32_t cap;
-    uint32_t *cursor;
-    Status *status;
-};
-
-#ifndef NEAREST_PLAIN
-__device__ __forceinline__ uint32_t wave_value(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ uint64_t least(uint64_t a, uint64_t b) { return a < b ? a : b; }
-#endif
-
-// k_nearest. Persistent lanes: a wave takes chunks of CHUNK queries — its first by its place in the grid, later ones from the cursor — and
-// a lane whose walk has ended stores its record and is idle; once NEAREST_REFILL lanes are idle (or all) the idle lanes take the next
-// queries of the chunk. Queries differ in length by orders of magnitude: a point on the surface ends after one descent, a point far
-// outside walks much of the tree. Types are branched on at run time (closest_on_prim): the descriptor does not carry the type mask, and
-// one launch per mask would need a reduction over the records in bind for a gain that only the leaf step could show (a probe with the
-// leaf's type fixed to "triangle" compiled to the same 96 VGPRs and occupancy: DESIGN.md).
+// k_nearest. Types are branched on at run time (closest_on_prim): the descriptor does not carry the type mask, and one launch per mask would
+// need a reduction over the records in bind for a gain that only the leaf step could show (a probe with the leaf's type fixed to
+// "triangle" compiled to the same 96 VGPRs and occupancy: DESIGN.md).
 __global__ void __launch_bounds__(BLOCK) k_nearest(Launch a) {
     __shared__ uint2 ring[RING * BLOCK];
-    const size_t lanes = (size_t)gridDim.x * BLOCK;
-    const Stack st{ring + threadIdx.x, a.spill + ((size_t)blockIdx.x * BLOCK + threadIdx.x), lanes, a.cap, &a.status->overflow};
-    Lane L;
-    L.qi = NONE;
-#ifdef NEAREST_PLAIN
-    for (size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x; i < a.n; i += lanes) {
-        begin(L, a.sc, st, a.points, (uint32_t)i, a.us, a.use_us != 0, a.hits, a.status);
-        while (L.qi != NONE) step(L, a.sc, st, a.hits, a.status);
-    }
-#else
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = wave_value(blockIdx.x * WAVES + threadIdx.x / 64u), waves = gridDim.x * WAVES;
-    // the cursor (wave-uniform): [next, end) is what is left of the wave's chunk; chunks behind the static ones come from the counter
-    const uint64_t static_end = (uint64_t)waves * CHUNK;
-    uint32_t next = (uint32_t)least((uint64_t)wave * CHUNK, a.n), end = (uint32_t)least(((uint64_t)wave + 1) * CHUNK, a.n);
-    bool dry = false;
-    for (;;) {
-        unsigned long long idle = __ballot(L.qi == NONE);
-        if (idle && !dry && ((uint32_t)__popcll(idle) >= NEAREST_REFILL || idle == ~0ull)) {
-            while (idle && !dry) {
-                if (next == end) {
-                    uint32_t got = 0;
-                    if (static_end < a.n) {
-                        if (lane == 0) got = atomicAdd(a.cursor, CHUNK);
-                        got = wave_value(got);
-                    }
-                    const uint64_t base = static_end + got;
-                    if (static_end >= a.n || base >= a.n) { dry = true; break; }
-                    next = (uint32_t)base;
-                    end = (uint32_t)least(base + CHUNK, a.n);
-                }
-                const uint32_t want = (uint32_t)__popcll(idle), got = min(want, end - next);
-                const uint32_t rank = (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
-                if (L.qi == NONE && rank < got) begin(L, a.sc, st, a.points, next + rank, a.us, a.use_us != 0, a.hits, a.status);
-                next += got;
-                idle = __ballot(L.qi == NONE);  // (a query that was a miss at once has left its lane idle)
-            }
-            idle = __ballot(L.qi == NONE);
-        }
-        if (idle == ~0ull) {
-            if (dry) break;
-            continue;
-        }
-        if (L.qi != NONE) step(L, a.sc, st, a.hits, a.status);
-    }
-#endif
+    const Stack<uint2> st(ring, a.spill, a.cap, a.status);
+    walk_queries<Lane>(st, a);
 }
 
-// ---- the neighbour lists --------------------------------------------------------------------------------------------------------------
-// k_within<FILL>: the walk of k_nearest without a best so far. The lane, its stack and the persistent-lane loop are RESTATED here and not
-// shared with k_nearest through a template or a header: that kernel's instructions are held to what they were (profiles/within.txt), and
-// DESIGN.md "Neighbour lists" names the three as a candidate for a later "state once" change.
-struct WLane {
-    uint32_t qi;           ///< the query, or NONE
-    uint32_t node;         ///< the ref to visit next
-    uint32_t sp, spilled;  ///< stack entries in all, and how many of them (the oldest) are in the global column
-    float p[3], r2;
-    uint32_t at, end;      ///< count: the items so far, unused; fill: where the next item goes, and where the list ends
-#ifdef NEAREST_COUNT
-    uint32_t boxes, tests;
-#endif
-};
-
-/// The stack of a lane as Stack above, its entries the ref alone: ring[(i % RING) * BLOCK + thread], spill[i * lanes + lane].
-struct WStack {
-    uint32_t *ring, *spill;
-    size_t lanes;
-    uint32_t cap;
-    uint32_t *overflow;
-};
-
+// ---- the neighbour lists: k_within_count and k_within_fill ------------------------------------------------------------------------------
+// The walk of k_nearest without a best so far: nothing that is found prunes anything, so a stack entry is the ref alone, a record's children
+// are entered lower first — the contract's order of a list — and what comes off the stack is not tested again.
 struct WLaunch {
     SceneView sc;
     const float4 *points;
@@ -391,30 +406,16 @@ struct WLaunch {
     Status *status;
 };
 
-__device__ __forceinline__ void wpush(WLane &L, const WStack &st, uint32_t ref) {
-    if (L.sp - L.spilled == RING) {
-        if (L.spilled >= st.cap) {  // (as push above: the entry is dropped and the run is reported void)
-            *st.overflow = 1u;
-            return;
-        }
-        st.spill[L.spilled * st.lanes] = st.ring[(L.spilled % RING) * BLOCK];
-        L.spilled++;
-    }
-    st.ring[(L.sp % RING) * BLOCK] = ref;
-    L.sp++;
-}
-
-__device__ __forceinline__ uint32_t wpop(WLane &L, const WStack &st) {
-    L.sp--;
-    if (L.sp >= L.spilled) return st.ring[(L.sp % RING) * BLOCK];
-    L.spilled = L.sp;
-    return st.spill[L.sp * st.lanes];
-}
+template <bool FILL>
+struct WLane : Walk {
+    uint32_t at, end;        ///< count: the items so far, unused; fill: where the next item goes, and where the list ends
+    unsigned long long sum = 0;  ///< count: the items of all lists this lane has finished
+};
 
 /// One candidate: an item of the list if it is accepted. The fill stores it where the offsets put it, and nowhere else: an index at or
 /// beyond the list's end or the capacity is not written and marks the run.
 template <bool FILL>
-__device__ __forceinline__ void wcandidate(WLane &L, const WLaunch &a, uint32_t type, const PrimData &d, uint32_t ord) {
+__device__ __forceinline__ void candidate(WLane<FILL> &L, const WLaunch &a, uint32_t type, const PrimData &d, uint32_t ord) {
     float q[3];
     const float d2 = nr::closest_on_prim(type, d.rec, d.box, L.p, q);
     if (nr::within_accept(d2, L.r2)) {
@@ -436,12 +437,12 @@ __device__ __forceinline__ void wcandidate(WLane &L, const WLaunch &a, uint32_t 
 
 /// The walk has ended: the count stores the list's length, the fill holds the list to its offsets; the lane is idle.
 template <bool FILL>
-__device__ __forceinline__ void wfinish(WLane &L, const WLaunch &a, unsigned long long &sum) {
+__device__ __forceinline__ void finish(WLane<FILL> &L, const WLaunch &a) {
     if (FILL) {
         if (L.at != L.end) a.status->mismatch = 1u;
     } else {
         a.offsets[L.qi] = L.at;
-        sum += L.at;
+        L.sum += L.at;
     }
 #ifdef NEAREST_COUNT
     atomicAdd(&a.status->w_box_steps, (unsigned long long)L.boxes);
@@ -451,40 +452,30 @@ __device__ __forceinline__ void wfinish(WLane &L, const WLaunch &a, unsigned lon
 }
 
 template <bool FILL>
-__device__ __forceinline__ void wnext(WLane &L, const WStack &st, const WLaunch &a, unsigned long long &sum) {
-    if (L.sp == 0) { wfinish<FILL>(L, a, sum); return; }
-    L.node = wpop(L, st);  // (what was stacked was not pruned, and nothing has changed since: there is no best so far)
+__device__ __forceinline__ void next_node(WLane<FILL> &L, const Stack<uint32_t> &st, const WLaunch &a) {
+    if (L.sp == 0) { finish(L, a); return; }
+    L.node = st.pop(L);  // (what was stacked was not pruned, and nothing has changed since: there is no best so far)
 }
 
 /// Query i begins: an empty list at once, or the user sphere as the first candidate and the root.
 template <bool FILL>
-__device__ __forceinline__ void wbegin(WLane &L, const WLaunch &a, uint32_t i, unsigned long long &sum) {
-    const float4 pt = a.points[i];
-    L.qi = i;
-    L.p[0] = pt.x; L.p[1] = pt.y; L.p[2] = pt.z;
-    L.r2 = pt.w * pt.w;
-    L.sp = L.spilled = 0;
+__device__ __forceinline__ void begin(WLane<FILL> &L, const Stack<uint32_t> &, const WLaunch &a, uint32_t i) {
+    const float r = take_query(L, a.points, i);
     L.at = L.end = 0;
     if (FILL) { L.at = a.offsets[i]; L.end = a.offsets[i + 1u]; }
-#ifdef NEAREST_COUNT
-    L.boxes = L.tests = 0;
-#endif
-    if (!nr::query_ok(L.p, pt.w)) { wfinish<FILL>(L, a, sum); return; }
+    if (!nr::query_ok(L.p, r)) { finish(L, a); return; }
     if (a.use_us) {
         PrimData d;
-        for (int k = 0; k < 12; k++) d.rec[k] = 0.0f;
-        d.rec[0] = a.us.x; d.rec[1] = a.us.y; d.rec[2] = a.us.z; d.rec[4] = a.us.w;
-        d.box[0] = a.us.x - a.us.w; d.box[1] = a.us.y - a.us.w; d.box[2] = a.us.z - a.us.w;
-        d.box[3] = a.us.x + a.us.w; d.box[4] = a.us.y + a.us.w; d.box[5] = a.us.z + a.us.w;
-        wcandidate<FILL>(L, a, nr::SPHERE, d, nr::USER_SPHERE);
+        user_sphere_prim(a.us.x, a.us.y, a.us.z, a.us.w, d);
+        candidate(L, a, nr::SPHERE, d, nr::USER_SPHERE);
     }
-    if (nr::within_pruned(nr::box_d2(a.sc.root_lo, a.sc.root_hi, L.p), L.r2)) { wfinish<FILL>(L, a, sum); return; }
+    if (nr::within_pruned(nr::box_d2(a.sc.root_lo, a.sc.root_hi, L.p), L.r2)) { finish(L, a); return; }
     L.node = a.sc.root_ref;
 }
 
-/// One step of a lane's walk: a record (both boxes; the lower child entered, the upper stacked, each unless pruned) or a leaf (as step).
+/// One step of a lane's walk: a record (both boxes; the lower child entered, the upper stacked, each unless pruned) or a leaf.
 template <bool FILL>
-__device__ __forceinline__ void wstep(WLane &L, const WStack &st, const WLaunch &a, unsigned long long &sum) {
+__device__ __forceinline__ void step(WLane<FILL> &L, const Stack<uint32_t> &st, const WLaunch &a) {
     const uint32_t ref = L.node;
     if (!(ref & REF_LEAF)) {
         const float4 *rec = a.sc.recs + 4u * ref;
@@ -497,85 +488,29 @@ __device__ __forceinline__ void wstep(WLane &L, const WStack &st, const WLaunch 
         L.boxes++;
 #endif
         if (klo && khi) {
-            wpush(L, st, rhi);
+            st.push(L, rhi);
             L.node = rlo;
         } else if (klo) L.node = rlo;
         else if (khi) L.node = rhi;
-        else wnext<FILL>(L, st, a, sum);
+        else next_node(L, st, a);
         return;
     }
-    const uint32_t first = ref & REF_INDEX;
-    const bool flagged = (ref & (REF_TRIS | REF_SMALL)) != 0;
-    PrimData cur, nxt;
-    load_prim(a.sc, first, cur);
-    nxt = cur;
-    if (flagged && (ref & REF_TWO)) load_prim(a.sc, first + 1u, nxt);
-    const uint32_t count = flagged ? ((ref & REF_TWO) ? 2u : 1u) : __float_as_uint(cur.rec[3]) >> 2;
-    for (uint32_t k = 0; k < count; k++) {
-        if (!flagged && k + 1u < count) load_prim(a.sc, first + k + 1u, nxt);
-        wcandidate<FILL>(L, a, __float_as_uint(cur.rec[3]) & 3u, cur, first + k);
-        cur = nxt;
-    }
-    wnext<FILL>(L, st, a, sum);
+    walk_leaf(a.sc, ref, [&](uint32_t type, const PrimData &d, uint32_t ord) { candidate(L, a, type, d, ord); });
+    next_node(L, st, a);
 }
 
-// k_within_count (FILL = false) and k_within_fill (FILL = true): the persistent-lane loop of k_nearest. The count leaves each list's length
-// at offsets[qi] and adds the lengths of a wave's queries, summed in 64 bits lane by lane and then across the wave, to the status' total
-// with one atomic per wave at the end of its life. The fill writes list qi from offsets[qi] on, in the order of the walk.
+// k_within_count (FILL = false) and k_within_fill (FILL = true). The count leaves each list's length at offsets[qi] and adds the lengths of
+// a wave's queries, summed in 64 bits lane by lane and then across the wave, to the status' total with one atomic per wave at the end of
+// its life. The fill writes list qi from offsets[qi] on, in the order of the walk.
 template <bool FILL>
 __device__ __forceinline__ void within_body(const WLaunch &a, uint32_t *ring) {
-    const size_t lanes = (size_t)gridDim.x * BLOCK;
-    const WStack st{ring + threadIdx.x, a.spill + ((size_t)blockIdx.x * BLOCK + threadIdx.x), lanes, a.cap, &a.status->overflow};
-    WLane L;
-    L.qi = NONE;
-    unsigned long long sum = 0;
-#ifdef NEAREST_PLAIN
-    for (size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x; i < a.n; i += lanes) {
-        wbegin<FILL>(L, a, (uint32_t)i, sum);
-        while (L.qi != NONE) wstep<FILL>(L, st, a, sum);
-    }
-#else
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = wave_value(blockIdx.x * WAVES + threadIdx.x / 64u), waves = gridDim.x * WAVES;
-    const uint64_t static_end = (uint64_t)waves * CHUNK;
-    uint32_t next = (uint32_t)least((uint64_t)wave * CHUNK, a.n), end = (uint32_t)least(((uint64_t)wave + 1) * CHUNK, a.n);
-    bool dry = false;
-    for (;;) {
-        unsigned long long idle = __ballot(L.qi == NONE);
-        if (idle && !dry && ((uint32_t)__popcll(idle) >= NEAREST_REFILL || idle == ~0ull)) {
-            while (idle && !dry) {
-                if (next == end) {
-                    uint32_t got = 0;
-                    if (static_end < a.n) {
-                        if (lane == 0) got = atomicAdd(a.cursor, CHUNK);
-                        got = wave_value(got);
-                    }
-                    const uint64_t base = static_end + got;
-                    if (static_end >= a.n || base >= a.n) { dry = true; break; }
-                    next = (uint32_t)base;
-                    end = (uint32_t)least(base + CHUNK, a.n);
-                }
-                const uint32_t want = (uint32_t)__popcll(idle), got = min(want, end - next);
-                const uint32_t rank = (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
-                if (L.qi == NONE && rank < got) wbegin<FILL>(L, a, next + rank, sum);
-                next += got;
-                idle = __ballot(L.qi == NONE);  // (a query whose list is empty at once has left its lane idle)
-            }
-            idle = __ballot(L.qi == NONE);
-        }
-        if (idle == ~0ull) {
-            if (dry) break;
-            continue;
-        }
-        if (L.qi != NONE) wstep<FILL>(L, st, a, sum);
-    }
-#endif
-#ifndef NEAREST_TOTAL_REDUCE
+    const Stack<uint32_t> st(ring, a.spill, a.cap, a.status);
+    const WLane<FILL> L = walk_queries<WLane<FILL>>(st, a);
     if (!FILL) {
+        unsigned long long sum = L.sum;
         for (int d = 32; d > 0; d >>= 1) sum += __shfl_down(sum, d, 64);
         if ((threadIdx.x & 63u) == 0 && sum) atomicAdd(&a.status->total, sum);
     }
-#endif
 }
 
 __global__ void __launch_bounds__(BLOCK) k_within_count(WLaunch a) {
@@ -650,25 +585,63 @@ int check_bound(const gpuart_nearest *h, const gpuart_hip_scene *s) {
     return 0;
 }
 
-/// One launch over n queries in device memory.
-int launch(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, uint32_t n, const float us[4], gpuart_nearest_hit *hits) {
-    const size_t levels = (size_t)s->max_depth + 2;
-    const size_t by_budget = std::max<size_t>(1, h->spill_budget / (levels * sizeof(uint2) * BLOCK));
+/// What every run checks before its own arrays: the handle, its binding, the query count and the user sphere.
+int check_queries(gpuart_nearest *h, const gpuart_hip_scene *s, size_t n, const float us[4]) {
+    if (int rc = check_handle(LIB, h)) return rc;
+    if (int rc = check_bound(h, s)) return rc;
+    if (n > GPUART_HIP_MAX_RAYS) return fail(GPUART_HIP_ERR_ARG, "nearest: too many queries: " + std::to_string(n));
+    return check_user_sphere(us);
+}
+
+int check_run(gpuart_nearest *h, const gpuart_hip_scene *s, const void *points, size_t n, const float us[4], const void *hits, size_t align) {
+    if (int rc = check_queries(h, s, n, us)) return rc;
+    if (n && (!points || !hits)) return fail(GPUART_HIP_ERR_ARG, "nearest: points or hits is NULL");
+    if (misaligned({points, hits}, align)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned pointer (points and hits need " + std::to_string(align) + " bytes)");
+    if (n && overlaps(points, n * 16, hits, n * 32)) return fail(GPUART_HIP_ERR_ARG, "nearest: hits overlaps points");
+    return 0;
+}
+
+int check_within(gpuart_nearest *h, const gpuart_hip_scene *s, const void *points, size_t n, const float us[4], const void *offsets, size_t align) {
+    if (int rc = check_queries(h, s, n, us)) return rc;
+    if (n && (!points || !offsets)) return fail(GPUART_HIP_ERR_ARG, "nearest: points or offsets is NULL");
+    if (misaligned({points}, align) || misaligned({offsets}, 4)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned pointer (points needs " + std::to_string(align) + " bytes, offsets 4)");
+    if (n && overlaps(points, n * 16, offsets, (n + 1) * 4)) return fail(GPUART_HIP_ERR_ARG, "nearest: offsets overlaps points");
+    return 0;
+}
+
+int too_many(uint64_t total, uint64_t cap) {
+    return fail(GPUART_HIP_ERR_ARG, "nearest: the lists hold " + std::to_string(total) + " items, more than the " + std::to_string(cap) + " a result may hold");
+}
+
+/// What every launch over n queries in device memory begins with: the grid — the blocks the spill budget pays for (a column entry is what
+/// the kernel's stack holds: the lists' 4 bytes are half of k_nearest's), the blocks the work fills, and `most` —, the lanes' stack columns,
+/// the arguments every kernel has, and the cursor at zero.
+template <class A>
+int prepare(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, uint32_t n, const float us[4], uint32_t most, A &a, uint32_t &grid) {
+    const size_t levels = (size_t)s->max_depth + 2, block_bytes = levels * sizeof(*a.spill) * BLOCK;
+    const size_t by_budget = std::max<size_t>(1, h->spill_budget / block_bytes);
     const size_t by_work = ((size_t)n + (size_t)CHUNK * WAVES - 1) / ((size_t)CHUNK * WAVES);
-    const uint32_t grid = (uint32_t)std::min({by_budget, by_work, (size_t)h->max_blocks});
-    if (int rc = ensure(h->stream, h->spill, levels * sizeof(uint2) * BLOCK * grid)) return rc;
-    Launch a;
+    grid = (uint32_t)std::min({by_budget, by_work, (size_t)most});
+    if (int rc = ensure(h->stream, h->spill, block_bytes * grid)) return rc;
     a.sc = view_of(s);
     a.points = (const float4 *)points;
     a.n = n;
     a.us = us ? make_float4(us[0], us[1], us[2], us[3]) : make_float4(0, 0, 0, 0);
     a.use_us = us ? 1u : 0u;
-    a.hits = hits;
-    a.spill = (uint2 *)h->spill.mem;
+    a.spill = (decltype(a.spill))h->spill.mem;
     a.cap = (uint32_t)levels;
     a.cursor = h->cursor;
     a.status = h->status;
     HIP_TRY(hipMemsetAsync(h->cursor, 0, sizeof(uint32_t), h->stream));
+    return 0;
+}
+
+/// One launch of k_nearest.
+int launch(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, uint32_t n, const float us[4], gpuart_nearest_hit *hits) {
+    Launch a{};
+    uint32_t grid;
+    if (int rc = prepare(h, s, points, n, us, h->max_blocks, a, grid)) return rc;
+    a.hits = hits;
     h->walk.start(h->stream);
     HIP_TRY(h->walk.mark());
     k_nearest<<<grid, BLOCK, 0, h->stream>>>(a);
@@ -680,99 +653,21 @@ int launch(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, ui
     return 0;
 }
 
-/// What a finished stream may have left: a walk that met a full stack column.
-int read_overflow(gpuart_nearest *h) {
-    uint32_t over = 0;
-    HIP_TRY(hipMemcpyAsync(&over, &h->status->overflow, 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (over) {
-        HIP_TRY(hipMemsetAsync(&h->status->overflow, 0, 4, h->stream));
-        return fail(GPUART_HIP_ERR_ARG, "nearest: a walk met a full stack: the tree is deeper than the descriptor's max_depth says; the results are void");
-    }
-    return 0;
-}
-
-int check_run(gpuart_nearest *h, const gpuart_hip_scene *s, const void *points, size_t n, const float us[4], const void *hits, size_t align) {
-    if (int rc = check_handle(LIB, h)) return rc;
-    if (int rc = check_bound(h, s)) return rc;
-    if (n > GPUART_HIP_MAX_RAYS) return fail(GPUART_HIP_ERR_ARG, "nearest: too many queries: " + std::to_string(n));
-    if (int rc = check_user_sphere(us)) return rc;
-    if (n && (!points || !hits)) return fail(GPUART_HIP_ERR_ARG, "nearest: points or hits is NULL");
-    if (misaligned({points, hits}, align)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned pointer (points and hits need " + std::to_string(align) + " bytes)");
-    if (n && overlaps(points, n * 16, hits, n * 32)) return fail(GPUART_HIP_ERR_ARG, "nearest: hits overlaps points");
-    return 0;
-}
-
-// ---- the neighbour lists: the host's part -----------------------------------------------------------------------------------------------
-int check_within(gpuart_nearest *h, const gpuart_hip_scene *s, const void *points, size_t n, const float us[4], const void *offsets, size_t align) {
-    if (int rc = check_handle(LIB, h)) return rc;
-    if (int rc = check_bound(h, s)) return rc;
-    if (n > GPUART_HIP_MAX_RAYS) return fail(GPUART_HIP_ERR_ARG, "nearest: too many queries: " + std::to_string(n));
-    if (int rc = check_user_sphere(us)) return rc;
-    if (n && (!points || !offsets)) return fail(GPUART_HIP_ERR_ARG, "nearest: points or offsets is NULL");
-    if (misaligned({points}, align) || misaligned({offsets}, 4)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned pointer (points needs " + std::to_string(align) + " bytes, offsets 4)");
-    if (n && overlaps(points, n * 16, offsets, (n + 1) * 4)) return fail(GPUART_HIP_ERR_ARG, "nearest: offsets overlaps points");
-    return 0;
-}
-
-int too_many(uint64_t total, uint64_t cap) {
-    return fail(GPUART_HIP_ERR_ARG, "nearest: the lists hold " + std::to_string(total) + " items, more than the " + std::to_string(cap) + " a result may hold");
-}
-
-/// The grid, the spill columns and the launch's arguments but the lists' own.
-int within_args(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, uint32_t n, const float us[4], int pass, WLaunch &a, uint32_t &grid) {
-    const size_t levels = (size_t)s->max_depth + 2;
-    const size_t by_budget = std::max<size_t>(1, h->spill_budget / (levels * sizeof(uint32_t) * BLOCK));  // (entries of 4 bytes: half of k_nearest's columns)
-    const size_t by_work = ((size_t)n + (size_t)CHUNK * WAVES - 1) / ((size_t)CHUNK * WAVES);
-    grid = (uint32_t)std::min({by_budget, by_work, (size_t)h->max_blocks, (size_t)h->within_blocks[pass]});
-    if (int rc = ensure(h->stream, h->spill, levels * sizeof(uint32_t) * BLOCK * grid)) return rc;
-    a.sc = view_of(s);
-    a.points = (const float4 *)points;
-    a.n = n;
-    a.us = us ? make_float4(us[0], us[1], us[2], us[3]) : make_float4(0, 0, 0, 0);
-    a.use_us = us ? 1u : 0u;
-    a.offsets = nullptr;
-    a.items = nullptr;
-    a.capacity = 0;
-    a.spill = (uint32_t *)h->spill.mem;
-    a.cap = (uint32_t)levels;
-    a.cursor = h->cursor;
-    a.status = h->status;
-    return 0;
-}
-
-#ifdef NEAREST_TOTAL_REDUCE
-struct Widen {
-    __host__ __device__ unsigned long long operator()(uint32_t v) const { return v; }
-};
-#endif
-
 /// The count of n queries in device memory into offsets[0 .. n], scanned in place; the total stays in the status.
 int launch_count(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, uint32_t n, const float us[4], uint32_t *offsets) {
-    WLaunch a;
+    WLaunch a{};
     uint32_t grid;
-    if (int rc = within_args(h, s, points, n, us, 0, a, grid)) return rc;
+    if (int rc = prepare(h, s, points, n, us, std::min(h->max_blocks, h->within_blocks[0]), a, grid)) return rc;
     a.offsets = offsets;
     size_t scan_bytes = 0;
     HIP_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, offsets, offsets, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), h->stream));
-#ifdef NEAREST_TOTAL_REDUCE
-    size_t reduce_bytes = 0;
-    HIP_TRY(rocprim::reduce(nullptr, reduce_bytes, rocprim::make_transform_iterator(offsets, Widen()), &h->status->total, 0ull, (size_t)n,
-                            rocprim::plus<unsigned long long>(), h->stream));
-    scan_bytes = std::max(scan_bytes, reduce_bytes);  // (one temporary buffer serves both, one after the other)
-#endif
     if (int rc = ensure(h->stream, h->scan_temp, scan_bytes + 16)) return rc;
-    HIP_TRY(hipMemsetAsync(h->cursor, 0, sizeof(uint32_t), h->stream));
     HIP_TRY(hipMemsetAsync(&h->status->total, 0, sizeof(unsigned long long), h->stream));
     HIP_TRY(hipMemsetAsync(offsets + n, 0, sizeof(uint32_t), h->stream));
     h->wcount.start(h->stream);
     HIP_TRY(h->wcount.mark());
     k_within_count<<<grid, BLOCK, 0, h->stream>>>(a);
     HIP_TRY(hipGetLastError());
-#ifdef NEAREST_TOTAL_REDUCE
-    HIP_TRY(rocprim::reduce(h->scan_temp.mem, reduce_bytes, rocprim::make_transform_iterator(offsets, Widen()), &h->status->total, 0ull, (size_t)n,
-                            rocprim::plus<unsigned long long>(), h->stream));
-#endif
     HIP_TRY(h->wcount.mark());
     HIP_TRY(rocprim::exclusive_scan(h->scan_temp.mem, scan_bytes, offsets, offsets, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), h->stream));
     HIP_TRY(h->wcount.mark());
@@ -797,13 +692,12 @@ int read_total(gpuart_nearest *h) {
 
 int launch_fill(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, uint32_t n, const float us[4], const uint32_t *offsets,
                 gpuart_nearest_hit *items, uint32_t capacity) {
-    WLaunch a;
+    WLaunch a{};
     uint32_t grid;
-    if (int rc = within_args(h, s, points, n, us, 1, a, grid)) return rc;
+    if (int rc = prepare(h, s, points, n, us, std::min(h->max_blocks, h->within_blocks[1]), a, grid)) return rc;
     a.offsets = const_cast<uint32_t *>(offsets);
     a.items = items;
     a.capacity = capacity;
-    HIP_TRY(hipMemsetAsync(h->cursor, 0, sizeof(uint32_t), h->stream));
     h->wfill.start(h->stream);
     HIP_TRY(h->wfill.mark());
     k_within_fill<<<grid, BLOCK, 0, h->stream>>>(a);
@@ -815,20 +709,45 @@ int launch_fill(gpuart_nearest *h, const gpuart_hip_scene *s, const float *point
     return 0;
 }
 
-/// What a finished stream may have left: a fill whose lists were not what its offsets said.
-int read_mismatch(gpuart_nearest *h) {
-    uint32_t bad = 0;
-    HIP_TRY(hipMemcpyAsync(&bad, &h->status->mismatch, 4, hipMemcpyDeviceToHost, h->stream));
+/// What a finished stream may have left in a word of the status: the word is read and, where it is set, cleared and the run fails with `text`.
+int read_flag(gpuart_nearest *h, uint32_t *flag, const char *text) {
+    uint32_t set = 0;
+    HIP_TRY(hipMemcpyAsync(&set, flag, 4, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    if (bad) {
-        HIP_TRY(hipMemsetAsync(&h->status->mismatch, 0, 4, h->stream));
-        return fail(GPUART_HIP_ERR_ARG, "nearest: the offsets are not this query set's count: the results are void");
+    if (set) {
+        HIP_TRY(hipMemsetAsync(flag, 0, 4, h->stream));
+        return fail(GPUART_HIP_ERR_ARG, text);
     }
+    return 0;
+}
+
+/// A walk that met a full stack column.
+int read_overflow(gpuart_nearest *h) {
+    return read_flag(h, &h->status->overflow, "nearest: a walk met a full stack: the tree is deeper than the descriptor's max_depth says; the results are void");
+}
+
+/// A fill whose lists were not what its offsets said.
+int read_mismatch(gpuart_nearest *h) {
+    return read_flag(h, &h->status->mismatch, "nearest: the offsets are not this query set's count: the results are void");
+}
+
+/// The two NEAREST_COUNT counters of the status from `first` on, read once the stream has finished, and zeroed.
+int read_counts(gpuart_nearest *h, unsigned long long Status::*first, uint64_t out[2]) {
+    if (int rc = check_handle(LIB, h)) return rc;
+    if (!out) return fail(GPUART_HIP_ERR_ARG, "nearest: out is NULL");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    unsigned long long c[2];
+    HIP_TRY(hipMemcpy(c, &(h->status->*first), 16, hipMemcpyDeviceToHost));
+    out[0] = c[0]; out[1] = c[1];
+    HIP_TRY(hipMemset(&(h->status->*first), 0, 16));
     return 0;
 }
 
 /// The fill pass in host memory, staged in chunks of host_chunk queries: a chunk's points and its offsets, made local to the chunk, go
 /// to the staging buffer (points, then items, then offsets), its items come back to items + offsets[chunk]. offsets: ascending, n + 1.
+/// (The three staged paths — gpuart_nearest_run_host, the count of gpuart_nearest_within_host, this — each write their chunk loop out:
+/// they share two lines, the chunk's start and size, and differ in the staging layout, in what goes up and in what comes back.)
 int fill_staged(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, size_t n, const float us[4], const uint32_t *offsets,
                 gpuart_nearest_hit *items) {
     const size_t chunk = std::min(n, h->host_chunk);
@@ -1007,9 +926,9 @@ int gpuart_nearest_brute_host(gpuart_nearest *, const float *, size_t, const flo
         uint32_t ord = nr::NO_PRIM, type = 0;
         if (nr::query_ok(p, r)) {
             if (us) {
-                const float rec[12] = {us[0], us[1], us[2], 0, us[3], 0, 0, 0, 0, 0, 0, 0};
-                const float box[6] = {us[0] - us[3], us[1] - us[3], us[2] - us[3], us[0] + us[3], us[1] + us[3], us[2] + us[3]};
-                const float d2 = nr::closest_on_prim(nr::SPHERE, rec, box, p, q);
+                PrimData d;
+                user_sphere_prim(us[0], us[1], us[2], us[3], d);
+                const float d2 = nr::closest_on_prim(nr::SPHERE, d.rec, d.box, p, q);
                 if (nr::better(d2, nr::USER_SPHERE, r2, best, ord)) { best = d2; ord = nr::USER_SPHERE; type = nr::SPHERE; memcpy(bq, q, 12); }
             }
             for (size_t k = 0; k < n_prims; k++) {
@@ -1054,17 +973,7 @@ int gpuart_nearest_last_launch(gpuart_nearest *h, uint32_t *blocks, uint32_t *la
     return 0;
 }
 
-int gpuart_nearest_counts(gpuart_nearest *h, uint64_t out[2]) {
-    if (int rc = check_handle(LIB, h)) return rc;
-    if (!out) return fail(GPUART_HIP_ERR_ARG, "nearest: out is NULL");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    Status st;
-    HIP_TRY(hipMemcpy(&st, h->status, sizeof st, hipMemcpyDeviceToHost));
-    out[0] = st.box_steps; out[1] = st.prim_tests;
-    HIP_TRY(hipMemset(&h->status->box_steps, 0, 16));
-    return 0;
-}
+int gpuart_nearest_counts(gpuart_nearest *h, uint64_t out[2]) { return read_counts(h, &Status::box_steps, out); }
 
 // ---- the neighbour lists --------------------------------------------------------------------------------------------------------------
 int gpuart_nearest_within_count(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, size_t n, const float us[4], uint32_t *offsets) {
@@ -1180,9 +1089,9 @@ int gpuart_nearest_within_brute_host(const float *recs, size_t n_recs, uint32_t 
         float q[3];
         if (!nr::query_ok(p, r)) return;
         if (us) {
-            const float rec[12] = {us[0], us[1], us[2], 0, us[3], 0, 0, 0, 0, 0, 0, 0};
-            const float box[6] = {us[0] - us[3], us[1] - us[3], us[2] - us[3], us[0] + us[3], us[1] + us[3], us[2] + us[3]};
-            const float d2 = nr::closest_on_prim(nr::SPHERE, rec, box, p, q);
+            PrimData d;
+            user_sphere_prim(us[0], us[1], us[2], us[3], d);
+            const float d2 = nr::closest_on_prim(nr::SPHERE, d.rec, d.box, p, q);
             if (nr::within_accept(d2, r2)) emit(gpuart_nearest_hit{sqrtf(d2), {q[0], q[1], q[2]}, d2, (int32_t)nr::USER_SPHERE, (int32_t)nr::SPHERE, 0});
         }
         for (const uint32_t k : order) {
@@ -1228,16 +1137,6 @@ int gpuart_nearest_within_step_ms(gpuart_nearest *h, double ms[3]) {
     return 0;
 }
 
-int gpuart_nearest_within_counts(gpuart_nearest *h, uint64_t out[2]) {
-    if (int rc = check_handle(LIB, h)) return rc;
-    if (!out) return fail(GPUART_HIP_ERR_ARG, "nearest: out is NULL");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    Status st;
-    HIP_TRY(hipMemcpy(&st, h->status, sizeof st, hipMemcpyDeviceToHost));
-    out[0] = st.w_box_steps; out[1] = st.w_prim_tests;
-    HIP_TRY(hipMemset(&h->status->w_box_steps, 0, 16));
-    return 0;
-}
+int gpuart_nearest_within_counts(gpuart_nearest *h, uint64_t out[2]) { return read_counts(h, &Status::w_box_steps, out); }
 
 }  // extern "C"

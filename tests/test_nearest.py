@@ -8,6 +8,7 @@ around the wave and the cursor's chunk, every kind of radius, with and without t
 be refused is refused with nothing written."""
 import ctypes as C
 import os
+import re
 
 import numpy as np
 import pytest
@@ -255,6 +256,10 @@ def test_the_kernel_has_no_scratch_and_the_library_exports_its_header(B, tmp_pat
     text = "\n".join(meta[kernels[0]])
     assert ".private_segment_fixed_size: 0" in text and ".vgpr_spill_count: 0" in text, text
     assert ".group_segment_fixed_size: %d" % (8 * 256 * B.NEAREST_RING) in text, text
+    # 5 waves per SIMD (DESIGN.md "Closest points"): a SIMD's 512 registers per lane over 5 waves are 102, and registers are allocated in
+    # eights: 96. No AGPRs (they come out of the same 512) and nothing spilled
+    assert int(re.search(r"\.vgpr_count:\s+(\d+)", text).group(1)) <= 96, text
+    assert re.search(r"\.agpr_count:\s+0\b", text) and ".sgpr_spill_count: 0" in text, text
     names = exported(lib)
     assert names and all(n.startswith("gpuart_nearest_") for n in names), names
     with open(os.path.join(ROOT, "include", "gpuart_nearest.h")) as f:

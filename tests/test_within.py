@@ -8,6 +8,7 @@ and spill limit, through every input kind; the capacity protocol never writes ou
 refused with nothing written. There is no tolerance anywhere."""
 import ctypes as C
 import os
+import re
 
 import numpy as np
 import pytest
@@ -229,6 +230,10 @@ def test_the_kernels_have_no_scratch_and_the_library_exports_its_header(B, tmp_p
         text = "\n".join(meta[k])
         assert ".private_segment_fixed_size: 0" in text and ".vgpr_spill_count: 0" in text, text
         assert ".group_segment_fixed_size: %d" % (4 * 256 * B.NEAREST_RING) in text, text
+        # 5 waves per SIMD (DESIGN.md "Neighbour lists"): a SIMD's 512 registers per lane over 5 waves are 102, and registers are allocated
+        # in eights: 96. No AGPRs (they come out of the same 512) and nothing spilled
+        assert int(re.search(r"\.vgpr_count:\s+(\d+)", text).group(1)) <= 96, text
+        assert re.search(r"\.agpr_count:\s+0\b", text) and ".sgpr_spill_count: 0" in text, text
     names = exported(lib)
     assert sum(n.startswith("gpuart_nearest_within_") for n in names) == 9 and all(n.startswith("gpuart_nearest_") for n in names), names
     with open(os.path.join(ROOT, "include", "gpuart_nearest.h")) as f:

@@ -14,7 +14,10 @@ and per kind:
 
   rate     Mqueries/s of the shipped library (persistent lanes) and of the plain form (one thread per query, grid stride), from HIP events
            around the launch (gpuart_nearest_step_ms): 2 warm-up launches each, then R launches of each, alternating; median and range.
-           Both forms' records are compared bit for bit first: faster and different is not faster
+           All forms' records are compared bit for bit first: faster and different is not faster
+  spread   the shipped form against itself: a second handle of the same library in the same rounds, the ratio of the two medians
+  parent   gpuart_amd/lib_ab/libgpuart_nearest_parent.so, if it is there — the library of another commit, copied there by hand —, in the same
+           rounds: shipped / parent time beside the spread, and half the range of the parent's rounds, the other noise the run shows
   steps    box steps (records read) and primitive tests per query, from the counting builds (-DNEAREST_COUNT), not from the timed ones
   rays     Backend.trace_rays closest-hit on as many incoherent rays (origins uniform in the root box, uniform directions), call to return
            on device tensors, in the same run: the yardstick
@@ -109,8 +112,9 @@ def main():
     repeats, n = arg("--repeats", 7), arg("--queries", 1 << 20)
     side = int(round(n ** 0.5))
     cam = dict(S.BENCH_CAMERA); cam["dir"] = S.camera_dir(cam)
-    shipped = Handle(os.path.join(B.LIBDIR, "libgpuart_nearest.so"))
-    plain, count, plain_count = variant("plain"), variant("count"), variant("plain_count")
+    shipped_path = os.path.join(B.LIBDIR, "libgpuart_nearest.so")
+    shipped, again = Handle(shipped_path), Handle(shipped_path)
+    plain, count, plain_count, parent = variant("plain"), variant("count"), variant("plain_count"), variant("parent")
     if not (plain and count and plain_count):
         print("the variants are not built (make -C gpuart_amd/csrc nearest-variants): the plain form and the step counts are NOT MEASURED")
     hip = C.CDLL("libamdhip64.so")
@@ -123,7 +127,7 @@ def main():
         print("%s: %d primitives, %d records, depth %d" % (which, scene.n_prims, scene.n_recs, scene.max_depth))
         sets, surface_pixels = workloads(be, scene, n, side)
         print("  %d queries per kind; the surface points come from %d hit pixels of a %d x %d frame" % (n, surface_pixels, side, side))
-        forms = [("persistent", shipped)] + ([("plain", plain)] if plain else [])
+        forms = [("persistent", shipped), ("again", again)] + ([("plain", plain)] if plain else []) + ([("parent", parent)] if parent else [])
         checks = []
         for _, h in forms:
             for _ in range(3):
@@ -144,11 +148,15 @@ def main():
                 for name, h in forms:
                     h.run(scene, points, out[name])
                     ms[name].append(h.step_ms()[1])
+            med = {name: statistics.median(ms[name]) for name, _ in forms}
             line = "  %-8s" % kind + "".join("  %s %s Mq/s" % (name, spread([n / t / 1e3 for t in ms[name]])) for name, _ in forms)
+            line += "  same build twice %+.1f %%" % (100 * (med["again"] / med["persistent"] - 1))
             if plain:
-                a, b = statistics.median(ms["persistent"]), statistics.median(ms["plain"])
-                line += "  persistent/plain time %.3f; records %s" % (a / b, "bit-identical" if same else "DIFFER")
-            print(line + "  (%.0f %% answered)" % (100 * hit_share))
+                line += "; persistent/plain time %.3f" % (med["persistent"] / med["plain"])
+            if parent:
+                line += "; persistent/parent time %.3f (half the range of the parent's rounds: %.1f %%)" % (
+                    med["persistent"] / med["parent"], 50 * (max(ms["parent"]) - min(ms["parent"])) / med["parent"])
+            print(line + "; records of all forms %s  (%.0f %% answered)" % ("bit-identical" if same else "DIFFER", 100 * hit_share))
             for name, c in (("persistent", count), ("plain", plain_count)):
                 if c:
                     c.counts()
@@ -183,7 +191,7 @@ def main():
               % (spread([1e3 * c for c in checks]), len(checks), len(ordinals), spread([1e3 * t for t in rf[1:]])))
         be.close()
         r.close()
-    for h in (shipped, plain, count, plain_count):
+    for h in (shipped, again, plain, count, plain_count, parent):
         if h:
             h.close()
 

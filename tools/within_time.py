@@ -16,9 +16,9 @@ long. Per point (scene, kind, radius):
            (persistent-lane) form and the plain form alternating; median and range. Mqueries/s over count + scan + fill, Mitems/s over the
            fill, and the fill's 32 bytes per item over its time against the HBM peak (8.0 TB/s: MI355X_MICROARCH.md) — the bytes the result
            needs, not what the walk reads. Offsets and items of both forms are compared bit for bit first
-  total    the count pass of a build that sums the total by rocPRIM's reduce over the lengths (-DNEAREST_TOTAL_REDUCE: the reduce runs between
-           the count kernel and the scan and is timed with the count) against the shipped one atomic per wave
   spread   the shipped form against itself: a second handle of the same library, alternating, the ratio of the two medians
+  parent   gpuart_amd/lib_ab/libgpuart_nearest_parent.so, if it is there — the library of another commit, copied there by hand —, in the same
+           rounds: shipped / parent time per pass beside the spread, and half the range of the parent's rounds, the other noise the run shows
   steps    box steps and primitive tests per query and pass, from the counting builds (-DNEAREST_COUNT), not from the timed ones
   beside   closest_points (gpuart_nearest_run) on the same points with the same r and with r = +inf, HIP events; Backend.within on device
            tensors, call to return
@@ -152,7 +152,7 @@ def main():
     cam = dict(S.BENCH_CAMERA); cam["dir"] = S.camera_dir(cam)
     shipped_path = os.path.join(B.LIBDIR, "libgpuart_nearest.so")
     shipped, again = Handle(shipped_path), Handle(shipped_path)
-    plain, count, plain_count, reduce_ = variant("plain"), variant("count"), variant("plain_count"), variant("reduce")
+    plain, count, plain_count, parent = variant("plain"), variant("count"), variant("plain_count"), variant("parent")
     if not (plain and count and plain_count):
         say("the variants are not built (make -C gpuart_amd/csrc nearest-variants): the plain form and the step counts are NOT MEASURED")
     say("neighbour lists on %s; %d queries per kind, median (range) of %d rounds after 2 warm-up rounds; times in ms" % (torch.cuda.get_device_name(0), n, repeats))
@@ -165,7 +165,7 @@ def main():
         scene = be.scene_device()
         extent = max(b - a for a, b in zip(scene.root_min[:], scene.root_max[:]))
         say("%s: %d primitives, %d records, depth %d, root extent %.4g" % (which, scene.n_prims, scene.n_recs, scene.max_depth, extent))
-        forms = [("persistent", shipped), ("again", again)] + ([("plain", plain)] if plain else []) + ([("reduce", reduce_)] if reduce_ else [])
+        forms = [("persistent", shipped), ("again", again)] + ([("plain", plain)] if plain else []) + ([("parent", parent)] if parent else [])
         for _, h in forms:
             h.bind(scene)
         for c in (count, plain_count):
@@ -202,8 +202,10 @@ def main():
                     ratio = [med["plain"][k] / med["persistent"][k] for k in (0, 2)]
                     line += "; plain / persistent time: count %.3f, fill %.3f" % tuple(ratio)
                     verdict.append(all(ratio[k] < 1 - noise[k] for k in (0, 1)))
-                if reduce_:
-                    line += "; total by reduce / by atomic, count time: %.3f" % (med["reduce"][0] / med["persistent"][0])
+                if parent:
+                    line += "; persistent / parent time: count %.3f, fill %.3f (half the range of the parent's rounds: count %.1f %%, fill %.1f %%)" % (
+                        tuple(med["persistent"][k] / med["parent"][k] for k in (0, 2))
+                        + tuple(50 * (max(ms["parent"][k]) - min(ms["parent"][k])) / med["parent"][k] for k in (0, 2)))
                 say(line)
                 for name, c in (("persistent", count), ("plain", plain_count)):
                     if c:
@@ -235,7 +237,7 @@ def main():
         say("the plain form is faster than the persistent one by more than the same-build spread, in both passes, at %d of %d points" % (sum(verdict), len(verdict)))
     say("NOT MEASURED: mixed-type scenes at this size (both scenes are triangles only); a one-pass variant with a fixed number of slots per query; "
         "user spheres; host-memory (staged) calls")
-    for h in (shipped, again, plain, count, plain_count, reduce_):
+    for h in (shipped, again, plain, count, plain_count, parent):
         if h:
             h.close()
     if out_path:
