@@ -462,88 +462,7 @@ GD_FN bool leaf_test_small(const Scene &sc, const Ray &r, uint32_t first, bool t
     return false;
 }
 
-// ---- traversal stack: short per-lane ring in LDS + spill to global memory -------------------------
-// Entry = (upper child's ref, parent's box-entry parameter, the child's own box-entry parameter).
-// Entries [base, sp) live in the LDS ring (slot = index % RING, one column per
-// lane -> conflict-free accesses); entries [0, base) live in a per-lane global spill column. The oldest
-// entries (closest to the root, popped last) are the ones spilled, so spills are rare; any tree depth
-// up to the reference's 1024 levels works without a separate code path.
-#ifndef GD_RING
-#define GD_RING 8
-#endif
-
-struct StackEntry {
-    uint32_t ref;   ///< upper child: record index, or GD_REF_LEAF | first primitive
-    float pe, he;   ///< box-entry parameter of the parent / of the child itself (GD_ENTRY_MISS: box not hit)
-};
-
-#if (GD_RING & (GD_RING - 1)) == 0
-#define GD_RING_SLOT(i) ((i) & (GD_RING - 1))
-#else
-#define GD_RING_SLOT(i) ((i) % GD_RING)  // i < 1024 + GD_RING: a multiply-shift
-#endif
-
-struct TravStack {
-    uint2 *ring_a;           ///< LDS, [GD_RING][BLOCK]: (ref, pe)
-    float *ring_b;           ///< LDS, [GD_RING][BLOCK]: he
-    uint4 *spill;            ///< global, [levels][total_lanes]; this lane's column is spill[level * spill_stride]
-    uint32_t ring_stride;    ///< BLOCK
-    uint32_t spill_stride;   ///< total lanes of the launch
-    uint32_t sp, base;
-    GD_FN void reset() { sp = 0; base = 0; }
-    /// The replicas of a ray (thin-wave modes) read what its first replica stored: the stores of `if (writer)` must stay ahead
-    /// of the other lanes' loads in the instruction stream. Per thread the compiler could legally turn "conditional store, then
-    /// load" into "writer keeps the value, the others load" and run the others first; a wavefront-scope fence (no instruction:
-    /// a wave executes its memory operations in order) plus a wave barrier pin the order.
-    static GD_FN void replica_fence() {
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    }
-    /// `writer`: this lane performs the stores. A ray that several lanes carry as identical replicas (the thin-wave modes
-    /// below) has ONE column; every replica keeps sp / base and reads the column, only the first one writes it.
-    GD_FN void push(StackEntry e, bool writer = true) {
-        GD_STACK_EVENT(writer, 0);
-        if (sp - base == GD_RING) {
-            GD_STACK_EVENT(writer, 1);
-            uint32_t o = GD_RING_SLOT(base) * ring_stride;
-            uint2 a = ring_a[o];
-            if (writer) spill[(size_t)base * spill_stride] = make_uint4(a.x, a.y, __float_as_uint(ring_b[o]), 0);
-            replica_fence();
-            base++;
-        }
-        uint32_t o = GD_RING_SLOT(sp) * ring_stride;
-        if (writer) {
-            ring_a[o] = make_uint2(e.ref, __float_as_uint(e.pe));
-            ring_b[o] = e.he;
-        }
-        replica_fence();
-        sp++;
-    }
-    GD_FN StackEntry pop(bool writer = true) {  // precondition: sp > 0
-        GD_STACK_EVENT(writer, 2);
-        if (sp == base) {
-            GD_STACK_EVENT(writer, 3);
-            base--;
-            uint4 v = spill[(size_t)base * spill_stride];
-            uint32_t o = GD_RING_SLOT(base) * ring_stride;
-            if (writer) {
-                ring_a[o] = make_uint2(v.x, v.y);
-                ring_b[o] = __uint_as_float(v.z);
-            }
-            replica_fence();
-        }
-        sp--;
-        uint32_t o = GD_RING_SLOT(sp) * ring_stride;
-        uint2 a = ring_a[o];
-        StackEntry e;
-        e.ref = a.x; e.pe = __uint_as_float(a.y); e.he = ring_b[o];
-        // Keep the entry's three words in the two LDS reads issued here: left alone the compiler reads the parameters first (4 + 4 bytes),
-        // compares, and fetches the ref with a THIRD read once the entry is accepted — a second LDS round trip in the dependent chain
-        // pop -> enter -> record address -> fetch of every step that ends in a pop.
-        asm volatile("" : "+v"(e.ref), "+v"(e.pe), "+v"(e.he));
-        return e;
-    }
-};
+#include "trav_stack.h"  // GD_RING, StackEntry, TravStack: short per-lane ring in LDS + spill to global memory
 
 /// Traversal state of one ray. In the reference's order (every walk that is not an ordered NEAREST one: the counting and
 /// one-thread-per-pixel kernels, trees with irregular boxes, Sun-shadow queries, a query that trav_settle sends round again)
@@ -1000,16 +919,33 @@ GD_FN void trav_packet(const Scene &sc, F3 ro, F3 rd, F3 rdiv, Trav &t, TravStac
             box_pair_fast(sc, r, rdiv, rec, q0, q1, q2, q3, act, el, eh, hl, hh);
             GD_STATS({ const unsigned long long a_ = __ballot(act); if ((threadIdx.x & 63) == 0) { atomicAdd(&g_packet_stats[0], 1ull); atomicAdd(&g_packet_stats[1], (unsigned long long)__popcll(a_)); } })
             const bool lo = act & hl & !(el > t.closest), hi = act & hh & !(eh > t.closest);
-            if (__ballot(hi) != 0) {
-                StackEntry e;
-                e.ref = __float_as_uint(q1.w); e.pe = t.entry; e.he = hi ? eh : GD_ENTRY_MISS;
-                st.push(e);
-            }
+            const float he = hi ? eh : GD_ENTRY_MISS;  // the upper child's stack entry for this lane (trav_step_box: MISS where its own walk stacks nothing)
+            const bool stacks = __ballot(hi) != 0;     // wave-uniform: some lane's walk stacks the upper child
             if (__ballot(lo) != 0) {
+                if (stacks) {
+                    StackEntry e;
+                    e.ref = __float_as_uint(q1.w); e.pe = t.entry; e.he = he;
+                    GD_STATS(if ((threadIdx.x & 63) == 0) atomicAdd(&g_packet_stats[4], 1ull);)
+                    st.push(e);
+                }
                 act = lo;
                 t.entry = lo ? el : t.entry;
                 ref = __float_as_uint(q0.w);
                 continue;
+            }
+            if (stacks) {
+                // ---- upper-only step: no lane goes down, so the entry would be popped at once, with no leaf test in between (`closest` is what
+                // it is now). The pop's own test on the values in registers instead of a round trip through the ring; the stack stays as it is (a
+                // push and its pop leave the same entries behind, at the ring's edge too: only the oldest ring entry's place, ring or spill column,
+                // and `base` differ — tools/trav_stack_check.cpp).
+                GD_STATS(if ((threadIdx.x & 63) == 0) atomicAdd(&g_packet_stats[7], 1ull);)
+                const bool take = (t.state != TRAV_DONE) & !(t.entry > t.closest) & !(he > t.closest);
+                if (__ballot(take) != 0) {
+                    act = take;
+                    t.entry = take ? he : t.entry;
+                    ref = __float_as_uint(q1.w);
+                    continue;
+                }
             }
         } else {
             // ---- leaf: the primitive tests of trav_step_leaf for the lanes at it; a shadow query is settled by one accepted hit
@@ -1026,6 +962,7 @@ GD_FN void trav_packet(const Scene &sc, F3 ro, F3 rd, F3 rdiv, Trav &t, TravStac
             if (st.sp == 0) { t.state = TRAV_DONE; return; }
             const StackEntry e = st.pop();
             const bool take = (t.state != TRAV_DONE) & !(e.pe > t.closest) & !(e.he > t.closest);
+            GD_STATS({ const int k_ = __ballot(take) != 0 ? 5 : 6; if ((threadIdx.x & 63) == 0) atomicAdd(&g_packet_stats[k_], 1ull); })
             if (__ballot(take) != 0) {
                 act = take;
                 t.entry = take ? e.he : t.entry;

@@ -27,8 +27,10 @@
 namespace gd {
 // trav_pop: [0] trips of its loop as waves execute them, [1] lanes in those trips, [2] calls (wave level), [3] lanes in the calls
 GD_STATS(__device__ unsigned long long g_pop_stats[4];)
-// trav_packet: [0] box steps of packets, [1] active lanes in them, [2] leaf steps, [3] active lanes in them
-GD_STATS(__device__ unsigned long long g_packet_stats[4];)
+// trav_packet (k_trace's packets and the walking k_gen's): [0] box steps of packets, [1] active lanes in them, [2] leaf steps, [3] active lanes
+// in them, [4] pushes, [5] trips of the pop loop that some lane takes, [6] trips that no lane takes, [7] upper-only steps (no lane goes down
+// the lower child, some lane's walk stacks the upper one: the packet enters it from registers, no push and no pop)
+GD_STATS(__device__ unsigned long long g_packet_stats[8];)
 // trav_step_box: [0] boxes, [1] quick answers that stand, [2] steps, [3] steps that had to run the face tests (a lane withdrew),
 // [4] standing answers that differ from the face tests (must stay 0), [5] of them: marked odd by the face tests
 GD_QCHECK(__device__ unsigned long long g_quick_stats[8];)

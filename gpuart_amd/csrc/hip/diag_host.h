@@ -4,7 +4,7 @@
 #ifdef GD_STEP_STATS
 /// reads (and clears) k_trace's step statistics (kernels_pipeline.h): box steps, lanes in them, leaf steps, lanes in them, rounds of the
 /// wide loop, lanes holding a ray in them, refill episodes; then trav_pop's trips, the phase ticks and the packet walks' steps (box steps,
-/// active lanes in them, leaf steps, active lanes in them): 20 words
+/// active lanes in them, leaf steps, active lanes in them, pushes, pop trips with and without a taker, upper-only steps): 24 words
 int gpuart_hip_debug_step_stats(gpuart_hip_ctx *c, unsigned long long *out) {
     if (!c || !out) return GPUART_HIP_ERR_ARG;
     static unsigned long long zero[8];
@@ -15,8 +15,8 @@ int gpuart_hip_debug_step_stats(gpuart_hip_ctx *c, unsigned long long *out) {
     HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(gd::g_pop_stats), zero, 4 * sizeof(unsigned long long)));
     HIP_TRY(hipMemcpyFromSymbol(out + 12, HIP_SYMBOL(g_phase_ticks), 4 * sizeof(unsigned long long)));
     HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_phase_ticks), zero, 4 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemcpyFromSymbol(out + 16, HIP_SYMBOL(gd::g_packet_stats), 4 * sizeof(unsigned long long)));  // out: 20 words
-    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(gd::g_packet_stats), zero, 4 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemcpyFromSymbol(out + 16, HIP_SYMBOL(gd::g_packet_stats), 8 * sizeof(unsigned long long)));  // out: 24 words
+    HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(gd::g_packet_stats), zero, 8 * sizeof(unsigned long long)));
     return 0;
 }
 #endif

@@ -787,8 +787,11 @@ k_trace(Scene sc, Frame f, gpuart_params P, PathBuffers b, int seg_c, int seg_s,
             };
             if (M == 2) thin_rounds(std::integral_constant<int, 2>());
             else thin_rounds(std::integral_constant<int, 4>());
-        } else
-        // ---- traverse until enough lanes have finished (a lane without a ray is in state DONE)
+        } else {
+        // ---- traverse until enough lanes have finished (a lane without a ray is in state DONE): the rounds go on while more than `stay` lanes
+        // are busy. One threshold for the three ends of the loop (`exhausted` and `hold` change outside it only): no lane busy; a wave that
+        // may refill has refill_lanes idle ones; a draining wave that may move to pairs / quads of lanes per ray is down to 32 rays.
+        const uint32_t stay = !exhausted ? (!hold && tune.refill_lanes <= 64u ? 64u - tune.refill_lanes : 0u) : THIN_OK ? BLOCK / 2 : 0u;
         for (;;) {
             GD_STATS({ const unsigned long long dd = __ballot(t.state == TRAV_DESCEND); if (dd) { ss_box++; ss_box_lanes += (uint32_t)__popcll(dd); } ss_rounds++; ss_held += (uint32_t)__popcll(__ballot(slot != SLOT_INVALID)); })
             if (t.state == TRAV_DESCEND) trav_step_box<COUNT, GD_BOXES_OF(TYPES), NEAR>(sc, Ray{ro, rd}, rdiv, t, st, COUNT ? &wc : nullptr, !shadow && !refwalk);
@@ -796,22 +799,22 @@ k_trace(Scene sc, Frame f, gpuart_params P, PathBuffers b, int seg_c, int seg_s,
             unsigned long long descending = __ballot(t.state == TRAV_DESCEND);
             // leaves are tested once 1/leaf_share of the lanes that still have a ray wait at one (at most leaf_lanes):
             // a wave that is draining its last rays must not hold leaves back for a quorum it can no longer reach
-            const uint32_t waiting = (uint32_t)__popcll(at_leaf);
-            if (at_leaf && (waiting >= tune.leaf_lanes || tune.leaf_share * waiting >= waiting + (uint32_t)__popcll(descending))) {
-                GD_STATS(ss_leaf++; ss_leaf_lanes += waiting;)
-                if (t.state & 1) {
-                    trav_step_leaf<false, COUNT, TYPES, NEAR>(sc, Ray{ro, rd}, t, st, COUNT ? &wc : nullptr, !shadow && !refwalk);
-                    // the reference only asks a shadow query whether anything was hit: one accepted hit settles it
-                    if (shadow && any_shadow && t.hit_prim != GD_NO_PRIM) t.state = TRAV_DONE;
+            // (no lane at a leaf: no quorum arithmetic)
+            if (at_leaf) {
+                const uint32_t waiting = (uint32_t)__popcll(at_leaf);
+                if (waiting >= tune.leaf_lanes || tune.leaf_share * waiting >= waiting + (uint32_t)__popcll(descending)) {
+                    GD_STATS(ss_leaf++; ss_leaf_lanes += waiting;)
+                    if (t.state & 1) {
+                        trav_step_leaf<false, COUNT, TYPES, NEAR>(sc, Ray{ro, rd}, t, st, COUNT ? &wc : nullptr, !shadow && !refwalk);
+                        // the reference only asks a shadow query whether anything was hit: one accepted hit settles it
+                        if (shadow && any_shadow && t.hit_prim != GD_NO_PRIM) t.state = TRAV_DONE;
+                    }
+                    descending = __ballot(t.state == TRAV_DESCEND);
+                    at_leaf = __ballot((t.state & 1) != 0);
                 }
-                descending = __ballot(t.state == TRAV_DESCEND);
-                at_leaf = __ballot((t.state & 1) != 0);
             }
-            unsigned long long busy = descending | at_leaf;
-            if (!busy) break;
-            if (!exhausted && !hold && 64u - (uint32_t)__popcll(busy) >= tune.refill_lanes) break;
-            // a draining wave may move to pairs / quads once it is down to 32 rays
-            if (THIN_OK && exhausted && (uint32_t)__popcll(busy) <= BLOCK / 2) break;
+            if ((uint32_t)__popcll(descending | at_leaf) <= stay) break;
+        }
         }
         GD_SS_PHASE(ss_t_trav)
         // ---- a finished nearest-first query that cannot vouch for its answer walks again, in the reference's order (every replica alike)

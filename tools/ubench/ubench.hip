@@ -4,6 +4,8 @@
 //   aabb      : gd::aabb_entry (the product's own box test) on register-resident data: box tests per second with no memory
 //   gather    : 64-byte node records fetched at data-dependent addresses (4 x global_load_dwordx4 per lane), the access
 //               pattern of trav_step_box, over arrays of several sizes (L1 / L2 / Infinity-Cache resident)
+//   issue     : `ubench issue` — the scalar unit's issue rate per CU (independent s_add_u32) at 1, 2, 4 waves on each of 1, 2, 4 SIMDs,
+//               beside v_fma_f32 in the same harness
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -I../../gpuart_amd/csrc/hip -I../../include -o ubench ubench.hip
 // Prints one line per measurement; `ubench json` prints one JSON object (tools/ubench/run.sh stores it under profiles/).
 #include <hip/hip_runtime.h>
@@ -101,6 +103,54 @@ __global__ void __launch_bounds__(64) k_valu_select(float *out, int iters, unsig
     unsigned long long t1 = __builtin_readcyclecounter();
     out[blockIdx.x * 64 + threadIdx.x] = k[0] + k[1] + k[2] + k[3] + v[0] + v[1] + v[2] + v[3];
     if (threadIdx.x == 0) cycles[blockIdx.x] = t1 - t0;
+}
+
+// ---- scalar issue: what does ONE compute unit's scalar unit sustain? (round 11, profiles/r11/issue_budget.txt) ------------------------
+// One workgroup of 16 waves on one CU. Every wave reads the SIMD it landed on (HW_ID bits 5:4) and takes a rank among the waves of that
+// SIMD; the waves with SIMD < simds and rank < waves run `iters` x 128 independent instructions (8 accumulators), the others go straight
+// to the end. KIND 0: s_add_u32 (scalar registers), 1: v_fma_f32 — the same harness on the vector unit, whose rate is known (MI355X: a
+// SIMD issues one wave64 VALU instruction per 2 cycles at best), as a check of the harness and of the clock.
+// stamps[4 * wave] = the shader-clock counter before and after the stream, then the 100 MHz counter before and after; part[wave] = 1 + SIMD
+// if the wave ran the stream, else 0.
+template <int KIND>
+__global__ void __launch_bounds__(1024) k_issue(int simds, int waves, int iters, float *out, unsigned long long *stamps, int *part) {
+    __shared__ int s_rank[4];
+    if (threadIdx.x < 4) s_rank[threadIdx.x] = 0;
+    __syncthreads();
+    const int simd = (int)__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4) & 3;  // hwreg(HW_REG_HW_ID, 4, 2): SIMD_ID
+    int rank = 0;
+    if ((threadIdx.x & 63) == 0) rank = atomicAdd(&s_rank[simd], 1);
+    rank = __builtin_amdgcn_readfirstlane(rank);
+    const bool runs = simd < simds && rank < waves;
+    __syncthreads();
+    uint32_t a[8];
+    float v[8];
+    for (int i = 0; i < 8; i++) { a[i] = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x + i)); v[i] = threadIdx.x * 0.001f + i; }
+    const uint32_t b = (uint32_t)__builtin_amdgcn_readfirstlane(iters | 1);
+    const float fb = 1.0000001f, fc = 1e-9f;
+    unsigned long long t0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime(), t1 = t0, r1 = r0;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (runs) {
+        for (int it = 0; it < iters; it++) {
+#pragma unroll
+            for (int k = 0; k < 16; k++)
+#pragma unroll
+                for (int i = 0; i < 8; i++) {
+                    if (KIND == 0) asm volatile("s_add_u32 %0, %0, %1" : "+s"(a[i]) : "s"(b) : "scc");
+                    else asm volatile("v_fma_f32 %0, %0, %1, %2" : "+v"(v[i]) : "v"(fb), "v"(fc));
+                }
+        }
+        t1 = __builtin_amdgcn_s_memtime();
+        r1 = __builtin_amdgcn_s_memrealtime();
+    }
+    uint32_t s = 0; float f = 0;
+    for (int i = 0; i < 8; i++) { s += a[i]; f += v[i]; }
+    out[threadIdx.x] = f + (float)s;
+    if ((threadIdx.x & 63) == 0) {
+        const uint32_t w = threadIdx.x >> 6;
+        stamps[4 * w] = t0; stamps[4 * w + 1] = t1; stamps[4 * w + 2] = r0; stamps[4 * w + 3] = r1;
+        part[w] = runs ? 1 + simd : 0;
+    }
 }
 
 // ---- the product's box test on registers ---------------------------------------------------------
@@ -530,6 +580,42 @@ static void timed(const char *name, int waves_per_simd, double work_per_wave, co
     CHECK(hipEventDestroy(e0)); CHECK(hipEventDestroy(e1));
 }
 
+// scalar and vector issue rate of one CU with `waves` resident waves on each of `simds` SIMDs (k_issue): instructions per shader clock
+// and CU over the span from the first wave's start to the last wave's end, and the clock the two counters imply.
+static void issue_rates() {
+    float *out; unsigned long long *stamps; int *part;
+    CHECK(hipMalloc(&out, 1024 * 4)); CHECK(hipMalloc(&stamps, 64 * 8)); CHECK(hipMalloc(&part, 16 * 4));
+    const int iters = 8192;  // x 128 instructions per wave: about a million
+    printf("issue rate of ONE compute unit (one workgroup of 16 waves; the waves on the first S SIMDs with rank < W run %d x 128 independent instructions)\n", iters);
+    for (int kind = 0; kind < 2; kind++)
+        for (int simds : {1, 2, 4})
+            for (int waves : {1, 2, 4}) {
+                unsigned long long h[64]; int p[16];
+                for (int rep = 0; rep < 2; rep++) {  // the second launch counts
+                    if (kind == 0) k_issue<0><<<1, 1024>>>(simds, waves, iters, out, stamps, part);
+                    else k_issue<1><<<1, 1024>>>(simds, waves, iters, out, stamps, part);
+                    CHECK(hipDeviceSynchronize());
+                }
+                CHECK(hipMemcpy(h, stamps, sizeof h, hipMemcpyDeviceToHost));
+                CHECK(hipMemcpy(p, part, sizeof p, hipMemcpyDeviceToHost));
+                unsigned long long t_first = ~0ull, t_last = 0, r_first = ~0ull, r_last = 0; int n = 0, per_simd[4] = {0, 0, 0, 0};
+                for (int w = 0; w < 16; w++)
+                    if (p[w]) {
+                        n++; per_simd[(p[w] - 1) & 3]++;
+                        if (h[4 * w] < t_first) t_first = h[4 * w];
+                        if (h[4 * w + 1] > t_last) t_last = h[4 * w + 1];
+                        if (h[4 * w + 2] < r_first) r_first = h[4 * w + 2];
+                        if (h[4 * w + 3] > r_last) r_last = h[4 * w + 3];
+                    }
+                const double instr = (double)n * iters * 128.0;
+                const double clocks = n ? (double)(t_last - t_first) : 0.0, sec = n ? (double)(r_last - r_first) / 100e6 : 0.0;
+                printf("%-10s SIMDs %d  waves/SIMD %d  (ran: %2d waves, per SIMD %d %d %d %d)  %10.0f shader clocks  %7.3f instr/clk/CU  %7.3f instr/clk/wave   clock %.2f GHz\n",
+                       kind == 0 ? "s_add_u32" : "v_fma_f32", simds, waves, n, per_simd[0], per_simd[1], per_simd[2], per_simd[3], clocks,
+                       clocks > 0 ? instr / clocks : 0.0, clocks > 0 && n ? instr / clocks / n : 0.0, sec > 0 ? clocks / sec * 1e-9 : 0.0);
+            }
+    CHECK(hipFree(out)); CHECK(hipFree(stamps)); CHECK(hipFree(part));
+}
+
 int main(int argc, char **argv) {
     const bool json = argc > 1 && !strcmp(argv[1], "json");
     hipDeviceProp_t prop;
@@ -544,6 +630,10 @@ int main(int argc, char **argv) {
         for (int r = 0; r < 40; r++) k_valu_indep<<<g_cus * 32, 64>>>(o, 8192, cy);
         CHECK(hipDeviceSynchronize());
         CHECK(hipFree(o)); CHECK(hipFree(cy));
+    }
+    if (argc > 1 && !strcmp(argv[1], "issue")) {  // `ubench issue`: only this part
+        issue_rates();
+        return 0;
     }
     const bool only_node = getenv("UBENCH_ONLY_NODE") != nullptr;
     if (!only_node) {
