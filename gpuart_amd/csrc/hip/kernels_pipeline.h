@@ -351,6 +351,9 @@ __global__ void k_accumulate(float4 *__restrict__ accum, const float4 *__restric
 #ifndef GD_TRACE_WAVES_LEAN
 #define GD_TRACE_WAVES_LEAN 6  // the kernels without cone / sphere code fit 6 waves per SIMD (<= 80 VGPRs)
 #endif
+#ifndef GD_ROUND_STEPS
+#define GD_ROUND_STEPS 2  // box steps of k_trace's wide loop between two passes through its round tail ("The round's cadence")
+#endif
 // ---- the persistent-lane loop of k_direct_persistent and k_ray_query (kernels_query.h), stated once ---------------------------------
 // A wave takes chunks of entries (pixel slots, queries) from a cursor, a lane that is done with its entry takes the next one, and once
 // the cursor is dry a wave that is down to 32 (16) entries carries each by a pair (quad) of lanes. The kernels keep the state a lane carries,
@@ -792,9 +795,18 @@ k_trace(Scene sc, Frame f, gpuart_params P, PathBuffers b, int seg_c, int seg_s,
         // are busy. One threshold for the three ends of the loop (`exhausted` and `hold` change outside it only): no lane busy; a wave that
         // may refill has refill_lanes idle ones; a draining wave that may move to pairs / quads of lanes per ray is down to 32 rays.
         const uint32_t stay = !exhausted ? (!hold && tune.refill_lanes <= 64u ? 64u - tune.refill_lanes : 0u) : THIN_OK ? BLOCK / 2 : 0u;
+        // A round is GD_ROUND_STEPS box steps, then the tail (ballots, leaf quorum and leaf step, the compare): the tail's scalar work is paid
+        // once per round, and a lane that reaches a leaf or its end in an earlier step of the round waits out the others. A lane's walk is a
+        // state machine on its own registers and its own stack column: when the wave looks at the ballots decides in which round a leaf is
+        // tested and when a lane is refilled, never what a lane computes — every frame stays what it was bit for bit, and the refill and
+        // thin-mode exits are reached at most GD_ROUND_STEPS - 1 steps late. (1: the loop of one step per tail, instruction for instruction.)
         for (;;) {
-            GD_STATS({ const unsigned long long dd = __ballot(t.state == TRAV_DESCEND); if (dd) { ss_box++; ss_box_lanes += (uint32_t)__popcll(dd); } ss_rounds++; ss_held += (uint32_t)__popcll(__ballot(slot != SLOT_INVALID)); })
-            if (t.state == TRAV_DESCEND) trav_step_box<COUNT, GD_BOXES_OF(TYPES), NEAR>(sc, Ray{ro, rd}, rdiv, t, st, COUNT ? &wc : nullptr, !shadow && !refwalk);
+            GD_STATS(ss_rounds++; ss_held += (uint32_t)__popcll(__ballot(slot != SLOT_INVALID));)
+#pragma unroll
+            for (int step = 0; step < GD_ROUND_STEPS; step++) {
+                GD_STATS({ const unsigned long long dd = __ballot(t.state == TRAV_DESCEND); if (dd) { ss_box++; ss_box_lanes += (uint32_t)__popcll(dd); } })
+                if (t.state == TRAV_DESCEND) trav_step_box<COUNT, GD_BOXES_OF(TYPES), NEAR>(sc, Ray{ro, rd}, rdiv, t, st, COUNT ? &wc : nullptr, !shadow && !refwalk);
+            }
             unsigned long long at_leaf = __ballot((t.state & 1) != 0);  // the leaf states are the odd ones
             unsigned long long descending = __ballot(t.state == TRAV_DESCEND);
             // leaves are tested once 1/leaf_share of the lanes that still have a ray wait at one (at most leaf_lanes):

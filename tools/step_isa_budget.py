@@ -53,6 +53,13 @@ spill = next(k for k in range(faces, push + 1) if "global_store_dwordx4" in text
 tail = next(k for k in range(push, len(blocks)) if "s_bcnt1_i32_b64" in text(blocks[k]))
 leaf = next(k for k in range(tail, len(blocks)) if "v_rcp_f32" in text(blocks[k]))
 pop = next(k for k in range(leaf, len(blocks)) if re.search(r"ds_read_b64|ds_read_b32", text(blocks[k])) and "v_max_f32" in text(blocks[k]))
+# Round 12's structure, where the build has it. GD_ROUND_STEPS > 1: a second record fetch between the first step's push and the tail — the
+# second step of the round. GD_POP_PEEL: two pop blocks (the entry's two LDS reads and the compare) after the first step's push instead of
+# one — the first trip straight-line, then the loop, with the wave-uniform test of the lanes that need another trip between them.
+rec2 = next((k for k in range(push + 1, tail) if len(re.findall(r"global_load_dwordx[34] ", text(blocks[k]))) >= 4 and "offset:48" in text(blocks[k])), None)
+step_end = rec2 - 1 if rec2 else tail - 1  # the block that ends the first step
+pops = [k for k in range(push + 1, step_end) if all(w in text(blocks[k]) for w in ("ds_read_b64", "ds_read_b32", "v_max_f32"))]
+peeled = len(pops) == 2
 rows = [
     ("round head: which lanes descend; fetch of the 64-byte record", blocks[rec - 1][0], blocks[rec][1]),
     ("two quick box answers (box_quick.h)", blocks[quick][0], blocks[quick][1]),
@@ -60,9 +67,19 @@ rows = [
     ("push: decision + write of the entry to the LDS ring", blocks[faces + 1][0], blocks[spill][0]),
     ("  [rare] ring full: the oldest entry goes to global memory", blocks[spill][0], blocks[spill][1]),
     ("push: the two LDS writes", blocks[push][0], blocks[push][1]),
-    ("enter the lower child / go and pop: decision, new state from the ref", blocks[push + 1][0], blocks[tail - 1][1] if tail - 1 > push else blocks[push + 1][1]),
+    ("enter the lower child / go and pop: decision, new state from the ref", blocks[push + 1][0], blocks[step_end][1] if step_end > push else blocks[push + 1][1]),
+]
+if peeled:
+    rows += [
+        ("  of it: the pop's first trip, straight-line: empty? spilled? read, two tests, enter", blocks[pops[0] - 3][0], blocks[pops[0] + 2][1]),
+        ("  of it: the wave-uniform test of the lanes that need another trip", blocks[pops[0] + 3][0], blocks[pops[1]][0]),
+        ("  of it: the loop behind that test, one trip", blocks[pops[1]][0], blocks[pops[1] + 4][1]),
+    ]
+if rec2:
+    rows.append(("the round's second step: head, box answers, push, enter / go and pop", blocks[rec2 - 1][0], blocks[tail - 1][1]))
+rows += [
     ("round tail: ballots, leaf quorum, refill and thin-mode exits", blocks[tail - 1][0], blocks[leaf - 1][1]),
-    ("pop loop, one trip: stack empty? entry spilled? read pe / he / ref, test", blocks[pop][0], blocks[pop + 2][1]),
+    ("leaf step's pop, first trip straight-line" if peeled else "pop loop, one trip: stack empty? entry spilled? read pe / he / ref, test", blocks[pop][0], blocks[pop + 2][1]),
 ]
 print("k_trace<false, 38>: %s" % count(0, len(L)))
 for name, a, b in rows:

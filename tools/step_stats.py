@@ -46,7 +46,9 @@ for w in WORK:
     print("%s, %d passes through k_trace:" % (w, K))
     print("  box steps  %12d   lanes per box step  %5.1f of 64" % (box, box_lanes / max(1, box)))
     print("  leaf steps %12d   lanes per leaf step %5.1f of 64   (one leaf step per %.2f box steps)" % (leaf, leaf_lanes / max(1, leaf), box / max(1, leaf)))
-    print("  rounds     %12d   lanes holding a ray %5.1f of 64   refill episodes %d (one per %.1f rounds)" % (rounds, held / max(1, rounds), refills, rounds / max(1, refills)))
+    # (a round: GD_ROUND_STEPS box steps, then one pass through the tail; a box step is counted only if some lane takes part in it)
+    print("  rounds     %12d   lanes holding a ray %5.1f of 64   refill episodes %d (one per %.1f rounds)   %.2f box steps per round" % (
+        rounds, held / max(1, rounds), refills, rounds / max(1, refills), box / max(1, rounds)))
     print("  pops (trav_pop, all kernels of the run): %d wave-level calls with %.1f lanes each; the loop runs %.2f trips per call, %.1f lanes per trip" % (
         calls, call_lanes / max(1, calls), trips / max(1, calls), trip_lanes / max(1, trips)))
     print("  packet walks (GPUART_HIP_PACKET): box steps %d with %.1f active lanes of 64, leaf steps %d with %.1f" % (
