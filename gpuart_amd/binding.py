@@ -92,6 +92,7 @@ NEAREST_HIT = np.dtype([("dist", np.float32), ("q", np.float32, 3), ("d2", np.fl
 NEAREST_CHUNK = 64  # GPUART_NEAREST_CHUNK
 NEAREST_RING = 8    # GPUART_NEAREST_RING
 NEAREST_MAX_DEPTH = 1024  # GPUART_NEAREST_MAX_DEPTH
+NEAREST_KNN_MAX = 32  # GPUART_NEAREST_KNN_MAX
 
 
 def _params(cls, defaults, noun, params):
@@ -1381,6 +1382,43 @@ class Backend:
         h._chk(N.gpuart_nearest_run_host(h, C.byref(scene), _p(points), C.c_size_t(points.shape[0]), us, _p(hits)))
         return hits
 
+    def nearest_k(self, points, k, user_sphere=None, out=None):
+        """Per query (p.xyz, r) of points (n, 4) the k nearest primitives within r (1 <= k <= NEAREST_KNN_MAX), as include/gpuart_nearest.h
+        "k nearest" defines them: row i holds query i's candidates in ascending distance — equal distances by ordinal, the user sphere
+        (ordinal -2) last —, each the record `within` lists for that primitive, and misses (prim -1) behind the last one found. A NumPy
+        array runs through host memory (synchronous) and returns an (n, k) NEAREST_HIT array. A contiguous (n, 4) float32 tensor on this
+        context's device runs in place and returns an (n, k, 8) float32 tensor, written into `out` if given; streams, checks and refusals
+        as closest_points. k = 1 gives closest_points' records."""
+        N = nearest_lib()
+        us = _user_sphere(user_sphere)
+        k = int(k)
+        if not 1 <= k <= NEAREST_KNN_MAX:
+            raise ValueError("k must be in 1 .. %d" % NEAREST_KNN_MAX)
+        scene = self.scene_device()
+        h = self._nearest_handle(scene)
+        if type(points).__module__.startswith("torch"):
+            import torch
+            if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous() or points.device.type != "cuda":
+                raise ValueError("points must be a contiguous (n, 4) float32 tensor on the GPU")
+            index = points.device.index if points.device.index is not None else torch.cuda.current_device()
+            if index != self.device:
+                raise ValueError("points is on cuda:%d, this context on device %d: the kernel reads the tensor's memory in place" % (index, self.device))
+            n = points.shape[0]
+            hits = out if out is not None else torch.empty((n, k, 8), dtype=torch.float32, device=points.device)
+            if hits.dtype != torch.float32 or tuple(hits.shape) != (n, k, 8) or not hits.is_contiguous() or hits.device != points.device:
+                raise ValueError("out must be a contiguous (n, k, 8) float32 tensor on the points' device")
+            torch.cuda.current_stream(points.device).synchronize()
+            h._chk(N.gpuart_nearest_knn_run(h, C.byref(scene), C.c_void_p(points.data_ptr() if n else None), C.c_size_t(n), C.c_size_t(k), us,
+                                            C.c_void_p(hits.data_ptr() if n else None)))
+            h.finish()
+            return hits
+        if out is not None:
+            raise ValueError("out goes with device tensors")
+        points = _points_array(points)
+        hits = np.zeros((points.shape[0], k), NEAREST_HIT)
+        h._chk(N.gpuart_nearest_knn_run_host(h, C.byref(scene), _p(points), C.c_size_t(points.shape[0]), C.c_size_t(k), us, _p(hits)))
+        return hits
+
     def within(self, points, user_sphere=None, max_items=1 << 27, out=None):
         """Per query (p.xyz, r) of points (n, 4) the list of every primitive within r, as include/gpuart_nearest.h "Neighbour lists" defines
         it, in CSR form: (offsets, items), list i = items[offsets[i]:offsets[i + 1]] in the tree's order (the user sphere, ordinal -2,
@@ -1976,6 +2014,19 @@ class Renderer:
         if not self.L.gpuart_renderer_closest_points(self.h, _p(points), C.c_size_t(points.shape[0]), C.c_int(1 if user_sphere else 0), _p(hits)):
             raise HipError("closest_points refused or failed: Renderer::ClosestPoints says why on stderr (an empty scene and a tree with irregular "
                            "boxes are not queried)")
+        return hits
+
+    def nearest_primitives(self, points, k, user_sphere=True):
+        """Renderer::NearestPrimitives: points (n, 4) = p.xyz, r in host memory; user_sphere = include the renderer's current user sphere.
+        Returns an (n, k) NEAREST_HIT array: row i holds query i's k nearest in ascending distance, misses behind them."""
+        points = _points_array(points)
+        k = int(k)
+        if not 1 <= k <= NEAREST_KNN_MAX:
+            raise ValueError("k must be in 1 .. %d" % NEAREST_KNN_MAX)
+        hits = np.zeros((points.shape[0], k), NEAREST_HIT)
+        if not self.L.gpuart_renderer_nearest_primitives(self.h, _p(points), C.c_size_t(points.shape[0]), C.c_size_t(k), C.c_int(1 if user_sphere else 0), _p(hits)):
+            raise HipError("nearest_primitives refused or failed: Renderer::NearestPrimitives says why on stderr (an empty scene and a tree with "
+                           "irregular boxes are not queried)")
         return hits
 
     def primitives_within(self, points, with_user_sphere=True):

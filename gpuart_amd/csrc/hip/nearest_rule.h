@@ -185,4 +185,15 @@ NR_FN bool within_accept(float d2, float r2) { return d2 <= r2; }
 /// lemma b <= d2 of everything below the child, so b > r2 implies d2 > r2 for all of it: the walk loses no item.
 NR_FN bool within_pruned(float b, float r2) { return b > r2; }
 
+// ---- the k nearest: the first k of the accepted primitives in the order below (gpuart_nearest_knn_*) -----------------------------------
+/// Does the candidate (d2a, orda) come before (d2b, ordb) in an answer: nearer, or equally near with the lower ordinal — `better` without
+/// the acceptance. USER_SPHERE is above every tree ordinal, so the user sphere comes after every tree primitive of equal d2.
+NR_FN bool knn_before(float d2a, uint32_t orda, float d2b, uint32_t ordb) { return d2a < d2b || (d2a == d2b && orda < ordb); }
+
+/// Is the child whose box is at squared distance b skipped by a k-nearest walk: beyond the radius, or — only once k candidates are kept
+/// (`full`) — strictly beyond the d2 of the worst kept. The lemma's corollary, extended: b <= d2 of everything below the child, so
+/// b > worst_d2 puts all of it strictly behind every kept candidate, and what is kept later only comes before the worst of now: nothing
+/// pruned can precede anything in the answer. At b == worst_d2 a primitive of lower ordinal may lie below: the prune is strict.
+NR_FN bool knn_pruned(float b, float r2, bool full, float worst_d2) { return b > r2 || (full && b > worst_d2); }
+
 }  // namespace nearest_rule

@@ -379,6 +379,10 @@ int gpuart_renderer_closest_points(gpuart_renderer *r, const float *points, size
     return r->impl.ClosestPoints(points, n, withUserSphere != 0, hits) ? 1 : 0;
 }
 
+int gpuart_renderer_nearest_primitives(gpuart_renderer *r, const float *points, size_t n, size_t k, int withUserSphere, gpuart_nearest_hit *hits) {
+    return r->impl.NearestPrimitives(points, n, k, withUserSphere != 0, hits) ? 1 : 0;
+}
+
 int gpuart_renderer_primitives_within(gpuart_renderer *r, const float *points, size_t n, int withUserSphere, uint32_t *offsets,
                                       gpuart_nearest_hit *items, size_t capacity, uint64_t *total) {
     return r->impl.PrimitivesWithin(points, n, withUserSphere != 0, offsets, items, capacity, total) ? 1 : 0;

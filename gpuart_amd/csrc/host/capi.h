@@ -220,6 +220,9 @@ int gpuart_renderer_pick(gpuart_renderer *r, const uint32_t *xy, size_t n, int w
 /* Renderer::ClosestPoints (host memory, synchronous; 1 on success, 0 on refusal or error): points n x 4 floats {p.xyz, r}, hits n records
  * of include/gpuart_nearest.h; a hit's prim is the device ordinal, the position in the renderer's sorted list (-2: the user sphere). */
 int gpuart_renderer_closest_points(gpuart_renderer *r, const float *points, size_t n, int withUserSphere, gpuart_nearest_hit *hits);
+/* Renderer::NearestPrimitives (host memory, synchronous; 1 on success, 0 on refusal or error): points n x 4 floats {p.xyz, r}, hits n * k
+ * records, query i's k nearest at hits[i * k ..] in ascending distance, misses behind them; 1 <= k <= GPUART_NEAREST_KNN_MAX. */
+int gpuart_renderer_nearest_primitives(gpuart_renderer *r, const float *points, size_t n, size_t k, int withUserSphere, gpuart_nearest_hit *hits);
 /* Renderer::PrimitivesWithin (host memory, synchronous; 1 on success, 0 on refusal or error) by the two-call protocol of
  * gpuart_nearest_within_host: offsets[n + 1] and *total are always written; items (capacity records) only when it is not NULL and
  * capacity >= *total — call once with items = NULL to learn the total, then again with room for it. Ordinals as closest_points'. */

@@ -567,6 +567,15 @@ bool Renderer::ClosestPoints(const float *points, size_t n, bool withUserSphere,
     return Check(gpuart_nearest_run_host(Nearest, &scene, points, n, withUserSphere ? us : nullptr, hits), "querying closest points", gpuart_nearest_last_error);
 }
 
+bool Renderer::NearestPrimitives(const float *points, size_t n, size_t k, bool withUserSphere, gpuart_nearest_hit *hits) {
+    if (!IsOK || (n && (!points || !hits))) return false;
+    gpuart_hip_scene scene;
+    if (!BindNearest("NearestPrimitives", scene)) return false;
+    const float us[4] = {UserSphere.pos.x, UserSphere.pos.y, UserSphere.pos.z, UserSphere.radius};
+    return Check(gpuart_nearest_knn_run_host(Nearest, &scene, points, n, k, withUserSphere ? us : nullptr, hits), "querying the k nearest primitives",
+                 gpuart_nearest_last_error);
+}
+
 // ---- neighbour lists (include/gpuart_nearest.h, "Neighbour lists") ----------------------------------
 bool Renderer::PrimitivesWithin(const float *points, size_t n, bool withUserSphere, uint32_t *offsets, gpuart_nearest_hit *items, size_t capacity, uint64_t *total) {
     if (!IsOK || (n && !points) || !offsets || !total) return false;

@@ -329,6 +329,11 @@ public:
     /// is made by the first call and bound again after SetPrimitives, RebuildTree and EditPrimitives (a refit keeps the binding). False
     /// on refusal — an empty scene, a tree with irregular boxes — or error (std::cerr says why).
     bool ClosestPoints(const float *points, size_t n, bool withUserSphere, gpuart_nearest_hit *hits);
+    /// The k nearest primitives of each query (include/gpuart_nearest.h, "k nearest"; 1 <= k <= GPUART_NEAREST_KNN_MAX): hits[i * k + j] is the
+    /// j-th nearest of query i within its r, in ascending distance (equal distances by ordinal, the user sphere last), as the record a
+    /// neighbour list holds for that primitive; the slots behind the last one found are misses. The handle, its binding and the refusals
+    /// are ClosestPoints'. Synchronous; no image changes.
+    bool NearestPrimitives(const float *points, size_t n, size_t k, bool withUserSphere, gpuart_nearest_hit *hits);
     /// Neighbour lists (include/gpuart_nearest.h, "Neighbour lists"): per query every primitive within r, as CSR — list i is
     /// items[offsets[i] .. offsets[i + 1]), in the tree's order, the user sphere (ordinal -2) first. The ordinals are those ClosestPoints
     /// reports; the handle, its binding and the refusals are ClosestPoints'. Synchronous; no image changes.

@@ -5,14 +5,17 @@
 // k_within_count, rocPRIM's scan, k_within_fill. The three kernels differ in what a candidate does, in how a record's children are ordered
 // and in what ends a query; a lane's state, its stack, the leaf walk, the user sphere, a query's prologue and the persistent-lane loop are
 // stated once ("the walk: what the three kernels share") and compile to the kernels the written-out copies gave (profiles/nearest_walk.txt).
+// Behind them the k nearest of the same header: k_knn, a fourth lane type of that walk, whose best so far is a list of k in LDS (DESIGN.md
+// "k nearest", profiles/knn.txt).
 //
 // Compile-time switches (tools/nearest_time.py builds the variants; the shipped library sets none):
-//   NEAREST_PLAIN   the three kernels as one thread per query with a grid stride and no refill: the A/B partner of the persistent-lane form
-//   NEAREST_COUNT   box steps and primitive tests counted per query and summed (gpuart_nearest_counts, gpuart_nearest_within_counts): a
+//   NEAREST_PLAIN   the kernels as one thread per query with a grid stride and no refill: the A/B partner of the persistent-lane form
+//   NEAREST_COUNT   box steps and primitive tests counted per query and summed (gpuart_nearest_counts, _within_counts, _knn_counts): a
 //                   counting build, not a timed one
 //   NEAREST_REFILL  idle lanes of a wave at which it takes new queries (default 16)
 #include <rocprim/device/device_scan.hpp>
 
+#include <algorithm>
 #include <vector>
 
 #include "../image/image_lib.h"
@@ -51,6 +54,7 @@ struct Status {
     uint32_t pad;
     unsigned long long total;                      ///< of the last count: the items of all lists
     unsigned long long w_box_steps, w_prim_tests;  ///< NEAREST_COUNT
+    unsigned long long k_box_steps, k_prim_tests;  ///< NEAREST_COUNT: the k nearest (k_knn)
 };
 
 struct SceneView {
@@ -523,6 +527,266 @@ __global__ void __launch_bounds__(BLOCK) k_within_fill(WLaunch a) {
     within_body<true>(a, ring);
 }
 
+// ---- the k nearest: k_knn -----------------------------------------------------------------------------------------------------------------
+// The walk of k_nearest with the best so far replaced by the k best so far: the bound that prunes is the d2 of the worst of them, and only
+// once k are kept (nearest_rule.h: knn_pruned). What is kept is {d2, ordinal}, 8 bytes, in a column of LDS (entry j of a thread at
+// list[j * BLOCK + thread]: the bank is the thread's alone, whatever j) as a binary max-heap on the contract's order, the worst at the root
+// and its key in registers: a candidate is one compare against registers unless it is kept. At the end of a walk the heap is sorted in place
+// and each kept ordinal's point is computed a second time for its record — closest_on_prim is a function of its operands, so the record is
+// the one k_within_fill writes — which keeps 8 bytes per entry instead of 32.
+struct KnnLaunch {
+    SceneView sc;
+    const float4 *points;
+    uint32_t n;
+    float4 us;
+    uint32_t use_us;
+    uint32_t k;                ///< 1 .. the kernel's capacity
+    gpuart_nearest_hit *hits;  ///< n * k
+    uint2 *spill;
+    uint32_t cap;
+    uint32_t *cursor;
+    Status *status;
+};
+
+/// This thread's column of the kept lists of a kernel of capacity CAP: entry j at [j * BLOCK].
+template <uint32_t CAP>
+__device__ __forceinline__ uint2 *knn_list() {
+    __shared__ uint2 list[CAP * BLOCK];
+    return list + threadIdx.x;
+}
+
+/// A member of the launch's arguments, read from the kernel's argument segment where it is used (k_knn's only argument is the KnnLaunch, at
+/// offset 0 of the segment; the read is volatile, so it stays where it is written). The root box, the user sphere, points and hits are
+/// needed once or twice per query, in steps with registers to spare; as plain members of `a` the compiler loads them ahead of the lane
+/// loop and holds their fourteen words in scalar registers through the leaf step, where the kernel then has thirteen too few and spills.
+template <class T>
+__device__ __forceinline__ T launch_value(size_t offset) {
+    typedef const char __attribute__((address_space(4))) *Segment;
+    return *(const volatile T __attribute__((address_space(4))) *)((Segment)__builtin_amdgcn_kernarg_segment_ptr() + offset);
+}
+__device__ __forceinline__ float launch_word(size_t offset) { return launch_value<float>(offset); }
+/// A pointer member, with what the compiler knows of a kernel argument and cannot of a word it has read: that it points to global memory.
+template <class T>
+__device__ __forceinline__ T *launch_pointer(size_t offset) {
+    typedef T __attribute__((address_space(1))) *Global;
+    return (T *)(Global)launch_value<uintptr_t>(offset);
+}
+
+/// What a lane's `node` says before its walk and once it has ended — no tree's ref: leaves that begin at REF_INDEX, beyond every primitive.
+/// SPHERE_FIRST: the next step tests the user sphere and enters the root; WALKED: the next step sorts the kept and writes the misses behind
+/// them; WRITING: each further step writes one record, the lane's `sp` (the stack is empty) counting them. So the sort is stated once in
+/// the kernel and not at each of the four places where a walk can end, a record's point is computed where a candidate's is, by the same
+/// instructions — the kernel holds one closest_on_prim over the four types, as k_nearest does —, and the user sphere has one place.
+constexpr uint32_t WALKED = REF_LEAF | REF_INDEX, WRITING = REF_LEAF | REF_TWO | REF_INDEX, SPHERE_FIRST = REF_LEAF | REF_SMALL | REF_INDEX;
+
+template <uint32_t CAP>
+struct KLane : Walk {
+    uint32_t kept;       ///< entries of the list
+    float worst;         ///< the heap's root (the worst kept) while the list is full; else +inf and NO_PRIM
+    uint32_t worst_ord;
+};
+
+__device__ __forceinline__ bool before(const uint2 &x, const uint2 &y) { return nr::knn_before(__uint_as_float(x.x), x.y, __uint_as_float(y.x), y.y); }
+
+/// `e` takes the root's place in the heap of m entries and sinks to where both its children come before it. (An only child is read
+/// twice, as its own sibling: one loop with one way out, where a branch for it would nest another.)
+__device__ __forceinline__ void sift_down(uint2 *list, uint32_t m, uint2 e) {
+    uint32_t i = 0;
+    for (uint32_t c = 1u; c < m; c = 2u * i + 1u) {
+        const uint32_t c1 = min(c + 1u, m - 1u);
+        const uint2 h0 = list[c * BLOCK], h1 = list[c1 * BLOCK];
+        const bool second = before(h0, h1);
+        const uint2 hc = second ? h1 : h0;
+        if (!before(e, hc)) break;
+        list[i * BLOCK] = hc;
+        i = second ? c1 : c;
+    }
+    list[i * BLOCK] = e;
+}
+
+/// One candidate (d2, ord): kept if it is accepted and the list has room (it rises from the end: parents that come before it move down),
+/// or if it comes before the worst kept, which then leaves (it sinks from the root).
+template <uint32_t CAP>
+__device__ __forceinline__ void keep(KLane<CAP> &L, const KnnLaunch &a, float d2, uint32_t ord) {
+    uint2 *list = knn_list<CAP>();
+    const uint2 e = make_uint2(__float_as_uint(d2), ord);
+    const bool accepted = nr::within_accept(d2, L.r2), room = L.kept < a.k;
+    const bool rises = accepted && room, sinks = accepted && !room && nr::knn_before(d2, ord, L.worst, L.worst_ord);
+    if (rises) {
+        uint32_t i = L.kept++;
+        while (i) {
+            const uint32_t parent = (i - 1u) >> 1;
+            const uint2 hp = list[parent * BLOCK];
+            if (!before(hp, e)) break;
+            list[i * BLOCK] = hp;
+            i = parent;
+        }
+        list[i * BLOCK] = e;
+    }
+    if (sinks) sift_down(list, a.k, e);
+    if ((rises || sinks) && L.kept == a.k) {
+        const uint2 root = list[0];
+        L.worst = __uint_as_float(root.x);
+        L.worst_ord = root.y;
+    }
+}
+
+template <uint32_t CAP>
+__device__ __forceinline__ bool knn_skip(const KLane<CAP> &L, const KnnLaunch &a, float b) { return nr::knn_pruned(b, L.r2, L.kept == a.k, L.worst); }
+
+/// The walk has ended: the heap is sorted in place (the root goes behind the heap, which shrinks by one) and the miss record fills the
+/// slots behind the kept. With nothing kept the query is answered and the lane is idle; else the records follow, one a step.
+template <uint32_t CAP>
+__device__ __forceinline__ void sort_kept(KLane<CAP> &L, const KnnLaunch &a) {
+    uint2 *list = knn_list<CAP>();
+    for (uint32_t m = L.kept; m > 1u; m--) {
+        const uint2 root = list[0], last = list[(m - 1u) * BLOCK];
+        list[(m - 1u) * BLOCK] = root;
+        sift_down(list, m - 1u, last);
+    }
+    float4 *o = (float4 *)(launch_pointer<gpuart_nearest_hit>(offsetof(KnnLaunch, hits)) + (size_t)L.qi * a.k);
+    for (uint32_t j = L.kept; j < a.k; j++) {
+        o[2u * j] = make_float4(-1.0f, 0.0f, 0.0f, 0.0f);
+        o[2u * j + 1u] = make_float4(0.0f, __int_as_float(-1), __int_as_float(-1), 0.0f);
+    }
+#ifdef NEAREST_COUNT
+    atomicAdd(&a.status->k_box_steps, (unsigned long long)L.boxes);
+    atomicAdd(&a.status->k_prim_tests, (unsigned long long)L.tests);
+#endif
+    L.sp = 0;
+    if (L.kept) L.node = WRITING;
+    else L.qi = NONE;
+}
+
+/// The record of the kept entry L.sp, whose point and distance have just been computed again; behind the last one the lane is idle.
+template <uint32_t CAP>
+__device__ __forceinline__ void write_kept(KLane<CAP> &L, const KnnLaunch &a, uint32_t type, const float q[3], float d2, uint32_t ord) {
+    float4 *o = (float4 *)(launch_pointer<gpuart_nearest_hit>(offsetof(KnnLaunch, hits)) + ((size_t)L.qi * a.k + L.sp));
+    o[0] = make_float4(sqrtf(d2), q[0], q[1], q[2]);
+    o[1] = make_float4(d2, __uint_as_float(ord), __uint_as_float(type & 3u), 0.0f);
+    if (++L.sp == L.kept) {
+        L.sp = 0;
+        L.qi = NONE;
+    }
+}
+
+/// The next node off the stack that is not pruned by now, or the end of the walk.
+template <uint32_t CAP>
+__device__ __forceinline__ void next_node(KLane<CAP> &L, const Stack<uint2> &st, const KnnLaunch &a) {
+    for (;;) {
+        if (L.sp == 0) { L.node = WALKED; return; }
+        const uint2 e = st.pop(L);
+        if (!knn_skip(L, a, __uint_as_float(e.y))) { L.node = e.x; return; }
+    }
+}
+
+/// The walk begins at the root, unless the root is pruned already.
+template <uint32_t CAP>
+__device__ __forceinline__ void enter_root(KLane<CAP> &L, const KnnLaunch &a) {
+    float lo[3], hi[3];
+    for (int c = 0; c < 3; c++) {
+        lo[c] = launch_word(offsetof(KnnLaunch, sc.root_lo) + 4 * c);
+        hi[c] = launch_word(offsetof(KnnLaunch, sc.root_hi) + 4 * c);
+    }
+    L.node = knn_skip(L, a, nr::box_d2(lo, hi, L.p)) ? WALKED : a.sc.root_ref;
+}
+
+/// Query i begins: its walk has ended at once, or its first node is the user sphere, or the root.
+template <uint32_t CAP>
+__device__ __forceinline__ void begin(KLane<CAP> &L, const Stack<uint2> &, const KnnLaunch &a, uint32_t i) {
+    const float r = take_query(L, launch_pointer<const float4>(offsetof(KnnLaunch, points)), i);
+    L.kept = 0; L.worst = __builtin_inff(); L.worst_ord = nr::NO_PRIM;
+    if (!nr::query_ok(L.p, r)) L.node = WALKED;
+    else if (a.use_us) L.node = SPHERE_FIRST;
+    else enter_root(L, a);
+}
+
+/// One step of a lane: of its walk, as k_nearest's — a record (both boxes, the nearer child entered, the farther stacked with its distance)
+/// or a leaf —, or of its answer: the sort, or one record. A kept primitive's record goes through the leaf's code as a leaf of that one
+/// primitive; the user sphere's, which is no primitive of the scene, is written here.
+template <uint32_t CAP>
+__device__ __forceinline__ void step(KLane<CAP> &L, const Stack<uint2> &st, const KnnLaunch &a) {
+    uint32_t ref = L.node;
+    if (ref == WALKED) { sort_kept(L, a); return; }
+    const bool writing = ref == WRITING;
+    bool sphere = ref == SPHERE_FIRST;
+    if (writing) {
+        const uint32_t ord = knn_list<CAP>()[L.sp * BLOCK].y;
+        sphere = ord == nr::USER_SPHERE;
+        ref = REF_LEAF | REF_SMALL | ord;
+    }
+    if (sphere) {
+        PrimData d;
+        float q[3];
+        user_sphere_prim(launch_word(offsetof(KnnLaunch, us.x)), launch_word(offsetof(KnnLaunch, us.y)), launch_word(offsetof(KnnLaunch, us.z)),
+                         launch_word(offsetof(KnnLaunch, us.w)), d);
+        const float d2 = nr::closest_on_prim(nr::SPHERE, d.rec, d.box, L.p, q);
+        if (writing) {
+            write_kept(L, a, nr::SPHERE, q, d2, nr::USER_SPHERE);
+        } else {
+            keep(L, a, d2, nr::USER_SPHERE);
+#ifdef NEAREST_COUNT
+            L.tests++;
+#endif
+            enter_root(L, a);
+        }
+        return;
+    }
+    if (!(ref & REF_LEAF)) {
+        const float4 *rec = a.sc.recs + 4u * ref;
+        const float4 ra = rec[0], rb = rec[1], rc = rec[2], rd = rec[3];
+        float l0[3], h0[3], l1[3], h1[3];
+        xyz(ra, l0); xyz(rb, h0); xyz(rc, l1); xyz(rd, h1);
+        const float dlo = nr::box_d2(l0, h0, L.p), dhi = nr::box_d2(l1, h1, L.p);
+        const uint32_t rlo = __float_as_uint(ra.w), rhi = __float_as_uint(rb.w);
+        const bool klo = !knn_skip(L, a, dlo), khi = !knn_skip(L, a, dhi);
+#ifdef NEAREST_COUNT
+        L.boxes++;
+#endif
+        if (klo && khi) {
+            const bool upper_first = dhi < dlo;
+            st.push(L, make_uint2(upper_first ? rlo : rhi, __float_as_uint(upper_first ? dlo : dhi)));
+            L.node = upper_first ? rhi : rlo;
+        } else if (klo) L.node = rlo;
+        else if (khi) L.node = rhi;
+        else next_node(L, st, a);
+        return;
+    }
+    walk_leaf(a.sc, ref, [&](uint32_t type, const PrimData &d, uint32_t ord) {
+        float q[3];
+        const float d2 = nr::closest_on_prim(type, d.rec, d.box, L.p, q);
+        if (writing) {
+            write_kept(L, a, type, q, d2, ord);
+        } else {
+            keep(L, a, d2, ord);
+#ifdef NEAREST_COUNT
+            L.tests++;
+#endif
+        }
+    });
+    if (!writing) next_node(L, st, a);
+}
+
+// k_knn<CAP>: lists of up to CAP entries, CAP * 2 KiB of LDS per workgroup beside the ring's 16 KiB. The occupancy is the LDS's: the host
+// picks the smallest capacity that holds the call's k (knn_capacity) and sizes the grid per capacity.
+template <uint32_t CAP>
+__global__ void __launch_bounds__(BLOCK) k_knn(KnnLaunch a) {
+    __shared__ uint2 ring[RING * BLOCK];
+    const Stack<uint2> st(ring, a.spill, a.cap, a.status);
+    walk_queries<KLane<CAP>>(st, a);
+}
+
+constexpr uint32_t KNN_SIZES = 4;
+constexpr uint32_t KNN_CAPS[KNN_SIZES] = {4, 8, 16, GPUART_NEAREST_KNN_MAX};
+void (*const KNN_KERNELS[KNN_SIZES])(KnnLaunch) = {k_knn<4>, k_knn<8>, k_knn<16>, k_knn<GPUART_NEAREST_KNN_MAX>};
+
+/// The smallest capacity that holds lists of k entries (1 <= k <= GPUART_NEAREST_KNN_MAX), as an index of the two arrays above.
+uint32_t knn_capacity(uint32_t k) {
+    uint32_t s = 0;
+    while (KNN_CAPS[s] < k) s++;
+    return s;
+}
+
 }  // namespace
 
 struct gpuart_nearest : ImageHandle {
@@ -549,6 +813,10 @@ struct gpuart_nearest : ImageHandle {
     uint64_t last_total = 0;
     size_t counted_n = 0;        ///< the queries of the last count
     std::vector<uint32_t> host_offsets;  ///< within_host: a chunk's
+    // the k nearest
+    uint32_t knn_blocks[KNN_SIZES] = {0, 0, 0, 0};  ///< of k_knn per capacity: what the device holds at once
+    StepTimer kwalk;
+    bool kwalked = false;
 };
 
 namespace {
@@ -601,6 +869,17 @@ int check_run(gpuart_nearest *h, const gpuart_hip_scene *s, const void *points, 
     return 0;
 }
 
+/// What the runs of the k nearest check: k and n * k before what check_run checks of a run whose hits hold n * k records.
+int check_knn(gpuart_nearest *h, const gpuart_hip_scene *s, const void *points, size_t n, size_t k, const float us[4], const void *hits, size_t align) {
+    if (int rc = check_queries(h, s, n, us)) return rc;
+    if (k < 1 || k > GPUART_NEAREST_KNN_MAX) return fail(GPUART_HIP_ERR_ARG, "nearest: k is " + std::to_string(k) + ": not in 1 .. " + std::to_string(GPUART_NEAREST_KNN_MAX));
+    if (n * k > GPUART_HIP_MAX_RAYS) return fail(GPUART_HIP_ERR_ARG, "nearest: too many records: " + std::to_string(n) + " queries of k = " + std::to_string(k));
+    if (n && (!points || !hits)) return fail(GPUART_HIP_ERR_ARG, "nearest: points or hits is NULL");
+    if (misaligned({points, hits}, align)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned pointer (points and hits need " + std::to_string(align) + " bytes)");
+    if (n && overlaps(points, n * 16, hits, n * k * 32)) return fail(GPUART_HIP_ERR_ARG, "nearest: hits overlaps points");
+    return 0;
+}
+
 int check_within(gpuart_nearest *h, const gpuart_hip_scene *s, const void *points, size_t n, const float us[4], const void *offsets, size_t align) {
     if (int rc = check_queries(h, s, n, us)) return rc;
     if (n && (!points || !offsets)) return fail(GPUART_HIP_ERR_ARG, "nearest: points or offsets is NULL");
@@ -648,6 +927,25 @@ int launch(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, ui
     HIP_TRY(hipGetLastError());
     HIP_TRY(h->walk.mark());
     h->walked = true;
+    h->last_blocks = grid;
+    h->last_launches++;
+    return 0;
+}
+
+/// One launch of k_knn, of the capacity that holds k.
+int launch_knn(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, uint32_t n, uint32_t k, const float us[4], gpuart_nearest_hit *hits) {
+    KnnLaunch a{};
+    uint32_t grid;
+    const uint32_t size = knn_capacity(k);
+    if (int rc = prepare(h, s, points, n, us, std::min(h->max_blocks, h->knn_blocks[size]), a, grid)) return rc;
+    a.k = k;
+    a.hits = hits;
+    h->kwalk.start(h->stream);
+    HIP_TRY(h->kwalk.mark());
+    KNN_KERNELS[size]<<<grid, BLOCK, 0, h->stream>>>(a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(h->kwalk.mark());
+    h->kwalked = true;
     h->last_blocks = grid;
     h->last_launches++;
     return 0;
@@ -817,6 +1115,7 @@ int gpuart_nearest_create(int device, gpuart_nearest **out) {
         if (e == hipSuccess) e = h->walk.create(1);
         if (e == hipSuccess) e = h->wcount.create(2);
         if (e == hipSuccess) e = h->wfill.create(1);
+        if (e == hipSuccess) e = h->kwalk.create(1);
         return e;
     });
     if (rc) return rc;
@@ -829,6 +1128,10 @@ int gpuart_nearest_create(int device, gpuart_nearest **out) {
     h->within_blocks[0] = (uint32_t)per_cu * (uint32_t)cus;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_within_fill, BLOCK, 0) != hipSuccess || per_cu < 1) per_cu = 1;
     h->within_blocks[1] = (uint32_t)per_cu * (uint32_t)cus;
+    for (uint32_t k = 0; k < KNN_SIZES; k++) {  // (the lists' LDS sets it: 2 KiB per entry of the capacity beside the ring's 16 KiB)
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, KNN_KERNELS[k], BLOCK, 0) != hipSuccess || per_cu < 1) per_cu = 1;
+        h->knn_blocks[k] = (uint32_t)per_cu * (uint32_t)cus;
+    }
     return 0;
 }
 
@@ -839,6 +1142,7 @@ int gpuart_nearest_destroy(gpuart_nearest *h) {
     h->walk.destroy();
     h->wcount.destroy();
     h->wfill.destroy();
+    h->kwalk.destroy();
     delete h;
     return 0;
 }
@@ -1138,5 +1442,84 @@ int gpuart_nearest_within_step_ms(gpuart_nearest *h, double ms[3]) {
 }
 
 int gpuart_nearest_within_counts(gpuart_nearest *h, uint64_t out[2]) { return read_counts(h, &Status::w_box_steps, out); }
+
+// ---- the k nearest ----------------------------------------------------------------------------------------------------------------------
+int gpuart_nearest_knn_run(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, size_t n, size_t k, const float us[4], gpuart_nearest_hit *hits) {
+    if (int rc = check_knn(h, s, points, n, k, us, hits, 16)) return rc;
+    if (!n) return 0;
+    HIP_TRY(hipSetDevice(h->device));
+    h->last_launches = 0;
+    return launch_knn(h, s, points, (uint32_t)n, (uint32_t)k, us, hits);
+}
+
+int gpuart_nearest_knn_run_host(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, size_t n, size_t k, const float us[4], gpuart_nearest_hit *hits) {
+    if (int rc = check_knn(h, s, points, n, k, us, hits, 4)) return rc;
+    if (!n) return 0;
+    HIP_TRY(hipSetDevice(h->device));
+    // a chunk's records are no more than a chunk of gpuart_nearest_run_host holds: host_chunk / k queries, at least one
+    const size_t chunk = std::min(n, std::max<size_t>(1, h->host_chunk / k));
+    h->last_launches = 0;
+    if (int rc = ensure(h->stream, h->staging, chunk * (16 + 32 * k))) return rc;
+    float *dpoints = (float *)h->staging.mem;
+    gpuart_nearest_hit *dhits = (gpuart_nearest_hit *)((char *)h->staging.mem + chunk * 16);
+    for (size_t at = 0; at < n; at += chunk) {
+        const size_t m = std::min(chunk, n - at);
+        HIP_TRY(hipMemcpyAsync(dpoints, points + 4 * at, m * 16, hipMemcpyHostToDevice, h->stream));
+        if (int rc = launch_knn(h, s, dpoints, (uint32_t)m, (uint32_t)k, us, dhits)) return rc;
+        HIP_TRY(hipMemcpyAsync(hits + at * k, dhits, m * k * 32, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    return read_overflow(h);
+}
+
+int gpuart_nearest_knn_brute_host(gpuart_nearest *, const float *, size_t, const float *prims, const float *prim_boxes, size_t n_prims, const float *points, size_t n,
+                                  size_t k, const float us[4], gpuart_nearest_hit *hits) {
+    if ((n_prims && (!prims || !prim_boxes)) || (n && (!points || !hits))) return fail(GPUART_HIP_ERR_ARG, "nearest: prims, prim_boxes, points or hits is NULL");
+    if (n_prims > REF_INDEX) return fail(GPUART_HIP_ERR_ARG, "nearest: too many primitives: " + std::to_string(n_prims));
+    if (k < 1 || k > GPUART_NEAREST_KNN_MAX) return fail(GPUART_HIP_ERR_ARG, "nearest: k is " + std::to_string(k) + ": not in 1 .. " + std::to_string(GPUART_NEAREST_KNN_MAX));
+    if (int rc = check_user_sphere(us)) return rc;
+    std::vector<gpuart_nearest_hit> accepted;
+    for (size_t i = 0; i < n; i++) {
+        const float *p = points + 4 * i, r = p[3], r2 = r * r;
+        accepted.clear();
+        if (nr::query_ok(p, r)) {
+            float q[3];
+            for (size_t c = 0; c < n_prims + (us ? 1 : 0); c++) {  // every primitive, the user sphere behind them
+                PrimData d;
+                const bool sphere = c == n_prims;
+                if (sphere) {
+                    user_sphere_prim(us[0], us[1], us[2], us[3], d);
+                } else {
+                    memcpy(d.rec, prims + 12 * c, 48);
+                    memcpy(d.box, prim_boxes + 6 * c, 24);
+                }
+                uint32_t w;
+                memcpy(&w, d.rec + 3, 4);
+                const float d2 = nr::closest_on_prim(w & 3u, d.rec, d.box, p, q);
+                if (nr::within_accept(d2, r2))
+                    accepted.push_back(gpuart_nearest_hit{sqrtf(d2), {q[0], q[1], q[2]}, d2, (int32_t)(sphere ? nr::USER_SPHERE : (uint32_t)c), (int32_t)(w & 3u), 0});
+            }
+        }
+        const size_t found = std::min(k, accepted.size());
+        std::partial_sort(accepted.begin(), accepted.begin() + found, accepted.end(), [](const gpuart_nearest_hit &x, const gpuart_nearest_hit &y) {
+            return nr::knn_before(x.d2, (uint32_t)x.prim, y.d2, (uint32_t)y.prim);
+        });
+        for (size_t j = 0; j < k; j++) hits[i * k + j] = j < found ? accepted[j] : gpuart_nearest_hit{-1.0f, {0, 0, 0}, 0.0f, -1, -1, 0};
+    }
+    return 0;
+}
+
+int gpuart_nearest_knn_step_ms(gpuart_nearest *h, double ms[1]) {
+    if (int rc = check_handle(LIB, h)) return rc;
+    if (!ms) return fail(GPUART_HIP_ERR_ARG, "nearest: ms is NULL");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->kwalked)
+        if (int rc = h->kwalk.read()) return rc;
+    ms[0] = h->kwalk.ms[0];
+    return 0;
+}
+
+int gpuart_nearest_knn_counts(gpuart_nearest *h, uint64_t out[2]) { return read_counts(h, &Status::k_box_steps, out); }
 
 }  // extern "C"

@@ -168,6 +168,45 @@ int gpuart_nearest_within_step_ms(gpuart_nearest *h, double ms[3]);
 /* gpuart_nearest_counts for the walks of the lists, both passes. */
 int gpuart_nearest_within_counts(gpuart_nearest *h, uint64_t out[2]);
 
+/* ---- k nearest: the k nearest primitives of a point (DESIGN.md "k nearest"; tests/knn_ref.py restates this) ---------------------------
+ *   query       (p, r), exactly as above, and one k per call, 1 <= k <= GPUART_NEAREST_KNN_MAX;
+ *   candidates  every primitive whose d2 = dist2(p, closest_on_prim(..)) satisfies d2 <= r*r (fp32 product, <=), and with a user sphere
+ *               the sphere, ordinal -2, under the same acceptance. An invalid query (r NaN or negative, a word of p that is not finite)
+ *               has no candidates;
+ *   order       ascending d2 (fp32 compare); equal d2: tree primitives by ascending device ordinal, and the user sphere — as the uint32
+ *               0xfffffffe above every ordinal — behind every tree primitive of equal d2 (nearest_rule.h: knn_before);
+ *   answer      hits[i * k + j], j = 0 .. k - 1, is the j-th candidate of query i in that order: bit for bit the record the neighbour
+ *               list holds for that primitive — sqrtf(d2), q, d2, the ordinal, the type, 0. Slots past the number of candidates hold the
+ *               miss record: dist = -1, q = 0, d2 = 0, prim = -1, type = -1, 0. For k = 1 the output is gpuart_nearest_run's byte for byte;
+ *   walk        a child — and the root — is skipped if and only if the squared distance of p to its box is > r*r, or k candidates are kept
+ *               and it is > the d2 of the worst kept, strictly (nearest_rule.h: knn_pruned). While fewer than k are kept only the radius
+ *               prunes. By the lemma that distance is <= the d2 of everything below the child: what is skipped comes strictly behind every
+ *               kept candidate, and the kept only ever improve, so the walk returns the brute force's records in any child order; at
+ *               equality a primitive of lower ordinal may lie below, which is why the prune is strict. The kernel enters the nearer child
+ *               first.
+ * One walk per query and a fixed-size answer: no count, no scan, no second pass. A bound handle as gpuart_nearest_run needs it, the same
+ * refusals with nothing written, and gpuart_nearest_set_limits applies (max_blocks, the spill budget, host_chunk). */
+#define GPUART_NEAREST_KNN_MAX 32u /* the most k: a lane's kept list lives in LDS, 8 bytes per entry */
+
+/* points: n x 4 floats; hits: n * k records — device memory, 16-byte aligned, asynchronous on the handle's stream; gpuart_nearest_finish
+ * reports a full stack as for gpuart_nearest_run. GPUART_HIP_ERR_ARG, with nothing written, for k = 0 or k > GPUART_NEAREST_KNN_MAX,
+ * n * k > GPUART_HIP_MAX_RAYS, hits overlapping points and everything gpuart_nearest_run refuses; n = 0 does nothing. */
+int gpuart_nearest_knn_run(gpuart_nearest *h, const gpuart_hip_scene *scene, const float *points, size_t n, size_t k, const float userSphere[4],
+                           gpuart_nearest_hit *hits);
+/* The same in host memory (4-byte alignment), synchronous, staged through the handle's memory in chunks of host_chunk / k queries (at
+ * least one), so that a chunk's records are no more than a chunk of gpuart_nearest_run_host holds. */
+int gpuart_nearest_knn_run_host(gpuart_nearest *h, const gpuart_hip_scene *scene, const float *points, size_t n, size_t k, const float userSphere[4],
+                                gpuart_nearest_hit *hits);
+/* The definition itself, with no device: every primitive tested, the accepted sorted; arguments as gpuart_nearest_brute_host (recs is
+ * ignored, h may be NULL). GPUART_HIP_ERR_ARG for NULL pointers where the matching count is above zero and for k = 0 or
+ * k > GPUART_NEAREST_KNN_MAX. */
+int gpuart_nearest_knn_brute_host(gpuart_nearest *h, const float *recs, size_t n_recs, const float *prims, const float *prim_boxes, size_t n_prims,
+                                  const float *points, size_t n, size_t k, const float userSphere[4], gpuart_nearest_hit *hits);
+/* Device time in ms of the last k-nearest walk. */
+int gpuart_nearest_knn_step_ms(gpuart_nearest *h, double ms[1]);
+/* gpuart_nearest_counts for the k-nearest walks. */
+int gpuart_nearest_knn_counts(gpuart_nearest *h, uint64_t out[2]);
+
 #ifdef __cplusplus
 }
 #endif
