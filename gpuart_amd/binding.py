@@ -1487,6 +1487,132 @@ class Backend:
             h._chk(N.gpuart_nearest_within_fill_host(*args, _p(items), C.c_size_t(total.value)))
         return offsets, items
 
+    def _overlap_device(self, N, h, scene, n, max_items, out, device, count, fill):
+        """The device route of overlaps and overlapping_pairs: count(offsets_ptr), the 8-byte total, fill(offsets_ptr, items_ptr, capacity),
+        with the tensors and checks of `within` (items: int32 (total,))."""
+        import torch
+        total = C.c_uint64(0)
+        offsets, items = out if out is not None else (None, None)
+        if offsets is None:
+            offsets = torch.zeros((n + 1,), dtype=torch.int32, device=device)
+        if offsets.dtype != torch.int32 or tuple(offsets.shape) != (n + 1,) or not offsets.is_contiguous() or offsets.device != device:
+            raise ValueError("out[0] must be a contiguous (n + 1,) int32 tensor on the context's device")
+        if items is not None and (items.dtype != torch.int32 or items.dim() != 1 or not items.is_contiguous() or items.device != device):
+            raise ValueError("out[1] must be a contiguous (capacity,) int32 tensor on the context's device")
+        torch.cuda.current_stream(device).synchronize()
+        if n == 0:
+            offsets.zero_()
+            return offsets, items if items is not None else torch.empty((0,), dtype=torch.int32, device=device)
+        h._chk(count(C.c_void_p(offsets.data_ptr())))
+        rc = N.gpuart_nearest_overlap_total(h, C.byref(total))
+        if total.value > max_items:
+            raise ValueError("the lists hold %d items, more than max_items = %d" % (total.value, max_items))
+        h._chk(rc)
+        if items is None:
+            items = torch.empty((total.value,), dtype=torch.int32, device=device)
+        elif items.shape[0] < total.value:
+            raise ValueError("out[1] has room for %d items, the lists hold %d" % (items.shape[0], total.value))
+        cap = items.shape[0]
+        h._chk(fill(C.c_void_p(offsets.data_ptr()), C.c_void_p(items.data_ptr() if cap else None), C.c_size_t(cap)))
+        h.finish()
+        return offsets, items
+
+    @staticmethod
+    def _margin(margin):
+        margin = float(np.float32(margin))
+        if not (0.0 <= margin < float("inf")):
+            raise ValueError("margin must be finite and not negative")
+        return margin
+
+    def overlaps(self, boxes, margin=0.0, user_sphere=None, max_items=1 << 27, out=None):
+        """Per query box (lo.xyz, hi.xyz) of boxes (n, 6), inflated by `margin` on every side, the ordinals of every primitive whose own box
+        meets it, as include/gpuart_nearest.h "Box overlap" defines them, in CSR form: (offsets, items), list i =
+        items[offsets[i]:offsets[i + 1]] in the tree's order (the user sphere, ordinal -2, first). A NumPy array runs through host memory
+        (synchronous) and returns (offsets uint32 (n + 1,), items int32 (total,)). A contiguous (n, 6) float32 tensor on this context's
+        device runs in place and returns int32 tensors, written into out = (offsets, items) if given; streams, max_items and refusals as
+        `within`. A margin that is NaN, infinite or negative raises ValueError."""
+        N = nearest_lib()
+        us = _user_sphere(user_sphere)
+        margin = self._margin(margin)
+        max_items = int(max_items)
+        if max_items < 0:
+            raise ValueError("max_items is negative")
+        scene = self.scene_device()
+        h = self._nearest_handle(scene)
+        m = C.c_float(margin)
+        if type(boxes).__module__.startswith("torch"):
+            import torch
+            if boxes.dtype != torch.float32 or boxes.dim() != 2 or boxes.shape[1] != 6 or not boxes.is_contiguous() or boxes.device.type != "cuda":
+                raise ValueError("boxes must be a contiguous (n, 6) float32 tensor on the GPU")
+            index = boxes.device.index if boxes.device.index is not None else torch.cuda.current_device()
+            if index != self.device:
+                raise ValueError("boxes is on cuda:%d, this context on device %d: the kernel reads the tensor's memory in place" % (index, self.device))
+            n = boxes.shape[0]
+            ptr = C.c_void_p(boxes.data_ptr() if n else None)
+            return self._overlap_device(N, h, scene, n, max_items, out, boxes.device,
+                                        lambda o: N.gpuart_nearest_overlap_count(h, C.byref(scene), ptr, C.c_size_t(n), m, us, o),
+                                        lambda o, it, cap: N.gpuart_nearest_overlap_fill(h, C.byref(scene), ptr, C.c_size_t(n), m, us, o, it, cap))
+        if out is not None:
+            raise ValueError("out goes with device tensors")
+        boxes = np.ascontiguousarray(boxes, np.float32)
+        if boxes.ndim != 2 or boxes.shape[1] != 6:
+            raise ValueError("boxes must be (n, 6): lo.xyz, hi.xyz")
+        n = boxes.shape[0]
+        offsets = np.zeros(n + 1, np.uint32)
+        total = C.c_uint64(0)
+        args = (h, C.byref(scene), _p(boxes), C.c_size_t(n), m, us, _p(offsets))
+        rc = N.gpuart_nearest_overlap_host(*args, None, C.c_size_t(0), C.byref(total))
+        if total.value > max_items:
+            raise ValueError("the lists hold %d items, more than max_items = %d" % (total.value, max_items))
+        h._chk(rc)
+        items = np.zeros(total.value, np.int32)
+        if total.value:     # (the fill alone: the offsets are the count's of a moment ago)
+            h._chk(N.gpuart_nearest_overlap_fill_host(*args, _p(items), C.c_size_t(total.value)))
+        return offsets, items
+
+    def overlapping_pairs(self, margin=0.0, max_items=1 << 27, device=False, out=None, as_pairs=False):
+        """The overlapping pairs of the scene's own primitives (include/gpuart_nearest.h "Box overlap", pairs): list i holds the ordinals
+        j > i whose box meets primitive i's box inflated by `margin`, in the tree's order; nothing is uploaded. Returns (offsets uint32
+        (n_prims + 1,), items int32 (total,)) as NumPy arrays, or with device=True int32 tensors on the context's device (written into
+        out = (offsets, items) if given; only the 8-byte total crosses the host). as_pairs=True returns instead the (total, 2) int32
+        array or tensor of (i, j), i < j, expanded from the CSR. Adjacent triangles of a mesh share vertices and always overlap:
+        filtering topological neighbours is the caller's."""
+        N = nearest_lib()
+        margin = self._margin(margin)
+        max_items = int(max_items)
+        if max_items < 0:
+            raise ValueError("max_items is negative")
+        scene = self.scene_device()
+        h = self._nearest_handle(scene)
+        m = C.c_float(margin)
+        n = int(scene.n_prims)
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            offsets, items = self._overlap_device(N, h, scene, n, max_items, out, dev,
+                                                  lambda o: N.gpuart_nearest_pairs_count(h, C.byref(scene), m, o),
+                                                  lambda o, it, cap: N.gpuart_nearest_pairs_fill(h, C.byref(scene), m, o, it, cap))
+            if not as_pairs:
+                return offsets, items
+            total = int(offsets[-1].item())
+            i = torch.repeat_interleave(torch.arange(n, dtype=torch.int32, device=dev), torch.diff(offsets).to(torch.int64), output_size=total)
+            return torch.stack([i, items[:total]], 1)
+        if out is not None:
+            raise ValueError("out goes with device=True")
+        offsets = np.zeros(n + 1, np.uint32)
+        total = C.c_uint64(0)
+        rc = N.gpuart_nearest_pairs_host(h, C.byref(scene), m, _p(offsets), None, C.c_size_t(0), C.byref(total))
+        if total.value > max_items:
+            raise ValueError("the lists hold %d items, more than max_items = %d" % (total.value, max_items))
+        h._chk(rc)
+        items = np.zeros(total.value, np.int32)
+        if total.value:
+            h._chk(N.gpuart_nearest_pairs_host(h, C.byref(scene), m, _p(offsets), _p(items), C.c_size_t(total.value), C.byref(total)))
+        if not as_pairs:
+            return offsets, items
+        i = np.repeat(np.arange(n, dtype=np.int32), np.diff(offsets.astype(np.int64)))
+        return np.stack([i, items], 1).reshape(-1, 2)
+
     def pick(self, xy, user_sphere=None, want_prims=False):
         """Closest hit of the camera rays of frame pixels xy (n, 2) = (x, y), row 0 = bottom, any pixel of the frame: a RAY_HIT record
         array (and the primitive ordinals)."""
@@ -2044,6 +2170,40 @@ class Renderer:
         if not ok:
             raise HipError("primitives_within refused or failed: Renderer::PrimitivesWithin says why on stderr (an empty scene and a tree with "
                            "irregular boxes are not queried)")
+        return offsets, items
+
+    def primitives_overlapping(self, boxes, margin=0.0, with_user_sphere=True):
+        """Renderer::PrimitivesOverlapping: boxes (n, 6) = lo.xyz, hi.xyz in host memory, inflated by margin -> (offsets uint32 (n + 1,),
+        items int32 (total,)), list i = items[offsets[i]:offsets[i + 1]]; ordinals as closest_points reports them."""
+        boxes = np.ascontiguousarray(boxes, np.float32)
+        if boxes.ndim != 2 or boxes.shape[1] != 6:
+            raise ValueError("boxes must be (n, 6): lo.xyz, hi.xyz")
+        n = boxes.shape[0]
+        offsets = np.zeros(n + 1, np.uint32)
+        total = C.c_uint64(0)
+        us, m = C.c_int(1 if with_user_sphere else 0), C.c_float(float(margin))
+        ok = self.L.gpuart_renderer_primitives_overlapping(self.h, _p(boxes), C.c_size_t(n), m, us, _p(offsets), None, C.c_size_t(0), C.byref(total))
+        items = np.zeros(total.value if ok else 0, np.int32)
+        if ok and total.value:
+            ok = self.L.gpuart_renderer_primitives_overlapping_fill(self.h, _p(boxes), C.c_size_t(n), m, us, _p(offsets), _p(items), C.c_size_t(len(items)))
+        if not ok:
+            raise HipError("primitives_overlapping refused or failed: Renderer::PrimitivesOverlapping says why on stderr (an empty scene, a tree "
+                           "with irregular boxes and a margin that is NaN, infinite or negative are refused)")
+        return offsets, items
+
+    def overlapping_pairs(self, margin=0.0):
+        """Renderer::OverlappingPairs: (offsets uint32 (n_prims + 1,), items int32 (total,)): list i holds the ordinals j > i whose box meets
+        primitive i's box inflated by margin."""
+        n = int(self.backend.scene_device().n_prims)
+        offsets = np.zeros(n + 1, np.uint32)
+        total = C.c_uint64(0)
+        m = C.c_float(float(margin))
+        ok = self.L.gpuart_renderer_overlapping_pairs(self.h, m, _p(offsets), None, C.c_size_t(0), C.byref(total))
+        items = np.zeros(total.value if ok else 0, np.int32)
+        if ok and total.value:
+            ok = self.L.gpuart_renderer_overlapping_pairs(self.h, m, _p(offsets), _p(items), C.c_size_t(len(items)), C.byref(total))
+        if not ok:
+            raise HipError("overlapping_pairs refused or failed: Renderer::OverlappingPairs says why on stderr")
         return offsets, items
 
     def last_setprims_ms(self):

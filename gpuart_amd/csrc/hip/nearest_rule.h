@@ -185,6 +185,44 @@ NR_FN bool within_accept(float d2, float r2) { return d2 <= r2; }
 /// lemma b <= d2 of everything below the child, so b > r2 implies d2 > r2 for all of it: the walk loses no item.
 NR_FN bool within_pruned(float b, float r2) { return b > r2; }
 
+// ---- box overlap: every primitive whose box meets a query box (gpuart_nearest_overlap_*, gpuart_nearest_pairs_*) ------------------------
+// The query is a box [lo, hi] and one margin m >= 0 per call; what is tested is the INFLATED box qlo = fl(lo - m), qhi = fl(hi + m), each
+// component one fp32 operation (an overflow to -+inf is allowed: such a side reaches everything). A primitive is an item if and only if
+// its own box [blo, bhi] (prim_boxes) satisfies qlo <= bhi && blo <= qhi on all three axes: touching counts. Comparisons of stored
+// numbers only: nothing rounds behind the two subtractions and additions that made q.
+//   THE LEMMA of the overlap walk. If b = [blo, bhi] lies inside B = [Blo, Bhi] (Blo <= blo, bhi <= Bhi: what gpuart_nearest_bind checks
+//   of every child and every leaf's primitives) and q overlaps b, then q overlaps B: qlo <= bhi <= Bhi and Blo <= blo <= qhi, per axis.
+//   So a walk that skips a child — or the root — exactly when its box fails overlap_test against the same (qlo, qhi) loses no item.
+//   The margin is on the QUERY's side, once: in fp32 fl(lo_i - m) <= hi_j and lo_i <= fl(hi_j + m) can disagree (lo_i = 1,
+//   hi_j = 1 - 2^-24, m = 2^-25: false and true), so for pairs the contract says whose box is inflated — the lower ordinal's.
+/// Is m a margin: neither NaN nor negative nor infinite.
+NR_FN bool overlap_margin_ok(float m) { return m >= 0.0f && m < INFINITY; }
+
+/// Is box (lo.xyz, hi.xyz) a query at all: six finite words, lo <= hi on every axis (tree_rule::box_ok, written out: a NaN fails).
+NR_FN bool overlap_query_ok(const float box[6]) {
+    bool ok = true;
+    for (int k = 0; k < 3; k++) ok = ok && box[k] <= box[3 + k] && fabsf(box[k]) < INFINITY && fabsf(box[3 + k]) < INFINITY;
+    return ok;
+}
+
+/// The inflated query: qlo = lo - m, qhi = hi + m.
+NR_FN void overlap_inflate(const float box[6], float m, float qlo[3], float qhi[3]) {
+    for (int k = 0; k < 3; k++) {
+        qlo[k] = box[k] - m;
+        qhi[k] = box[3 + k] + m;
+    }
+}
+
+/// Does the inflated query (qlo, qhi) meet the box (blo, bhi): the item test, and — negated — the walk's prune.
+NR_FN bool overlap_test(const float qlo[3], const float qhi[3], const float blo[3], const float bhi[3]) {
+    bool ok = true;
+    for (int k = 0; k < 3; k++) ok = ok && qlo[k] <= bhi[k] && blo[k] <= qhi[k];
+    return ok;
+}
+
+/// Is primitive j an item of the pair list of primitive i: strictly above it, so a pair {i, j} appears once, in the lower ordinal's list.
+NR_FN bool pairs_keep(uint32_t i, uint32_t j) { return j > i; }
+
 // ---- the k nearest: the first k of the accepted primitives in the order below (gpuart_nearest_knn_*) -----------------------------------
 /// Does the candidate (d2a, orda) come before (d2b, ordb) in an answer: nearer, or equally near with the lower ordinal — `better` without
 /// the acceptance. USER_SPHERE is above every tree ordinal, so the user sphere comes after every tree primitive of equal d2.

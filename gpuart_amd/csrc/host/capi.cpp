@@ -392,6 +392,21 @@ int gpuart_renderer_primitives_within_fill(gpuart_renderer *r, const float *poin
                                            gpuart_nearest_hit *items, size_t capacity) {
     return r->impl.FillPrimitivesWithin(points, n, withUserSphere != 0, offsets, items, capacity) ? 1 : 0;
 }
+
+int gpuart_renderer_primitives_overlapping(gpuart_renderer *r, const float *boxes, size_t n, float margin, int withUserSphere, uint32_t *offsets,
+                                           int32_t *items, size_t capacity, uint64_t *total) {
+    return r->impl.PrimitivesOverlapping(boxes, n, margin, withUserSphere != 0, offsets, items, capacity, total) ? 1 : 0;
+}
+
+int gpuart_renderer_primitives_overlapping_fill(gpuart_renderer *r, const float *boxes, size_t n, float margin, int withUserSphere, const uint32_t *offsets,
+                                                int32_t *items, size_t capacity) {
+    return r->impl.FillPrimitivesOverlapping(boxes, n, margin, withUserSphere != 0, offsets, items, capacity) ? 1 : 0;
+}
+
+int gpuart_renderer_overlapping_pairs(gpuart_renderer *r, float margin, uint32_t *offsets, int32_t *items, size_t capacity, uint64_t *total) {
+    return r->impl.OverlappingPairs(margin, offsets, items, capacity, total) ? 1 : 0;
+}
+
 int gpuart_renderer_set_camera(gpuart_renderer *r, const float pos[3], const float dir[3], const float up[3], float fovY,
                                float screenDist) {
     return r->impl.SetCamera(make_camera(pos, dir, up, fovY, screenDist)) ? 1 : 0;

@@ -232,6 +232,18 @@ int gpuart_renderer_primitives_within(gpuart_renderer *r, const float *points, s
  * wrote, so the queries are walked twice in all and not three times. */
 int gpuart_renderer_primitives_within_fill(gpuart_renderer *r, const float *points, size_t n, int withUserSphere, const uint32_t *offsets,
                                            gpuart_nearest_hit *items, size_t capacity);
+/* Renderer::PrimitivesOverlapping (host memory, synchronous; 1 on success, 0 on refusal or error) by the two-call protocol of
+ * gpuart_nearest_overlap_host: boxes n x 6 floats {lo.xyz, hi.xyz}, one margin; offsets[n + 1] and *total are always written; items
+ * (capacity ordinals) only when it is not NULL and capacity >= *total. Ordinals as closest_points'. */
+int gpuart_renderer_primitives_overlapping(gpuart_renderer *r, const float *boxes, size_t n, float margin, int withUserSphere, uint32_t *offsets,
+                                           int32_t *items, size_t capacity, uint64_t *total);
+/* The second call without its count: Renderer::FillPrimitivesOverlapping fills items (capacity >= offsets[n]) for the offsets the first
+ * call wrote. */
+int gpuart_renderer_primitives_overlapping_fill(gpuart_renderer *r, const float *boxes, size_t n, float margin, int withUserSphere, const uint32_t *offsets,
+                                                int32_t *items, size_t capacity);
+/* Renderer::OverlappingPairs by the same two-call protocol: offsets has n_prims + 1 words; list i holds the ordinals j > i whose box meets
+ * primitive i's box inflated by margin. */
+int gpuart_renderer_overlapping_pairs(gpuart_renderer *r, float margin, uint32_t *offsets, int32_t *items, size_t capacity, uint64_t *total);
 gpuart_hip_ctx *gpuart_renderer_backend(gpuart_renderer *r);
 void gpuart_renderer_params(gpuart_renderer *r, gpuart_params *out);
 /* What the renderer's last SetPrimitives spent inside the library, ms: whole call, BVH build, compilation, re-layout + upload. */

@@ -605,6 +605,52 @@ bool Renderer::FillPrimitivesWithin(const float *points, size_t n, bool withUser
                  "filling the lists of the primitives within a radius", gpuart_nearest_last_error);
 }
 
+// ---- box overlap (include/gpuart_nearest.h, "Box overlap") --------------------------------------------
+bool Renderer::PrimitivesOverlapping(const float *boxes, size_t n, float margin, bool withUserSphere, uint32_t *offsets, int32_t *items, size_t capacity, uint64_t *total) {
+    if (!IsOK || (n && !boxes) || !offsets || !total) return false;
+    gpuart_hip_scene scene;
+    if (!BindNearest("PrimitivesOverlapping", scene)) return false;
+    const float us[4] = {UserSphere.pos.x, UserSphere.pos.y, UserSphere.pos.z, UserSphere.radius};
+    return Check(gpuart_nearest_overlap_host(Nearest, &scene, boxes, n, margin, withUserSphere ? us : nullptr, offsets, items, capacity, total),
+                 "listing the primitives that overlap a box", gpuart_nearest_last_error);
+}
+
+bool Renderer::PrimitivesOverlapping(const float *boxes, size_t n, float margin, bool withUserSphere, std::vector<uint32_t> &offsets, std::vector<int32_t> &items) {
+    offsets.assign(n + 1, 0u);
+    items.clear();
+    uint64_t total = 0;
+    if (!PrimitivesOverlapping(boxes, n, margin, withUserSphere, offsets.data(), nullptr, 0, &total)) return false;
+    if (!total) return true;
+    items.resize(total);
+    return FillPrimitivesOverlapping(boxes, n, margin, withUserSphere, offsets.data(), items.data(), items.size());
+}
+
+bool Renderer::FillPrimitivesOverlapping(const float *boxes, size_t n, float margin, bool withUserSphere, const uint32_t *offsets, int32_t *items, size_t capacity) {
+    if (!IsOK || (n && !boxes) || !offsets) return false;
+    gpuart_hip_scene scene;
+    if (!BindNearest("PrimitivesOverlapping", scene)) return false;
+    const float us[4] = {UserSphere.pos.x, UserSphere.pos.y, UserSphere.pos.z, UserSphere.radius};
+    return Check(gpuart_nearest_overlap_fill_host(Nearest, &scene, boxes, n, margin, withUserSphere ? us : nullptr, offsets, items, capacity),
+                 "filling the lists of the primitives that overlap a box", gpuart_nearest_last_error);
+}
+
+bool Renderer::OverlappingPairs(float margin, uint32_t *offsets, int32_t *items, size_t capacity, uint64_t *total) {
+    if (!IsOK || !offsets || !total) return false;
+    gpuart_hip_scene scene;
+    if (!BindNearest("OverlappingPairs", scene)) return false;
+    return Check(gpuart_nearest_pairs_host(Nearest, &scene, margin, offsets, items, capacity, total), "listing the overlapping pairs", gpuart_nearest_last_error);
+}
+
+bool Renderer::OverlappingPairs(float margin, std::vector<uint32_t> &offsets, std::vector<int32_t> &items) {
+    offsets.assign((size_t)Tree.GetNumPrimitives() + 1, 0u);
+    items.clear();
+    uint64_t total = 0;
+    if (!OverlappingPairs(margin, offsets.data(), nullptr, 0, &total)) return false;
+    if (!total) return true;
+    items.resize(total);
+    return OverlappingPairs(margin, offsets.data(), items.data(), items.size(), &total);
+}
+
 // ---- lighting / user sphere ---------------------------------------------------------------------
 void Renderer::SetUserSphere(const Vec3f &pos, float radius, float emittance) {
     UserSphere.pos = pos;

@@ -344,6 +344,21 @@ public:
     /// The fill alone, for the offsets a call with items = NULL has just written (gpuart_nearest_within_fill_host): the second step of the
     /// vector form above, which so walks the queries twice and not three times.
     bool FillPrimitivesWithin(const float *points, size_t n, bool withUserSphere, const uint32_t *offsets, gpuart_nearest_hit *items, size_t capacity);
+    /// Box overlap (include/gpuart_nearest.h, "Box overlap"): `boxes` = n x 6 floats {lo.xyz, hi.xyz} in host memory; per query, inflated by
+    /// `margin` on every side, the ordinals of every primitive whose own box meets it, as CSR — list i is items[offsets[i] .. offsets[i + 1]),
+    /// in the tree's order, the user sphere (ordinal -2) first. The ordinals are those ClosestPoints reports; the handle, its binding and the
+    /// refusals are ClosestPoints'. Synchronous; no image changes.
+    bool PrimitivesOverlapping(const float *boxes, size_t n, float margin, bool withUserSphere, std::vector<uint32_t> &offsets, std::vector<int32_t> &items);
+    /// The same by the two-call protocol of gpuart_nearest_overlap_host: offsets[n + 1] and *total are always written, items only when it
+    /// is not NULL and `capacity` ordinals hold the total.
+    bool PrimitivesOverlapping(const float *boxes, size_t n, float margin, bool withUserSphere, uint32_t *offsets, int32_t *items, size_t capacity, uint64_t *total);
+    /// The fill alone, for the offsets a call with items = NULL has just written (gpuart_nearest_overlap_fill_host).
+    bool FillPrimitivesOverlapping(const float *boxes, size_t n, float margin, bool withUserSphere, const uint32_t *offsets, int32_t *items, size_t capacity);
+    /// The overlapping pairs of the scene's own primitives at `margin` (gpuart_nearest_pairs_host): list i holds the ordinals j > i whose box
+    /// meets primitive i's inflated box; offsets has GetNumPrimitives() + 1 words. Adjacent triangles of a mesh always overlap: filtering
+    /// topological neighbours is the caller's. The vector form, and the two-call protocol as above.
+    bool OverlappingPairs(float margin, std::vector<uint32_t> &offsets, std::vector<int32_t> &items);
+    bool OverlappingPairs(float margin, uint32_t *offsets, int32_t *items, size_t capacity, uint64_t *total);
     unsigned GetTileWidth() const { return Tile.w; }
     unsigned GetTileHeight() const { return Tile.h; }
     const BoundingVolumesHierarchy &GetBVH() const { return Tree; }

@@ -6,11 +6,13 @@
 // and in what ends a query; a lane's state, its stack, the leaf walk, the user sphere, a query's prologue and the persistent-lane loop are
 // stated once ("the walk: what the three kernels share") and compile to the kernels the written-out copies gave (profiles/nearest_walk.txt).
 // Behind them the k nearest of the same header: k_knn, a fourth lane type of that walk, whose best so far is a list of k in LDS (DESIGN.md
-// "k nearest", profiles/knn.txt).
+// "k nearest", profiles/knn.txt). Behind them box overlap: k_overlap_count and k_overlap_fill, a fifth lane type whose query is a box and whose
+// candidates are the primitives' boxes — box queries and, with the scene's own boxes as the queries, overlapping pairs (DESIGN.md "Box
+// overlap", profiles/overlap.txt).
 //
 // Compile-time switches (tools/nearest_time.py builds the variants; the shipped library sets none):
 //   NEAREST_PLAIN   the kernels as one thread per query with a grid stride and no refill: the A/B partner of the persistent-lane form
-//   NEAREST_COUNT   box steps and primitive tests counted per query and summed (gpuart_nearest_counts, _within_counts, _knn_counts): a
+//   NEAREST_COUNT   box steps and primitive tests counted per query and summed (gpuart_nearest_counts, _within_counts, _knn_counts, _overlap_counts): a
 //                   counting build, not a timed one
 //   NEAREST_REFILL  idle lanes of a wave at which it takes new queries (default 16)
 #include <rocprim/device/device_scan.hpp>
@@ -55,6 +57,7 @@ struct Status {
     unsigned long long total;                      ///< of the last count: the items of all lists
     unsigned long long w_box_steps, w_prim_tests;  ///< NEAREST_COUNT
     unsigned long long k_box_steps, k_prim_tests;  ///< NEAREST_COUNT: the k nearest (k_knn)
+    unsigned long long o_box_steps, o_prim_tests;  ///< NEAREST_COUNT: box overlap (k_overlap), both passes, box queries and pairs
 };
 
 struct SceneView {
@@ -787,6 +790,176 @@ uint32_t knn_capacity(uint32_t k) {
     return s;
 }
 
+// ---- box overlap: k_overlap_count and k_overlap_fill -------------------------------------------------------------------------------------
+// A fifth lane type of the walk: the query is a box, inflated once by the call's margin, and both the item test and the prune are
+// nearest_rule.h's overlap_test — comparisons of stored numbers. As in k_within nothing that is found prunes anything: a stack entry is the
+// ref, the lower child is entered first, what comes off the stack is not tested again. An item is the ordinal, 4 bytes. The leaf step reads
+// the primitives' boxes and, of an unflagged leaf, the count word of its first record — not the 48-byte records walk_leaf loads.
+// Pairs are the same kernels under a launch flag: the host points `boxes` at the scene's own prim_boxes from the launch's first ordinal on,
+// query i's own ordinal is self0 + i, and an item is kept only strictly above it (pairs_keep). The flag is wave-uniform; the one compare it
+// adds to a box query's item is not worth a second pair of kernels.
+struct OLaunch {
+    SceneView sc;
+    const float *boxes;  ///< query i's six words {lo.xyz, hi.xyz} at boxes + 6 i
+    uint32_t n;
+    uint32_t self0;      ///< pairs: the ordinal of query 0
+    uint32_t pairs;
+    float margin;
+    float4 us;
+    uint32_t use_us;
+    uint32_t *offsets;   ///< count: written; fill: read
+    int32_t *items;      ///< fill
+    uint32_t capacity;   ///< fill: ordinals of items
+    uint32_t *spill;
+    uint32_t cap;
+    uint32_t *cursor;
+    Status *status;
+};
+
+template <bool FILL>
+struct OLane : Walk {
+    float qlo[3], qhi[3];        ///< the inflated query
+    uint32_t self;               ///< pairs: the query's own ordinal
+    uint32_t at, end;            ///< count: the items so far, unused; fill: where the next item goes, and where the list ends
+    unsigned long long sum = 0;  ///< count: the items of all lists this lane has finished
+};
+
+/// One candidate: the box [blo, bhi] of ordinal `ord`. The fill stores an item where the offsets put it, and nowhere else.
+template <bool FILL>
+__device__ __forceinline__ void offer(OLane<FILL> &L, const OLaunch &a, uint32_t ord, const float blo[3], const float bhi[3]) {
+    if (nr::overlap_test(L.qlo, L.qhi, blo, bhi) && (!a.pairs || nr::pairs_keep(L.self, ord))) {
+        if (FILL) {
+            if (L.at < L.end && L.at < a.capacity) a.items[L.at] = (int32_t)ord;
+            else a.status->mismatch = 1u;
+        }
+        L.at++;
+    }
+#ifdef NEAREST_COUNT
+    L.tests++;
+#endif
+}
+
+template <bool FILL>
+__device__ __forceinline__ void finish(OLane<FILL> &L, const OLaunch &a) {
+    if (FILL) {
+        if (L.at != L.end) a.status->mismatch = 1u;
+    } else {
+        a.offsets[L.qi] = L.at;
+        L.sum += L.at;
+    }
+#ifdef NEAREST_COUNT
+    atomicAdd(&a.status->o_box_steps, (unsigned long long)L.boxes);
+    atomicAdd(&a.status->o_prim_tests, (unsigned long long)L.tests);
+#endif
+    L.qi = NONE;
+}
+
+template <bool FILL>
+__device__ __forceinline__ void next_node(OLane<FILL> &L, const Stack<uint32_t> &st, const OLaunch &a) {
+    if (L.sp == 0) { finish(L, a); return; }
+    L.node = st.pop(L);
+}
+
+__device__ __forceinline__ void load_box(const SceneView &sc, uint32_t i, float b[6]) {
+    const float *bx = sc.pbox + 6u * i;
+    for (int k = 0; k < 6; k++) b[k] = bx[k];
+}
+
+/// The leaf `ref`: candidate(box, ordinal) for each of its primitives, in walk_leaf's order and with its loads ahead, of the boxes alone.
+template <class Candidate>
+__device__ __forceinline__ void walk_leaf_boxes(const SceneView &sc, uint32_t ref, Candidate candidate) {
+    const uint32_t first = ref & REF_INDEX;
+    const bool flagged = (ref & (REF_TRIS | REF_SMALL)) != 0;
+    float cur[6], nxt[6];
+    load_box(sc, first, cur);
+    for (int k = 0; k < 6; k++) nxt[k] = cur[k];
+    if (flagged && (ref & REF_TWO)) load_box(sc, first + 1u, nxt);
+    uint32_t count = (ref & REF_TWO) ? 2u : 1u;
+    if (!flagged) count = __float_as_uint(((const float *)sc.prims)[12u * first + 3u]) >> 2;
+    for (uint32_t k = 0; k < count; k++) {
+        if (!flagged && k + 1u < count) load_box(sc, first + k + 1u, nxt);
+        candidate(cur, first + k);
+        for (int c = 0; c < 6; c++) cur[c] = nxt[c];
+    }
+}
+
+/// Query i begins: an empty list at once (no box, or one that misses the root), or the user sphere's box as the first candidate and the root.
+template <bool FILL>
+__device__ __forceinline__ void begin(OLane<FILL> &L, const Stack<uint32_t> &, const OLaunch &a, uint32_t i) {
+    const float *b = a.boxes + 6 * (size_t)i;
+    const float box[6] = {b[0], b[1], b[2], b[3], b[4], b[5]};
+    L.qi = i;
+    L.self = a.self0 + i;
+    L.sp = L.spilled = 0;
+#ifdef NEAREST_COUNT
+    L.boxes = L.tests = 0;
+#endif
+    L.at = L.end = 0;
+    if (FILL) { L.at = a.offsets[i]; L.end = a.offsets[i + 1u]; }
+    nr::overlap_inflate(box, a.margin, L.qlo, L.qhi);
+    if (!nr::overlap_query_ok(box)) { finish(L, a); return; }
+    if (a.use_us) {
+        PrimData d;
+        user_sphere_prim(a.us.x, a.us.y, a.us.z, a.us.w, d);
+        offer(L, a, nr::USER_SPHERE, d.box, d.box + 3);
+    }
+    if (!nr::overlap_test(L.qlo, L.qhi, a.sc.root_lo, a.sc.root_hi)) { finish(L, a); return; }
+    L.node = a.sc.root_ref;
+}
+
+/// One step of a lane's walk: a record (both boxes; the lower child entered, the upper stacked, each unless it misses the query) or a leaf.
+template <bool FILL>
+__device__ __forceinline__ void step(OLane<FILL> &L, const Stack<uint32_t> &st, const OLaunch &a) {
+    const uint32_t ref = L.node;
+    if (!(ref & REF_LEAF)) {
+        const float4 *rec = a.sc.recs + 4u * ref;
+        const float4 ra = rec[0], rb = rec[1], rc = rec[2], rd = rec[3];
+        float l0[3], h0[3], l1[3], h1[3];
+        xyz(ra, l0); xyz(rb, h0); xyz(rc, l1); xyz(rd, h1);
+        const bool klo = nr::overlap_test(L.qlo, L.qhi, l0, h0), khi = nr::overlap_test(L.qlo, L.qhi, l1, h1);
+        const uint32_t rlo = __float_as_uint(ra.w), rhi = __float_as_uint(rb.w);
+#ifdef NEAREST_COUNT
+        L.boxes++;
+#endif
+        if (klo && khi) {
+            st.push(L, rhi);
+            L.node = rlo;
+        } else if (klo) L.node = rlo;
+        else if (khi) L.node = rhi;
+        else next_node(L, st, a);
+        return;
+    }
+    walk_leaf_boxes(a.sc, ref, [&](const float *bx, uint32_t ord) { offer(L, a, ord, bx, bx + 3); });
+    next_node(L, st, a);
+}
+
+// k_overlap_count (FILL = false) and k_overlap_fill (FILL = true): the protocol of the k_within pair — lengths at offsets[qi] and one 64-bit
+// atomic per wave for the total; the fill writes list qi from offsets[qi] on, in the order of the walk.
+template <bool FILL>
+__device__ __forceinline__ void overlap_body(const OLaunch &a, uint32_t *ring) {
+    const Stack<uint32_t> st(ring, a.spill, a.cap, a.status);
+    const OLane<FILL> L = walk_queries<OLane<FILL>>(st, a);
+    if (!FILL) {
+        unsigned long long sum = L.sum;
+        for (int d = 32; d > 0; d >>= 1) sum += __shfl_down(sum, d, 64);
+        if ((threadIdx.x & 63u) == 0 && sum) atomicAdd(&a.status->total, sum);
+    }
+}
+
+__global__ void __launch_bounds__(BLOCK) k_overlap_count(OLaunch a) {
+    __shared__ uint32_t ring[RING * BLOCK];
+    overlap_body<false>(a, ring);
+}
+
+__global__ void __launch_bounds__(BLOCK) k_overlap_fill(OLaunch a) {
+    __shared__ uint32_t ring[RING * BLOCK];
+    overlap_body<true>(a, ring);
+}
+
+/// Whose the last count was: the three kinds of lists share the handle's bookkeeping of it, and a fill of another kind is refused.
+enum { COUNT_WITHIN = 1, COUNT_OVERLAP = 2, COUNT_PAIRS = 3 };
+const char *const COUNT_NAMES[4] = {"nothing", "neighbour lists (within)", "box queries (overlap)", "pairs"};
+
 }  // namespace
 
 struct gpuart_nearest : ImageHandle {
@@ -817,6 +990,11 @@ struct gpuart_nearest : ImageHandle {
     uint32_t knn_blocks[KNN_SIZES] = {0, 0, 0, 0};  ///< of k_knn per capacity: what the device holds at once
     StepTimer kwalk;
     bool kwalked = false;
+    // box overlap: box queries and pairs. They share the lists' bookkeeping of "the last count" above, which therefore says whose it is
+    uint32_t overlap_blocks[2] = {0, 0};  ///< of k_overlap_count and k_overlap_fill: what the device holds at once
+    int counted_kind = 0;        ///< COUNT_WITHIN, COUNT_OVERLAP or COUNT_PAIRS: what the last count counted (0: nothing yet)
+    StepTimer ocount, ofill;     ///< count and scan; fill
+    bool ocounted = false, ofilled = false;
 };
 
 namespace {
@@ -894,16 +1072,15 @@ int too_many(uint64_t total, uint64_t cap) {
 
 /// What every launch over n queries in device memory begins with: the grid — the blocks the spill budget pays for (a column entry is what
 /// the kernel's stack holds: the lists' 4 bytes are half of k_nearest's), the blocks the work fills, and `most` —, the lanes' stack columns,
-/// the arguments every kernel has, and the cursor at zero.
+/// the arguments every kernel has (its queries are the caller's to set), and the cursor at zero.
 template <class A>
-int prepare(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, uint32_t n, const float us[4], uint32_t most, A &a, uint32_t &grid) {
+int prepare(gpuart_nearest *h, const gpuart_hip_scene *s, uint32_t n, const float us[4], uint32_t most, A &a, uint32_t &grid) {
     const size_t levels = (size_t)s->max_depth + 2, block_bytes = levels * sizeof(*a.spill) * BLOCK;
     const size_t by_budget = std::max<size_t>(1, h->spill_budget / block_bytes);
     const size_t by_work = ((size_t)n + (size_t)CHUNK * WAVES - 1) / ((size_t)CHUNK * WAVES);
     grid = (uint32_t)std::min({by_budget, by_work, (size_t)most});
     if (int rc = ensure(h->stream, h->spill, block_bytes * grid)) return rc;
     a.sc = view_of(s);
-    a.points = (const float4 *)points;
     a.n = n;
     a.us = us ? make_float4(us[0], us[1], us[2], us[3]) : make_float4(0, 0, 0, 0);
     a.use_us = us ? 1u : 0u;
@@ -919,7 +1096,8 @@ int prepare(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, u
 int launch(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, uint32_t n, const float us[4], gpuart_nearest_hit *hits) {
     Launch a{};
     uint32_t grid;
-    if (int rc = prepare(h, s, points, n, us, h->max_blocks, a, grid)) return rc;
+    if (int rc = prepare(h, s, n, us, h->max_blocks, a, grid)) return rc;
+    a.points = (const float4 *)points;
     a.hits = hits;
     h->walk.start(h->stream);
     HIP_TRY(h->walk.mark());
@@ -937,7 +1115,8 @@ int launch_knn(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points
     KnnLaunch a{};
     uint32_t grid;
     const uint32_t size = knn_capacity(k);
-    if (int rc = prepare(h, s, points, n, us, std::min(h->max_blocks, h->knn_blocks[size]), a, grid)) return rc;
+    if (int rc = prepare(h, s, n, us, std::min(h->max_blocks, h->knn_blocks[size]), a, grid)) return rc;
+    a.points = (const float4 *)points;
     a.k = k;
     a.hits = hits;
     h->kwalk.start(h->stream);
@@ -955,7 +1134,8 @@ int launch_knn(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points
 int launch_count(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, uint32_t n, const float us[4], uint32_t *offsets) {
     WLaunch a{};
     uint32_t grid;
-    if (int rc = prepare(h, s, points, n, us, std::min(h->max_blocks, h->within_blocks[0]), a, grid)) return rc;
+    if (int rc = prepare(h, s, n, us, std::min(h->max_blocks, h->within_blocks[0]), a, grid)) return rc;
+    a.points = (const float4 *)points;
     a.offsets = offsets;
     size_t scan_bytes = 0;
     HIP_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, offsets, offsets, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), h->stream));
@@ -972,6 +1152,7 @@ int launch_count(gpuart_nearest *h, const gpuart_hip_scene *s, const float *poin
     h->counted = true;
     h->total_read = false;
     h->counted_n = n;
+    h->counted_kind = COUNT_WITHIN;
     h->last_blocks = grid;
     h->last_launches++;
     return 0;
@@ -992,7 +1173,8 @@ int launch_fill(gpuart_nearest *h, const gpuart_hip_scene *s, const float *point
                 gpuart_nearest_hit *items, uint32_t capacity) {
     WLaunch a{};
     uint32_t grid;
-    if (int rc = prepare(h, s, points, n, us, std::min(h->max_blocks, h->within_blocks[1]), a, grid)) return rc;
+    if (int rc = prepare(h, s, n, us, std::min(h->max_blocks, h->within_blocks[1]), a, grid)) return rc;
+    a.points = (const float4 *)points;
     a.offsets = const_cast<uint32_t *>(offsets);
     a.items = items;
     a.capacity = capacity;
@@ -1070,6 +1252,214 @@ int fill_staged(gpuart_nearest *h, const gpuart_hip_scene *s, const float *point
     return read_mismatch(h);
 }
 
+// ---- box overlap -----------------------------------------------------------------------------------------------------------------------
+int tree_order(const float *recs, size_t n_recs, uint32_t root_ref, const float *prims, size_t n_prims, std::vector<uint32_t> &order);
+
+/// A fill of `kind` wants the last count to be of its own kind.
+int check_kind(const gpuart_nearest *h, int kind) {
+    if (h->counted_kind == kind) return 0;
+    return fail(GPUART_HIP_ERR_ARG, std::string("nearest: the last count was of ") + COUNT_NAMES[h->counted_kind] + ", this fill is of " + COUNT_NAMES[kind]);
+}
+
+int check_margin(float margin) {
+    return nr::overlap_margin_ok(margin) ? 0 : fail(GPUART_HIP_ERR_ARG, "nearest: the margin is NaN, infinite or negative");
+}
+
+/// The queries of an overlap launch: n boxes at `boxes` (device), or — pairs — the scene's own boxes of the ordinals first .. first + n - 1.
+struct OQueries {
+    const float *boxes;
+    uint32_t n, first;
+    bool pairs;
+    float margin;
+    const float *us;
+};
+
+OQueries pair_queries(const gpuart_hip_scene *s, size_t first, size_t n, float margin) {
+    return OQueries{(const float *)s->prim_boxes + 6 * first, (uint32_t)n, (uint32_t)first, true, margin, nullptr};
+}
+
+template <class A>
+void set_queries(A &a, const OQueries &q) {
+    a.boxes = q.boxes;
+    a.self0 = q.first;
+    a.pairs = q.pairs ? 1u : 0u;
+    a.margin = q.margin;
+}
+
+/// The count of an overlap launch into offsets[0 .. n] (device), scanned in place; the total stays in the status.
+int launch_ocount(gpuart_nearest *h, const gpuart_hip_scene *s, const OQueries &q, uint32_t *offsets) {
+    OLaunch a{};
+    uint32_t grid;
+    if (int rc = prepare(h, s, q.n, q.us, std::min(h->max_blocks, h->overlap_blocks[0]), a, grid)) return rc;
+    set_queries(a, q);
+    a.offsets = offsets;
+    size_t scan_bytes = 0;
+    HIP_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, offsets, offsets, 0u, (size_t)q.n + 1, rocprim::plus<uint32_t>(), h->stream));
+    if (int rc = ensure(h->stream, h->scan_temp, scan_bytes + 16)) return rc;
+    HIP_TRY(hipMemsetAsync(&h->status->total, 0, sizeof(unsigned long long), h->stream));
+    HIP_TRY(hipMemsetAsync(offsets + q.n, 0, sizeof(uint32_t), h->stream));
+    h->ocount.start(h->stream);
+    HIP_TRY(h->ocount.mark());
+    k_overlap_count<<<grid, BLOCK, 0, h->stream>>>(a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(h->ocount.mark());
+    HIP_TRY(rocprim::exclusive_scan(h->scan_temp.mem, scan_bytes, offsets, offsets, 0u, (size_t)q.n + 1, rocprim::plus<uint32_t>(), h->stream));
+    HIP_TRY(h->ocount.mark());
+    h->ocounted = true;
+    h->total_read = false;
+    h->counted_n = q.n;
+    h->counted_kind = q.pairs ? COUNT_PAIRS : COUNT_OVERLAP;
+    h->last_blocks = grid;
+    h->last_launches++;
+    return 0;
+}
+
+int launch_ofill(gpuart_nearest *h, const gpuart_hip_scene *s, const OQueries &q, const uint32_t *offsets, int32_t *items, uint32_t capacity) {
+    OLaunch a{};
+    uint32_t grid;
+    if (int rc = prepare(h, s, q.n, q.us, std::min(h->max_blocks, h->overlap_blocks[1]), a, grid)) return rc;
+    set_queries(a, q);
+    a.offsets = const_cast<uint32_t *>(offsets);
+    a.items = items;
+    a.capacity = capacity;
+    h->ofill.start(h->stream);
+    HIP_TRY(h->ofill.mark());
+    k_overlap_fill<<<grid, BLOCK, 0, h->stream>>>(a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(h->ofill.mark());
+    h->ofilled = h->fill_pending = true;
+    h->last_blocks = grid;
+    h->last_launches++;
+    return 0;
+}
+
+/// What the box queries check before a launch: the handle and its binding, n, the user sphere, the margin, the two arrays.
+int check_overlap(gpuart_nearest *h, const gpuart_hip_scene *s, const void *boxes, size_t n, float margin, const float us[4], const void *offsets) {
+    if (int rc = check_queries(h, s, n, us)) return rc;
+    if (int rc = check_margin(margin)) return rc;
+    if (n && (!boxes || !offsets)) return fail(GPUART_HIP_ERR_ARG, "nearest: boxes or offsets is NULL");
+    if (misaligned({boxes, offsets}, 4)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned pointer (boxes and offsets need 4 bytes)");
+    if (n && overlaps(boxes, n * 24, offsets, (n + 1) * 4)) return fail(GPUART_HIP_ERR_ARG, "nearest: offsets overlaps boxes");
+    return 0;
+}
+
+/// What the pairs check: the handle and its binding, the margin, the offsets.
+int check_pairs(gpuart_nearest *h, const gpuart_hip_scene *s, float margin, const void *offsets) {
+    if (int rc = check_queries(h, s, s ? s->n_prims : 0, nullptr)) return rc;
+    if (int rc = check_margin(margin)) return rc;
+    if (!offsets) return fail(GPUART_HIP_ERR_ARG, "nearest: offsets is NULL");
+    if (misaligned({offsets}, 4)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned pointer (offsets needs 4 bytes)");
+    return 0;
+}
+
+/// What a device fill checks behind its queries: the last count (its n, its kind, its total against the caps and the capacity) and items.
+/// Returns 1 where there is nothing to fill.
+int check_ofill(gpuart_nearest *h, int kind, size_t n, const void *queries, size_t query_bytes, const uint32_t *offsets, const int32_t *items, size_t &capacity) {
+    if (misaligned({items}, 4)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned pointer (items needs 4 bytes)");
+    if (n != h->counted_n) return fail(GPUART_HIP_ERR_ARG, "nearest: the last count was of " + std::to_string(h->counted_n) + " queries, not of " + std::to_string(n));
+    if (int rc = check_kind(h, kind)) return rc;
+    if (!n) return 1;
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = read_total(h)) return rc;
+    if (h->last_total > h->max_items) return too_many(h->last_total, h->max_items);
+    if (capacity < h->last_total)
+        return fail(GPUART_HIP_ERR_ARG, "nearest: items has room for " + std::to_string(capacity) + " ordinals, the last count's total is " + std::to_string(h->last_total));
+    if (capacity && !items) return fail(GPUART_HIP_ERR_ARG, "nearest: items is NULL");
+    capacity = std::min<size_t>(capacity, GPUART_NEAREST_WITHIN_MAX_ITEMS);
+    if (capacity && ((queries && overlaps(items, capacity * 4, queries, query_bytes)) || overlaps(items, capacity * 4, offsets, (n + 1) * 4)))
+        return fail(GPUART_HIP_ERR_ARG, "nearest: items overlaps boxes or offsets");
+    return 0;
+}
+
+/// Both passes of an overlap run into host memory, staged in chunks of host_chunk queries: for box queries a chunk's boxes go up, for pairs
+/// (boxes == NULL) nothing does — a launch takes its first ordinal. Offsets are rebased on the host. fill_only: offsets are the caller's.
+/// The staging buffer: a chunk's boxes, then its offsets, then its items.
+int overlap_staged(gpuart_nearest *h, const gpuart_hip_scene *s, const float *boxes, size_t n, float margin, const float us[4], uint32_t *offsets,
+                   int32_t *items, size_t capacity, uint64_t *total, bool fill_only) {
+    const bool pairs = !boxes;
+    const size_t chunk = std::min(n, h->host_chunk);
+    h->host_offsets.resize(chunk + 1);
+    uint32_t *local = h->host_offsets.data();
+    const size_t head = chunk * 24 + (chunk + 1) * 4;
+    auto queries = [&](size_t at, size_t m) {
+        return pairs ? pair_queries(s, at, m, margin) : OQueries{(const float *)h->staging.mem, (uint32_t)m, 0u, false, margin, us};
+    };
+    if (!fill_only) {
+        if (int rc = ensure(h->stream, h->staging, head)) return rc;
+        uint64_t base = 0;
+        for (size_t at = 0; at < n; at += chunk) {
+            const size_t m = std::min(chunk, n - at);
+            uint32_t *doffsets = (uint32_t *)((char *)h->staging.mem + chunk * 24);
+            if (!pairs) HIP_TRY(hipMemcpyAsync(h->staging.mem, boxes + 6 * at, m * 24, hipMemcpyHostToDevice, h->stream));
+            if (int rc = launch_ocount(h, s, queries(at, m), doffsets)) return rc;
+            HIP_TRY(hipMemcpyAsync(local, doffsets, m * 4, hipMemcpyDeviceToHost, h->stream));
+            if (int rc = read_total(h)) return rc;
+            for (size_t k = 0; k < m; k++) offsets[at + k] = (uint32_t)(base + local[k]);
+            base += h->last_total;
+        }
+        offsets[n] = (uint32_t)base;
+        *total = base;
+        h->last_total = base;
+        h->counted_n = n;
+        if (int rc = read_overflow(h)) return rc;
+        if (base > h->max_items) return too_many(base, h->max_items);
+        if (!items || capacity < base) return 0;
+    }
+    for (size_t at = 0; at < n; at += chunk) {
+        const size_t m = std::min(chunk, n - at);
+        const size_t room = offsets[at + m] - offsets[at];
+        if (int rc = ensure(h->stream, h->staging, head + room * 4)) return rc;
+        uint32_t *doffsets = (uint32_t *)((char *)h->staging.mem + chunk * 24);
+        int32_t *ditems = (int32_t *)((char *)h->staging.mem + head);
+        for (size_t k = 0; k <= m; k++) local[k] = offsets[at + k] - offsets[at];
+        if (!pairs) HIP_TRY(hipMemcpyAsync(h->staging.mem, boxes + 6 * at, m * 24, hipMemcpyHostToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(doffsets, local, (m + 1) * 4, hipMemcpyHostToDevice, h->stream));
+        if (int rc = launch_ofill(h, s, queries(at, m), doffsets, ditems, (uint32_t)room)) return rc;
+        if (room) HIP_TRY(hipMemcpyAsync(items + offsets[at], ditems, room * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    h->fill_pending = false;
+    if (int rc = read_overflow(h)) return rc;
+    return read_mismatch(h);
+}
+
+/// The definition on host arrays, for box queries (boxes != NULL) and pairs: every primitive tested in the tree's order.
+int overlap_brute(const float *recs, size_t n_recs, uint32_t root_ref, const float *prims, const float *prim_boxes, size_t n_prims, const float *boxes, size_t n,
+                  float margin, const float us[4], uint32_t *offsets, int32_t *items, size_t capacity, uint64_t *total) {
+    const bool pairs = !boxes;
+    if (int rc = check_margin(margin)) return rc;
+    if (int rc = check_user_sphere(us)) return rc;
+    std::vector<uint32_t> order;
+    if (int rc = tree_order(recs, n_recs, root_ref, prims, n_prims, order)) return rc;
+    auto visit = [&](size_t i, auto &&emit) {
+        const float *box = pairs ? prim_boxes + 6 * i : boxes + 6 * i;
+        float qlo[3], qhi[3];
+        if (!nr::overlap_query_ok(box)) return;
+        nr::overlap_inflate(box, margin, qlo, qhi);
+        if (us) {
+            PrimData d;
+            user_sphere_prim(us[0], us[1], us[2], us[3], d);
+            if (nr::overlap_test(qlo, qhi, d.box, d.box + 3)) emit((int32_t)nr::USER_SPHERE);
+        }
+        for (const uint32_t k : order) {
+            const float *b = prim_boxes + 6 * (size_t)k;
+            if (nr::overlap_test(qlo, qhi, b, b + 3) && (!pairs || nr::pairs_keep((uint32_t)i, k))) emit((int32_t)k);
+        }
+    };
+    uint64_t sum = 0;
+    for (size_t i = 0; i < n; i++) {
+        offsets[i] = (uint32_t)sum;
+        visit(i, [&](int32_t) { sum++; });
+    }
+    offsets[n] = (uint32_t)sum;
+    *total = sum;
+    if (sum > GPUART_NEAREST_WITHIN_MAX_ITEMS) return too_many(sum, GPUART_NEAREST_WITHIN_MAX_ITEMS);
+    if (!items || capacity < sum) return 0;
+    size_t at = 0;
+    for (size_t i = 0; i < n; i++) visit(i, [&](int32_t k) { items[at++] = k; });
+    return 0;
+}
+
 /// The ordinals in the order of the unpruned depth-first walk from root_ref, lower child first; 0, or why the records are refused.
 int tree_order(const float *recs, size_t n_recs, uint32_t root_ref, const float *prims, size_t n_prims, std::vector<uint32_t> &order) {
     order.clear();
@@ -1116,6 +1506,8 @@ int gpuart_nearest_create(int device, gpuart_nearest **out) {
         if (e == hipSuccess) e = h->wcount.create(2);
         if (e == hipSuccess) e = h->wfill.create(1);
         if (e == hipSuccess) e = h->kwalk.create(1);
+        if (e == hipSuccess) e = h->ocount.create(2);
+        if (e == hipSuccess) e = h->ofill.create(1);
         return e;
     });
     if (rc) return rc;
@@ -1132,6 +1524,10 @@ int gpuart_nearest_create(int device, gpuart_nearest **out) {
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, KNN_KERNELS[k], BLOCK, 0) != hipSuccess || per_cu < 1) per_cu = 1;
         h->knn_blocks[k] = (uint32_t)per_cu * (uint32_t)cus;
     }
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_overlap_count, BLOCK, 0) != hipSuccess || per_cu < 1) per_cu = 1;
+    h->overlap_blocks[0] = (uint32_t)per_cu * (uint32_t)cus;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_overlap_fill, BLOCK, 0) != hipSuccess || per_cu < 1) per_cu = 1;
+    h->overlap_blocks[1] = (uint32_t)per_cu * (uint32_t)cus;
     return 0;
 }
 
@@ -1143,6 +1539,8 @@ int gpuart_nearest_destroy(gpuart_nearest *h) {
     h->wcount.destroy();
     h->wfill.destroy();
     h->kwalk.destroy();
+    h->ocount.destroy();
+    h->ofill.destroy();
     delete h;
     return 0;
 }
@@ -1161,6 +1559,7 @@ int gpuart_nearest_bind(gpuart_nearest *h, const gpuart_hip_scene *s) {
     h->counted_n = 0;  // (the status is zeroed below, the last count's total with it: a fill wants a count of this binding)
     h->last_total = 0;
     h->total_read = true;
+    h->counted_kind = 0;
     if (!s) return fail(GPUART_HIP_ERR_ARG, "nearest: scene is NULL");
     if (int rc = check_descriptor(s, LIB, "", "queried for closest points", true)) return rc;
     if (misaligned({s->recs, s->prims}, 16) || misaligned({s->prim_boxes}, 4)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned arrays");
@@ -1287,6 +1686,7 @@ int gpuart_nearest_within_count(gpuart_nearest *h, const gpuart_hip_scene *s, co
         h->last_total = 0;
         h->total_read = true;
         h->counted_n = 0;
+        h->counted_kind = COUNT_WITHIN;
         return 0;
     }
     HIP_TRY(hipSetDevice(h->device));
@@ -1308,6 +1708,7 @@ int gpuart_nearest_within_fill(gpuart_nearest *h, const gpuart_hip_scene *s, con
     if (misaligned({items}, 16)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned pointer (items needs 16 bytes)");
     if (n != h->counted_n) return fail(GPUART_HIP_ERR_ARG, "nearest: the last count was of " + std::to_string(h->counted_n) + " queries, not of " + std::to_string(n));
     if (!n) return 0;
+    if (int rc = check_kind(h, COUNT_WITHIN)) return rc;
     HIP_TRY(hipSetDevice(h->device));
     if (int rc = read_total(h)) return rc;
     if (h->last_total > h->max_items) return too_many(h->last_total, h->max_items);
@@ -1521,5 +1922,124 @@ int gpuart_nearest_knn_step_ms(gpuart_nearest *h, double ms[1]) {
 }
 
 int gpuart_nearest_knn_counts(gpuart_nearest *h, uint64_t out[2]) { return read_counts(h, &Status::k_box_steps, out); }
+
+// ---- box overlap: box queries ---------------------------------------------------------------------------------------------------------------
+int gpuart_nearest_overlap_count(gpuart_nearest *h, const gpuart_hip_scene *s, const float *boxes, size_t n, float margin, const float us[4], uint32_t *offsets) {
+    if (int rc = check_overlap(h, s, boxes, n, margin, us, offsets)) return rc;
+    h->last_launches = 0;
+    if (!n) {
+        h->last_total = 0;
+        h->total_read = true;
+        h->counted_n = 0;
+        h->counted_kind = COUNT_OVERLAP;
+        return 0;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    return launch_ocount(h, s, OQueries{boxes, (uint32_t)n, 0u, false, margin, us}, offsets);
+}
+
+int gpuart_nearest_overlap_total(gpuart_nearest *h, uint64_t *total) { return gpuart_nearest_within_total(h, total); }
+
+int gpuart_nearest_overlap_fill(gpuart_nearest *h, const gpuart_hip_scene *s, const float *boxes, size_t n, float margin, const float us[4], const uint32_t *offsets,
+                                int32_t *items, size_t capacity) {
+    if (int rc = check_overlap(h, s, boxes, n, margin, us, offsets)) return rc;
+    if (int rc = check_ofill(h, COUNT_OVERLAP, n, boxes, n * 24, offsets, items, capacity)) return rc < 0 ? rc : 0;
+    h->last_launches = 0;
+    return launch_ofill(h, s, OQueries{boxes, (uint32_t)n, 0u, false, margin, us}, offsets, items, (uint32_t)capacity);
+}
+
+int gpuart_nearest_overlap_host(gpuart_nearest *h, const gpuart_hip_scene *s, const float *boxes, size_t n, float margin, const float us[4], uint32_t *offsets,
+                                int32_t *items, size_t capacity, uint64_t *total) {
+    if (int rc = check_overlap(h, s, boxes, n, margin, us, offsets)) return rc;
+    if (!offsets || !total) return fail(GPUART_HIP_ERR_ARG, "nearest: offsets or total is NULL");
+    if (misaligned({items}, 4)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned pointer (items needs 4 bytes)");
+    offsets[0] = 0;
+    *total = 0;
+    h->last_launches = 0;
+    if (!n) return 0;
+    HIP_TRY(hipSetDevice(h->device));
+    return overlap_staged(h, s, boxes, n, margin, us, offsets, items, capacity, total, false);
+}
+
+int gpuart_nearest_overlap_fill_host(gpuart_nearest *h, const gpuart_hip_scene *s, const float *boxes, size_t n, float margin, const float us[4],
+                                     const uint32_t *offsets, int32_t *items, size_t capacity) {
+    if (int rc = check_overlap(h, s, boxes, n, margin, us, offsets)) return rc;
+    if (!offsets) return fail(GPUART_HIP_ERR_ARG, "nearest: offsets is NULL");
+    if (misaligned({items}, 4)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned pointer (items needs 4 bytes)");
+    if (offsets[0] != 0) return fail(GPUART_HIP_ERR_ARG, "nearest: offsets[0] is not 0");
+    for (size_t i = 0; i < n; i++)
+        if (offsets[i + 1] < offsets[i]) return fail(GPUART_HIP_ERR_ARG, "nearest: the offsets decrease at query " + std::to_string(i));
+    const uint64_t total = offsets[n];
+    if (total > h->max_items) return too_many(total, h->max_items);
+    if (capacity < total)
+        return fail(GPUART_HIP_ERR_ARG, "nearest: items has room for " + std::to_string(capacity) + " ordinals, the offsets end at " + std::to_string(total));
+    if (total && !items) return fail(GPUART_HIP_ERR_ARG, "nearest: items is NULL");
+    h->last_launches = 0;
+    if (!n) return 0;
+    HIP_TRY(hipSetDevice(h->device));
+    return overlap_staged(h, s, boxes, n, margin, us, const_cast<uint32_t *>(offsets), items, capacity, nullptr, true);
+}
+
+int gpuart_nearest_overlap_brute_host(const float *recs, size_t n_recs, uint32_t root_ref, const float *prims, const float *prim_boxes, size_t n_prims,
+                                      const float *boxes, size_t n, float margin, const float us[4], uint32_t *offsets, int32_t *items, size_t capacity,
+                                      uint64_t *total) {
+    if ((n_prims && (!prims || !prim_boxes)) || (n_recs && !recs) || (n && !boxes) || !offsets || !total)
+        return fail(GPUART_HIP_ERR_ARG, "nearest: recs, prims, prim_boxes, boxes, offsets or total is NULL");
+    if (n_prims > REF_INDEX || n_recs > REF_INDEX) return fail(GPUART_HIP_ERR_ARG, "nearest: too many primitives or records: " + std::to_string(n_prims));
+    if (n > GPUART_HIP_MAX_RAYS) return fail(GPUART_HIP_ERR_ARG, "nearest: too many queries: " + std::to_string(n));
+    const float none[6] = {0, 0, 0, 0, 0, 0};
+    return overlap_brute(recs, n_recs, root_ref, prims, prim_boxes, n_prims, n ? boxes : none, n, margin, us, offsets, items, capacity, total);
+}
+
+int gpuart_nearest_overlap_step_ms(gpuart_nearest *h, double ms[3]) {
+    if (int rc = check_handle(LIB, h)) return rc;
+    if (!ms) return fail(GPUART_HIP_ERR_ARG, "nearest: ms is NULL");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->ocounted)
+        if (int rc = h->ocount.read()) return rc;
+    if (h->ofilled)
+        if (int rc = h->ofill.read()) return rc;
+    ms[0] = h->ocount.ms[0];
+    ms[1] = h->ocount.ms[1];
+    ms[2] = h->ofill.ms[0];
+    return 0;
+}
+
+int gpuart_nearest_overlap_counts(gpuart_nearest *h, uint64_t out[2]) { return read_counts(h, &Status::o_box_steps, out); }
+
+// ---- box overlap: pairs -----------------------------------------------------------------------------------------------------------------------
+int gpuart_nearest_pairs_count(gpuart_nearest *h, const gpuart_hip_scene *s, float margin, uint32_t *offsets) {
+    if (int rc = check_pairs(h, s, margin, offsets)) return rc;
+    h->last_launches = 0;
+    HIP_TRY(hipSetDevice(h->device));
+    return launch_ocount(h, s, pair_queries(s, 0, s->n_prims, margin), offsets);
+}
+
+int gpuart_nearest_pairs_fill(gpuart_nearest *h, const gpuart_hip_scene *s, float margin, const uint32_t *offsets, int32_t *items, size_t capacity) {
+    if (int rc = check_pairs(h, s, margin, offsets)) return rc;
+    if (int rc = check_ofill(h, COUNT_PAIRS, s->n_prims, nullptr, 0, offsets, items, capacity)) return rc < 0 ? rc : 0;
+    h->last_launches = 0;
+    return launch_ofill(h, s, pair_queries(s, 0, s->n_prims, margin), offsets, items, (uint32_t)capacity);
+}
+
+int gpuart_nearest_pairs_host(gpuart_nearest *h, const gpuart_hip_scene *s, float margin, uint32_t *offsets, int32_t *items, size_t capacity, uint64_t *total) {
+    if (int rc = check_pairs(h, s, margin, offsets)) return rc;
+    if (!total) return fail(GPUART_HIP_ERR_ARG, "nearest: total is NULL");
+    if (misaligned({items}, 4)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned pointer (items needs 4 bytes)");
+    offsets[0] = 0;
+    *total = 0;
+    h->last_launches = 0;
+    HIP_TRY(hipSetDevice(h->device));
+    return overlap_staged(h, s, nullptr, s->n_prims, margin, nullptr, offsets, items, capacity, total, false);
+}
+
+int gpuart_nearest_pairs_brute_host(const float *recs, size_t n_recs, uint32_t root_ref, const float *prims, const float *prim_boxes, size_t n_prims, float margin,
+                                    uint32_t *offsets, int32_t *items, size_t capacity, uint64_t *total) {
+    if ((n_prims && (!prims || !prim_boxes)) || (n_recs && !recs) || !offsets || !total)
+        return fail(GPUART_HIP_ERR_ARG, "nearest: recs, prims, prim_boxes, offsets or total is NULL");
+    if (n_prims > REF_INDEX || n_recs > REF_INDEX) return fail(GPUART_HIP_ERR_ARG, "nearest: too many primitives or records: " + std::to_string(n_prims));
+    return overlap_brute(recs, n_recs, root_ref, prims, prim_boxes, n_prims, nullptr, n_prims, margin, nullptr, offsets, items, capacity, total);
+}
 
 }  // extern "C"

@@ -140,7 +140,8 @@ int gpuart_nearest_within_total(gpuart_nearest *h, uint64_t *total);
  * >= offsets[i + 1] or >= capacity is not written, and a list that is longer or shorter than its offsets say marks the run:
  * gpuart_nearest_finish then returns GPUART_HIP_ERR_ARG, "the offsets are not this query set's count: the results are void". A fill
  * never writes outside items[0 .. capacity), whatever it is handed. Refused before any launch: a capacity below the last count's total
- * (the call waits for the stream to learn it), that total above the cap, another n than the last count's. */
+ * (the call waits for the stream to learn it), that total above the cap, another n than the last count's, a last count of another kind
+ * (box overlap, below). */
 int gpuart_nearest_within_fill(gpuart_nearest *h, const gpuart_hip_scene *scene, const float *points, size_t n, const float userSphere[4],
                                const uint32_t *offsets, gpuart_nearest_hit *items, size_t capacity);
 /* Both passes in host memory (4-byte alignment), synchronous, staged in chunks of the host_chunk of gpuart_nearest_set_limits; a chunk's
@@ -206,6 +207,70 @@ int gpuart_nearest_knn_brute_host(gpuart_nearest *h, const float *recs, size_t n
 int gpuart_nearest_knn_step_ms(gpuart_nearest *h, double ms[1]);
 /* gpuart_nearest_counts for the k-nearest walks. */
 int gpuart_nearest_knn_counts(gpuart_nearest *h, uint64_t out[2]);
+
+/* ---- Box overlap: every primitive whose box meets a box, and the overlapping pairs of the scene's own primitives (DESIGN.md "Box
+ * overlap"; tests/overlap_ref.py restates this). Plain fp32, comparisons only, no tolerance -------------------------------------------------
+ *   query     a box {lo.xyz, hi.xyz}, six floats in the layout of prim_boxes, and one margin per call. The inflated box is qlo = lo - margin,
+ *             qhi = hi + margin, each component one fp32 operation; an overflow to -+inf is allowed. A query with a word that is not finite
+ *             or with lo > hi on some axis has an empty list. A margin that is NaN, infinite or negative is refused before any launch;
+ *   item      the device ordinal (int32) of every primitive whose own box prim_boxes[j] = (blo, bhi) satisfies, on all three axes,
+ *             qlo <= bhi && blo <= qhi: touching counts. With a user sphere (c, R) the sphere takes part through its box c -+ R, ordinal -2;
+ *   order     as the neighbour lists: the user sphere first, then the unpruned depth-first walk, lower child first, a leaf's primitives by
+ *             ascending ordinal. A function of the tree alone;
+ *   walk      a child, and the root, is skipped if and only if its box fails the same test against (qlo, qhi). If b lies inside B and q
+ *             overlaps b then q overlaps B (nearest_rule.h), and gpuart_nearest_bind has checked the nesting; only stored numbers are
+ *             compared, so nothing rounds and the pruned walk loses no item;
+ *   output    CSR exactly as the neighbour lists: offsets[n + 1] (uint32), items[total] (int32), the exact 64-bit total, the cap of
+ *             GPUART_NEAREST_WITHIN_MAX_ITEMS and the lower cap of gpuart_nearest_within_set_max_items, nothing written above it;
+ *   pairs     query i is prim_boxes[i] of the bound scene, i = 0 .. n_prims - 1, inflated by the margin and read on the device; list i holds
+ *             the ordinals j > i that this box query lists, in the same order; no user sphere. A pair {i, j} appears once, in the lower
+ *             ordinal's list, and THE LOWER ORDINAL'S BOX IS THE INFLATED ONE: in fp32 fl(lo_i - m) <= hi_j and lo_i <= fl(hi_j + m) can
+ *             disagree (lo_i = 1, hi_j = 1 - 2^-24, m = 2^-25: false, true), so a symmetric-looking implementation lists other pairs.
+ *             Adjacent triangles of a mesh share vertices and therefore always overlap: filtering topological neighbours is the caller's.
+ * Count and fill as the neighbour lists, with the same refusals, each with nothing written. The handle remembers one "last count" — its n,
+ * its total and whose it was —: a fill of one kind (within, overlap, pairs) after a count of another is refused. gpuart_nearest_set_limits
+ * applies; the spill columns cost 1 KiB per level and workgroup. */
+
+/* boxes: n x 6 floats, offsets: n + 1 words — device memory, 4-byte aligned, not overlapping; asynchronous. n = 0 does nothing. */
+int gpuart_nearest_overlap_count(gpuart_nearest *h, const gpuart_hip_scene *scene, const float *boxes, size_t n, float margin, const float userSphere[4],
+                                 uint32_t *offsets);
+/* Waits for the stream and yields the exact total of the last count (of any kind). GPUART_HIP_ERR_ARG, with *total written, above the cap. */
+int gpuart_nearest_overlap_total(gpuart_nearest *h, uint64_t *total);
+/* Writes list i at items[offsets[i] ..]: the boxes, n, margin and user sphere of the last count, and its offsets. items: `capacity` ordinals
+ * in device memory, 4-byte aligned (NULL with capacity 0), overlapping neither boxes nor offsets. Asynchronous. Every store is guarded by
+ * the list's end and the capacity; a list longer or shorter than its offsets say is reported by gpuart_nearest_finish ("the offsets are not
+ * this query set's count"). Refused before any launch: a capacity below the last count's total, that total above the cap, another n than the
+ * last count's, a last count of another kind. */
+int gpuart_nearest_overlap_fill(gpuart_nearest *h, const gpuart_hip_scene *scene, const float *boxes, size_t n, float margin, const float userSphere[4],
+                                const uint32_t *offsets, int32_t *items, size_t capacity);
+/* Both passes in host memory, synchronous, staged in chunks of host_chunk queries with offsets rebased on the host: the two-call protocol of
+ * gpuart_nearest_within_host (offsets and *total always; items only when items != NULL and capacity >= *total). */
+int gpuart_nearest_overlap_host(gpuart_nearest *h, const gpuart_hip_scene *scene, const float *boxes, size_t n, float margin, const float userSphere[4],
+                                uint32_t *offsets, int32_t *items, size_t capacity, uint64_t *total);
+/* The fill pass alone in host memory, as gpuart_nearest_within_fill_host. */
+int gpuart_nearest_overlap_fill_host(gpuart_nearest *h, const gpuart_hip_scene *scene, const float *boxes, size_t n, float margin, const float userSphere[4],
+                                     const uint32_t *offsets, int32_t *items, size_t capacity);
+/* The definition itself, with no device and no pruning: the tree order derived from recs and root_ref (prims gives an unflagged leaf's
+ * count), every primitive's box tested. Host memory; offsets, items, capacity and total as gpuart_nearest_overlap_host. */
+int gpuart_nearest_overlap_brute_host(const float *recs, size_t n_recs, uint32_t root_ref, const float *prims, const float *prim_boxes, size_t n_prims,
+                                      const float *boxes, size_t n, float margin, const float userSphere[4], uint32_t *offsets, int32_t *items,
+                                      size_t capacity, uint64_t *total);
+/* Device time in ms of the last overlap or pairs count, its scan and the last such fill. */
+int gpuart_nearest_overlap_step_ms(gpuart_nearest *h, double ms[3]);
+/* gpuart_nearest_counts for the overlap walks: box steps and box tests, both passes, box queries and pairs. */
+int gpuart_nearest_overlap_counts(gpuart_nearest *h, uint64_t out[2]);
+
+/* The pairs of the bound scene: offsets: n_prims + 1 words, items: `capacity` ordinals — device memory, 4-byte aligned; asynchronous. The
+ * total is gpuart_nearest_overlap_total's; the fill takes the margin of the count and its offsets. Nothing is uploaded. */
+int gpuart_nearest_pairs_count(gpuart_nearest *h, const gpuart_hip_scene *scene, float margin, uint32_t *offsets);
+int gpuart_nearest_pairs_fill(gpuart_nearest *h, const gpuart_hip_scene *scene, float margin, const uint32_t *offsets, int32_t *items, size_t capacity);
+/* Both passes with the results in host memory, synchronous, staged over ranges of host_chunk ordinals (a launch takes a first ordinal); the
+ * two-call protocol of gpuart_nearest_overlap_host. */
+int gpuart_nearest_pairs_host(gpuart_nearest *h, const gpuart_hip_scene *scene, float margin, uint32_t *offsets, int32_t *items, size_t capacity,
+                              uint64_t *total);
+/* The definition of the pairs with no device: list i = the box query prim_boxes[i] with every j <= i removed. */
+int gpuart_nearest_pairs_brute_host(const float *recs, size_t n_recs, uint32_t root_ref, const float *prims, const float *prim_boxes, size_t n_prims,
+                                    float margin, uint32_t *offsets, int32_t *items, size_t capacity, uint64_t *total);
 
 #ifdef __cplusplus
 }
