@@ -1363,12 +1363,7 @@ class Backend:
         h = self._nearest_handle(scene)
         if type(points).__module__.startswith("torch"):
             import torch
-            if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous() or points.device.type != "cuda":
-                raise ValueError("points must be a contiguous (n, 4) float32 tensor on the GPU")
-            index = points.device.index if points.device.index is not None else torch.cuda.current_device()
-            if index != self.device:
-                raise ValueError("points is on cuda:%d, this context on device %d: the kernel reads the tensor's memory in place" % (index, self.device))
-            n = points.shape[0]
+            n = self._device_queries("points", points, 4)
             hits = out if out is not None else torch.empty((n, 8), dtype=torch.float32, device=points.device)
             if hits.dtype != torch.float32 or tuple(hits.shape) != (n, 8) or not hits.is_contiguous() or hits.device != points.device:
                 raise ValueError("out must be a contiguous (n, 8) float32 tensor on the points' device")
@@ -1398,12 +1393,7 @@ class Backend:
         h = self._nearest_handle(scene)
         if type(points).__module__.startswith("torch"):
             import torch
-            if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous() or points.device.type != "cuda":
-                raise ValueError("points must be a contiguous (n, 4) float32 tensor on the GPU")
-            index = points.device.index if points.device.index is not None else torch.cuda.current_device()
-            if index != self.device:
-                raise ValueError("points is on cuda:%d, this context on device %d: the kernel reads the tensor's memory in place" % (index, self.device))
-            n = points.shape[0]
+            n = self._device_queries("points", points, 4)
             hits = out if out is not None else torch.empty((n, k, 8), dtype=torch.float32, device=points.device)
             if hits.dtype != torch.float32 or tuple(hits.shape) != (n, k, 8) or not hits.is_contiguous() or hits.device != points.device:
                 raise ValueError("out must be a contiguous (n, k, 8) float32 tensor on the points' device")
@@ -1435,86 +1425,76 @@ class Backend:
             raise ValueError("max_items is negative")
         scene = self.scene_device()
         h = self._nearest_handle(scene)
-        total = C.c_uint64(0)
-
-        def refuse_above(total, rc=0):
-            if total > max_items:
-                raise ValueError("the lists hold %d items, more than max_items = %d" % (total, max_items))
-            h._chk(rc)
-
         if type(points).__module__.startswith("torch"):
             import torch
-            if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous() or points.device.type != "cuda":
-                raise ValueError("points must be a contiguous (n, 4) float32 tensor on the GPU")
-            index = points.device.index if points.device.index is not None else torch.cuda.current_device()
-            if index != self.device:
-                raise ValueError("points is on cuda:%d, this context on device %d: the kernel reads the tensor's memory in place" % (index, self.device))
-            n = points.shape[0]
-            offsets, items = out if out is not None else (None, None)
-            if offsets is None:
-                offsets = torch.zeros((n + 1,), dtype=torch.int32, device=points.device)
-            if offsets.dtype != torch.int32 or tuple(offsets.shape) != (n + 1,) or not offsets.is_contiguous() or offsets.device != points.device:
-                raise ValueError("out[0] must be a contiguous (n + 1,) int32 tensor on the points' device")
-            if items is not None and (items.dtype != torch.float32 or items.dim() != 2 or items.shape[1] != 8 or not items.is_contiguous() or
-                                      items.device != points.device):
-                raise ValueError("out[1] must be a contiguous (capacity, 8) float32 tensor on the points' device")
-            torch.cuda.current_stream(points.device).synchronize()
-            if n == 0:
-                offsets.zero_()
-                return offsets, items if items is not None else torch.empty((0, 8), dtype=torch.float32, device=points.device)
-            h._chk(N.gpuart_nearest_within_count(h, C.byref(scene), C.c_void_p(points.data_ptr()), C.c_size_t(n), us, C.c_void_p(offsets.data_ptr())))
-            rc = N.gpuart_nearest_within_total(h, C.byref(total))
-            refuse_above(total.value, rc)
-            if items is None:
-                items = torch.empty((total.value, 8), dtype=torch.float32, device=points.device)
-            elif items.shape[0] < total.value:
-                raise ValueError("out[1] has room for %d items, the lists hold %d" % (items.shape[0], total.value))
-            cap = items.shape[0]
-            h._chk(N.gpuart_nearest_within_fill(h, C.byref(scene), C.c_void_p(points.data_ptr()), C.c_size_t(n), us, C.c_void_p(offsets.data_ptr()),
-                                                C.c_void_p(items.data_ptr() if cap else None), C.c_size_t(cap)))
-            h.finish()
-            return offsets, items
+            n = self._device_queries("points", points, 4)
+            ptr = C.c_void_p(points.data_ptr())
+            return self._lists_device(N.gpuart_nearest_within_total, h, n, max_items, out, points.device, "the points' device", (8,), torch.float32,
+                                      lambda o: N.gpuart_nearest_within_count(h, C.byref(scene), ptr, C.c_size_t(n), us, o),
+                                      lambda o, it, cap: N.gpuart_nearest_within_fill(h, C.byref(scene), ptr, C.c_size_t(n), us, o, it, cap))
         if out is not None:
             raise ValueError("out goes with device tensors")
         points = _points_array(points)
-        n = points.shape[0]
-        offsets = np.zeros(n + 1, np.uint32)
-        args = (h, C.byref(scene), _p(points), C.c_size_t(n), us, _p(offsets))
-        rc = N.gpuart_nearest_within_host(*args, None, C.c_size_t(0), C.byref(total))
-        refuse_above(total.value, rc)
-        items = np.zeros(total.value, NEAREST_HIT)
-        if total.value:     # (the fill alone: the offsets are the count's of a moment ago)
-            h._chk(N.gpuart_nearest_within_fill_host(*args, _p(items), C.c_size_t(total.value)))
-        return offsets, items
+        args = (h, C.byref(scene), _p(points), C.c_size_t(points.shape[0]), us)
+        return self._lists_host(h, points.shape[0], max_items, NEAREST_HIT,
+                                lambda o, total: N.gpuart_nearest_within_host(*args, o, None, C.c_size_t(0), total),
+                                lambda o, it, cap, total: N.gpuart_nearest_within_fill_host(*args, o, it, cap))
 
-    def _overlap_device(self, N, h, scene, n, max_items, out, device, count, fill):
-        """The device route of overlaps and overlapping_pairs: count(offsets_ptr), the 8-byte total, fill(offsets_ptr, items_ptr, capacity),
-        with the tensors and checks of `within` (items: int32 (total,))."""
+    def _device_queries(self, name, t, columns):
+        """The queries of a device route: `t` is a contiguous (n, columns) float32 tensor on this context's device, or ValueError; n."""
+        import torch
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != columns or not t.is_contiguous() or t.device.type != "cuda":
+            raise ValueError("%s must be a contiguous (n, %d) float32 tensor on the GPU" % (name, columns))
+        index = t.device.index if t.device.index is not None else torch.cuda.current_device()
+        if index != self.device:
+            raise ValueError("%s is on cuda:%d, this context on device %d: the kernel reads the tensor's memory in place" % (name, index, self.device))
+        return t.shape[0]
+
+    def _lists_device(self, total_of, h, n, max_items, out, device, where, trailing, dtype, count, fill):
+        """The device route of within, overlaps and overlapping_pairs: count(offsets_ptr), the 8-byte total through the entry `total_of`,
+        fill(offsets_ptr, items_ptr, capacity). offsets: int32 (n + 1,); items: `dtype` (total, *trailing) — float32 records of 8 words,
+        or int32 ordinals —, both on `device`, which the messages call `where`; out = (offsets, items) or None."""
         import torch
         total = C.c_uint64(0)
         offsets, items = out if out is not None else (None, None)
         if offsets is None:
             offsets = torch.zeros((n + 1,), dtype=torch.int32, device=device)
         if offsets.dtype != torch.int32 or tuple(offsets.shape) != (n + 1,) or not offsets.is_contiguous() or offsets.device != device:
-            raise ValueError("out[0] must be a contiguous (n + 1,) int32 tensor on the context's device")
-        if items is not None and (items.dtype != torch.int32 or items.dim() != 1 or not items.is_contiguous() or items.device != device):
-            raise ValueError("out[1] must be a contiguous (capacity,) int32 tensor on the context's device")
+            raise ValueError("out[0] must be a contiguous (n + 1,) int32 tensor on " + where)
+        if items is not None and (items.dtype != dtype or items.dim() != 1 + len(trailing) or tuple(items.shape[1:]) != trailing or not items.is_contiguous() or
+                                  items.device != device):
+            raise ValueError("out[1] must be a contiguous (capacity%s) %s tensor on %s" % ("".join(", %d" % d for d in trailing) or ",", str(dtype).split(".")[-1], where))
         torch.cuda.current_stream(device).synchronize()
         if n == 0:
             offsets.zero_()
-            return offsets, items if items is not None else torch.empty((0,), dtype=torch.int32, device=device)
+            return offsets, items if items is not None else torch.empty((0, *trailing), dtype=dtype, device=device)
         h._chk(count(C.c_void_p(offsets.data_ptr())))
-        rc = N.gpuart_nearest_overlap_total(h, C.byref(total))
+        rc = total_of(h, C.byref(total))
         if total.value > max_items:
             raise ValueError("the lists hold %d items, more than max_items = %d" % (total.value, max_items))
         h._chk(rc)
         if items is None:
-            items = torch.empty((total.value,), dtype=torch.int32, device=device)
+            items = torch.empty((total.value, *trailing), dtype=dtype, device=device)
         elif items.shape[0] < total.value:
             raise ValueError("out[1] has room for %d items, the lists hold %d" % (items.shape[0], total.value))
         cap = items.shape[0]
         h._chk(fill(C.c_void_p(offsets.data_ptr()), C.c_void_p(items.data_ptr() if cap else None), C.c_size_t(cap)))
         h.finish()
+        return offsets, items
+
+    @staticmethod
+    def _lists_host(h, n, max_items, item_dtype, count, fill):
+        """The host route of the same three: count(offsets_p, total_ref) with no items, a total above max_items refused, the items
+        allocated, fill(offsets_p, items_p, capacity, total_ref) unless there are none: (offsets uint32 (n + 1,), items)."""
+        offsets = np.zeros(n + 1, np.uint32)
+        total = C.c_uint64(0)
+        rc = count(_p(offsets), C.byref(total))
+        if total.value > max_items:
+            raise ValueError("the lists hold %d items, more than max_items = %d" % (total.value, max_items))
+        h._chk(rc)
+        items = np.zeros(total.value, item_dtype)
+        if total.value:     # (the fill alone where the library has one: the offsets are the count's of a moment ago)
+            h._chk(fill(_p(offsets), _p(items), C.c_size_t(total.value), C.byref(total)))
         return offsets, items
 
     @staticmethod
@@ -1542,33 +1522,20 @@ class Backend:
         m = C.c_float(margin)
         if type(boxes).__module__.startswith("torch"):
             import torch
-            if boxes.dtype != torch.float32 or boxes.dim() != 2 or boxes.shape[1] != 6 or not boxes.is_contiguous() or boxes.device.type != "cuda":
-                raise ValueError("boxes must be a contiguous (n, 6) float32 tensor on the GPU")
-            index = boxes.device.index if boxes.device.index is not None else torch.cuda.current_device()
-            if index != self.device:
-                raise ValueError("boxes is on cuda:%d, this context on device %d: the kernel reads the tensor's memory in place" % (index, self.device))
-            n = boxes.shape[0]
+            n = self._device_queries("boxes", boxes, 6)
             ptr = C.c_void_p(boxes.data_ptr() if n else None)
-            return self._overlap_device(N, h, scene, n, max_items, out, boxes.device,
-                                        lambda o: N.gpuart_nearest_overlap_count(h, C.byref(scene), ptr, C.c_size_t(n), m, us, o),
-                                        lambda o, it, cap: N.gpuart_nearest_overlap_fill(h, C.byref(scene), ptr, C.c_size_t(n), m, us, o, it, cap))
+            return self._lists_device(N.gpuart_nearest_overlap_total, h, n, max_items, out, boxes.device, "the context's device", (), torch.int32,
+                                      lambda o: N.gpuart_nearest_overlap_count(h, C.byref(scene), ptr, C.c_size_t(n), m, us, o),
+                                      lambda o, it, cap: N.gpuart_nearest_overlap_fill(h, C.byref(scene), ptr, C.c_size_t(n), m, us, o, it, cap))
         if out is not None:
             raise ValueError("out goes with device tensors")
         boxes = np.ascontiguousarray(boxes, np.float32)
         if boxes.ndim != 2 or boxes.shape[1] != 6:
             raise ValueError("boxes must be (n, 6): lo.xyz, hi.xyz")
-        n = boxes.shape[0]
-        offsets = np.zeros(n + 1, np.uint32)
-        total = C.c_uint64(0)
-        args = (h, C.byref(scene), _p(boxes), C.c_size_t(n), m, us, _p(offsets))
-        rc = N.gpuart_nearest_overlap_host(*args, None, C.c_size_t(0), C.byref(total))
-        if total.value > max_items:
-            raise ValueError("the lists hold %d items, more than max_items = %d" % (total.value, max_items))
-        h._chk(rc)
-        items = np.zeros(total.value, np.int32)
-        if total.value:     # (the fill alone: the offsets are the count's of a moment ago)
-            h._chk(N.gpuart_nearest_overlap_fill_host(*args, _p(items), C.c_size_t(total.value)))
-        return offsets, items
+        args = (h, C.byref(scene), _p(boxes), C.c_size_t(boxes.shape[0]), m, us)
+        return self._lists_host(h, boxes.shape[0], max_items, np.int32,
+                                lambda o, total: N.gpuart_nearest_overlap_host(*args, o, None, C.c_size_t(0), total),
+                                lambda o, it, cap, total: N.gpuart_nearest_overlap_fill_host(*args, o, it, cap))
 
     def overlapping_pairs(self, margin=0.0, max_items=1 << 27, device=False, out=None, as_pairs=False):
         """The overlapping pairs of the scene's own primitives (include/gpuart_nearest.h "Box overlap", pairs): list i holds the ordinals
@@ -1589,9 +1556,9 @@ class Backend:
         if device:
             import torch
             dev = torch.device("cuda", self.device)
-            offsets, items = self._overlap_device(N, h, scene, n, max_items, out, dev,
-                                                  lambda o: N.gpuart_nearest_pairs_count(h, C.byref(scene), m, o),
-                                                  lambda o, it, cap: N.gpuart_nearest_pairs_fill(h, C.byref(scene), m, o, it, cap))
+            offsets, items = self._lists_device(N.gpuart_nearest_overlap_total, h, n, max_items, out, dev, "the context's device", (), torch.int32,
+                                                lambda o: N.gpuart_nearest_pairs_count(h, C.byref(scene), m, o),
+                                                lambda o, it, cap: N.gpuart_nearest_pairs_fill(h, C.byref(scene), m, o, it, cap))
             if not as_pairs:
                 return offsets, items
             total = int(offsets[-1].item())
@@ -1599,15 +1566,9 @@ class Backend:
             return torch.stack([i, items[:total]], 1)
         if out is not None:
             raise ValueError("out goes with device=True")
-        offsets = np.zeros(n + 1, np.uint32)
-        total = C.c_uint64(0)
-        rc = N.gpuart_nearest_pairs_host(h, C.byref(scene), m, _p(offsets), None, C.c_size_t(0), C.byref(total))
-        if total.value > max_items:
-            raise ValueError("the lists hold %d items, more than max_items = %d" % (total.value, max_items))
-        h._chk(rc)
-        items = np.zeros(total.value, np.int32)
-        if total.value:
-            h._chk(N.gpuart_nearest_pairs_host(h, C.byref(scene), m, _p(offsets), _p(items), C.c_size_t(total.value), C.byref(total)))
+        offsets, items = self._lists_host(h, n, max_items, np.int32,
+                                          lambda o, total: N.gpuart_nearest_pairs_host(h, C.byref(scene), m, o, None, C.c_size_t(0), total),
+                                          lambda o, it, cap, total: N.gpuart_nearest_pairs_host(h, C.byref(scene), m, o, it, cap, total))
         if not as_pairs:
             return offsets, items
         i = np.repeat(np.arange(n, dtype=np.int32), np.diff(offsets.astype(np.int64)))

@@ -8,7 +8,11 @@
 // Behind them the k nearest of the same header: k_knn, a fourth lane type of that walk, whose best so far is a list of k in LDS (DESIGN.md
 // "k nearest", profiles/knn.txt). Behind them box overlap: k_overlap_count and k_overlap_fill, a fifth lane type whose query is a box and whose
 // candidates are the primitives' boxes — box queries and, with the scene's own boxes as the queries, overlapping pairs (DESIGN.md "Box
-// overlap", profiles/overlap.txt).
+// overlap", profiles/overlap.txt). What two lane types share is stated once beside what all share: the ordered record step of k_nearest and
+// k_knn (k_knn keeps its record branch written out: as a call it costs two VGPRs) and the list lane — at, end, sum, begin, finish, next
+// node, body — of k_within and k_overlap, whose lower-first record steps stay in place; on the host one timed launch, one count and one fill launch, one staged CSR run, one fill
+// check and one check of caller-given offsets for the three kinds of list, one launch and one chunk loop for k_nearest and k_knn
+// (profiles/nearest_lists.txt).
 //
 // Compile-time switches (tools/nearest_time.py builds the variants; the shipped library sets none):
 //   NEAREST_PLAIN   the kernels as one thread per query with a grid stride and no refill: the A/B partner of the persistent-lane form
@@ -205,16 +209,21 @@ __device__ __forceinline__ void walk_leaf(const SceneView &sc, uint32_t ref, Can
     }
 }
 
-/// Query i enters the lane: its point and radius, an empty stack, counters at zero. Returns the radius as the caller gave it.
-__device__ __forceinline__ float take_query(Walk &L, const float4 *points, uint32_t i) {
-    const float4 pt = points[i];
+/// Query i enters the lane: an empty stack, counters at zero.
+__device__ __forceinline__ void reset_walk(Walk &L, uint32_t i) {
     L.qi = i;
-    L.p[0] = pt.x; L.p[1] = pt.y; L.p[2] = pt.z;
-    L.r2 = pt.w * pt.w;
     L.sp = L.spilled = 0;
 #ifdef NEAREST_COUNT
     L.boxes = L.tests = 0;
 #endif
+}
+
+/// Query i, a point and a radius, enters the lane. Returns the radius as the caller gave it.
+__device__ __forceinline__ float take_query(Walk &L, const float4 *points, uint32_t i) {
+    const float4 pt = points[i];
+    reset_walk(L, i);
+    L.p[0] = pt.x; L.p[1] = pt.y; L.p[2] = pt.z;
+    L.r2 = pt.w * pt.w;
     return pt.w;
 }
 
@@ -282,6 +291,107 @@ __device__ __forceinline__ L_ walk_queries(const Stack<E> &st, const A &a) {
     return L;
 }
 
+/// The record `ref`, read whole: both children's boxes and refs.
+struct Record {
+    float l0[3], h0[3], l1[3], h1[3];
+    uint32_t rlo, rhi;
+
+    __device__ __forceinline__ Record(const SceneView &sc, uint32_t ref) {
+        const float4 *rec = sc.recs + 4u * ref;  // (base + 32-bit offset: 4 * n_recs <= 2^30)
+        const float4 ra = rec[0], rb = rec[1], rc = rec[2], rd = rec[3];
+        xyz(ra, l0); xyz(rb, h0); xyz(rc, l1); xyz(rd, h1);
+        rlo = __float_as_uint(ra.w);
+        rhi = __float_as_uint(rb.w);
+    }
+};
+
+/// The ordered record step (k_nearest; of k_knn, whose record branch stays written out, the pop). Like begin and step it finds what differs
+/// by the lane's type: skip(L, a, d2) — a box at d2 cannot hold anything the query still wants — and walk_ended(L, a). The lower-first step
+/// of the lists stays in their steps: with the box test behind a hook, a member or a callable the four kernels' instructions move
+/// (profiles/nearest_lists.txt).
+/// The next node off the stack that is not skipped by now, or the end of the walk.
+template <class L_, class A>
+__device__ __forceinline__ void next_ordered(L_ &L, const Stack<uint2> &st, const A &a) {
+    for (;;) {
+        if (L.sp == 0) { walk_ended(L, a); return; }
+        const uint2 e = st.pop(L);
+        if (!skip(L, a, __uint_as_float(e.y))) { L.node = e.x; return; }
+    }
+}
+
+/// The ordered step (k_nearest, k_knn): the nearer child is entered, the farther stacked with its distance, each unless it is skipped.
+template <class L_, class A>
+__device__ __forceinline__ void ordered_record(L_ &L, const Stack<uint2> &st, const A &a, uint32_t ref) {
+    const Record r(a.sc, ref);
+    const float dlo = nr::box_d2(r.l0, r.h0, L.p), dhi = nr::box_d2(r.l1, r.h1, L.p);
+    const bool klo = !skip(L, a, dlo), khi = !skip(L, a, dhi);
+#ifdef NEAREST_COUNT
+    L.boxes++;
+#endif
+    if (klo && khi) {
+        const bool upper_first = dhi < dlo;
+        st.push(L, make_uint2(upper_first ? r.rlo : r.rhi, __float_as_uint(upper_first ? dlo : dhi)));
+        L.node = upper_first ? r.rhi : r.rlo;
+    } else if (klo) L.node = r.rlo;
+    else if (khi) L.node = r.rhi;
+    else next_ordered(L, st, a);
+}
+
+/// A lane of the lists (k_within, k_overlap): nothing that is found prunes anything, so a stack entry is the ref alone, a record's children
+/// are entered lower first — the contract's order of a list — and what comes off the stack is not tested again. The count leaves each
+/// list's length at offsets[qi] and sums the lengths of the lane's queries; the fill writes list qi from offsets[qi] on, in the walk's order.
+/// Q: what the kind's query holds beyond a point and a radius, ahead of the list's own members (behind them k_overlap's instructions move).
+struct PointQuery {};
+template <class Q>
+struct ListLane : Walk, Q {
+    uint32_t at, end;            ///< count: the items so far, unused; fill: where the next item goes, and where the list ends
+    unsigned long long sum = 0;  ///< count: the items of all lists this lane has finished
+};
+
+/// Query i's list begins: empty for the count, between its two offsets for the fill.
+template <class L_, class A>
+__device__ __forceinline__ void list_begin(L_ &L, const A &a, uint32_t i) {
+    L.at = L.end = 0;
+    if (L_::FILLS) { L.at = a.offsets[i]; L.end = a.offsets[i + 1u]; }
+}
+
+/// The walk has ended: the count stores the list's length, the fill holds the list to its offsets; the lane is idle. counters(L): the
+/// first of the lane kind's two NEAREST_COUNT members of the status.
+template <class L_, class A>
+__device__ __forceinline__ void list_finish(L_ &L, const A &a) {
+    if (L_::FILLS) {
+        if (L.at != L.end) a.status->mismatch = 1u;
+    } else {
+        a.offsets[L.qi] = L.at;
+        L.sum += L.at;
+    }
+#ifdef NEAREST_COUNT
+    unsigned long long *c = &(a.status->*counters(L));
+    atomicAdd(c, (unsigned long long)L.boxes);
+    atomicAdd(c + 1, (unsigned long long)L.tests);
+#endif
+    L.qi = NONE;
+}
+
+template <class L_, class A>
+__device__ __forceinline__ void list_next(L_ &L, const Stack<uint32_t> &st, const A &a) {
+    if (L.sp == 0) { list_finish(L, a); return; }
+    L.node = st.pop(L);  // (what was stacked was not pruned, and nothing has changed since: there is no best so far)
+}
+
+/// A list kernel's body: the lengths of a wave's queries, summed in 64 bits lane by lane and then across the wave, go to the status' total
+/// with one atomic per wave at the end of its life.
+template <class L_, class A>
+__device__ __forceinline__ void list_body(const A &a, uint32_t *ring) {
+    const Stack<uint32_t> st(ring, a.spill, a.cap, a.status);
+    const L_ L = walk_queries<L_>(st, a);
+    if (!L_::FILLS) {
+        unsigned long long sum = L.sum;
+        for (int d = 32; d > 0; d >>= 1) sum += __shfl_down(sum, d, 64);
+        if ((threadIdx.x & 63u) == 0 && sum) atomicAdd(&a.status->total, sum);
+    }
+}
+
 // ---- closest points: k_nearest ----------------------------------------------------------------------------------------------------------
 struct Launch {
     SceneView sc;
@@ -335,14 +445,8 @@ __device__ __forceinline__ void finish(Lane &L, const Launch &a) {
     L.qi = NONE;
 }
 
-/// The next node off the stack that is not pruned by now, or the end of the walk.
-__device__ __forceinline__ void next_node(Lane &L, const Stack<uint2> &st, const Launch &a) {
-    for (;;) {
-        if (L.sp == 0) { finish(L, a); return; }
-        const uint2 e = st.pop(L);
-        if (!nr::pruned(__uint_as_float(e.y), L.r2, L.best)) { L.node = e.x; return; }
-    }
-}
+__device__ __forceinline__ bool skip(const Lane &L, const Launch &, float d2) { return nr::pruned(d2, L.r2, L.best); }
+__device__ __forceinline__ void walk_ended(Lane &L, const Launch &a) { finish(L, a); }
 
 /// Query i begins: a miss at once, or the user sphere as the first candidate and the root.
 __device__ __forceinline__ void begin(Lane &L, const Stack<uint2> &, const Launch &a, uint32_t i) {
@@ -359,31 +463,12 @@ __device__ __forceinline__ void begin(Lane &L, const Stack<uint2> &, const Launc
     L.node = a.sc.root_ref;
 }
 
-/// One step of a lane's walk: a record (both boxes, the nearer child entered, the farther stacked with its distance) or a leaf.
+/// One step of a lane's walk: a record (the ordered step) or a leaf.
 __device__ __forceinline__ void step(Lane &L, const Stack<uint2> &st, const Launch &a) {
     const uint32_t ref = L.node;
-    if (!(ref & REF_LEAF)) {
-        const float4 *rec = a.sc.recs + 4u * ref;  // (base + 32-bit offset: 4 * n_recs <= 2^30)
-        const float4 ra = rec[0], rb = rec[1], rc = rec[2], rd = rec[3];
-        float l0[3], h0[3], l1[3], h1[3];
-        xyz(ra, l0); xyz(rb, h0); xyz(rc, l1); xyz(rd, h1);
-        const float dlo = nr::box_d2(l0, h0, L.p), dhi = nr::box_d2(l1, h1, L.p);
-        const uint32_t rlo = __float_as_uint(ra.w), rhi = __float_as_uint(rb.w);
-        const bool klo = !nr::pruned(dlo, L.r2, L.best), khi = !nr::pruned(dhi, L.r2, L.best);
-#ifdef NEAREST_COUNT
-        L.boxes++;
-#endif
-        if (klo && khi) {
-            const bool upper_first = dhi < dlo;
-            st.push(L, make_uint2(upper_first ? rlo : rhi, __float_as_uint(upper_first ? dlo : dhi)));
-            L.node = upper_first ? rhi : rlo;
-        } else if (klo) L.node = rlo;
-        else if (khi) L.node = rhi;
-        else next_node(L, st, a);
-        return;
-    }
+    if (!(ref & REF_LEAF)) { ordered_record(L, st, a, ref); return; }
     walk_leaf(a.sc, ref, [&](uint32_t type, const PrimData &d, uint32_t ord) { candidate(L, type, d, ord); });
-    next_node(L, st, a);
+    next_ordered(L, st, a);
 }
 
 // k_nearest. Types are branched on at run time (closest_on_prim): the descriptor does not carry the type mask, and one launch per mask would
@@ -396,8 +481,7 @@ __global__ void __launch_bounds__(BLOCK) k_nearest(Launch a) {
 }
 
 // ---- the neighbour lists: k_within_count and k_within_fill ------------------------------------------------------------------------------
-// The walk of k_nearest without a best so far: nothing that is found prunes anything, so a stack entry is the ref alone, a record's children
-// are entered lower first — the contract's order of a list — and what comes off the stack is not tested again.
+// The walk of k_nearest without a best so far, as a list lane: an item is the 32-byte record of a primitive within r.
 struct WLaunch {
     SceneView sc;
     const float4 *points;
@@ -414,10 +498,11 @@ struct WLaunch {
 };
 
 template <bool FILL>
-struct WLane : Walk {
-    uint32_t at, end;        ///< count: the items so far, unused; fill: where the next item goes, and where the list ends
-    unsigned long long sum = 0;  ///< count: the items of all lists this lane has finished
+struct WLane : ListLane<PointQuery> {
+    static constexpr bool FILLS = FILL;
 };
+template <bool FILL>
+__device__ __forceinline__ unsigned long long Status::*counters(const WLane<FILL> &) { return &Status::w_box_steps; }
 
 /// One candidate: an item of the list if it is accepted. The fill stores it where the offsets put it, and nowhere else: an index at or
 /// beyond the list's end or the capacity is not written and marks the run.
@@ -442,92 +527,52 @@ __device__ __forceinline__ void candidate(WLane<FILL> &L, const WLaunch &a, uint
 #endif
 }
 
-/// The walk has ended: the count stores the list's length, the fill holds the list to its offsets; the lane is idle.
-template <bool FILL>
-__device__ __forceinline__ void finish(WLane<FILL> &L, const WLaunch &a) {
-    if (FILL) {
-        if (L.at != L.end) a.status->mismatch = 1u;
-    } else {
-        a.offsets[L.qi] = L.at;
-        L.sum += L.at;
-    }
-#ifdef NEAREST_COUNT
-    atomicAdd(&a.status->w_box_steps, (unsigned long long)L.boxes);
-    atomicAdd(&a.status->w_prim_tests, (unsigned long long)L.tests);
-#endif
-    L.qi = NONE;
-}
-
-template <bool FILL>
-__device__ __forceinline__ void next_node(WLane<FILL> &L, const Stack<uint32_t> &st, const WLaunch &a) {
-    if (L.sp == 0) { finish(L, a); return; }
-    L.node = st.pop(L);  // (what was stacked was not pruned, and nothing has changed since: there is no best so far)
-}
-
 /// Query i begins: an empty list at once, or the user sphere as the first candidate and the root.
 template <bool FILL>
 __device__ __forceinline__ void begin(WLane<FILL> &L, const Stack<uint32_t> &, const WLaunch &a, uint32_t i) {
     const float r = take_query(L, a.points, i);
-    L.at = L.end = 0;
-    if (FILL) { L.at = a.offsets[i]; L.end = a.offsets[i + 1u]; }
-    if (!nr::query_ok(L.p, r)) { finish(L, a); return; }
+    list_begin(L, a, i);
+    if (!nr::query_ok(L.p, r)) { list_finish(L, a); return; }
     if (a.use_us) {
         PrimData d;
         user_sphere_prim(a.us.x, a.us.y, a.us.z, a.us.w, d);
         candidate(L, a, nr::SPHERE, d, nr::USER_SPHERE);
     }
-    if (nr::within_pruned(nr::box_d2(a.sc.root_lo, a.sc.root_hi, L.p), L.r2)) { finish(L, a); return; }
+    if (nr::within_pruned(nr::box_d2(a.sc.root_lo, a.sc.root_hi, L.p), L.r2)) { list_finish(L, a); return; }
     L.node = a.sc.root_ref;
 }
 
-/// One step of a lane's walk: a record (both boxes; the lower child entered, the upper stacked, each unless pruned) or a leaf.
+/// One step of a lane's walk: a record (both boxes, lower child first) or a leaf.
 template <bool FILL>
 __device__ __forceinline__ void step(WLane<FILL> &L, const Stack<uint32_t> &st, const WLaunch &a) {
     const uint32_t ref = L.node;
-    if (!(ref & REF_LEAF)) {
-        const float4 *rec = a.sc.recs + 4u * ref;
-        const float4 ra = rec[0], rb = rec[1], rc = rec[2], rd = rec[3];
-        float l0[3], h0[3], l1[3], h1[3];
-        xyz(ra, l0); xyz(rb, h0); xyz(rc, l1); xyz(rd, h1);
-        const bool klo = !nr::within_pruned(nr::box_d2(l0, h0, L.p), L.r2), khi = !nr::within_pruned(nr::box_d2(l1, h1, L.p), L.r2);
-        const uint32_t rlo = __float_as_uint(ra.w), rhi = __float_as_uint(rb.w);
+    if (!(ref & REF_LEAF)) {  // the lower child is entered, the upper stacked, each unless pruned
+        const Record r(a.sc, ref);
+        const bool klo = !nr::within_pruned(nr::box_d2(r.l0, r.h0, L.p), L.r2), khi = !nr::within_pruned(nr::box_d2(r.l1, r.h1, L.p), L.r2);
 #ifdef NEAREST_COUNT
         L.boxes++;
 #endif
         if (klo && khi) {
-            st.push(L, rhi);
-            L.node = rlo;
-        } else if (klo) L.node = rlo;
-        else if (khi) L.node = rhi;
-        else next_node(L, st, a);
+            st.push(L, r.rhi);
+            L.node = r.rlo;
+        } else if (klo) L.node = r.rlo;
+        else if (khi) L.node = r.rhi;
+        else list_next(L, st, a);
         return;
     }
     walk_leaf(a.sc, ref, [&](uint32_t type, const PrimData &d, uint32_t ord) { candidate(L, a, type, d, ord); });
-    next_node(L, st, a);
+    list_next(L, st, a);
 }
 
-// k_within_count (FILL = false) and k_within_fill (FILL = true). The count leaves each list's length at offsets[qi] and adds the lengths of
-// a wave's queries, summed in 64 bits lane by lane and then across the wave, to the status' total with one atomic per wave at the end of
-// its life. The fill writes list qi from offsets[qi] on, in the order of the walk.
-template <bool FILL>
-__device__ __forceinline__ void within_body(const WLaunch &a, uint32_t *ring) {
-    const Stack<uint32_t> st(ring, a.spill, a.cap, a.status);
-    const WLane<FILL> L = walk_queries<WLane<FILL>>(st, a);
-    if (!FILL) {
-        unsigned long long sum = L.sum;
-        for (int d = 32; d > 0; d >>= 1) sum += __shfl_down(sum, d, 64);
-        if ((threadIdx.x & 63u) == 0 && sum) atomicAdd(&a.status->total, sum);
-    }
-}
-
+// k_within_count (FILL = false) and k_within_fill (FILL = true).
 __global__ void __launch_bounds__(BLOCK) k_within_count(WLaunch a) {
     __shared__ uint32_t ring[RING * BLOCK];
-    within_body<false>(a, ring);
+    list_body<WLane<false>>(a, ring);
 }
 
 __global__ void __launch_bounds__(BLOCK) k_within_fill(WLaunch a) {
     __shared__ uint32_t ring[RING * BLOCK];
-    within_body<true>(a, ring);
+    list_body<WLane<true>>(a, ring);
 }
 
 // ---- the k nearest: k_knn -----------------------------------------------------------------------------------------------------------------
@@ -635,7 +680,10 @@ __device__ __forceinline__ void keep(KLane<CAP> &L, const KnnLaunch &a, float d2
 }
 
 template <uint32_t CAP>
-__device__ __forceinline__ bool knn_skip(const KLane<CAP> &L, const KnnLaunch &a, float b) { return nr::knn_pruned(b, L.r2, L.kept == a.k, L.worst); }
+__device__ __forceinline__ bool skip(const KLane<CAP> &L, const KnnLaunch &a, float d2) { return nr::knn_pruned(d2, L.r2, L.kept == a.k, L.worst); }
+/// The walk has ended; the next step sorts the kept.
+template <uint32_t CAP>
+__device__ __forceinline__ void walk_ended(KLane<CAP> &L, const KnnLaunch &) { L.node = WALKED; }
 
 /// The walk has ended: the heap is sorted in place (the root goes behind the heap, which shrinks by one) and the miss record fills the
 /// slots behind the kept. With nothing kept the query is answered and the lane is idle; else the records follow, one a step.
@@ -673,16 +721,6 @@ __device__ __forceinline__ void write_kept(KLane<CAP> &L, const KnnLaunch &a, ui
     }
 }
 
-/// The next node off the stack that is not pruned by now, or the end of the walk.
-template <uint32_t CAP>
-__device__ __forceinline__ void next_node(KLane<CAP> &L, const Stack<uint2> &st, const KnnLaunch &a) {
-    for (;;) {
-        if (L.sp == 0) { L.node = WALKED; return; }
-        const uint2 e = st.pop(L);
-        if (!knn_skip(L, a, __uint_as_float(e.y))) { L.node = e.x; return; }
-    }
-}
-
 /// The walk begins at the root, unless the root is pruned already.
 template <uint32_t CAP>
 __device__ __forceinline__ void enter_root(KLane<CAP> &L, const KnnLaunch &a) {
@@ -691,7 +729,7 @@ __device__ __forceinline__ void enter_root(KLane<CAP> &L, const KnnLaunch &a) {
         lo[c] = launch_word(offsetof(KnnLaunch, sc.root_lo) + 4 * c);
         hi[c] = launch_word(offsetof(KnnLaunch, sc.root_hi) + 4 * c);
     }
-    L.node = knn_skip(L, a, nr::box_d2(lo, hi, L.p)) ? WALKED : a.sc.root_ref;
+    L.node = skip(L, a, nr::box_d2(lo, hi, L.p)) ? WALKED : a.sc.root_ref;
 }
 
 /// Query i begins: its walk has ended at once, or its first node is the user sphere, or the root.
@@ -735,14 +773,14 @@ __device__ __forceinline__ void step(KLane<CAP> &L, const Stack<uint2> &st, cons
         }
         return;
     }
-    if (!(ref & REF_LEAF)) {
+    if (!(ref & REF_LEAF)) {  // ordered_record, written out: as a call of it this kernel takes 96 VGPRs for 94 (profiles/nearest_lists.txt)
         const float4 *rec = a.sc.recs + 4u * ref;
         const float4 ra = rec[0], rb = rec[1], rc = rec[2], rd = rec[3];
         float l0[3], h0[3], l1[3], h1[3];
         xyz(ra, l0); xyz(rb, h0); xyz(rc, l1); xyz(rd, h1);
         const float dlo = nr::box_d2(l0, h0, L.p), dhi = nr::box_d2(l1, h1, L.p);
         const uint32_t rlo = __float_as_uint(ra.w), rhi = __float_as_uint(rb.w);
-        const bool klo = !knn_skip(L, a, dlo), khi = !knn_skip(L, a, dhi);
+        const bool klo = !skip(L, a, dlo), khi = !skip(L, a, dhi);
 #ifdef NEAREST_COUNT
         L.boxes++;
 #endif
@@ -752,7 +790,7 @@ __device__ __forceinline__ void step(KLane<CAP> &L, const Stack<uint2> &st, cons
             L.node = upper_first ? rhi : rlo;
         } else if (klo) L.node = rlo;
         else if (khi) L.node = rhi;
-        else next_node(L, st, a);
+        else next_ordered(L, st, a);
         return;
     }
     walk_leaf(a.sc, ref, [&](uint32_t type, const PrimData &d, uint32_t ord) {
@@ -767,7 +805,7 @@ __device__ __forceinline__ void step(KLane<CAP> &L, const Stack<uint2> &st, cons
 #endif
         }
     });
-    if (!writing) next_node(L, st, a);
+    if (!writing) next_ordered(L, st, a);
 }
 
 // k_knn<CAP>: lists of up to CAP entries, CAP * 2 KiB of LDS per workgroup beside the ring's 16 KiB. The occupancy is the LDS's: the host
@@ -816,13 +854,16 @@ struct OLaunch {
     Status *status;
 };
 
-template <bool FILL>
-struct OLane : Walk {
-    float qlo[3], qhi[3];        ///< the inflated query
-    uint32_t self;               ///< pairs: the query's own ordinal
-    uint32_t at, end;            ///< count: the items so far, unused; fill: where the next item goes, and where the list ends
-    unsigned long long sum = 0;  ///< count: the items of all lists this lane has finished
+struct BoxQuery {
+    float qlo[3], qhi[3];  ///< the inflated query
+    uint32_t self;         ///< pairs: the query's own ordinal
 };
+template <bool FILL>
+struct OLane : ListLane<BoxQuery> {
+    static constexpr bool FILLS = FILL;
+};
+template <bool FILL>
+__device__ __forceinline__ unsigned long long Status::*counters(const OLane<FILL> &) { return &Status::o_box_steps; }
 
 /// One candidate: the box [blo, bhi] of ordinal `ord`. The fill stores an item where the offsets put it, and nowhere else.
 template <bool FILL>
@@ -837,27 +878,6 @@ __device__ __forceinline__ void offer(OLane<FILL> &L, const OLaunch &a, uint32_t
 #ifdef NEAREST_COUNT
     L.tests++;
 #endif
-}
-
-template <bool FILL>
-__device__ __forceinline__ void finish(OLane<FILL> &L, const OLaunch &a) {
-    if (FILL) {
-        if (L.at != L.end) a.status->mismatch = 1u;
-    } else {
-        a.offsets[L.qi] = L.at;
-        L.sum += L.at;
-    }
-#ifdef NEAREST_COUNT
-    atomicAdd(&a.status->o_box_steps, (unsigned long long)L.boxes);
-    atomicAdd(&a.status->o_prim_tests, (unsigned long long)L.tests);
-#endif
-    L.qi = NONE;
-}
-
-template <bool FILL>
-__device__ __forceinline__ void next_node(OLane<FILL> &L, const Stack<uint32_t> &st, const OLaunch &a) {
-    if (L.sp == 0) { finish(L, a); return; }
-    L.node = st.pop(L);
 }
 
 __device__ __forceinline__ void load_box(const SceneView &sc, uint32_t i, float b[6]) {
@@ -888,77 +908,74 @@ template <bool FILL>
 __device__ __forceinline__ void begin(OLane<FILL> &L, const Stack<uint32_t> &, const OLaunch &a, uint32_t i) {
     const float *b = a.boxes + 6 * (size_t)i;
     const float box[6] = {b[0], b[1], b[2], b[3], b[4], b[5]};
-    L.qi = i;
+    reset_walk(L, i);
     L.self = a.self0 + i;
-    L.sp = L.spilled = 0;
-#ifdef NEAREST_COUNT
-    L.boxes = L.tests = 0;
-#endif
-    L.at = L.end = 0;
-    if (FILL) { L.at = a.offsets[i]; L.end = a.offsets[i + 1u]; }
+    list_begin(L, a, i);
     nr::overlap_inflate(box, a.margin, L.qlo, L.qhi);
-    if (!nr::overlap_query_ok(box)) { finish(L, a); return; }
+    if (!nr::overlap_query_ok(box)) { list_finish(L, a); return; }
     if (a.use_us) {
         PrimData d;
         user_sphere_prim(a.us.x, a.us.y, a.us.z, a.us.w, d);
         offer(L, a, nr::USER_SPHERE, d.box, d.box + 3);
     }
-    if (!nr::overlap_test(L.qlo, L.qhi, a.sc.root_lo, a.sc.root_hi)) { finish(L, a); return; }
+    if (!nr::overlap_test(L.qlo, L.qhi, a.sc.root_lo, a.sc.root_hi)) { list_finish(L, a); return; }
     L.node = a.sc.root_ref;
 }
 
-/// One step of a lane's walk: a record (both boxes; the lower child entered, the upper stacked, each unless it misses the query) or a leaf.
+/// One step of a lane's walk: a record (both boxes, lower child first) or a leaf.
 template <bool FILL>
 __device__ __forceinline__ void step(OLane<FILL> &L, const Stack<uint32_t> &st, const OLaunch &a) {
     const uint32_t ref = L.node;
-    if (!(ref & REF_LEAF)) {
-        const float4 *rec = a.sc.recs + 4u * ref;
-        const float4 ra = rec[0], rb = rec[1], rc = rec[2], rd = rec[3];
-        float l0[3], h0[3], l1[3], h1[3];
-        xyz(ra, l0); xyz(rb, h0); xyz(rc, l1); xyz(rd, h1);
-        const bool klo = nr::overlap_test(L.qlo, L.qhi, l0, h0), khi = nr::overlap_test(L.qlo, L.qhi, l1, h1);
-        const uint32_t rlo = __float_as_uint(ra.w), rhi = __float_as_uint(rb.w);
+    if (!(ref & REF_LEAF)) {  // the lower child is entered, the upper stacked, each unless it misses the query
+        const Record r(a.sc, ref);
+        const bool klo = nr::overlap_test(L.qlo, L.qhi, r.l0, r.h0), khi = nr::overlap_test(L.qlo, L.qhi, r.l1, r.h1);
 #ifdef NEAREST_COUNT
         L.boxes++;
 #endif
         if (klo && khi) {
-            st.push(L, rhi);
-            L.node = rlo;
-        } else if (klo) L.node = rlo;
-        else if (khi) L.node = rhi;
-        else next_node(L, st, a);
+            st.push(L, r.rhi);
+            L.node = r.rlo;
+        } else if (klo) L.node = r.rlo;
+        else if (khi) L.node = r.rhi;
+        else list_next(L, st, a);
         return;
     }
     walk_leaf_boxes(a.sc, ref, [&](const float *bx, uint32_t ord) { offer(L, a, ord, bx, bx + 3); });
-    next_node(L, st, a);
+    list_next(L, st, a);
 }
 
-// k_overlap_count (FILL = false) and k_overlap_fill (FILL = true): the protocol of the k_within pair — lengths at offsets[qi] and one 64-bit
-// atomic per wave for the total; the fill writes list qi from offsets[qi] on, in the order of the walk.
-template <bool FILL>
-__device__ __forceinline__ void overlap_body(const OLaunch &a, uint32_t *ring) {
-    const Stack<uint32_t> st(ring, a.spill, a.cap, a.status);
-    const OLane<FILL> L = walk_queries<OLane<FILL>>(st, a);
-    if (!FILL) {
-        unsigned long long sum = L.sum;
-        for (int d = 32; d > 0; d >>= 1) sum += __shfl_down(sum, d, 64);
-        if ((threadIdx.x & 63u) == 0 && sum) atomicAdd(&a.status->total, sum);
-    }
-}
-
+// k_overlap_count (FILL = false) and k_overlap_fill (FILL = true).
 __global__ void __launch_bounds__(BLOCK) k_overlap_count(OLaunch a) {
     __shared__ uint32_t ring[RING * BLOCK];
-    overlap_body<false>(a, ring);
+    list_body<OLane<false>>(a, ring);
 }
 
 __global__ void __launch_bounds__(BLOCK) k_overlap_fill(OLaunch a) {
     __shared__ uint32_t ring[RING * BLOCK];
-    overlap_body<true>(a, ring);
+    list_body<OLane<true>>(a, ring);
 }
 
 /// Whose the last count was: the three kinds of lists share the handle's bookkeeping of it, and a fill of another kind is refused.
 enum { COUNT_WITHIN = 1, COUNT_OVERLAP = 2, COUNT_PAIRS = 3 };
 const char *const COUNT_NAMES[4] = {"nothing", "neighbour lists (within)", "box queries (overlap)", "pairs"};
+
+/// The walk kernels as slots of the handle's occupancy figures (a fill's is its count's + 1), and the timed steps (likewise).
+enum { K_NEAREST, K_WCOUNT, K_WFILL, K_OCOUNT, K_OFILL, K_KNN, KERNELS = K_KNN + KNN_SIZES };
+enum { T_CHECK, T_WALK, T_KWALK, T_WCOUNT, T_WFILL, T_OCOUNT, T_OFILL, TIMERS };
+constexpr int TIMER_STEPS[TIMERS] = {1, 1, 1, 2, 1, 2, 1};  ///< a count is its kernel and the scan
+
+/// What tells the two kinds of list launch apart on the host.
+template <class A>
+struct ListKernels {
+    void (*count)(A);
+    void (*fill)(A);
+    uint32_t slot;  ///< of the count
+    int timer;      ///< of the count
+};
+const ListKernels<WLaunch> WITHIN_KERNELS = {k_within_count, k_within_fill, K_WCOUNT, T_WCOUNT};
+const ListKernels<OLaunch> OVERLAP_KERNELS = {k_overlap_count, k_overlap_fill, K_OCOUNT, T_OCOUNT};
+const ListKernels<WLaunch> &kernels_of(const WLaunch &) { return WITHIN_KERNELS; }
+const ListKernels<OLaunch> &kernels_of(const OLaunch &) { return OVERLAP_KERNELS; }
 
 }  // namespace
 
@@ -968,33 +985,22 @@ struct gpuart_nearest : ImageHandle {
     gpuart_hip_scene scene{};    ///< what the handle is bound to
     bool bound = false;
     DeviceBuffer spill;          ///< the lanes' global stack columns
-    DeviceBuffer staging;        ///< run_host: points and hits of a chunk
-    uint32_t device_blocks = 0;  ///< of k_nearest: what the device holds at once
-    uint32_t max_blocks = 0;     ///< the most a launch takes: device_blocks, or what gpuart_nearest_set_limits says
+    DeviceBuffer staging;        ///< the runs through host memory: a chunk's queries and what comes back
+    uint32_t blocks[KERNELS] = {};  ///< per kernel: the workgroups the device holds at once
+    uint32_t max_blocks = 0;     ///< the most a launch takes: k_nearest's figure, or what gpuart_nearest_set_limits says
     size_t spill_budget = SPILL_BUDGET, host_chunk = HOST_CHUNK;  ///< likewise
     uint32_t last_blocks = 0, last_launches = 0;  ///< the last launch's grid; the launches of the last run
-    StepTimer check, walk;       ///< one step each
-    bool walked = false;
-    // the neighbour lists
+    StepTimer timers[TIMERS];
+    bool recorded[TIMERS] = {};  ///< the timer's events have been recorded
+    // the lists: the three kinds share the bookkeeping of "the last count", which therefore says whose it is
     DeviceBuffer scan_temp;      ///< rocPRIM's
-    uint32_t within_blocks[2] = {0, 0};  ///< of k_within_count and k_within_fill: what the device holds at once
     uint64_t max_items = GPUART_NEAREST_WITHIN_MAX_ITEMS;
-    StepTimer wcount, wfill;     ///< count and scan; fill
-    bool counted = false, filled = false;  ///< the timers' events have been recorded
     bool fill_pending = false;   ///< a fill was launched since the last finish looked at the mismatch word
     bool total_read = false;     ///< last_total is the last count's
     uint64_t last_total = 0;
     size_t counted_n = 0;        ///< the queries of the last count
-    std::vector<uint32_t> host_offsets;  ///< within_host: a chunk's
-    // the k nearest
-    uint32_t knn_blocks[KNN_SIZES] = {0, 0, 0, 0};  ///< of k_knn per capacity: what the device holds at once
-    StepTimer kwalk;
-    bool kwalked = false;
-    // box overlap: box queries and pairs. They share the lists' bookkeeping of "the last count" above, which therefore says whose it is
-    uint32_t overlap_blocks[2] = {0, 0};  ///< of k_overlap_count and k_overlap_fill: what the device holds at once
     int counted_kind = 0;        ///< COUNT_WITHIN, COUNT_OVERLAP or COUNT_PAIRS: what the last count counted (0: nothing yet)
-    StepTimer ocount, ofill;     ///< count and scan; fill
-    bool ocounted = false, ofilled = false;
+    std::vector<uint32_t> host_offsets;  ///< a staged chunk's
 };
 
 namespace {
@@ -1039,22 +1045,16 @@ int check_queries(gpuart_nearest *h, const gpuart_hip_scene *s, size_t n, const 
     return check_user_sphere(us);
 }
 
-int check_run(gpuart_nearest *h, const gpuart_hip_scene *s, const void *points, size_t n, const float us[4], const void *hits, size_t align) {
+/// What the runs that answer with records check: of the k nearest, k and n * k first; of the closest points (k = 0) one record a query.
+int check_hits(gpuart_nearest *h, const gpuart_hip_scene *s, const void *points, size_t n, size_t k, bool knn, const float us[4], const void *hits, size_t align) {
     if (int rc = check_queries(h, s, n, us)) return rc;
+    if (knn) {
+        if (k < 1 || k > GPUART_NEAREST_KNN_MAX) return fail(GPUART_HIP_ERR_ARG, "nearest: k is " + std::to_string(k) + ": not in 1 .. " + std::to_string(GPUART_NEAREST_KNN_MAX));
+        if (n * k > GPUART_HIP_MAX_RAYS) return fail(GPUART_HIP_ERR_ARG, "nearest: too many records: " + std::to_string(n) + " queries of k = " + std::to_string(k));
+    }
     if (n && (!points || !hits)) return fail(GPUART_HIP_ERR_ARG, "nearest: points or hits is NULL");
     if (misaligned({points, hits}, align)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned pointer (points and hits need " + std::to_string(align) + " bytes)");
-    if (n && overlaps(points, n * 16, hits, n * 32)) return fail(GPUART_HIP_ERR_ARG, "nearest: hits overlaps points");
-    return 0;
-}
-
-/// What the runs of the k nearest check: k and n * k before what check_run checks of a run whose hits hold n * k records.
-int check_knn(gpuart_nearest *h, const gpuart_hip_scene *s, const void *points, size_t n, size_t k, const float us[4], const void *hits, size_t align) {
-    if (int rc = check_queries(h, s, n, us)) return rc;
-    if (k < 1 || k > GPUART_NEAREST_KNN_MAX) return fail(GPUART_HIP_ERR_ARG, "nearest: k is " + std::to_string(k) + ": not in 1 .. " + std::to_string(GPUART_NEAREST_KNN_MAX));
-    if (n * k > GPUART_HIP_MAX_RAYS) return fail(GPUART_HIP_ERR_ARG, "nearest: too many records: " + std::to_string(n) + " queries of k = " + std::to_string(k));
-    if (n && (!points || !hits)) return fail(GPUART_HIP_ERR_ARG, "nearest: points or hits is NULL");
-    if (misaligned({points, hits}, align)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned pointer (points and hits need " + std::to_string(align) + " bytes)");
-    if (n && overlaps(points, n * 16, hits, n * k * 32)) return fail(GPUART_HIP_ERR_ARG, "nearest: hits overlaps points");
+    if (n && overlaps(points, n * 16, hits, n * (knn ? k : 1) * 32)) return fail(GPUART_HIP_ERR_ARG, "nearest: hits overlaps points");
     return 0;
 }
 
@@ -1066,19 +1066,46 @@ int check_within(gpuart_nearest *h, const gpuart_hip_scene *s, const void *point
     return 0;
 }
 
+int check_margin(float margin) {
+    return nr::overlap_margin_ok(margin) ? 0 : fail(GPUART_HIP_ERR_ARG, "nearest: the margin is NaN, infinite or negative");
+}
+
+/// What the box queries check before a launch: the handle and its binding, n, the user sphere, the margin, the two arrays.
+int check_overlap(gpuart_nearest *h, const gpuart_hip_scene *s, const void *boxes, size_t n, float margin, const float us[4], const void *offsets) {
+    if (int rc = check_queries(h, s, n, us)) return rc;
+    if (int rc = check_margin(margin)) return rc;
+    if (n && (!boxes || !offsets)) return fail(GPUART_HIP_ERR_ARG, "nearest: boxes or offsets is NULL");
+    if (misaligned({boxes, offsets}, 4)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned pointer (boxes and offsets need 4 bytes)");
+    if (n && overlaps(boxes, n * 24, offsets, (n + 1) * 4)) return fail(GPUART_HIP_ERR_ARG, "nearest: offsets overlaps boxes");
+    return 0;
+}
+
+/// What the pairs check: the handle and its binding, the margin, the offsets.
+int check_pairs(gpuart_nearest *h, const gpuart_hip_scene *s, float margin, const void *offsets) {
+    if (int rc = check_queries(h, s, s ? s->n_prims : 0, nullptr)) return rc;
+    if (int rc = check_margin(margin)) return rc;
+    if (!offsets) return fail(GPUART_HIP_ERR_ARG, "nearest: offsets is NULL");
+    if (misaligned({offsets}, 4)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned pointer (offsets needs 4 bytes)");
+    return 0;
+}
+
+int check_items_aligned(const void *items, size_t align) {
+    return misaligned({items}, align) ? fail(GPUART_HIP_ERR_ARG, "nearest: misaligned pointer (items needs " + std::to_string(align) + " bytes)") : 0;
+}
+
 int too_many(uint64_t total, uint64_t cap) {
     return fail(GPUART_HIP_ERR_ARG, "nearest: the lists hold " + std::to_string(total) + " items, more than the " + std::to_string(cap) + " a result may hold");
 }
 
 /// What every launch over n queries in device memory begins with: the grid — the blocks the spill budget pays for (a column entry is what
-/// the kernel's stack holds: the lists' 4 bytes are half of k_nearest's), the blocks the work fills, and `most` —, the lanes' stack columns,
-/// the arguments every kernel has (its queries are the caller's to set), and the cursor at zero.
+/// the kernel's stack holds: the lists' 4 bytes are half of k_nearest's), the blocks the work fills, and the kernel's `slot` under the
+/// handle's limit —, the lanes' stack columns, the arguments every kernel has (its queries are the caller's to set), and the cursor at zero.
 template <class A>
-int prepare(gpuart_nearest *h, const gpuart_hip_scene *s, uint32_t n, const float us[4], uint32_t most, A &a, uint32_t &grid) {
+int prepare(gpuart_nearest *h, const gpuart_hip_scene *s, uint32_t n, const float us[4], uint32_t slot, A &a, uint32_t &grid) {
     const size_t levels = (size_t)s->max_depth + 2, block_bytes = levels * sizeof(*a.spill) * BLOCK;
     const size_t by_budget = std::max<size_t>(1, h->spill_budget / block_bytes);
     const size_t by_work = ((size_t)n + (size_t)CHUNK * WAVES - 1) / ((size_t)CHUNK * WAVES);
-    grid = (uint32_t)std::min({by_budget, by_work, (size_t)most});
+    grid = (uint32_t)std::min({by_budget, by_work, (size_t)std::min(h->max_blocks, h->blocks[slot])});
     if (int rc = ensure(h->stream, h->spill, block_bytes * grid)) return rc;
     a.sc = view_of(s);
     a.n = n;
@@ -1092,98 +1119,16 @@ int prepare(gpuart_nearest *h, const gpuart_hip_scene *s, uint32_t n, const floa
     return 0;
 }
 
-/// One launch of k_nearest.
-int launch(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, uint32_t n, const float us[4], gpuart_nearest_hit *hits) {
-    Launch a{};
-    uint32_t grid;
-    if (int rc = prepare(h, s, n, us, h->max_blocks, a, grid)) return rc;
-    a.points = (const float4 *)points;
-    a.hits = hits;
-    h->walk.start(h->stream);
-    HIP_TRY(h->walk.mark());
-    k_nearest<<<grid, BLOCK, 0, h->stream>>>(a);
+/// One kernel on the handle's stream between the first two marks of `timer`, and the bookkeeping of a launch.
+template <class A>
+int launch_timed(gpuart_nearest *h, int timer, void (*kernel)(A), const A &a, uint32_t grid) {
+    StepTimer &t = h->timers[timer];
+    t.start(h->stream);
+    HIP_TRY(t.mark());
+    kernel<<<grid, BLOCK, 0, h->stream>>>(a);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(h->walk.mark());
-    h->walked = true;
-    h->last_blocks = grid;
-    h->last_launches++;
-    return 0;
-}
-
-/// One launch of k_knn, of the capacity that holds k.
-int launch_knn(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, uint32_t n, uint32_t k, const float us[4], gpuart_nearest_hit *hits) {
-    KnnLaunch a{};
-    uint32_t grid;
-    const uint32_t size = knn_capacity(k);
-    if (int rc = prepare(h, s, n, us, std::min(h->max_blocks, h->knn_blocks[size]), a, grid)) return rc;
-    a.points = (const float4 *)points;
-    a.k = k;
-    a.hits = hits;
-    h->kwalk.start(h->stream);
-    HIP_TRY(h->kwalk.mark());
-    KNN_KERNELS[size]<<<grid, BLOCK, 0, h->stream>>>(a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(h->kwalk.mark());
-    h->kwalked = true;
-    h->last_blocks = grid;
-    h->last_launches++;
-    return 0;
-}
-
-/// The count of n queries in device memory into offsets[0 .. n], scanned in place; the total stays in the status.
-int launch_count(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, uint32_t n, const float us[4], uint32_t *offsets) {
-    WLaunch a{};
-    uint32_t grid;
-    if (int rc = prepare(h, s, n, us, std::min(h->max_blocks, h->within_blocks[0]), a, grid)) return rc;
-    a.points = (const float4 *)points;
-    a.offsets = offsets;
-    size_t scan_bytes = 0;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, offsets, offsets, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), h->stream));
-    if (int rc = ensure(h->stream, h->scan_temp, scan_bytes + 16)) return rc;
-    HIP_TRY(hipMemsetAsync(&h->status->total, 0, sizeof(unsigned long long), h->stream));
-    HIP_TRY(hipMemsetAsync(offsets + n, 0, sizeof(uint32_t), h->stream));
-    h->wcount.start(h->stream);
-    HIP_TRY(h->wcount.mark());
-    k_within_count<<<grid, BLOCK, 0, h->stream>>>(a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(h->wcount.mark());
-    HIP_TRY(rocprim::exclusive_scan(h->scan_temp.mem, scan_bytes, offsets, offsets, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), h->stream));
-    HIP_TRY(h->wcount.mark());
-    h->counted = true;
-    h->total_read = false;
-    h->counted_n = n;
-    h->counted_kind = COUNT_WITHIN;
-    h->last_blocks = grid;
-    h->last_launches++;
-    return 0;
-}
-
-/// Waits for the stream and reads the last count's total.
-int read_total(gpuart_nearest *h) {
-    if (h->total_read) return 0;
-    unsigned long long t = 0;
-    HIP_TRY(hipMemcpyAsync(&t, &h->status->total, 8, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    h->last_total = t;
-    h->total_read = true;
-    return 0;
-}
-
-int launch_fill(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, uint32_t n, const float us[4], const uint32_t *offsets,
-                gpuart_nearest_hit *items, uint32_t capacity) {
-    WLaunch a{};
-    uint32_t grid;
-    if (int rc = prepare(h, s, n, us, std::min(h->max_blocks, h->within_blocks[1]), a, grid)) return rc;
-    a.points = (const float4 *)points;
-    a.offsets = const_cast<uint32_t *>(offsets);
-    a.items = items;
-    a.capacity = capacity;
-    h->wfill.start(h->stream);
-    HIP_TRY(h->wfill.mark());
-    k_within_fill<<<grid, BLOCK, 0, h->stream>>>(a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(h->wfill.mark());
-    h->filled = h->fill_pending = true;
+    HIP_TRY(t.mark());
+    h->recorded[timer] = true;
     h->last_blocks = grid;
     h->last_launches++;
     return 0;
@@ -1211,12 +1156,179 @@ int read_mismatch(gpuart_nearest *h) {
     return read_flag(h, &h->status->mismatch, "nearest: the offsets are not this query set's count: the results are void");
 }
 
-/// The two NEAREST_COUNT counters of the status from `first` on, read once the stream has finished, and zeroed.
-int read_counts(gpuart_nearest *h, unsigned long long Status::*first, uint64_t out[2]) {
+/// One launch of k_nearest (k = 0) or of the k_knn whose capacity holds k.
+int launch(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, uint32_t n, uint32_t k, const float us[4], gpuart_nearest_hit *hits) {
+    auto go = [&](auto a, void (*kernel)(decltype(a)), uint32_t slot, int timer) {
+        uint32_t grid;
+        if (int rc = prepare(h, s, n, us, slot, a, grid)) return rc;
+        a.points = (const float4 *)points;
+        a.hits = hits;
+        return launch_timed(h, timer, kernel, a, grid);
+    };
+    if (!k) return go(Launch{}, k_nearest, K_NEAREST, T_WALK);
+    KnnLaunch a{};
+    a.k = k;
+    const uint32_t size = knn_capacity(k);
+    return go(a, KNN_KERNELS[size], K_KNN + size, T_KWALK);
+}
+
+/// A run of `launch` through host memory, staged in chunks: a chunk's records are no more than host_chunk, so of the k nearest it is
+/// host_chunk / k queries, at least one. The staging buffer: a chunk's points, then its records.
+int run_staged(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, size_t n, size_t k, const float us[4], gpuart_nearest_hit *hits) {
+    const size_t per = k ? k : 1, chunk = std::min(n, std::max<size_t>(1, h->host_chunk / per));
+    h->last_launches = 0;
+    if (int rc = ensure(h->stream, h->staging, chunk * (16 + 32 * per))) return rc;
+    float *dpoints = (float *)h->staging.mem;
+    gpuart_nearest_hit *dhits = (gpuart_nearest_hit *)((char *)h->staging.mem + chunk * 16);
+    for (size_t at = 0; at < n; at += chunk) {
+        const size_t m = std::min(chunk, n - at);
+        HIP_TRY(hipMemcpyAsync(dpoints, points + 4 * at, m * 16, hipMemcpyHostToDevice, h->stream));
+        if (int rc = launch(h, s, dpoints, (uint32_t)m, (uint32_t)k, us, dhits)) return rc;
+        HIP_TRY(hipMemcpyAsync(hits + at * per, dhits, m * per * 32, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    return read_overflow(h);
+}
+
+// ---- the lists: what the neighbour lists, the box queries and the pairs share on the host ------------------------------------------------
+/// A launch struct with its queries set: the points of the neighbour lists; n boxes at `boxes` (device), or — pairs — the scene's own
+/// boxes from the ordinal `first` on.
+WLaunch within_launch(const void *points) {
+    WLaunch a{};
+    a.points = (const float4 *)points;
+    return a;
+}
+OLaunch overlap_launch(const void *boxes, float margin, bool pairs = false, size_t first = 0) {
+    OLaunch a{};
+    a.boxes = (const float *)boxes;
+    a.self0 = (uint32_t)first;
+    a.pairs = pairs ? 1u : 0u;
+    a.margin = margin;
+    return a;
+}
+OLaunch pairs_launch(const gpuart_hip_scene *s, float margin, size_t first = 0) { return overlap_launch((const float *)s->prim_boxes + 6 * first, margin, true, first); }
+
+/// The count of a's n queries into offsets[0 .. n] (device), scanned in place; the total stays in the status.
+template <class A>
+int launch_count(gpuart_nearest *h, const gpuart_hip_scene *s, A a, uint32_t n, const float us[4], int kind, uint32_t *offsets) {
+    const ListKernels<A> &ks = kernels_of(a);
+    uint32_t grid;
+    if (int rc = prepare(h, s, n, us, ks.slot, a, grid)) return rc;
+    a.offsets = offsets;
+    size_t scan_bytes = 0;
+    HIP_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, offsets, offsets, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), h->stream));
+    if (int rc = ensure(h->stream, h->scan_temp, scan_bytes + 16)) return rc;
+    HIP_TRY(hipMemsetAsync(&h->status->total, 0, sizeof(unsigned long long), h->stream));
+    HIP_TRY(hipMemsetAsync(offsets + n, 0, sizeof(uint32_t), h->stream));
+    if (int rc = launch_timed(h, ks.timer, ks.count, a, grid)) return rc;
+    HIP_TRY(rocprim::exclusive_scan(h->scan_temp.mem, scan_bytes, offsets, offsets, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), h->stream));
+    HIP_TRY(h->timers[ks.timer].mark());
+    h->total_read = false;
+    h->counted_n = n;
+    h->counted_kind = kind;
+    return 0;
+}
+
+/// A count of no queries launches nothing.
+void counted_nothing(gpuart_nearest *h, int kind) {
+    h->last_total = 0;
+    h->total_read = true;
+    h->counted_n = 0;
+    h->counted_kind = kind;
+}
+
+/// The fill of a's n queries: list i into items from offsets[i] on (device), below `capacity`.
+template <class A, class Item>
+int launch_fill(gpuart_nearest *h, const gpuart_hip_scene *s, A a, uint32_t n, const float us[4], const uint32_t *offsets, Item *items, uint32_t capacity) {
+    const ListKernels<A> &ks = kernels_of(a);
+    uint32_t grid;
+    if (int rc = prepare(h, s, n, us, ks.slot + 1, a, grid)) return rc;
+    a.offsets = const_cast<uint32_t *>(offsets);
+    a.items = items;
+    a.capacity = capacity;
+    if (int rc = launch_timed(h, ks.timer + 1, ks.fill, a, grid)) return rc;
+    h->fill_pending = true;
+    return 0;
+}
+
+/// Waits for the stream and reads the last count's total.
+int read_total(gpuart_nearest *h) {
+    if (h->total_read) return 0;
+    unsigned long long t = 0;
+    HIP_TRY(hipMemcpyAsync(&t, &h->status->total, 8, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->last_total = t;
+    h->total_read = true;
+    return 0;
+}
+
+/// What a device fill of `kind` checks behind its queries: items, the last count — its n, its kind, its total against the caps and the
+/// capacity — and what items may not overlap. `items_are`: what an item is called ("records", "ordinals"), `queries_are` likewise.
+/// Returns 1 where there is nothing to fill.
+int check_fill(gpuart_nearest *h, int kind, size_t n, const void *queries, size_t query_bytes, const char *queries_are, const uint32_t *offsets, const void *items,
+               size_t item_bytes, size_t item_align, const char *items_are, size_t &capacity) {
+    if (int rc = check_items_aligned(items, item_align)) return rc;
+    if (n != h->counted_n) return fail(GPUART_HIP_ERR_ARG, "nearest: the last count was of " + std::to_string(h->counted_n) + " queries, not of " + std::to_string(n));
+    // A fill of no neighbour lists succeeds whatever the last count was of; the other two kinds look at whose it was first. The difference
+    // is the entry points' as they were written, kept as it is (tests/test_overlap.py holds the table).
+    if (!n && kind == COUNT_WITHIN) return 1;
+    if (h->counted_kind != kind)
+        return fail(GPUART_HIP_ERR_ARG, std::string("nearest: the last count was of ") + COUNT_NAMES[h->counted_kind] + ", this fill is of " + COUNT_NAMES[kind]);
+    if (!n) return 1;
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = read_total(h)) return rc;
+    if (h->last_total > h->max_items) return too_many(h->last_total, h->max_items);
+    if (capacity < h->last_total)
+        return fail(GPUART_HIP_ERR_ARG, "nearest: items has room for " + std::to_string(capacity) + " " + items_are + ", the last count's total is " + std::to_string(h->last_total));
+    if (capacity && !items) return fail(GPUART_HIP_ERR_ARG, "nearest: items is NULL");
+    capacity = std::min<size_t>(capacity, GPUART_NEAREST_WITHIN_MAX_ITEMS);
+    if (capacity && ((queries && overlaps(items, capacity * item_bytes, queries, query_bytes)) || overlaps(items, capacity * item_bytes, offsets, (n + 1) * 4)))
+        return fail(GPUART_HIP_ERR_ARG, std::string("nearest: items overlaps ") + queries_are + " or offsets");
+    h->last_launches = 0;
+    return 0;
+}
+
+/// What a _fill_host entry checks of the caller's offsets (host) and items behind its queries. Returns 1 where there is nothing to fill.
+int check_host_fill(gpuart_nearest *h, size_t n, const uint32_t *offsets, const void *items, const char *items_are, size_t capacity) {
+    if (!offsets) return fail(GPUART_HIP_ERR_ARG, "nearest: offsets is NULL");
+    if (int rc = check_items_aligned(items, 4)) return rc;
+    if (offsets[0] != 0) return fail(GPUART_HIP_ERR_ARG, "nearest: offsets[0] is not 0");
+    for (size_t i = 0; i < n; i++)
+        if (offsets[i + 1] < offsets[i]) return fail(GPUART_HIP_ERR_ARG, "nearest: the offsets decrease at query " + std::to_string(i));
+    const uint64_t total = offsets[n];
+    if (total > h->max_items) return too_many(total, h->max_items);
+    if (capacity < total)
+        return fail(GPUART_HIP_ERR_ARG, "nearest: items has room for " + std::to_string(capacity) + " " + items_are + ", the offsets end at " + std::to_string(total));
+    if (total && !items) return fail(GPUART_HIP_ERR_ARG, "nearest: items is NULL");
+    h->last_launches = 0;
+    if (!n) return 1;
+    HIP_TRY(hipSetDevice(h->device));
+    return 0;
+}
+
+/// What the entries that read something back open with: the handle, where to put it (`name` for the text), the device, a finished stream.
+int open_read(gpuart_nearest *h, const void *out, const char *name) {
     if (int rc = check_handle(LIB, h)) return rc;
-    if (!out) return fail(GPUART_HIP_ERR_ARG, "nearest: out is NULL");
+    if (!out) return fail(GPUART_HIP_ERR_ARG, std::string("nearest: ") + name + " is NULL");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+/// gpuart_nearest_*_step_ms: the steps of the timers first .. first + count - 1, read where they have been recorded.
+int step_ms(gpuart_nearest *h, int first, int count, double *ms) {
+    if (int rc = open_read(h, ms, "ms")) return rc;
+    for (int t = first; t < first + count; t++) {
+        if (h->recorded[t])  // (bind reads its own: T_CHECK is never marked as recorded)
+            if (int rc = h->timers[t].read()) return rc;
+        for (int k = 0; k < TIMER_STEPS[t]; k++) *ms++ = h->timers[t].ms[k];
+    }
+    return 0;
+}
+
+/// The two NEAREST_COUNT counters of the status from `first` on, read once the stream has finished, and zeroed.
+int read_counts(gpuart_nearest *h, unsigned long long Status::*first, uint64_t out[2]) {
+    if (int rc = open_read(h, out, "out")) return rc;
     unsigned long long c[2];
     HIP_TRY(hipMemcpy(c, &(h->status->*first), 16, hipMemcpyDeviceToHost));
     out[0] = c[0]; out[1] = c[1];
@@ -1224,177 +1336,32 @@ int read_counts(gpuart_nearest *h, unsigned long long Status::*first, uint64_t o
     return 0;
 }
 
-/// The fill pass in host memory, staged in chunks of host_chunk queries: a chunk's points and its offsets, made local to the chunk, go
-/// to the staging buffer (points, then items, then offsets), its items come back to items + offsets[chunk]. offsets: ascending, n + 1.
-/// (The three staged paths — gpuart_nearest_run_host, the count of gpuart_nearest_within_host, this — each write their chunk loop out:
-/// they share two lines, the chunk's start and size, and differ in the staging layout, in what goes up and in what comes back.)
-int fill_staged(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, size_t n, const float us[4], const uint32_t *offsets,
-                gpuart_nearest_hit *items) {
+/// Both passes of a list run into host memory, staged in chunks of host_chunk queries. The count: a chunk's queries go up (query_bytes each;
+/// 0 for the pairs, whose launch takes its first ordinal), its lengths come back and are rebased by the running total. The fill: the
+/// offsets, made local to the chunk, go up with the queries and the chunk's items come back to items + offsets[chunk]. fill_only: the
+/// offsets (ascending, n + 1) are the caller's. make(at, queries): the launch struct of the chunk that begins at query `at`, its queries
+/// in device memory. The staging buffer: a chunk's queries, then its offsets, then — on a 16-byte boundary — its items.
+template <class Item, class Make>
+int lists_staged(gpuart_nearest *h, const gpuart_hip_scene *s, const void *queries, size_t query_bytes, size_t n, const float us[4], int kind, uint32_t *offsets,
+                 Item *items, size_t capacity, uint64_t *total, bool fill_only, Make make) {
     const size_t chunk = std::min(n, h->host_chunk);
     h->host_offsets.resize(chunk + 1);
     uint32_t *local = h->host_offsets.data();
-    for (size_t at = 0; at < n; at += chunk) {
-        const size_t m = std::min(chunk, n - at);
-        const size_t room = offsets[at + m] - offsets[at];
-        if (int rc = ensure(h->stream, h->staging, chunk * 16 + room * 32 + (chunk + 1) * 4)) return rc;
-        float *dpoints = (float *)h->staging.mem;
-        gpuart_nearest_hit *ditems = (gpuart_nearest_hit *)((char *)h->staging.mem + chunk * 16);
-        uint32_t *doffsets = (uint32_t *)((char *)h->staging.mem + chunk * 16 + room * 32);
-        for (size_t k = 0; k <= m; k++) local[k] = offsets[at + k] - offsets[at];
-        HIP_TRY(hipMemcpyAsync(dpoints, points + 4 * at, m * 16, hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(doffsets, local, (m + 1) * 4, hipMemcpyHostToDevice, h->stream));
-        if (int rc = launch_fill(h, s, dpoints, (uint32_t)m, us, doffsets, ditems, (uint32_t)room)) return rc;
-        if (room) HIP_TRY(hipMemcpyAsync(items + offsets[at], ditems, room * 32, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-    }
-    h->fill_pending = false;
-    if (int rc = read_overflow(h)) return rc;
-    return read_mismatch(h);
-}
-
-// ---- box overlap -----------------------------------------------------------------------------------------------------------------------
-int tree_order(const float *recs, size_t n_recs, uint32_t root_ref, const float *prims, size_t n_prims, std::vector<uint32_t> &order);
-
-/// A fill of `kind` wants the last count to be of its own kind.
-int check_kind(const gpuart_nearest *h, int kind) {
-    if (h->counted_kind == kind) return 0;
-    return fail(GPUART_HIP_ERR_ARG, std::string("nearest: the last count was of ") + COUNT_NAMES[h->counted_kind] + ", this fill is of " + COUNT_NAMES[kind]);
-}
-
-int check_margin(float margin) {
-    return nr::overlap_margin_ok(margin) ? 0 : fail(GPUART_HIP_ERR_ARG, "nearest: the margin is NaN, infinite or negative");
-}
-
-/// The queries of an overlap launch: n boxes at `boxes` (device), or — pairs — the scene's own boxes of the ordinals first .. first + n - 1.
-struct OQueries {
-    const float *boxes;
-    uint32_t n, first;
-    bool pairs;
-    float margin;
-    const float *us;
-};
-
-OQueries pair_queries(const gpuart_hip_scene *s, size_t first, size_t n, float margin) {
-    return OQueries{(const float *)s->prim_boxes + 6 * first, (uint32_t)n, (uint32_t)first, true, margin, nullptr};
-}
-
-template <class A>
-void set_queries(A &a, const OQueries &q) {
-    a.boxes = q.boxes;
-    a.self0 = q.first;
-    a.pairs = q.pairs ? 1u : 0u;
-    a.margin = q.margin;
-}
-
-/// The count of an overlap launch into offsets[0 .. n] (device), scanned in place; the total stays in the status.
-int launch_ocount(gpuart_nearest *h, const gpuart_hip_scene *s, const OQueries &q, uint32_t *offsets) {
-    OLaunch a{};
-    uint32_t grid;
-    if (int rc = prepare(h, s, q.n, q.us, std::min(h->max_blocks, h->overlap_blocks[0]), a, grid)) return rc;
-    set_queries(a, q);
-    a.offsets = offsets;
-    size_t scan_bytes = 0;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, offsets, offsets, 0u, (size_t)q.n + 1, rocprim::plus<uint32_t>(), h->stream));
-    if (int rc = ensure(h->stream, h->scan_temp, scan_bytes + 16)) return rc;
-    HIP_TRY(hipMemsetAsync(&h->status->total, 0, sizeof(unsigned long long), h->stream));
-    HIP_TRY(hipMemsetAsync(offsets + q.n, 0, sizeof(uint32_t), h->stream));
-    h->ocount.start(h->stream);
-    HIP_TRY(h->ocount.mark());
-    k_overlap_count<<<grid, BLOCK, 0, h->stream>>>(a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(h->ocount.mark());
-    HIP_TRY(rocprim::exclusive_scan(h->scan_temp.mem, scan_bytes, offsets, offsets, 0u, (size_t)q.n + 1, rocprim::plus<uint32_t>(), h->stream));
-    HIP_TRY(h->ocount.mark());
-    h->ocounted = true;
-    h->total_read = false;
-    h->counted_n = q.n;
-    h->counted_kind = q.pairs ? COUNT_PAIRS : COUNT_OVERLAP;
-    h->last_blocks = grid;
-    h->last_launches++;
-    return 0;
-}
-
-int launch_ofill(gpuart_nearest *h, const gpuart_hip_scene *s, const OQueries &q, const uint32_t *offsets, int32_t *items, uint32_t capacity) {
-    OLaunch a{};
-    uint32_t grid;
-    if (int rc = prepare(h, s, q.n, q.us, std::min(h->max_blocks, h->overlap_blocks[1]), a, grid)) return rc;
-    set_queries(a, q);
-    a.offsets = const_cast<uint32_t *>(offsets);
-    a.items = items;
-    a.capacity = capacity;
-    h->ofill.start(h->stream);
-    HIP_TRY(h->ofill.mark());
-    k_overlap_fill<<<grid, BLOCK, 0, h->stream>>>(a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(h->ofill.mark());
-    h->ofilled = h->fill_pending = true;
-    h->last_blocks = grid;
-    h->last_launches++;
-    return 0;
-}
-
-/// What the box queries check before a launch: the handle and its binding, n, the user sphere, the margin, the two arrays.
-int check_overlap(gpuart_nearest *h, const gpuart_hip_scene *s, const void *boxes, size_t n, float margin, const float us[4], const void *offsets) {
-    if (int rc = check_queries(h, s, n, us)) return rc;
-    if (int rc = check_margin(margin)) return rc;
-    if (n && (!boxes || !offsets)) return fail(GPUART_HIP_ERR_ARG, "nearest: boxes or offsets is NULL");
-    if (misaligned({boxes, offsets}, 4)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned pointer (boxes and offsets need 4 bytes)");
-    if (n && overlaps(boxes, n * 24, offsets, (n + 1) * 4)) return fail(GPUART_HIP_ERR_ARG, "nearest: offsets overlaps boxes");
-    return 0;
-}
-
-/// What the pairs check: the handle and its binding, the margin, the offsets.
-int check_pairs(gpuart_nearest *h, const gpuart_hip_scene *s, float margin, const void *offsets) {
-    if (int rc = check_queries(h, s, s ? s->n_prims : 0, nullptr)) return rc;
-    if (int rc = check_margin(margin)) return rc;
-    if (!offsets) return fail(GPUART_HIP_ERR_ARG, "nearest: offsets is NULL");
-    if (misaligned({offsets}, 4)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned pointer (offsets needs 4 bytes)");
-    return 0;
-}
-
-/// What a device fill checks behind its queries: the last count (its n, its kind, its total against the caps and the capacity) and items.
-/// Returns 1 where there is nothing to fill.
-int check_ofill(gpuart_nearest *h, int kind, size_t n, const void *queries, size_t query_bytes, const uint32_t *offsets, const int32_t *items, size_t &capacity) {
-    if (misaligned({items}, 4)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned pointer (items needs 4 bytes)");
-    if (n != h->counted_n) return fail(GPUART_HIP_ERR_ARG, "nearest: the last count was of " + std::to_string(h->counted_n) + " queries, not of " + std::to_string(n));
-    if (int rc = check_kind(h, kind)) return rc;
-    if (!n) return 1;
-    HIP_TRY(hipSetDevice(h->device));
-    if (int rc = read_total(h)) return rc;
-    if (h->last_total > h->max_items) return too_many(h->last_total, h->max_items);
-    if (capacity < h->last_total)
-        return fail(GPUART_HIP_ERR_ARG, "nearest: items has room for " + std::to_string(capacity) + " ordinals, the last count's total is " + std::to_string(h->last_total));
-    if (capacity && !items) return fail(GPUART_HIP_ERR_ARG, "nearest: items is NULL");
-    capacity = std::min<size_t>(capacity, GPUART_NEAREST_WITHIN_MAX_ITEMS);
-    if (capacity && ((queries && overlaps(items, capacity * 4, queries, query_bytes)) || overlaps(items, capacity * 4, offsets, (n + 1) * 4)))
-        return fail(GPUART_HIP_ERR_ARG, "nearest: items overlaps boxes or offsets");
-    return 0;
-}
-
-/// Both passes of an overlap run into host memory, staged in chunks of host_chunk queries: for box queries a chunk's boxes go up, for pairs
-/// (boxes == NULL) nothing does — a launch takes its first ordinal. Offsets are rebased on the host. fill_only: offsets are the caller's.
-/// The staging buffer: a chunk's boxes, then its offsets, then its items.
-int overlap_staged(gpuart_nearest *h, const gpuart_hip_scene *s, const float *boxes, size_t n, float margin, const float us[4], uint32_t *offsets,
-                   int32_t *items, size_t capacity, uint64_t *total, bool fill_only) {
-    const bool pairs = !boxes;
-    const size_t chunk = std::min(n, h->host_chunk);
-    h->host_offsets.resize(chunk + 1);
-    uint32_t *local = h->host_offsets.data();
-    const size_t head = chunk * 24 + (chunk + 1) * 4;
-    auto queries = [&](size_t at, size_t m) {
-        return pairs ? pair_queries(s, at, m, margin) : OQueries{(const float *)h->staging.mem, (uint32_t)m, 0u, false, margin, us};
+    const size_t head = (chunk * query_bytes + (chunk + 1) * 4 + 15) / 16 * 16;
+    auto doffsets = [&] { return (uint32_t *)((char *)h->staging.mem + chunk * query_bytes); };
+    auto send_queries = [&](size_t at, size_t m) {
+        return query_bytes ? hipMemcpyAsync(h->staging.mem, (const char *)queries + at * query_bytes, m * query_bytes, hipMemcpyHostToDevice, h->stream) : hipSuccess;
     };
     if (!fill_only) {
         if (int rc = ensure(h->stream, h->staging, head)) return rc;
         uint64_t base = 0;
         for (size_t at = 0; at < n; at += chunk) {
             const size_t m = std::min(chunk, n - at);
-            uint32_t *doffsets = (uint32_t *)((char *)h->staging.mem + chunk * 24);
-            if (!pairs) HIP_TRY(hipMemcpyAsync(h->staging.mem, boxes + 6 * at, m * 24, hipMemcpyHostToDevice, h->stream));
-            if (int rc = launch_ocount(h, s, queries(at, m), doffsets)) return rc;
-            HIP_TRY(hipMemcpyAsync(local, doffsets, m * 4, hipMemcpyDeviceToHost, h->stream));
+            HIP_TRY(send_queries(at, m));
+            if (int rc = launch_count(h, s, make(at, h->staging.mem), (uint32_t)m, us, kind, doffsets())) return rc;
+            HIP_TRY(hipMemcpyAsync(local, doffsets(), m * 4, hipMemcpyDeviceToHost, h->stream));
             if (int rc = read_total(h)) return rc;
-            for (size_t k = 0; k < m; k++) offsets[at + k] = (uint32_t)(base + local[k]);
+            for (size_t k = 0; k < m; k++) offsets[at + k] = (uint32_t)(base + local[k]);  // (rebased: the chunk's lists follow the earlier chunks')
             base += h->last_total;
         }
         offsets[n] = (uint32_t)base;
@@ -1408,19 +1375,52 @@ int overlap_staged(gpuart_nearest *h, const gpuart_hip_scene *s, const float *bo
     for (size_t at = 0; at < n; at += chunk) {
         const size_t m = std::min(chunk, n - at);
         const size_t room = offsets[at + m] - offsets[at];
-        if (int rc = ensure(h->stream, h->staging, head + room * 4)) return rc;
-        uint32_t *doffsets = (uint32_t *)((char *)h->staging.mem + chunk * 24);
-        int32_t *ditems = (int32_t *)((char *)h->staging.mem + head);
+        if (int rc = ensure(h->stream, h->staging, head + room * sizeof(Item))) return rc;
+        Item *ditems = (Item *)((char *)h->staging.mem + head);
         for (size_t k = 0; k <= m; k++) local[k] = offsets[at + k] - offsets[at];
-        if (!pairs) HIP_TRY(hipMemcpyAsync(h->staging.mem, boxes + 6 * at, m * 24, hipMemcpyHostToDevice, h->stream));
-        HIP_TRY(hipMemcpyAsync(doffsets, local, (m + 1) * 4, hipMemcpyHostToDevice, h->stream));
-        if (int rc = launch_ofill(h, s, queries(at, m), doffsets, ditems, (uint32_t)room)) return rc;
-        if (room) HIP_TRY(hipMemcpyAsync(items + offsets[at], ditems, room * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(send_queries(at, m));
+        HIP_TRY(hipMemcpyAsync(doffsets(), local, (m + 1) * 4, hipMemcpyHostToDevice, h->stream));
+        if (int rc = launch_fill(h, s, make(at, h->staging.mem), (uint32_t)m, us, doffsets(), ditems, (uint32_t)room)) return rc;
+        if (room) HIP_TRY(hipMemcpyAsync(items + offsets[at], ditems, room * sizeof(Item), hipMemcpyDeviceToHost, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
     }
     h->fill_pending = false;
     if (int rc = read_overflow(h)) return rc;
     return read_mismatch(h);
+}
+
+/// What the three _host entries do behind their checks: an empty result, then the staged run.
+template <class Item, class Make>
+int lists_host(gpuart_nearest *h, const gpuart_hip_scene *s, const void *queries, size_t query_bytes, size_t n, const float us[4], int kind, uint32_t *offsets,
+               Item *items, size_t capacity, uint64_t *total, Make make) {
+    if (int rc = check_items_aligned(items, 4)) return rc;
+    offsets[0] = 0;
+    *total = 0;
+    h->last_launches = 0;
+    if (!n) return 0;
+    HIP_TRY(hipSetDevice(h->device));
+    return lists_staged(h, s, queries, query_bytes, n, us, kind, offsets, items, capacity, total, false, make);
+}
+
+// ---- the definitions on host arrays -------------------------------------------------------------------------------------------------------
+int tree_order(const float *recs, size_t n_recs, uint32_t root_ref, const float *prims, size_t n_prims, std::vector<uint32_t> &order);
+
+/// The two passes of a definition: visit(i, emit) calls emit(item) for every item of list i, in the contract's order. Offsets and the total
+/// from a first pass, the cap, and — with room for them — the items from a second.
+template <class Item, class Visit>
+int two_passes(size_t n, Visit visit, uint32_t *offsets, Item *items, size_t capacity, uint64_t *total) {
+    uint64_t sum = 0;
+    for (size_t i = 0; i < n; i++) {
+        offsets[i] = (uint32_t)sum;
+        visit(i, [&](const Item &) { sum++; });
+    }
+    offsets[n] = (uint32_t)sum;
+    *total = sum;
+    if (sum > GPUART_NEAREST_WITHIN_MAX_ITEMS) return too_many(sum, GPUART_NEAREST_WITHIN_MAX_ITEMS);
+    if (!items || capacity < sum) return 0;
+    size_t at = 0;
+    for (size_t i = 0; i < n; i++) visit(i, [&](const Item &item) { items[at++] = item; });
+    return 0;
 }
 
 /// The definition on host arrays, for box queries (boxes != NULL) and pairs: every primitive tested in the tree's order.
@@ -1446,18 +1446,7 @@ int overlap_brute(const float *recs, size_t n_recs, uint32_t root_ref, const flo
             if (nr::overlap_test(qlo, qhi, b, b + 3) && (!pairs || nr::pairs_keep((uint32_t)i, k))) emit((int32_t)k);
         }
     };
-    uint64_t sum = 0;
-    for (size_t i = 0; i < n; i++) {
-        offsets[i] = (uint32_t)sum;
-        visit(i, [&](int32_t) { sum++; });
-    }
-    offsets[n] = (uint32_t)sum;
-    *total = sum;
-    if (sum > GPUART_NEAREST_WITHIN_MAX_ITEMS) return too_many(sum, GPUART_NEAREST_WITHIN_MAX_ITEMS);
-    if (!items || capacity < sum) return 0;
-    size_t at = 0;
-    for (size_t i = 0; i < n; i++) visit(i, [&](int32_t k) { items[at++] = k; });
-    return 0;
+    return two_passes(n, visit, offsets, items, capacity, total);
 }
 
 /// The ordinals in the order of the unpruned depth-first walk from root_ref, lower child first; 0, or why the records are refused.
@@ -1501,46 +1490,32 @@ int gpuart_nearest_create(int device, gpuart_nearest **out) {
         hipError_t e = hipMalloc((void **)&h->status, sizeof(Status));
         if (e == hipSuccess) e = hipMalloc((void **)&h->cursor, sizeof(uint32_t));
         if (e == hipSuccess) e = hipMemset(h->status, 0, sizeof(Status));
-        if (e == hipSuccess) e = h->check.create(1);
-        if (e == hipSuccess) e = h->walk.create(1);
-        if (e == hipSuccess) e = h->wcount.create(2);
-        if (e == hipSuccess) e = h->wfill.create(1);
-        if (e == hipSuccess) e = h->kwalk.create(1);
-        if (e == hipSuccess) e = h->ocount.create(2);
-        if (e == hipSuccess) e = h->ofill.create(1);
+        for (int t = 0; t < TIMERS && e == hipSuccess; t++) e = h->timers[t].create(TIMER_STEPS[t]);
         return e;
     });
     if (rc) return rc;
     gpuart_nearest *h = *out;
-    int per_cu = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_nearest, BLOCK, 0) != hipSuccess || per_cu < 1) per_cu = 1;
+    int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < 1) cus = 1;
-    h->device_blocks = h->max_blocks = (uint32_t)per_cu * (uint32_t)cus;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_within_count, BLOCK, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-    h->within_blocks[0] = (uint32_t)per_cu * (uint32_t)cus;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_within_fill, BLOCK, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-    h->within_blocks[1] = (uint32_t)per_cu * (uint32_t)cus;
-    for (uint32_t k = 0; k < KNN_SIZES; k++) {  // (the lists' LDS sets it: 2 KiB per entry of the capacity beside the ring's 16 KiB)
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, KNN_KERNELS[k], BLOCK, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-        h->knn_blocks[k] = (uint32_t)per_cu * (uint32_t)cus;
-    }
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_overlap_count, BLOCK, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-    h->overlap_blocks[0] = (uint32_t)per_cu * (uint32_t)cus;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_overlap_fill, BLOCK, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-    h->overlap_blocks[1] = (uint32_t)per_cu * (uint32_t)cus;
+    auto held = [&](uint32_t slot, auto kernel) {  // the workgroups of `kernel` the device holds at once
+        int per_cu = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, BLOCK, 0) != hipSuccess || per_cu < 1) per_cu = 1;
+        h->blocks[slot] = (uint32_t)per_cu * (uint32_t)cus;
+    };
+    held(K_NEAREST, k_nearest);
+    held(K_WCOUNT, k_within_count);
+    held(K_WFILL, k_within_fill);
+    held(K_OCOUNT, k_overlap_count);
+    held(K_OFILL, k_overlap_fill);
+    for (uint32_t k = 0; k < KNN_SIZES; k++) held(K_KNN + k, KNN_KERNELS[k]);  // (the lists' LDS sets it: 2 KiB per entry of the capacity beside the ring's 16 KiB)
+    h->max_blocks = h->blocks[K_NEAREST];
     return 0;
 }
 
 int gpuart_nearest_destroy(gpuart_nearest *h) {
     if (!h) return 0;
     destroy_handle(h, {h->status, h->cursor, h->spill.mem, h->staging.mem, h->scan_temp.mem});
-    h->check.destroy();
-    h->walk.destroy();
-    h->wcount.destroy();
-    h->wfill.destroy();
-    h->kwalk.destroy();
-    h->ocount.destroy();
-    h->ofill.destroy();
+    for (StepTimer &t : h->timers) t.destroy();
     delete h;
     return 0;
 }
@@ -1570,15 +1545,16 @@ int gpuart_nearest_bind(gpuart_nearest *h, const gpuart_hip_scene *s) {
     if (!tree_rule::root_ref_ok(s->root_ref, s->n_recs, s->n_prims)) return fail(GPUART_HIP_ERR_ARG, "nearest: the root ref is neither record 0 nor a leaf inside the primitives");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipMemsetAsync(h->status, 0, sizeof(Status), h->stream));
-    h->check.start(h->stream);
-    HIP_TRY(h->check.mark());
+    StepTimer &check = h->timers[T_CHECK];
+    check.start(h->stream);
+    HIP_TRY(check.mark());
     k_nr_nesting<<<blocks(s->n_recs + 1), 256, 0, h->stream>>>(view_of(s), h->status);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(h->check.mark());
+    HIP_TRY(check.mark());
     uint32_t refused = 0;
     HIP_TRY(hipMemcpyAsync(&refused, &h->status->refused, 4, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    if (int rc = h->check.read()) return rc;
+    if (int rc = check.read()) return rc;
     if (refused) {
         const char *const why[4] = {"", "a box it holds is not finite and ordered", "a ref or a leaf's count it holds is out of range, or an interior child is not behind its parent",
                                     "a child's boxes (or a leaf's primitive boxes) do not lie inside the box it holds for that child"};
@@ -1592,30 +1568,18 @@ int gpuart_nearest_bind(gpuart_nearest *h, const gpuart_hip_scene *s) {
 }
 
 int gpuart_nearest_run(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, size_t n, const float us[4], gpuart_nearest_hit *hits) {
-    if (int rc = check_run(h, s, points, n, us, hits, 16)) return rc;
+    if (int rc = check_hits(h, s, points, n, 0, false, us, hits, 16)) return rc;
     if (!n) return 0;
     HIP_TRY(hipSetDevice(h->device));
     h->last_launches = 0;
-    return launch(h, s, points, (uint32_t)n, us, hits);
+    return launch(h, s, points, (uint32_t)n, 0, us, hits);
 }
 
 int gpuart_nearest_run_host(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, size_t n, const float us[4], gpuart_nearest_hit *hits) {
-    if (int rc = check_run(h, s, points, n, us, hits, 4)) return rc;
+    if (int rc = check_hits(h, s, points, n, 0, false, us, hits, 4)) return rc;
     if (!n) return 0;
     HIP_TRY(hipSetDevice(h->device));
-    const size_t chunk = std::min(n, h->host_chunk);
-    h->last_launches = 0;
-    if (int rc = ensure(h->stream, h->staging, chunk * (16 + 32))) return rc;
-    float *dpoints = (float *)h->staging.mem;
-    gpuart_nearest_hit *dhits = (gpuart_nearest_hit *)((char *)h->staging.mem + chunk * 16);
-    for (size_t at = 0; at < n; at += chunk) {
-        const size_t m = std::min(chunk, n - at);
-        HIP_TRY(hipMemcpyAsync(dpoints, points + 4 * at, m * 16, hipMemcpyHostToDevice, h->stream));
-        if (int rc = launch(h, s, dpoints, (uint32_t)m, us, dhits)) return rc;
-        HIP_TRY(hipMemcpyAsync(hits + at, dhits, m * 32, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-    }
-    return read_overflow(h);
+    return run_staged(h, s, points, n, 0, us, hits);
 }
 
 int gpuart_nearest_brute_host(gpuart_nearest *, const float *, size_t, const float *prims, const float *prim_boxes, size_t n_prims, const float *points, size_t n,
@@ -1649,21 +1613,11 @@ int gpuart_nearest_brute_host(gpuart_nearest *, const float *, size_t, const flo
     return 0;
 }
 
-int gpuart_nearest_step_ms(gpuart_nearest *h, double ms[2]) {
-    if (int rc = check_handle(LIB, h)) return rc;
-    if (!ms) return fail(GPUART_HIP_ERR_ARG, "nearest: ms is NULL");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->walked)
-        if (int rc = h->walk.read()) return rc;
-    ms[0] = h->check.ms[0];
-    ms[1] = h->walk.ms[0];
-    return 0;
-}
+int gpuart_nearest_step_ms(gpuart_nearest *h, double ms[2]) { return step_ms(h, T_CHECK, 2, ms); }
 
 int gpuart_nearest_set_limits(gpuart_nearest *h, uint32_t max_blocks, size_t spill_bytes, size_t host_chunk) {
     if (int rc = check_handle(LIB, h)) return rc;
-    h->max_blocks = max_blocks ? std::min(max_blocks, h->device_blocks) : h->device_blocks;
+    h->max_blocks = max_blocks ? std::min(max_blocks, h->blocks[K_NEAREST]) : h->blocks[K_NEAREST];
     h->spill_budget = spill_bytes ? spill_bytes : SPILL_BUDGET;
     h->host_chunk = host_chunk ? std::min(host_chunk, HOST_CHUNK) : HOST_CHUNK;
     return 0;
@@ -1683,14 +1637,11 @@ int gpuart_nearest_within_count(gpuart_nearest *h, const gpuart_hip_scene *s, co
     if (int rc = check_within(h, s, points, n, us, offsets, 16)) return rc;
     h->last_launches = 0;
     if (!n) {
-        h->last_total = 0;
-        h->total_read = true;
-        h->counted_n = 0;
-        h->counted_kind = COUNT_WITHIN;
+        counted_nothing(h, COUNT_WITHIN);
         return 0;
     }
     HIP_TRY(hipSetDevice(h->device));
-    return launch_count(h, s, points, (uint32_t)n, us, offsets);
+    return launch_count(h, s, within_launch(points), (uint32_t)n, us, COUNT_WITHIN, offsets);
 }
 
 int gpuart_nearest_within_total(gpuart_nearest *h, uint64_t *total) {
@@ -1705,77 +1656,23 @@ int gpuart_nearest_within_total(gpuart_nearest *h, uint64_t *total) {
 int gpuart_nearest_within_fill(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, size_t n, const float us[4], const uint32_t *offsets,
                                gpuart_nearest_hit *items, size_t capacity) {
     if (int rc = check_within(h, s, points, n, us, offsets, 16)) return rc;
-    if (misaligned({items}, 16)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned pointer (items needs 16 bytes)");
-    if (n != h->counted_n) return fail(GPUART_HIP_ERR_ARG, "nearest: the last count was of " + std::to_string(h->counted_n) + " queries, not of " + std::to_string(n));
-    if (!n) return 0;
-    if (int rc = check_kind(h, COUNT_WITHIN)) return rc;
-    HIP_TRY(hipSetDevice(h->device));
-    if (int rc = read_total(h)) return rc;
-    if (h->last_total > h->max_items) return too_many(h->last_total, h->max_items);
-    if (capacity < h->last_total)
-        return fail(GPUART_HIP_ERR_ARG, "nearest: items has room for " + std::to_string(capacity) + " records, the last count's total is " + std::to_string(h->last_total));
-    if (capacity && !items) return fail(GPUART_HIP_ERR_ARG, "nearest: items is NULL");
-    capacity = std::min<size_t>(capacity, GPUART_NEAREST_WITHIN_MAX_ITEMS);
-    if (capacity && (overlaps(items, capacity * 32, points, n * 16) || overlaps(items, capacity * 32, offsets, (n + 1) * 4)))
-        return fail(GPUART_HIP_ERR_ARG, "nearest: items overlaps points or offsets");
-    h->last_launches = 0;
-    return launch_fill(h, s, points, (uint32_t)n, us, offsets, items, (uint32_t)capacity);
+    if (int rc = check_fill(h, COUNT_WITHIN, n, points, n * 16, "points", offsets, items, 32, 16, "records", capacity)) return rc < 0 ? rc : 0;
+    return launch_fill(h, s, within_launch(points), (uint32_t)n, us, offsets, items, (uint32_t)capacity);
 }
 
 int gpuart_nearest_within_host(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, size_t n, const float us[4], uint32_t *offsets,
                                gpuart_nearest_hit *items, size_t capacity, uint64_t *total) {
     if (int rc = check_within(h, s, points, n, us, offsets, 4)) return rc;
     if (!offsets || !total) return fail(GPUART_HIP_ERR_ARG, "nearest: offsets or total is NULL");
-    if (misaligned({items}, 4)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned pointer (items needs 4 bytes)");
-    offsets[0] = 0;
-    *total = 0;
-    h->last_launches = 0;
-    if (!n) return 0;
-    HIP_TRY(hipSetDevice(h->device));
-    const size_t chunk = std::min(n, h->host_chunk);
-    // the staging buffer: a chunk's points, then its items, then its offsets
-    if (int rc = ensure(h->stream, h->staging, chunk * 16 + (chunk + 1) * 4)) return rc;
-    h->host_offsets.resize(chunk + 1);
-    uint32_t *local = h->host_offsets.data();
-    uint64_t base = 0;
-    for (size_t at = 0; at < n; at += chunk) {
-        const size_t m = std::min(chunk, n - at);
-        float *dpoints = (float *)h->staging.mem;
-        uint32_t *doffsets = (uint32_t *)((char *)h->staging.mem + chunk * 16);
-        HIP_TRY(hipMemcpyAsync(dpoints, points + 4 * at, m * 16, hipMemcpyHostToDevice, h->stream));
-        if (int rc = launch_count(h, s, dpoints, (uint32_t)m, us, doffsets)) return rc;
-        HIP_TRY(hipMemcpyAsync(local, doffsets, m * 4, hipMemcpyDeviceToHost, h->stream));
-        if (int rc = read_total(h)) return rc;
-        for (size_t k = 0; k < m; k++) offsets[at + k] = (uint32_t)(base + local[k]);  // (rebased: the chunk's lists follow the earlier chunks')
-        base += h->last_total;
-    }
-    offsets[n] = (uint32_t)base;
-    *total = base;
-    h->last_total = base;
-    h->counted_n = n;
-    if (int rc = read_overflow(h)) return rc;
-    if (base > h->max_items) return too_many(base, h->max_items);
-    if (!items || capacity < base) return 0;
-    return fill_staged(h, s, points, n, us, offsets, items);
+    return lists_host(h, s, points, 16, n, us, COUNT_WITHIN, offsets, items, capacity, total, [](size_t, const void *staged) { return within_launch(staged); });
 }
 
 int gpuart_nearest_within_fill_host(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, size_t n, const float us[4], const uint32_t *offsets,
                                     gpuart_nearest_hit *items, size_t capacity) {
     if (int rc = check_within(h, s, points, n, us, offsets, 4)) return rc;
-    if (!offsets) return fail(GPUART_HIP_ERR_ARG, "nearest: offsets is NULL");
-    if (misaligned({items}, 4)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned pointer (items needs 4 bytes)");
-    if (offsets[0] != 0) return fail(GPUART_HIP_ERR_ARG, "nearest: offsets[0] is not 0");
-    for (size_t i = 0; i < n; i++)
-        if (offsets[i + 1] < offsets[i]) return fail(GPUART_HIP_ERR_ARG, "nearest: the offsets decrease at query " + std::to_string(i));
-    const uint64_t total = offsets[n];
-    if (total > h->max_items) return too_many(total, h->max_items);
-    if (capacity < total)
-        return fail(GPUART_HIP_ERR_ARG, "nearest: items has room for " + std::to_string(capacity) + " records, the offsets end at " + std::to_string(total));
-    if (total && !items) return fail(GPUART_HIP_ERR_ARG, "nearest: items is NULL");
-    h->last_launches = 0;
-    if (!n) return 0;
-    HIP_TRY(hipSetDevice(h->device));
-    return fill_staged(h, s, points, n, us, offsets, items);
+    if (int rc = check_host_fill(h, n, offsets, items, "records", capacity)) return rc < 0 ? rc : 0;
+    return lists_staged(h, s, points, 16, n, us, COUNT_WITHIN, const_cast<uint32_t *>(offsets), items, capacity, nullptr, true,
+                        [](size_t, const void *staged) { return within_launch(staged); });
 }
 
 int gpuart_nearest_within_brute_host(const float *recs, size_t n_recs, uint32_t root_ref, const float *prims, const float *prim_boxes, size_t n_prims,
@@ -1807,18 +1704,7 @@ int gpuart_nearest_within_brute_host(const float *recs, size_t n_recs, uint32_t 
             if (nr::within_accept(d2, r2)) emit(gpuart_nearest_hit{sqrtf(d2), {q[0], q[1], q[2]}, d2, (int32_t)k, (int32_t)(w & 3u), 0});
         }
     };
-    uint64_t sum = 0;
-    for (size_t i = 0; i < n; i++) {
-        offsets[i] = (uint32_t)sum;
-        visit(i, [&](const gpuart_nearest_hit &) { sum++; });
-    }
-    offsets[n] = (uint32_t)sum;
-    *total = sum;
-    if (sum > GPUART_NEAREST_WITHIN_MAX_ITEMS) return too_many(sum, GPUART_NEAREST_WITHIN_MAX_ITEMS);
-    if (!items || capacity < sum) return 0;
-    size_t at = 0;
-    for (size_t i = 0; i < n; i++) visit(i, [&](const gpuart_nearest_hit &r) { items[at++] = r; });
-    return 0;
+    return two_passes(n, visit, offsets, items, capacity, total);
 }
 
 int gpuart_nearest_within_set_max_items(gpuart_nearest *h, uint64_t max_items) {
@@ -1827,50 +1713,24 @@ int gpuart_nearest_within_set_max_items(gpuart_nearest *h, uint64_t max_items) {
     return 0;
 }
 
-int gpuart_nearest_within_step_ms(gpuart_nearest *h, double ms[3]) {
-    if (int rc = check_handle(LIB, h)) return rc;
-    if (!ms) return fail(GPUART_HIP_ERR_ARG, "nearest: ms is NULL");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->counted)
-        if (int rc = h->wcount.read()) return rc;
-    if (h->filled)
-        if (int rc = h->wfill.read()) return rc;
-    ms[0] = h->wcount.ms[0];
-    ms[1] = h->wcount.ms[1];
-    ms[2] = h->wfill.ms[0];
-    return 0;
-}
+int gpuart_nearest_within_step_ms(gpuart_nearest *h, double ms[3]) { return step_ms(h, T_WCOUNT, 2, ms); }
 
 int gpuart_nearest_within_counts(gpuart_nearest *h, uint64_t out[2]) { return read_counts(h, &Status::w_box_steps, out); }
 
 // ---- the k nearest ----------------------------------------------------------------------------------------------------------------------
 int gpuart_nearest_knn_run(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, size_t n, size_t k, const float us[4], gpuart_nearest_hit *hits) {
-    if (int rc = check_knn(h, s, points, n, k, us, hits, 16)) return rc;
+    if (int rc = check_hits(h, s, points, n, k, true, us, hits, 16)) return rc;
     if (!n) return 0;
     HIP_TRY(hipSetDevice(h->device));
     h->last_launches = 0;
-    return launch_knn(h, s, points, (uint32_t)n, (uint32_t)k, us, hits);
+    return launch(h, s, points, (uint32_t)n, (uint32_t)k, us, hits);
 }
 
 int gpuart_nearest_knn_run_host(gpuart_nearest *h, const gpuart_hip_scene *s, const float *points, size_t n, size_t k, const float us[4], gpuart_nearest_hit *hits) {
-    if (int rc = check_knn(h, s, points, n, k, us, hits, 4)) return rc;
+    if (int rc = check_hits(h, s, points, n, k, true, us, hits, 4)) return rc;
     if (!n) return 0;
     HIP_TRY(hipSetDevice(h->device));
-    // a chunk's records are no more than a chunk of gpuart_nearest_run_host holds: host_chunk / k queries, at least one
-    const size_t chunk = std::min(n, std::max<size_t>(1, h->host_chunk / k));
-    h->last_launches = 0;
-    if (int rc = ensure(h->stream, h->staging, chunk * (16 + 32 * k))) return rc;
-    float *dpoints = (float *)h->staging.mem;
-    gpuart_nearest_hit *dhits = (gpuart_nearest_hit *)((char *)h->staging.mem + chunk * 16);
-    for (size_t at = 0; at < n; at += chunk) {
-        const size_t m = std::min(chunk, n - at);
-        HIP_TRY(hipMemcpyAsync(dpoints, points + 4 * at, m * 16, hipMemcpyHostToDevice, h->stream));
-        if (int rc = launch_knn(h, s, dpoints, (uint32_t)m, (uint32_t)k, us, dhits)) return rc;
-        HIP_TRY(hipMemcpyAsync(hits + at * k, dhits, m * k * 32, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-    }
-    return read_overflow(h);
+    return run_staged(h, s, points, n, k, us, hits);
 }
 
 int gpuart_nearest_knn_brute_host(gpuart_nearest *, const float *, size_t, const float *prims, const float *prim_boxes, size_t n_prims, const float *points, size_t n,
@@ -1910,16 +1770,7 @@ int gpuart_nearest_knn_brute_host(gpuart_nearest *, const float *, size_t, const
     return 0;
 }
 
-int gpuart_nearest_knn_step_ms(gpuart_nearest *h, double ms[1]) {
-    if (int rc = check_handle(LIB, h)) return rc;
-    if (!ms) return fail(GPUART_HIP_ERR_ARG, "nearest: ms is NULL");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->kwalked)
-        if (int rc = h->kwalk.read()) return rc;
-    ms[0] = h->kwalk.ms[0];
-    return 0;
-}
+int gpuart_nearest_knn_step_ms(gpuart_nearest *h, double ms[1]) { return step_ms(h, T_KWALK, 1, ms); }
 
 int gpuart_nearest_knn_counts(gpuart_nearest *h, uint64_t out[2]) { return read_counts(h, &Status::k_box_steps, out); }
 
@@ -1928,14 +1779,11 @@ int gpuart_nearest_overlap_count(gpuart_nearest *h, const gpuart_hip_scene *s, c
     if (int rc = check_overlap(h, s, boxes, n, margin, us, offsets)) return rc;
     h->last_launches = 0;
     if (!n) {
-        h->last_total = 0;
-        h->total_read = true;
-        h->counted_n = 0;
-        h->counted_kind = COUNT_OVERLAP;
+        counted_nothing(h, COUNT_OVERLAP);
         return 0;
     }
     HIP_TRY(hipSetDevice(h->device));
-    return launch_ocount(h, s, OQueries{boxes, (uint32_t)n, 0u, false, margin, us}, offsets);
+    return launch_count(h, s, overlap_launch(boxes, margin), (uint32_t)n, us, COUNT_OVERLAP, offsets);
 }
 
 int gpuart_nearest_overlap_total(gpuart_nearest *h, uint64_t *total) { return gpuart_nearest_within_total(h, total); }
@@ -1943,41 +1791,23 @@ int gpuart_nearest_overlap_total(gpuart_nearest *h, uint64_t *total) { return gp
 int gpuart_nearest_overlap_fill(gpuart_nearest *h, const gpuart_hip_scene *s, const float *boxes, size_t n, float margin, const float us[4], const uint32_t *offsets,
                                 int32_t *items, size_t capacity) {
     if (int rc = check_overlap(h, s, boxes, n, margin, us, offsets)) return rc;
-    if (int rc = check_ofill(h, COUNT_OVERLAP, n, boxes, n * 24, offsets, items, capacity)) return rc < 0 ? rc : 0;
-    h->last_launches = 0;
-    return launch_ofill(h, s, OQueries{boxes, (uint32_t)n, 0u, false, margin, us}, offsets, items, (uint32_t)capacity);
+    if (int rc = check_fill(h, COUNT_OVERLAP, n, boxes, n * 24, "boxes", offsets, items, 4, 4, "ordinals", capacity)) return rc < 0 ? rc : 0;
+    return launch_fill(h, s, overlap_launch(boxes, margin), (uint32_t)n, us, offsets, items, (uint32_t)capacity);
 }
 
 int gpuart_nearest_overlap_host(gpuart_nearest *h, const gpuart_hip_scene *s, const float *boxes, size_t n, float margin, const float us[4], uint32_t *offsets,
                                 int32_t *items, size_t capacity, uint64_t *total) {
     if (int rc = check_overlap(h, s, boxes, n, margin, us, offsets)) return rc;
     if (!offsets || !total) return fail(GPUART_HIP_ERR_ARG, "nearest: offsets or total is NULL");
-    if (misaligned({items}, 4)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned pointer (items needs 4 bytes)");
-    offsets[0] = 0;
-    *total = 0;
-    h->last_launches = 0;
-    if (!n) return 0;
-    HIP_TRY(hipSetDevice(h->device));
-    return overlap_staged(h, s, boxes, n, margin, us, offsets, items, capacity, total, false);
+    return lists_host(h, s, boxes, 24, n, us, COUNT_OVERLAP, offsets, items, capacity, total, [&](size_t, const void *staged) { return overlap_launch(staged, margin); });
 }
 
 int gpuart_nearest_overlap_fill_host(gpuart_nearest *h, const gpuart_hip_scene *s, const float *boxes, size_t n, float margin, const float us[4],
                                      const uint32_t *offsets, int32_t *items, size_t capacity) {
     if (int rc = check_overlap(h, s, boxes, n, margin, us, offsets)) return rc;
-    if (!offsets) return fail(GPUART_HIP_ERR_ARG, "nearest: offsets is NULL");
-    if (misaligned({items}, 4)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned pointer (items needs 4 bytes)");
-    if (offsets[0] != 0) return fail(GPUART_HIP_ERR_ARG, "nearest: offsets[0] is not 0");
-    for (size_t i = 0; i < n; i++)
-        if (offsets[i + 1] < offsets[i]) return fail(GPUART_HIP_ERR_ARG, "nearest: the offsets decrease at query " + std::to_string(i));
-    const uint64_t total = offsets[n];
-    if (total > h->max_items) return too_many(total, h->max_items);
-    if (capacity < total)
-        return fail(GPUART_HIP_ERR_ARG, "nearest: items has room for " + std::to_string(capacity) + " ordinals, the offsets end at " + std::to_string(total));
-    if (total && !items) return fail(GPUART_HIP_ERR_ARG, "nearest: items is NULL");
-    h->last_launches = 0;
-    if (!n) return 0;
-    HIP_TRY(hipSetDevice(h->device));
-    return overlap_staged(h, s, boxes, n, margin, us, const_cast<uint32_t *>(offsets), items, capacity, nullptr, true);
+    if (int rc = check_host_fill(h, n, offsets, items, "ordinals", capacity)) return rc < 0 ? rc : 0;
+    return lists_staged(h, s, boxes, 24, n, us, COUNT_OVERLAP, const_cast<uint32_t *>(offsets), items, capacity, nullptr, true,
+                        [&](size_t, const void *staged) { return overlap_launch(staged, margin); });
 }
 
 int gpuart_nearest_overlap_brute_host(const float *recs, size_t n_recs, uint32_t root_ref, const float *prims, const float *prim_boxes, size_t n_prims,
@@ -1991,20 +1821,7 @@ int gpuart_nearest_overlap_brute_host(const float *recs, size_t n_recs, uint32_t
     return overlap_brute(recs, n_recs, root_ref, prims, prim_boxes, n_prims, n ? boxes : none, n, margin, us, offsets, items, capacity, total);
 }
 
-int gpuart_nearest_overlap_step_ms(gpuart_nearest *h, double ms[3]) {
-    if (int rc = check_handle(LIB, h)) return rc;
-    if (!ms) return fail(GPUART_HIP_ERR_ARG, "nearest: ms is NULL");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->ocounted)
-        if (int rc = h->ocount.read()) return rc;
-    if (h->ofilled)
-        if (int rc = h->ofill.read()) return rc;
-    ms[0] = h->ocount.ms[0];
-    ms[1] = h->ocount.ms[1];
-    ms[2] = h->ofill.ms[0];
-    return 0;
-}
+int gpuart_nearest_overlap_step_ms(gpuart_nearest *h, double ms[3]) { return step_ms(h, T_OCOUNT, 2, ms); }
 
 int gpuart_nearest_overlap_counts(gpuart_nearest *h, uint64_t out[2]) { return read_counts(h, &Status::o_box_steps, out); }
 
@@ -2013,25 +1830,19 @@ int gpuart_nearest_pairs_count(gpuart_nearest *h, const gpuart_hip_scene *s, flo
     if (int rc = check_pairs(h, s, margin, offsets)) return rc;
     h->last_launches = 0;
     HIP_TRY(hipSetDevice(h->device));
-    return launch_ocount(h, s, pair_queries(s, 0, s->n_prims, margin), offsets);
+    return launch_count(h, s, pairs_launch(s, margin), (uint32_t)s->n_prims, nullptr, COUNT_PAIRS, offsets);
 }
 
 int gpuart_nearest_pairs_fill(gpuart_nearest *h, const gpuart_hip_scene *s, float margin, const uint32_t *offsets, int32_t *items, size_t capacity) {
     if (int rc = check_pairs(h, s, margin, offsets)) return rc;
-    if (int rc = check_ofill(h, COUNT_PAIRS, s->n_prims, nullptr, 0, offsets, items, capacity)) return rc < 0 ? rc : 0;
-    h->last_launches = 0;
-    return launch_ofill(h, s, pair_queries(s, 0, s->n_prims, margin), offsets, items, (uint32_t)capacity);
+    if (int rc = check_fill(h, COUNT_PAIRS, s->n_prims, nullptr, 0, "boxes", offsets, items, 4, 4, "ordinals", capacity)) return rc < 0 ? rc : 0;
+    return launch_fill(h, s, pairs_launch(s, margin), (uint32_t)s->n_prims, nullptr, offsets, items, (uint32_t)capacity);
 }
 
 int gpuart_nearest_pairs_host(gpuart_nearest *h, const gpuart_hip_scene *s, float margin, uint32_t *offsets, int32_t *items, size_t capacity, uint64_t *total) {
     if (int rc = check_pairs(h, s, margin, offsets)) return rc;
     if (!total) return fail(GPUART_HIP_ERR_ARG, "nearest: total is NULL");
-    if (misaligned({items}, 4)) return fail(GPUART_HIP_ERR_ARG, "nearest: misaligned pointer (items needs 4 bytes)");
-    offsets[0] = 0;
-    *total = 0;
-    h->last_launches = 0;
-    HIP_TRY(hipSetDevice(h->device));
-    return overlap_staged(h, s, nullptr, s->n_prims, margin, nullptr, offsets, items, capacity, total, false);
+    return lists_host(h, s, nullptr, 0, s->n_prims, nullptr, COUNT_PAIRS, offsets, items, capacity, total, [&](size_t first, const void *) { return pairs_launch(s, margin, first); });
 }
 
 int gpuart_nearest_pairs_brute_host(const float *recs, size_t n_recs, uint32_t root_ref, const float *prims, const float *prim_boxes, size_t n_prims, float margin,

@@ -597,6 +597,119 @@ def test_the_capacity_is_never_exceeded_and_wrong_offsets_are_reported(B, be):
     check(be, queries, margin, "after the mismatch", US, device=True)
 
 
+COUNTS = (("within", 0), ("within", 3), ("overlap", 0), ("overlap", 3), ("pairs", 7))
+FILLS = (("within_fill", 0), ("within_fill", 3), ("overlap_fill", 0), ("overlap_fill", 3), ("pairs_fill", 7), ("within_fill_host", 0), ("within_fill_host", 3),
+         ("overlap_fill_host", 0), ("overlap_fill_host", 3))
+KIND = "nearest: the last count was of %s, this fill is of %s"
+WITHIN, OVERLAP, PAIRS = "neighbour lists (within)", "box queries (overlap)", "pairs"
+NOT_OF = "nearest: the last count was of %d queries, not of %d"
+# (count, its n) -> per fill of FILLS: (return code, the last error where it failed, (blocks, launches) of the last launch where it did not),
+# as a run of the library before the list protocol was stated once gave them.
+FILL_TABLE = {
+    ("within", 0): (
+        (0, "", (0, 0)), (-1, NOT_OF % (0, 3), None),
+        (-1, KIND % (WITHIN, OVERLAP), None), (-1, NOT_OF % (0, 3), None), (-1, NOT_OF % (0, 7), None),
+        (0, "", (0, 0)), (0, "", (1, 1)), (0, "", (1, 0)), (0, "", (1, 1))),
+    ("within", 3): (
+        (-1, NOT_OF % (3, 0), None), (0, "", (1, 1)),
+        (-1, NOT_OF % (3, 0), None), (-1, KIND % (WITHIN, OVERLAP), None), (-1, NOT_OF % (3, 7), None),
+        (0, "", (1, 0)), (0, "", (1, 1)), (0, "", (1, 0)), (0, "", (1, 1))),
+    ("overlap", 0): (
+        # a within fill of no queries returns before it looks at whose the last count was; a box-query fill looks first (the next table's row)
+        (0, "", (1, 0)), (-1, NOT_OF % (0, 3), None),
+        (0, "", (1, 0)), (-1, NOT_OF % (0, 3), None), (-1, NOT_OF % (0, 7), None),
+        (0, "", (1, 0)), (0, "", (1, 1)), (0, "", (1, 0)), (0, "", (1, 1))),
+    ("overlap", 3): (
+        (-1, NOT_OF % (3, 0), None), (-1, KIND % (OVERLAP, WITHIN), None),
+        (-1, NOT_OF % (3, 0), None), (0, "", (1, 1)), (-1, NOT_OF % (3, 7), None),
+        (0, "", (1, 0)), (0, "", (1, 1)), (0, "", (1, 0)), (0, "", (1, 1))),
+    ("pairs", 7): (
+        (-1, NOT_OF % (7, 0), None), (-1, NOT_OF % (7, 3), None),
+        (-1, NOT_OF % (7, 0), None), (-1, NOT_OF % (7, 3), None), (0, "", (1, 1)),
+        (0, "", (1, 0)), (0, "", (1, 1)), (0, "", (1, 0)), (0, "", (1, 1))),
+}
+
+
+def fill_rows(B, be):
+    """Every fill of FILLS after every count of COUNTS on the seven primitives of "mixed7": {count: its row of FILL_TABLE}. The device fills
+    get the offsets the count left, the two _fill_host entries the restatement's; every items array has room."""
+    import torch
+    from tests.util import to_device
+    N = B.nearest_lib()
+    upload_scene(be, "mixed7")
+    queries, margin = scene_queries(be, 3, seed=4, spread=False)
+    queries = np.array(queries)
+    points = np.concatenate([queries[:, :3], np.full((3, 1), margin, F)], 1).astype(F)
+    scene = be.scene_device()
+    assert int(scene.n_prims) == 7
+    h = be._nearest_handle(scene)
+    tq, tp = to_device(queries), to_device(points)
+    off = torch.zeros(8, dtype=torch.int32, device="cuda:0")
+    hits = torch.zeros((256, 8), dtype=torch.float32, device="cuda:0")
+    items = torch.zeros(256, dtype=torch.int32, device="cuda:0")
+    host_off = {("within", 3): np.array(WR.brute(*device_scene(be), points, None)[0], np.uint32), ("overlap", 3): np.array(expected(be, queries, margin)[0], np.uint32),
+                ("within", 0): np.zeros(1, np.uint32), ("overlap", 0): np.zeros(1, np.uint32)}
+    host_hits, host_items = np.zeros((256, 8), F), np.zeros(256, np.int32)
+    torch.cuda.synchronize()
+    sc, m, dp = C.byref(scene), C.c_float(margin), lambda t: C.c_void_p(t.data_ptr())
+    cap = C.c_size_t(256)
+    calls = {
+        "within": lambda n: N.gpuart_nearest_within_count(h, sc, dp(tp), C.c_size_t(n), None, dp(off)),
+        "overlap": lambda n: N.gpuart_nearest_overlap_count(h, sc, dp(tq), C.c_size_t(n), m, None, dp(off)),
+        "pairs": lambda n: N.gpuart_nearest_pairs_count(h, sc, m, dp(off)),
+        "within_fill": lambda n: N.gpuart_nearest_within_fill(h, sc, dp(tp), C.c_size_t(n), None, dp(off), dp(hits), cap),
+        "overlap_fill": lambda n: N.gpuart_nearest_overlap_fill(h, sc, dp(tq), C.c_size_t(n), m, None, dp(off), dp(items), cap),
+        "pairs_fill": lambda n: N.gpuart_nearest_pairs_fill(h, sc, m, dp(off), dp(items), cap),
+        "within_fill_host": lambda n: N.gpuart_nearest_within_fill_host(h, sc, _p(points), C.c_size_t(n), None, _p(host_off["within", n]), _p(host_hits), cap),
+        "overlap_fill_host": lambda n: N.gpuart_nearest_overlap_fill_host(h, sc, _p(queries), C.c_size_t(n), m, None, _p(host_off["overlap", n]), _p(host_items), cap),
+    }
+    rows = {}
+    for count in COUNTS:
+        row = []
+        for fill, n in FILLS:
+            assert calls[count[0]](count[1]) == 0, (count, N.gpuart_nearest_last_error().decode())
+            rc = calls[fill](n)
+            row.append((rc, N.gpuart_nearest_last_error().decode() if rc else "", None if rc else last_launch(B, h)))
+            assert N.gpuart_nearest_finish(h) == 0, (count, fill, n, N.gpuart_nearest_last_error().decode())
+        rows[count] = tuple(row)
+    return rows
+
+
+@gpu
+def test_every_fill_after_every_count_answers_as_it_did(B, be):
+    """The three kinds of count (neighbour lists, box queries, pairs) times the four fills (those three, and each _fill_host), at no queries
+    and at three: the return code, the text where the call fails, the last launch's two numbers where it does not. FILL_TABLE is what the
+    library answered before the lists' protocol was stated once for the kinds, the one difference between them included: a within fill of no
+    queries succeeds whatever the last count was of, a box-query fill of none is refused after a count of another kind."""
+    rows = fill_rows(B, be)
+    for count in COUNTS:
+        for (fill, n), got, exp in zip(FILLS, rows[count], FILL_TABLE[count]):
+            assert got == exp, "after the count of %s, n = %d: %s, n = %d" % (*count, fill, n)
+
+
+@gpu
+def test_five_queries_through_host_memory_in_chunks_of_two_are_the_unchunked_bytes(B, be):
+    """host_chunk = 2: three staged launches per pass, the last one short; offsets rebased by the running total, items at the chunk's place."""
+    from oracle import oracle
+    be.upload_bvh(np.ascontiguousarray(oracle.build_bvh(NC.mixed(5, 1))[0], F))
+    assert int(be.scene_device().n_prims) == 5
+    queries, margin = scene_queries(be, 5, seed=3, spread=False)
+    queries = np.array(queries)
+    h = limits(B, be)
+    wide = 2 * OC.margins(device_scene(be)[2])[3]   # half the extent: there are pairs in more than one chunk
+    whole, whole_pairs = be.overlaps(queries, margin, user_sphere=US), be.overlapping_pairs(wide)
+    assert last_launch(B, h)[1] == 2 and whole[0][-1] > 0 and whole_pairs[0][-1] > 0
+    limits(B, be, host_chunk=2)
+    staged = be.overlaps(queries, margin, user_sphere=US)
+    assert last_launch(B, h)[1] == 3, "the fill alone: chunks of 2, 2 and 1"
+    assert_lists(staged, whole, "box queries in chunks of two")
+    assert_lists(staged, expected(be, queries, margin, US), "box queries in chunks of two, the definition")
+    staged = be.overlapping_pairs(wide)
+    assert last_launch(B, h)[1] == 2 * 3, "count and fill, chunks of 2, 2 and 1 ordinals"
+    assert_lists(staged, whole_pairs, "pairs in chunks of two")
+    assert_lists(staged, expected_pairs(be, wide), "pairs in chunks of two, the definition")
+
+
 @gpu
 def test_a_lowered_cap_refuses_the_total_and_a_total_of_zero_works(B, be):
     import torch

@@ -604,6 +604,21 @@ def test_every_input_kind_gives_the_same_bytes(B, be):
 
 
 @gpu
+def test_five_queries_through_host_memory_in_chunks_of_two_are_the_unchunked_bytes(B, be):
+    """host_chunk = 2: three staged launches per pass, the last one short; offsets rebased by the running total, items at the chunk's place."""
+    upload_scene(be, "mixed7")
+    points = scene_queries(be, 5, seed=3, spread=False)
+    h = limits(B, be)
+    whole = be.within(points, user_sphere=US)
+    assert last_launch(B, h)[1] == 1 and whole[0][-1] > 0
+    limits(B, be, host_chunk=2)
+    staged = be.within(points, user_sphere=US)
+    assert last_launch(B, h)[1] == 3, "the fill alone: chunks of 2, 2 and 1"
+    assert_lists(staged, whole, "in chunks of two")
+    assert_lists(staged, expected(be, points, US), "in chunks of two, the definition")
+
+
+@gpu
 def test_the_renderer_lists_what_the_backend_does(B):
     from gpuart_amd import synth_scenes as S
     cam = dict(S.DEFAULT_CAMERA)

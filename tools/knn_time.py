@@ -18,6 +18,8 @@ and per kind k = 1, 8 and 32. Per point (scene, kind, k):
   closest  closest_points (gpuart_nearest_run) on the same points in the same rounds — the baseline: median and range of both, Mqueries/s,
            and the ratio of the medians. At k = 1 the two outputs are compared bit for bit first
   spread   the k-nearest walk against itself: a second handle of the same library in the same rounds, the ratio of the two medians
+  parent   gpuart_amd/lib_ab/libgpuart_nearest_parent.so, if it is there — the library of another commit, copied there by hand —, in the same
+           rounds: shipped / parent time beside the spread, half the range of the parent's rounds, and its records compared with the shipped ones
   route    what a caller did before, on the first N / 4 queries, 1 warm-up round and 3 rounds: `within` at the radius whose mean list is k
            items long (bisection on the count over the first 2^16 queries; 2^12 of the far points, whose lists grow to the whole scene
            within the bracket), count + scan + fill from HIP events, then the items copied to the host and sorted there by (query, d2,
@@ -49,11 +51,14 @@ def spread(v):
     return "%.3f (%.3f .. %.3f)" % (statistics.median(v), min(v), max(v))
 
 
-class Handle:
-    """A gpuart_nearest of the shipped library."""
+PARENT = os.path.join(ROOT, "gpuart_amd", "lib_ab", "libgpuart_nearest_parent.so")
 
-    def __init__(self):
-        self.L = B.nearest_lib()
+
+class Handle:
+    """A gpuart_nearest of the shipped library, or of the library at `path`."""
+
+    def __init__(self, path=None):
+        self.L = C.CDLL(path) if path else B.nearest_lib()
         self.L.gpuart_nearest_last_error.restype = C.c_char_p
         self.h = C.c_void_p()
         self.chk(self.L.gpuart_nearest_create(C.c_int(0), C.byref(self.h)))
@@ -155,6 +160,7 @@ def main():
     side = int(round(n ** 0.5))
     cam = dict(S.BENCH_CAMERA); cam["dir"] = S.camera_dir(cam)
     first, again = Handle(), Handle()
+    parent = Handle(PARENT) if os.path.exists(PARENT) else None
     say("k nearest on %s; %d queries per kind, r = +inf, median (range) of %d rounds after 2 warm-up rounds; times in ms" % (torch.cuda.get_device_name(0), n, repeats))
     r = B.Renderer(side, side, cam)
     r.set_user_sphere(S.USER_SPHERE[:3], 0.0, 0.0)
@@ -164,21 +170,29 @@ def main():
     extent = max(b - a for a, b in zip(scene.root_min[:], scene.root_max[:]))
     say("%s: %d primitives, %d records, depth %d, root extent %.4g" % (which, scene.n_prims, scene.n_recs, scene.max_depth, extent))
     first.bind(scene); again.bind(scene)
+    if parent:
+        parent.bind(scene)
     for kind, p in workloads(be, scene, n, side).items():
         points = with_radius(p, float("inf"))
         one = torch.empty((n, 8), dtype=torch.float32, device="cuda:0")
         for k in KS:
             hits = torch.empty((n, k, 8), dtype=torch.float32, device="cuda:0")
-            ms = {"knn": [], "again": [], "closest": []}
+            ms = {"knn": [], "again": [], "closest": [], "parent": []}
+            theirs = torch.empty_like(hits) if parent else None
             for round_ in range(repeats + 2):
-                for name, t in (("knn", first.knn(scene, points, k, hits)), ("closest", first.nearest(scene, points, one)), ("again", again.knn(scene, points, k, hits))):
+                for name, t in (("knn", first.knn(scene, points, k, hits)), ("closest", first.nearest(scene, points, one)), ("again", again.knn(scene, points, k, hits))) + (
+                        (("parent", parent.knn(scene, points, k, theirs)),) if parent else ()):
                     if round_ >= 2:
                         ms[name].append(t)
             blocks = again.last_blocks()
-            med = {name: statistics.median(v) for name, v in ms.items()}
+            med = {name: statistics.median(v) for name, v in ms.items() if v}
             same = ""
+            if parent:
+                same = "; knn / parent time %.3f (half the range of the parent's rounds: %.1f %%), records %s" % (
+                    med["knn"] / med["parent"], 50 * (max(ms["parent"]) - min(ms["parent"])) / med["parent"],
+                    "bit-identical" if torch.equal(hits.view(torch.int32), theirs.view(torch.int32)) else "DIFFER")
             if k == 1:
-                same = "; k = 1 against closest_points: " + ("bit-identical" if torch.equal(hits.view(torch.int32).reshape(n, 8), one.view(torch.int32)) else "DIFFER")
+                same += "; k = 1 against closest_points: " + ("bit-identical" if torch.equal(hits.view(torch.int32).reshape(n, 8), one.view(torch.int32)) else "DIFFER")
             found = float((hits[:, :, 5].view(torch.int32) != -1).sum()) / n
             say("  %-8s k = %-2d  knn %s = %.1f Mq/s on %d workgroups | closest_points %s = %.1f Mq/s | knn / closest time %.2f | same build twice %+.1f %% | %.2f found per query%s"
                 % (kind, k, spread(ms["knn"]), n / med["knn"] / 1e3, blocks, spread(ms["closest"]), n / med["closest"] / 1e3, med["knn"] / med["closest"],
@@ -207,12 +221,14 @@ def main():
                 " = %.2f Mq/s | per query knn takes 1 / %.1f of the device passes' time and 1 / %.0f of the whole route's"
                 % (radius, radius / extent, total / m, m, spread(dev), spread(wall), m / statistics.median(wall) / 1e3, statistics.median(dev) * (n / m) / med["knn"],
                    statistics.median(wall) * (n / m) / med["knn"]))
-            del hits, rows, items, offsets
+            del hits, theirs, rows, items, offsets
     be.close()
     r.close()
     say("NOT MEASURED: mixed-type scenes at this size (both scenes are triangles only); a register-resident list for k <= 4; a k per query; user "
         "spheres; host-memory (staged) calls; a sorted insertion list in place of the heap")
     first.close(); again.close()
+    if parent:
+        parent.close()
     if out_path:
         with open(out_path, "a" if "--append" in sys.argv else "w") as f:
             f.write("\n".join(OUT) + "\n")

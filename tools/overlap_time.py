@@ -12,6 +12,9 @@ per scene — scene_d (cfg3's, 100 352 triangles) and big (dragon871k = scene_d(
   boxes    N = 2^20 box queries — cubes centred uniformly in the root box — of three sizes, found by bisection so that the mean list is about
            1, 8 and 64 items long, the same way
   plain    the persistent-lane form against the NEAREST_PLAIN build, alternating in the same rounds; offsets and items compared first
+  spread   the shipped form against itself: a second handle of the same library, alternating, the ratio of the two medians
+  parent   gpuart_amd/lib_ab/libgpuart_nearest_parent.so, if it is there — the library of another commit, copied there by hand —, in the same
+           rounds: shipped / parent time per pass beside the spread, and half the range of the parent's rounds, the other noise the run shows
   steps    box steps and box tests per query and pass, from the counting build (-DNEAREST_COUNT), not from the timed ones
   within   gpuart_nearest_within_count / _fill on the boxes' centres at the radius of the same mean list length: the only existing route
            to the same candidates, in the same run
@@ -149,9 +152,16 @@ def report(label, ms, n, total, unit):
         c, s, f = (statistics.median(x) for x in v)
         say("            %-10s count %s  scan %s  fill %s  | %.1f M%s/s and %.3f Gitems/s over the three" % (name, spread(v[0]), spread(v[1]), spread(v[2]),
                                                                                                           n / (c + s + f) / 1e3, unit, total / (c + s + f) / 1e6))
+    med = lambda name, k: statistics.median(ms[name][k])
     if "plain" in ms:
-        med = lambda name, k: statistics.median(ms[name][k])
         say("            plain / persistent time: count %.3f, fill %.3f" % (med("plain", 0) / med("persistent", 0), med("plain", 2) / med("persistent", 2)))
+    if "again" in ms:
+        line = "            same build twice: count %+.1f %%, fill %+.1f %%" % tuple(100 * (med("again", k) / med("persistent", k) - 1) for k in (0, 2))
+        if "parent" in ms:
+            line += "; persistent / parent time: count %.3f, fill %.3f (half the range of the parent's rounds: count %.1f %%, fill %.1f %%)" % (
+                tuple(med("persistent", k) / med("parent", k) for k in (0, 2))
+                + tuple(50 * (max(ms["parent"][k]) - min(ms["parent"][k])) / med("parent", k) for k in (0, 2)))
+        say(line)
 
 
 def main():
@@ -159,12 +169,12 @@ def main():
     arg = lambda name, default, kind=int: kind(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
     repeats, n, out_path = arg("--repeats", 7), arg("--queries", 1 << 20), arg("--out", "", str)
     cam = dict(S.BENCH_CAMERA); cam["dir"] = S.camera_dir(cam)
-    shipped = Handle(os.path.join(B.LIBDIR, "libgpuart_nearest.so"))
-    plain, counting = variant("plain"), variant("count")
+    shipped, again = (Handle(os.path.join(B.LIBDIR, "libgpuart_nearest.so")) for _ in range(2))
+    plain, counting, parent = variant("plain"), variant("count"), variant("parent")
     if not (plain and counting):
         say("the variants are not built (make -C gpuart_amd/csrc nearest-variants): the plain form and the step counts are NOT MEASURED")
     say("box overlap on %s; median (range) of %d rounds after 1 warm-up round, one run; times in ms" % (torch.cuda.get_device_name(0), repeats))
-    forms = [("persistent", shipped)] + ([("plain", plain)] if plain else [])
+    forms = [("persistent", shipped), ("again", again)] + ([("plain", plain)] if plain else []) + ([("parent", parent)] if parent else [])
     for which, make in (("scene_d", S.scene_d), ("big", lambda: S.scene_d(660, 660))):
         r = B.Renderer(64, 64, cam)
         r.set_user_sphere(S.USER_SPHERE[:3], 0.0, 0.0)
@@ -174,7 +184,7 @@ def main():
         P = int(scene.n_prims)
         extent = max(b - a for a, b in zip(scene.root_min[:], scene.root_max[:]))
         say("%s: %d primitives, %d records, depth %d, root extent %.4g" % (which, P, scene.n_recs, scene.max_depth, extent))
-        for h in (shipped, plain, counting):
+        for h in (shipped, again, plain, counting, parent):
             if h:
                 h.bind(scene)
         # ---- pairs
@@ -248,7 +258,7 @@ def main():
         r.close()
     say("NOT MEASURED: skipping subtrees by ordinal range in the pairs (every pair's walk is done from both sides and the half with j <= i is discarded: "
         "the records hold no per-record maximum ordinal); mixed-type scenes at this size; user spheres; the host-memory (staged) calls; a margin per query")
-    for h in (shipped, plain, counting):
+    for h in (shipped, again, plain, counting, parent):
         if h:
             h.close()
     if out_path:
